@@ -3,6 +3,10 @@
 
   python bench.py --gpus N --steps K --warmup W          (N > 1 without a launcher: the ranks are spawned here)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+  python bench.py --full ...                             (+ CPU baseline, clock, roofline, the other BASELINE configs)
+  python bench.py --dump-outputs DIR ...                 (+ what the timed launches computed, DIR/<name>.npy)
+
+A plain run sets up, warms up, times the K steps and prints the line; everything else it can measure is behind --full.
 
 A bench "step" = ONE LAUNCH of gg_batch_rollout over the whole resident batch: `--plies-per-step` (default 256)
 plies for every game - sample a uniform valid action per game on the device, apply it (capture resolution, ko, new
@@ -172,6 +176,13 @@ class HipBackend:
     def sync(self):
         self.torch.cuda.synchronize(self.device)
 
+    def snapshot(self):
+        return self.states.clone(), self.rng.clone()
+
+    def restore(self, snap):
+        self.states.copy_(snap[0])
+        self.rng.copy_(snap[1])
+
     def played(self):
         return int(self.steps_done.sum())
 
@@ -313,10 +324,13 @@ def run_rank(rank, world, backend, opts, dist=None):
     # idle gap the first ~10 launches of this shape run 5 % slow on one lease (1.96 -> 1.86 ms) and the driver's round-5 box
     # still ran 7 % slow after 0.35 s (1.98 ms timed, 1.85 ms for the same shape seconds later) - the clock ramp is per box.
     # The shader clock is sampled through amdsmi DURING this phase only (mean of the second half of the samples =
-    # `clocks.sclk_mhz`); the timed region itself runs with no sampler thread (it cost 0.2 - 0.4 % there).
+    # `clocks.sclk_mhz`); the timed region itself runs with no sampler thread (it cost 0.2 - 0.4 % there).  Only a --full run
+    # samples the clock.  The settle launches play on the live games, whose state is restored afterwards: their count depends on
+    # the machine, so the games the timed launches start from (and what --dump-outputs writes) must not.
     settle, n_s = None, 0
     if hasattr(backend, 'clock_sampler') and opts.get('clock_settle_s', 0.35) > 0:      # (the CPU test backend has neither)
-        probe = backend.clock_sampler()
+        probe = backend.clock_sampler() if opts.get('sample_clock', True) else None
+        snap = backend.snapshot() if hasattr(backend, 'snapshot') else None
         if probe is not None:
             probe.__enter__()
         t_s, windows = time.perf_counter(), []
@@ -337,6 +351,9 @@ def run_rank(rank, world, backend, opts, dist=None):
                 break
         if probe is not None:
             probe.__exit__(None, None, None)
+        if snap is not None:
+            backend.restore(snap)
+            snap = None
         settle = {'sclk_mhz': None, 'launches': n_s, 'seconds': round(time.perf_counter() - t_s, 3),
                   'first_window_launch_ms': round(windows[0], 5), 'last_window_launch_ms': round(windows[-1], 5),
                   'settled': bool(flat),
@@ -349,6 +366,8 @@ def run_rank(rank, world, backend, opts, dist=None):
                            'max': max(probe.mhz), 'power_raw': probe.record().get('power_raw')})
         elif probe is not None:
             settle['note'] = probe.record().get('note')
+        else:
+            settle['note'] = 'clock not sampled (bench.py --full samples it)'
     # (the played-steps counter is read BEFORE the warm-up - whose launches do not count - so that nothing but the fence sits
     # between the last warm-up launch and the first timed one: a reduction + a host read there is an idle gap on the device)
     before = backend.played()
@@ -421,6 +440,55 @@ def run_rank(rank, world, backend, opts, dist=None):
             'games_per_gpu': per_gpu, 'count': count, 'first': first, 'steps_played': played_all,
             'per_rank_launch_ms': per_rank_ms, 'per_rank': per_rank, 'distinct_devices': len(set(devs)) if devs[0][0] >= 0 else None,
             'comm': comm, 'clocks': clocks, 'settle_launches': n_s}
+
+
+# ------------------------------------------------------------------------------------------------ --dump-outputs
+DUMP_GAMES = 4096      # 19x19: 4 096 boards as float32 = 35.5 MB, under the 64 MB an output dump may take
+
+
+def dump_sample(total_games):
+    """Global game indices whose outputs --dump-outputs writes: every game up to DUMP_GAMES, else a fixed seeded sample."""
+    import numpy as np
+    if total_games <= DUMP_GAMES:
+        return np.arange(total_games)
+    return np.sort(np.random.default_rng(SEED).choice(total_games, DUMP_GAMES, replace=False))
+
+
+def dump_outputs(outdir, back, rank, world, opts, dist=None):
+    """What the timed launches handed back for the sampled games (global index order), written by rank 0 after the timed
+    region: states.npy (float32 [S,6,N,N], the boards), rng.npy (float64 [S,2], low / high 32 bits of each game's generator
+    state), steps_done.npy (float64 [S], the plies the timed launches counted) and game_index.npy (float64 [S]).  Every
+    rank fills the rows of its own shard; a sum all-reduce brings them together.  Returns the record for the line."""
+    import numpy as np
+    torch = back.torch
+    N = opts['size']
+    total = opts['games_per_gpu'] * world
+    first, count = shard(total, rank, world)
+    idx = dump_sample(total)
+    mine = np.flatnonzero((idx >= first) & (idx < first + count))
+    rows = torch.as_tensor(mine, device=back.device)
+    local = torch.as_tensor(idx[mine] - first, device=back.device)
+    states = torch.zeros((len(idx), 6, N, N), dtype=torch.float32, device=back.device)
+    rng = torch.zeros((len(idx), 2), dtype=torch.float64, device=back.device)
+    steps = torch.zeros(len(idx), dtype=torch.float64, device=back.device)
+    if len(mine):
+        r = back.rng[local]
+        states[rows] = back.states[local].float()
+        rng[rows, 0] = (r & 0xFFFFFFFF).double()
+        rng[rows, 1] = ((r >> 32) & 0xFFFFFFFF).double()
+        steps[rows] = back.steps_done[local].double()
+    if dist is not None:
+        for t in (states, rng, steps):
+            dist.all_reduce(t, op=dist.ReduceOp.SUM)
+    if rank != 0:
+        return None
+    arrays = {'states': states.cpu().numpy(), 'rng': rng.cpu().numpy(), 'steps_done': steps.cpu().numpy(),
+              'game_index': idx.astype(np.float64)}
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + '.npy'), a)
+    return {'dir': outdir, 'files': sorted(name + '.npy' for name in arrays), 'games': len(idx), 'of_games': total,
+            'bytes': int(sum(a.nbytes for a in arrays.values()))}
 
 
 # ------------------------------------------------------------------------------------------------ roofline records
@@ -1087,10 +1155,15 @@ def parse_args(argv=None):
                     default=256, help='plies per kernel launch (= per bench step)')
     ap.add_argument('--burn-in', type=int, default=1, help='untimed launches before warm-up (same shape as the timed ones)')
     ap.add_argument('--desync', type=int, default=640, help='spread of extra burn-in plies across the batch (0 = lock-step)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beyond the headline: CPU baseline, clock samples, roofline, the untimed extras and, at N > 1, '
+                         'the weak-scaling base (a plain run sets up, warms up, times the steps and prints the line)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what they computed (a fixed sample of %d games) as DIR/<name>.npy' % DUMP_GAMES)
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU baseline')
     ap.add_argument('--cpu-seconds', type=float, default=6.0, help='wall seconds per CPU-baseline worker')
     ap.add_argument('--cpu-workers', type=int, default=0, help='CPU-baseline worker processes (0 = every usable core)')
-    ap.add_argument('--no-also', action='store_true', help='skip the untimed extras (clean profiling passes)')
+    ap.add_argument('--no-also', action='store_true', help='--full without the untimed extras (clean profiling passes)')
     ap.add_argument('--comm', choices=('nccl', 'gloo'), default='nccl',
                     help='process-group backend for barrier + reductions (gloo: rehearse the N > 1 path on a box with fewer '
                          'GPUs than ranks - ranks then share devices round-robin)')
@@ -1137,7 +1210,7 @@ def main(argv=None):
     args.gpus = world
 
     cpu = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         # every world size carries the CPU path of the same box in the same run (north_star); on rank 0, before the GPU
         # context and the process group exist (spawned workers) - the other ranks wait for it at the rendezvous
         cpu = cpu_baseline(args.size, args.cpu_seconds, args.cpu_workers or None)
@@ -1174,15 +1247,18 @@ def main(argv=None):
 
     opts = {'size': args.size, 'plies_per_step': max(1, args.plies_per_step), 'steps': max(1, args.steps),
             'warmup': max(0, args.warmup), 'games_per_gpu': args.games_per_gpu or (65536 if world == 1 else 131072),
-            'desync': args.desync, 'burn_in_steps': max(0, args.burn_in), 'world': world}
+            'desync': args.desync, 'burn_in_steps': max(0, args.burn_in), 'world': world, 'sample_clock': args.full}
     back = HipBackend(dev)
     res = run_rank(rank, world, back, opts, dist if use_dist else None)
+    dumped = None
+    if args.dump_outputs:      # before anything else touches the games
+        dumped = dump_outputs(args.dump_outputs, back, rank, world, opts, dist if use_dist else None)
 
     # N > 1: the weak-scaling base of THIS run - rank 0 repeats the timed launches alone (every other rank idle at the barrier:
     # its shard is the per-GPU batch, the launch shape is the timed one) - so that the line carries its own efficiency =
     # value(N) / (N x base) instead of leaving the division to a second run
     solo = None
-    if world > 1:
+    if world > 1 and args.full:
         if use_dist:
             dist.barrier()
         if rank == 0:
@@ -1198,7 +1274,7 @@ def main(argv=None):
     if rank == 0:
         N, F, K, W = opts['size'], opts['plies_per_step'], opts['steps'], opts['warmup']
         opts['clocks'] = res.get('clocks')
-        also, per_ply = ({}, None) if args.no_also else extras(dev, back, opts)
+        also, per_ply = ({}, None) if args.no_also or not args.full else extras(dev, back, opts)
         launch_ms = res['kernel_ms'] / K
         line = {
             'metric': METRIC, 'value': round(res['value'], 1), 'unit': 'env steps/s', 'n_gpus': world, 'steps': K, 'warmup': W,
@@ -1212,7 +1288,6 @@ def main(argv=None):
                 'env_steps_per_bench_step': F * res['total_games'], 'burn_in_steps': opts['burn_in_steps'],
                 'desync_plies': opts['desync'], 'sharding': 'batch split across ranks by global game index, no collective',
             },
-            'roofline': roofline_record(dev, N, res['count'], F, launch_ms, per_ply, res.get('clocks')),
             'clocks': res.get('clocks'),
             # what the communicator saw (None at a plain one-process run): backend, its world size, the ranks an
             # all-reduce of ones counted; and every rank's own average launch time (HIP events on its stream)
@@ -1222,9 +1297,13 @@ def main(argv=None):
             'per_rank': res.get('per_rank'), 'distinct_devices': res.get('distinct_devices'),
             'per_gpu_steps_per_s': [round(F * res['games_per_gpu'] / (x * 1e-3), 1) for x in res['per_rank_launch_ms']],
         }
-        line['roofline'].update(flat_config_scalars(line, also, res))
         if numa is not None:
             line['rank0_numa'] = numa
+        if dumped is not None:
+            line['outputs'] = dumped
+    if rank == 0 and args.full:
+        line['roofline'] = roofline_record(dev, N, res['count'], F, launch_ms, per_ply, res.get('clocks'))
+        line['roofline'].update(flat_config_scalars(line, also, res))
         if solo:
             line['weak_scaling_base'] = {'games': res['games_per_gpu'], 'steps_per_s_one_gpu': round(solo, 1),
                                          'how': 'rank 0 alone, the other ranks idle at a barrier: the same %d launches of the same shape, right after the timed region' % K}

@@ -51,8 +51,44 @@ def _check(line, n_gpus, steps, warmup):
         assert roof['traffic'] is not None and roof['traffic'] > 0
 
 
+def _check_dump(outdir, line, every=16):
+    """What --dump-outputs wrote: float32 / float64 arrays, under 64 MB, and - for every `every`-th sampled game - the boards,
+    generator state and played-step counter the oracle computes for that game on bench.py's schedule (de-sync slice of its
+    shard, burn-in, warm-up, timed launches; the settle launches leave no trace)."""
+    import numpy as np
+    import bench
+    from oracle import c_oracle
+    cfg, world = line['config'], line['n_gpus']
+    N, F, total, per_gpu = cfg['board'], cfg['plies_per_step'], cfg['games'], cfg['games_per_gpu']
+    out = {n: np.load(os.path.join(outdir, n + '.npy')) for n in ('states', 'rng', 'steps_done', 'game_index')}
+    assert out['states'].dtype == np.float32 and all(out[k].dtype == np.float64 for k in ('rng', 'steps_done', 'game_index'))
+    assert sum(a.nbytes for a in out.values()) <= 64 * 2 ** 20
+    assert line['outputs']['games'] == len(out['game_index']) and line['outputs']['of_games'] == total
+    idx = out['game_index'].astype(np.int64)
+    assert np.array_equal(idx, bench.dump_sample(total))
+    assert np.all(out['steps_done'] == line['steps'] * F)
+    pick = np.arange(0, len(idx), every)
+    games = idx[pick]
+    desync = np.zeros(len(games), np.int64)
+    for j, i in enumerate(games):
+        r = int(i) // per_gpu
+        first, count = bench.shard(total, r, world)
+        assert first <= i < first + count
+        desync[j] = ((int(i) - first) // ((count + 15) // 16)) * cfg['desync_plies'] // 16
+    want = np.zeros((len(games), 6, N, N), np.uint8)
+    want_rng = np.array([c_oracle.lib().gg_oracle_rng_seed(bench.SEED, int(i)) for i in games], np.uint64)
+    for d in np.unique(desync):
+        if d:
+            m = desync == d
+            want[m], want_rng[m], _ = c_oracle.batch_rollout_mt(want[m], want_rng[m], int(d), True)
+    want, want_rng, _ = c_oracle.batch_rollout_mt(want, want_rng, F * (cfg['burn_in_steps'] + line['warmup'] + line['steps']), True)
+    assert np.array_equal(out['states'][pick], want.astype(np.float32))
+    rng = out['rng'][pick].astype(np.uint64)
+    assert np.array_equal(rng[:, 0] | (rng[:, 1] << np.uint64(32)), np.asarray(want_rng).view(np.uint64))
+
+
 def test_bench_one_gpu_plain_invocation():
-    line = _run([sys.executable, 'bench.py', '--gpus', '1', '--steps', '3', '--warmup', '1', '--cpu-seconds', '0.5',
+    line = _run([sys.executable, 'bench.py', '--gpus', '1', '--steps', '3', '--warmup', '1', '--full', '--cpu-seconds', '0.5',
                  '--cpu-workers', '8'])
     _check(line, 1, 3, 1)
     assert line['comm']['backend'] is None and line['rccl_world_size'] is None and len(line['per_rank_launch_ms']) == 1
@@ -83,10 +119,31 @@ def test_bench_one_gpu_plain_invocation():
     assert all(r['fused_steps_per_s'] > 0 and r['one_ply_steps_per_s'] > 0 for rows in sweep.values() for r in rows)
 
 
+def test_bench_plain_run_is_lean_and_dumps_what_it_computed(tmp_path):
+    """The plain run the driver times: headline fields only (no CPU baseline, roofline or extras), exactly --steps timed
+    launches, and --dump-outputs writes the same arrays on every run with the same arguments - those the oracle computes."""
+    lines = []
+    for k in range(2):
+        lines.append(_run([sys.executable, 'bench.py', '--gpus', '1', '--steps', '2', '--warmup', '1',
+                           '--dump-outputs', str(tmp_path / ('d%d' % k))]))
+    line = lines[0]
+    for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step', 'config', 'outputs'):
+        assert k in line, k
+    for k in ('cpu_baseline', 'roofline', 'also', 'weak_scaling_base'):
+        assert k not in line, k
+    assert line['steps'] == 2 and line['warmup'] == 1 and line['per_rank'][0]['steps_played'] == 2 * 256 * 65536
+    assert line['config']['games'] == 65536 and line['value'] > 1e8
+    assert line['value'] == pytest.approx(line['config']['env_steps_per_bench_step'] / (line['ms_per_step'] * 1e-3), rel=1e-3)
+    import numpy as np
+    for name in line['outputs']['files']:
+        assert np.array_equal(np.load(tmp_path / 'd0' / name), np.load(tmp_path / 'd1' / name)), name
+    _check_dump(str(tmp_path / 'd0'), line)
+
+
 @pytest.mark.parametrize('launcher', ['torch.distributed.run', 'self-spawn'])
-def test_bench_two_ranks(launcher):
-    tail = ['bench.py', '--gpus', '2', '--comm', 'gloo', '--games-per-gpu', '16384', '--steps', '2', '--warmup', '1', '--no-also',
-            '--cpu-seconds', '0.5', '--cpu-workers', '4']
+def test_bench_two_ranks(launcher, tmp_path):
+    tail = ['bench.py', '--gpus', '2', '--comm', 'gloo', '--games-per-gpu', '16384', '--steps', '2', '--warmup', '1', '--full', '--no-also',
+            '--cpu-seconds', '0.5', '--cpu-workers', '4', '--dump-outputs', str(tmp_path)]
     if launcher == 'self-spawn':
         cmd = [sys.executable] + tail
     else:
@@ -107,6 +164,7 @@ def test_bench_two_ranks(launcher):
     assert line['weak_scaling_base']['games'] == 16384 and line['weak_scaling_base']['steps_per_s_one_gpu'] > 0
     assert line['efficiency'] == pytest.approx(line['value'] / (2 * line['weak_scaling_base']['steps_per_s_one_gpu']), rel=1e-3)
     assert 0 < line['efficiency'] <= 1.05 and 'numa_node' in line['rank0_numa']          # (two ranks share ONE GPU here: ~0.5)
+    _check_dump(str(tmp_path), line)                     # both ranks' games, gathered on rank 0
 
 
 def test_bench_one_rank_over_rccl():
@@ -115,7 +173,7 @@ def test_bench_one_rank_over_rccl():
     the first contact with the communicator."""
     line = _run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1', '--master-addr', '127.0.0.1',
                  '--master-port', str(_free_port()), 'bench.py', '--gpus', '1', '--comm', 'nccl', '--steps', '2', '--warmup', '1',
-                 '--no-also', '--no-cpu-baseline'])
+                 '--full', '--no-also', '--no-cpu-baseline'])
     _check(line, 1, 2, 1)
     assert line['comm'] == {'backend': 'nccl', 'world_size': 1, 'ranks_counted': 1} and line['rccl_world_size'] == 1
     assert len(line['per_rank']) == 1 and line['per_rank'][0]['first_game'] == 0
@@ -127,7 +185,7 @@ def test_bench_per_rank_records_and_nccl_device_check():
     visible GPUs is refused with a clear message instead of RCCL's duplicate-GPU failure."""
     import torch
     line = _run([sys.executable, 'bench.py', '--gpus', '2', '--comm', 'gloo', '--games-per-gpu', '16384', '--steps', '2', '--warmup', '1',
-                 '--no-also', '--no-cpu-baseline'])
+                 '--full', '--no-also', '--no-cpu-baseline'])
     per = line['per_rank']
     assert [p['first_game'] for p in per] == [0, 16384] and [p['steps_played'] for p in per] == [2 * 256 * 16384] * 2
     ndev = torch.cuda.device_count()

@@ -28,6 +28,7 @@ def _checked_backend(sample):
     class Checked(bench.HipBackend):
         launches = 0
         deepest = 0
+        restores = 0
 
         def setup(self, count, size, first_game):
             super().setup(count, size, first_game)
@@ -53,7 +54,15 @@ def _checked_backend(sample):
             assert np.array_equal(self.states[sel_t].cpu().numpy(), w), ('states', self.launches, plies, lo, hi)
             assert np.array_equal(self.rng[sel_t].cpu().numpy().view(np.uint64), r), ('rng', self.launches)
             self.launches += 1
-            self.deepest = int(self.plies.max())
+            self.deepest = max(self.deepest, int(self.plies.max()))
+
+        def snapshot(self):      # (run_rank puts the games back after its settle launches: so does the replay)
+            return super().snapshot(), self.want.copy(), self.want_rng.copy(), self.plies.copy(), self.counted.copy()
+
+        def restore(self, snap):
+            super().restore(snap[0])
+            self.want, self.want_rng, self.plies, self.counted = (a.copy() for a in snap[1:])
+            self.restores += 1
 
     return Checked(torch.device('cuda', 0))
 
@@ -63,7 +72,9 @@ def test_bench_trajectory_subsample_vs_oracle():
     slice launches of 40 ... 600 plies, 1 burn-in + 5 warm-up + 4 timed launches of 256 plies over all 65 536 games -
     k_rollout4<19, 0, false, true, false, false>) is followed by an oracle replay of 512 games chosen by global game index
     (every 128th, offset 5: all 16 slices); states, generator states and the kernel's own step counters must agree
-    after each of the 25 launches (+ the untimed clock-settle launches of the same shape), i.e. up to ~3 160 plies into a slot's life (mean game length ~640)."""
+    after each of the 25 launches (+ the untimed clock-settle launches of the same shape, which play on from the burn-in and are
+    then undone), i.e. up to ~3 160 plies into a slot's life on the fixed schedule and far beyond it in the settle phase (mean
+    game length ~640)."""
     import bench
     back = _checked_backend(512)
     opts = {'size': 19, 'plies_per_step': 256, 'steps': 4, 'warmup': 5, 'games_per_gpu': 65536, 'desync': 640,
@@ -71,7 +82,8 @@ def test_bench_trajectory_subsample_vs_oracle():
     res = bench.run_rank(0, 1, back, opts, None)
     assert res['steps_played'] == 4 * 256 * 65536
     assert back.launches == 15 + 1 + res['settle_launches'] + 5 + 4 and res['settle_launches'] >= 4     # (+ the clock-settle launches, untimed)
-    assert back.deepest >= 2560 + 560 + 256 * res['settle_launches']
+    assert back.deepest >= 256 + 560 + 256 * res['settle_launches'] and back.restores == 1    # settle launches checked, then undone
+    assert int(back.plies.max()) >= 2560 + 560                     # the timed games: de-sync + burn-in + warm-up + timed plies
     assert np.array_equal(back.steps_done[back.idx_t].cpu().numpy(), back.counted)
     # the sub-sample really is the stationary mix: dense boards, finished-and-restarted games, every slice
     stones = back.want[:, 0].sum(axis=(1, 2)) + back.want[:, 1].sum(axis=(1, 2))

@@ -122,6 +122,71 @@ def test_bench_run_rank_two_ranks_over_gloo(tmp_path):
     assert hashlib.sha256(got.tobytes()).hexdigest() != hashlib.sha256(np.zeros_like(got).tobytes()).hexdigest()
 
 
+class SettlingOracleBackend(OracleBackend):
+    """The oracle backend with the hooks that switch bench.run_rank's settle phase on (clock sampler, snapshot / restore)."""
+
+    def clock_sampler(self):
+        return None
+
+    def snapshot(self):
+        return self.states.copy(), self.rng.copy()
+
+    def restore(self, snap):
+        self.states[...], self.rng[...] = snap
+
+
+def test_bench_settle_launches_leave_no_trace_in_the_games():
+    """The settle phase runs as many launches as the machine needs; the games the timed launches start from (and what
+    --dump-outputs writes) are those of the fixed schedule: de-sync, burn-in, warm-up, timed steps."""
+    import bench
+    count = OPTS['games_per_gpu']
+    back = SettlingOracleBackend()
+    res = bench.run_rank(0, 1, back, dict(OPTS, world=1, sample_clock=False, clock_settle_s=0.01, clock_settle_max_s=0.05))
+    assert res['settle_launches'] >= 8 and res['clocks']['sclk_mhz'] is None
+    solo = OracleBackend()
+    solo.setup(count, OPTS['size'], 0)
+    chunk = (count + 15) // 16
+    for g in range(1, 16):
+        lo, hi = g * chunk, min(count, (g + 1) * chunk)
+        if lo < hi:
+            solo.rollout(g * OPTS['desync'] // 16, lo, hi)
+    solo.rollout(OPTS['plies_per_step'] * (OPTS['burn_in_steps'] + OPTS['warmup'] + OPTS['steps']))
+    assert np.array_equal(back.states, solo.states) and np.array_equal(back.rng, solo.rng)
+
+
+def test_bench_dump_outputs_sample_and_format(tmp_path):
+    """--dump-outputs: a fixed sample of the games in float32 / float64 (every game of a small batch), the generator state
+    split into exact 32-bit halves, at most 64 MB at the default 19x19 shape."""
+    import torch
+    import bench
+    assert bench.parse_args(['--dump-outputs', 'x']).dump_outputs == 'x' and bench.parse_args([]).dump_outputs is None
+    a = bench.dump_sample(65536)
+    assert len(a) == bench.DUMP_GAMES and np.array_equal(a, bench.dump_sample(65536)) and np.all(np.diff(a) > 0) and a[-1] < 65536
+    assert np.array_equal(bench.dump_sample(1000), np.arange(1000))
+    S = bench.DUMP_GAMES
+    assert S * 6 * 19 * 19 * 4 + S * (2 + 1 + 1) * 8 <= 64 * 2 ** 20
+
+    class Back:
+        pass
+    back = Back()
+    back.torch, back.device = torch, torch.device('cpu')
+    g = torch.Generator().manual_seed(5)
+    back.states = torch.randint(0, 2, (6000, 6, 9, 9), dtype=torch.uint8, generator=g)
+    back.rng = torch.randint(-2 ** 63, 2 ** 63 - 1, (6000,), dtype=torch.int64, generator=g)
+    back.steps_done = torch.full((6000,), 768, dtype=torch.int64)
+    rec = bench.dump_outputs(str(tmp_path / 'out'), back, 0, 1, {'size': 9, 'games_per_gpu': 6000})
+    assert rec['games'] == S and rec['of_games'] == 6000
+    assert sorted(os.listdir(tmp_path / 'out')) == rec['files'] == ['game_index.npy', 'rng.npy', 'states.npy', 'steps_done.npy']
+    out = {n[:-4]: np.load(tmp_path / 'out' / n) for n in rec['files']}
+    assert out['states'].dtype == np.float32 and all(out[k].dtype == np.float64 for k in ('rng', 'steps_done', 'game_index'))
+    idx = out['game_index'].astype(np.int64)
+    assert np.array_equal(idx, bench.dump_sample(6000))
+    assert np.array_equal(out['states'], back.states.numpy()[idx].astype(np.float32))
+    rng = out['rng'].astype(np.uint64)
+    assert np.array_equal(rng[:, 0] | (rng[:, 1] << np.uint64(32)), back.rng.numpy().view(np.uint64)[idx])
+    assert np.all(out['steps_done'] == 768)
+
+
 def test_bench_shard_is_the_package_shard():
     import bench
     from gymgo_amd.envs.vec_env import shard
@@ -136,6 +201,7 @@ def test_bench_argument_plumbing():
     import bench
     a = bench.parse_args(['--gpus', '8', '--steps', '20', '--warmup', '5'])
     assert (a.gpus, a.steps, a.warmup, a.plies_per_step) == (8, 20, 5, 256)       # F is NOT tied to --steps
+    assert not a.full and bench.parse_args(['--full']).full          # a plain run times the headline only
     a = bench.parse_args(['--fuse', '64'])
     assert a.plies_per_step == 64 and a.gpus == 1
     assert bench.algo_bytes_per_step(19) == 4336 and bench.fused_bytes_per_game(19) == 4348

@@ -9,11 +9,11 @@
 TAG=${1:-r02}; F=${2:-256}; shift; shift
 R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out/$TAG; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-BENCH="python $R/bench.py --steps 20 --warmup 5 --plies-per-step $F $*"
+BENCH="python $R/bench.py --steps 20 --warmup 5 --full --plies-per-step $F $*"
 if [ -n "$LIGHT" ]; then timeout 900 $BENCH --no-cpu-baseline --no-also > $O/bench.json 2> $O/bench.err
 else timeout 900 $BENCH > $O/bench.json 2> $O/bench.err; fi
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -o kt -- $BENCH --no-cpu-baseline --no-also > $O/kt.log 2>&1
-SHORT="python $R/bench.py --steps 6 --warmup 0 --burn-in 2 --plies-per-step $F --no-cpu-baseline --no-also $*"
+SHORT="python $R/bench.py --steps 6 --warmup 0 --burn-in 2 --full --plies-per-step $F --no-cpu-baseline --no-also $*"
 timeout 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pmc_fetch -o p -- $SHORT > $O/pmc_fetch.log 2>&1
 timeout 600 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/pmc_write -o p -- $SHORT > $O/pmc_write.log 2>&1
 timeout 600 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY --kernel-trace --output-format csv -d $O/pmc_inst -o p -- $SHORT > $O/pmc_inst.log 2>&1
