@@ -173,21 +173,28 @@ __device__ __forceinline__ void flood_jobs(const uint32_t (&m)[R], const uint32_
   (void)sweeps;
 }
 
-// liberties (dilate & empty, counted; only min(count, 2) is used) of the group gt[], m[] = the rows of its colour, ot[] = the
-// other colour's rows (read from LDS together with m[], BEFORE the flood: read behind it they cost the lane a round trip)
+// liberties (dilate & empty) of the group gt[], SATURATED: min(count, 2) - all any caller uses; m[] = the rows of its colour,
+// ot[] = the other colour's rows (read from LDS together with m[], BEFORE the flood: read behind it they cost the lane a round
+// trip).  Nothing is counted: o = the OR of the liberty rows, d = the columns that hold a liberty in two rows (a liberty row
+// ANDed with the OR of the rows before it, one v_bitop3 per row); two or more liberties iff d != 0 or o has two bits.  Three
+// chains over the rows r % 3, joined by a majority (a column set in two chains).  (Counting took nineteen v_bcnt, 4 cycles each.)
 template <int R>
 __device__ __forceinline__ uint32_t job_liberties(const uint32_t (&gt)[R], const uint32_t (&ot)[R], const uint32_t (&m)[R]) {
   constexpr uint32_t FULLROW = (1u << R) - 1u;
-  uint32_t cnt3[3] = {0u, 0u, 0u};
+  uint32_t o3[3] = {0u, 0u, 0u}, d3[3] = {0u, 0u, 0u};
 #pragma unroll
   for (int r = 0; r < R; ++r) {
     const uint32_t e = B3(ot[r], m[r], FULLROW, ~(TA | TB) & TC & 0xFF);   // empty points
     const uint32_t up = r > 0 ? gt[r - 1] : 0u, dn = r + 1 < R ? gt[r + 1] : 0u;
     const uint32_t dd = B3(shl1(gt[r]), gt[r] >> 1, up, T_OR3);
     const uint32_t l = B3(dd, dn, e, (TA | TB) & TC);
-    cnt3[r % 3] += (uint32_t)__popc(l);   // (three accumulating chains, not one of nineteen v_bcnt)
+    d3[r % 3] = B3(l, o3[r % 3], d3[r % 3], T_ANDOR);
+    o3[r % 3] = B3(l, o3[r % 3], 0u, T_OR3);
   }
-  return cnt3[0] + cnt3[1] + cnt3[2];
+  const uint32_t o = B3(o3[0], o3[1], o3[2], T_OR3);
+  const uint32_t d = B3(d3[0], d3[1], d3[2], T_OR3) | B3(o3[0], o3[1], o3[2], T_MAJ);
+  const uint32_t two = B3(o - 1u, o, d, T_ANDOR);   // o & (o - 1) | d
+  return (o != 0u ? 1u : 0u) + (two != 0u ? 1u : 0u);
 }
 
 // job descriptor: bits 0-4 board, 5-13 the seed (flat point index), 15 the colour flooded, 16 the job floods G, 18 the job exists,
@@ -644,8 +651,14 @@ __global__ __launch_bounds__(kWave, 2) void k_rollout5(uint8_t *__restrict__ sta
             pz[i] = make_uint4(res[4 * i], 4 * i + 1 < R ? res[4 * i + 1] : 0u, 4 * i + 2 < R ? res[4 * i + 2] : 0u, 4 * i + 3 < R ? res[4 * i + 3] : 0u);
           if (lib2) atomicOr(clsv + sj, lib2 << 4);
         } else if (have && cnt < 2u) {
+          // (two rows per ds_or_b64: the blocks and RS are even, and for odd R the last pair ORs zero into row R, inside the
+          // block; half the LDS instructions of nineteen ds_or_b32 - skipping empty rows by a per-row branch instead cost 4 %)
+          static_assert(Lds5<R>::kG % 2 == 0 && RS % 2 == 0 && R + 1 <= RS, "8-byte aligned row pairs inside the block");
 #pragma unroll
-          for (int r = 0; r < R; ++r) atomicOr(gb + RS + r, res[r]);
+          for (int r = 0; r < R; r += 2) {
+            const uint32_t hi = r + 1 < R ? res[r + 1] : 0u;
+            atomicOr(reinterpret_cast<unsigned long long *>(gb + RS + r), ((unsigned long long)hi << 32) | res[r]);
+          }
           if (cnt == 0u) atomicOr(clsv + sj, 1u << ((d >> 19) & 3u));
         }
       }
