@@ -44,3 +44,22 @@ extern "C" int32_t gg_ab_sweeps_read_r5(unsigned long long *out2) {
 // A/B builds only: read and clear the phase clocks of THIS translation unit's launches (gg_prof has internal linkage)
 GG_PROF_READ(gg_ab_prof_read_r5)
 #endif
+
+#ifdef GG_AB_P3
+// A/B builds only: read and clear the phase-3 branch counters of k_rollout5 (gg_v5.h: gg_p3)
+extern "C" int32_t gg_ab_p3_read_r5(unsigned long long *out10) {
+  if (hipDeviceSynchronize() != hipSuccess) return 1;
+  if (hipMemcpyFromSymbol(out10, HIP_SYMBOL(gg::gg_p3), 80) != hipSuccess) return 2;
+  unsigned long long z[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  return hipMemcpyToSymbol(HIP_SYMBOL(gg::gg_p3), z, 80) == hipSuccess ? 0 : 3;
+}
+#endif
+
+#if defined(GG_AB_P3) || defined(GG_AB_LIVE)
+// A/B builds with -DGG_AB_LIVE or -DGG_AB_P3 only: boards of k_rollout5 launches whose live plies were not a prefix of the launch or whose played count
+// differs from their number of draws (gg_v5.h: gg_live_bad; zero when the invariant holds)
+extern "C" int32_t gg_ab_live_bad_r5(unsigned long long *out1) {
+  if (hipDeviceSynchronize() != hipSuccess) return 1;
+  return hipMemcpyFromSymbol(out1, HIP_SYMBOL(gg::gg_live_bad), 8) == hipSuccess ? 0 : 2;
+}
+#endif

@@ -197,6 +197,30 @@ __device__ __forceinline__ uint32_t job_liberties(const uint32_t (&gt)[R], const
   return (o != 0u ? 1u : 0u) + (two != 0u ? 1u : 0u);
 }
 
+#ifdef GG_AB_P3
+// A/B builds only (make ab EXTRA=-DGG_AB_P3, tools/exp/r5_p3_counts.py): the wave-plies that take each wave-wide branch of
+// phase 3 and the trip count of the atari-join, counted in registers (the branches are wave-uniform) and added up once per group
+// of boards.  [0] wave-plies, [1] capt_m, [2] ncapn == 1 && libsG == 0, [3] ko1, [4] anya && capt_m (the branch in front of the
+// atari-join's seeds up to round 7; gone since, always 0), [5] anyf, [6] atari-join trips, [7] the most trips of one wave-ply
+// (max), [8] boards that capture, [9] boards that move
+static __device__ unsigned long long gg_p3[10];
+#define GG_P3(k, n) (p3c_[k] += (n))
+#else
+#define GG_P3(k, n) ((void)0)
+#endif
+#ifdef GG_AB_MARK
+#define GG_MARK(k) asm volatile("; GGMARK " #k ::: "memory")   // phase-3 branch bodies in the listing (tools/exp/r5_p3_mix.py)
+#else
+#define GG_MARK(k) do {} while (0)
+#endif
+#if defined(GG_AB_P3) || defined(GG_AB_LIVE)
+// A/B builds with -DGG_AB_LIVE (or the -DGG_AB_P3 counter build) only: boards whose live plies were not a prefix of the launch or
+// whose played count is not their number of draws.  Its own switch, not every GG_AB build: the per-ply bookkeeping sits in phase 1
+// and would skew the phase clocks (-DGG_AB_PROF) of one side of an A/B comparison.
+#define GG_LIVE_CHECK 1
+static __device__ unsigned long long gg_live_bad;
+#endif
+
 // job descriptor: bits 0-4 board, 5-13 the seed (flat point index), 15 the colour flooded, 16 the job floods G, 18 the job exists,
 // 19-20 the direction of q's neighbour it starts from (0 up, 1 down, 2 left, 3 right)
 // info word of a board (cleared in phase 1, ORed by its jobs): bits 0-3 the directions whose opponent group was captured, 4-5 the
@@ -394,6 +418,13 @@ __global__ __launch_bounds__(kWave, 2) void k_rollout5(uint8_t *__restrict__ sta
     uint32_t flr = flagsv[s5];
     const uint64_t x0r = ((uint64_t)rngv[2 * s5 + 1] << 32) | rngv[2 * s5];
     int playedr = 0;
+#ifdef GG_AB_P3
+    uint32_t p3c_[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+#endif
+#ifdef GG_LIVE_CHECK
+    int drawsr = 0;        // plies on which this board was live (drew a move or passed)
+    bool was_dead = false; // a ply on which it was not live has passed
+#endif
     // ---------------------------------------------------------------- the plies
     GG_PROF(6);   // load
     FairShare fair(lds + Lds5<R>::kFair);
@@ -429,6 +460,14 @@ __global__ __launch_bounds__(kWave, 2) void k_rollout5(uint8_t *__restrict__ sta
         const bool done = (fl >> 2) & 1u;
         const bool live = on && !(done && !auto_reset);
         const bool reset = live && done;           // auto-reset: the board is init_state from now on
+        // Invariant: a board's live plies are a PREFIX of the launch (`on` never changes inside it; a done board stays done
+        // unless auto_reset, and then it is live on every ply), and every live ply draws exactly once and moves (a_q >= 0:
+        // phase 3 counts it) - so `played` equals the number of draws, which the write-back turns into the generator's advance.
+#ifdef GG_LIVE_CHECK
+        if (live && was_dead) atomicAdd(&gg_live_bad, 1ull);
+        was_dead = was_dead || (bl && !live);
+        drawsr += live ? 1 : 0;
+#endif
         uint32_t v[RPL], p[RPL];
         const uint32_t rm = reset ? ~0u : 0u;   // a board being reset plays on the empty board
 #pragma unroll
@@ -691,21 +730,32 @@ __global__ __launch_bounds__(kWave, 2) void k_rollout5(uint8_t *__restrict__ sta
         const uint32_t capt_m = info & 15u;   // the directions in which an opponent group died (never set on a board that does not move)
         // The collection block holds the opponent groups next to q with NO liberty left (captured: q was their only liberty, so
         // they were never in M) or with exactly ONE (they had q and one more: they were in M).  So it splits by M alone:
-        // captured = all4 & ~M, leaving M = all4 & M.
-        uint32_t g0[RPL], cap[RPL];
+        // captured = all4 & ~M, leaving M = all4 & M.  (all4 holds opponent stones only.)
+        uint32_t g0[RPL], opp1[RPL];
 #pragma unroll
         for (int r = 0; r < RPL; ++r) {
           g0[r] = bg[r];   // the G block: the flood of G, the stone alone as phase 1 left it there, or nothing (pass / idle board)
-          cap[r] = B3(all4[r], M[r], M[r], TA & ~TB & 0xFF);
+          opp1[r] = B3(opp0[r], all4[r], M[r], TA & ~(TB & ~TC) & 0xFF);   // opp0 & ~cap: the opponent's stones after the captures
         }
         // liberties of G among the empty points (saturated at 2): G's own count, or the empty neighbours of q when the
         // stone stands alone
         const uint32_t ne = qs & 7u, ne2 = ne < 2u ? ne : 2u;
         uint32_t libsG = ((qs >> 11) & 1u) ? ((info >> 4) & 3u) : ne2;
         uint32_t ko_oh = 0, ko_bit = 0;   // the ko point: one-hot row of this lane / column bit (almost always none)
+        GG_P3(0, 1u);
+        GG_P3(8, (uint32_t)__popcll(__ballot(capt_m != 0u && t5 == 0)));
+        GG_P3(9, (uint32_t)__popcll(__ballot(a >= 0 && t5 == 0)));
+        GG_MARK(10);
         if (__ballot(capt_m != 0u)) {   // a capture on some board of the wave
+          GG_MARK(11);
+          GG_P3(1, 1u);
+          uint32_t cap[RPL];   // the captured stones
+#pragma unroll
+          for (int r = 0; r < RPL; ++r) cap[r] = B3(all4[r], M[r], M[r], TA & ~TB & 0xFF);
           const uint32_t ncapn = (uint32_t)__popc(capt_m);        // captured neighbours of q
           if (__ballot(ncapn == 1u && libsG == 0u)) {
+            GG_MARK(12);
+            GG_P3(2, 1u);
             uint32_t dg[RPL];
             dilate_rows<RPL>(g0, dg);
             uint32_t cntc = 0;
@@ -714,6 +764,7 @@ __global__ __launch_bounds__(kWave, 2) void k_rollout5(uint8_t *__restrict__ sta
             const uint32_t c2 = cntc < 2u ? cntc : 2u;
             const uint32_t tot = c2 + dpp0<QP_X1>(c2);
             libsG += (ncapn == 1u && libsG == 0u) ? (tot < 2u ? tot : 2u) : ncapn;
+            GG_MARK(13);
           } else {
             libsG += ncapn;
           }
@@ -721,6 +772,8 @@ __global__ __launch_bounds__(kWave, 2) void k_rollout5(uint8_t *__restrict__ sta
           // stone first: rare enough to keep the rest off the usual path)
           const bool ko1 = ncapn == 1u && !(qs & CL_OPEN);
           if (__ballot(ko1)) {
+            GG_MARK(14);
+            GG_P3(3, 1u);
             uint32_t died = 0;   // captured stones on this lane's rows (one captured neighbour: exactly one stone died iff its group is that stone)
 #pragma unroll
             for (int r = 0; r < RPL; ++r) died += (uint32_t)__popc(cap[r]);
@@ -729,46 +782,96 @@ __global__ __launch_bounds__(kWave, 2) void k_rollout5(uint8_t *__restrict__ sta
             const uint32_t kr = (uint32_t)ar - (capt_m & 1u) + ((capt_m >> 1) & 1u) - (uint32_t)r0;
             ko_oh = (ko && kr < (uint32_t)RPL) ? (1u << (kr & 31)) : 0u;
             ko_bit = 1u << (((uint32_t)ac - ((capt_m >> 2) & 1u) + (capt_m >> 3)) & 31u);
+            GG_MARK(15);
           }
+          GG_MARK(16);
           // the mover's groups in atari next to a captured stone (and not merged into G) now have >= 2 liberties: they join M
-          // before the classes are patched
-          uint32_t atari[RPL];
-          uint32_t anya = 0;
+          // before the classes are patched.  The seeds are the stones of such groups next to a captured stone (zero on a board
+          // without a capture: its cap is empty); the fill grows them inside `atari` by one-step dilation, Gauss-Seidel in
+          // the lane (a row sees the row swept just before it as already grown; the partner lane's seam row as it was at the
+          // start of the trip), down and up in turn, until a trip adds nothing.  The fixed point is the union of the atari
+          // groups the seeds touch whatever the order.  The wave still runs as many trips as its slowest board needs, but
+          // fewer than with the Jacobi dilation of round 7 (2.40 against 2.87 per wave-ply that enters the loop, 47 % of
+          // them), at 6 instead of 7 VALU per row and trip (profiles/r08_p3_counts.txt).
+          uint32_t atari[RPL], f[RPL], anyf = 0;
+          {
+            const uint32_t up = dpp0<0x138>(cap[RPL - 1]), dn = dpp0<0x130>(cap[0]);
 #pragma unroll
-          for (int r = 0; r < RPL; ++r) { atari[r] = B3(mine1[r], M[r], g0[r], TA & ~(TB | TC) & 0xFF); anya |= atari[r]; }
-          if (__ballot(anya != 0u && capt_m != 0u)) {
-            uint32_t f[RPL], anyf = 0;
-            dilate_rows<RPL>(cap, f);
-#pragma unroll
-            for (int r = 0; r < RPL; ++r) { f[r] &= atari[r]; anyf |= f[r]; }
-            if (__ballot(anyf != 0)) {
-#pragma unroll 1
-              for (int it = 0; it < R * R; ++it) {
-                uint32_t dd[RPL], chg = 0;
-                dilate_rows<RPL>(f, dd);
-#pragma unroll
-                for (int r = 0; r < RPL; ++r) {
-                  const uint32_t nw = B3(dd[r], atari[r], f[r], T_ANDOR);
-                  chg |= nw ^ f[r];
-                  f[r] = nw;
-                }
-                if (__ballot(chg != 0) == 0) break;
-              }
-#pragma unroll
-              for (int r = 0; r < RPL; ++r) M[r] |= f[r];
+            for (int r = 0; r < RPL; ++r) {
+              atari[r] = B3(mine1[r], M[r], g0[r], TA & ~(TB | TC) & 0xFF);   // mine & ~M & ~G
+              const uint32_t above = r == 0 ? up : cap[r - 1], below = r == RPL - 1 ? dn : cap[r + 1];
+              const uint32_t v = B3(cap[r] >> 1, above, below, T_OR3);
+              f[r] = B3(shl1(cap[r]), v, atari[r], (TA | TB) & TC);           // dilate(cap) & atari
+              anyf |= f[r];
             }
           }
+          GG_MARK(17);
+          if (__ballot(anyf != 0u)) {
+            GG_MARK(18);
+            GG_P3(5, 1u);
+#ifdef GG_AB_P3
+            uint32_t trips_ = 0;
+#define GG_TRIP ++trips_
+#else
+#define GG_TRIP do {} while (0)
+#endif
+            // one trip over the lane's rows in order R0, R0 + D, ..: a row grows from its (already grown) predecessor, its old
+            // successor and itself; chg collects the bits a trip adds
+#define GG_JOIN_TRIP(R0, D)                                                                                               \
+            do {                                                                                                          \
+              GG_TRIP;                                                                                                    \
+              const uint32_t up_ = dpp0<0x138>(f[RPL - 1]), dn_ = dpp0<0x130>(f[0]);                                      \
+              chg = 0;                                                                                                    \
+              _Pragma("unroll") for (int i_ = 0; i_ < RPL; ++i_) {                                                        \
+                const int r_ = (R0) + (D) * i_;                                                                           \
+                const uint32_t above_ = r_ == 0 ? up_ : f[r_ == 0 ? 0 : r_ - 1];                                          \
+                const uint32_t below_ = r_ == RPL - 1 ? dn_ : f[r_ == RPL - 1 ? 0 : r_ + 1];                              \
+                const uint32_t v_ = B3(f[r_] >> 1, above_, below_, T_OR3);                                              \
+                const uint32_t g_ = B3(shl1(f[r_]), v_, atari[r_], (TA | TB) & TC);                                      \
+                chg = B3(g_, f[r_], chg, (TA & ~TB & 0xFF) | TC);                                                         \
+                f[r_] |= g_;                                                                                              \
+              }                                                                                                           \
+            } while (0)
+            uint32_t chg;
+#pragma unroll 1
+            for (int it = 0; it < R * R; ++it) {
+              GG_JOIN_TRIP(0, 1);
+              if (__ballot(chg != 0u) == 0) break;
+              GG_JOIN_TRIP(RPL - 1, -1);
+              if (__ballot(chg != 0u) == 0) break;
+            }
+#undef GG_JOIN_TRIP
+#undef GG_TRIP
+#ifdef GG_AB_P3
+            GG_P3(6, trips_);
+            p3c_[7] = trips_ > p3c_[7] ? trips_ : p3c_[7];
+#endif
+#pragma unroll
+            for (int r = 0; r < RPL; ++r) M[r] |= f[r];
+            GG_MARK(19);
+          }
         }
+        GG_MARK(20);
+        // The mask rule.  The new M: the stones of M outside G and the collected groups (those left with one liberty leave M; a
+        // captured group was never in it), and G if it has two liberties - (M & ~G & ~all4) | (gsel & G); it is the old rule's
+        // (M & mine & ~G) | (gsel & G) | (M & opp & ~all4), as M holds stones only and all4 opponent stones only.  A point is
+        // a legal move for the next player iff it is empty and has a neighbour in x: an empty point, a stone of the mover
+        // outside the new M (in atari: placing there captures) or an opponent stone in it (a group it joins keeps a liberty):
+        // x = full & ~(new M ? mine : opp).  Six v_bitop3 per row and the dilation (the old chain: nine).  Equal to the old
+        // chain in every bit case these invariants admit (20 of 128), and they hold from ply to ply: M holds stones only (the load
+        // takes it from the analysis' class planes, a reset clears it, each ply keeps a subset of M | G | the atari-join's mover
+        // stones, and a captured stone was never in M); all4 holds opponent stones only and G mover stones only (phase 1 clears
+        // both blocks, the jobs OR in fills inside their own colour's rows); every set lies inside `full` (rows and columns
+        // >= N of the planes are zero).
         const uint32_t gsel = libsG >= 2u ? ~0u : 0u;
-        uint32_t Mo2[RPL], opp1[RPL], Mm2[RPL], e[RPL], x[RPL], nbr[RPL];
+        uint32_t e[RPL], x[RPL], nbr[RPL];
 #pragma unroll
         for (int r = 0; r < RPL; ++r) {
-          Mo2[r] = B3(M[r], opp0[r], all4[r], TA & TB & ~TC & 0xFF);        // (a captured group was never in M)
-          opp1[r] = B3(opp0[r], cap[r], cap[r], TA & ~TB & 0xFF);
-          const uint32_t Mm = B3(M[r], mine1[r], g0[r], TA & TB & ~TC & 0xFF);
-          Mm2[r] = B3(gsel, g0[r], Mm, T_ANDOR);                           // (M & mine & ~g0) | (gsel & g0)
+          const uint32_t u = B3(M[r], g0[r], all4[r], TA & ~(TB | TC) & 0xFF);   // M & ~G & ~all4
+          M[r] = B3(gsel, g0[r], u, T_ANDOR);                                      // the new M
+          const uint32_t y = B3(M[r], mine1[r], opp1[r], T_SEL);
+          x[r] = B3(full[r], y, y, TA & ~TB & 0xFF);
           e[r] = B3(full[r], opp1[r], mine1[r], TA & ~(TB | TC) & 0xFF);
-          x[r] = B3(mine1[r], Mm2[r], e[r], (TA & ~TB & 0xFF) | TC) | Mo2[r];
         }
         dilate_rows<RPL>(x, nbr);
         const uint32_t mv_m = moves_now ? ~0u : 0u;
@@ -776,7 +879,6 @@ __global__ __launch_bounds__(kWave, 2) void k_rollout5(uint8_t *__restrict__ sta
         for (int r = 0; r < RPL; ++r) {
           const uint32_t invalid = B3(e[r], nbr[r], full[r], ~(TA & TB) & TC & 0xFF);
           inv_r[r] = B3(mv_m, invalid, inv_r[r], T_SEL);
-          M[r] = Mm2[r] | Mo2[r];
         }
         if (__ballot(ko_oh != 0u)) {   // (only a board that moved has a ko point)
 #pragma unroll
@@ -805,6 +907,18 @@ __global__ __launch_bounds__(kWave, 2) void k_rollout5(uint8_t *__restrict__ sta
     }
     if (plies >= 8) fair.release();
     GG_PROF(5);
+#ifdef GG_AB_P3
+    if (ln0 == 0) {
+#pragma unroll
+      for (int k = 0; k < 10; ++k) {
+        if (k == 7) atomicMax(&gg_p3[7], (unsigned long long)p3c_[7]);
+        else atomicAdd(&gg_p3[k], (unsigned long long)p3c_[k]);
+      }
+    }
+#endif
+#ifdef GG_LIVE_CHECK
+    if (playedr != drawsr) atomicAdd(&gg_live_bad, 1ull);
+#endif
 
     // ---------------------------------------------------------------- store
     int lnS;
