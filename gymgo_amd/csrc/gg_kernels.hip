@@ -28,6 +28,7 @@
 #include "gg_ws.h"
 #include "gg_sym.h"
 #include "gg_ns16.h"
+#include "gg_po.h"
 #include "gymgo_amd.h"
 
 namespace gg {
@@ -408,6 +409,31 @@ uint32_t recip16(int32_t N) {
     else { GG_K(19, false); }                \
   } while (0)
 
+
+// ---- batched Monte Carlo playouts (gg_po.h): argument checks of both entry points, then the launch of the fill /
+// harvest kernel for the board's row capacity
+static int32_t po_args(PoArgs &a, const uint32_t *roots, int64_t R, int32_t N, int32_t K, int64_t first_root,
+                       uint64_t base_seed, int32_t max_plies, int32_t chunk_plies, float komi, uint32_t *slots, uint64_t *rng,
+                       int64_t *plies, int64_t *job, int64_t S, int64_t *counter, int32_t *counts, int64_t *sums,
+                       int32_t *ownership) {
+  if (N < 2 || N > GG_MAX_BOARD || R < 0 || S < 1) return GG_E_BADSIZE;
+  if (K < 1 || chunk_plies < 1 || max_plies < 1 || max_plies % chunk_plies || first_root < 0) return GG_E_BADARG;
+  if ((first_root + R) > (int64_t(1) << 62) / K) return GG_E_BADSIZE;   // global job ids must fit an int64
+  if (!roots || !slots || !rng || !plies || !job || !counter || !counts || !sums) return GG_E_NULLPTR;
+  a.roots = roots; a.slots = slots; a.rng = rng; a.plies = plies; a.job = job; a.counter = counter; a.counts = counts;
+  a.sums = sums; a.own = ownership; a.S = S; a.J = R * K; a.first_job = first_root * K; a.base_seed = base_seed; a.K = K;
+  a.max_plies = max_plies; a.komi = komi;
+  return 0;
+}
+
+template <bool FILL>
+static void launch_po(const PoArgs &a, int32_t N, int cus, hipStream_t s) {
+  const int nbw = N <= 13 ? Lat<13>::NBW : Lat<19>::NBW;
+  const int grid = grid_for(cus, (a.S + nbw - 1) / nbw, 64);
+#define GG_K(R, F) k_po_harvest<R, F, FILL><<<grid, kWave, 0, s>>>(a, N)
+  GG_DISPATCH_N(N);
+#undef GG_K
+}
 }  // namespace
 
 extern "C" {
@@ -1104,6 +1130,48 @@ int32_t gg_rng_seed(uint64_t *rng, uint64_t base_seed, int64_t first_game, int64
   hipStream_t s = (hipStream_t)hip_stream;
   k_rng_seed<<<(unsigned)((B + 255) / 256), 256, 0, s>>>(rng, base_seed, first_game, B);
   return (int32_t)hipGetLastError();
+}
+
+int32_t gg_playouts_begin(const uint32_t *roots, int64_t R, int32_t N, int32_t K, int64_t first_root, uint64_t base_seed,
+                          int32_t max_plies, int32_t chunk_plies, uint32_t *slots, uint64_t *rng, int64_t *plies, int64_t *job,
+                          int64_t S, int64_t *counter, int32_t *counts, int64_t *sums, int32_t *ownership, void *hip_stream) {
+  PoArgs a;
+  if (int32_t e = po_args(a, roots, R, N, K, first_root, base_seed, max_plies, chunk_plies, 0.f, slots, rng, plies, job, S,
+                          counter, counts, sums, ownership))
+    return e;
+  OnDeviceOf on_dev(slots);
+  hipStream_t s = (hipStream_t)hip_stream;
+  hipError_t err = hipSuccess;
+  if (R > 0) {
+    err = hipMemsetAsync(counts, 0, sizeof(int32_t) * 4 * R, s);
+    if (err == hipSuccess) err = hipMemsetAsync(sums, 0, sizeof(int64_t) * 2 * R, s);
+    if (err == hipSuccess && ownership) err = hipMemsetAsync(ownership, 0, sizeof(int32_t) * 2 * N * N * R, s);
+    if (err != hipSuccess) return (int32_t)err;
+  }
+  launch_po<true>(a, N, on_dev.cus(), s);
+  return (int32_t)hipGetLastError();
+}
+
+int32_t gg_playouts_advance(const uint32_t *roots, int64_t R, int32_t N, int32_t K, int64_t first_root, uint64_t base_seed,
+                            int32_t max_plies, int32_t chunk_plies, float komi, int32_t chunks, uint32_t *slots, uint64_t *rng,
+                            int64_t *plies, int64_t *job, int64_t S, int64_t *counter, int32_t *counts, int64_t *sums,
+                            int32_t *ownership, void *hip_stream) {
+  PoArgs a;
+  if (int32_t e = po_args(a, roots, R, N, K, first_root, base_seed, max_plies, chunk_plies, komi, slots, rng, plies, job, S,
+                          counter, counts, sums, ownership))
+    return e;
+  if (chunks < 0) return GG_E_BADARG;
+  if (R == 0 || chunks == 0) return 0;
+  OnDeviceOf on_dev(slots);
+  const int cus = on_dev.cus();
+  hipStream_t s = (hipStream_t)hip_stream;
+  for (int c = 0; c < chunks; ++c) {
+    // the existing tracked dispatch, auto_reset = 0: finished and empty slots stay frozen
+    if (int32_t e = gg_batch_rollout_tracked(slots, rng, nullptr, plies, S, N, chunk_plies, 0, hip_stream)) return e;
+    launch_po<false>(a, N, cus, s);
+    if (int32_t e = (int32_t)hipGetLastError()) return e;
+  }
+  return 0;
 }
 
 }  // extern "C"

@@ -9,6 +9,8 @@ Containers
 Errors: an illegal move raises AssertionError (gym_go/gogame.py:59, :117); action_size() without
 arguments raises RuntimeError (:196).
 """
+import collections
+
 import numpy as np
 import torch
 
@@ -776,6 +778,123 @@ def batch_env_step_tracked(tracked, actions=None, rng=None, komi=0.0, reward_met
     _lib.check(code, 'gg_batch_env_step_tracked')
     return out
 
+
+
+# ---------------------------------------------------------------- Monte Carlo playouts to the end of the game
+# K uniform-random playouts of every root until the game ends (GoEnv.uniform_random_action + step, gym_go/envs/go_env.py:49-81),
+# scored with Tromp-Taylor areas (gogame.areas / winning, gym_go/gogame.py:225-230, :275-300) and reduced per root on the
+# device (gg_playouts_begin / gg_playouts_advance, include/gymgo_amd.h): the leaf values of a Monte Carlo search, value
+# targets, ownership estimates.
+
+Playouts = collections.namedtuple('Playouts', 'black_wins white_wins draws unfinished margin_sum plies_sum ownership')
+Playouts.__doc__ = """Per-root results of batch_playouts: black_wins / white_wins / draws / unfinished (int32: outcome
+sign(black - white - komi); playouts cut off by max_plies), margin_sum (int64: sum of black - white area), plies_sum (int64:
+plies played) and ownership (int32 [R, 2, N, N]: per point, in how many playouts it ended in black's / white's area; None
+unless asked for)."""
+
+
+def _run_playouts(roots, R, N, K, max_plies, komi, seed, first_root, ownership, S, chunk_plies, dev):
+    """Device work of batch_playouts on tracked roots: -> (counts int32 [R, 4], sums int64 [R, 2], own or None)."""
+    L = _lib.lib()
+    J = R * K
+    W = tracked_words(N)
+    slots = torch.empty((S, W), dtype=_I32, device=dev)
+    rng = torch.empty(S, dtype=_I64, device=dev)
+    plies = torch.empty(S, dtype=_I64, device=dev)
+    job = torch.empty(S, dtype=_I64, device=dev)
+    counter = torch.empty(2, dtype=_I64, device=dev)
+    counts = torch.empty((R, 4), dtype=_I32, device=dev)
+    sums = torch.empty((R, 2), dtype=_I64, device=dev)
+    own = torch.empty((R, 2, N, N), dtype=_I32, device=dev) if ownership else None
+    stream = _lib.current_raw_stream(dev)   # torch's current stream: the counter copies below go there too
+    common = (_lib.dev_ptr(roots, _I32, 'roots'), R, N, K, int(first_root), int(seed) & (2 ** 64 - 1), int(max_plies),
+              int(chunk_plies))
+    bufs = (_lib.dev_ptr(slots, _I32, 'slots'), _lib.dev_ptr(rng, _I64, 'rng'), _lib.dev_ptr(plies, _I64, 'plies'),
+            _lib.dev_ptr(job, _I64, 'job'), S, _lib.dev_ptr(counter, _I64, 'counter'), _lib.dev_ptr(counts, _I32, 'counts'),
+            _lib.dev_ptr(sums, _I64, 'sums'), _lib.dev_ptr(own, _I32, 'ownership'))
+    _lib.check(L.gg_playouts_begin(*common, *bufs, stream), 'gg_playouts_begin')
+    # Every playout is harvested within max_plies / chunk_plies chunks of its start and all S slots are busy while the queue
+    # holds jobs, so this many chunks always suffice; more means the device did not do what it was asked: raise, never spin.
+    M = int(max_plies) // int(chunk_plies)
+    bound = (-(-J // S) + 1) * M + 2
+    step = max(1, min(4, M))
+    # Two batches of chunks in flight: the outstanding-job count of one is read (pinned copy + event wait) while the next runs.
+    host = [torch.empty(2, dtype=_I64, pin_memory=True) for _ in range(2)]
+    pending, queued, k = [], 0, 0
+    with torch.cuda.device(dev):
+        while True:
+            if queued < bound:
+                n = min(step, bound - queued)
+                _lib.check(L.gg_playouts_advance(*common[:8], float(komi), n, *bufs, stream), 'gg_playouts_advance')
+                queued += n
+                host[k].copy_(counter, non_blocking=True)
+                ev = torch.cuda.Event()
+                ev.record()
+                pending.append((ev, host[k]))
+                k ^= 1
+            if len(pending) == 2 or queued >= bound:
+                ev, h = pending.pop(0)
+                ev.synchronize()
+                outstanding = int(h[1]) - int(h[0])
+                if outstanding == 0:
+                    break
+                if not pending:
+                    raise _lib.GymGoNativeError('batch_playouts: %d jobs still outstanding after %d chunks (the bound for %d '
+                                                'jobs on %d slots)' % (outstanding, queued, J, S))
+        for ev, _ in pending:   # (the pinned buffers stay alive until the copies still queued have landed)
+            ev.synchronize()
+    return counts, sums, own
+
+
+def batch_playouts(batch_states, playouts, max_plies=None, komi=0.0, seed=20260927, first_root=0, ownership=False, slots=None,
+                   chunk_plies=32):
+    """`playouts` uniform-random playouts of every root of batch_states ([R, 6, N, N]) to the end of the game, scored and
+    reduced per root on the device -> Playouts (device tensors for a device tensor, NumPy arrays for NumPy input).
+
+    Playout j of root r is global job p = (first_root + r) * playouts + j: its generator is rng_seed(.., seed, first_game=p),
+    it plays batch_rollout's sampler without auto-reset from root r until the game ends or max_plies plies have been played
+    (then it also counts as unfinished) and is scored as it stands.  Results are integer sums: they do not depend on
+    `slots` (working boards, default: enough to fill the device) or `chunk_plies` (plies per rollout launch between two
+    harvests; max_plies must be a multiple of it), and shards by first_root concatenate to the whole.  Default max_plies:
+    8 N^2 rounded up to a multiple of chunk_plies.  The roots are not modified."""
+    box = _Box(batch_states)
+    st = box.t
+    if st.dim() != 4 or st.shape[1] != govars.NUM_CHNLS or st.shape[2] != st.shape[3]:
+        raise ValueError('batch_states must be [R, 6, N, N] (got %s)' % (tuple(st.shape),))
+    R, N, K, chunk_plies = st.shape[0], st.shape[2], int(playouts), int(chunk_plies)
+    if chunk_plies < 1:
+        raise ValueError('chunk_plies must be >= 1')
+    if max_plies is None:
+        max_plies = -(-8 * N * N // chunk_plies) * chunk_plies
+    max_plies = int(max_plies)
+    if K < 1 or max_plies < 1 or max_plies % chunk_plies or int(first_root) < 0:
+        raise ValueError('need playouts >= 1, max_plies >= 1 and a multiple of chunk_plies, first_root >= 0 (got %d, %d, %d, %d)'
+                         % (K, max_plies, chunk_plies, int(first_root)))
+    dev = st.device
+    if slots is None:
+        slots = 256 * int(_lib.lib().gg_device_cus())   # 19x19: k_rollout5 from 256 games per CU on
+    S = max(1, min(int(slots), R * K))
+    if R == 0:
+        counts = torch.zeros((0, 4), dtype=_I32, device=dev)
+        sums = torch.zeros((0, 2), dtype=_I64, device=dev)
+        own = torch.zeros((0, 2, N, N), dtype=_I32, device=dev) if ownership else None
+    else:
+        counts, sums, own = _run_playouts(batch_track(st), R, N, K, max_plies, komi, seed, first_root, ownership, S,
+                                          chunk_plies, dev)
+    res = (counts[:, 0], counts[:, 1], counts[:, 2], counts[:, 3], sums[:, 0], sums[:, 1], own)
+    if box.numpy:
+        res = tuple(None if t is None else t.cpu().numpy() for t in res)
+    return Playouts(*res)
+
+
+def playouts(state, n, **kw):
+    """batch_playouts of one state [6, N, N] -> Playouts of scalars (and ownership [2, N, N])."""
+    box = _Box(state)
+    res = batch_playouts(box.t[None], n, **kw)
+    out = tuple(None if t is None else t[0] for t in res)
+    if box.numpy:
+        out = tuple(None if t is None else t.cpu().numpy() for t in out)
+    return Playouts(*out)
 
 # ---------------------------------------------------------------- policy-weighted sampling on the device
 # gogame.random_weighted_action / random_action (gym_go/gogame.py:385-404) for every game of a batch: what a self-play loop

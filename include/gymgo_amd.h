@@ -349,6 +349,41 @@ int32_t gg_batch_symmetry_rows(const uint32_t *in, int32_t planes, const int32_t
 /* rng[b] = initial generator state for (base_seed, game index first_game + b). */
 int32_t gg_rng_seed(uint64_t *rng, uint64_t base_seed, int64_t first_game, int64_t B, void *hip_stream);
 
+/*
+ * Batched Monte Carlo playouts to the end of the game, scored and reduced per root.  Composes the loop of
+ * GoEnv.uniform_random_action + step (gym_go/envs/go_env.py:78-81; gogame.next_state gym_go/gogame.py:34-87) until the
+ * game ends, then gogame.winning (:225-230) on gogame.areas (Tromp-Taylor, :275-300) of the final position.
+ * Playout j of local root r is global job p = (first_root + r) * K + j: its generator starts as gg_rng_seed(base_seed,
+ * first_game = p), it plays the sampler of gg_batch_rollout from roots[r] with auto_reset = 0 until the game-over flag is
+ * set or max_plies plies have been played (a root that has ended plays none) and is scored as it stands: b, w = areas,
+ * outcome = sign(b - w - komi) (komi as float32).  Per root (integer sums: no result depends on S, chunk_plies or the
+ * order in which the device finishes the jobs):
+ *   counts    int32 [R][4]: black wins, white wins, draws, unfinished (playouts cut off by max_plies)
+ *   sums      int64 [R][2]: sum of (b - w), sum of plies played
+ *   ownership int32 [R][2][N][N] (nullable): per point, the number of playouts that ended with it in black's / white's area
+ * roots: tracked boards uint32 [R][gg_tracked_words(N)] (gg_batch_track_states), read only.  S working slots, caller-owned
+ * and otherwise opaque: slots uint32 [S][gg_tracked_words(N)], rng uint64 [S], plies int64 [S], job int64 [S];
+ * counter int64 [2] = {next job id, the value it reaches once every job is done}: counter[1] - counter[0] = jobs outstanding
+ * (every harvested playout takes one id from the queue, ids from R K on refill nothing).
+ *   gg_playouts_begin    zeroes counts / sums / ownership, sets counter = {m, R K + m} with m = min(S, R K) and fills the
+ *                        first m slots with jobs 0, 1, ... (the other slots: empty, frozen boards)
+ *   gg_playouts_advance  queues `chunks` x (gg_batch_rollout_tracked of chunk_plies plies on all S slots + one harvest
+ *                        launch that scores every slot whose playout has ended, adds it to its root and refills the slot
+ *                        from the queue).  The work is done once counter[0] == counter[1]; a playout takes at most
+ *                        max_plies / chunk_plies chunks, so (ceil(R K / S) + 1) * max_plies / chunk_plies chunks always suffice.
+ * Both calls take the same arguments (komi and chunks: advance only) and must be given them unchanged between a begin
+ * and the advances that follow it.  GG_E_BADSIZE: N outside [2, 19], R < 0, S < 1; GG_E_BADARG: K < 1, chunk_plies < 1,
+ * max_plies < 1 or not a multiple of chunk_plies, first_root < 0, chunks < 0; GG_E_NULLPTR: a buffer other than
+ * ownership is NULL.
+ */
+int32_t gg_playouts_begin(const uint32_t *roots, int64_t R, int32_t N, int32_t K, int64_t first_root, uint64_t base_seed,
+                          int32_t max_plies, int32_t chunk_plies, uint32_t *slots, uint64_t *rng, int64_t *plies, int64_t *job,
+                          int64_t S, int64_t *counter, int32_t *counts, int64_t *sums, int32_t *ownership, void *hip_stream);
+int32_t gg_playouts_advance(const uint32_t *roots, int64_t R, int32_t N, int32_t K, int64_t first_root, uint64_t base_seed,
+                            int32_t max_plies, int32_t chunk_plies, float komi, int32_t chunks, uint32_t *slots, uint64_t *rng,
+                            int64_t *plies, int64_t *job, int64_t S, int64_t *counter, int32_t *counts, int64_t *sums,
+                            int32_t *ownership, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

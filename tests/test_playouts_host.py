@@ -1,0 +1,97 @@
+"""CPU: batched Monte Carlo playouts (gg_playouts_begin / gg_playouts_advance, gogame.batch_playouts) without a device -
+argument checks of the C-ABI, no CPU fallback in the Python API, and the expectation helpers the GPU tests build on
+(tests/playout_expect.py) against the C restatement."""
+import numpy as np
+import pytest
+
+import playout_expect as px
+from oracle import c_oracle
+
+
+@pytest.fixture(scope='module')
+def built(native_built):
+    from gymgo_amd import _lib
+    return _lib
+
+
+def _begin(L, R=4, N=9, K=2, first_root=0, max_plies=64, chunk=32, S=8, ptr=1):
+    p = ptr or None
+    return L.gg_playouts_begin(p, R, N, K, first_root, 7, max_plies, chunk, p, p, p, p, S, p, p, p, None, None)
+
+
+def _advance(L, R=4, N=9, K=2, first_root=0, max_plies=64, chunk=32, chunks=1, S=8, ptr=1):
+    p = ptr or None
+    return L.gg_playouts_advance(p, R, N, K, first_root, 7, max_plies, chunk, 0.0, chunks, p, p, p, p, S, p, p, p, None, None)
+
+
+def test_playout_entry_points_check_arguments_before_device_work(built):
+    L = built.lib()
+    for call in (_begin, _advance):
+        assert call(L, N=1) == -1 and call(L, N=20) == -1
+        assert call(L, R=-1) == -1 and call(L, S=0) == -1
+        assert call(L, K=0) == -3
+        assert call(L, chunk=0) == -3
+        assert call(L, max_plies=48, chunk=32) == -3
+        assert call(L, max_plies=0) == -3
+        assert call(L, first_root=-1) == -3
+        assert call(L, ptr=0) == -2
+    assert _advance(L, chunks=-1) == -3
+    # (a valid set of arguments with NULL buffers is still a NULL-pointer error, not a launch)
+    assert _advance(L, chunks=0, ptr=0) == -2
+
+
+def test_batch_playouts_has_no_cpu_fallback(built):
+    import torch
+    from gymgo_amd import gogame
+    if torch.cuda.is_available():
+        pytest.skip('device present')
+    with pytest.raises(built.GymGoNativeError):
+        gogame.batch_playouts(np.zeros((2, 6, 9, 9), np.uint8), 4)
+    with pytest.raises(built.GymGoNativeError):
+        gogame.playouts(np.zeros((6, 9, 9), np.uint8), 4)
+    with pytest.raises(built.GymGoNativeError):
+        gogame.batch_playouts(torch.zeros((2, 6, 9, 9), dtype=torch.uint8), 4)
+
+
+def test_plies_from_generator_match_ply_by_ply_replay():
+    """The sampler advances the generator once per ply played: the helper's inversion against a one-ply-at-a-time replay."""
+    N, B = 7, 192
+    st = np.zeros((B, 6, N, N), np.uint8)
+    rng0 = c_oracle.rng_seed(11, B)
+    fin, rng1, _ = c_oracle.batch_rollout(st, rng0, 96, auto_reset=False)
+    got = px.plies_from_rng(rng0, rng1)
+    cur, rng, count = st.copy(), rng0.copy(), np.zeros(B, np.int64)
+    for _ in range(96):
+        alive = cur[:, 5, 0, 0] == 0
+        cur, rng, _ = c_oracle.batch_rollout(cur, rng, 1, auto_reset=False)
+        count += alive
+    assert np.array_equal(cur, fin) and np.array_equal(got, count)
+    assert 0 < got.min() and (got < 96).any() and (got == 96).any()
+
+
+@pytest.mark.parametrize('N', [5, 9, 19])
+def test_ownership_helper_sums_to_the_areas(N):
+    roots = px.make_roots(N, 24, 3, max_ply=6 * N * N // 4, step=4 * N)
+    fin, _, _ = c_oracle.batch_rollout(np.repeat(roots, 8, axis=0), c_oracle.rng_seed(5, 24 * 8), 8 * N * N, auto_reset=False)
+    own = px.ownership(fin)
+    b, w = c_oracle.batch_areas(fin)
+    assert np.array_equal(own[:, 0].sum(axis=(1, 2)), b) and np.array_equal(own[:, 1].sum(axis=(1, 2)), w)
+    assert not (own[:, 0] & own[:, 1]).any()
+    assert np.array_equal(own[:, 0] | fin[:, 0], own[:, 0]) and np.array_equal(own[:, 1] | fin[:, 1], own[:, 1])
+    assert (b + w < N * N).any()   # some points are nobody's
+
+
+def test_expected_results_are_consistent():
+    N, R, K = 9, 16, 6
+    roots = px.make_roots(N, R, 9, max_ply=60, step=4)
+    full = px.expected(roots, K, 8 * N * N, komi=0.0, with_ownership=True)
+    assert np.array_equal(full['black_wins'] + full['white_wins'] + full['draws'], np.full(R, K))
+    assert full['unfinished'].sum() == 0 and full['plies_sum'][-1] == 0   # (the last root has ended: no plies)
+    assert np.array_equal(full['ownership'][:, 0].sum(axis=(1, 2)) - full['ownership'][:, 1].sum(axis=(1, 2)), full['margin_sum'])
+    cut = px.expected(roots, K, 8, komi=0.0)
+    assert cut['unfinished'][:-1].min() > 0 and cut['plies_sum'].max() <= 8 * K
+    # two shards by first_root are the whole
+    a = px.expected(roots[:5], K, 8 * N * N, first_root=0)
+    b = px.expected(roots[5:], K, 8 * N * N, first_root=5)
+    for k in ('black_wins', 'margin_sum', 'plies_sum'):
+        assert np.array_equal(np.concatenate([a[k], b[k]]), full[k])
