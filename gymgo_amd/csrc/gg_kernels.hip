@@ -434,6 +434,33 @@ static void launch_po(const PoArgs &a, int32_t N, int cus, hipStream_t s) {
   GG_DISPATCH_N(N);
 #undef GG_K
 }
+
+// ---- first-move playouts (gg_po.h, MpArgs): the checks of po_args on the pair space, in the same order
+static int32_t mp_args(MpArgs &m, const uint32_t *roots, int64_t R, int32_t N, const int32_t *plan, int64_t T, int32_t K,
+                       int64_t first_root, uint64_t base_seed, int32_t max_plies, int32_t chunk_plies, float komi, uint32_t *slots,
+                       uint64_t *rng, int64_t *plies, int64_t *job, int64_t S, int64_t *counter, int32_t *counts, int64_t *sums) {
+  if (N < 2 || N > GG_MAX_BOARD || R < 0 || S < 1) return GG_E_BADSIZE;
+  const int64_t A = (int64_t)N * N + 1;
+  if (R > (int64_t)0x7FFFFFFF / A || T < 0 || T > R * A) return GG_E_BADSIZE;   // pair ids r A + a are int32
+  if (K < 1 || chunk_plies < 1 || max_plies < 1 || max_plies % chunk_plies || first_root < 0) return GG_E_BADARG;
+  if ((first_root + R) > ((int64_t(1) << 62) / K) / A) return GG_E_BADSIZE;   // global job ids must fit an int64
+  if (!roots || !plan || !slots || !rng || !plies || !job || !counter || !counts || !sums) return GG_E_NULLPTR;
+  PoArgs &a = m;
+  a.roots = roots; a.slots = slots; a.rng = rng; a.plies = plies; a.job = job; a.counter = counter; a.counts = counts;
+  a.sums = sums; a.own = nullptr; a.S = S; a.J = T * K; a.first_job = 0; a.base_seed = base_seed; a.K = K;
+  a.max_plies = max_plies; a.komi = komi;
+  m.plan = plan; m.first_pair = first_root * A; m.A = (int32_t)A;
+  return 0;
+}
+
+template <bool FILL>
+static void launch_mp(const MpArgs &m, int32_t N, int cus, hipStream_t s) {
+  const int nbw = N <= 13 ? Lat<13>::NBW : Lat<19>::NBW;
+  const int grid = grid_for(cus, (m.S + nbw - 1) / nbw, 64);
+#define GG_K(R, F) k_po_harvest<R, F, FILL, MpArgs><<<grid, kWave, 0, s>>>(m, N)
+  GG_DISPATCH_N(N);
+#undef GG_K
+}
 }  // namespace
 
 extern "C" {
@@ -1169,6 +1196,63 @@ int32_t gg_playouts_advance(const uint32_t *roots, int64_t R, int32_t N, int32_t
     // the existing tracked dispatch, auto_reset = 0: finished and empty slots stay frozen
     if (int32_t e = gg_batch_rollout_tracked(slots, rng, nullptr, plies, S, N, chunk_plies, 0, hip_stream)) return e;
     launch_po<false>(a, N, cus, s);
+    if (int32_t e = (int32_t)hipGetLastError()) return e;
+  }
+  return 0;
+}
+
+int32_t gg_move_playouts_plan(const uint32_t *roots, int64_t R, int32_t N, int32_t *offsets, int32_t *plan, void *hip_stream) {
+  if (N < 2 || N > GG_MAX_BOARD || R < 0) return GG_E_BADSIZE;
+  if (R > (int64_t)0x7FFFFFFF / (N * N + 1)) return GG_E_BADSIZE;   // plan entries r A + a are int32
+  if (!roots || !offsets || !plan) return GG_E_NULLPTR;
+  OnDeviceOf on_dev(offsets);
+  hipStream_t s = (hipStream_t)hip_stream;
+  if (R == 0) return (int32_t)hipMemsetAsync(offsets, 0, sizeof(int32_t), s);   // offsets[0] = T = 0
+  const int cus = on_dev.cus();
+  k_mp_counts<<<(unsigned)((R + 255) / 256), 256, 0, s>>>(roots, offsets, R, N);
+  k_children_order_scan<<<1, 1024, 0, s>>>(offsets, nullptr, R, N * N + 1);   // counts -> exclusive offsets, offsets[R] = T
+  k_mp_plan<<<grid_for(cus, (R + 3) / 4), 4 * kWave, 0, s>>>(roots, offsets, plan, R, N);
+  return (int32_t)hipGetLastError();
+}
+
+int32_t gg_move_playouts_begin(const uint32_t *roots, int64_t R, int32_t N, const int32_t *plan, int64_t T, int32_t K,
+                               int64_t first_root, uint64_t base_seed, int32_t max_plies, int32_t chunk_plies, uint32_t *slots,
+                               uint64_t *rng, int64_t *plies, int64_t *job, int64_t S, int64_t *counter, int32_t *counts,
+                               int64_t *sums, void *hip_stream) {
+  MpArgs m;
+  if (int32_t e = mp_args(m, roots, R, N, plan, T, K, first_root, base_seed, max_plies, chunk_plies, 0.f, slots, rng, plies, job,
+                          S, counter, counts, sums))
+    return e;
+  OnDeviceOf on_dev(slots);
+  hipStream_t s = (hipStream_t)hip_stream;
+  hipError_t err = hipSuccess;
+  if (R > 0) {
+    const int64_t pairs = R * m.A;
+    err = hipMemsetAsync(counts, 0, sizeof(int32_t) * 4 * pairs, s);
+    if (err == hipSuccess) err = hipMemsetAsync(sums, 0, sizeof(int64_t) * 2 * pairs, s);
+    if (err != hipSuccess) return (int32_t)err;
+  }
+  launch_mp<true>(m, N, on_dev.cus(), s);
+  return (int32_t)hipGetLastError();
+}
+
+int32_t gg_move_playouts_advance(const uint32_t *roots, int64_t R, int32_t N, const int32_t *plan, int64_t T, int32_t K,
+                                 int64_t first_root, uint64_t base_seed, int32_t max_plies, int32_t chunk_plies, float komi,
+                                 int32_t chunks, uint32_t *slots, uint64_t *rng, int64_t *plies, int64_t *job, int64_t S,
+                                 int64_t *counter, int32_t *counts, int64_t *sums, void *hip_stream) {
+  MpArgs m;
+  if (int32_t e = mp_args(m, roots, R, N, plan, T, K, first_root, base_seed, max_plies, chunk_plies, komi, slots, rng, plies, job,
+                          S, counter, counts, sums))
+    return e;
+  if (chunks < 0) return GG_E_BADARG;
+  if (T == 0 || chunks == 0) return 0;
+  OnDeviceOf on_dev(slots);
+  const int cus = on_dev.cus();
+  hipStream_t s = (hipStream_t)hip_stream;
+  for (int c = 0; c < chunks; ++c) {
+    // the same tracked dispatch as gg_playouts_advance: refills and first moves happen in the harvest, between launches
+    if (int32_t e = gg_batch_rollout_tracked(slots, rng, nullptr, plies, S, N, chunk_plies, 0, hip_stream)) return e;
+    launch_mp<false>(m, N, cus, s);
     if (int32_t e = (int32_t)hipGetLastError()) return e;
   }
   return 0;

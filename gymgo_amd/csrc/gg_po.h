@@ -12,7 +12,13 @@
 //
 // Layout: one row per lane, one board per LPB lanes (gg_lat.h): the areas are lat_areas' two floods of the empty points,
 // here also returned as owned rows for the per-point ownership counts.
+//
+// Flat Monte Carlo (gg_move_playouts_plan / _begin / _advance): the same kernel with MpArgs.  The plan (k_mp_counts, the
+// scan of k_children_order_scan, k_mp_plan) lists the legal (root, action) pairs; a refill plays the pair's action on the
+// root with lat_play_full (the five-flood ply) before it stores the child, so the first move also happens between launches.
 #pragma once
+#include <type_traits>
+
 #include "gg_lat.h"
 
 namespace gg {
@@ -67,10 +73,23 @@ __device__ __forceinline__ void lat_areas_owned(uint32_t bl, uint32_t wh, uint32
   area_w = sum >> 16;
 }
 
+// First-move playouts (gg_move_playouts_*): the jobs of a legal (root, action) pair are K playouts from the child.  The plan
+// lists the T legal pairs as r A + a (A = N^2 + 1); local job q is playout j = q % K of pair plan[q / K], global job
+// ((first_root + r) A + a) K + j.  A slot's job word holds the pair, not q: the counters are indexed by it.
+struct MpArgs : PoArgs {  // J = T K; first_job and own unused
+  const int32_t *plan;    // [T] r A + a
+  int64_t first_pair;     // first_root A
+  int32_t A;
+};
+
 // FILL (gg_playouts_begin): slot s takes job s (an empty, frozen board from s = J on) and the counter is set to
 // {min(S, J), J + min(S, J)}.  HARVEST (gg_playouts_advance, after every rollout chunk): see the file's header.
-template <int R, bool FULLN, bool FILL>
-__global__ __launch_bounds__(kWave) void k_po_harvest(PoArgs a, int N) {
+// MOVE (gg_move_playouts_*): a refill loads the pair's root into the registers of the ply (as env_step_lat_body does), plays
+// the pair's action with lat_play_full - wave-collective, so before the finished boards part from the others - and stores
+// the child in the tracked layout; the counters are per pair.
+template <int R, bool FULLN, bool FILL, typename Args = PoArgs>
+__global__ __launch_bounds__(kWave) void k_po_harvest(Args a, int N) {
+  constexpr bool MOVE = std::is_same<Args, MpArgs>::value;
   using L = Lat<R>;
   constexpr int LPB = L::LPB, NBW = L::NBW;
   if (FULLN) N = R;
@@ -112,7 +131,7 @@ __global__ __launch_bounds__(kWave) void k_po_harvest(PoArgs a, int N) {
       uint32_t ob, ow, ab, aw;
       lat_areas_owned<R>(bl, wh, full, ob, ow, ab, aw);
       if (fin) {
-        const int64_t root = jid / a.K;
+        const int64_t root = MOVE ? jid : jid / a.K;   // (MOVE: the pair r A + a)
         if (r == 0) {
           const int d = (int)ab - (int)aw;
           const float x = (float)d - a.komi;
@@ -121,7 +140,7 @@ __global__ __launch_bounds__(kWave) void k_po_harvest(PoArgs a, int N) {
           atomicAdd(reinterpret_cast<unsigned long long *>(a.sums + 2 * root), (unsigned long long)(int64_t)d);
           atomicAdd(reinterpret_cast<unsigned long long *>(a.sums + 2 * root + 1), (unsigned long long)a.plies[s]);
         }
-        if (a.own && r < N) {
+        if (!MOVE && a.own && r < N) {
           int32_t *pb = a.own + (2 * root * N + r) * N, *pw = pb + N * N;
           for (uint32_t m = ob; m; m &= m - 1) atomicAdd(pb + __builtin_ctz(m), 1);
           for (uint32_t m = ow; m; m &= m - 1) atomicAdd(pw + __builtin_ctz(m), 1);
@@ -133,6 +152,46 @@ __global__ __launch_bounds__(kWave) void k_po_harvest(PoArgs a, int N) {
       if (lane == 0) base = atomicAdd(reinterpret_cast<unsigned long long *>(a.counter), (unsigned long long)__popcll(lead));
       const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)base), hi = __builtin_amdgcn_readfirstlane((uint32_t)(base >> 32));
       next = (int64_t)(((uint64_t)hi << 32) | lo) + __popcll(lead & ((1ull << (j * LPB)) - 1ull));
+    }
+    if constexpr (MOVE) {
+      const bool refill = fin && next < a.J;
+      uint32_t me = 0, op = 0, M = 0, inv = 0, fl = 0, Q = 0;
+      bool pass = false;
+      int64_t pair = 0, gjob = 0;
+      if (refill) {   // the root's rows in the registers of the ply, the action as Q / pass
+        const int64_t c = next / a.K;
+        pair = a.plan[c];
+        const int64_t root = pair / a.A;
+        const int act = (int)(pair - root * a.A);
+        gjob = (a.first_pair + pair) * a.K + (next - c * a.K);
+        const uint32_t *src = a.roots + root * W;
+        fl = src[5 * N] & 7u;
+        uint32_t bl = 0, wh = 0;
+        if (r < N) {
+          bl = src[r]; wh = src[N + r]; inv = src[2 * N + r];
+          M = src[3 * N + r] | src[4 * N + r];
+        }
+        me = (fl & 1u) ? wh : bl;
+        op = (fl & 1u) ? bl : wh;
+        pass = act == N * N;
+        const int ar = pass ? 0 : act / N;
+        Q = (!pass && r == ar) ? (1u << (act - ar * N)) : 0u;
+      }
+      if (__ballot(refill)) lat_play_full<R>(me, op, M, inv, fl, Q, pass, refill ? ~0u : 0u, full);
+      if (refill) {   // the child, tracked: a fresh generator, the ply count from zero (the first move is not counted)
+        const uint32_t bl = (fl & 1u) ? op : me, wh = (fl & 1u) ? me : op;
+        if (r < N) {
+          slot[r] = bl; slot[N + r] = wh; slot[2 * N + r] = inv;
+          slot[3 * N + r] = M & bl; slot[4 * N + r] = M & wh;
+        }
+        if (r == 0) {
+          slot[5 * N] = fl;
+          a.rng[s] = po_seed(a.base_seed, gjob);
+          a.plies[s] = 0;
+          a.job[s] = pair;
+        }
+        continue;
+      }
     }
     if (!fin) continue;
     if (next < a.J) {   // refill: the root's words, a fresh generator, the ply count from zero
@@ -159,6 +218,44 @@ __global__ __launch_bounds__(kWave) void k_po_harvest(PoArgs a, int N) {
         a.job[s] = -1;
       }
     }
+  }
+}
+
+// The plan of gg_move_playouts_plan, step 1: per tracked root, the number of legal first moves (the points whose invalid bit
+// is clear + the pass; none once the game has ended), one thread per root.  Step 2 is k_children_order_scan (gg_v2.h).
+static __global__ void k_mp_counts(const uint32_t *__restrict__ roots, int32_t *__restrict__ counts, int64_t R, int N) {
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i >= R) return;
+  const uint32_t *g = roots + i * (5 * N + 1);
+  const uint32_t full = (1u << N) - 1u;
+  int c = 1;
+  for (int y = 0; y < N; ++y) c += __popc(full & ~g[2 * N + y]);
+  counts[i] = (g[5 * N] & 4u) ? 0 : c;
+}
+
+// step 3: root r's legal actions in ascending order (the pass last) at plan[offsets[r] ..], one wave per root: 64 points
+// per round, the rank of each legal point by a ballot prefix.
+static __global__ void k_mp_plan(const uint32_t *__restrict__ roots, const int32_t *__restrict__ offsets,
+                                 int32_t *__restrict__ plan, int64_t R, int N) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t wave = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) / kWave;
+  const int64_t nwaves = (gridDim.x * (int64_t)blockDim.x) / kWave;
+  const int P = N * N, A = P + 1;
+  for (int64_t r = wave; r < R; r += nwaves) {
+    const uint32_t *g = roots + r * (5 * N + 1);
+    if (g[5 * N] & 4u) continue;
+    int32_t *out = plan + offsets[r];
+    const int32_t base = (int32_t)r * A;
+    int k = 0;
+    for (int p0 = 0; p0 < P; p0 += kWave) {
+      const int p = p0 + lane;
+      const int y = p / N;
+      const bool ok = p < P && !((g[2 * N + (p < P ? y : 0)] >> (p - y * N)) & 1u);
+      const uint64_t m = __ballot(ok);
+      if (ok) out[k + __popcll(m & ((1ull << lane) - 1ull))] = base + p;
+      k += __popcll(m);
+    }
+    if (lane == 0) out[k] = base + P;
   }
 }
 

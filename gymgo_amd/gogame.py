@@ -793,26 +793,9 @@ plies played) and ownership (int32 [R, 2, N, N]: per point, in how many playouts
 unless asked for)."""
 
 
-def _run_playouts(roots, R, N, K, max_plies, komi, seed, first_root, ownership, S, chunk_plies, dev):
-    """Device work of batch_playouts on tracked roots: -> (counts int32 [R, 4], sums int64 [R, 2], own or None)."""
-    L = _lib.lib()
-    J = R * K
-    W = tracked_words(N)
-    slots = torch.empty((S, W), dtype=_I32, device=dev)
-    rng = torch.empty(S, dtype=_I64, device=dev)
-    plies = torch.empty(S, dtype=_I64, device=dev)
-    job = torch.empty(S, dtype=_I64, device=dev)
-    counter = torch.empty(2, dtype=_I64, device=dev)
-    counts = torch.empty((R, 4), dtype=_I32, device=dev)
-    sums = torch.empty((R, 2), dtype=_I64, device=dev)
-    own = torch.empty((R, 2, N, N), dtype=_I32, device=dev) if ownership else None
-    stream = _lib.current_raw_stream(dev)   # torch's current stream: the counter copies below go there too
-    common = (_lib.dev_ptr(roots, _I32, 'roots'), R, N, K, int(first_root), int(seed) & (2 ** 64 - 1), int(max_plies),
-              int(chunk_plies))
-    bufs = (_lib.dev_ptr(slots, _I32, 'slots'), _lib.dev_ptr(rng, _I64, 'rng'), _lib.dev_ptr(plies, _I64, 'plies'),
-            _lib.dev_ptr(job, _I64, 'job'), S, _lib.dev_ptr(counter, _I64, 'counter'), _lib.dev_ptr(counts, _I32, 'counts'),
-            _lib.dev_ptr(sums, _I64, 'sums'), _lib.dev_ptr(own, _I32, 'ownership'))
-    _lib.check(L.gg_playouts_begin(*common, *bufs, stream), 'gg_playouts_begin')
+def _drive_playouts(advance, counter, J, S, max_plies, chunk_plies, dev, what):
+    """Host loop of batch_playouts / batch_move_playouts after the begin call: queues advance(n) (n chunks) until the
+    counter's outstanding-job count reaches zero."""
     # Every playout is harvested within max_plies / chunk_plies chunks of its start and all S slots are busy while the queue
     # holds jobs, so this many chunks always suffice; more means the device did not do what it was asked: raise, never spin.
     M = int(max_plies) // int(chunk_plies)
@@ -825,7 +808,7 @@ def _run_playouts(roots, R, N, K, max_plies, komi, seed, first_root, ownership, 
         while True:
             if queued < bound:
                 n = min(step, bound - queued)
-                _lib.check(L.gg_playouts_advance(*common[:8], float(komi), n, *bufs, stream), 'gg_playouts_advance')
+                advance(n)
                 queued += n
                 host[k].copy_(counter, non_blocking=True)
                 ev = torch.cuda.Event()
@@ -839,11 +822,60 @@ def _run_playouts(roots, R, N, K, max_plies, komi, seed, first_root, ownership, 
                 if outstanding == 0:
                     break
                 if not pending:
-                    raise _lib.GymGoNativeError('batch_playouts: %d jobs still outstanding after %d chunks (the bound for %d '
-                                                'jobs on %d slots)' % (outstanding, queued, J, S))
+                    raise _lib.GymGoNativeError('%s: %d jobs still outstanding after %d chunks (the bound for %d '
+                                                'jobs on %d slots)' % (what, outstanding, queued, J, S))
         for ev, _ in pending:   # (the pinned buffers stay alive until the copies still queued have landed)
             ev.synchronize()
+
+
+def _slot_buffers(S, N, dev):
+    """Working slots of the playout queue: (slots, rng, plies, job, counter) device tensors."""
+    return (torch.empty((S, tracked_words(N)), dtype=_I32, device=dev), torch.empty(S, dtype=_I64, device=dev),
+            torch.empty(S, dtype=_I64, device=dev), torch.empty(S, dtype=_I64, device=dev),
+            torch.empty(2, dtype=_I64, device=dev))
+
+
+def _run_playouts(roots, R, N, K, max_plies, komi, seed, first_root, ownership, S, chunk_plies, dev):
+    """Device work of batch_playouts on tracked roots: -> (counts int32 [R, 4], sums int64 [R, 2], own or None)."""
+    L = _lib.lib()
+    J = R * K
+    slots, rng, plies, job, counter = _slot_buffers(S, N, dev)
+    counts = torch.empty((R, 4), dtype=_I32, device=dev)
+    sums = torch.empty((R, 2), dtype=_I64, device=dev)
+    own = torch.empty((R, 2, N, N), dtype=_I32, device=dev) if ownership else None
+    stream = _lib.current_raw_stream(dev)   # torch's current stream: the counter copies below go there too
+    common = (_lib.dev_ptr(roots, _I32, 'roots'), R, N, K, int(first_root), int(seed) & (2 ** 64 - 1), int(max_plies),
+              int(chunk_plies))
+    bufs = (_lib.dev_ptr(slots, _I32, 'slots'), _lib.dev_ptr(rng, _I64, 'rng'), _lib.dev_ptr(plies, _I64, 'plies'),
+            _lib.dev_ptr(job, _I64, 'job'), S, _lib.dev_ptr(counter, _I64, 'counter'), _lib.dev_ptr(counts, _I32, 'counts'),
+            _lib.dev_ptr(sums, _I64, 'sums'), _lib.dev_ptr(own, _I32, 'ownership'))
+    _lib.check(L.gg_playouts_begin(*common, *bufs, stream), 'gg_playouts_begin')
+
+    def advance(n):
+        _lib.check(L.gg_playouts_advance(*common, float(komi), n, *bufs, stream), 'gg_playouts_advance')
+
+    _drive_playouts(advance, counter, J, S, max_plies, chunk_plies, dev, 'batch_playouts')
     return counts, sums, own
+
+
+def _playout_args(st, playouts, max_plies, chunk_plies, first_root):
+    """Argument checks and defaults shared by batch_playouts and batch_move_playouts -> (R, N, K, max_plies, chunk_plies)."""
+    if st.dim() != 4 or st.shape[1] != govars.NUM_CHNLS or st.shape[2] != st.shape[3]:
+        raise ValueError('batch_states must be [R, 6, N, N] (got %s)' % (tuple(st.shape),))
+    R, N, K, chunk_plies = st.shape[0], st.shape[2], int(playouts), int(chunk_plies)
+    if chunk_plies < 1:
+        raise ValueError('chunk_plies must be >= 1')
+    if max_plies is None:
+        max_plies = -(-8 * N * N // chunk_plies) * chunk_plies
+    max_plies = int(max_plies)
+    if K < 1 or max_plies < 1 or max_plies % chunk_plies or int(first_root) < 0:
+        raise ValueError('need playouts >= 1, max_plies >= 1 and a multiple of chunk_plies, first_root >= 0 (got %d, %d, %d, %d)'
+                         % (K, max_plies, chunk_plies, int(first_root)))
+    return R, N, K, max_plies, chunk_plies
+
+
+def _default_slots(slots):
+    return 256 * int(_lib.lib().gg_device_cus()) if slots is None else slots   # 19x19: k_rollout5 from 256 games per CU on
 
 
 def batch_playouts(batch_states, playouts, max_plies=None, komi=0.0, seed=20260927, first_root=0, ownership=False, slots=None,
@@ -859,21 +891,9 @@ def batch_playouts(batch_states, playouts, max_plies=None, komi=0.0, seed=202609
     8 N^2 rounded up to a multiple of chunk_plies.  The roots are not modified."""
     box = _Box(batch_states)
     st = box.t
-    if st.dim() != 4 or st.shape[1] != govars.NUM_CHNLS or st.shape[2] != st.shape[3]:
-        raise ValueError('batch_states must be [R, 6, N, N] (got %s)' % (tuple(st.shape),))
-    R, N, K, chunk_plies = st.shape[0], st.shape[2], int(playouts), int(chunk_plies)
-    if chunk_plies < 1:
-        raise ValueError('chunk_plies must be >= 1')
-    if max_plies is None:
-        max_plies = -(-8 * N * N // chunk_plies) * chunk_plies
-    max_plies = int(max_plies)
-    if K < 1 or max_plies < 1 or max_plies % chunk_plies or int(first_root) < 0:
-        raise ValueError('need playouts >= 1, max_plies >= 1 and a multiple of chunk_plies, first_root >= 0 (got %d, %d, %d, %d)'
-                         % (K, max_plies, chunk_plies, int(first_root)))
+    R, N, K, max_plies, chunk_plies = _playout_args(st, playouts, max_plies, chunk_plies, first_root)
     dev = st.device
-    if slots is None:
-        slots = 256 * int(_lib.lib().gg_device_cus())   # 19x19: k_rollout5 from 256 games per CU on
-    S = max(1, min(int(slots), R * K))
+    S = max(1, min(int(_default_slots(slots)), R * K))
     if R == 0:
         counts = torch.zeros((0, 4), dtype=_I32, device=dev)
         sums = torch.zeros((0, 2), dtype=_I64, device=dev)
@@ -895,6 +915,116 @@ def playouts(state, n, **kw):
     if box.numpy:
         out = tuple(None if t is None else t.cpu().numpy() for t in out)
     return Playouts(*out)
+
+
+# ---------------------------------------------------------------- flat Monte Carlo: playouts per legal first move
+# The statistics batch_playouts gives per root, per legal first move instead (gg_move_playouts_plan / _begin / _advance,
+# include/gymgo_amd.h): the root's legal actions are listed on the device, and a refill of the playout queue plays the
+# job's first move before its playout starts - no child is materialised, no playout runs for an illegal action.
+
+MovePlayouts = collections.namedtuple('MovePlayouts', 'legal black_wins white_wins draws unfinished margin_sum plies_sum')
+MovePlayouts.__doc__ = """Per (root, first move) results of batch_move_playouts, each [R, N*N + 1]: legal (bool), black_wins /
+white_wins / draws / unfinished (int32), margin_sum / plies_sum (int64; plies_sum does not count the first move) - as in
+Playouts, all zero where the move is not legal."""
+
+
+def _run_move_playouts(roots, R, N, K, max_plies, komi, seed, first_root, slots, chunk_plies, dev):
+    """Device work of batch_move_playouts on tracked roots: -> (legal bool [R, A], counts int32 [R, A, 4], sums [R, A, 2])."""
+    L = _lib.lib()
+    A = N * N + 1
+    stream = _lib.current_raw_stream(dev)
+    offsets = torch.empty(R + 1, dtype=_I32, device=dev)
+    plan = torch.empty(max(R * A, 1), dtype=_I32, device=dev)
+    rp = _lib.dev_ptr(roots, _I32, 'roots')
+    with torch.cuda.device(dev):
+        _lib.check(L.gg_move_playouts_plan(rp, R, N, _lib.dev_ptr(offsets, _I32, 'offsets'), _lib.dev_ptr(plan, _I32, 'plan'),
+                                           stream), 'gg_move_playouts_plan')
+        T = int(offsets[R])   # (a synchronising read, as the un-padded children do)
+    counts = torch.zeros((R, A, 4), dtype=_I32, device=dev)
+    sums = torch.zeros((R, A, 2), dtype=_I64, device=dev)
+    legal = torch.zeros((R, A), dtype=torch.bool, device=dev)
+    if T == 0:
+        return legal, counts, sums
+    legal.view(-1)[plan[:T].long()] = True
+    J = T * K
+    S = max(1, min(int(slots), J))
+    slot_t, rng, plies, job, counter = _slot_buffers(S, N, dev)
+    common = (rp, R, N, _lib.dev_ptr(plan, _I32, 'plan'), T, K, int(first_root), int(seed) & (2 ** 64 - 1), int(max_plies),
+              int(chunk_plies))
+    bufs = (_lib.dev_ptr(slot_t, _I32, 'slots'), _lib.dev_ptr(rng, _I64, 'rng'), _lib.dev_ptr(plies, _I64, 'plies'),
+            _lib.dev_ptr(job, _I64, 'job'), S, _lib.dev_ptr(counter, _I64, 'counter'), _lib.dev_ptr(counts, _I32, 'counts'),
+            _lib.dev_ptr(sums, _I64, 'sums'))
+    _lib.check(L.gg_move_playouts_begin(*common, *bufs, stream), 'gg_move_playouts_begin')
+
+    def advance(n):
+        _lib.check(L.gg_move_playouts_advance(*common, float(komi), n, *bufs, stream), 'gg_move_playouts_advance')
+
+    _drive_playouts(advance, counter, J, S, max_plies, chunk_plies, dev, 'batch_move_playouts')
+    return legal, counts, sums
+
+
+def batch_move_playouts(batch_states, playouts, max_plies=None, komi=0.0, seed=20260927, first_root=0, slots=None,
+                        chunk_plies=32):
+    """Flat Monte Carlo: `playouts` playouts after every legal first move of every root of batch_states ([R, 6, N, N]),
+    reduced per (root, action) on the device -> MovePlayouts of [R, N*N + 1] (device tensors for a device tensor, NumPy
+    arrays for NumPy input).
+
+    Action a is legal at root r when the root's game has not ended and a is the pass or its plane-3 (invalid) bit is clear.
+    A root whose game has ended has NO legal first move - its row is all False and zero (unlike children(), which keeps
+    every slot of such a state).  Playout j of the legal pair (r, a) is global job ((first_root + r) * A + a) * playouts + j
+    (A = N*N + 1): it starts from next_state(root_r, a) and is played and scored as batch_playouts plays its playouts,
+    max_plies counting the plies after the first move.  So row (r, a) equals batch_playouts(next_state(root_r, a)[None],
+    playouts, first_root=(first_root + r) * A + a, ...).  Defaults, validation and the invariance under slots, chunk_plies
+    and sharding by first_root are those of batch_playouts.  The roots are not modified."""
+    box = _Box(batch_states)
+    st = box.t
+    R, N, K, max_plies, chunk_plies = _playout_args(st, playouts, max_plies, chunk_plies, first_root)
+    dev = st.device
+    slots = _default_slots(slots)
+    A = N * N + 1
+    if R == 0:
+        legal = torch.zeros((0, A), dtype=torch.bool, device=dev)
+        counts = torch.zeros((0, A, 4), dtype=_I32, device=dev)
+        sums = torch.zeros((0, A, 2), dtype=_I64, device=dev)
+    else:
+        legal, counts, sums = _run_move_playouts(batch_track(st), R, N, K, max_plies, komi, seed, first_root, slots,
+                                                 chunk_plies, dev)
+    res = (legal, counts[..., 0], counts[..., 1], counts[..., 2], counts[..., 3], sums[..., 0], sums[..., 1])
+    if box.numpy:
+        res = tuple(t.cpu().numpy() for t in res)
+    return MovePlayouts(*res)
+
+
+def move_playouts(state, n, **kw):
+    """batch_move_playouts of one state [6, N, N] -> MovePlayouts of [N*N + 1] vectors."""
+    box = _Box(state)
+    res = batch_move_playouts(box.t[None], n, **kw)
+    out = tuple(t[0] for t in res)
+    if box.numpy:
+        out = tuple(t.cpu().numpy() for t in out)
+    return MovePlayouts(*out)
+
+
+def flat_mc_actions(batch_states, playouts, **kw):
+    """The flat Monte Carlo move of every root -> int64 [R]: the legal action with the most (mover's wins - mover's losses)
+    over batch_move_playouts(batch_states, playouts, **kw), the mover being the root's turn (plane 2); ties go to the lowest
+    action, a root without a legal move gives -1."""
+    box = _Box(batch_states)
+    res = batch_move_playouts(box.t, playouts, **kw)
+    st = box.t
+    R = st.shape[0]
+    if R == 0:
+        act = torch.zeros(0, dtype=_I64, device=st.device)
+    else:
+        bw, ww = res.black_wins.to(_I64), res.white_wins.to(_I64)
+        white = st[:, govars.TURN_CHNL, 0, 0].to(torch.bool)[:, None]
+        score = torch.where(white, ww - bw, bw - ww)
+        score = torch.where(res.legal, score, torch.full_like(score, -(2 ** 62)))
+        best = score.max(dim=1, keepdim=True).values
+        idx = torch.arange(score.shape[1], dtype=_I64, device=st.device).expand_as(score)
+        act = torch.where(score == best, idx, torch.full_like(idx, score.shape[1])).min(dim=1).values   # the lowest of the best
+        act = torch.where(res.legal.any(dim=1), act, torch.full_like(act, -1))
+    return act.cpu().numpy() if box.numpy else act
 
 # ---------------------------------------------------------------- policy-weighted sampling on the device
 # gogame.random_weighted_action / random_action (gym_go/gogame.py:385-404) for every game of a batch: what a self-play loop

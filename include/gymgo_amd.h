@@ -384,6 +384,37 @@ int32_t gg_playouts_advance(const uint32_t *roots, int64_t R, int32_t N, int32_t
                             int64_t *plies, int64_t *job, int64_t S, int64_t *counter, int32_t *counts, int64_t *sums,
                             int32_t *ownership, void *hip_stream);
 
+/*
+ * Flat Monte Carlo: the playouts above per legal FIRST MOVE.  A = N*N + 1.  Action a is legal at root r when the root's game
+ * has not ended and a is the pass (a = N*N) or point a's invalid bit is clear: exactly the moves the tracked step accepts.
+ * A root whose game has ended has NO legal first move (unlike gg_batch_children, which keeps all A slots of such a parent).
+ * Playout j of the legal pair (r, a) is global job p = ((first_root + r) A + a) K + j: it starts from the child
+ * next_state(roots[r], a) with the generator gg_rng_seed(base_seed, first_game = p) and is then played and scored exactly as
+ * a playout of gg_playouts_* (max_plies counts the plies AFTER the first move; a first move that ends the game - a pass
+ * after a pass - gives a finished playout of 0 plies).  So row (r, a) equals gg_playouts_* of that child alone with
+ * first_root = (first_root + r) A + a.  No ownership output.
+ *   gg_move_playouts_plan     offsets int32 [R+1] = exclusive prefix sums of the number of legal first moves per root
+ *                             (offsets[R] = T, the number of legal pairs: read it back before the calls below);
+ *                             plan int32 [R*A]: plan[offsets[r] + k] = r A + a_k, a_k root r's k-th legal action in
+ *                             ascending order (the pass last); only the first T entries are written.
+ *                             GG_E_BADSIZE: N outside [2, 19], R < 0, R*A does not fit an int32; GG_E_NULLPTR.
+ *   gg_move_playouts_begin / gg_move_playouts_advance: the protocol of gg_playouts_begin / advance on J = T K jobs.  Local
+ *                             job q is playout q % K of the pair plan[q / K].  Outputs per pair, indexed by r A + a, zero for
+ *                             the illegal ones: counts int32 [R][A][4], sums int64 [R][A][2] (as above; Σ plies without the
+ *                             first move).  (ceil(T K / S) + 1) * max_plies / chunk_plies chunks always suffice.
+ * The argument checks are those of gg_playouts_*, in the same order, with GG_E_BADSIZE also for R*A beyond an int32 and
+ * T outside [0, R*A]; plan is required.
+ */
+int32_t gg_move_playouts_plan(const uint32_t *roots, int64_t R, int32_t N, int32_t *offsets, int32_t *plan, void *hip_stream);
+int32_t gg_move_playouts_begin(const uint32_t *roots, int64_t R, int32_t N, const int32_t *plan, int64_t T, int32_t K,
+                               int64_t first_root, uint64_t base_seed, int32_t max_plies, int32_t chunk_plies, uint32_t *slots,
+                               uint64_t *rng, int64_t *plies, int64_t *job, int64_t S, int64_t *counter, int32_t *counts,
+                               int64_t *sums, void *hip_stream);
+int32_t gg_move_playouts_advance(const uint32_t *roots, int64_t R, int32_t N, const int32_t *plan, int64_t T, int32_t K,
+                                 int64_t first_root, uint64_t base_seed, int32_t max_plies, int32_t chunk_plies, float komi,
+                                 int32_t chunks, uint32_t *slots, uint64_t *rng, int64_t *plies, int64_t *job, int64_t S,
+                                 int64_t *counter, int32_t *counts, int64_t *sums, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
