@@ -22,7 +22,8 @@ EXPORTS = (
     'gg_batch_untrack_states', 'gg_batch_rollout_tracked', 'gg_batch_play_moves_tracked', 'gg_batch_env_step_tracked',
     'gg_rng_seed', 'gg_batch_env_step_tracked_weighted', 'gg_batch_sample_weighted', 'gg_batch_sample_weighted_rows',
     'gg_batch_symmetry', 'gg_batch_symmetry_rows', 'gg_batch_env_step_scored', 'gg_playouts_begin', 'gg_playouts_advance',
-    'gg_move_playouts_plan', 'gg_move_playouts_begin', 'gg_move_playouts_advance',
+    'gg_move_playouts_plan', 'gg_move_playouts_begin', 'gg_move_playouts_advance', 'gg_uct_begin', 'gg_uct_select',
+    'gg_uct_backup',
 )
 
 _vp, _i64, _i32, _u64 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_uint64
@@ -71,6 +72,9 @@ _SIGNATURES = {
                                 _vp, _vp], _i32),
     'gg_move_playouts_advance': ([_vp, _i64, _i32, _vp, _i64, _i32, _i64, _u64, _i32, _i32, ctypes.c_float, _i32, _vp, _vp, _vp,
                                   _vp, _i64, _vp, _vp, _vp, _vp], _i32),
+    'gg_uct_begin': ([_vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
+    'gg_uct_select': ([_i64, _i32, _i32, _i32, ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
+    'gg_uct_backup': ([_i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
 }
 
 _lib = None

@@ -29,6 +29,7 @@
 #include "gg_sym.h"
 #include "gg_ns16.h"
 #include "gg_po.h"
+#include "gg_uct.h"
 #include "gymgo_amd.h"
 
 namespace gg {
@@ -460,6 +461,16 @@ static void launch_mp(const MpArgs &m, int32_t N, int cus, hipStream_t s) {
 #define GG_K(R, F) k_po_harvest<R, F, FILL, MpArgs><<<grid, kWave, 0, s>>>(m, N)
   GG_DISPATCH_N(N);
 #undef GG_K
+}
+
+// ---- UCT tree search (gg_uct.h): the checks of po_args on the tree's sizes, in the same order
+static int32_t uct_args(UctArgs &u, int64_t R, int32_t N, int32_t I, int32_t K, double c) {
+  if (N < 2 || N > GG_MAX_BOARD || R < 0) return GG_E_BADSIZE;
+  if (I < 1 || K < 1 || !(c >= 0.0 && c <= __DBL_MAX__)) return GG_E_BADARG;
+  if ((int64_t)I * K > 0x7FFFFFFF) return GG_E_BADSIZE;   // the root's n = I K is an int32
+  u = UctArgs{};
+  u.R = R; u.N = N; u.I = I; u.K = K; u.c = c;
+  return 0;
 }
 }  // namespace
 
@@ -1256,6 +1267,56 @@ int32_t gg_move_playouts_advance(const uint32_t *roots, int64_t R, int32_t N, co
     if (int32_t e = (int32_t)hipGetLastError()) return e;
   }
   return 0;
+}
+
+int32_t gg_uct_begin(const uint32_t *roots, int64_t R, int32_t N, int32_t I, int32_t K, uint32_t *boards, int32_t *child,
+                     int32_t *links, int32_t *stats, int32_t *nodes, void *hip_stream) {
+  UctArgs u;
+  if (int32_t e = uct_args(u, R, N, I, K, 0.0)) return e;
+  if (!roots || !boards || !child || !links || !stats || !nodes) return GG_E_NULLPTR;
+  if (R == 0) return 0;
+  u.boards = boards; u.child = child; u.links = links; u.stats = stats; u.nodes = nodes;
+  OnDeviceOf on_dev(boards);
+  hipStream_t s = (hipStream_t)hip_stream;
+  const int64_t NN = (int64_t)I + 1, A = (int64_t)N * N + 1;
+  hipError_t err = hipMemsetAsync(child, 0xFF, sizeof(int32_t) * R * NN * A, s);   // -1: no child
+  if (err == hipSuccess) err = hipMemsetAsync(links, 0xFF, sizeof(int32_t) * R * NN * 2, s);
+  if (err == hipSuccess) err = hipMemsetAsync(stats, 0, sizeof(int32_t) * R * NN * 4, s);
+  if (err != hipSuccess) return (int32_t)err;
+  const int64_t words = R * (5 * N + 1);
+  k_uct_begin<<<(unsigned)((words + 255) / 256), 256, 0, s>>>(roots, u);
+  return (int32_t)hipGetLastError();
+}
+
+int32_t gg_uct_select(int64_t R, int32_t N, int32_t I, int32_t K, double c, const double *log_table, const uint32_t *boards,
+                      int32_t *child, int32_t *links, int32_t *stats, int32_t *nodes, uint32_t *leaf, int32_t *move,
+                      int32_t *leaf_id, void *hip_stream) {
+  UctArgs u;
+  if (int32_t e = uct_args(u, R, N, I, K, c)) return e;
+  if (!log_table || !boards || !child || !links || !stats || !nodes || !leaf || !move || !leaf_id) return GG_E_NULLPTR;
+  if (R == 0) return 0;
+  u.boards = const_cast<uint32_t *>(boards); u.child = child; u.links = links; u.stats = stats; u.nodes = nodes;
+  u.leaf = leaf; u.move = move; u.leaf_id = leaf_id; u.log_table = log_table;
+  OnDeviceOf on_dev(leaf);
+  hipStream_t s = (hipStream_t)hip_stream;
+  k_uct_select<<<grid_for(on_dev.cus(), (R + 3) / 4), 4 * kWave, 0, s>>>(u);
+  return (int32_t)hipGetLastError();
+}
+
+int32_t gg_uct_backup(int64_t R, int32_t N, int32_t I, int32_t K, const int32_t *counts, const int64_t *sums, int64_t *totals,
+                      uint32_t *boards, const int32_t *links, int32_t *stats, const uint32_t *leaf, const int32_t *move,
+                      const int32_t *leaf_id, void *hip_stream) {
+  UctArgs u;
+  if (int32_t e = uct_args(u, R, N, I, K, 0.0)) return e;
+  if (!counts || !sums || !boards || !links || !stats || !leaf || !move || !leaf_id) return GG_E_NULLPTR;
+  if (R == 0) return 0;
+  u.boards = boards; u.links = const_cast<int32_t *>(links); u.stats = stats; u.leaf = const_cast<uint32_t *>(leaf);
+  u.move = const_cast<int32_t *>(move); u.leaf_id = const_cast<int32_t *>(leaf_id); u.counts = counts; u.sums = sums;
+  u.totals = totals;
+  OnDeviceOf on_dev(leaf);
+  hipStream_t s = (hipStream_t)hip_stream;
+  k_uct_backup<<<grid_for(on_dev.cus(), (R + 3) / 4), 4 * kWave, 0, s>>>(u);
+  return (int32_t)hipGetLastError();
 }
 
 }  // extern "C"

@@ -10,6 +10,7 @@ Errors: an illegal move raises AssertionError (gym_go/gogame.py:59, :117); actio
 arguments raises RuntimeError (:196).
 """
 import collections
+import math
 
 import numpy as np
 import torch
@@ -835,13 +836,17 @@ def _slot_buffers(S, N, dev):
             torch.empty(2, dtype=_I64, device=dev))
 
 
-def _run_playouts(roots, R, N, K, max_plies, komi, seed, first_root, ownership, S, chunk_plies, dev):
-    """Device work of batch_playouts on tracked roots: -> (counts int32 [R, 4], sums int64 [R, 2], own or None)."""
+def _playout_buffers(R, S, N, dev):
+    """Everything _run_playouts writes for R roots on S slots: (slots, rng, plies, job, counter, counts, sums)."""
+    return _slot_buffers(S, N, dev) + (torch.empty((R, 4), dtype=_I32, device=dev), torch.empty((R, 2), dtype=_I64, device=dev))
+
+
+def _run_playouts(roots, R, N, K, max_plies, komi, seed, first_root, ownership, S, chunk_plies, dev, buffers=None):
+    """Device work of batch_playouts on tracked roots: -> (counts int32 [R, 4], sums int64 [R, 2], own or None).
+    buffers: _playout_buffers(R, S, N, dev) to reuse (a search evaluates its leaves with the same buffers every iteration)."""
     L = _lib.lib()
     J = R * K
-    slots, rng, plies, job, counter = _slot_buffers(S, N, dev)
-    counts = torch.empty((R, 4), dtype=_I32, device=dev)
-    sums = torch.empty((R, 2), dtype=_I64, device=dev)
+    slots, rng, plies, job, counter, counts, sums = buffers if buffers is not None else _playout_buffers(R, S, N, dev)
     own = torch.empty((R, 2, N, N), dtype=_I32, device=dev) if ownership else None
     stream = _lib.current_raw_stream(dev)   # torch's current stream: the counter copies below go there too
     common = (_lib.dev_ptr(roots, _I32, 'roots'), R, N, K, int(first_root), int(seed) & (2 ** 64 - 1), int(max_plies),
@@ -1024,6 +1029,149 @@ def flat_mc_actions(batch_states, playouts, **kw):
         idx = torch.arange(score.shape[1], dtype=_I64, device=st.device).expand_as(score)
         act = torch.where(score == best, idx, torch.full_like(idx, score.shape[1])).min(dim=1).values   # the lowest of the best
         act = torch.where(res.legal.any(dim=1), act, torch.full_like(act, -1))
+    return act.cpu().numpy() if box.numpy else act
+
+
+# ---------------------------------------------------------------- UCT tree search over the playouts
+# R independent searches (gg_uct_begin / gg_uct_select / gg_uct_backup, include/gymgo_amd.h): the trees live on the device,
+# each iteration selects and expands one leaf per root, evaluates the R leaves with batch_playouts' queue and backs the
+# counts up - the host only queues launches and waits for the playout queue to drain.
+
+Uct = collections.namedtuple('Uct', 'legal visits black_wins white_wins draws root_visits unfinished plies_sum nodes tree')
+Uct.__doc__ = """Results of batch_uct per root: legal (bool [R, A], A = N*N + 1), visits / black_wins / white_wins / draws
+(int32 [R, A]: the stats of the root's children, 0 where there is none), root_visits (int32 [R]), unfinished / plies_sum
+(int64 [R]: over every playout of the search), nodes (int32 [R]: tree nodes in use) and tree (UctTree or None)."""
+UctTree = collections.namedtuple('UctTree', 'parent action visits black_wins white_wins draws')
+UctTree.__doc__ = """The whole tree of every root, each field int32 [R, iterations + 1] indexed by node (node 0 = the root;
+parent / action -1 at the root and at unused nodes, whose stats are 0)."""
+
+_JOB_MUL, _GOLDEN_GAMMA, _M64 = 0xD1342543DE82EF95, 0x9E3779B97F4A7C15, 2 ** 64 - 1
+
+
+def _uct_seed(seed, i):
+    """Base seed of iteration i's playouts: what gg_rng_seed(base_seed=seed, first_game=i) writes (rng_seed's generator)."""
+    return (((int(seed) & _M64) ^ ((int(i) * _JOB_MUL) & _M64)) + _GOLDEN_GAMMA) & _M64
+
+
+def _uct_args(iterations, playouts, c):
+    I, K, c = int(iterations), int(playouts), float(c)
+    if I < 1 or not math.isfinite(c) or c < 0 or I * K >= 2 ** 31:
+        raise ValueError('need iterations >= 1, c >= 0 and finite, iterations * playouts < 2^31 (got %d, %r, %d)' % (I, c, I * K))
+    return I, c
+
+
+def _legal_roots(st):
+    """bool [R, A]: the pass and every point whose plane-3 bit is clear, nothing for a root whose game has ended."""
+    R, N = st.shape[0], st.shape[2]
+    legal = torch.cat([st[:, govars.INVD_CHNL].reshape(R, N * N) == 0, torch.ones((R, 1), dtype=torch.bool, device=st.device)], 1)
+    ended = st[:, govars.DONE_CHNL].reshape(R, N * N).any(dim=1).bool()   # (any() of uint8 is uint8)
+    return legal & ~ended[:, None]
+
+
+def _run_uct(roots, R, N, I, K, c, max_plies, komi, seed, first_root, S, chunk_plies, dev):
+    """Device work of batch_uct on tracked roots -> (child int32 [R, I+1, A], links [R, I+1, 2], stats [R, I+1, 4],
+    nodes [R], totals int64 [R, 2])."""
+    L = _lib.lib()
+    W, A, NN = tracked_words(N), N * N + 1, I + 1
+    boards = torch.empty((R, NN, W), dtype=_I32, device=dev)
+    child = torch.empty((R, NN, A), dtype=_I32, device=dev)
+    links = torch.empty((R, NN, 2), dtype=_I32, device=dev)
+    stats = torch.empty((R, NN, 4), dtype=_I32, device=dev)
+    nodes = torch.empty(R, dtype=_I32, device=dev)
+    leaf = torch.empty((R, W), dtype=_I32, device=dev)
+    move = torch.empty(R, dtype=_I32, device=dev)
+    leaf_id = torch.empty(R, dtype=_I32, device=dev)
+    totals = torch.zeros((R, 2), dtype=_I64, device=dev)
+    with np.errstate(divide='ignore'):   # (L[0] = -inf is never read: a node with children has n >= K)
+        log_table = torch.from_numpy(np.log(np.arange(NN, dtype=np.float64) * K)).to(dev)
+    pbufs = _playout_buffers(R, S, N, dev)
+    counts, sums = pbufs[5], pbufs[6]
+    stream = _lib.current_raw_stream(dev)
+    p = lambda t, dt, name: _lib.dev_ptr(t, dt, name)
+    tree = (p(boards, _I32, 'boards'), p(child, _I32, 'child'), p(links, _I32, 'links'), p(stats, _I32, 'stats'),
+            p(nodes, _I32, 'nodes'))
+    lp, mp, ip = p(leaf, _I32, 'leaf'), p(move, _I32, 'move'), p(leaf_id, _I32, 'leaf_id')
+    _lib.check(L.gg_uct_begin(p(roots, _I32, 'roots'), R, N, I, K, *tree, stream), 'gg_uct_begin')
+    for i in range(I):
+        _lib.check(L.gg_uct_select(R, N, I, K, c, _lib.dev_ptr(log_table, torch.float64, 'log_table'), *tree, lp, mp, ip,
+                                   stream), 'gg_uct_select')
+        _lib.check(L.gg_batch_play_moves_tracked(lp, mp, None, R, N, 1, stream), 'gg_batch_play_moves_tracked')
+        _run_playouts(leaf, R, N, K, max_plies, komi, _uct_seed(seed, i), first_root, False, S, chunk_plies, dev, pbufs)
+        _lib.check(L.gg_uct_backup(R, N, I, K, p(counts, _I32, 'counts'), p(sums, _I64, 'sums'), p(totals, _I64, 'totals'),
+                                   tree[0], tree[2], tree[3], lp, mp, ip, stream), 'gg_uct_backup')
+    return child, links, stats, nodes, totals
+
+
+def batch_uct(batch_states, iterations, playouts, c=math.sqrt(2), max_plies=None, komi=0.0, seed=20260927, first_root=0,
+              slots=None, chunk_plies=32, tree=False):
+    """UCT search of `iterations` iterations from every root of batch_states ([R, 6, N, N]), the leaves evaluated with
+    `playouts` playouts each -> Uct (device tensors for a device tensor, NumPy arrays for NumPy input).
+
+    Each root has its own tree with room for iterations + 1 nodes.  Iteration i, per root: select from the root - at a node
+    whose game has ended, that node is the leaf; else the lowest legal action (batch_move_playouts' rule: the pass and every
+    point whose plane-3 bit is clear) without a child is expanded into a new node, the leaf; else descend to the child of the
+    largest U = (2 w + d) / (2 n) + c * sqrt(log(n_parent) / n) (w: the wins of the colour to move at the parent; float64,
+    in this order, no fused multiply-add; ties to the lowest action).  The R leaves are evaluated by exactly
+    batch_playouts(leaves, playouts, max_plies, komi, seed=s_i, first_root=first_root), s_i = rng_seed(.., seed,
+    first_game=i)[0]'s value, and n += playouts, the wins and draws are added on the path from the leaf to the root.
+    So a root that has not ended gets root_visits = iterations * playouts; an ended root evaluates itself every iteration.
+    Defaults and validation are those of batch_playouts, plus iterations >= 1, c >= 0 and finite, iterations * playouts
+    < 2^31; results do not depend on `slots` or `chunk_plies`, and shards by first_root concatenate to the whole.
+    tree=True also returns the whole tree (UctTree).  The roots are not modified.
+
+    Device memory of the tree: R * (iterations + 1) * (4 (5N + 1) + 4 (N^2 + 1) + 24) bytes (boards, child tables, links and
+    stats: 1 856 bytes per node at 19x19, 124 MB for 1 024 roots x 64 iterations), plus the playout slots of batch_playouts."""
+    box = _Box(batch_states)
+    st = box.t
+    R, N, K, max_plies, chunk_plies = _playout_args(st, playouts, max_plies, chunk_plies, first_root)
+    I, c = _uct_args(iterations, K, c)
+    dev = st.device
+    A = N * N + 1
+    legal = _legal_roots(st)
+    if R == 0:
+        child = torch.full((0, I + 1, A), -1, dtype=_I32, device=dev)
+        links = torch.full((0, I + 1, 2), -1, dtype=_I32, device=dev)
+        stats = torch.zeros((0, I + 1, 4), dtype=_I32, device=dev)
+        nodes = torch.zeros(0, dtype=_I32, device=dev)
+        totals = torch.zeros((0, 2), dtype=_I64, device=dev)
+    else:
+        S = max(1, min(int(_default_slots(slots)), R * K))
+        child, links, stats, nodes, totals = _run_uct(batch_track(st), R, N, I, K, c, max_plies, komi, seed, first_root, S,
+                                                      chunk_plies, dev)
+    rc = child[:, 0, :]
+    kid = torch.gather(stats, 1, rc.clamp(min=0).long()[..., None].expand(R, A, 4))
+    kid = torch.where((rc >= 0)[..., None], kid, torch.zeros_like(kid))
+    res = [legal, kid[..., 0], kid[..., 1], kid[..., 2], kid[..., 3], stats[:, 0, 0], totals[:, 0], totals[:, 1], nodes]
+    whole = (links[..., 0], links[..., 1], stats[..., 0], stats[..., 1], stats[..., 2], stats[..., 3]) if tree else None
+    if box.numpy:
+        res = [t.cpu().numpy() for t in res]
+        whole = None if whole is None else tuple(t.cpu().numpy() for t in whole)
+    return Uct(*res, tree=None if whole is None else UctTree(*whole))
+
+
+def uct(state, iterations, playouts, **kw):
+    """batch_uct of one state [6, N, N] -> Uct of [N*N + 1] vectors and scalars (tree fields [iterations + 1])."""
+    box = _Box(state)
+    res = batch_uct(box.t[None], iterations, playouts, **kw)
+    out = [t[0] for t in res[:-1]]
+    whole = None if res.tree is None else [t[0] for t in res.tree]
+    if box.numpy:
+        out = [t.cpu().numpy() for t in out]
+        whole = None if whole is None else [t.cpu().numpy() for t in whole]
+    return Uct(*out, tree=None if whole is None else UctTree(*whole))
+
+
+def uct_actions(batch_states, iterations, playouts, **kw):
+    """The UCT move of every root -> int64 [R]: the legal root child with the most visits after batch_uct(batch_states,
+    iterations, playouts, **kw); ties go to the lowest action, a root without a legal move gives -1."""
+    box = _Box(batch_states)
+    res = batch_uct(box.t, iterations, playouts, **kw)
+    st = box.t
+    v = torch.where(res.legal, res.visits.to(_I64), torch.full_like(res.visits, -1, dtype=_I64))
+    idx = torch.arange(v.shape[1], dtype=_I64, device=st.device).expand_as(v)
+    act = torch.where(v == v.max(dim=1, keepdim=True).values, idx, torch.full_like(idx, v.shape[1])).min(dim=1).values \
+        if v.shape[0] else torch.zeros(0, dtype=_I64, device=st.device)
+    act = torch.where(res.legal.any(dim=1), act, torch.full_like(act, -1))
     return act.cpu().numpy() if box.numpy else act
 
 # ---------------------------------------------------------------- policy-weighted sampling on the device

@@ -415,6 +415,43 @@ int32_t gg_move_playouts_advance(const uint32_t *roots, int64_t R, int32_t N, co
                                  int32_t chunks, uint32_t *slots, uint64_t *rng, int64_t *plies, int64_t *job, int64_t S,
                                  int64_t *counter, int32_t *counts, int64_t *sums, void *hip_stream);
 
+/*
+ * UCT tree search over the playouts above, R independent searches of I iterations, the trees on the device.  A = N*N + 1.
+ * Each root r has a tree with room for I + 1 nodes (node 0 = the root); a node holds its tracked board, parent / action
+ * (-1 at the root), integer stats n / black wins / white wins / draws and a child table child[a] (-1: not expanded).
+ * The legal actions of node x: none once x's game has ended, else the pass and every point whose invalid bit is clear.
+ * Iteration i, per root:
+ *   1. select (gg_uct_select): from x = 0, while x's game has not ended: if some legal a has no child, the lowest such a
+ *      is expanded - node y = nodes[r]++ with parent x, action a, zero stats, child_x[a] = y - and y is the leaf;
+ *      otherwise x = child_x[a*], a* the legal action of the largest U (ties to the lowest action) with, for c = child_x[a]
+ *      and w = black wins of c if black is to move at x (flag bit 0 clear), else white wins of c:
+ *        U = (2 w + d_c) / (2 n_c) + C * sqrt(log_table[n_x / K] / n_c)
+ *      in float64, each operation rounded to nearest in this order, no fused multiply-add.  A node whose game has ended
+ *      is the leaf itself.  Writes leaf[r] = the board of the node the walk stopped at (the new node's parent, or the
+ *      ended node), move[r] = the expanded action (-1: none), leaf_id[r] = the leaf.
+ *   2. the caller plays move on leaf (gg_batch_play_moves_tracked(leaf, move, NULL, R, N, T = 1): -1 is out of range, the
+ *      board stays put) and evaluates leaf with gg_playouts_begin / _advance (roots = leaf, K playouts per root).
+ *   3. backup (gg_uct_backup): stores leaf[r] as node y's board when move[r] >= 0, then adds K to n and counts[r][0..2] to
+ *      the black wins / white wins / draws of every node from leaf_id[r] up to the root; totals (nullable, int64 [R][2],
+ *      zeroed by the caller) += counts[r][3] (unfinished), sums[r][1] (plies).
+ * Buffers, caller-owned (W = gg_tracked_words(N)): boards uint32 [R][I+1][W], child int32 [R][I+1][A], links int32 [R][I+1][2]
+ * (parent, action; -1 / -1 at unused nodes), stats int32 [R][I+1][4] (n, black wins, white wins, draws), nodes int32 [R];
+ * leaf uint32 [R][W], move int32 [R], leaf_id int32 [R]; log_table double [I+1] = log(t K), t = 0 .. I.
+ *   gg_uct_begin   node 0 = roots[r] (tracked, read only), every child table -1, links -1, stats 0, nodes = 1.
+ * A select without room (more than I selects after a begin) evaluates the node it stopped at: no write beyond a tree.
+ * The argument checks come before any device work, in the order of gg_playouts_*: GG_E_BADSIZE: N outside [2, 19],
+ * R < 0; GG_E_BADARG: I < 1, K < 1, C negative or not finite (select); GG_E_BADSIZE: I K >= 2^31; GG_E_NULLPTR: a buffer
+ * other than totals is NULL.  R = 0 is no work.  The same R, N, I, K go to every call of one search.
+ */
+int32_t gg_uct_begin(const uint32_t *roots, int64_t R, int32_t N, int32_t I, int32_t K, uint32_t *boards, int32_t *child,
+                     int32_t *links, int32_t *stats, int32_t *nodes, void *hip_stream);
+int32_t gg_uct_select(int64_t R, int32_t N, int32_t I, int32_t K, double c, const double *log_table, const uint32_t *boards,
+                      int32_t *child, int32_t *links, int32_t *stats, int32_t *nodes, uint32_t *leaf, int32_t *move,
+                      int32_t *leaf_id, void *hip_stream);
+int32_t gg_uct_backup(int64_t R, int32_t N, int32_t I, int32_t K, const int32_t *counts, const int64_t *sums, int64_t *totals,
+                      uint32_t *boards, const int32_t *links, int32_t *stats, const uint32_t *leaf, const int32_t *move,
+                      const int32_t *leaf_id, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

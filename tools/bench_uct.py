@@ -1,0 +1,85 @@
+"""UCT tree search (gogame.batch_uct) against I back-to-back batch_playouts calls of the same R and K; prints one JSON line per
+root count.
+
+  python tools/bench_uct.py [--roots 256 1024] [--k 256] [--iters 64] [--size 19] [--plies 120] [--reps 3]
+
+Workload: R mid-game roots (random play from the empty board, `--plies` plies), komi 7.5, default slot count, I iterations
+of K playouts per leaf.  In one process, alternating, median of `--reps` runs each:
+  (a) batch_uct(roots, I, K);
+  (b) I calls of batch_playouts(roots, K, seed=i): the same playout volume with no tree (the roots as leaves).
+ratio = time (b) / time (a) per playout: what the select, one-move step and backup launches - and the host loop around
+them - cost on top of the playouts (1.0: nothing).  Both drain the playout queue once per iteration.  Plies are the plies
+the playouts played (plies_sum).  For the device-time split of k_uct_select, the one-move step (k_play_moves*) and
+k_uct_backup, run once under `rocprofv3 --kernel-trace --stats -- python tools/bench_uct.py --reps 1`.
+"""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def _timed(fn):
+    import torch
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    out = fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) * 1e-3, out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--roots', type=int, nargs='+', default=[256, 1024])
+    ap.add_argument('--k', type=int, default=256)
+    ap.add_argument('--iters', type=int, default=64)
+    ap.add_argument('--size', type=int, default=19)
+    ap.add_argument('--plies', type=int, default=120)
+    ap.add_argument('--reps', type=int, default=3)
+    args = ap.parse_args()
+
+    import torch
+    from gymgo_amd import gogame, _lib
+    torch.cuda.set_device(0)
+    N, K, I = args.size, args.k, args.iters
+    for R in args.roots:
+        roots = gogame.batch_init_state(R, N, device='cuda:0')
+        gogame.batch_rollout(roots, gogame.rng_seed(R, 17), args.plies, auto_reset=False)   # mid-game roots
+        kw = dict(komi=7.5)
+
+        def run_a():
+            return gogame.batch_uct(roots, I, K, seed=1, **kw)
+
+        def run_b():
+            return [gogame.batch_playouts(roots, K, seed=i, **kw) for i in range(I)]
+
+        ref = run_a()   # warm-up
+        run_b()
+        assert bool((ref.root_visits == I * K).all())
+        plies_a = int(ref.plies_sum.sum())
+        ta, tb, plies_b = [], [], 0
+        for _ in range(args.reps):   # alternating
+            ta.append(_timed(run_a)[0])
+            t, outs = _timed(run_b)
+            tb.append(t)
+            plies_b = sum(int(o.plies_sum.sum()) for o in outs)
+        ta.sort()
+        tb.sort()
+        sa, sb = ta[len(ta) // 2], tb[len(tb) // 2]
+        P = R * K * I
+        res = {'metric': 'uct_playouts_per_s', 'size': N, 'roots': R, 'k': K, 'iterations': I, 'root_plies': args.plies,
+               'playouts': P, 'cus': int(_lib.lib().gg_device_cus()), 'jobs_per_slot': R * K / (256 * int(_lib.lib().gg_device_cus())),
+               'seconds_uct': sa, 'seconds_playouts': sb, 'iterations_per_s': I / sa, 'playouts_per_s': P / sa,
+               'plies_per_s': plies_a / sa, 'mean_plies_uct': plies_a / P, 'playouts_per_s_plain': P / sb,
+               'plies_per_s_plain': plies_b / sb, 'mean_plies_plain': plies_b / P,
+               'ratio': (P / sa) / (P / sb), 'ratio_plies': (plies_a / sa) / (plies_b / sb),
+               'mean_nodes': float(ref.nodes.float().mean()), 'reps': args.reps}
+        print(json.dumps(res), flush=True)
+
+
+if __name__ == '__main__':
+    main()
