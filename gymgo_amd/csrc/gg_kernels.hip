@@ -2,8 +2,10 @@
 // grid sizing and dispatch on the board-size template.  The kernels live in gg_common.h (shared building blocks),
 // gg_v2.h (per-ply kernels: two boards per wavefront, every liberty class from scratch), gg_v4.h (multi-ply kernels:
 // sixteen boards per wavefront, liberty classes carried from ply to ply), gg_aux.h (stand-alone sampler and capture
-// resolution), gg_ws.h (policy-weighted sampling), gg_sym.h (batched symmetries) and gg_ns16.h (the per-ply kernels for
-// big batches).  Which kernel serves an entry point depends on the arguments only (board size, batch size, plies per
+// resolution), gg_ws.h (policy-weighted sampling), gg_sym.h (batched symmetries), gg_ns16.h (the per-ply kernels for
+// big batches), gg_po.h (Monte Carlo playouts: the fill / harvest kernel of the playout queue and the plan of legal first
+// moves) and gg_uct.h (UCT tree search: begin, select, backup).  The playout and search entry points launch the multi-ply
+// kernels through gg_batch_rollout_tracked, whose launches live in the other three translation units.  Which kernel serves an entry point depends on the arguments only (board size, batch size, plies per
 // launch) and on the CU count the grids are sized for - the device's own, or GYMGO_AMD_CUS (forced_cus below), the one
 // environment variable the shipped build reads; results depend on neither.  Mutable global state, all of it performance-only
 // (no result depends on any of it): g_cus (CU count per device, relaxed atomics: racing first callers store the same value), the
@@ -411,65 +413,95 @@ uint32_t recip16(int32_t N) {
   } while (0)
 
 
-// ---- batched Monte Carlo playouts (gg_po.h): argument checks of both entry points, then the launch of the fill /
-// harvest kernel for the board's row capacity
-static int32_t po_args(PoArgs &a, const uint32_t *roots, int64_t R, int32_t N, int32_t K, int64_t first_root,
-                       uint64_t base_seed, int32_t max_plies, int32_t chunk_plies, float komi, uint32_t *slots, uint64_t *rng,
-                       int64_t *plies, int64_t *job, int64_t S, int64_t *counter, int32_t *counts, int64_t *sums,
-                       int32_t *ownership) {
+// ---- the playout queue (gg_po.h) behind gg_playouts_* (PoArgs, one result cell per root) and gg_move_playouts_* (MpArgs,
+// cells = A result cells per root, one per first move).  po_args: the argument checks both families share, in the order
+// the header documents, then the fill.  units = the roots (pairs) the jobs are counted over: J = units K.  The first-move
+// family's own checks arrive evaluated (mp_args) and are looked at where they stand in that order.
+static int32_t po_args(PoArgs &a, int64_t cells, int64_t units, bool own_sizes_ok, bool own_ptrs_ok, const uint32_t *roots, int64_t R,
+                       int32_t N, int32_t K, int64_t first_root, uint64_t base_seed, int32_t max_plies, int32_t chunk_plies,
+                       float komi, uint32_t *slots, uint64_t *rng, int64_t *plies, int64_t *job, int64_t S, int64_t *counter,
+                       int32_t *counts, int64_t *sums, int32_t *ownership) {
   if (N < 2 || N > GG_MAX_BOARD || R < 0 || S < 1) return GG_E_BADSIZE;
+  if (!own_sizes_ok) return GG_E_BADSIZE;
   if (K < 1 || chunk_plies < 1 || max_plies < 1 || max_plies % chunk_plies || first_root < 0) return GG_E_BADARG;
-  if ((first_root + R) > (int64_t(1) << 62) / K) return GG_E_BADSIZE;   // global job ids must fit an int64
-  if (!roots || !slots || !rng || !plies || !job || !counter || !counts || !sums) return GG_E_NULLPTR;
+  if ((first_root + R) > ((int64_t(1) << 62) / K) / cells) return GG_E_BADSIZE;   // global job ids must fit an int64
+  if (!roots || !own_ptrs_ok || !slots || !rng || !plies || !job || !counter || !counts || !sums) return GG_E_NULLPTR;
   a.roots = roots; a.slots = slots; a.rng = rng; a.plies = plies; a.job = job; a.counter = counter; a.counts = counts;
-  a.sums = sums; a.own = ownership; a.S = S; a.J = R * K; a.first_job = first_root * K; a.base_seed = base_seed; a.K = K;
+  a.sums = sums; a.own = ownership; a.S = S; a.J = units * K; a.first_job = first_root * K; a.base_seed = base_seed; a.K = K;
   a.max_plies = max_plies; a.komi = komi;
   return 0;
 }
 
-template <bool FILL>
-static void launch_po(const PoArgs &a, int32_t N, int cus, hipStream_t s) {
-  const int nbw = N <= 13 ? Lat<13>::NBW : Lat<19>::NBW;
-  const int grid = grid_for(cus, (a.S + nbw - 1) / nbw, 64);
-#define GG_K(R, F) k_po_harvest<R, F, FILL><<<grid, kWave, 0, s>>>(a, N)
-  GG_DISPATCH_N(N);
-#undef GG_K
-}
-
-// ---- first-move playouts (gg_po.h, MpArgs): the checks of po_args on the pair space, in the same order
+// first-move playouts: po_args on the pair space (J = T K over the plan's T legal pairs; first_job and own unused)
 static int32_t mp_args(MpArgs &m, const uint32_t *roots, int64_t R, int32_t N, const int32_t *plan, int64_t T, int32_t K,
                        int64_t first_root, uint64_t base_seed, int32_t max_plies, int32_t chunk_plies, float komi, uint32_t *slots,
                        uint64_t *rng, int64_t *plies, int64_t *job, int64_t S, int64_t *counter, int32_t *counts, int64_t *sums) {
-  if (N < 2 || N > GG_MAX_BOARD || R < 0 || S < 1) return GG_E_BADSIZE;
   const int64_t A = (int64_t)N * N + 1;
-  if (R > (int64_t)0x7FFFFFFF / A || T < 0 || T > R * A) return GG_E_BADSIZE;   // pair ids r A + a are int32
-  if (K < 1 || chunk_plies < 1 || max_plies < 1 || max_plies % chunk_plies || first_root < 0) return GG_E_BADARG;
-  if ((first_root + R) > ((int64_t(1) << 62) / K) / A) return GG_E_BADSIZE;   // global job ids must fit an int64
-  if (!roots || !plan || !slots || !rng || !plies || !job || !counter || !counts || !sums) return GG_E_NULLPTR;
-  PoArgs &a = m;
-  a.roots = roots; a.slots = slots; a.rng = rng; a.plies = plies; a.job = job; a.counter = counter; a.counts = counts;
-  a.sums = sums; a.own = nullptr; a.S = S; a.J = T * K; a.first_job = 0; a.base_seed = base_seed; a.K = K;
-  a.max_plies = max_plies; a.komi = komi;
-  m.plan = plan; m.first_pair = first_root * A; m.A = (int32_t)A;
+  const bool pairs_ok = R >= 0 && R <= (int64_t)0x7FFFFFFF / A && T >= 0 && T <= R * A;   // pair ids r A + a are int32
+  if (int32_t e = po_args(m, A, T, pairs_ok, plan != nullptr, roots, R, N, K, first_root, base_seed, max_plies, chunk_plies, komi,
+                          slots, rng, plies, job, S, counter, counts, sums, nullptr))
+    return e;
+  m.first_job = 0; m.plan = plan; m.first_pair = first_root * A; m.A = (int32_t)A;
   return 0;
 }
 
-template <bool FILL>
-static void launch_mp(const MpArgs &m, int32_t N, int cus, hipStream_t s) {
+// the fill (begin) / harvest (advance) kernel for the board's row capacity
+template <bool FILL, class Args>
+static void launch_harvest(const Args &a, int32_t N, int cus, hipStream_t s) {
   const int nbw = N <= 13 ? Lat<13>::NBW : Lat<19>::NBW;
-  const int grid = grid_for(cus, (m.S + nbw - 1) / nbw, 64);
-#define GG_K(R, F) k_po_harvest<R, F, FILL, MpArgs><<<grid, kWave, 0, s>>>(m, N)
+  const int grid = grid_for(cus, (a.S + nbw - 1) / nbw, 64);
+#define GG_K(R, F) k_po_harvest<R, F, FILL, Args><<<grid, kWave, 0, s>>>(a, N)
   GG_DISPATCH_N(N);
 #undef GG_K
 }
 
-// ---- UCT tree search (gg_uct.h): the checks of po_args on the tree's sizes, in the same order
-static int32_t uct_args(UctArgs &u, int64_t R, int32_t N, int32_t I, int32_t K, double c) {
+// begin: zero the `cells` result cells (R, or R A), fill the slots with the first jobs
+template <class Args>
+static int32_t po_begin(const Args &a, int64_t cells, int32_t N, void *hip_stream) {
+  OnDeviceOf on_dev(a.slots);
+  hipStream_t s = (hipStream_t)hip_stream;
+  hipError_t err = hipSuccess;
+  if (cells > 0) {
+    err = hipMemsetAsync(a.counts, 0, sizeof(int32_t) * 4 * cells, s);
+    if (err == hipSuccess) err = hipMemsetAsync(a.sums, 0, sizeof(int64_t) * 2 * cells, s);
+    if (err == hipSuccess && a.own) err = hipMemsetAsync(a.own, 0, sizeof(int32_t) * 2 * N * N * cells, s);
+    if (err != hipSuccess) return (int32_t)err;
+  }
+  launch_harvest<true>(a, N, on_dev.cus(), s);
+  return (int32_t)hipGetLastError();
+}
+
+// advance: `chunks` times chunk_plies plies on every slot, then the harvest (refills, and in the first-move family the first
+// moves, happen there, between launches)
+template <class Args>
+static int32_t po_advance(const Args &a, int32_t N, int32_t chunk_plies, int32_t chunks, void *hip_stream) {
+  if (chunks < 0) return GG_E_BADARG;
+  if (a.J == 0 || chunks == 0) return 0;
+  OnDeviceOf on_dev(a.slots);
+  const int cus = on_dev.cus();
+  hipStream_t s = (hipStream_t)hip_stream;
+  for (int c = 0; c < chunks; ++c) {
+    // the existing tracked dispatch, auto_reset = 0: finished and empty slots stay frozen
+    if (int32_t e = gg_batch_rollout_tracked(a.slots, a.rng, nullptr, a.plies, a.S, N, chunk_plies, 0, hip_stream)) return e;
+    launch_harvest<false>(a, N, cus, s);
+    if (int32_t e = (int32_t)hipGetLastError()) return e;
+  }
+  return 0;
+}
+
+// ---- UCT tree search (gg_uct.h): the checks of po_args on the tree's sizes, in the same order, then the fill; the entry
+// points check their own pointers.  UctArgs serves three kernels and each of these members is written by one of them, so
+// they are not const there: gg_uct_select only reads boards, gg_uct_backup only reads links, leaf, move and leaf_id and
+// takes them as const - the casts below.
+static int32_t uct_args(UctArgs &u, int64_t R, int32_t N, int32_t I, int32_t K, double c, const uint32_t *boards, int32_t *child,
+                        const int32_t *links, int32_t *stats, int32_t *nodes, const uint32_t *leaf, const int32_t *move,
+                        const int32_t *leaf_id, const double *log_table = nullptr, const int32_t *counts = nullptr,
+                        const int64_t *sums = nullptr, int64_t *totals = nullptr) {
   if (N < 2 || N > GG_MAX_BOARD || R < 0) return GG_E_BADSIZE;
   if (I < 1 || K < 1 || !(c >= 0.0 && c <= __DBL_MAX__)) return GG_E_BADARG;
   if ((int64_t)I * K > 0x7FFFFFFF) return GG_E_BADSIZE;   // the root's n = I K is an int32
-  u = UctArgs{};
-  u.R = R; u.N = N; u.I = I; u.K = K; u.c = c;
+  u = UctArgs{const_cast<uint32_t *>(boards), child, const_cast<int32_t *>(links), stats, nodes, const_cast<uint32_t *>(leaf),
+              const_cast<int32_t *>(move), const_cast<int32_t *>(leaf_id), log_table, counts, sums, totals, c, R, N, I, K};
   return 0;
 }
 }  // namespace
@@ -1174,20 +1206,10 @@ int32_t gg_playouts_begin(const uint32_t *roots, int64_t R, int32_t N, int32_t K
                           int32_t max_plies, int32_t chunk_plies, uint32_t *slots, uint64_t *rng, int64_t *plies, int64_t *job,
                           int64_t S, int64_t *counter, int32_t *counts, int64_t *sums, int32_t *ownership, void *hip_stream) {
   PoArgs a;
-  if (int32_t e = po_args(a, roots, R, N, K, first_root, base_seed, max_plies, chunk_plies, 0.f, slots, rng, plies, job, S,
-                          counter, counts, sums, ownership))
+  if (int32_t e = po_args(a, 1, R, true, true, roots, R, N, K, first_root, base_seed, max_plies, chunk_plies, 0.f, slots, rng, plies,
+                          job, S, counter, counts, sums, ownership))
     return e;
-  OnDeviceOf on_dev(slots);
-  hipStream_t s = (hipStream_t)hip_stream;
-  hipError_t err = hipSuccess;
-  if (R > 0) {
-    err = hipMemsetAsync(counts, 0, sizeof(int32_t) * 4 * R, s);
-    if (err == hipSuccess) err = hipMemsetAsync(sums, 0, sizeof(int64_t) * 2 * R, s);
-    if (err == hipSuccess && ownership) err = hipMemsetAsync(ownership, 0, sizeof(int32_t) * 2 * N * N * R, s);
-    if (err != hipSuccess) return (int32_t)err;
-  }
-  launch_po<true>(a, N, on_dev.cus(), s);
-  return (int32_t)hipGetLastError();
+  return po_begin(a, R, N, hip_stream);
 }
 
 int32_t gg_playouts_advance(const uint32_t *roots, int64_t R, int32_t N, int32_t K, int64_t first_root, uint64_t base_seed,
@@ -1195,21 +1217,10 @@ int32_t gg_playouts_advance(const uint32_t *roots, int64_t R, int32_t N, int32_t
                             int64_t *plies, int64_t *job, int64_t S, int64_t *counter, int32_t *counts, int64_t *sums,
                             int32_t *ownership, void *hip_stream) {
   PoArgs a;
-  if (int32_t e = po_args(a, roots, R, N, K, first_root, base_seed, max_plies, chunk_plies, komi, slots, rng, plies, job, S,
-                          counter, counts, sums, ownership))
+  if (int32_t e = po_args(a, 1, R, true, true, roots, R, N, K, first_root, base_seed, max_plies, chunk_plies, komi, slots, rng, plies,
+                          job, S, counter, counts, sums, ownership))
     return e;
-  if (chunks < 0) return GG_E_BADARG;
-  if (R == 0 || chunks == 0) return 0;
-  OnDeviceOf on_dev(slots);
-  const int cus = on_dev.cus();
-  hipStream_t s = (hipStream_t)hip_stream;
-  for (int c = 0; c < chunks; ++c) {
-    // the existing tracked dispatch, auto_reset = 0: finished and empty slots stay frozen
-    if (int32_t e = gg_batch_rollout_tracked(slots, rng, nullptr, plies, S, N, chunk_plies, 0, hip_stream)) return e;
-    launch_po<false>(a, N, cus, s);
-    if (int32_t e = (int32_t)hipGetLastError()) return e;
-  }
-  return 0;
+  return po_advance(a, N, chunk_plies, chunks, hip_stream);
 }
 
 int32_t gg_move_playouts_plan(const uint32_t *roots, int64_t R, int32_t N, int32_t *offsets, int32_t *plan, void *hip_stream) {
@@ -1234,17 +1245,7 @@ int32_t gg_move_playouts_begin(const uint32_t *roots, int64_t R, int32_t N, cons
   if (int32_t e = mp_args(m, roots, R, N, plan, T, K, first_root, base_seed, max_plies, chunk_plies, 0.f, slots, rng, plies, job,
                           S, counter, counts, sums))
     return e;
-  OnDeviceOf on_dev(slots);
-  hipStream_t s = (hipStream_t)hip_stream;
-  hipError_t err = hipSuccess;
-  if (R > 0) {
-    const int64_t pairs = R * m.A;
-    err = hipMemsetAsync(counts, 0, sizeof(int32_t) * 4 * pairs, s);
-    if (err == hipSuccess) err = hipMemsetAsync(sums, 0, sizeof(int64_t) * 2 * pairs, s);
-    if (err != hipSuccess) return (int32_t)err;
-  }
-  launch_mp<true>(m, N, on_dev.cus(), s);
-  return (int32_t)hipGetLastError();
+  return po_begin(m, R * m.A, N, hip_stream);
 }
 
 int32_t gg_move_playouts_advance(const uint32_t *roots, int64_t R, int32_t N, const int32_t *plan, int64_t T, int32_t K,
@@ -1255,27 +1256,15 @@ int32_t gg_move_playouts_advance(const uint32_t *roots, int64_t R, int32_t N, co
   if (int32_t e = mp_args(m, roots, R, N, plan, T, K, first_root, base_seed, max_plies, chunk_plies, komi, slots, rng, plies, job,
                           S, counter, counts, sums))
     return e;
-  if (chunks < 0) return GG_E_BADARG;
-  if (T == 0 || chunks == 0) return 0;
-  OnDeviceOf on_dev(slots);
-  const int cus = on_dev.cus();
-  hipStream_t s = (hipStream_t)hip_stream;
-  for (int c = 0; c < chunks; ++c) {
-    // the same tracked dispatch as gg_playouts_advance: refills and first moves happen in the harvest, between launches
-    if (int32_t e = gg_batch_rollout_tracked(slots, rng, nullptr, plies, S, N, chunk_plies, 0, hip_stream)) return e;
-    launch_mp<false>(m, N, cus, s);
-    if (int32_t e = (int32_t)hipGetLastError()) return e;
-  }
-  return 0;
+  return po_advance(m, N, chunk_plies, chunks, hip_stream);
 }
 
 int32_t gg_uct_begin(const uint32_t *roots, int64_t R, int32_t N, int32_t I, int32_t K, uint32_t *boards, int32_t *child,
                      int32_t *links, int32_t *stats, int32_t *nodes, void *hip_stream) {
   UctArgs u;
-  if (int32_t e = uct_args(u, R, N, I, K, 0.0)) return e;
+  if (int32_t e = uct_args(u, R, N, I, K, 0.0, boards, child, links, stats, nodes, nullptr, nullptr, nullptr)) return e;
   if (!roots || !boards || !child || !links || !stats || !nodes) return GG_E_NULLPTR;
   if (R == 0) return 0;
-  u.boards = boards; u.child = child; u.links = links; u.stats = stats; u.nodes = nodes;
   OnDeviceOf on_dev(boards);
   hipStream_t s = (hipStream_t)hip_stream;
   const int64_t NN = (int64_t)I + 1, A = (int64_t)N * N + 1;
@@ -1292,11 +1281,9 @@ int32_t gg_uct_select(int64_t R, int32_t N, int32_t I, int32_t K, double c, cons
                       int32_t *child, int32_t *links, int32_t *stats, int32_t *nodes, uint32_t *leaf, int32_t *move,
                       int32_t *leaf_id, void *hip_stream) {
   UctArgs u;
-  if (int32_t e = uct_args(u, R, N, I, K, c)) return e;
+  if (int32_t e = uct_args(u, R, N, I, K, c, boards, child, links, stats, nodes, leaf, move, leaf_id, log_table)) return e;
   if (!log_table || !boards || !child || !links || !stats || !nodes || !leaf || !move || !leaf_id) return GG_E_NULLPTR;
   if (R == 0) return 0;
-  u.boards = const_cast<uint32_t *>(boards); u.child = child; u.links = links; u.stats = stats; u.nodes = nodes;
-  u.leaf = leaf; u.move = move; u.leaf_id = leaf_id; u.log_table = log_table;
   OnDeviceOf on_dev(leaf);
   hipStream_t s = (hipStream_t)hip_stream;
   k_uct_select<<<grid_for(on_dev.cus(), (R + 3) / 4), 4 * kWave, 0, s>>>(u);
@@ -1307,12 +1294,11 @@ int32_t gg_uct_backup(int64_t R, int32_t N, int32_t I, int32_t K, const int32_t 
                       uint32_t *boards, const int32_t *links, int32_t *stats, const uint32_t *leaf, const int32_t *move,
                       const int32_t *leaf_id, void *hip_stream) {
   UctArgs u;
-  if (int32_t e = uct_args(u, R, N, I, K, 0.0)) return e;
+  if (int32_t e = uct_args(u, R, N, I, K, 0.0, boards, nullptr, links, stats, nullptr, leaf, move, leaf_id, nullptr, counts, sums,
+                           totals))
+    return e;
   if (!counts || !sums || !boards || !links || !stats || !leaf || !move || !leaf_id) return GG_E_NULLPTR;
   if (R == 0) return 0;
-  u.boards = boards; u.links = const_cast<int32_t *>(links); u.stats = stats; u.leaf = const_cast<uint32_t *>(leaf);
-  u.move = const_cast<int32_t *>(move); u.leaf_id = const_cast<int32_t *>(leaf_id); u.counts = counts; u.sums = sums;
-  u.totals = totals;
   OnDeviceOf on_dev(leaf);
   hipStream_t s = (hipStream_t)hip_stream;
   k_uct_backup<<<grid_for(on_dev.cus(), (R + 3) / 4), 4 * kWave, 0, s>>>(u);

@@ -780,7 +780,6 @@ def batch_env_step_tracked(tracked, actions=None, rng=None, komi=0.0, reward_met
     return out
 
 
-
 # ---------------------------------------------------------------- Monte Carlo playouts to the end of the game
 # K uniform-random playouts of every root until the game ends (GoEnv.uniform_random_action + step, gym_go/envs/go_env.py:49-81),
 # scored with Tromp-Taylor areas (gogame.areas / winning, gym_go/gogame.py:225-230, :275-300) and reduced per root on the
@@ -792,6 +791,10 @@ Playouts.__doc__ = """Per-root results of batch_playouts: black_wins / white_win
 sign(black - white - komi); playouts cut off by max_plies), margin_sum (int64: sum of black - white area), plies_sum (int64:
 plies played) and ownership (int32 [R, 2, N, N]: per point, in how many playouts it ended in black's / white's area; None
 unless asked for)."""
+
+# the seeding of rng_seed and of the playout jobs (k_rng_seed, csrc/gg_common.h; po_seed, csrc/gg_po.h): the multiplier of the
+# game / job index and splitmix64's increment
+_JOB_MUL, _GOLDEN_GAMMA, _M64 = 0xD1342543DE82EF95, 0x9E3779B97F4A7C15, 2 ** 64 - 1
 
 
 def _drive_playouts(advance, counter, J, S, max_plies, chunk_plies, dev, what):
@@ -829,6 +832,18 @@ def _drive_playouts(advance, counter, J, S, max_plies, chunk_plies, dev, what):
             ev.synchronize()
 
 
+def _run_queue(family, what, head, komi, bufs, counter, J, S, max_plies, chunk_plies, dev):
+    """gg_<family>_begin, then gg_<family>_advance until the counter drains (_drive_playouts).  head: the arguments up to
+    chunk_plies, bufs: those from slots on (_queue_ptrs, and what the family adds); advance takes komi and the chunk count
+    between the two."""
+    begin, advance = 'gg_%s_begin' % family, 'gg_%s_advance' % family
+    begin_fn, advance_fn = getattr(_lib.lib(), begin), getattr(_lib.lib(), advance)
+    stream = _lib.current_raw_stream(dev)   # torch's current stream: the counter copies of _drive_playouts go there too
+    _lib.check(begin_fn(*head, *bufs, stream), begin)
+    _drive_playouts(lambda n: _lib.check(advance_fn(*head, float(komi), n, *bufs, stream), advance),
+                    counter, J, S, max_plies, chunk_plies, dev, what)
+
+
 def _slot_buffers(S, N, dev):
     """Working slots of the playout queue: (slots, rng, plies, job, counter) device tensors."""
     return (torch.empty((S, tracked_words(N)), dtype=_I32, device=dev), torch.empty(S, dtype=_I64, device=dev),
@@ -841,25 +856,24 @@ def _playout_buffers(R, S, N, dev):
     return _slot_buffers(S, N, dev) + (torch.empty((R, 4), dtype=_I32, device=dev), torch.empty((R, 2), dtype=_I64, device=dev))
 
 
+def _queue_ptrs(slots, rng, plies, job, counter, counts, sums):
+    """The queue's buffers as both families' C entry points take them: slots, rng, plies, job, S, counter, counts, sums."""
+    return (_lib.dev_ptr(slots, _I32, 'slots'), _lib.dev_ptr(rng, _I64, 'rng'), _lib.dev_ptr(plies, _I64, 'plies'),
+            _lib.dev_ptr(job, _I64, 'job'), slots.shape[0], _lib.dev_ptr(counter, _I64, 'counter'),
+            _lib.dev_ptr(counts, _I32, 'counts'), _lib.dev_ptr(sums, _I64, 'sums'))
+
+
 def _run_playouts(roots, R, N, K, max_plies, komi, seed, first_root, ownership, S, chunk_plies, dev, buffers=None):
-    """Device work of batch_playouts on tracked roots: -> (counts int32 [R, 4], sums int64 [R, 2], own or None).
-    buffers: _playout_buffers(R, S, N, dev) to reuse (a search evaluates its leaves with the same buffers every iteration)."""
-    L = _lib.lib()
-    J = R * K
-    slots, rng, plies, job, counter, counts, sums = buffers if buffers is not None else _playout_buffers(R, S, N, dev)
+    """Device work of batch_playouts on tracked roots: -> (counts int32 [R, 4], sums int64 [R, 2], own or None); no launch
+    for R = 0.  buffers: _playout_buffers(R, S, N, dev) to reuse (a search evaluates its leaves with the same buffers every
+    iteration)."""
+    buffers = buffers if buffers is not None else _playout_buffers(R, S, N, dev)
+    counter, counts, sums = buffers[4:]
     own = torch.empty((R, 2, N, N), dtype=_I32, device=dev) if ownership else None
-    stream = _lib.current_raw_stream(dev)   # torch's current stream: the counter copies below go there too
-    common = (_lib.dev_ptr(roots, _I32, 'roots'), R, N, K, int(first_root), int(seed) & (2 ** 64 - 1), int(max_plies),
-              int(chunk_plies))
-    bufs = (_lib.dev_ptr(slots, _I32, 'slots'), _lib.dev_ptr(rng, _I64, 'rng'), _lib.dev_ptr(plies, _I64, 'plies'),
-            _lib.dev_ptr(job, _I64, 'job'), S, _lib.dev_ptr(counter, _I64, 'counter'), _lib.dev_ptr(counts, _I32, 'counts'),
-            _lib.dev_ptr(sums, _I64, 'sums'), _lib.dev_ptr(own, _I32, 'ownership'))
-    _lib.check(L.gg_playouts_begin(*common, *bufs, stream), 'gg_playouts_begin')
-
-    def advance(n):
-        _lib.check(L.gg_playouts_advance(*common, float(komi), n, *bufs, stream), 'gg_playouts_advance')
-
-    _drive_playouts(advance, counter, J, S, max_plies, chunk_plies, dev, 'batch_playouts')
+    if R > 0:
+        head = (_lib.dev_ptr(roots, _I32, 'roots'), R, N, K, int(first_root), int(seed) & _M64, int(max_plies), int(chunk_plies))
+        _run_queue('playouts', 'batch_playouts', head, komi, _queue_ptrs(*buffers) + (_lib.dev_ptr(own, _I32, 'ownership'),),
+                   counter, R * K, S, max_plies, chunk_plies, dev)
     return counts, sums, own
 
 
@@ -883,6 +897,37 @@ def _default_slots(slots):
     return 256 * int(_lib.lib().gg_device_cus()) if slots is None else slots   # 19x19: k_rollout5 from 256 games per CU on
 
 
+def _track_roots(st):
+    """batch_track; an empty batch without a launch (the run helpers return their empty results before they touch it)."""
+    return batch_track(st) if st.shape[0] else torch.empty((0, tracked_words(st.shape[2])), dtype=_I32, device=st.device)
+
+
+def _back(box, res, row0=False):
+    """Results in the caller's form: every tensor of `res` (a tensor, None, or a - nested - namedtuple of them) as it is or, for
+    NumPy input, as a NumPy array; row0: its row 0 (the single-state forms)."""
+    if res is None:
+        return None
+    if isinstance(res, tuple):
+        return type(res)(*[_back(box, t, row0) for t in res])
+    res = res[0] if row0 else res
+    return res.cpu().numpy() if box.numpy else res
+
+
+def _single(batch_fn, state, *args, **kw):
+    """The single-state form of a batch function: state [6, N, N] as a batch of one, row 0 of every result."""
+    box = _Box(state)
+    return _back(box, batch_fn(box.t[None], *args, **kw), row0=True)
+
+
+def _best_legal(box, legal, score):
+    """int64 [R]: per row of score (int64 [R, A], above -2^62) the legal action with the largest score, ties to the lowest
+    action, -1 for a row without a legal action."""
+    score = torch.where(legal, score, torch.full_like(score, -(2 ** 62)))
+    idx = torch.arange(score.shape[1], dtype=_I64, device=score.device).expand_as(score)
+    act = torch.where(score == score.max(dim=1, keepdim=True).values, idx, torch.full_like(idx, score.shape[1])).min(dim=1).values
+    return _back(box, torch.where(legal.any(dim=1), act, torch.full_like(act, -1)))
+
+
 def batch_playouts(batch_states, playouts, max_plies=None, komi=0.0, seed=20260927, first_root=0, ownership=False, slots=None,
                    chunk_plies=32):
     """`playouts` uniform-random playouts of every root of batch_states ([R, 6, N, N]) to the end of the game, scored and
@@ -897,29 +942,15 @@ def batch_playouts(batch_states, playouts, max_plies=None, komi=0.0, seed=202609
     box = _Box(batch_states)
     st = box.t
     R, N, K, max_plies, chunk_plies = _playout_args(st, playouts, max_plies, chunk_plies, first_root)
-    dev = st.device
     S = max(1, min(int(_default_slots(slots)), R * K))
-    if R == 0:
-        counts = torch.zeros((0, 4), dtype=_I32, device=dev)
-        sums = torch.zeros((0, 2), dtype=_I64, device=dev)
-        own = torch.zeros((0, 2, N, N), dtype=_I32, device=dev) if ownership else None
-    else:
-        counts, sums, own = _run_playouts(batch_track(st), R, N, K, max_plies, komi, seed, first_root, ownership, S,
-                                          chunk_plies, dev)
-    res = (counts[:, 0], counts[:, 1], counts[:, 2], counts[:, 3], sums[:, 0], sums[:, 1], own)
-    if box.numpy:
-        res = tuple(None if t is None else t.cpu().numpy() for t in res)
-    return Playouts(*res)
+    counts, sums, own = _run_playouts(_track_roots(st), R, N, K, max_plies, komi, seed, first_root, ownership, S, chunk_plies,
+                                      st.device)
+    return _back(box, Playouts(counts[:, 0], counts[:, 1], counts[:, 2], counts[:, 3], sums[:, 0], sums[:, 1], own))
 
 
 def playouts(state, n, **kw):
     """batch_playouts of one state [6, N, N] -> Playouts of scalars (and ownership [2, N, N])."""
-    box = _Box(state)
-    res = batch_playouts(box.t[None], n, **kw)
-    out = tuple(None if t is None else t[0] for t in res)
-    if box.numpy:
-        out = tuple(None if t is None else t.cpu().numpy() for t in out)
-    return Playouts(*out)
+    return _single(batch_playouts, state, n, **kw)
 
 
 # ---------------------------------------------------------------- flat Monte Carlo: playouts per legal first move
@@ -934,37 +965,30 @@ Playouts, all zero where the move is not legal."""
 
 
 def _run_move_playouts(roots, R, N, K, max_plies, komi, seed, first_root, slots, chunk_plies, dev):
-    """Device work of batch_move_playouts on tracked roots: -> (legal bool [R, A], counts int32 [R, A, 4], sums [R, A, 2])."""
-    L = _lib.lib()
+    """Device work of batch_move_playouts on tracked roots: -> (legal bool [R, A], counts int32 [R, A, 4], sums [R, A, 2]); no
+    launch for R = 0."""
     A = N * N + 1
-    stream = _lib.current_raw_stream(dev)
-    offsets = torch.empty(R + 1, dtype=_I32, device=dev)
-    plan = torch.empty(max(R * A, 1), dtype=_I32, device=dev)
-    rp = _lib.dev_ptr(roots, _I32, 'roots')
-    with torch.cuda.device(dev):
-        _lib.check(L.gg_move_playouts_plan(rp, R, N, _lib.dev_ptr(offsets, _I32, 'offsets'), _lib.dev_ptr(plan, _I32, 'plan'),
-                                           stream), 'gg_move_playouts_plan')
-        T = int(offsets[R])   # (a synchronising read, as the un-padded children do)
     counts = torch.zeros((R, A, 4), dtype=_I32, device=dev)
     sums = torch.zeros((R, A, 2), dtype=_I64, device=dev)
     legal = torch.zeros((R, A), dtype=torch.bool, device=dev)
+    if R == 0:
+        return legal, counts, sums
+    offsets = torch.empty(R + 1, dtype=_I32, device=dev)
+    plan = torch.empty(R * A, dtype=_I32, device=dev)
+    rp, pp = _lib.dev_ptr(roots, _I32, 'roots'), _lib.dev_ptr(plan, _I32, 'plan')
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().gg_move_playouts_plan(rp, R, N, _lib.dev_ptr(offsets, _I32, 'offsets'), pp,
+                                                    _lib.current_raw_stream(dev)), 'gg_move_playouts_plan')
+        T = int(offsets[R])   # (a synchronising read, as the un-padded children do)
     if T == 0:
         return legal, counts, sums
     legal.view(-1)[plan[:T].long()] = True
     J = T * K
     S = max(1, min(int(slots), J))
-    slot_t, rng, plies, job, counter = _slot_buffers(S, N, dev)
-    common = (rp, R, N, _lib.dev_ptr(plan, _I32, 'plan'), T, K, int(first_root), int(seed) & (2 ** 64 - 1), int(max_plies),
-              int(chunk_plies))
-    bufs = (_lib.dev_ptr(slot_t, _I32, 'slots'), _lib.dev_ptr(rng, _I64, 'rng'), _lib.dev_ptr(plies, _I64, 'plies'),
-            _lib.dev_ptr(job, _I64, 'job'), S, _lib.dev_ptr(counter, _I64, 'counter'), _lib.dev_ptr(counts, _I32, 'counts'),
-            _lib.dev_ptr(sums, _I64, 'sums'))
-    _lib.check(L.gg_move_playouts_begin(*common, *bufs, stream), 'gg_move_playouts_begin')
-
-    def advance(n):
-        _lib.check(L.gg_move_playouts_advance(*common, float(komi), n, *bufs, stream), 'gg_move_playouts_advance')
-
-    _drive_playouts(advance, counter, J, S, max_plies, chunk_plies, dev, 'batch_move_playouts')
+    slot_bufs = _slot_buffers(S, N, dev)
+    head = (rp, R, N, pp, T, K, int(first_root), int(seed) & _M64, int(max_plies), int(chunk_plies))
+    _run_queue('move_playouts', 'batch_move_playouts', head, komi, _queue_ptrs(*slot_bufs, counts, sums), slot_bufs[4], J, S,
+               max_plies, chunk_plies, dev)
     return legal, counts, sums
 
 
@@ -984,30 +1008,15 @@ def batch_move_playouts(batch_states, playouts, max_plies=None, komi=0.0, seed=2
     box = _Box(batch_states)
     st = box.t
     R, N, K, max_plies, chunk_plies = _playout_args(st, playouts, max_plies, chunk_plies, first_root)
-    dev = st.device
-    slots = _default_slots(slots)
-    A = N * N + 1
-    if R == 0:
-        legal = torch.zeros((0, A), dtype=torch.bool, device=dev)
-        counts = torch.zeros((0, A, 4), dtype=_I32, device=dev)
-        sums = torch.zeros((0, A, 2), dtype=_I64, device=dev)
-    else:
-        legal, counts, sums = _run_move_playouts(batch_track(st), R, N, K, max_plies, komi, seed, first_root, slots,
-                                                 chunk_plies, dev)
-    res = (legal, counts[..., 0], counts[..., 1], counts[..., 2], counts[..., 3], sums[..., 0], sums[..., 1])
-    if box.numpy:
-        res = tuple(t.cpu().numpy() for t in res)
-    return MovePlayouts(*res)
+    legal, counts, sums = _run_move_playouts(_track_roots(st), R, N, K, max_plies, komi, seed, first_root, _default_slots(slots),
+                                             chunk_plies, st.device)
+    return _back(box, MovePlayouts(legal, counts[..., 0], counts[..., 1], counts[..., 2], counts[..., 3], sums[..., 0],
+                                   sums[..., 1]))
 
 
 def move_playouts(state, n, **kw):
     """batch_move_playouts of one state [6, N, N] -> MovePlayouts of [N*N + 1] vectors."""
-    box = _Box(state)
-    res = batch_move_playouts(box.t[None], n, **kw)
-    out = tuple(t[0] for t in res)
-    if box.numpy:
-        out = tuple(t.cpu().numpy() for t in out)
-    return MovePlayouts(*out)
+    return _single(batch_move_playouts, state, n, **kw)
 
 
 def flat_mc_actions(batch_states, playouts, **kw):
@@ -1016,20 +1025,9 @@ def flat_mc_actions(batch_states, playouts, **kw):
     action, a root without a legal move gives -1."""
     box = _Box(batch_states)
     res = batch_move_playouts(box.t, playouts, **kw)
-    st = box.t
-    R = st.shape[0]
-    if R == 0:
-        act = torch.zeros(0, dtype=_I64, device=st.device)
-    else:
-        bw, ww = res.black_wins.to(_I64), res.white_wins.to(_I64)
-        white = st[:, govars.TURN_CHNL, 0, 0].to(torch.bool)[:, None]
-        score = torch.where(white, ww - bw, bw - ww)
-        score = torch.where(res.legal, score, torch.full_like(score, -(2 ** 62)))
-        best = score.max(dim=1, keepdim=True).values
-        idx = torch.arange(score.shape[1], dtype=_I64, device=st.device).expand_as(score)
-        act = torch.where(score == best, idx, torch.full_like(idx, score.shape[1])).min(dim=1).values   # the lowest of the best
-        act = torch.where(res.legal.any(dim=1), act, torch.full_like(act, -1))
-    return act.cpu().numpy() if box.numpy else act
+    bw, ww = res.black_wins.to(_I64), res.white_wins.to(_I64)
+    white = box.t[:, govars.TURN_CHNL, 0, 0].to(torch.bool)[:, None]
+    return _best_legal(box, res.legal, torch.where(white, ww - bw, bw - ww))
 
 
 # ---------------------------------------------------------------- UCT tree search over the playouts
@@ -1045,11 +1043,10 @@ UctTree = collections.namedtuple('UctTree', 'parent action visits black_wins whi
 UctTree.__doc__ = """The whole tree of every root, each field int32 [R, iterations + 1] indexed by node (node 0 = the root;
 parent / action -1 at the root and at unused nodes, whose stats are 0)."""
 
-_JOB_MUL, _GOLDEN_GAMMA, _M64 = 0xD1342543DE82EF95, 0x9E3779B97F4A7C15, 2 ** 64 - 1
-
 
 def _uct_seed(seed, i):
-    """Base seed of iteration i's playouts: what gg_rng_seed(base_seed=seed, first_game=i) writes (rng_seed's generator)."""
+    """Base seed of iteration i's playouts, on the host (no device round trip per iteration): restates gg_rng_seed(base_seed=
+    seed, first_game=i) (k_rng_seed), the generator of game i = (seed ^ i * _JOB_MUL) + _GOLDEN_GAMMA mod 2^64."""
     return (((int(seed) & _M64) ^ ((int(i) * _JOB_MUL) & _M64)) + _GOLDEN_GAMMA) & _M64
 
 
@@ -1070,7 +1067,7 @@ def _legal_roots(st):
 
 def _run_uct(roots, R, N, I, K, c, max_plies, komi, seed, first_root, S, chunk_plies, dev):
     """Device work of batch_uct on tracked roots -> (child int32 [R, I+1, A], links [R, I+1, 2], stats [R, I+1, 4],
-    nodes [R], totals int64 [R, 2])."""
+    nodes [R], totals int64 [R, 2]); no launch for R = 0."""
     L = _lib.lib()
     W, A, NN = tracked_words(N), N * N + 1, I + 1
     boards = torch.empty((R, NN, W), dtype=_I32, device=dev)
@@ -1078,10 +1075,12 @@ def _run_uct(roots, R, N, I, K, c, max_plies, komi, seed, first_root, S, chunk_p
     links = torch.empty((R, NN, 2), dtype=_I32, device=dev)
     stats = torch.empty((R, NN, 4), dtype=_I32, device=dev)
     nodes = torch.empty(R, dtype=_I32, device=dev)
+    totals = torch.zeros((R, 2), dtype=_I64, device=dev)
+    if R == 0:
+        return child, links, stats, nodes, totals
     leaf = torch.empty((R, W), dtype=_I32, device=dev)
     move = torch.empty(R, dtype=_I32, device=dev)
     leaf_id = torch.empty(R, dtype=_I32, device=dev)
-    totals = torch.zeros((R, 2), dtype=_I64, device=dev)
     with np.errstate(divide='ignore'):   # (L[0] = -inf is never read: a node with children has n >= K)
         log_table = torch.from_numpy(np.log(np.arange(NN, dtype=np.float64) * K)).to(dev)
     pbufs = _playout_buffers(R, S, N, dev)
@@ -1125,40 +1124,20 @@ def batch_uct(batch_states, iterations, playouts, c=math.sqrt(2), max_plies=None
     st = box.t
     R, N, K, max_plies, chunk_plies = _playout_args(st, playouts, max_plies, chunk_plies, first_root)
     I, c = _uct_args(iterations, K, c)
-    dev = st.device
-    A = N * N + 1
-    legal = _legal_roots(st)
-    if R == 0:
-        child = torch.full((0, I + 1, A), -1, dtype=_I32, device=dev)
-        links = torch.full((0, I + 1, 2), -1, dtype=_I32, device=dev)
-        stats = torch.zeros((0, I + 1, 4), dtype=_I32, device=dev)
-        nodes = torch.zeros(0, dtype=_I32, device=dev)
-        totals = torch.zeros((0, 2), dtype=_I64, device=dev)
-    else:
-        S = max(1, min(int(_default_slots(slots)), R * K))
-        child, links, stats, nodes, totals = _run_uct(batch_track(st), R, N, I, K, c, max_plies, komi, seed, first_root, S,
-                                                      chunk_plies, dev)
+    S = max(1, min(int(_default_slots(slots)), R * K))
+    child, links, stats, nodes, totals = _run_uct(_track_roots(st), R, N, I, K, c, max_plies, komi, seed, first_root, S,
+                                                  chunk_plies, st.device)
     rc = child[:, 0, :]
-    kid = torch.gather(stats, 1, rc.clamp(min=0).long()[..., None].expand(R, A, 4))
+    kid = torch.gather(stats, 1, rc.clamp(min=0).long()[..., None].expand(R, N * N + 1, 4))
     kid = torch.where((rc >= 0)[..., None], kid, torch.zeros_like(kid))
-    res = [legal, kid[..., 0], kid[..., 1], kid[..., 2], kid[..., 3], stats[:, 0, 0], totals[:, 0], totals[:, 1], nodes]
-    whole = (links[..., 0], links[..., 1], stats[..., 0], stats[..., 1], stats[..., 2], stats[..., 3]) if tree else None
-    if box.numpy:
-        res = [t.cpu().numpy() for t in res]
-        whole = None if whole is None else tuple(t.cpu().numpy() for t in whole)
-    return Uct(*res, tree=None if whole is None else UctTree(*whole))
+    whole = UctTree(links[..., 0], links[..., 1], stats[..., 0], stats[..., 1], stats[..., 2], stats[..., 3]) if tree else None
+    return _back(box, Uct(_legal_roots(st), kid[..., 0], kid[..., 1], kid[..., 2], kid[..., 3], stats[:, 0, 0], totals[:, 0],
+                          totals[:, 1], nodes, whole))
 
 
 def uct(state, iterations, playouts, **kw):
     """batch_uct of one state [6, N, N] -> Uct of [N*N + 1] vectors and scalars (tree fields [iterations + 1])."""
-    box = _Box(state)
-    res = batch_uct(box.t[None], iterations, playouts, **kw)
-    out = [t[0] for t in res[:-1]]
-    whole = None if res.tree is None else [t[0] for t in res.tree]
-    if box.numpy:
-        out = [t.cpu().numpy() for t in out]
-        whole = None if whole is None else [t.cpu().numpy() for t in whole]
-    return Uct(*out, tree=None if whole is None else UctTree(*whole))
+    return _single(batch_uct, state, iterations, playouts, **kw)
 
 
 def uct_actions(batch_states, iterations, playouts, **kw):
@@ -1166,13 +1145,8 @@ def uct_actions(batch_states, iterations, playouts, **kw):
     iterations, playouts, **kw); ties go to the lowest action, a root without a legal move gives -1."""
     box = _Box(batch_states)
     res = batch_uct(box.t, iterations, playouts, **kw)
-    st = box.t
-    v = torch.where(res.legal, res.visits.to(_I64), torch.full_like(res.visits, -1, dtype=_I64))
-    idx = torch.arange(v.shape[1], dtype=_I64, device=st.device).expand_as(v)
-    act = torch.where(v == v.max(dim=1, keepdim=True).values, idx, torch.full_like(idx, v.shape[1])).min(dim=1).values \
-        if v.shape[0] else torch.zeros(0, dtype=_I64, device=st.device)
-    act = torch.where(res.legal.any(dim=1), act, torch.full_like(act, -1))
-    return act.cpu().numpy() if box.numpy else act
+    return _best_legal(box, res.legal, res.visits.to(_I64))
+
 
 # ---------------------------------------------------------------- policy-weighted sampling on the device
 # gogame.random_weighted_action / random_action (gym_go/gogame.py:385-404) for every game of a batch: what a self-play loop

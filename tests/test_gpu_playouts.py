@@ -1,6 +1,6 @@
 """-m gpu: batched Monte Carlo playouts (gogame.batch_playouts: gg_playouts_begin / gg_playouts_advance, the harvest kernel of
 gg_po.h around the tracked rollout) - every per-root output equal to the C restatement's replay of every playout
-(tests/playout_expect.py), on all three rollout families, with and without refills, cut-offs, komi, ownership, and
+(tests/mc_expect.py), on all three rollout families, with and without refills, cut-offs, komi, ownership, and
 invariance under the slot count, the chunk length and sharding by root."""
 import os
 import subprocess
@@ -9,41 +9,29 @@ import sys
 import numpy as np
 import pytest
 
-import playout_expect as px
+import mc_expect as mc
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
-KEYS = ('black_wins', 'white_wins', 'draws', 'unfinished', 'margin_sum', 'plies_sum')
-
-
-def _dev_roots(roots):
-    import torch
-    return torch.from_numpy(roots).cuda()
 
 
 def _check(got, want, own=False):
-    for k in KEYS:
-        g = getattr(got, k)
-        g = g.cpu().numpy() if hasattr(g, 'cpu') else g
-        assert np.array_equal(g, want[k]), (k, np.nonzero(g != want[k])[0][:8], g[:8], want[k][:8])
-    if own:
-        g = got.ownership.cpu().numpy() if hasattr(got.ownership, 'cpu') else got.ownership
-        assert np.array_equal(g, want['ownership']), 'ownership'
-    else:
+    mc.check(got, want, mc.KEYS + (('ownership',) if own else ()))
+    if not own:
         assert got.ownership is None
 
 
 @pytest.fixture(scope='module')
 def roots19():
-    return px.make_roots(19, 128, 101, max_ply=200, step=8)
+    return mc.make_roots(19, 128, 101, max_ply=200, step=8)
 
 
 def test_playouts_19x19_with_and_without_refills(roots19):
     """128 mid-game roots (an empty one, a finished one) x 8 on 256 slots (each refilled ~4x) and on 1 024 (no refill); the
     roots are left as they were."""
     from gymgo_amd import gogame
-    want = px.expected(roots19, 8, 2912, komi=7.5, base_seed=5)
-    r = _dev_roots(roots19)
+    want = mc.expected_playouts(roots19, 8, 2912, komi=7.5, base_seed=5)
+    r = mc.to_dev(roots19)
     before = r.clone()
     for S in (256, 1024):
         got = gogame.batch_playouts(r, 8, max_plies=2912, komi=7.5, seed=5, slots=S)
@@ -55,8 +43,8 @@ def test_playouts_19x19_with_and_without_refills(roots19):
 @pytest.mark.parametrize('N', [7, 9, 13])
 def test_playouts_small_boards_small_slot_counts(N):
     from gymgo_amd import gogame
-    roots = px.make_roots(N, 40, 7 + N, max_ply=3 * N * N // 2, step=N)
-    want = px.expected(roots, 6, -(-8 * N * N // 32) * 32, komi=0.0, base_seed=N, with_ownership=True)
+    roots = mc.make_roots(N, 40, 7 + N, max_ply=3 * N * N // 2, step=N)
+    want = mc.expected_playouts(roots, 6, -(-8 * N * N // 32) * 32, komi=0.0, base_seed=N, with_ownership=True)
     got = gogame.batch_playouts(roots, 6, komi=0.0, seed=N, slots=48, ownership=True)   # NumPy in, NumPy out
     assert isinstance(got.black_wins, np.ndarray)
     _check(got, want, own=True)
@@ -65,9 +53,9 @@ def test_playouts_small_boards_small_slot_counts(N):
 def test_playouts_cut_off_komi_and_ownership(roots19):
     """max_plies = 64: most playouts are cut off, scored as they stand and counted as unfinished; komi 0 (draws) and negative."""
     from gymgo_amd import gogame
-    r = _dev_roots(roots19)
+    r = mc.to_dev(roots19)
     for komi, cp in ((0.0, 32), (-3.5, 16)):
-        want = px.expected(roots19, 8, 64, komi=komi, base_seed=9, with_ownership=True)
+        want = mc.expected_playouts(roots19, 8, 64, komi=komi, base_seed=9, with_ownership=True)
         assert want['unfinished'].sum() > 512
         got = gogame.batch_playouts(r, 8, max_plies=64, komi=komi, seed=9, slots=300, chunk_plies=cp, ownership=True)
         _check(got, want, own=True)
@@ -77,9 +65,9 @@ def test_playouts_invariant_under_slots_chunks_and_shards():
     from gymgo_amd import gogame
     import torch
     N, R, K = 9, 96, 8
-    roots = px.make_roots(N, R, 33, max_ply=100, step=4)
-    want = px.expected(roots, K, 704, komi=0.5, base_seed=77, with_ownership=True)
-    r = _dev_roots(roots)
+    roots = mc.make_roots(N, R, 33, max_ply=100, step=4)
+    want = mc.expected_playouts(roots, K, 704, komi=0.5, base_seed=77, with_ownership=True)
+    r = mc.to_dev(roots)
     for S, cp in ((R * K, 32), (512, 16), (96, 64), (96, 32)):
         got = gogame.batch_playouts(r, K, max_plies=704, komi=0.5, seed=77, slots=S, chunk_plies=cp, ownership=True)
         _check(got, want, own=True)
@@ -97,11 +85,11 @@ import numpy as np
 sys.path.insert(0, %(root)r); sys.path.insert(0, %(here)r)
 import torch
 from gymgo_amd import gogame, _lib
-import playout_expect as px
+import mc_expect as mc
 assert int(_lib.lib().gg_device_cus()) == 4
 for N, R, K in ((19, 128, 12), (9, 160, 16), (13, 160, 12)):
-    roots = px.make_roots(N, R, 500 + N, max_ply=2 * N * N // 3, step=N)
-    want = px.expected(roots, K, -(-8 * N * N // 32) * 32, komi=7.5, base_seed=N, with_ownership=N == 19)
+    roots = mc.make_roots(N, R, 500 + N, max_ply=2 * N * N // 3, step=N)
+    want = mc.expected_playouts(roots, K, -(-8 * N * N // 32) * 32, komi=7.5, base_seed=N, with_ownership=N == 19)
     # 1 024 slots: k_rollout5 (more than 128 / 159 games per CU); 19x19 on 256 slots as well: k_rollout4
     for S in ((1024, 256) if N == 19 else (1024,)):
         got = gogame.batch_playouts(torch.from_numpy(roots).cuda(), K, komi=7.5, seed=N, slots=S, ownership=N == 19)

@@ -1,11 +1,10 @@
 """CPU: flat Monte Carlo (gg_move_playouts_plan / _begin / _advance, gogame.batch_move_playouts) without a device - argument
 checks of the C-ABI, no CPU fallback in the Python API, and the expectation helpers the GPU tests build on
-(tests/move_playout_expect.py) against the C restatement."""
+(tests/mc_expect.py) against the C restatement."""
 import numpy as np
 import pytest
 
-import move_playout_expect as mx
-import playout_expect as px
+import mc_expect as mc
 from oracle import c_oracle
 
 
@@ -72,14 +71,14 @@ def test_job_seed_restatement_matches_the_c_generator():
     ids = np.concatenate([np.arange(0, 300), np.array([12345, 2 ** 31 - 1, 2 ** 31, 2 ** 40 + 7, 3 * 2 ** 50 + 11, 2 ** 62 - 1])])
     for seed in (0, 20260927, 2 ** 64 - 1):
         want = np.array([L.gg_oracle_rng_seed(seed, int(i)) for i in ids], np.uint64)
-        assert np.array_equal(mx.po_seed(seed, ids), want)
-    assert np.array_equal(mx.po_seed(5, np.arange(64)), c_oracle.rng_seed(5, 64))
+        assert np.array_equal(mc.po_seed(seed, ids), want)
+    assert np.array_equal(mc.po_seed(5, np.arange(64)), c_oracle.rng_seed(5, 64))
 
 
 @pytest.mark.parametrize('N', [5, 7, 9, 19])
 def test_legal_mask_is_valid_moves_with_ended_roots_zeroed(N):
-    roots = np.concatenate([px.make_roots(N, 12, 4, max_ply=N * N, step=N), mx.crafted_roots(N)])
-    legal = mx.legal_mask(roots)
+    roots = np.concatenate([mc.make_roots(N, 12, 4, max_ply=N * N, step=N), mc.crafted_roots(N)])
+    legal = mc.legal_mask(roots)
     R, A = roots.shape[0], N * N + 1
     ended = roots[:, 5, 0, 0] != 0
     assert ended[-1] and ended[-5] and ended.sum() >= 2          # make_roots' finished game and the crafted one
@@ -90,20 +89,20 @@ def test_legal_mask_is_valid_moves_with_ended_roots_zeroed(N):
     kids = c_oracle.batch_children(roots)
     assert np.array_equal(legal[~ended], kids[~ended].reshape(R - ended.sum(), A, -1).any(axis=2))
     # the crafted roots: the ko point may not be retaken, the pass after a pass ends the game
-    ko = mx.crafted_roots(N)[2]
-    assert not mx.legal_mask(ko[None])[0, mx.KO_POINT[0] * N + mx.KO_POINT[1]]
-    end_kid = c_oracle.next_state(mx.crafted_roots(N)[1], N * N)
+    ko = mc.crafted_roots(N)[2]
+    assert not mc.legal_mask(ko[None])[0, mc.KO_POINT[0] * N + mc.KO_POINT[1]]
+    end_kid = c_oracle.next_state(mc.crafted_roots(N)[1], N * N)
     assert end_kid[5].all()
 
 
 def test_expected_move_results_are_consistent():
     N, K = 7, 6
-    roots = np.concatenate([px.make_roots(N, 6, 2, max_ply=40, step=8)[:-1], mx.crafted_roots(N)])
-    e = mx.expected(roots, K, 8 * N * N, komi=0.0, base_seed=3)
+    roots = np.concatenate([mc.make_roots(N, 6, 2, max_ply=40, step=8)[:-1], mc.crafted_roots(N)])
+    e = mc.expected_move_playouts(roots, K, 8 * N * N, komi=0.0, base_seed=3)
     legal = e['legal']
     total = e['black_wins'] + e['white_wins'] + e['draws']
     assert np.array_equal(total[legal], np.full(legal.sum(), K)) and not total[~legal].any()
-    for k in mx.KEYS:
+    for k in mc.KEYS:
         assert not e[k][~legal].any(), k
     assert e['unfinished'].sum() == 0
     # the crafted pass root: its pass child has ended, K finished playouts of 0 plies
@@ -114,24 +113,24 @@ def test_expected_move_results_are_consistent():
     r, a = np.nonzero(legal)
     for r_, a_ in list(zip(r, a))[::29]:
         kid = c_oracle.next_state(roots[r_], int(a_))
-        one = px.expected(kid[None], K, 8 * N * N, komi=0.0, base_seed=3, first_root=(5 + r_) * (N * N + 1) + a_)
-        sh = mx.expected(roots[r_:r_ + 1], K, 8 * N * N, komi=0.0, base_seed=3, first_root=5 + r_)
-        for k in mx.KEYS:
+        one = mc.expected_playouts(kid[None], K, 8 * N * N, komi=0.0, base_seed=3, first_root=(5 + r_) * (N * N + 1) + a_)
+        sh = mc.expected_move_playouts(roots[r_:r_ + 1], K, 8 * N * N, komi=0.0, base_seed=3, first_root=5 + r_)
+        for k in mc.KEYS:
             assert one[k][0] == sh[k][0, a_], k
     # shards by first_root are the whole
-    s1 = mx.expected(roots[:4], K, 8 * N * N, base_seed=3)
-    s2 = mx.expected(roots[4:], K, 8 * N * N, base_seed=3, first_root=4)
-    for k in ('legal',) + mx.KEYS:
+    s1 = mc.expected_move_playouts(roots[:4], K, 8 * N * N, base_seed=3)
+    s2 = mc.expected_move_playouts(roots[4:], K, 8 * N * N, base_seed=3, first_root=4)
+    for k in ('legal',) + mc.KEYS:
         assert np.array_equal(np.concatenate([s1[k], s2[k]]), e[k]), k
 
 
 def test_flat_mc_choice_restatement():
-    roots = mx.crafted_roots(5)
+    roots = mc.crafted_roots(5)
     A = 26
-    res = {'legal': mx.legal_mask(roots), 'black_wins': np.zeros((4, A), np.int32), 'white_wins': np.zeros((4, A), np.int32)}
+    res = {'legal': mc.legal_mask(roots), 'black_wins': np.zeros((4, A), np.int32), 'white_wins': np.zeros((4, A), np.int32)}
     res['black_wins'][:, 7] = 3
     res['white_wins'][:, 9] = 3
-    got = mx.flat_mc_choice(roots, res)
+    got = mc.flat_mc_choice(roots, res)
     # the mover's wins count: action 7 for black to move, 9 for white; the finished root has no move
     turn = roots[:, 2, 0, 0]
     assert got[3] == -1
@@ -139,4 +138,4 @@ def test_flat_mc_choice_restatement():
         assert got[i] == (9 if turn[i] else 7)
     res['black_wins'][:] = 0
     res['white_wins'][:] = 0
-    assert list(mx.flat_mc_choice(roots, res)[:3]) == [int(np.flatnonzero(res['legal'][i])[0]) for i in range(3)]
+    assert list(mc.flat_mc_choice(roots, res)[:3]) == [int(np.flatnonzero(res['legal'][i])[0]) for i in range(3)]

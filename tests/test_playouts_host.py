@@ -1,10 +1,10 @@
 """CPU: batched Monte Carlo playouts (gg_playouts_begin / gg_playouts_advance, gogame.batch_playouts) without a device -
 argument checks of the C-ABI, no CPU fallback in the Python API, and the expectation helpers the GPU tests build on
-(tests/playout_expect.py) against the C restatement."""
+(tests/mc_expect.py) against the C restatement."""
 import numpy as np
 import pytest
 
-import playout_expect as px
+import mc_expect as mc
 from oracle import c_oracle
 
 
@@ -59,7 +59,7 @@ def test_plies_from_generator_match_ply_by_ply_replay():
     st = np.zeros((B, 6, N, N), np.uint8)
     rng0 = c_oracle.rng_seed(11, B)
     fin, rng1, _ = c_oracle.batch_rollout(st, rng0, 96, auto_reset=False)
-    got = px.plies_from_rng(rng0, rng1)
+    got = mc.plies_from_rng(rng0, rng1)
     cur, rng, count = st.copy(), rng0.copy(), np.zeros(B, np.int64)
     for _ in range(96):
         alive = cur[:, 5, 0, 0] == 0
@@ -71,9 +71,9 @@ def test_plies_from_generator_match_ply_by_ply_replay():
 
 @pytest.mark.parametrize('N', [5, 9, 19])
 def test_ownership_helper_sums_to_the_areas(N):
-    roots = px.make_roots(N, 24, 3, max_ply=6 * N * N // 4, step=4 * N)
+    roots = mc.make_roots(N, 24, 3, max_ply=6 * N * N // 4, step=4 * N)
     fin, _, _ = c_oracle.batch_rollout(np.repeat(roots, 8, axis=0), c_oracle.rng_seed(5, 24 * 8), 8 * N * N, auto_reset=False)
-    own = px.ownership(fin)
+    own = mc.ownership(fin)
     b, w = c_oracle.batch_areas(fin)
     assert np.array_equal(own[:, 0].sum(axis=(1, 2)), b) and np.array_equal(own[:, 1].sum(axis=(1, 2)), w)
     assert not (own[:, 0] & own[:, 1]).any()
@@ -83,15 +83,15 @@ def test_ownership_helper_sums_to_the_areas(N):
 
 def test_expected_results_are_consistent():
     N, R, K = 9, 16, 6
-    roots = px.make_roots(N, R, 9, max_ply=60, step=4)
-    full = px.expected(roots, K, 8 * N * N, komi=0.0, with_ownership=True)
+    roots = mc.make_roots(N, R, 9, max_ply=60, step=4)
+    full = mc.expected_playouts(roots, K, 8 * N * N, komi=0.0, with_ownership=True)
     assert np.array_equal(full['black_wins'] + full['white_wins'] + full['draws'], np.full(R, K))
     assert full['unfinished'].sum() == 0 and full['plies_sum'][-1] == 0   # (the last root has ended: no plies)
     assert np.array_equal(full['ownership'][:, 0].sum(axis=(1, 2)) - full['ownership'][:, 1].sum(axis=(1, 2)), full['margin_sum'])
-    cut = px.expected(roots, K, 8, komi=0.0)
+    cut = mc.expected_playouts(roots, K, 8, komi=0.0)
     assert cut['unfinished'][:-1].min() > 0 and cut['plies_sum'].max() <= 8 * K
     # two shards by first_root are the whole
-    a = px.expected(roots[:5], K, 8 * N * N, first_root=0)
-    b = px.expected(roots[5:], K, 8 * N * N, first_root=5)
+    a = mc.expected_playouts(roots[:5], K, 8 * N * N, first_root=0)
+    b = mc.expected_playouts(roots[5:], K, 8 * N * N, first_root=5)
     for k in ('black_wins', 'margin_sum', 'plies_sum'):
         assert np.array_equal(np.concatenate([a[k], b[k]]), full[k])

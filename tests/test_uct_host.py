@@ -1,14 +1,12 @@
 """CPU: UCT tree search (gg_uct_begin / _select / _backup, gogame.batch_uct) without a device - argument checks of the C-ABI,
-no CPU fallback in the Python API, and the restatement the GPU tests build on (tests/uct_expect.py) checked against
-playout_expect and its own invariants."""
+no CPU fallback in the Python API, and the restatement the GPU tests build on (tests/mc_expect.py) checked against
+the C restatement and its own invariants."""
 import math
 
 import numpy as np
 import pytest
 
-import move_playout_expect as mx
-import playout_expect as px
-import uct_expect as ux
+import mc_expect as mc
 from oracle import c_oracle
 
 
@@ -72,16 +70,16 @@ def test_iteration_seed_is_the_generator_of_game_i(built):
     for seed in (0, 20260927, 2 ** 64 - 1):
         want = c_oracle.rng_seed(seed, 40)
         for i in range(40):
-            assert ux.iteration_seed(seed, i) == int(want[i]) == gogame._uct_seed(seed, i)
-    assert gogame._uct_seed(7, 12345) == int(mx.po_seed(7, 12345)[()])
+            assert int(mc.po_seed(seed, i)) == int(want[i]) == gogame._uct_seed(seed, i)
+    assert gogame._uct_seed(7, 12345) == int(mc.po_seed(7, 12345)[()])
 
 
 def test_score_is_the_float64_expression():
-    L = ux.log_table(8, 16)
+    L = mc.log_table(8, 16)
     assert L[0] == -np.inf and L[3] == math.log(48.0)
-    u = ux.score(5, 3, 16, L[4], math.sqrt(2))
+    u = mc.score(5, 3, 16, L[4], math.sqrt(2))
     assert u == (2.0 * 5 + 3) / (2.0 * 16) + math.sqrt(2) * math.sqrt(math.log(64) / 16)
-    assert ux.score(0, 0, 4, L[1], 0.0) == 0.0
+    assert mc.score(0, 0, 4, L[1], 0.0) == 0.0
 
 
 @pytest.mark.parametrize('N', [5, 9])
@@ -89,19 +87,19 @@ def test_first_iterations_expand_the_legal_actions_in_order(N):
     """With I <= |legal(root)| every iteration expands the root's next legal action, and that child's stats are exactly
     batch_playouts of the child with the iteration's seed."""
     K, seed, f0 = 3, 11, 2
-    roots = np.concatenate([px.make_roots(N, 3, 5, max_ply=N * N // 2, step=N)[1:2], mx.crafted_roots(N)[:3]])
+    roots = np.concatenate([mc.make_roots(N, 3, 5, max_ply=N * N // 2, step=N)[1:2], mc.crafted_roots(N)[:3]])
     I = 6
-    e = ux.expected(roots, I, K, base_seed=seed, first_root=f0)
+    e = mc.expected_uct(roots, I, K, base_seed=seed, first_root=f0)
     mp = -(-8 * N * N // 32) * 32
     for r in range(roots.shape[0]):
-        acts = ux.legal_actions(roots[r])
+        acts = mc.legal_actions(roots[r])
         assert acts.size >= I
         t = e['tree']
         assert list(t['action'][r, 1:]) == list(acts[:I]) and (t['parent'][r, 1:] == 0).all()
         assert t['parent'][r, 0] == -1 and t['action'][r, 0] == -1 and e['nodes'][r] == I + 1
         for i in range(I):
             kid = c_oracle.next_state(roots[r], int(acts[i]))
-            one = px.expected(kid[None], K, mp, base_seed=ux.iteration_seed(seed, i), first_root=f0 + r)
+            one = mc.expected_playouts(kid[None], K, mp, base_seed=int(mc.po_seed(seed, i)), first_root=f0 + r)
             assert t['visits'][r, i + 1] == K == e['visits'][r, acts[i]]
             for k in ('black_wins', 'white_wins', 'draws'):
                 assert t[k][r, i + 1] == one[k][0] == e[k][r, acts[i]], (r, i, k)
@@ -115,8 +113,8 @@ def test_search_invariants_and_terminal_nodes():
     children's (K times for a terminal node: it is evaluated each time it is reached); the search reaches terminal nodes;
     shards by first_root are the whole."""
     N, K, I = 5, 2, 60
-    roots = np.concatenate([mx.crafted_roots(N)[1:2], px.make_roots(N, 3, 9, max_ply=20, step=10)[1:2]])
-    e = ux.expected(roots, I, K, c=0.8, base_seed=4)
+    roots = np.concatenate([mc.crafted_roots(N)[1:2], mc.make_roots(N, 3, 9, max_ply=20, step=10)[1:2]])
+    e = mc.expected_uct(roots, I, K, c=0.8, base_seed=4)
     terminal_seen = 0
     for r, t in enumerate(e['trees']):
         assert e['root_visits'][r] == I * K == e['visits'][r].sum()
@@ -133,16 +131,16 @@ def test_search_invariants_and_terminal_nodes():
             assert t.stats[x, 1:].sum() == n[x]
         assert (e['tree']['visits'][r, used:] == 0).all() and (e['tree']['parent'][r, used:] == -1).all()
     assert terminal_seen > 0
-    a = ux.expected(roots[:1], I, K, c=0.8, base_seed=4)
-    b = ux.expected(roots[1:], I, K, c=0.8, base_seed=4, first_root=1)
-    for k in ux.ROOT_KEYS:
+    a = mc.expected_uct(roots[:1], I, K, c=0.8, base_seed=4)
+    b = mc.expected_uct(roots[1:], I, K, c=0.8, base_seed=4, first_root=1)
+    for k in mc.ROOT_KEYS:
         assert np.array_equal(np.concatenate([a[k], b[k]]), e[k]), k
 
 
 def test_ended_root_gives_the_trivial_result():
     N, K, I = 7, 4, 5
-    roots = mx.crafted_roots(N)[3:]
-    e = ux.expected(roots, I, K, base_seed=3)
+    roots = mc.crafted_roots(N)[3:]
+    e = mc.expected_uct(roots, I, K, base_seed=3)
     assert not e['legal'].any() and e['nodes'].tolist() == [1]
     assert e['root_visits'].tolist() == [I * K] and e['plies_sum'].tolist() == [0] and e['unfinished'].tolist() == [0]
     for k in ('visits', 'black_wins', 'white_wins', 'draws'):
@@ -150,17 +148,17 @@ def test_ended_root_gives_the_trivial_result():
     b, w = c_oracle.batch_areas(roots)
     col = 'black_wins' if b[0] > w[0] else ('white_wins' if b[0] < w[0] else 'draws')
     assert e['tree'][col][0, 0] == I * K
-    assert ux.most_visited(e).tolist() == [-1]
+    assert mc.most_visited(e).tolist() == [-1]
 
 
 def test_most_visited_restatement():
-    roots = mx.crafted_roots(5)
+    roots = mc.crafted_roots(5)
     A = 26
-    res = {'legal': mx.legal_mask(roots), 'visits': np.zeros((4, A), np.int32)}
+    res = {'legal': mc.legal_mask(roots), 'visits': np.zeros((4, A), np.int32)}
     res['visits'][:, 20] = 4                                   # (4, 0) and (4, 2): empty on the three live roots
     res['visits'][:, 22] = 4
-    assert ux.most_visited(res).tolist() == [20, 20, 20, -1]
+    assert mc.most_visited(res).tolist() == [20, 20, 20, -1]
     res['visits'][2, 7] = 9                                    # (1, 2) is occupied on the ko root: not a candidate
-    assert ux.most_visited(res).tolist() == [20, 20, 20, -1]
+    assert mc.most_visited(res).tolist() == [20, 20, 20, -1]
     res['visits'][:] = 0
-    assert ux.most_visited(res)[:3].tolist() == [int(np.flatnonzero(res['legal'][i])[0]) for i in range(3)]
+    assert mc.most_visited(res)[:3].tolist() == [int(np.flatnonzero(res['legal'][i])[0]) for i in range(3)]

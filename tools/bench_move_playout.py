@@ -15,23 +15,9 @@ harvest launches, run this once under `rocprofv3 --kernel-trace --stats -- pytho
 """
 import argparse
 import json
-import os
-import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-
-def _timed(fn):
-    import torch
-    torch.cuda.synchronize()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    out = fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) * 1e-3, out
+from mc_bench import median_timed, mid_game_roots   # (puts the repository on sys.path)
 
 
 def main():
@@ -49,9 +35,7 @@ def main():
     torch.cuda.set_device(0)
     N, R, K = args.size, args.roots, args.k
     A = N * N + 1
-    dev = 'cuda:0'
-    roots = gogame.batch_init_state(R, N, device=dev)
-    gogame.batch_rollout(roots, gogame.rng_seed(R, 17), args.plies, auto_reset=False)   # mid-game roots
+    roots = mid_game_roots(R, N, args.plies)
     kw = dict(komi=7.5, seed=1, slots=args.slots)
 
     # (b)'s input: the padded children, illegal slots (all-zero boards) marked as finished games
@@ -79,13 +63,7 @@ def main():
     plies = int(ref_a.plies_sum.sum())
     assert plies == int(ref_b.plies_sum[legal].sum()) == int(ref_b.plies_sum.sum())
 
-    ta, tb = [], []
-    for _ in range(args.reps):   # alternating
-        ta.append(_timed(run_a)[0])
-        tb.append(_timed(run_b)[0])
-    ta.sort()
-    tb.sort()
-    sa, sb = ta[len(ta) // 2], tb[len(tb) // 2]
+    (sa, _), (sb, _) = median_timed(run_a, run_b, reps=args.reps)
     T = int(legal.sum())
     res = {'metric': 'move_playout_plies_per_s', 'size': N, 'roots': R, 'k': K, 'root_plies': args.plies,
            'legal_pairs': T, 'padded_pairs': R * A, 'playouts': T * K, 'cus': int(_lib.lib().gg_device_cus()),

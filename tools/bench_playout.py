@@ -10,26 +10,8 @@ For the split of device time between the rollout chunks and the harvest launches
 """
 import argparse
 import json
-import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-
-def _timed(fn, reps):
-    import torch
-    times, out = [], None
-    for _ in range(reps):
-        torch.cuda.synchronize()
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        out = fn()
-        b.record()
-        b.synchronize()
-        times.append(a.elapsed_time(b) * 1e-3)
-    times.sort()
-    return times[len(times) // 2], out
+from mc_bench import median_timed   # (puts the repository on sys.path)
 
 
 def main():
@@ -54,7 +36,7 @@ def main():
     tracked = gogame.batch_track(gogame.batch_init_state(S, N, device='cuda:0'))
     rng = gogame.rng_seed(S, 3)
     gogame.batch_rollout_tracked(tracked, rng, 256)   # warm-up (and mid-game boards)
-    t_roll, _ = _timed(lambda: gogame.batch_rollout_tracked(tracked, rng, 256), args.reps)
+    (t_roll, _), = median_timed(lambda: gogame.batch_rollout_tracked(tracked, rng, 256), reps=args.reps)
     ceiling = S * 256 / t_roll
 
     res = {'metric': 'playout_plies_per_s', 'size': N, 'roots': R, 'k': K, 'slots': S, 'chunk_plies': args.chunk, 'cus': cus,
@@ -62,7 +44,7 @@ def main():
     for own in (False, True):
         run = lambda: gogame.batch_playouts(roots, K, komi=7.5, seed=1, slots=S, chunk_plies=args.chunk, ownership=own)
         run()   # warm-up
-        t, out = _timed(run, args.reps)
+        (t, out), = median_timed(run, reps=args.reps)
         plies = int(out.plies_sum.sum())
         tag = '_own' if own else ''
         res['seconds' + tag] = t

@@ -14,22 +14,8 @@ k_uct_backup, run once under `rocprofv3 --kernel-trace --stats -- python tools/b
 """
 import argparse
 import json
-import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-
-def _timed(fn):
-    import torch
-    torch.cuda.synchronize()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    out = fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) * 1e-3, out
+from mc_bench import median_timed, mid_game_roots   # (puts the repository on sys.path)
 
 
 def main():
@@ -47,8 +33,7 @@ def main():
     torch.cuda.set_device(0)
     N, K, I = args.size, args.k, args.iters
     for R in args.roots:
-        roots = gogame.batch_init_state(R, N, device='cuda:0')
-        gogame.batch_rollout(roots, gogame.rng_seed(R, 17), args.plies, auto_reset=False)   # mid-game roots
+        roots = mid_game_roots(R, N, args.plies)
         kw = dict(komi=7.5)
 
         def run_a():
@@ -61,15 +46,8 @@ def main():
         run_b()
         assert bool((ref.root_visits == I * K).all())
         plies_a = int(ref.plies_sum.sum())
-        ta, tb, plies_b = [], [], 0
-        for _ in range(args.reps):   # alternating
-            ta.append(_timed(run_a)[0])
-            t, outs = _timed(run_b)
-            tb.append(t)
-            plies_b = sum(int(o.plies_sum.sum()) for o in outs)
-        ta.sort()
-        tb.sort()
-        sa, sb = ta[len(ta) // 2], tb[len(tb) // 2]
+        (sa, _), (sb, outs) = median_timed(run_a, run_b, reps=args.reps)
+        plies_b = sum(int(o.plies_sum.sum()) for o in outs)
         P = R * K * I
         res = {'metric': 'uct_playouts_per_s', 'size': N, 'roots': R, 'k': K, 'iterations': I, 'root_plies': args.plies,
                'playouts': P, 'cus': int(_lib.lib().gg_device_cus()), 'jobs_per_slot': R * K / (256 * int(_lib.lib().gg_device_cus())),
