@@ -23,7 +23,8 @@ EXPORTS = (
     'gg_rng_seed', 'gg_batch_env_step_tracked_weighted', 'gg_batch_sample_weighted', 'gg_batch_sample_weighted_rows',
     'gg_batch_symmetry', 'gg_batch_symmetry_rows', 'gg_batch_env_step_scored', 'gg_playouts_begin', 'gg_playouts_advance',
     'gg_move_playouts_plan', 'gg_move_playouts_begin', 'gg_move_playouts_advance', 'gg_uct_begin', 'gg_uct_select',
-    'gg_uct_backup',
+    'gg_uct_backup', 'gg_batch_eye_mask', 'gg_batch_rollout_tracked_policy', 'gg_playouts_advance_policy',
+    'gg_move_playouts_advance_policy',
 )
 
 _vp, _i64, _i32, _u64 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_uint64
@@ -75,6 +76,12 @@ _SIGNATURES = {
     'gg_uct_begin': ([_vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
     'gg_uct_select': ([_i64, _i32, _i32, _i32, ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
     'gg_uct_backup': ([_i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
+    'gg_batch_eye_mask': ([_vp, _vp, _i64, _i32, _vp], _i32),
+    'gg_batch_rollout_tracked_policy': ([_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp], _i32),
+    'gg_playouts_advance_policy': ([_vp, _i64, _i32, _i32, _i64, _u64, _i32, _i32, ctypes.c_float, _i32, _i32, _vp, _vp, _vp, _vp,
+                                    _i64, _vp, _vp, _vp, _vp, _vp], _i32),
+    'gg_move_playouts_advance_policy': ([_vp, _i64, _i32, _vp, _i64, _i32, _i64, _u64, _i32, _i32, ctypes.c_float, _i32, _i32, _vp,
+                                         _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp], _i32),
 }
 
 _lib = None

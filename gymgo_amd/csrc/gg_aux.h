@@ -8,6 +8,34 @@
 
 namespace gg {
 
+// gg_batch_eye_mask: the mover's eyes (gg_common.h: eye_row) of byte-plane boards, one thread per point - off the hot
+// path, it exists so that the rule of the no_eye_fill playouts can be checked and used on its own.  All zero once the game has ended.
+__global__ __launch_bounds__(256) void k_eye_mask(const uint8_t *__restrict__ states, uint8_t *__restrict__ mask, int64_t B, int N) {
+  const int P = N * N;
+  const int64_t total = B * P;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t b = i / P;
+    const int q = (int)(i - b * P), r = q / N, c = q - r * N;
+    const uint8_t *g = states + b * 6 * (int64_t)P;
+    const uint8_t *me = g + (g[2 * P] ? P : 0), *op = g + (g[2 * P] ? 0 : P);
+    bool eye = !g[5 * P] && !me[q] && !op[q];
+    if (eye) {
+      if (r > 0) eye = eye && me[q - N];
+      if (r < N - 1) eye = eye && me[q + N];
+      if (c > 0) eye = eye && me[q - 1];
+      if (c < N - 1) eye = eye && me[q + 1];
+      int d = 0;
+      if (r > 0 && c > 0) d += op[q - N - 1] ? 1 : 0;
+      if (r > 0 && c < N - 1) d += op[q - N + 1] ? 1 : 0;
+      if (r < N - 1 && c > 0) d += op[q + N - 1] ? 1 : 0;
+      if (r < N - 1 && c < N - 1) d += op[q + N + 1] ? 1 : 0;
+      const bool edge = r == 0 || c == 0 || r == N - 1 || c == N - 1;
+      eye = eye && d <= (edge ? 0 : 1);
+    }
+    mask[i] = eye ? 1 : 0;
+  }
+}
+
 // GoEnv.uniform_random_action (gym_go/envs/go_env.py:78-81) for every game: one draw of the per-game generator, the
 // k-th valid action of plane 3 in ascending order, k == count: the pass (every point once the game has ended:
 // gogame.invalid_moves, gym_go/gogame.py:155-156).  Sixteen boards per wavefront: all loads of the group up front (plane 3

@@ -64,6 +64,26 @@ __device__ __forceinline__ uint32_t dpp0(uint32_t v) {
   return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xF, true);
 }
 
+// Playout policies of the tracked multi-ply kernels (include/gymgo_amd.h: GG_POLICY_*)
+constexpr int kPolUniform = 0, kPolNoEyeFill = 1;
+
+// One row of the MOVER'S EYES: an empty point whose on-board orthogonal neighbours are all the mover's stones and
+// whose on-board diagonal neighbours hold at most one opponent stone - none when the point lies on the first / last row or
+// column.  me / op = the row's stones, meU / meD = the mover's rows above / below WITH the border counted as the mover's (all
+// ones off the board), opU / opD = the opponent's rows above / below (zero off the board), full = the N-bit row mask,
+// edge = full on the first / last row, else the first and last column bit.
+__device__ __forceinline__ uint32_t eye_row(uint32_t me, uint32_t op, uint32_t meU, uint32_t meD, uint32_t opU, uint32_t opD,
+                                            uint32_t full, uint32_t edge, int N) {
+  const uint32_t left = shl1(me) | 1u, right = (me >> 1) | (1u << (N - 1));         // a mover's stone or the border on either side
+  const uint32_t orth = B3(left, right, meU, TA & TB & TC) & meD;
+  const uint32_t a = shl1(opU), b = opU >> 1, c = shl1(opD), d = opD >> 1;           // the four diagonals
+  const uint32_t any3 = B3(a, b, c, T_OR3), maj = B3(a, b, c, T_MAJ);
+  const uint32_t two = B3(d, any3, maj, T_ANDOR);                                    // at least two of the four
+  const uint32_t bad = B3(edge, any3 | d, two, T_SEL);
+  const uint32_t empty = B3(full, me, op, TA & ~(TB | TC) & 0xFF);
+  return B3(empty, orth, bad, T_AND_ANDN);
+}
+
 // OR-accumulation of a compile-time-indexed series of terms, two per v_bitop3_b32: `acc |= a; acc |= b` is fused by the compiler
 // into v_or3_b32 (4 issue cycles), the same truth table as a bitop3 issues in 2.  idx & 1 == 0: the term is parked in `pend`,
 // == 1: acc = acc | pend | term; a series of odd length ORs the last parked term in itself.

@@ -44,6 +44,10 @@ void launch_rollout_lat(int io, uint8_t *st, uint64_t *rng, int32_t *last_action
                         int auto_reset, bool w4, hipStream_t s);
 void launch_env_step_lat(uint32_t *tracked, uint64_t *rng, int64_t *steps_done, int64_t B, int32_t N, int auto_reset,
                          const EnvArgs &env, bool w4, hipStream_t s);
+void launch_rollout5_policy(int N, uint8_t *st, uint64_t *rng, int32_t *last_actions, int64_t *steps_done, int64_t B, uint32_t inv,
+                            int plies, int auto_reset, int nb, int grid, hipStream_t s);
+void launch_rollout_lat_policy(uint8_t *st, uint64_t *rng, int32_t *last_actions, int64_t *steps_done, int64_t B, int32_t N, int plies,
+                               int auto_reset, hipStream_t s);
 }
 
 namespace {
@@ -455,6 +459,8 @@ static void launch_harvest(const Args &a, int32_t N, int cus, hipStream_t s) {
 #undef GG_K
 }
 
+static bool policy_ok(int32_t policy) { return policy == GG_POLICY_UNIFORM || policy == GG_POLICY_NO_EYE_FILL; }
+
 // begin: zero the `cells` result cells (R, or R A), fill the slots with the first jobs
 template <class Args>
 static int32_t po_begin(const Args &a, int64_t cells, int32_t N, void *hip_stream) {
@@ -474,15 +480,15 @@ static int32_t po_begin(const Args &a, int64_t cells, int32_t N, void *hip_strea
 // advance: `chunks` times chunk_plies plies on every slot, then the harvest (refills, and in the first-move family the first
 // moves, happen there, between launches)
 template <class Args>
-static int32_t po_advance(const Args &a, int32_t N, int32_t chunk_plies, int32_t chunks, void *hip_stream) {
-  if (chunks < 0) return GG_E_BADARG;
+static int32_t po_advance(const Args &a, int32_t N, int32_t chunk_plies, int32_t chunks, int32_t policy, void *hip_stream) {
+  if (chunks < 0 || !policy_ok(policy)) return GG_E_BADARG;
   if (a.J == 0 || chunks == 0) return 0;
   OnDeviceOf on_dev(a.slots);
   const int cus = on_dev.cus();
   hipStream_t s = (hipStream_t)hip_stream;
   for (int c = 0; c < chunks; ++c) {
     // the existing tracked dispatch, auto_reset = 0: finished and empty slots stay frozen
-    if (int32_t e = gg_batch_rollout_tracked(a.slots, a.rng, nullptr, a.plies, a.S, N, chunk_plies, 0, hip_stream)) return e;
+    if (int32_t e = gg_batch_rollout_tracked_policy(a.slots, a.rng, nullptr, a.plies, a.S, N, chunk_plies, 0, policy, hip_stream)) return e;
     launch_harvest<false>(a, N, cus, s);
     if (int32_t e = (int32_t)hipGetLastError()) return e;
   }
@@ -1083,6 +1089,35 @@ int32_t gg_batch_rollout_tracked(uint32_t *tracked, uint64_t *rng, int32_t *last
   return (int32_t)hipGetLastError();
 }
 
+// The draw under a playout policy lives in the two families the playout queue runs on: k_rollout_lat where the
+// uniform path takes it, k_rollout5 where the uniform path takes it, and k_rollout_lat again - its plain form serves every batch
+// size and launch length - in the band that the uniform path gives to k_rollout4, which has no policy draw.
+int32_t gg_batch_rollout_tracked_policy(uint32_t *tracked, uint64_t *rng, int32_t *last_actions, int64_t *steps_done, int64_t B,
+                                        int32_t N, int32_t plies, int32_t auto_reset, int32_t policy, void *hip_stream) {
+  if (policy == GG_POLICY_UNIFORM) return gg_batch_rollout_tracked(tracked, rng, last_actions, steps_done, B, N, plies, auto_reset, hip_stream);
+  if (plies < 0 || policy != GG_POLICY_NO_EYE_FILL) return GG_E_BADARG;
+  GG_ENTER(tracked);
+  if (plies == 0) return 0;
+  if (!rng) return GG_E_NULLPTR;
+  uint8_t *st = reinterpret_cast<uint8_t *>(tracked);
+  if (!use_lat(cus, B, N, plies, true) && use_rollout5(cus, B, N, plies)) {
+    int grid5;
+    const int nb5 = boards_per_wave5(cus, B, grid5);
+    launch_rollout5_policy(N, st, rng, last_actions, steps_done, B, inv, plies, auto_reset, nb5, grid5, s);
+    return (int32_t)hipGetLastError();
+  }
+  launch_rollout_lat_policy(st, rng, last_actions, steps_done, B, N, plies, auto_reset, s);
+  return (int32_t)hipGetLastError();
+}
+
+int32_t gg_batch_eye_mask(const uint8_t *states, uint8_t *mask, int64_t B, int32_t N, void *hip_stream) {
+  GG_ENTER(states);
+  if (!mask) return GG_E_NULLPTR;
+  const int64_t blocks = (B * N * N + 255) / 256;
+  k_eye_mask<<<(unsigned)(blocks < (int64_t)cus * 64 ? blocks : (int64_t)cus * 64), 256, 0, s>>>(states, mask, B, N);
+  return (int32_t)hipGetLastError();
+}
+
 int32_t gg_batch_play_moves_tracked(uint32_t *tracked, const int32_t *moves, int32_t *played, int64_t B, int32_t N, int32_t T,
                                     void *hip_stream) {
   if (T < 0) return GG_E_BADARG;
@@ -1220,7 +1255,18 @@ int32_t gg_playouts_advance(const uint32_t *roots, int64_t R, int32_t N, int32_t
   if (int32_t e = po_args(a, 1, R, true, true, roots, R, N, K, first_root, base_seed, max_plies, chunk_plies, komi, slots, rng, plies,
                           job, S, counter, counts, sums, ownership))
     return e;
-  return po_advance(a, N, chunk_plies, chunks, hip_stream);
+  return po_advance(a, N, chunk_plies, chunks, GG_POLICY_UNIFORM, hip_stream);
+}
+
+int32_t gg_playouts_advance_policy(const uint32_t *roots, int64_t R, int32_t N, int32_t K, int64_t first_root, uint64_t base_seed,
+                                   int32_t max_plies, int32_t chunk_plies, float komi, int32_t chunks, int32_t policy,
+                                   uint32_t *slots, uint64_t *rng, int64_t *plies, int64_t *job, int64_t S, int64_t *counter,
+                                   int32_t *counts, int64_t *sums, int32_t *ownership, void *hip_stream) {
+  PoArgs a;
+  if (int32_t e = po_args(a, 1, R, true, true, roots, R, N, K, first_root, base_seed, max_plies, chunk_plies, komi, slots, rng, plies,
+                          job, S, counter, counts, sums, ownership))
+    return e;
+  return po_advance(a, N, chunk_plies, chunks, policy, hip_stream);
 }
 
 int32_t gg_move_playouts_plan(const uint32_t *roots, int64_t R, int32_t N, int32_t *offsets, int32_t *plan, void *hip_stream) {
@@ -1256,7 +1302,19 @@ int32_t gg_move_playouts_advance(const uint32_t *roots, int64_t R, int32_t N, co
   if (int32_t e = mp_args(m, roots, R, N, plan, T, K, first_root, base_seed, max_plies, chunk_plies, komi, slots, rng, plies, job,
                           S, counter, counts, sums))
     return e;
-  return po_advance(m, N, chunk_plies, chunks, hip_stream);
+  return po_advance(m, N, chunk_plies, chunks, GG_POLICY_UNIFORM, hip_stream);
+}
+
+int32_t gg_move_playouts_advance_policy(const uint32_t *roots, int64_t R, int32_t N, const int32_t *plan, int64_t T, int32_t K,
+                                        int64_t first_root, uint64_t base_seed, int32_t max_plies, int32_t chunk_plies,
+                                        float komi, int32_t chunks, int32_t policy, uint32_t *slots, uint64_t *rng,
+                                        int64_t *plies, int64_t *job, int64_t S, int64_t *counter, int32_t *counts,
+                                        int64_t *sums, void *hip_stream) {
+  MpArgs m;
+  if (int32_t e = mp_args(m, roots, R, N, plan, T, K, first_root, base_seed, max_plies, chunk_plies, komi, slots, rng, plies, job,
+                          S, counter, counts, sums))
+    return e;
+  return po_advance(m, N, chunk_plies, chunks, policy, hip_stream);
 }
 
 int32_t gg_uct_begin(const uint32_t *roots, int64_t R, int32_t N, int32_t I, int32_t K, uint32_t *boards, int32_t *child,

@@ -525,7 +525,8 @@ struct LdsLat {
 // also pays for every instruction-cache line it has to jump to (3.19 us per hipGraph node at config 2's size against 3.36)
 // WPB: waves per workgroup, each wave an independent group of boards (a launch of single-wave workgroups enters the machine over
 // ~0.26 ns per workgroup - tools/exp/oneply_ramp.py - which a ONE-ply launch of a thousand workgroups feels: k_rollout_lat_w4)
-template <int R, bool FULLN, bool AUTO, int IO, int WPB, bool SHORT>
+// POL: the playout policy of the draw (kPolUniform; kPolNoEyeFill: tracked boards, the plain form - DESIGN 15)
+template <int R, bool FULLN, bool AUTO, int IO, int WPB, bool SHORT, int POL = kPolUniform>
 __device__ __forceinline__ void rollout_lat_body(uint8_t *__restrict__ states, uint64_t *__restrict__ rng,
                                                  int32_t *__restrict__ last_actions,
                                                  int64_t *__restrict__ steps_done, int64_t B, int N, int plies,
@@ -642,16 +643,27 @@ __device__ __forceinline__ void rollout_lat_body(uint8_t *__restrict__ states, u
         }
         uh = (uint32_t)__builtin_amdgcn_ds_bpermute((lane_b0 + (t & (LPB - 1))) << 2, (int)uq);
       }
-      const uint32_t valid = full & ~inv;
+      uint32_t valid = full & ~inv;
+      if constexpr (POL == kPolNoEyeFill) {
+        // no_eye_fill: the mover's eyes leave the candidates (rows above / below: the neighbouring lanes; the border counts as
+        // the mover's), the pass is drawn only when nothing else is left; the generator advances as ever
+        // (the DPP moves run in every lane, outside any select: a lane masked off while its neighbour reads it would hand over zero)
+        const bool top = r == 0, bot = r == N - 1;
+        const uint32_t aboveM = lat_above<LPB>(me), belowM = lat_below<LPB>(me);
+        const uint32_t aboveO = lat_above<LPB>(op), belowO = lat_below<LPB>(op);
+        const uint32_t meU = aboveM | (top ? full : 0u), meD = belowM | (bot ? full : 0u);
+        const uint32_t edge = (top || bot) ? full : (1u | (1u << (N - 1)));
+        valid &= ~eye_row(me, op, meU, meD, aboveO, belowO, full, edge, N);
+      }
       const uint32_t cnt = (uint32_t)__popc(valid);
       const uint32_t incl = lat_board_scan<LPB>(cnt);
       const uint32_t total = lat_board_sum<LPB>(cnt);
-      const uint32_t k = __umulhi(uh, total + 1u);
+      const uint32_t k = __umulhi(uh, POL == kPolNoEyeFill ? total : total + 1u);
       const uint32_t tt = k - (incl - cnt);
       const bool hit = live && tt < cnt;                 // this lane's row holds the k-th valid point
       const uint32_t pos = lat_kth_bit<L::kBits>(valid, tt);
       const uint32_t Q = hit ? (1u << pos) : 0u;
-      const bool pass = k == total;                      // (the same in every lane of the board)
+      const bool pass = POL == kPolNoEyeFill ? total == 0u : k == total;   // (the same in every lane of the board)
       {   // the action of the board's last live ply: the hit lane holds it, every lane holds a pass, the others -1
         const int cand = hit ? rN + (int)pos : (pass ? P : -1);
         lastv = (int)B3(lv, (uint32_t)cand, (uint32_t)lastv, T_SEL);
@@ -694,6 +706,14 @@ __global__ __launch_bounds__(kWave, 4) void k_rollout_lat(uint8_t *__restrict__ 
                                                           int64_t *__restrict__ steps_done, int64_t B, int N, int plies,
                                                           int auto_reset) {
   rollout_lat_body<R, FULLN, AUTO, IO, 1, SHORT>(states, rng, last_actions, steps_done, B, N, plies, auto_reset);
+}
+// tracked boards, the draw under a playout policy (the plain form: every launch length from one ply up)
+template <int R, bool FULLN, bool AUTO, int POL>
+__global__ __launch_bounds__(kWave, 4) void k_rollout_lat_pol(uint8_t *__restrict__ states, uint64_t *__restrict__ rng,
+                                                              int32_t *__restrict__ last_actions,
+                                                              int64_t *__restrict__ steps_done, int64_t B, int N, int plies,
+                                                              int auto_reset) {
+  rollout_lat_body<R, FULLN, AUTO, 2, 1, false, POL>(states, rng, last_actions, steps_done, B, N, plies, auto_reset);
 }
 // tracked boards, a few plies per launch: four waves per workgroup
 template <int R, bool FULLN, bool AUTO, bool SHORT>

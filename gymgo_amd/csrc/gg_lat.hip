@@ -49,6 +49,25 @@ void launch_rollout_lat(int io, uint8_t *st, uint64_t *rng, int32_t *last_action
 }
 #undef GG_LAT
 
+// gg_batch_rollout_tracked_policy (policy != uniform): the plain tracked form with the policy in its draw, whatever the launch
+// length and the batch size (one wave per four / two boards)
+#define GG_LATP(R, F)                                                                                                           \
+  do {                                                                                                                          \
+    const unsigned grid_ = (unsigned)((B + Lat<R>::NBW - 1) / Lat<R>::NBW);                                                     \
+    if (auto_reset) k_rollout_lat_pol<R, F, true, kPolNoEyeFill><<<grid_, kWave, 0, s>>>(st, rng, last_actions, steps_done, B, N, plies, 1); \
+    else k_rollout_lat_pol<R, F, false, kPolNoEyeFill><<<grid_, kWave, 0, s>>>(st, rng, last_actions, steps_done, B, N, plies, 0); \
+  } while (0)
+void launch_rollout_lat_policy(uint8_t *st, uint64_t *rng, int32_t *last_actions, int64_t *steps_done, int64_t B, int32_t N, int plies,
+                               int auto_reset, hipStream_t s) {
+  if (N == 9) GG_LATP(9, true);
+  else if (N < 9) GG_LATP(9, false);
+  else if (N == 13) GG_LATP(13, true);
+  else if (N < 13) GG_LATP(13, false);
+  else if (N == 19) GG_LATP(19, true);
+  else GG_LATP(19, false);
+}
+#undef GG_LATP
+
 // gg_batch_env_step_tracked on a batch that leaves the SIMDs under-filled: the same one-ply kernel with GoEnv.step's outputs
 #define GG_LATE(R, F)                                                                                                          \
   do {                                                                                                                         \

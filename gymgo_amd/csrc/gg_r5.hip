@@ -28,6 +28,14 @@ void launch_rollout5(int io, int N, uint8_t *st, uint64_t *rng, int32_t *last_ac
 #undef GG_R5
 }
 
+// gg_batch_rollout_tracked_policy (policy != uniform) on a full machine: tracked boards, the policy in the draw of phase 1
+void launch_rollout5_policy(int N, uint8_t *st, uint64_t *rng, int32_t *last_actions, int64_t *steps_done, int64_t B, uint32_t inv,
+                            int plies, int auto_reset, int nb, int grid, hipStream_t s) {
+  if (N == 19) k_rollout5_pol<19, 2><<<grid, kWave, 0, s>>>(st, rng, last_actions, steps_done, B, inv, plies, auto_reset, nb);
+  else if (N == 13) k_rollout5_pol<13, 2><<<grid, kWave, 0, s>>>(st, rng, last_actions, steps_done, B, inv, plies, auto_reset, nb);
+  else k_rollout5_pol<9, 2><<<grid, kWave, 0, s>>>(st, rng, last_actions, steps_done, B, inv, plies, auto_reset, nb);
+}
+
 }  // namespace gg
 
 #ifdef GG_AB_SWEEPS

@@ -710,15 +710,54 @@ def batch_untrack(tracked, out=None):
     return states
 
 
-def batch_rollout_tracked(tracked, rng, plies, auto_reset=True, last_actions=None, steps_done=None):
-    """IN PLACE batch_rollout on tracked boards (gg_batch_rollout_tracked)."""
+POLICIES = {'uniform': 0, 'no_eye_fill': 1}   # GG_POLICY_* of include/gymgo_amd.h
+
+
+def _policy_code(policy):
+    """The playout policy's C code; ValueError for anything but the names of POLICIES (checked before a device is touched)."""
+    if not any(policy is k or (type(policy) is type(k) and policy == k) for k in POLICIES):
+        raise ValueError("policy must be 'uniform' or 'no_eye_fill' (got %r)" % (policy,))
+    return POLICIES[policy]
+
+
+def batch_rollout_tracked(tracked, rng, plies, auto_reset=True, last_actions=None, steps_done=None, *, policy='uniform'):
+    """IN PLACE batch_rollout on tracked boards (gg_batch_rollout_tracked).  policy: 'uniform' (every legal point and the
+    pass alike) or 'no_eye_fill' (the mover's eyes - batch_eye_mask - are never played, the pass only when nothing else is
+    left; gg_batch_rollout_tracked_policy)."""
+    pol = _policy_code(policy)
     N = _tracked_size(tracked)
     B = tracked.shape[0]
-    code = _lib.lib().gg_batch_rollout_tracked(
-        _lib.dev_ptr(tracked, _I32, 'tracked'), _lib.dev_ptr(rng, _I64, 'rng'), _lib.dev_ptr(last_actions, _I32, 'last_actions'),
-        _lib.dev_ptr(steps_done, _I64, 'steps_done'), B, N, int(plies), int(bool(auto_reset)), _lib.stream_ptr(tracked.device))
-    _lib.check(code, 'gg_batch_rollout_tracked')
+    args = (_lib.dev_ptr(tracked, _I32, 'tracked'), _lib.dev_ptr(rng, _I64, 'rng'), _lib.dev_ptr(last_actions, _I32, 'last_actions'),
+            _lib.dev_ptr(steps_done, _I64, 'steps_done'), B, N, int(plies), int(bool(auto_reset)))
+    if pol:
+        _lib.check(_lib.lib().gg_batch_rollout_tracked_policy(*args, pol, _lib.stream_ptr(tracked.device)),
+                   'gg_batch_rollout_tracked_policy')
+    else:
+        _lib.check(_lib.lib().gg_batch_rollout_tracked(*args, _lib.stream_ptr(tracked.device)), 'gg_batch_rollout_tracked')
     return tracked
+
+
+def batch_eye_mask(batch_states):
+    """The mover's eyes of every board -> uint8 [B, N, N] (gg_batch_eye_mask): an empty point whose orthogonal neighbours on the
+    board are all the mover's stones and of whose diagonal neighbours on the board at most one is the opponent's - none when
+    the point lies on the first / last row or column.  All zero once the game has ended.  These are the points the
+    'no_eye_fill' playouts never play."""
+    box = _Box(batch_states)
+    st = box.t
+    if st.dim() != 4 or st.shape[1] != govars.NUM_CHNLS or st.shape[2] != st.shape[3]:
+        raise ValueError('batch_states must be [B, 6, N, N] (got %s)' % (tuple(st.shape),))
+    B, N = st.shape[0], st.shape[2]
+    mask = torch.empty((B, N, N), dtype=_U8, device=st.device)
+    code = _lib.lib().gg_batch_eye_mask(_lib.dev_ptr(st, _U8, 'states'), _lib.dev_ptr(mask, _U8, 'mask'), B, N,
+                                        _lib.stream_ptr(st.device))
+    _lib.check(code, 'gg_batch_eye_mask')
+    return _back(box, mask)
+
+
+def eye_mask(state):
+    """batch_eye_mask of one state [6, N, N] -> uint8 [N, N]."""
+    box = _Box(state)
+    return _back(box, batch_eye_mask(box.t[None]), row0=True)
 
 
 def batch_play_moves_tracked(tracked, moves, played=None):
@@ -832,15 +871,15 @@ def _drive_playouts(advance, counter, J, S, max_plies, chunk_plies, dev, what):
             ev.synchronize()
 
 
-def _run_queue(family, what, head, komi, bufs, counter, J, S, max_plies, chunk_plies, dev):
-    """gg_<family>_begin, then gg_<family>_advance until the counter drains (_drive_playouts).  head: the arguments up to
-    chunk_plies, bufs: those from slots on (_queue_ptrs, and what the family adds); advance takes komi and the chunk count
-    between the two."""
-    begin, advance = 'gg_%s_begin' % family, 'gg_%s_advance' % family
+def _run_queue(family, what, head, komi, bufs, counter, J, S, max_plies, chunk_plies, dev, policy=0):
+    """gg_<family>_begin, then gg_<family>_advance_policy until the counter drains (_drive_playouts).  head: the arguments up
+    to chunk_plies, bufs: those from slots on (_queue_ptrs, and what the family adds); advance takes komi, the chunk count
+    and the playout policy's code between the two."""
+    begin, advance = 'gg_%s_begin' % family, 'gg_%s_advance_policy' % family
     begin_fn, advance_fn = getattr(_lib.lib(), begin), getattr(_lib.lib(), advance)
     stream = _lib.current_raw_stream(dev)   # torch's current stream: the counter copies of _drive_playouts go there too
     _lib.check(begin_fn(*head, *bufs, stream), begin)
-    _drive_playouts(lambda n: _lib.check(advance_fn(*head, float(komi), n, *bufs, stream), advance),
+    _drive_playouts(lambda n: _lib.check(advance_fn(*head, float(komi), n, int(policy), *bufs, stream), advance),
                     counter, J, S, max_plies, chunk_plies, dev, what)
 
 
@@ -863,7 +902,7 @@ def _queue_ptrs(slots, rng, plies, job, counter, counts, sums):
             _lib.dev_ptr(counts, _I32, 'counts'), _lib.dev_ptr(sums, _I64, 'sums'))
 
 
-def _run_playouts(roots, R, N, K, max_plies, komi, seed, first_root, ownership, S, chunk_plies, dev, buffers=None):
+def _run_playouts(roots, R, N, K, max_plies, komi, seed, first_root, ownership, S, chunk_plies, dev, buffers=None, policy=0):
     """Device work of batch_playouts on tracked roots: -> (counts int32 [R, 4], sums int64 [R, 2], own or None); no launch
     for R = 0.  buffers: _playout_buffers(R, S, N, dev) to reuse (a search evaluates its leaves with the same buffers every
     iteration)."""
@@ -873,7 +912,7 @@ def _run_playouts(roots, R, N, K, max_plies, komi, seed, first_root, ownership, 
     if R > 0:
         head = (_lib.dev_ptr(roots, _I32, 'roots'), R, N, K, int(first_root), int(seed) & _M64, int(max_plies), int(chunk_plies))
         _run_queue('playouts', 'batch_playouts', head, komi, _queue_ptrs(*buffers) + (_lib.dev_ptr(own, _I32, 'ownership'),),
-                   counter, R * K, S, max_plies, chunk_plies, dev)
+                   counter, R * K, S, max_plies, chunk_plies, dev, policy)
     return counts, sums, own
 
 
@@ -915,6 +954,7 @@ def _back(box, res, row0=False):
 
 def _single(batch_fn, state, *args, **kw):
     """The single-state form of a batch function: state [6, N, N] as a batch of one, row 0 of every result."""
+    _policy_code(kw.get('policy', 'uniform'))
     box = _Box(state)
     return _back(box, batch_fn(box.t[None], *args, **kw), row0=True)
 
@@ -929,7 +969,7 @@ def _best_legal(box, legal, score):
 
 
 def batch_playouts(batch_states, playouts, max_plies=None, komi=0.0, seed=20260927, first_root=0, ownership=False, slots=None,
-                   chunk_plies=32):
+                   chunk_plies=32, *, policy='uniform'):
     """`playouts` uniform-random playouts of every root of batch_states ([R, 6, N, N]) to the end of the game, scored and
     reduced per root on the device -> Playouts (device tensors for a device tensor, NumPy arrays for NumPy input).
 
@@ -938,13 +978,15 @@ def batch_playouts(batch_states, playouts, max_plies=None, komi=0.0, seed=202609
     (then it also counts as unfinished) and is scored as it stands.  Results are integer sums: they do not depend on
     `slots` (working boards, default: enough to fill the device) or `chunk_plies` (plies per rollout launch between two
     harvests; max_plies must be a multiple of it), and shards by first_root concatenate to the whole.  Default max_plies:
-    8 N^2 rounded up to a multiple of chunk_plies.  The roots are not modified."""
+    8 N^2 rounded up to a multiple of chunk_plies.  The roots are not modified.
+    policy: what a playout ply draws from - 'uniform' (batch_rollout's sampler) or 'no_eye_fill' (batch_rollout_tracked)."""
+    pol = _policy_code(policy)
     box = _Box(batch_states)
     st = box.t
     R, N, K, max_plies, chunk_plies = _playout_args(st, playouts, max_plies, chunk_plies, first_root)
     S = max(1, min(int(_default_slots(slots)), R * K))
     counts, sums, own = _run_playouts(_track_roots(st), R, N, K, max_plies, komi, seed, first_root, ownership, S, chunk_plies,
-                                      st.device)
+                                      st.device, policy=pol)
     return _back(box, Playouts(counts[:, 0], counts[:, 1], counts[:, 2], counts[:, 3], sums[:, 0], sums[:, 1], own))
 
 
@@ -964,7 +1006,7 @@ white_wins / draws / unfinished (int32), margin_sum / plies_sum (int64; plies_su
 Playouts, all zero where the move is not legal."""
 
 
-def _run_move_playouts(roots, R, N, K, max_plies, komi, seed, first_root, slots, chunk_plies, dev):
+def _run_move_playouts(roots, R, N, K, max_plies, komi, seed, first_root, slots, chunk_plies, dev, policy=0):
     """Device work of batch_move_playouts on tracked roots: -> (legal bool [R, A], counts int32 [R, A, 4], sums [R, A, 2]); no
     launch for R = 0."""
     A = N * N + 1
@@ -988,12 +1030,12 @@ def _run_move_playouts(roots, R, N, K, max_plies, komi, seed, first_root, slots,
     slot_bufs = _slot_buffers(S, N, dev)
     head = (rp, R, N, pp, T, K, int(first_root), int(seed) & _M64, int(max_plies), int(chunk_plies))
     _run_queue('move_playouts', 'batch_move_playouts', head, komi, _queue_ptrs(*slot_bufs, counts, sums), slot_bufs[4], J, S,
-               max_plies, chunk_plies, dev)
+               max_plies, chunk_plies, dev, policy)
     return legal, counts, sums
 
 
 def batch_move_playouts(batch_states, playouts, max_plies=None, komi=0.0, seed=20260927, first_root=0, slots=None,
-                        chunk_plies=32):
+                        chunk_plies=32, *, policy='uniform'):
     """Flat Monte Carlo: `playouts` playouts after every legal first move of every root of batch_states ([R, 6, N, N]),
     reduced per (root, action) on the device -> MovePlayouts of [R, N*N + 1] (device tensors for a device tensor, NumPy
     arrays for NumPy input).
@@ -1004,12 +1046,14 @@ def batch_move_playouts(batch_states, playouts, max_plies=None, komi=0.0, seed=2
     (A = N*N + 1): it starts from next_state(root_r, a) and is played and scored as batch_playouts plays its playouts,
     max_plies counting the plies after the first move.  So row (r, a) equals batch_playouts(next_state(root_r, a)[None],
     playouts, first_root=(first_root + r) * A + a, ...).  Defaults, validation and the invariance under slots, chunk_plies
-    and sharding by first_root are those of batch_playouts.  The roots are not modified."""
+    and sharding by first_root are those of batch_playouts.  The roots are not modified.
+    policy: as in batch_playouts; it governs the playout plies only - every legal first move is tried."""
+    pol = _policy_code(policy)
     box = _Box(batch_states)
     st = box.t
     R, N, K, max_plies, chunk_plies = _playout_args(st, playouts, max_plies, chunk_plies, first_root)
     legal, counts, sums = _run_move_playouts(_track_roots(st), R, N, K, max_plies, komi, seed, first_root, _default_slots(slots),
-                                             chunk_plies, st.device)
+                                             chunk_plies, st.device, policy=pol)
     return _back(box, MovePlayouts(legal, counts[..., 0], counts[..., 1], counts[..., 2], counts[..., 3], sums[..., 0],
                                    sums[..., 1]))
 
@@ -1023,6 +1067,7 @@ def flat_mc_actions(batch_states, playouts, **kw):
     """The flat Monte Carlo move of every root -> int64 [R]: the legal action with the most (mover's wins - mover's losses)
     over batch_move_playouts(batch_states, playouts, **kw), the mover being the root's turn (plane 2); ties go to the lowest
     action, a root without a legal move gives -1."""
+    _policy_code(kw.get('policy', 'uniform'))
     box = _Box(batch_states)
     res = batch_move_playouts(box.t, playouts, **kw)
     bw, ww = res.black_wins.to(_I64), res.white_wins.to(_I64)
@@ -1065,7 +1110,7 @@ def _legal_roots(st):
     return legal & ~ended[:, None]
 
 
-def _run_uct(roots, R, N, I, K, c, max_plies, komi, seed, first_root, S, chunk_plies, dev):
+def _run_uct(roots, R, N, I, K, c, max_plies, komi, seed, first_root, S, chunk_plies, dev, policy=0):
     """Device work of batch_uct on tracked roots -> (child int32 [R, I+1, A], links [R, I+1, 2], stats [R, I+1, 4],
     nodes [R], totals int64 [R, 2]); no launch for R = 0."""
     L = _lib.lib()
@@ -1095,14 +1140,14 @@ def _run_uct(roots, R, N, I, K, c, max_plies, komi, seed, first_root, S, chunk_p
         _lib.check(L.gg_uct_select(R, N, I, K, c, _lib.dev_ptr(log_table, torch.float64, 'log_table'), *tree, lp, mp, ip,
                                    stream), 'gg_uct_select')
         _lib.check(L.gg_batch_play_moves_tracked(lp, mp, None, R, N, 1, stream), 'gg_batch_play_moves_tracked')
-        _run_playouts(leaf, R, N, K, max_plies, komi, _uct_seed(seed, i), first_root, False, S, chunk_plies, dev, pbufs)
+        _run_playouts(leaf, R, N, K, max_plies, komi, _uct_seed(seed, i), first_root, False, S, chunk_plies, dev, pbufs, policy)
         _lib.check(L.gg_uct_backup(R, N, I, K, p(counts, _I32, 'counts'), p(sums, _I64, 'sums'), p(totals, _I64, 'totals'),
                                    tree[0], tree[2], tree[3], lp, mp, ip, stream), 'gg_uct_backup')
     return child, links, stats, nodes, totals
 
 
 def batch_uct(batch_states, iterations, playouts, c=math.sqrt(2), max_plies=None, komi=0.0, seed=20260927, first_root=0,
-              slots=None, chunk_plies=32, tree=False):
+              slots=None, chunk_plies=32, tree=False, *, policy='uniform'):
     """UCT search of `iterations` iterations from every root of batch_states ([R, 6, N, N]), the leaves evaluated with
     `playouts` playouts each -> Uct (device tensors for a device tensor, NumPy arrays for NumPy input).
 
@@ -1119,14 +1164,16 @@ def batch_uct(batch_states, iterations, playouts, c=math.sqrt(2), max_plies=None
     tree=True also returns the whole tree (UctTree).  The roots are not modified.
 
     Device memory of the tree: R * (iterations + 1) * (4 (5N + 1) + 4 (N^2 + 1) + 24) bytes (boards, child tables, links and
-    stats: 1 856 bytes per node at 19x19, 124 MB for 1 024 roots x 64 iterations), plus the playout slots of batch_playouts."""
+    stats: 1 856 bytes per node at 19x19, 124 MB for 1 024 roots x 64 iterations), plus the playout slots of batch_playouts.
+    policy: as in batch_playouts; it governs the playouts of the leaves only - the tree keeps every legal action."""
+    pol = _policy_code(policy)
     box = _Box(batch_states)
     st = box.t
     R, N, K, max_plies, chunk_plies = _playout_args(st, playouts, max_plies, chunk_plies, first_root)
     I, c = _uct_args(iterations, K, c)
     S = max(1, min(int(_default_slots(slots)), R * K))
     child, links, stats, nodes, totals = _run_uct(_track_roots(st), R, N, I, K, c, max_plies, komi, seed, first_root, S,
-                                                  chunk_plies, st.device)
+                                                  chunk_plies, st.device, policy=pol)
     rc = child[:, 0, :]
     kid = torch.gather(stats, 1, rc.clamp(min=0).long()[..., None].expand(R, N * N + 1, 4))
     kid = torch.where((rc >= 0)[..., None], kid, torch.zeros_like(kid))
@@ -1143,6 +1190,7 @@ def uct(state, iterations, playouts, **kw):
 def uct_actions(batch_states, iterations, playouts, **kw):
     """The UCT move of every root -> int64 [R]: the legal root child with the most visits after batch_uct(batch_states,
     iterations, playouts, **kw); ties go to the lowest action, a root without a legal move gives -1."""
+    _policy_code(kw.get('policy', 'uniform'))
     box = _Box(batch_states)
     res = batch_uct(box.t, iterations, playouts, **kw)
     return _best_legal(box, res.legal, res.visits.to(_I64))

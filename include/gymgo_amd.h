@@ -452,6 +452,38 @@ int32_t gg_uct_backup(int64_t R, int32_t N, int32_t I, int32_t K, const int32_t 
                       uint32_t *boards, const int32_t *links, int32_t *stats, const uint32_t *leaf, const int32_t *move,
                       const int32_t *leaf_id, void *hip_stream);
 
+/*
+ * Playout policies: what a ply of the tracked rollout - and so of every playout above - draws from.
+ *   GG_POLICY_UNIFORM      the sampler of gg_batch_rollout: every legal point and the pass with equal probability
+ *   GG_POLICY_NO_EYE_FILL  never fill your own eye, pass only when nothing else is left.  A point p is an EYE OF THE MOVER
+ *                          when p is empty, every orthogonal neighbour of p on the board holds a stone of the mover and, with
+ *                          D = the diagonal neighbours of p on the board that hold an opponent stone, D = 0 if p lies on the
+ *                          first or last row or column, else D <= 1.  The candidates are the points whose invalid bit is
+ *                          clear and that are not eyes of the mover, in ascending order, n of them.  A ply advances the
+ *                          generator exactly once as the uniform sampler does, whether or not the draw is used; the action
+ *                          is the pass if n = 0, else the floor((u >> 32) n / 2^32)-th candidate.
+ * First moves (gg_move_playouts_*) and the tree (gg_uct_*) keep all legal actions: the policy governs playout plies only.
+ *   gg_batch_eye_mask                mask uint8 [B][N][N] = the mover's eyes of byte-plane boards uint8 [B][6][N][N] (all
+ *                                    zero for a game that has ended); checks as gg_batch_invalid_mask
+ *   gg_batch_rollout_tracked_policy  gg_batch_rollout_tracked with the policy (GG_POLICY_UNIFORM forwards to it)
+ *   gg_playouts_advance_policy, gg_move_playouts_advance_policy: the _advance calls with `policy` after `chunks`
+ * GG_E_BADARG for a policy other than the two above, checked with the other arguments before any device work.
+ */
+#define GG_POLICY_UNIFORM 0
+#define GG_POLICY_NO_EYE_FILL 1
+int32_t gg_batch_eye_mask(const uint8_t *states, uint8_t *mask, int64_t B, int32_t N, void *hip_stream);
+int32_t gg_batch_rollout_tracked_policy(uint32_t *tracked, uint64_t *rng, int32_t *last_actions, int64_t *steps_done, int64_t B,
+                                        int32_t N, int32_t plies, int32_t auto_reset, int32_t policy, void *hip_stream);
+int32_t gg_playouts_advance_policy(const uint32_t *roots, int64_t R, int32_t N, int32_t K, int64_t first_root, uint64_t base_seed,
+                                   int32_t max_plies, int32_t chunk_plies, float komi, int32_t chunks, int32_t policy,
+                                   uint32_t *slots, uint64_t *rng, int64_t *plies, int64_t *job, int64_t S, int64_t *counter,
+                                   int32_t *counts, int64_t *sums, int32_t *ownership, void *hip_stream);
+int32_t gg_move_playouts_advance_policy(const uint32_t *roots, int64_t R, int32_t N, const int32_t *plan, int64_t T, int32_t K,
+                                        int64_t first_root, uint64_t base_seed, int32_t max_plies, int32_t chunk_plies,
+                                        float komi, int32_t chunks, int32_t policy, uint32_t *slots, uint64_t *rng,
+                                        int64_t *plies, int64_t *job, int64_t S, int64_t *counter, int32_t *counts,
+                                        int64_t *sums, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

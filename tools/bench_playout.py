@@ -1,12 +1,14 @@
 """Batched Monte Carlo playouts (gogame.batch_playouts) against the tracked rollout they are built on; prints one JSON line.
 
-  python tools/bench_playout.py [--roots 32768] [--k 16] [--size 19] [--slots S] [--reps 3]
+  python tools/bench_playout.py [--roots 32768] [--k 16] [--size 19] [--slots S] [--reps 3] [--policy no_eye_fill]
 
 Workload: R empty roots x K playouts to the end of the game (komi 7.5, default slot count: 256 per CU), without and with
 ownership.  Ceiling, in the same process: gg_batch_rollout_tracked on S boards x 256 plies with auto-reset (the rollout
 kernel the playouts run on, at the same batch size).  Plies are the plies the playouts actually played (plies_sum).
 For the split of device time between the rollout chunks and the harvest launches, run this once under
 `rocprofv3 --kernel-trace --stats -- python tools/bench_playout.py --reps 1` (k_rollout* vs k_po_harvest).
+--policy no_eye_fill: the playouts (without ownership) under that policy NEXT TO the uniform ones in the same run, the two
+sides alternating (keys with the suffix _policy; policy_ratio_* = policy / uniform), and the tracked rollout under the policy.
 """
 import argparse
 import json
@@ -22,6 +24,7 @@ def main():
     ap.add_argument('--slots', type=int, default=None)
     ap.add_argument('--chunk', type=int, default=32)
     ap.add_argument('--reps', type=int, default=3)
+    ap.add_argument('--policy', default='uniform', choices=sorted(('uniform', 'no_eye_fill')))
     args = ap.parse_args()
 
     import torch
@@ -55,6 +58,26 @@ def main():
             res['mean_plies'] = plies / (R * K)
             res['unfinished'] = int(out.unfinished.sum())
             res['black_win_rate'] = int(out.black_wins.sum()) / (R * K)
+    if args.policy != 'uniform':
+        pol = args.policy
+        res['policy'] = pol
+        gogame.batch_rollout_tracked(tracked, rng, 256, policy=pol)
+        (t_pol, _), = median_timed(lambda: gogame.batch_rollout_tracked(tracked, rng, 256, policy=pol), reps=args.reps)
+        res['tracked_rollout_plies_per_s_policy'] = S * 256 / t_pol
+        runs = {'': lambda: gogame.batch_playouts(roots, K, komi=7.5, seed=1, slots=S, chunk_plies=args.chunk),
+                '_policy': lambda: gogame.batch_playouts(roots, K, komi=7.5, seed=1, slots=S, chunk_plies=args.chunk, policy=pol)}
+        runs['_policy']()   # warm-up
+        timed = dict(zip(runs, median_timed(*runs.values(), reps=args.reps)))   # the two sides alternating
+        for k, (t, out) in timed.items():
+            plies = int(out.plies_sum.sum())
+            res['alt_seconds' + k] = t
+            res['alt_playouts_per_s' + k] = R * K / t
+            res['alt_plies_per_s' + k] = plies / t
+            res['alt_mean_plies' + k] = plies / (R * K)
+            res['alt_unfinished' + k] = int(out.unfinished.sum())
+        res['black_win_rate_policy'] = int(timed['_policy'][1].black_wins.sum()) / (R * K)
+        res['policy_ratio_plies_per_s'] = res['alt_plies_per_s_policy'] / res['alt_plies_per_s']
+        res['policy_ratio_playouts_per_s'] = res['alt_playouts_per_s_policy'] / res['alt_playouts_per_s']
     print(json.dumps(res))
 
 
