@@ -24,7 +24,7 @@ EXPORTS = (
     'gg_batch_symmetry', 'gg_batch_symmetry_rows', 'gg_batch_env_step_scored', 'gg_playouts_begin', 'gg_playouts_advance',
     'gg_move_playouts_plan', 'gg_move_playouts_begin', 'gg_move_playouts_advance', 'gg_uct_begin', 'gg_uct_select',
     'gg_uct_backup', 'gg_batch_eye_mask', 'gg_batch_rollout_tracked_policy', 'gg_playouts_advance_policy',
-    'gg_move_playouts_advance_policy',
+    'gg_move_playouts_advance_policy', 'gg_puct_begin', 'gg_puct_select', 'gg_puct_backup',
 )
 
 _vp, _i64, _i32, _u64 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_uint64
@@ -82,6 +82,9 @@ _SIGNATURES = {
                                     _i64, _vp, _vp, _vp, _vp, _vp], _i32),
     'gg_move_playouts_advance_policy': ([_vp, _i64, _i32, _vp, _i64, _i32, _i64, _u64, _i32, _i32, ctypes.c_float, _i32, _i32, _vp,
                                          _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp], _i32),
+    'gg_puct_begin': ([_vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
+    'gg_puct_select': ([_i64, _i32, _i32, ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
+    'gg_puct_backup': ([_i64, _i32, _i32, ctypes.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
 }
 
 _lib = None

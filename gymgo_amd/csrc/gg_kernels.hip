@@ -4,7 +4,8 @@
 // sixteen boards per wavefront, liberty classes carried from ply to ply), gg_aux.h (stand-alone sampler and capture
 // resolution), gg_ws.h (policy-weighted sampling), gg_sym.h (batched symmetries), gg_ns16.h (the per-ply kernels for
 // big batches), gg_po.h (Monte Carlo playouts: the fill / harvest kernel of the playout queue and the plan of legal first
-// moves) and gg_uct.h (UCT tree search: begin, select, backup).  The playout and search entry points launch the multi-ply
+// moves), gg_uct.h (UCT tree search: begin, select, backup) and gg_puct.h (PUCT tree search with priors and an outside
+// evaluator: begin, select, backup).  The playout and search entry points launch the multi-ply
 // kernels through gg_batch_rollout_tracked, whose launches live in the other three translation units.  Which kernel serves an entry point depends on the arguments only (board size, batch size, plies per
 // launch) and on the CU count the grids are sized for - the device's own, or GYMGO_AMD_CUS (forced_cus below), the one
 // environment variable the shipped build reads; results depend on neither.  Mutable global state, all of it performance-only
@@ -32,6 +33,7 @@
 #include "gg_ns16.h"
 #include "gg_po.h"
 #include "gg_uct.h"
+#include "gg_puct.h"
 #include "gymgo_amd.h"
 
 namespace gg {
@@ -508,6 +510,20 @@ static int32_t uct_args(UctArgs &u, int64_t R, int32_t N, int32_t I, int32_t K, 
   if ((int64_t)I * K > 0x7FFFFFFF) return GG_E_BADSIZE;   // the root's n = I K is an int32
   u = UctArgs{const_cast<uint32_t *>(boards), child, const_cast<int32_t *>(links), stats, nodes, const_cast<uint32_t *>(leaf),
               const_cast<int32_t *>(move), const_cast<int32_t *>(leaf_id), log_table, counts, sums, totals, c, R, N, I, K};
+  return 0;
+}
+
+// ---- PUCT tree search (gg_puct.h): sizes, then arguments, then the entry points' own pointer checks, as above
+static int32_t puct_args(PuctArgs &u, int64_t R, int32_t N, int32_t I, double c, float komi, const uint32_t *boards, int32_t *child,
+                         const float *prior, const int32_t *links, const gg_puct_stat *stats, int32_t *nodes, const uint32_t *leaf,
+                         const int32_t *move, const int32_t *leaf_id, const float *priors = nullptr, const float *values = nullptr) {
+  static_assert(sizeof(gg_puct_stat) == sizeof(PuctStat) && sizeof(PuctStat) == 16, "one 16-byte record per node");
+  if (N < 2 || N > GG_MAX_BOARD || R < 0) return GG_E_BADSIZE;
+  if (I < 1 || I == 0x7FFFFFFF || !(c >= 0.0 && c <= __DBL_MAX__) || !(komi >= -__FLT_MAX__ && komi <= __FLT_MAX__))
+    return GG_E_BADARG;   // (I + 1 nodes per tree: the node count is an int32 as well)
+  u = PuctArgs{const_cast<uint32_t *>(boards), child, const_cast<float *>(prior), const_cast<int32_t *>(links),
+               reinterpret_cast<PuctStat *>(const_cast<gg_puct_stat *>(stats)), nodes, const_cast<uint32_t *>(leaf),
+               const_cast<int32_t *>(move), const_cast<int32_t *>(leaf_id), priors, values, c, R, N, I, komi};
   return 0;
 }
 }  // namespace
@@ -1360,6 +1376,54 @@ int32_t gg_uct_backup(int64_t R, int32_t N, int32_t I, int32_t K, const int32_t 
   OnDeviceOf on_dev(leaf);
   hipStream_t s = (hipStream_t)hip_stream;
   k_uct_backup<<<grid_for(on_dev.cus(), (R + 3) / 4), 4 * kWave, 0, s>>>(u);
+  return (int32_t)hipGetLastError();
+}
+
+int32_t gg_puct_begin(const uint32_t *roots, int64_t R, int32_t N, int32_t I, uint32_t *boards, int32_t *child, float *prior,
+                      int32_t *links, gg_puct_stat *stats, int32_t *nodes, void *hip_stream) {
+  PuctArgs u;
+  if (int32_t e = puct_args(u, R, N, I, 0.0, 0.f, boards, child, prior, links, stats, nodes, nullptr, nullptr, nullptr)) return e;
+  if (!roots || !boards || !child || !prior || !links || !stats || !nodes) return GG_E_NULLPTR;
+  if (R == 0) return 0;
+  OnDeviceOf on_dev(boards);
+  hipStream_t s = (hipStream_t)hip_stream;
+  const int64_t NN = (int64_t)I + 1, A = (int64_t)N * N + 1;
+  hipError_t err = hipMemsetAsync(child, 0xFF, sizeof(int32_t) * R * NN * A, s);   // -1: no child
+  if (err == hipSuccess) err = hipMemsetAsync(prior, 0, sizeof(float) * R * NN * A, s);
+  if (err == hipSuccess) err = hipMemsetAsync(links, 0xFF, sizeof(int32_t) * R * NN * 2, s);
+  if (err == hipSuccess) err = hipMemsetAsync(stats, 0, sizeof(gg_puct_stat) * R * NN, s);
+  if (err != hipSuccess) return (int32_t)err;
+  const int64_t words = R * (5 * N + 1);
+  k_puct_begin<<<(unsigned)((words + 255) / 256), 256, 0, s>>>(roots, u);
+  return (int32_t)hipGetLastError();
+}
+
+int32_t gg_puct_select(int64_t R, int32_t N, int32_t I, double c, const uint32_t *boards, int32_t *child, const float *prior,
+                       int32_t *links, const gg_puct_stat *stats, int32_t *nodes, uint32_t *leaf, int32_t *move, int32_t *leaf_id,
+                       void *hip_stream) {
+  PuctArgs u;
+  if (int32_t e = puct_args(u, R, N, I, c, 0.f, boards, child, prior, links, stats, nodes, leaf, move, leaf_id)) return e;
+  if (!boards || !child || !prior || !links || !stats || !nodes || !leaf || !move || !leaf_id) return GG_E_NULLPTR;
+  if (R == 0) return 0;
+  OnDeviceOf on_dev(leaf);
+  hipStream_t s = (hipStream_t)hip_stream;
+  k_puct_select<<<grid_for(on_dev.cus(), (R + 3) / 4), 4 * kWave, 0, s>>>(u);
+  return (int32_t)hipGetLastError();
+}
+
+int32_t gg_puct_backup(int64_t R, int32_t N, int32_t I, float komi, const float *priors, const float *values, uint32_t *boards,
+                       float *prior, const int32_t *links, gg_puct_stat *stats, const uint32_t *leaf, const int32_t *move,
+                       const int32_t *leaf_id, void *hip_stream) {
+  PuctArgs u;
+  if (int32_t e = puct_args(u, R, N, I, 0.0, komi, boards, nullptr, prior, links, stats, nullptr, leaf, move, leaf_id, priors, values))
+    return e;
+  if (!priors || !values || !boards || !prior || !links || !stats || !leaf || !move || !leaf_id) return GG_E_NULLPTR;
+  if (R == 0) return 0;
+  OnDeviceOf on_dev(leaf);
+  hipStream_t s = (hipStream_t)hip_stream;
+  const int grid = grid_for(on_dev.cus(), (R + 3) / 4);
+  GG_DISPATCH(N, (k_puct_backup<9><<<grid, 4 * kWave, 0, s>>>(u)), (k_puct_backup<13><<<grid, 4 * kWave, 0, s>>>(u)),
+              (k_puct_backup<19><<<grid, 4 * kWave, 0, s>>>(u)));
   return (int32_t)hipGetLastError();
 }
 

@@ -1196,6 +1196,219 @@ def uct_actions(batch_states, iterations, playouts, **kw):
     return _best_legal(box, res.legal, res.visits.to(_I64))
 
 
+# ---------------------------------------------------------------- PUCT tree search with priors and an outside evaluator
+# R independent AlphaZero-style searches (gg_puct_begin / gg_puct_select / gg_puct_backup, include/gymgo_amd.h): the trees
+# live on the device, each iteration selects one leaf per root by the PUCT score, hands the R leaves out as byte planes with
+# their legality mask, and backs the caller's priors and values up.  The host only queues launches: nothing is read back.
+
+Puct = collections.namedtuple('Puct', 'legal visits value_sum priors root_visits root_value_sum nodes tree')
+Puct.__doc__ = """Results of batch_puct per root: legal (bool [R, A], A = N*N + 1), visits (int32 [R, A]) / value_sum (float64
+[R, A]: the n / w of the root's children, w from black's point of view; 0 where there is none), priors (float32 [R, A]: the
+root's, as stored - zero on illegal actions), root_visits (int32 [R]), root_value_sum (float64 [R]), nodes (int32 [R]: tree
+nodes in use) and tree (PuctTree or None)."""
+PuctTree = collections.namedtuple('PuctTree', 'parent action visits value_sum')
+PuctTree.__doc__ = """The whole tree of every root, each field [R, iterations + 1] indexed by node (node 0 = the root): parent /
+action / visits int32 (-1 / -1 / 0 at unused nodes; -1 / -1 at the root), value_sum float64 (w, black's point of view)."""
+
+
+def _puct_args(iterations, c, komi):
+    I, c, komi = int(iterations), float(c), float(komi)
+    if I < 1 or I >= 2 ** 31 - 1 or not math.isfinite(c) or c < 0 or not math.isfinite(komi):
+        raise ValueError('need 1 <= iterations < 2^31 - 1, c >= 0 and finite, komi finite (got %d, %r, %r)' % (I, c, komi))
+    return I, c, komi
+
+
+class PuctSearch:
+    """The step-wise form of batch_puct, for callers who batch their network calls their own way:
+
+        search = PuctSearch(batch_states, iterations, c=1.25, komi=0.0)
+        for _ in range(iterations):
+            states, legal = search.select()          # uint8 [R, 6, N, N], bool [R, A]: device tensors owned by the search,
+            priors, values = network(states, legal)  # valid until the next select()
+            search.backup(priors, values)            # float32 [R, A], float32 [R]
+        result = search.result()                     # Puct (NumPy arrays if batch_states was a NumPy array)
+
+    select() and backup() alternate, at most `iterations` times; result() may be called whenever no leaf is outstanding.
+    Anything else raises ValueError.  Every call queues its launches on torch's current stream of the states' device and
+    returns without synchronising.  Semantics, sizes and device memory: batch_puct."""
+
+    def __init__(self, batch_states, iterations, c=1.25, komi=0.0):
+        self._box = _Box(batch_states)
+        st = self._box.t
+        if st.dim() != 4 or st.shape[1] != govars.NUM_CHNLS or st.shape[2] != st.shape[3]:
+            raise ValueError('batch_states must be [R, 6, N, N] (got %s)' % (tuple(st.shape),))
+        self._I, self._c, self._komi = _puct_args(iterations, c, komi)
+        R, N, I, dev = st.shape[0], st.shape[2], self._I, st.device
+        self._R, self._N, self._dev = R, N, dev
+        W, A, NN = tracked_words(N), N * N + 1, I + 1
+        self._legal_roots = _legal_roots(st)
+        self._boards = torch.empty((R, NN, W), dtype=_I32, device=dev)
+        self._child = torch.empty((R, NN, A), dtype=_I32, device=dev)
+        self._prior = torch.empty((R, NN, A), dtype=torch.float32, device=dev)
+        self._links = torch.empty((R, NN, 2), dtype=_I32, device=dev)
+        self._stats = torch.empty((R, NN, 4), dtype=_I32, device=dev)   # gg_puct_stat: w float64 (words 0 - 1), n (word 2), 0
+        self._nodes = torch.empty(R, dtype=_I32, device=dev)
+        self._leaf = torch.empty((R, W), dtype=_I32, device=dev)
+        self._move = torch.empty(R, dtype=_I32, device=dev)
+        self._leaf_id = torch.empty(R, dtype=_I32, device=dev)
+        self._states = torch.empty((R, govars.NUM_CHNLS, N, N), dtype=_U8, device=dev)
+        self._legal = torch.empty((R, A), dtype=torch.bool, device=dev)
+        self._done, self._pending = 0, False
+        if not R:   # no device work at all: select / backup only keep the call order
+            return
+        p = _lib.dev_ptr
+        self._tree = (p(self._boards, _I32, 'boards'), p(self._child, _I32, 'child'), p(self._prior, torch.float32, 'prior'),
+                      p(self._links, _I32, 'links'), p(self._stats, _I32, 'stats'), p(self._nodes, _I32, 'nodes'))
+        self._out = (p(self._leaf, _I32, 'leaf'), p(self._move, _I32, 'move'), p(self._leaf_id, _I32, 'leaf_id'))
+        _lib.check(_lib.lib().gg_puct_begin(p(_track_roots(st), _I32, 'roots'), R, N, I, *self._tree,
+                                            _lib.current_raw_stream(dev)), 'gg_puct_begin')
+
+    @property
+    def iterations_done(self):
+        return self._done
+
+    def select(self):
+        """Step 1 and 2 of the next iteration -> (states uint8 [R, 6, N, N], legal bool [R, A]) of the R leaves."""
+        if self._pending:
+            raise ValueError('PuctSearch.select(): the leaves of the last select() have not been backed up')
+        if self._done >= self._I:
+            raise ValueError('PuctSearch.select(): all %d iterations are done' % self._I)
+        R, N, I = self._R, self._N, self._I
+        if R:
+            L, stream = _lib.lib(), _lib.current_raw_stream(self._dev)
+            lp, mp, ip = self._out
+            _lib.check(L.gg_puct_select(R, N, I, self._c, *self._tree, lp, mp, ip, stream), 'gg_puct_select')
+            _lib.check(L.gg_batch_play_moves_tracked(lp, mp, None, R, N, 1, stream), 'gg_batch_play_moves_tracked')
+            _lib.check(L.gg_batch_untrack_states(lp, _lib.dev_ptr(self._states, _U8, 'states'), R, N, stream),
+                       'gg_batch_untrack_states')
+            with torch.cuda.device(self._dev):
+                self._legal.copy_(_legal_roots(self._states))
+        self._pending = True
+        return self._states, self._legal
+
+    def backup(self, priors, values):
+        """Step 4: priors float32 [R, A] and values float32 [R] (the value for the player to move at the leaf) of the leaves
+        the last select() handed out; tensors on the search's device or NumPy arrays."""
+        if not self._pending:
+            raise ValueError('PuctSearch.backup(): no select() is outstanding')
+        R, N, A = self._R, self._N, self._N * self._N + 1
+        f32 = lambda x: (x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))).to(
+            device=self._dev, dtype=torch.float32).contiguous()
+        priors, values = f32(priors), f32(values)
+        if tuple(priors.shape) != (R, A) or values.numel() != R:
+            raise ValueError('need priors [%d, %d] and values [%d] (got %s, %s)' % (R, A, R, tuple(priors.shape), tuple(values.shape)))
+        if R:
+            boards, _, prior, links, stats, _ = self._tree
+            _lib.check(_lib.lib().gg_puct_backup(R, N, self._I, self._komi, _lib.dev_ptr(priors, torch.float32, 'priors'),
+                                                 _lib.dev_ptr(values.reshape(R), torch.float32, 'values'), boards, prior, links,
+                                                 stats, *self._out, _lib.current_raw_stream(self._dev)), 'gg_puct_backup')
+        self._pending = False
+        self._done += 1
+
+    def result(self, tree=False):
+        """-> Puct of the iterations done so far (tree=True: with the whole tree, PuctTree).  For device input some fields are
+        views of the search's own buffers: clone what has to survive a later select()."""
+        if self._pending:
+            raise ValueError('PuctSearch.result(): the leaves of the last select() have not been backed up')
+        R, A = self._R, self._N * self._N + 1
+        n, w = self._stats[..., 2], self._stats.view(torch.float64)[..., 0]
+        rc = self._child[:, 0, :]
+        has, idx = rc >= 0, rc.clamp(min=0).long()
+        visits = torch.where(has, torch.gather(n, 1, idx), torch.zeros_like(rc))
+        vsum = torch.where(has, torch.gather(w, 1, idx), torch.zeros((R, A), dtype=torch.float64, device=self._dev))
+        whole = PuctTree(self._links[..., 0], self._links[..., 1], n, w) if tree else None
+        return _back(self._box, Puct(self._legal_roots, visits, vsum, self._prior[:, 0, :], n[:, 0], w[:, 0], self._nodes, whole))
+
+
+def batch_puct(batch_states, iterations, evaluator, c=1.25, komi=0.0, tree=False):
+    """PUCT search (the AlphaZero search) of `iterations` iterations from every root of batch_states ([R, 6, N, N]) with the
+    caller's evaluator -> Puct (device tensors for a device tensor, NumPy arrays for NumPy input).  The loop over PuctSearch.
+
+    evaluator(states, legal) -> (priors, values): states uint8 [R, 6, N, N] and legal bool [R, A] (A = N*N + 1) are device
+    tensors whatever batch_states was; priors float32 [R, A], values float32 [R] - the value in [-1, 1] for the player to move
+    at the leaf.  Priors are NOT renormalised by the library (a float sum would depend on the kernel's order): normalising
+    over `legal` is the evaluator's job.  Root Dirichlet noise is its business too: iteration 0 always hands out the roots.
+
+    Each root has its own tree with room for iterations + 1 nodes; a node keeps n (visits), w (float64 sum of the backed-up
+    values from BLACK's point of view), its priors and a child table.  Iteration i, per root: select from the root - a node
+    whose game has ended, or that has not been evaluated (the root at i = 0), is the leaf; else take the legal action
+    (batch_uct's rule) of the largest U = q + c * prior[a] * sqrt(n_x) / (1 + n_c), q = +-w_c / n_c for the player to move at
+    x (0 without visits; float64, in this order, no fused multiply-add; ties to the lowest action): without a child under
+    it, the child is created and is the leaf, else the walk goes on there.  n_x counts the node's own evaluation
+    (n_x = 1 + sum of n_c): with the children's sum alone the first selection below a fresh node would see sqrt(0) and
+    ignore the priors.  The leaves are evaluated; a node's first evaluation stores max(prior, 0) on its legal actions and 0
+    elsewhere (NaN -> 0); the value is clamped to [-1, 1] (NaN -> 0) and turned to black's point of view - at a leaf whose
+    game has ended it is sign(black area - white area - komi) instead and the evaluator's row is ignored - and n += 1,
+    w += value on the path from the leaf to the root.  So root_visits = iterations, a live root's visits sum to
+    iterations - 1, an ended root evaluates itself every iteration.  No random numbers; the result of a root depends on
+    that root and the evaluator's answers alone, so shards by root concatenate to the whole.  Needs 1 <= iterations < 2^31 - 1,
+    c >= 0 and finite, komi finite.  tree=True also returns the whole tree (PuctTree).  The roots are not modified.
+
+    Device memory of the tree: R * (iterations + 1) * (4 (5N + 1) + 8 (N^2 + 1) + 24) bytes (boards, child tables, priors,
+    links and stats: 3 304 bytes, about 3.3 KB, per node at 19x19; 220 MB for 1 024 roots x 64 iterations)."""
+    ek = getattr(evaluator, 'komi', None)   # (playout_evaluator says what komi it scores with)
+    if ek is not None and float(ek) != float(komi):
+        raise ValueError('the evaluator scores its playouts with komi %r, the search its ended leaves with %r' % (ek, komi))
+    search = PuctSearch(batch_states, iterations, c, komi)
+    for _ in range(search._I):
+        states, legal = search.select()
+        priors, values = evaluator(states, legal)
+        search.backup(priors, values)
+    return search.result(tree=tree)
+
+
+def puct(state, iterations, evaluator, **kw):
+    """batch_puct of one state [6, N, N] -> Puct of [N*N + 1] vectors and scalars (tree fields [iterations + 1]); the evaluator
+    still sees a batch of one."""
+    return _single(batch_puct, state, iterations, evaluator, **kw)
+
+
+def puct_actions(batch_states, iterations, evaluator, **kw):
+    """The PUCT move of every root -> int64 [R]: the legal root child with the most visits after batch_puct(batch_states,
+    iterations, evaluator, **kw); ties go to the lowest action, a root without a legal move gives -1."""
+    box = _Box(batch_states)
+    res = batch_puct(box.t, iterations, evaluator, **kw)
+    return _best_legal(box, res.legal, res.visits.to(_I64))
+
+
+def playout_evaluator(playouts, max_plies=None, seed=20260927, first_root=0, policy='uniform', slots=None, chunk_plies=32, *,
+                      komi):
+    """A ready-made evaluator for batch_puct / PuctSearch that needs no network: uniform priors and Monte Carlo values.
+    priors = float32(1) / float32(number of legal actions) on the legal actions, 0 elsewhere; values = float32(wins of the
+    side to move - its losses) / float32(playouts) over exactly batch_playouts(leaves, playouts, max_plies, komi,
+    seed=s_j, first_root, slots=slots, chunk_plies=chunk_plies, policy=policy) in its j-th call (j = 0, 1, ...), s_j the
+    generator of game j under `seed` as in batch_uct.  komi (required, keyword only): the komi of the search - the playouts
+    and the search's ended leaves must be scored alike, so there is no default to forget; batch_puct refuses an evaluator
+    whose komi (its attribute `komi`) differs from its own.  The object counts its calls: make a new one per search.  Its attribute plies_sum is an int64 device scalar: the plies all its playouts have played
+    (None before the first call)."""
+    pol_name, K = policy, int(playouts)
+    _policy_code(policy)
+    komi = float(komi)
+    if K < 1 or not math.isfinite(komi):
+        raise ValueError('need playouts >= 1 and a finite komi')
+    calls = [0]
+
+    def evaluate(states, legal):
+        j = calls[0]
+        calls[0] += 1
+        res = batch_playouts(states, K, max_plies, komi, seed=_uct_seed(seed, j), first_root=first_root, slots=slots,
+                             chunk_plies=chunk_plies, policy=pol_name)
+        # (tensor / tensor: a true float32 division - by a Python number torch multiplies with the rounded reciprocal)
+        one, kf = (torch.full((), v, dtype=torch.float32, device=legal.device) for v in (1.0, float(K)))
+        count = legal.sum(dim=1, keepdim=True).to(torch.float32)
+        priors = torch.where(legal, one / count, torch.zeros_like(one))
+        white = states[:, govars.TURN_CHNL, 0, 0].to(torch.bool)
+        diff = res.black_wins - res.white_wins
+        values = torch.where(white, -diff, diff).to(torch.float32) / kf
+        plies = res.plies_sum.sum()
+        evaluate.plies_sum = plies if evaluate.plies_sum is None else evaluate.plies_sum + plies
+        return priors, values
+
+    evaluate.plies_sum = None
+    evaluate.komi = komi
+    return evaluate
+
+
 # ---------------------------------------------------------------- policy-weighted sampling on the device
 # gogame.random_weighted_action / random_action (gym_go/gogame.py:385-404) for every game of a batch: what a self-play loop
 # with a policy network calls after the forward pass.  The draw is defined in integers (include/gymgo_amd.h,

@@ -484,6 +484,57 @@ int32_t gg_move_playouts_advance_policy(const uint32_t *roots, int64_t R, int32_
                                         int64_t *plies, int64_t *job, int64_t S, int64_t *counter, int32_t *counts,
                                         int64_t *sums, void *hip_stream);
 
+/*
+ * PUCT tree search with priors and a caller-supplied evaluator (the AlphaZero search), R independent searches of I
+ * iterations, the trees on the device.  A = N*N + 1.  Each root r has a tree with room for I + 1 nodes (node 0 = the root); a
+ * node holds its tracked board, parent / action (-1 at the root), a stat record {w: float64 sum of the backed-up values FROM
+ * BLACK'S POINT OF VIEW, n: int32 visits}, float32 priors prior[a] (all zero until the node is evaluated) and a child table
+ * child[a] (-1: no child).  The legal actions of node x are those of gg_uct_*: none once x's game has ended, else the pass
+ * and every point whose invalid bit is clear.  Nothing in the tree draws random numbers; root r's results depend on root r
+ * alone.  Iteration i, per root:
+ *   1. select (gg_puct_select): from x = 0.  If x's game has ended or n_x = 0 (not evaluated yet: only the root, at i = 0),
+ *      x is the leaf and move = -1.  Otherwise a* = the legal action of the largest U (ties to the lowest action); without a
+ *      child under a*, node y = nodes[r]++ with parent x, action a*, child_x[a*] = y is the leaf and move = a*; else
+ *      x = child_x[a*] and the walk goes on.  With s = +1 if black is to move at x (flag bit 0 clear), else -1, and n_c, w_c
+ *      the record of the child under a (n_c = 0 without a child):
+ *        q = n_c == 0 ? 0 : s * w_c / n_c;  t1 = C * prior_x[a];  t2 = sqrt(n_x);  t3 = t1 * t2;  t4 = t3 / (1 + n_c);  U = q + t4
+ *      in float64, each operation rounded to nearest in this order, no fused multiply-add; a U that is NaN (C = 0 times an
+ *      infinite prior) counts as -infinity.  n_x counts the node's own evaluation (n_x = 1 + the sum of n_c), so the first
+ *      selection below a fresh node sees sqrt(1) and follows the priors.  Writes leaf[r] = the board of the node the walk
+ *      stopped at (the new node's parent, or the leaf itself), move[r], leaf_id[r] = the leaf.
+ *   2. the caller plays move on leaf (gg_batch_play_moves_tracked(leaf, move, NULL, R, N, T = 1): -1 is out of range, the
+ *      board stays put), turns leaf into byte planes (gg_batch_untrack_states) and has them evaluated: priors float32 [R][A]
+ *      and values float32 [R], the value from the point of view of the player to move at the leaf.  Priors are NOT
+ *      renormalised here (a float sum would depend on its order): that is the evaluator's job.
+ *   3. backup (gg_puct_backup): stores leaf[r] as node y's board when move[r] >= 0.  If n_y = 0, prior_y[a] = priors[r][a]
+ *      where a is legal at y and priors[r][a] > 0, else 0 (NaN, negatives, illegal actions -> 0).  If y's game has ended,
+ *      v = sign(b - w - komi) of its Tromp-Taylor areas (komi as float32, as gg_playouts_*) and the evaluator's row is
+ *      ignored; else v = s_y * clamp(values[r], -1, 1) with NaN -> 0.  Every node from y up to the root: n += 1, w += v (one
+ *      float64 add per node and iteration, in iteration order).
+ * Buffers, caller-owned (W = gg_tracked_words(N)): boards uint32 [R][I+1][W], child int32 [R][I+1][A], prior float [R][I+1][A],
+ * links int32 [R][I+1][2] (parent, action; -1 / -1 at unused nodes), stats gg_puct_stat [R][I+1], nodes int32 [R];
+ * leaf uint32 [R][W], move int32 [R], leaf_id int32 [R].  4 W + 8 A + 24 bytes per node.
+ *   gg_puct_begin   node 0 = roots[r] (tracked, read only), every child table -1, priors 0, links -1, stats 0, nodes = 1.
+ * A select without room (all I + 1 nodes in use: I selects use I of them) evaluates the node it stopped at, with move = -1:
+ * no write beyond a tree.
+ * The argument checks come before any device work, in the order of gg_uct_*: GG_E_BADSIZE: N outside [2, 19], R < 0;
+ * GG_E_BADARG: I < 1 or I = 2^31 - 1 (I + 1 nodes are counted in an int32), C negative or not finite (select), komi not
+ * finite (backup); GG_E_NULLPTR: a buffer is NULL.  R = 0 is no work.  The same R, N, I go to every call of one search.
+ */
+typedef struct {
+  double w;         /* sum of the backed-up values, black's point of view */
+  int32_t n;        /* visits, the node's own evaluation included */
+  int32_t reserved; /* 0 */
+} gg_puct_stat;
+int32_t gg_puct_begin(const uint32_t *roots, int64_t R, int32_t N, int32_t I, uint32_t *boards, int32_t *child, float *prior,
+                      int32_t *links, gg_puct_stat *stats, int32_t *nodes, void *hip_stream);
+int32_t gg_puct_select(int64_t R, int32_t N, int32_t I, double c, const uint32_t *boards, int32_t *child, const float *prior,
+                       int32_t *links, const gg_puct_stat *stats, int32_t *nodes, uint32_t *leaf, int32_t *move, int32_t *leaf_id,
+                       void *hip_stream);
+int32_t gg_puct_backup(int64_t R, int32_t N, int32_t I, float komi, const float *priors, const float *values, uint32_t *boards,
+                       float *prior, const int32_t *links, gg_puct_stat *stats, const uint32_t *leaf, const int32_t *move,
+                       const int32_t *leaf_id, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
