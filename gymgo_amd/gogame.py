@@ -1207,8 +1207,9 @@ Puct.__doc__ = """Results of batch_puct per root: legal (bool [R, A], A = N*N + 
 root's, as stored - zero on illegal actions), root_visits (int32 [R]), root_value_sum (float64 [R]), nodes (int32 [R]: tree
 nodes in use) and tree (PuctTree or None)."""
 PuctTree = collections.namedtuple('PuctTree', 'parent action visits value_sum')
-PuctTree.__doc__ = """The whole tree of every root, each field [R, iterations + 1] indexed by node (node 0 = the root): parent /
-action / visits int32 (-1 / -1 / 0 at unused nodes; -1 / -1 at the root), value_sum float64 (w, black's point of view)."""
+PuctTree.__doc__ = """The whole tree of every root, each field [R, iterations + 1] ([R, iterations * leaves + 1] with `leaves`)
+indexed by node (node 0 = the root): parent / action / visits int32 (-1 / -1 / 0 at unused nodes; -1 / -1 at the root),
+value_sum float64 (w, black's point of view)."""
 
 
 def _puct_args(iterations, c, komi):
@@ -1216,6 +1217,18 @@ def _puct_args(iterations, c, komi):
     if I < 1 or I >= 2 ** 31 - 1 or not math.isfinite(c) or c < 0 or not math.isfinite(komi):
         raise ValueError('need 1 <= iterations < 2^31 - 1, c >= 0 and finite, komi finite (got %d, %r, %r)' % (I, c, komi))
     return I, c, komi
+
+
+def _puct_leaves(iterations, leaves):
+    """leaves=None -> None (the one-leaf path); else the validated int L >= 1 with iterations * L < 2^31 - 1."""
+    if leaves is None:
+        return None
+    if isinstance(leaves, bool) or not isinstance(leaves, (int, np.integer)):
+        raise ValueError('leaves must be None or an integer >= 1 (got %r)' % (leaves,))
+    L = int(leaves)
+    if L < 1 or int(iterations) * L >= 2 ** 31 - 1:
+        raise ValueError('need leaves >= 1 and iterations * leaves < 2^31 - 1 (got %d, %d)' % (L, int(iterations) * L))
+    return L
 
 
 class PuctSearch:
@@ -1230,16 +1243,27 @@ class PuctSearch:
 
     select() and backup() alternate, at most `iterations` times; result() may be called whenever no leaf is outstanding.
     Anything else raises ValueError.  Every call queues its launches on torch's current stream of the states' device and
-    returns without synchronising.  Semantics, sizes and device memory: batch_puct."""
+    returns without synchronising.  Semantics, sizes and device memory: batch_puct.
 
-    def __init__(self, batch_states, iterations, c=1.25, komi=0.0):
+    leaves=L (an integer >= 1; None = the path above, untouched): every round hands out up to L leaves per root, chosen
+    one after the other under virtual loss (batch_puct).  select() then returns states uint8 [R * L, 6, N, N] and legal
+    bool [R * L, A] in row order r * L + j, backup() takes priors [R * L, A] and values [R * L]; rows of empty slots are
+    evaluated like any other and ignored.  `search.live` (bool [R, L], a device tensor valid until the next select()) says
+    which slots hold a leaf, for evaluators that want to skip the rest.  The tree has iterations * L + 1 nodes per root."""
+
+    def __init__(self, batch_states, iterations, c=1.25, komi=0.0, leaves=None):
         self._box = _Box(batch_states)
         st = self._box.t
         if st.dim() != 4 or st.shape[1] != govars.NUM_CHNLS or st.shape[2] != st.shape[3]:
             raise ValueError('batch_states must be [R, 6, N, N] (got %s)' % (tuple(st.shape),))
         self._I, self._c, self._komi = _puct_args(iterations, c, komi)
-        R, N, I, dev = st.shape[0], st.shape[2], self._I, st.device
+        self._L = _puct_leaves(self._I, leaves)
+        R, N, dev = st.shape[0], st.shape[2], st.device
         self._R, self._N, self._dev = R, N, dev
+        if self._L is not None:
+            self._init_leaves(st)
+            return
+        I = self._I
         W, A, NN = tracked_words(N), N * N + 1, I + 1
         self._legal_roots = _legal_roots(st)
         self._boards = torch.empty((R, NN, W), dtype=_I32, device=dev)
@@ -1263,16 +1287,76 @@ class PuctSearch:
         _lib.check(_lib.lib().gg_puct_begin(p(_track_roots(st), _I32, 'roots'), R, N, I, *self._tree,
                                             _lib.current_raw_stream(dev)), 'gg_puct_begin')
 
+    def _init_leaves(self, st):
+        """The buffers of the several-leaves path: the tree of C + 1 = iterations * leaves + 1 nodes (gg_puct_begin with
+        I = C: the same bytes as a one-leaf tree of C iterations), R * L rows of everything that is handed out."""
+        R, N, L, dev = self._R, self._N, self._L, self._dev
+        C = self._C = self._I * L
+        W, A, NN, B = tracked_words(N), N * N + 1, C + 1, R * L
+        self._legal_roots = _legal_roots(st)
+        self._boards = torch.empty((R, NN, W), dtype=_I32, device=dev)
+        self._child = torch.empty((R, NN, A), dtype=_I32, device=dev)
+        self._prior = torch.empty((R, NN, A), dtype=torch.float32, device=dev)
+        self._links = torch.empty((R, NN, 2), dtype=_I32, device=dev)
+        self._stats = torch.empty((R, NN, 4), dtype=_I32, device=dev)   # gg_puct_stat: w float64 (words 0 - 1), n (word 2), v
+        self._nodes = torch.empty(R, dtype=_I32, device=dev)
+        self._leaf = torch.empty((B, W), dtype=_I32, device=dev)
+        self._move = torch.empty(B, dtype=_I32, device=dev)
+        self._leaf_id = torch.empty(B, dtype=_I32, device=dev)
+        self._states = torch.empty((B, govars.NUM_CHNLS, N, N), dtype=_U8, device=dev)
+        self._legal = torch.empty((B, A), dtype=torch.bool, device=dev)
+        self.live = torch.zeros((R, L), dtype=torch.bool, device=dev)
+        self._done, self._pending = 0, False
+        if not R:
+            return
+        p = _lib.dev_ptr
+        self._tree = (p(self._boards, _I32, 'boards'), p(self._child, _I32, 'child'), p(self._prior, torch.float32, 'prior'),
+                      p(self._links, _I32, 'links'), p(self._stats, _I32, 'stats'), p(self._nodes, _I32, 'nodes'))
+        self._out = (p(self._leaf, _I32, 'leaf'), p(self._move, _I32, 'move'), p(self._leaf_id, _I32, 'leaf_id'))
+        self._hand = (p(self._states, _U8, 'states'), p(self._legal, torch.bool, 'legal'), p(self.live, torch.bool, 'live'))
+        _lib.check(_lib.lib().gg_puct_begin(p(_track_roots(st), _I32, 'roots'), R, N, C, *self._tree,
+                                            _lib.current_raw_stream(dev)), 'gg_puct_begin')
+
     @property
     def iterations_done(self):
         return self._done
 
+    def _select_leaves(self):
+        R, N, L = self._R, self._N, self._L
+        if R:
+            lib, stream = _lib.lib(), _lib.current_raw_stream(self._dev)
+            lp, mp, ip = self._out
+            sp, gp, vp = self._hand
+            _lib.check(lib.gg_puct_select_leaves(R, N, self._C, L, self._c, *self._tree, lp, mp, ip, stream), 'gg_puct_select_leaves')
+            _lib.check(lib.gg_batch_play_moves_tracked(lp, mp, None, R * L, N, 1, stream), 'gg_batch_play_moves_tracked')
+            _lib.check(lib.gg_batch_untrack_states(lp, sp, R * L, N, stream), 'gg_batch_untrack_states')
+            _lib.check(lib.gg_puct_legal(lp, ip, R * L, N, gp, vp, stream), 'gg_puct_legal')
+        self._pending = True
+        return self._states, self._legal
+
+    def _backup_leaves(self, priors, values):
+        R, N, L, A = self._R, self._N, self._L, self._N * self._N + 1
+        B = R * L
+        if tuple(priors.shape) != (B, A) or values.numel() != B:
+            raise ValueError('need priors [%d, %d] and values [%d] (got %s, %s)' % (B, A, B, tuple(priors.shape), tuple(values.shape)))
+        if R:
+            boards, _, prior, links, stats, _ = self._tree
+            _lib.check(_lib.lib().gg_puct_backup_leaves(R, N, self._C, L, self._komi, _lib.dev_ptr(priors, torch.float32, 'priors'),
+                                                        _lib.dev_ptr(values.reshape(B), torch.float32, 'values'), boards, prior,
+                                                        links, stats, *self._out, _lib.current_raw_stream(self._dev)),
+                       'gg_puct_backup_leaves')
+        self._pending = False
+        self._done += 1
+
     def select(self):
-        """Step 1 and 2 of the next iteration -> (states uint8 [R, 6, N, N], legal bool [R, A]) of the R leaves."""
+        """Step 1 and 2 of the next iteration -> (states uint8 [R, 6, N, N], legal bool [R, A]) of the R leaves ([R * L, ..]
+        with leaves=L)."""
         if self._pending:
             raise ValueError('PuctSearch.select(): the leaves of the last select() have not been backed up')
         if self._done >= self._I:
             raise ValueError('PuctSearch.select(): all %d iterations are done' % self._I)
+        if self._L is not None:
+            return self._select_leaves()
         R, N, I = self._R, self._N, self._I
         if R:
             L, stream = _lib.lib(), _lib.current_raw_stream(self._dev)
@@ -1295,6 +1379,8 @@ class PuctSearch:
         f32 = lambda x: (x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))).to(
             device=self._dev, dtype=torch.float32).contiguous()
         priors, values = f32(priors), f32(values)
+        if self._L is not None:
+            return self._backup_leaves(priors, values)
         if tuple(priors.shape) != (R, A) or values.numel() != R:
             raise ValueError('need priors [%d, %d] and values [%d] (got %s, %s)' % (R, A, R, tuple(priors.shape), tuple(values.shape)))
         if R:
@@ -1320,7 +1406,7 @@ class PuctSearch:
         return _back(self._box, Puct(self._legal_roots, visits, vsum, self._prior[:, 0, :], n[:, 0], w[:, 0], self._nodes, whole))
 
 
-def batch_puct(batch_states, iterations, evaluator, c=1.25, komi=0.0, tree=False):
+def batch_puct(batch_states, iterations, evaluator, c=1.25, komi=0.0, tree=False, leaves=None):
     """PUCT search (the AlphaZero search) of `iterations` iterations from every root of batch_states ([R, 6, N, N]) with the
     caller's evaluator -> Puct (device tensors for a device tensor, NumPy arrays for NumPy input).  The loop over PuctSearch.
 
@@ -1345,11 +1431,24 @@ def batch_puct(batch_states, iterations, evaluator, c=1.25, komi=0.0, tree=False
     c >= 0 and finite, komi finite.  tree=True also returns the whole tree (PuctTree).  The roots are not modified.
 
     Device memory of the tree: R * (iterations + 1) * (4 (5N + 1) + 8 (N^2 + 1) + 24) bytes (boards, child tables, priors,
-    links and stats: 3 304 bytes, about 3.3 KB, per node at 19x19; 220 MB for 1 024 roots x 64 iterations)."""
+    links and stats: 3 304 bytes, about 3.3 KB, per node at 19x19; 220 MB for 1 024 roots x 64 iterations).
+
+    leaves=L (an integer >= 1; the default None is the search above, launch for launch): `iterations` ROUNDS of up to L leaves
+    per root.  A node also has v, its virtual visits (0 outside a round).  The L slots of a root are selected one after the
+    other; each walks from the root: a node with n = 0 and v > 0 was handed out earlier in this round - a collision: this
+    slot and the root's later ones stay empty (evaluated as a copy of the root and ignored) -; else an ended or unevaluated
+    node is the leaf; else the walk follows the largest U' = q + c * prior[a] * sqrt(n_x + v_x) / (1 + n_c + v_c),
+    q = (+-w_c - v_c) / (n_c + v_c) - one virtual visit is one loss for the side that chose the child - and expands as
+    above.  The slot's path from the leaf to the root then gets v += 1.  The evaluator sees states [R * L, 6, N, N] and legal
+    [R * L, A] (row r * L + j = slot j of root r) and returns priors [R * L, A], values [R * L]; the backup runs the slots in
+    order (n += 1, w += value, v -= 1 on the path).  root_visits = the non-empty slots (round 0 evaluates the root alone);
+    leaves=1 gives the tree of leaves=None exactly; no random numbers, shards by root still concatenate.  Needs
+    iterations * L < 2^31 - 1.  Device memory of the tree: R * (iterations * L + 1) * (4 (5N + 1) + 8 (N^2 + 1) + 24)
+    bytes - the formula above with iterations * L + 1 nodes - and PuctTree fields are [R, iterations * L + 1]."""
     ek = getattr(evaluator, 'komi', None)   # (playout_evaluator says what komi it scores with)
     if ek is not None and float(ek) != float(komi):
         raise ValueError('the evaluator scores its playouts with komi %r, the search its ended leaves with %r' % (ek, komi))
-    search = PuctSearch(batch_states, iterations, c, komi)
+    search = PuctSearch(batch_states, iterations, c, komi, leaves=leaves)
     for _ in range(search._I):
         states, legal = search.select()
         priors, values = evaluator(states, legal)

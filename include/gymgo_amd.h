@@ -524,7 +524,7 @@ int32_t gg_move_playouts_advance_policy(const uint32_t *roots, int64_t R, int32_
 typedef struct {
   double w;         /* sum of the backed-up values, black's point of view */
   int32_t n;        /* visits, the node's own evaluation included */
-  int32_t reserved; /* 0 */
+  int32_t reserved; /* 0 on the one-leaf path; v, the virtual visits, of gg_puct_*_leaves: 0 outside a round */
 } gg_puct_stat;
 int32_t gg_puct_begin(const uint32_t *roots, int64_t R, int32_t N, int32_t I, uint32_t *boards, int32_t *child, float *prior,
                       int32_t *links, gg_puct_stat *stats, int32_t *nodes, void *hip_stream);
@@ -534,6 +534,52 @@ int32_t gg_puct_select(int64_t R, int32_t N, int32_t I, double c, const uint32_t
 int32_t gg_puct_backup(int64_t R, int32_t N, int32_t I, float komi, const float *priors, const float *values, uint32_t *boards,
                        float *prior, const int32_t *links, gg_puct_stat *stats, const uint32_t *leaf, const int32_t *move,
                        const int32_t *leaf_id, void *hip_stream);
+
+/*
+ * PUCT with several leaves per root per round and virtual loss: a second select / backup pair on the SAME tree (same
+ * buffers, same bytes; gg_puct_begin is reused unchanged with I = C).  R roots, T rounds, L >= 1 slots per root and round;
+ * the tree has room for C + 1 nodes, C = T * L.  Each node has n, w and priors as above plus v, an int32 count of virtual
+ * visits: the reserved word of gg_puct_stat, 0 outside a round.  Slot j of root r is row r * L + j of leaf / move /
+ * leaf_id / priors / values.  One round, per root:
+ *   1. select (gg_puct_select_leaves) runs slots j = 0 .. L - 1 strictly in order.  Each slot walks from x = 0 and tests, in
+ *      this order:
+ *      a. n_x = 0 and v_x > 0: x was handed out earlier in this round and is not evaluated yet - a collision.  This slot and
+ *         every later slot of this root are EMPTY: leaf_id = -1, move = -1, leaf = a copy of node 0's board; selection for
+ *         this root ends, nothing is added to any v.  The test comes before any read of x's board (a node created in this
+ *         round has no board in the tree until its backup).
+ *      b. the game has ended at x: x is the leaf, move = -1.  An ended node may be taken by several slots of one round.
+ *      c. n_x = 0 (and v_x = 0): x is the leaf, move = -1 (the root in round 0).
+ *      d. otherwise a* = the legal action of the largest U', ties to the lowest action.  With s = +-1 for the mover at x and
+ *         n_c, w_c, v_c all 0 without a child:
+ *           ne = n_c + v_c;  q = ne == 0 ? 0 : (s * w_c - (double)v_c) / (double)ne;  t1 = c * prior_x[a];
+ *           t2 = sqrt((double)(n_x + v_x));  t3 = t1 * t2;  t4 = t3 / (double)(1 + ne);  U' = q + t4
+ *         in float64, in this order, no fused multiply-add, NaN counts as -infinity: one virtual visit is one loss for the
+ *         side that chose the child.  With every v = 0 this is U of gg_puct_select bit for bit.  No child under a*: with room,
+ *         node y = nodes[r]++ is linked in and is the leaf, move = a*; without room (only when driven past C leaves) x is
+ *         the leaf as it is, move = -1.  A child under a*: descend.
+ *      After a slot has found its leaf, v += 1 on every node from the leaf up to the root.
+ *   2. the caller plays the R * L moves (gg_batch_play_moves_tracked(leaf, move, NULL, R * L, N, T = 1)), untracks the
+ *      boards and may take the legality mask from gg_puct_legal; rows of empty slots are evaluated like any other and ignored.
+ *   3. backup (gg_puct_backup_leaves) runs the slots in ascending order and skips leaf_id = -1.  Each slot does exactly step 3
+ *      of gg_puct_backup with row r * L + j, and v -= 1 (never below 0) on the same chain.  The float64 additions into w
+ *      happen in slot order.  After a backup every v of the tree is 0.
+ * So root n = the number of non-empty slots so far (at most T * L), round 0 evaluates the root alone, and L = 1 never
+ * collides and grows the tree of gg_puct_select / gg_puct_backup exactly.
+ * Buffers: the tree as above with C where I stood; leaf uint32 [R*L][W], move / leaf_id int32 [R*L], priors float [R*L][A],
+ * values float [R*L].  The argument checks come before any device work, in the order above: GG_E_BADSIZE, then
+ * GG_E_BADARG (the conditions of gg_puct_select / gg_puct_backup on C, or L < 1, or L > C), then GG_E_NULLPTR.
+ *   gg_puct_legal   from B played tracked boards leaf [B][W] and leaf_id [B]: legal uint8 [B][A] (1 = the pass and every
+ *                   point whose invalid bit is clear; all 0 once the game has ended) and live uint8 [B] (1 where
+ *                   leaf_id >= 0), in one launch.  GG_E_BADSIZE: N outside [2, 19], B < 0; GG_E_NULLPTR; B = 0 is no work.
+ */
+int32_t gg_puct_select_leaves(int64_t R, int32_t N, int32_t C, int32_t L, double c, const uint32_t *boards, int32_t *child,
+                              const float *prior, int32_t *links, gg_puct_stat *stats, int32_t *nodes, uint32_t *leaf,
+                              int32_t *move, int32_t *leaf_id, void *hip_stream);
+int32_t gg_puct_backup_leaves(int64_t R, int32_t N, int32_t C, int32_t L, float komi, const float *priors, const float *values,
+                              uint32_t *boards, float *prior, const int32_t *links, gg_puct_stat *stats, const uint32_t *leaf,
+                              const int32_t *move, const int32_t *leaf_id, void *hip_stream);
+int32_t gg_puct_legal(const uint32_t *leaf, const int32_t *leaf_id, int64_t B, int32_t N, uint8_t *legal, uint8_t *live,
+                      void *hip_stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,331 @@
+"""-m gpu: PUCT with several leaves per root per round and virtual loss (gogame.batch_puct(.., leaves=L) / PuctSearch(..,
+leaves=L): gg_puct_begin / k_puct_select_leaves / the tracked one-move step / untrack / k_puct_legal / the caller's evaluator
+/ k_puct_backup_leaves) - every Puct field and the whole tree equal to the restatement (tests/mc_puct_leaves_expect.py)
+exactly, value sums as bit patterns: ended nodes taken twice in a round, every board size class, komi, crafted roots,
+L in {1, 2, 4, 8, 64}, the hash / hostile / pass evaluators, c in {0, 1.25, 10^6}, the playout evaluator under both policies,
+the step-wise form, NumPy input, shards by root, a non-default stream, R = 0; leaves=1 against leaves=None bit for bit; the
+legality mask and the live mask; the virtual-visit word between select and backup and after it, and the select past
+capacity, with the entry points called directly on the test's own buffers."""
+import numpy as np
+import pytest
+
+import mc_expect as mc
+import mc_puct_expect as pe
+import mc_puct_leaves_expect as pl
+
+pytestmark = pytest.mark.gpu
+
+
+def _invariants(got, want, T, L):
+    legal, v = mc.to_np(got.legal), mc.to_np(got.visits)
+    live = np.stack(want['live'])
+    assert np.array_equal(mc.to_np(got.root_visits), live.sum(axis=(0, 2)))
+    assert (mc.to_np(got.root_visits) <= T * L).all() and not v[~legal].any() and not mc.to_np(got.priors)[~legal].any()
+    alive = legal.any(axis=1)
+    assert (v.sum(axis=1)[alive] == mc.to_np(got.root_visits)[alive] - 1).all()
+
+
+def test_leaves_5x5_takes_ended_nodes_twice_in_a_round():
+    """Far past the root's 26 actions: ended nodes (a pass after a pass) lie inside the tree and are taken by two slots of one
+    round, which is not a collision; on the pass line rounds after round 0 stop on collisions; NumPy in, NumPy out."""
+    from gymgo_amd import gogame
+    N, T, L = 5, 60, 4
+    roots = np.concatenate([mc.crafted_roots(N)[:3], mc.make_roots(N, 4, 31, max_ply=20, step=6)[1:3]])
+    want = pl.expected_puct_leaves(roots, T, L, pe.hash_evaluator_np, c=0.6, komi=0.5)
+    assert sum(t.ended_twice for t in want['trees']) > 0
+    got = gogame.batch_puct(roots, T, pe.hash_evaluator_t, c=0.6, komi=0.5, tree=True, leaves=L)
+    assert isinstance(got.visits, np.ndarray) and got.visits.dtype == np.int32 and got.value_sum.dtype == np.float64
+    assert got.tree.parent.shape == (roots.shape[0], T * L + 1)
+    pe.check(got, want)
+    _invariants(got, want, T, L)
+    # the pass line: all the prior on the pass and c = 10^6 walk every slot down one line - collisions, then the ended node twice
+    want = pl.expected_puct_leaves(roots, 12, 2, pe.pass_evaluator_np, c=1e6, komi=0.5)
+    assert sum(t.ended_twice for t in want['trees']) > 0 and sum(t.collisions - 1 for t in want['trees']) > 0
+    pe.check(gogame.batch_puct(roots, 12, pe.pass_evaluator_t, c=1e6, komi=0.5, tree=True, leaves=2), want, tag='pass')
+
+
+@pytest.mark.parametrize('N,L', [(7, 2), (9, 8)])
+def test_leaves_mid_game_and_crafted_roots(N, L):
+    import torch
+    from gymgo_amd import gogame
+    T = 2 * N * N // L
+    roots = np.concatenate([mc.make_roots(N, 4, 50 + N, max_ply=N * N, step=N)[1:3], mc.crafted_roots(N)])
+    want = pl.expected_puct_leaves(roots, T, L, pe.hash_evaluator_np, komi=0.5)
+    r = mc.to_dev(roots)
+    before = r.clone()
+    got = gogame.batch_puct(r, T, pe.hash_evaluator_t, komi=0.5, tree=True, leaves=L)
+    assert got.legal.dtype == torch.bool and got.visits.dtype == torch.int32 and got.value_sum.dtype == torch.float64
+    pe.check(got, want)
+    assert bool((r == before).all())                                  # the roots are not modified
+    _invariants(got, want, T, L)
+    # the ended root: round 0 evaluates it alone, every later slot takes it again; no node but itself
+    assert mc.to_np(got.nodes)[-1] == 1 and int(got.root_visits[-1]) == 1 + (T - 1) * L
+    assert np.array_equal(mc.to_np(gogame.puct_actions(r, T, pe.hash_evaluator_t, komi=0.5, leaves=L)), pe.most_visited(want))
+
+
+def test_leaves_13x13():
+    from gymgo_amd import gogame
+    N, T, L = 13, 30, 4
+    roots = np.concatenate([mc.make_roots(N, 4, 13, max_ply=150, step=50)[1:], mc.crafted_roots(N)[1:3]])
+    want = pl.expected_puct_leaves(roots, T, L, pe.hash_evaluator_np, c=2.0, komi=6.5)
+    got = gogame.batch_puct(mc.to_dev(roots), T, pe.hash_evaluator_t, c=2.0, komi=6.5, tree=True, leaves=L)
+    pe.check(got, want)
+    _invariants(got, want, T, L)
+
+
+@pytest.mark.parametrize('komi', [7.5, 0.0])
+def test_leaves_19x19(komi):
+    from gymgo_amd import gogame
+    N, T, L = 19, 15, 4
+    roots = np.concatenate([mc.make_roots(N, 4, 7, max_ply=240, step=120)[1:], mc.crafted_roots(N)[1:]])
+    want = pl.expected_puct_leaves(roots, T, L, pe.hash_evaluator_np, komi=komi)
+    got = gogame.batch_puct(mc.to_dev(roots), T, pe.hash_evaluator_t, komi=komi, tree=True, leaves=L)
+    pe.check(got, want, tag=komi)
+    _invariants(got, want, T, L)
+    one = gogame.puct(mc.to_dev(roots[1]), T, pe.hash_evaluator_t, komi=komi, tree=True, leaves=L)
+    for k in pe.ROOT_KEYS:
+        assert np.array_equal(pe.bits(getattr(one, k)), pe.bits(want[k][1])), k
+    for k in pe.TREE_KEYS:
+        assert np.array_equal(pe.bits(getattr(one.tree, k)), pe.bits(want['tree'][k][1])), k
+
+
+EVALUATORS = {'hash': (pe.hash_evaluator_np, pe.hash_evaluator_t), 'hostile': (pe.hostile_evaluator_np, pe.hostile_evaluator_t),
+              'pass': (pe.pass_evaluator_np, pe.pass_evaluator_t)}
+
+
+@pytest.mark.parametrize('L', [1, 2, 4, 8, 64])
+@pytest.mark.parametrize('name,c', [('hash', 1.25), ('hash', 0.0), ('hash', 1e6), ('hostile', 1.25), ('hostile', 0.0),
+                                    ('pass', 1e6), ('pass', 1.25)])
+def test_leaves_evaluators_and_c(L, name, c):
+    """NaN, negative and infinite priors, mass on illegal actions, all-zero rows, values outside [-1, 1] (hostile); all the
+    prior on the pass; c = 0 (q alone, NaN scores with an infinite prior) and c = 10^6 (the priors alone) - for every L."""
+    from gymgo_amd import gogame
+    N = 9
+    T = max(3, 128 // L)
+    ev_np, ev_t = EVALUATORS[name]
+    roots = np.concatenate([mc.make_roots(N, 5, 62, max_ply=80, step=16), mc.crafted_roots(N)[1:]])
+    want = pl.expected_puct_leaves(roots, T, L, ev_np, c=c, komi=0.5)
+    got = gogame.batch_puct(mc.to_dev(roots), T, ev_t, c=c, komi=0.5, tree=True, leaves=L)
+    pe.check(got, want, tag=(L, name, c))
+    _invariants(got, want, T, L)
+    assert np.isfinite(mc.to_np(got.tree.value_sum)).all()
+    if L == 1:
+        pe.check(got, pe.expected_puct(roots, T, ev_np, c=c, komi=0.5), tag='one leaf')
+
+
+@pytest.mark.parametrize('N,T,name,c,komi', [(5, 90, 'hash', 0.6, 0.5), (9, 80, 'hostile', 1.25, 0.5), (9, 40, 'pass', 1e6, -0.5),
+                                             (13, 40, 'hash', 0.0, 6.5), (19, 30, 'hash', 1.25, 7.5)])
+def test_leaves_1_equals_leaves_none_bit_for_bit(N, T, name, c, komi):
+    import torch
+    from gymgo_amd import gogame
+    _, ev_t = EVALUATORS[name]
+    r = mc.to_dev(np.concatenate([mc.make_roots(N, 5, 17 + N, max_ply=2 * N * N // 3, step=N)[1:], mc.crafted_roots(N)]))
+    a = gogame.batch_puct(r, T, ev_t, c=c, komi=komi, tree=True)
+    b = gogame.batch_puct(r, T, ev_t, c=c, komi=komi, tree=True, leaves=1)
+    for k in pe.ROOT_KEYS:
+        x, y = mc.to_np(getattr(a, k)), mc.to_np(getattr(b, k))
+        assert x.shape == y.shape and x.dtype == y.dtype and np.array_equal(pe.bits(x), pe.bits(y)), k
+    for k in pe.TREE_KEYS:
+        x, y = mc.to_np(getattr(a.tree, k)), mc.to_np(getattr(b.tree, k))
+        assert x.shape == y.shape and x.dtype == y.dtype and np.array_equal(pe.bits(x), pe.bits(y)), k
+    # the same bytes: boards, child tables, priors and the stat records (the reserved word included) of the two trees
+    sa, sb = gogame.PuctSearch(r, T, c=c, komi=komi), gogame.PuctSearch(r, T, c=c, komi=komi, leaves=1)
+    for s in (sa, sb):
+        for _ in range(T):
+            s.backup(*ev_t(*s.select()))
+    used = torch.arange(T + 1, device='cuda')[None, :] < sa._nodes[:, None]
+    assert bool((sa._nodes == sb._nodes).all())
+    for x, y in ((sa._child, sb._child), (sa._prior.view(torch.int32), sb._prior.view(torch.int32)), (sa._stats, sb._stats),
+                 (sa._links, sb._links)):
+        assert bool((x == y).all())
+    assert bool(((sa._boards == sb._boards) | ~used[..., None]).all())   # (boards of unused nodes are never written)
+
+
+@pytest.mark.parametrize('policy', ['uniform', 'no_eye_fill'])
+def test_leaves_playout_evaluator(policy):
+    from gymgo_amd import gogame
+    N, T, L, K, f0 = 9, 8, 4, 8, 2
+    roots = np.concatenate([mc.make_roots(N, 4, 5, max_ply=60, step=20)[1:], mc.crafted_roots(N)[1:]])
+    ev_np = pe.playout_evaluator_np(K, 672, komi=0.5, seed=11, first_root=f0, policy=policy)
+    want = pl.expected_puct_leaves(roots, T, L, ev_np, komi=0.5)
+    ev = gogame.playout_evaluator(K, seed=11, first_root=f0, policy=policy, slots=64, komi=0.5)
+    got = gogame.batch_puct(mc.to_dev(roots), T, ev, komi=0.5, tree=True, leaves=L)
+    pe.check(got, want, tag=policy)
+    _invariants(got, want, T, L)
+
+
+def test_leaves_step_by_step_masks_numpy_input_shards_and_stream():
+    import torch
+    from gymgo_amd import gogame
+    N, T, L, R = 9, 16, 4, 7
+    A = N * N + 1
+    roots = mc.make_roots(N, R, 41, max_ply=70, step=10)
+    want = pl.expected_puct_leaves(roots, T, L, pe.hash_evaluator_np, c=1.1, komi=0.5)
+    r = mc.to_dev(roots)
+    whole = gogame.batch_puct(r, T, pe.hash_evaluator_t, c=1.1, komi=0.5, tree=True, leaves=L)
+    pe.check(whole, want, tag='whole')
+    # the step-wise form: shapes, the legality mask, the live mask, the call order
+    s = gogame.PuctSearch(r, T, c=1.1, komi=0.5, leaves=L)
+    with pytest.raises(ValueError):
+        s.backup(torch.zeros((R * L, A), device='cuda'), torch.zeros(R * L, device='cuda'))
+    for i in range(T):
+        states, legal = s.select()
+        assert states.is_cuda and states.dtype == torch.uint8 and tuple(states.shape) == (R * L, 6, N, N)
+        assert legal.is_cuda and legal.dtype == torch.bool and tuple(legal.shape) == (R * L, A)
+        assert s.live.is_cuda and s.live.dtype == torch.bool and tuple(s.live.shape) == (R, L)
+        assert bool((legal == gogame._legal_roots(states)).all())
+        assert np.array_equal(mc.to_np(legal), mc.legal_mask(mc.to_np(states)))
+        assert bool((s.live.reshape(-1) == (s._leaf_id >= 0)).all())
+        assert np.array_equal(mc.to_np(s.live), want['live'][i]), i
+        assert bool((states.reshape(R, L, 6, N, N)[~s.live] == r[:, None].expand(R, L, 6, N, N)[~s.live]).all())   # empty: the root
+        if i == 0:
+            assert bool((states[::L] == r).all()) and s.live.sum(dim=1).tolist() == [1] * R   # round 0: the roots alone
+            with pytest.raises(ValueError):
+                s.select()
+            with pytest.raises(ValueError):
+                s.result()
+            with pytest.raises(ValueError):
+                s.backup(torch.zeros((R, A), device='cuda'), torch.zeros(R, device='cuda'))   # one row per slot is needed
+        s.backup(*pe.hash_evaluator_t(states, legal))
+    with pytest.raises(ValueError):
+        s.select()
+    pe.check(s.result(tree=True), want, tag='steps')
+    pe.check(s.result(), want, tree=False, tag='steps')
+    # an evaluator that answers garbage on the empty slots changes nothing
+    def picky(states, legal):
+        p, v = pe.hash_evaluator_t(states, legal)
+        dead = ~search.live.reshape(-1)
+        p[dead] = float('nan')
+        v[dead] = float('inf')
+        return p, v
+    search = gogame.PuctSearch(r, T, c=1.1, komi=0.5, leaves=L)
+    for _ in range(T):
+        search.backup(*picky(*search.select()))
+    pe.check(search.result(tree=True), want, tag='picky')
+    # NumPy evaluations into backup; NumPy roots
+    s = gogame.PuctSearch(roots, T, c=1.1, komi=0.5, leaves=L)
+    for i in range(T):
+        states, legal = s.select()
+        s.backup(*pe.hash_evaluator_np(mc.to_np(states), mc.to_np(legal)))
+    got = s.result(tree=True)
+    assert isinstance(got.visits, np.ndarray)
+    pe.check(got, want, tag='numpy')
+    # shards by root concatenate to the whole
+    a = gogame.batch_puct(r[:3], T, pe.hash_evaluator_t, c=1.1, komi=0.5, leaves=L)
+    b = gogame.batch_puct(r[3:], T, pe.hash_evaluator_t, c=1.1, komi=0.5, leaves=L)
+    pe.check(gogame.Puct(*[torch.cat([x, y]) for x, y in zip(a[:-1], b[:-1])], tree=None), want, tree=False, tag='shards')
+    # a non-default stream
+    stream = torch.cuda.Stream()
+    with torch.cuda.stream(stream):
+        got = gogame.batch_puct(r, T, pe.hash_evaluator_t, c=1.1, komi=0.5, tree=True, leaves=L)
+    stream.synchronize()
+    pe.check(got, want, tag='stream')
+    assert bool((r == mc.to_dev(roots)).all())
+
+
+def test_leaves_empty_batch_and_argument_errors():
+    import torch
+    from gymgo_amd import gogame
+    N, L = 9, 3
+    calls = []
+
+    def ev(states, legal):
+        calls.append((tuple(states.shape), tuple(legal.shape)))
+        return torch.zeros((0, N * N + 1), device='cuda'), torch.zeros(0, device='cuda')
+
+    empty = torch.zeros((0, 6, N, N), dtype=torch.uint8, device='cuda')
+    got = gogame.batch_puct(empty, 3, ev, tree=True, leaves=L)
+    assert calls == [((0, 6, N, N), (0, N * N + 1))] * 3
+    assert got.legal.shape == (0, N * N + 1) and got.nodes.shape == (0,) and got.tree.parent.shape == (0, 3 * L + 1)
+    assert gogame.puct_actions(empty, 3, ev, leaves=L).shape == (0,)
+    roots = mc.to_dev(mc.make_roots(N, 2, 3, max_ply=20, step=10))
+    for bad in (0, -2, 1.5, 2 ** 31):
+        with pytest.raises(ValueError):
+            gogame.batch_puct(roots, 2, pe.hash_evaluator_t, leaves=bad)
+    ended = np.repeat(mc.crafted_roots(N)[3:], 3, axis=0)
+    assert gogame.puct_actions(mc.to_dev(ended), 4, pe.hash_evaluator_t, leaves=L).tolist() == [-1, -1, -1]
+
+
+def test_leaves_virtual_visits_and_select_past_capacity_on_own_buffers():
+    """The entry points called directly on this test's buffers, each followed by a tail of sentinel words.  Between a select
+    and its backup the reserved word of every node equals the number of this round's slots whose path runs through it;
+    after each backup it is 0 on every node.  Driven past T rounds the trees fill up: a select that finds no room hands out
+    the node it stopped at with move = -1, `nodes` stays at C + 1 and nothing is written beyond a tree (the sentinels, and
+    the neighbouring roots' trees through the restatement).  Leaf ids, moves, leaf boards and the whole tree equal the
+    restatement after every round."""
+    import torch
+    from gymgo_amd import gogame, _lib
+    N, T, L, extra, c, komi = 5, 5, 4, 8, 0.6, 0.5
+    A, W, C = N * N + 1, 5 * N + 1, T * L
+    NN, TAIL, MARK = C + 1, 4096, 0x5A5A5A5A
+    roots = np.concatenate([mc.crafted_roots(N)[:3], mc.make_roots(N, 5, 23, max_ply=20, step=5)[1:4]])
+    R = roots.shape[0]
+    B = R * L
+    dev = torch.device('cuda', torch.cuda.current_device())
+    lib, stream = _lib.lib(), _lib.current_raw_stream(dev)
+
+    def buf(words, dtype=torch.int32):
+        flat = torch.full((words + TAIL,), MARK, dtype=torch.int32, device=dev)
+        return flat, flat[:words].view(dtype)
+
+    flats, views = {}, {}
+    for name, words, dtype in (('boards', R * NN * W, torch.int32), ('child', R * NN * A, torch.int32),
+                               ('prior', R * NN * A, torch.float32), ('links', R * NN * 2, torch.int32),
+                               ('stats', R * NN * 4, torch.int32), ('nodes', R, torch.int32), ('leaf', B * W, torch.int32),
+                               ('move', B, torch.int32), ('leaf_id', B, torch.int32)):
+        flats[name], views[name] = buf(words, dtype)
+    ptr = {k: v.data_ptr() for k, v in views.items()}
+    tree = [ptr[k] for k in ('boards', 'child', 'prior', 'links', 'stats', 'nodes')]
+    out = [ptr[k] for k in ('leaf', 'move', 'leaf_id')]
+    states = torch.empty((B, 6, N, N), dtype=torch.uint8, device=dev)
+    legal = torch.empty((B, A), dtype=torch.bool, device=dev)
+    live = torch.empty(B, dtype=torch.bool, device=dev)
+    tracked = gogame._track_roots(mc.to_dev(roots))
+    assert lib.gg_puct_begin(tracked.data_ptr(), R, N, C, *tree, stream) == 0
+    stats = views['stats'].view(R, NN, 4)
+    links = views['links'].view(R, NN, 2)
+    trees = [pl.LeavesTree(roots[r], C) for r in range(R)]
+    no_room = 0
+    for k in range(T + extra):
+        assert lib.gg_puct_select_leaves(R, N, C, L, c, *tree, *out, stream) == 0
+        picked = [t.select_round(c, L) for t in trees]
+        ids = [y for row in picked for y, _, _ in row]
+        moves = [mv for row in picked for _, mv, _ in row]
+        assert views['leaf_id'].tolist() == ids and views['move'].tolist() == moves, k
+        # v between select and backup: the path counts of this round, from the device's own leaf ids and links
+        par = mc.to_np(links[..., 0])
+        count = np.zeros((R, NN), np.int32)
+        for row, y in enumerate(ids):
+            while y >= 0:
+                count[row // L, y] += 1
+                y = par[row // L, y]
+        assert np.array_equal(mc.to_np(stats[..., 3]), count), k
+        assert np.array_equal(count, np.stack([t.v for t in trees])), k
+        for r, t in enumerate(trees):
+            for y, mv, _ in picked[r]:
+                no_room += k >= T and y >= 0 and mv == -1 and y not in t.pending and t.legal[y].size > 0 and t.n[y] > 0
+        assert lib.gg_batch_play_moves_tracked(ptr['leaf'], ptr['move'], None, B, N, 1, stream) == 0
+        assert lib.gg_batch_untrack_states(ptr['leaf'], states.data_ptr(), B, N, stream) == 0
+        assert lib.gg_puct_legal(ptr['leaf'], ptr['leaf_id'], B, N, legal.data_ptr(), live.data_ptr(), stream) == 0
+        leaves = np.stack([b for row in picked for _, _, b in row])
+        assert np.array_equal(mc.to_np(states), leaves), k
+        assert np.array_equal(mc.to_np(legal), mc.legal_mask(leaves)) and live.tolist() == [y >= 0 for y in ids]
+        p, v = pe.hash_evaluator_t(states, legal)
+        assert lib.gg_puct_backup_leaves(R, N, C, L, komi, p.contiguous().data_ptr(), v.contiguous().data_ptr(), ptr['boards'],
+                                         ptr['prior'], ptr['links'], ptr['stats'], *out, stream) == 0
+        pn, vn = pe.hash_evaluator_np(leaves, mc.legal_mask(leaves))
+        for r, t in enumerate(trees):
+            for j, (y, _, _) in enumerate(picked[r]):
+                if y >= 0:
+                    t.backup_slot(y, pn[r * L + j], vn[r * L + j], komi)
+        assert not bool(stats[..., 3].any()), k                       # every v is 0 after the backup
+        assert (views['nodes'] <= NN).all() and views['nodes'].tolist() == [len(t.boards) for t in trees]
+        assert np.array_equal(mc.to_np(views['child'].view(R, NN, A)), np.stack([t.child for t in trees]).astype(np.int32)), k
+        assert np.array_equal(par, np.stack([t.parent for t in trees])), k
+        assert np.array_equal(mc.to_np(stats[..., 2]), np.stack([t.n for t in trees])), k
+        assert np.array_equal(pe.bits(stats.view(torch.float64)[..., 0]), pe.bits(np.stack([t.w for t in trees]))), k
+        assert np.array_equal(pe.bits(views['prior'].view(R, NN, A)), pe.bits(np.stack([t.prior for t in trees]))), k
+        for name, flat in flats.items():
+            assert bool((flat[-TAIL:] == MARK).all()), (k, name)      # nothing beyond the buffers
+    assert no_room > 0                                                # the branch was taken, at live and evaluated nodes
+    assert any(len(t.boards) == NN for t in trees)

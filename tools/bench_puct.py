@@ -14,6 +14,14 @@ Workload: R mid-game roots (random play from the empty board, `--plies` plies), 
   playouts:  batch_puct with gogame.playout_evaluator(K) and batch_uct(roots, I, K) alternate in one process, median of
              `--reps` runs each; ratio = PUCT iterations/s over UCT iterations/s.  The two searches grow different trees, so
              plies/s of both are reported too.
+
+  --leaves L [L ...]: several leaves per root per round (batch_puct(.., leaves=L)) against leaves=None at the same total leaf
+  budget: `--iters` is the budget I, the search with L leaves runs I // L rounds in a tree of the same size.
+  null:      batch_puct(.., leaves=L) and batch_puct(..) alternate in one process, median of `--reps`; us_per_leaf is wall time
+             over the leaves that were evaluated per root (the non-empty slots: mean root_visits), ratio = us_per_leaf of
+             leaves=None over that of leaves=L.
+  playouts:  plies/s of the search with playout_evaluator(K) for leaves=L against leaves=None at the same R, and against
+             leaves=None at `--ref-roots` (the batch size the drain argument compares with), all alternating in one process.
 """
 import argparse
 import json
@@ -31,6 +39,8 @@ def main():
     ap.add_argument('--plies', type=int, default=120)
     ap.add_argument('--reps', type=int, default=3)
     ap.add_argument('--c', type=float, default=1.25)
+    ap.add_argument('--leaves', type=int, nargs='+', default=None)
+    ap.add_argument('--ref-roots', type=int, default=1024)
     args = ap.parse_args()
 
     import torch
@@ -43,6 +53,10 @@ def main():
         for I in args.iters or ([64, 800] if null else [64]):
             base = {'size': N, 'roots': R, 'iterations': I, 'root_plies': args.plies, 'c': args.c,
                     'cus': int(_lib.lib().gg_device_cus()), 'reps': args.reps}
+            if args.leaves:
+                for res in _leaves(args, gogame, torch, roots, base, null):
+                    print(json.dumps(res), flush=True)
+                continue
             if null:
                 priors = torch.full((R, A), 1.0 / A, dtype=torch.float32, device='cuda:0')
                 values = torch.zeros(R, dtype=torch.float32, device='cuda:0')
@@ -80,6 +94,58 @@ def main():
                            mean_plies_puct=plies_a / P, mean_plies_uct=plies_b / P,
                            mean_nodes=float(pa.nodes.float().mean()), mean_nodes_uct=float(ub.nodes.float().mean()))
             print(json.dumps(res), flush=True)
+
+
+def _leaves(args, gogame, torch, roots, base, null):
+    """The --leaves comparison: one result per L, each against leaves=None in alternation."""
+    R, N, I, K = base['roots'], base['size'], base['iterations'], args.k
+    A = N * N + 1
+    if null:
+        for L in args.leaves:
+            T = I // L
+            priors = torch.full((R * L, A), 1.0 / A, dtype=torch.float32, device='cuda:0')
+            values = torch.zeros(R * L, dtype=torch.float32, device='cuda:0')
+            ev_l = lambda states, legal: (priors, values)
+            ev_1 = lambda states, legal: (priors[:R], values[:R])
+            run_l = lambda: gogame.batch_puct(roots, T, ev_l, c=args.c, komi=7.5, tree=True, leaves=L)
+            run_1 = lambda: gogame.batch_puct(roots, I, ev_1, c=args.c, komi=7.5, tree=True)
+            run_l(), run_1()   # warm-up
+            (sl, ol), (s1, o1) = median_timed(run_l, run_1, reps=args.reps)
+            done = float(ol.root_visits.double().mean())
+            assert bool((o1.root_visits == I).all())
+            us_l, us_1 = sl / done * 1e6, s1 / I * 1e6
+            yield dict(base, metric='puct_leaves_wall_us_per_leaf', evaluator='null', leaves=L, rounds=T, seconds=sl,
+                       seconds_one_leaf=s1, leaves_evaluated_per_root=done, live_slots_per_round=done / T,
+                       us_per_leaf=us_l, us_per_leaf_one_leaf=us_1, ratio=us_1 / us_l, us_per_round=sl / T * 1e6,
+                       mean_nodes=float(ol.nodes.float().mean()), mean_nodes_one_leaf=float(o1.nodes.float().mean()),
+                       mean_node_depth=_mean_leaf_depth(ol.tree.parent, ol.nodes))
+        return
+    kw = dict(komi=7.5)
+    ref_roots = mid_game_roots(args.ref_roots, N, args.plies)
+    evs = {}
+
+    def runner(key, rts, rounds, L):
+        def run():
+            evs[key] = gogame.playout_evaluator(K, seed=1, **kw)
+            return gogame.batch_puct(rts, rounds, evs[key], c=args.c, leaves=L, **kw)
+        return run
+
+    runs = [('none', runner('none', roots, I, None)), ('ref', runner('ref', ref_roots, I, None))]
+    runs += [(L, runner(L, roots, I // L, L)) for L in args.leaves]
+    for _, fn in runs:
+        fn()   # warm-up
+    timed_runs = median_timed(*[fn for _, fn in runs], reps=args.reps)
+    rate = {key: int(evs[key].plies_sum) / s for (key, _), (s, _) in zip(runs, timed_runs)}
+    for (key, _), (s, out) in zip(runs, timed_runs):
+        L = None if key in ('none', 'ref') else key
+        rr = args.ref_roots if key == 'ref' else R
+        rounds = I if L is None else I // L
+        done = float(out.root_visits.double().mean())
+        yield dict(base, metric='puct_leaves_plies_per_s', evaluator='playouts', k=K, roots=rr, leaves=L, rounds=rounds,
+                   seconds=s, plies=int(evs[key].plies_sum), plies_per_s=rate[key], ratio_to_one_leaf=rate[key] / rate['none'],
+                   ratio_to_ref_roots=rate[key] / rate['ref'], ref_roots=args.ref_roots,
+                   leaves_evaluated_per_root=done, live_slots_per_round=done / rounds,
+                   jobs_per_slot=rr * (L or 1) * K / (256 * base['cus']))
 
 
 def _mean_leaf_depth(parent, nodes):
