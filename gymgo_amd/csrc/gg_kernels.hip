@@ -1482,4 +1482,21 @@ int32_t gg_puct_legal(const uint32_t *leaf, const int32_t *leaf_id, int64_t B, i
   return (int32_t)hipGetLastError();
 }
 
+int32_t gg_puct_advance(const int32_t *actions, const uint32_t *next, int64_t R, int32_t N, int32_t C, uint32_t *boards,
+                        int32_t *child, float *prior, int32_t *links, gg_puct_stat *stats, int32_t *nodes, int32_t *remap,
+                        int32_t *kept, void *hip_stream) {
+  PuctAdvanceArgs u;
+  if (int32_t e = puct_args(u.t, R, N, C, 0.0, 0.f, boards, child, prior, links, stats, nodes, nullptr, nullptr, nullptr)) return e;
+  if (!actions || !next || !boards || !child || !prior || !links || !stats || !nodes || !remap) return GG_E_NULLPTR;
+  if (R == 0) return 0;
+  u.actions = actions;
+  u.next = next;
+  u.remap = remap;
+  u.kept = kept;   // (may be NULL)
+  OnDeviceOf on_dev(boards);
+  hipStream_t s = (hipStream_t)hip_stream;
+  k_puct_advance<<<grid_for(on_dev.cus(), (R + 3) / 4), 4 * kWave, 0, s>>>(u);
+  return (int32_t)hipGetLastError();
+}
+
 }  // extern "C"

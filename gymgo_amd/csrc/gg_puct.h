@@ -436,4 +436,243 @@ static __global__ __launch_bounds__(256) void k_puct_legal(const uint32_t *__res
   }
 }
 
+// ---------------------------------------------------------------- tree reuse across moves: keep the subtree of the move played
+// k_puct_advance (gg_puct_advance of include/gymgo_amd.h, which holds the normative text).  Between two rounds (every v = 0)
+// root r plays actions[r]: the subtree under that root child becomes the tree, in place, by an order-preserving renumbering;
+// without such a child the tree is gg_puct_begin's for the board next[r]; -1 leaves the tree alone.  One wave per root, as
+// everywhere in this file, in three steps:
+//   MARK    ascending over 64 nodes at a time: node x is kept when it is k or its parent (smaller id) is kept.  Parents inside
+//           the chunk are resolved by pointer jumping over shuffles, parents of earlier chunks from remap (a hand-over fence
+//           per chunk); the new id of a kept node is the running count plus the ballot's prefix count.  remap[x] = new id, -1.
+//   MOVE    ascending again, kPuctGroup kept nodes per turn: all their rows are loaded (dwordx4 per lane, the rows are only
+//           4-byte aligned), then the child entries and the parent go through remap, then everything is stored at the new ids.
+//           new(x) <= x and the sweep ascends, so a store never lands on a row that is still to be read: the rows of new id
+//           j were those of a source <= every later source, and inside a turn every load precedes every store in program
+//           order (the stores wait for their own operands, loads of one wave return in order).
+//           HARDWARE ASSUMPTION, not the language's memory model: inside a turn one lane's store may land on words another
+//           lane loaded in the same turn (new id n3 = source x1), with no fence between them.  That is safe because (a) a
+//           wave's vector memory instructions issue in program order and its loads return in order (one vmcnt counter), so a
+//           store, which waits for its own data, is issued after every earlier load of the wave has returned, and (b) the
+//           compiler keeps the loads in front of the stores, which it must for a single lane already: both go through the
+//           same base pointers at run-time indices.  Across lanes C++ calls this a data race; gfx9 wave execution orders it.
+//           A puct_handover() in front of the store phase would say the same thing to the compiler; it is not there because
+//           it is not needed on this target and its cost was not measured.
+//   RESET   after a fence (every load above has returned): the nodes [kept, m) go back to gg_puct_begin's state as five flat
+//           fills, dwordx4 from the first 16-byte boundary on.
+// Every index is bounded by the tree: m clamped, parents in [k, x), children in (x, m), new ids clamped to [0, x].
+
+typedef uint32_t puct_q __attribute__((ext_vector_type(4), aligned(4)));     // four words of a row: any word boundary
+typedef uint32_t puct_q16 __attribute__((ext_vector_type(4), aligned(16)));  // four words on a 16-byte boundary
+
+struct PuctAdvanceArgs {
+  PuctArgs t;                // the tree; t.I = C, the capacity (leaf, move, leaf_id, priors, values unused)
+  const int32_t *actions;    // [R] the action played at each root, -1 = none
+  const uint32_t *next;      // [R][5N+1] the root's board after its action (read where a fresh tree is made)
+  int32_t *remap;            // [R][C+1] scratch: the new id of every node, -1 = dropped
+  int32_t *kept;             // [R] nodes kept (0: a fresh tree), may be NULL
+};
+
+constexpr int kPuctGroup = 4;   // kept nodes whose loads are in flight together (about 13 KB per wave at 19x19)
+
+// Q * 64 dwordx4 and up to 3 single words per lane: a row of at most 256 Q + 3 words
+template <int Q>
+struct PuctRow {
+  puct_q q[Q];
+  uint32_t t;
+};
+
+template <int Q>
+__device__ __forceinline__ void puct_row_load(PuctRow<Q> &v, const uint32_t *src, int words, int lane, bool on) {
+  const int nq = words >> 2;
+#pragma unroll
+  for (int i = 0; i < Q; ++i) {
+    const int q = lane + i * kWave;
+    v.q[i] = puct_q{~0u, ~0u, ~0u, ~0u};
+    if (on && q < nq) v.q[i] = *reinterpret_cast<const puct_q *>(src + 4 * q);
+  }
+  const int tw = 4 * nq + lane;   // (the words after the last whole four: lanes 0 .. words % 4 - 1)
+  v.t = ~0u;
+  if (on && tw < words) v.t = src[tw];
+}
+
+template <int Q>
+__device__ __forceinline__ void puct_row_store(const PuctRow<Q> &v, uint32_t *dst, int words, int lane, bool on) {
+  const int nq = words >> 2;
+#pragma unroll
+  for (int i = 0; i < Q; ++i) {
+    const int q = lane + i * kWave;
+    if (on && q < nq) *reinterpret_cast<puct_q *>(dst + 4 * q) = v.q[i];
+  }
+  const int tw = 4 * nq + lane;
+  if (on && tw < words) dst[tw] = v.t;
+}
+
+// a child entry of node x under the renumbering: negative entries stay, a child id in (x, m) becomes its new id, anything
+// else (only with corrupt buffers) -1.  The gather has no branch - an entry without a child reads remap[k], which is inside
+// the tree - so that all the gathers of a turn are in flight together.
+__device__ __forceinline__ uint32_t puct_new_child(uint32_t e, int x, int k, int m, const int32_t *rm) {
+  const int c = (int)e;
+  const bool inside = c > x && c < m;
+  const uint32_t id = (uint32_t)rm[inside ? c : k];
+  const uint32_t neg = (uint32_t)(c >> 31), in = 0u - (uint32_t)inside;   // all ones / zero: the choice below stays arithmetic
+  return (e & neg) | ((id | ~in) & ~neg);
+}
+
+// p[0 .. words) = value: single words up to the first 16-byte boundary, dwordx4 from there, single words for the rest
+__device__ __forceinline__ void puct_fill(uint32_t *p, int64_t words, uint32_t value, int lane) {
+  if (words <= 0) return;
+  const int64_t head = min(words, (int64_t)((4 - (int)((reinterpret_cast<uintptr_t>(p) >> 2) & 3)) & 3));
+  if (lane < head) p[lane] = value;
+  p += head;
+  words -= head;
+  const int64_t nq = words >> 2;
+  puct_q16 *q = reinterpret_cast<puct_q16 *>(p);
+  const puct_q16 v = {value, value, value, value};
+  for (int64_t i = lane; i < nq; i += kWave) q[i] = v;
+  const int64_t tw = 4 * nq + lane;
+  if (tw < words) p[tw] = value;
+}
+
+static __global__ __launch_bounds__(4 * kWave) void k_puct_advance(PuctAdvanceArgs b) {
+  static_assert(5 * GG_MAX_BOARD + 1 <= 4 * kWave + 3 && GG_MAX_BOARD * GG_MAX_BOARD + 1 <= 8 * kWave + 3,
+                "a board fits PuctRow<1>, a child or prior row PuctRow<2>");
+  const PuctArgs &a = b.t;
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t wave = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) / kWave;
+  const int64_t nwaves = (gridDim.x * (int64_t)blockDim.x) / kWave;
+  const int N = a.N, W = 5 * N + 1, A = N * N + 1, NN = a.I + 1;
+  for (int64_t r = wave; r < a.R; r += nwaves) {
+    uint32_t *bd = a.boards + r * NN * W;
+    uint32_t *ch = reinterpret_cast<uint32_t *>(a.child) + r * NN * A;
+    uint32_t *pr = reinterpret_cast<uint32_t *>(a.prior) + r * NN * A;   // (priors move as bit patterns)
+    int32_t *ln = a.links + r * NN * 2;
+    PuctStat *st = a.stats + r * NN;
+    int32_t *rm = b.remap + r * NN;
+    const int m = __builtin_amdgcn_readfirstlane(max(1, min(a.nodes[r], NN)));   // (1 <= m <= C + 1: every index below stays inside the tree)
+    const int act = b.actions[r];
+    int k = -1;   // the node that becomes the root: 0 = the root stays, -1 = none (a fresh tree)
+    if (act == -1) {
+      k = 0;
+    } else if (act >= 0 && act < A) {
+      const int c0 = (int)ch[act];
+      if (c0 >= 1 && c0 < m) k = c0;
+    }
+    k = __builtin_amdgcn_readfirstlane(k);
+    if (k == 0) {   // not a byte of the tree changes
+      if (lane == 0 && b.kept) b.kept[r] = m;
+      continue;
+    }
+    int cnt = 0;   // kept nodes so far
+    if (k > 0) {
+      const int base0 = k & ~(kWave - 1);   // (nodes below k are dropped: their remap entries are never read)
+      // MARK
+      for (int base = base0; base < m; base += kWave) {
+        const int x = base + lane;
+        const int p = x < m ? ln[2 * (int64_t)x] : -1;
+        int state = 0, ptr = 0;   // 0: dropped, 1: kept, 2: as the parent, which is lane ptr of this chunk
+        if (x == k) {
+          state = 1;
+        } else if (x > k && x < m && p >= k && p < x) {   // (parents have smaller ids; below k nothing is kept)
+          if (p >= base) {
+            state = 2;
+            ptr = p - base;
+          } else {
+            state = rm[p] >= 0 ? 1 : 0;
+          }
+        }
+        // an unresolved lane points at a lower lane: the lowest of them resolves in every turn, jumping halves the chains
+        while (__ballot(state == 2)) {
+          const int s = __shfl(state, ptr), pp = __shfl(ptr, ptr);
+          if (state == 2) {
+            if (s != 2) state = s;
+            else ptr = pp;
+          }
+        }
+        const unsigned long long mask = __ballot(state == 1);
+        if (x < m) rm[x] = state == 1 ? cnt + __popcll(mask & ((1ull << lane) - 1ull)) : -1;
+        cnt += __popcll(mask);
+        puct_handover();   // the next chunk's lanes read remap entries that other lanes stored here
+      }
+      // MOVE
+      for (int base = base0; base < m; base += kWave) {
+        const int x = base + lane;
+        const int id = x < m ? rm[x] : -1;
+        unsigned long long mask = __ballot(id >= 0);
+        while (mask) {
+          int xs[kPuctGroup], ns[kPuctGroup];
+          PuctRow<1> vb[kPuctGroup];
+          PuctRow<2> vc[kPuctGroup], vp[kPuctGroup];
+          int32_t lp[kPuctGroup], la[kPuctGroup];
+          puct_q16 vs[kPuctGroup];   // the stat records as four words: w (two), n, v
+#pragma unroll
+          for (int i = 0; i < kPuctGroup; ++i) {
+            xs[i] = -1;
+            ns[i] = 0;
+            if (mask) {
+              const int bit = __ffsll(mask) - 1;
+              xs[i] = base + bit;
+              ns[i] = max(0, min(__shfl(id, bit), xs[i]));   // (new(x) <= x)
+              mask &= mask - 1ull;
+            }
+          }
+#pragma unroll
+          for (int i = 0; i < kPuctGroup; ++i) {   // every load of the turn
+            const bool on = xs[i] >= 0;
+            const int64_t x64 = on ? xs[i] : 0;
+            puct_row_load(vc[i], ch + x64 * A, A, lane, on);
+            puct_row_load(vp[i], pr + x64 * A, A, lane, on);
+            puct_row_load(vb[i], bd + x64 * W, W, lane, on);
+            lp[i] = ln[2 * x64];   // (every lane the same words, no branch: only lane 0 stores them)
+            la[i] = ln[2 * x64 + 1];
+            vs[i] = *reinterpret_cast<const puct_q16 *>(st + x64);
+          }
+#pragma unroll
+          for (int i = 0; i < kPuctGroup; ++i) {   // the renumbering: child entries and the parent
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+              vc[i].q[j].x = puct_new_child(vc[i].q[j].x, xs[i], k, m, rm);
+              vc[i].q[j].y = puct_new_child(vc[i].q[j].y, xs[i], k, m, rm);
+              vc[i].q[j].z = puct_new_child(vc[i].q[j].z, xs[i], k, m, rm);
+              vc[i].q[j].w = puct_new_child(vc[i].q[j].w, xs[i], k, m, rm);
+            }
+            vc[i].t = puct_new_child(vc[i].t, xs[i], k, m, rm);
+            const bool below = lp[i] >= k && lp[i] < xs[i];   // (a kept node other than k has its parent in [k, x))
+            const int32_t np = rm[below ? lp[i] : k];
+            lp[i] = xs[i] == k || !below ? -1 : np;
+            la[i] = xs[i] == k ? -1 : la[i];   // the new root
+            vs[i].w = 0u;   // v
+          }
+#pragma unroll
+          for (int i = 0; i < kPuctGroup; ++i) {   // every store of the turn (after every load: the assumption stated above)
+            const bool on = xs[i] >= 0;
+            const int64_t n64 = ns[i];
+            puct_row_store(vc[i], ch + n64 * A, A, lane, on);
+            puct_row_store(vp[i], pr + n64 * A, A, lane, on);
+            puct_row_store(vb[i], bd + n64 * W, W, lane, on);
+            if (on && lane == 0) {
+              ln[2 * n64] = lp[i];
+              ln[2 * n64 + 1] = la[i];
+              *reinterpret_cast<puct_q16 *>(st + n64) = vs[i];
+            }
+          }
+        }
+      }
+    } else {   // a fresh tree: node 0 = next[r]
+      const uint32_t *nx = b.next + r * W;
+      for (int i = lane; i < W; i += kWave) bd[i] = nx[i];
+    }
+    puct_handover();   // RESET: every row above has been read
+    const int lo = cnt;   // (0 for a fresh tree: node 0 gets begin's rows as well, all but its board)
+    puct_fill(ch + (int64_t)lo * A, (int64_t)(m - lo) * A, ~0u, lane);
+    puct_fill(pr + (int64_t)lo * A, (int64_t)(m - lo) * A, 0u, lane);
+    puct_fill(reinterpret_cast<uint32_t *>(ln) + (int64_t)lo * 2, (int64_t)(m - lo) * 2, ~0u, lane);
+    puct_fill(reinterpret_cast<uint32_t *>(st) + (int64_t)lo * 4, (int64_t)(m - lo) * 4, 0u, lane);
+    puct_fill(bd + (int64_t)max(lo, 1) * W, (int64_t)(m - max(lo, 1)) * W, 0u, lane);
+    if (lane == 0) {
+      a.nodes[r] = max(cnt, 1);
+      if (b.kept) b.kept[r] = cnt;
+    }
+  }
+}
+
 }  // namespace gg

@@ -1207,8 +1207,8 @@ Puct.__doc__ = """Results of batch_puct per root: legal (bool [R, A], A = N*N + 
 root's, as stored - zero on illegal actions), root_visits (int32 [R]), root_value_sum (float64 [R]), nodes (int32 [R]: tree
 nodes in use) and tree (PuctTree or None)."""
 PuctTree = collections.namedtuple('PuctTree', 'parent action visits value_sum')
-PuctTree.__doc__ = """The whole tree of every root, each field [R, iterations + 1] ([R, iterations * leaves + 1] with `leaves`)
-indexed by node (node 0 = the root): parent / action / visits int32 (-1 / -1 / 0 at unused nodes; -1 / -1 at the root),
+PuctTree.__doc__ = """The whole tree of every root, each field [R, iterations + 1] ([R, iterations * leaves + 1] with `leaves`;
+[R, capacity] with `capacity`) indexed by node (node 0 = the root): parent / action / visits int32 (-1 / -1 / 0 at unused nodes; -1 / -1 at the root),
 value_sum float64 (w, black's point of view)."""
 
 
@@ -1231,6 +1231,20 @@ def _puct_leaves(iterations, leaves):
     return L
 
 
+def _puct_capacity(iterations, leaves, capacity):
+    """-> nodes per root: capacity=None gives iterations + 1 (iterations * leaves + 1); an integer must be at least that and
+    below 2^31."""
+    least = int(iterations) * (leaves or 1) + 1
+    if capacity is None:
+        return least
+    if isinstance(capacity, bool) or not isinstance(capacity, (int, np.integer)) or not least <= int(capacity) < 2 ** 31:
+        raise ValueError('capacity must be None or an integer in [%d, 2^31) (got %r)' % (least, capacity))
+    return int(capacity)
+
+
+_ON_DEVICE = collections.namedtuple('_OnDevice', 'numpy')(False)   # a _Box stand-in: results stay device tensors
+
+
 class PuctSearch:
     """The step-wise form of batch_puct, for callers who batch their network calls their own way:
 
@@ -1249,22 +1263,36 @@ class PuctSearch:
     one after the other under virtual loss (batch_puct).  select() then returns states uint8 [R * L, 6, N, N] and legal
     bool [R * L, A] in row order r * L + j, backup() takes priors [R * L, A] and values [R * L]; rows of empty slots are
     evaluated like any other and ignored.  `search.live` (bool [R, L], a device tensor valid until the next select()) says
-    which slots hold a leaf, for evaluators that want to skip the rest.  The tree has iterations * L + 1 nodes per root."""
+    which slots hold a leaf, for evaluators that want to skip the rest.  The tree has iterations * L + 1 nodes per root.
 
-    def __init__(self, batch_states, iterations, c=1.25, komi=0.0, leaves=None):
-        self._box = _Box(batch_states)
+    capacity (None = the sizes above, every allocation and launch as without it): the nodes per root, an integer >= that
+    default and < 2^31; `iterations` stays the bound on rounds.  Room beyond the default is what advance() needs to go on
+    growing a kept tree.
+
+    advance(actions) plays one action per root between two rounds and keeps the subtree under it (gg_puct_advance); then
+    `iterations` more rounds may follow.  A tree that is full falls under the no-room rule of batch_puct: the search goes
+    on refining values and expands nothing.  No finite capacity excludes that over many moves; result().nodes shows how
+    full the trees are.  A kept root is already evaluated and is not handed out again, so root noise that the evaluator
+    adds reaches only fresh roots."""
+
+    def __init__(self, batch_states, iterations, c=1.25, komi=0.0, leaves=None, capacity=None):
+        self._box = batch_states if isinstance(batch_states, _Box) else _Box(batch_states)   # (a _Box: puct_play's own states)
         st = self._box.t
         if st.dim() != 4 or st.shape[1] != govars.NUM_CHNLS or st.shape[2] != st.shape[3]:
             raise ValueError('batch_states must be [R, 6, N, N] (got %s)' % (tuple(st.shape),))
         self._I, self._c, self._komi = _puct_args(iterations, c, komi)
+        self._I0 = self._I      # the rounds as constructed: advance()'s default, whatever an earlier advance was given
         self._L = _puct_leaves(self._I, leaves)
+        NN = _puct_capacity(self._I, self._L, capacity)
         R, N, dev = st.shape[0], st.shape[2], st.device
         self._R, self._N, self._dev = R, N, dev
+        self._C = NN - 1        # what the kernels get as I / C: only a capacity there
+        self._scratch = None    # advance()'s buffers, allocated on its first call
         if self._L is not None:
             self._init_leaves(st)
             return
-        I = self._I
-        W, A, NN = tracked_words(N), N * N + 1, I + 1
+        I = self._C
+        W, A = tracked_words(N), N * N + 1
         self._legal_roots = _legal_roots(st)
         self._boards = torch.empty((R, NN, W), dtype=_I32, device=dev)
         self._child = torch.empty((R, NN, A), dtype=_I32, device=dev)
@@ -1291,7 +1319,7 @@ class PuctSearch:
         """The buffers of the several-leaves path: the tree of C + 1 = iterations * leaves + 1 nodes (gg_puct_begin with
         I = C: the same bytes as a one-leaf tree of C iterations), R * L rows of everything that is handed out."""
         R, N, L, dev = self._R, self._N, self._L, self._dev
-        C = self._C = self._I * L
+        C = self._C
         W, A, NN, B = tracked_words(N), N * N + 1, C + 1, R * L
         self._legal_roots = _legal_roots(st)
         self._boards = torch.empty((R, NN, W), dtype=_I32, device=dev)
@@ -1357,7 +1385,7 @@ class PuctSearch:
             raise ValueError('PuctSearch.select(): all %d iterations are done' % self._I)
         if self._L is not None:
             return self._select_leaves()
-        R, N, I = self._R, self._N, self._I
+        R, N, I = self._R, self._N, self._C
         if R:
             L, stream = _lib.lib(), _lib.current_raw_stream(self._dev)
             lp, mp, ip = self._out
@@ -1385,7 +1413,7 @@ class PuctSearch:
             raise ValueError('need priors [%d, %d] and values [%d] (got %s, %s)' % (R, A, R, tuple(priors.shape), tuple(values.shape)))
         if R:
             boards, _, prior, links, stats, _ = self._tree
-            _lib.check(_lib.lib().gg_puct_backup(R, N, self._I, self._komi, _lib.dev_ptr(priors, torch.float32, 'priors'),
+            _lib.check(_lib.lib().gg_puct_backup(R, N, self._C, self._komi, _lib.dev_ptr(priors, torch.float32, 'priors'),
                                                  _lib.dev_ptr(values.reshape(R), torch.float32, 'values'), boards, prior, links,
                                                  stats, *self._out, _lib.current_raw_stream(self._dev)), 'gg_puct_backup')
         self._pending = False
@@ -1396,6 +1424,10 @@ class PuctSearch:
         views of the search's own buffers: clone what has to survive a later select()."""
         if self._pending:
             raise ValueError('PuctSearch.result(): the leaves of the last select() have not been backed up')
+        return _back(self._box, self._result(tree))
+
+    def _result(self, tree=False):
+        """result() as device tensors, whatever batch_states was."""
         R, A = self._R, self._N * self._N + 1
         n, w = self._stats[..., 2], self._stats.view(torch.float64)[..., 0]
         rc = self._child[:, 0, :]
@@ -1403,10 +1435,101 @@ class PuctSearch:
         visits = torch.where(has, torch.gather(n, 1, idx), torch.zeros_like(rc))
         vsum = torch.where(has, torch.gather(w, 1, idx), torch.zeros((R, A), dtype=torch.float64, device=self._dev))
         whole = PuctTree(self._links[..., 0], self._links[..., 1], n, w) if tree else None
-        return _back(self._box, Puct(self._legal_roots, visits, vsum, self._prior[:, 0, :], n[:, 0], w[:, 0], self._nodes, whole))
+        return Puct(self._legal_roots, visits, vsum, self._prior[:, 0, :], n[:, 0], w[:, 0], self._nodes, whole)
+
+    def root_states(self):
+        """-> uint8 [R, 6, N, N]: the current roots, untracked from node 0 of every tree (a new tensor, or NumPy array for
+        NumPy input), so that the caller need not step a second copy of the games."""
+        if self._pending:
+            raise ValueError('PuctSearch.root_states(): the leaves of the last select() have not been backed up')
+        return self._box.back(self._root_states()) if self._box.numpy else self._root_states()
+
+    def _root_states(self):
+        R, N = self._R, self._N
+        states = torch.empty((R, govars.NUM_CHNLS, N, N), dtype=_U8, device=self._dev)
+        if R:
+            self._advance_buffers()
+            with torch.cuda.device(self._dev):
+                self._next.copy_(self._boards[:, 0, :])
+            _lib.check(_lib.lib().gg_batch_untrack_states(_lib.dev_ptr(self._next, _I32, 'next'), _lib.dev_ptr(states, _U8, 'states'),
+                                                          R, N, _lib.current_raw_stream(self._dev)), 'gg_batch_untrack_states')
+        return states
+
+    def _advance_buffers(self):
+        """next [R, W], remap [R, capacity] and kept [R]: allocated once per search."""
+        if self._scratch is None:
+            R, dev = self._R, self._dev
+            self._next = torch.empty((R, tracked_words(self._N)), dtype=_I32, device=dev)
+            self._remap = torch.empty((R, self._C + 1), dtype=_I32, device=dev)
+            self._kept = torch.empty(R, dtype=_I32, device=dev)
+            self._scratch = tuple(_lib.dev_ptr(t, _I32, n) for t, n in ((self._next, 'next'), (self._remap, 'remap'),
+                                                                        (self._kept, 'kept'))) if R else ()
+        return self._scratch
+
+    def _play_on_roots(self, acts):
+        """next = node 0's boards after acts (int64 [R] on the device; R > 0) -> the pointers of (actions as int32, next,
+        remap, kept).  Whatever lies outside [-1, A) - below -1 too, which must not become the -1 that leaves a root
+        alone - goes down as A: an illegal action in int32 range."""
+        A = self._N * self._N + 1
+        acts = torch.where((acts < -1) | (acts > A), torch.full_like(acts, A), acts).to(_I32).contiguous()
+        np_, rp, kp = self._advance_buffers()
+        ap = _lib.dev_ptr(acts, _I32, 'actions')
+        with torch.cuda.device(self._dev):
+            self._next.copy_(self._boards[:, 0, :])
+        stream = _lib.current_raw_stream(self._dev)
+        _lib.check(_lib.lib().gg_batch_play_moves_tracked(np_, ap, None, self._R, self._N, 1, stream), 'gg_batch_play_moves_tracked')
+        return ap, np_, rp, kp
+
+    def _played_states(self, acts):
+        """-> uint8 [R, 6, N, N], a new device tensor: the roots after acts (int64 [R] on the device, -1 stays put), played on
+        a copy of node 0's boards alone; the tree is not touched."""
+        R, N = self._R, self._N
+        states = torch.empty((R, govars.NUM_CHNLS, N, N), dtype=_U8, device=self._dev)
+        if R:
+            _, np_, _, _ = self._play_on_roots(acts)
+            _lib.check(_lib.lib().gg_batch_untrack_states(np_, _lib.dev_ptr(states, _U8, 'states'), R, N,
+                                                          _lib.current_raw_stream(self._dev)), 'gg_batch_untrack_states')
+        return states
+
+    def advance(self, actions, iterations=None, check=True):
+        """Play actions (int [R], a tensor or NumPy array; -1 = this root does not move) between two rounds and keep the
+        subtree under each action -> kept, an int32 [R] device tensor owned by the search: the nodes kept per root, 0 where
+        the tree starts afresh (the action had no child yet).  The next boards come from gg_batch_play_moves_tracked on a
+        copy of the roots, the trees are renumbered in place by gg_puct_advance, result().legal follows the new roots and
+        the round counter starts again: `iterations` (default: as constructed, whatever an earlier advance was given) more
+        rounds may follow.  check=True verifies on
+        the device that every action other than -1 is legal at its root - one synchronisation - and raises ValueError naming
+        the first root where it is not; check=False does not synchronise: an illegal action then does what
+        gg_batch_play_moves_tracked does with it, and its root gets a fresh tree (so does anything outside [-1, A): only -1
+        itself leaves a root alone)."""
+        if self._pending:
+            raise ValueError('PuctSearch.advance(): the leaves of the last select() have not been backed up')
+        R, N, A = self._R, self._N, self._N * self._N + 1
+        if not isinstance(actions, torch.Tensor):
+            actions = torch.from_numpy(np.ascontiguousarray(actions))
+        if tuple(actions.shape) != (R,) or actions.dtype.is_floating_point or actions.dtype == torch.bool:
+            raise ValueError('actions must be integers [%d] (got %s %s)' % (R, actions.dtype, tuple(actions.shape)))
+        rounds = self._I0 if iterations is None else _puct_args(iterations, self._c, self._komi)[0]
+        if not R:
+            self._done, self._I = 0, rounds
+            return torch.empty(0, dtype=_I32, device=self._dev)
+        acts = actions.to(device=self._dev, dtype=_I64)
+        if check:
+            inside = (acts >= 0) & (acts < A)
+            ok = torch.gather(self._legal_roots, 1, acts.clamp(0, A - 1)[:, None])[:, 0] & inside
+            bad = torch.nonzero((acts != -1) & ~ok)
+            if bad.numel():   # (the synchronisation)
+                r = int(bad[0, 0])
+                raise ValueError('PuctSearch.advance(): action %d is not legal at root %d' % (int(acts[r]), r))
+        ap, np_, rp, kp = self._play_on_roots(acts)
+        _lib.check(_lib.lib().gg_puct_advance(ap, np_, R, N, self._C, *self._tree, rp, kp, _lib.current_raw_stream(self._dev)),
+                   'gg_puct_advance')
+        self._legal_roots = _legal_roots(self._root_states())
+        self._done, self._I = 0, rounds
+        return self._kept
 
 
-def batch_puct(batch_states, iterations, evaluator, c=1.25, komi=0.0, tree=False, leaves=None):
+def batch_puct(batch_states, iterations, evaluator, c=1.25, komi=0.0, tree=False, leaves=None, capacity=None):
     """PUCT search (the AlphaZero search) of `iterations` iterations from every root of batch_states ([R, 6, N, N]) with the
     caller's evaluator -> Puct (device tensors for a device tensor, NumPy arrays for NumPy input).  The loop over PuctSearch.
 
@@ -1444,16 +1567,63 @@ def batch_puct(batch_states, iterations, evaluator, c=1.25, komi=0.0, tree=False
     order (n += 1, w += value, v -= 1 on the path).  root_visits = the non-empty slots (round 0 evaluates the root alone);
     leaves=1 gives the tree of leaves=None exactly; no random numbers, shards by root still concatenate.  Needs
     iterations * L < 2^31 - 1.  Device memory of the tree: R * (iterations * L + 1) * (4 (5N + 1) + 8 (N^2 + 1) + 24)
-    bytes - the formula above with iterations * L + 1 nodes - and PuctTree fields are [R, iterations * L + 1]."""
-    ek = getattr(evaluator, 'komi', None)   # (playout_evaluator says what komi it scores with)
-    if ek is not None and float(ek) != float(komi):
-        raise ValueError('the evaluator scores its playouts with komi %r, the search its ended leaves with %r' % (ek, komi))
-    search = PuctSearch(batch_states, iterations, c, komi, leaves=leaves)
+    bytes - the formula above with iterations * L + 1 nodes - and PuctTree fields are [R, iterations * L + 1].
+
+    capacity (None: the sizes above): the nodes per root, an integer >= the default and < 2^31; the tree, its device memory
+    and the PuctTree fields are then [R, capacity].  It changes no result of this call (the extra nodes stay unused): it is
+    PuctSearch.advance and puct_play that need the room."""
+    _puct_komi_guard(evaluator, komi)
+    search = PuctSearch(batch_states, iterations, c, komi, leaves=leaves, capacity=capacity)
     for _ in range(search._I):
         states, legal = search.select()
         priors, values = evaluator(states, legal)
         search.backup(priors, values)
     return search.result(tree=tree)
+
+
+def _puct_komi_guard(evaluator, komi):
+    ek = getattr(evaluator, 'komi', None)   # (playout_evaluator says what komi it scores with)
+    if ek is not None and float(ek) != float(komi):
+        raise ValueError('the evaluator scores its playouts with komi %r, the search its ended leaves with %r' % (ek, komi))
+
+
+def puct_play(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, leaves=None, capacity=None, reuse=True):
+    """Play `moves` moves from every root of batch_states ([R, 6, N, N]) with a PUCT search per move -> (actions int64
+    [R, moves], the final states uint8 [R, 6, N, N]); device tensors for a device tensor, NumPy arrays for NumPy input.
+    Per move: `iterations` rounds of PuctSearch (batch_puct's loop, with `leaves` and `capacity` as there), the move of
+    every root is its legal child with the most visits (ties to the lowest action; -1 for a root without a legal move,
+    which stays where it is), then PuctSearch.advance: with reuse=True the subtree under the move played is the next
+    move's tree, so its visits are not paid for again and the roots get deeper for the same evaluator work.  reuse=False
+    is the same loop with a new PuctSearch on the next states (the move played on node 0's boards alone, no advance over a
+    tree that is dropped) after every move: what a caller could do before advance
+    existed, kept as the comparison.  The evaluator is called moves * iterations times and must score with the search's
+    komi (batch_puct's guard).
+
+    A kept tree keeps its nodes, so with the default capacity it is full after the first move or soon after: a full tree
+    falls under the no-room rule - it goes on refining the values of the nodes it has and expands nothing.  Give `capacity`
+    room for the moves to come; no finite capacity excludes a full tree over many moves, and PuctSearch.result().nodes
+    shows how full the trees are.  A kept root is already evaluated and is not handed out again, so root noise that the
+    evaluator adds reaches only fresh roots."""
+    _puct_komi_guard(evaluator, komi)
+    moves = int(moves)
+    if moves < 0:
+        raise ValueError('need moves >= 0 (got %d)' % moves)
+    search = PuctSearch(batch_states, iterations, c, komi, leaves=leaves, capacity=capacity)
+    box = search._box
+    played = torch.empty((search._R, moves), dtype=_I64, device=box.t.device)
+    for mv in range(moves):
+        for _ in range(search._I):
+            states, legal = search.select()
+            priors, values = evaluator(states, legal)
+            search.backup(priors, values)
+        res = search._result()
+        played[:, mv] = _best_legal(_ON_DEVICE, res.legal, res.visits.to(_I64))
+        if reuse:
+            search.advance(played[:, mv], check=False)
+        else:   # only node 0's boards are played on: the tree goes, so no advance over it; the states stay on the device
+            box.t = search._played_states(played[:, mv])
+            search = PuctSearch(box, iterations, c, komi, leaves=leaves, capacity=capacity)
+    return _back(box, played), box.back(search._root_states())
 
 
 def puct(state, iterations, evaluator, **kw):

@@ -581,6 +581,43 @@ int32_t gg_puct_backup_leaves(int64_t R, int32_t N, int32_t C, int32_t L, float 
 int32_t gg_puct_legal(const uint32_t *leaf, const int32_t *leaf_id, int64_t B, int32_t N, uint8_t *legal, uint8_t *live,
                       void *hip_stream);
 
+/*
+ * Tree reuse across moves: every root plays one action and the subtree under it becomes the tree, in place.  The tree is
+ * the one of gg_puct_* above with room for C + 1 nodes (C where I stood), on either path.  The call is only defined outside
+ * a round (after a backup, or before the first select), when every v = 0.  actions int32 [R]; next uint32 [R][W], the
+ * tracked board of each root after its action (what gg_batch_play_moves_tracked(.., T = 1) makes of node 0's board; read
+ * only where a fresh tree is made); remap int32 [R][C+1], caller-owned scratch whose contents afterwards are unspecified;
+ * kept int32 [R], may be NULL.  Per root r, with a = actions[r], m = nodes[r] clamped to [1, C + 1] and child_0 the root's
+ * child table:
+ *   a = -1                                  k = 0: the root stays (a game that has ended, a root the caller does not move)
+ *   0 <= a < A and 1 <= child_0[a] < m      k = child_0[a]
+ *   anything else                           k = -1
+ * k = 0: no byte of the tree changes (nodes[r] included); kept[r] = m.
+ * k > 0: the kept set K is k and every node whose parent chain reaches k: ascending over x in (k, m), x is kept when its
+ *   parent p satisfies k <= p < x and p is kept (parents have smaller ids, so one pass decides it).  new(x) = the number of
+ *   kept nodes below x, an order-preserving renumbering with new(k) = 0.  Node new(x) receives x's board, its prior row (as
+ *   bit patterns), n and w, and v = 0; its links become (new(parent_x), action_x), (-1, -1) at the new root; in its child
+ *   row a negative entry stays, an entry c with x < c < m becomes new(c) - a child of a kept node is kept - and any other
+ *   entry (only with corrupt buffers) -1, as does an entry whose node was not kept.  nodes[r] = kept[r] = |K|.  Every node
+ *   in [|K|, m) is put back into gg_puct_begin's state - child -1, prior +0, links -1 / -1, stats all-zero bytes - and its
+ *   board words are set to 0.
+ * k = -1: node 0 = next[r] with child -1, prior +0, links -1 / -1, stats zero; the nodes in [1, m) as above;
+ *   nodes[r] = 1, kept[r] = 0: what gg_puct_begin leaves for that root.
+ * Nodes >= m are not touched.  (gg_puct_begin does not write the boards of unused nodes: they are unspecified until an
+ * advance zeroes them, and nothing reads the board of a node >= nodes[r].)
+ * So n_x = 1 + the sum of n_c still holds in the kept tree, the new root is already evaluated (the next select scores at
+ * once; root visits start at the child's n), child ids stay larger than their parent's and below nodes[r], and root r's
+ * result depends on root r alone.  A kept tree may be full: selects then fall under the no-room rule above.
+ * Alignment: stats must start on a 16-byte boundary - a record is read and written as one 16-byte access, as by
+ * gg_puct_select_leaves / gg_puct_backup_leaves -; every other buffer needs the 4 bytes of its element type and no more
+ * (rows are moved and reset with 16-byte accesses at any word address, single words up to a boundary where it matters).
+ * The argument checks come before any device work, in the order above: GG_E_BADSIZE: N outside [2, 19], R < 0;
+ * GG_E_BADARG: C < 1 or C = 2^31 - 1; GG_E_NULLPTR: any pointer but kept is NULL.  R = 0 is no work.
+ */
+int32_t gg_puct_advance(const int32_t *actions, const uint32_t *next, int64_t R, int32_t N, int32_t C, uint32_t *boards,
+                        int32_t *child, float *prior, int32_t *links, gg_puct_stat *stats, int32_t *nodes, int32_t *remap,
+                        int32_t *kept, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

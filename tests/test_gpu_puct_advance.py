@@ -1,0 +1,358 @@
+"""-m gpu: tree reuse across moves (gogame.PuctSearch.advance / root_states / puct_play, capacity=: k_puct_advance behind
+gg_puct_advance).  After an advance the WHOLE tree buffers - boards, child tables, priors, links, stat records, node counts,
+the reset tail and the untouched nodes behind it - equal the restatement (tests/mc_puct_advance_expect.py), floats as bit
+patterns: every board size class, both search paths, the hash / hostile / pass evaluators, action vectors that mix the
+most-visited child, the least-visited child, an unvisited legal action, -1 and ended roots; -1 everywhere changes no byte; a
+fresh tree is a new PuctSearch's, buffer for buffer; several moves in a row against expected_puct_play, a full tree under the
+no-room rule among them; puct_play(reuse=False) against a loop over batch_puct; the entry point on the test's own buffers
+with sentinel words behind them; shards, a stream, NumPy input, check=True, kept = NULL."""
+import numpy as np
+import pytest
+
+import mc_expect as mc
+import mc_puct_expect as pe
+import mc_puct_advance_expect as pa
+from oracle import c_oracle
+
+pytestmark = pytest.mark.gpu
+
+MARK = 0x5A5A5A5A
+EVALUATORS = {'hash': (pe.hash_evaluator_np, pe.hash_evaluator_t), 'hostile': (pe.hostile_evaluator_np, pe.hostile_evaluator_t),
+              'pass': (pe.pass_evaluator_np, pe.pass_evaluator_t)}
+BUFFERS = ('boards', 'child', 'prior', 'links', 'stats', 'nodes')
+
+
+def _roots(N, seed):
+    return np.concatenate([mc.make_roots(N, 4, seed, max_ply=N * N // 2, step=max(2, N * N // 8))[1:], mc.crafted_roots(N)])
+
+
+def _search(roots, T, L, capacity, c=1.25, komi=0.5):
+    """A PuctSearch whose unused boards hold MARK (gg_puct_begin leaves them unspecified), and the restatement's trees."""
+    from gymgo_amd import gogame
+    s = gogame.PuctSearch(mc.to_dev(roots), T, c=c, komi=komi, leaves=L, capacity=capacity)
+    s._boards[:, 1:] = MARK
+    return s, pa.make_trees(roots, s._C + 1, L)
+
+
+def _rounds(s, trees, T, L, name, c=1.25, komi=0.5):
+    ev_np, ev_t = EVALUATORS[name]
+    for _ in range(T):
+        s.backup(*ev_t(*s.select()))
+    pa.search_rounds(trees, T, L, ev_np, c, komi)
+
+
+def _got(s):
+    return {k: mc.to_np(getattr(s, '_' + k)).copy() for k in BUFFERS}
+
+
+def _want(trees, N):
+    """The tree buffers of the restatement: used nodes from the trees (boards through the library's own track kernel), the
+    nodes an advance has reset in begin's state with zero boards, MARK on the boards nothing has written."""
+    from gymgo_amd import gogame
+    R, NN, A, W = len(trees), trees[0].n.shape[0], N * N + 1, 5 * N + 1
+    boards = np.full((R, NN, W), MARK, np.int32)
+    for r, t in enumerate(trees):
+        used = len(t.boards)
+        boards[r, :used] = mc.to_np(gogame.batch_track(mc.to_dev(np.stack(t.boards))))
+        boards[r, used:max(used, getattr(t, 'zeroed', 0))] = 0
+    stats = np.zeros((R, NN, 4), np.int32)
+    stats[..., :2] = np.stack([t.w for t in trees]).astype(np.float64).view(np.int32).reshape(R, NN, 2)
+    stats[..., 2] = np.stack([t.n for t in trees])
+    return {'boards': boards, 'child': np.stack([t.child for t in trees]).astype(np.int32),
+            'prior': np.stack([t.prior for t in trees]),
+            'links': np.stack([np.stack([t.parent, t.action], axis=1) for t in trees]).astype(np.int32), 'stats': stats,
+            'nodes': np.array([len(t.boards) for t in trees], np.int32)}
+
+
+def _equal(got, want, tag):
+    for k in BUFFERS:
+        g, w = pe.bits(got[k]), pe.bits(want[k])
+        assert g.shape == w.shape and g.dtype == w.dtype, (tag, k, g.shape, g.dtype, w.shape, w.dtype)
+        assert np.array_equal(g, w), (tag, k, np.argwhere(g != w)[:8])
+
+
+def _mixed_actions(trees):
+    """Per root, by its index: the most-visited child, the least-visited child, an unvisited legal action, -1; ended roots -1."""
+    acts, kinds, live = [], [], 0
+    for t in trees:
+        legal = t.legal[0]
+        kids = sorted((int(t.n[t.child[0, a]]), int(a)) for a in legal if t.child[0, a] >= 0)
+        free = [int(a) for a in legal if t.child[0, a] < 0]
+        kind = 'ended' if legal.size == 0 else ('most', 'least', 'unvisited', 'stay')[live % 4]
+        live += legal.size > 0
+        if kind == 'unvisited' and not free:
+            kind = 'least'
+        if kind in ('most', 'least') and not kids:
+            kind = 'stay'
+        acts.append({'ended': -1, 'stay': -1, 'most': kids[-1][1] if kids else -1, 'least': kids[0][1] if kids else -1,
+                     'unvisited': free[-1] if free else -1}[kind])
+        kinds.append(kind)
+    return np.array(acts, np.int64), kinds
+
+
+def _advance_both(s, trees, acts, **kw):
+    kept = s.advance(mc.to_dev(acts) if kw.pop('device', True) else acts, **kw)
+    want = [pa.advance(t, int(a), pa.next_root(t, int(a))) for t, a in zip(trees, acts)]
+    assert mc.to_np(kept).tolist() == want and mc.to_np(kept).dtype == np.int32
+    return want
+
+
+CASES = [(5, None, 'hash', 40), (5, 1, 'hash', 40), (5, 4, 'pass', 12), (7, 1, 'hostile', 40), (7, 8, 'hash', 8),
+         (9, None, 'hostile', 60), (9, 4, 'hash', 20), (9, 8, 'hostile', 10), (13, None, 'hash', 40), (13, 8, 'pass', 6),
+         (19, None, 'hostile', 30), (19, 1, 'pass', 12), (19, 4, 'hash', 12), (19, 8, 'hash', 6)]
+
+
+@pytest.mark.parametrize('N,L,name,T', CASES)
+def test_advance_whole_tree_buffers(N, L, name, T):
+    import torch
+    roots = _roots(N, 70 + N)
+    R, A = roots.shape[0], N * N + 1
+    c = 1e6 if name == 'pass' else 1.25
+    s, trees = _search(roots, T, L, 2 * T * (L or 1) + 7, c=c)
+    _rounds(s, trees, T, L, name, c=c)
+    _equal(_got(s), _want(trees, N), 'searched')
+    acts, kinds = _mixed_actions(trees)
+    assert {'most', 'least', 'unvisited', 'stay', 'ended'} <= set(kinds), kinds
+    kept = _advance_both(s, trees, acts)
+    assert any(k > 1 for k in kept) and 0 in kept
+    _equal(_got(s), _want(trees, N), 'advanced')
+    res = s.result(tree=True)
+    want = pa.results(trees, A)
+    want['trees'] = trees
+    pe.check(res, want, tag='result')                               # legal follows the new roots
+    assert np.array_equal(mc.to_np(s.root_states()), np.stack([t.boards[0] for t in trees]))
+    # -1 everywhere: not a byte changes
+    before = _got(s)
+    assert mc.to_np(s.advance(torch.full((R,), -1, dtype=torch.int32, device='cuda'))).tolist() == [len(t.boards) for t in trees]
+    _equal(_got(s), before, 'stay')
+    # the search goes on in the kept trees, then a second move
+    _rounds(s, trees, T, L, name, c=c)
+    _equal(_got(s), _want(trees, N), 'searched again')
+    acts, _ = _mixed_actions(trees)
+    _advance_both(s, trees, acts)
+    _equal(_got(s), _want(trees, N), 'advanced again')
+
+
+@pytest.mark.parametrize('N,L', [(5, None), (9, 4), (19, 1)])
+def test_advance_to_a_fresh_tree_is_a_new_search(N, L):
+    from gymgo_amd import gogame
+    T = 10
+    roots = np.stack([x for x in _roots(N, 5) if mc.legal_actions(x).size])[:4]   # live roots only
+    s, trees = _search(roots, T, L, 3 * T * (L or 1))
+    _rounds(s, trees, T, L, 'hash')
+    acts = np.array([[int(a) for a in t.legal[0] if t.child[0, a] < 0][0] for t in trees], np.int64)
+    assert _advance_both(s, trees, acts) == [0] * len(trees)
+    nxt = np.stack([t.boards[0] for t in trees])
+    assert np.array_equal(nxt, np.stack([c_oracle.next_state(roots[r], int(acts[r])) for r in range(len(trees))]))
+    new = gogame.PuctSearch(mc.to_dev(nxt), T, komi=0.5, leaves=L, capacity=3 * T * (L or 1))
+    a, b = _got(s), _got(new)
+    for k in BUFFERS[1:]:
+        assert np.array_equal(pe.bits(a[k]), pe.bits(b[k])), k
+    assert np.array_equal(a['boards'][:, 0], b['boards'][:, 0])      # (begin does not write the boards of unused nodes)
+    assert np.array_equal(mc.to_np(s.result().legal), mc.to_np(new.result().legal))
+    _rounds(s, trees, T, L, 'hash')
+    for _ in range(T):
+        new.backup(*pe.hash_evaluator_t(*new.select()))
+    pe.check(s.result(tree=True), dict(pa.results(trees, N * N + 1), trees=trees), tag='after')
+    for k in BUFFERS[1:]:
+        assert np.array_equal(pe.bits(_got(s)[k]), pe.bits(_got(new)[k])), k
+
+
+@pytest.mark.parametrize('N,L,name,T,M,capacity', [(5, None, 'hash', 30, 5, None), (5, 4, 'hash', 10, 4, None),
+                                                   (9, 4, 'hostile', 12, 4, 200), (7, 1, 'pass', 20, 4, 90),
+                                                   (19, None, 'hash', 12, 4, 60)])
+def test_several_moves_equal_expected_puct_play(N, L, name, T, M, capacity):
+    """Search, move, search again: every Puct / PuctTree field before every move, the actions and the final states.  With
+    capacity=None the kept trees are full from the second move on: the no-room rule after an advance."""
+    from gymgo_amd import gogame
+    ev_np, ev_t = EVALUATORS[name]
+    c = 0.6 if N == 5 else 1.25
+    roots = _roots(N, 31)
+    sizes = []
+    acts, final, per_move, trees = pa.expected_puct_play(roots, M, T, ev_np, c=c, komi=0.5, leaves=L, capacity=capacity,
+                                                         on_move=lambda mv, ts, a, k: sizes.append([len(t.boards) for t in ts]))
+    NN = T * (L or 1) + 1 if capacity is None else capacity
+    if capacity is None:
+        assert any((per_move[mv]['nodes'] == NN).any() and (per_move[mv - 1]['nodes'] == NN).any() for mv in range(1, M))
+    s = gogame.PuctSearch(mc.to_dev(roots), T, c=c, komi=0.5, leaves=L, capacity=capacity)
+    for mv in range(M):
+        for _ in range(T):
+            s.backup(*ev_t(*s.select()))
+        got = s.result(tree=True)
+        assert got.tree.parent.shape == (roots.shape[0], NN)
+        pe.check(got, dict(per_move[mv], trees=None), tag=mv)
+        move = gogame._best_legal(gogame._ON_DEVICE, got.legal, got.visits.long())
+        assert np.array_equal(mc.to_np(move), acts[:, mv]), mv
+        s.advance(move)
+        assert mc.to_np(s.result().nodes).tolist() == sizes[mv]
+    assert np.array_equal(mc.to_np(s.root_states()), final)
+    a2, f2 = gogame.puct_play(mc.to_dev(roots), M, T, ev_t, c=c, komi=0.5, leaves=L, capacity=capacity)
+    assert a2.is_cuda and a2.dtype.is_floating_point is False and tuple(a2.shape) == (roots.shape[0], M)
+    assert np.array_equal(mc.to_np(a2), acts) and np.array_equal(mc.to_np(f2), final)
+
+
+def test_puct_play_without_reuse_is_a_loop_over_batch_puct():
+    from gymgo_amd import gogame
+    N, T, M, L = 9, 16, 4, 2
+    roots = _roots(N, 12)
+    states, want = roots.copy(), np.zeros((roots.shape[0], M), np.int64)
+    for mv in range(M):
+        res = gogame.batch_puct(states, T, pe.hash_evaluator_t, komi=0.5, leaves=L)
+        want[:, mv] = pe.most_visited(res)
+        states = np.stack([s if a < 0 else c_oracle.next_state(s, int(a)) for s, a in zip(states, want[:, mv])])
+    acts, final = gogame.puct_play(roots, M, T, pe.hash_evaluator_t, komi=0.5, leaves=L, reuse=False)
+    assert isinstance(acts, np.ndarray) and acts.dtype == np.int64 and final.dtype == roots.dtype
+    assert np.array_equal(acts, want) and np.array_equal(final, states)
+    e_acts, e_final, _, _ = pa.expected_puct_play(roots, M, T, pe.hash_evaluator_np, komi=0.5, leaves=L, reuse=False)
+    assert np.array_equal(acts, e_acts) and np.array_equal(final, e_final)
+    kept, _ = gogame.puct_play(roots, M, T, pe.hash_evaluator_t, komi=0.5, leaves=L, capacity=4 * T * L, reuse=True)
+    e_kept, _, _, _ = pa.expected_puct_play(roots, M, T, pe.hash_evaluator_np, komi=0.5, leaves=L, capacity=4 * T * L)
+    assert np.array_equal(kept, e_kept)
+    ev = gogame.playout_evaluator(4, komi=0.5, slots=64)
+    with pytest.raises(ValueError):
+        gogame.puct_play(roots, 1, 2, ev, komi=7.5)
+
+
+def test_entry_point_on_own_buffers_shards_stream_numpy_and_check():
+    """gg_puct_advance called directly on copies of a searched tree, each buffer followed by sentinel words: nothing is
+    written beyond them, with kept and with kept = NULL; the halves of the batch advance to the halves of the whole; a
+    non-default stream; NumPy actions; check=True names the first root with an illegal action and changes nothing."""
+    import torch
+    from gymgo_amd import gogame, _lib
+    N, T, L, TAIL = 9, 12, 4, 4096
+    A, W = N * N + 1, 5 * N + 1
+    roots = _roots(N, 44)
+    R = roots.shape[0]
+    s, trees = _search(roots, T, L, 2 * T * L + 3)
+    _rounds(s, trees, T, L, 'hash')
+    NN = s._C + 1
+    acts, _ = _mixed_actions(trees)
+    dev = torch.device('cuda', torch.cuda.current_device())
+    lib, stream = _lib.lib(), _lib.current_raw_stream(dev)
+
+    def copies(rows):
+        flats, views = {}, {}
+        for k in BUFFERS:
+            src = getattr(s, '_' + k)[rows].contiguous()
+            words = src.numel() * src.element_size() // 4
+            flats[k] = torch.full((words + TAIL,), MARK, dtype=torch.int32, device=dev)
+            flats[k][:words] = src.view(torch.int32).reshape(-1)
+            views[k] = flats[k][:words]
+        n = len(range(R)[rows])
+        for k, words in (('next', n * W), ('remap', n * NN), ('kept', n), ('actions', n)):
+            flats[k] = torch.full((words + TAIL,), MARK, dtype=torch.int32, device=dev)
+            views[k] = flats[k][:words]
+        views['actions'][:] = mc.to_dev(acts[rows]).to(torch.int32)
+        nxt = s._boards[rows, 0, :].contiguous()
+        assert lib.gg_batch_play_moves_tracked(nxt.data_ptr(), views['actions'].data_ptr(), None, n, N, 1, stream) == 0
+        views['next'][:] = nxt.reshape(-1)
+        return flats, views, n
+
+    def call(views, n, kept=True):
+        p = {k: v.data_ptr() for k, v in views.items()}
+        return lib.gg_puct_advance(p['actions'], p['next'], n, N, s._C, *[p[k] for k in BUFFERS], p['remap'],
+                                   p['kept'] if kept else None, stream)
+
+    whole = {}
+    for rows, kept in ((slice(None), True), (slice(None), False), (slice(0, 3), True), (slice(3, None), True)):
+        flats, views, n = copies(rows)
+        assert call(views, n, kept) == 0
+        for k, flat in flats.items():
+            assert bool((flat[-TAIL:] == MARK).all()), (rows, k)       # nothing beyond the buffers
+        if not kept:
+            assert bool((views['kept'] == MARK).all())
+        whole[(rows.start, rows.stop, kept)] = {k: views[k].clone() for k in BUFFERS + ('kept',)}
+    full, null = whole[(None, None, True)], whole[(None, None, False)]
+    for k in BUFFERS:
+        assert torch.equal(full[k], null[k]), k
+        assert torch.equal(full[k], torch.cat([whole[(0, 3, True)][k], whole[(3, None, True)][k]])), k   # shards by root
+    assert torch.equal(full['kept'], torch.cat([whole[(0, 3, True)]['kept'], whole[(3, None, True)]['kept']]))
+    # check=True: an illegal action (an occupied point) raises, names the first such root and leaves the tree alone
+    before = _got(s)
+    bad = acts.copy()
+    live = [r for r, t in enumerate(trees) if t.legal[0].size and t.legal[0].size < A]
+    illegal = [int(np.setdiff1d(np.arange(A), trees[r].legal[0])[0]) for r in live]
+    bad[live[-1]], bad[live[0]] = illegal[-1], illegal[0]
+    with pytest.raises(ValueError, match='root %d' % live[0]):
+        s.advance(bad)
+    with pytest.raises(ValueError):
+        s.advance(np.where(acts < 0, A + 5, acts))
+    _equal(_got(s), before, 'refused')
+    # NumPy actions on a non-default stream: the search's own buffers equal the direct call's and the restatement
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        kept = _advance_both(s, trees, acts, device=False)
+    side.synchronize()
+    assert mc.to_np(full['kept']).tolist() == kept
+    got = _got(s)
+    _equal(got, _want(trees, N), 'stream')
+    for k in BUFFERS:
+        assert np.array_equal(got[k].reshape(-1).view(np.int32), mc.to_np(full[k])), k
+
+
+@pytest.mark.parametrize('L', [None, 4])
+def test_unchecked_actions_outside_the_range_give_a_fresh_tree(L):
+    """check=False: whatever lies outside [-1, A) - below -1 too, which must not be taken for the -1 that leaves a root
+    alone - is an illegal action: k = -1, the fresh tree on what gg_batch_play_moves_tracked makes of the root and A.  Two
+    equal searches, one advanced with such values, one with A in their place: every buffer equal, nodes = 1 and kept = 0
+    at those roots, and their rows in gg_puct_begin's state.  The default of advance(iterations=) is the constructor's."""
+    import torch
+    N, T = 9, 10
+    A = N * N + 1
+    roots = _roots(N, 9)
+    R = roots.shape[0]
+    pair = []
+    for _ in range(2):
+        s, trees = _search(roots, T, L, 2 * T * (L or 1))
+        for _ in range(T):
+            s.backup(*pe.hash_evaluator_t(*s.select()))
+        pair.append(s)
+    pa.search_rounds(trees, T, L, pe.hash_evaluator_np, 1.25, 0.5)
+    acts, _ = _mixed_actions(trees)
+    odd = [-5, A + 5, 2 ** 40, -2 ** 40]
+    rows = list(range(R))[:len(odd)]
+    assert len(rows) == len(odd) < R and any(len(trees[r].boards) > 1 for r in rows)
+    wild, plain = acts.copy(), acts.copy()
+    wild[rows], plain[rows] = odd, A
+    kept_w = mc.to_np(pair[0].advance(mc.to_dev(wild), iterations=3, check=False)).copy()
+    kept_p = mc.to_np(pair[1].advance(mc.to_dev(plain), check=False)).copy()
+    assert np.array_equal(kept_w, kept_p) and not kept_w[rows].any()
+    a, b = _got(pair[0]), _got(pair[1])
+    _equal(a, b, 'outside the range')
+    assert (a['nodes'][rows] == 1).all()
+    m = [len(trees[r].boards) for r in rows]
+    for r, used in zip(rows, m):
+        assert (a['child'][r, :used] == -1).all() and not pe.bits(a['prior'][r, :used]).any()
+        assert (a['links'][r, :used] == -1).all() and not a['stats'][r, :used].any() and not a['boards'][r, 1:used].any()
+    others = [r for r in range(R) if r not in rows]
+    want = [pa.advance(trees[r], int(acts[r]), pa.next_root(trees[r], int(acts[r]))) for r in others]
+    assert kept_w[others].tolist() == want
+    got, exp = _got(pair[0]), _want(trees, N)
+    for k in BUFFERS:
+        assert np.array_equal(pe.bits(got[k][others]), pe.bits(exp[k][others])), k
+    s = pair[0]
+    for _ in range(3):
+        s.backup(*pe.hash_evaluator_t(*s.select()))
+    with pytest.raises(ValueError):
+        s.select()
+    s.advance(torch.full((R,), -1, dtype=torch.int64, device='cuda'))
+    assert s.iterations_done == 0
+    for _ in range(T):                                              # as constructed, not the 3 of the advance before
+        s.backup(*pe.hash_evaluator_t(*s.select()))
+    with pytest.raises(ValueError):
+        s.select()
+
+
+def test_capacity_none_is_the_search_as_it_was():
+    from gymgo_amd import gogame
+    N, T = 9, 24
+    roots = _roots(N, 3)
+    want = pe.expected_puct(roots, T, pe.hash_evaluator_np, komi=0.5)
+    pe.check(gogame.batch_puct(mc.to_dev(roots), T, pe.hash_evaluator_t, komi=0.5, tree=True), want)
+    got = gogame.batch_puct(mc.to_dev(roots), T, pe.hash_evaluator_t, komi=0.5, tree=True, capacity=T + 30)
+    assert got.tree.parent.shape == (roots.shape[0], T + 30)
+    for k in pe.ROOT_KEYS:
+        assert np.array_equal(pe.bits(getattr(got, k)), pe.bits(want[k])), k
+    for k in pe.TREE_KEYS:
+        assert np.array_equal(pe.bits(mc.to_np(getattr(got.tree, k))[:, :T + 1]), pe.bits(want['tree'][k])), k

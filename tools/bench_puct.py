@@ -22,6 +22,14 @@ Workload: R mid-game roots (random play from the empty board, `--plies` plies), 
              leaves=None over that of leaves=L.
   playouts:  plies/s of the search with playout_evaluator(K) for leaves=L against leaves=None at the same R, and against
              leaves=None at `--ref-roots` (the batch size the drain argument compares with), all alternating in one process.
+
+  --moves M [--reuse | --no-reuse] [--capacity-factor F]: M moves in a row (search `--iters` rounds, play the most-visited
+  child, PuctSearch.advance), the tree with room for F * (the default) nodes.  Per move: wall ms of the search, of advance()
+  and of constructing a fresh PuctSearch of the same capacity on R roots (what a caller did before advance existed;
+  alternating with advance, median of `--reps`), the mean share of nodes and of root visits that advance kept, and the mean
+  root visits after the move's search.  --no-reuse starts every move from a new PuctSearch (the same rounds per move).
+  --evaluator peaked: fixed preallocated priors that fall geometrically with the action index (ratio 1/2), values 0.
+  For the kernel's device time: `rocprofv3 --kernel-trace --stats -- python tools/bench_puct.py --moves M --reps 1 ...`.
 """
 import argparse
 import json
@@ -31,7 +39,7 @@ from mc_bench import median_timed, mid_game_roots, timed   # (puts the repositor
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--evaluator', choices=['null', 'playouts'], default='null')
+    ap.add_argument('--evaluator', choices=['null', 'playouts', 'peaked'], default='null')
     ap.add_argument('--roots', type=int, nargs='+', default=None)
     ap.add_argument('--iters', type=int, nargs='+', default=None)
     ap.add_argument('--k', type=int, default=256)
@@ -41,7 +49,13 @@ def main():
     ap.add_argument('--c', type=float, default=1.25)
     ap.add_argument('--leaves', type=int, nargs='+', default=None)
     ap.add_argument('--ref-roots', type=int, default=1024)
+    ap.add_argument('--moves', type=int, default=None)
+    ap.add_argument('--reuse', dest='reuse', action='store_true', default=True)
+    ap.add_argument('--no-reuse', dest='reuse', action='store_false')
+    ap.add_argument('--capacity-factor', type=int, default=2)
     args = ap.parse_args()
+    if args.evaluator == 'peaked' and args.moves is None:
+        ap.error('--evaluator peaked needs --moves')
 
     import torch
     from gymgo_amd import gogame, _lib
@@ -53,6 +67,11 @@ def main():
         for I in args.iters or ([64, 800] if null else [64]):
             base = {'size': N, 'roots': R, 'iterations': I, 'root_plies': args.plies, 'c': args.c,
                     'cus': int(_lib.lib().gg_device_cus()), 'reps': args.reps}
+            if args.moves is not None:
+                for L in args.leaves or [None]:
+                    for res in _moves(args, gogame, torch, roots, base, L):
+                        print(json.dumps(res), flush=True)
+                continue
             if args.leaves:
                 for res in _leaves(args, gogame, torch, roots, base, null):
                     print(json.dumps(res), flush=True)
@@ -146,6 +165,59 @@ def _leaves(args, gogame, torch, roots, base, null):
                    ratio_to_ref_roots=rate[key] / rate['ref'], ref_roots=args.ref_roots,
                    leaves_evaluated_per_root=done, live_slots_per_round=done / rounds,
                    jobs_per_slot=rr * (L or 1) * K / (256 * base['cus']))
+
+
+def _moves(args, gogame, torch, roots, base, L):
+    """The --moves loop: one result per move."""
+    R, N, I, K = base['roots'], base['size'], base['iterations'], args.k
+    A, B = N * N + 1, R * (L or 1)
+    T = I // (L or 1)
+    capacity = args.capacity_factor * T * (L or 1) + 1
+    if args.evaluator == 'playouts':
+        ev = gogame.playout_evaluator(K, seed=1, komi=7.5)
+    else:
+        row = torch.full((A,), 1.0 / A) if args.evaluator == 'null' else 0.5 ** torch.arange(1, A + 1, dtype=torch.float64)
+        priors = row.to(torch.float32).to('cuda:0')[None, :].expand(B, A).contiguous()
+        values = torch.zeros(B, dtype=torch.float32, device='cuda:0')
+        ev = lambda states, legal: (priors, values)
+
+    def rounds(search):
+        for _ in range(T):
+            search.backup(*ev(*search.select()))
+
+    search = gogame.PuctSearch(roots, T, c=args.c, komi=7.5, leaves=L, capacity=capacity)
+    for mv in range(args.moves):
+        s_search, _ = timed(lambda: rounds(search))
+        res = search._result()
+        visits_before, nodes_before = res.root_visits.double().clone(), res.nodes.double().clone()
+        acts = gogame._best_legal(gogame._ON_DEVICE, res.legal, res.visits.long())
+        best = res.visits.gather(1, acts.clamp(min=0)[:, None])[:, 0].double()
+        # advance on copies of the tree (alternating with the construction of a fresh search), then once for real
+        names = ('_boards', '_child', '_prior', '_links', '_stats', '_nodes')
+        saved = [getattr(search, n).clone() for n in names]
+
+        def advance():
+            for n, t in zip(names, saved):
+                getattr(search, n).copy_(t)
+            torch.cuda.synchronize()
+            return timed(lambda: search.advance(acts, check=False))[0]
+
+        nxt = search.root_states()   # (a fresh search costs the same on any R boards)
+        fresh = lambda: timed(lambda: gogame.PuctSearch(nxt, T, c=args.c, komi=7.5, leaves=L, capacity=capacity))[0]
+        adv, new = [], []
+        for _ in range(args.reps):
+            adv.append(advance())
+            new.append(fresh())
+        med = lambda ts: sorted(ts)[len(ts) // 2]
+        kept = search._kept.double()
+        if not args.reuse:
+            search = gogame.PuctSearch(search.root_states(), T, c=args.c, komi=7.5, leaves=L, capacity=capacity)
+        yield dict(base, metric='puct_advance_per_move', evaluator=args.evaluator, leaves=L, rounds=T, move=mv, reuse=args.reuse,
+                   capacity=capacity, search_ms=s_search * 1e3, advance_ms=med(adv) * 1e3, fresh_search_ms=med(new) * 1e3,
+                   ratio_fresh_over_advance=med(new) / med(adv), root_visits_after_search=float(visits_before.mean()),
+                   nodes_before=float(nodes_before.mean()), kept_nodes=float(kept.mean()),
+                   share_nodes_kept=float((kept / nodes_before).mean()), share_visits_kept=float((best / visits_before).mean()),
+                   kept_visits=float(best.mean()), tree_full=float((nodes_before >= capacity).double().mean()))
 
 
 def _mean_leaf_depth(parent, nodes):
