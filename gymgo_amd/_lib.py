@@ -25,7 +25,7 @@ EXPORTS = (
     'gg_move_playouts_plan', 'gg_move_playouts_begin', 'gg_move_playouts_advance', 'gg_uct_begin', 'gg_uct_select',
     'gg_uct_backup', 'gg_batch_eye_mask', 'gg_batch_rollout_tracked_policy', 'gg_playouts_advance_policy',
     'gg_move_playouts_advance_policy', 'gg_puct_begin', 'gg_puct_select', 'gg_puct_backup',
-    'gg_puct_select_leaves', 'gg_puct_backup_leaves', 'gg_puct_legal', 'gg_puct_advance',
+    'gg_puct_select_leaves', 'gg_puct_backup_leaves', 'gg_puct_legal', 'gg_puct_advance', 'gg_batch_rollout_ws',
 )
 
 _vp, _i64, _i32, _u64 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_uint64
@@ -40,6 +40,7 @@ _SIGNATURES = {
     'gg_batch_children_offsets': ([_vp, _vp, _vp, _i64, _i32, _vp], _i32),
     'gg_batch_children_compact': ([_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp], _i32),
     'gg_batch_rollout': ([_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp], _i32),
+    'gg_batch_rollout_ws': ([_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp], _i32),
     'gg_batch_env_step': ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, ctypes.c_float, _i32, _i32, _vp], _i32),
     'gg_batch_env_step_scored': ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, ctypes.c_float, _i32, _i32, _vp], _i32),
     'gg_batch_sample_actions': ([_vp, _vp, _vp, _i64, _i32, _vp], _i32),

@@ -41,7 +41,7 @@ namespace gg {
 void launch_rollout4(int io, uint8_t *st, uint64_t *rng, int32_t *last_actions, int64_t *steps_done, int64_t B, int32_t N,
                      uint32_t inv, int plies, int auto_reset, int nb, int grid, hipStream_t s);
 void launch_rollout5(int io, int N, uint8_t *st, uint64_t *rng, int32_t *last_actions, int64_t *steps_done, int64_t B, uint32_t inv,
-                     int plies, int auto_reset, int nb, int grid, hipStream_t s);
+                     int plies, int auto_reset, int nb, int grid, hipStream_t s, uint32_t *ws);
 void launch_rollout_lat(int io, uint8_t *st, uint64_t *rng, int32_t *last_actions, int64_t *steps_done, int64_t B, int32_t N, int plies,
                         int auto_reset, bool w4, hipStream_t s);
 void launch_env_step_lat(uint32_t *tracked, uint64_t *rng, int64_t *steps_done, int64_t B, int32_t N, int auto_reset,
@@ -750,10 +750,13 @@ int32_t gg_batch_children_compact(const uint8_t *states, const int32_t *offsets,
   return (int32_t)hipGetLastError();
 }
 
-int32_t gg_batch_rollout(uint8_t *states, uint64_t *rng, int32_t *last_actions, int64_t *steps_done, int64_t B,
-                         int32_t N, int32_t plies, int32_t auto_reset, void *hip_stream) {
+// gg_batch_rollout (workspace == nullptr, use_ws false) and gg_batch_rollout_ws: one dispatch; the workspace goes to the
+// byte-plane load of k_rollout5 and to no other kernel
+static int32_t batch_rollout(uint8_t *states, uint64_t *rng, int32_t *last_actions, int64_t *steps_done, uint32_t *workspace,
+                             bool use_ws, int64_t B, int32_t N, int32_t plies, int32_t auto_reset, void *hip_stream) {
   if (plies < 0) return GG_E_BADARG;
   GG_ENTER(states);
+  if (use_ws && !workspace) return GG_E_NULLPTR;
   if (plies == 0) return 0;
   if (!rng) return GG_E_NULLPTR;
   if (use_lat(cus, B, N, plies)) {   // an under-filled machine: one row per lane, the ply in registers (gg_lat.h, launched from gg_rollout.hip)
@@ -763,7 +766,7 @@ int32_t gg_batch_rollout(uint8_t *states, uint64_t *rng, int32_t *last_actions, 
   if (use_rollout5(cus, B, N, plies)) {   // a full machine: 32 boards per wave, the floods of a ply as a job list (gg_v5.h)
     int grid;
     const int nb = boards_per_wave5(cus, B, grid);
-    launch_rollout5(0, N, states, rng, last_actions, steps_done, B, inv, plies, auto_reset, nb, grid, s);
+    launch_rollout5(0, N, states, rng, last_actions, steps_done, B, inv, plies, auto_reset, nb, grid, s, workspace);
     return (int32_t)hipGetLastError();
   }
   if (use_multi_ply(cus, B, plies)) {   // liberty classes carried across the plies, 16 boards per wave
@@ -811,6 +814,16 @@ int32_t gg_batch_rollout(uint8_t *states, uint64_t *rng, int32_t *last_actions, 
 #undef GG_K
   }
   return (int32_t)hipGetLastError();
+}
+
+int32_t gg_batch_rollout(uint8_t *states, uint64_t *rng, int32_t *last_actions, int64_t *steps_done, int64_t B,
+                         int32_t N, int32_t plies, int32_t auto_reset, void *hip_stream) {
+  return batch_rollout(states, rng, last_actions, steps_done, nullptr, false, B, N, plies, auto_reset, hip_stream);
+}
+
+int32_t gg_batch_rollout_ws(uint8_t *states, uint64_t *rng, int32_t *last_actions, int64_t *steps_done, uint32_t *workspace,
+                            int64_t B, int32_t N, int32_t plies, int32_t auto_reset, void *hip_stream) {
+  return batch_rollout(states, rng, last_actions, steps_done, workspace, true, B, N, plies, auto_reset, hip_stream);
 }
 
 int32_t gg_batch_env_step(uint8_t *states, const int32_t *actions, uint64_t *rng, float *rewards, uint8_t *dones,
@@ -1109,7 +1122,7 @@ int32_t gg_batch_rollout_tracked(uint32_t *tracked, uint64_t *rng, int32_t *last
   if (use_rollout5(cus, B, N, plies)) {
     int grid5;
     const int nb5 = boards_per_wave5(cus, B, grid5);
-    launch_rollout5(2, N, st, rng, last_actions, steps_done, B, inv, plies, auto_reset, nb5, grid5, s);
+    launch_rollout5(2, N, st, rng, last_actions, steps_done, B, inv, plies, auto_reset, nb5, grid5, s, nullptr);
     return (int32_t)hipGetLastError();
   }
   int grid3;

@@ -15,12 +15,13 @@
 namespace gg {
 
 // full-size 19x19 boards, byte planes (io 0) or tracked boards (io 2)
+// ws (byte planes only, nullable): the caller's workspace of gg_batch_rollout_ws, uint32 [B][5 N + 1]
 void launch_rollout5(int io, int N, uint8_t *st, uint64_t *rng, int32_t *last_actions, int64_t *steps_done, int64_t B, uint32_t inv,
-                     int plies, int auto_reset, int nb, int grid, hipStream_t s) {
-#define GG_R5(R)                                                                                                              \
-  do {                                                                                                                        \
-    if (io == 0) k_rollout5<R, 0><<<grid, kWave, 0, s>>>(st, rng, last_actions, steps_done, B, inv, plies, auto_reset, nb);   \
-    else k_rollout5<R, 2><<<grid, kWave, 0, s>>>(st, rng, last_actions, steps_done, B, inv, plies, auto_reset, nb);           \
+                     int plies, int auto_reset, int nb, int grid, hipStream_t s, uint32_t *ws) {
+#define GG_R5(R)                                                                                                                  \
+  do {                                                                                                                            \
+    if (io == 0) k_rollout5<R, 0><<<grid, kWave, 0, s>>>(st, rng, last_actions, steps_done, B, inv, plies, auto_reset, nb, ws);   \
+    else k_rollout5<R, 2><<<grid, kWave, 0, s>>>(st, rng, last_actions, steps_done, B, inv, plies, auto_reset, nb, nullptr);      \
   } while (0)
   if (N == 19) GG_R5(19);
   else if (N == 13) GG_R5(13);
@@ -31,9 +32,9 @@ void launch_rollout5(int io, int N, uint8_t *st, uint64_t *rng, int32_t *last_ac
 // gg_batch_rollout_tracked_policy (policy != uniform) on a full machine: tracked boards, the policy in the draw of phase 1
 void launch_rollout5_policy(int N, uint8_t *st, uint64_t *rng, int32_t *last_actions, int64_t *steps_done, int64_t B, uint32_t inv,
                             int plies, int auto_reset, int nb, int grid, hipStream_t s) {
-  if (N == 19) k_rollout5_pol<19, 2><<<grid, kWave, 0, s>>>(st, rng, last_actions, steps_done, B, inv, plies, auto_reset, nb);
-  else if (N == 13) k_rollout5_pol<13, 2><<<grid, kWave, 0, s>>>(st, rng, last_actions, steps_done, B, inv, plies, auto_reset, nb);
-  else k_rollout5_pol<9, 2><<<grid, kWave, 0, s>>>(st, rng, last_actions, steps_done, B, inv, plies, auto_reset, nb);
+  if (N == 19) k_rollout5_pol<19, 2><<<grid, kWave, 0, s>>>(st, rng, last_actions, steps_done, B, inv, plies, auto_reset, nb, nullptr);
+  else if (N == 13) k_rollout5_pol<13, 2><<<grid, kWave, 0, s>>>(st, rng, last_actions, steps_done, B, inv, plies, auto_reset, nb, nullptr);
+  else k_rollout5_pol<9, 2><<<grid, kWave, 0, s>>>(st, rng, last_actions, steps_done, B, inv, plies, auto_reset, nb, nullptr);
 }
 
 }  // namespace gg
@@ -60,6 +61,26 @@ extern "C" int32_t gg_ab_p3_read_r5(unsigned long long *out10) {
   if (hipMemcpyFromSymbol(out10, HIP_SYMBOL(gg::gg_p3), 80) != hipSuccess) return 2;
   unsigned long long z[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   return hipMemcpyToSymbol(HIP_SYMBOL(gg::gg_p3), z, 80) == hipSuccess ? 0 : 3;
+}
+#endif
+
+#ifdef GG_AB_WS
+// A/B builds only: read and clear the workspace counters of k_rollout5's byte-plane load (gg_v5.h: gg_wsc; pairs skipped, pairs analysed)
+extern "C" int32_t gg_ab_ws_read_r5(unsigned long long *out2) {
+  if (hipDeviceSynchronize() != hipSuccess) return 1;
+  if (hipMemcpyFromSymbol(out2, HIP_SYMBOL(gg::gg_wsc), 16) != hipSuccess) return 2;
+  unsigned long long z[2] = {0, 0};
+  return hipMemcpyToSymbol(HIP_SYMBOL(gg::gg_wsc), z, 16) == hipSuccess ? 0 : 3;
+}
+#endif
+
+#ifdef GG_AB_LOADSPLIT
+// A/B builds only: read and clear the clocks of the parts of k_rollout5's byte-plane load (gg_v5.h: gg_lsplit)
+extern "C" int32_t gg_ab_load_split_read_r5(unsigned long long *out4) {
+  if (hipDeviceSynchronize() != hipSuccess) return 1;
+  if (hipMemcpyFromSymbol(out4, HIP_SYMBOL(gg::gg_lsplit), 32) != hipSuccess) return 2;
+  unsigned long long z[4] = {0, 0, 0, 0};
+  return hipMemcpyToSymbol(HIP_SYMBOL(gg::gg_lsplit), z, 32) == hipSuccess ? 0 : 3;
 }
 #endif
 

@@ -221,6 +221,39 @@ static __device__ unsigned long long gg_p3[10];
 static __device__ unsigned long long gg_live_bad;
 #endif
 
+#ifdef GG_AB_WS
+// A/B builds only (make ab EXTRA=-DGG_AB_WS, tools/exp/r5_ws_counts.py): the pairs of boards of workspace launches whose analysis
+// the load skipped ([0]: both boards stand in the workspace stone for stone) and the pairs it analysed ([1]), counted in registers
+// (the branch is wave-uniform) and added up once per group of boards
+static __device__ unsigned long long gg_wsc[2];
+#define GG_WSC_DECL uint32_t wsc_[2] = {0u, 0u}
+#define GG_WSC(hit) (wsc_[(hit) ? 0 : 1] += 1u)
+#define GG_WSC_FLUSH do { if (ws && ln0 == 0) { atomicAdd(&gg_wsc[0], (unsigned long long)wsc_[0]); \
+    atomicAdd(&gg_wsc[1], (unsigned long long)wsc_[1]); } } while (0)
+#else
+#define GG_WSC_DECL do {} while (0)
+#define GG_WSC(hit) ((void)0)
+#define GG_WSC_FLUSH do {} while (0)
+#endif
+#ifdef GG_AB_LOADSPLIT
+// A/B builds only (make ab EXTRA=-DGG_AB_LOADSPLIT, tools/exp/r5_load_split.py): shader-clock time of the parts of the byte-plane
+// load of k_rollout5, summed over the pairs of a wave: [0] staging + bytes -> rows, [1] the analysis (or the workspace compare),
+// [2] the hand-over of the mask and M rows to the lanes that own the boards, [3] groups of boards.  LDS waits only: the next
+// pair's global loads stay in flight across the marks, as in the shipped kernel.
+static __device__ unsigned long long gg_lsplit[4];
+#define GG_LS_DECL unsigned long long tls_[3] = {0, 0, 0}, tlc_ = clock64()
+#define GG_LS(k) do { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_sched_barrier(0); \
+    const unsigned long long n_ = clock64(); __builtin_amdgcn_sched_barrier(0); tls_[k] += n_ - tlc_; tlc_ = n_; } while (0)
+#define GG_LS_START do { __builtin_amdgcn_sched_barrier(0); tlc_ = clock64(); __builtin_amdgcn_sched_barrier(0); } while (0)
+#define GG_LS_FLUSH do { if (ln0 == 0) { for (int k_ = 0; k_ < 3; ++k_) atomicAdd(&gg_lsplit[k_], tls_[k_]); \
+    atomicAdd(&gg_lsplit[3], 1ull); } } while (0)
+#else
+#define GG_LS_DECL do {} while (0)
+#define GG_LS(k) do {} while (0)
+#define GG_LS_START do {} while (0)
+#define GG_LS_FLUSH do {} while (0)
+#endif
+
 // job descriptor: bits 0-4 board, 5-13 the seed (flat point index), 15 the colour flooded, 16 the job floods G, 18 the job exists,
 // 19-20 the direction of q's neighbour it starts from (0 up, 1 down, 2 left, 3 right)
 // info word of a board (cleared in phase 1, ORed by its jobs): bits 0-3 the directions whose opponent group was captured, 4-5 the

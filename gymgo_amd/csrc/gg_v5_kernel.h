@@ -2,10 +2,15 @@
 // GG_R5_POL = the policy of its draw (kPolUniform: k_rollout5; kPolNoEyeFill: k_rollout5_pol).  Textual inclusion
 // and not a shared inline body: k_rollout5 stays the kernel it was, instruction for instruction and by name (bench.py ties
 // its PMC record to the machine code behind the mangled name).  No include guard.
+// ws (byte planes only, nullable: gg_batch_rollout_ws): the caller's workspace, uint32 [B][5 N + 1] in the layout of a tracked board.
+// The load takes M of a board from there when its stones equal the workspace's rows EXACTLY (checked per pair of boards) and skips
+// the from-scratch analysis; the store leaves the stones and M of every board it wrote, or analysed, behind.  Words 0 .. 2 N (the
+// stones) and 3 N .. 5 N (M & black, M & white) of a board are used; the others are never touched.
 template <int R, int IO>
 __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ states, uint64_t *__restrict__ rng,
                                                        int32_t *__restrict__ last_actions, int64_t *__restrict__ steps_done,
-                                                       int64_t B, uint32_t inv, int plies, int auto_reset, int nb) {
+                                                       int64_t B, uint32_t inv, int plies, int auto_reset, int nb,
+                                                       uint32_t *__restrict__ ws) {
   constexpr int POL = GG_R5_POL;
   static_assert(IO == 0 || IO == 2, "byte planes or tracked boards");
   constexpr int N = R;
@@ -44,6 +49,9 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
     uint32_t inv_r[RPL], M[RPL];
 #pragma unroll
     for (int r = 0; r < RPL; ++r) inv_r[r] = M[r] = 0u;
+    uint32_t wsmiss = 0;   // (workspace launches) bit s: board s was analysed from scratch at load - its workspace entry is rewritten
+    GG_WSC_DECL;
+    GG_LS_DECL;
     GG_PROF_DECL;
     // ---------------------------------------------------------------- load
     WAVE_SYNC();
@@ -118,6 +126,17 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
       }
       uint4 cv0 = make_uint4(0, 0, 0, 0), cv1 = cv0, cv2 = cv0, nv0 = cv0, nv1 = cv0, nv2 = cv0;
       uint32_t cfb = 0, nfb = 0;
+      // the workspace rows of the lane's board (row lanes): black, white, M & black, M & white - fetched with the pair's bytes
+      uint32_t cw0 = 0, cw1 = 0, cw2 = 0, cw3 = 0, nw0 = 0, nw1 = 0, nw2 = 0, nw3 = 0;
+#define GG_ISSUE_WS5(I, A0, A1, A2, A3)                                                                                \
+      do {                                                                                                             \
+        const int s_ = 2 * (I) + hf.h;                                                                                 \
+        const int64_t b_ = (b_first + s_ < B) ? b_first + s_ : B - 1;                                                  \
+        if (hf.hl < N) {                                                                                               \
+          const uint32_t *wp_ = ws + b_ * (int64_t)W + hf.hl;                                                          \
+          A0 = wp_[0]; A1 = wp_[N]; A2 = wp_[3 * N]; A3 = wp_[4 * N];                                                  \
+        }                                                                                                              \
+      } while (0)
 #define GG_ISSUE_PAIR5(I, V0, V1, V2, FB)                                                                              \
       do {                                                                                                             \
         const int s_ = 2 * (I) + hf.h;                                                                                 \
@@ -136,9 +155,11 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
         if (NVL > 2 && hf.hl + 64 < nv_) V2 = ga_[hf.hl + 64];                                                         \
       } while (0)
       if (nb >= 2) GG_ISSUE_PAIR5(0, cv0, cv1, cv2, cfb);
+      if (ws && nb >= 2) GG_ISSUE_WS5(0, cw0, cw1, cw2, cw3);
 #pragma unroll 1
       for (int i = 0; i < nb / 2; ++i) {
         if (i + 1 < nb / 2) GG_ISSUE_PAIR5(i + 1, nv0, nv1, nv2, nfb);
+        if (ws && i + 1 < nb / 2) GG_ISSUE_WS5(i + 1, nw0, nw1, nw2, nw3);
         const int s = 2 * i + hf.h;
         const bool on = b_first + s < B;
         const int64_t b = on ? b_first + s : B - 1;
@@ -147,6 +168,7 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
         uint8_t *io = reinterpret_cast<uint8_t *>(v2) + hf.h * Cfg<R>::kIoBytes;
         const uint32_t mi = (uint32_t)((uintptr_t)gs & 15u);
         const int nv = (int)(mi + 4 * P + 15) >> 4;
+        GG_LS_START;
         const uint32_t flags = half_of(__ballot(cfb != 0), hf.h) & 0xFu;   // bit 0 turn, 1 (unused), 2 passed, 3 done
         WAVE_SYNC();
         uint4 *iov = reinterpret_cast<uint4 *>(io);
@@ -158,8 +180,20 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
         white = plane_to_row<R>(io + mi + P, N, hf.hl);
         invalid = plane_to_row<R>(io + mi + 3 * P, N, hf.hl);
         const uint32_t turn = flags & 1u, passed = (flags >> 2) & 1u, done = (flags >> 3) & 1u;
-        uint32_t ab;
-        analyze2<R, false>(black, white, hf.full_l1 & ~(black | white), hf, v2, mb, ab, mw, nullptr, nullptr, true);
+        GG_LS(0);
+        // both boards of the pair stand in the workspace stone for stone: their M comes from there, no analysis
+        bool known = false;
+        if (ws) {
+          known = __ballot(hf.hl < N && (black != cw0 || white != cw1)) == 0;
+          if (known) { mb = cw2; mw = cw3; }
+          else wsmiss |= 3u << (2 * i);
+          GG_WSC(known);
+        }
+        if (!known) {
+          uint32_t ab;
+          analyze2<R, false>(black, white, hf.full_l1 & ~(black | white), hf, v2, mb, ab, mw, nullptr, nullptr, true);
+        }
+        GG_LS(1);
         if (row) {
           st[0 * PL + s * RS + hf.hl] = black;
           st[1 * PL + s * RS + hf.hl] = white;
@@ -181,9 +215,13 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
           }
         }
         WAVE_SYNC();
+        GG_LS(2);
         cv0 = nv0; cv1 = nv1; cv2 = nv2; cfb = nfb;
+        if (ws) { cw0 = nw0; cw1 = nw1; cw2 = nw2; cw3 = nw3; }
       }
 #undef GG_ISSUE_PAIR5
+#undef GG_ISSUE_WS5
+      GG_LS_FLUSH;
     }
     // the slot of an absent job: an all-zero block and class word (the loop area was the load's scratch)
     WAVE_SYNC();
@@ -793,7 +831,45 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
         if (steps_done && played) atomicAdd(reinterpret_cast<unsigned long long *>(steps_done) + b, (unsigned long long)played);
       }
       WAVE_SYNC();
+      if (ws) {
+        // the workspace entries of the boards whose bytes were written and of those analysed at load (any other board's entry
+        // already holds exactly this): stones out of the planes, M & stones parked behind them (the emitter is done with the
+        // loop area), then one flat coalesced copy of the four row sets as the tracked store above does it
+        const uint64_t wmask = __ballot(lnS < nbrd && (any_wr || ((wsmiss >> (lnS & 31)) & 1u)));
+        if (wmask) {
+#pragma unroll
+          for (int r = 0; r < RPL; ++r) {
+            if (r05s + r < RS) {
+              const uint32_t bk = st[0 * PL + s5s * RS + r05s + r], wh = st[1 * PL + s5s * RS + r05s + r];
+              park[0 * PL + s5s * RS + r05s + r] = M[r] & bk;
+              park[1 * PL + s5s * RS + r05s + r] = M[r] & wh;
+            }
+          }
+          WAVE_SYNC();
+          uint32_t *wg = ws + b_first * (int64_t)W;
+          const int nw4 = nbrd * 4 * N;
+#pragma unroll 1
+          for (int i0 = lnS; i0 < nw4; i0 += 4 * kWave) {
+            uint32_t v[4];
+            int at[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+              const int i = i0 + k * kWave;
+              const int ic = i < nw4 ? i : 0;
+              const int sb = ic / (4 * N), w = ic - sb * (4 * N);
+              const int pl = w / N, rw = w - pl * N;
+              v[k] = pl < 2 ? st[pl * PL + sb * RS + rw] : park[(pl - 2) * PL + sb * RS + rw];
+              at[k] = (i < nw4 && ((wmask >> sb) & 1ull)) ? sb * W + (pl < 2 ? w : w + N) : -1;
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+              if (at[k] >= 0) wg[at[k]] = v[k];
+          }
+          WAVE_SYNC();
+        }
+      }
     }
+    GG_WSC_FLUSH;
     GG_PROF(7);   // write-back
     GG_PROF_FLUSH;
   }

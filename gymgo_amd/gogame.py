@@ -11,6 +11,8 @@ arguments raises RuntimeError (:196).
 """
 import collections
 import math
+import os
+import weakref
 
 import numpy as np
 import torch
@@ -501,14 +503,57 @@ def rng_seed(batch_size, base_seed=20260927, first_game=0, device=None):
     return rng
 
 
-def batch_rollout(batch_states, rng, plies, auto_reset=True, last_actions=None, steps_done=None):
-    """IN PLACE: `plies` uniform-random steps per game with the board resident on-chip (gg_batch_rollout)."""
+# Workspaces batch_rollout attaches to the state tensors it is called on again and again: id(tensor) -> [data_ptr, shape,
+# device, workspace or None].  Entries leave with their tensor (weakref.finalize).
+_ROLLOUT_WS = {}
+
+
+def _rollout_workspace(t):
+    """The workspace batch_rollout keeps for the device tensor `t` (uint32 [B][tracked_words(N)] as int32, zeroed), or None.
+    The first call on a tensor object only records it - a one-shot call, or a slice made for one call, allocates nothing -,
+    the second allocates.  An entry whose tensor no longer has the pointer, shape and device it was recorded with starts over."""
+    if os.environ.get('GYMGO_AMD_ROLLOUT_WS', '1') == '0':
+        return None
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != _U8 or t.dim() != 4 or not t.is_contiguous():
+        return None
+    key, sig = id(t), (t.data_ptr(), tuple(t.shape), t.device)
+    ent = _ROLLOUT_WS.get(key)
+    if ent is None or ent[0] != sig:
+        if ent is None:
+            weakref.finalize(t, _ROLLOUT_WS.pop, key, None)
+        _ROLLOUT_WS[key] = [sig, None]
+        return None
+    if ent[1] is None:
+        if torch.cuda.is_current_stream_capturing():      # no allocation inside a stream capture: this call goes without
+            return None
+        ent[1] = torch.zeros((t.shape[0], 5 * t.shape[2] + 1), dtype=_I32, device=t.device)
+    return ent[1]
+
+
+def batch_rollout(batch_states, rng, plies, auto_reset=True, last_actions=None, steps_done=None, workspace=None):
+    """IN PLACE: `plies` uniform-random steps per game with the board resident on-chip (gg_batch_rollout).
+    workspace: int32 [B][tracked_words(N)], zero-filled before its first use (gg_batch_rollout_ws: big launches take the liberty
+    classes of every board that still is what the last call left from there, instead of analysing it again; results do not
+    depend on it).  None: from its second call on the same tensor object on, the call keeps a workspace of its own for that
+    tensor (388 B per 19x19 game, freed with the tensor; GYMGO_AMD_ROLLOUT_WS=0 switches that off)."""
     B, C, N, _ = batch_states.shape
-    code = _lib.lib().gg_batch_rollout(
+    if workspace is None:
+        workspace = _rollout_workspace(batch_states)
+    elif tuple(workspace.shape) != (B, 5 * N + 1):
+        raise ValueError('workspace must be int32 [%d][%d] (got %s)' % (B, 5 * N + 1, tuple(workspace.shape)))
+    if workspace is None:
+        code = _lib.lib().gg_batch_rollout(
+            _lib.dev_ptr(batch_states, _U8, 'states'), _lib.dev_ptr(rng, _I64, 'rng'),
+            _lib.dev_ptr(last_actions, _I32, 'last_actions'), _lib.dev_ptr(steps_done, _I64, 'steps_done'),
+            B, N, int(plies), int(bool(auto_reset)), _lib.stream_ptr(batch_states.device))
+        _lib.check(code, 'gg_batch_rollout')
+        return batch_states
+    code = _lib.lib().gg_batch_rollout_ws(
         _lib.dev_ptr(batch_states, _U8, 'states'), _lib.dev_ptr(rng, _I64, 'rng'),
         _lib.dev_ptr(last_actions, _I32, 'last_actions'), _lib.dev_ptr(steps_done, _I64, 'steps_done'),
-        B, N, int(plies), int(bool(auto_reset)), _lib.stream_ptr(batch_states.device))
-    _lib.check(code, 'gg_batch_rollout')
+        _lib.dev_ptr(workspace, _I32, 'workspace'), B, N, int(plies), int(bool(auto_reset)),
+        _lib.stream_ptr(batch_states.device))
+    _lib.check(code, 'gg_batch_rollout_ws')
     return batch_states
 
 

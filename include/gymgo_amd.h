@@ -155,6 +155,20 @@ int32_t gg_batch_rollout(uint8_t *states, uint64_t *rng, int32_t *last_actions, 
                          int32_t N, int32_t plies, int32_t auto_reset, void *hip_stream);
 
 /*
+ * gg_batch_rollout with a caller-owned WORKSPACE
+ * Same arguments, results (states, rng, last_actions, steps_done) and kernel dispatch as gg_batch_rollout, plus `workspace`:
+ * uint32 [B][gg_tracked_words(N)], zero-filled before its first use and otherwise opaque.  A launch of the thirty-two-board
+ * kernel on byte planes leaves in it the stones and liberty classes of every position it wrote to `states`; the next call
+ * takes the liberty classes of game b from there when planes 0 / 1 of states[b] equal the workspace's stones EXACTLY
+ * (checked per board, every call) and analyses the board from scratch otherwise.  A loop that calls the rollout again and
+ * again on one resident buffer therefore pays the full liberty analysis once, whatever else edits some of the boards in
+ * between; results never depend on the workspace content.  Launches served by any other kernel (small batches, short
+ * launches) neither read nor write the workspace.
+ */
+int32_t gg_batch_rollout_ws(uint8_t *states, uint64_t *rng, int32_t *last_actions, int64_t *steps_done, uint32_t *workspace,
+                            int64_t B, int32_t N, int32_t plies, int32_t auto_reset, void *hip_stream);
+
+/*
  * GoEnv.step for every game of a batched env, IN PLACE, one launch            gym_go/envs/go_env.py:49-76
  *   1. auto_reset != 0: a finished game (plane 5 set) is reset first (GoEnv.reset, :40-47); auto_reset == 0: it
  *      is refused (status 1, row untouched; the reference asserts `not self.done`, :53).
