@@ -1512,4 +1512,42 @@ int32_t gg_puct_advance(const int32_t *actions, const uint32_t *next, int64_t R,
   return (int32_t)hipGetLastError();
 }
 
+int32_t gg_puct_root_noise(int64_t R, int32_t N, int32_t C, float eps, const float *noise, uint8_t *todo, const uint32_t *boards,
+                           float *prior, const gg_puct_stat *stats, const int32_t *nodes, void *hip_stream) {
+  PuctRootArgs u{};
+  if (int32_t e = puct_args(u.t, R, N, C, 0.0, 0.f, boards, nullptr, prior, nullptr, stats, const_cast<int32_t *>(nodes), nullptr,
+                            nullptr, nullptr))
+    return e;
+  if (!(eps >= 0.f && eps <= 1.f)) return GG_E_BADARG;
+  if (R == 0) return 0;
+  if (!noise || !todo || !boards || !prior || !stats || !nodes) return GG_E_NULLPTR;
+  u.noise = noise;
+  u.todo = todo;
+  u.eps = eps;
+  OnDeviceOf on_dev(boards);
+  hipStream_t s = (hipStream_t)hip_stream;
+  k_puct_root_noise<<<grid_for(on_dev.cus(), (R + 3) / 4), 4 * kWave, 0, s>>>(u);
+  return (int32_t)hipGetLastError();
+}
+
+int32_t gg_puct_root_policy(int64_t R, int32_t N, int32_t C, const uint8_t *sample, uint64_t *rng, const uint32_t *boards,
+                            const int32_t *child, const gg_puct_stat *stats, const int32_t *nodes, int32_t *actions, float *pi,
+                            float *value, void *hip_stream) {
+  PuctRootArgs u{};
+  if (int32_t e = puct_args(u.t, R, N, C, 0.0, 0.f, boards, const_cast<int32_t *>(child), nullptr, nullptr, stats,
+                            const_cast<int32_t *>(nodes), nullptr, nullptr, nullptr))
+    return e;
+  if (R == 0) return 0;
+  if (!boards || !child || !stats || !nodes || !actions || (sample && !rng)) return GG_E_NULLPTR;
+  u.sample = sample;   // (may be NULL: no root draws)
+  u.rng = rng;
+  u.actions = actions;
+  u.pi = pi;           // (may be NULL)
+  u.value = value;     // (may be NULL)
+  OnDeviceOf on_dev(boards);
+  hipStream_t s = (hipStream_t)hip_stream;
+  k_puct_root_policy<<<grid_for(on_dev.cus(), (R + 3) / 4), 4 * kWave, 0, s>>>(u);
+  return (int32_t)hipGetLastError();
+}
+
 }  // extern "C"

@@ -675,4 +675,167 @@ static __global__ __launch_bounds__(4 * kWave) void k_puct_advance(PuctAdvanceAr
   }
 }
 
+// ---------------------------------------------------------------- self-play: noise into the root's priors, the move and the policy target
+// k_puct_root_noise / k_puct_root_policy (gg_puct_root_noise / gg_puct_root_policy of include/gymgo_amd.h, which holds the
+// normative text).  Both run outside a round (every v = 0) on node 0 of every tree, one wave per root as everywhere in this
+// file, the lanes striding over the A actions with legality from the root board's invalid rows - k_puct_select's rule.  No
+// atomics, no LDS, nothing read back.
+//   NOISE   an applicable root (todo set, node 0 evaluated, game not over) gets prior_0[a] = keep prior_0[a] + eps z[a] on its
+//           legal actions (float32, two products and one sum, no contraction; z = the noise with NaN / negatives / -0 as +0;
+//           a NaN result as the one quiet NaN) and +0 elsewhere; todo[r] = 0.  Every other root keeps all its bytes.
+//   POLICY  the lanes gather the visits of the root's children (kPuctStrides per lane, kept in registers), the wave sums them
+//           (S) and takes the argmax (ties to the lowest action); with sample[r] and S > 0 one step of the root's generator
+//           gives k in [0, S) and the action is the first one, ascending, whose running sum exceeds k: per stride an inclusive
+//           scan over the lanes on top of the strides before it, the first lane past k from a ballot.  pi = n_a / S.
+
+struct PuctRootArgs {
+  PuctArgs t;                // the tree; t.I = C, the capacity (leaf, move, leaf_id, priors, values unused)
+  const float *noise;        // [R][A] (noise)
+  uint8_t *todo;             // [R] read and written (noise)
+  float eps;                 // (noise)
+  const uint8_t *sample;     // [R] 1 = draw the action in proportion to the visits; NULL = all 0 (policy)
+  uint64_t *rng;             // [R] gg_rng_seed's generator, advanced once per draw (policy)
+  int32_t *actions;          // [R] (policy)
+  float *pi;                 // [R][A], may be NULL (policy)
+  float *value;              // [R], may be NULL (policy)
+};
+
+constexpr int kPuctStrides = (GG_MAX_BOARD * GG_MAX_BOARD + 1 + kWave - 1) / kWave;   // 6 actions per lane at 19x19
+
+__device__ __forceinline__ float puct_mix(float keep, float p, float eps, float z) {
+#pragma clang fp contract(off)
+  const float a = __fmul_rn(keep, p);
+  const float b = __fmul_rn(eps, z);
+  const float s = __fadd_rn(a, b);
+  return s == s ? s : __uint_as_float(0x7FC00000u);   // (0 times an infinite value: one NaN, whatever the hardware's payload)
+}
+
+static __global__ __launch_bounds__(4 * kWave) void k_puct_root_noise(PuctRootArgs b) {
+  const PuctArgs &a = b.t;
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t wave = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) / kWave;
+  const int64_t nwaves = (gridDim.x * (int64_t)blockDim.x) / kWave;
+  const int N = a.N, W = 5 * N + 1, P = N * N, A = P + 1, NN = a.I + 1;
+  const float keep = __fsub_rn(1.0f, b.eps);
+  for (int64_t r = wave; r < a.R; r += nwaves) {
+    if (b.todo[r] == 0) continue;
+    const uint32_t *g = a.boards + r * NN * W;   // node 0
+    const uint32_t flag = g[5 * N];
+    if ((flag & 4u) || a.stats[r * NN].n <= 0) continue;   // the game has ended, or the root is not evaluated yet: not a byte changes
+    const float *z = b.noise + r * A;
+    float *pr = a.prior + r * NN * A;   // node 0's row
+    for (int act = lane; act < A; act += kWave) {
+      const int row = act / N;
+      const bool legal = act == P || !((g[2 * N + (act < P ? row : 0)] >> (act - row * N)) & 1u);
+      const float zv = z[act];
+      const float v = puct_mix(keep, pr[act], b.eps, zv > 0.f ? zv : 0.f);   // (NaN, negatives, -0 -> +0)
+      pr[act] = legal ? v : 0.f;
+    }
+    if (lane == 0) b.todo[r] = 0;
+  }
+}
+
+static __global__ __launch_bounds__(4 * kWave) void k_puct_root_policy(PuctRootArgs b) {
+  const PuctArgs &a = b.t;
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t wave = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) / kWave;
+  const int64_t nwaves = (gridDim.x * (int64_t)blockDim.x) / kWave;
+  const int N = a.N, W = 5 * N + 1, P = N * N, A = P + 1, NN = a.I + 1;
+  for (int64_t r = wave; r < a.R; r += nwaves) {
+    const uint32_t *g = a.boards + r * NN * W;   // node 0
+    const int32_t *ch = a.child + r * NN * A;    // node 0's row
+    const PuctStat *st = a.stats + r * NN;
+    float *pi = b.pi ? b.pi + r * A : nullptr;
+    const uint32_t flag = __builtin_amdgcn_readfirstlane(g[5 * N]);
+    if (flag & 4u) {   // the game has ended: no action, an all-zero row, the generator untouched
+      if (pi)
+        for (int act = lane; act < A; act += kWave) pi[act] = 0.f;
+      if (lane == 0) {
+        b.actions[r] = -1;
+        if (b.value) b.value[r] = 0.f;
+      }
+      continue;
+    }
+    const int nodes = max(1, min(a.nodes[r], NN));   // (1 <= nodes <= C + 1: every index below stays inside the tree)
+    uint32_t na[kPuctStrides];   // the visits under this lane's actions, 0 where illegal or without a child
+    uint32_t legal = 0u;         // bit i: the action of stride i is legal
+    uint32_t sum = 0u;
+    int32_t best = -1;
+    int besta = A;
+#pragma unroll
+    for (int i = 0; i < kPuctStrides; ++i) {
+      const int act = i * kWave + lane;
+      na[i] = 0u;
+      if (act < A) {
+        const int row = act / N;
+        if (act == P || !((g[2 * N + (act < P ? row : 0)] >> (act - row * N)) & 1u)) {
+          legal |= 1u << i;
+          const int c = ch[act];
+          if (c > 0 && c < nodes) {
+            const int32_t n = st[c].n;
+            na[i] = n < 0 ? 0u : (uint32_t)n;
+          }
+          sum += na[i];
+          if ((int32_t)na[i] > best) {   // (this lane's actions ascend: the first of equal counts stays)
+            best = (int32_t)na[i];
+            besta = act;
+          }
+        }
+      }
+    }
+    // S, and the wave's argmax with ties to the lowest action (a lane without a legal action holds -1 / A and loses every tie)
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) {
+      sum += __shfl_xor(sum, o);
+      const int32_t ob = __shfl_xor(best, o);
+      const int oa = __shfl_xor(besta, o);
+      if (ob > best || (ob == best && oa < besta)) {
+        best = ob;
+        besta = oa;
+      }
+    }
+    const uint32_t S = sum;
+    int action = besta < A ? besta : P;   // (the pass is always legal: the fallback only with corrupt buffers)
+    const bool draw = b.sample && b.sample[r] != 0 && S > 0u;
+    if (draw) {
+      uint64_t x = b.rng[r];
+      const uint64_t u = splitmix_next(x);
+      const uint32_t k = (uint32_t)(((u >> 32) * (uint64_t)S) >> 32);   // in [0, S)
+      uint32_t base = 0u;   // the visits of the strides before this one
+#pragma unroll
+      for (int i = 0; i < kPuctStrides; ++i) {
+        uint32_t run = na[i];   // inclusive scan over the lanes: the actions of a stride ascend with the lane
+#pragma unroll
+        for (int o = 1; o < kWave; o <<= 1) {
+          const uint32_t up = __shfl_up(run, o);
+          if (lane >= o) run += up;
+        }
+        const unsigned long long past = __ballot(base + run > k);
+        if (past) {
+          action = i * kWave + (__ffsll(past) - 1);
+          break;
+        }
+        base += __shfl(run, kWave - 1);
+      }
+      if (lane == 0) b.rng[r] = x;
+    }
+    if (pi) {
+      const float fs = (float)S;
+#pragma unroll
+      for (int i = 0; i < kPuctStrides; ++i) {
+        const int act = i * kWave + lane;
+        if (act < A) pi[act] = S > 0u && ((legal >> i) & 1u) ? __fdiv_rn((float)na[i], fs) : 0.f;
+      }
+    }
+    if (lane == 0) {
+      b.actions[r] = action;
+      if (b.value) {
+        const PuctStat k0 = st[0];
+        const double s = (flag & 1u) ? -1.0 : 1.0;
+        b.value[r] = k0.n > 0 ? (float)(s * k0.w / (double)k0.n) : 0.f;
+      }
+    }
+  }
+}
+
 }  // namespace gg

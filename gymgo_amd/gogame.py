@@ -1318,7 +1318,11 @@ class PuctSearch:
     `iterations` more rounds may follow.  A tree that is full falls under the no-room rule of batch_puct: the search goes
     on refining values and expands nothing.  No finite capacity excludes that over many moves; result().nodes shows how
     full the trees are.  A kept root is already evaluated and is not handed out again, so root noise that the evaluator
-    adds reaches only fresh roots."""
+    adds would reach only fresh roots: add_root_noise() mixes noise into the stored priors of kept and fresh roots alike.
+
+    add_root_noise(noise, eps, todo) and root_policy(sample, rng) are what a self-play loop needs on top (puct_selfplay is
+    that loop): exploration noise in the root's priors, the move by the most visits or drawn in proportion to them, and
+    the policy target and root value, all on the device."""
 
     def __init__(self, batch_states, iterations, c=1.25, komi=0.0, leaves=None, capacity=None):
         self._box = batch_states if isinstance(batch_states, _Box) else _Box(batch_states)   # (a _Box: puct_play's own states)
@@ -1573,6 +1577,79 @@ class PuctSearch:
         self._done, self._I = 0, rounds
         return self._kept
 
+    def add_root_noise(self, noise, eps=0.25, todo=None):
+        """Mix noise into the root's stored priors (gg_puct_root_noise) -> todo.  noise: float32 [R, A], a tensor or NumPy
+        array, NOT normalised by the library (dirichlet_noise makes rows that sum to 1 over the legal actions); eps in
+        [0, 1]; todo: a bool or uint8 [R] device tensor, updated in place (None: a fresh all-ones buffer, which is returned).
+        A root with todo set that is evaluated and whose game has not ended gets prior = (1 - eps) * prior + eps * noise on
+        its legal actions (float32, NaN / negative noise as 0) and its todo cleared; every other root keeps its bytes.  So
+        one call before round 0 reaches the kept roots, a second call with the same noise and todo after round 0 the fresh
+        roots that round has just evaluated, and no root is changed twice.  May be called whenever no leaf is outstanding;
+        queues one launch, reads nothing back."""
+        if self._pending:
+            raise ValueError('PuctSearch.add_root_noise(): the leaves of the last select() have not been backed up')
+        R, A = self._R, self._N * self._N + 1
+        eps = float(eps)
+        if not 0.0 <= eps <= 1.0:
+            raise ValueError('need 0 <= eps <= 1 (got %r)' % eps)
+        if not isinstance(noise, torch.Tensor):
+            noise = torch.from_numpy(np.ascontiguousarray(noise))
+        if tuple(noise.shape) != (R, A):
+            raise ValueError('noise must be [%d, %d] (got %s)' % (R, A, tuple(noise.shape)))
+        if todo is None:
+            todo = torch.ones(R, dtype=_U8, device=self._dev)
+        elif (not isinstance(todo, torch.Tensor) or todo.dtype not in (torch.bool, _U8) or tuple(todo.shape) != (R,)
+              or not todo.is_contiguous()):
+            raise ValueError('todo must be a contiguous bool or uint8 [%d] device tensor' % R)
+        if R:
+            noise = noise.to(device=self._dev, dtype=torch.float32).contiguous()
+            boards, _, prior, _, stats, nodes = self._tree
+            _lib.check(_lib.lib().gg_puct_root_noise(R, self._N, self._C, eps, _lib.dev_ptr(noise, torch.float32, 'noise'),
+                                                     _lib.dev_ptr(todo, todo.dtype, 'todo'), boards, prior, stats, nodes,
+                                                     _lib.current_raw_stream(self._dev)), 'gg_puct_root_noise')
+        return todo
+
+    def root_policy(self, sample=None, rng=None, pi=True):
+        """The move, the policy target and the value of every root (gg_puct_root_policy) -> (actions int64 [R], pi float32
+        [R, A] or None with pi=False, value float32 [R]); device tensors, or NumPy arrays for NumPy input.  sample: None (no
+        root draws) or bool / uint8 [R]; where it is set and the root's children have visits, the action is drawn in
+        proportion to the visit counts with rng - the caller's gogame.rng_seed(..) tensor, int64 [R] on the device,
+        advanced in place once per root that draws -, elsewhere it is the legal child with the most visits, ties to the
+        lowest action: puct_actions' move.  pi = visits / their sum (all zero without visits), value = the root's mean
+        value for the player to move.  A root whose game has ended gives -1, a zero row and 0.  May be called whenever no
+        leaf is outstanding; queues one launch, reads nothing back."""
+        if self._pending:
+            raise ValueError('PuctSearch.root_policy(): the leaves of the last select() have not been backed up')
+        R = self._R
+        if sample is not None:
+            if rng is None:
+                raise ValueError('PuctSearch.root_policy(): sample needs rng (gogame.rng_seed)')
+            if not isinstance(sample, torch.Tensor):
+                sample = torch.from_numpy(np.ascontiguousarray(sample))
+            if tuple(sample.shape) != (R,) or sample.dtype not in (torch.bool, _U8):
+                raise ValueError('sample must be bool or uint8 [%d] (got %s %s)' % (R, sample.dtype, tuple(sample.shape)))
+            if (not isinstance(rng, torch.Tensor) or rng.dtype != _I64 or tuple(rng.shape) != (R,) or not rng.is_contiguous()):
+                raise ValueError('rng must be a contiguous int64 [%d] device tensor (gogame.rng_seed)' % R)
+            sample = sample.to(self._dev).contiguous()
+        acts, p, v = self._root_policy(sample, rng, pi)
+        return tuple(_back(self._box, t) for t in (acts.to(_I64), p, v))
+
+    def _root_policy(self, sample, rng, pi=True):
+        """root_policy() on checked device tensors -> (actions int32 [R], pi or None, value), new device tensors."""
+        R, A, dev = self._R, self._N * self._N + 1, self._dev
+        acts = torch.empty(R, dtype=_I32, device=dev)
+        p = torch.empty((R, A), dtype=torch.float32, device=dev) if pi else None
+        v = torch.empty(R, dtype=torch.float32, device=dev)
+        if R:
+            boards, child, _, _, stats, nodes = self._tree
+            d = _lib.dev_ptr
+            _lib.check(_lib.lib().gg_puct_root_policy(R, self._N, self._C, None if sample is None else d(sample, sample.dtype, 'sample'),
+                                                      d(rng, _I64, 'rng') if sample is not None else None, boards, child, stats,
+                                                      nodes, d(acts, _I32, 'actions'), d(p, torch.float32, 'pi'),
+                                                      d(v, torch.float32, 'value'), _lib.current_raw_stream(dev)),
+                       'gg_puct_root_policy')
+        return acts, p, v
+
 
 def batch_puct(batch_states, iterations, evaluator, c=1.25, komi=0.0, tree=False, leaves=None, capacity=None):
     """PUCT search (the AlphaZero search) of `iterations` iterations from every root of batch_states ([R, 6, N, N]) with the
@@ -1581,7 +1658,9 @@ def batch_puct(batch_states, iterations, evaluator, c=1.25, komi=0.0, tree=False
     evaluator(states, legal) -> (priors, values): states uint8 [R, 6, N, N] and legal bool [R, A] (A = N*N + 1) are device
     tensors whatever batch_states was; priors float32 [R, A], values float32 [R] - the value in [-1, 1] for the player to move
     at the leaf.  Priors are NOT renormalised by the library (a float sum would depend on the kernel's order): normalising
-    over `legal` is the evaluator's job.  Root Dirichlet noise is its business too: iteration 0 always hands out the roots.
+    over `legal` is the evaluator's job.  Root Dirichlet noise can be its business too - iteration 0 always hands out the roots -
+    but only for a search from fresh roots: a root kept by PuctSearch.advance is not handed out again, and
+    PuctSearch.add_root_noise reaches both kinds.
 
     Each root has its own tree with room for iterations + 1 nodes; a node keeps n (visits), w (float64 sum of the backed-up
     values from BLACK's point of view), its priors and a child table.  Iteration i, per root: select from the root - a node
@@ -1648,7 +1727,8 @@ def puct_play(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, leav
     falls under the no-room rule - it goes on refining the values of the nodes it has and expands nothing.  Give `capacity`
     room for the moves to come; no finite capacity excludes a full tree over many moves, and PuctSearch.result().nodes
     shows how full the trees are.  A kept root is already evaluated and is not handed out again, so root noise that the
-    evaluator adds reaches only fresh roots."""
+    evaluator adds would reach only fresh roots: PuctSearch.add_root_noise reaches kept roots too, and puct_selfplay is this
+    loop with it, with moves drawn from the visit counts and with the training records."""
     _puct_komi_guard(evaluator, komi)
     moves = int(moves)
     if moves < 0:
@@ -1669,6 +1749,112 @@ def puct_play(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, leav
             box.t = search._played_states(played[:, mv])
             search = PuctSearch(box, iterations, c, komi, leaves=leaves, capacity=capacity)
     return _back(box, played), box.back(search._root_states())
+
+
+def dirichlet_noise(alpha, generator=None):
+    """Root exploration noise for puct_selfplay -> a callable noise(move, legal) -> float32 [R, A] on legal's device: per
+    root a Dirichlet(alpha) sample over its legal actions (legal: bool [R, A]) - Gamma(alpha) draws by torch (`generator`:
+    a torch.Generator of that device, None = torch's default), zero on illegal actions, divided by the row sum; a row
+    whose draws all underflowed is uniform over the legal actions, a root without legal actions gets zeros.  NOT
+    bit-defined: the draws are torch's and the row sum is a float sum in torch's order, so a game played with this noise
+    is reproducible only as far as torch's generator is; everything the library does with the noise is exact."""
+    alpha = float(alpha)
+    if not (alpha > 0 and math.isfinite(alpha)):
+        raise ValueError('need alpha > 0 and finite (got %r)' % alpha)
+
+    def noise(move, legal):
+        conc = torch.full(legal.shape, alpha, dtype=torch.float32, device=legal.device)
+        g = torch.where(legal, torch._standard_gamma(conc, generator=generator), torch.zeros_like(conc))
+        total = g.sum(dim=1, keepdim=True)
+        count = legal.sum(dim=1, keepdim=True).to(torch.float32)
+        uniform = torch.where(legal, 1.0 / count.clamp(min=1.0), torch.zeros_like(conc))
+        return torch.where(total > 0, g / total.clamp(min=torch.finfo(torch.float32).tiny), uniform)
+
+    return noise
+
+
+SelfPlay = collections.namedtuple('SelfPlay', 'actions pi value outcome lengths final_states states')
+SelfPlay.__doc__ = """Records of puct_selfplay per root: actions (int64 [R, moves], -1 once the game has ended), pi (float32
+[R, moves, A]: the root's visit counts over their sum before each move, zero rows once the game has ended), value (float32
+[R, moves]: the root's mean value for the player to move), outcome (int8 [R]: sign(black area - white area - komi) of a game
+that ended, 0 for one still running), lengths (int32 [R]: moves played), final_states (uint8 [R, 6, N, N]) and states (uint8
+[R, moves, 6, N, N], the roots before each move, or None)."""
+
+
+def puct_selfplay(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, leaves=None, capacity=None, noise=None,
+                  eps=0.25, sample_moves=0, seed=20260927, first_game=0, record_states=False):
+    """Self-play games for training: `moves` moves from every root of batch_states ([R, 6, N, N]) with a PUCT search per move
+    on the kept tree -> SelfPlay (device tensors for a device tensor, NumPy arrays for NumPy input).  puct_play's
+    reuse=True loop (`iterations` rounds per move with `leaves` and `capacity` as there, then PuctSearch.advance) with
+    four changes, per move mv:
+      - noise (None, or a callable noise(mv, legal) -> float32 [R, A] as dirichlet_noise returns; legal: the roots' bool
+        [R, A]): z = noise(mv, legal) is mixed into the roots' priors with weight eps by PuctSearch.add_root_noise, once
+        before round 0 - which reaches the roots kept from the move before - and once after it with the same z and todo -
+        which reaches the fresh roots round 0 has just evaluated; no root gets it twice, ended roots never.
+      - after the last round PuctSearch.root_policy gives the move, the policy target and the root value: while
+        mv < sample_moves the move is drawn in proportion to the visit counts, afterwards it is the child with the most
+        visits (puct_play's move).  The generators are rng_seed(R, seed, first_game), made once per call, so shards by root
+        with first_game = the shard's first root concatenate to the whole.
+      - the records are kept: see SelfPlay.  A game that has ended stays where it is: action -1, a zero pi row, value 0.
+      - outcome: for a game that ended, sign(black area - white area - komi) by the rule of the search's ended leaves (komi
+        and the difference in float32); 0 for a game still running after `moves`.
+    Nothing synchronises: every step queues launches on torch's current stream.  The evaluator is called moves * iterations
+    times and must score with the search's komi (batch_puct's guard).  Without record_states a trainer replays the
+    positions from the roots with batch_play_moves(states, actions).  Device memory of the records: pi takes
+    4 * R * moves * A bytes (189 MB for 1 024 roots x 128 moves at 19x19), states 6 N^2 * R * moves.  moves = 0 or R = 0:
+    no device call, empty records of these shapes."""
+    _puct_komi_guard(evaluator, komi)
+    moves, sample_moves, eps = int(moves), int(sample_moves), float(eps)
+    if moves < 0:
+        raise ValueError('need moves >= 0 (got %d)' % moves)
+    if sample_moves < 0:
+        raise ValueError('need sample_moves >= 0 (got %d)' % sample_moves)
+    if not 0.0 <= eps <= 1.0:
+        raise ValueError('need 0 <= eps <= 1 (got %r)' % eps)
+    if noise is not None and not callable(noise):
+        raise ValueError('noise must be None or a callable noise(move, legal) -> float32 [R, A]')
+    box = batch_states if isinstance(batch_states, _Box) else _Box(batch_states)
+    st = box.t
+    if st.dim() != 4 or st.shape[1] != govars.NUM_CHNLS or st.shape[2] != st.shape[3]:
+        raise ValueError('batch_states must be [R, 6, N, N] (got %s)' % (tuple(st.shape),))
+    I, c, komi = _puct_args(iterations, c, komi)
+    _puct_capacity(I, _puct_leaves(I, leaves), capacity)
+    R, N, dev = st.shape[0], st.shape[2], st.device
+    A = N * N + 1
+    played = torch.full((R, moves), -1, dtype=_I64, device=dev)
+    pis = torch.zeros((R, moves, A), dtype=torch.float32, device=dev)
+    vals = torch.zeros((R, moves), dtype=torch.float32, device=dev)
+    lengths = torch.zeros(R, dtype=_I32, device=dev)
+    outcome = torch.zeros(R, dtype=torch.int8, device=dev)
+    before = torch.empty((R, moves, govars.NUM_CHNLS, N, N), dtype=_U8, device=dev) if record_states else None
+    if not R or not moves:
+        return _back(box, SelfPlay(played, pis, vals, outcome, lengths, st, before))
+    search = PuctSearch(box, I, c, komi, leaves=leaves, capacity=capacity)
+    rng = rng_seed(R, seed, first_game, device=dev)
+    ones, todo = torch.ones(R, dtype=_U8, device=dev), torch.empty(R, dtype=_U8, device=dev)
+    for mv in range(moves):
+        if record_states:
+            before[:, mv] = search._root_states()
+        if noise is not None:
+            z = noise(mv, search._legal_roots)
+            todo.fill_(1)
+            search.add_root_noise(z, eps, todo)     # the roots kept from the move before
+        for t in range(search._I):
+            states, legal = search.select()
+            priors, values = evaluator(states, legal)
+            search.backup(priors, values)
+            if t == 0 and noise is not None:
+                search.add_root_noise(z, eps, todo)   # the fresh roots round 0 has just evaluated
+        acts, p, v = search._root_policy(ones if mv < sample_moves else None, rng)
+        played[:, mv], pis[:, mv], vals[:, mv] = acts, p, v
+        lengths += (acts >= 0).to(_I32)
+        search.advance(played[:, mv], check=False)
+    final = search._root_states()
+    black, white = _areas_dev(final)
+    x = (black - white).to(torch.float32) - torch.full((), komi, dtype=torch.float32, device=dev)   # gg_puct_backup's terminal rule
+    ended = final[:, govars.DONE_CHNL, 0, 0] != 0
+    outcome = torch.where(ended, torch.sign(x), torch.zeros_like(x)).to(torch.int8)
+    return _back(box, SelfPlay(played, pis, vals, outcome, lengths, final, before))
 
 
 def puct(state, iterations, evaluator, **kw):

@@ -632,6 +632,50 @@ int32_t gg_puct_advance(const int32_t *actions, const uint32_t *next, int64_t R,
                         int32_t *child, float *prior, int32_t *links, gg_puct_stat *stats, int32_t *nodes, int32_t *remap,
                         int32_t *kept, void *hip_stream);
 
+/*
+ * Self-play on the kept tree: noise into the root's priors, the move drawn from the visit counts, the policy target.  The
+ * tree is the one of gg_puct_* above with room for C + 1 nodes (C where I stood), on either path.  Both calls are only
+ * defined outside a round (after a backup, after an advance, or before the first select), when every v = 0; both run one
+ * wave per root, use no atomics and read nothing back; root r's results depend on root r alone.  The legal actions of the
+ * root are those of gg_puct_select at node 0: none once its game has ended, else the pass and every point whose invalid bit
+ * is clear.
+ *   gg_puct_root_noise   noise float32 [R][A]; todo uint8 [R], read and written; eps float32 in [0, 1].  Root r is APPLICABLE
+ *     when todo[r] != 0, node 0 is evaluated (n_0 > 0) and the root's game has not ended.  An applicable root gets, with
+ *     keep = 1.0f - eps in float32 and z = noise[r][a] where NaN, negatives and -0 count as +0:
+ *       a legal:    prior_0[a] = (keep * prior_0[a]) + (eps * z)
+ *       a illegal:  prior_0[a] = +0
+ *     the two float32 products and the one float32 sum each rounded to nearest in this order, no fused multiply-add; a sum
+ *     that is NaN (0 times an infinite z or prior) is stored as the quiet NaN 0x7FC00000, which the selects count as
+ *     -infinity like any NaN score; and todo[r] = 0.  Every other root keeps all its bytes and its todo value.  The noise is
+ *     NOT normalised here (the rule of the priors above: a float sum would depend on its order): a Dirichlet sample over the
+ *     legal actions is the caller's to make.  The todo protocol reaches both kinds of root without a host read: one call
+ *     before round 0 changes the kept roots (already evaluated) and clears their todo, the same call again after round 0
+ *     changes the fresh roots that round 0 has just evaluated; ended roots are never touched, and a root is changed once.
+ *   gg_puct_root_policy   sample uint8 [R], NULL = all 0; rng uint64 [R], the generator of gg_rng_seed, required when sample
+ *     is not NULL; actions int32 [R]; pi float32 [R][A], may be NULL; value float32 [R], may be NULL.  Per root, n_a = the
+ *     visits of the child under the legal action a (0 without a child) and S = the sum of the n_a as an int32.
+ *     The root's game has ended: actions[r] = -1, the pi row all +0, value[r] = +0, rng[r] untouched.  Otherwise:
+ *       pi[r][a] = float(n_a) / float(S), one float32 division rounded to nearest; +0 on illegal actions; the whole row +0
+ *         when S = 0.
+ *       value[r] = float(s * w_0 / n_0), the float64 division first, then the conversion to float32, s = +1 if black is to
+ *         move at the root (flag bit 0 clear), else -1: the root's mean value for the player to move; +0 when n_0 = 0.
+ *       sample[r] = 0, or S = 0: actions[r] = the legal action of the largest n_a, ties to the lowest action; rng[r] untouched.
+ *       otherwise the ply step of the sampler above: x += 0x9E3779B97F4A7C15; u = splitmix64_finalise(x);
+ *         k = ((u >> 32) * S) >> 32 in 64-bit integers; actions[r] = the first legal action, ascending, whose running sum of
+ *         n_a exceeds k; rng[r] = x (advanced once).
+ *     So a root draws with P(a) = n_a / S up to 2^-32, and only the two rules exist - the most visits, and in proportion to
+ *     the visits: the temperatures 0 and 1 of the AlphaZero schedule.  A general temperature needs pow and could not be
+ *     bit-exact: it is out of scope.
+ * The argument checks come before any device work, in the order above: GG_E_BADSIZE: N outside [2, 19], R < 0;
+ * GG_E_BADARG: C < 1 or C = 2^31 - 1, eps outside [0, 1] or NaN (root_noise); R = 0 is no work and returns 0 before any
+ * pointer is looked at; GG_E_NULLPTR: any pointer but sample, rng, pi, value is NULL, or sample is given without rng.
+ */
+int32_t gg_puct_root_noise(int64_t R, int32_t N, int32_t C, float eps, const float *noise, uint8_t *todo, const uint32_t *boards,
+                           float *prior, const gg_puct_stat *stats, const int32_t *nodes, void *hip_stream);
+int32_t gg_puct_root_policy(int64_t R, int32_t N, int32_t C, const uint8_t *sample, uint64_t *rng, const uint32_t *boards,
+                            const int32_t *child, const gg_puct_stat *stats, const int32_t *nodes, int32_t *actions, float *pi,
+                            float *value, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

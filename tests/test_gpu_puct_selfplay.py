@@ -1,0 +1,411 @@
+"""-m gpu: PUCT self-play (gogame.PuctSearch.add_root_noise / root_policy, puct_selfplay, dirichlet_noise: k_puct_root_noise /
+k_puct_root_policy behind gg_puct_root_noise / gg_puct_root_policy).  Whole buffers as bit patterns - prior, todo, rng,
+actions, pi, value, and the tree buffers the calls must not touch - against the restatement
+(tests/mc_puct_selfplay_expect.py): 5x5 (A = 26, less than a wave of lanes), 9x9 (A = 82, two strides) and 19x19 (A = 362, a
+partial last stride), 7 roots (not a multiple of the four waves of a workgroup, ended roots among them), both search paths,
+the hash and hostile evaluators, kept / fresh / ended roots under the todo protocol; the entry points on the test's own
+buffers with sentinel words behind every output (2^31 - 1 visits, a child without visits between visited ones, a single
+visited child, S = 0 with sample = 1, hostile noise values, eps at 0 and 1, pi = NULL, value = NULL, sample = NULL);
+puct_selfplay over 5 moves against expected_selfplay, against puct_play, in shards, on a stream, with NumPy input."""
+import numpy as np
+import pytest
+
+import mc_expect as mc
+import mc_puct_expect as pe
+import mc_puct_advance_expect as pa
+import mc_puct_selfplay_expect as ps
+
+pytestmark = pytest.mark.gpu
+
+MARK = 0x5A5A5A5A
+EVALUATORS = {'hash': (pe.hash_evaluator_np, pe.hash_evaluator_t), 'hostile': (pe.hostile_evaluator_np, pe.hostile_evaluator_t),
+              'pass': (pe.pass_evaluator_np, pe.pass_evaluator_t)}
+BUFFERS = ('boards', 'child', 'prior', 'links', 'stats', 'nodes')
+
+
+def _roots(N, seed):
+    """7 roots: three of random play, the empty board, a root after a pass, a ko, a finished game."""
+    return np.concatenate([mc.make_roots(N, 4, seed, max_ply=N * N // 2, step=max(2, N * N // 8))[1:], mc.crafted_roots(N)])
+
+
+def _got(s):
+    return {k: mc.to_np(getattr(s, '_' + k)).copy() for k in BUFFERS}
+
+
+def _want(trees, N):
+    """The tree buffers of the restatement: used nodes from the trees (boards through the library's own track kernel), the
+    nodes an advance has reset with zero boards, MARK on the boards nothing has written."""
+    from gymgo_amd import gogame
+    R, NN, W = len(trees), trees[0].n.shape[0], 5 * N + 1
+    boards = np.full((R, NN, W), MARK, np.int32)
+    for r, t in enumerate(trees):
+        used = len(t.boards)
+        boards[r, :used] = mc.to_np(gogame.batch_track(mc.to_dev(np.stack(t.boards))))
+        boards[r, used:max(used, getattr(t, 'zeroed', 0))] = 0
+    stats = np.zeros((R, NN, 4), np.int32)
+    stats[..., :2] = np.stack([t.w for t in trees]).astype(np.float64).view(np.int32).reshape(R, NN, 2)
+    stats[..., 2] = np.stack([t.n for t in trees])
+    return {'boards': boards, 'child': np.stack([t.child for t in trees]).astype(np.int32),
+            'prior': np.stack([t.prior for t in trees]),
+            'links': np.stack([np.stack([t.parent, t.action], axis=1) for t in trees]).astype(np.int32), 'stats': stats,
+            'nodes': np.array([len(t.boards) for t in trees], np.int32)}
+
+
+def _equal(got, want, tag):
+    for k in BUFFERS:
+        g, w = pe.bits(got[k]), pe.bits(want[k])
+        assert g.shape == w.shape and g.dtype == w.dtype, (tag, k, g.shape, g.dtype, w.shape, w.dtype)
+        assert np.array_equal(g, w), (tag, k, np.argwhere(g != w)[:8])
+
+
+def _same_bits(got, want, tag):
+    g, w = pe.bits(mc.to_np(got)), pe.bits(np.asarray(want))
+    assert g.shape == w.shape and g.dtype == w.dtype, (tag, g.shape, g.dtype, w.shape, w.dtype)
+    assert np.array_equal(g, w), (tag, np.argwhere(g != w)[:8])
+
+
+def _rounds(s, trees, T, L, name, c=1.25, komi=0.5):
+    ev_np, ev_t = EVALUATORS[name]
+    for _ in range(T):
+        s.backup(*ev_t(*s.select()))
+    pa.search_rounds(trees, T, L, ev_np, c, komi)
+
+
+def _odd_noise(R, A, salt=0):
+    """float32 [R, A] in (0, 1] with NaN, negatives, -0 and +inf strewn in, nothing masked by legality."""
+    k = (np.arange(R * A, dtype=np.int64).reshape(R, A) * 37 + salt * 101) % 64
+    z = ((k + 1).astype(np.float32) / np.float32(64)).astype(np.float32)
+    for m, v in ((3, np.nan), (5, -1.0), (7, -0.0), (11, np.inf)):
+        z = np.where(k % 16 == m, np.float32(v), z).astype(np.float32)
+    return z
+
+
+def _rng_words(rng):
+    return np.array([int(x) for x in rng], dtype=np.uint64)
+
+
+def _policy_both(s, trees, sample, rng_t, rng):
+    """root_policy on the device and on the restatement -> the generators afterwards; everything compared as bit patterns."""
+    acts, pi, val = s.root_policy(None if sample is None else mc.to_dev(sample), rng_t)
+    assert acts.is_cuda and acts.dtype.is_floating_point is False and acts.element_size() == 8
+    want = [ps.root_policy(t, 0 if sample is None else int(sample[r]), rng[r]) for r, t in enumerate(trees)]
+    _same_bits(acts, np.array([w[0] for w in want], np.int64), 'actions')
+    _same_bits(pi, np.stack([w[1] for w in want]), 'pi')
+    _same_bits(val, np.array([w[2] for w in want], np.float32), 'value')
+    rng = [w[3] for w in want]
+    if rng_t is not None:
+        assert np.array_equal(mc.to_np(rng_t).view(np.uint64), _rng_words(rng)), 'rng'
+    return rng
+
+
+CASES = [(5, None, 'hash'), (5, 4, 'hostile'), (9, None, 'hostile'), (9, 1, 'hash'), (9, 4, 'hash'), (19, None, 'hash'),
+         (19, 1, 'hostile'), (19, 4, 'hostile')]
+
+
+@pytest.mark.parametrize('N,L,name', CASES)
+def test_noise_and_policy_on_searched_trees(N, L, name):
+    import torch
+    from gymgo_amd import gogame
+    T, eps = 6, 0.25
+    roots = _roots(N, 60 + N)
+    R, A = roots.shape[0], N * N + 1
+    assert R == 7
+    s = gogame.PuctSearch(mc.to_dev(roots), T, komi=0.5, leaves=L, capacity=3 * T * (L or 1) + 5)
+    s._boards[:, 1:] = MARK
+    trees = pa.make_trees(roots, s._C + 1, L)
+    rng = ps.seeds(R, 99, 4)
+    rng_t = gogame.rng_seed(R, 99, 4)
+    # before anything is evaluated: noise reaches no root, the policy is all zero and draws nothing
+    z0 = _odd_noise(R, A)
+    todo = s.add_root_noise(z0, eps)
+    assert todo.dtype == torch.uint8 and bool((todo == 1).all())
+    _equal(_got(s), _want(trees, N), 'unevaluated')
+    rng = _policy_both(s, trees, np.ones(R, np.uint8), rng_t, rng)
+    _rounds(s, trees, T, L, name)
+    sample = (np.arange(R) % 2 == 0).astype(np.uint8)
+    before = _got(s)
+    rng = _policy_both(s, trees, sample, rng_t, rng)
+    rng = _policy_both(s, trees, None, None, rng)
+    _equal(_got(s), before, 'the policy changes no byte of the tree')
+    _equal(before, _want(trees, N), 'searched')
+    # a move that leaves kept, fresh and ended roots; then the todo protocol around round 0
+    acts = []
+    for r, t in enumerate(trees):
+        free = [int(a) for a in t.legal[0] if t.child[0, a] < 0]
+        acts.append(free[-1] if r % 3 == 1 and free else pa.most_visited_root(t))
+    s.advance(mc.to_dev(np.array(acts, np.int64)))
+    for t, a in zip(trees, acts):
+        pa.advance(t, a, pa.next_root(t, a))
+    kinds = ['ended' if t.legal[0].size == 0 else ('kept' if t.n[0] > 0 else 'fresh') for t in trees]
+    assert {'ended', 'kept', 'fresh'} <= set(kinds), kinds
+    z = _odd_noise(R, A, salt=1)
+    todo = torch.ones(R, dtype=torch.bool, device='cuda')
+    assert s.add_root_noise(mc.to_dev(z), eps, todo) is todo
+    want_todo = [ps.root_noise(t, z[r], eps, 1) for r, t in enumerate(trees)]
+    assert want_todo == [int(k != 'kept') for k in kinds]
+    assert mc.to_np(todo).astype(np.int64).tolist() == want_todo
+    _equal(_got(s), _want(trees, N), 'noise on the kept roots')
+    _rounds(s, trees, 1, L, name)
+    s.add_root_noise(z, eps, todo)
+    want_todo = [ps.root_noise(t, z[r], eps, want_todo[r]) for r, t in enumerate(trees)]
+    assert want_todo == [int(k == 'ended') for k in kinds] and mc.to_np(todo).astype(np.int64).tolist() == want_todo
+    _equal(_got(s), _want(trees, N), 'noise on the fresh roots')
+    s.add_root_noise(z, eps, todo)                                    # a third call changes nothing
+    _equal(_got(s), _want(trees, N), 'noise once')
+    _rounds(s, trees, T - 1, L, name)
+    _equal(_got(s), _want(trees, N), 'searched with noise')
+    rng = _policy_both(s, trees, 1 - sample, rng_t, rng)
+    acts2, pi2, val2 = s.root_policy(pi=False)
+    assert pi2 is None and np.array_equal(mc.to_np(acts2), [pa.most_visited_root(t) for t in trees])
+    got = s.result()
+    assert np.array_equal(mc.to_np(acts2), mc.to_np(gogame._best_legal(gogame._ON_DEVICE, got.legal, got.visits.long())))
+
+
+def _hand_made_trees(N, C):
+    """Trees built by hand (pe.Tree objects whose child boards are never read): per root the case it stands for."""
+    A = N * N + 1
+    crafted = mc.crafted_roots(N)
+    empty, passed, ko, end = crafted
+    trees, names = [], []
+
+    def tree(root, kids, n0, w0, name):
+        t = pe.Tree(root, C)
+        for i, (a, n, w) in enumerate(kids):
+            y = i + 1
+            t.boards.append(root.copy())
+            t.legal.append(mc.legal_actions(root))
+            t.parent[y], t.action[y], t.child[0, a], t.n[y], t.w[y] = 0, a, y, n, w
+        t.n[0], t.w[0] = n0, w0
+        if n0:
+            t.prior[0, t.legal[0]] = (np.arange(t.legal[0].size) % 5 + 1).astype(np.float32) / np.float32(16)
+        trees.append(t)
+        names.append(name)
+
+    tree(empty, [(1, 2 ** 30, 3.5), (70, 2 ** 30 - 1, -2.25)], 2 ** 31 - 1, 12345.678, '2^31 - 1 visits')
+    tree(empty, [(3, 5, 1.0), (4, 0, 0.0), (5, 7, -3.0), (A - 1, 2, 0.5)], 15, -1.75, 'a child without visits between visited ones')
+    tree(passed, [(66, 9, 4.0)], 10, 4.5, 'a single visited child')
+    tree(empty, [], 1, 0.25, 'S = 0')
+    tree(empty, [(2, 0, 0.0), (A - 1, 0, 0.0)], 0, 0.0, 'not evaluated')
+    tree(end, [], 3, -3.0, 'ended')
+    tree(ko, [(40, 1, 1.0), (63, 1, 1.0), (64, 1, -1.0), (A - 1, 1, 0.0)], 5, -0.0, 'ties across two strides, white to move')
+    assert trees[6].boards[0][2, 0, 0] != 0 and all(a in trees[6].legal[0] for a in (40, 63, 64, A - 1))
+    return trees, names
+
+
+def test_entry_points_on_own_buffers_with_sentinels():
+    import torch
+    from gymgo_amd import gogame, _lib
+    N, C, TAIL = 9, 5, 1024
+    A = N * N + 1
+    trees, names = _hand_made_trees(N, C)
+    R = len(trees)
+    assert R % 4 and sum(ps.root_visits(trees[0])) == 2 ** 31 - 1
+    want = _want(trees, N)
+    dev = torch.device('cuda', torch.cuda.current_device())
+    lib, stream = _lib.lib(), _lib.current_raw_stream(dev)
+
+    def padded(arr):
+        words = np.ascontiguousarray(arr).view(np.int32 if arr.dtype.itemsize >= 4 else np.uint8).reshape(-1)
+        mark = np.int32(MARK) if words.dtype == np.int32 else np.uint8(0x5A)
+        flat = torch.from_numpy(np.concatenate([words, np.full(TAIL, mark, words.dtype)])).to(dev)
+        return flat, words.size
+
+    def tail_ok(flat, n):
+        return bool((flat[n:] == (MARK if flat.dtype == torch.int32 else 0x5A)).all())
+
+    tree = {k: padded(want[k]) for k in BUFFERS}
+    ptr = {k: v[0].data_ptr() for k, v in tree.items()}
+    rng0 = ps.seeds(R, 5, 11)
+    # ---- the policy: every root draws / no root draws / sample = NULL; pi = NULL; value = NULL
+    for sample, with_pi, with_value in ((np.ones(R, np.uint8), True, True), (np.zeros(R, np.uint8), True, True), (None, True, True),
+                                        (np.ones(R, np.uint8), False, True), (np.ones(R, np.uint8), True, False)):
+        outs = {'actions': padded(np.full(R, 77, np.int32)), 'pi': padded(np.full((R, A), 7.0, np.float32)),
+                'value': padded(np.full(R, 7.0, np.float32)), 'rng': padded(_rng_words(rng0).view(np.int64)),
+                'sample': padded(sample if sample is not None else np.zeros(R, np.uint8))}
+        p = {k: v[0].data_ptr() for k, v in outs.items()}
+        code = lib.gg_puct_root_policy(R, N, C, p['sample'] if sample is not None else None, p['rng'] if sample is not None else None,
+                                       ptr['boards'], ptr['child'], ptr['stats'], ptr['nodes'], p['actions'],
+                                       p['pi'] if with_pi else None, p['value'] if with_value else None, stream)
+        assert code == 0
+        exp = [ps.root_policy(t, 0 if sample is None else int(sample[r]), rng0[r]) for r, t in enumerate(trees)]
+        tag = (None if sample is None else int(sample[0]), with_pi, with_value)
+        for k, (flat, n) in list(outs.items()) + list(tree.items()):
+            assert tail_ok(flat, n), (tag, k)                          # nothing beyond any buffer
+        _same_bits(outs['actions'][0][:R], np.array([e[0] for e in exp], np.int32), (tag, 'actions'))
+        _same_bits(outs['pi'][0][:R * A].view(torch.float32).reshape(R, A),
+                   np.stack([e[1] for e in exp]) if with_pi else np.full((R, A), 7.0, np.float32), (tag, 'pi'))
+        _same_bits(outs['value'][0][:R].view(torch.float32),
+                   np.array([e[2] for e in exp], np.float32) if with_value else np.full(R, 7.0, np.float32), (tag, 'value'))
+        assert np.array_equal(mc.to_np(outs['rng'][0][:2 * R]).view(np.uint64), _rng_words([e[3] for e in exp])), (tag, 'rng')
+        for k in BUFFERS:                                              # the tree is read only
+            assert np.array_equal(mc.to_np(tree[k][0][:tree[k][1]]), np.ascontiguousarray(want[k]).view(np.int32).reshape(-1)), (tag, k)
+        if sample is not None and sample.all():
+            drew = [e[3] != x for e, x in zip(exp, rng0)]
+            assert drew == [True, True, True, False, False, False, True], (names, drew)   # S = 0, unevaluated, ended: no draw
+            assert exp[0][0] in (1, 70) and exp[2][0] == 66 and exp[3][0] == 0 and exp[5][0] == -1
+        else:
+            assert [e[0] for e in exp] == [1, 5, 66, 0, 0, -1, 40]    # ties to the lowest action
+    # the 64-bit product: generators whose upper word is large land in the second child of 2^31 - 1 visits
+    hits = set()
+    for x in ps.seeds(64, 3):
+        hits.add(ps.root_policy(trees[0], 1, x)[0])
+    assert hits == {1, 70}
+    many = padded(want['boards'][0])                                   # root 0 alone, one generator after the other
+    for x in ps.seeds(8, 3):
+        rng_t = torch.from_numpy(_rng_words([x]).view(np.int64)).to(dev)
+        one = torch.ones(1, dtype=torch.uint8, device=dev)
+        act = torch.full((1,), 77, dtype=torch.int32, device=dev)
+        assert lib.gg_puct_root_policy(1, N, C, one.data_ptr(), rng_t.data_ptr(), many[0].data_ptr(), ptr['child'], ptr['stats'],
+                                       ptr['nodes'], act.data_ptr(), None, None, stream) == 0
+        assert int(act[0]) == ps.root_policy(trees[0], 1, x)[0]
+    # ---- the noise: hostile values, eps at 0, 1 and between, a todo vector with holes
+    z = _odd_noise(R, A, salt=2)
+    z[0, :8] = [np.nan, -1.0, -0.0, np.inf, 0.5, 1.0, 0.0, 2.0 ** -130]
+    for eps, todo0 in ((0.0, np.ones(R, np.uint8)), (1.0, np.ones(R, np.uint8)), (0.25, np.array([1, 0, 2, 255, 1, 1, 0], np.uint8))):
+        work = [pe.Tree.__new__(pe.Tree) for _ in trees]
+        for wk, t in zip(work, trees):
+            wk.__dict__.update({k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in t.__dict__.items()})
+        tree = {k: padded(want[k]) for k in BUFFERS}
+        ptr = {k: v[0].data_ptr() for k, v in tree.items()}
+        zt, tt = padded(z), padded(todo0)
+        code = lib.gg_puct_root_noise(R, N, C, eps, zt[0].data_ptr(), tt[0].data_ptr(), ptr['boards'], ptr['prior'], ptr['stats'],
+                                      ptr['nodes'], stream)
+        assert code == 0
+        exp_todo = [ps.root_noise(wk, z[r], eps, int(todo0[r])) for r, wk in enumerate(work)]
+        exp = _want(work, N)
+        for k, (flat, n) in list(tree.items()) + [('noise', zt), ('todo', tt)]:
+            assert tail_ok(flat, n), (eps, k)
+        for k in BUFFERS:
+            assert np.array_equal(mc.to_np(tree[k][0][:tree[k][1]]), np.ascontiguousarray(exp[k]).view(np.int32).reshape(-1)), (eps, k)
+        got_todo = mc.to_np(tt[0][:R]).tolist()
+        assert got_todo == exp_todo, (eps, got_todo)
+        if eps == 0.25:
+            assert exp_todo == [0, 0, 0, 0, 1, 1, 0]
+        changed = [not np.array_equal(pe.bits(exp['prior'][r]), pe.bits(want['prior'][r])) for r in range(R)]
+        if eps == 1.0:
+            assert changed == [True, True, True, True, False, False, True], changed   # unevaluated and ended roots never
+            assert pe.bits(exp['prior'][0, 0, :8]).tolist() == pe.bits(np.array([0, 0, 0, np.inf, 0.5, 1, 0, 2.0 ** -130], np.float32)).tolist()
+        if eps == 0.0:
+            rest = ~np.isinf(z)                                         # 1 * prior + 0 * z: only 0 * inf shows
+            assert pe.bits(exp['prior'][0, 0, 3:4])[0] == 0x7FC00000
+            assert np.array_equal(pe.bits(exp['prior'][:, 0])[rest], pe.bits(want['prior'][:, 0])[rest])
+
+
+def _selfplay_noise(R_total):
+    def full(mv, rows=slice(None)):
+        return lambda m, legal: _odd_noise(R_total, mc.to_np(legal).shape[1], salt=m)[rows]
+    return full
+
+
+def _check_selfplay(got, e, tag, states=True):
+    for k in ('actions', 'pi', 'value', 'outcome', 'lengths', 'final_states') + (('states',) if states else ()):
+        _same_bits(getattr(got, k), e[k], (tag, k))
+
+
+SELFPLAY = [(5, None, 'hash', 12, 0, None), (5, 4, 'hash', 6, 2, None), (5, None, 'hostile', 12, 5, 200), (5, 1, 'pass', 8, 2, 60),
+            (9, 4, 'hash', 4, 2, None), (9, None, 'hash', 10, 5, 120), (9, 1, 'hostile', 8, 0, None)]
+
+
+@pytest.mark.parametrize('N,L,name,T,sample_moves,capacity', SELFPLAY)
+def test_selfplay_equals_expected_selfplay(N, L, name, T, sample_moves, capacity):
+    from gymgo_amd import gogame
+    M, komi = 5, 0.5
+    ev_np, ev_t = EVALUATORS[name]
+    c = 1e6 if name == 'pass' else (0.6 if N == 5 else 1.25)
+    roots = _roots(N, 21)
+    R = roots.shape[0]
+    noise = _selfplay_noise(R)(0)
+    e = ps.expected_selfplay(roots, M, T, ev_np, c=c, komi=komi, leaves=L, capacity=capacity, noise=noise, eps=0.25,
+                             sample_moves=sample_moves, seed=7, first_game=2)
+    if name == 'pass':                                                  # games that end inside the five moves
+        mid = (e['lengths'] > 0) & (e['lengths'] < M)
+        assert mid.any() and (e['outcome'][mid] != 0).all() and (e['actions'][mid, -1] == -1).all()
+    assert (e['lengths'] == 0).any() and (name == 'pass' or (e['lengths'] == M).any())
+    got = gogame.puct_selfplay(mc.to_dev(roots), M, T, ev_t, c=c, komi=komi, leaves=L, capacity=capacity, noise=noise, eps=0.25,
+                               sample_moves=sample_moves, seed=7, first_game=2, record_states=True)
+    assert isinstance(got, gogame.SelfPlay) and all(x.is_cuda for x in got)
+    _check_selfplay(got, e, (N, L, name))
+    # the recorded states are what batch_play_moves makes of the roots and the actions
+    for mv in range(M):
+        replay = mc.to_dev(roots)
+        if mv:
+            gogame.batch_play_moves(replay, got.actions[:, :mv].clamp(min=0) * (got.actions[:, :mv] >= 0)
+                                    + (got.actions[:, :mv] < 0) * (N * N + 5))
+        assert np.array_equal(mc.to_np(replay), mc.to_np(got.states[:, mv])), mv
+    plain = gogame.puct_selfplay(mc.to_dev(roots), M, T, ev_t, c=c, komi=komi, leaves=L, capacity=capacity, noise=noise, eps=0.25,
+                                 sample_moves=sample_moves, seed=7, first_game=2)
+    assert plain.states is None
+    _check_selfplay(plain, e, (N, L, name, 'plain'), states=False)
+
+
+def test_selfplay_without_noise_and_sampling_is_puct_play():
+    from gymgo_amd import gogame
+    N, T, M, L = 9, 8, 4, 2
+    roots = _roots(N, 12)
+    acts, final = gogame.puct_play(mc.to_dev(roots), M, T, pe.hash_evaluator_t, komi=0.5, leaves=L, capacity=80)
+    got = gogame.puct_selfplay(mc.to_dev(roots), M, T, pe.hash_evaluator_t, komi=0.5, leaves=L, capacity=80)
+    assert np.array_equal(mc.to_np(got.actions), mc.to_np(acts)) and np.array_equal(mc.to_np(got.final_states), mc.to_np(final))
+    e = ps.expected_selfplay(roots, M, T, pe.hash_evaluator_np, komi=0.5, leaves=L, capacity=80)
+    _check_selfplay(got, e, 'plain', states=False)
+
+
+def test_selfplay_shards_stream_and_numpy():
+    import torch
+    from gymgo_amd import gogame
+    N, T, M, L = 5, 6, 5, 2
+    roots = _roots(N, 33)
+    R = roots.shape[0]
+    full = _selfplay_noise(R)
+    kw = dict(c=0.6, komi=0.5, leaves=L, capacity=60, eps=0.5, sample_moves=M, seed=123)
+    e = ps.expected_selfplay(roots, M, T, pe.hash_evaluator_np, noise=full(0), first_game=10, **kw)
+    whole = gogame.puct_selfplay(mc.to_dev(roots), M, T, pe.hash_evaluator_t, noise=full(0), first_game=10, record_states=True, **kw)
+    _check_selfplay(whole, e, 'whole')
+    parts = [gogame.puct_selfplay(mc.to_dev(roots[a:b]), M, T, pe.hash_evaluator_t, noise=full(0, slice(a, b)), first_game=10 + a,
+                                  record_states=True, **kw) for a, b in ((0, 3), (3, R))]
+    for k in gogame.SelfPlay._fields:                                   # shards by root concatenate to the whole
+        assert torch.equal(torch.cat([getattr(p, k) for p in parts]), getattr(whole, k)), k
+    other = gogame.puct_selfplay(mc.to_dev(roots), M, T, pe.hash_evaluator_t, noise=full(0), first_game=11, **kw)
+    assert not torch.equal(other.actions, whole.actions)               # (another generator: other games)
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        on_side = gogame.puct_selfplay(mc.to_dev(roots), M, T, pe.hash_evaluator_t, noise=full(0), first_game=10, **kw)
+    side.synchronize()
+    _check_selfplay(on_side, e, 'stream', states=False)
+    as_np = gogame.puct_selfplay(roots.astype(np.float64), M, T, pe.hash_evaluator_t, noise=full(0), first_game=10,
+                                 record_states=True, **kw)
+    assert all(isinstance(x, np.ndarray) for x in as_np)
+    _check_selfplay(as_np, e, 'numpy')
+    s = gogame.PuctSearch(roots, T, komi=0.5)
+    for _ in range(T):
+        s.backup(*pe.hash_evaluator_t(*s.select()))
+    acts, pi, val = s.root_policy()
+    assert isinstance(acts, np.ndarray) and acts.dtype == np.int64 and pi.dtype == np.float32 and val.dtype == np.float32
+    assert np.array_equal(acts, pe.most_visited(s.result()))
+
+
+def test_dirichlet_noise_properties():
+    import torch
+    from gymgo_amd import gogame
+    N = 9
+    roots = _roots(N, 8)
+    legal = torch.from_numpy(mc.legal_mask(roots)).cuda()
+    gen = torch.Generator(device='cuda').manual_seed(3)
+    for alpha in (0.03, 0.3, 10.0):
+        noise = gogame.dirichlet_noise(alpha, generator=gen)
+        for mv in range(2):
+            z = noise(mv, legal)
+            assert z.is_cuda and z.dtype == torch.float32 and tuple(z.shape) == tuple(legal.shape)
+            assert bool((z >= 0).all()) and not bool(z[~legal].any())
+            sums = z.double().sum(dim=1)
+            live = legal.any(dim=1)
+            # (the row sum is a float32 sum of A = 82 terms, each quotient one more rounding: below 83 * 2^-24 = 5e-6)
+            assert bool(((sums - 1).abs() < 1e-5)[live].all()) and not bool(sums[~live].any()) and bool((~live).any())
+    s = gogame.PuctSearch(mc.to_dev(roots), 4, komi=0.5)
+    s.backup(*pe.hash_evaluator_t(*s.select()))
+    before = mc.to_np(s._prior[:, 0]).copy()
+    todo = s.add_root_noise(gogame.dirichlet_noise(0.3, generator=gen)(0, s.result().legal))
+    after = mc.to_np(s._prior[:, 0])
+    live = mc.to_np(legal.any(dim=1))
+    assert mc.to_np(todo).tolist() == [0 if x else 1 for x in live]
+    assert (np.abs(after.sum(axis=1) - (0.75 * before.sum(axis=1) + 0.25))[live] < 1e-4).all() and not after[~mc.to_np(legal)].any()

@@ -30,9 +30,20 @@ Workload: R mid-game roots (random play from the empty board, `--plies` plies), 
   root visits after the move's search.  --no-reuse starts every move from a new PuctSearch (the same rounds per move).
   --evaluator peaked: fixed preallocated priors that fall geometrically with the action index (ratio 1/2), values 0.
   For the kernel's device time: `rocprofv3 --kernel-trace --stats -- python tools/bench_puct.py --moves M --reps 1 ...`.
+
+  --selfplay --moves M [--leaves L] [--alpha 0.03] [--eps 0.25]: gogame.puct_selfplay (the kept tree with room for
+  `--capacity-factor` times the default, Dirichlet noise by add_root_noise, every move drawn from the visit counts, the
+  records on the device, no synchronisation) against what a caller could do without it: a new PuctSearch per move
+  (puct_play's reuse=False loop), the same noise mixed into the priors by the evaluator on its first call of every move,
+  result() read back per move, pi and the draw on the host.  Null evaluator, `--iters` rounds per move; both alternate in
+  one process, wall seconds (host clock around the call and a synchronisation) as the median of `--reps`.  The two play
+  different games (kept trees, other generators): the figure is the cost of a move, not a strength.  For the device time
+  of k_puct_root_noise / k_puct_root_policy: `rocprofv3 --kernel-trace --stats -- python tools/bench_puct.py --selfplay
+  --moves M --reps 1 ...`.
 """
 import argparse
 import json
+import time
 
 from mc_bench import median_timed, mid_game_roots, timed   # (puts the repository on sys.path)
 
@@ -53,9 +64,14 @@ def main():
     ap.add_argument('--reuse', dest='reuse', action='store_true', default=True)
     ap.add_argument('--no-reuse', dest='reuse', action='store_false')
     ap.add_argument('--capacity-factor', type=int, default=2)
+    ap.add_argument('--selfplay', action='store_true')
+    ap.add_argument('--alpha', type=float, default=0.03)
+    ap.add_argument('--eps', type=float, default=0.25)
     args = ap.parse_args()
     if args.evaluator == 'peaked' and args.moves is None:
         ap.error('--evaluator peaked needs --moves')
+    if args.selfplay and (args.moves is None or args.evaluator != 'null'):
+        ap.error('--selfplay needs --moves and the null evaluator')
 
     import torch
     from gymgo_amd import gogame, _lib
@@ -67,6 +83,10 @@ def main():
         for I in args.iters or ([64, 800] if null else [64]):
             base = {'size': N, 'roots': R, 'iterations': I, 'root_plies': args.plies, 'c': args.c,
                     'cus': int(_lib.lib().gg_device_cus()), 'reps': args.reps}
+            if args.selfplay:
+                for L in args.leaves or [None]:
+                    print(json.dumps(_selfplay(args, gogame, torch, roots, base, L)), flush=True)
+                continue
             if args.moves is not None:
                 for L in args.leaves or [None]:
                     for res in _moves(args, gogame, torch, roots, base, L):
@@ -218,6 +238,64 @@ def _moves(args, gogame, torch, roots, base, L):
                    nodes_before=float(nodes_before.mean()), kept_nodes=float(kept.mean()),
                    share_nodes_kept=float((kept / nodes_before).mean()), share_visits_kept=float((best / visits_before).mean()),
                    kept_visits=float(best.mean()), tree_full=float((nodes_before >= capacity).double().mean()))
+
+
+def _selfplay(args, gogame, torch, roots, base, L):
+    """The --selfplay comparison: one result."""
+    import numpy as np
+    R, N, T, M = base['roots'], base['size'], base['iterations'], args.moves
+    A, B = N * N + 1, R * (L or 1)
+    capacity = args.capacity_factor * T * (L or 1) + 1
+    priors = torch.full((B, A), 1.0 / A, dtype=torch.float32, device='cuda:0')
+    values = torch.zeros(B, dtype=torch.float32, device='cuda:0')
+    null = lambda states, legal: (priors, values)
+    noise = gogame.dirichlet_noise(args.alpha)
+
+    def ours():
+        return gogame.puct_selfplay(roots, M, T, null, c=args.c, komi=7.5, leaves=L, capacity=capacity, noise=noise, eps=args.eps,
+                                    sample_moves=M)
+
+    def theirs():
+        states, host_rng = roots, np.random.default_rng(1)
+        acts, pis = np.zeros((R, M), np.int64), np.zeros((R, M, A), np.float32)
+        for mv in range(M):
+            search = gogame.PuctSearch(states, T, c=args.c, komi=7.5, leaves=L)
+            for t in range(T):
+                st, legal = search.select()
+                p = priors
+                if t == 0:   # round 0 hands out the roots (slot 0 of every root): the only place noise can go
+                    rows = slice(None, None, L or 1)
+                    p = priors.clone()
+                    p[rows] = (1 - args.eps) * p[rows] + args.eps * noise(mv, legal[rows])
+                search.backup(p, values)
+            visits = search.result().visits.cpu().numpy().astype(np.float64)   # (the synchronisation)
+            total = visits.sum(axis=1, keepdims=True)
+            pi = np.divide(visits, total, out=np.zeros_like(visits), where=total > 0)
+            pis[:, mv] = pi
+            cum = np.cumsum(pi, axis=1)
+            draw = (cum < host_rng.random((R, 1))).sum(axis=1).clip(max=A - 1)
+            acts[:, mv] = np.where(total[:, 0] > 0, draw, -1)
+            states = search._played_states(torch.from_numpy(acts[:, mv]).to('cuda:0'))
+        return acts, pis, states
+
+    def wall(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, out
+
+    wall(ours), wall(theirs)   # warm-up
+    ta, tb = [], []
+    for _ in range(args.reps):
+        ta.append(wall(ours))
+        tb.append(wall(theirs))
+    med = lambda ts: sorted(t for t, _ in ts)[len(ts) // 2]
+    rec = ta[-1][1]
+    return dict(base, metric='puct_selfplay_wall_s', evaluator='null', leaves=L, rounds=T, moves=M, capacity=capacity,
+                alpha=args.alpha, eps=args.eps, seconds_selfplay=med(ta), seconds_fresh_search_host_pi=med(tb),
+                ratio=med(tb) / med(ta), ms_per_move_selfplay=med(ta) / M * 1e3, ms_per_move_fresh=med(tb) / M * 1e3,
+                mean_length=float(rec.lengths.double().mean()), pi_bytes=4 * R * M * A)
 
 
 def _mean_leaf_depth(parent, nodes):
