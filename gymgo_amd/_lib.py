@@ -26,7 +26,8 @@ EXPORTS = (
     'gg_uct_backup', 'gg_batch_eye_mask', 'gg_batch_rollout_tracked_policy', 'gg_playouts_advance_policy',
     'gg_move_playouts_advance_policy', 'gg_puct_begin', 'gg_puct_select', 'gg_puct_backup',
     'gg_puct_select_leaves', 'gg_puct_backup_leaves', 'gg_puct_legal', 'gg_puct_advance', 'gg_batch_rollout_ws',
-    'gg_puct_root_noise', 'gg_puct_root_policy',
+    'gg_puct_root_noise', 'gg_puct_root_policy', 'gg_feature_planes', 'gg_batch_group_liberties', 'gg_batch_features',
+    'gg_batch_features_tracked',
 )
 
 _vp, _i64, _i32, _u64 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_uint64
@@ -94,6 +95,10 @@ _SIGNATURES = {
     'gg_puct_advance': ([_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
     'gg_puct_root_noise': ([_i64, _i32, _i32, ctypes.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
     'gg_puct_root_policy': ([_i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
+    'gg_feature_planes': ([], _i32),
+    'gg_batch_group_liberties': ([_vp, _vp, _i64, _i32, _vp], _i32),
+    'gg_batch_features': ([_vp, _vp, _i32, _i64, _i32, _vp], _i32),
+    'gg_batch_features_tracked': ([_vp, _vp, _i32, _i64, _i32, _vp], _i32),
 }
 
 _lib = None

@@ -50,6 +50,9 @@ void launch_rollout5_policy(int N, uint8_t *st, uint64_t *rng, int32_t *last_act
                             int plies, int auto_reset, int nb, int grid, hipStream_t s);
 void launch_rollout_lat_policy(uint8_t *st, uint64_t *rng, int32_t *last_actions, int64_t *steps_done, int64_t B, int32_t N, int plies,
                                int auto_reset, hipStream_t s);
+// gg_feat.hip: the feature-plane kernels (gg_feat.h)
+void launch_features(bool tracked, const void *in, void *out, int dtype, int64_t B, int32_t N, int cus, hipStream_t s);
+void launch_group_liberties(const uint8_t *states, uint8_t *libs, int64_t B, int32_t N, int cus, hipStream_t s);
 }
 
 namespace {
@@ -1157,6 +1160,34 @@ int32_t gg_batch_eye_mask(const uint8_t *states, uint8_t *mask, int64_t B, int32
   if (!mask) return GG_E_NULLPTR;
   const int64_t blocks = (B * N * N + 255) / 256;
   k_eye_mask<<<(unsigned)(blocks < (int64_t)cus * 64 ? blocks : (int64_t)cus * 64), 256, 0, s>>>(states, mask, B, N);
+  return (int32_t)hipGetLastError();
+}
+
+// ---- network input planes with per-group liberty counts (gg_feat.h; the launches: gg_feat.hip)
+int32_t gg_feature_planes(void) { return 16; }   // kFeatPlanes of gg_feat.h
+
+int32_t gg_batch_group_liberties(const uint8_t *states, uint8_t *libs, int64_t B, int32_t N, void *hip_stream) {
+  GG_ENTER(states);
+  if (!libs) return GG_E_NULLPTR;
+  launch_group_liberties(states, libs, B, N, cus, s);
+  return (int32_t)hipGetLastError();
+}
+
+int32_t gg_batch_features(const uint8_t *states, void *out, int32_t out_dtype, int64_t B, int32_t N, void *hip_stream) {
+  if (out_dtype < GG_W_F32 || out_dtype > GG_FEAT_U8) return GG_E_BADSIZE;
+  GG_ENTER(states);
+  if (!out) return GG_E_NULLPTR;
+  if ((uintptr_t)out & 15u) return GG_E_BADARG;
+  launch_features(false, states, out, out_dtype, B, N, cus, s);
+  return (int32_t)hipGetLastError();
+}
+
+int32_t gg_batch_features_tracked(const uint32_t *tracked, void *out, int32_t out_dtype, int64_t B, int32_t N, void *hip_stream) {
+  if (out_dtype < GG_W_F32 || out_dtype > GG_FEAT_U8) return GG_E_BADSIZE;
+  GG_ENTER(tracked);
+  if (!out) return GG_E_NULLPTR;
+  if ((uintptr_t)out & 15u) return GG_E_BADARG;
+  launch_features(true, tracked, out, out_dtype, B, N, cus, s);
   return (int32_t)hipGetLastError();
 }
 

@@ -805,6 +805,113 @@ def eye_mask(state):
     return _back(box, batch_eye_mask(box.t[None]), row0=True)
 
 
+# ---------------------------------------------------------------- network input planes with per-group liberty counts
+FEATURE_PLANES = 16   # gg_feature_planes() of include/gymgo_amd.h
+FEATURE_NAMES = ('own', 'opponent', 'own_libs_1', 'own_libs_2', 'own_libs_3', 'own_libs_4plus', 'opp_libs_1', 'opp_libs_2',
+                 'opp_libs_3', 'opp_libs_4plus', 'legal', 'ko', 'capture', 'black_to_move', 'prev_pass', 'ones')
+FEATURE_DTYPES = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2, torch.uint8: 3}   # GG_W_* / GG_FEAT_U8
+
+
+def _feature_dtype(dtype):
+    """The C code of a plane dtype; ValueError for anything but the four of FEATURE_DTYPES (before a device is touched)."""
+    if not isinstance(dtype, torch.dtype) or dtype not in FEATURE_DTYPES:
+        raise ValueError('dtype must be torch.uint8, float16, bfloat16 or float32 (got %r)' % (dtype,))
+    return FEATURE_DTYPES[dtype]
+
+
+def _feature_out(out, shape, dtype, device=None):
+    """out=None, or a contiguous 16-byte aligned device tensor of exactly this shape and dtype (on `device` when given)."""
+    if out is None:
+        return
+    if (not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != dtype or tuple(out.shape) != tuple(shape)
+            or not out.is_contiguous() or out.data_ptr() % 16 or (device is not None and out.device != device)):
+        raise ValueError('out must be a contiguous, 16-byte aligned %s %s tensor on the states\' device (got %s)' % (
+            dtype, list(shape), '%s %s on %s' % (out.dtype, list(out.shape), out.device) if isinstance(out, torch.Tensor) else type(out)))
+
+
+def _states_shape(x, what='batch_states'):
+    """(B, N) of a [B, 6, N, N] tensor or array; ValueError otherwise (before a device is touched)."""
+    shape = tuple(x.shape) if isinstance(x, torch.Tensor) else np.shape(x)
+    if len(shape) != 4 or shape[1] != govars.NUM_CHNLS or shape[2] != shape[3]:
+        raise ValueError('%s must be [B, 6, N, N] (got %s)' % (what, shape))
+    return shape[0], shape[2]
+
+
+def batch_group_liberties(batch_states):
+    """The liberties of the group of the stone at every point -> uint8 [B, N, N] (gg_batch_group_liberties): a group is a
+    maximal orthogonally connected set of stones of one colour, its liberties are the distinct empty points next to any of
+    its stones; the count is exact up to 255 (saturated there) and 0 at empty points.  The per-group counterpart of
+    `liberties` / `num_liberties`, which dilate a whole colour.  One launch; device memory of the result: B * N^2 bytes."""
+    B, N = _states_shape(batch_states)
+    box = _Box(batch_states)
+    st = box.t
+    libs = torch.empty((B, N, N), dtype=_U8, device=st.device)
+    code = _lib.lib().gg_batch_group_liberties(_lib.dev_ptr(st, _U8, 'states'), _lib.dev_ptr(libs, _U8, 'libs'), B, N,
+                                               _lib.stream_ptr(st.device))
+    _lib.check(code, 'gg_batch_group_liberties')
+    return _back(box, libs)
+
+
+def group_liberties(state):
+    """batch_group_liberties of one state [6, N, N] -> uint8 [N, N]."""
+    box = _Box(state)
+    return _back(box, batch_group_liberties(box.t[None]), row0=True)
+
+
+def batch_features(batch_states, dtype=torch.float16, out=None):
+    """Network input planes of every board -> [B, 16, N, N] of `dtype` (gg_batch_features), from the mover's point of view
+    ("own" = the player to move).  Plane by plane (FEATURE_NAMES), each value exactly 0 or 1:
+       0      own stone                      1      opponent stone
+       2 - 5  own stone whose group has exactly 1 / exactly 2 / exactly 3 / >= 4 liberties (a hand-made group with none: no plane)
+       6 - 9  the same for opponent stones
+      10      legal point: empty, plane 3 (invalid) clear, game not over
+      11      ko point: empty, plane 3 set, game not over, next to an opponent group with exactly one liberty (this point)
+      12      capturing point: legal and next to an opponent group with exactly one liberty
+      13      all ones iff the mover is black      14      all ones iff the previous move was a pass      15      all ones
+    Groups and liberties as in batch_group_liberties.  Exact: every group is counted by a flood of its own on the device;
+    plane 3 of the input is taken as given.  dtype: torch.uint8, float16, bfloat16 or float32 (ValueError otherwise; 0 and 1
+    are exact in all four).  out: a contiguous, 16-byte aligned device tensor of that shape and dtype to write into.  NumPy in
+    gives NumPy out (through the device; not for bfloat16, which NumPy lacks).  One launch; device memory of the result:
+    16 * B * N^2 elements - 11.5 KB per 19x19 board in a 16-bit dtype."""
+    code = _feature_dtype(dtype)
+    B, N = _states_shape(batch_states)
+    _feature_out(out, (B, FEATURE_PLANES, N, N), dtype)
+    if not isinstance(batch_states, torch.Tensor) and dtype == torch.bfloat16:
+        raise ValueError('NumPy has no bfloat16: pass a device tensor, or another dtype')
+    box = _Box(batch_states)
+    st = box.t
+    _feature_out(out, (B, FEATURE_PLANES, N, N), dtype, st.device)
+    planes = out if out is not None else torch.empty((B, FEATURE_PLANES, N, N), dtype=dtype, device=st.device)
+    _lib.check(_lib.lib().gg_batch_features(_lib.dev_ptr(st, _U8, 'states'), _lib.dev_ptr(planes, dtype, 'out'), code, B, N,
+                                            _lib.stream_ptr(st.device)), 'gg_batch_features')
+    return _back(box, planes)
+
+
+def features(state, dtype=torch.float16):
+    """batch_features of one state [6, N, N] -> [16, N, N]."""
+    _feature_dtype(dtype)
+    if not isinstance(state, torch.Tensor) and dtype == torch.bfloat16:
+        raise ValueError('NumPy has no bfloat16: pass a device tensor, or another dtype')
+    box = _Box(state)
+    return _back(box, batch_features(box.t[None], dtype), row0=True)
+
+
+def batch_features_tracked(tracked, dtype=torch.float16, out=None):
+    """batch_features of tracked boards (int32 [B, 5N+1], a device tensor) -> [B, 16, N, N] of `dtype`
+    (gg_batch_features_tracked): bit for bit what batch_features gives for batch_untrack(tracked) - the search's leaf
+    boards go to the network without the byte planes in between.  dtype, out, exactness and device memory: batch_features."""
+    code = _feature_dtype(dtype)
+    if not isinstance(tracked, torch.Tensor) or tracked.dim() != 2:
+        raise ValueError('tracked boards are int32 [B, 5N+1] device tensors')
+    N = _tracked_size(tracked)
+    B = tracked.shape[0]
+    _feature_out(out, (B, FEATURE_PLANES, N, N), dtype, tracked.device if tracked.is_cuda else None)
+    planes = out if out is not None else torch.empty((B, FEATURE_PLANES, N, N), dtype=dtype, device=tracked.device)
+    _lib.check(_lib.lib().gg_batch_features_tracked(_lib.dev_ptr(tracked, _I32, 'tracked'), _lib.dev_ptr(planes, dtype, 'out'), code,
+                                                    B, N, _lib.stream_ptr(tracked.device)), 'gg_batch_features_tracked')
+    return planes
+
+
 def batch_play_moves_tracked(tracked, moves, played=None):
     """IN PLACE batch_play_moves on tracked boards; moves [B, T] (T = 1: one GoEnv.step per game) -> played int32 [B]."""
     N = _tracked_size(tracked)
@@ -1322,9 +1429,16 @@ class PuctSearch:
 
     add_root_noise(noise, eps, todo) and root_policy(sample, rng) are what a self-play loop needs on top (puct_selfplay is
     that loop): exploration noise in the root's priors, the move by the most visits or drawn in proportion to them, and
-    the policy target and root value, all on the device."""
+    the policy target and root value, all on the device.
 
-    def __init__(self, batch_states, iterations, c=1.25, komi=0.0, leaves=None, capacity=None):
+    features (None = everything above, launch for launch; or a dtype of batch_features): select() returns (planes, legal)
+    with planes [R, 16, N, N] ([R * L, ..] with leaves=L) of that dtype - batch_features of the leaves, made from the tracked
+    leaf boards by gg_batch_features_tracked - instead of (states, legal).  With leaves=L that launch REPLACES the untrack
+    of the leaf boards; on the one-leaf path `legal` comes from the untracked states, so it is one launch more.  Rows of
+    empty slots hold the planes of whatever board their row holds.  Device memory: 16 N^2 elements per row handed out."""
+
+    def __init__(self, batch_states, iterations, c=1.25, komi=0.0, leaves=None, capacity=None, features=None):
+        self._feat = None if features is None else (features, _feature_dtype(features))
         self._box = batch_states if isinstance(batch_states, _Box) else _Box(batch_states)   # (a _Box: puct_play's own states)
         st = self._box.t
         if st.dim() != 4 or st.shape[1] != govars.NUM_CHNLS or st.shape[2] != st.shape[3]:
@@ -1355,6 +1469,8 @@ class PuctSearch:
         self._states = torch.empty((R, govars.NUM_CHNLS, N, N), dtype=_U8, device=dev)
         self._legal = torch.empty((R, A), dtype=torch.bool, device=dev)
         self._done, self._pending = 0, False
+        if self._feat is not None:
+            self._planes = torch.empty((R, FEATURE_PLANES, N, N), dtype=self._feat[0], device=dev)
         if not R:   # no device work at all: select / backup only keep the call order
             return
         p = _lib.dev_ptr
@@ -1380,7 +1496,10 @@ class PuctSearch:
         self._leaf = torch.empty((B, W), dtype=_I32, device=dev)
         self._move = torch.empty(B, dtype=_I32, device=dev)
         self._leaf_id = torch.empty(B, dtype=_I32, device=dev)
-        self._states = torch.empty((B, govars.NUM_CHNLS, N, N), dtype=_U8, device=dev)
+        if self._feat is None:
+            self._states = torch.empty((B, govars.NUM_CHNLS, N, N), dtype=_U8, device=dev)
+        else:   # (the leaves go out as planes: no byte-plane buffer)
+            self._states = self._planes = torch.empty((B, FEATURE_PLANES, N, N), dtype=self._feat[0], device=dev)
         self._legal = torch.empty((B, A), dtype=torch.bool, device=dev)
         self.live = torch.zeros((R, L), dtype=torch.bool, device=dev)
         self._done, self._pending = 0, False
@@ -1390,7 +1509,7 @@ class PuctSearch:
         self._tree = (p(self._boards, _I32, 'boards'), p(self._child, _I32, 'child'), p(self._prior, torch.float32, 'prior'),
                       p(self._links, _I32, 'links'), p(self._stats, _I32, 'stats'), p(self._nodes, _I32, 'nodes'))
         self._out = (p(self._leaf, _I32, 'leaf'), p(self._move, _I32, 'move'), p(self._leaf_id, _I32, 'leaf_id'))
-        self._hand = (p(self._states, _U8, 'states'), p(self._legal, torch.bool, 'legal'), p(self.live, torch.bool, 'live'))
+        self._hand = (p(self._states, self._states.dtype, 'states'), p(self._legal, torch.bool, 'legal'), p(self.live, torch.bool, 'live'))
         _lib.check(_lib.lib().gg_puct_begin(p(_track_roots(st), _I32, 'roots'), R, N, C, *self._tree,
                                             _lib.current_raw_stream(dev)), 'gg_puct_begin')
 
@@ -1406,7 +1525,10 @@ class PuctSearch:
             sp, gp, vp = self._hand
             _lib.check(lib.gg_puct_select_leaves(R, N, self._C, L, self._c, *self._tree, lp, mp, ip, stream), 'gg_puct_select_leaves')
             _lib.check(lib.gg_batch_play_moves_tracked(lp, mp, None, R * L, N, 1, stream), 'gg_batch_play_moves_tracked')
-            _lib.check(lib.gg_batch_untrack_states(lp, sp, R * L, N, stream), 'gg_batch_untrack_states')
+            if self._feat is None:
+                _lib.check(lib.gg_batch_untrack_states(lp, sp, R * L, N, stream), 'gg_batch_untrack_states')
+            else:   # (sp: the planes)
+                _lib.check(lib.gg_batch_features_tracked(lp, sp, self._feat[1], R * L, N, stream), 'gg_batch_features_tracked')
             _lib.check(lib.gg_puct_legal(lp, ip, R * L, N, gp, vp, stream), 'gg_puct_legal')
         self._pending = True
         return self._states, self._legal
@@ -1427,7 +1549,7 @@ class PuctSearch:
 
     def select(self):
         """Step 1 and 2 of the next iteration -> (states uint8 [R, 6, N, N], legal bool [R, A]) of the R leaves ([R * L, ..]
-        with leaves=L)."""
+        with leaves=L); with features=dtype (planes [R, 16, N, N] of that dtype, legal)."""
         if self._pending:
             raise ValueError('PuctSearch.select(): the leaves of the last select() have not been backed up')
         if self._done >= self._I:
@@ -1444,8 +1566,11 @@ class PuctSearch:
                        'gg_batch_untrack_states')
             with torch.cuda.device(self._dev):
                 self._legal.copy_(_legal_roots(self._states))
+            if self._feat is not None:
+                _lib.check(L.gg_batch_features_tracked(lp, _lib.dev_ptr(self._planes, self._feat[0], 'planes'), self._feat[1], R, N,
+                                                       stream), 'gg_batch_features_tracked')
         self._pending = True
-        return self._states, self._legal
+        return (self._states if self._feat is None else self._planes), self._legal
 
     def backup(self, priors, values):
         """Step 4: priors float32 [R, A] and values float32 [R] (the value for the player to move at the leaf) of the leaves
@@ -1651,7 +1776,7 @@ class PuctSearch:
         return acts, p, v
 
 
-def batch_puct(batch_states, iterations, evaluator, c=1.25, komi=0.0, tree=False, leaves=None, capacity=None):
+def batch_puct(batch_states, iterations, evaluator, c=1.25, komi=0.0, tree=False, leaves=None, capacity=None, features=None):
     """PUCT search (the AlphaZero search) of `iterations` iterations from every root of batch_states ([R, 6, N, N]) with the
     caller's evaluator -> Puct (device tensors for a device tensor, NumPy arrays for NumPy input).  The loop over PuctSearch.
 
@@ -1695,9 +1820,15 @@ def batch_puct(batch_states, iterations, evaluator, c=1.25, komi=0.0, tree=False
 
     capacity (None: the sizes above): the nodes per root, an integer >= the default and < 2^31; the tree, its device memory
     and the PuctTree fields are then [R, capacity].  It changes no result of this call (the extra nodes stay unused): it is
-    PuctSearch.advance and puct_play that need the room."""
+    PuctSearch.advance and puct_play that need the room.
+
+    features (None: the search above, launch for launch; or torch.uint8 / float16 / bfloat16 / float32): the evaluator is
+    called as evaluator(planes, legal) with planes [R, 16, N, N] ([R * L, ..]) of that dtype - batch_features of the leaves,
+    written by one launch from the tracked leaf boards (PuctSearch) - instead of the byte-plane states.  An evaluator that
+    needs states (playout_evaluator: its attribute needs_states) is refused with ValueError."""
     _puct_komi_guard(evaluator, komi)
-    search = PuctSearch(batch_states, iterations, c, komi, leaves=leaves, capacity=capacity)
+    _puct_features_guard(evaluator, features)
+    search = PuctSearch(batch_states, iterations, c, komi, leaves=leaves, capacity=capacity, features=features)
     for _ in range(search._I):
         states, legal = search.select()
         priors, values = evaluator(states, legal)
@@ -1711,7 +1842,14 @@ def _puct_komi_guard(evaluator, komi):
         raise ValueError('the evaluator scores its playouts with komi %r, the search its ended leaves with %r' % (ek, komi))
 
 
-def puct_play(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, leaves=None, capacity=None, reuse=True):
+def _puct_features_guard(evaluator, features):
+    if features is not None:
+        _feature_dtype(features)
+        if getattr(evaluator, 'needs_states', False):   # (playout_evaluator plays on from the byte planes)
+            raise ValueError('the evaluator needs states (needs_states), the search hands out feature planes (features=%r)' % (features,))
+
+
+def puct_play(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, leaves=None, capacity=None, reuse=True, features=None):
     """Play `moves` moves from every root of batch_states ([R, 6, N, N]) with a PUCT search per move -> (actions int64
     [R, moves], the final states uint8 [R, 6, N, N]); device tensors for a device tensor, NumPy arrays for NumPy input.
     Per move: `iterations` rounds of PuctSearch (batch_puct's loop, with `leaves` and `capacity` as there), the move of
@@ -1728,12 +1866,14 @@ def puct_play(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, leav
     room for the moves to come; no finite capacity excludes a full tree over many moves, and PuctSearch.result().nodes
     shows how full the trees are.  A kept root is already evaluated and is not handed out again, so root noise that the
     evaluator adds would reach only fresh roots: PuctSearch.add_root_noise reaches kept roots too, and puct_selfplay is this
-    loop with it, with moves drawn from the visit counts and with the training records."""
+    loop with it, with moves drawn from the visit counts and with the training records.  features: as batch_puct - the
+    evaluator gets (planes, legal)."""
     _puct_komi_guard(evaluator, komi)
+    _puct_features_guard(evaluator, features)
     moves = int(moves)
     if moves < 0:
         raise ValueError('need moves >= 0 (got %d)' % moves)
-    search = PuctSearch(batch_states, iterations, c, komi, leaves=leaves, capacity=capacity)
+    search = PuctSearch(batch_states, iterations, c, komi, leaves=leaves, capacity=capacity, features=features)
     box = search._box
     played = torch.empty((search._R, moves), dtype=_I64, device=box.t.device)
     for mv in range(moves):
@@ -1747,7 +1887,7 @@ def puct_play(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, leav
             search.advance(played[:, mv], check=False)
         else:   # only node 0's boards are played on: the tree goes, so no advance over it; the states stay on the device
             box.t = search._played_states(played[:, mv])
-            search = PuctSearch(box, iterations, c, komi, leaves=leaves, capacity=capacity)
+            search = PuctSearch(box, iterations, c, komi, leaves=leaves, capacity=capacity, features=features)
     return _back(box, played), box.back(search._root_states())
 
 
@@ -1782,7 +1922,7 @@ that ended, 0 for one still running), lengths (int32 [R]: moves played), final_s
 
 
 def puct_selfplay(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, leaves=None, capacity=None, noise=None,
-                  eps=0.25, sample_moves=0, seed=20260927, first_game=0, record_states=False):
+                  eps=0.25, sample_moves=0, seed=20260927, first_game=0, record_states=False, features=None):
     """Self-play games for training: `moves` moves from every root of batch_states ([R, 6, N, N]) with a PUCT search per move
     on the kept tree -> SelfPlay (device tensors for a device tensor, NumPy arrays for NumPy input).  puct_play's
     reuse=True loop (`iterations` rounds per move with `leaves` and `capacity` as there, then PuctSearch.advance) with
@@ -1802,8 +1942,10 @@ def puct_selfplay(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, 
     times and must score with the search's komi (batch_puct's guard).  Without record_states a trainer replays the
     positions from the roots with batch_play_moves(states, actions).  Device memory of the records: pi takes
     4 * R * moves * A bytes (189 MB for 1 024 roots x 128 moves at 19x19), states 6 N^2 * R * moves.  moves = 0 or R = 0:
-    no device call, empty records of these shapes."""
+    no device call, empty records of these shapes.  features: as batch_puct - the evaluator gets (planes, legal); the records
+    (states included) are unchanged, a trainer applies batch_features to the recorded positions."""
     _puct_komi_guard(evaluator, komi)
+    _puct_features_guard(evaluator, features)
     moves, sample_moves, eps = int(moves), int(sample_moves), float(eps)
     if moves < 0:
         raise ValueError('need moves >= 0 (got %d)' % moves)
@@ -1829,7 +1971,7 @@ def puct_selfplay(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, 
     before = torch.empty((R, moves, govars.NUM_CHNLS, N, N), dtype=_U8, device=dev) if record_states else None
     if not R or not moves:
         return _back(box, SelfPlay(played, pis, vals, outcome, lengths, st, before))
-    search = PuctSearch(box, I, c, komi, leaves=leaves, capacity=capacity)
+    search = PuctSearch(box, I, c, komi, leaves=leaves, capacity=capacity, features=features)
     rng = rng_seed(R, seed, first_game, device=dev)
     ones, todo = torch.ones(R, dtype=_U8, device=dev), torch.empty(R, dtype=_U8, device=dev)
     for mv in range(moves):
@@ -1906,6 +2048,7 @@ def playout_evaluator(playouts, max_plies=None, seed=20260927, first_root=0, pol
 
     evaluate.plies_sum = None
     evaluate.komi = komi
+    evaluate.needs_states = True   # (it plays on from the byte planes: batch_puct refuses it together with features=)
     return evaluate
 
 

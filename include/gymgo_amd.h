@@ -676,6 +676,44 @@ int32_t gg_puct_root_policy(int64_t R, int32_t N, int32_t C, const uint8_t *samp
                             const int32_t *child, const gg_puct_stat *stats, const int32_t *nodes, int32_t *actions, float *pi,
                             float *value, void *hip_stream);
 
+/*
+ * Network input planes with per-group liberty counts: what an evaluator of gg_puct_* is fed, from byte planes or from the
+ * tracked leaf boards, in one launch.  A GROUP is a maximal orthogonally connected set of stones of one colour, its
+ * LIBERTIES are the distinct empty points orthogonally adjacent to any of its stones.  OWN = the player to move (plane 2 /
+ * flag bit 0), OPPONENT = the other colour.  F = gg_feature_planes() = 16 planes per board, out [B][16][N][N], every
+ * element exactly 0 or 1:
+ *    0       own stone
+ *    1       opponent stone
+ *    2 - 5   own stone whose group has exactly 1 / exactly 2 / exactly 3 / >= 4 liberties (a stone of a hand-made group
+ *            without liberties sets none of them)
+ *    6 - 9   the same for opponent stones
+ *   10       legal point: empty, plane 3 (invalid) clear, game not over
+ *   11       ko point: empty, plane 3 set, game not over, and some orthogonally adjacent OPPONENT group has exactly one
+ *            liberty (this point) - the ko is the only reason the rules refuse a capturing move (gym_go/gogame.py:72-75),
+ *            so this tells it from suicide
+ *   12       capturing point: plane 10 set and some adjacent opponent group has exactly one liberty
+ *   13       every point, iff the mover is black
+ *   14       every point, iff the previous move was a pass
+ *   15       every point
+ * Plane 3 of the input (the invalid row set of a tracked board) is taken as given, not recomputed.  Every group is counted
+ * by a flood of its own whatever the input form - the class rows of a tracked board are not read - so
+ * gg_batch_features_tracked of gg_batch_track_states(s) equals gg_batch_features(s) bit for bit.
+ *   gg_batch_group_liberties   libs uint8 [B][N][N] = the number of liberties of the group of the stone at each point,
+ *                              saturated at 255; 0 at empty points.  The per-group counterpart of gogame.liberties /
+ *                              num_liberties (gym_go/gogame.py:231-262), which count per colour.
+ *   gg_batch_features          states uint8 [B][6][N][N] -> out [B][16][N][N] of out_dtype: GG_W_F32 / GG_W_BF16 / GG_W_F16
+ *                              or GG_FEAT_U8 (0 and 1 are exact in all four)
+ *   gg_batch_features_tracked  the same from tracked boards uint32 [B][gg_tracked_words(N)]
+ * out must be 16-byte aligned (a board's planes are a multiple of 16 bytes long: every store is an aligned 16-byte store;
+ * GG_E_BADARG otherwise).  Checks as gg_batch_eye_mask: GG_E_BADSIZE for N outside [2, 19], B < 0 or an out_dtype other
+ * than the four; B = 0 is no work; GG_E_NULLPTR.  Every call queues one launch on hip_stream and never synchronises.
+ */
+#define GG_FEAT_U8 3 /* uint8 elements (after GG_W_F32 / GG_W_BF16 / GG_W_F16) */
+int32_t gg_feature_planes(void);
+int32_t gg_batch_group_liberties(const uint8_t *states, uint8_t *libs, int64_t B, int32_t N, void *hip_stream);
+int32_t gg_batch_features(const uint8_t *states, void *out, int32_t out_dtype, int64_t B, int32_t N, void *hip_stream);
+int32_t gg_batch_features_tracked(const uint32_t *tracked, void *out, int32_t out_dtype, int64_t B, int32_t N, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

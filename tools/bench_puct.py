@@ -31,6 +31,9 @@ Workload: R mid-game roots (random play from the empty board, `--plies` plies), 
   --evaluator peaked: fixed preallocated priors that fall geometrically with the action index (ratio 1/2), values 0.
   For the kernel's device time: `rocprofv3 --kernel-trace --stats -- python tools/bench_puct.py --moves M --reps 1 ...`.
 
+  --features (null evaluator, with or without --leaves): the search hands out float16 feature planes (batch_puct(..,
+  features=torch.float16): gg_batch_features_tracked in the round) instead of byte-plane states; the evaluator ignores them.
+
   --selfplay --moves M [--leaves L] [--alpha 0.03] [--eps 0.25]: gogame.puct_selfplay (the kept tree with room for
   `--capacity-factor` times the default, Dirichlet noise by add_root_noise, every move drawn from the visit counts, the
   records on the device, no synchronisation) against what a caller could do without it: a new PuctSearch per move
@@ -67,6 +70,7 @@ def main():
     ap.add_argument('--selfplay', action='store_true')
     ap.add_argument('--alpha', type=float, default=0.03)
     ap.add_argument('--eps', type=float, default=0.25)
+    ap.add_argument('--features', action='store_true')
     args = ap.parse_args()
     if args.evaluator == 'peaked' and args.moves is None:
         ap.error('--evaluator peaked needs --moves')
@@ -99,7 +103,8 @@ def main():
             if null:
                 priors = torch.full((R, A), 1.0 / A, dtype=torch.float32, device='cuda:0')
                 values = torch.zeros(R, dtype=torch.float32, device='cuda:0')
-                run = lambda: gogame.batch_puct(roots, I, lambda states, legal: (priors, values), c=args.c, komi=7.5, tree=True)
+                run = lambda: gogame.batch_puct(roots, I, lambda states, legal: (priors, values), c=args.c, komi=7.5, tree=True,
+                                                features=torch.float16 if args.features else None)
                 ref = run()   # warm-up
                 assert bool((ref.root_visits == I).all())
                 (s, out), = median_timed(run, reps=args.reps)
@@ -146,7 +151,8 @@ def _leaves(args, gogame, torch, roots, base, null):
             values = torch.zeros(R * L, dtype=torch.float32, device='cuda:0')
             ev_l = lambda states, legal: (priors, values)
             ev_1 = lambda states, legal: (priors[:R], values[:R])
-            run_l = lambda: gogame.batch_puct(roots, T, ev_l, c=args.c, komi=7.5, tree=True, leaves=L)
+            run_l = lambda: gogame.batch_puct(roots, T, ev_l, c=args.c, komi=7.5, tree=True, leaves=L,
+                                              features=torch.float16 if args.features else None)
             run_1 = lambda: gogame.batch_puct(roots, I, ev_1, c=args.c, komi=7.5, tree=True)
             run_l(), run_1()   # warm-up
             (sl, ol), (s1, o1) = median_timed(run_l, run_1, reps=args.reps)
