@@ -27,7 +27,8 @@ EXPORTS = (
     'gg_move_playouts_advance_policy', 'gg_puct_begin', 'gg_puct_select', 'gg_puct_backup',
     'gg_puct_select_leaves', 'gg_puct_backup_leaves', 'gg_puct_legal', 'gg_puct_advance', 'gg_batch_rollout_ws',
     'gg_puct_root_noise', 'gg_puct_root_policy', 'gg_feature_planes', 'gg_batch_group_liberties', 'gg_batch_features',
-    'gg_batch_features_tracked',
+    'gg_batch_features_tracked', 'gg_batch_features_oriented', 'gg_batch_features_tracked_oriented', 'gg_batch_symmetry_policy',
+    'gg_batch_draw_orient',
 )
 
 _vp, _i64, _i32, _u64 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_uint64
@@ -99,6 +100,10 @@ _SIGNATURES = {
     'gg_batch_group_liberties': ([_vp, _vp, _i64, _i32, _vp], _i32),
     'gg_batch_features': ([_vp, _vp, _i32, _i64, _i32, _vp], _i32),
     'gg_batch_features_tracked': ([_vp, _vp, _i32, _i64, _i32, _vp], _i32),
+    'gg_batch_features_oriented': ([_vp, _vp, _vp, _i32, _i64, _i32, _vp], _i32),
+    'gg_batch_features_tracked_oriented': ([_vp, _vp, _vp, _i32, _i64, _i32, _vp], _i32),
+    'gg_batch_symmetry_policy': ([_vp, _vp, _vp, _i32, _i32, _i64, _i32, _vp], _i32),
+    'gg_batch_draw_orient': ([_vp, _vp, _i64, _vp], _i32),
 }
 
 _lib = None

@@ -552,4 +552,15 @@ static __global__ void k_rng_seed(uint64_t *rng, uint64_t base_seed, int64_t fir
   rng[i] = x;
 }
 
+// gg_batch_draw_orient: one orientation per row, one ply step of the generator above: orient = u >> 61 (the draw
+// ((u >> 32) * 8) >> 32 of gg_puct_root_policy with eight outcomes), the generator advances once
+static __global__ void k_draw_orient(uint64_t *rng, int32_t *orient, int64_t B) {
+  int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i >= B) return;
+  uint64_t x = rng[i];
+  const uint64_t u = splitmix_next(x);
+  orient[i] = (int32_t)(u >> 61);
+  rng[i] = x;
+}
+
 }  // namespace gg

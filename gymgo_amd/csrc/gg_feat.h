@@ -142,64 +142,141 @@ __device__ __forceinline__ V16a feat_expand(uint32_t x, uint32_t one) {
   return o;
 }
 
+// ORIENTED planes (gg_batch_features_oriented / gg_batch_features_tracked_oriented): the three loaded row sets of a board
+// (black, white, invalid) are turned into view o of the board in registers, right after the load - everything after it works
+// on the turned position, so the sixteen planes come out turned alike (all of them are geometric; the flags do not move).
+// The geometry is k_symmetry_rows' (gg_sym.h), in this layout:
+//   no rotation:  out[r] bit c = x[R(r)] bit C(c)          R = the row flip: a lane permutation inside the board's lanes,
+//   rotation:     out[r] bit c = xt[C(N-1-r)] bit R(c)     C = the column flip: a bit reversal of the row; xt = the transpose
+// The transpose is the block-swap network over the board's lanes: four stages for a board of 16 lanes, five for 32.  Every
+// stage is one lane exchange at a fixed distance: DPP quad permutes (1, 2), a DPP row rotation (8), ds_swizzle in bit mode
+// (4, 16: no DPP control swaps at those distances inside a row of 16 / across two) - none touches memory.  The stage masks
+// are periodic in 16 bits, so a board of 16 lanes transposes TWO row sets at once, one per half of a register.  The row
+// selection is one ds_bpermute per register: its source depends on the board's own orientation, which differs from board to
+// board of a wave.  A wave none of whose boards rotates skips the stages.
+template <int J> __device__ __forceinline__ uint32_t feat_xchg(uint32_t x) {   // lane i reads lane i ^ J
+  if (J == 1) return dpp0<0xB1>(x);         // quad_perm [1, 0, 3, 2]
+  else if (J == 2) return dpp0<0x4E>(x);    // quad_perm [2, 3, 0, 1]
+  else if (J == 8) return dpp0<0x128>(x);   // row_ror:8
+  else return (uint32_t)__builtin_amdgcn_ds_swizzle((int)x, (J << 10) | 0x1F);   // and 0x1F, or 0, xor J
+}
+template <int J> __device__ __forceinline__ uint32_t feat_tstage(uint32_t xt, int r) {
+  constexpr uint32_t LOWM = J == 16 ? 0x0000FFFFu : J == 8 ? 0x00FF00FFu : J == 4 ? 0x0F0F0F0Fu : J == 2 ? 0x33333333u : 0x55555555u;
+  const uint32_t y = feat_xchg<J>(xt);
+  const uint32_t up = (xt & LOWM) | ((y & LOWM) << J);      // (r & J) == 0: the partner's low column blocks into the high ones
+  const uint32_t dn = (xt & ~LOWM) | ((y & ~LOWM) >> J);    // (r & J) != 0: the partner's high blocks into the low ones
+  return (r & J) ? dn : up;
+}
+// bit c of row r <- bit r of row c over the board's LPB lanes (LPB = 16: in both halves of the register)
+template <int LPB> __device__ __forceinline__ uint32_t feat_transpose(uint32_t x, int r) {
+  if (LPB == 32) x = feat_tstage<16>(x, r);
+  x = feat_tstage<8>(x, r);
+  x = feat_tstage<4>(x, r);
+  x = feat_tstage<2>(x, r);
+  return feat_tstage<1>(x, r);
+}
+// bl / wh / inv of every board of the wave -> view o of the board (o: this lane's board's orientation, 0 .. 7)
+template <int R>
+__device__ __forceinline__ void feat_orient(uint32_t &bl, uint32_t &wh, uint32_t &inv, int o, int N, int r, int lane, uint32_t full) {
+  constexpr int LPB = Feat<R>::LPB, NX = LPB == 16 ? 2 : 3;
+  uint32_t x[NX];
+  if (LPB == 16) { x[0] = bl | (wh << 16); x[NX - 1] = inv; }
+  else { x[0] = bl; x[1] = wh; x[NX - 1] = inv; }
+  const bool rot = (o & 4) != 0;
+  if (__ballot(rot) != 0ull) {
+#pragma unroll
+    for (int k = 0; k < NX; ++k) {
+      const uint32_t xt = feat_transpose<LPB>(x[k], r);
+      x[k] = rot ? xt : x[k];
+    }
+  }
+  // the source row: C(N-1-r) of the transposed set, R(r) of the plain one; then the reversal of the row's bits
+  const bool down = rot ? (o & 1) == 0 : (o & 2) != 0;
+  const int srow = r < N ? (down ? N - 1 - r : r) : 0;
+  const int src = ((lane & ~(LPB - 1)) + srow) << 2;
+  const bool rev = rot ? (o & 2) != 0 : (o & 1) != 0;
+  const uint32_t sh = (uint32_t)(32 - N);
+#pragma unroll
+  for (int k = 0; k < NX; ++k) x[k] = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)x[k]);
+  uint32_t y[3];
+  if (LPB == 16) { y[0] = x[0] & 0xFFFFu; y[1] = x[0] >> 16; y[2] = x[NX - 1]; }
+  else { y[0] = x[0]; y[1] = x[1]; y[2] = x[NX - 1]; }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) y[k] = (rev ? __brev(y[k]) >> sh : y[k]) & full;
+  bl = y[0]; wh = y[1]; inv = y[2];
+}
+
 // gg_batch_features / gg_batch_features_tracked: out [B][16][N][N] of ESIZE-byte elements (`one`: the bit pattern of 1),
-// 16-byte aligned.  One single-wave workgroup per NBW boards (grid-stride).
+// 16-byte aligned.  One single-wave workgroup per NBW boards (grid-stride).  The body is spelled ONCE, as a macro, for the
+// plain and the oriented kernel (TURN: the statement between the load and the analysis): the plain kernels then compile from
+// the token sequence they had before the oriented ones existed and keep their machine code instruction for instruction - as
+// a function template shared by both they did not (the inlined copy commuted operands and swapped instructions).
+#define GG_FEATURES_BODY(TURN)                                                                                                        \
+  using F_ = Feat<R>;                                                                                                                 \
+  constexpr int LPB = F_::LPB, NBW = F_::NBW, EPV = 16 / ESIZE;                                                                       \
+  __shared__ __attribute__((aligned(16))) uint32_t lds[F_::kLdsWords];                                                                \
+  const int lane = threadIdx.x & (kWave - 1);                                                                                         \
+  const int r = lane & (LPB - 1), j = lane / LPB;                                                                                     \
+  const int P = N * N;                                                                                                                \
+  const uint32_t full = r < N ? (1u << N) - 1u : 0u;                                                                                  \
+  const int64_t ngroups = (B + NBW - 1) / NBW;                                                                                        \
+  for (int64_t g = blockIdx.x; g < ngroups; g += gridDim.x) {                                                                         \
+    const int64_t b_first = g * NBW;                                                                                                  \
+    const int nb = (int)(B - b_first < NBW ? B - b_first : NBW);                                                                      \
+    const bool on = j < nb;                                                                                                           \
+    uint32_t bl, wh, inv, fl;                                                                                                         \
+    if (TRACKED) feat_load_tracked(static_cast<const uint32_t *>(in), on ? b_first + j : B - 1, N, r, on, full, bl, wh, inv, fl);     \
+    else feat_load_bytes<R>(static_cast<const uint8_t *>(in), b_first, nb, N, r, j, on, full, lds, lane, bl, wh, inv, fl);            \
+    TURN;                                                                                                                             \
+    uint32_t cls[4];                                                                                                                  \
+    feat_groups<R, false>(bl, wh, full, cls);                                                                                         \
+    /* the sixteen rows of this lane (include/gymgo_amd.h: the table of planes) */                                                       \
+    const bool white = (fl & 1u) != 0, done = (fl & 4u) != 0;                                                                         \
+    const uint32_t own = white ? wh : bl, opp = white ? bl : wh;                                                                      \
+    const uint32_t E = full & ~(bl | wh);                                                                                             \
+    const uint32_t legal = done ? 0u : (E & ~inv);                                                                                    \
+    const uint32_t cap = E & lat_dilate<LPB>(opp & cls[0]);   /* next to an opponent group whose one liberty is this point */            \
+    const uint32_t rows[kFeatPlanes] = {own, opp, own & cls[0], own & cls[1], own & cls[2], own & cls[3],                             \
+                                        opp & cls[0], opp & cls[1], opp & cls[2], opp & cls[3],                                       \
+                                        legal, done ? 0u : (E & inv & cap), legal & cap,                                              \
+                                        white ? 0u : full, (fl & 2u) ? full : 0u, full};                                              \
+    /* the wave's bit-string */                                                                                                          \
+    const int nbits = nb * kFeatPlanes * P;                                                                                           \
+    for (int w = lane; w < ((nbits + 31) >> 5) + 1; w += kWave) lds[w] = 0;                                                           \
+    WAVE_SYNC();                                                                                                                      \
+    if (on && r < N) {                                                                                                                \
+      const uint32_t q0 = (uint32_t)(j * kFeatPlanes * P + r * N);                                                                    \
+      _Pragma("unroll")                                                                                                                \
+      for (int p = 0; p < kFeatPlanes; ++p) {                                                                                         \
+        if (rows[p]) {                                                                                                                \
+          const uint32_t q = q0 + (uint32_t)(p * P);                                                                                  \
+          const uint64_t x = (uint64_t)rows[p] << (q & 31u);                                                                          \
+          atomicOr(lds + (q >> 5), (uint32_t)x);                                                                                      \
+          if ((uint32_t)(x >> 32)) atomicOr(lds + (q >> 5) + 1, (uint32_t)(x >> 32));                                                 \
+        }                                                                                                                             \
+      }                                                                                                                               \
+    }                                                                                                                                 \
+    WAVE_SYNC();                                                                                                                      \
+    uint8_t *dst = out + b_first * (int64_t)(kFeatPlanes * ESIZE) * P;                                                                \
+    const int nvec = nb * P * ESIZE;   /* = nbits / EPV */                                                                               \
+    for (int v = lane; v < nvec; v += kWave) {                                                                                        \
+      const uint32_t q = (uint32_t)(v * EPV);                                                                                         \
+      *reinterpret_cast<V16a *>(dst + 16 * (int64_t)v) = feat_expand<ESIZE>(lds[q >> 5] >> (q & 31u), one);                           \
+    }                                                                                                                                 \
+    WAVE_SYNC();                                                                                                                      \
+  }
 template <int R, int ESIZE, bool TRACKED>
 __global__ __launch_bounds__(kWave) void k_features(const void *__restrict__ in, uint8_t *__restrict__ out, uint32_t one,
                                                     int64_t B, int N) {
-  using F_ = Feat<R>;
-  constexpr int LPB = F_::LPB, NBW = F_::NBW, EPV = 16 / ESIZE;
-  __shared__ __attribute__((aligned(16))) uint32_t lds[F_::kLdsWords];
-  const int lane = threadIdx.x & (kWave - 1);
-  const int r = lane & (LPB - 1), j = lane / LPB;
-  const int P = N * N;
-  const uint32_t full = r < N ? (1u << N) - 1u : 0u;
-  const int64_t ngroups = (B + NBW - 1) / NBW;
-  for (int64_t g = blockIdx.x; g < ngroups; g += gridDim.x) {
-    const int64_t b_first = g * NBW;
-    const int nb = (int)(B - b_first < NBW ? B - b_first : NBW);
-    const bool on = j < nb;
-    uint32_t bl, wh, inv, fl;
-    if (TRACKED) feat_load_tracked(static_cast<const uint32_t *>(in), on ? b_first + j : B - 1, N, r, on, full, bl, wh, inv, fl);
-    else feat_load_bytes<R>(static_cast<const uint8_t *>(in), b_first, nb, N, r, j, on, full, lds, lane, bl, wh, inv, fl);
-    uint32_t cls[4];
-    feat_groups<R, false>(bl, wh, full, cls);
-    // the sixteen rows of this lane (include/gymgo_amd.h: the table of planes)
-    const bool white = (fl & 1u) != 0, done = (fl & 4u) != 0;
-    const uint32_t own = white ? wh : bl, opp = white ? bl : wh;
-    const uint32_t E = full & ~(bl | wh);
-    const uint32_t legal = done ? 0u : (E & ~inv);
-    const uint32_t cap = E & lat_dilate<LPB>(opp & cls[0]);   // next to an opponent group whose one liberty is this point
-    const uint32_t rows[kFeatPlanes] = {own, opp, own & cls[0], own & cls[1], own & cls[2], own & cls[3],
-                                        opp & cls[0], opp & cls[1], opp & cls[2], opp & cls[3],
-                                        legal, done ? 0u : (E & inv & cap), legal & cap,
-                                        white ? 0u : full, (fl & 2u) ? full : 0u, full};
-    // the wave's bit-string
-    const int nbits = nb * kFeatPlanes * P;
-    for (int w = lane; w < ((nbits + 31) >> 5) + 1; w += kWave) lds[w] = 0;
-    WAVE_SYNC();
-    if (on && r < N) {
-      const uint32_t q0 = (uint32_t)(j * kFeatPlanes * P + r * N);
-#pragma unroll
-      for (int p = 0; p < kFeatPlanes; ++p) {
-        if (rows[p]) {
-          const uint32_t q = q0 + (uint32_t)(p * P);
-          const uint64_t x = (uint64_t)rows[p] << (q & 31u);
-          atomicOr(lds + (q >> 5), (uint32_t)x);
-          if ((uint32_t)(x >> 32)) atomicOr(lds + (q >> 5) + 1, (uint32_t)(x >> 32));
-        }
-      }
-    }
-    WAVE_SYNC();
-    uint8_t *dst = out + b_first * (int64_t)(kFeatPlanes * ESIZE) * P;
-    const int nvec = nb * P * ESIZE;   // = nbits / EPV
-    for (int v = lane; v < nvec; v += kWave) {
-      const uint32_t q = (uint32_t)(v * EPV);
-      *reinterpret_cast<V16a *>(dst + 16 * (int64_t)v) = feat_expand<ESIZE>(lds[q >> 5] >> (q & 31u), one);
-    }
-    WAVE_SYNC();
-  }
+  GG_FEATURES_BODY((void)0)
 }
+// ... in view orient[b] (int32 [B]) of every board: gg_batch_features_oriented / gg_batch_features_tracked_oriented
+template <int R, int ESIZE, bool TRACKED>
+__global__ __launch_bounds__(kWave) void k_features_oriented(const void *__restrict__ in, const int32_t *__restrict__ orient,
+                                                             uint8_t *__restrict__ out, uint32_t one, int64_t B, int N) {
+  GG_FEATURES_BODY(feat_orient<R>(bl, wh, inv, on ? (orient[b_first + j] & 7) : 0, N, r, lane, full))
+}
+#undef GG_FEATURES_BODY
 
 // gg_batch_group_liberties: libs uint8 [B][N][N] = min(liberties of the group of the stone at the point, 255), 0 at empty points
 template <int R>

@@ -1,5 +1,5 @@
-// gg_feat.hip - the launches of the feature-plane kernels (gg_feat.h: gg_batch_features, gg_batch_features_tracked,
-// gg_batch_group_liberties) as a translation unit of their own, compiled with the default code-generation switches: the
+// gg_feat.hip - the launches of the feature-plane kernels (gg_feat.h: gg_batch_features, gg_batch_features_tracked, their
+// oriented forms, gg_batch_group_liberties) as a translation unit of their own, compiled with the default code-generation switches: the
 // machine code of every kernel of the other four units - and the hashes bench.py ties their PMC records to - does not
 // depend on anything in here.
 #include <hip/hip_runtime.h>
@@ -35,6 +35,29 @@ unsigned feat_grid(int cus, int64_t B, int nbw) {
     else GG_FEAT_E(R, 4, 0x3F800000u);                            \
   } while (0)
 void launch_features(bool tracked, const void *in, void *out, int dtype, int64_t B, int32_t N, int cus, hipStream_t s) {
+  if (N <= 9) GG_FEAT(9);
+  else if (N <= 13) GG_FEAT(13);
+  else GG_FEAT(19);
+}
+#undef GG_FEAT
+#undef GG_FEAT_E
+
+// ... and view orient[b] of them (k_features_oriented: the same grid, the boards turned in registers after the load)
+#define GG_FEAT_E(R, ES, ONE)                                                                                                        \
+  do {                                                                                                                               \
+    const unsigned grid_ = feat_grid(cus, B, Feat<R>::NBW);                                                                          \
+    if (tracked) k_features_oriented<R, ES, true><<<grid_, kWave, 0, s>>>(in, orient, static_cast<uint8_t *>(out), ONE, B, N);       \
+    else k_features_oriented<R, ES, false><<<grid_, kWave, 0, s>>>(in, orient, static_cast<uint8_t *>(out), ONE, B, N);              \
+  } while (0)
+#define GG_FEAT(R)                                                \
+  do {                                                            \
+    if (dtype == GG_FEAT_U8) GG_FEAT_E(R, 1, 1u);                 \
+    else if (dtype == GG_W_F16) GG_FEAT_E(R, 2, 0x3C00u);         \
+    else if (dtype == GG_W_BF16) GG_FEAT_E(R, 2, 0x3F80u);        \
+    else GG_FEAT_E(R, 4, 0x3F800000u);                            \
+  } while (0)
+void launch_features_oriented(bool tracked, const void *in, const int32_t *orient, void *out, int dtype, int64_t B, int32_t N, int cus,
+                              hipStream_t s) {
   if (N <= 9) GG_FEAT(9);
   else if (N <= 13) GG_FEAT(13);
   else GG_FEAT(19);

@@ -52,6 +52,8 @@ void launch_rollout_lat_policy(uint8_t *st, uint64_t *rng, int32_t *last_actions
                                int auto_reset, hipStream_t s);
 // gg_feat.hip: the feature-plane kernels (gg_feat.h)
 void launch_features(bool tracked, const void *in, void *out, int dtype, int64_t B, int32_t N, int cus, hipStream_t s);
+void launch_features_oriented(bool tracked, const void *in, const int32_t *orient, void *out, int dtype, int64_t B, int32_t N, int cus,
+                              hipStream_t s);
 void launch_group_liberties(const uint8_t *states, uint8_t *libs, int64_t B, int32_t N, int cus, hipStream_t s);
 }
 
@@ -1191,6 +1193,26 @@ int32_t gg_batch_features_tracked(const uint32_t *tracked, void *out, int32_t ou
   return (int32_t)hipGetLastError();
 }
 
+int32_t gg_batch_features_oriented(const uint8_t *states, const int32_t *orient, void *out, int32_t out_dtype, int64_t B, int32_t N,
+                                   void *hip_stream) {
+  if (out_dtype < GG_W_F32 || out_dtype > GG_FEAT_U8) return GG_E_BADSIZE;
+  GG_ENTER(states);
+  if (!out || !orient) return GG_E_NULLPTR;
+  if ((uintptr_t)out & 15u) return GG_E_BADARG;
+  launch_features_oriented(false, states, orient, out, out_dtype, B, N, cus, s);
+  return (int32_t)hipGetLastError();
+}
+
+int32_t gg_batch_features_tracked_oriented(const uint32_t *tracked, const int32_t *orient, void *out, int32_t out_dtype, int64_t B,
+                                           int32_t N, void *hip_stream) {
+  if (out_dtype < GG_W_F32 || out_dtype > GG_FEAT_U8) return GG_E_BADSIZE;
+  GG_ENTER(tracked);
+  if (!out || !orient) return GG_E_NULLPTR;
+  if ((uintptr_t)out & 15u) return GG_E_BADARG;
+  launch_features_oriented(true, tracked, orient, out, out_dtype, B, N, cus, s);
+  return (int32_t)hipGetLastError();
+}
+
 int32_t gg_batch_play_moves_tracked(uint32_t *tracked, const int32_t *moves, int32_t *played, int64_t B, int32_t N, int32_t T,
                                     void *hip_stream) {
   if (T < 0) return GG_E_BADARG;
@@ -1297,6 +1319,32 @@ int32_t gg_batch_symmetry_rows(const uint32_t *in, int32_t planes, const int32_t
   if (!out) return GG_E_NULLPTR;
   const int grid = grid_for(cus, (B + 1) / 2, 128);   // short iterations: 54 -> 47 us per 65 536 tracked boards with 4x the workgroups
   k_symmetry_rows<<<grid, kWave, 0, s>>>(in, orient, out, B, N, planes);
+  return (int32_t)hipGetLastError();
+}
+
+int32_t gg_batch_symmetry_policy(const void *in, const int32_t *orient, void *out, int32_t elem_size, int32_t inverse, int64_t B,
+                                 int32_t N, void *hip_stream) {
+  if (elem_size != 1 && elem_size != 2 && elem_size != 4) return GG_E_BADSIZE;
+  GG_ENTER(in);
+  if (!orient || !out) return GG_E_NULLPTR;
+  const int A = N * N + 1;
+  const int rows = kPolElems / A < kPolRows ? kPolElems / A : kPolRows;
+  const int grid = grid_for(cus, (B + rows - 1) / rows);
+  const uint8_t *ip = static_cast<const uint8_t *>(in);
+  uint8_t *op = static_cast<uint8_t *>(out);
+  if (elem_size == 1) k_symmetry_policy<1><<<grid, kWave, 0, s>>>(ip, orient, op, inverse != 0, B, N, rows);
+  else if (elem_size == 2) k_symmetry_policy<2><<<grid, kWave, 0, s>>>(ip, orient, op, inverse != 0, B, N, rows);
+  else k_symmetry_policy<4><<<grid, kWave, 0, s>>>(ip, orient, op, inverse != 0, B, N, rows);
+  return (int32_t)hipGetLastError();
+}
+
+int32_t gg_batch_draw_orient(uint64_t *rng, int32_t *orient, int64_t B, void *hip_stream) {
+  if (B < 0) return GG_E_BADSIZE;
+  if (B == 0) return 0;
+  if (!rng || !orient) return GG_E_NULLPTR;
+  OnDeviceOf on_dev(rng);
+  hipStream_t s = (hipStream_t)hip_stream;
+  k_draw_orient<<<(unsigned)((B + 255) / 256), 256, 0, s>>>(rng, orient, B);
   return (int32_t)hipGetLastError();
 }
 

@@ -10,7 +10,8 @@
 // aligned vector accesses only; and row-mask boards (packed 3 N + 1 / tracked 5 N + 1 words, gg_batch_pack_states /
 // gg_batch_track_states), where a column flip is a bit reversal of the row masks, a row flip a lane permutation and
 // the rotation a 32 x 32 bit-matrix transpose across the lanes of a half-wave - liberty classes and the invalid-move rows (ko point included) are
-// geometric, so a transformed tracked board is a valid tracked board.
+// geometric, so a transformed tracked board is a valid tracked board.  A third form turns vectors over the actions
+// (k_symmetry_policy: what a network reads and writes beside the planes).
 #pragma once
 #include "gg_common.h"
 #include "gg_v2.h"
@@ -251,6 +252,71 @@ __global__ __launch_bounds__(kWave) void k_symmetry_bits(const uint8_t *__restri
     }
   }
 #undef GG_SYM_FETCH
+}
+
+// Vectors over the ACTIONS (gg_batch_symmetry_policy): rows of A = N^2 + 1 elements of ES bytes - priors, legal masks,
+// visit-count targets - moved as bit patterns.  Forward: the first N^2 elements are turned as a one-plane image (the rule
+// above: out[q] = in[source of q]), inverse: out[a] = in[where a lands in the view] (symmetry_actions); the pass stays.
+// Both are GATHERS in LDS.  A workgroup (one wave) takes `rows` consecutive rows at a time - one contiguous slice of HBM
+// in, one out, both through stage_in / stage_out: aligned 16-byte accesses whatever the alignment of the bases, and no
+// byte outside the rows is written.  (chunk row, board row, column) of every element of a chunk is tabulated once per
+// workgroup (the only divisions); the orientations of a chunk's rows are staged as bytes.
+constexpr int kPolElems = 1536;   // elements per chunk (four rows of 19x19)
+constexpr int kPolRows = 320;     // rows per chunk at most (1536 / 5 = 307 rows of 2x2)
+template <int ES>
+__global__ __launch_bounds__(kWave) void k_symmetry_policy(const uint8_t *__restrict__ in, const int32_t *__restrict__ orient,
+                                                           uint8_t *__restrict__ out, int inverse, int64_t B, int N, int rows) {
+  __shared__ __attribute__((aligned(16))) uint8_t src[kPolElems * ES + 32];
+  __shared__ __attribute__((aligned(16))) uint8_t dst[kPolElems * ES + 32];
+  __shared__ uint32_t tab[kPolElems];   // (row of the chunk << 16) | (board row << 8) | column; board row 0xFF: the pass
+  __shared__ uint8_t os[kPolRows];
+  const int lane = threadIdx.x;
+  const int P = N * N, A = P + 1;
+  for (int e = lane; e < rows * A; e += kWave) {
+    const int j = e / A, a = e - j * A, r = a / N;
+    tab[e] = ((uint32_t)j << 16) | (a == P ? 0xFF00u : (uint32_t)((r << 8) | (a - r * N)));
+  }
+  const int64_t nchunks = (B + rows - 1) / rows;
+  for (int64_t ch = blockIdx.x; ch < nchunks; ch += gridDim.x) {
+    const int64_t b0 = ch * rows;
+    const int nb = (int)(B - b0 < rows ? B - b0 : rows), ne = nb * A;
+    WAVE_SYNC();   // (the previous chunk has left dst)
+    const uint32_t mi = stage_in(in + b0 * (int64_t)A * ES, ne * ES, src, lane);
+    for (int j = lane; j < nb; j += kWave) os[j] = (uint8_t)(orient[b0 + j] & 7);
+    uint8_t *g = out + b0 * (int64_t)A * ES;
+    const uint32_t mo = (uint32_t)((uintptr_t)g & 15u);
+    WAVE_SYNC();
+    const bool typed = ((mi | mo) & (uint32_t)(ES - 1)) == 0u;   // (bases that are not even element-aligned: byte by byte)
+    for (int e = lane; e < ne; e += kWave) {
+      const uint32_t w = tab[e];
+      const int j = (int)(w >> 16), r = (int)((w >> 8) & 0xFFu), c = (int)(w & 0xFFu);
+      int sa = P;
+      if (r != 0xFF) {
+        const int o = os[j];
+        int sr, sc;
+        if (inverse) {   // where (r, c) lands in the view
+          const int r1 = (o & 2) ? N - 1 - r : r, c1 = (o & 1) ? N - 1 - c : c;
+          sr = (o & 4) ? N - 1 - c1 : r1;
+          sc = (o & 4) ? r1 : c1;
+        } else {
+          sym_source(o, N, r, c, sr, sc);
+        }
+        sa = sr * N + sc;
+      }
+      const uint8_t *sp = src + mi + (j * A + sa) * ES;
+      uint8_t *dp = dst + mo + e * ES;
+      if (ES == 1) *dp = *sp;
+      else if (typed) {
+        if (ES == 2) *reinterpret_cast<uint16_t *>(dp) = *reinterpret_cast<const uint16_t *>(sp);
+        else *reinterpret_cast<uint32_t *>(dp) = *reinterpret_cast<const uint32_t *>(sp);
+      } else {
+#pragma unroll
+        for (int k = 0; k < ES; ++k) dp[k] = sp[k];
+      }
+    }
+    WAVE_SYNC();
+    stage_out(g, ne * ES, dst, lane);
+  }
 }
 
 // row-mask boards: one board per 32-lane half (lane r of the half = row r of every plane).

@@ -858,7 +858,18 @@ def group_liberties(state):
     return _back(box, batch_group_liberties(box.t[None]), row0=True)
 
 
-def batch_features(batch_states, dtype=torch.float16, out=None):
+def _orient_arg(orient, B):
+    """ValueError unless orient is B integers (a tensor or an array) - before a device is touched."""
+    if isinstance(orient, torch.Tensor):
+        n, integral = orient.numel(), not (orient.dtype.is_floating_point or orient.dtype.is_complex or orient.dtype == torch.bool)
+    else:
+        orient = np.asarray(orient)
+        n, integral = orient.size, orient.dtype.kind in 'iu'
+    if not integral or n != B:
+        raise ValueError('orient must be %d integers in 0..7, one per row (got %d of %s)' % (B, n, orient.dtype))
+
+
+def batch_features(batch_states, dtype=torch.float16, out=None, orient=None):
     """Network input planes of every board -> [B, 16, N, N] of `dtype` (gg_batch_features), from the mover's point of view
     ("own" = the player to move).  Plane by plane (FEATURE_NAMES), each value exactly 0 or 1:
        0      own stone                      1      opponent stone
@@ -872,18 +883,30 @@ def batch_features(batch_states, dtype=torch.float16, out=None):
     plane 3 of the input is taken as given.  dtype: torch.uint8, float16, bfloat16 or float32 (ValueError otherwise; 0 and 1
     are exact in all four).  out: a contiguous, 16-byte aligned device tensor of that shape and dtype to write into.  NumPy in
     gives NumPy out (through the device; not for bfloat16, which NumPy lacks).  One launch; device memory of the result:
-    16 * B * N^2 elements - 11.5 KB per 19x19 board in a 16-bit dtype."""
+    16 * B * N^2 elements - 11.5 KB per 19x19 board in a 16-bit dtype.
+    orient (None: the call above, launch for launch; or int [B], a tensor or an array, only orient & 7 is read): row b is
+    view orient[b] of its planes, all sixteen turned alike (gg_batch_features_oriented; bit 0 flips the columns, then bit 1
+    the rows, then bit 2 rotates: batch_symmetry's orientations).  That is also batch_features of the turned position,
+    batch_symmetry(batch_states, orient).  Still one launch."""
     code = _feature_dtype(dtype)
     B, N = _states_shape(batch_states)
     _feature_out(out, (B, FEATURE_PLANES, N, N), dtype)
+    if orient is not None:
+        _orient_arg(orient, B)
     if not isinstance(batch_states, torch.Tensor) and dtype == torch.bfloat16:
         raise ValueError('NumPy has no bfloat16: pass a device tensor, or another dtype')
     box = _Box(batch_states)
     st = box.t
     _feature_out(out, (B, FEATURE_PLANES, N, N), dtype, st.device)
     planes = out if out is not None else torch.empty((B, FEATURE_PLANES, N, N), dtype=dtype, device=st.device)
-    _lib.check(_lib.lib().gg_batch_features(_lib.dev_ptr(st, _U8, 'states'), _lib.dev_ptr(planes, dtype, 'out'), code, B, N,
-                                            _lib.stream_ptr(st.device)), 'gg_batch_features')
+    if orient is None:
+        _lib.check(_lib.lib().gg_batch_features(_lib.dev_ptr(st, _U8, 'states'), _lib.dev_ptr(planes, dtype, 'out'), code, B, N,
+                                                _lib.stream_ptr(st.device)), 'gg_batch_features')
+    else:
+        o = _actions_tensor(orient, B, st.device)
+        _lib.check(_lib.lib().gg_batch_features_oriented(_lib.dev_ptr(st, _U8, 'states'), _lib.dev_ptr(o, _I32, 'orient'),
+                                                         _lib.dev_ptr(planes, dtype, 'out'), code, B, N, _lib.stream_ptr(st.device)),
+                   'gg_batch_features_oriented')
     return _back(box, planes)
 
 
@@ -896,19 +919,29 @@ def features(state, dtype=torch.float16):
     return _back(box, batch_features(box.t[None], dtype), row0=True)
 
 
-def batch_features_tracked(tracked, dtype=torch.float16, out=None):
+def batch_features_tracked(tracked, dtype=torch.float16, out=None, orient=None):
     """batch_features of tracked boards (int32 [B, 5N+1], a device tensor) -> [B, 16, N, N] of `dtype`
     (gg_batch_features_tracked): bit for bit what batch_features gives for batch_untrack(tracked) - the search's leaf
-    boards go to the network without the byte planes in between.  dtype, out, exactness and device memory: batch_features."""
+    boards go to the network without the byte planes in between.  dtype, out, exactness and device memory: batch_features.
+    orient: as batch_features (gg_batch_features_tracked_oriented) - what batch_symmetry_rows followed by this call gives,
+    in one launch and without the second board buffer."""
     code = _feature_dtype(dtype)
     if not isinstance(tracked, torch.Tensor) or tracked.dim() != 2:
         raise ValueError('tracked boards are int32 [B, 5N+1] device tensors')
     N = _tracked_size(tracked)
     B = tracked.shape[0]
+    if orient is not None:
+        _orient_arg(orient, B)
     _feature_out(out, (B, FEATURE_PLANES, N, N), dtype, tracked.device if tracked.is_cuda else None)
     planes = out if out is not None else torch.empty((B, FEATURE_PLANES, N, N), dtype=dtype, device=tracked.device)
-    _lib.check(_lib.lib().gg_batch_features_tracked(_lib.dev_ptr(tracked, _I32, 'tracked'), _lib.dev_ptr(planes, dtype, 'out'), code,
-                                                    B, N, _lib.stream_ptr(tracked.device)), 'gg_batch_features_tracked')
+    if orient is None:
+        _lib.check(_lib.lib().gg_batch_features_tracked(_lib.dev_ptr(tracked, _I32, 'tracked'), _lib.dev_ptr(planes, dtype, 'out'), code,
+                                                        B, N, _lib.stream_ptr(tracked.device)), 'gg_batch_features_tracked')
+    else:
+        o = _actions_tensor(orient, B, tracked.device)
+        _lib.check(_lib.lib().gg_batch_features_tracked_oriented(_lib.dev_ptr(tracked, _I32, 'tracked'), _lib.dev_ptr(o, _I32, 'orient'),
+                                                                 _lib.dev_ptr(planes, dtype, 'out'), code, B, N,
+                                                                 _lib.stream_ptr(tracked.device)), 'gg_batch_features_tracked_oriented')
     return planes
 
 
@@ -1435,10 +1468,27 @@ class PuctSearch:
     with planes [R, 16, N, N] ([R * L, ..] with leaves=L) of that dtype - batch_features of the leaves, made from the tracked
     leaf boards by gg_batch_features_tracked - instead of (states, legal).  With leaves=L that launch REPLACES the untrack
     of the leaf boards; on the one-leaf path `legal` comes from the untracked states, so it is one launch more.  Rows of
-    empty slots hold the planes of whatever board their row holds.  Device memory: 16 N^2 elements per row handed out."""
+    empty slots hold the planes of whatever board their row holds.  Device memory: 16 N^2 elements per row handed out.
 
-    def __init__(self, batch_states, iterations, c=1.25, komi=0.0, leaves=None, capacity=None, features=None):
+    symmetry (None = everything above, launch for launch; or an integer base seed; needs features=, ValueError otherwise):
+    every evaluation sees its leaf in a random one of the eight orientations of batch_symmetry - AlphaGo Zero's random
+    rotation or reflection per leaf.  The search keeps one generator per row it hands out, rng_seed(R * rows, symmetry,
+    first_root * rows) with rows = L (1 without leaves): shards by root with first_root = the shard's first root
+    concatenate to the whole.  Every select() draws one orientation per row (batch_draw_orient; `search.orient`, int32
+    [R * rows], a device tensor valid until the next select()) and hands out planes AND legal in that view: the planes by
+    the oriented feature launch, which replaces the plain one, legal through batch_symmetry_policy; backup() turns the
+    priors back (inverse=True) before the backup launch it queues anyway.  The tree, the stored priors, root_policy,
+    add_root_noise and advance stay in the board's own frame: the tree is bit for bit the tree of the same search
+    without symmetry and with the evaluator E'(planes, legal) = inverse_o(E(view_o(planes), view_o(legal))), o the
+    orientations drawn for that call (the values are not turned).  Two launches more per select(), one per backup()."""
+
+    def __init__(self, batch_states, iterations, c=1.25, komi=0.0, leaves=None, capacity=None, features=None, symmetry=None,
+                 first_root=0):
         self._feat = None if features is None else (features, _feature_dtype(features))
+        _puct_symmetry_guard(symmetry, features)
+        self._sym = None if symmetry is None else int(symmetry)
+        self._first_root = int(first_root)
+        self.orient = None
         self._box = batch_states if isinstance(batch_states, _Box) else _Box(batch_states)   # (a _Box: puct_play's own states)
         st = self._box.t
         if st.dim() != 4 or st.shape[1] != govars.NUM_CHNLS or st.shape[2] != st.shape[3]:
@@ -1471,6 +1521,7 @@ class PuctSearch:
         self._done, self._pending = 0, False
         if self._feat is not None:
             self._planes = torch.empty((R, FEATURE_PLANES, N, N), dtype=self._feat[0], device=dev)
+        self._init_symmetry(R)
         if not R:   # no device work at all: select / backup only keep the call order
             return
         p = _lib.dev_ptr
@@ -1503,6 +1554,7 @@ class PuctSearch:
         self._legal = torch.empty((B, A), dtype=torch.bool, device=dev)
         self.live = torch.zeros((R, L), dtype=torch.bool, device=dev)
         self._done, self._pending = 0, False
+        self._init_symmetry(B)
         if not R:
             return
         p = _lib.dev_ptr
@@ -1512,6 +1564,39 @@ class PuctSearch:
         self._hand = (p(self._states, self._states.dtype, 'states'), p(self._legal, torch.bool, 'legal'), p(self.live, torch.bool, 'live'))
         _lib.check(_lib.lib().gg_puct_begin(p(_track_roots(st), _I32, 'roots'), R, N, C, *self._tree,
                                             _lib.current_raw_stream(dev)), 'gg_puct_begin')
+
+    def _init_symmetry(self, B):
+        """symmetry: the generators of the B rows handed out, their orientations, legal in the view, the priors turned back."""
+        if self._sym is None:
+            return
+        A, dev = self._N * self._N + 1, self._dev
+        self.orient = torch.zeros(B, dtype=_I32, device=dev)
+        self._legal_view = torch.empty((B, A), dtype=torch.bool, device=dev)
+        self._priors_back = torch.empty((B, A), dtype=torch.float32, device=dev)
+        self._sym_rng = torch.empty(B, dtype=_I64, device=dev)
+        if B:
+            rows = B // self._R
+            _lib.check(_lib.lib().gg_rng_seed(_lib.dev_ptr(self._sym_rng, _I64, 'rng'), self._sym & (2 ** 64 - 1),
+                                              self._first_root * rows, B, _lib.current_raw_stream(dev)), 'gg_rng_seed')
+
+    def _draw_orient(self, B, stream):
+        """The orientations of this select()'s B rows -> the pointer of search.orient."""
+        op = _lib.dev_ptr(self.orient, _I32, 'orient')
+        _lib.check(_lib.lib().gg_batch_draw_orient(_lib.dev_ptr(self._sym_rng, _I64, 'rng'), op, B, stream), 'gg_batch_draw_orient')
+        return op
+
+    def _turn_legal(self, op, B, stream):
+        _lib.check(_lib.lib().gg_batch_symmetry_policy(_lib.dev_ptr(self._legal, torch.bool, 'legal'), op,
+                                                       _lib.dev_ptr(self._legal_view, torch.bool, 'legal'), 1, 0, B, self._N, stream),
+                   'gg_batch_symmetry_policy')
+
+    def _turn_priors_back(self, priors, B):
+        """priors [B, A] over the views -> over the boards (R > 0)."""
+        _lib.check(_lib.lib().gg_batch_symmetry_policy(_lib.dev_ptr(priors, torch.float32, 'priors'),
+                                                       _lib.dev_ptr(self.orient, _I32, 'orient'),
+                                                       _lib.dev_ptr(self._priors_back, torch.float32, 'priors'), 4, 1, B, self._N,
+                                                       _lib.current_raw_stream(self._dev)), 'gg_batch_symmetry_policy')
+        return self._priors_back
 
     @property
     def iterations_done(self):
@@ -1527,11 +1612,17 @@ class PuctSearch:
             _lib.check(lib.gg_batch_play_moves_tracked(lp, mp, None, R * L, N, 1, stream), 'gg_batch_play_moves_tracked')
             if self._feat is None:
                 _lib.check(lib.gg_batch_untrack_states(lp, sp, R * L, N, stream), 'gg_batch_untrack_states')
-            else:   # (sp: the planes)
+            elif self._sym is None:   # (sp: the planes)
                 _lib.check(lib.gg_batch_features_tracked(lp, sp, self._feat[1], R * L, N, stream), 'gg_batch_features_tracked')
+            else:
+                op = self._draw_orient(R * L, stream)
+                _lib.check(lib.gg_batch_features_tracked_oriented(lp, op, sp, self._feat[1], R * L, N, stream),
+                           'gg_batch_features_tracked_oriented')
             _lib.check(lib.gg_puct_legal(lp, ip, R * L, N, gp, vp, stream), 'gg_puct_legal')
+            if self._sym is not None:
+                self._turn_legal(op, R * L, stream)
         self._pending = True
-        return self._states, self._legal
+        return self._states, (self._legal if self._sym is None else self._legal_view)
 
     def _backup_leaves(self, priors, values):
         R, N, L, A = self._R, self._N, self._L, self._N * self._N + 1
@@ -1539,6 +1630,8 @@ class PuctSearch:
         if tuple(priors.shape) != (B, A) or values.numel() != B:
             raise ValueError('need priors [%d, %d] and values [%d] (got %s, %s)' % (B, A, B, tuple(priors.shape), tuple(values.shape)))
         if R:
+            if self._sym is not None:
+                priors = self._turn_priors_back(priors, B)
             boards, _, prior, links, stats, _ = self._tree
             _lib.check(_lib.lib().gg_puct_backup_leaves(R, N, self._C, L, self._komi, _lib.dev_ptr(priors, torch.float32, 'priors'),
                                                         _lib.dev_ptr(values.reshape(B), torch.float32, 'values'), boards, prior,
@@ -1566,11 +1659,16 @@ class PuctSearch:
                        'gg_batch_untrack_states')
             with torch.cuda.device(self._dev):
                 self._legal.copy_(_legal_roots(self._states))
-            if self._feat is not None:
+            if self._feat is not None and self._sym is None:
                 _lib.check(L.gg_batch_features_tracked(lp, _lib.dev_ptr(self._planes, self._feat[0], 'planes'), self._feat[1], R, N,
                                                        stream), 'gg_batch_features_tracked')
+            elif self._feat is not None:
+                op = self._draw_orient(R, stream)
+                _lib.check(L.gg_batch_features_tracked_oriented(lp, op, _lib.dev_ptr(self._planes, self._feat[0], 'planes'),
+                                                                self._feat[1], R, N, stream), 'gg_batch_features_tracked_oriented')
+                self._turn_legal(op, R, stream)
         self._pending = True
-        return (self._states if self._feat is None else self._planes), self._legal
+        return (self._states if self._feat is None else self._planes), (self._legal if self._sym is None else self._legal_view)
 
     def backup(self, priors, values):
         """Step 4: priors float32 [R, A] and values float32 [R] (the value for the player to move at the leaf) of the leaves
@@ -1586,6 +1684,8 @@ class PuctSearch:
         if tuple(priors.shape) != (R, A) or values.numel() != R:
             raise ValueError('need priors [%d, %d] and values [%d] (got %s, %s)' % (R, A, R, tuple(priors.shape), tuple(values.shape)))
         if R:
+            if self._sym is not None:
+                priors = self._turn_priors_back(priors, R)
             boards, _, prior, links, stats, _ = self._tree
             _lib.check(_lib.lib().gg_puct_backup(R, N, self._C, self._komi, _lib.dev_ptr(priors, torch.float32, 'priors'),
                                                  _lib.dev_ptr(values.reshape(R), torch.float32, 'values'), boards, prior, links,
@@ -1776,7 +1876,8 @@ class PuctSearch:
         return acts, p, v
 
 
-def batch_puct(batch_states, iterations, evaluator, c=1.25, komi=0.0, tree=False, leaves=None, capacity=None, features=None):
+def batch_puct(batch_states, iterations, evaluator, c=1.25, komi=0.0, tree=False, leaves=None, capacity=None, features=None,
+               symmetry=None, first_root=0):
     """PUCT search (the AlphaZero search) of `iterations` iterations from every root of batch_states ([R, 6, N, N]) with the
     caller's evaluator -> Puct (device tensors for a device tensor, NumPy arrays for NumPy input).  The loop over PuctSearch.
 
@@ -1825,10 +1926,15 @@ def batch_puct(batch_states, iterations, evaluator, c=1.25, komi=0.0, tree=False
     features (None: the search above, launch for launch; or torch.uint8 / float16 / bfloat16 / float32): the evaluator is
     called as evaluator(planes, legal) with planes [R, 16, N, N] ([R * L, ..]) of that dtype - batch_features of the leaves,
     written by one launch from the tracked leaf boards (PuctSearch) - instead of the byte-plane states.  An evaluator that
-    needs states (playout_evaluator: its attribute needs_states) is refused with ValueError."""
+    needs states (playout_evaluator: its attribute needs_states) is refused with ValueError.
+
+    symmetry (None: the search above, launch for launch; or an integer base seed, with features=): the evaluator sees every
+    leaf - planes and legal - in a random orientation and its priors are turned back (PuctSearch); first_root: the global
+    index of root 0, so that shards by root draw what the whole draws."""
     _puct_komi_guard(evaluator, komi)
     _puct_features_guard(evaluator, features)
-    search = PuctSearch(batch_states, iterations, c, komi, leaves=leaves, capacity=capacity, features=features)
+    search = PuctSearch(batch_states, iterations, c, komi, leaves=leaves, capacity=capacity, features=features, symmetry=symmetry,
+                        first_root=first_root)
     for _ in range(search._I):
         states, legal = search.select()
         priors, values = evaluator(states, legal)
@@ -1842,6 +1948,11 @@ def _puct_komi_guard(evaluator, komi):
         raise ValueError('the evaluator scores its playouts with komi %r, the search its ended leaves with %r' % (ek, komi))
 
 
+def _puct_symmetry_guard(symmetry, features):
+    if symmetry is not None and features is None:   # (before a device is touched)
+        raise ValueError('symmetry turns the planes and legal that features= hands out: give features= too')
+
+
 def _puct_features_guard(evaluator, features):
     if features is not None:
         _feature_dtype(features)
@@ -1849,7 +1960,8 @@ def _puct_features_guard(evaluator, features):
             raise ValueError('the evaluator needs states (needs_states), the search hands out feature planes (features=%r)' % (features,))
 
 
-def puct_play(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, leaves=None, capacity=None, reuse=True, features=None):
+def puct_play(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, leaves=None, capacity=None, reuse=True, features=None,
+              symmetry=None, first_root=0):
     """Play `moves` moves from every root of batch_states ([R, 6, N, N]) with a PUCT search per move -> (actions int64
     [R, moves], the final states uint8 [R, 6, N, N]); device tensors for a device tensor, NumPy arrays for NumPy input.
     Per move: `iterations` rounds of PuctSearch (batch_puct's loop, with `leaves` and `capacity` as there), the move of
@@ -1867,13 +1979,15 @@ def puct_play(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, leav
     shows how full the trees are.  A kept root is already evaluated and is not handed out again, so root noise that the
     evaluator adds would reach only fresh roots: PuctSearch.add_root_noise reaches kept roots too, and puct_selfplay is this
     loop with it, with moves drawn from the visit counts and with the training records.  features: as batch_puct - the
-    evaluator gets (planes, legal)."""
+    evaluator gets (planes, legal).  symmetry, first_root: as batch_puct; with reuse=False the search of move mv draws from
+    the base seed symmetry + mv (a new search would repeat the first one's draws otherwise)."""
     _puct_komi_guard(evaluator, komi)
     _puct_features_guard(evaluator, features)
     moves = int(moves)
     if moves < 0:
         raise ValueError('need moves >= 0 (got %d)' % moves)
-    search = PuctSearch(batch_states, iterations, c, komi, leaves=leaves, capacity=capacity, features=features)
+    search = PuctSearch(batch_states, iterations, c, komi, leaves=leaves, capacity=capacity, features=features, symmetry=symmetry,
+                        first_root=first_root)
     box = search._box
     played = torch.empty((search._R, moves), dtype=_I64, device=box.t.device)
     for mv in range(moves):
@@ -1887,7 +2001,8 @@ def puct_play(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, leav
             search.advance(played[:, mv], check=False)
         else:   # only node 0's boards are played on: the tree goes, so no advance over it; the states stay on the device
             box.t = search._played_states(played[:, mv])
-            search = PuctSearch(box, iterations, c, komi, leaves=leaves, capacity=capacity, features=features)
+            search = PuctSearch(box, iterations, c, komi, leaves=leaves, capacity=capacity, features=features,
+                                symmetry=None if symmetry is None else int(symmetry) + mv + 1, first_root=first_root)
     return _back(box, played), box.back(search._root_states())
 
 
@@ -1922,7 +2037,7 @@ that ended, 0 for one still running), lengths (int32 [R]: moves played), final_s
 
 
 def puct_selfplay(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, leaves=None, capacity=None, noise=None,
-                  eps=0.25, sample_moves=0, seed=20260927, first_game=0, record_states=False, features=None):
+                  eps=0.25, sample_moves=0, seed=20260927, first_game=0, record_states=False, features=None, symmetry=None):
     """Self-play games for training: `moves` moves from every root of batch_states ([R, 6, N, N]) with a PUCT search per move
     on the kept tree -> SelfPlay (device tensors for a device tensor, NumPy arrays for NumPy input).  puct_play's
     reuse=True loop (`iterations` rounds per move with `leaves` and `capacity` as there, then PuctSearch.advance) with
@@ -1943,7 +2058,10 @@ def puct_selfplay(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, 
     positions from the roots with batch_play_moves(states, actions).  Device memory of the records: pi takes
     4 * R * moves * A bytes (189 MB for 1 024 roots x 128 moves at 19x19), states 6 N^2 * R * moves.  moves = 0 or R = 0:
     no device call, empty records of these shapes.  features: as batch_puct - the evaluator gets (planes, legal); the records
-    (states included) are unchanged, a trainer applies batch_features to the recorded positions."""
+    (states included) are unchanged.  symmetry (None, or an integer base seed, with features=): every leaf evaluation in a
+    random orientation, as batch_puct; the search gets first_root=first_game, so shards concatenate here too.  The records stay
+    in the boards' own frame.  A trainer takes its samples from the records with selfplay_batch: the planes of the recorded
+    positions and the policy targets, in any of the eight orientations."""
     _puct_komi_guard(evaluator, komi)
     _puct_features_guard(evaluator, features)
     moves, sample_moves, eps = int(moves), int(sample_moves), float(eps)
@@ -1955,6 +2073,7 @@ def puct_selfplay(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, 
         raise ValueError('need 0 <= eps <= 1 (got %r)' % eps)
     if noise is not None and not callable(noise):
         raise ValueError('noise must be None or a callable noise(move, legal) -> float32 [R, A]')
+    _puct_symmetry_guard(symmetry, features)
     box = batch_states if isinstance(batch_states, _Box) else _Box(batch_states)
     st = box.t
     if st.dim() != 4 or st.shape[1] != govars.NUM_CHNLS or st.shape[2] != st.shape[3]:
@@ -1971,7 +2090,7 @@ def puct_selfplay(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, 
     before = torch.empty((R, moves, govars.NUM_CHNLS, N, N), dtype=_U8, device=dev) if record_states else None
     if not R or not moves:
         return _back(box, SelfPlay(played, pis, vals, outcome, lengths, st, before))
-    search = PuctSearch(box, I, c, komi, leaves=leaves, capacity=capacity, features=features)
+    search = PuctSearch(box, I, c, komi, leaves=leaves, capacity=capacity, features=features, symmetry=symmetry, first_root=first_game)
     rng = rng_seed(R, seed, first_game, device=dev)
     ones, todo = torch.ones(R, dtype=_U8, device=dev), torch.empty(R, dtype=_U8, device=dev)
     for mv in range(moves):
@@ -2002,12 +2121,14 @@ def puct_selfplay(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, 
 def puct(state, iterations, evaluator, **kw):
     """batch_puct of one state [6, N, N] -> Puct of [N*N + 1] vectors and scalars (tree fields [iterations + 1]); the evaluator
     still sees a batch of one."""
+    _puct_symmetry_guard(kw.get('symmetry'), kw.get('features'))
     return _single(batch_puct, state, iterations, evaluator, **kw)
 
 
 def puct_actions(batch_states, iterations, evaluator, **kw):
     """The PUCT move of every root -> int64 [R]: the legal root child with the most visits after batch_puct(batch_states,
     iterations, evaluator, **kw); ties go to the lowest action, a root without a legal move gives -1."""
+    _puct_symmetry_guard(kw.get('symmetry'), kw.get('features'))
     box = _Box(batch_states)
     res = batch_puct(box.t, iterations, evaluator, **kw)
     return _best_legal(box, res.legal, res.visits.to(_I64))
@@ -2190,3 +2311,113 @@ def symmetry_actions(actions, orient, board_size):
     r = torch.where((o & 4) != 0, N - 1 - c1, r1)
     c = torch.where((o & 4) != 0, r1, c1)
     return torch.where(a >= N * N, a, r * N + c).to(_I32)
+
+
+POLICY_DTYPES = {torch.bool: 1, torch.uint8: 1, torch.float16: 2, torch.bfloat16: 2, torch.float32: 4, torch.int32: 4}   # element bytes
+
+
+def _policy_size(A):
+    """N of a row of A = N*N + 1 elements with N in [2, 19]; ValueError otherwise."""
+    N = int(round(math.sqrt(max(int(A) - 1, 0))))
+    if N * N + 1 != A or not 2 <= N <= 19:
+        raise ValueError('rows over the actions hold N*N + 1 elements with N in [2, 19] (got %d)' % A)
+    return N
+
+
+def batch_symmetry_policy(policy, orient, inverse=False, out=None):
+    """Turn vectors over the actions - priors, legal masks, visit-count targets - with the board (gg_batch_symmetry_policy).
+    policy: [B, A] of bool / uint8 / float16 / bfloat16 / float32 / int32, A = N*N + 1 with N in [2, 19]; orient: int [B], a
+    tensor or an array (batch_symmetry's orientations, only orient & 7 is read).  With T = symmetry_actions(., orient[b], N):
+    inverse=False gives out[b, T(a)] = policy[b, a] - the first N*N elements turned as batch_symmetry turns a one-plane image,
+    the pass kept: a vector over the board becomes the vector over the view; inverse=True gives out[b, a] = policy[b, T(a)]:
+    a vector over the view (what a network answers on oriented planes) comes back to the board.  Elements move as bit
+    patterns.  out: a contiguous device tensor of policy's shape and dtype that does not overlap it; slices of larger
+    tensors are fine on both sides, no alignment is needed.  Anything else raises ValueError before a device is touched.
+    NumPy in gives NumPy out (not bfloat16).  One launch, no synchronisation."""
+    is_np = not isinstance(policy, torch.Tensor)
+    if is_np:
+        policy = np.asarray(policy)
+        if policy.dtype not in (np.bool_, np.uint8, np.float16, np.float32, np.int32):
+            raise ValueError('policy must be bool, uint8, float16, float32 or int32 (got %s)' % policy.dtype)
+    elif policy.dtype not in POLICY_DTYPES:
+        raise ValueError('policy must be bool, uint8, float16, bfloat16, float32 or int32 (got %s)' % policy.dtype)
+    if policy.ndim != 2:
+        raise ValueError('policy must be [B, N*N + 1] (got %s)' % (tuple(policy.shape),))
+    B, A = policy.shape
+    N = _policy_size(A)
+    _orient_arg(orient, B)
+    if is_np:
+        if out is not None:
+            raise ValueError('out needs a device tensor as policy')
+        policy = torch.from_numpy(np.ascontiguousarray(policy)).to(_device())
+    elif not policy.is_cuda:
+        raise ValueError('policy must be a device tensor or a NumPy array')
+    if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != policy.dtype or tuple(out.shape) != (B, A)
+                            or out.device != policy.device or not out.is_contiguous()):
+        raise ValueError('out must be a contiguous %s [%d, %d] tensor on policy\'s device' % (policy.dtype, B, A))
+    policy = policy.contiguous()
+    es = POLICY_DTYPES[policy.dtype]
+    if out is None:
+        out = torch.empty((B, A), dtype=policy.dtype, device=policy.device)
+    elif B and out.data_ptr() < policy.data_ptr() + B * A * es and policy.data_ptr() < out.data_ptr() + B * A * es:
+        raise ValueError('out overlaps policy')
+    o = _actions_tensor(orient, B, policy.device)
+    _lib.check(_lib.lib().gg_batch_symmetry_policy(_lib.dev_ptr(policy, policy.dtype, 'policy'), _lib.dev_ptr(o, _I32, 'orient'),
+                                                   _lib.dev_ptr(out, out.dtype, 'out'), es, 1 if inverse else 0, B, N,
+                                                   _lib.stream_ptr(policy.device)), 'gg_batch_symmetry_policy')
+    return out.cpu().numpy() if is_np else out
+
+
+def batch_draw_orient(rng):
+    """One orientation per generator -> int32 [B] on rng's device (gg_batch_draw_orient): rng is rng_seed's int64 [B] device
+    tensor, advanced in place by one step per row; orient[b] = the top three bits of the generator's output.  One launch."""
+    if not isinstance(rng, torch.Tensor) or rng.dtype != _I64 or rng.dim() != 1 or not rng.is_contiguous():
+        raise ValueError('rng must be a contiguous int64 [B] device tensor (gogame.rng_seed)')
+    B = rng.shape[0]
+    orient = torch.empty(B, dtype=_I32, device=rng.device)
+    _lib.check(_lib.lib().gg_batch_draw_orient(_lib.dev_ptr(rng, _I64, 'rng'), _lib.dev_ptr(orient, _I32, 'orient'), B,
+                                               _lib.stream_ptr(rng.device)), 'gg_batch_draw_orient')
+    return orient
+
+
+def selfplay_targets(record, games, moves):
+    """The value target and the validity of recorded positions -> (z float32 [B], valid bool [B]), plain torch on the
+    record's device.  record: a SelfPlay made with record_states=True (ValueError if record.states is None); games, moves:
+    int [B], position i is move moves[i] of game games[i].  z = the outcome from the point of view of the player to move at
+    that position: +outcome if black moves (plane 2 of the recorded state is clear), else -outcome; valid = moves <
+    lengths[games]: the game had not ended there."""
+    if record.states is None:
+        raise ValueError('the record has no states: run puct_selfplay with record_states=True')
+    t = lambda x, dev=None: (x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))).to(device=dev)
+    states = t(record.states)
+    dev = states.device
+    g, m = t(games, dev).to(_I64), t(moves, dev).to(_I64)
+    if g.dim() != 1 or g.shape != m.shape:
+        raise ValueError('games and moves must be int [B] (got %s, %s)' % (tuple(g.shape), tuple(m.shape)))
+    white = states[g, m, govars.TURN_CHNL, 0, 0] != 0
+    outcome = t(record.outcome, dev)[g].to(torch.float32)
+    return torch.where(white, -outcome, outcome), m < t(record.lengths, dev)[g].to(_I64)
+
+
+def selfplay_batch(record, games, moves, orient, dtype=torch.float16):
+    """Training samples from a self-play record, in one of the eight orientations each -> (planes [B, 16, N, N] of `dtype`,
+    pi [B, A] float32, z float32 [B], valid bool [B]).  record: a SelfPlay of puct_selfplay(.., record_states=True)
+    (ValueError if record.states is None); games, moves, orient: int [B] - sample i is the position before move moves[i] of
+    game games[i], seen in view orient[i].  planes = batch_features of the recorded position with orient (one launch), pi =
+    the recorded visit-count target turned with batch_symmetry_policy - both in the view; z, valid: selfplay_targets.  The
+    eightfold augmentation of a sample is this call with orient = 0 .. 7.  Nothing synchronises; device tensors, or NumPy
+    arrays for a NumPy record (through the device)."""
+    _feature_dtype(dtype)
+    z, valid = selfplay_targets(record, games, moves)
+    is_np = not isinstance(record.states, torch.Tensor)
+    B = z.shape[0]
+    _orient_arg(orient, B)
+    if is_np and dtype == torch.bfloat16:
+        raise ValueError('NumPy has no bfloat16: pass a device record, or another dtype')
+    dev = _device() if is_np else record.states.device
+    t = lambda x: (x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))).to(device=dev)
+    g, m = t(games).to(_I64), t(moves).to(_I64)
+    planes = batch_features(t(record.states)[g, m], dtype, orient=orient)
+    pi = batch_symmetry_policy(t(record.pi)[g, m].to(torch.float32), orient)
+    res = (planes, pi, z.to(dev), valid.to(dev))
+    return tuple(x.cpu().numpy() for x in res) if is_np else res

@@ -714,6 +714,44 @@ int32_t gg_batch_group_liberties(const uint8_t *states, uint8_t *libs, int64_t B
 int32_t gg_batch_features(const uint8_t *states, void *out, int32_t out_dtype, int64_t B, int32_t N, void *hip_stream);
 int32_t gg_batch_features_tracked(const uint32_t *tracked, void *out, int32_t out_dtype, int64_t B, int32_t N, void *hip_stream);
 
+/*
+ * Symmetry-aware network input and output: the planes a network reads in one of the eight orientations of
+ * gg_batch_symmetry, vectors over the actions turned forward and back, and the draw of the orientations.  Orientation o:
+ * bit 0 flips the columns, then bit 1 flips the rows, then bit 2 rotates by 90 degrees; only o & 7 is read.
+ *
+ *   gg_batch_features_oriented / gg_batch_features_tracked_oriented    orient int32 [B]
+ *     out[b] is view orient[b] of gg_batch_features(states)[b] (gg_batch_features_tracked(tracked)[b]): every one of the
+ *     sixteen planes turned alike, as gg_batch_symmetry turns a uint8 image of sixteen channels.  All sixteen planes are
+ *     geometric, plane 3 of the input is taken as given and the ko point moves with the board, so out[b] is ALSO
+ *     gg_batch_features of the turned position: of gg_batch_symmetry(states, orient)[b], and of
+ *     gg_batch_symmetry_rows(tracked, 5, orient)[b].  The inputs are not changed.  One launch: the boards are turned in
+ *     registers after the load.  Checks: those of gg_batch_features, the same codes in the same order, GG_E_NULLPTR also
+ *     for orient.
+ *
+ *   gg_batch_symmetry_policy    in, out: [B][A] elements of elem_size bytes, A = N*N + 1; orient int32 [B]
+ *     Rows over the actions - priors, legal masks, visit-count targets - moved as bit patterns (elem_size 1, 2 or 4: bool,
+ *     uint8, float16, bfloat16, float32, int32; NaN payloads survive).  With T(a) = the action that marks on view
+ *     orient[b] the point action a marks on the board (the pass stays the pass):
+ *       inverse == 0:  out[b][T(a)] = in[b][a]   - the first N*N elements turned as a one-plane image by gg_batch_symmetry's
+ *                                                  rule, element N*N kept: a vector over the board becomes one over the view
+ *       inverse != 0:  out[b][a] = in[b][T(a)]   - a vector over the view comes back to the board
+ *     in and out must not overlap; neither needs any alignment (every access to memory is an aligned 16-byte access or a
+ *     single byte inside the rows).  GG_E_BADSIZE for N outside [2, 19], B < 0 or an elem_size other than 1, 2, 4; B = 0 is
+ *     no work; GG_E_NULLPTR.  One launch.
+ *
+ *   gg_batch_draw_orient        rng uint64 [B] (gg_rng_seed's generator), orient int32 [B]
+ *     orient[b] = u >> 61 with u the generator's next output - one ply step, rng[b] advances once: gg_puct_root_policy's
+ *     draw ((u >> 32) * S) >> 32 with S = 8.  GG_E_BADSIZE for B < 0; B = 0 is no work; GG_E_NULLPTR.  One launch.
+ * Every call queues its launch on hip_stream and never synchronises.
+ */
+int32_t gg_batch_features_oriented(const uint8_t *states, const int32_t *orient, void *out, int32_t out_dtype, int64_t B, int32_t N,
+                                   void *hip_stream);
+int32_t gg_batch_features_tracked_oriented(const uint32_t *tracked, const int32_t *orient, void *out, int32_t out_dtype, int64_t B,
+                                           int32_t N, void *hip_stream);
+int32_t gg_batch_symmetry_policy(const void *in, const int32_t *orient, void *out, int32_t elem_size, int32_t inverse, int64_t B,
+                                 int32_t N, void *hip_stream);
+int32_t gg_batch_draw_orient(uint64_t *rng, int32_t *orient, int64_t B, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
