@@ -40,12 +40,12 @@ void launch_rollout5_policy(int N, uint8_t *st, uint64_t *rng, int32_t *last_act
 }  // namespace gg
 
 #ifdef GG_AB_SWEEPS
-// A/B builds only: read and clear the sweep counters of k_rollout5's flood batches
-extern "C" int32_t gg_ab_sweeps_read_r5(unsigned long long *out2) {
+// A/B builds only: read and clear the counters of k_rollout5's flood batches (gg_v5.h: gg_sweeps5)
+extern "C" int32_t gg_ab_sweeps_read_r5(unsigned long long *out10) {
   if (hipDeviceSynchronize() != hipSuccess) return 1;
-  if (hipMemcpyFromSymbol(out2, HIP_SYMBOL(gg::gg_sweeps), 16) != hipSuccess) return 2;
-  unsigned long long z[2] = {0, 0};
-  return hipMemcpyToSymbol(HIP_SYMBOL(gg::gg_sweeps), z, 16) == hipSuccess ? 0 : 3;
+  if (hipMemcpyFromSymbol(out10, HIP_SYMBOL(gg::gg_sweeps5), 80) != hipSuccess) return 2;
+  unsigned long long z[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  return hipMemcpyToSymbol(HIP_SYMBOL(gg::gg_sweeps5), z, 80) == hipSuccess ? 0 : 3;
 }
 #endif
 

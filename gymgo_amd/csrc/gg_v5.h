@@ -116,13 +116,63 @@ __device__ __forceinline__ void kth_set_bit10(const uint32_t (&v)[10], const uin
   pos = ps;
 }
 
+// the first closure test of a flood batch comes after this many sweeps (from then on every sweep is followed by its test).
+// 19x19: after down + up - 2.03 sweeps up to the weak closure instead of 3.00; 26 % of the batches then have an unsettled
+// lane, open in the ONE direction the last sweep did not close, and run on for 1.07 sweeps (flood_jobs resumes in place): 2.31
+// sweeps per batch in all against 3.02, 1.204 -> 1.154 ms per launch of 65 536 games x 256 plies (tools/exp/r5_sweeps.py,
+// profiles/r12_sweeps.txt).  9x9 and 13x13 keep the test after down + up + down (the early test measured -1.5 % / -3 % there
+// in round 6) and their restart form, flood_jobs_restart.  (A/B builds: -DGG_AB_FLOODK=3 for the three-sweep schedule at 19x19.)
+template <int R>
+constexpr int flood_first_test() {
+#ifdef GG_AB_FLOODK
+  return R == 19 ? GG_AB_FLOODK : 3;
+#else
+  return R == 19 ? 2 : 3;
+#endif
+}
+
+#ifdef GG_AB_SWEEPS
+// A/B builds only (make ab EXTRA=-DGG_AB_SWEEPS, tools/exp/r5_sweeps.py), per flood batch of k_rollout5: [0] sweeps up to the
+// weak closure of the G lanes, [1] batches, [2] batches with an unsettled lane at that point, [3 .. 6] those batches by the
+// sweeps they run on until no lane is unsettled (1, 2, 3, 4 or more), [7] / [8] unsettled lanes at that point that flood a
+// G / an opponent group, [9] sweeps run on in all
+static __device__ unsigned long long gg_sweeps5[10];
+#endif
+
+// liberties (dilate & empty) of the group gt[], SATURATED: min(count, 2) - all any caller uses; m[] = the rows of its colour,
+// ot[] = the other colour's rows (read from LDS together with m[], BEFORE the flood: read behind it they cost the lane a round
+// trip).  Nothing is counted: o = the OR of the liberty rows, d = the columns that hold a liberty in two rows (a liberty row
+// ANDed with the OR of the rows before it, one v_bitop3 per row); two or more liberties iff d != 0 or o has two bits.  Three
+// chains over the rows r % 3, joined by a majority (a column set in two chains).  (Counting took nineteen v_bcnt, 4 cycles each.)
+template <int R>
+__device__ __forceinline__ uint32_t job_liberties(const uint32_t (&gt)[R], const uint32_t (&ot)[R], const uint32_t (&m)[R]) {
+  constexpr uint32_t FULLROW = (1u << R) - 1u;
+  uint32_t o3[3] = {0u, 0u, 0u}, d3[3] = {0u, 0u, 0u};
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const uint32_t e = B3(ot[r], m[r], FULLROW, ~(TA | TB) & TC & 0xFF);   // empty points
+    const uint32_t up = r > 0 ? gt[r - 1] : 0u, dn = r + 1 < R ? gt[r + 1] : 0u;
+    const uint32_t dd = B3(shl1(gt[r]), gt[r] >> 1, up, T_OR3);
+    const uint32_t l = B3(dd, dn, e, (TA | TB) & TC);
+    d3[r % 3] = B3(l, o3[r % 3], d3[r % 3], T_ANDOR);
+    o3[r % 3] = B3(l, o3[r % 3], 0u, T_OR3);
+  }
+  const uint32_t o = B3(o3[0], o3[1], o3[2], T_OR3);
+  const uint32_t d = B3(d3[0], d3[1], d3[2], T_OR3) | B3(o3[0], o3[1], o3[2], T_MAJ);
+  const uint32_t two = B3(o - 1u, o, d, T_ANDOR);   // o & (o - 1) | d
+  return (o != 0u ? 1u : 0u) + (two != 0u ? 1u : 0u);
+}
+
+// The 9x9 and 13x13 form of the batch (flood_jobs below is the 19x19 one; with the SAME schedule the one-loop form measured
+// 2.3 % slower than this one at 19x19, and these sizes keep the three-sweep schedule: docs/history/r12.md): a first call with WEAK and need = the G lanes, the
+// liberties, and for the lanes left unsettled a second call from the re-encoded fill.
 // flood2_serial (gg_common.h; seeds with their odd rows bit-reversed) for a batch of JOBS of which only some need a fixed
 // point: the sweeps go on while a lane with `need` is open.  WEAK: such a lane counts as open only where the fill could still
 // grow into a stone that is NOT in `mm` (the rows of M, the stones whose group had >= 2 liberties before the move).  res[] =
 // the fill as the last closure test saw it, normal bit order; `open` = what that test found for this lane (0: its fill is
 // closed).  A lane whose flood is cut short holds a PART of its group - every liberty of the part is a liberty of the group.
 template <int R, bool WEAK>
-__device__ __forceinline__ void flood_jobs(const uint32_t (&m)[R], const uint32_t (&mrev)[R], uint32_t (&f)[R], uint32_t (&res)[R],
+__device__ __forceinline__ void flood_jobs_restart(const uint32_t (&m)[R], const uint32_t (&mrev)[R], uint32_t (&f)[R], uint32_t (&res)[R],
                                            bool need, const uint32_t (&mm)[R], uint32_t &open) {
   int sweeps = 0;
 #pragma unroll 1
@@ -166,35 +216,106 @@ __device__ __forceinline__ void flood_jobs(const uint32_t (&m)[R], const uint32_
       if (__ballot((WEAK ? opw : op) != 0 && need) == 0) { sweeps = 2 * it + 2; break; }
     }
   }
-#ifdef GG_AB_SWEEPS
-  { int l_; asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l_));
-    if (l_ == 0) { atomicAdd(&gg_sweeps[0], (unsigned long long)sweeps); atomicAdd(&gg_sweeps[1], 1ull); } }
-#endif
   (void)sweeps;
 }
 
-// liberties (dilate & empty) of the group gt[], SATURATED: min(count, 2) - all any caller uses; m[] = the rows of its colour,
-// ot[] = the other colour's rows (read from LDS together with m[], BEFORE the flood: read behind it they cost the lane a round
-// trip).  Nothing is counted: o = the OR of the liberty rows, d = the columns that hold a liberty in two rows (a liberty row
-// ANDed with the OR of the rows before it, one v_bitop3 per row); two or more liberties iff d != 0 or o has two bits.  Three
-// chains over the rows r % 3, joined by a majority (a column set in two chains).  (Counting took nineteen v_bcnt, 4 cycles each.)
+// flood2_serial (gg_common.h; seeds with their odd rows bit-reversed) for a batch of JOBS of which only some need a fixed
+// point, from the seeds to the liberty counts: returns min(liberties, 2) of res[] = the fill as the last closure test saw
+// it, normal bit order.  A lane whose flood is cut short holds a PART of its group - every liberty of the part is a liberty
+// of the group.  One loop, sweeps alternately down and up, the fill in f[] in the alternating bit order from the first
+// sweep to the last (a test reads f[], it never writes it); from sweep flood_first_test<R>() on every sweep is followed by
+// its closure test (after a down sweep only upwards, after an up sweep only downwards):
+//  * until the lanes with isG are WEAKLY closed - open only where the fill could still grow into a stone that is NOT in mm
+//    (the rows of M, the stones whose group had >= 2 liberties before the move) - a test ends there;
+//  * then the liberties of every lane's part are taken, and a lane that is open (in the strong sense, G or not) with fewer
+//    than two of them is UNSETTLED: its group may be captured or leave M, its full extent matters.  While there is one, the
+//    loop goes on in place - the next sweep of the alternation, its test, the liberties again.  Such a lane is open in the one
+//    direction the last sweep did not close: one more sweep settles nearly all of them.
+// What becomes of the lanes that were settled while others sweep on: nothing is masked and nothing latched - every lane
+// sweeps, and res[] / the count are those of the LAST test for all of them (as the restart this replaces recomputed them
+// for every lane).  That is exact because being settled is monotone in the fill and what a settled lane hands on does not
+// depend on how far its fill got: a closed fill is a fixed point of a sweep; a part with two liberties keeps them as it
+// grows (the count is saturated), and then an opponent lane hands on nothing at all while a G lane hands on a part of G
+// that holds all of G's stones outside M - the weak closure, which further growth through stones of M cannot undo (a group
+// outside M hangs on q stone by stone, never behind a group of M) - and phase 3 only ORs it into M.  The same holds for
+// the lanes of a batch that merely wait for its slowest flood, with this schedule as with any other.
 template <int R>
-__device__ __forceinline__ uint32_t job_liberties(const uint32_t (&gt)[R], const uint32_t (&ot)[R], const uint32_t (&m)[R]) {
-  constexpr uint32_t FULLROW = (1u << R) - 1u;
-  uint32_t o3[3] = {0u, 0u, 0u}, d3[3] = {0u, 0u, 0u};
+__device__ __forceinline__ uint32_t flood_jobs(const uint32_t (&m)[R], const uint32_t (&mrev)[R], uint32_t (&f)[R], uint32_t (&res)[R],
+                                               const uint32_t (&ot)[R], const uint32_t (&mm)[R], bool isG, bool have) {
+  constexpr int K = flood_first_test<R>();
+  static_assert(K >= 1 && K <= 3, "the first closure test comes after one, two or three sweeps");
+  uint32_t cnt = 0;
+  bool resumed = false;   // (wave-uniform) the G lanes are weakly closed: every test from here on is followed by the liberties
+#ifdef GG_AB_SWEEPS
+  int sw_ = 0, sw0_ = 0;
+  uint32_t ng_ = 0, no_ = 0;
+#define GG_SW5_SWEEP() (++sw_)
+#else
+#define GG_SW5_SWEEP() ((void)0)
+#endif
+  // after a test (op / opw = where this lane is open / weakly open): is the batch done?
+  auto done = [&](uint32_t op, uint32_t opw) -> bool {
+    if (!resumed && __ballot(opw != 0u && isG) != 0) return false;
+    cnt = job_liberties<R>(res, ot, m);
+    const bool unsettled = have && op != 0u && cnt < 2u;
+    const uint64_t u = __ballot(unsettled);
+#ifdef GG_AB_SWEEPS
+    if (!resumed) { sw0_ = sw_; ng_ = (uint32_t)__popcll(__ballot(unsettled && isG)); no_ = (uint32_t)__popcll(u) - ng_; }
+#endif
+    resumed = true;
+    return u == 0;
+  };
+#pragma unroll 1
+  for (int it = 0; it < R * R; ++it) {
 #pragma unroll
-  for (int r = 0; r < R; ++r) {
-    const uint32_t e = B3(ot[r], m[r], FULLROW, ~(TA | TB) & TC & 0xFF);   // empty points
-    const uint32_t up = r > 0 ? gt[r - 1] : 0u, dn = r + 1 < R ? gt[r + 1] : 0u;
-    const uint32_t dd = B3(shl1(gt[r]), gt[r] >> 1, up, T_OR3);
-    const uint32_t l = B3(dd, dn, e, (TA | TB) & TC);
-    d3[r % 3] = B3(l, o3[r % 3], d3[r % 3], T_ANDOR);
-    o3[r % 3] = B3(l, o3[r % 3], 0u, T_OR3);
+    for (int r = 0; r < R; ++r) FLOOD_VISIT(r, r - 1, (r & 1) != 0);       // down: domain (r&1) -> ((r+1)&1)
+    GG_SW5_SWEEP();
+    if (K <= 1 || it > 0) {
+      uint32_t op = 0, opw = 0, above = 0;
+#pragma unroll
+      for (int r = R - 1; r >= 0; --r) {
+        const uint32_t g = ((r + 1) & 1) ? __brev(f[r]) : f[r];
+        res[r] = g;
+        if (r < R - 1) {
+          const uint32_t t = B3(above, m[r], g, T_AND_ANDN);   // a filled stone below a fillable, unfilled one
+          op |= t;
+          opw = B3(t, mm[r], opw, (TA & ~TB & 0xFF) | TC);
+        }
+        above = g;
+      }
+      if (done(op, opw)) break;
+    }
+#pragma unroll
+    for (int r = R - 1; r >= 0; --r) FLOOD_VISIT(r, r + 1, ((r + 1) & 1) != 0);  // up: domain ((r+1)&1) -> (r&1)
+    GG_SW5_SWEEP();
+    if (K <= 2 || it > 0) {
+      uint32_t op = 0, opw = 0, below = 0;
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const uint32_t g = (r & 1) ? __brev(f[r]) : f[r];
+        res[r] = g;
+        if (r > 0) {
+          const uint32_t t = B3(below, m[r], g, T_AND_ANDN);
+          op |= t;
+          opw = B3(t, mm[r], opw, (TA & ~TB & 0xFF) | TC);
+        }
+        below = g;
+      }
+      if (done(op, opw)) break;
+    }
   }
-  const uint32_t o = B3(o3[0], o3[1], o3[2], T_OR3);
-  const uint32_t d = B3(d3[0], d3[1], d3[2], T_OR3) | B3(o3[0], o3[1], o3[2], T_MAJ);
-  const uint32_t two = B3(o - 1u, o, d, T_ANDOR);   // o & (o - 1) | d
-  return (o != 0u ? 1u : 0u) + (two != 0u ? 1u : 0u);
+#undef GG_SW5_SWEEP
+#ifdef GG_AB_SWEEPS
+  { int l_; asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l_));
+    if (l_ == 0) {
+      const int ex_ = sw_ - sw0_;
+      atomicAdd(&gg_sweeps5[0], (unsigned long long)sw0_); atomicAdd(&gg_sweeps5[1], 1ull);
+      if (ng_ + no_) { atomicAdd(&gg_sweeps5[2], 1ull); atomicAdd(&gg_sweeps5[2 + (ex_ < 4 ? ex_ : 4)], 1ull); }
+      atomicAdd(&gg_sweeps5[7], (unsigned long long)ng_); atomicAdd(&gg_sweeps5[8], (unsigned long long)no_);
+      atomicAdd(&gg_sweeps5[9], (unsigned long long)ex_);
+    } }
+#endif
+  return cnt;
 }
 
 #ifdef GG_AB_P3

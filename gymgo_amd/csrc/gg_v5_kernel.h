@@ -495,27 +495,34 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
           }
           GG_PROF(1);
           // Which floods must reach their fixed point inside the batch's loop?  (Its length is the longest of its floods: 4.21
-          // sweeps per batch when all 1.56 floods per board count, 3.87 when only G's 0.6 per board do, 3.00 - the minimum - with
-          // the weak closure below, tools/exp/r5_sweeps.py: 1.445 -> 1.415 -> 1.349 ms per launch of 65 536 games x 256 plies;
-          // 1.8 % of the batches have a lane that floods on afterwards.)
+          // sweeps per batch when all 1.56 floods per board count, 3.87 when only G's 0.6 per board do, 3.00 with the weak
+          // closure below and a first test after three sweeps, tools/exp/r5_sweeps.py: 1.445 -> 1.415 -> 1.349 ms per launch of
+          // 65 536 games x 256 plies; flood_first_test<R>() in gg_v5.h says after which sweep the first test comes today.)
           //  * An OPPONENT group never: cut short, the part found so far either has two liberties - liberties of the whole
           //    group, which keeps its class: phase 3 never sees it - or fewer, and then the group may be captured or leave M
-          //    and its full extent matters: that lane floods on afterwards (below; groups with < 2 liberties are small).
+          //    and its full extent matters: the lane is unsettled and the loop goes on for it (groups with < 2 liberties are small).
           //  * The mover's group G only as far as its stones OUTSIDE M go: with two liberties found G joins M whole, and what the
           //    cut-short flood has not reached of it are stones of groups that were in M already (a group in atari that q
           //    connects hangs on q itself, stone by stone outside M: the weak closure holds it whole); with fewer, as above.
+          // 19x19: while a lane is unsettled the loop goes on IN PLACE, one sweep and its test at a time (flood_jobs): no
+          // restart from a re-encoded fill, the liberties taken once per test.
           // (the two-chain flood2_dual: 1.758 against 1.579 ms per launch - one more sweep-equivalent, as in k_rollout4)
-          uint32_t open = 0;
-          flood_jobs<R, true>(m, mrev, f, res, isG != 0u, mm, open);
-          GG_PROF(2);
-          cnt = job_liberties<R>(res, ot, m);
-          const bool unsettled = have && open != 0u && cnt < 2u;
-          if (__ballot(unsettled)) {
-            // (the sweeps resume from the fill as the last test left it: normal bit order -> odd rows reversed)
-#pragma unroll
-            for (int r = 0; r < R; ++r) f[r] = (r & 1) ? __brev(res[r]) : res[r];
-            flood_jobs<R, false>(m, mrev, f, res, unsettled, mm, open);
+          if constexpr (R == 19) {
+            cnt = flood_jobs<R>(m, mrev, f, res, ot, mm, isG != 0u, have);
+            GG_PROF(2);   // (with the liberties, which the loop takes after its tests)
+          } else {
+            // (9x9, 13x13: the restart form - first test after three sweeps, unsettled lanes flood on from the re-encoded fill)
+            uint32_t open = 0;
+            flood_jobs_restart<R, true>(m, mrev, f, res, isG != 0u, mm, open);
+            GG_PROF(2);
             cnt = job_liberties<R>(res, ot, m);
+            const bool unsettled = have && open != 0u && cnt < 2u;
+            if (__ballot(unsettled)) {
+#pragma unroll
+              for (int r = 0; r < R; ++r) f[r] = (r & 1) ? __brev(res[r]) : res[r];
+              flood_jobs_restart<R, false>(m, mrev, f, res, unsettled, mm, open);
+              cnt = job_liberties<R>(res, ot, m);
+            }
           }
         }
         const uint32_t lib2 = cnt < 2u ? cnt : 2u;
