@@ -945,6 +945,96 @@ def batch_features_tracked(tracked, dtype=torch.float16, out=None, orient=None):
     return planes
 
 
+# ---------------------------------------------------------------- pass-alive (Benson) life planes
+LIFE_PLANES = 4   # gg_life_planes() of include/gymgo_amd.h
+LIFE_NAMES = ('own_alive', 'opp_alive', 'own_safe', 'opp_safe')
+
+
+def _life_out(out, shape, dtype, device=None):
+    """out=None, or a contiguous device tensor of exactly this shape and dtype (on `device` when given)."""
+    if out is None:
+        return
+    if (not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != dtype or tuple(out.shape) != tuple(shape)
+            or not out.is_contiguous() or (device is not None and out.device != device)):
+        raise ValueError('out must be a contiguous %s %s tensor on the states\' device (got %s)' % (
+            dtype, list(shape), '%s %s on %s' % (out.dtype, list(out.shape), out.device) if isinstance(out, torch.Tensor) else type(out)))
+
+
+def _life_launch(name, boards, boards_dtype, orient, planes, dtype, code, want_settled, B, N):
+    """One launch of gg_batch_life / gg_batch_life_tracked on the boards' device -> the settled bytes or None."""
+    dev = boards.device
+    flags = torch.empty(B, dtype=_U8, device=dev) if want_settled else None
+    o = None if orient is None else _actions_tensor(orient, B, dev)
+    _lib.check(getattr(_lib.lib(), name)(_lib.dev_ptr(boards, boards_dtype, 'boards'), _lib.dev_ptr(o, _I32, 'orient'),
+                                         _lib.dev_ptr(planes, dtype, 'out'), _lib.dev_ptr(flags, _U8, 'settled'), code, B, N,
+                                         _lib.stream_ptr(dev)), name)
+    return flags
+
+
+def batch_life(batch_states, dtype=torch.uint8, out=None, orient=None, settled=False):
+    """Pass-alive (Benson) life planes of every board -> [B, 4, N, N] of `dtype` (gg_batch_life), from the mover's point of
+    view, each value exactly 0 or 1 (LIFE_NAMES):
+       0  own stones that can never be captured, whatever the opponent plays and even if the owner always passes
+       1  the opponent's such stones
+       2  the points (empty, or holding opponent stones) of the regions those own chains enclose and live by
+       3  the same for the opponent
+    For a colour, chains are the components of its stones and regions the components of everything else; a region is vital to a
+    chain when it has an empty point and every empty point of it touches the chain; chains with fewer than two vital regions
+    are dropped, then regions that border a dropped chain, until nothing changes (include/gymgo_amd.h).  Exact, no reading:
+    only planes 0, 1 and 2 of the states are read, so an ended game gets its planes like any other.  dtype: torch.uint8,
+    float16, bfloat16 or float32 (ValueError otherwise).  out: a contiguous device tensor of that shape and dtype to write
+    into.  orient (None, or int [B], only orient & 7 is read): row b is view orient[b] of its planes - also the planes of the
+    turned position.  settled=True: -> (planes, uint8 [B]): 1 iff every point of the board lies in some plane (nothing is
+    left to play for; it does not depend on orient).  NumPy in gives NumPy out (through the device; not for bfloat16).
+    One launch either way; device memory of the result: 4 * B * N^2 elements (+ B bytes)."""
+    code = _feature_dtype(dtype)
+    B, N = _states_shape(batch_states)
+    _life_out(out, (B, LIFE_PLANES, N, N), dtype)
+    if orient is not None:
+        _orient_arg(orient, B)
+    if not isinstance(batch_states, torch.Tensor) and dtype == torch.bfloat16:
+        raise ValueError('NumPy has no bfloat16: pass a device tensor, or another dtype')
+    box = _Box(batch_states)
+    st = box.t
+    _life_out(out, (B, LIFE_PLANES, N, N), dtype, st.device)
+    planes = out if out is not None else torch.empty((B, LIFE_PLANES, N, N), dtype=dtype, device=st.device)
+    flags = _life_launch('gg_batch_life', st, _U8, orient, planes, dtype, code, settled, B, N)
+    return (_back(box, planes), _back(box, flags)) if settled else _back(box, planes)
+
+
+def life(state, dtype=torch.uint8, settled=False):
+    """batch_life of one state [6, N, N] -> [4, N, N] (with settled=True: and a uint8 scalar)."""
+    _feature_dtype(dtype)
+    if not isinstance(state, torch.Tensor) and dtype == torch.bfloat16:
+        raise ValueError('NumPy has no bfloat16: pass a device tensor, or another dtype')
+    box = _Box(state)
+    res = batch_life(box.t[None], dtype, settled=settled)
+    return (_back(box, res[0], row0=True), _back(box, res[1], row0=True)) if settled else _back(box, res, row0=True)
+
+
+def batch_life_tracked(tracked, dtype=torch.uint8, out=None, orient=None, settled=False):
+    """batch_life of tracked boards (int32 [B, 5N+1], a device tensor) -> [B, 4, N, N] of `dtype` (gg_batch_life_tracked):
+    bit for bit what batch_life gives for batch_untrack(tracked); only the two stone row sets and the turn flag are read."""
+    code = _feature_dtype(dtype)
+    if not isinstance(tracked, torch.Tensor) or tracked.dim() != 2:
+        raise ValueError('tracked boards are int32 [B, 5N+1] device tensors')
+    N = _tracked_size(tracked)
+    B = tracked.shape[0]
+    if orient is not None:
+        _orient_arg(orient, B)
+    _life_out(out, (B, LIFE_PLANES, N, N), dtype, tracked.device if tracked.is_cuda else None)
+    planes = out if out is not None else torch.empty((B, LIFE_PLANES, N, N), dtype=dtype, device=tracked.device)
+    flags = _life_launch('gg_batch_life_tracked', tracked, _I32, orient, planes, dtype, code, settled, B, N)
+    return (planes, flags) if settled else planes
+
+
+def batch_settled(batch_states):
+    """uint8 [B]: 1 iff every point of the board is a pass-alive stone or lies in a region such stones live by (batch_life's
+    settled byte): nothing is left to play for - the test a self-play driver ends a game on.  The empty board is not
+    settled.  The launch of batch_life into a scratch buffer."""
+    return batch_life(batch_states, torch.uint8, settled=True)[1]
+
+
 def batch_play_moves_tracked(tracked, moves, played=None):
     """IN PLACE batch_play_moves on tracked boards; moves [B, T] (T = 1: one GoEnv.step per game) -> played int32 [B]."""
     N = _tracked_size(tracked)
@@ -1480,12 +1570,20 @@ class PuctSearch:
     priors back (inverse=True) before the backup launch it queues anyway.  The tree, the stored priors, root_policy,
     add_root_noise and advance stay in the board's own frame: the tree is bit for bit the tree of the same search
     without symmetry and with the evaluator E'(planes, legal) = inverse_o(E(view_o(planes), view_o(legal))), o the
-    orientations drawn for that call (the values are not turned).  Two launches more per select(), one per backup()."""
+    orientations drawn for that call (the values are not turned).  Two launches more per select(), one per backup().
+
+    life (False = everything above, launch for launch; True needs features=, ValueError otherwise): select() returns
+    (planes, legal, life) with life [R, 4, N, N] ([R * L, ..]) of the feature dtype - batch_life of the leaves, from the
+    tracked leaf boards with leaves=L (gg_batch_life_tracked), from the untracked states on the one-leaf path
+    (gg_batch_life) - in the orientation of `search.orient` with symmetry=.  One launch more per select(); backup, advance,
+    root_policy and the tree do not change.  Rows of empty slots hold the planes of whatever board their row holds."""
 
     def __init__(self, batch_states, iterations, c=1.25, komi=0.0, leaves=None, capacity=None, features=None, symmetry=None,
-                 first_root=0):
+                 first_root=0, life=False):
         self._feat = None if features is None else (features, _feature_dtype(features))
         _puct_symmetry_guard(symmetry, features)
+        _puct_life_guard(life, features)
+        self._life = bool(life)
         self._sym = None if symmetry is None else int(symmetry)
         self._first_root = int(first_root)
         self.orient = None
@@ -1521,6 +1619,8 @@ class PuctSearch:
         self._done, self._pending = 0, False
         if self._feat is not None:
             self._planes = torch.empty((R, FEATURE_PLANES, N, N), dtype=self._feat[0], device=dev)
+        if self._life:
+            self._life_planes = torch.empty((R, LIFE_PLANES, N, N), dtype=self._feat[0], device=dev)
         self._init_symmetry(R)
         if not R:   # no device work at all: select / backup only keep the call order
             return
@@ -1552,6 +1652,8 @@ class PuctSearch:
         else:   # (the leaves go out as planes: no byte-plane buffer)
             self._states = self._planes = torch.empty((B, FEATURE_PLANES, N, N), dtype=self._feat[0], device=dev)
         self._legal = torch.empty((B, A), dtype=torch.bool, device=dev)
+        if self._life:
+            self._life_planes = torch.empty((B, LIFE_PLANES, N, N), dtype=self._feat[0], device=dev)
         self.live = torch.zeros((R, L), dtype=torch.bool, device=dev)
         self._done, self._pending = 0, False
         self._init_symmetry(B)
@@ -1621,8 +1723,13 @@ class PuctSearch:
             _lib.check(lib.gg_puct_legal(lp, ip, R * L, N, gp, vp, stream), 'gg_puct_legal')
             if self._sym is not None:
                 self._turn_legal(op, R * L, stream)
+            if self._life:
+                _lib.check(lib.gg_batch_life_tracked(lp, None if self._sym is None else op,
+                                                     _lib.dev_ptr(self._life_planes, self._feat[0], 'life'), None, self._feat[1],
+                                                     R * L, N, stream), 'gg_batch_life_tracked')
         self._pending = True
-        return self._states, (self._legal if self._sym is None else self._legal_view)
+        legal = self._legal if self._sym is None else self._legal_view
+        return (self._states, legal, self._life_planes) if self._life else (self._states, legal)
 
     def _backup_leaves(self, priors, values):
         R, N, L, A = self._R, self._N, self._L, self._N * self._N + 1
@@ -1642,7 +1749,8 @@ class PuctSearch:
 
     def select(self):
         """Step 1 and 2 of the next iteration -> (states uint8 [R, 6, N, N], legal bool [R, A]) of the R leaves ([R * L, ..]
-        with leaves=L); with features=dtype (planes [R, 16, N, N] of that dtype, legal)."""
+        with leaves=L); with features=dtype (planes [R, 16, N, N] of that dtype, legal); with life=True (planes, legal, life
+        [R, 4, N, N] of that dtype)."""
         if self._pending:
             raise ValueError('PuctSearch.select(): the leaves of the last select() have not been backed up')
         if self._done >= self._I:
@@ -1667,8 +1775,15 @@ class PuctSearch:
                 _lib.check(L.gg_batch_features_tracked_oriented(lp, op, _lib.dev_ptr(self._planes, self._feat[0], 'planes'),
                                                                 self._feat[1], R, N, stream), 'gg_batch_features_tracked_oriented')
                 self._turn_legal(op, R, stream)
+            if self._life:
+                _lib.check(L.gg_batch_life(_lib.dev_ptr(self._states, _U8, 'states'), None if self._sym is None else op,
+                                           _lib.dev_ptr(self._life_planes, self._feat[0], 'life'), None, self._feat[1], R, N,
+                                           stream), 'gg_batch_life')
         self._pending = True
-        return (self._states if self._feat is None else self._planes), (self._legal if self._sym is None else self._legal_view)
+        legal = self._legal if self._sym is None else self._legal_view
+        if self._life:
+            return self._planes, legal, self._life_planes
+        return (self._states if self._feat is None else self._planes), legal
 
     def backup(self, priors, values):
         """Step 4: priors float32 [R, A] and values float32 [R] (the value for the player to move at the leaf) of the leaves
@@ -1877,7 +1992,7 @@ class PuctSearch:
 
 
 def batch_puct(batch_states, iterations, evaluator, c=1.25, komi=0.0, tree=False, leaves=None, capacity=None, features=None,
-               symmetry=None, first_root=0):
+               symmetry=None, first_root=0, life=False):
     """PUCT search (the AlphaZero search) of `iterations` iterations from every root of batch_states ([R, 6, N, N]) with the
     caller's evaluator -> Puct (device tensors for a device tensor, NumPy arrays for NumPy input).  The loop over PuctSearch.
 
@@ -1930,14 +2045,18 @@ def batch_puct(batch_states, iterations, evaluator, c=1.25, komi=0.0, tree=False
 
     symmetry (None: the search above, launch for launch; or an integer base seed, with features=): the evaluator sees every
     leaf - planes and legal - in a random orientation and its priors are turned back (PuctSearch); first_root: the global
-    index of root 0, so that shards by root draw what the whole draws."""
+    index of root 0, so that shards by root draw what the whole draws.
+
+    life (False: the search above, launch for launch; True, with features=): the evaluator is called as
+    evaluator(planes, legal, life) with life [R, 4, N, N] ([R * L, ..]) of the feature dtype - batch_life of the leaves, in
+    the leaf's orientation with symmetry= (PuctSearch).  The tree does not depend on it but through the evaluator."""
     _puct_komi_guard(evaluator, komi)
     _puct_features_guard(evaluator, features)
+    _puct_life_guard(life, features)
     search = PuctSearch(batch_states, iterations, c, komi, leaves=leaves, capacity=capacity, features=features, symmetry=symmetry,
-                        first_root=first_root)
+                        first_root=first_root, life=life)
     for _ in range(search._I):
-        states, legal = search.select()
-        priors, values = evaluator(states, legal)
+        priors, values = evaluator(*search.select())
         search.backup(priors, values)
     return search.result(tree=tree)
 
@@ -1953,6 +2072,11 @@ def _puct_symmetry_guard(symmetry, features):
         raise ValueError('symmetry turns the planes and legal that features= hands out: give features= too')
 
 
+def _puct_life_guard(life, features):
+    if life and features is None:   # (before a device is touched)
+        raise ValueError('life=True hands out the life planes in the dtype of features=: give features= too')
+
+
 def _puct_features_guard(evaluator, features):
     if features is not None:
         _feature_dtype(features)
@@ -1961,7 +2085,7 @@ def _puct_features_guard(evaluator, features):
 
 
 def puct_play(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, leaves=None, capacity=None, reuse=True, features=None,
-              symmetry=None, first_root=0):
+              symmetry=None, first_root=0, life=False):
     """Play `moves` moves from every root of batch_states ([R, 6, N, N]) with a PUCT search per move -> (actions int64
     [R, moves], the final states uint8 [R, 6, N, N]); device tensors for a device tensor, NumPy arrays for NumPy input.
     Per move: `iterations` rounds of PuctSearch (batch_puct's loop, with `leaves` and `capacity` as there), the move of
@@ -1980,20 +2104,21 @@ def puct_play(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, leav
     evaluator adds would reach only fresh roots: PuctSearch.add_root_noise reaches kept roots too, and puct_selfplay is this
     loop with it, with moves drawn from the visit counts and with the training records.  features: as batch_puct - the
     evaluator gets (planes, legal).  symmetry, first_root: as batch_puct; with reuse=False the search of move mv draws from
-    the base seed symmetry + mv (a new search would repeat the first one's draws otherwise)."""
+    the base seed symmetry + mv (a new search would repeat the first one's draws otherwise).  life: as batch_puct - the
+    evaluator gets (planes, legal, life)."""
     _puct_komi_guard(evaluator, komi)
     _puct_features_guard(evaluator, features)
+    _puct_life_guard(life, features)
     moves = int(moves)
     if moves < 0:
         raise ValueError('need moves >= 0 (got %d)' % moves)
     search = PuctSearch(batch_states, iterations, c, komi, leaves=leaves, capacity=capacity, features=features, symmetry=symmetry,
-                        first_root=first_root)
+                        first_root=first_root, life=life)
     box = search._box
     played = torch.empty((search._R, moves), dtype=_I64, device=box.t.device)
     for mv in range(moves):
         for _ in range(search._I):
-            states, legal = search.select()
-            priors, values = evaluator(states, legal)
+            priors, values = evaluator(*search.select())
             search.backup(priors, values)
         res = search._result()
         played[:, mv] = _best_legal(_ON_DEVICE, res.legal, res.visits.to(_I64))
@@ -2002,7 +2127,7 @@ def puct_play(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, leav
         else:   # only node 0's boards are played on: the tree goes, so no advance over it; the states stay on the device
             box.t = search._played_states(played[:, mv])
             search = PuctSearch(box, iterations, c, komi, leaves=leaves, capacity=capacity, features=features,
-                                symmetry=None if symmetry is None else int(symmetry) + mv + 1, first_root=first_root)
+                                symmetry=None if symmetry is None else int(symmetry) + mv + 1, first_root=first_root, life=life)
     return _back(box, played), box.back(search._root_states())
 
 
@@ -2037,7 +2162,8 @@ that ended, 0 for one still running), lengths (int32 [R]: moves played), final_s
 
 
 def puct_selfplay(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, leaves=None, capacity=None, noise=None,
-                  eps=0.25, sample_moves=0, seed=20260927, first_game=0, record_states=False, features=None, symmetry=None):
+                  eps=0.25, sample_moves=0, seed=20260927, first_game=0, record_states=False, features=None, symmetry=None,
+                  life=False):
     """Self-play games for training: `moves` moves from every root of batch_states ([R, 6, N, N]) with a PUCT search per move
     on the kept tree -> SelfPlay (device tensors for a device tensor, NumPy arrays for NumPy input).  puct_play's
     reuse=True loop (`iterations` rounds per move with `leaves` and `capacity` as there, then PuctSearch.advance) with
@@ -2061,9 +2187,12 @@ def puct_selfplay(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, 
     (states included) are unchanged.  symmetry (None, or an integer base seed, with features=): every leaf evaluation in a
     random orientation, as batch_puct; the search gets first_root=first_game, so shards concatenate here too.  The records stay
     in the boards' own frame.  A trainer takes its samples from the records with selfplay_batch: the planes of the recorded
-    positions and the policy targets, in any of the eight orientations."""
+    positions and the policy targets, in any of the eight orientations.  life: as batch_puct - the evaluator gets (planes,
+    legal, life); the records do not change, and there is no stopping rule here: a driver that wants to stop settled games
+    early asks batch_settled(search.root_states()) in a loop of its own."""
     _puct_komi_guard(evaluator, komi)
     _puct_features_guard(evaluator, features)
+    _puct_life_guard(life, features)
     moves, sample_moves, eps = int(moves), int(sample_moves), float(eps)
     if moves < 0:
         raise ValueError('need moves >= 0 (got %d)' % moves)
@@ -2090,7 +2219,8 @@ def puct_selfplay(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, 
     before = torch.empty((R, moves, govars.NUM_CHNLS, N, N), dtype=_U8, device=dev) if record_states else None
     if not R or not moves:
         return _back(box, SelfPlay(played, pis, vals, outcome, lengths, st, before))
-    search = PuctSearch(box, I, c, komi, leaves=leaves, capacity=capacity, features=features, symmetry=symmetry, first_root=first_game)
+    search = PuctSearch(box, I, c, komi, leaves=leaves, capacity=capacity, features=features, symmetry=symmetry, first_root=first_game,
+                        life=life)
     rng = rng_seed(R, seed, first_game, device=dev)
     ones, todo = torch.ones(R, dtype=_U8, device=dev), torch.empty(R, dtype=_U8, device=dev)
     for mv in range(moves):
@@ -2101,8 +2231,7 @@ def puct_selfplay(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, 
             todo.fill_(1)
             search.add_root_noise(z, eps, todo)     # the roots kept from the move before
         for t in range(search._I):
-            states, legal = search.select()
-            priors, values = evaluator(states, legal)
+            priors, values = evaluator(*search.select())
             search.backup(priors, values)
             if t == 0 and noise is not None:
                 search.add_root_noise(z, eps, todo)   # the fresh roots round 0 has just evaluated
@@ -2122,6 +2251,7 @@ def puct(state, iterations, evaluator, **kw):
     """batch_puct of one state [6, N, N] -> Puct of [N*N + 1] vectors and scalars (tree fields [iterations + 1]); the evaluator
     still sees a batch of one."""
     _puct_symmetry_guard(kw.get('symmetry'), kw.get('features'))
+    _puct_life_guard(kw.get('life', False), kw.get('features'))
     return _single(batch_puct, state, iterations, evaluator, **kw)
 
 
@@ -2129,6 +2259,7 @@ def puct_actions(batch_states, iterations, evaluator, **kw):
     """The PUCT move of every root -> int64 [R]: the legal root child with the most visits after batch_puct(batch_states,
     iterations, evaluator, **kw); ties go to the lowest action, a root without a legal move gives -1."""
     _puct_symmetry_guard(kw.get('symmetry'), kw.get('features'))
+    _puct_life_guard(kw.get('life', False), kw.get('features'))
     box = _Box(batch_states)
     res = batch_puct(box.t, iterations, evaluator, **kw)
     return _best_legal(box, res.legal, res.visits.to(_I64))
@@ -2399,14 +2530,15 @@ def selfplay_targets(record, games, moves):
     return torch.where(white, -outcome, outcome), m < t(record.lengths, dev)[g].to(_I64)
 
 
-def selfplay_batch(record, games, moves, orient, dtype=torch.float16):
+def selfplay_batch(record, games, moves, orient, dtype=torch.float16, life=False):
     """Training samples from a self-play record, in one of the eight orientations each -> (planes [B, 16, N, N] of `dtype`,
     pi [B, A] float32, z float32 [B], valid bool [B]).  record: a SelfPlay of puct_selfplay(.., record_states=True)
     (ValueError if record.states is None); games, moves, orient: int [B] - sample i is the position before move moves[i] of
     game games[i], seen in view orient[i].  planes = batch_features of the recorded position with orient (one launch), pi =
     the recorded visit-count target turned with batch_symmetry_policy - both in the view; z, valid: selfplay_targets.  The
     eightfold augmentation of a sample is this call with orient = 0 .. 7.  Nothing synchronises; device tensors, or NumPy
-    arrays for a NumPy record (through the device)."""
+    arrays for a NumPy record (through the device).  life=True: a fifth element, the life planes [B, 4, N, N] of the
+    recorded positions in view orient and dtype `dtype` (batch_life, one launch more)."""
     _feature_dtype(dtype)
     z, valid = selfplay_targets(record, games, moves)
     is_np = not isinstance(record.states, torch.Tensor)
@@ -2417,7 +2549,10 @@ def selfplay_batch(record, games, moves, orient, dtype=torch.float16):
     dev = _device() if is_np else record.states.device
     t = lambda x: (x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))).to(device=dev)
     g, m = t(games).to(_I64), t(moves).to(_I64)
-    planes = batch_features(t(record.states)[g, m], dtype, orient=orient)
+    positions = t(record.states)[g, m]
+    planes = batch_features(positions, dtype, orient=orient)
     pi = batch_symmetry_policy(t(record.pi)[g, m].to(torch.float32), orient)
     res = (planes, pi, z.to(dev), valid.to(dev))
+    if life:
+        res += (batch_life(positions, dtype, orient=orient),)
     return tuple(x.cpu().numpy() for x in res) if is_np else res

@@ -752,6 +752,40 @@ int32_t gg_batch_symmetry_policy(const void *in, const int32_t *orient, void *ou
                                  int32_t N, void *hip_stream);
 int32_t gg_batch_draw_orient(uint64_t *rng, int32_t *orient, int64_t B, void *hip_stream);
 
+/*
+ * Pass-alive (Benson) life planes: the stones that can never be captured, whatever the opponent plays and even
+ * if their owner always passes, and the points they decide - exact, all integers and sets, no reading.  For a colour X:
+ * S = the points holding a stone of X, O = the other colour's stones, E = the empty points; adjacency is orthogonal and on
+ * the board.  CHAINS are the connected components of S, REGIONS the connected components of the complement of S (E and O
+ * together).  A region r is VITAL to a chain c when r contains an empty point and every empty point of r is adjacent to a
+ * stone of c (a region without an empty point is vital to nothing); r BORDERS c when some point of r is adjacent to a
+ * stone of c.  Start with A = all chains and Q = all regions and repeat until neither changes:
+ *   1. drop from A every chain with fewer than two regions of Q vital to it;
+ *   2. drop from Q every region that borders a chain of X not in A.
+ * alive(X) = the stones of the chains left in A; safe(X) = the points (empty or O) of every region left in Q that is vital
+ * to at least one chain left in A; both empty when X has no stones.  Only planes 0, 1 and 2 of a state are read (of a
+ * tracked board: the two stone row sets and the turn flag): an ended game gets its planes like any other, a hand-made chain
+ * without liberties simply follows the definition.  L = gg_life_planes() = 4 planes per board, out [B][4][N][N], every
+ * element exactly 0 or 1, OWN = the player to move:
+ *    0  alive(own)      1  alive(opponent)      2  safe(own)      3  safe(opponent)
+ * settled (NULL, or uint8 [B]): settled[b] = 1 iff every point of board b lies in plane 0 | 1 | 2 | 3, else 0 (the empty board
+ * is not settled).  orient (NULL, or int32 [B], only orient[b] & 7 is read; gg_batch_symmetry's orientations): out[b] is view
+ * orient[b] of the unoriented result, which is also the result of the turned position; settled does not depend on it.
+ *   gg_batch_life           states uint8 [B][6][N][N] -> out of out_dtype: GG_W_F32 / GG_W_BF16 / GG_W_F16 / GG_FEAT_U8
+ *   gg_batch_life_tracked   the same from tracked boards uint32 [B][gg_tracked_words(N)]: the same bytes for
+ *                           gg_batch_track_states(s) and s
+ * out needs the alignment of its element only (4 N^2 elements are no multiple of 16 bytes for odd N in uint8): the stores
+ * are aligned 16-byte vectors inside a wave's slice of out and single elements at its two ragged ends; nothing outside
+ * out [B][4][N][N] and settled [B] is written.  Checks, in this order: GG_E_BADSIZE for N outside [2, 19], B < 0 or an
+ * out_dtype other than the four; B = 0 is no work and returns 0; GG_E_NULLPTR for a NULL input or out; GG_E_BADARG for an
+ * out not aligned to its element size.  Every call queues ONE launch on hip_stream and never synchronises.
+ */
+int32_t gg_life_planes(void);
+int32_t gg_batch_life(const uint8_t *states, const int32_t *orient, void *out, uint8_t *settled, int32_t out_dtype, int64_t B,
+                      int32_t N, void *hip_stream);
+int32_t gg_batch_life_tracked(const uint32_t *tracked, const int32_t *orient, void *out, uint8_t *settled, int32_t out_dtype,
+                              int64_t B, int32_t N, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
