@@ -528,17 +528,17 @@ static int32_t puct_args(PuctArgs &u, int64_t R, int32_t N, int32_t I, double c,
     return GG_E_BADARG;   // (I + 1 nodes per tree: the node count is an int32 as well)
   u = PuctArgs{const_cast<uint32_t *>(boards), child, const_cast<float *>(prior), const_cast<int32_t *>(links),
                reinterpret_cast<PuctStat *>(const_cast<gg_puct_stat *>(stats)), nodes, const_cast<uint32_t *>(leaf),
-               const_cast<int32_t *>(move), const_cast<int32_t *>(leaf_id), priors, values, c, R, N, I, komi};
+               const_cast<int32_t *>(move), const_cast<int32_t *>(leaf_id), priors, values, c, R, N, I, komi, 1};
   return 0;
 }
 
 // several leaves per root and round: the tree's checks with the capacity C where I stood, then L (1 <= L <= C: a round of
 // L slots must fit the tree)
-static int32_t puct_leaves_args(PuctLeavesArgs &u, int64_t R, int32_t N, int32_t C, int32_t L, double c, float komi,
+static int32_t puct_leaves_args(PuctArgs &u, int64_t R, int32_t N, int32_t C, int32_t L, double c, float komi,
                                 const uint32_t *boards, int32_t *child, const float *prior, const int32_t *links,
                                 const gg_puct_stat *stats, int32_t *nodes, const uint32_t *leaf, const int32_t *move,
                                 const int32_t *leaf_id, const float *priors = nullptr, const float *values = nullptr) {
-  if (int32_t e = puct_args(u.t, R, N, C, c, komi, boards, child, prior, links, stats, nodes, leaf, move, leaf_id, priors, values))
+  if (int32_t e = puct_args(u, R, N, C, c, komi, boards, child, prior, links, stats, nodes, leaf, move, leaf_id, priors, values))
     return e;
   if (L < 1 || L > C) return GG_E_BADARG;
   u.L = L;
@@ -1512,7 +1512,7 @@ int32_t gg_puct_select(int64_t R, int32_t N, int32_t I, double c, const uint32_t
   if (R == 0) return 0;
   OnDeviceOf on_dev(leaf);
   hipStream_t s = (hipStream_t)hip_stream;
-  k_puct_select<<<grid_for(on_dev.cus(), (R + 3) / 4), 4 * kWave, 0, s>>>(u);
+  k_puct_select<false><<<grid_for(on_dev.cus(), (R + 3) / 4), 4 * kWave, 0, s>>>(u);
   return (int32_t)hipGetLastError();
 }
 
@@ -1527,28 +1527,28 @@ int32_t gg_puct_backup(int64_t R, int32_t N, int32_t I, float komi, const float 
   OnDeviceOf on_dev(leaf);
   hipStream_t s = (hipStream_t)hip_stream;
   const int grid = grid_for(on_dev.cus(), (R + 3) / 4);
-  GG_DISPATCH(N, (k_puct_backup<9><<<grid, 4 * kWave, 0, s>>>(u)), (k_puct_backup<13><<<grid, 4 * kWave, 0, s>>>(u)),
-              (k_puct_backup<19><<<grid, 4 * kWave, 0, s>>>(u)));
+  GG_DISPATCH(N, (k_puct_backup<9, false><<<grid, 4 * kWave, 0, s>>>(u)), (k_puct_backup<13, false><<<grid, 4 * kWave, 0, s>>>(u)),
+              (k_puct_backup<19, false><<<grid, 4 * kWave, 0, s>>>(u)));
   return (int32_t)hipGetLastError();
 }
 
 int32_t gg_puct_select_leaves(int64_t R, int32_t N, int32_t C, int32_t L, double c, const uint32_t *boards, int32_t *child,
                               const float *prior, int32_t *links, gg_puct_stat *stats, int32_t *nodes, uint32_t *leaf,
                               int32_t *move, int32_t *leaf_id, void *hip_stream) {
-  PuctLeavesArgs u;
+  PuctArgs u;
   if (int32_t e = puct_leaves_args(u, R, N, C, L, c, 0.f, boards, child, prior, links, stats, nodes, leaf, move, leaf_id)) return e;
   if (!boards || !child || !prior || !links || !stats || !nodes || !leaf || !move || !leaf_id) return GG_E_NULLPTR;
   if (R == 0) return 0;
   OnDeviceOf on_dev(leaf);
   hipStream_t s = (hipStream_t)hip_stream;
-  k_puct_select_leaves<<<grid_for(on_dev.cus(), (R + 3) / 4), 4 * kWave, 0, s>>>(u);
+  k_puct_select<true><<<grid_for(on_dev.cus(), (R + 3) / 4), 4 * kWave, 0, s>>>(u);
   return (int32_t)hipGetLastError();
 }
 
 int32_t gg_puct_backup_leaves(int64_t R, int32_t N, int32_t C, int32_t L, float komi, const float *priors, const float *values,
                               uint32_t *boards, float *prior, const int32_t *links, gg_puct_stat *stats, const uint32_t *leaf,
                               const int32_t *move, const int32_t *leaf_id, void *hip_stream) {
-  PuctLeavesArgs u;
+  PuctArgs u;
   if (int32_t e = puct_leaves_args(u, R, N, C, L, 0.0, komi, boards, nullptr, prior, links, stats, nullptr, leaf, move, leaf_id,
                                    priors, values))
     return e;
@@ -1557,8 +1557,8 @@ int32_t gg_puct_backup_leaves(int64_t R, int32_t N, int32_t C, int32_t L, float 
   OnDeviceOf on_dev(leaf);
   hipStream_t s = (hipStream_t)hip_stream;
   const int grid = grid_for(on_dev.cus(), (R + 3) / 4);
-  GG_DISPATCH(N, (k_puct_backup_leaves<9><<<grid, 4 * kWave, 0, s>>>(u)), (k_puct_backup_leaves<13><<<grid, 4 * kWave, 0, s>>>(u)),
-              (k_puct_backup_leaves<19><<<grid, 4 * kWave, 0, s>>>(u)));
+  GG_DISPATCH(N, (k_puct_backup<9, true><<<grid, 4 * kWave, 0, s>>>(u)), (k_puct_backup<13, true><<<grid, 4 * kWave, 0, s>>>(u)),
+              (k_puct_backup<19, true><<<grid, 4 * kWave, 0, s>>>(u)));
   return (int32_t)hipGetLastError();
 }
 

@@ -1538,7 +1538,10 @@ class PuctSearch:
     one after the other under virtual loss (batch_puct).  select() then returns states uint8 [R * L, 6, N, N] and legal
     bool [R * L, A] in row order r * L + j, backup() takes priors [R * L, A] and values [R * L]; rows of empty slots are
     evaluated like any other and ignored.  `search.live` (bool [R, L], a device tensor valid until the next select()) says
-    which slots hold a leaf, for evaluators that want to skip the rest.  The tree has iterations * L + 1 nodes per root.
+    which slots hold a leaf, for evaluators that want to skip the rest ([R, 1] and all true with leaves=None).  The tree
+    has iterations * L + 1 nodes per root.  Either way a select() queues the select launch (gg_puct_select, or
+    gg_puct_select_leaves with L), the one-move step on the leaf boards, their untrack and gg_puct_legal, which writes
+    `legal` and `live` from the tracked leaves; only the entry points of select and backup differ.
 
     capacity (None = the sizes above, every allocation and launch as without it): the nodes per root, an integer >= that
     default and < 2^31; `iterations` stays the bound on rounds.  Room beyond the default is what advance() needs to go on
@@ -1556,9 +1559,9 @@ class PuctSearch:
 
     features (None = everything above, launch for launch; or a dtype of batch_features): select() returns (planes, legal)
     with planes [R, 16, N, N] ([R * L, ..] with leaves=L) of that dtype - batch_features of the leaves, made from the tracked
-    leaf boards by gg_batch_features_tracked - instead of (states, legal).  With leaves=L that launch REPLACES the untrack
-    of the leaf boards; on the one-leaf path `legal` comes from the untracked states, so it is one launch more.  Rows of
-    empty slots hold the planes of whatever board their row holds.  Device memory: 16 N^2 elements per row handed out.
+    leaf boards by gg_batch_features_tracked - instead of (states, legal).  That launch REPLACES the untrack of the leaf
+    boards, with and without leaves=L: nothing is untracked.  Rows of empty slots hold the planes of whatever board their
+    row holds.  Device memory: 16 N^2 elements per row handed out.
 
     symmetry (None = everything above, launch for launch; or an integer base seed; needs features=, ValueError otherwise):
     every evaluation sees its leaf in a random one of the eight orientations of batch_symmetry - AlphaGo Zero's random
@@ -1574,9 +1577,9 @@ class PuctSearch:
 
     life (False = everything above, launch for launch; True needs features=, ValueError otherwise): select() returns
     (planes, legal, life) with life [R, 4, N, N] ([R * L, ..]) of the feature dtype - batch_life of the leaves, from the
-    tracked leaf boards with leaves=L (gg_batch_life_tracked), from the untracked states on the one-leaf path
-    (gg_batch_life) - in the orientation of `search.orient` with symmetry=.  One launch more per select(); backup, advance,
-    root_policy and the tree do not change.  Rows of empty slots hold the planes of whatever board their row holds."""
+    tracked leaf boards (gg_batch_life_tracked) - in the orientation of `search.orient` with symmetry=.  One launch more
+    per select(); backup, advance, root_policy and the tree do not change.  Rows of empty slots hold the planes of whatever
+    board their row holds."""
 
     def __init__(self, batch_states, iterations, c=1.25, komi=0.0, leaves=None, capacity=None, features=None, symmetry=None,
                  first_root=0, life=False):
@@ -1599,44 +1602,7 @@ class PuctSearch:
         self._R, self._N, self._dev = R, N, dev
         self._C = NN - 1        # what the kernels get as I / C: only a capacity there
         self._scratch = None    # advance()'s buffers, allocated on its first call
-        if self._L is not None:
-            self._init_leaves(st)
-            return
-        I = self._C
-        W, A = tracked_words(N), N * N + 1
-        self._legal_roots = _legal_roots(st)
-        self._boards = torch.empty((R, NN, W), dtype=_I32, device=dev)
-        self._child = torch.empty((R, NN, A), dtype=_I32, device=dev)
-        self._prior = torch.empty((R, NN, A), dtype=torch.float32, device=dev)
-        self._links = torch.empty((R, NN, 2), dtype=_I32, device=dev)
-        self._stats = torch.empty((R, NN, 4), dtype=_I32, device=dev)   # gg_puct_stat: w float64 (words 0 - 1), n (word 2), 0
-        self._nodes = torch.empty(R, dtype=_I32, device=dev)
-        self._leaf = torch.empty((R, W), dtype=_I32, device=dev)
-        self._move = torch.empty(R, dtype=_I32, device=dev)
-        self._leaf_id = torch.empty(R, dtype=_I32, device=dev)
-        self._states = torch.empty((R, govars.NUM_CHNLS, N, N), dtype=_U8, device=dev)
-        self._legal = torch.empty((R, A), dtype=torch.bool, device=dev)
-        self._done, self._pending = 0, False
-        if self._feat is not None:
-            self._planes = torch.empty((R, FEATURE_PLANES, N, N), dtype=self._feat[0], device=dev)
-        if self._life:
-            self._life_planes = torch.empty((R, LIFE_PLANES, N, N), dtype=self._feat[0], device=dev)
-        self._init_symmetry(R)
-        if not R:   # no device work at all: select / backup only keep the call order
-            return
-        p = _lib.dev_ptr
-        self._tree = (p(self._boards, _I32, 'boards'), p(self._child, _I32, 'child'), p(self._prior, torch.float32, 'prior'),
-                      p(self._links, _I32, 'links'), p(self._stats, _I32, 'stats'), p(self._nodes, _I32, 'nodes'))
-        self._out = (p(self._leaf, _I32, 'leaf'), p(self._move, _I32, 'move'), p(self._leaf_id, _I32, 'leaf_id'))
-        _lib.check(_lib.lib().gg_puct_begin(p(_track_roots(st), _I32, 'roots'), R, N, I, *self._tree,
-                                            _lib.current_raw_stream(dev)), 'gg_puct_begin')
-
-    def _init_leaves(self, st):
-        """The buffers of the several-leaves path: the tree of C + 1 = iterations * leaves + 1 nodes (gg_puct_begin with
-        I = C: the same bytes as a one-leaf tree of C iterations), R * L rows of everything that is handed out."""
-        R, N, L, dev = self._R, self._N, self._L, self._dev
-        C = self._C
-        W, A, NN, B = tracked_words(N), N * N + 1, C + 1, R * L
+        W, A, B = tracked_words(N), N * N + 1, R * (self._L or 1)   # B: the rows handed out per select()
         self._legal_roots = _legal_roots(st)
         self._boards = torch.empty((R, NN, W), dtype=_I32, device=dev)
         self._child = torch.empty((R, NN, A), dtype=_I32, device=dev)
@@ -1650,21 +1616,21 @@ class PuctSearch:
         if self._feat is None:
             self._states = torch.empty((B, govars.NUM_CHNLS, N, N), dtype=_U8, device=dev)
         else:   # (the leaves go out as planes: no byte-plane buffer)
-            self._states = self._planes = torch.empty((B, FEATURE_PLANES, N, N), dtype=self._feat[0], device=dev)
+            self._states = torch.empty((B, FEATURE_PLANES, N, N), dtype=self._feat[0], device=dev)
         self._legal = torch.empty((B, A), dtype=torch.bool, device=dev)
         if self._life:
             self._life_planes = torch.empty((B, LIFE_PLANES, N, N), dtype=self._feat[0], device=dev)
-        self.live = torch.zeros((R, L), dtype=torch.bool, device=dev)
+        self.live = torch.full((R, self._L or 1), self._L is None, dtype=torch.bool, device=dev)   # (one leaf: always live)
         self._done, self._pending = 0, False
         self._init_symmetry(B)
-        if not R:
+        if not R:   # no device work at all: select / backup only keep the call order
             return
         p = _lib.dev_ptr
         self._tree = (p(self._boards, _I32, 'boards'), p(self._child, _I32, 'child'), p(self._prior, torch.float32, 'prior'),
                       p(self._links, _I32, 'links'), p(self._stats, _I32, 'stats'), p(self._nodes, _I32, 'nodes'))
         self._out = (p(self._leaf, _I32, 'leaf'), p(self._move, _I32, 'move'), p(self._leaf_id, _I32, 'leaf_id'))
         self._hand = (p(self._states, self._states.dtype, 'states'), p(self._legal, torch.bool, 'legal'), p(self.live, torch.bool, 'live'))
-        _lib.check(_lib.lib().gg_puct_begin(p(_track_roots(st), _I32, 'roots'), R, N, C, *self._tree,
+        _lib.check(_lib.lib().gg_puct_begin(p(_track_roots(st), _I32, 'roots'), R, N, self._C, *self._tree,
                                             _lib.current_raw_stream(dev)), 'gg_puct_begin')
 
     def _init_symmetry(self, B):
@@ -1704,49 +1670,6 @@ class PuctSearch:
     def iterations_done(self):
         return self._done
 
-    def _select_leaves(self):
-        R, N, L = self._R, self._N, self._L
-        if R:
-            lib, stream = _lib.lib(), _lib.current_raw_stream(self._dev)
-            lp, mp, ip = self._out
-            sp, gp, vp = self._hand
-            _lib.check(lib.gg_puct_select_leaves(R, N, self._C, L, self._c, *self._tree, lp, mp, ip, stream), 'gg_puct_select_leaves')
-            _lib.check(lib.gg_batch_play_moves_tracked(lp, mp, None, R * L, N, 1, stream), 'gg_batch_play_moves_tracked')
-            if self._feat is None:
-                _lib.check(lib.gg_batch_untrack_states(lp, sp, R * L, N, stream), 'gg_batch_untrack_states')
-            elif self._sym is None:   # (sp: the planes)
-                _lib.check(lib.gg_batch_features_tracked(lp, sp, self._feat[1], R * L, N, stream), 'gg_batch_features_tracked')
-            else:
-                op = self._draw_orient(R * L, stream)
-                _lib.check(lib.gg_batch_features_tracked_oriented(lp, op, sp, self._feat[1], R * L, N, stream),
-                           'gg_batch_features_tracked_oriented')
-            _lib.check(lib.gg_puct_legal(lp, ip, R * L, N, gp, vp, stream), 'gg_puct_legal')
-            if self._sym is not None:
-                self._turn_legal(op, R * L, stream)
-            if self._life:
-                _lib.check(lib.gg_batch_life_tracked(lp, None if self._sym is None else op,
-                                                     _lib.dev_ptr(self._life_planes, self._feat[0], 'life'), None, self._feat[1],
-                                                     R * L, N, stream), 'gg_batch_life_tracked')
-        self._pending = True
-        legal = self._legal if self._sym is None else self._legal_view
-        return (self._states, legal, self._life_planes) if self._life else (self._states, legal)
-
-    def _backup_leaves(self, priors, values):
-        R, N, L, A = self._R, self._N, self._L, self._N * self._N + 1
-        B = R * L
-        if tuple(priors.shape) != (B, A) or values.numel() != B:
-            raise ValueError('need priors [%d, %d] and values [%d] (got %s, %s)' % (B, A, B, tuple(priors.shape), tuple(values.shape)))
-        if R:
-            if self._sym is not None:
-                priors = self._turn_priors_back(priors, B)
-            boards, _, prior, links, stats, _ = self._tree
-            _lib.check(_lib.lib().gg_puct_backup_leaves(R, N, self._C, L, self._komi, _lib.dev_ptr(priors, torch.float32, 'priors'),
-                                                        _lib.dev_ptr(values.reshape(B), torch.float32, 'values'), boards, prior,
-                                                        links, stats, *self._out, _lib.current_raw_stream(self._dev)),
-                       'gg_puct_backup_leaves')
-        self._pending = False
-        self._done += 1
-
     def select(self):
         """Step 1 and 2 of the next iteration -> (states uint8 [R, 6, N, N], legal bool [R, A]) of the R leaves ([R * L, ..]
         with leaves=L); with features=dtype (planes [R, 16, N, N] of that dtype, legal); with life=True (planes, legal, life
@@ -1755,56 +1678,57 @@ class PuctSearch:
             raise ValueError('PuctSearch.select(): the leaves of the last select() have not been backed up')
         if self._done >= self._I:
             raise ValueError('PuctSearch.select(): all %d iterations are done' % self._I)
-        if self._L is not None:
-            return self._select_leaves()
-        R, N, I = self._R, self._N, self._C
+        R, N, B = self._R, self._N, self._R * (self._L or 1)
         if R:
-            L, stream = _lib.lib(), _lib.current_raw_stream(self._dev)
+            lib, stream = _lib.lib(), _lib.current_raw_stream(self._dev)
             lp, mp, ip = self._out
-            _lib.check(L.gg_puct_select(R, N, I, self._c, *self._tree, lp, mp, ip, stream), 'gg_puct_select')
-            _lib.check(L.gg_batch_play_moves_tracked(lp, mp, None, R, N, 1, stream), 'gg_batch_play_moves_tracked')
-            _lib.check(L.gg_batch_untrack_states(lp, _lib.dev_ptr(self._states, _U8, 'states'), R, N, stream),
-                       'gg_batch_untrack_states')
-            with torch.cuda.device(self._dev):
-                self._legal.copy_(_legal_roots(self._states))
-            if self._feat is not None and self._sym is None:
-                _lib.check(L.gg_batch_features_tracked(lp, _lib.dev_ptr(self._planes, self._feat[0], 'planes'), self._feat[1], R, N,
-                                                       stream), 'gg_batch_features_tracked')
-            elif self._feat is not None:
-                op = self._draw_orient(R, stream)
-                _lib.check(L.gg_batch_features_tracked_oriented(lp, op, _lib.dev_ptr(self._planes, self._feat[0], 'planes'),
-                                                                self._feat[1], R, N, stream), 'gg_batch_features_tracked_oriented')
-                self._turn_legal(op, R, stream)
+            sp, gp, vp = self._hand
+            if self._L is None:
+                _lib.check(lib.gg_puct_select(R, N, self._C, self._c, *self._tree, lp, mp, ip, stream), 'gg_puct_select')
+            else:
+                _lib.check(lib.gg_puct_select_leaves(R, N, self._C, self._L, self._c, *self._tree, lp, mp, ip, stream),
+                           'gg_puct_select_leaves')
+            _lib.check(lib.gg_batch_play_moves_tracked(lp, mp, None, B, N, 1, stream), 'gg_batch_play_moves_tracked')
+            if self._feat is None:
+                _lib.check(lib.gg_batch_untrack_states(lp, sp, B, N, stream), 'gg_batch_untrack_states')
+            elif self._sym is None:   # (sp: the planes)
+                _lib.check(lib.gg_batch_features_tracked(lp, sp, self._feat[1], B, N, stream), 'gg_batch_features_tracked')
+            else:
+                op = self._draw_orient(B, stream)
+                _lib.check(lib.gg_batch_features_tracked_oriented(lp, op, sp, self._feat[1], B, N, stream),
+                           'gg_batch_features_tracked_oriented')
+            _lib.check(lib.gg_puct_legal(lp, ip, B, N, gp, vp, stream), 'gg_puct_legal')
+            if self._sym is not None:
+                self._turn_legal(op, B, stream)
             if self._life:
-                _lib.check(L.gg_batch_life(_lib.dev_ptr(self._states, _U8, 'states'), None if self._sym is None else op,
-                                           _lib.dev_ptr(self._life_planes, self._feat[0], 'life'), None, self._feat[1], R, N,
-                                           stream), 'gg_batch_life')
+                _lib.check(lib.gg_batch_life_tracked(lp, None if self._sym is None else op,
+                                                     _lib.dev_ptr(self._life_planes, self._feat[0], 'life'), None, self._feat[1],
+                                                     B, N, stream), 'gg_batch_life_tracked')
         self._pending = True
         legal = self._legal if self._sym is None else self._legal_view
-        if self._life:
-            return self._planes, legal, self._life_planes
-        return (self._states if self._feat is None else self._planes), legal
+        return (self._states, legal, self._life_planes) if self._life else (self._states, legal)
 
     def backup(self, priors, values):
         """Step 4: priors float32 [R, A] and values float32 [R] (the value for the player to move at the leaf) of the leaves
-        the last select() handed out; tensors on the search's device or NumPy arrays."""
+        the last select() handed out ([R * L, A] and [R * L] with leaves=L); tensors on the search's device or NumPy arrays."""
         if not self._pending:
             raise ValueError('PuctSearch.backup(): no select() is outstanding')
-        R, N, A = self._R, self._N, self._N * self._N + 1
+        R, N, A, B = self._R, self._N, self._N * self._N + 1, self._R * (self._L or 1)
         f32 = lambda x: (x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))).to(
             device=self._dev, dtype=torch.float32).contiguous()
         priors, values = f32(priors), f32(values)
-        if self._L is not None:
-            return self._backup_leaves(priors, values)
-        if tuple(priors.shape) != (R, A) or values.numel() != R:
-            raise ValueError('need priors [%d, %d] and values [%d] (got %s, %s)' % (R, A, R, tuple(priors.shape), tuple(values.shape)))
+        if tuple(priors.shape) != (B, A) or values.numel() != B:
+            raise ValueError('need priors [%d, %d] and values [%d] (got %s, %s)' % (B, A, B, tuple(priors.shape), tuple(values.shape)))
         if R:
             if self._sym is not None:
-                priors = self._turn_priors_back(priors, R)
+                priors = self._turn_priors_back(priors, B)
             boards, _, prior, links, stats, _ = self._tree
-            _lib.check(_lib.lib().gg_puct_backup(R, N, self._C, self._komi, _lib.dev_ptr(priors, torch.float32, 'priors'),
-                                                 _lib.dev_ptr(values.reshape(R), torch.float32, 'values'), boards, prior, links,
-                                                 stats, *self._out, _lib.current_raw_stream(self._dev)), 'gg_puct_backup')
+            rows = (_lib.dev_ptr(priors, torch.float32, 'priors'), _lib.dev_ptr(values.reshape(B), torch.float32, 'values'),
+                    boards, prior, links, stats, *self._out, _lib.current_raw_stream(self._dev))
+            if self._L is None:
+                _lib.check(_lib.lib().gg_puct_backup(R, N, self._C, self._komi, *rows), 'gg_puct_backup')
+            else:
+                _lib.check(_lib.lib().gg_puct_backup_leaves(R, N, self._C, self._L, self._komi, *rows), 'gg_puct_backup_leaves')
         self._pending = False
         self._done += 1
 

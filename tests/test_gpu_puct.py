@@ -301,3 +301,58 @@ def test_puct_select_without_room_evaluates_the_node_it_stopped_at():
         assert np.array_equal(pe.bits(s._prior), pe.bits(np.stack([t.prior for t in trees]))), k
     assert no_room > 0                              # the branch was taken, at live and evaluated nodes
     assert all(t.n[0] == I + extra for t in trees)
+
+
+@pytest.mark.parametrize('N', [5, 9])
+def test_puct_one_leaf_entry_points_ignore_the_reserved_word(N):
+    """gg_puct_select / gg_puct_backup on this test's own buffers, I iterations from an ended root, a root after a pass and a
+    mid-game root: once with the reserved word of every stat record at 0, once at 7.  Every tree buffer but that word is the
+    same bytes in both runs and equal to the restatement, and the word is still 7 on every record afterwards - the one-leaf
+    kernels neither read nor write it."""
+    import torch
+    from gymgo_amd import gogame, _lib
+    I, c, komi = 12, 0.6, 0.5
+    A, W, NN = N * N + 1, 5 * N + 1, I + 1
+    roots = np.concatenate([mc.crafted_roots(N)[3:], mc.crafted_roots(N)[1:2], mc.make_roots(N, 4, 29 + N, max_ply=3 * N, step=N)[2:3]])
+    R = roots.shape[0]
+    assert R == 3 and roots[0, 5].all() and roots[1, 4].all() and not roots[1:, 5].any() and roots[2, :2].any()
+    want = pe.expected_puct(roots, I, pe.hash_evaluator_np, c=c, komi=komi)
+    dev = torch.device('cuda', torch.cuda.current_device())
+    lib, stream = _lib.lib(), _lib.current_raw_stream(dev)
+    tracked = gogame._track_roots(mc.to_dev(roots))
+
+    def run(word):
+        z = lambda *shape, dtype=torch.int32: torch.zeros(shape, dtype=dtype, device=dev)
+        t = dict(boards=z(R, NN, W), child=z(R, NN, A), prior=z(R, NN, A, dtype=torch.float32), links=z(R, NN, 2),
+                 stats=z(R, NN, 4), nodes=z(R))
+        leaf, move, leaf_id = z(R, W), z(R), z(R)
+        states = torch.empty((R, 6, N, N), dtype=torch.uint8, device=dev)
+        tree = [t[k].data_ptr() for k in ('boards', 'child', 'prior', 'links', 'stats', 'nodes')]
+        out = [leaf.data_ptr(), move.data_ptr(), leaf_id.data_ptr()]
+        assert lib.gg_puct_begin(tracked.data_ptr(), R, N, I, *tree, stream) == 0
+        t['stats'][..., 3] = word
+        for _ in range(I):
+            assert lib.gg_puct_select(R, N, I, c, *tree, *out, stream) == 0
+            assert lib.gg_batch_play_moves_tracked(out[0], out[1], None, R, N, 1, stream) == 0
+            assert lib.gg_batch_untrack_states(out[0], states.data_ptr(), R, N, stream) == 0
+            p, v = pe.hash_evaluator_t(states, gogame._legal_roots(states))
+            assert lib.gg_puct_backup(R, N, I, komi, p.contiguous().data_ptr(), v.contiguous().data_ptr(), t['boards'].data_ptr(),
+                                      t['prior'].data_ptr(), t['links'].data_ptr(), t['stats'].data_ptr(), *out, stream) == 0
+        assert bool((t['stats'][..., 3] == word).all())                # the word is where it was, on every record
+        return t
+
+    a, b = run(0), run(7)
+    for k in ('boards', 'child', 'links', 'nodes'):
+        assert bool((a[k] == b[k]).all()), k
+    assert bool((a['prior'].view(torch.int32) == b['prior'].view(torch.int32)).all())
+    assert bool((a['stats'][..., :3] == b['stats'][..., :3]).all())
+    trees = want['trees']
+    assert b['nodes'].tolist() == [len(t.boards) for t in trees]
+    assert np.array_equal(mc.to_np(b['child']), np.stack([t.child for t in trees]).astype(np.int32))
+    assert np.array_equal(mc.to_np(b['links'][..., 0]), np.stack([t.parent for t in trees]))
+    assert np.array_equal(mc.to_np(b['links'][..., 1]), np.stack([t.action for t in trees]))
+    assert np.array_equal(mc.to_np(b['stats'][..., 2]), np.stack([t.n for t in trees]))
+    assert np.array_equal(pe.bits(b['stats'].view(torch.float64)[..., 0]), pe.bits(np.stack([t.w for t in trees])))
+    assert np.array_equal(pe.bits(b['prior']), pe.bits(np.stack([t.prior for t in trees])))
+    for r, t in enumerate(trees):   # the boards of the nodes in use
+        assert np.array_equal(mc.to_np(gogame.batch_untrack(b['boards'][r, :len(t.boards)].contiguous())), np.stack(t.boards)), r

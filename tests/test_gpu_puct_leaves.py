@@ -329,3 +329,74 @@ def test_leaves_virtual_visits_and_select_past_capacity_on_own_buffers():
             assert bool((flat[-TAIL:] == MARK).all()), (k, name)      # nothing beyond the buffers
     assert no_room > 0                                                # the branch was taken, at live and evaluated nodes
     assert any(len(t.boards) == NN for t in trees)
+
+
+def _planes_evaluator_t(planes, legal, life):
+    """On the device, from everything a select() hands out: priors from the capture plane, the point index and legal, the
+    value from the stone planes and the life planes.  Not symmetric: a turned leaf gets other priors."""
+    import torch
+    p, lf = planes.to(torch.float32), life.to(torch.float32)
+    B, N = p.shape[0], p.shape[-1]
+    q = 1 + (torch.arange(N * N, device=p.device) % 7).to(torch.float32) / 8
+    w = torch.cat([(1 + 2 * p[:, 12].reshape(B, N * N)) * q, torch.ones((B, 1), device=p.device)], dim=1) * legal
+    stones = (p[:, 0] - p[:, 1]).sum(dim=(1, 2))
+    decided = (lf[:, 0] + lf[:, 2] - lf[:, 1] - lf[:, 3]).sum(dim=(1, 2))
+    return w / w.sum(dim=1, keepdim=True).clamp(min=1), (stones + decided / 2) / (N * N)
+
+
+@pytest.mark.parametrize('N,R,T', [(5, 4, 10), (9, 4, 10), (19, 2, 4)])
+def test_leaves_none_hands_out_what_leaves_1_hands_out_with_everything_on(N, R, T):
+    """features, life and symmetry switched on: leaves=None and leaves=1 hand out the same planes, legal, life planes and
+    orientations at every select(), bit for bit (19x19: the 32-lane layout of the feature and life kernels), `live` is all
+    true, and the final results are equal as bit patterns."""
+    import torch
+    from gymgo_amd import gogame
+    roots = np.concatenate([mc.make_roots(N, 4, 50 + N, max_ply=N * N, step=N)[2:3], mc.crafted_roots(N)[1:]])[:R]
+    assert roots.shape[0] == R and not roots[:2, 5].any() and (R == 2 or roots[3, 5].all())
+    kw = dict(c=1.1, komi=0.5, features=torch.float16, life=True, symmetry=1234 + N)
+    sa, sb = gogame.PuctSearch(mc.to_dev(roots), T, **kw), gogame.PuctSearch(mc.to_dev(roots), T, leaves=1, **kw)
+    assert sa._L is None and sb._L == 1
+    turned = False
+    for t in range(T):
+        ha, hb = sa.select(), sb.select()
+        assert len(ha) == len(hb) == 3
+        for x, y, shape, dtype in zip(ha, hb, ((R, 16, N, N), (R, N * N + 1), (R, 4, N, N)), (torch.float16, torch.bool, torch.float16)):
+            assert tuple(x.shape) == tuple(y.shape) == shape and x.dtype == y.dtype == dtype, t
+            assert np.array_equal(pe.bits(x.view(torch.int16) if dtype == torch.float16 else x),
+                                  pe.bits(y.view(torch.int16) if dtype == torch.float16 else y)), (t, shape)
+        assert sa.orient.dtype == torch.int32 and tuple(sa.orient.shape) == (R,) and bool((sa.orient == sb.orient).all()), t
+        turned = turned or bool((sa.orient != 0).any())
+        for s in (sa, sb):
+            assert s.live.dtype == torch.bool and tuple(s.live.shape) == (R, 1) and bool(s.live.all()), t
+        sa.backup(*_planes_evaluator_t(*ha))
+        sb.backup(*_planes_evaluator_t(*hb))
+    assert turned
+    a, b = sa.result(tree=True), sb.result(tree=True)
+    assert int(a.root_visits.sum()) == R * T
+    for k in pe.ROOT_KEYS:
+        x, y = mc.to_np(getattr(a, k)), mc.to_np(getattr(b, k))
+        assert x.shape == y.shape and x.dtype == y.dtype and np.array_equal(pe.bits(x), pe.bits(y)), k
+    for k in pe.TREE_KEYS:
+        x, y = mc.to_np(getattr(a.tree, k)), mc.to_np(getattr(b.tree, k))
+        assert x.shape == y.shape and x.dtype == y.dtype and np.array_equal(pe.bits(x), pe.bits(y)), k
+
+
+def test_leaves_none_legal_is_the_mask_of_the_states_handed_out():
+    """leaves=None without features: at every select() the returned legal equals _legal_roots of the returned states (an
+    ended root among the roots: its row is all false) and `live` is [R, 1], all true."""
+    import torch
+    from gymgo_amd import gogame
+    N, T = 5, 30
+    roots = np.concatenate([mc.crafted_roots(N), mc.make_roots(N, 4, 31, max_ply=20, step=6)[1:3]])
+    R = roots.shape[0]
+    assert roots[3, 5].all()
+    s = gogame.PuctSearch(mc.to_dev(roots), T, c=0.6, komi=0.5)
+    for t in range(T):
+        states, legal = s.select()
+        assert legal.dtype == torch.bool and tuple(legal.shape) == (R, N * N + 1)
+        assert bool((legal == gogame._legal_roots(states)).all()), t
+        assert np.array_equal(mc.to_np(legal), mc.legal_mask(mc.to_np(states))), t
+        assert not bool(legal[3].any()) and bool(legal[:3].any(dim=1).all())
+        assert s.live.dtype == torch.bool and tuple(s.live.shape) == (R, 1) and bool(s.live.all())
+        s.backup(*pe.hash_evaluator_t(states, legal))
+    pe.check(s.result(tree=True), pe.expected_puct(roots, T, pe.hash_evaluator_np, c=0.6, komi=0.5))

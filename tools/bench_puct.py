@@ -6,7 +6,7 @@ batch_uct at the same R, I, K; prints one JSON line per configuration.
 
 Workload: R mid-game roots (random play from the empty board, `--plies` plies), komi 7.5.
   null:      the evaluator returns the same preallocated priors (1 / A everywhere) and values (0) every time - no evaluator
-             work, so an iteration is k_puct_select, the one-move step, untrack, the legality mask (a few torch kernels) and
+             work, so an iteration is k_puct_select, the one-move step, untrack, the legality mask (k_puct_legal) and
              k_puct_backup plus the host loop around them.  us_per_iteration is wall time (events on the stream) of
              batch_puct / I, gg_puct_begin's memsets included (begin_ms: measured on its own); median of `--reps` runs.
              For the device time per kernel run it once under `rocprofv3 --kernel-trace --stats -- python
