@@ -28,7 +28,8 @@ EXPORTS = (
     'gg_puct_select_leaves', 'gg_puct_backup_leaves', 'gg_puct_legal', 'gg_puct_advance', 'gg_batch_rollout_ws',
     'gg_puct_root_noise', 'gg_puct_root_policy', 'gg_feature_planes', 'gg_batch_group_liberties', 'gg_batch_features',
     'gg_batch_features_tracked', 'gg_batch_features_oriented', 'gg_batch_features_tracked_oriented', 'gg_batch_symmetry_policy',
-    'gg_batch_draw_orient', 'gg_life_planes', 'gg_batch_life', 'gg_batch_life_tracked',
+    'gg_batch_draw_orient', 'gg_life_planes', 'gg_batch_life', 'gg_batch_life_tracked', 'gg_batch_ladder',
+    'gg_batch_ladder_tracked',
 )
 
 _vp, _i64, _i32, _u64 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_uint64
@@ -107,6 +108,8 @@ _SIGNATURES = {
     'gg_life_planes': ([], _i32),
     'gg_batch_life': ([_vp, _vp, _vp, _vp, _i32, _i64, _i32, _vp], _i32),
     'gg_batch_life_tracked': ([_vp, _vp, _vp, _vp, _i32, _i64, _i32, _vp], _i32),
+    'gg_batch_ladder': ([_vp, _vp, _vp, _vp, _i32, _i64, _i32, _vp], _i32),
+    'gg_batch_ladder_tracked': ([_vp, _vp, _vp, _vp, _i32, _i64, _i32, _vp], _i32),
 }
 
 _lib = None

@@ -1035,6 +1035,79 @@ def batch_settled(batch_states):
     return batch_life(batch_states, torch.uint8, settled=True)[1]
 
 
+# ---------------------------------------------------------------- ladder planes
+LADDER_PLANES = 4   # GG_LADDER_PLANES of include/gymgo_amd.h
+LADDER_NAMES = ('own_laddered', 'opp_laddered', 'ladder_capture', 'ladder_escape')
+
+
+def _ladder_launch(name, boards, boards_dtype, orient, planes, dtype, code, want_aborted, B, N):
+    """One launch of gg_batch_ladder / gg_batch_ladder_tracked on the boards' device -> the aborted bytes or None."""
+    dev = boards.device
+    counts = torch.empty(B, dtype=_U8, device=dev) if want_aborted else None
+    o = None if orient is None else _actions_tensor(orient, B, dev)
+    _lib.check(getattr(_lib.lib(), name)(_lib.dev_ptr(boards, boards_dtype, 'boards'), _lib.dev_ptr(o, _I32, 'orient'),
+                                         _lib.dev_ptr(planes, dtype, 'out'), _lib.dev_ptr(counts, _U8, 'aborted'), code, B, N,
+                                         _lib.stream_ptr(dev)), name)
+    return counts
+
+
+def batch_ladder(batch_states, dtype=torch.uint8, out=None, orient=None, aborted=False):
+    """Ladder planes of every board -> [B, 4, N, N] of `dtype` (gg_batch_ladder), from the mover's point of view, each value
+    exactly 0 or 1 (LADDER_NAMES):
+       0  own stones of laddered chains          1  the opponent's
+       2  ladder captures: the ataris on an opponent chain with two liberties that capture it in a ladder
+       3  ladder escapes: the moves that get an own chain with one liberty out
+    by a bounded search per board on the device: the prey extends or captures a chaser in atari, the attacker ataris on either
+    of the two liberties, until the prey has three liberties (escaped) or none to play for (captured); a chain with two
+    liberties is laddered when some atari works, a chain with one when no move escapes.  A root query gets
+    GG_LADDER_DEPTH(N) = 4 N plies and GG_LADDER_NODES(N) = 16 N nodes; past either it is aborted and answers "not captured" /
+    "escapes".  The definition with its evaluation order: include/gymgo_amd.h.  Exact, bit for bit.  A board whose game is
+    over gets planes 2 and 3 clear.  dtype: torch.uint8, float16, bfloat16 or float32 (ValueError otherwise).  out: a
+    contiguous device tensor of that shape and dtype to write into.  orient (None, or int [B], only orient & 7 is read): row b
+    holds the planes of the turned position (turned first, then searched).  aborted=True: -> (planes, uint8 [B]): the
+    aborted root queries of the board, saturated at 255.  NumPy in gives NumPy out (through the device; not for bfloat16).
+    One launch either way; device memory of the result: 4 * B * N^2 elements (+ B bytes)."""
+    code = _feature_dtype(dtype)
+    B, N = _states_shape(batch_states)
+    _life_out(out, (B, LADDER_PLANES, N, N), dtype)
+    if orient is not None:
+        _orient_arg(orient, B)
+    if not isinstance(batch_states, torch.Tensor) and dtype == torch.bfloat16:
+        raise ValueError('NumPy has no bfloat16: pass a device tensor, or another dtype')
+    box = _Box(batch_states)
+    st = box.t
+    _life_out(out, (B, LADDER_PLANES, N, N), dtype, st.device)
+    planes = out if out is not None else torch.empty((B, LADDER_PLANES, N, N), dtype=dtype, device=st.device)
+    counts = _ladder_launch('gg_batch_ladder', st, _U8, orient, planes, dtype, code, aborted, B, N)
+    return (_back(box, planes), _back(box, counts)) if aborted else _back(box, planes)
+
+
+def ladder(state, dtype=torch.uint8, aborted=False):
+    """batch_ladder of one state [6, N, N] -> [4, N, N] (with aborted=True: and a uint8 scalar)."""
+    _feature_dtype(dtype)
+    if not isinstance(state, torch.Tensor) and dtype == torch.bfloat16:
+        raise ValueError('NumPy has no bfloat16: pass a device tensor, or another dtype')
+    box = _Box(state)
+    res = batch_ladder(box.t[None], dtype, aborted=aborted)
+    return (_back(box, res[0], row0=True), _back(box, res[1], row0=True)) if aborted else _back(box, res, row0=True)
+
+
+def batch_ladder_tracked(tracked, dtype=torch.uint8, out=None, orient=None, aborted=False):
+    """batch_ladder of tracked boards (int32 [B, 5N+1], a device tensor) -> [B, 4, N, N] of `dtype` (gg_batch_ladder_tracked):
+    bit for bit what batch_ladder gives for batch_untrack(tracked); the class rows are not read."""
+    code = _feature_dtype(dtype)
+    if not isinstance(tracked, torch.Tensor) or tracked.dim() != 2:
+        raise ValueError('tracked boards are int32 [B, 5N+1] device tensors')
+    N = _tracked_size(tracked)
+    B = tracked.shape[0]
+    if orient is not None:
+        _orient_arg(orient, B)
+    _life_out(out, (B, LADDER_PLANES, N, N), dtype, tracked.device if tracked.is_cuda else None)
+    planes = out if out is not None else torch.empty((B, LADDER_PLANES, N, N), dtype=dtype, device=tracked.device)
+    counts = _ladder_launch('gg_batch_ladder_tracked', tracked, _I32, orient, planes, dtype, code, aborted, B, N)
+    return (planes, counts) if aborted else planes
+
+
 def batch_play_moves_tracked(tracked, moves, played=None):
     """IN PLACE batch_play_moves on tracked boards; moves [B, T] (T = 1: one GoEnv.step per game) -> played int32 [B]."""
     N = _tracked_size(tracked)
@@ -1579,14 +1652,21 @@ class PuctSearch:
     (planes, legal, life) with life [R, 4, N, N] ([R * L, ..]) of the feature dtype - batch_life of the leaves, from the
     tracked leaf boards (gg_batch_life_tracked) - in the orientation of `search.orient` with symmetry=.  One launch more
     per select(); backup, advance, root_policy and the tree do not change.  Rows of empty slots hold the planes of whatever
-    board their row holds."""
+    board their row holds.
+
+    ladder (False = everything above, launch for launch; True needs features=, ValueError otherwise): select() returns the
+    ladder planes [R, 4, N, N] ([R * L, ..]) of the feature dtype as its last element, after the life planes if both are on -
+    batch_ladder of the leaves, from the tracked leaf boards (gg_batch_ladder_tracked), in the orientation of
+    `search.orient` with symmetry= (the planes of the turned leaf).  One launch more per select(); nothing else changes."""
 
     def __init__(self, batch_states, iterations, c=1.25, komi=0.0, leaves=None, capacity=None, features=None, symmetry=None,
-                 first_root=0, life=False):
+                 first_root=0, life=False, ladder=False):
         self._feat = None if features is None else (features, _feature_dtype(features))
         _puct_symmetry_guard(symmetry, features)
         _puct_life_guard(life, features)
+        _puct_ladder_guard(ladder, features)
         self._life = bool(life)
+        self._ladder = bool(ladder)
         self._sym = None if symmetry is None else int(symmetry)
         self._first_root = int(first_root)
         self.orient = None
@@ -1620,6 +1700,8 @@ class PuctSearch:
         self._legal = torch.empty((B, A), dtype=torch.bool, device=dev)
         if self._life:
             self._life_planes = torch.empty((B, LIFE_PLANES, N, N), dtype=self._feat[0], device=dev)
+        if self._ladder:
+            self._ladder_planes = torch.empty((B, LADDER_PLANES, N, N), dtype=self._feat[0], device=dev)
         self.live = torch.full((R, self._L or 1), self._L is None, dtype=torch.bool, device=dev)   # (one leaf: always live)
         self._done, self._pending = 0, False
         self._init_symmetry(B)
@@ -1673,7 +1755,7 @@ class PuctSearch:
     def select(self):
         """Step 1 and 2 of the next iteration -> (states uint8 [R, 6, N, N], legal bool [R, A]) of the R leaves ([R * L, ..]
         with leaves=L); with features=dtype (planes [R, 16, N, N] of that dtype, legal); with life=True (planes, legal, life
-        [R, 4, N, N] of that dtype)."""
+        [R, 4, N, N] of that dtype); with ladder=True the ladder planes [R, 4, N, N] of that dtype as the last element."""
         if self._pending:
             raise ValueError('PuctSearch.select(): the leaves of the last select() have not been backed up')
         if self._done >= self._I:
@@ -1704,9 +1786,14 @@ class PuctSearch:
                 _lib.check(lib.gg_batch_life_tracked(lp, None if self._sym is None else op,
                                                      _lib.dev_ptr(self._life_planes, self._feat[0], 'life'), None, self._feat[1],
                                                      B, N, stream), 'gg_batch_life_tracked')
+            if self._ladder:
+                _lib.check(lib.gg_batch_ladder_tracked(lp, None if self._sym is None else op,
+                                                       _lib.dev_ptr(self._ladder_planes, self._feat[0], 'ladder'), None,
+                                                       self._feat[1], B, N, stream), 'gg_batch_ladder_tracked')
         self._pending = True
         legal = self._legal if self._sym is None else self._legal_view
-        return (self._states, legal, self._life_planes) if self._life else (self._states, legal)
+        res = (self._states, legal, self._life_planes) if self._life else (self._states, legal)
+        return res + (self._ladder_planes,) if self._ladder else res
 
     def backup(self, priors, values):
         """Step 4: priors float32 [R, A] and values float32 [R] (the value for the player to move at the leaf) of the leaves
@@ -1916,7 +2003,7 @@ class PuctSearch:
 
 
 def batch_puct(batch_states, iterations, evaluator, c=1.25, komi=0.0, tree=False, leaves=None, capacity=None, features=None,
-               symmetry=None, first_root=0, life=False):
+               symmetry=None, first_root=0, life=False, ladder=False):
     """PUCT search (the AlphaZero search) of `iterations` iterations from every root of batch_states ([R, 6, N, N]) with the
     caller's evaluator -> Puct (device tensors for a device tensor, NumPy arrays for NumPy input).  The loop over PuctSearch.
 
@@ -1973,12 +2060,17 @@ def batch_puct(batch_states, iterations, evaluator, c=1.25, komi=0.0, tree=False
 
     life (False: the search above, launch for launch; True, with features=): the evaluator is called as
     evaluator(planes, legal, life) with life [R, 4, N, N] ([R * L, ..]) of the feature dtype - batch_life of the leaves, in
-    the leaf's orientation with symmetry= (PuctSearch).  The tree does not depend on it but through the evaluator."""
+    the leaf's orientation with symmetry= (PuctSearch).  The tree does not depend on it but through the evaluator.
+
+    ladder (False: the search above, launch for launch; True, with features=): the evaluator is called as
+    evaluator(planes, legal, [life,] ladder) with ladder [R, 4, N, N] ([R * L, ..]) of the feature dtype - batch_ladder of the
+    leaves, in the leaf's orientation with symmetry= (PuctSearch)."""
     _puct_komi_guard(evaluator, komi)
     _puct_features_guard(evaluator, features)
     _puct_life_guard(life, features)
+    _puct_ladder_guard(ladder, features)
     search = PuctSearch(batch_states, iterations, c, komi, leaves=leaves, capacity=capacity, features=features, symmetry=symmetry,
-                        first_root=first_root, life=life)
+                        first_root=first_root, life=life, ladder=ladder)
     for _ in range(search._I):
         priors, values = evaluator(*search.select())
         search.backup(priors, values)
@@ -2001,6 +2093,11 @@ def _puct_life_guard(life, features):
         raise ValueError('life=True hands out the life planes in the dtype of features=: give features= too')
 
 
+def _puct_ladder_guard(ladder, features):
+    if ladder and features is None:   # (before a device is touched)
+        raise ValueError('ladder=True hands out the ladder planes in the dtype of features=: give features= too')
+
+
 def _puct_features_guard(evaluator, features):
     if features is not None:
         _feature_dtype(features)
@@ -2009,7 +2106,7 @@ def _puct_features_guard(evaluator, features):
 
 
 def puct_play(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, leaves=None, capacity=None, reuse=True, features=None,
-              symmetry=None, first_root=0, life=False):
+              symmetry=None, first_root=0, life=False, ladder=False):
     """Play `moves` moves from every root of batch_states ([R, 6, N, N]) with a PUCT search per move -> (actions int64
     [R, moves], the final states uint8 [R, 6, N, N]); device tensors for a device tensor, NumPy arrays for NumPy input.
     Per move: `iterations` rounds of PuctSearch (batch_puct's loop, with `leaves` and `capacity` as there), the move of
@@ -2029,15 +2126,16 @@ def puct_play(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, leav
     loop with it, with moves drawn from the visit counts and with the training records.  features: as batch_puct - the
     evaluator gets (planes, legal).  symmetry, first_root: as batch_puct; with reuse=False the search of move mv draws from
     the base seed symmetry + mv (a new search would repeat the first one's draws otherwise).  life: as batch_puct - the
-    evaluator gets (planes, legal, life)."""
+    evaluator gets (planes, legal, life).  ladder: as batch_puct - the ladder planes as the evaluator's last argument."""
     _puct_komi_guard(evaluator, komi)
     _puct_features_guard(evaluator, features)
     _puct_life_guard(life, features)
+    _puct_ladder_guard(ladder, features)
     moves = int(moves)
     if moves < 0:
         raise ValueError('need moves >= 0 (got %d)' % moves)
     search = PuctSearch(batch_states, iterations, c, komi, leaves=leaves, capacity=capacity, features=features, symmetry=symmetry,
-                        first_root=first_root, life=life)
+                        first_root=first_root, life=life, ladder=ladder)
     box = search._box
     played = torch.empty((search._R, moves), dtype=_I64, device=box.t.device)
     for mv in range(moves):
@@ -2051,7 +2149,8 @@ def puct_play(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, leav
         else:   # only node 0's boards are played on: the tree goes, so no advance over it; the states stay on the device
             box.t = search._played_states(played[:, mv])
             search = PuctSearch(box, iterations, c, komi, leaves=leaves, capacity=capacity, features=features,
-                                symmetry=None if symmetry is None else int(symmetry) + mv + 1, first_root=first_root, life=life)
+                                symmetry=None if symmetry is None else int(symmetry) + mv + 1, first_root=first_root, life=life,
+                                ladder=ladder)
     return _back(box, played), box.back(search._root_states())
 
 
@@ -2087,7 +2186,7 @@ that ended, 0 for one still running), lengths (int32 [R]: moves played), final_s
 
 def puct_selfplay(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, leaves=None, capacity=None, noise=None,
                   eps=0.25, sample_moves=0, seed=20260927, first_game=0, record_states=False, features=None, symmetry=None,
-                  life=False):
+                  life=False, ladder=False):
     """Self-play games for training: `moves` moves from every root of batch_states ([R, 6, N, N]) with a PUCT search per move
     on the kept tree -> SelfPlay (device tensors for a device tensor, NumPy arrays for NumPy input).  puct_play's
     reuse=True loop (`iterations` rounds per move with `leaves` and `capacity` as there, then PuctSearch.advance) with
@@ -2113,10 +2212,12 @@ def puct_selfplay(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, 
     in the boards' own frame.  A trainer takes its samples from the records with selfplay_batch: the planes of the recorded
     positions and the policy targets, in any of the eight orientations.  life: as batch_puct - the evaluator gets (planes,
     legal, life); the records do not change, and there is no stopping rule here: a driver that wants to stop settled games
-    early asks batch_settled(search.root_states()) in a loop of its own."""
+    early asks batch_settled(search.root_states()) in a loop of its own.  ladder: as batch_puct - the ladder planes as the
+    evaluator's last argument; the records do not change."""
     _puct_komi_guard(evaluator, komi)
     _puct_features_guard(evaluator, features)
     _puct_life_guard(life, features)
+    _puct_ladder_guard(ladder, features)
     moves, sample_moves, eps = int(moves), int(sample_moves), float(eps)
     if moves < 0:
         raise ValueError('need moves >= 0 (got %d)' % moves)
@@ -2144,7 +2245,7 @@ def puct_selfplay(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, 
     if not R or not moves:
         return _back(box, SelfPlay(played, pis, vals, outcome, lengths, st, before))
     search = PuctSearch(box, I, c, komi, leaves=leaves, capacity=capacity, features=features, symmetry=symmetry, first_root=first_game,
-                        life=life)
+                        life=life, ladder=ladder)
     rng = rng_seed(R, seed, first_game, device=dev)
     ones, todo = torch.ones(R, dtype=_U8, device=dev), torch.empty(R, dtype=_U8, device=dev)
     for mv in range(moves):
@@ -2176,6 +2277,7 @@ def puct(state, iterations, evaluator, **kw):
     still sees a batch of one."""
     _puct_symmetry_guard(kw.get('symmetry'), kw.get('features'))
     _puct_life_guard(kw.get('life', False), kw.get('features'))
+    _puct_ladder_guard(kw.get('ladder', False), kw.get('features'))
     return _single(batch_puct, state, iterations, evaluator, **kw)
 
 
@@ -2184,6 +2286,7 @@ def puct_actions(batch_states, iterations, evaluator, **kw):
     iterations, evaluator, **kw); ties go to the lowest action, a root without a legal move gives -1."""
     _puct_symmetry_guard(kw.get('symmetry'), kw.get('features'))
     _puct_life_guard(kw.get('life', False), kw.get('features'))
+    _puct_ladder_guard(kw.get('ladder', False), kw.get('features'))
     box = _Box(batch_states)
     res = batch_puct(box.t, iterations, evaluator, **kw)
     return _best_legal(box, res.legal, res.visits.to(_I64))
@@ -2454,7 +2557,7 @@ def selfplay_targets(record, games, moves):
     return torch.where(white, -outcome, outcome), m < t(record.lengths, dev)[g].to(_I64)
 
 
-def selfplay_batch(record, games, moves, orient, dtype=torch.float16, life=False):
+def selfplay_batch(record, games, moves, orient, dtype=torch.float16, life=False, ladder=False):
     """Training samples from a self-play record, in one of the eight orientations each -> (planes [B, 16, N, N] of `dtype`,
     pi [B, A] float32, z float32 [B], valid bool [B]).  record: a SelfPlay of puct_selfplay(.., record_states=True)
     (ValueError if record.states is None); games, moves, orient: int [B] - sample i is the position before move moves[i] of
@@ -2462,7 +2565,8 @@ def selfplay_batch(record, games, moves, orient, dtype=torch.float16, life=False
     the recorded visit-count target turned with batch_symmetry_policy - both in the view; z, valid: selfplay_targets.  The
     eightfold augmentation of a sample is this call with orient = 0 .. 7.  Nothing synchronises; device tensors, or NumPy
     arrays for a NumPy record (through the device).  life=True: a fifth element, the life planes [B, 4, N, N] of the
-    recorded positions in view orient and dtype `dtype` (batch_life, one launch more)."""
+    recorded positions in view orient and dtype `dtype` (batch_life, one launch more).  ladder=True: as the last element the
+    ladder planes [B, 4, N, N] of the recorded positions in view orient and dtype `dtype` (batch_ladder, one launch more)."""
     _feature_dtype(dtype)
     z, valid = selfplay_targets(record, games, moves)
     is_np = not isinstance(record.states, torch.Tensor)
@@ -2479,4 +2583,6 @@ def selfplay_batch(record, games, moves, orient, dtype=torch.float16, life=False
     res = (planes, pi, z.to(dev), valid.to(dev))
     if life:
         res += (batch_life(positions, dtype, orient=orient),)
+    if ladder:
+        res += (batch_ladder(positions, dtype, orient=orient),)
     return tuple(x.cpu().numpy() for x in res) if is_np else res

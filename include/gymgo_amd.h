@@ -786,6 +786,55 @@ int32_t gg_batch_life(const uint8_t *states, const int32_t *orient, void *out, u
 int32_t gg_batch_life_tracked(const uint32_t *tracked, const int32_t *orient, void *out, uint8_t *settled, int32_t out_dtype,
                               int64_t B, int32_t N, void *hip_stream);
 
+/*
+ * Ladder planes: the first tactical fact that needs reading - a bounded search per board, all integers and
+ * sets, bit-exact against tests/ladder_expect.py.
+ * TERMS.  Colours, chains and liberties as for the feature planes; points are ordered row-major.  The PREY is a chain, the
+ * DEFENDER its colour, the ATTACKER the other colour.  A search is a sequence of legal moves on a copy of the position:
+ * captures as in the rules (the opponent chains next to the played stone that are left without a liberty go first); a
+ * move is legal when the point is empty, is not the current ko point and, after captures, the played stone's chain has a
+ * liberty; a move that captures exactly one stone and whose own chain is then that single stone with exactly one liberty
+ * makes the captured point the ko point for the next move only.  At the root the ko point of the position (plane 11 of the
+ * feature planes) applies exactly when the first player of the search is the player to move, otherwise there is none.
+ * NODE D(pos, c): the defender moves, c has exactly one liberty L.  Options, in order: 1. L; 2. the sole liberty of each
+ * attacker chain adjacent to c that has exactly one liberty - distinct points in row-major order, L skipped.  A legal
+ * option leaves the chain c' that holds c's stones with n liberties: n >= 3: the option escapes; n <= 1: it fails;
+ * n == 2: it escapes iff A(pos', c') is false.  D is true (captured) iff no option escapes; evaluation stops at the first.
+ * NODE A(pos, c): the attacker moves, c has exactly two liberties L1 < L2.  For each Li in order that is legal for the
+ * attacker the option works iff D(pos', c) is true.  A is true iff some option works; evaluation stops at the first.
+ * BOUNDS.  Every entry into D or A counts one node; its depth is the number of moves played on the copy.  A root query that
+ * would enter a node at depth > GG_LADDER_DEPTH(N) = 4 N, or a node beyond number GG_LADDER_NODES(N) = 16 N, is ABORTED:
+ * its answer is "not captured" for an attacker query and "escapes" for a defender query, whatever had been found.  (The
+ * principal line of a ladder across the board's diagonal is below 4 N plies; a wrong atari costs about two nodes before the
+ * prey has three liberties, so 16 N leaves a factor above the clean ladder and bounds the launch.)  The evaluation order is
+ * part of the definition: it decides what an aborted query had counted.
+ * ROOT QUERIES, one budget each, independent of one another.  For every chain c with exactly two liberties and each Li:
+ * work(c, Li) iff Li is legal for the attacker and D of the resulting position is true (false if aborted).  For every chain
+ * c with exactly one liberty and each option o of D: esc(c, o) iff o is legal and escapes (true if aborted).
+ * laddered(c): some work(c, Li) for a two-liberty chain, no esc(c, o) for a one-liberty chain; chains with none or with three
+ * and more liberties never.  Whose turn it is does not enter but through the root ko.
+ * out [B][GG_LADDER_PLANES][N][N], every element exactly 0 or 1, OWN = the player to move:
+ *    0  own stones of laddered chains             1  opponent stones of laddered chains
+ *    2  ladder captures: the points Li with work(c, Li) for an opponent two-liberty chain c
+ *    3  ladder escapes: the points o with esc(c, o) for an own one-liberty chain c
+ * A board whose game is over gets planes 2 and 3 clear.  aborted (NULL, or uint8 [B]): min(aborted root queries of the
+ * board, 255).  orient (NULL, or int32 [B], only orient[b] & 7 is read; gg_batch_symmetry's orientations): out[b] and
+ * aborted[b] are those of the TURNED position - turned first, then searched (the planes are geometric up to the row-major
+ * tie-breaks, which only matter inside aborted queries).
+ *   gg_batch_ladder           states uint8 [B][6][N][N] -> out of out_dtype: GG_W_F32 / GG_W_BF16 / GG_W_F16 / GG_FEAT_U8
+ *   gg_batch_ladder_tracked   the same from tracked boards uint32 [B][gg_tracked_words(N)]: the same bytes for
+ *                             gg_batch_track_states(s) and s
+ * Alignment, stores and the checks with their order and codes: gg_batch_life's.  Every call queues ONE launch on hip_stream
+ * and never synchronises; no global atomics.
+ */
+#define GG_LADDER_PLANES 4
+#define GG_LADDER_DEPTH(N) (4 * (N))
+#define GG_LADDER_NODES(N) (16 * (N))
+int32_t gg_batch_ladder(const uint8_t *states, const int32_t *orient, void *out, uint8_t *aborted, int32_t out_dtype, int64_t B,
+                        int32_t N, void *hip_stream);
+int32_t gg_batch_ladder_tracked(const uint32_t *tracked, const int32_t *orient, void *out, uint8_t *aborted, int32_t out_dtype,
+                                int64_t B, int32_t N, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
