@@ -12,7 +12,7 @@ import pytest
 import features_expect as fe
 import ladder_expect as le
 import mc_expect as mc
-import mc_policy_expect as mp
+import plane_cases as pc
 import test_gpu_features as tgf
 import test_gpu_life as tgl
 import test_gpu_symmetry_io as tsio
@@ -31,16 +31,9 @@ def batch_of(N):
 
 @functools.lru_cache(maxsize=None)
 def positions(N):
-    """Policy positions from the empty board (the CPU policy_rollout, auto_reset off), a third of the boards each after
-    N^2 / 2, N^2 and 3 N^2 / 2 plies -> (NumPy states, planes, aborted, stats), computed once."""
-    B = batch_of(N)
-    cur, rng = np.zeros((B, 6, N, N), np.uint8), mc.po_seed(11 + N, np.arange(B))
-    cuts = [0, B // 3, 2 * B // 3, B]
-    out, done = np.zeros_like(cur), 0
-    for i, depth in enumerate((N * N // 2, N * N, 3 * N * N // 2)):
-        cur, rng, _, _ = mp.policy_rollout(cur, rng, depth - done, auto_reset=False)
-        done = depth
-        out[cuts[i]:cuts[i + 1]] = cur[cuts[i]:cuts[i + 1]]
+    """Policy positions from the empty board (plane_cases.policy_positions: a third of the boards each after N^2 / 2, N^2
+    and 3 N^2 / 2 plies) -> (NumPy states, planes, aborted, stats), computed once."""
+    out = pc.policy_positions(N, batch_of(N), seed=11)
     planes, aborted, stats = le.batch_ladder(out, stats=True)
     return out, planes, aborted, stats
 
