@@ -1,74 +1,81 @@
-// gg_feat.hip - the launches of the feature-plane kernels (gg_feat.h: gg_batch_features, gg_batch_features_tracked, their
-// oriented forms, gg_batch_group_liberties) as a translation unit of their own, compiled with the default code-generation switches: the
-// machine code of every kernel of the other four units - and the hashes bench.py ties their PMC records to - does not
-// depend on anything in here.
+// gg_feat.hip - the feature-plane kernels (gg_feat.h) with their entry points (gg_feature_planes, gg_batch_group_liberties,
+// gg_batch_features, gg_batch_features_tracked and their oriented forms) as a translation unit of their own, compiled with
+// the default code-generation switches: the machine code of every kernel of the other units - and the hashes bench.py ties
+// their PMC records to - does not depend on anything in here.  The launch path is plane_launch of gg_planes.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "gg_common.h"
-#include "gg_v2.h"
-#include "gg_lat.h"
+#include "gymgo_amd.h"
 #include "gg_feat.h"
 
-namespace gg {
-
 namespace {
-// one single-wave workgroup per four (N <= 13) / two boards, at most 64 per compute unit (the rest: grid-stride)
-unsigned feat_grid(int cus, int64_t B, int nbw) {
-  const int64_t groups = (B + nbw - 1) / nbw, cap = (int64_t)cus * 64;
-  return (unsigned)(groups < cap ? groups : cap);
+
+using namespace gg;
+
+// k_features / k_features_oriented (orient given) with the element size as a template argument
+struct FeatureCall {
+  const void *in;
+  const int32_t *orient;
+  uint8_t *out;
+  int64_t B;
+  int32_t N;
+  template <int R, int ES, bool TRACKED>
+  void launch_e(unsigned grid, hipStream_t s, uint32_t one) const {
+    if (orient) k_features_oriented<R, ES, TRACKED><<<grid, kWave, 0, s>>>(in, orient, out, one, B, N);
+    else k_features<R, ES, TRACKED><<<grid, kWave, 0, s>>>(in, out, one, B, N);
+  }
+  template <int R, bool TRACKED>
+  void launch(unsigned grid, hipStream_t s, int esh, uint32_t one) const {
+    if (esh == 0) launch_e<R, 1, TRACKED>(grid, s, one);
+    else if (esh == 1) launch_e<R, 2, TRACKED>(grid, s, one);
+    else launch_e<R, 4, TRACKED>(grid, s, one);
+  }
+};
+
+// out: 16-byte aligned; oriented: orient must be given
+int32_t batch_features(bool tracked, const void *in, const int32_t *orient, bool oriented, void *out, int32_t dtype, int64_t B,
+                       int32_t N, void *hip_stream) {
+  return plane_launch(FeatureCall{in, orient, static_cast<uint8_t *>(out), B, N}, tracked, in, out, oriented ? orient : out, 15, dtype,
+                      B, N, hip_stream);
 }
+
+struct LibertiesCall {
+  const uint8_t *states;
+  uint8_t *libs;
+  int64_t B;
+  int32_t N;
+  template <int R, bool TRACKED>
+  void launch(unsigned grid, hipStream_t s, int, uint32_t) const {
+    k_group_liberties<R><<<grid, kWave, 0, s>>>(states, libs, B, N);
+  }
+};
+
 }  // namespace
 
-// dtype: GG_W_F32 / GG_W_BF16 / GG_W_F16 / GG_FEAT_U8 (checked by the caller); `in`: byte planes, or tracked boards
-#define GG_FEAT_E(R, ES, ONE)                                                                                          \
-  do {                                                                                                                 \
-    const unsigned grid_ = feat_grid(cus, B, Feat<R>::NBW);                                                            \
-    if (tracked) k_features<R, ES, true><<<grid_, kWave, 0, s>>>(in, static_cast<uint8_t *>(out), ONE, B, N);          \
-    else k_features<R, ES, false><<<grid_, kWave, 0, s>>>(in, static_cast<uint8_t *>(out), ONE, B, N);                 \
-  } while (0)
-#define GG_FEAT(R)                                                \
-  do {                                                            \
-    if (dtype == GG_FEAT_U8) GG_FEAT_E(R, 1, 1u);                 \
-    else if (dtype == GG_W_F16) GG_FEAT_E(R, 2, 0x3C00u);         \
-    else if (dtype == GG_W_BF16) GG_FEAT_E(R, 2, 0x3F80u);        \
-    else GG_FEAT_E(R, 4, 0x3F800000u);                            \
-  } while (0)
-void launch_features(bool tracked, const void *in, void *out, int dtype, int64_t B, int32_t N, int cus, hipStream_t s) {
-  if (N <= 9) GG_FEAT(9);
-  else if (N <= 13) GG_FEAT(13);
-  else GG_FEAT(19);
-}
-#undef GG_FEAT
-#undef GG_FEAT_E
+extern "C" {
 
-// ... and view orient[b] of them (k_features_oriented: the same grid, the boards turned in registers after the load)
-#define GG_FEAT_E(R, ES, ONE)                                                                                                        \
-  do {                                                                                                                               \
-    const unsigned grid_ = feat_grid(cus, B, Feat<R>::NBW);                                                                          \
-    if (tracked) k_features_oriented<R, ES, true><<<grid_, kWave, 0, s>>>(in, orient, static_cast<uint8_t *>(out), ONE, B, N);       \
-    else k_features_oriented<R, ES, false><<<grid_, kWave, 0, s>>>(in, orient, static_cast<uint8_t *>(out), ONE, B, N);              \
-  } while (0)
-#define GG_FEAT(R)                                                \
-  do {                                                            \
-    if (dtype == GG_FEAT_U8) GG_FEAT_E(R, 1, 1u);                 \
-    else if (dtype == GG_W_F16) GG_FEAT_E(R, 2, 0x3C00u);         \
-    else if (dtype == GG_W_BF16) GG_FEAT_E(R, 2, 0x3F80u);        \
-    else GG_FEAT_E(R, 4, 0x3F800000u);                            \
-  } while (0)
-void launch_features_oriented(bool tracked, const void *in, const int32_t *orient, void *out, int dtype, int64_t B, int32_t N, int cus,
-                              hipStream_t s) {
-  if (N <= 9) GG_FEAT(9);
-  else if (N <= 13) GG_FEAT(13);
-  else GG_FEAT(19);
-}
-#undef GG_FEAT
-#undef GG_FEAT_E
+int32_t gg_feature_planes(void) { return gg::kFeatPlanes; }
 
-void launch_group_liberties(const uint8_t *states, uint8_t *libs, int64_t B, int32_t N, int cus, hipStream_t s) {
-  if (N <= 9) k_group_liberties<9><<<feat_grid(cus, B, Feat<9>::NBW), kWave, 0, s>>>(states, libs, B, N);
-  else if (N <= 13) k_group_liberties<13><<<feat_grid(cus, B, Feat<13>::NBW), kWave, 0, s>>>(states, libs, B, N);
-  else k_group_liberties<19><<<feat_grid(cus, B, Feat<19>::NBW), kWave, 0, s>>>(states, libs, B, N);
+int32_t gg_batch_group_liberties(const uint8_t *states, uint8_t *libs, int64_t B, int32_t N, void *hip_stream) {
+  return plane_launch(LibertiesCall{states, libs, B, N}, false, states, libs, libs, 0, GG_FEAT_U8, B, N, hip_stream);
 }
 
-}  // namespace gg
+int32_t gg_batch_features(const uint8_t *states, void *out, int32_t out_dtype, int64_t B, int32_t N, void *hip_stream) {
+  return batch_features(false, states, nullptr, false, out, out_dtype, B, N, hip_stream);
+}
+
+int32_t gg_batch_features_tracked(const uint32_t *tracked, void *out, int32_t out_dtype, int64_t B, int32_t N, void *hip_stream) {
+  return batch_features(true, tracked, nullptr, false, out, out_dtype, B, N, hip_stream);
+}
+
+int32_t gg_batch_features_oriented(const uint8_t *states, const int32_t *orient, void *out, int32_t out_dtype, int64_t B, int32_t N,
+                                   void *hip_stream) {
+  return batch_features(false, states, orient, true, out, out_dtype, B, N, hip_stream);
+}
+
+int32_t gg_batch_features_tracked_oriented(const uint32_t *tracked, const int32_t *orient, void *out, int32_t out_dtype, int64_t B,
+                                           int32_t N, void *hip_stream) {
+  return batch_features(true, tracked, orient, true, out, out_dtype, B, N, hip_stream);
+}
+
+}  // extern "C"

@@ -24,6 +24,7 @@
 #endif
 
 #include "gg_common.h"
+#include "gg_host.h"
 #include "gg_v2.h"
 #include "gg_v4.h"
 #include "gg_v5.h"
@@ -50,11 +51,6 @@ void launch_rollout5_policy(int N, uint8_t *st, uint64_t *rng, int32_t *last_act
                             int plies, int auto_reset, int nb, int grid, hipStream_t s);
 void launch_rollout_lat_policy(uint8_t *st, uint64_t *rng, int32_t *last_actions, int64_t *steps_done, int64_t B, int32_t N, int plies,
                                int auto_reset, hipStream_t s);
-// gg_feat.hip: the feature-plane kernels (gg_feat.h)
-void launch_features(bool tracked, const void *in, void *out, int dtype, int64_t B, int32_t N, int cus, hipStream_t s);
-void launch_features_oriented(bool tracked, const void *in, const int32_t *orient, void *out, int dtype, int64_t B, int32_t N, int cus,
-                              hipStream_t s);
-void launch_group_liberties(const uint8_t *states, uint8_t *libs, int64_t B, int32_t N, int cus, hipStream_t s);
 }
 
 namespace {
@@ -80,7 +76,9 @@ int forced_cus() {
   return forced;
 }
 
-int cus_of(int dev) {
+}  // namespace
+
+int gg::cus_of(int dev) {
   if (const int f = forced_cus()) return f;
   if (dev < 0 || dev >= kMaxDevices) return 256;
   int c = g_cus[dev].load(std::memory_order_relaxed);
@@ -91,24 +89,7 @@ int cus_of(int dev) {
   return c;
 }
 
-// Kernels are launched on the device that OWNS the buffers (the stream handed over belongs to it too), whatever the
-// calling thread's current device is; the current device is restored on return.  One hipPointerGetAttributes per call.
-struct OnDeviceOf {
-  int prev = -1, dev = 0;
-  bool switched = false;
-  explicit OnDeviceOf(const void *p) {
-    (void)hipGetDevice(&prev);
-    dev = prev < 0 ? 0 : prev;
-    hipPointerAttribute_t at;
-    if (p && hipPointerGetAttributes(&at, p) == hipSuccess) dev = at.device;
-    else (void)hipGetLastError();   // a pointer HIP does not know: launch on the current device (and fail there)
-    if (dev != prev) switched = hipSetDevice(dev) == hipSuccess;
-  }
-  ~OnDeviceOf() {
-    if (switched) (void)hipSetDevice(prev);
-  }
-  int cus() const { return cus_of(dev); }
-};
+namespace {
 
 // persistent grid: enough single-wave workgroups to fill every SIMD several times over
 int grid_for(int cus, int64_t work, int per_cu = 32) {
@@ -1162,54 +1143,6 @@ int32_t gg_batch_eye_mask(const uint8_t *states, uint8_t *mask, int64_t B, int32
   if (!mask) return GG_E_NULLPTR;
   const int64_t blocks = (B * N * N + 255) / 256;
   k_eye_mask<<<(unsigned)(blocks < (int64_t)cus * 64 ? blocks : (int64_t)cus * 64), 256, 0, s>>>(states, mask, B, N);
-  return (int32_t)hipGetLastError();
-}
-
-// ---- network input planes with per-group liberty counts (gg_feat.h; the launches: gg_feat.hip)
-int32_t gg_feature_planes(void) { return 16; }   // kFeatPlanes of gg_feat.h
-
-int32_t gg_batch_group_liberties(const uint8_t *states, uint8_t *libs, int64_t B, int32_t N, void *hip_stream) {
-  GG_ENTER(states);
-  if (!libs) return GG_E_NULLPTR;
-  launch_group_liberties(states, libs, B, N, cus, s);
-  return (int32_t)hipGetLastError();
-}
-
-int32_t gg_batch_features(const uint8_t *states, void *out, int32_t out_dtype, int64_t B, int32_t N, void *hip_stream) {
-  if (out_dtype < GG_W_F32 || out_dtype > GG_FEAT_U8) return GG_E_BADSIZE;
-  GG_ENTER(states);
-  if (!out) return GG_E_NULLPTR;
-  if ((uintptr_t)out & 15u) return GG_E_BADARG;
-  launch_features(false, states, out, out_dtype, B, N, cus, s);
-  return (int32_t)hipGetLastError();
-}
-
-int32_t gg_batch_features_tracked(const uint32_t *tracked, void *out, int32_t out_dtype, int64_t B, int32_t N, void *hip_stream) {
-  if (out_dtype < GG_W_F32 || out_dtype > GG_FEAT_U8) return GG_E_BADSIZE;
-  GG_ENTER(tracked);
-  if (!out) return GG_E_NULLPTR;
-  if ((uintptr_t)out & 15u) return GG_E_BADARG;
-  launch_features(true, tracked, out, out_dtype, B, N, cus, s);
-  return (int32_t)hipGetLastError();
-}
-
-int32_t gg_batch_features_oriented(const uint8_t *states, const int32_t *orient, void *out, int32_t out_dtype, int64_t B, int32_t N,
-                                   void *hip_stream) {
-  if (out_dtype < GG_W_F32 || out_dtype > GG_FEAT_U8) return GG_E_BADSIZE;
-  GG_ENTER(states);
-  if (!out || !orient) return GG_E_NULLPTR;
-  if ((uintptr_t)out & 15u) return GG_E_BADARG;
-  launch_features_oriented(false, states, orient, out, out_dtype, B, N, cus, s);
-  return (int32_t)hipGetLastError();
-}
-
-int32_t gg_batch_features_tracked_oriented(const uint32_t *tracked, const int32_t *orient, void *out, int32_t out_dtype, int64_t B,
-                                           int32_t N, void *hip_stream) {
-  if (out_dtype < GG_W_F32 || out_dtype > GG_FEAT_U8) return GG_E_BADSIZE;
-  GG_ENTER(tracked);
-  if (!out || !orient) return GG_E_NULLPTR;
-  if ((uintptr_t)out & 15u) return GG_E_BADARG;
-  launch_features_oriented(true, tracked, orient, out, out_dtype, B, N, cus, s);
   return (int32_t)hipGetLastError();
 }
 

@@ -32,7 +32,7 @@
 // rows per level take, and it is LDS per wave that bounds the waves per compute unit here.
 // Every loop is bounded by construction: a round tries an option (a node has at most 1 + the number of attacker chains
 // options and a query at most 16 N nodes), pops a level (at most 4 N) or takes a chain off the board's list.
-// EMISSION: k_life's - an LDS bit-string per wave, aligned 16-byte vectors inside the wave's slice, single elements at the
+// EMISSION: k_life's (plane_emit of gg_planes.h) - an LDS bit-string per wave, aligned 16-byte vectors inside the wave's slice, single elements at the
 // ragged ends, nothing outside the slice.
 #pragma once
 #include "gg_feat.h"
@@ -46,7 +46,7 @@ struct Ladder {
   using F_ = Feat<R>;
   static constexpr int LPB = F_::LPB, NBW = F_::NBW;
   static constexpr int kLevels = 4 * R;                                             // GG_LADDER_DEPTH(R): one record per ply
-  static constexpr int kBsWords = (15 + NBW * kLadderPlanes * R * R + 31) / 32 + 2;   // the bit-string (+ the spill word of the last OR)
+  static constexpr int kBsWords = plane_bs_words<R>(kLadderPlanes, 15);
   static constexpr int kIoWords = kBsWords > F_::kIoWords ? kBsWords : F_::kIoWords;  // (the staged input is dead by then)
   static constexpr int kLdsWords = kIoWords + kLevels * kWave;
   // THE ROUNDS OF A BOARD.  In every round a board that has work takes a chain off its list, tries one option or finds its
@@ -94,24 +94,17 @@ __global__ __launch_bounds__(kWave) void k_ladder(const void *__restrict__ in, c
                                                   uint8_t *__restrict__ out, uint8_t *__restrict__ aborted, int esh, uint32_t one,
                                                   int64_t B, int N) {
   using L_ = Ladder<R>;
-  constexpr int LPB = L_::LPB, NBW = L_::NBW;
+  constexpr int LPB = L_::LPB;
   __shared__ __attribute__((aligned(16))) uint32_t lds[L_::kLdsWords];
   uint32_t *stack = lds + L_::kIoWords;
-  const int lane = threadIdx.x & (kWave - 1);
-  const int r = lane & (LPB - 1), j = lane / LPB;
-  const int P = N * N;
-  const uint32_t full = r < N ? (1u << N) - 1u : 0u;
-  const int epv = 16 >> esh;   // elements per 16-byte vector: 16, 8, 4
+  PlaneFrame<R> f(N);
+  const int lane = f.lane;
+  const uint32_t full = f.full;
   const int max_depth = GG_LADDER_DEPTH(N), max_nodes = GG_LADDER_NODES(N);
-  const int64_t ngroups = (B + NBW - 1) / NBW;
-  for (int64_t g = blockIdx.x; g < ngroups; g += gridDim.x) {
-    const int64_t b_first = g * NBW;
-    const int nb = (int)(B - b_first < NBW ? B - b_first : NBW);
-    const bool on = j < nb;
+  for (int64_t g = blockIdx.x; g < f.groups(B); g += gridDim.x) {
+    f.at(g, B);
     uint32_t bl0, wh0, inv, fl;
-    if (TRACKED) feat_load_tracked(static_cast<const uint32_t *>(in), on ? b_first + j : B - 1, N, r, on, full, bl0, wh0, inv, fl);
-    else feat_load_bytes<R>(static_cast<const uint8_t *>(in), b_first, nb, N, r, j, on, full, lds, lane, bl0, wh0, inv, fl);
-    if (orient) feat_orient<R>(bl0, wh0, inv, on ? (orient[b_first + j] & 7) : 0, N, r, lane, full);
+    plane_load<R, TRACKED>(in, orient, f, B, N, lds, bl0, wh0, inv, fl);
     const bool white = (fl & 1u) != 0, over = (fl & 4u) != 0;
     uint32_t remq, ko0;
     {
@@ -289,56 +282,11 @@ __global__ __launch_bounds__(kWave) void k_ladder(const void *__restrict__ in, c
 #undef GG_LAD_FILE
     }
     if (st != 2) nab = 255u;   // out of rounds (Ladder<R>::kRounds: not reached): say so
-    if (aborted && on && r == 0) aborted[b_first + j] = (uint8_t)nab;
+    if (aborted && f.on && f.r == 0) aborted[f.b_first + f.j] = (uint8_t)nab;
     const uint32_t own0 = white ? wh0 : bl0, opp0 = white ? bl0 : wh0;
     const uint32_t rows[kLadderPlanes] = {lad & own0, lad & opp0, over ? 0u : p2, over ? 0u : p3};
-    // the wave's bit-string: bit mo + e = element e of the wave's slice of `out`
-    uint8_t *dst = out + ((b_first * (int64_t)(kLadderPlanes * P)) << esh);
-    const uint32_t mis = (uint32_t)((uintptr_t)dst & 15u);
-    const int mo = (int)(mis >> esh);
-    const int nel = nb * kLadderPlanes * P, end = mo + nel;
-    WAVE_SYNC();
-    for (int w = lane; w < ((end + 31) >> 5) + 1; w += kWave) lds[w] = 0;
-    WAVE_SYNC();
-    if (on && r < N) {
-      const uint32_t q0 = (uint32_t)(mo + j * kLadderPlanes * P + r * N);
-#pragma unroll
-      for (int p = 0; p < kLadderPlanes; ++p) {
-        if (rows[p]) {
-          const uint32_t q = q0 + (uint32_t)(p * P);
-          const uint64_t x = (uint64_t)rows[p] << (q & 31u);
-          atomicOr(lds + (q >> 5), (uint32_t)x);
-          if ((uint32_t)(x >> 32)) atomicOr(lds + (q >> 5) + 1, (uint32_t)(x >> 32));
-        }
-      }
-    }
-    WAVE_SYNC();
-    uint8_t *ga = dst - mis;
-    const int v0 = mo ? 1 : 0, v1 = end >> (4 - esh);
-    for (int v = v0 + lane; v < v1; v += kWave) {
-      const uint32_t q = (uint32_t)(v << (4 - esh));
-      const uint32_t x = lds[q >> 5] >> (q & 31u);
-      *reinterpret_cast<V16a *>(ga + 16 * (int64_t)v) = esh == 0 ? feat_expand<1>(x, one) : esh == 1 ? feat_expand<2>(x, one)
-                                                                                                       : feat_expand<4>(x, one);
-    }
-    // the ragged ends as single elements: lanes 0 - 15 the head, 16 - 31 the tail; a slice inside one vector: all of it
-    int e0 = -1, estep = nel;
-    if (v1 >= v0) {
-      const int head = mo ? epv - mo : 0, tail = end & (epv - 1);
-      if (lane < 16) { if (lane < head) e0 = lane; }
-      else if (lane < 32 && lane - 16 < tail) e0 = nel - tail + (lane - 16);
-    } else {
-      e0 = lane;
-      estep = kWave;
-    }
-    for (int e = e0; e >= 0 && e < nel; e += estep) {
-      const uint32_t q = (uint32_t)(mo + e);
-      const uint32_t v = ((lds[q >> 5] >> (q & 31u)) & 1u) ? one : 0u;
-      if (esh == 0) dst[e] = (uint8_t)v;
-      else if (esh == 1) reinterpret_cast<uint16_t *>(dst)[e] = (uint16_t)v;
-      else reinterpret_cast<uint32_t *>(dst)[e] = v;
-    }
-    WAVE_SYNC();
+    WAVE_SYNC();   // (the stack's last reads before the string is zeroed)
+    plane_emit<R, kLadderPlanes>(out, esh, one, rows, lds, f, N);
   }
 }
 

@@ -23,7 +23,7 @@
 // Every loop is bounded by construction: a region round takes a point off some board's unvisited set, a candidate round a
 // stone off some board's (at most four) candidates, a pass that is not the last a chain off some board's alive set.
 //
-// EMISSION: 4 N^2 elements per board - not a multiple of 16 bytes for odd N in uint8, so `out` needs element alignment only.
+// EMISSION (plane_emit of gg_planes.h): 4 N^2 elements per board - not a multiple of 16 bytes for odd N in uint8, so `out` needs element alignment only.
 // The boards of a wave are contiguous in `out`: the lanes OR their four row masks into one bit-string per wave in LDS whose
 // bit (mo + e) is element e of the wave's slice, mo = the slice's misalignment in elements; every aligned 16-byte vector
 // inside the slice is then a run of 16 / element size bits that never crosses a word (k_features' walk), and the two ragged
@@ -39,35 +39,10 @@ template <int R>
 struct Life {
   using F_ = Feat<R>;
   static constexpr int LPB = F_::LPB, NBW = F_::NBW, FW = F_::FW, K = F_::K;
-  static constexpr uint32_t FM = Lat<R>::FM;
-  static constexpr int kBsWords = (15 + NBW * kLifePlanes * R * R + 31) / 32 + 2;   // the bit-string (+ the spill word of the last OR)
+  static constexpr uint32_t FM = Planes<R>::FM;
+  static constexpr int kBsWords = plane_bs_words<R>(kLifePlanes, 15);
   static constexpr int kLdsWords = kBsWords > F_::kIoWords ? kBsWords : F_::kIoWords;   // (the staged input is dead by then)
 };
-
-// colour k's row of a pair
-template <int R>
-__device__ __forceinline__ uint32_t life_field(const uint32_t (&X)[Life<R>::K], int k) {
-  constexpr int K = Life<R>::K;
-  if (K == 1) return (k ? X[0] >> (Life<R>::FW & 31) : X[0]) & Life<R>::FM;
-  return X[k ? K - 1 : 0];
-}
-// the pair (b, w)
-template <int R>
-__device__ __forceinline__ void life_pair(uint32_t b, uint32_t w, uint32_t (&X)[Life<R>::K]) {
-  constexpr int K = Life<R>::K;
-  if (K == 1) X[0] = b | (w << (Life<R>::FW & 31));
-  else { X[0] = b; X[K - 1] = w; }
-}
-// per colour, the lowest point of the first lane of the board that holds one (feat_groups' seeds): X -> F
-template <int R>
-__device__ __forceinline__ void life_seeds(const uint32_t (&X)[Life<R>::K], uint32_t (&F)[Life<R>::K]) {
-  const uint32_t xb = life_field<R>(X, 0), xw = life_field<R>(X, 1);
-  const uint32_t has = (xb ? 1u : 0u) | (xw ? 0x10000u : 0u);
-  const uint32_t incl = lat_board_scan<Life<R>::LPB>(has);
-  const uint32_t sb = (xb != 0u && (incl & 0xFFFFu) == 1u) ? (xb & (0u - xb)) : 0u;
-  const uint32_t sw = (xw != 0u && (incl >> 16) == 1u) ? (xw & (0u - xw)) : 0u;
-  life_pair<R>(sb, sw, F);
-}
 
 // bl / wh: this lane's row of black / white stones (zero in rows >= N and on boards that are not there) -> the rows of
 // alive(black), alive(white), safe(black), safe(white)
@@ -79,9 +54,9 @@ __device__ __forceinline__ void life_benson(uint32_t bl, uint32_t wh, uint32_t f
   constexpr uint32_t FM = L_::FM;
   const uint32_t E = full & ~(bl | wh);
   uint32_t S[K], Sr[K], C[K], Cr[K], Ee[K], A[K], safe[K];
-  life_pair<R>(bl, wh, S);
-  life_pair<R>(full & ~bl, full & ~wh, C);
-  life_pair<R>(E, E, Ee);
+  plane_pair<R>(bl, wh, S);
+  plane_pair<R>(full & ~bl, full & ~wh, C);
+  plane_pair<R>(E, E, Ee);
 #pragma unroll
   for (int k = 0; k < K; ++k) { Sr[k] = __brev(S[k]); Cr[k] = __brev(C[k]); A[k] = S[k]; safe[k] = 0; }
 #pragma unroll 1
@@ -96,7 +71,7 @@ __device__ __forceinline__ void life_benson(uint32_t bl, uint32_t wh, uint32_t f
       for (int k = 0; k < K; ++k) any |= rem[k];
       if (__ballot(any != 0u) == 0ull) break;
       uint32_t F[K];
-      life_seeds<R>(rem, F);
+      plane_seeds<R>(rem, F);
       lat_flood<LPB, K>(F, C, Cr);                 // the next region of either colour
       uint32_t bord[K], RE[K], nt[K];
 #pragma unroll
@@ -110,7 +85,7 @@ __device__ __forceinline__ void life_benson(uint32_t bl, uint32_t wh, uint32_t f
       uint32_t w = 0;
 #pragma unroll
       for (int c = 0; c < 2; ++c)
-        w |= ((life_field<R>(bord, c) ? 1u : 0u) | (life_field<R>(RE, c) ? 32u : 0u) | (life_field<R>(nt, c) ? 1024u : 0u)) << (15 * c);
+        w |= ((plane_field<R>(bord, c) ? 1u : 0u) | (plane_field<R>(RE, c) ? 32u : 0u) | (plane_field<R>(nt, c) ? 1024u : 0u)) << (15 * c);
       const uint32_t sum = lat_board_sum<LPB>(w);
       bool ok[2];
 #pragma unroll
@@ -121,10 +96,10 @@ __device__ __forceinline__ void life_benson(uint32_t bl, uint32_t wh, uint32_t f
       if (__ballot(ok[0] || ok[1]) == 0ull) continue;
       // 3. the chains next to the region's lowest empty point (all of them alive, by 1.)
       uint32_t okm[K], REk[K], P0[K], cand[K];
-      life_pair<R>(ok[0] ? FM : 0u, ok[1] ? FM : 0u, okm);
+      plane_pair<R>(ok[0] ? FM : 0u, ok[1] ? FM : 0u, okm);
 #pragma unroll
       for (int k = 0; k < K; ++k) REk[k] = RE[k] & okm[k];
-      life_seeds<R>(REk, P0);
+      plane_seeds<R>(REk, P0);
 #pragma unroll
       for (int k = 0; k < K; ++k) cand[k] = lat_dilate<LPB>(P0[k]) & S[k];
 #pragma unroll 1
@@ -134,7 +109,7 @@ __device__ __forceinline__ void life_benson(uint32_t bl, uint32_t wh, uint32_t f
         for (int k = 0; k < K; ++k) anyc |= cand[k];
         if (__ballot(anyc != 0u) == 0ull) break;
         uint32_t G[K];
-        life_seeds<R>(cand, G);
+        plane_seeds<R>(cand, G);
         lat_flood<LPB, K>(G, S, Sr);
         uint32_t miss[K];
 #pragma unroll
@@ -144,10 +119,10 @@ __device__ __forceinline__ void life_benson(uint32_t bl, uint32_t wh, uint32_t f
         }
         uint32_t w2 = 0;
 #pragma unroll
-        for (int c = 0; c < 2; ++c) w2 |= ((life_field<R>(G, c) ? 1u : 0u) | (life_field<R>(miss, c) ? 256u : 0u)) << (16 * c);
+        for (int c = 0; c < 2; ++c) w2 |= ((plane_field<R>(G, c) ? 1u : 0u) | (plane_field<R>(miss, c) ? 256u : 0u)) << (16 * c);
         const uint32_t s2 = lat_board_sum<LPB>(w2);
         uint32_t vm[K];   // the region is vital to the chain
-        life_pair<R>((s2 & 0xFFu) != 0u && (s2 & 0xFF00u) == 0u ? FM : 0u,
+        plane_pair<R>((s2 & 0xFFu) != 0u && (s2 & 0xFF00u) == 0u ? FM : 0u,
                      ((s2 >> 16) & 0xFFu) != 0u && (s2 >> 24) == 0u ? FM : 0u, vm);
 #pragma unroll
         for (int k = 0; k < K; ++k) {
@@ -164,8 +139,8 @@ __device__ __forceinline__ void life_benson(uint32_t bl, uint32_t wh, uint32_t f
     for (int k = 0; k < K; ++k) { diff |= A[k] ^ twice[k]; A[k] = twice[k]; }
     if (__ballot(diff != 0u) == 0ull) break;
   }
-  ab = life_field<R>(A, 0); aw = life_field<R>(A, 1);
-  sb = life_field<R>(safe, 0); sw = life_field<R>(safe, 1);
+  ab = plane_field<R>(A, 0); aw = plane_field<R>(A, 1);
+  sb = plane_field<R>(safe, 0); sw = plane_field<R>(safe, 1);
 }
 
 // gg_batch_life / gg_batch_life_tracked: out [B][4][N][N] of elements of 1 << esh bytes (`one`: the bit pattern of 1), aligned to
@@ -175,77 +150,22 @@ template <int R, bool TRACKED>
 __global__ __launch_bounds__(kWave) void k_life(const void *__restrict__ in, const int32_t *__restrict__ orient,
                                                 uint8_t *__restrict__ out, uint8_t *__restrict__ settled, int esh, uint32_t one,
                                                 int64_t B, int N) {
-  using L_ = Life<R>;
-  constexpr int LPB = L_::LPB, NBW = L_::NBW;
-  __shared__ __attribute__((aligned(16))) uint32_t lds[L_::kLdsWords];
-  const int lane = threadIdx.x & (kWave - 1);
-  const int r = lane & (LPB - 1), j = lane / LPB;
-  const int P = N * N;
-  const uint32_t full = r < N ? (1u << N) - 1u : 0u;
-  const int epv = 16 >> esh;   // elements per 16-byte vector: 16, 8, 4
-  const int64_t ngroups = (B + NBW - 1) / NBW;
-  for (int64_t g = blockIdx.x; g < ngroups; g += gridDim.x) {
-    const int64_t b_first = g * NBW;
-    const int nb = (int)(B - b_first < NBW ? B - b_first : NBW);
-    const bool on = j < nb;
+  constexpr int LPB = Life<R>::LPB;
+  __shared__ __attribute__((aligned(16))) uint32_t lds[Life<R>::kLdsWords];
+  PlaneFrame<R> f(N);
+  for (int64_t g = blockIdx.x; g < f.groups(B); g += gridDim.x) {
+    f.at(g, B);
     uint32_t bl, wh, inv, fl;
-    if (TRACKED) feat_load_tracked(static_cast<const uint32_t *>(in), on ? b_first + j : B - 1, N, r, on, full, bl, wh, inv, fl);
-    else feat_load_bytes<R>(static_cast<const uint8_t *>(in), b_first, nb, N, r, j, on, full, lds, lane, bl, wh, inv, fl);
-    if (orient) feat_orient<R>(bl, wh, inv, on ? (orient[b_first + j] & 7) : 0, N, r, lane, full);
+    plane_load<R, TRACKED>(in, orient, f, B, N, lds, bl, wh, inv, fl);
     uint32_t ab, aw, sb, sw;
-    life_benson<R>(bl, wh, full, ab, aw, sb, sw);
+    life_benson<R>(bl, wh, f.full, ab, aw, sb, sw);
     if (settled) {   // every point of the board lies in some plane
-      const uint32_t open = lat_board_sum<LPB>((ab | aw | sb | sw) != full ? 1u : 0u);
-      if (on && r == 0) settled[b_first + j] = open == 0u ? 1 : 0;
+      const uint32_t open = lat_board_sum<LPB>((ab | aw | sb | sw) != f.full ? 1u : 0u);
+      if (f.on && f.r == 0) settled[f.b_first + f.j] = open == 0u ? 1 : 0;
     }
     const bool white = (fl & 1u) != 0;
     const uint32_t rows[kLifePlanes] = {white ? aw : ab, white ? ab : aw, white ? sw : sb, white ? sb : sw};
-    // the wave's bit-string: bit mo + e = element e of the wave's slice of `out`
-    uint8_t *dst = out + ((b_first * (int64_t)(kLifePlanes * P)) << esh);
-    const uint32_t mis = (uint32_t)((uintptr_t)dst & 15u);
-    const int mo = (int)(mis >> esh);
-    const int nel = nb * kLifePlanes * P, end = mo + nel;
-    for (int w = lane; w < ((end + 31) >> 5) + 1; w += kWave) lds[w] = 0;
-    WAVE_SYNC();
-    if (on && r < N) {
-      const uint32_t q0 = (uint32_t)(mo + j * kLifePlanes * P + r * N);
-#pragma unroll
-      for (int p = 0; p < kLifePlanes; ++p) {
-        if (rows[p]) {
-          const uint32_t q = q0 + (uint32_t)(p * P);
-          const uint64_t x = (uint64_t)rows[p] << (q & 31u);
-          atomicOr(lds + (q >> 5), (uint32_t)x);
-          if ((uint32_t)(x >> 32)) atomicOr(lds + (q >> 5) + 1, (uint32_t)(x >> 32));
-        }
-      }
-    }
-    WAVE_SYNC();
-    uint8_t *ga = dst - mis;
-    const int v0 = mo ? 1 : 0, v1 = end >> (4 - esh);
-    for (int v = v0 + lane; v < v1; v += kWave) {
-      const uint32_t q = (uint32_t)(v << (4 - esh));
-      const uint32_t x = lds[q >> 5] >> (q & 31u);
-      *reinterpret_cast<V16a *>(ga + 16 * (int64_t)v) = esh == 0 ? feat_expand<1>(x, one) : esh == 1 ? feat_expand<2>(x, one)
-                                                                                                       : feat_expand<4>(x, one);
-    }
-    // the ragged ends as single elements: lanes 0 - 15 the head, 16 - 31 the tail; a slice inside one vector: all of it
-    int e0 = -1, estep = nel;
-    if (v1 >= v0) {
-      const int head = mo ? epv - mo : 0, tail = end & (epv - 1);
-      if (lane < 16) { if (lane < head) e0 = lane; }
-      else if (lane < 32 && lane - 16 < tail) e0 = nel - tail + (lane - 16);
-    } else {
-      e0 = lane;
-      estep = kWave;
-    }
-    for (int e = e0; e >= 0 && e < nel; e += estep) {
-      const uint32_t q = (uint32_t)(mo + e);
-      const uint32_t v = ((lds[q >> 5] >> (q & 31u)) & 1u) ? one : 0u;
-      if (esh == 0) dst[e] = (uint8_t)v;
-      else if (esh == 1) reinterpret_cast<uint16_t *>(dst)[e] = (uint16_t)v;
-      else reinterpret_cast<uint32_t *>(dst)[e] = v;
-    }
-    WAVE_SYNC();
+    plane_emit<R, kLifePlanes>(out, esh, one, rows, lds, f, N);
   }
 }
 

@@ -1,64 +1,33 @@
-// gg_life.hip - the pass-alive life planes (gg_life.h: gg_life_planes, gg_batch_life, gg_batch_life_tracked) as a translation
-// unit of their own, entry points included, compiled with the default code-generation switches: the machine code of every
-// kernel of the other five units - and the hashes bench.py ties their PMC records to - does not depend on anything in here.
+// gg_life.hip - the pass-alive life planes (gg_life.h) with their entry points (gg_life_planes, gg_batch_life,
+// gg_batch_life_tracked) as a translation unit of their own, compiled with the default code-generation switches: the machine
+// code of every kernel of the other units - and the hashes bench.py ties their PMC records to - does not depend on anything
+// in here.  The launch path is plane_launch of gg_planes.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "gymgo_amd.h"
-#include "gg_common.h"
-#include "gg_v2.h"
-#include "gg_lat.h"
-#include "gg_feat.h"
 #include "gg_life.h"
 
 namespace {
 
 using namespace gg;
 
-// the launch goes to the device that owns the buffers, whatever the calling thread's current device is (restored on return)
-struct OnOwner {
-  int prev = -1, dev = 0;
-  bool switched = false;
-  explicit OnOwner(const void *p) {
-    (void)hipGetDevice(&prev);
-    dev = prev < 0 ? 0 : prev;
-    hipPointerAttribute_t at;
-    if (p && hipPointerGetAttributes(&at, p) == hipSuccess) dev = at.device;
-    else (void)hipGetLastError();   // a pointer HIP does not know: launch on the current device (and fail there)
-    if (dev != prev) switched = hipSetDevice(dev) == hipSuccess;
-  }
-  ~OnOwner() {
-    if (switched) (void)hipSetDevice(prev);
+struct LifeCall {
+  const void *in;
+  const int32_t *orient;
+  uint8_t *out, *settled;
+  int64_t B;
+  int32_t N;
+  template <int R, bool TRACKED>
+  void launch(unsigned grid, hipStream_t s, int esh, uint32_t one) const {
+    k_life<R, TRACKED><<<grid, kWave, 0, s>>>(in, orient, out, settled, esh, one, B, N);
   }
 };
 
-template <int R>
-void launch_life_r(bool tracked, const void *in, const int32_t *orient, uint8_t *out, uint8_t *settled, int esh, uint32_t one,
-                   int64_t B, int32_t N, int cus, hipStream_t s) {
-  // one single-wave workgroup per four (N <= 13) / two boards, at most 64 per compute unit (the rest: grid-stride)
-  const int64_t groups = (B + Life<R>::NBW - 1) / Life<R>::NBW, cap = (int64_t)cus * 64;
-  const unsigned grid = (unsigned)(groups < cap ? groups : cap);
-  if (tracked) k_life<R, true><<<grid, kWave, 0, s>>>(in, orient, out, settled, esh, one, B, N);
-  else k_life<R, false><<<grid, kWave, 0, s>>>(in, orient, out, settled, esh, one, B, N);
-}
-
 int32_t batch_life(bool tracked, const void *in, const int32_t *orient, void *out, uint8_t *settled, int32_t dtype, int64_t B,
                    int32_t N, void *hip_stream) {
-  if (N < 2 || N > GG_MAX_BOARD || B < 0 || dtype < GG_W_F32 || dtype > GG_FEAT_U8) return GG_E_BADSIZE;
-  if (B == 0) return 0;
-  if (!in || !out) return GG_E_NULLPTR;
-  const int esh = dtype == GG_FEAT_U8 ? 0 : (dtype == GG_W_F32 ? 2 : 1);   // log2 of the element size
-  if ((uintptr_t)out & (uintptr_t)((1 << esh) - 1)) return GG_E_BADARG;
-  const uint32_t one = dtype == GG_FEAT_U8 ? 1u : dtype == GG_W_F16 ? 0x3C00u : dtype == GG_W_BF16 ? 0x3F80u : 0x3F800000u;
-  OnOwner on_dev(in);
-  int cus = gg_device_cus();   // (of the device made current above; GYMGO_AMD_CUS honoured)
-  if (cus <= 0) cus = 256;
-  hipStream_t s = (hipStream_t)hip_stream;
-  uint8_t *o = static_cast<uint8_t *>(out);
-  if (N <= 9) launch_life_r<9>(tracked, in, orient, o, settled, esh, one, B, N, cus, s);
-  else if (N <= 13) launch_life_r<13>(tracked, in, orient, o, settled, esh, one, B, N, cus, s);
-  else launch_life_r<19>(tracked, in, orient, o, settled, esh, one, B, N, cus, s);
-  return (int32_t)hipGetLastError();
+  return plane_launch(LifeCall{in, orient, static_cast<uint8_t *>(out), settled, B, N}, tracked, in, out, out, 0, dtype, B, N,
+                      hip_stream);
 }
 
 }  // namespace

@@ -819,14 +819,16 @@ def _feature_dtype(dtype):
     return FEATURE_DTYPES[dtype]
 
 
-def _feature_out(out, shape, dtype, device=None):
-    """out=None, or a contiguous 16-byte aligned device tensor of exactly this shape and dtype (on `device` when given)."""
+def _planes_out(out, shape, dtype, align, device=None):
+    """out=None, or a contiguous device tensor of exactly this shape and dtype whose address is a multiple of `align` bytes
+    (on `device` when given)."""
     if out is None:
         return
     if (not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != dtype or tuple(out.shape) != tuple(shape)
-            or not out.is_contiguous() or out.data_ptr() % 16 or (device is not None and out.device != device)):
-        raise ValueError('out must be a contiguous, 16-byte aligned %s %s tensor on the states\' device (got %s)' % (
-            dtype, list(shape), '%s %s on %s' % (out.dtype, list(out.shape), out.device) if isinstance(out, torch.Tensor) else type(out)))
+            or not out.is_contiguous() or out.data_ptr() % align or (device is not None and out.device != device)):
+        raise ValueError('out must be a contiguous%s %s %s tensor on the states\' device (got %s)' % (
+            ', %d-byte aligned' % align if align > 1 else '', dtype, list(shape),
+            '%s %s on %s' % (out.dtype, list(out.shape), out.device) if isinstance(out, torch.Tensor) else type(out)))
 
 
 def _states_shape(x, what='batch_states'):
@@ -869,6 +871,65 @@ def _orient_arg(orient, B):
         raise ValueError('orient must be %d integers in 0..7, one per row (got %d of %s)' % (B, n, orient.dtype))
 
 
+def _plane_launch(name, boards_ptr, orient_ptr, out_ptr, extra_ptr, code, B, N, stream):
+    """One launch of a plane entry point on raw pointers.  name: gg_batch_features[_tracked] - its _oriented form when
+    orient_ptr is given, and no per-board bytes (extra_ptr is False) - or gg_batch_life[_tracked] / gg_batch_ladder[_tracked],
+    which take orient (or None) and the per-board bytes (or None) themselves."""
+    if extra_ptr is not False:
+        args = (boards_ptr, orient_ptr, out_ptr, extra_ptr)
+    elif orient_ptr is None:
+        args = (boards_ptr, out_ptr)
+    else:
+        name, args = name + '_oriented', (boards_ptr, orient_ptr, out_ptr)
+    _lib.check(getattr(_lib.lib(), name)(*args, code, B, N, stream), name)
+
+
+def _planes(name, count, align, boards, tracked, dtype, out, orient, extra=None):
+    """The body of the six batch plane calls: `count` planes per board from byte planes (a tensor or an array) or, `tracked`,
+    from tracked boards (a device tensor), through the C entry point `name` (_plane_launch), into `out` (aligned to
+    `align` bytes) or a new tensor.  extra: None (the entry point has no per-board bytes), or whether they are wanted
+    -> planes, or (planes, bytes uint8 [B]).  Every ValueError comes before a device is touched."""
+    code = _feature_dtype(dtype)
+    if tracked:
+        if not isinstance(boards, torch.Tensor) or boards.dim() != 2:
+            raise ValueError('tracked boards are int32 [B, 5N+1] device tensors')
+        N = _tracked_size(boards)
+        B = boards.shape[0]
+    else:
+        B, N = _states_shape(boards)
+        _planes_out(out, (B, count, N, N), dtype, align)
+    if orient is not None:
+        _orient_arg(orient, B)
+    if tracked:
+        box, st = None, boards
+        _planes_out(out, (B, count, N, N), dtype, align, st.device if st.is_cuda else None)
+    else:
+        if not isinstance(boards, torch.Tensor) and dtype == torch.bfloat16:
+            raise ValueError('NumPy has no bfloat16: pass a device tensor, or another dtype')
+        box = _Box(boards)
+        st = box.t
+        _planes_out(out, (B, count, N, N), dtype, align, st.device)
+    planes = out if out is not None else torch.empty((B, count, N, N), dtype=dtype, device=st.device)
+    bytes_ = torch.empty(B, dtype=_U8, device=st.device) if extra else None
+    o = None if orient is None else _actions_tensor(orient, B, st.device)
+    _plane_launch(name, _lib.dev_ptr(st, _I32 if tracked else _U8, 'tracked' if tracked else 'states'), _lib.dev_ptr(o, _I32, 'orient'),
+                  _lib.dev_ptr(planes, dtype, 'out'), False if extra is None else _lib.dev_ptr(bytes_, _U8, 'bytes'), code, B, N,
+                  _lib.stream_ptr(st.device))
+    if box is not None:
+        planes, bytes_ = _back(box, planes), _back(box, bytes_)
+    return (planes, bytes_) if extra else planes
+
+
+def _plane_single(batch_fn, state, dtype, **kw):
+    """The single-state form of a batch plane call: state [6, N, N] as a batch of one, row 0 of every result."""
+    _feature_dtype(dtype)
+    if not isinstance(state, torch.Tensor) and dtype == torch.bfloat16:
+        raise ValueError('NumPy has no bfloat16: pass a device tensor, or another dtype')
+    box = _Box(state)
+    res = batch_fn(box.t[None], dtype, **kw)
+    return tuple(_back(box, t, row0=True) for t in res) if isinstance(res, tuple) else _back(box, res, row0=True)
+
+
 def batch_features(batch_states, dtype=torch.float16, out=None, orient=None):
     """Network input planes of every board -> [B, 16, N, N] of `dtype` (gg_batch_features), from the mover's point of view
     ("own" = the player to move).  Plane by plane (FEATURE_NAMES), each value exactly 0 or 1:
@@ -888,35 +949,12 @@ def batch_features(batch_states, dtype=torch.float16, out=None, orient=None):
     view orient[b] of its planes, all sixteen turned alike (gg_batch_features_oriented; bit 0 flips the columns, then bit 1
     the rows, then bit 2 rotates: batch_symmetry's orientations).  That is also batch_features of the turned position,
     batch_symmetry(batch_states, orient).  Still one launch."""
-    code = _feature_dtype(dtype)
-    B, N = _states_shape(batch_states)
-    _feature_out(out, (B, FEATURE_PLANES, N, N), dtype)
-    if orient is not None:
-        _orient_arg(orient, B)
-    if not isinstance(batch_states, torch.Tensor) and dtype == torch.bfloat16:
-        raise ValueError('NumPy has no bfloat16: pass a device tensor, or another dtype')
-    box = _Box(batch_states)
-    st = box.t
-    _feature_out(out, (B, FEATURE_PLANES, N, N), dtype, st.device)
-    planes = out if out is not None else torch.empty((B, FEATURE_PLANES, N, N), dtype=dtype, device=st.device)
-    if orient is None:
-        _lib.check(_lib.lib().gg_batch_features(_lib.dev_ptr(st, _U8, 'states'), _lib.dev_ptr(planes, dtype, 'out'), code, B, N,
-                                                _lib.stream_ptr(st.device)), 'gg_batch_features')
-    else:
-        o = _actions_tensor(orient, B, st.device)
-        _lib.check(_lib.lib().gg_batch_features_oriented(_lib.dev_ptr(st, _U8, 'states'), _lib.dev_ptr(o, _I32, 'orient'),
-                                                         _lib.dev_ptr(planes, dtype, 'out'), code, B, N, _lib.stream_ptr(st.device)),
-                   'gg_batch_features_oriented')
-    return _back(box, planes)
+    return _planes('gg_batch_features', FEATURE_PLANES, 16, batch_states, False, dtype, out, orient)
 
 
 def features(state, dtype=torch.float16):
     """batch_features of one state [6, N, N] -> [16, N, N]."""
-    _feature_dtype(dtype)
-    if not isinstance(state, torch.Tensor) and dtype == torch.bfloat16:
-        raise ValueError('NumPy has no bfloat16: pass a device tensor, or another dtype')
-    box = _Box(state)
-    return _back(box, batch_features(box.t[None], dtype), row0=True)
+    return _plane_single(batch_features, state, dtype)
 
 
 def batch_features_tracked(tracked, dtype=torch.float16, out=None, orient=None):
@@ -925,50 +963,12 @@ def batch_features_tracked(tracked, dtype=torch.float16, out=None, orient=None):
     boards go to the network without the byte planes in between.  dtype, out, exactness and device memory: batch_features.
     orient: as batch_features (gg_batch_features_tracked_oriented) - what batch_symmetry_rows followed by this call gives,
     in one launch and without the second board buffer."""
-    code = _feature_dtype(dtype)
-    if not isinstance(tracked, torch.Tensor) or tracked.dim() != 2:
-        raise ValueError('tracked boards are int32 [B, 5N+1] device tensors')
-    N = _tracked_size(tracked)
-    B = tracked.shape[0]
-    if orient is not None:
-        _orient_arg(orient, B)
-    _feature_out(out, (B, FEATURE_PLANES, N, N), dtype, tracked.device if tracked.is_cuda else None)
-    planes = out if out is not None else torch.empty((B, FEATURE_PLANES, N, N), dtype=dtype, device=tracked.device)
-    if orient is None:
-        _lib.check(_lib.lib().gg_batch_features_tracked(_lib.dev_ptr(tracked, _I32, 'tracked'), _lib.dev_ptr(planes, dtype, 'out'), code,
-                                                        B, N, _lib.stream_ptr(tracked.device)), 'gg_batch_features_tracked')
-    else:
-        o = _actions_tensor(orient, B, tracked.device)
-        _lib.check(_lib.lib().gg_batch_features_tracked_oriented(_lib.dev_ptr(tracked, _I32, 'tracked'), _lib.dev_ptr(o, _I32, 'orient'),
-                                                                 _lib.dev_ptr(planes, dtype, 'out'), code, B, N,
-                                                                 _lib.stream_ptr(tracked.device)), 'gg_batch_features_tracked_oriented')
-    return planes
+    return _planes('gg_batch_features_tracked', FEATURE_PLANES, 16, tracked, True, dtype, out, orient)
 
 
 # ---------------------------------------------------------------- pass-alive (Benson) life planes
 LIFE_PLANES = 4   # gg_life_planes() of include/gymgo_amd.h
 LIFE_NAMES = ('own_alive', 'opp_alive', 'own_safe', 'opp_safe')
-
-
-def _life_out(out, shape, dtype, device=None):
-    """out=None, or a contiguous device tensor of exactly this shape and dtype (on `device` when given)."""
-    if out is None:
-        return
-    if (not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != dtype or tuple(out.shape) != tuple(shape)
-            or not out.is_contiguous() or (device is not None and out.device != device)):
-        raise ValueError('out must be a contiguous %s %s tensor on the states\' device (got %s)' % (
-            dtype, list(shape), '%s %s on %s' % (out.dtype, list(out.shape), out.device) if isinstance(out, torch.Tensor) else type(out)))
-
-
-def _life_launch(name, boards, boards_dtype, orient, planes, dtype, code, want_settled, B, N):
-    """One launch of gg_batch_life / gg_batch_life_tracked on the boards' device -> the settled bytes or None."""
-    dev = boards.device
-    flags = torch.empty(B, dtype=_U8, device=dev) if want_settled else None
-    o = None if orient is None else _actions_tensor(orient, B, dev)
-    _lib.check(getattr(_lib.lib(), name)(_lib.dev_ptr(boards, boards_dtype, 'boards'), _lib.dev_ptr(o, _I32, 'orient'),
-                                         _lib.dev_ptr(planes, dtype, 'out'), _lib.dev_ptr(flags, _U8, 'settled'), code, B, N,
-                                         _lib.stream_ptr(dev)), name)
-    return flags
 
 
 def batch_life(batch_states, dtype=torch.uint8, out=None, orient=None, settled=False):
@@ -987,45 +987,18 @@ def batch_life(batch_states, dtype=torch.uint8, out=None, orient=None, settled=F
     turned position.  settled=True: -> (planes, uint8 [B]): 1 iff every point of the board lies in some plane (nothing is
     left to play for; it does not depend on orient).  NumPy in gives NumPy out (through the device; not for bfloat16).
     One launch either way; device memory of the result: 4 * B * N^2 elements (+ B bytes)."""
-    code = _feature_dtype(dtype)
-    B, N = _states_shape(batch_states)
-    _life_out(out, (B, LIFE_PLANES, N, N), dtype)
-    if orient is not None:
-        _orient_arg(orient, B)
-    if not isinstance(batch_states, torch.Tensor) and dtype == torch.bfloat16:
-        raise ValueError('NumPy has no bfloat16: pass a device tensor, or another dtype')
-    box = _Box(batch_states)
-    st = box.t
-    _life_out(out, (B, LIFE_PLANES, N, N), dtype, st.device)
-    planes = out if out is not None else torch.empty((B, LIFE_PLANES, N, N), dtype=dtype, device=st.device)
-    flags = _life_launch('gg_batch_life', st, _U8, orient, planes, dtype, code, settled, B, N)
-    return (_back(box, planes), _back(box, flags)) if settled else _back(box, planes)
+    return _planes('gg_batch_life', LIFE_PLANES, 1, batch_states, False, dtype, out, orient, bool(settled))
 
 
 def life(state, dtype=torch.uint8, settled=False):
     """batch_life of one state [6, N, N] -> [4, N, N] (with settled=True: and a uint8 scalar)."""
-    _feature_dtype(dtype)
-    if not isinstance(state, torch.Tensor) and dtype == torch.bfloat16:
-        raise ValueError('NumPy has no bfloat16: pass a device tensor, or another dtype')
-    box = _Box(state)
-    res = batch_life(box.t[None], dtype, settled=settled)
-    return (_back(box, res[0], row0=True), _back(box, res[1], row0=True)) if settled else _back(box, res, row0=True)
+    return _plane_single(batch_life, state, dtype, settled=settled)
 
 
 def batch_life_tracked(tracked, dtype=torch.uint8, out=None, orient=None, settled=False):
     """batch_life of tracked boards (int32 [B, 5N+1], a device tensor) -> [B, 4, N, N] of `dtype` (gg_batch_life_tracked):
     bit for bit what batch_life gives for batch_untrack(tracked); only the two stone row sets and the turn flag are read."""
-    code = _feature_dtype(dtype)
-    if not isinstance(tracked, torch.Tensor) or tracked.dim() != 2:
-        raise ValueError('tracked boards are int32 [B, 5N+1] device tensors')
-    N = _tracked_size(tracked)
-    B = tracked.shape[0]
-    if orient is not None:
-        _orient_arg(orient, B)
-    _life_out(out, (B, LIFE_PLANES, N, N), dtype, tracked.device if tracked.is_cuda else None)
-    planes = out if out is not None else torch.empty((B, LIFE_PLANES, N, N), dtype=dtype, device=tracked.device)
-    flags = _life_launch('gg_batch_life_tracked', tracked, _I32, orient, planes, dtype, code, settled, B, N)
-    return (planes, flags) if settled else planes
+    return _planes('gg_batch_life_tracked', LIFE_PLANES, 1, tracked, True, dtype, out, orient, bool(settled))
 
 
 def batch_settled(batch_states):
@@ -1038,17 +1011,6 @@ def batch_settled(batch_states):
 # ---------------------------------------------------------------- ladder planes
 LADDER_PLANES = 4   # GG_LADDER_PLANES of include/gymgo_amd.h
 LADDER_NAMES = ('own_laddered', 'opp_laddered', 'ladder_capture', 'ladder_escape')
-
-
-def _ladder_launch(name, boards, boards_dtype, orient, planes, dtype, code, want_aborted, B, N):
-    """One launch of gg_batch_ladder / gg_batch_ladder_tracked on the boards' device -> the aborted bytes or None."""
-    dev = boards.device
-    counts = torch.empty(B, dtype=_U8, device=dev) if want_aborted else None
-    o = None if orient is None else _actions_tensor(orient, B, dev)
-    _lib.check(getattr(_lib.lib(), name)(_lib.dev_ptr(boards, boards_dtype, 'boards'), _lib.dev_ptr(o, _I32, 'orient'),
-                                         _lib.dev_ptr(planes, dtype, 'out'), _lib.dev_ptr(counts, _U8, 'aborted'), code, B, N,
-                                         _lib.stream_ptr(dev)), name)
-    return counts
 
 
 def batch_ladder(batch_states, dtype=torch.uint8, out=None, orient=None, aborted=False):
@@ -1067,45 +1029,18 @@ def batch_ladder(batch_states, dtype=torch.uint8, out=None, orient=None, aborted
     holds the planes of the turned position (turned first, then searched).  aborted=True: -> (planes, uint8 [B]): the
     aborted root queries of the board, saturated at 255.  NumPy in gives NumPy out (through the device; not for bfloat16).
     One launch either way; device memory of the result: 4 * B * N^2 elements (+ B bytes)."""
-    code = _feature_dtype(dtype)
-    B, N = _states_shape(batch_states)
-    _life_out(out, (B, LADDER_PLANES, N, N), dtype)
-    if orient is not None:
-        _orient_arg(orient, B)
-    if not isinstance(batch_states, torch.Tensor) and dtype == torch.bfloat16:
-        raise ValueError('NumPy has no bfloat16: pass a device tensor, or another dtype')
-    box = _Box(batch_states)
-    st = box.t
-    _life_out(out, (B, LADDER_PLANES, N, N), dtype, st.device)
-    planes = out if out is not None else torch.empty((B, LADDER_PLANES, N, N), dtype=dtype, device=st.device)
-    counts = _ladder_launch('gg_batch_ladder', st, _U8, orient, planes, dtype, code, aborted, B, N)
-    return (_back(box, planes), _back(box, counts)) if aborted else _back(box, planes)
+    return _planes('gg_batch_ladder', LADDER_PLANES, 1, batch_states, False, dtype, out, orient, bool(aborted))
 
 
 def ladder(state, dtype=torch.uint8, aborted=False):
     """batch_ladder of one state [6, N, N] -> [4, N, N] (with aborted=True: and a uint8 scalar)."""
-    _feature_dtype(dtype)
-    if not isinstance(state, torch.Tensor) and dtype == torch.bfloat16:
-        raise ValueError('NumPy has no bfloat16: pass a device tensor, or another dtype')
-    box = _Box(state)
-    res = batch_ladder(box.t[None], dtype, aborted=aborted)
-    return (_back(box, res[0], row0=True), _back(box, res[1], row0=True)) if aborted else _back(box, res, row0=True)
+    return _plane_single(batch_ladder, state, dtype, aborted=aborted)
 
 
 def batch_ladder_tracked(tracked, dtype=torch.uint8, out=None, orient=None, aborted=False):
     """batch_ladder of tracked boards (int32 [B, 5N+1], a device tensor) -> [B, 4, N, N] of `dtype` (gg_batch_ladder_tracked):
     bit for bit what batch_ladder gives for batch_untrack(tracked); the class rows are not read."""
-    code = _feature_dtype(dtype)
-    if not isinstance(tracked, torch.Tensor) or tracked.dim() != 2:
-        raise ValueError('tracked boards are int32 [B, 5N+1] device tensors')
-    N = _tracked_size(tracked)
-    B = tracked.shape[0]
-    if orient is not None:
-        _orient_arg(orient, B)
-    _life_out(out, (B, LADDER_PLANES, N, N), dtype, tracked.device if tracked.is_cuda else None)
-    planes = out if out is not None else torch.empty((B, LADDER_PLANES, N, N), dtype=dtype, device=tracked.device)
-    counts = _ladder_launch('gg_batch_ladder_tracked', tracked, _I32, orient, planes, dtype, code, aborted, B, N)
-    return (planes, counts) if aborted else planes
+    return _planes('gg_batch_ladder_tracked', LADDER_PLANES, 1, tracked, True, dtype, out, orient, bool(aborted))
 
 
 def batch_play_moves_tracked(tracked, moves, played=None):
@@ -1773,23 +1708,18 @@ class PuctSearch:
             _lib.check(lib.gg_batch_play_moves_tracked(lp, mp, None, B, N, 1, stream), 'gg_batch_play_moves_tracked')
             if self._feat is None:
                 _lib.check(lib.gg_batch_untrack_states(lp, sp, B, N, stream), 'gg_batch_untrack_states')
-            elif self._sym is None:   # (sp: the planes)
-                _lib.check(lib.gg_batch_features_tracked(lp, sp, self._feat[1], B, N, stream), 'gg_batch_features_tracked')
-            else:
-                op = self._draw_orient(B, stream)
-                _lib.check(lib.gg_batch_features_tracked_oriented(lp, op, sp, self._feat[1], B, N, stream),
-                           'gg_batch_features_tracked_oriented')
+            else:   # (sp: the planes)
+                op = None if self._sym is None else self._draw_orient(B, stream)
+                _plane_launch('gg_batch_features_tracked', lp, op, sp, False, self._feat[1], B, N, stream)
             _lib.check(lib.gg_puct_legal(lp, ip, B, N, gp, vp, stream), 'gg_puct_legal')
             if self._sym is not None:
                 self._turn_legal(op, B, stream)
             if self._life:
-                _lib.check(lib.gg_batch_life_tracked(lp, None if self._sym is None else op,
-                                                     _lib.dev_ptr(self._life_planes, self._feat[0], 'life'), None, self._feat[1],
-                                                     B, N, stream), 'gg_batch_life_tracked')
+                _plane_launch('gg_batch_life_tracked', lp, op, _lib.dev_ptr(self._life_planes, self._feat[0], 'life'), None,
+                              self._feat[1], B, N, stream)
             if self._ladder:
-                _lib.check(lib.gg_batch_ladder_tracked(lp, None if self._sym is None else op,
-                                                       _lib.dev_ptr(self._ladder_planes, self._feat[0], 'ladder'), None,
-                                                       self._feat[1], B, N, stream), 'gg_batch_ladder_tracked')
+                _plane_launch('gg_batch_ladder_tracked', lp, op, _lib.dev_ptr(self._ladder_planes, self._feat[0], 'ladder'), None,
+                              self._feat[1], B, N, stream)
         self._pending = True
         legal = self._legal if self._sym is None else self._legal_view
         res = (self._states, legal, self._life_planes) if self._life else (self._states, legal)
