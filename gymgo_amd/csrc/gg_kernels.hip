@@ -37,22 +37,6 @@
 #include "gg_puct.h"
 #include "gymgo_amd.h"
 
-namespace gg {
-// gg_rollout.hip: the fused multi-ply launches with drawn moves, a translation unit of their own (one code-generation switch differs)
-void launch_rollout4(int io, uint8_t *st, uint64_t *rng, int32_t *last_actions, int64_t *steps_done, int64_t B, int32_t N,
-                     uint32_t inv, int plies, int auto_reset, int nb, int grid, hipStream_t s);
-void launch_rollout5(int io, int N, uint8_t *st, uint64_t *rng, int32_t *last_actions, int64_t *steps_done, int64_t B, uint32_t inv,
-                     int plies, int auto_reset, int nb, int grid, hipStream_t s, uint32_t *ws);
-void launch_rollout_lat(int io, uint8_t *st, uint64_t *rng, int32_t *last_actions, int64_t *steps_done, int64_t B, int32_t N, int plies,
-                        int auto_reset, bool w4, hipStream_t s);
-void launch_env_step_lat(uint32_t *tracked, uint64_t *rng, int64_t *steps_done, int64_t B, int32_t N, int auto_reset,
-                         const EnvArgs &env, bool w4, hipStream_t s);
-void launch_rollout5_policy(int N, uint8_t *st, uint64_t *rng, int32_t *last_actions, int64_t *steps_done, int64_t B, uint32_t inv,
-                            int plies, int auto_reset, int nb, int grid, hipStream_t s);
-void launch_rollout_lat_policy(uint8_t *st, uint64_t *rng, int32_t *last_actions, int64_t *steps_done, int64_t B, int32_t N, int plies,
-                               int auto_reset, hipStream_t s);
-}
-
 namespace {
 
 using namespace gg;
@@ -161,21 +145,6 @@ AgeSplit age_split(const void *kern, int cus, int64_t npairs, bool split, int &g
   return as;
 }
 
-// Grid of a sixteen-board kernel (gg_ns16.h).  19x19: the resident set of three waves per SIMD with a SIMD's groups split
-// by wave age (cumulative shares c1, c2) - but only when this kernel really has three resident waves per SIMD on this
-// device; any other occupancy (a compiler that needs more registers, a partitioned device) takes one workgroup per group
-// like the smaller boards, whose results are the same and whose performance degrades gently.
-template <typename... KArgs>
-AgeSplit ns16_grid(void (*kern19)(KArgs...), int cus, int64_t ngroups, int32_t N, uint32_t c1, uint32_t c2, int &grid16) {
-  AgeSplit as = {0, {c1, c2, 65536u}};
-  grid16 = (int)ngroups;
-  if (N == 19 && waves_per_simd_of(reinterpret_cast<const void *>(kern19)) == 3) {
-    as.cols = cus * 4;
-    grid16 = as.cols * 3;
-  }
-  return as;
-}
-
 template <typename... KArgs, typename... Args>
 void launch_pairs(void (*kern)(KArgs...), int cus, int64_t npairs, bool split, hipStream_t s, Args... args) {
   int grid;
@@ -207,10 +176,34 @@ bool use_ns16(int cus, int64_t B, int32_t N, int per19, int per13, int per9) {
   return big && ngroups >= (int64_t)cus * 4 * per_simd;
 }
 
+// THE TAKE-OVER of a batch by a sixteen-board kernel family: kern19 = its 19x19 instantiation, per19 / per13 / per9 = the
+// groups per SIMD it serves the board size from (use_ns16), c1 / c2 = the cumulative shares of a SIMD's groups its oldest /
+// two oldest waves take.  launch(size tag, grid, age split) launches the instantiation of the tag's R; true when it did.
+// The grid at 19x19: the resident set of three waves per SIMD with a SIMD's groups split by wave age - but only when this
+// kernel really has three resident waves per SIMD on this device; any other occupancy (a compiler that needs more
+// registers, a partitioned device) takes one workgroup per group like the smaller boards, whose results are the same and
+// whose performance degrades gently.
+template <typename... KArgs, class Launch>
+bool ns16_takeover(void (*kern19)(KArgs...), int cus, int64_t B, int32_t N, int per19, int per13, int per9, uint32_t c1, uint32_t c2,
+                   Launch &&launch) {
+  if (!use_ns16(cus, B, N, per19, per13, per9)) return false;
+  AgeSplit as = {0, {c1, c2, 65536u}};
+  int grid16 = (int)((B + kNB16 - 1) / kNB16);
+  if (N == 19 && waves_per_simd_of(reinterpret_cast<const void *>(kern19)) == 3) {
+    as.cols = cus * 4;
+    grid16 = as.cols * 3;
+  }
+  by_rows(N, [&](auto t) { launch(t, grid16, as); });
+  return true;
+}
+
 // multi-ply kernel: boards per wave (even, <= kNB4 = 16).  The flood batch of a ply costs the same for 2 or 16 boards, so
 // the more the better; small batches take fewer per wave so that every SIMD still gets a wave.  65 536 games on 256 CUs:
 // 16 boards x 4 096 waves = exactly the resident set (4 waves per SIMD).
-int boards_per_wave(int cus, int64_t B, int &grid) {
+struct WaveGrid {
+  int nb, grid;   // boards per wave, workgroups
+};
+WaveGrid boards_per_wave(int cus, int64_t B) {
   int64_t nb = B / ((int64_t)cus * 4);
 #ifdef GG_AB
   if (const char *e = getenv("GG_AB_NB")) nb = atoi(e);
@@ -218,8 +211,7 @@ int boards_per_wave(int cus, int64_t B, int &grid) {
   if (nb > kNB4) nb = kNB4;
   nb &= ~(int64_t)1;
   if (nb < 2) nb = 2;
-  grid = grid_for(cus, (B + nb - 1) / nb);
-  return (int)nb;
+  return {(int)nb, grid_for(cus, (B + nb - 1) / nb)};
 }
 
 // Byte-plane / packed boards enter a multi-ply launch through one full analysis per board; the multi-ply kernel pays
@@ -237,7 +229,7 @@ bool use_multi_ply(int cus, int64_t B, int plies) {
 
 // The thirty-two-board multi-ply kernel (gg_v5.h: a pair of lanes per board, the floods of a ply as a compacted job list) serves
 // the fused launches of full-size 19x19 batches from the point on where k_rollout4 would need a THIRD wave per SIMD (more than 128
-// games per CU; round 6, last session: also 9x9 and 13x13 batches, from 160 games per CU); 19.5 KB of LDS per wave = eight waves per CU = two per SIMD.  Boards per wave: as many as keep the rounds of
+// games per CU; round 6, last session: also 9x9 and 13x13 batches, with more than 159 games per CU); 19.5 KB of LDS per wave = eight waves per CU = two per SIMD.  Boards per wave: as many as keep the rounds of
 // resident waves full (65 536 games on 256 CUs: 32 boards x 2 048 waves; 34 816: 18 boards).  Measured new / k_rollout4, ms per
 // launch of 256 plies (profiles/r06f_r5_edges.txt, r06f_r5_time.txt): 32 768 games 1.195 / 1.190, 34 816 1.208 / 1.455, 49 152
 // 1.247 / 1.490, 65 536 1.304 / 1.835, 98 304 2.47 / 3.55, 131 072 2.57 / 3.62; and per launch length at 65 536 games: 2 plies
@@ -246,7 +238,7 @@ bool use_multi_ply(int cus, int64_t B, int plies) {
 bool use_rollout5(int cus, int64_t B, int32_t N, int plies) {
   // 9x9 / 13x13 (tools/exp/r5_small.py, ms per launch of 256 plies, new / k_rollout4 or k_rollout_lat): 9x9 32 768 games 0.735 / 0.726,
   // 40 960 0.826 / 0.854, 49 152 0.845 / 0.869, 65 536 0.874 / 1.032, 131 072 1.98 / 2.36; 13x13 32 768 0.966 / 0.894, 40 960 0.987 /
-  // 1.084, 49 152 1.009 / 1.104, 65 536 1.051 / 1.337, 131 072 2.32 / 2.64 -> from 160 games per CU on (13x13 with a row stride of
+  // 1.084, 49 152 1.009 / 1.104, 65 536 1.051 / 1.337, 131 072 2.32 / 2.64 -> with more than 159 games per CU (13x13 with a row stride of
   // 20 words: with the 16 of the other kernels the blocks of every fourth board share their LDS banks, 1.42 ms at 65 536 games)
   int64_t per_cu = N == 19 ? 4 * kNB5 : 5 * kNB5 - 1;
   int min_plies = 8;
@@ -258,7 +250,7 @@ bool use_rollout5(int cus, int64_t B, int32_t N, int plies) {
 #endif
   return ok && plies >= min_plies && B > (int64_t)cus * per_cu;
 }
-int boards_per_wave5(int cus, int64_t B, int &grid) {
+WaveGrid boards_per_wave5(int cus, int64_t B) {
   const int64_t resident = (int64_t)cus * 8;
   const int64_t waves = (B + kNB5 - 1) / kNB5, rounds = (waves + resident - 1) / resident;
   int64_t nb = (B + rounds * resident - 1) / (rounds * resident);
@@ -268,8 +260,7 @@ int boards_per_wave5(int cus, int64_t B, int &grid) {
   nb = (nb + 1) & ~(int64_t)1;
   if (nb > kNB5) nb = kNB5;
   if (nb < 2) nb = 2;
-  grid = grid_for(cus, (B + nb - 1) / nb);
-  return (int)nb;
+  return {(int)nb, grid_for(cus, (B + nb - 1) / nb)};
 }
 
 // The latency-shaped multi-ply kernel (gg_lat.h: one row per lane, four 9x9 / 13x13 boards or two 19x19 boards per wave, the
@@ -342,6 +333,20 @@ bool lat_w4(int cus, int64_t B, int32_t N, int plies) {
   return w4;
 }
 
+// Small launches of the two-board kernels go out as four-wave workgroups too, up to two waves per SIMD (9x9: four): the
+// dispatcher's ramp is per workgroup, and there is no pipeline to fill (the measurements stand at the call sites).
+// (A/B builds: GG_AB_WPB = 1 / 4 forces the form below 24 pairs per CU; gg_batch_next_states, `straight`: GG_AB_NS_STRAIGHT
+// = 0 / 1, up to 24 pairs per CU.)
+bool small_launch(int cus, int64_t npairs, int32_t N, bool straight = false) {
+  bool small = npairs <= (int64_t)cus * (N <= 9 ? 16 : 8);
+#ifdef GG_AB
+  if (const char *e = getenv(straight ? "GG_AB_NS_STRAIGHT" : "GG_AB_WPB"))
+    small = straight ? atoi(e) != 0 && npairs <= (int64_t)cus * 24 : atoi(e) == 4 && npairs < (int64_t)cus * 24;
+#endif
+  return small;
+}
+const AgeSplit kNoSplit = {0, {0, 0, 0}};
+
 int32_t check(int64_t B, int32_t N) { return (N < 2 || N > GG_MAX_BOARD || B < 0) ? GG_E_BADSIZE : 0; }
 
 // reciprocal for the in-kernel action -> (row, col) split; exactness is verified for every action
@@ -352,58 +357,21 @@ uint32_t recip16(int32_t N) {
   return inv;
 }
 
-// multi-ply kernel: the instantiation with compile-time N when the board fills its row capacity (9, 13, 19)
-#define GG_DISPATCH4(N, IO, MOVES, GRID, ...)                                                          \
-  do {                                                                                                  \
-    if ((N) == 9) { k_rollout4<9, IO, MOVES, true><<<GRID, kWave, 0, s>>>(__VA_ARGS__); }        \
-    else if ((N) < 9) { k_rollout4<9, IO, MOVES, false><<<GRID, kWave, 0, s>>>(__VA_ARGS__); }   \
-    else if ((N) == 13) { k_rollout4<13, IO, MOVES, true><<<GRID, kWave, 0, s>>>(__VA_ARGS__); } \
-    else if ((N) < 13) { k_rollout4<13, IO, MOVES, false><<<GRID, kWave, 0, s>>>(__VA_ARGS__); } \
-    else if ((N) == 19) { k_rollout4<19, IO, MOVES, true><<<GRID, kWave, 0, s>>>(__VA_ARGS__); } \
-    else { k_rollout4<19, IO, MOVES, false><<<GRID, kWave, 0, s>>>(__VA_ARGS__); }               \
-  } while (0)
+// k_rollout4 with the moves given or drawn from weights (IO: 0 byte planes, 1 packed, 2 tracked boards, 3 byte planes through the
+// caller's workspace; ENV: one ply with GoEnv.step's outputs; WTS: the moves drawn from policy weights by the kernel): the
+// instantiation with compile-time N when the board fills its row capacity.  (Drawn moves without outputs: gg_rollout.hip.)
+template <int IO, bool MOVES, bool ENV = false, bool WTS = false, typename... Args>
+void launch4(int32_t N, int grid, hipStream_t s, Args... args) {
+  by_size(N, [&](auto t) { k_rollout4<decltype(t)::R, IO, MOVES, decltype(t)::FULL, ENV, WTS><<<grid, kWave, 0, s>>>(args...); });
+}
 
-// the env-step instantiation (tracked boards, one ply, GoEnv.step outputs)
-#define GG_DISPATCH4E(N, MOVES, GRID, ...)                                                                \
-  do {                                                                                                     \
-    if ((N) == 9) { k_rollout4<9, 2, MOVES, true, true><<<GRID, kWave, 0, s>>>(__VA_ARGS__); }        \
-    else if ((N) < 9) { k_rollout4<9, 2, MOVES, false, true><<<GRID, kWave, 0, s>>>(__VA_ARGS__); }   \
-    else if ((N) == 13) { k_rollout4<13, 2, MOVES, true, true><<<GRID, kWave, 0, s>>>(__VA_ARGS__); } \
-    else if ((N) < 13) { k_rollout4<13, 2, MOVES, false, true><<<GRID, kWave, 0, s>>>(__VA_ARGS__); } \
-    else if ((N) == 19) { k_rollout4<19, 2, MOVES, true, true><<<GRID, kWave, 0, s>>>(__VA_ARGS__); } \
-    else { k_rollout4<19, 2, MOVES, false, true><<<GRID, kWave, 0, s>>>(__VA_ARGS__); }               \
-  } while (0)
-
-// ... with the moves drawn from policy weights by the kernel
-#define GG_DISPATCH4W(N, GRID, ...)                                                                        \
-  do {                                                                                                     \
-    if ((N) == 9) { k_rollout4<9, 2, true, true, true, true><<<GRID, kWave, 0, s>>>(__VA_ARGS__); }        \
-    else if ((N) < 9) { k_rollout4<9, 2, true, false, true, true><<<GRID, kWave, 0, s>>>(__VA_ARGS__); }   \
-    else if ((N) == 13) { k_rollout4<13, 2, true, true, true, true><<<GRID, kWave, 0, s>>>(__VA_ARGS__); } \
-    else if ((N) < 13) { k_rollout4<13, 2, true, false, true, true><<<GRID, kWave, 0, s>>>(__VA_ARGS__); } \
-    else if ((N) == 19) { k_rollout4<19, 2, true, true, true, true><<<GRID, kWave, 0, s>>>(__VA_ARGS__); } \
-    else { k_rollout4<19, 2, true, false, true, true><<<GRID, kWave, 0, s>>>(__VA_ARGS__); }               \
-  } while (0)
-
-#define GG_DISPATCH(N, CALL9, CALL13, CALL19) \
-  do {                                        \
-    if ((N) <= 9) { CALL9; }                  \
-    else if ((N) <= 13) { CALL13; }           \
-    else { CALL19; }                          \
-  } while (0)
-
-// GG_K(R, F) = the launch of the kernel for row capacity R; F: the board fills the capacity (N == R is a compile-time
-// constant in that instantiation)
-#define GG_DISPATCH_N(N)                     \
-  do {                                       \
-    if ((N) == 9) { GG_K(9, true); }         \
-    else if ((N) < 9) { GG_K(9, false); }    \
-    else if ((N) == 13) { GG_K(13, true); }  \
-    else if ((N) < 13) { GG_K(13, false); }  \
-    else if ((N) == 19) { GG_K(19, true); }  \
-    else { GG_K(19, false); }                \
-  } while (0)
-
+// the tree-search kernels: four roots per four-wave workgroup, on the device that owns `p`
+template <typename... KArgs, typename... Args>
+int32_t launch_roots(void (*kern)(KArgs...), const void *p, int64_t R, void *hip_stream, Args... args) {
+  OnDeviceOf on_dev(p);
+  kern<<<grid_for(on_dev.cus(), (R + 3) / 4), 4 * kWave, 0, (hipStream_t)hip_stream>>>(args...);
+  return (int32_t)hipGetLastError();
+}
 
 // ---- the playout queue (gg_po.h) behind gg_playouts_* (PoArgs, one result cell per root) and gg_move_playouts_* (MpArgs,
 // cells = A result cells per root, one per first move).  po_args: the argument checks both families share, in the order
@@ -442,9 +410,7 @@ template <bool FILL, class Args>
 static void launch_harvest(const Args &a, int32_t N, int cus, hipStream_t s) {
   const int nbw = N <= 13 ? Lat<13>::NBW : Lat<19>::NBW;
   const int grid = grid_for(cus, (a.S + nbw - 1) / nbw, 64);
-#define GG_K(R, F) k_po_harvest<R, F, FILL, Args><<<grid, kWave, 0, s>>>(a, N)
-  GG_DISPATCH_N(N);
-#undef GG_K
+  by_size(N, [&](auto t) { k_po_harvest<decltype(t)::R, decltype(t)::FULL, FILL, Args><<<grid, kWave, 0, s>>>(a, N); });
 }
 
 static bool policy_ok(int32_t policy) { return policy == GG_POLICY_UNIFORM || policy == GG_POLICY_NO_EYE_FILL; }
@@ -575,41 +541,28 @@ int32_t gg_batch_next_states(const uint8_t *in, const int32_t *actions, uint8_t 
   // against 60.0 with one workgroup per group; 1 : 1 : 2 70.6), the smaller boards (four waves per SIMD) one workgroup
   // per group.
   {
-    const int64_t ngroups = (B + kNB16 - 1) / kNB16;
-    const bool big = use_ns16(cus, B, N, 4, 2, 2);
     double c1 = 0.5, c2 = 0.75;
 #ifdef GG_AB
     if (const char *e = getenv("GG_AB_NS16_CUT")) sscanf(e, "%lf,%lf", &c1, &c2);
 #endif
-    if (big) {
-      int grid16;
-      AgeSplit as = ns16_grid(k_next_states16<19>, cus, ngroups, N, (uint32_t)(c1 * 65536.0), (uint32_t)(c2 * 65536.0), grid16);
+    if (ns16_takeover(k_next_states16<19>, cus, B, N, 4, 2, 2, (uint32_t)(c1 * 65536.0), (uint32_t)(c2 * 65536.0),
+                      [&](auto t, int grid16, AgeSplit as) {
 #ifdef GG_AB
-      if (const char *e = getenv("GG_AB_NS16_GRID")) { grid16 = atoi(e); as.cols = 0; }
-      {
-        const int dbg = getenv("GG_AB_NS16_DBG") ? atoi(getenv("GG_AB_NS16_DBG")) : 0;
-        (void)hipMemcpyToSymbolAsync(HIP_SYMBOL(gg::gg_ns16_dbg), &dbg, sizeof dbg, 0, hipMemcpyHostToDevice, s);
-      }
+                        if (const char *e = getenv("GG_AB_NS16_GRID")) { grid16 = atoi(e); as.cols = 0; }
+                        const int dbg = getenv("GG_AB_NS16_DBG") ? atoi(getenv("GG_AB_NS16_DBG")) : 0;
+                        (void)hipMemcpyToSymbolAsync(HIP_SYMBOL(gg::gg_ns16_dbg), &dbg, sizeof dbg, 0, hipMemcpyHostToDevice, s);
 #endif
-      GG_DISPATCH(N, (k_next_states16<9><<<grid16, kWave, 0, s>>>(in, actions, out, status, B, canonical, as)),
-                  (k_next_states16<13><<<grid16, kWave, 0, s>>>(in, actions, out, status, B, canonical, as)),
-                  (k_next_states16<19><<<grid16, kWave, 0, s>>>(in, actions, out, status, B, canonical, as)));
+                        k_next_states16<decltype(t)::R><<<grid16, kWave, 0, s>>>(in, actions, out, status, B, canonical, as);
+                      }))
       return (int32_t)hipGetLastError();
-    }
   }
   const int64_t npairs = (B + 1) / 2;
   // up to two waves per SIMD (9x9: four) there is no pipeline to fill: one pair per wave, every read of the pair in flight at
   // once, four-wave workgroups (k_next_states2s; hipGraph node, 9x9 / 13x13 / 19x19 x 4 096 games 6.53 -> 5.88 / 7.82 -> 6.96 / 9.18 -> 8.66 us:
   // profiles/r05p_perply_nodes.txt)
-  bool straight = npairs <= (int64_t)cus * (N <= 9 ? 16 : 8);
-#ifdef GG_AB
-  if (const char *e = getenv("GG_AB_NS_STRAIGHT")) straight = atoi(e) != 0 && npairs <= (int64_t)cus * 24;
-#endif
-  if (straight) {
+  if (small_launch(cus, npairs, N, true)) {
     const unsigned grid4 = (unsigned)((npairs + 3) / 4);
-    GG_DISPATCH(N, (k_next_states2s<9, 4><<<grid4, 4 * kWave, 0, s>>>(in, actions, out, status, B, N, inv, canonical)),
-                (k_next_states2s<13, 4><<<grid4, 4 * kWave, 0, s>>>(in, actions, out, status, B, N, inv, canonical)),
-                (k_next_states2s<19, 4><<<grid4, 4 * kWave, 0, s>>>(in, actions, out, status, B, N, inv, canonical)));
+    by_rows(N, [&](auto t) { k_next_states2s<decltype(t)::R, 4><<<grid4, 4 * kWave, 0, s>>>(in, actions, out, status, B, N, inv, canonical); });
     return (int32_t)hipGetLastError();
   }
   int grid = grid_resident(cus, npairs, GG_LB_PLY);
@@ -624,9 +577,9 @@ int32_t gg_batch_next_states(const uint8_t *in, const int32_t *actions, uint8_t 
   if (getenv("GG_AB_NS_EVEN")) cols = 0;
 #endif
   if (cols) grid = cols * GG_LB_PLY;
-  GG_DISPATCH(N, (k_next_states2<9><<<grid, kWave, 0, s>>>(in, actions, out, status, B, N, inv, canonical, cols, share1, share2)),
-              (k_next_states2<13><<<grid, kWave, 0, s>>>(in, actions, out, status, B, N, inv, canonical, cols, share1, share2)),
-              (k_next_states2<19><<<grid, kWave, 0, s>>>(in, actions, out, status, B, N, inv, canonical, cols, share1, share2)));
+  by_rows(N, [&](auto t) {
+    k_next_states2<decltype(t)::R><<<grid, kWave, 0, s>>>(in, actions, out, status, B, N, inv, canonical, cols, share1, share2);
+  });
   return (int32_t)hipGetLastError();
 }
 
@@ -634,11 +587,10 @@ int32_t gg_batch_next_states_ws(const uint8_t *in, const int32_t *actions, uint8
                                 int64_t B, int32_t N, int32_t canonical, void *hip_stream) {
   GG_ENTER(in);
   if (!actions || !out || !workspace) return GG_E_NULLPTR;
-  int grid;
-  const int nb = boards_per_wave(cus, B, grid);
+  const WaveGrid w = boards_per_wave(cus, B);
   EnvArgs env = EnvArgs();
   env.status = status; env.states_out = out; env.ws = workspace; env.canonical = canonical;
-  GG_DISPATCH4(N, 3, true, grid, const_cast<uint8_t *>(in), nullptr, nullptr, nullptr, B, N, inv, 1, 0, nb, actions, nullptr, env);
+  launch4<3, true>(N, w.grid, s, const_cast<uint8_t *>(in), nullptr, nullptr, nullptr, B, N, inv, 1, 0, w.nb, actions, nullptr, env);
   return (int32_t)hipGetLastError();
 }
 
@@ -652,21 +604,14 @@ int32_t gg_batch_invalid_mask(const uint8_t *states, const int32_t *ko, uint8_t 
       // 3 072 resident waves are one round and a third); with the groups of a SIMD split 2 : 1 : 1 over its three waves by
       // age it is, from four groups per SIMD on (round 4: 65 536 boards 49.0 -> 47.0 us, 131 072: 87.3 -> 81.3; 49 152:
       // 37.0 -> 38.5, so not below))
-    const int64_t ngroups = (B + kNB16 - 1) / kNB16;
-    const bool big = use_ns16(cus, B, N, 4, 2, 1);
-    if (big) {
-      int grid16;   // (19x19: three waves per SIMD share a SIMD's groups 2 : 1 : 1 by age, like gg_batch_next_states)
-      const AgeSplit as = ns16_grid(k_invalid_mask16<19>, cus, ngroups, N, 32768u, 49152u, grid16);
-      if (N == 9) k_invalid_mask16<9><<<grid16, kWave, 0, s>>>(states, ko, mask, B, as);
-      else if (N == 13) k_invalid_mask16<13><<<grid16, kWave, 0, s>>>(states, ko, mask, B, as);
-      else k_invalid_mask16<19><<<grid16, kWave, 0, s>>>(states, ko, mask, B, as);
+    // (19x19: three waves per SIMD share a SIMD's groups 2 : 1 : 1 by age, like gg_batch_next_states)
+    if (ns16_takeover(k_invalid_mask16<19>, cus, B, N, 4, 2, 1, 32768u, 49152u, [&](auto t, int grid16, const AgeSplit &as) {
+          k_invalid_mask16<decltype(t)::R><<<grid16, kWave, 0, s>>>(states, ko, mask, B, as);
+        }))
       return (int32_t)hipGetLastError();
-    }
   }
   const int64_t npairs = (B + 1) / 2;
-#define GG_K(R, F) launch_pairs(k_invalid_mask2<R, F>, cus, npairs, true, s, states, ko, mask, B, N, inv)
-  GG_DISPATCH_N(N);
-#undef GG_K
+  by_size(N, [&](auto t) { launch_pairs(k_invalid_mask2<decltype(t)::R, decltype(t)::FULL>, cus, npairs, true, s, states, ko, mask, B, N, inv); });
   return (int32_t)hipGetLastError();
 }
 
@@ -676,9 +621,7 @@ int32_t gg_batch_areas(const uint8_t *states, int32_t *black, int32_t *white, in
   const int64_t groups = (B + LdsAreas<19>::kBoards - 1) / LdsAreas<19>::kBoards;   // one wave per sixteen boards
   if (groups > 0x7FFFFFFF) return GG_E_BADSIZE;
   const int grid = (int)groups;
-#define GG_K(R, F) k_areas4<R, F><<<grid, kWave, 0, s>>>(states, black, white, B, N)
-  GG_DISPATCH_N(N);
-#undef GG_K
+  by_size(N, [&](auto t) { k_areas4<decltype(t)::R, decltype(t)::FULL><<<grid, kWave, 0, s>>>(states, black, white, B, N); });
   return (int32_t)hipGetLastError();
 }
 
@@ -702,9 +645,7 @@ int32_t gg_batch_children(const uint8_t *states, uint8_t *children, int64_t B, i
   if (!children) return GG_E_NULLPTR;
   const int chunks = children_chunks(cus, B, N * N + 1);
   const int grid = grid_for(cus, B * chunks);
-  GG_DISPATCH(N, (k_children3<9><<<grid, kWave, 0, s>>>(states, children, B, N, inv, canonical, chunks)),
-              (k_children3<13><<<grid, kWave, 0, s>>>(states, children, B, N, inv, canonical, chunks)),
-              (k_children3<19><<<grid, kWave, 0, s>>>(states, children, B, N, inv, canonical, chunks)));
+  by_rows(N, [&](auto t) { k_children3<decltype(t)::R><<<grid, kWave, 0, s>>>(states, children, B, N, inv, canonical, chunks); });
   return (int32_t)hipGetLastError();
 }
 
@@ -730,9 +671,9 @@ int32_t gg_batch_children_compact(const uint8_t *states, const int32_t *offsets,
   if (B > (int64_t)0x7FFFFFFF / (N * N + 1)) return GG_E_BADSIZE;
   const int chunks = children_chunks(cus, B, N * N + 1);
   const int grid = grid_for(cus, B * chunks);
-  GG_DISPATCH(N, (k_children3<9, false, true><<<grid, kWave, 0, s>>>(states, children, B, N, inv, canonical, chunks, offsets, order)),
-              (k_children3<13, false, true><<<grid, kWave, 0, s>>>(states, children, B, N, inv, canonical, chunks, offsets, order)),
-              (k_children3<19, false, true><<<grid, kWave, 0, s>>>(states, children, B, N, inv, canonical, chunks, offsets, order)));
+  by_rows(N, [&](auto t) {
+    k_children3<decltype(t)::R, false, true><<<grid, kWave, 0, s>>>(states, children, B, N, inv, canonical, chunks, offsets, order);
+  });
   return (int32_t)hipGetLastError();
 }
 
@@ -750,55 +691,41 @@ static int32_t batch_rollout(uint8_t *states, uint64_t *rng, int32_t *last_actio
     return (int32_t)hipGetLastError();
   }
   if (use_rollout5(cus, B, N, plies)) {   // a full machine: 32 boards per wave, the floods of a ply as a job list (gg_v5.h)
-    int grid;
-    const int nb = boards_per_wave5(cus, B, grid);
-    launch_rollout5(0, N, states, rng, last_actions, steps_done, B, inv, plies, auto_reset, nb, grid, s, workspace);
+    const WaveGrid w = boards_per_wave5(cus, B);
+    launch_rollout5(0, N, states, rng, last_actions, steps_done, B, inv, plies, auto_reset, w.nb, w.grid, s, workspace);
     return (int32_t)hipGetLastError();
   }
   if (use_multi_ply(cus, B, plies)) {   // liberty classes carried across the plies, 16 boards per wave
-    int grid;
-    const int nb = boards_per_wave(cus, B, grid);
-    launch_rollout4(0, states, rng, last_actions, steps_done, B, N, inv, plies, auto_reset, nb, grid, s);
+    const WaveGrid w = boards_per_wave(cus, B);
+    launch_rollout4(0, states, rng, last_actions, steps_done, B, N, inv, plies, auto_reset, w.nb, w.grid, s);
     return (int32_t)hipGetLastError();
   }
-  if (plies == 1) {   // one ply per launch on a big batch of full-size boards: the env step without the GoEnv outputs (gg_ns16.h)
-    const int64_t ngroups = (B + kNB16 - 1) / kNB16;
-    const bool big = use_ns16(cus, B, N, 3, 2, 1);
-    if (big) {
-      int grid16;
-      const AgeSplit as = ns16_grid(k_env_step16<19, false>, cus, ngroups, N, 32768u, 49152u, grid16);
-      GG_DISPATCH(N, (k_env_step16<9, false><<<grid16, kWave, 0, s>>>(states, nullptr, rng, nullptr, nullptr, nullptr, nullptr, B, 0.f, auto_reset, as, last_actions, steps_done)),
-                  (k_env_step16<13, false><<<grid16, kWave, 0, s>>>(states, nullptr, rng, nullptr, nullptr, nullptr, nullptr, B, 0.f, auto_reset, as, last_actions, steps_done)),
-                  (k_env_step16<19, false><<<grid16, kWave, 0, s>>>(states, nullptr, rng, nullptr, nullptr, nullptr, nullptr, B, 0.f, auto_reset, as, last_actions, steps_done)));
-      return (int32_t)hipGetLastError();
-    }
-  }
+  // one ply per launch on a big batch of full-size boards: the env step without the GoEnv outputs (gg_ns16.h)
+  if (plies == 1 && ns16_takeover(k_env_step16<19, false>, cus, B, N, 3, 2, 1, 32768u, 49152u, [&](auto t, int grid16, const AgeSplit &as) {
+        k_env_step16<decltype(t)::R, false><<<grid16, kWave, 0, s>>>(states, nullptr, rng, nullptr, nullptr, nullptr, nullptr, B, 0.f, auto_reset,
+                                                                      as, last_actions, steps_done);
+      }))
+    return (int32_t)hipGetLastError();
   const int64_t npairs = (B + 1) / 2;
-  if (plies <= 2) {
-    // small launches go out as four-wave workgroups: the dispatcher's ramp is per workgroup (k_rollout2, WPB).  hipGraph node,
-    // one ply, single-wave -> four-wave workgroups (profiles/r05p_wpb.txt): 9x9 4 096 / 8 192 games 6.02 -> 5.82 / 7.97 -> 7.61 us,
-    // 13x13 4 096 6.98 -> 6.80 (8 192: 9.67 -> 10.66, the four waves' LDS no longer fits three times per CU), 19x19 4 096 8.49 ->
-    // 8.37; 1 024 games: no change -> up to two waves per SIMD (9x9: four)
-    int wpb = npairs <= (int64_t)cus * (N <= 9 ? 16 : 8) ? 4 : 1;
-#ifdef GG_AB
-    if (const char *e = getenv("GG_AB_WPB")) wpb = atoi(e) == 4 && npairs < (int64_t)cus * 24 ? 4 : 1;
-#endif
-    if (wpb == 4) {
-      const AgeSplit none = {0, {0, 0, 0}};
-      const unsigned grid4 = (unsigned)((npairs + 3) / 4);
-#define GG_K(R, F) k_rollout2_w4<R, F><<<grid4, 4 * kWave, 0, s>>>(states, rng, last_actions, steps_done, B, N, inv, plies, auto_reset, none)
-      GG_DISPATCH_N(N);
-#undef GG_K
-      return (int32_t)hipGetLastError();
-    }
-#define GG_K(R, F) launch_pairs(k_rollout2<R, true, false, F>, cus, npairs, true, s, states, rng, last_actions, steps_done, B, N, inv, plies, auto_reset)
-    GG_DISPATCH_N(N);
-#undef GG_K
-  } else {
-#define GG_K(R, F) launch_pairs(k_rollout2<R, false, false, F>, cus, npairs, plies < 8, s, states, rng, last_actions, steps_done, B, N, inv, plies, auto_reset)
-    GG_DISPATCH_N(N);
-#undef GG_K
+  // small launches go out as four-wave workgroups: the dispatcher's ramp is per workgroup (k_rollout2, WPB).  hipGraph node,
+  // one ply, single-wave -> four-wave workgroups (profiles/r05p_wpb.txt): 9x9 4 096 / 8 192 games 6.02 -> 5.82 / 7.97 -> 7.61 us,
+  // 13x13 4 096 6.98 -> 6.80 (8 192: 9.67 -> 10.66, the four waves' LDS no longer fits three times per CU), 19x19 4 096 8.49 ->
+  // 8.37; 1 024 games: no change -> up to two waves per SIMD (9x9: four)
+  if (plies <= 2 && small_launch(cus, npairs, N)) {
+    const unsigned grid4 = (unsigned)((npairs + 3) / 4);
+    by_size(N, [&](auto t) {
+      k_rollout2_w4<decltype(t)::R, decltype(t)::FULL><<<grid4, 4 * kWave, 0, s>>>(states, rng, last_actions, steps_done, B, N, inv, plies,
+                                                                              auto_reset, kNoSplit);
+    });
+    return (int32_t)hipGetLastError();
   }
+  // the one- and two-ply instantiation; longer launches split the pairs of a SIMD by wave age below eight plies only
+  by_size(N, [&](auto t) {
+    by_flag(plies <= 2, [&](auto sh) {
+      launch_pairs(k_rollout2<decltype(t)::R, decltype(sh)::value, false, decltype(t)::FULL>, cus, npairs, plies < 8, s, states, rng,
+                   last_actions, steps_done, B, N, inv, plies, auto_reset);
+    });
+  });
   return (int32_t)hipGetLastError();
 }
 
@@ -818,53 +745,29 @@ int32_t gg_batch_env_step(uint8_t *states, const int32_t *actions, uint64_t *rng
   if (reward_method != GG_REWARD_REAL && reward_method != GG_REWARD_HEURISTIC) return GG_E_BADARG;
   GG_ENTER(states);
   if (!actions && !rng) return GG_E_NULLPTR;
-  {   // big batches of full-size boards: the class-major analysis, sixteen boards per wave (as gg_batch_next_states)
-    const int64_t ngroups = (B + kNB16 - 1) / kNB16;
-    const bool big = use_ns16(cus, B, N, 3, 2, 1);
-    if (big) {
-      int grid16;   // 19x19: a SIMD's groups 2 : 1 : 1 by wave age
-      const AgeSplit as = reward_method == GG_REWARD_HEURISTIC ? ns16_grid(k_env_step16<19, true>, cus, ngroups, N, 32768u, 49152u, grid16)
-                                                               : ns16_grid(k_env_step16<19, false>, cus, ngroups, N, 32768u, 49152u, grid16);
-      if (reward_method == GG_REWARD_HEURISTIC) {
-        GG_DISPATCH(N, (k_env_step16<9, true><<<grid16, kWave, 0, s>>>(states, actions, rng, rewards, dones, status, taken_actions, B, komi, auto_reset, as)),
-                    (k_env_step16<13, true><<<grid16, kWave, 0, s>>>(states, actions, rng, rewards, dones, status, taken_actions, B, komi, auto_reset, as)),
-                    (k_env_step16<19, true><<<grid16, kWave, 0, s>>>(states, actions, rng, rewards, dones, status, taken_actions, B, komi, auto_reset, as)));
-      } else {
-        GG_DISPATCH(N, (k_env_step16<9, false><<<grid16, kWave, 0, s>>>(states, actions, rng, rewards, dones, status, taken_actions, B, komi, auto_reset, as)),
-                    (k_env_step16<13, false><<<grid16, kWave, 0, s>>>(states, actions, rng, rewards, dones, status, taken_actions, B, komi, auto_reset, as)),
-                    (k_env_step16<19, false><<<grid16, kWave, 0, s>>>(states, actions, rng, rewards, dones, status, taken_actions, B, komi, auto_reset, as)));
-      }
-      return (int32_t)hipGetLastError();
-    }
-  }
   const int64_t npairs = (B + 1) / 2;
-  bool w4 = npairs <= (int64_t)cus * (N <= 9 ? 16 : 8);   // small launches: four-wave workgroups (gg_batch_rollout, k_rollout2_w4)
-#ifdef GG_AB
-  if (const char *e = getenv("GG_AB_WPB")) w4 = atoi(e) == 4 && npairs < (int64_t)cus * 24;
-#endif
-  if (w4) {
-    const AgeSplit none = {0, {0, 0, 0}};
-    const unsigned grid4 = (unsigned)((npairs + 3) / 4);
-    if (reward_method == GG_REWARD_HEURISTIC) {
-#define GG_K(R, F) k_env_step2_w4<R, true, F><<<grid4, 4 * kWave, 0, s>>>(states, actions, rng, rewards, dones, status, taken_actions, B, N, inv, komi, auto_reset, none)
-      GG_DISPATCH_N(N);
-#undef GG_K
-    } else {
-#define GG_K(R, F) k_env_step2_w4<R, false, F><<<grid4, 4 * kWave, 0, s>>>(states, actions, rng, rewards, dones, status, taken_actions, B, N, inv, komi, auto_reset, none)
-      GG_DISPATCH_N(N);
-#undef GG_K
+  by_flag(reward_method == GG_REWARD_HEURISTIC, [&](auto h) {
+    constexpr bool HEUR = decltype(h)::value;
+    // big batches of full-size boards: the class-major analysis, sixteen boards per wave (as gg_batch_next_states); 19x19: a
+    // SIMD's groups 2 : 1 : 1 by wave age
+    if (ns16_takeover(k_env_step16<19, HEUR>, cus, B, N, 3, 2, 1, 32768u, 49152u, [&](auto t, int grid16, const AgeSplit &as) {
+          k_env_step16<decltype(t)::R, HEUR><<<grid16, kWave, 0, s>>>(states, actions, rng, rewards, dones, status, taken_actions, B, komi,
+                                                                     auto_reset, as);
+        }))
+      return;
+    if (small_launch(cus, npairs, N)) {   // four-wave workgroups (gg_batch_rollout, k_rollout2_w4)
+      const unsigned grid4 = (unsigned)((npairs + 3) / 4);
+      by_size(N, [&](auto t) {
+        k_env_step2_w4<decltype(t)::R, HEUR, decltype(t)::FULL><<<grid4, 4 * kWave, 0, s>>>(states, actions, rng, rewards, dones, status,
+                                                                                       taken_actions, B, N, inv, komi, auto_reset, kNoSplit);
+      });
+      return;
     }
-    return (int32_t)hipGetLastError();
-  }
-  if (reward_method == GG_REWARD_HEURISTIC) {
-#define GG_K(R, F) launch_pairs(k_env_step2<R, true, false, F>, cus, npairs, true, s, states, actions, rng, rewards, dones, status, taken_actions, B, N, inv, komi, auto_reset)
-    GG_DISPATCH_N(N);
-#undef GG_K
-  } else {
-#define GG_K(R, F) launch_pairs(k_env_step2<R, false, false, F>, cus, npairs, true, s, states, actions, rng, rewards, dones, status, taken_actions, B, N, inv, komi, auto_reset)
-    GG_DISPATCH_N(N);
-#undef GG_K
-  }
+    by_size(N, [&](auto t) {
+      launch_pairs(k_env_step2<decltype(t)::R, HEUR, false, decltype(t)::FULL>, cus, npairs, true, s, states, actions, rng, rewards, dones,
+                   status, taken_actions, B, N, inv, komi, auto_reset);
+    });
+  });
   return (int32_t)hipGetLastError();
 }
 
@@ -880,22 +783,21 @@ int32_t gg_batch_env_step_scored(uint8_t *states, const int32_t *actions, uint64
   if (!areas) return GG_E_NULLPTR;
   const int real = reward_method == GG_REWARD_REAL ? 1 : 0;
   const int64_t npairs = (B + 1) / 2;
-  if (npairs <= (int64_t)cus * (N <= 9 ? 16 : 8)) {   // small launches: four-wave workgroups (gg_batch_env_step)
-    const AgeSplit none = {0, {0, 0, 0}};
+  if (small_launch(cus, npairs, N)) {   // four-wave workgroups (gg_batch_env_step)
     const unsigned grid4 = (unsigned)((npairs + 3) / 4);
-#define GG_K(R, F) k_env_step2_w4<R, true, F><<<grid4, 4 * kWave, 0, s>>>(states, actions, rng, rewards, dones, status, taken_actions, B, N, inv, komi, auto_reset, none, areas, real)
-    GG_DISPATCH_N(N);
-#undef GG_K
+    by_size(N, [&](auto t) {
+      k_env_step2_w4<decltype(t)::R, true, decltype(t)::FULL><<<grid4, 4 * kWave, 0, s>>>(states, actions, rng, rewards, dones, status,
+                                                                                     taken_actions, B, N, inv, komi, auto_reset, kNoSplit,
+                                                                                     areas, real);
+    });
     return (int32_t)hipGetLastError();
   }
-#define GG_K(R, F)                                                                                                          \
-  do {                                                                                                                      \
-    int grid;                                                                                                               \
-    const AgeSplit as = age_split(reinterpret_cast<const void *>(k_env_step2<R, true, false, F>), cus, npairs, true, grid); \
-    k_env_step2<R, true, false, F><<<grid, kWave, 0, s>>>(states, actions, rng, rewards, dones, status, taken_actions, B, N, inv, komi, auto_reset, as, areas, real); \
-  } while (0)
-  GG_DISPATCH_N(N);
-#undef GG_K
+  by_size(N, [&](auto t) {
+    const auto kern = k_env_step2<decltype(t)::R, true, false, decltype(t)::FULL>;
+    int grid;
+    const AgeSplit as = age_split(reinterpret_cast<const void *>(kern), cus, npairs, true, grid);
+    kern<<<grid, kWave, 0, s>>>(states, actions, rng, rewards, dones, status, taken_actions, B, N, inv, komi, auto_reset, as, areas, real);
+  });
   return (int32_t)hipGetLastError();
 }
 
@@ -906,9 +808,7 @@ int32_t gg_batch_sample_actions(const uint8_t *states, uint64_t *rng, int32_t *a
   const int64_t groups = (B + LdsSample<19>::kBoards - 1) / LdsSample<19>::kBoards;   // one wave per sixteen boards
   if (groups > 0x7FFFFFFF) return GG_E_BADSIZE;
   const int grid = (int)groups;
-  GG_DISPATCH(N, (k_sample16<9><<<grid, kWave, 0, s>>>(states, rng, actions, B, N)),
-              (k_sample16<13><<<grid, kWave, 0, s>>>(states, rng, actions, B, N)),
-              (k_sample16<19><<<grid, kWave, 0, s>>>(states, rng, actions, B, N)));
+  by_rows(N, [&](auto t) { k_sample16<decltype(t)::R><<<grid, kWave, 0, s>>>(states, rng, actions, B, N); });
   return (int32_t)hipGetLastError();
 }
 
@@ -918,9 +818,7 @@ int32_t gg_batch_update_pieces(uint8_t *states, const int32_t *adj, int32_t K, c
   GG_ENTER(states);
   if (!players || (K > 0 && !adj)) return GG_E_NULLPTR;
   const int grid = grid_for(cus, B);
-  GG_DISPATCH(N, (k_update_pieces<9><<<grid, kWave, 0, s>>>(states, adj, K, players, killed, B, N, inv)),
-              (k_update_pieces<13><<<grid, kWave, 0, s>>>(states, adj, K, players, killed, B, N, inv)),
-              (k_update_pieces<19><<<grid, kWave, 0, s>>>(states, adj, K, players, killed, B, N, inv)));
+  by_rows(N, [&](auto t) { k_update_pieces<decltype(t)::R><<<grid, kWave, 0, s>>>(states, adj, K, players, killed, B, N, inv); });
   return (int32_t)hipGetLastError();
 }
 
@@ -939,9 +837,7 @@ int32_t gg_batch_pack_states(const uint8_t *states, uint32_t *packed, int64_t B,
   GG_ENTER(states);
   if (!packed) return GG_E_NULLPTR;
   const int grid = grid_for(cus, (B + 1) / 2);
-  GG_DISPATCH(N, (k_pack<9><<<grid, kWave, 0, s>>>(states, packed, B, N)),
-              (k_pack<13><<<grid, kWave, 0, s>>>(states, packed, B, N)),
-              (k_pack<19><<<grid, kWave, 0, s>>>(states, packed, B, N)));
+  by_rows(N, [&](auto t) { k_pack<decltype(t)::R><<<grid, kWave, 0, s>>>(states, packed, B, N); });
   return (int32_t)hipGetLastError();
 }
 
@@ -949,9 +845,7 @@ int32_t gg_batch_unpack_states(const uint32_t *packed, uint8_t *states, int64_t 
   GG_ENTER(packed);
   if (!states) return GG_E_NULLPTR;
   const int grid = grid_for(cus, (B + 1) / 2);
-  GG_DISPATCH(N, (k_unpack<9><<<grid, kWave, 0, s>>>(packed, states, B, N, 3)),
-              (k_unpack<13><<<grid, kWave, 0, s>>>(packed, states, B, N, 3)),
-              (k_unpack<19><<<grid, kWave, 0, s>>>(packed, states, B, N, 3)));
+  by_rows(N, [&](auto t) { k_unpack<decltype(t)::R><<<grid, kWave, 0, s>>>(packed, states, B, N, 3); });
   return (int32_t)hipGetLastError();
 }
 
@@ -961,9 +855,9 @@ int32_t gg_batch_next_states_packed(const uint32_t *in, const int32_t *actions, 
   GG_ENTER(in);
   if (!actions || !out) return GG_E_NULLPTR;
   const int64_t npairs = (B + 1) / 2;
-#define GG_K(R, F) launch_pairs(k_next_states_p<R, F>, cus, npairs, true, s, in, actions, out, status, B, N, inv, canonical)
-  GG_DISPATCH_N(N);
-#undef GG_K
+  by_size(N, [&](auto t) {
+    launch_pairs(k_next_states_p<decltype(t)::R, decltype(t)::FULL>, cus, npairs, true, s, in, actions, out, status, B, N, inv, canonical);
+  });
   return (int32_t)hipGetLastError();
 }
 
@@ -975,15 +869,15 @@ int32_t gg_batch_rollout_packed(uint32_t *packed, uint64_t *rng, int32_t *last_a
   if (!rng) return GG_E_NULLPTR;
   uint8_t *st = reinterpret_cast<uint8_t *>(packed);
   if (use_multi_ply(cus, B, plies)) {
-    int grid3;
-    const int nb = boards_per_wave(cus, B, grid3);
-    launch_rollout4(1, st, rng, last_actions, steps_done, B, N, inv, plies, auto_reset, nb, grid3, s);
+    const WaveGrid w = boards_per_wave(cus, B);
+    launch_rollout4(1, st, rng, last_actions, steps_done, B, N, inv, plies, auto_reset, w.nb, w.grid, s);
     return (int32_t)hipGetLastError();
   }
   const int64_t npairs = (B + 1) / 2;
-#define GG_K(R, F) launch_pairs(k_rollout2<R, false, true, F>, cus, npairs, plies < 8, s, st, rng, last_actions, steps_done, B, N, inv, plies, auto_reset)
-  GG_DISPATCH_N(N);
-#undef GG_K
+  by_size(N, [&](auto t) {
+    launch_pairs(k_rollout2<decltype(t)::R, false, true, decltype(t)::FULL>, cus, npairs, plies < 8, s, st, rng, last_actions, steps_done, B,
+                 N, inv, plies, auto_reset);
+  });
   return (int32_t)hipGetLastError();
 }
 
@@ -995,15 +889,12 @@ int32_t gg_batch_env_step_packed(uint32_t *packed, const int32_t *actions, uint6
   if (!actions && !rng) return GG_E_NULLPTR;
   const int64_t npairs = (B + 1) / 2;
   uint8_t *st = reinterpret_cast<uint8_t *>(packed);
-  if (reward_method == GG_REWARD_HEURISTIC) {
-#define GG_K(R, F) launch_pairs(k_env_step2<R, true, true, F>, cus, npairs, true, s, st, actions, rng, rewards, dones, status, taken_actions, B, N, inv, komi, auto_reset)
-    GG_DISPATCH_N(N);
-#undef GG_K
-  } else {
-#define GG_K(R, F) launch_pairs(k_env_step2<R, false, true, F>, cus, npairs, true, s, st, actions, rng, rewards, dones, status, taken_actions, B, N, inv, komi, auto_reset)
-    GG_DISPATCH_N(N);
-#undef GG_K
-  }
+  by_size(N, [&](auto t) {
+    by_flag(reward_method == GG_REWARD_HEURISTIC, [&](auto h) {
+      launch_pairs(k_env_step2<decltype(t)::R, decltype(h)::value, true, decltype(t)::FULL>, cus, npairs, true, s, st, actions, rng, rewards,
+                   dones, status, taken_actions, B, N, inv, komi, auto_reset);
+    });
+  });
   return (int32_t)hipGetLastError();
 }
 
@@ -1015,9 +906,7 @@ int32_t gg_batch_children_packed(const uint32_t *packed, uint32_t *children, int
   const int grid = grid_for(cus, B * chunks);
   const uint8_t *st = reinterpret_cast<const uint8_t *>(packed);
   uint8_t *ch = reinterpret_cast<uint8_t *>(children);
-  GG_DISPATCH(N, (k_children3<9, true><<<grid, kWave, 0, s>>>(st, ch, B, N, inv, canonical, chunks)),
-              (k_children3<13, true><<<grid, kWave, 0, s>>>(st, ch, B, N, inv, canonical, chunks)),
-              (k_children3<19, true><<<grid, kWave, 0, s>>>(st, ch, B, N, inv, canonical, chunks)));
+  by_rows(N, [&](auto t) { k_children3<decltype(t)::R, true><<<grid, kWave, 0, s>>>(st, ch, B, N, inv, canonical, chunks); });
   return (int32_t)hipGetLastError();
 }
 
@@ -1027,15 +916,12 @@ int32_t gg_batch_play_moves(uint8_t *states, const int32_t *moves, int32_t *play
   GG_ENTER(states);
   if (T > 0 && !moves) return GG_E_NULLPTR;
   if (use_multi_ply(cus, B, T)) {
-    int grid3;
-    const int nb = boards_per_wave(cus, B, grid3);
-    GG_DISPATCH4(N, 0, true, grid3, states, nullptr, nullptr, nullptr, B, N, inv, T, 0, nb, moves, played);
+    const WaveGrid w = boards_per_wave(cus, B);
+    launch4<0, true>(N, w.grid, s, states, nullptr, nullptr, nullptr, B, N, inv, T, 0, w.nb, moves, played);
     return (int32_t)hipGetLastError();
   }
   const int64_t npairs = (B + 1) / 2;
-  GG_DISPATCH(N, (launch_pairs(k_play_moves2<9, false>, cus, npairs, true, s, states, moves, played, B, N, inv, T)),
-              (launch_pairs(k_play_moves2<13, false>, cus, npairs, true, s, states, moves, played, B, N, inv, T)),
-              (launch_pairs(k_play_moves2<19, false>, cus, npairs, true, s, states, moves, played, B, N, inv, T)));
+  by_rows(N, [&](auto t) { launch_pairs(k_play_moves2<decltype(t)::R, false>, cus, npairs, true, s, states, moves, played, B, N, inv, T); });
   return (int32_t)hipGetLastError();
 }
 
@@ -1046,15 +932,12 @@ int32_t gg_batch_play_moves_packed(uint32_t *packed, const int32_t *moves, int32
   if (T > 0 && !moves) return GG_E_NULLPTR;
   uint8_t *st = reinterpret_cast<uint8_t *>(packed);
   if (use_multi_ply(cus, B, T)) {
-    int grid3;
-    const int nb = boards_per_wave(cus, B, grid3);
-    GG_DISPATCH4(N, 1, true, grid3, st, nullptr, nullptr, nullptr, B, N, inv, T, 0, nb, moves, played);
+    const WaveGrid w = boards_per_wave(cus, B);
+    launch4<1, true>(N, w.grid, s, st, nullptr, nullptr, nullptr, B, N, inv, T, 0, w.nb, moves, played);
     return (int32_t)hipGetLastError();
   }
   const int64_t npairs = (B + 1) / 2;
-  GG_DISPATCH(N, (launch_pairs(k_play_moves2<9, true>, cus, npairs, true, s, st, moves, played, B, N, inv, T)),
-              (launch_pairs(k_play_moves2<13, true>, cus, npairs, true, s, st, moves, played, B, N, inv, T)),
-              (launch_pairs(k_play_moves2<19, true>, cus, npairs, true, s, st, moves, played, B, N, inv, T)));
+  by_rows(N, [&](auto t) { launch_pairs(k_play_moves2<decltype(t)::R, true>, cus, npairs, true, s, st, moves, played, B, N, inv, T); });
   return (int32_t)hipGetLastError();
 }
 
@@ -1065,22 +948,15 @@ int32_t gg_batch_track_states(const uint8_t *states, uint32_t *tracked, int64_t 
   GG_ENTER(states);
   if (!tracked) return GG_E_NULLPTR;
   {   // big batches of full-size boards: the class-major analysis, sixteen boards per wave (as gg_batch_invalid_mask)
-    const int64_t ngroups = (B + kNB16 - 1) / kNB16;
     // (us per 65 536 / 131 072 boards, two-board kernel -> sixteen-board kernel: 19x19 48.3 -> 47.3 / 110.5 -> 102.1,
     // 13x13 39.0 -> 30.7 / 80.4 -> 62.7, 9x9 30.3 -> 22.0 / 52.6 -> 35.4; the take-over sizes are the mask's)
-    if (use_ns16(cus, B, N, 4, 2, 1)) {
-      int grid16;
-      const AgeSplit as = ns16_grid(k_track16<19>, cus, ngroups, N, 32768u, 49152u, grid16);
-      if (N == 9) k_track16<9><<<grid16, kWave, 0, s>>>(states, tracked, B, as);
-      else if (N == 13) k_track16<13><<<grid16, kWave, 0, s>>>(states, tracked, B, as);
-      else k_track16<19><<<grid16, kWave, 0, s>>>(states, tracked, B, as);
+    if (ns16_takeover(k_track16<19>, cus, B, N, 4, 2, 1, 32768u, 49152u, [&](auto t, int grid16, const AgeSplit &as) {
+          k_track16<decltype(t)::R><<<grid16, kWave, 0, s>>>(states, tracked, B, as);
+        }))
       return (int32_t)hipGetLastError();
-    }
   }
   const int64_t npairs = (B + 1) / 2;
-  GG_DISPATCH(N, (launch_pairs(k_track<9>, cus, npairs, true, s, states, tracked, B, N, inv)),
-              (launch_pairs(k_track<13>, cus, npairs, true, s, states, tracked, B, N, inv)),
-              (launch_pairs(k_track<19>, cus, npairs, true, s, states, tracked, B, N, inv)));
+  by_rows(N, [&](auto t) { launch_pairs(k_track<decltype(t)::R>, cus, npairs, true, s, states, tracked, B, N, inv); });
   return (int32_t)hipGetLastError();
 }
 
@@ -1088,9 +964,7 @@ int32_t gg_batch_untrack_states(const uint32_t *tracked, uint8_t *states, int64_
   GG_ENTER(tracked);
   if (!states) return GG_E_NULLPTR;
   const int grid = grid_for(cus, (B + 1) / 2);
-  GG_DISPATCH(N, (k_unpack<9><<<grid, kWave, 0, s>>>(tracked, states, B, N, 5)),
-              (k_unpack<13><<<grid, kWave, 0, s>>>(tracked, states, B, N, 5)),
-              (k_unpack<19><<<grid, kWave, 0, s>>>(tracked, states, B, N, 5)));
+  by_rows(N, [&](auto t) { k_unpack<decltype(t)::R><<<grid, kWave, 0, s>>>(tracked, states, B, N, 5); });
   return (int32_t)hipGetLastError();
 }
 
@@ -1106,14 +980,12 @@ int32_t gg_batch_rollout_tracked(uint32_t *tracked, uint64_t *rng, int32_t *last
     return (int32_t)hipGetLastError();
   }
   if (use_rollout5(cus, B, N, plies)) {
-    int grid5;
-    const int nb5 = boards_per_wave5(cus, B, grid5);
-    launch_rollout5(2, N, st, rng, last_actions, steps_done, B, inv, plies, auto_reset, nb5, grid5, s, nullptr);
+    const WaveGrid w5 = boards_per_wave5(cus, B);
+    launch_rollout5(2, N, st, rng, last_actions, steps_done, B, inv, plies, auto_reset, w5.nb, w5.grid, s, nullptr);
     return (int32_t)hipGetLastError();
   }
-  int grid3;
-  const int nb = boards_per_wave(cus, B, grid3);
-  launch_rollout4(2, st, rng, last_actions, steps_done, B, N, inv, plies, auto_reset, nb, grid3, s);
+  const WaveGrid w = boards_per_wave(cus, B);
+  launch_rollout4(2, st, rng, last_actions, steps_done, B, N, inv, plies, auto_reset, w.nb, w.grid, s);
   return (int32_t)hipGetLastError();
 }
 
@@ -1129,9 +1001,8 @@ int32_t gg_batch_rollout_tracked_policy(uint32_t *tracked, uint64_t *rng, int32_
   if (!rng) return GG_E_NULLPTR;
   uint8_t *st = reinterpret_cast<uint8_t *>(tracked);
   if (!use_lat(cus, B, N, plies, true) && use_rollout5(cus, B, N, plies)) {
-    int grid5;
-    const int nb5 = boards_per_wave5(cus, B, grid5);
-    launch_rollout5_policy(N, st, rng, last_actions, steps_done, B, inv, plies, auto_reset, nb5, grid5, s);
+    const WaveGrid w5 = boards_per_wave5(cus, B);
+    launch_rollout5_policy(N, st, rng, last_actions, steps_done, B, inv, plies, auto_reset, w5.nb, w5.grid, s);
     return (int32_t)hipGetLastError();
   }
   launch_rollout_lat_policy(st, rng, last_actions, steps_done, B, N, plies, auto_reset, s);
@@ -1152,9 +1023,8 @@ int32_t gg_batch_play_moves_tracked(uint32_t *tracked, const int32_t *moves, int
   GG_ENTER(tracked);
   if (T > 0 && !moves) return GG_E_NULLPTR;
   uint8_t *st = reinterpret_cast<uint8_t *>(tracked);
-  int grid3;
-  const int nb = boards_per_wave(cus, B, grid3);
-  GG_DISPATCH4(N, 2, true, grid3, st, nullptr, nullptr, nullptr, B, N, inv, T, 0, nb, moves, played);
+  const WaveGrid w = boards_per_wave(cus, B);
+  launch4<2, true>(N, w.grid, s, st, nullptr, nullptr, nullptr, B, N, inv, T, 0, w.nb, moves, played);
   return (int32_t)hipGetLastError();
 }
 
@@ -1166,8 +1036,7 @@ int32_t gg_batch_env_step_tracked(uint32_t *tracked, const int32_t *actions, uin
   GG_ENTER(tracked);
   if (!actions && !rng) return GG_E_NULLPTR;
   uint8_t *st = reinterpret_cast<uint8_t *>(tracked);
-  int grid;
-  const int nb = boards_per_wave(cus, B, grid);
+  const WaveGrid w = boards_per_wave(cus, B);
   EnvArgs env;
   env.actions = actions; env.rewards = rewards; env.dones = dones; env.status = status; env.taken = taken_actions;
   env.states_out = states_out; env.komi = komi; env.heuristic = reward_method == GG_REWARD_HEURISTIC;
@@ -1176,11 +1045,10 @@ int32_t gg_batch_env_step_tracked(uint32_t *tracked, const int32_t *actions, uin
     launch_env_step_lat(tracked, rng, steps_done, B, N, auto_reset, env, lat_w4(cus, B, N, 1), s);
     return (int32_t)hipGetLastError();
   }
-  if (actions) {
-    GG_DISPATCH4E(N, true, grid, st, nullptr, nullptr, steps_done, B, N, inv, 1, auto_reset, nb, actions, nullptr, env);
-  } else {
-    GG_DISPATCH4E(N, false, grid, st, rng, nullptr, steps_done, B, N, inv, 1, auto_reset, nb, nullptr, nullptr, env);
-  }
+  by_flag(actions != nullptr, [&](auto mv) {   // the moves given, or drawn (then from rng)
+    constexpr bool MOVES = decltype(mv)::value;
+    launch4<2, MOVES, true>(N, w.grid, s, st, MOVES ? nullptr : rng, nullptr, steps_done, B, N, inv, 1, auto_reset, w.nb, actions, nullptr, env);
+  });
   return (int32_t)hipGetLastError();
 }
 
@@ -1193,14 +1061,13 @@ int32_t gg_batch_env_step_tracked_weighted(uint32_t *tracked, const void *weight
   GG_ENTER(tracked);
   if (!weights || !rng) return GG_E_NULLPTR;
   uint8_t *st = reinterpret_cast<uint8_t *>(tracked);
-  int grid;
-  const int nb = boards_per_wave(cus, B, grid);
+  const WaveGrid w = boards_per_wave(cus, B);
   EnvArgs env = EnvArgs();
   env.rewards = rewards; env.dones = dones; env.status = status; env.taken = taken_actions;
   env.states_out = states_out; env.komi = komi; env.heuristic = reward_method == GG_REWARD_HEURISTIC;
   env.weights = weights; env.wdtype = weight_dtype;
   // the given-moves instantiation, with the move of every game drawn from its weights by the kernel itself
-  GG_DISPATCH4W(N, grid, st, rng, nullptr, steps_done, B, N, inv, 1, auto_reset, nb, nullptr, nullptr, env);
+  launch4<2, true, true, true>(N, w.grid, s, st, rng, nullptr, steps_done, B, N, inv, 1, auto_reset, w.nb, nullptr, nullptr, env);
   return (int32_t)hipGetLastError();
 }
 
@@ -1210,9 +1077,7 @@ int32_t gg_batch_sample_weighted(const uint8_t *states, const void *weights, int
   GG_ENTER(weights);
   if (!rng || !actions) return GG_E_NULLPTR;   // states may be NULL: nothing is masked
   const int grid = grid_for(cus, (B + 3) / 4);
-  GG_DISPATCH(N, (k_sample_weighted<9><<<grid, kWave, 0, s>>>(states, weights, weight_dtype, rng, actions, B, N)),
-              (k_sample_weighted<13><<<grid, kWave, 0, s>>>(states, weights, weight_dtype, rng, actions, B, N)),
-              (k_sample_weighted<19><<<grid, kWave, 0, s>>>(states, weights, weight_dtype, rng, actions, B, N)));
+  by_rows(N, [&](auto t) { k_sample_weighted<decltype(t)::R><<<grid, kWave, 0, s>>>(states, weights, weight_dtype, rng, actions, B, N); });
   return (int32_t)hipGetLastError();
 }
 
@@ -1224,9 +1089,7 @@ int32_t gg_batch_sample_weighted_rows(const uint32_t *boards, int32_t planes, co
   if (!weights || !rng || !actions) return GG_E_NULLPTR;
   const int grid = grid_for(cus, (B + 3) / 4);
   const int W = planes * N + 1;
-  GG_DISPATCH(N, (k_sample_weighted_rows<9><<<grid, kWave, 0, s>>>(boards, W, weights, weight_dtype, rng, actions, B, N)),
-              (k_sample_weighted_rows<13><<<grid, kWave, 0, s>>>(boards, W, weights, weight_dtype, rng, actions, B, N)),
-              (k_sample_weighted_rows<19><<<grid, kWave, 0, s>>>(boards, W, weights, weight_dtype, rng, actions, B, N)));
+  by_rows(N, [&](auto t) { k_sample_weighted_rows<decltype(t)::R><<<grid, kWave, 0, s>>>(boards, W, weights, weight_dtype, rng, actions, B, N); });
   return (int32_t)hipGetLastError();
 }
 
@@ -1305,11 +1168,8 @@ int32_t gg_playouts_advance(const uint32_t *roots, int64_t R, int32_t N, int32_t
                             int32_t max_plies, int32_t chunk_plies, float komi, int32_t chunks, uint32_t *slots, uint64_t *rng,
                             int64_t *plies, int64_t *job, int64_t S, int64_t *counter, int32_t *counts, int64_t *sums,
                             int32_t *ownership, void *hip_stream) {
-  PoArgs a;
-  if (int32_t e = po_args(a, 1, R, true, true, roots, R, N, K, first_root, base_seed, max_plies, chunk_plies, komi, slots, rng, plies,
-                          job, S, counter, counts, sums, ownership))
-    return e;
-  return po_advance(a, N, chunk_plies, chunks, GG_POLICY_UNIFORM, hip_stream);
+  return gg_playouts_advance_policy(roots, R, N, K, first_root, base_seed, max_plies, chunk_plies, komi, chunks, GG_POLICY_UNIFORM, slots,
+                                    rng, plies, job, S, counter, counts, sums, ownership, hip_stream);
 }
 
 int32_t gg_playouts_advance_policy(const uint32_t *roots, int64_t R, int32_t N, int32_t K, int64_t first_root, uint64_t base_seed,
@@ -1352,11 +1212,8 @@ int32_t gg_move_playouts_advance(const uint32_t *roots, int64_t R, int32_t N, co
                                  int64_t first_root, uint64_t base_seed, int32_t max_plies, int32_t chunk_plies, float komi,
                                  int32_t chunks, uint32_t *slots, uint64_t *rng, int64_t *plies, int64_t *job, int64_t S,
                                  int64_t *counter, int32_t *counts, int64_t *sums, void *hip_stream) {
-  MpArgs m;
-  if (int32_t e = mp_args(m, roots, R, N, plan, T, K, first_root, base_seed, max_plies, chunk_plies, komi, slots, rng, plies, job,
-                          S, counter, counts, sums))
-    return e;
-  return po_advance(m, N, chunk_plies, chunks, GG_POLICY_UNIFORM, hip_stream);
+  return gg_move_playouts_advance_policy(roots, R, N, plan, T, K, first_root, base_seed, max_plies, chunk_plies, komi, chunks,
+                                         GG_POLICY_UNIFORM, slots, rng, plies, job, S, counter, counts, sums, hip_stream);
 }
 
 int32_t gg_move_playouts_advance_policy(const uint32_t *roots, int64_t R, int32_t N, const int32_t *plan, int64_t T, int32_t K,
@@ -1396,10 +1253,7 @@ int32_t gg_uct_select(int64_t R, int32_t N, int32_t I, int32_t K, double c, cons
   if (int32_t e = uct_args(u, R, N, I, K, c, boards, child, links, stats, nodes, leaf, move, leaf_id, log_table)) return e;
   if (!log_table || !boards || !child || !links || !stats || !nodes || !leaf || !move || !leaf_id) return GG_E_NULLPTR;
   if (R == 0) return 0;
-  OnDeviceOf on_dev(leaf);
-  hipStream_t s = (hipStream_t)hip_stream;
-  k_uct_select<<<grid_for(on_dev.cus(), (R + 3) / 4), 4 * kWave, 0, s>>>(u);
-  return (int32_t)hipGetLastError();
+  return launch_roots(k_uct_select, leaf, R, hip_stream, u);
 }
 
 int32_t gg_uct_backup(int64_t R, int32_t N, int32_t I, int32_t K, const int32_t *counts, const int64_t *sums, int64_t *totals,
@@ -1411,10 +1265,7 @@ int32_t gg_uct_backup(int64_t R, int32_t N, int32_t I, int32_t K, const int32_t 
     return e;
   if (!counts || !sums || !boards || !links || !stats || !leaf || !move || !leaf_id) return GG_E_NULLPTR;
   if (R == 0) return 0;
-  OnDeviceOf on_dev(leaf);
-  hipStream_t s = (hipStream_t)hip_stream;
-  k_uct_backup<<<grid_for(on_dev.cus(), (R + 3) / 4), 4 * kWave, 0, s>>>(u);
-  return (int32_t)hipGetLastError();
+  return launch_roots(k_uct_backup, leaf, R, hip_stream, u);
 }
 
 int32_t gg_puct_begin(const uint32_t *roots, int64_t R, int32_t N, int32_t I, uint32_t *boards, int32_t *child, float *prior,
@@ -1443,10 +1294,7 @@ int32_t gg_puct_select(int64_t R, int32_t N, int32_t I, double c, const uint32_t
   if (int32_t e = puct_args(u, R, N, I, c, 0.f, boards, child, prior, links, stats, nodes, leaf, move, leaf_id)) return e;
   if (!boards || !child || !prior || !links || !stats || !nodes || !leaf || !move || !leaf_id) return GG_E_NULLPTR;
   if (R == 0) return 0;
-  OnDeviceOf on_dev(leaf);
-  hipStream_t s = (hipStream_t)hip_stream;
-  k_puct_select<false><<<grid_for(on_dev.cus(), (R + 3) / 4), 4 * kWave, 0, s>>>(u);
-  return (int32_t)hipGetLastError();
+  return launch_roots(k_puct_select<false>, leaf, R, hip_stream, u);
 }
 
 int32_t gg_puct_backup(int64_t R, int32_t N, int32_t I, float komi, const float *priors, const float *values, uint32_t *boards,
@@ -1457,12 +1305,7 @@ int32_t gg_puct_backup(int64_t R, int32_t N, int32_t I, float komi, const float 
     return e;
   if (!priors || !values || !boards || !prior || !links || !stats || !leaf || !move || !leaf_id) return GG_E_NULLPTR;
   if (R == 0) return 0;
-  OnDeviceOf on_dev(leaf);
-  hipStream_t s = (hipStream_t)hip_stream;
-  const int grid = grid_for(on_dev.cus(), (R + 3) / 4);
-  GG_DISPATCH(N, (k_puct_backup<9, false><<<grid, 4 * kWave, 0, s>>>(u)), (k_puct_backup<13, false><<<grid, 4 * kWave, 0, s>>>(u)),
-              (k_puct_backup<19, false><<<grid, 4 * kWave, 0, s>>>(u)));
-  return (int32_t)hipGetLastError();
+  return by_rows(N, [&](auto t) { return launch_roots(k_puct_backup<decltype(t)::R, false>, leaf, R, hip_stream, u); });
 }
 
 int32_t gg_puct_select_leaves(int64_t R, int32_t N, int32_t C, int32_t L, double c, const uint32_t *boards, int32_t *child,
@@ -1472,10 +1315,7 @@ int32_t gg_puct_select_leaves(int64_t R, int32_t N, int32_t C, int32_t L, double
   if (int32_t e = puct_leaves_args(u, R, N, C, L, c, 0.f, boards, child, prior, links, stats, nodes, leaf, move, leaf_id)) return e;
   if (!boards || !child || !prior || !links || !stats || !nodes || !leaf || !move || !leaf_id) return GG_E_NULLPTR;
   if (R == 0) return 0;
-  OnDeviceOf on_dev(leaf);
-  hipStream_t s = (hipStream_t)hip_stream;
-  k_puct_select<true><<<grid_for(on_dev.cus(), (R + 3) / 4), 4 * kWave, 0, s>>>(u);
-  return (int32_t)hipGetLastError();
+  return launch_roots(k_puct_select<true>, leaf, R, hip_stream, u);
 }
 
 int32_t gg_puct_backup_leaves(int64_t R, int32_t N, int32_t C, int32_t L, float komi, const float *priors, const float *values,
@@ -1487,12 +1327,7 @@ int32_t gg_puct_backup_leaves(int64_t R, int32_t N, int32_t C, int32_t L, float 
     return e;
   if (!priors || !values || !boards || !prior || !links || !stats || !leaf || !move || !leaf_id) return GG_E_NULLPTR;
   if (R == 0) return 0;
-  OnDeviceOf on_dev(leaf);
-  hipStream_t s = (hipStream_t)hip_stream;
-  const int grid = grid_for(on_dev.cus(), (R + 3) / 4);
-  GG_DISPATCH(N, (k_puct_backup<9, true><<<grid, 4 * kWave, 0, s>>>(u)), (k_puct_backup<13, true><<<grid, 4 * kWave, 0, s>>>(u)),
-              (k_puct_backup<19, true><<<grid, 4 * kWave, 0, s>>>(u)));
-  return (int32_t)hipGetLastError();
+  return by_rows(N, [&](auto t) { return launch_roots(k_puct_backup<decltype(t)::R, true>, leaf, R, hip_stream, u); });
 }
 
 int32_t gg_puct_legal(const uint32_t *leaf, const int32_t *leaf_id, int64_t B, int32_t N, uint8_t *legal, uint8_t *live,
@@ -1518,10 +1353,7 @@ int32_t gg_puct_advance(const int32_t *actions, const uint32_t *next, int64_t R,
   u.next = next;
   u.remap = remap;
   u.kept = kept;   // (may be NULL)
-  OnDeviceOf on_dev(boards);
-  hipStream_t s = (hipStream_t)hip_stream;
-  k_puct_advance<<<grid_for(on_dev.cus(), (R + 3) / 4), 4 * kWave, 0, s>>>(u);
-  return (int32_t)hipGetLastError();
+  return launch_roots(k_puct_advance, boards, R, hip_stream, u);
 }
 
 int32_t gg_puct_root_noise(int64_t R, int32_t N, int32_t C, float eps, const float *noise, uint8_t *todo, const uint32_t *boards,
@@ -1536,10 +1368,7 @@ int32_t gg_puct_root_noise(int64_t R, int32_t N, int32_t C, float eps, const flo
   u.noise = noise;
   u.todo = todo;
   u.eps = eps;
-  OnDeviceOf on_dev(boards);
-  hipStream_t s = (hipStream_t)hip_stream;
-  k_puct_root_noise<<<grid_for(on_dev.cus(), (R + 3) / 4), 4 * kWave, 0, s>>>(u);
-  return (int32_t)hipGetLastError();
+  return launch_roots(k_puct_root_noise, boards, R, hip_stream, u);
 }
 
 int32_t gg_puct_root_policy(int64_t R, int32_t N, int32_t C, const uint8_t *sample, uint64_t *rng, const uint32_t *boards,
@@ -1556,10 +1385,7 @@ int32_t gg_puct_root_policy(int64_t R, int32_t N, int32_t C, const uint8_t *samp
   u.actions = actions;
   u.pi = pi;           // (may be NULL)
   u.value = value;     // (may be NULL)
-  OnDeviceOf on_dev(boards);
-  hipStream_t s = (hipStream_t)hip_stream;
-  k_puct_root_policy<<<grid_for(on_dev.cus(), (R + 3) / 4), 4 * kWave, 0, s>>>(u);
-  return (int32_t)hipGetLastError();
+  return launch_roots(k_puct_root_policy, boards, R, hip_stream, u);
 }
 
 }  // extern "C"

@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 #include "gg_common.h"
+#include "gg_host.h"
 #include "gg_v2.h"
 #include "gg_lat.h"
 
@@ -16,79 +17,54 @@ namespace gg {
 // gg_batch_rollout on a batch that leaves the SIMDs under-filled (gg_kernels.hip: use_lat): one single-wave workgroup per
 // four 9x9 / 13x13 boards or two 19x19 boards.
 // io: 0 byte planes, 2 tracked boards (`st` is the batch in that format)
-#define GG_LAT(R, F)                                                                                                            \
-  do {                                                                                                                          \
-    const unsigned grid_ = (unsigned)((B + Lat<R>::NBW - 1) / Lat<R>::NBW);                                                     \
-    const unsigned grid4_ = (grid_ + 3u) / 4u;                                                                                  \
-    if (io == 0) {                                                                                                              \
-      if (auto_reset) k_rollout_lat<R, F, true, 0><<<grid_, kWave, 0, s>>>(st, rng, last_actions, steps_done, B, N, plies, 1);  \
-      else k_rollout_lat<R, F, false, 0><<<grid_, kWave, 0, s>>>(st, rng, last_actions, steps_done, B, N, plies, 0);            \
-    } else if (w4 && plies <= 2) {                                                                                              \
-      if (auto_reset) k_rollout_lat_w4<R, F, true, true><<<grid4_, 4 * kWave, 0, s>>>(st, rng, last_actions, steps_done, B, N, plies, 1); \
-      else k_rollout_lat_w4<R, F, false, true><<<grid4_, 4 * kWave, 0, s>>>(st, rng, last_actions, steps_done, B, N, plies, 0); \
-    } else if (w4) {                                                                                                            \
-      if (auto_reset) k_rollout_lat_w4<R, F, true, false><<<grid4_, 4 * kWave, 0, s>>>(st, rng, last_actions, steps_done, B, N, plies, 1); \
-      else k_rollout_lat_w4<R, F, false, false><<<grid4_, 4 * kWave, 0, s>>>(st, rng, last_actions, steps_done, B, N, plies, 0); \
-    } else if (plies <= 2) {                                                                                                    \
-      if (auto_reset) k_rollout_lat<R, F, true, 2, true><<<grid_, kWave, 0, s>>>(st, rng, last_actions, steps_done, B, N, plies, 1); \
-      else k_rollout_lat<R, F, false, 2, true><<<grid_, kWave, 0, s>>>(st, rng, last_actions, steps_done, B, N, plies, 0);      \
-    } else {                                                                                                                    \
-      if (auto_reset) k_rollout_lat<R, F, true, 2><<<grid_, kWave, 0, s>>>(st, rng, last_actions, steps_done, B, N, plies, 1);  \
-      else k_rollout_lat<R, F, false, 2><<<grid_, kWave, 0, s>>>(st, rng, last_actions, steps_done, B, N, plies, 0);            \
-    }                                                                                                                           \
-  } while (0)
 // w4 (tracked boards only): four waves per workgroup (k_rollout_lat_w4: short launches of few workgroups)
 void launch_rollout_lat(int io, uint8_t *st, uint64_t *rng, int32_t *last_actions, int64_t *steps_done, int64_t B, int32_t N, int plies,
                         int auto_reset, bool w4, hipStream_t s) {
-  if (N == 9) GG_LAT(9, true);
-  else if (N < 9) GG_LAT(9, false);
-  else if (N == 13) GG_LAT(13, true);
-  else if (N < 13) GG_LAT(13, false);
-  else if (N == 19) GG_LAT(19, true);
-  else GG_LAT(19, false);
+  by_size(N, [&](auto t) {
+    by_flag(auto_reset != 0, [&](auto ar) {
+      constexpr int R = decltype(t)::R;
+      constexpr bool F = decltype(t)::FULL, AR = decltype(ar)::value;
+      const unsigned grid = (unsigned)((B + Lat<R>::NBW - 1) / Lat<R>::NBW), grid4 = (grid + 3u) / 4u;
+      if (io == 0) {
+        k_rollout_lat<R, F, AR, 0><<<grid, kWave, 0, s>>>(st, rng, last_actions, steps_done, B, N, plies, (int)AR);
+        return;
+      }
+      by_flag(plies <= 2, [&](auto sh) {   // tracked boards: the one- and two-ply form
+        constexpr bool SHORT = decltype(sh)::value;
+        if (w4) k_rollout_lat_w4<R, F, AR, SHORT><<<grid4, 4 * kWave, 0, s>>>(st, rng, last_actions, steps_done, B, N, plies, (int)AR);
+        else k_rollout_lat<R, F, AR, 2, SHORT><<<grid, kWave, 0, s>>>(st, rng, last_actions, steps_done, B, N, plies, (int)AR);
+      });
+    });
+  });
 }
-#undef GG_LAT
 
 // gg_batch_rollout_tracked_policy (policy != uniform): the plain tracked form with the policy in its draw, whatever the launch
 // length and the batch size (one wave per four / two boards)
-#define GG_LATP(R, F)                                                                                                           \
-  do {                                                                                                                          \
-    const unsigned grid_ = (unsigned)((B + Lat<R>::NBW - 1) / Lat<R>::NBW);                                                     \
-    if (auto_reset) k_rollout_lat_pol<R, F, true, kPolNoEyeFill><<<grid_, kWave, 0, s>>>(st, rng, last_actions, steps_done, B, N, plies, 1); \
-    else k_rollout_lat_pol<R, F, false, kPolNoEyeFill><<<grid_, kWave, 0, s>>>(st, rng, last_actions, steps_done, B, N, plies, 0); \
-  } while (0)
 void launch_rollout_lat_policy(uint8_t *st, uint64_t *rng, int32_t *last_actions, int64_t *steps_done, int64_t B, int32_t N, int plies,
                                int auto_reset, hipStream_t s) {
-  if (N == 9) GG_LATP(9, true);
-  else if (N < 9) GG_LATP(9, false);
-  else if (N == 13) GG_LATP(13, true);
-  else if (N < 13) GG_LATP(13, false);
-  else if (N == 19) GG_LATP(19, true);
-  else GG_LATP(19, false);
+  by_size(N, [&](auto t) {
+    by_flag(auto_reset != 0, [&](auto ar) {
+      constexpr int R = decltype(t)::R;
+      constexpr bool AR = decltype(ar)::value;
+      const unsigned grid = (unsigned)((B + Lat<R>::NBW - 1) / Lat<R>::NBW);
+      k_rollout_lat_pol<R, decltype(t)::FULL, AR, kPolNoEyeFill><<<grid, kWave, 0, s>>>(st, rng, last_actions, steps_done, B, N, plies, (int)AR);
+    });
+  });
 }
-#undef GG_LATP
 
 // gg_batch_env_step_tracked on a batch that leaves the SIMDs under-filled: the same one-ply kernel with GoEnv.step's outputs
-#define GG_LATE(R, F)                                                                                                          \
-  do {                                                                                                                         \
-    const unsigned grid_ = (unsigned)((B + Lat<R>::NBW - 1) / Lat<R>::NBW);                                                    \
-    const unsigned grid4_ = (grid_ + 3u) / 4u;                                                                                 \
-    if (w4) {                                                                                                                  \
-      if (env.actions) k_env_step_lat_w4<R, F, true><<<grid4_, 4 * kWave, 0, s>>>(tracked, rng, steps_done, B, N, auto_reset, env); \
-      else k_env_step_lat_w4<R, F, false><<<grid4_, 4 * kWave, 0, s>>>(tracked, rng, steps_done, B, N, auto_reset, env);       \
-    } else if (env.actions) k_env_step_lat<R, F, true><<<grid_, kWave, 0, s>>>(tracked, rng, steps_done, B, N, auto_reset, env); \
-    else k_env_step_lat<R, F, false><<<grid_, kWave, 0, s>>>(tracked, rng, steps_done, B, N, auto_reset, env);                 \
-  } while (0)
 void launch_env_step_lat(uint32_t *tracked, uint64_t *rng, int64_t *steps_done, int64_t B, int32_t N, int auto_reset,
                          const EnvArgs &env, bool w4, hipStream_t s) {
-  if (N == 9) GG_LATE(9, true);
-  else if (N < 9) GG_LATE(9, false);
-  else if (N == 13) GG_LATE(13, true);
-  else if (N < 13) GG_LATE(13, false);
-  else if (N == 19) GG_LATE(19, true);
-  else GG_LATE(19, false);
+  by_size(N, [&](auto t) {
+    by_flag(env.actions != nullptr, [&](auto mv) {
+      constexpr int R = decltype(t)::R;
+      constexpr bool F = decltype(t)::FULL, MOVES = decltype(mv)::value;
+      const unsigned grid = (unsigned)((B + Lat<R>::NBW - 1) / Lat<R>::NBW), grid4 = (grid + 3u) / 4u;
+      if (w4) k_env_step_lat_w4<R, F, MOVES><<<grid4, 4 * kWave, 0, s>>>(tracked, rng, steps_done, B, N, auto_reset, env);
+      else k_env_step_lat<R, F, MOVES><<<grid, kWave, 0, s>>>(tracked, rng, steps_done, B, N, auto_reset, env);
+    });
+  });
 }
-#undef GG_LATE
 
 }  // namespace gg
 

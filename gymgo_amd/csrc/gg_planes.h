@@ -286,9 +286,7 @@ int32_t plane_launch(const K &k, bool tracked, const void *in, const void *out, 
   OnDeviceOf on_dev(in);
   const int cus = on_dev.cus();
   hipStream_t s = (hipStream_t)hip_stream;
-  if (N <= 9) plane_launch_r<9>(k, tracked, cus, B, s, esh, kTypes[dtype].one);
-  else if (N <= 13) plane_launch_r<13>(k, tracked, cus, B, s, esh, kTypes[dtype].one);
-  else plane_launch_r<19>(k, tracked, cus, B, s, esh, kTypes[dtype].one);
+  by_rows(N, [&](auto t) { plane_launch_r<decltype(t)::R>(k, tracked, cus, B, s, esh, kTypes[dtype].one); });
   return (int32_t)hipGetLastError();
 }
 

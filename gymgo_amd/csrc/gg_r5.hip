@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "gg_common.h"
+#include "gg_host.h"
 #include "gg_v2.h"
 #include "gg_v4.h"
 #include "gg_v5.h"
@@ -14,27 +15,33 @@
 
 namespace gg {
 
-// full-size 19x19 boards, byte planes (io 0) or tracked boards (io 2)
+// k_rollout5 exists for boards that fill their rows and is reached at those sizes only (gg_kernels.hip: use_rollout5)
+template <class F>
+static void by_full_size(int N, F &&f) {
+  if (N == 19) f(SizeTag<19, true>{});
+  else if (N == 13) f(SizeTag<13, true>{});
+  else f(SizeTag<9, true>{});
+}
+
+// 9x9, 13x13 or 19x19 boards, byte planes (io 0) or tracked boards (io 2)
 // ws (byte planes only, nullable): the caller's workspace of gg_batch_rollout_ws, uint32 [B][5 N + 1]
 void launch_rollout5(int io, int N, uint8_t *st, uint64_t *rng, int32_t *last_actions, int64_t *steps_done, int64_t B, uint32_t inv,
                      int plies, int auto_reset, int nb, int grid, hipStream_t s, uint32_t *ws) {
-#define GG_R5(R)                                                                                                                  \
-  do {                                                                                                                            \
-    if (io == 0) k_rollout5<R, 0><<<grid, kWave, 0, s>>>(st, rng, last_actions, steps_done, B, inv, plies, auto_reset, nb, ws);   \
-    else k_rollout5<R, 2><<<grid, kWave, 0, s>>>(st, rng, last_actions, steps_done, B, inv, plies, auto_reset, nb, nullptr);      \
-  } while (0)
-  if (N == 19) GG_R5(19);
-  else if (N == 13) GG_R5(13);
-  else GG_R5(9);
-#undef GG_R5
+  by_full_size(N, [&](auto t) {
+    by_flag(io == 0, [&](auto planes) {
+      constexpr int IO = decltype(planes)::value ? 0 : 2;
+      k_rollout5<decltype(t)::R, IO><<<grid, kWave, 0, s>>>(st, rng, last_actions, steps_done, B, inv, plies, auto_reset, nb,
+                                                          IO == 0 ? ws : nullptr);
+    });
+  });
 }
 
 // gg_batch_rollout_tracked_policy (policy != uniform) on a full machine: tracked boards, the policy in the draw of phase 1
 void launch_rollout5_policy(int N, uint8_t *st, uint64_t *rng, int32_t *last_actions, int64_t *steps_done, int64_t B, uint32_t inv,
                             int plies, int auto_reset, int nb, int grid, hipStream_t s) {
-  if (N == 19) k_rollout5_pol<19, 2><<<grid, kWave, 0, s>>>(st, rng, last_actions, steps_done, B, inv, plies, auto_reset, nb, nullptr);
-  else if (N == 13) k_rollout5_pol<13, 2><<<grid, kWave, 0, s>>>(st, rng, last_actions, steps_done, B, inv, plies, auto_reset, nb, nullptr);
-  else k_rollout5_pol<9, 2><<<grid, kWave, 0, s>>>(st, rng, last_actions, steps_done, B, inv, plies, auto_reset, nb, nullptr);
+  by_full_size(N, [&](auto t) {
+    k_rollout5_pol<decltype(t)::R, 2><<<grid, kWave, 0, s>>>(st, rng, last_actions, steps_done, B, inv, plies, auto_reset, nb, nullptr);
+  });
 }
 
 }  // namespace gg

@@ -2,7 +2,7 @@
 ply as a compacted job list) against the pinned C oracle - states, generator states, last actions, step counters.
 
 gg_batch_rollout / gg_batch_rollout_tracked hand full-size 19x19 launches of >= 8 plies to it above 128 games per CU
-(gg_kernels.hip: use_rollout5; 9x9 and 13x13: from 160 games per CU), i.e. from 32 769 games on the whole device: the BASELINE config-3 test (test_gpu_configs.py) and the
+(gg_kernels.hip: use_rollout5; 9x9 and 13x13: above 159 games per CU), i.e. from 32 769 games on the whole device: the BASELINE config-3 test (test_gpu_configs.py) and the
 bench's own driver (test_gpu_deep.py) run it at that size.  Here the library is sized for FOUR compute units
 (GYMGO_AMD_CUS=4, read once per process: a process of its own), so that 513 games take the kernel and the oracle can replay
 whole games: both sides of the games / plies take-over, ragged last waves (a wave of 2 .. 32 boards), frozen games, resets, and a
@@ -58,10 +58,13 @@ def run(states, B, launches, auto_reset, seed, tracked):
 ''' % ROOT
 
 SMALL = PRELUDE + r'''
-# 9x9 / 13x13 on 4 CUs: the kernel takes launches of >= 8 plies from 640 games on (160 per CU); below that and for shorter launches
-# the one-row-per-lane and sixteen-board kernels serve the call
+# 9x9 / 13x13: the kernel takes launches of >= 8 plies with MORE than 159 games per CU (use_rollout5: B > cus (5 kNB5 - 1)), on 4 CUs
+# from 637 games on; up to 636 and for shorter launches the one-row-per-lane and sixteen-board kernels serve the call
+PER_CU = 159
+EDGE = PER_CU * _lib.lib().gg_device_cus()     # the last batch size the kernel does NOT take: 636
+assert EDGE == 636
 for N in (9, 13):
-    for B in (639, 640, 641, 700, 1025, 2049):
+    for B in (EDGE, EDGE + 1, EDGE + 2, 700, 1025, 2049):
         empty = np.zeros((B, 6, N, N), np.uint8)
         for tracked in (False, True):
             run(empty, B, (7, 8, 9, 60, 200), True, 300 + B + N, tracked)
