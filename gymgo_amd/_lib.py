@@ -1,9 +1,12 @@
 """ctypes loader of the in-tree HIP library (gymgo_amd/libgymgo_amd.so) + tensor plumbing.
 
 There is NO CPU fallback: if the shared library is missing, or a tensor is not a contiguous
-uint8/int32 ROCm device tensor, the call raises.  PyTorch is used only for device memory and the
-current HIP stream; every entry point of include/gymgo_amd.h is bound here with plain pointers.
+ROCm device tensor of the dtype its parameter takes, the call raises.  PyTorch is used only for device
+memory and the current HIP stream; every entry point of include/gymgo_amd.h is bound here with plain
+pointers, from ONE table (ABI) that tests/test_host_abi.py holds against the header, and reached through
+call().  A new entry point is one declaration in the header and one entry in the table.
 """
+import collections
 import ctypes
 import os
 import threading
@@ -14,103 +17,145 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libgymgo_amd.so')   # always the in-tree build: no override, no search path
 ABI_VERSION = 5                                      # GG_ABI_VERSION of include/gymgo_amd.h
 
-EXPORTS = (
-    'gg_version', 'gg_device_cus', 'gg_batch_next_states', 'gg_batch_next_states_ws', 'gg_batch_invalid_mask', 'gg_batch_areas',
-    'gg_batch_children', 'gg_batch_children_offsets', 'gg_batch_children_compact', 'gg_batch_rollout', 'gg_batch_env_step', 'gg_batch_sample_actions', 'gg_batch_update_pieces', 'gg_batch_reset_finished', 'gg_packed_words', 'gg_batch_pack_states',
-    'gg_batch_unpack_states', 'gg_batch_next_states_packed', 'gg_batch_rollout_packed', 'gg_batch_env_step_packed',
-    'gg_batch_children_packed', 'gg_batch_play_moves', 'gg_batch_play_moves_packed', 'gg_tracked_words', 'gg_batch_track_states',
-    'gg_batch_untrack_states', 'gg_batch_rollout_tracked', 'gg_batch_play_moves_tracked', 'gg_batch_env_step_tracked',
-    'gg_rng_seed', 'gg_batch_env_step_tracked_weighted', 'gg_batch_sample_weighted', 'gg_batch_sample_weighted_rows',
-    'gg_batch_symmetry', 'gg_batch_symmetry_rows', 'gg_batch_env_step_scored', 'gg_playouts_begin', 'gg_playouts_advance',
-    'gg_move_playouts_plan', 'gg_move_playouts_begin', 'gg_move_playouts_advance', 'gg_uct_begin', 'gg_uct_select',
-    'gg_uct_backup', 'gg_batch_eye_mask', 'gg_batch_rollout_tracked_policy', 'gg_playouts_advance_policy',
-    'gg_move_playouts_advance_policy', 'gg_puct_begin', 'gg_puct_select', 'gg_puct_backup',
-    'gg_puct_select_leaves', 'gg_puct_backup_leaves', 'gg_puct_legal', 'gg_puct_advance', 'gg_batch_rollout_ws',
-    'gg_puct_root_noise', 'gg_puct_root_policy', 'gg_feature_planes', 'gg_batch_group_liberties', 'gg_batch_features',
-    'gg_batch_features_tracked', 'gg_batch_features_oriented', 'gg_batch_features_tracked_oriented', 'gg_batch_symmetry_policy',
-    'gg_batch_draw_orient', 'gg_life_planes', 'gg_batch_life', 'gg_batch_life_tracked', 'gg_batch_ladder',
-    'gg_batch_ladder_tracked',
-)
+Param = collections.namedtuple('Param', 'name kind')
+Param.__doc__ = """One parameter of an entry point, under the name include/gymgo_amd.h gives it.  kind: the ctypes type of a scalar
+(c_void_p for hip_stream), or - a pointer to device memory - the torch dtype a tensor passed there must have, or a tuple of
+them where the header says `void *` / `uint8_t *` and the entry point takes several."""
 
-_vp, _i64, _i32, _u64 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_uint64
-_SIGNATURES = {
-    'gg_version': ([], _i32),
-    'gg_device_cus': ([], _i32),
-    'gg_batch_next_states': ([_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp], _i32),
-    'gg_batch_next_states_ws': ([_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp], _i32),
-    'gg_batch_invalid_mask': ([_vp, _vp, _vp, _i64, _i32, _vp], _i32),
-    'gg_batch_areas': ([_vp, _vp, _vp, _i64, _i32, _vp], _i32),
-    'gg_batch_children': ([_vp, _vp, _i64, _i32, _i32, _vp], _i32),
-    'gg_batch_children_offsets': ([_vp, _vp, _vp, _i64, _i32, _vp], _i32),
-    'gg_batch_children_compact': ([_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp], _i32),
-    'gg_batch_rollout': ([_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp], _i32),
-    'gg_batch_rollout_ws': ([_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp], _i32),
-    'gg_batch_env_step': ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, ctypes.c_float, _i32, _i32, _vp], _i32),
-    'gg_batch_env_step_scored': ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, ctypes.c_float, _i32, _i32, _vp], _i32),
-    'gg_batch_sample_actions': ([_vp, _vp, _vp, _i64, _i32, _vp], _i32),
-    'gg_batch_update_pieces': ([_vp, _vp, _i32, _vp, _vp, _i64, _i32, _vp], _i32),
-    'gg_batch_reset_finished': ([_vp, _i64, _i32, _vp], _i32),
-    'gg_packed_words': ([_i32], _i32),
-    'gg_batch_pack_states': ([_vp, _vp, _i64, _i32, _vp], _i32),
-    'gg_batch_unpack_states': ([_vp, _vp, _i64, _i32, _vp], _i32),
-    'gg_batch_next_states_packed': ([_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp], _i32),
-    'gg_batch_rollout_packed': ([_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp], _i32),
-    'gg_batch_env_step_packed': ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, ctypes.c_float, _i32, _i32, _vp], _i32),
-    'gg_batch_children_packed': ([_vp, _vp, _i64, _i32, _i32, _vp], _i32),
-    'gg_batch_play_moves': ([_vp, _vp, _vp, _i64, _i32, _i32, _vp], _i32),
-    'gg_batch_play_moves_packed': ([_vp, _vp, _vp, _i64, _i32, _i32, _vp], _i32),
-    'gg_tracked_words': ([_i32], _i32),
-    'gg_batch_track_states': ([_vp, _vp, _i64, _i32, _vp], _i32),
-    'gg_batch_untrack_states': ([_vp, _vp, _i64, _i32, _vp], _i32),
-    'gg_batch_rollout_tracked': ([_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp], _i32),
-    'gg_batch_play_moves_tracked': ([_vp, _vp, _vp, _i64, _i32, _i32, _vp], _i32),
-    'gg_batch_env_step_tracked': ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, ctypes.c_float, _i32, _i32, _vp], _i32),
-    'gg_rng_seed': ([_vp, _u64, _i64, _i64, _vp], _i32),
-    'gg_batch_env_step_tracked_weighted': ([_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, ctypes.c_float, _i32, _i32, _vp], _i32),
-    'gg_batch_sample_weighted': ([_vp, _vp, _i32, _vp, _vp, _i64, _i32, _vp], _i32),
-    'gg_batch_sample_weighted_rows': ([_vp, _i32, _vp, _i32, _vp, _vp, _i64, _i32, _vp], _i32),
-    'gg_batch_symmetry': ([_vp, _vp, _vp, _i64, _i32, _i32, _vp], _i32),
-    'gg_batch_symmetry_rows': ([_vp, _i32, _vp, _vp, _i64, _i32, _vp], _i32),
-    'gg_playouts_begin': ([_vp, _i64, _i32, _i32, _i64, _u64, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp], _i32),
-    'gg_playouts_advance': ([_vp, _i64, _i32, _i32, _i64, _u64, _i32, _i32, ctypes.c_float, _i32, _vp, _vp, _vp, _vp, _i64, _vp,
-                             _vp, _vp, _vp, _vp], _i32),
-    'gg_move_playouts_plan': ([_vp, _i64, _i32, _vp, _vp, _vp], _i32),
-    'gg_move_playouts_begin': ([_vp, _i64, _i32, _vp, _i64, _i32, _i64, _u64, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp,
-                                _vp, _vp], _i32),
-    'gg_move_playouts_advance': ([_vp, _i64, _i32, _vp, _i64, _i32, _i64, _u64, _i32, _i32, ctypes.c_float, _i32, _vp, _vp, _vp,
-                                  _vp, _i64, _vp, _vp, _vp, _vp], _i32),
-    'gg_uct_begin': ([_vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
-    'gg_uct_select': ([_i64, _i32, _i32, _i32, ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
-    'gg_uct_backup': ([_i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
-    'gg_batch_eye_mask': ([_vp, _vp, _i64, _i32, _vp], _i32),
-    'gg_batch_rollout_tracked_policy': ([_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp], _i32),
-    'gg_playouts_advance_policy': ([_vp, _i64, _i32, _i32, _i64, _u64, _i32, _i32, ctypes.c_float, _i32, _i32, _vp, _vp, _vp, _vp,
-                                    _i64, _vp, _vp, _vp, _vp, _vp], _i32),
-    'gg_move_playouts_advance_policy': ([_vp, _i64, _i32, _vp, _i64, _i32, _i64, _u64, _i32, _i32, ctypes.c_float, _i32, _i32, _vp,
-                                         _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp], _i32),
-    'gg_puct_begin': ([_vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
-    'gg_puct_select': ([_i64, _i32, _i32, ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
-    'gg_puct_backup': ([_i64, _i32, _i32, ctypes.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
-    'gg_puct_select_leaves': ([_i64, _i32, _i32, _i32, ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
-    'gg_puct_backup_leaves': ([_i64, _i32, _i32, _i32, ctypes.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
-    'gg_puct_legal': ([_vp, _vp, _i64, _i32, _vp, _vp, _vp], _i32),
-    'gg_puct_advance': ([_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
-    'gg_puct_root_noise': ([_i64, _i32, _i32, ctypes.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
-    'gg_puct_root_policy': ([_i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
-    'gg_feature_planes': ([], _i32),
-    'gg_batch_group_liberties': ([_vp, _vp, _i64, _i32, _vp], _i32),
-    'gg_batch_features': ([_vp, _vp, _i32, _i64, _i32, _vp], _i32),
-    'gg_batch_features_tracked': ([_vp, _vp, _i32, _i64, _i32, _vp], _i32),
-    'gg_batch_features_oriented': ([_vp, _vp, _vp, _i32, _i64, _i32, _vp], _i32),
-    'gg_batch_features_tracked_oriented': ([_vp, _vp, _vp, _i32, _i64, _i32, _vp], _i32),
-    'gg_batch_symmetry_policy': ([_vp, _vp, _vp, _i32, _i32, _i64, _i32, _vp], _i32),
-    'gg_batch_draw_orient': ([_vp, _vp, _i64, _vp], _i32),
-    'gg_life_planes': ([], _i32),
-    'gg_batch_life': ([_vp, _vp, _vp, _vp, _i32, _i64, _i32, _vp], _i32),
-    'gg_batch_life_tracked': ([_vp, _vp, _vp, _vp, _i32, _i64, _i32, _vp], _i32),
-    'gg_batch_ladder': ([_vp, _vp, _vp, _vp, _i32, _i64, _i32, _vp], _i32),
-    'gg_batch_ladder_tracked': ([_vp, _vp, _vp, _vp, _i32, _i64, _i32, _vp], _i32),
+_vp, _i32, _i64, _u64, _f32, _f64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_float, ctypes.c_double
+_U8, _I32, _I64, _F32 = torch.uint8, torch.int32, torch.int64, torch.float32     # uint32_t * / uint64_t * are int32 / int64 tensors
+_PLANES = (torch.float32, torch.bfloat16, torch.float16, torch.uint8)           # GG_W_* / GG_FEAT_U8 outputs
+_WEIGHTS = (torch.float32, torch.bfloat16, torch.float16)                       # GG_W_*
+_ROWS = (torch.bool, torch.uint8, torch.float16, torch.bfloat16, torch.float32, torch.int32)   # elem_size 1, 2, 4
+_FLAGS = (torch.bool, torch.uint8)
+
+
+def _params(kind, *names):
+    return tuple(Param(n, kind) for n in names)
+
+
+# parameter runs that several entry points share, as the header spells them
+_STREAM = _params(_vp, 'hip_stream')
+_BN = _params(_i64, 'B') + _params(_i32, 'N') + _STREAM
+_BNC = _params(_i64, 'B') + _params(_i32, 'N', 'canonical') + _STREAM
+_BNT = _params(_i64, 'B') + _params(_i32, 'N', 'T') + _STREAM
+_ROLL = _params(_I64, 'rng') + _params(_I32, 'last_actions') + _params(_I64, 'steps_done')
+_PLIES = _params(_i64, 'B') + _params(_i32, 'N', 'plies', 'auto_reset')
+_STEP = (_params(_I32, 'actions') + _params(_I64, 'rng') + _params(_F32, 'rewards') + _params(_U8, 'dones')
+         + _params(_I32, 'status', 'taken_actions'))
+_REWARD = _params(_i64, 'B') + _params(_i32, 'N') + _params(_f32, 'komi') + _params(_i32, 'reward_method', 'auto_reset') + _STREAM
+_OUT = _params(_PLANES, 'out')
+_OUT_BN = _params(_i32, 'out_dtype') + _BN
+_WEIGHTED = _params(_WEIGHTS, 'weights') + _params(_i32, 'weight_dtype')
+_JOBS = (_params(_i64, 'R') + _params(_i32, 'N', 'K') + _params(_i64, 'first_root') + _params(_u64, 'base_seed')
+         + _params(_i32, 'max_plies', 'chunk_plies'))
+_MOVE_JOBS = (_params(_i64, 'R') + _params(_i32, 'N') + _params(_I32, 'plan') + _params(_i64, 'T') + _params(_i32, 'K')
+              + _params(_i64, 'first_root') + _params(_u64, 'base_seed') + _params(_i32, 'max_plies', 'chunk_plies'))
+_CHUNKS = _params(_f32, 'komi') + _params(_i32, 'chunks')
+_QUEUE = (_params(_I32, 'slots') + _params(_I64, 'rng', 'plies', 'job') + _params(_i64, 'S') + _params(_I64, 'counter')
+          + _params(_I32, 'counts') + _params(_I64, 'sums'))
+_OWN = _params(_I32, 'ownership') + _STREAM
+_LEAF = _params(_I32, 'leaf', 'move', 'leaf_id') + _STREAM
+_RNI = _params(_i64, 'R') + _params(_i32, 'N', 'I')
+_RNC = _params(_i64, 'R') + _params(_i32, 'N', 'C')
+_PUCT_TREE = (_params(_I32, 'boards', 'child') + _params(_F32, 'prior') + _params(_I32, 'links', 'stats', 'nodes'))   # gg_puct_stat: 4 words
+_PUCT_BACK = (_params(_f32, 'komi') + _params(_F32, 'priors', 'values') + _params(_I32, 'boards') + _params(_F32, 'prior')
+              + _params(_I32, 'links', 'stats') + _LEAF)
+
+# THE description of the C ABI on the Python side: one entry per function of include/gymgo_amd.h, in header order, one Param
+# per parameter.  EXPORTS, the ctypes argtypes lib() sets and the marshalling of call() all come from here.
+ABI = {
+    'gg_version': (),
+    'gg_device_cus': (),
+    'gg_batch_next_states': _params(_U8, 'in') + _params(_I32, 'actions') + _params(_U8, 'out') + _params(_I32, 'status') + _BNC,
+    'gg_batch_next_states_ws': (_params(_U8, 'in') + _params(_I32, 'actions') + _params(_U8, 'out')
+                                + _params(_I32, 'status', 'workspace') + _BNC),
+    'gg_batch_invalid_mask': _params(_U8, 'states') + _params(_I32, 'ko') + _params(_U8, 'mask') + _BN,
+    'gg_batch_areas': _params(_U8, 'states') + _params(_I32, 'black', 'white') + _BN,
+    'gg_batch_children': _params(_U8, 'states', 'children') + _BNC,
+    'gg_batch_children_offsets': _params(_U8, 'states') + _params(_I32, 'offsets', 'order') + _BN,
+    'gg_batch_children_compact': _params(_U8, 'states') + _params(_I32, 'offsets', 'order') + _params(_U8, 'children') + _BNC,
+    'gg_batch_rollout': _params(_U8, 'states') + _ROLL + _PLIES + _STREAM,
+    'gg_batch_rollout_ws': _params(_U8, 'states') + _ROLL + _params(_I32, 'workspace') + _PLIES + _STREAM,
+    'gg_batch_env_step': _params(_U8, 'states') + _STEP + _REWARD,
+    'gg_batch_env_step_scored': _params(_U8, 'states') + _STEP + _params(_I32, 'areas') + _REWARD,
+    'gg_batch_sample_actions': _params(_U8, 'states') + _params(_I64, 'rng') + _params(_I32, 'actions') + _BN,
+    'gg_batch_update_pieces': (_params(_U8, 'states') + _params(_I32, 'adj') + _params(_i32, 'K') + _params(_I32, 'players')
+                               + _params(_U8, 'killed') + _BN),
+    'gg_batch_reset_finished': _params(_U8, 'states') + _BN,
+    'gg_packed_words': _params(_i32, 'N'),
+    'gg_batch_pack_states': _params(_U8, 'states') + _params(_I32, 'packed') + _BN,
+    'gg_batch_unpack_states': _params(_I32, 'packed') + _params(_U8, 'states') + _BN,
+    'gg_batch_next_states_packed': _params(_I32, 'in', 'actions', 'out', 'status') + _BNC,
+    'gg_batch_rollout_packed': _params(_I32, 'packed') + _ROLL + _PLIES + _STREAM,
+    'gg_batch_env_step_packed': _params(_I32, 'packed') + _STEP + _REWARD,
+    'gg_batch_children_packed': _params(_I32, 'packed', 'children') + _BNC,
+    'gg_batch_play_moves': _params(_U8, 'states') + _params(_I32, 'moves', 'played') + _BNT,
+    'gg_batch_play_moves_packed': _params(_I32, 'packed', 'moves', 'played') + _BNT,
+    'gg_tracked_words': _params(_i32, 'N'),
+    'gg_batch_track_states': _params(_U8, 'states') + _params(_I32, 'tracked') + _BN,
+    'gg_batch_untrack_states': _params(_I32, 'tracked') + _params(_U8, 'states') + _BN,
+    'gg_batch_rollout_tracked': _params(_I32, 'tracked') + _ROLL + _PLIES + _STREAM,
+    'gg_batch_play_moves_tracked': _params(_I32, 'tracked', 'moves', 'played') + _BNT,
+    'gg_batch_env_step_tracked': (_params(_I32, 'tracked') + _STEP + _params(_U8, 'states_out') + _params(_I64, 'steps_done')
+                                  + _REWARD),
+    'gg_batch_env_step_tracked_weighted': (_params(_I32, 'tracked') + _WEIGHTED + _STEP[1:] + _params(_U8, 'states_out')
+                                           + _params(_I64, 'steps_done') + _REWARD),
+    'gg_batch_sample_weighted': _params(_U8, 'states') + _WEIGHTED + _params(_I64, 'rng') + _params(_I32, 'actions') + _BN,
+    'gg_batch_sample_weighted_rows': (_params(_I32, 'boards') + _params(_i32, 'planes') + _WEIGHTED + _params(_I64, 'rng')
+                                      + _params(_I32, 'actions') + _BN),
+    'gg_batch_symmetry': (_params(_U8, 'in') + _params(_I32, 'orient') + _params(_U8, 'out') + _params(_i64, 'B')
+                          + _params(_i32, 'C', 'N') + _STREAM),
+    'gg_batch_symmetry_rows': _params(_I32, 'in') + _params(_i32, 'planes') + _params(_I32, 'orient', 'out') + _BN,
+    'gg_rng_seed': _params(_I64, 'rng') + _params(_u64, 'base_seed') + _params(_i64, 'first_game', 'B') + _STREAM,
+    'gg_playouts_begin': _params(_I32, 'roots') + _JOBS + _QUEUE + _OWN,
+    'gg_playouts_advance': _params(_I32, 'roots') + _JOBS + _CHUNKS + _QUEUE + _OWN,
+    'gg_move_playouts_plan': (_params(_I32, 'roots') + _params(_i64, 'R') + _params(_i32, 'N') + _params(_I32, 'offsets', 'plan')
+                              + _STREAM),
+    'gg_move_playouts_begin': _params(_I32, 'roots') + _MOVE_JOBS + _QUEUE + _STREAM,
+    'gg_move_playouts_advance': _params(_I32, 'roots') + _MOVE_JOBS + _CHUNKS + _QUEUE + _STREAM,
+    'gg_uct_begin': (_params(_I32, 'roots') + _RNI + _params(_i32, 'K') + _params(_I32, 'boards', 'child', 'links', 'stats', 'nodes')
+                     + _STREAM),
+    'gg_uct_select': (_RNI + _params(_i32, 'K') + _params(_f64, 'c') + _params(torch.float64, 'log_table')
+                      + _params(_I32, 'boards', 'child', 'links', 'stats', 'nodes') + _LEAF),
+    'gg_uct_backup': (_RNI + _params(_i32, 'K') + _params(_I32, 'counts') + _params(_I64, 'sums', 'totals')
+                      + _params(_I32, 'boards', 'links', 'stats') + _LEAF),
+    'gg_batch_eye_mask': _params(_U8, 'states', 'mask') + _BN,
+    'gg_batch_rollout_tracked_policy': _params(_I32, 'tracked') + _ROLL + _PLIES + _params(_i32, 'policy') + _STREAM,
+    'gg_playouts_advance_policy': _params(_I32, 'roots') + _JOBS + _CHUNKS + _params(_i32, 'policy') + _QUEUE + _OWN,
+    'gg_move_playouts_advance_policy': _params(_I32, 'roots') + _MOVE_JOBS + _CHUNKS + _params(_i32, 'policy') + _QUEUE + _STREAM,
+    'gg_puct_begin': _params(_I32, 'roots') + _RNI + _PUCT_TREE + _STREAM,
+    'gg_puct_select': _RNI + _params(_f64, 'c') + _PUCT_TREE + _LEAF,
+    'gg_puct_backup': _RNI + _PUCT_BACK,
+    'gg_puct_select_leaves': _RNC + _params(_i32, 'L') + _params(_f64, 'c') + _PUCT_TREE + _LEAF,
+    'gg_puct_backup_leaves': _RNC + _params(_i32, 'L') + _PUCT_BACK,
+    'gg_puct_legal': (_params(_I32, 'leaf', 'leaf_id') + _params(_i64, 'B') + _params(_i32, 'N') + _params(torch.bool, 'legal', 'live')
+                      + _STREAM),
+    'gg_puct_advance': _params(_I32, 'actions', 'next') + _RNC + _PUCT_TREE + _params(_I32, 'remap', 'kept') + _STREAM,
+    'gg_puct_root_noise': (_RNC + _params(_f32, 'eps') + _params(_F32, 'noise') + _params(_FLAGS, 'todo') + _params(_I32, 'boards')
+                           + _params(_F32, 'prior') + _params(_I32, 'stats', 'nodes') + _STREAM),
+    'gg_puct_root_policy': (_RNC + _params(_FLAGS, 'sample') + _params(_I64, 'rng') + _params(_I32, 'boards', 'child', 'stats', 'nodes', 'actions')
+                            + _params(_F32, 'pi', 'value') + _STREAM),
+    'gg_feature_planes': (),
+    'gg_batch_group_liberties': _params(_U8, 'states', 'libs') + _BN,
+    'gg_batch_features': _params(_U8, 'states') + _OUT + _OUT_BN,
+    'gg_batch_features_tracked': _params(_I32, 'tracked') + _OUT + _OUT_BN,
+    'gg_batch_features_oriented': _params(_U8, 'states') + _params(_I32, 'orient') + _OUT + _OUT_BN,
+    'gg_batch_features_tracked_oriented': _params(_I32, 'tracked', 'orient') + _OUT + _OUT_BN,
+    'gg_batch_symmetry_policy': (_params(_ROWS, 'in') + _params(_I32, 'orient') + _params(_ROWS, 'out')
+                                 + _params(_i32, 'elem_size', 'inverse') + _BN),
+    'gg_batch_draw_orient': _params(_I64, 'rng') + _params(_I32, 'orient') + _params(_i64, 'B') + _STREAM,
+    'gg_life_planes': (),
+    'gg_batch_life': _params(_U8, 'states') + _params(_I32, 'orient') + _OUT + _params(_U8, 'settled') + _OUT_BN,
+    'gg_batch_life_tracked': _params(_I32, 'tracked', 'orient') + _OUT + _params(_U8, 'settled') + _OUT_BN,
+    'gg_batch_ladder': _params(_U8, 'states') + _params(_I32, 'orient') + _OUT + _params(_U8, 'aborted') + _OUT_BN,
+    'gg_batch_ladder_tracked': _params(_I32, 'tracked', 'orient') + _OUT + _params(_U8, 'aborted') + _OUT_BN,
 }
+EXPORTS = tuple(ABI)
+_SIGNATURES = {f: ([p.kind if isinstance(p.kind, type) else _vp for p in ps], _i32) for f, ps in ABI.items()}   # argtypes, restype
+# call(): the number of parameters and (index, dtypes, name) of every pointer to device memory
+_POINTERS = {f: (len(ps), tuple((i, p.kind if isinstance(p.kind, tuple) else (p.kind,), p.name)
+                                for i, p in enumerate(ps) if not isinstance(p.kind, type))) for f, ps in ABI.items()}
 
 _lib = None
 
@@ -186,6 +231,11 @@ def current_raw_stream(device=None):
         return torch._C._cuda_getCurrentRawStream(torch.cuda.current_device() if idx is None else idx)
     except (AttributeError, TypeError):   # an older / newer torch without the raw getter
         return torch.cuda.current_stream(device).cuda_stream
+    except RuntimeError:
+        if torch.cuda.is_available():
+            raise
+        # (a call() site names its stream before call() looks at the tensors: without a device that is where it ends)
+        raise GymGoNativeError('no ROCm device visible; gymgo_amd has no CPU path') from None
 
 
 class stream_override:
@@ -265,13 +315,52 @@ def hip_event():
 
 
 def dev_ptr(t, dtype, name):
-    """Pointer of a contiguous device tensor of `dtype`; raises instead of silently copying."""
+    """Pointer of a contiguous device tensor of `dtype` (one dtype, or a tuple of those allowed); raises instead of silently
+    copying."""
     if t is None:
         return None
     if not isinstance(t, torch.Tensor) or not t.is_cuda:
         raise GymGoNativeError('%s must be a ROCm device tensor (got %r); gymgo_amd has no CPU path'
                                % (name, type(t) if not isinstance(t, torch.Tensor) else t.device))
-    if t.dtype != dtype or not t.is_contiguous():
+    # (call() tests these same four conditions in line before it comes here: change them in both places)
+    if t.dtype != dtype and not (isinstance(dtype, tuple) and t.dtype in dtype) or not t.is_contiguous():
         raise GymGoNativeError('%s must be contiguous %s (got %s, contiguous=%s)'
                                % (name, dtype, t.dtype, t.is_contiguous()))
     return t.data_ptr()
+
+
+def ptrs(fn, **tensors):
+    """dev_ptr of every tensor as the parameter of entry point `fn` it is named after - dtype(s) from the table -, in the order
+    given: for the paths that check their buffers once and hand call() the pointers from then on."""
+    kinds = {p.name: p.kind for p in ABI[fn]}
+    return tuple(dev_ptr(t, kinds[n], n) for n, t in tensors.items())
+
+
+def launch(fn, *args):
+    """fn(...) plus check and nothing else, for the paths whose every pointer is already an address (ptrs()) and whose host
+    time per launch is their cost: what call() does after it has looked at its arguments."""
+    code = getattr(_lib or lib(), fn)(*args)
+    if code:
+        check(code, fn)
+
+
+def call(fn, *args):
+    """Call entry point `fn` of the library and raise GymGoNativeError unless it returns 0.  args: one per parameter of
+    ABI[fn], the stream (stream_ptr / current_raw_stream: the caller's choice) last.  A pointer parameter takes None (NULL),
+    an int (a pointer the caller has prepared: ptrs(), or pinned host memory) or a tensor, which goes through dev_ptr with the
+    table's dtype(s) and the header's parameter name; scalars pass as they are."""
+    count, pointers = _POINTERS[fn]
+    if len(args) != count:
+        raise TypeError('%s takes %d arguments (%d given)' % (fn, count, len(args)))
+    args = list(args)
+    for i, dtypes, name in pointers:
+        a = args[i]
+        if a is None or type(a) is int:
+            continue
+        if type(a) is torch.Tensor and a.is_cuda and a.dtype in dtypes and a.is_contiguous():   # what dev_ptr asks, without the call
+            args[i] = a.data_ptr()
+        else:           # (a tensor subclass, or what dev_ptr refuses: its verdict, its message)
+            args[i] = dev_ptr(a, dtypes if len(dtypes) > 1 else dtypes[0], name)
+    code = getattr(_lib or lib(), fn)(*args)
+    if code:
+        check(code, fn)

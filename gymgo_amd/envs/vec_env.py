@@ -16,6 +16,8 @@ import torch
 
 from gymgo_amd import _lib, gogame, govars
 
+_TRACKED_STEP = 'gg_batch_env_step_tracked'   # the entry point of the prepared step
+
 
 def shard(total_games, rank, world_size):
     """Contiguous equal split of the game index range [0, total_games) -> (first_game, count)."""
@@ -139,16 +141,16 @@ class GoVecEnv:
             probs = None
         if self.layout == 'tracked' and probs is None:
             # the hot call of a self-play loop: the env's own buffers are validated ONCE (gogame.batch_env_step_tracked's
-            # checks, through _lib.dev_ptr), their pointers kept; a step is then the launch itself (8.6 -> 5.4 us of host time
+            # checks, through _lib.ptrs), their pointers kept; a step is then the launch itself (8.6 -> 5.4 us of host time
             # per call).  Re-validated whenever one of the buffers is re-bound; they must not be resized in place.
             key = (id(self.tracked), id(self.rng), id(self._obs), id(self.steps_done), self.komi, self.reward_method, self.auto_reset)
             prep = self._prep
             if prep is None or prep[0] != key:
                 # (the record keeps the tensors themselves: an object that is alive cannot hand its id() to a new one)
                 prep = self._prep = (key, self._prepare_tracked_step(), (self.tracked, self.rng, self._obs, self.steps_done))
-            fn, head, tail = prep[1]
-            a = 0 if actions is None else _lib.dev_ptr(actions, torch.int32, 'actions')
-            _lib.check(fn(head, a, *tail, _lib.stream_ptr(self.device)), 'gg_batch_env_step_tracked')
+            fn, head, act, tail = prep[1]
+            a = 0 if actions is None else _lib.dev_ptr(actions, act.kind, act.name)
+            _lib.check(fn(head, a, *tail, _lib.stream_ptr(self.device)), _TRACKED_STEP)
             rewards, dones, status, taken = self._step_out
             self._obs_fresh = True
             if check and bool((status != 0).any()):
@@ -174,8 +176,8 @@ class GoVecEnv:
         return obs, rewards, dones, status
 
     def _prepare_tracked_step(self):
-        """(entry point, first argument, the arguments after `actions` up to the stream) of gg_batch_env_step_tracked on this
-        env's buffers, every tensor checked as gogame.batch_env_step_tracked checks it."""
+        """(entry point, first argument, the table's `actions` parameter, the arguments after it up to the stream) of
+        gg_batch_env_step_tracked on this env's buffers, every tensor checked as gogame.batch_env_step_tracked checks it."""
         rewards, dones, status, taken = self._step_out
         B, N = self.batch_size, self.size
         if gogame._tracked_size(self.tracked) != N or self.tracked.shape[0] != B or tuple(self._obs.shape) != (B, 6, N, N):
@@ -183,12 +185,11 @@ class GoVecEnv:
         for t, n in ((self.rng, B), (rewards, B), (dones, B), (status, B), (taken, B), (self.steps_done, B)):
             if t.numel() != n:
                 raise ValueError('a step buffer of the env does not have one entry per game')
-        tail = (_lib.dev_ptr(self.rng, torch.int64, 'rng'), _lib.dev_ptr(rewards, torch.float32, 'rewards'),
-                _lib.dev_ptr(dones, torch.uint8, 'dones'), _lib.dev_ptr(status, torch.int32, 'status'),
-                _lib.dev_ptr(taken, torch.int32, 'taken'), _lib.dev_ptr(self._obs, torch.uint8, 'states_out'),
-                _lib.dev_ptr(self.steps_done, torch.int64, 'steps_done'), B, N, float(self.komi),
-                gogame.REWARD_METHODS[self.reward_method], int(bool(self.auto_reset)))
-        return _lib.lib().gg_batch_env_step_tracked, _lib.dev_ptr(self.tracked, torch.int32, 'tracked'), tail
+        head, *bufs = _lib.ptrs(_TRACKED_STEP, tracked=self.tracked, rng=self.rng, rewards=rewards, dones=dones, status=status,
+                                taken_actions=taken, states_out=self._obs, steps_done=self.steps_done)
+        tail = (*bufs, B, N, float(self.komi), gogame.REWARD_METHODS[self.reward_method], int(bool(self.auto_reset)))
+        act = next(p for p in _lib.ABI[_TRACKED_STEP] if p.name == 'actions')
+        return getattr(_lib.lib(), _TRACKED_STEP), head, act, tail
 
     def step_unfused(self, actions, check=False):
         """The same step as separate launches (reset, next_states, areas + torch reward arithmetic); float64 rewards."""

@@ -73,19 +73,10 @@ def _next_states_dev(states, actions, canonical, out=None, status=None, workspac
         raise ValueError('out must have the shape of the states %s' % (tuple(states.shape),))
     if status is None:
         status = torch.empty(B, dtype=_I32, device=states.device)
-    if workspace is not None:
-        if tuple(workspace.shape) != (B, 5 * N + 1):
-            raise ValueError('workspace must be int32 [B, 5N+1] (gogame.next_states_workspace)')
-        code = _lib.lib().gg_batch_next_states_ws(
-            _lib.dev_ptr(states, _U8, 'states'), _lib.dev_ptr(actions, _I32, 'actions'), _lib.dev_ptr(out, _U8, 'out'),
-            _lib.dev_ptr(status, _I32, 'status'), _lib.dev_ptr(workspace, _I32, 'workspace'), B, N, int(bool(canonical)),
-            _lib.stream_ptr(states.device))
-        _lib.check(code, 'gg_batch_next_states_ws')
-        return out, status
-    code = _lib.lib().gg_batch_next_states(
-        _lib.dev_ptr(states, _U8, 'states'), _lib.dev_ptr(actions, _I32, 'actions'), _lib.dev_ptr(out, _U8, 'out'),
-        _lib.dev_ptr(status, _I32, 'status'), B, N, int(bool(canonical)), _lib.stream_ptr(states.device))
-    _lib.check(code, 'gg_batch_next_states')
+    if workspace is not None and tuple(workspace.shape) != (B, 5 * N + 1):
+        raise ValueError('workspace must be int32 [B, 5N+1] (gogame.next_states_workspace)')
+    name, ws = ('gg_batch_next_states', ()) if workspace is None else ('gg_batch_next_states_ws', (workspace,))
+    _lib.call(name, states, actions, out, status, *ws, B, N, int(bool(canonical)), _lib.stream_ptr(states.device))
     return out, status
 
 
@@ -95,9 +86,7 @@ def _children_dev(states, canonical, out=None):
         out = torch.empty((B, N * N + 1, C, N, N), dtype=_U8, device=states.device)
     elif tuple(out.shape) != (B, N * N + 1, C, N, N):
         raise ValueError('out must be [B, N*N+1, 6, N, N]')
-    code = _lib.lib().gg_batch_children(_lib.dev_ptr(states, _U8, 'states'), _lib.dev_ptr(out, _U8, 'children'),
-                                        B, N, int(bool(canonical)), _lib.stream_ptr(states.device))
-    _lib.check(code, 'gg_batch_children')
+    _lib.call('gg_batch_children', states, out, B, N, int(bool(canonical)), _lib.stream_ptr(states.device))
     return out
 
 
@@ -113,9 +102,7 @@ def _children_offsets_dev(states, offsets=None, order=None):
         order = torch.empty(max(B, 1), dtype=_I32, device=states.device)
     elif order.numel() < B:
         raise ValueError('order must hold at least B = %d int32 (got %d)' % (B, order.numel()))
-    code = _lib.lib().gg_batch_children_offsets(_lib.dev_ptr(states, _U8, 'states'), _lib.dev_ptr(offsets, _I32, 'offsets'),
-                                                _lib.dev_ptr(order, _I32, 'order'), B, N, _lib.stream_ptr(states.device))
-    _lib.check(code, 'gg_batch_children_offsets')
+    _lib.call('gg_batch_children_offsets', states, offsets, order, B, N, _lib.stream_ptr(states.device))
     return offsets, order
 
 
@@ -136,10 +123,7 @@ def _children_compact_dev(states, canonical, offsets=None, out=None):
         total = int(offsets[B].item())
         if out.shape[0] < total:
             raise ValueError('out holds %d boards, the un-padded children of this batch are %d' % (out.shape[0], total))
-    code = _lib.lib().gg_batch_children_compact(_lib.dev_ptr(states, _U8, 'states'), _lib.dev_ptr(offsets, _I32, 'offsets'),
-                                                _lib.dev_ptr(order, _I32, 'order'), _lib.dev_ptr(out, _U8, 'children'), B, N,
-                                                int(bool(canonical)), _lib.stream_ptr(states.device))
-    _lib.check(code, 'gg_batch_children_compact')
+    _lib.call('gg_batch_children_compact', states, offsets, order, out, B, N, int(bool(canonical)), _lib.stream_ptr(states.device))
     return out, offsets
 
 
@@ -150,18 +134,14 @@ def _areas_dev(states, out=None):
         white = torch.empty(B, dtype=_I32, device=states.device)
     else:
         black, white = out
-    code = _lib.lib().gg_batch_areas(_lib.dev_ptr(states, _U8, 'states'), _lib.dev_ptr(black, _I32, 'black'),
-                                     _lib.dev_ptr(white, _I32, 'white'), B, N, _lib.stream_ptr(states.device))
-    _lib.check(code, 'gg_batch_areas')
+    _lib.call('gg_batch_areas', states, black, white, B, N, _lib.stream_ptr(states.device))
     return black, white
 
 
 def _invalid_mask_dev(states, ko=None):
     B, C, N, _ = states.shape
     mask = torch.empty((B, N, N), dtype=_U8, device=states.device)
-    code = _lib.lib().gg_batch_invalid_mask(_lib.dev_ptr(states, _U8, 'states'), _lib.dev_ptr(ko, _I32, 'ko'),
-                                            _lib.dev_ptr(mask, _U8, 'mask'), B, N, _lib.stream_ptr(states.device))
-    _lib.check(code, 'gg_batch_invalid_mask')
+    _lib.call('gg_batch_invalid_mask', states, ko, mask, B, N, _lib.stream_ptr(states.device))
     return mask
 
 
@@ -497,9 +477,7 @@ def rng_seed(batch_size, base_seed=20260927, first_game=0, device=None):
     device = device or _device()
     # uint64 storage as int64 tensor (torch has no general uint64 ops; only the bits matter)
     rng = torch.empty(batch_size, dtype=_I64, device=device)
-    code = _lib.lib().gg_rng_seed(_lib.dev_ptr(rng, _I64, 'rng'), int(base_seed) & (2 ** 64 - 1), int(first_game),
-                                  batch_size, _lib.stream_ptr(device))
-    _lib.check(code, 'gg_rng_seed')
+    _lib.call('gg_rng_seed', rng, int(base_seed) & (2 ** 64 - 1), int(first_game), batch_size, _lib.stream_ptr(device))
     return rng
 
 
@@ -541,19 +519,9 @@ def batch_rollout(batch_states, rng, plies, auto_reset=True, last_actions=None, 
         workspace = _rollout_workspace(batch_states)
     elif tuple(workspace.shape) != (B, 5 * N + 1):
         raise ValueError('workspace must be int32 [%d][%d] (got %s)' % (B, 5 * N + 1, tuple(workspace.shape)))
-    if workspace is None:
-        code = _lib.lib().gg_batch_rollout(
-            _lib.dev_ptr(batch_states, _U8, 'states'), _lib.dev_ptr(rng, _I64, 'rng'),
-            _lib.dev_ptr(last_actions, _I32, 'last_actions'), _lib.dev_ptr(steps_done, _I64, 'steps_done'),
-            B, N, int(plies), int(bool(auto_reset)), _lib.stream_ptr(batch_states.device))
-        _lib.check(code, 'gg_batch_rollout')
-        return batch_states
-    code = _lib.lib().gg_batch_rollout_ws(
-        _lib.dev_ptr(batch_states, _U8, 'states'), _lib.dev_ptr(rng, _I64, 'rng'),
-        _lib.dev_ptr(last_actions, _I32, 'last_actions'), _lib.dev_ptr(steps_done, _I64, 'steps_done'),
-        _lib.dev_ptr(workspace, _I32, 'workspace'), B, N, int(plies), int(bool(auto_reset)),
-        _lib.stream_ptr(batch_states.device))
-    _lib.check(code, 'gg_batch_rollout_ws')
+    name, ws = ('gg_batch_rollout', ()) if workspace is None else ('gg_batch_rollout_ws', (workspace,))
+    _lib.call(name, batch_states, rng, last_actions, steps_done, *ws, B, N, int(plies), int(bool(auto_reset)),
+              _lib.stream_ptr(batch_states.device))
     return batch_states
 
 
@@ -573,12 +541,8 @@ def batch_env_step(batch_states, actions=None, rng=None, komi=0.0, reward_method
         out = (torch.empty(B, dtype=torch.float32, device=dev), torch.empty(B, dtype=_U8, device=dev),
                torch.empty(B, dtype=_I32, device=dev), torch.empty(B, dtype=_I32, device=dev))
     rewards, dones, status, taken = out
-    code = _lib.lib().gg_batch_env_step(
-        _lib.dev_ptr(batch_states, _U8, 'states'), _lib.dev_ptr(actions, _I32, 'actions'),
-        _lib.dev_ptr(rng, _I64, 'rng'), _lib.dev_ptr(rewards, torch.float32, 'rewards'),
-        _lib.dev_ptr(dones, _U8, 'dones'), _lib.dev_ptr(status, _I32, 'status'), _lib.dev_ptr(taken, _I32, 'taken'),
-        B, N, float(komi), REWARD_METHODS[reward_method], int(bool(auto_reset)), _lib.stream_ptr(dev))
-    _lib.check(code, 'gg_batch_env_step')
+    _lib.call('gg_batch_env_step', batch_states, actions, rng, rewards, dones, status, taken, B, N, float(komi),
+              REWARD_METHODS[reward_method], int(bool(auto_reset)), _lib.stream_ptr(dev))
     return out
 
 
@@ -587,19 +551,14 @@ def batch_sample_actions(batch_states, rng):
     gym_go/envs/go_env.py:78-81, for every game at once)."""
     B, C, N, _ = batch_states.shape
     actions = torch.empty(B, dtype=_I32, device=batch_states.device)
-    code = _lib.lib().gg_batch_sample_actions(
-        _lib.dev_ptr(batch_states, _U8, 'states'), _lib.dev_ptr(rng, _I64, 'rng'),
-        _lib.dev_ptr(actions, _I32, 'actions'), B, N, _lib.stream_ptr(batch_states.device))
-    _lib.check(code, 'gg_batch_sample_actions')
+    _lib.call('gg_batch_sample_actions', batch_states, rng, actions, B, N, _lib.stream_ptr(batch_states.device))
     return actions
 
 
 def batch_reset_finished(batch_states):
     """IN PLACE: every finished game (plane 5 set) becomes init_state (GoVecEnv auto-reset, gg_batch_reset_finished)."""
     B, C, N, _ = batch_states.shape
-    code = _lib.lib().gg_batch_reset_finished(_lib.dev_ptr(batch_states, _U8, 'states'), B, N,
-                                              _lib.stream_ptr(batch_states.device))
-    _lib.check(code, 'gg_batch_reset_finished')
+    _lib.call('gg_batch_reset_finished', batch_states, B, N, _lib.stream_ptr(batch_states.device))
     return batch_states
 
 
@@ -613,9 +572,7 @@ def batch_pack(batch_states):
     9.3x smaller at 19x19 - replay buffers, checkpoints, the wire (gg_batch_pack_states)."""
     B, C, N, _ = batch_states.shape
     packed = torch.empty((B, packed_words(N)), dtype=_I32, device=batch_states.device)
-    code = _lib.lib().gg_batch_pack_states(_lib.dev_ptr(batch_states, _U8, 'states'), _lib.dev_ptr(packed, _I32, 'packed'),
-                                           B, N, _lib.stream_ptr(batch_states.device))
-    _lib.check(code, 'gg_batch_pack_states')
+    _lib.call('gg_batch_pack_states', batch_states, packed, B, N, _lib.stream_ptr(batch_states.device))
     return packed
 
 
@@ -625,9 +582,7 @@ def batch_unpack(packed, board_size):
     if packed.shape[1] != packed_words(board_size):
         raise ValueError('packed rows must have %d words for a %dx%d board' % (packed_words(board_size), board_size, board_size))
     states = torch.empty((B, govars.NUM_CHNLS, board_size, board_size), dtype=_U8, device=packed.device)
-    code = _lib.lib().gg_batch_unpack_states(_lib.dev_ptr(packed, _I32, 'packed'), _lib.dev_ptr(states, _U8, 'states'),
-                                             B, board_size, _lib.stream_ptr(packed.device))
-    _lib.check(code, 'gg_batch_unpack_states')
+    _lib.call('gg_batch_unpack_states', packed, states, B, board_size, _lib.stream_ptr(packed.device))
     return states
 
 
@@ -649,10 +604,7 @@ def batch_next_states_packed(packed, batch_action1d, canonical=False, check=True
     actions = _actions_tensor(batch_action1d, B, packed.device)
     out = torch.empty_like(packed)
     status = torch.empty(B, dtype=_I32, device=packed.device)
-    code = _lib.lib().gg_batch_next_states_packed(
-        _lib.dev_ptr(packed, _I32, 'packed'), _lib.dev_ptr(actions, _I32, 'actions'), _lib.dev_ptr(out, _I32, 'out'),
-        _lib.dev_ptr(status, _I32, 'status'), B, N, int(bool(canonical)), _lib.stream_ptr(packed.device))
-    _lib.check(code, 'gg_batch_next_states_packed')
+    _lib.call('gg_batch_next_states_packed', packed, actions, out, status, B, N, int(bool(canonical)), _lib.stream_ptr(packed.device))
     if check and bool((status != 0).any()):
         raise AssertionError('invalid move in batch (gym_go/gogame.py:117)')
     return out, status
@@ -662,10 +614,8 @@ def batch_rollout_packed(packed, rng, plies, auto_reset=True, last_actions=None,
     """IN PLACE batch_rollout on packed boards (gg_batch_rollout_packed)."""
     N = _packed_size(packed)
     B = packed.shape[0]
-    code = _lib.lib().gg_batch_rollout_packed(
-        _lib.dev_ptr(packed, _I32, 'packed'), _lib.dev_ptr(rng, _I64, 'rng'), _lib.dev_ptr(last_actions, _I32, 'last_actions'),
-        _lib.dev_ptr(steps_done, _I64, 'steps_done'), B, N, int(plies), int(bool(auto_reset)), _lib.stream_ptr(packed.device))
-    _lib.check(code, 'gg_batch_rollout_packed')
+    _lib.call('gg_batch_rollout_packed', packed, rng, last_actions, steps_done, B, N, int(plies), int(bool(auto_reset)),
+              _lib.stream_ptr(packed.device))
     return packed
 
 
@@ -680,12 +630,8 @@ def batch_env_step_packed(packed, actions=None, rng=None, komi=0.0, reward_metho
         out = (torch.empty(B, dtype=torch.float32, device=dev), torch.empty(B, dtype=_U8, device=dev),
                torch.empty(B, dtype=_I32, device=dev), torch.empty(B, dtype=_I32, device=dev))
     rewards, dones, status, taken = out
-    code = _lib.lib().gg_batch_env_step_packed(
-        _lib.dev_ptr(packed, _I32, 'packed'), _lib.dev_ptr(actions, _I32, 'actions'), _lib.dev_ptr(rng, _I64, 'rng'),
-        _lib.dev_ptr(rewards, torch.float32, 'rewards'), _lib.dev_ptr(dones, _U8, 'dones'), _lib.dev_ptr(status, _I32, 'status'),
-        _lib.dev_ptr(taken, _I32, 'taken'), B, N, float(komi), REWARD_METHODS[reward_method], int(bool(auto_reset)),
-        _lib.stream_ptr(dev))
-    _lib.check(code, 'gg_batch_env_step_packed')
+    _lib.call('gg_batch_env_step_packed', packed, actions, rng, rewards, dones, status, taken, B, N, float(komi),
+              REWARD_METHODS[reward_method], int(bool(auto_reset)), _lib.stream_ptr(dev))
     return out
 
 
@@ -694,9 +640,7 @@ def batch_children_packed(packed, canonical=False):
     N = _packed_size(packed)
     B = packed.shape[0]
     kids = torch.empty((B, N * N + 1, packed_words(N)), dtype=_I32, device=packed.device)
-    code = _lib.lib().gg_batch_children_packed(_lib.dev_ptr(packed, _I32, 'packed'), _lib.dev_ptr(kids, _I32, 'children'),
-                                               B, N, int(bool(canonical)), _lib.stream_ptr(packed.device))
-    _lib.check(code, 'gg_batch_children_packed')
+    _lib.call('gg_batch_children_packed', packed, kids, B, N, int(bool(canonical)), _lib.stream_ptr(packed.device))
     return kids
 
 
@@ -711,10 +655,8 @@ def batch_play_moves(batch_states, moves):
     if moves.dim() != 2 or moves.shape[0] != B:
         raise ValueError('moves must be [B, T]')
     played = torch.empty(B, dtype=_I32, device=batch_states.device)
-    fn = _lib.lib().gg_batch_play_moves_packed if packed else _lib.lib().gg_batch_play_moves
-    code = fn(_lib.dev_ptr(batch_states, _I32 if packed else _U8, 'states'), _lib.dev_ptr(moves, _I32, 'moves'),
-              _lib.dev_ptr(played, _I32, 'played'), B, N, moves.shape[1], _lib.stream_ptr(batch_states.device))
-    _lib.check(code, 'gg_batch_play_moves')
+    _lib.call('gg_batch_play_moves_packed' if packed else 'gg_batch_play_moves', batch_states, moves, played, B, N, moves.shape[1],
+              _lib.stream_ptr(batch_states.device))
     return played
 
 
@@ -736,9 +678,7 @@ def batch_track(batch_states):
     colour whose group has >= 2 liberties.  Tracked boards step at the fused kernel's rate even one ply per launch."""
     B, C, N, _ = batch_states.shape
     tracked = torch.empty((B, tracked_words(N)), dtype=_I32, device=batch_states.device)
-    code = _lib.lib().gg_batch_track_states(_lib.dev_ptr(batch_states, _U8, 'states'), _lib.dev_ptr(tracked, _I32, 'tracked'),
-                                            B, N, _lib.stream_ptr(batch_states.device))
-    _lib.check(code, 'gg_batch_track_states')
+    _lib.call('gg_batch_track_states', batch_states, tracked, B, N, _lib.stream_ptr(batch_states.device))
     return tracked
 
 
@@ -749,9 +689,7 @@ def batch_untrack(tracked, out=None):
     states = out if out is not None else torch.empty((B, govars.NUM_CHNLS, N, N), dtype=_U8, device=tracked.device)
     if tuple(states.shape) != (B, govars.NUM_CHNLS, N, N):
         raise ValueError('out must be uint8 [B, 6, N, N]')
-    code = _lib.lib().gg_batch_untrack_states(_lib.dev_ptr(tracked, _I32, 'tracked'), _lib.dev_ptr(states, _U8, 'states'),
-                                              B, N, _lib.stream_ptr(tracked.device))
-    _lib.check(code, 'gg_batch_untrack_states')
+    _lib.call('gg_batch_untrack_states', tracked, states, B, N, _lib.stream_ptr(tracked.device))
     return states
 
 
@@ -772,13 +710,9 @@ def batch_rollout_tracked(tracked, rng, plies, auto_reset=True, last_actions=Non
     pol = _policy_code(policy)
     N = _tracked_size(tracked)
     B = tracked.shape[0]
-    args = (_lib.dev_ptr(tracked, _I32, 'tracked'), _lib.dev_ptr(rng, _I64, 'rng'), _lib.dev_ptr(last_actions, _I32, 'last_actions'),
-            _lib.dev_ptr(steps_done, _I64, 'steps_done'), B, N, int(plies), int(bool(auto_reset)))
-    if pol:
-        _lib.check(_lib.lib().gg_batch_rollout_tracked_policy(*args, pol, _lib.stream_ptr(tracked.device)),
-                   'gg_batch_rollout_tracked_policy')
-    else:
-        _lib.check(_lib.lib().gg_batch_rollout_tracked(*args, _lib.stream_ptr(tracked.device)), 'gg_batch_rollout_tracked')
+    name, extra = ('gg_batch_rollout_tracked_policy', (pol,)) if pol else ('gg_batch_rollout_tracked', ())
+    _lib.call(name, tracked, rng, last_actions, steps_done, B, N, int(plies), int(bool(auto_reset)), *extra,
+              _lib.stream_ptr(tracked.device))
     return tracked
 
 
@@ -793,9 +727,7 @@ def batch_eye_mask(batch_states):
         raise ValueError('batch_states must be [B, 6, N, N] (got %s)' % (tuple(st.shape),))
     B, N = st.shape[0], st.shape[2]
     mask = torch.empty((B, N, N), dtype=_U8, device=st.device)
-    code = _lib.lib().gg_batch_eye_mask(_lib.dev_ptr(st, _U8, 'states'), _lib.dev_ptr(mask, _U8, 'mask'), B, N,
-                                        _lib.stream_ptr(st.device))
-    _lib.check(code, 'gg_batch_eye_mask')
+    _lib.call('gg_batch_eye_mask', st, mask, B, N, _lib.stream_ptr(st.device))
     return _back(box, mask)
 
 
@@ -848,9 +780,7 @@ def batch_group_liberties(batch_states):
     box = _Box(batch_states)
     st = box.t
     libs = torch.empty((B, N, N), dtype=_U8, device=st.device)
-    code = _lib.lib().gg_batch_group_liberties(_lib.dev_ptr(st, _U8, 'states'), _lib.dev_ptr(libs, _U8, 'libs'), B, N,
-                                               _lib.stream_ptr(st.device))
-    _lib.check(code, 'gg_batch_group_liberties')
+    _lib.call('gg_batch_group_liberties', st, libs, B, N, _lib.stream_ptr(st.device))
     return _back(box, libs)
 
 
@@ -871,17 +801,17 @@ def _orient_arg(orient, B):
         raise ValueError('orient must be %d integers in 0..7, one per row (got %d of %s)' % (B, n, orient.dtype))
 
 
-def _plane_launch(name, boards_ptr, orient_ptr, out_ptr, extra_ptr, code, B, N, stream):
-    """One launch of a plane entry point on raw pointers.  name: gg_batch_features[_tracked] - its _oriented form when
-    orient_ptr is given, and no per-board bytes (extra_ptr is False) - or gg_batch_life[_tracked] / gg_batch_ladder[_tracked],
-    which take orient (or None) and the per-board bytes (or None) themselves."""
-    if extra_ptr is not False:
-        args = (boards_ptr, orient_ptr, out_ptr, extra_ptr)
-    elif orient_ptr is None:
-        args = (boards_ptr, out_ptr)
+def _plane_launch(name, boards, orient, out, extra, code, B, N, stream, launch=_lib.call):
+    """One launch of a plane entry point on tensors (_lib.call) or, launch=_lib.launch, on prepared pointers alone.  name: gg_batch_features[_tracked] - its
+    _oriented form when orient is given, and no per-board bytes (extra is False) - or gg_batch_life[_tracked] /
+    gg_batch_ladder[_tracked], which take orient (or None) and the per-board bytes (or None) themselves."""
+    if extra is not False:
+        args = (boards, orient, out, extra)
+    elif orient is None:
+        args = (boards, out)
     else:
-        name, args = name + '_oriented', (boards_ptr, orient_ptr, out_ptr)
-    _lib.check(getattr(_lib.lib(), name)(*args, code, B, N, stream), name)
+        name, args = name + '_oriented', (boards, orient, out)
+    launch(name, *args, code, B, N, stream)
 
 
 def _planes(name, count, align, boards, tracked, dtype, out, orient, extra=None):
@@ -912,9 +842,7 @@ def _planes(name, count, align, boards, tracked, dtype, out, orient, extra=None)
     planes = out if out is not None else torch.empty((B, count, N, N), dtype=dtype, device=st.device)
     bytes_ = torch.empty(B, dtype=_U8, device=st.device) if extra else None
     o = None if orient is None else _actions_tensor(orient, B, st.device)
-    _plane_launch(name, _lib.dev_ptr(st, _I32 if tracked else _U8, 'tracked' if tracked else 'states'), _lib.dev_ptr(o, _I32, 'orient'),
-                  _lib.dev_ptr(planes, dtype, 'out'), False if extra is None else _lib.dev_ptr(bytes_, _U8, 'bytes'), code, B, N,
-                  _lib.stream_ptr(st.device))
+    _plane_launch(name, st, o, planes, False if extra is None else bytes_, code, B, N, _lib.stream_ptr(st.device))
     if box is not None:
         planes, bytes_ = _back(box, planes), _back(box, bytes_)
     return (planes, bytes_) if extra else planes
@@ -1050,10 +978,7 @@ def batch_play_moves_tracked(tracked, moves, played=None):
     moves = moves.to(device=tracked.device, dtype=_I32).reshape(B, -1).contiguous()
     if played is None:
         played = torch.empty(B, dtype=_I32, device=tracked.device)
-    code = _lib.lib().gg_batch_play_moves_tracked(_lib.dev_ptr(tracked, _I32, 'tracked'), _lib.dev_ptr(moves, _I32, 'moves'),
-                                                  _lib.dev_ptr(played, _I32, 'played'), B, N, moves.shape[1],
-                                                  _lib.stream_ptr(tracked.device))
-    _lib.check(code, 'gg_batch_play_moves_tracked')
+    _lib.call('gg_batch_play_moves_tracked', tracked, moves, played, B, N, moves.shape[1], _lib.stream_ptr(tracked.device))
     return played
 
 
@@ -1083,22 +1008,9 @@ def batch_env_step_tracked(tracked, actions=None, rng=None, komi=0.0, reward_met
     if states_out is not None and tuple(states_out.shape) != (B, govars.NUM_CHNLS, N, N):
         raise ValueError('states_out must be uint8 [B, 6, N, N]')
     rewards, dones, status, taken = out
-    if weights is not None:
-        code = _lib.lib().gg_batch_env_step_tracked_weighted(
-            _lib.dev_ptr(tracked, _I32, 'tracked'), _lib.dev_ptr(weights, weights.dtype, 'weights'), wcode, _lib.dev_ptr(rng, _I64, 'rng'),
-            _lib.dev_ptr(rewards, torch.float32, 'rewards'), _lib.dev_ptr(dones, _U8, 'dones'), _lib.dev_ptr(status, _I32, 'status'),
-            _lib.dev_ptr(taken, _I32, 'taken'), _lib.dev_ptr(states_out, _U8, 'states_out'),
-            _lib.dev_ptr(steps_done, _I64, 'steps_done'), B, N, float(komi),
-            REWARD_METHODS[reward_method], int(bool(auto_reset)), _lib.stream_ptr(dev))
-        _lib.check(code, 'gg_batch_env_step_tracked_weighted')
-        return out
-    code = _lib.lib().gg_batch_env_step_tracked(
-        _lib.dev_ptr(tracked, _I32, 'tracked'), _lib.dev_ptr(actions, _I32, 'actions'), _lib.dev_ptr(rng, _I64, 'rng'),
-        _lib.dev_ptr(rewards, torch.float32, 'rewards'), _lib.dev_ptr(dones, _U8, 'dones'), _lib.dev_ptr(status, _I32, 'status'),
-        _lib.dev_ptr(taken, _I32, 'taken'), _lib.dev_ptr(states_out, _U8, 'states_out'),
-        _lib.dev_ptr(steps_done, _I64, 'steps_done'), B, N, float(komi),
-        REWARD_METHODS[reward_method], int(bool(auto_reset)), _lib.stream_ptr(dev))
-    _lib.check(code, 'gg_batch_env_step_tracked')
+    name, move = ('gg_batch_env_step_tracked', (actions,)) if weights is None else ('gg_batch_env_step_tracked_weighted', (weights, wcode))
+    _lib.call(name, tracked, *move, rng, rewards, dones, status, taken, states_out, steps_done, B, N, float(komi),
+              REWARD_METHODS[reward_method], int(bool(auto_reset)), _lib.stream_ptr(dev))
     return out
 
 
@@ -1156,13 +1068,12 @@ def _drive_playouts(advance, counter, J, S, max_plies, chunk_plies, dev, what):
 
 def _run_queue(family, what, head, komi, bufs, counter, J, S, max_plies, chunk_plies, dev, policy=0):
     """gg_<family>_begin, then gg_<family>_advance_policy until the counter drains (_drive_playouts).  head: the arguments up
-    to chunk_plies, bufs: those from slots on (_queue_ptrs, and what the family adds); advance takes komi, the chunk count
+    to chunk_plies, bufs: those from slots on (_queue_args, and what the family adds); advance takes komi, the chunk count
     and the playout policy's code between the two."""
     begin, advance = 'gg_%s_begin' % family, 'gg_%s_advance_policy' % family
-    begin_fn, advance_fn = getattr(_lib.lib(), begin), getattr(_lib.lib(), advance)
     stream = _lib.current_raw_stream(dev)   # torch's current stream: the counter copies of _drive_playouts go there too
-    _lib.check(begin_fn(*head, *bufs, stream), begin)
-    _drive_playouts(lambda n: _lib.check(advance_fn(*head, float(komi), n, int(policy), *bufs, stream), advance),
+    _lib.call(begin, *head, *bufs, stream)
+    _drive_playouts(lambda n: _lib.call(advance, *head, float(komi), n, int(policy), *bufs, stream),
                     counter, J, S, max_plies, chunk_plies, dev, what)
 
 
@@ -1178,11 +1089,9 @@ def _playout_buffers(R, S, N, dev):
     return _slot_buffers(S, N, dev) + (torch.empty((R, 4), dtype=_I32, device=dev), torch.empty((R, 2), dtype=_I64, device=dev))
 
 
-def _queue_ptrs(slots, rng, plies, job, counter, counts, sums):
+def _queue_args(slots, rng, plies, job, counter, counts, sums):
     """The queue's buffers as both families' C entry points take them: slots, rng, plies, job, S, counter, counts, sums."""
-    return (_lib.dev_ptr(slots, _I32, 'slots'), _lib.dev_ptr(rng, _I64, 'rng'), _lib.dev_ptr(plies, _I64, 'plies'),
-            _lib.dev_ptr(job, _I64, 'job'), slots.shape[0], _lib.dev_ptr(counter, _I64, 'counter'),
-            _lib.dev_ptr(counts, _I32, 'counts'), _lib.dev_ptr(sums, _I64, 'sums'))
+    return slots, rng, plies, job, slots.shape[0], counter, counts, sums
 
 
 def _run_playouts(roots, R, N, K, max_plies, komi, seed, first_root, ownership, S, chunk_plies, dev, buffers=None, policy=0):
@@ -1193,9 +1102,9 @@ def _run_playouts(roots, R, N, K, max_plies, komi, seed, first_root, ownership, 
     counter, counts, sums = buffers[4:]
     own = torch.empty((R, 2, N, N), dtype=_I32, device=dev) if ownership else None
     if R > 0:
-        head = (_lib.dev_ptr(roots, _I32, 'roots'), R, N, K, int(first_root), int(seed) & _M64, int(max_plies), int(chunk_plies))
-        _run_queue('playouts', 'batch_playouts', head, komi, _queue_ptrs(*buffers) + (_lib.dev_ptr(own, _I32, 'ownership'),),
-                   counter, R * K, S, max_plies, chunk_plies, dev, policy)
+        head = (roots, R, N, K, int(first_root), int(seed) & _M64, int(max_plies), int(chunk_plies))
+        _run_queue('playouts', 'batch_playouts', head, komi, _queue_args(*buffers) + (own,), counter, R * K, S, max_plies,
+                   chunk_plies, dev, policy)
     return counts, sums, own
 
 
@@ -1300,10 +1209,8 @@ def _run_move_playouts(roots, R, N, K, max_plies, komi, seed, first_root, slots,
         return legal, counts, sums
     offsets = torch.empty(R + 1, dtype=_I32, device=dev)
     plan = torch.empty(R * A, dtype=_I32, device=dev)
-    rp, pp = _lib.dev_ptr(roots, _I32, 'roots'), _lib.dev_ptr(plan, _I32, 'plan')
     with torch.cuda.device(dev):
-        _lib.check(_lib.lib().gg_move_playouts_plan(rp, R, N, _lib.dev_ptr(offsets, _I32, 'offsets'), pp,
-                                                    _lib.current_raw_stream(dev)), 'gg_move_playouts_plan')
+        _lib.call('gg_move_playouts_plan', roots, R, N, offsets, plan, _lib.current_raw_stream(dev))
         T = int(offsets[R])   # (a synchronising read, as the un-padded children do)
     if T == 0:
         return legal, counts, sums
@@ -1311,8 +1218,8 @@ def _run_move_playouts(roots, R, N, K, max_plies, komi, seed, first_root, slots,
     J = T * K
     S = max(1, min(int(slots), J))
     slot_bufs = _slot_buffers(S, N, dev)
-    head = (rp, R, N, pp, T, K, int(first_root), int(seed) & _M64, int(max_plies), int(chunk_plies))
-    _run_queue('move_playouts', 'batch_move_playouts', head, komi, _queue_ptrs(*slot_bufs, counts, sums), slot_bufs[4], J, S,
+    head = (roots, R, N, plan, T, K, int(first_root), int(seed) & _M64, int(max_plies), int(chunk_plies))
+    _run_queue('move_playouts', 'batch_move_playouts', head, komi, _queue_args(*slot_bufs, counts, sums), slot_bufs[4], J, S,
                max_plies, chunk_plies, dev, policy)
     return legal, counts, sums
 
@@ -1396,7 +1303,6 @@ def _legal_roots(st):
 def _run_uct(roots, R, N, I, K, c, max_plies, komi, seed, first_root, S, chunk_plies, dev, policy=0):
     """Device work of batch_uct on tracked roots -> (child int32 [R, I+1, A], links [R, I+1, 2], stats [R, I+1, 4],
     nodes [R], totals int64 [R, 2]); no launch for R = 0."""
-    L = _lib.lib()
     W, A, NN = tracked_words(N), N * N + 1, I + 1
     boards = torch.empty((R, NN, W), dtype=_I32, device=dev)
     child = torch.empty((R, NN, A), dtype=_I32, device=dev)
@@ -1414,18 +1320,12 @@ def _run_uct(roots, R, N, I, K, c, max_plies, komi, seed, first_root, S, chunk_p
     pbufs = _playout_buffers(R, S, N, dev)
     counts, sums = pbufs[5], pbufs[6]
     stream = _lib.current_raw_stream(dev)
-    p = lambda t, dt, name: _lib.dev_ptr(t, dt, name)
-    tree = (p(boards, _I32, 'boards'), p(child, _I32, 'child'), p(links, _I32, 'links'), p(stats, _I32, 'stats'),
-            p(nodes, _I32, 'nodes'))
-    lp, mp, ip = p(leaf, _I32, 'leaf'), p(move, _I32, 'move'), p(leaf_id, _I32, 'leaf_id')
-    _lib.check(L.gg_uct_begin(p(roots, _I32, 'roots'), R, N, I, K, *tree, stream), 'gg_uct_begin')
+    _lib.call('gg_uct_begin', roots, R, N, I, K, boards, child, links, stats, nodes, stream)
     for i in range(I):
-        _lib.check(L.gg_uct_select(R, N, I, K, c, _lib.dev_ptr(log_table, torch.float64, 'log_table'), *tree, lp, mp, ip,
-                                   stream), 'gg_uct_select')
-        _lib.check(L.gg_batch_play_moves_tracked(lp, mp, None, R, N, 1, stream), 'gg_batch_play_moves_tracked')
+        _lib.call('gg_uct_select', R, N, I, K, c, log_table, boards, child, links, stats, nodes, leaf, move, leaf_id, stream)
+        _lib.call('gg_batch_play_moves_tracked', leaf, move, None, R, N, 1, stream)
         _run_playouts(leaf, R, N, K, max_plies, komi, _uct_seed(seed, i), first_root, False, S, chunk_plies, dev, pbufs, policy)
-        _lib.check(L.gg_uct_backup(R, N, I, K, p(counts, _I32, 'counts'), p(sums, _I64, 'sums'), p(totals, _I64, 'totals'),
-                                   tree[0], tree[2], tree[3], lp, mp, ip, stream), 'gg_uct_backup')
+        _lib.call('gg_uct_backup', R, N, I, K, counts, sums, totals, boards, links, stats, leaf, move, leaf_id, stream)
     return child, links, stats, nodes, totals
 
 
@@ -1642,13 +1542,14 @@ class PuctSearch:
         self._init_symmetry(B)
         if not R:   # no device work at all: select / backup only keep the call order
             return
-        p = _lib.dev_ptr
-        self._tree = (p(self._boards, _I32, 'boards'), p(self._child, _I32, 'child'), p(self._prior, torch.float32, 'prior'),
-                      p(self._links, _I32, 'links'), p(self._stats, _I32, 'stats'), p(self._nodes, _I32, 'nodes'))
-        self._out = (p(self._leaf, _I32, 'leaf'), p(self._move, _I32, 'move'), p(self._leaf_id, _I32, 'leaf_id'))
-        self._hand = (p(self._states, self._states.dtype, 'states'), p(self._legal, torch.bool, 'legal'), p(self.live, torch.bool, 'live'))
-        _lib.check(_lib.lib().gg_puct_begin(p(_track_roots(st), _I32, 'roots'), R, N, self._C, *self._tree,
-                                            _lib.current_raw_stream(dev)), 'gg_puct_begin')
+        # the search's own buffers are checked once, through the table; every call below gets their pointers
+        self._tree = _lib.ptrs('gg_puct_begin', boards=self._boards, child=self._child, prior=self._prior, links=self._links,
+                               stats=self._stats, nodes=self._nodes)
+        self._out = _lib.ptrs('gg_puct_select', leaf=self._leaf, move=self._move, leaf_id=self._leaf_id)
+        self._hand = (_lib.ptrs('gg_batch_untrack_states', states=self._states) if self._feat is None else
+                      _lib.ptrs('gg_batch_features_tracked', out=self._states)) + _lib.ptrs('gg_puct_legal', legal=self._legal, live=self.live)
+        self._rows = [p for p in _lib.ABI['gg_puct_backup'] if p.name in ('priors', 'values')]
+        _lib.call('gg_puct_begin', _track_roots(st), R, N, self._C, *self._tree, _lib.current_raw_stream(dev))
 
     def _init_symmetry(self, B):
         """symmetry: the generators of the B rows handed out, their orientations, legal in the view, the priors turned back."""
@@ -1661,26 +1562,21 @@ class PuctSearch:
         self._sym_rng = torch.empty(B, dtype=_I64, device=dev)
         if B:
             rows = B // self._R
-            _lib.check(_lib.lib().gg_rng_seed(_lib.dev_ptr(self._sym_rng, _I64, 'rng'), self._sym & (2 ** 64 - 1),
-                                              self._first_root * rows, B, _lib.current_raw_stream(dev)), 'gg_rng_seed')
+            _lib.call('gg_rng_seed', self._sym_rng, self._sym & (2 ** 64 - 1), self._first_root * rows, B, _lib.current_raw_stream(dev))
 
     def _draw_orient(self, B, stream):
         """The orientations of this select()'s B rows -> the pointer of search.orient."""
-        op = _lib.dev_ptr(self.orient, _I32, 'orient')
-        _lib.check(_lib.lib().gg_batch_draw_orient(_lib.dev_ptr(self._sym_rng, _I64, 'rng'), op, B, stream), 'gg_batch_draw_orient')
+        op, = _lib.ptrs('gg_batch_draw_orient', orient=self.orient)
+        _lib.call('gg_batch_draw_orient', self._sym_rng, op, B, stream)
         return op
 
     def _turn_legal(self, op, B, stream):
-        _lib.check(_lib.lib().gg_batch_symmetry_policy(_lib.dev_ptr(self._legal, torch.bool, 'legal'), op,
-                                                       _lib.dev_ptr(self._legal_view, torch.bool, 'legal'), 1, 0, B, self._N, stream),
-                   'gg_batch_symmetry_policy')
+        _lib.call('gg_batch_symmetry_policy', self._legal, op, self._legal_view, 1, 0, B, self._N, stream)
 
     def _turn_priors_back(self, priors, B):
         """priors [B, A] over the views -> over the boards (R > 0)."""
-        _lib.check(_lib.lib().gg_batch_symmetry_policy(_lib.dev_ptr(priors, torch.float32, 'priors'),
-                                                       _lib.dev_ptr(self.orient, _I32, 'orient'),
-                                                       _lib.dev_ptr(self._priors_back, torch.float32, 'priors'), 4, 1, B, self._N,
-                                                       _lib.current_raw_stream(self._dev)), 'gg_batch_symmetry_policy')
+        _lib.call('gg_batch_symmetry_policy', priors, self.orient, self._priors_back, 4, 1, B, self._N,
+                  _lib.current_raw_stream(self._dev))
         return self._priors_back
 
     @property
@@ -1697,29 +1593,25 @@ class PuctSearch:
             raise ValueError('PuctSearch.select(): all %d iterations are done' % self._I)
         R, N, B = self._R, self._N, self._R * (self._L or 1)
         if R:
-            lib, stream = _lib.lib(), _lib.current_raw_stream(self._dev)
+            # every pointer below is a prepared one and host time per round is this path's cost: fn(...) plus check, in line
+            lib, check, stream = _lib.lib(), _lib.check, _lib.current_raw_stream(self._dev)
             lp, mp, ip = self._out
             sp, gp, vp = self._hand
-            if self._L is None:
-                _lib.check(lib.gg_puct_select(R, N, self._C, self._c, *self._tree, lp, mp, ip, stream), 'gg_puct_select')
-            else:
-                _lib.check(lib.gg_puct_select_leaves(R, N, self._C, self._L, self._c, *self._tree, lp, mp, ip, stream),
-                           'gg_puct_select_leaves')
-            _lib.check(lib.gg_batch_play_moves_tracked(lp, mp, None, B, N, 1, stream), 'gg_batch_play_moves_tracked')
+            name, slots = ('gg_puct_select', ()) if self._L is None else ('gg_puct_select_leaves', (self._L,))
+            check(getattr(lib, name)(R, N, self._C, *slots, self._c, *self._tree, lp, mp, ip, stream), name)
+            check(lib.gg_batch_play_moves_tracked(lp, mp, None, B, N, 1, stream), 'gg_batch_play_moves_tracked')
             if self._feat is None:
-                _lib.check(lib.gg_batch_untrack_states(lp, sp, B, N, stream), 'gg_batch_untrack_states')
+                check(lib.gg_batch_untrack_states(lp, sp, B, N, stream), 'gg_batch_untrack_states')
             else:   # (sp: the planes)
                 op = None if self._sym is None else self._draw_orient(B, stream)
-                _plane_launch('gg_batch_features_tracked', lp, op, sp, False, self._feat[1], B, N, stream)
-            _lib.check(lib.gg_puct_legal(lp, ip, B, N, gp, vp, stream), 'gg_puct_legal')
+                _plane_launch('gg_batch_features_tracked', lp, op, sp, False, self._feat[1], B, N, stream, _lib.launch)
+            check(lib.gg_puct_legal(lp, ip, B, N, gp, vp, stream), 'gg_puct_legal')
             if self._sym is not None:
                 self._turn_legal(op, B, stream)
             if self._life:
-                _plane_launch('gg_batch_life_tracked', lp, op, _lib.dev_ptr(self._life_planes, self._feat[0], 'life'), None,
-                              self._feat[1], B, N, stream)
+                _plane_launch('gg_batch_life_tracked', lp, op, self._life_planes, None, self._feat[1], B, N, stream)
             if self._ladder:
-                _plane_launch('gg_batch_ladder_tracked', lp, op, _lib.dev_ptr(self._ladder_planes, self._feat[0], 'ladder'), None,
-                              self._feat[1], B, N, stream)
+                _plane_launch('gg_batch_ladder_tracked', lp, op, self._ladder_planes, None, self._feat[1], B, N, stream)
         self._pending = True
         legal = self._legal if self._sym is None else self._legal_view
         res = (self._states, legal, self._life_planes) if self._life else (self._states, legal)
@@ -1740,12 +1632,12 @@ class PuctSearch:
             if self._sym is not None:
                 priors = self._turn_priors_back(priors, B)
             boards, _, prior, links, stats, _ = self._tree
-            rows = (_lib.dev_ptr(priors, torch.float32, 'priors'), _lib.dev_ptr(values.reshape(B), torch.float32, 'values'),
-                    boards, prior, links, stats, *self._out, _lib.current_raw_stream(self._dev))
-            if self._L is None:
-                _lib.check(_lib.lib().gg_puct_backup(R, N, self._C, self._komi, *rows), 'gg_puct_backup')
-            else:
-                _lib.check(_lib.lib().gg_puct_backup_leaves(R, N, self._C, self._L, self._komi, *rows), 'gg_puct_backup_leaves')
+            name, slots = ('gg_puct_backup', ()) if self._L is None else ('gg_puct_backup_leaves', (self._L,))
+            kp, kv = self._rows     # (the evaluator's two tensors are checked every round, against the table's entry)
+            code = getattr(_lib.lib(), name)(R, N, self._C, *slots, self._komi, _lib.dev_ptr(priors, kp.kind, kp.name),
+                                             _lib.dev_ptr(values.reshape(B), kv.kind, kv.name), boards, prior, links, stats,
+                                             *self._out, _lib.current_raw_stream(self._dev))
+            _lib.check(code, name)
         self._pending = False
         self._done += 1
 
@@ -1781,8 +1673,7 @@ class PuctSearch:
             self._advance_buffers()
             with torch.cuda.device(self._dev):
                 self._next.copy_(self._boards[:, 0, :])
-            _lib.check(_lib.lib().gg_batch_untrack_states(_lib.dev_ptr(self._next, _I32, 'next'), _lib.dev_ptr(states, _U8, 'states'),
-                                                          R, N, _lib.current_raw_stream(self._dev)), 'gg_batch_untrack_states')
+            _lib.call('gg_batch_untrack_states', self._next, states, R, N, _lib.current_raw_stream(self._dev))
         return states
 
     def _advance_buffers(self):
@@ -1792,8 +1683,7 @@ class PuctSearch:
             self._next = torch.empty((R, tracked_words(self._N)), dtype=_I32, device=dev)
             self._remap = torch.empty((R, self._C + 1), dtype=_I32, device=dev)
             self._kept = torch.empty(R, dtype=_I32, device=dev)
-            self._scratch = tuple(_lib.dev_ptr(t, _I32, n) for t, n in ((self._next, 'next'), (self._remap, 'remap'),
-                                                                        (self._kept, 'kept'))) if R else ()
+            self._scratch = _lib.ptrs('gg_puct_advance', next=self._next, remap=self._remap, kept=self._kept) if R else ()
         return self._scratch
 
     def _play_on_roots(self, acts):
@@ -1803,11 +1693,10 @@ class PuctSearch:
         A = self._N * self._N + 1
         acts = torch.where((acts < -1) | (acts > A), torch.full_like(acts, A), acts).to(_I32).contiguous()
         np_, rp, kp = self._advance_buffers()
-        ap = _lib.dev_ptr(acts, _I32, 'actions')
+        ap, = _lib.ptrs('gg_puct_advance', actions=acts)
         with torch.cuda.device(self._dev):
             self._next.copy_(self._boards[:, 0, :])
-        stream = _lib.current_raw_stream(self._dev)
-        _lib.check(_lib.lib().gg_batch_play_moves_tracked(np_, ap, None, self._R, self._N, 1, stream), 'gg_batch_play_moves_tracked')
+        _lib.call('gg_batch_play_moves_tracked', np_, ap, None, self._R, self._N, 1, _lib.current_raw_stream(self._dev))
         return ap, np_, rp, kp
 
     def _played_states(self, acts):
@@ -1817,8 +1706,7 @@ class PuctSearch:
         states = torch.empty((R, govars.NUM_CHNLS, N, N), dtype=_U8, device=self._dev)
         if R:
             _, np_, _, _ = self._play_on_roots(acts)
-            _lib.check(_lib.lib().gg_batch_untrack_states(np_, _lib.dev_ptr(states, _U8, 'states'), R, N,
-                                                          _lib.current_raw_stream(self._dev)), 'gg_batch_untrack_states')
+            _lib.call('gg_batch_untrack_states', np_, states, R, N, _lib.current_raw_stream(self._dev))
         return states
 
     def advance(self, actions, iterations=None, check=True):
@@ -1852,8 +1740,7 @@ class PuctSearch:
                 r = int(bad[0, 0])
                 raise ValueError('PuctSearch.advance(): action %d is not legal at root %d' % (int(acts[r]), r))
         ap, np_, rp, kp = self._play_on_roots(acts)
-        _lib.check(_lib.lib().gg_puct_advance(ap, np_, R, N, self._C, *self._tree, rp, kp, _lib.current_raw_stream(self._dev)),
-                   'gg_puct_advance')
+        _lib.call('gg_puct_advance', ap, np_, R, N, self._C, *self._tree, rp, kp, _lib.current_raw_stream(self._dev))
         self._legal_roots = _legal_roots(self._root_states())
         self._done, self._I = 0, rounds
         return self._kept
@@ -1885,9 +1772,8 @@ class PuctSearch:
         if R:
             noise = noise.to(device=self._dev, dtype=torch.float32).contiguous()
             boards, _, prior, _, stats, nodes = self._tree
-            _lib.check(_lib.lib().gg_puct_root_noise(R, self._N, self._C, eps, _lib.dev_ptr(noise, torch.float32, 'noise'),
-                                                     _lib.dev_ptr(todo, todo.dtype, 'todo'), boards, prior, stats, nodes,
-                                                     _lib.current_raw_stream(self._dev)), 'gg_puct_root_noise')
+            _lib.call('gg_puct_root_noise', R, self._N, self._C, eps, noise, todo, boards, prior, stats, nodes,
+                      _lib.current_raw_stream(self._dev))
         return todo
 
     def root_policy(self, sample=None, rng=None, pi=True):
@@ -1923,12 +1809,8 @@ class PuctSearch:
         v = torch.empty(R, dtype=torch.float32, device=dev)
         if R:
             boards, child, _, _, stats, nodes = self._tree
-            d = _lib.dev_ptr
-            _lib.check(_lib.lib().gg_puct_root_policy(R, self._N, self._C, None if sample is None else d(sample, sample.dtype, 'sample'),
-                                                      d(rng, _I64, 'rng') if sample is not None else None, boards, child, stats,
-                                                      nodes, d(acts, _I32, 'actions'), d(p, torch.float32, 'pi'),
-                                                      d(v, torch.float32, 'value'), _lib.current_raw_stream(dev)),
-                       'gg_puct_root_policy')
+            _lib.call('gg_puct_root_policy', R, self._N, self._C, sample, rng if sample is not None else None, boards, child, stats,
+                      nodes, acts, p, v, _lib.current_raw_stream(dev))
         return acts, p, v
 
 
@@ -2304,10 +2186,7 @@ def batch_sample_weighted(batch_states, weights, rng, check=False):
         N = int(round((weights.shape[1] - 1) ** 0.5))
     w, wcode = _weights_tensor(weights, B, N, dev)
     actions = torch.empty(B, dtype=_I32, device=dev)
-    code = _lib.lib().gg_batch_sample_weighted(
-        _lib.dev_ptr(batch_states, _U8, 'states'), _lib.dev_ptr(w, w.dtype, 'weights'), wcode, _lib.dev_ptr(rng, _I64, 'rng'),
-        _lib.dev_ptr(actions, _I32, 'actions'), B, N, _lib.stream_ptr(dev))
-    _lib.check(code, 'gg_batch_sample_weighted')
+    _lib.call('gg_batch_sample_weighted', batch_states, w, wcode, rng, actions, B, N, _lib.stream_ptr(dev))
     return _check_drawn(actions, check)
 
 
@@ -2320,10 +2199,7 @@ def batch_sample_weighted_rows(boards, board_size, weights, rng, check=False):
         raise ValueError('boards must be packed [B, 3N+1] or tracked [B, 5N+1] int32 for N = %d (got %s)' % (N, tuple(boards.shape)))
     w, wcode = _weights_tensor(weights, B, N, boards.device)
     actions = torch.empty(B, dtype=_I32, device=boards.device)
-    code = _lib.lib().gg_batch_sample_weighted_rows(
-        _lib.dev_ptr(boards, _I32, 'boards'), planes, _lib.dev_ptr(w, w.dtype, 'weights'), wcode, _lib.dev_ptr(rng, _I64, 'rng'),
-        _lib.dev_ptr(actions, _I32, 'actions'), B, N, _lib.stream_ptr(boards.device))
-    _lib.check(code, 'gg_batch_sample_weighted_rows')
+    _lib.call('gg_batch_sample_weighted_rows', boards, planes, w, wcode, rng, actions, B, N, _lib.stream_ptr(boards.device))
     return _check_drawn(actions, check)
 
 
@@ -2354,9 +2230,7 @@ def batch_symmetry(batch_images, orient=None, out=None):
         raise ValueError('out must be uint8 %s' % (shape,))
     if orient is not None:
         orient = _actions_tensor(orient, B, dev)
-    code = _lib.lib().gg_batch_symmetry(_lib.dev_ptr(batch_images, _U8, 'images'), _lib.dev_ptr(orient, _I32, 'orient'),
-                                        _lib.dev_ptr(out, _U8, 'out'), B, C, N, _lib.stream_ptr(dev))
-    _lib.check(code, 'gg_batch_symmetry')
+    _lib.call('gg_batch_symmetry', batch_images, orient, out, B, C, N, _lib.stream_ptr(dev))
     return out
 
 
@@ -2371,9 +2245,7 @@ def batch_symmetry_rows(boards, board_size, orient=None):
     out = torch.empty((B, W) if orient is not None else (B, 8, W), dtype=_I32, device=boards.device)
     if orient is not None:
         orient = _actions_tensor(orient, B, boards.device)
-    code = _lib.lib().gg_batch_symmetry_rows(_lib.dev_ptr(boards, _I32, 'boards'), planes, _lib.dev_ptr(orient, _I32, 'orient'),
-                                             _lib.dev_ptr(out, _I32, 'out'), B, N, _lib.stream_ptr(boards.device))
-    _lib.check(code, 'gg_batch_symmetry_rows')
+    _lib.call('gg_batch_symmetry_rows', boards, planes, orient, out, B, N, _lib.stream_ptr(boards.device))
     return out
 
 
@@ -2450,9 +2322,7 @@ def batch_symmetry_policy(policy, orient, inverse=False, out=None):
     elif B and out.data_ptr() < policy.data_ptr() + B * A * es and policy.data_ptr() < out.data_ptr() + B * A * es:
         raise ValueError('out overlaps policy')
     o = _actions_tensor(orient, B, policy.device)
-    _lib.check(_lib.lib().gg_batch_symmetry_policy(_lib.dev_ptr(policy, policy.dtype, 'policy'), _lib.dev_ptr(o, _I32, 'orient'),
-                                                   _lib.dev_ptr(out, out.dtype, 'out'), es, 1 if inverse else 0, B, N,
-                                                   _lib.stream_ptr(policy.device)), 'gg_batch_symmetry_policy')
+    _lib.call('gg_batch_symmetry_policy', policy, o, out, es, 1 if inverse else 0, B, N, _lib.stream_ptr(policy.device))
     return out.cpu().numpy() if is_np else out
 
 
@@ -2463,8 +2333,7 @@ def batch_draw_orient(rng):
         raise ValueError('rng must be a contiguous int64 [B] device tensor (gogame.rng_seed)')
     B = rng.shape[0]
     orient = torch.empty(B, dtype=_I32, device=rng.device)
-    _lib.check(_lib.lib().gg_batch_draw_orient(_lib.dev_ptr(rng, _I64, 'rng'), _lib.dev_ptr(orient, _I32, 'orient'), B,
-                                               _lib.stream_ptr(rng.device)), 'gg_batch_draw_orient')
+    _lib.call('gg_batch_draw_orient', rng, orient, B, _lib.stream_ptr(rng.device))
     return orient
 
 

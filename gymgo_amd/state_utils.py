@@ -136,10 +136,7 @@ def batch_update_pieces(batch_non_pass, batch_state, batch_adj_locs, batch_playe
     killed = torch.empty((B, N, N), dtype=torch.uint8, device=t.device)
     adj_t = torch.from_numpy(adj).to(t.device)
     pls = torch.from_numpy(players).to(t.device)
-    code = _lib.lib().gg_batch_update_pieces(_lib.dev_ptr(t, torch.uint8, 'states'), _lib.dev_ptr(adj_t, torch.int32, 'adj'),
-                                             adj.shape[1], _lib.dev_ptr(pls, torch.int32, 'players'),
-                                             _lib.dev_ptr(killed, torch.uint8, 'killed'), B, N, _lib.stream_ptr(t.device))
-    _lib.check(code, 'gg_batch_update_pieces')
+    _lib.call('gg_batch_update_pieces', t, adj_t, adj.shape[1], pls, killed, B, N, _lib.stream_ptr(t.device))
     if is_t:
         batch_state[torch.as_tensor(idx, device=batch_state.device)] = t.to(batch_state.dtype)
     else:

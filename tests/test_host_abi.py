@@ -233,3 +233,96 @@ def test_cu_count_override_is_read_from_the_environment(built):
     base = run(None)
     assert run('0') == base and run('-3') == base and run('5000') == base and run('many') == base
     assert run('12abc') == base and run('8 ') == base and run('') == base      # a typo is ignored, not read as 12 / 8
+
+
+# ---------------------------------------------------------------- the binding table against the header
+
+_SCALARS = {'int32_t': 'c_int32', 'int64_t': 'c_int64', 'uint64_t': 'c_uint64', 'float': 'c_float', 'double': 'c_double'}
+_POINTEES = {'uint32_t': 'int32', 'int32_t': 'int32', 'uint64_t': 'int64', 'int64_t': 'int64', 'float': 'float32',
+             'double': 'float64', 'gg_puct_stat': 'int32'}
+
+
+def _header_declarations():
+    """{function: [(C type without const, is pointer, parameter name)]} of every `int32_t gg_*(...);` of the header."""
+    hdr = open(os.path.join(ROOT, 'include', 'gymgo_amd.h')).read()
+    decls = {}
+    for m in re.finditer(r'^\s*(?:int32_t|int)\s+(gg_\w+)\s*\((.*?)\);', hdr, flags=re.M | re.S):
+        params = []
+        for text in m.group(2).split(','):
+            text = ' '.join(text.split())
+            if text == 'void':
+                continue
+            pm = re.fullmatch(r'(?:const )?(\w+) ?(\*?) ?(\w+)', text)
+            assert pm, (m.group(1), text)
+            params.append((pm.group(1), pm.group(2) == '*', pm.group(3)))
+        decls[m.group(1)] = params
+    return decls
+
+
+def _abi_mismatches(decls, table):
+    """Every difference between the header's declarations and a binding table, as readable strings."""
+    import ctypes
+    import torch
+    bad = ['%s: declared in only one of header and table' % f for f in sorted(set(decls) ^ set(table))]
+    for f in sorted(set(decls) & set(table)):
+        if len(decls[f]) != len(table[f]):
+            bad.append('%s: %d parameters in the header, %d in the table' % (f, len(decls[f]), len(table[f])))
+            continue
+        for i, ((ctype, pointer, name), p) in enumerate(zip(decls[f], table[f])):
+            where = '%s parameter %d (%s)' % (f, i, name)
+            if p.name != name:
+                bad.append('%s: the table calls it %s' % (where, p.name))
+            if not pointer:
+                if p.kind is not getattr(ctypes, _SCALARS[ctype]):
+                    bad.append('%s: %s in the header, %r in the table' % (where, ctype, p.kind))
+                continue
+            if name == 'hip_stream':
+                if ctype != 'void' or p.kind is not ctypes.c_void_p:
+                    bad.append('%s: the stream must be a plain c_void_p, got %r' % (where, p.kind))
+                continue
+            dtypes = p.kind if isinstance(p.kind, tuple) else (p.kind,)
+            if not dtypes or not all(isinstance(d, torch.dtype) for d in dtypes):
+                bad.append('%s: a pointer needs torch dtype(s), got %r' % (where, p.kind))
+            elif ctype in ('void', 'uint8_t'):
+                if ctype == 'uint8_t' and len(dtypes) == 1 and dtypes[0] not in (torch.uint8, torch.bool):
+                    bad.append('%s: uint8_t * bound to %r alone' % (where, p.kind))
+            elif p.kind is not getattr(torch, _POINTEES[ctype]):
+                bad.append('%s: %s * in the header, %r in the table' % (where, ctype, p.kind))
+    return bad
+
+
+def test_binding_table_matches_the_header():
+    """Every parameter of every entry point: count, name, kind and width, and the tensor dtype a typed pointer takes."""
+    from gymgo_amd import _lib
+    decls = _header_declarations()
+    hdr = open(os.path.join(ROOT, 'include', 'gymgo_amd.h')).read()
+    assert set(decls) == set(re.findall(r'^\s*(?:int32_t|int)\s+(gg_\w+)\s*\(', hdr, flags=re.M)) and len(decls) == len(_lib.EXPORTS)
+    assert _abi_mismatches(decls, _lib.ABI) == []
+    assert _lib.EXPORTS == tuple(decls)          # header order
+    for f, (argtypes, restype) in _lib._SIGNATURES.items():   # what lib() hands ctypes comes from the same table
+        assert restype is ctypes.c_int32
+        assert argtypes == [p.kind if isinstance(p.kind, type) else ctypes.c_void_p for p in _lib.ABI[f]]
+
+
+def test_binding_table_check_can_fail():
+    """The comparison above reports a dropped parameter, a narrowed int64_t and two swapped names."""
+    from gymgo_amd import _lib
+    decls = _header_declarations()
+    f = 'gg_batch_areas'      # states, black, white, B, N, hip_stream
+    ps = _lib.ABI[f]
+    assert [p.name for p in ps[:4]] == ['states', 'black', 'white', 'B'] and ps[3].kind is ctypes.c_int64
+    dropped = dict(_lib.ABI, **{f: ps[:2] + ps[3:]})
+    narrowed = dict(_lib.ABI, **{f: ps[:3] + (ps[3]._replace(kind=ctypes.c_int32),) + ps[4:]})
+    swapped = dict(_lib.ABI, **{f: (ps[0], ps[2], ps[1]) + ps[3:]})
+    for table, word in ((dropped, '6 parameters in the header, 5 in the table'), (narrowed, 'int64_t in the header'),
+                        (swapped, 'the table calls it white')):
+        bad = _abi_mismatches(decls, table)
+        assert bad and all(b.startswith(f) for b in bad) and any(word in b for b in bad), bad
+    assert _abi_mismatches(decls, _lib.ABI) == []      # the copies left the table alone
+
+
+def test_call_counts_its_arguments_before_anything_is_loaded(monkeypatch):
+    from gymgo_amd import _lib
+    monkeypatch.setattr(_lib, 'lib', lambda: pytest.fail('the library was loaded'))
+    with pytest.raises(TypeError, match='gg_batch_areas'):
+        _lib.call('gg_batch_areas', None)
