@@ -139,27 +139,64 @@ constexpr int flood_first_test() {
 static __device__ unsigned long long gg_sweeps5[10];
 #endif
 
+// A/B switches of round 17 (make ab EXTRA=-DGG_AB_LIBSUM=0 ...; the defaults are what measured best together, docs/history/r17.md:
+// +3.0 % on the headline launch; the third alone +1.2 %, the first alone nothing):
+// GG_AB_LIBSUM 1: job_liberties keeps the OR and the SUM of the liberty rows, 0: the OR and the doubly-set columns (round 8's form);
+// GG_AB_PEEL 1: the first trip of flood_jobs<19> is straight-line code in front of its loop, 0: the loop alone;
+// GG_AB_PRIO 1: the wave's priority is lowered directly in front of the flood, 0: in front of the job set-up (gg_v5_kernel.h).
+#ifndef GG_AB_LIBSUM
+#define GG_AB_LIBSUM 1
+#endif
+#ifndef GG_AB_PEEL
+#define GG_AB_PEEL 1
+#endif
+#ifndef GG_AB_PRIO
+#define GG_AB_PRIO 1
+#endif
+
 // liberties (dilate & empty) of the group gt[], SATURATED: min(count, 2) - all any caller uses; m[] = the rows of its colour,
 // ot[] = the other colour's rows (read from LDS together with m[], BEFORE the flood: read behind it they cost the lane a round
-// trip).  Nothing is counted: o = the OR of the liberty rows, d = the columns that hold a liberty in two rows (a liberty row
-// ANDed with the OR of the rows before it, one v_bitop3 per row); two or more liberties iff d != 0 or o has two bits.  Three
-// chains over the rows r % 3, joined by a majority (a column set in two chains).  (Counting took nineteen v_bcnt, 4 cycles each.)
+// trip).  Nothing is counted: o = the OR of the liberty rows, S = their integer SUM (R rows below 2^R: no carry leaves the
+// word).  S - o = the sum over the columns c of (n_c - [n_c > 0]) 2^c, n_c = the rows that hold a liberty in column c: zero iff
+// no column is set in two rows, and S >= o >= the lowest bit of o.  So there are two or more liberties iff a column is set twice
+// (S != o) or o has two bits - in one test, iff S != o & -o.  Five instructions a row: four form the liberty row, and one
+// v_or3_b32 and one v_add3_u32 take in two rows each.  Three chains over the row pairs p % 3 (for an odd R row 0 starts chain 0
+// for nothing), joined by one v_or3 / v_add3.  (Round 8 kept o and the doubly-set columns, one v_bitop3 a row each: six a row
+// and a majority to join the chains; counting took nineteen v_bcnt.)
 template <int R>
 __device__ __forceinline__ uint32_t job_liberties(const uint32_t (&gt)[R], const uint32_t (&ot)[R], const uint32_t (&m)[R]) {
   constexpr uint32_t FULLROW = (1u << R) - 1u;
-  uint32_t o3[3] = {0u, 0u, 0u}, d3[3] = {0u, 0u, 0u};
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
+  static_assert(R < 27, "the sum of R rows below 2^R stays inside 32 bits");
+  auto row = [&](int r) -> uint32_t {
     const uint32_t e = B3(ot[r], m[r], FULLROW, ~(TA | TB) & TC & 0xFF);   // empty points
     const uint32_t up = r > 0 ? gt[r - 1] : 0u, dn = r + 1 < R ? gt[r + 1] : 0u;
     const uint32_t dd = B3(shl1(gt[r]), gt[r] >> 1, up, T_OR3);
-    const uint32_t l = B3(dd, dn, e, (TA | TB) & TC);
+    return B3(dd, dn, e, (TA | TB) & TC);
+  };
+#if GG_AB_LIBSUM
+  uint32_t o3[3] = {0u, 0u, 0u}, s3[3] = {0u, 0u, 0u};
+  if (R & 1) o3[0] = s3[0] = row(0);
+#pragma unroll
+  for (int r = R & 1; r < R; r += 2) {
+    const int c = (r / 2) % 3;
+    const uint32_t la = row(r), lb = row(r + 1);
+    o3[c] = la | lb | o3[c];   // v_or3_b32
+    s3[c] = la + lb + s3[c];   // v_add3_u32
+  }
+  const uint32_t o = o3[0] | o3[1] | o3[2], s = s3[0] + s3[1] + s3[2];
+  const uint32_t two = B3(o, 0u - o, s, (TA & TB) ^ TC);   // (o & -o) ^ S
+#else
+  uint32_t o3[3] = {0u, 0u, 0u}, d3[3] = {0u, 0u, 0u};
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const uint32_t l = row(r);
     d3[r % 3] = B3(l, o3[r % 3], d3[r % 3], T_ANDOR);
     o3[r % 3] = B3(l, o3[r % 3], 0u, T_OR3);
   }
   const uint32_t o = B3(o3[0], o3[1], o3[2], T_OR3);
   const uint32_t d = B3(d3[0], d3[1], d3[2], T_OR3) | B3(o3[0], o3[1], o3[2], T_MAJ);
   const uint32_t two = B3(o - 1u, o, d, T_ANDOR);   // o & (o - 1) | d
+#endif
   return (o != 0u ? 1u : 0u) + (two != 0u ? 1u : 0u);
 }
 
@@ -265,43 +302,64 @@ __device__ __forceinline__ uint32_t flood_jobs(const uint32_t (&m)[R], const uin
     resumed = true;
     return u == 0;
   };
-#pragma unroll 1
-  for (int it = 0; it < R * R; ++it) {
+  auto sweep_down = [&]() {   // domain (r&1) -> ((r+1)&1)
 #pragma unroll
-    for (int r = 0; r < R; ++r) FLOOD_VISIT(r, r - 1, (r & 1) != 0);       // down: domain (r&1) -> ((r+1)&1)
+    for (int r = 0; r < R; ++r) FLOOD_VISIT(r, r - 1, (r & 1) != 0);
     GG_SW5_SWEEP();
-    if (K <= 1 || it > 0) {
-      uint32_t op = 0, opw = 0, above = 0;
+  };
+  auto sweep_up = [&]() {     // domain ((r+1)&1) -> (r&1)
 #pragma unroll
-      for (int r = R - 1; r >= 0; --r) {
-        const uint32_t g = ((r + 1) & 1) ? __brev(f[r]) : f[r];
-        res[r] = g;
-        if (r < R - 1) {
-          const uint32_t t = B3(above, m[r], g, T_AND_ANDN);   // a filled stone below a fillable, unfilled one
-          op |= t;
-          opw = B3(t, mm[r], opw, (TA & ~TB & 0xFF) | TC);
-        }
-        above = g;
+    for (int r = R - 1; r >= 0; --r) FLOOD_VISIT(r, r + 1, ((r + 1) & 1) != 0);
+    GG_SW5_SWEEP();
+  };
+  // the test after a down sweep (is the fill closed UPWARDS?) and after an up sweep (downwards), with what follows it
+  auto done_after_down = [&]() -> bool {
+    uint32_t op = 0, opw = 0, above = 0;
+#pragma unroll
+    for (int r = R - 1; r >= 0; --r) {
+      const uint32_t g = ((r + 1) & 1) ? __brev(f[r]) : f[r];
+      res[r] = g;
+      if (r < R - 1) {
+        const uint32_t t = B3(above, m[r], g, T_AND_ANDN);   // a filled stone below a fillable, unfilled one
+        op |= t;
+        opw = B3(t, mm[r], opw, (TA & ~TB & 0xFF) | TC);
       }
-      if (done(op, opw)) break;
+      above = g;
     }
+    return done(op, opw);
+  };
+  auto done_after_up = [&]() -> bool {
+    uint32_t op = 0, opw = 0, below = 0;
 #pragma unroll
-    for (int r = R - 1; r >= 0; --r) FLOOD_VISIT(r, r + 1, ((r + 1) & 1) != 0);  // up: domain ((r+1)&1) -> (r&1)
-    GG_SW5_SWEEP();
-    if (K <= 2 || it > 0) {
-      uint32_t op = 0, opw = 0, below = 0;
-#pragma unroll
-      for (int r = 0; r < R; ++r) {
-        const uint32_t g = (r & 1) ? __brev(f[r]) : f[r];
-        res[r] = g;
-        if (r > 0) {
-          const uint32_t t = B3(below, m[r], g, T_AND_ANDN);
-          op |= t;
-          opw = B3(t, mm[r], opw, (TA & ~TB & 0xFF) | TC);
-        }
-        below = g;
+    for (int r = 0; r < R; ++r) {
+      const uint32_t g = (r & 1) ? __brev(f[r]) : f[r];
+      res[r] = g;
+      if (r > 0) {
+        const uint32_t t = B3(below, m[r], g, T_AND_ANDN);
+        op |= t;
+        opw = B3(t, mm[r], opw, (TA & ~TB & 0xFF) | TC);
       }
-      if (done(op, opw)) break;
+      below = g;
+    }
+    return done(op, opw);
+  };
+  // The first trip with the test after down + up (K == 2), peeled out of the loop as straight-line code: 74 % of the batches end
+  // here (profiles/r12_sweeps.txt).  The others enter the loop at its next down sweep with the fill, res[], cnt and `resumed` as
+  // the loop itself would have them there; from then on every sweep has its test.
+  constexpr bool PEEL = GG_AB_PEEL != 0 && K == 2;
+  bool fin = false;
+  if constexpr (PEEL) {
+    sweep_down();
+    sweep_up();
+    fin = done_after_up();
+  }
+  if (!fin) {
+#pragma unroll 1
+    for (int it = PEEL ? 1 : 0; it < R * R; ++it) {
+      sweep_down();
+      if ((PEEL || K <= 1 || it > 0) && done_after_down()) break;
+      sweep_up();
+      if ((PEEL || K <= 2 || it > 0) && done_after_up()) break;
     }
   }
 #undef GG_SW5_SWEEP

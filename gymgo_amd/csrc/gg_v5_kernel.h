@@ -428,7 +428,7 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
       // group (dilate & empty, saturated at 2), all rows in registers; the class word: bits 0-1 liberties, 5 an opponent group
       // without a liberty (captured).  An opponent group that keeps >= 2 liberties zeroes
       // its block: phase 3 never sees it.
-      if (plies >= 8) { if (lead) __builtin_amdgcn_s_setprio(0); else __builtin_amdgcn_s_setprio(1); }
+      if (!GG_AB_PRIO && plies >= 8) { if (lead) __builtin_amdgcn_s_setprio(0); else __builtin_amdgcn_s_setprio(1); }
 #pragma unroll 1
       for (int jb = 0; jb < njobs; jb += kWave) {
         const int j = jb + ln;
@@ -507,6 +507,9 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
           // 19x19: while a lane is unsettled the loop goes on IN PLACE, one sweep and its test at a time (flood_jobs): no
           // restart from a re-encoded fill, the liberties taken once per test.
           // (the two-chain flood2_dual: 1.758 against 1.579 ms per launch - one more sweep-equivalent, as in k_rollout4)
+          // the wave's priority falls HERE, in front of the dependent VALU chain it was introduced for, and not in front of the job loop:
+          // the set-up above is LDS round trips (round 17: +1.2 % on the headline launch alone, and what makes the shorter flood pay; -DGG_AB_PRIO=0 in A/B builds for the old place)
+          if (GG_AB_PRIO && plies >= 8) { if (lead) __builtin_amdgcn_s_setprio(0); else __builtin_amdgcn_s_setprio(1); }
           if constexpr (R == 19) {
             cnt = flood_jobs<R>(m, mrev, f, res, ot, mm, isG != 0u, have);
             GG_PROF(2);   // (with the liberties, which the loop takes after its tests)
