@@ -297,7 +297,7 @@ KO_POINT = (1, 1)
 
 
 def crafted_roots(N):
-    """Hand-made roots of size N >= 5: [the empty board, a root whose last move was a pass (its pass child is terminal), a
+    """Hand-made roots of size N >= 4 (3 has no room for the ko shape): [the empty board, a root whose last move was a pass (its pass child is terminal), a
     root with an active ko point at KO_POINT (white to move may not retake), a finished game]."""
     empty = np.zeros((6, N, N), np.uint8)
     passed = c_oracle.next_state(c_oracle.next_state(empty, (N // 2) * N + N // 2), N * N)   # black plays, white passes

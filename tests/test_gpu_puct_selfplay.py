@@ -102,14 +102,13 @@ CASES = [(5, None, 'hash'), (5, 4, 'hostile'), (9, None, 'hostile'), (9, 1, 'has
          (19, 1, 'hostile'), (19, 4, 'hostile')]
 
 
-@pytest.mark.parametrize('N,L,name', CASES)
-def test_noise_and_policy_on_searched_trees(N, L, name):
+def noise_and_policy_on_searched_trees(roots, L, name, kinds=frozenset(('ended', 'kept', 'fresh'))):
+    """kinds: what the move between the two searches must leave among the roots."""
     import torch
     from gymgo_amd import gogame
     T, eps = 6, 0.25
-    roots = _roots(N, 60 + N)
+    N = roots.shape[-1]
     R, A = roots.shape[0], N * N + 1
-    assert R == 7
     s = gogame.PuctSearch(mc.to_dev(roots), T, komi=0.5, leaves=L, capacity=3 * T * (L or 1) + 5)
     s._boards[:, 1:] = MARK
     trees = pa.make_trees(roots, s._C + 1, L)
@@ -136,8 +135,8 @@ def test_noise_and_policy_on_searched_trees(N, L, name):
     s.advance(mc.to_dev(np.array(acts, np.int64)))
     for t, a in zip(trees, acts):
         pa.advance(t, a, pa.next_root(t, a))
-    kinds = ['ended' if t.legal[0].size == 0 else ('kept' if t.n[0] > 0 else 'fresh') for t in trees]
-    assert {'ended', 'kept', 'fresh'} <= set(kinds), kinds
+    want_kinds, kinds = kinds, ['ended' if t.legal[0].size == 0 else ('kept' if t.n[0] > 0 else 'fresh') for t in trees]
+    assert want_kinds <= set(kinds), kinds
     z = _odd_noise(R, A, salt=1)
     todo = torch.ones(R, dtype=torch.bool, device='cuda')
     assert s.add_root_noise(mc.to_dev(z), eps, todo) is todo
@@ -159,6 +158,13 @@ def test_noise_and_policy_on_searched_trees(N, L, name):
     assert pi2 is None and np.array_equal(mc.to_np(acts2), [pa.most_visited_root(t) for t in trees])
     got = s.result()
     assert np.array_equal(mc.to_np(acts2), mc.to_np(gogame._best_legal(gogame._ON_DEVICE, got.legal, got.visits.long())))
+
+
+@pytest.mark.parametrize('N,L,name', CASES)
+def test_noise_and_policy_on_searched_trees(N, L, name):
+    roots = _roots(N, 60 + N)
+    assert roots.shape[0] == 7
+    noise_and_policy_on_searched_trees(roots, L, name)
 
 
 def _hand_made_trees(N, C):
