@@ -150,6 +150,9 @@ ABI = {
     'gg_batch_life_tracked': _params(_I32, 'tracked', 'orient') + _OUT + _params(_U8, 'settled') + _OUT_BN,
     'gg_batch_ladder': _params(_U8, 'states') + _params(_I32, 'orient') + _OUT + _params(_U8, 'aborted') + _OUT_BN,
     'gg_batch_ladder_tracked': _params(_I32, 'tracked', 'orient') + _OUT + _params(_U8, 'aborted') + _OUT_BN,
+    'gg_batch_move_planes': _params(_U8, 'states') + _params(_I32, 'orient') + _OUT + _OUT_BN,
+    'gg_batch_move_planes_tracked': _params(_I32, 'tracked', 'orient') + _OUT + _OUT_BN,
+    'gg_batch_move_counts': _params(_U8, 'states', 'out') + _BN,
 }
 EXPORTS = tuple(ABI)
 _SIGNATURES = {f: ([p.kind if isinstance(p.kind, type) else _vp for p in ps], _i32) for f, ps in ABI.items()}   # argtypes, restype

@@ -801,11 +801,17 @@ def _orient_arg(orient, B):
         raise ValueError('orient must be %d integers in 0..7, one per row (got %d of %s)' % (B, n, orient.dtype))
 
 
+_NO_BYTES = ()   # _plane_launch's extra of an entry point that takes orient itself and writes no per-board bytes
+
+
 def _plane_launch(name, boards, orient, out, extra, code, B, N, stream, launch=_lib.call):
     """One launch of a plane entry point on tensors (_lib.call) or, launch=_lib.launch, on prepared pointers alone.  name: gg_batch_features[_tracked] - its
     _oriented form when orient is given, and no per-board bytes (extra is False) - or gg_batch_life[_tracked] /
-    gg_batch_ladder[_tracked], which take orient (or None) and the per-board bytes (or None) themselves."""
-    if extra is not False:
+    gg_batch_ladder[_tracked], which take orient (or None) and the per-board bytes (or None) themselves, or
+    gg_batch_move_planes[_tracked], which take orient (or None) and have no per-board bytes (extra is _NO_BYTES)."""
+    if extra is _NO_BYTES:
+        args = (boards, orient, out)
+    elif extra is not False:
         args = (boards, orient, out, extra)
     elif orient is None:
         args = (boards, out)
@@ -815,10 +821,11 @@ def _plane_launch(name, boards, orient, out, extra, code, B, N, stream, launch=_
 
 
 def _planes(name, count, align, boards, tracked, dtype, out, orient, extra=None):
-    """The body of the six batch plane calls: `count` planes per board from byte planes (a tensor or an array) or, `tracked`,
+    """The body of the eight batch plane calls: `count` planes per board from byte planes (a tensor or an array) or, `tracked`,
     from tracked boards (a device tensor), through the C entry point `name` (_plane_launch), into `out` (aligned to
-    `align` bytes) or a new tensor.  extra: None (the entry point has no per-board bytes), or whether they are wanted
-    -> planes, or (planes, bytes uint8 [B]).  Every ValueError comes before a device is touched."""
+    `align` bytes) or a new tensor.  extra: None (the entry point has no per-board bytes and an _oriented form), _NO_BYTES
+    (none either, orient is a parameter), or whether they are wanted -> planes, or (planes, bytes uint8 [B]).  Every
+    ValueError comes before a device is touched."""
     code = _feature_dtype(dtype)
     if tracked:
         if not isinstance(boards, torch.Tensor) or boards.dim() != 2:
@@ -842,7 +849,8 @@ def _planes(name, count, align, boards, tracked, dtype, out, orient, extra=None)
     planes = out if out is not None else torch.empty((B, count, N, N), dtype=dtype, device=st.device)
     bytes_ = torch.empty(B, dtype=_U8, device=st.device) if extra else None
     o = None if orient is None else _actions_tensor(orient, B, st.device)
-    _plane_launch(name, st, o, planes, False if extra is None else bytes_, code, B, N, _lib.stream_ptr(st.device))
+    _plane_launch(name, st, o, planes, False if extra is None else _NO_BYTES if extra is _NO_BYTES else bytes_, code, B, N,
+                  _lib.stream_ptr(st.device))
     if box is not None:
         planes, bytes_ = _back(box, planes), _back(box, bytes_)
     return (planes, bytes_) if extra else planes
@@ -969,6 +977,61 @@ def batch_ladder_tracked(tracked, dtype=torch.uint8, out=None, orient=None, abor
     """batch_ladder of tracked boards (int32 [B, 5N+1], a device tensor) -> [B, 4, N, N] of `dtype` (gg_batch_ladder_tracked):
     bit for bit what batch_ladder gives for batch_untrack(tracked); the class rows are not read."""
     return _planes('gg_batch_ladder_tracked', LADDER_PLANES, 1, tracked, True, dtype, out, orient, bool(aborted))
+
+
+# ---------------------------------------------------------------- move-outcome planes
+MOVE_PLANES = 12   # GG_MOVE_PLANES of include/gymgo_amd.h
+MOVE_COUNTS = 3    # GG_MOVE_COUNTS
+MOVE_NAMES = ('libs_after_1', 'libs_after_2', 'libs_after_3', 'libs_after_4plus', 'captures_1', 'captures_2', 'captures_3',
+              'captures_4plus', 'self_atari_1', 'self_atari_2', 'self_atari_3', 'self_atari_4plus')
+MOVE_COUNT_NAMES = ('libs_after', 'captured', 'chain_size')
+
+
+def batch_move_planes(batch_states, dtype=torch.uint8, out=None, orient=None):
+    """Move-outcome planes of every board -> [B, 12, N, N] of `dtype` (gg_batch_move_planes), from the mover's point of view,
+    each value exactly 0 or 1 (MOVE_NAMES).  For every candidate point - empty, plane 3 clear, game not over: the legal plane
+    of batch_features - a stone of the mover is put there, the opponent chains left without a liberty are removed
+    (captured = their stones), and the chain of the played stone has libs liberties and size stones:
+       0 -  3  libs     exactly 1 / exactly 2 / exactly 3 / >= 4
+       4 -  7  captured exactly 1 / exactly 2 / exactly 3 / >= 4
+       8 - 11  a self-atari (libs exactly 1) of a chain of exactly 1 / exactly 2 / exactly 3 / >= 4 stones
+    A candidate whose chain would have no liberty (a suicide: only with a plane 3 that is not the true mask) and every point
+    that is no candidate is in no plane.  Exact, from the stones alone; the definition: include/gymgo_amd.h.  dtype:
+    torch.uint8, float16, bfloat16 or float32 (ValueError otherwise).  out: a contiguous device tensor of that shape and
+    dtype to write into.  orient (None, or int [B], only orient & 7 is read): row b is view orient[b] of its planes - also the
+    planes of the turned position.  NumPy in gives NumPy out (through the device; not for bfloat16).  One launch; device
+    memory of the result: 12 * B * N^2 elements - against the (N^2 + 1) * 6 * N^2 bytes per board of batch_children."""
+    return _planes('gg_batch_move_planes', MOVE_PLANES, 1, batch_states, False, dtype, out, orient, _NO_BYTES)
+
+
+def move_planes(state, dtype=torch.uint8):
+    """batch_move_planes of one state [6, N, N] -> [12, N, N]."""
+    return _plane_single(batch_move_planes, state, dtype)
+
+
+def batch_move_planes_tracked(tracked, dtype=torch.uint8, out=None, orient=None):
+    """batch_move_planes of tracked boards (int32 [B, 5N+1], a device tensor) -> [B, 12, N, N] of `dtype`
+    (gg_batch_move_planes_tracked): bit for bit what batch_move_planes gives for batch_untrack(tracked); the class rows
+    are not read."""
+    return _planes('gg_batch_move_planes_tracked', MOVE_PLANES, 1, tracked, True, dtype, out, orient, _NO_BYTES)
+
+
+def batch_move_counts(batch_states):
+    """The numbers behind batch_move_planes -> uint8 [B, 3, N, N] (gg_batch_move_counts; MOVE_COUNT_NAMES): at every
+    candidate point min(libs, 255), min(captured, 255), min(size, 255) of the move there, all three 0 for a suicide and at
+    every point that is no candidate.  One launch; device memory of the result: 3 * B * N^2 bytes."""
+    B, N = _states_shape(batch_states)
+    box = _Box(batch_states)
+    st = box.t
+    counts = torch.empty((B, MOVE_COUNTS, N, N), dtype=_U8, device=st.device)
+    _lib.call('gg_batch_move_counts', st, counts, B, N, _lib.stream_ptr(st.device))
+    return _back(box, counts)
+
+
+def move_counts(state):
+    """batch_move_counts of one state [6, N, N] -> uint8 [3, N, N]."""
+    box = _Box(state)
+    return _back(box, batch_move_counts(box.t[None]), row0=True)
 
 
 def batch_play_moves_tracked(tracked, moves, played=None):
@@ -1492,16 +1555,24 @@ class PuctSearch:
     ladder (False = everything above, launch for launch; True needs features=, ValueError otherwise): select() returns the
     ladder planes [R, 4, N, N] ([R * L, ..]) of the feature dtype as its last element, after the life planes if both are on -
     batch_ladder of the leaves, from the tracked leaf boards (gg_batch_ladder_tracked), in the orientation of
-    `search.orient` with symmetry= (the planes of the turned leaf).  One launch more per select(); nothing else changes."""
+    `search.orient` with symmetry= (the planes of the turned leaf).  One launch more per select(); nothing else changes.
+
+    outcome (False = everything above, launch for launch; True needs features=, ValueError otherwise): select() returns the
+    move-outcome planes [R, 12, N, N] ([R * L, ..]) of the feature dtype as its last element, after the life and ladder
+    planes when those are on - batch_move_planes of the leaves, from the tracked leaf boards
+    (gg_batch_move_planes_tracked), in the orientation of `search.orient` with symmetry=.  One launch more per select();
+    nothing else changes."""
 
     def __init__(self, batch_states, iterations, c=1.25, komi=0.0, leaves=None, capacity=None, features=None, symmetry=None,
-                 first_root=0, life=False, ladder=False):
+                 first_root=0, life=False, ladder=False, outcome=False):
         self._feat = None if features is None else (features, _feature_dtype(features))
         _puct_symmetry_guard(symmetry, features)
         _puct_life_guard(life, features)
         _puct_ladder_guard(ladder, features)
+        _puct_outcome_guard(outcome, features)
         self._life = bool(life)
         self._ladder = bool(ladder)
+        self._outcome = bool(outcome)
         self._sym = None if symmetry is None else int(symmetry)
         self._first_root = int(first_root)
         self.orient = None
@@ -1537,6 +1608,8 @@ class PuctSearch:
             self._life_planes = torch.empty((B, LIFE_PLANES, N, N), dtype=self._feat[0], device=dev)
         if self._ladder:
             self._ladder_planes = torch.empty((B, LADDER_PLANES, N, N), dtype=self._feat[0], device=dev)
+        if self._outcome:
+            self._outcome_planes = torch.empty((B, MOVE_PLANES, N, N), dtype=self._feat[0], device=dev)
         self.live = torch.full((R, self._L or 1), self._L is None, dtype=torch.bool, device=dev)   # (one leaf: always live)
         self._done, self._pending = 0, False
         self._init_symmetry(B)
@@ -1586,7 +1659,8 @@ class PuctSearch:
     def select(self):
         """Step 1 and 2 of the next iteration -> (states uint8 [R, 6, N, N], legal bool [R, A]) of the R leaves ([R * L, ..]
         with leaves=L); with features=dtype (planes [R, 16, N, N] of that dtype, legal); with life=True (planes, legal, life
-        [R, 4, N, N] of that dtype); with ladder=True the ladder planes [R, 4, N, N] of that dtype as the last element."""
+        [R, 4, N, N] of that dtype); with ladder=True the ladder planes [R, 4, N, N] of that dtype after those; with
+        outcome=True the move-outcome planes [R, 12, N, N] of that dtype as the last element."""
         if self._pending:
             raise ValueError('PuctSearch.select(): the leaves of the last select() have not been backed up')
         if self._done >= self._I:
@@ -1612,10 +1686,13 @@ class PuctSearch:
                 _plane_launch('gg_batch_life_tracked', lp, op, self._life_planes, None, self._feat[1], B, N, stream)
             if self._ladder:
                 _plane_launch('gg_batch_ladder_tracked', lp, op, self._ladder_planes, None, self._feat[1], B, N, stream)
+            if self._outcome:
+                _plane_launch('gg_batch_move_planes_tracked', lp, op, self._outcome_planes, _NO_BYTES, self._feat[1], B, N, stream)
         self._pending = True
         legal = self._legal if self._sym is None else self._legal_view
         res = (self._states, legal, self._life_planes) if self._life else (self._states, legal)
-        return res + (self._ladder_planes,) if self._ladder else res
+        res = res + (self._ladder_planes,) if self._ladder else res
+        return res + (self._outcome_planes,) if self._outcome else res
 
     def backup(self, priors, values):
         """Step 4: priors float32 [R, A] and values float32 [R] (the value for the player to move at the leaf) of the leaves
@@ -1815,7 +1892,7 @@ class PuctSearch:
 
 
 def batch_puct(batch_states, iterations, evaluator, c=1.25, komi=0.0, tree=False, leaves=None, capacity=None, features=None,
-               symmetry=None, first_root=0, life=False, ladder=False):
+               symmetry=None, first_root=0, life=False, ladder=False, outcome=False):
     """PUCT search (the AlphaZero search) of `iterations` iterations from every root of batch_states ([R, 6, N, N]) with the
     caller's evaluator -> Puct (device tensors for a device tensor, NumPy arrays for NumPy input).  The loop over PuctSearch.
 
@@ -1876,13 +1953,18 @@ def batch_puct(batch_states, iterations, evaluator, c=1.25, komi=0.0, tree=False
 
     ladder (False: the search above, launch for launch; True, with features=): the evaluator is called as
     evaluator(planes, legal, [life,] ladder) with ladder [R, 4, N, N] ([R * L, ..]) of the feature dtype - batch_ladder of the
-    leaves, in the leaf's orientation with symmetry= (PuctSearch)."""
+    leaves, in the leaf's orientation with symmetry= (PuctSearch).
+
+    outcome (False: the search above, launch for launch; True, with features=): the evaluator gets as its last argument,
+    after life and ladder when those are on, the move-outcome planes [R, 12, N, N] ([R * L, ..]) of the feature dtype -
+    batch_move_planes of the leaves, in the leaf's orientation with symmetry= (PuctSearch)."""
     _puct_komi_guard(evaluator, komi)
     _puct_features_guard(evaluator, features)
     _puct_life_guard(life, features)
     _puct_ladder_guard(ladder, features)
+    _puct_outcome_guard(outcome, features)
     search = PuctSearch(batch_states, iterations, c, komi, leaves=leaves, capacity=capacity, features=features, symmetry=symmetry,
-                        first_root=first_root, life=life, ladder=ladder)
+                        first_root=first_root, life=life, ladder=ladder, outcome=outcome)
     for _ in range(search._I):
         priors, values = evaluator(*search.select())
         search.backup(priors, values)
@@ -1910,6 +1992,11 @@ def _puct_ladder_guard(ladder, features):
         raise ValueError('ladder=True hands out the ladder planes in the dtype of features=: give features= too')
 
 
+def _puct_outcome_guard(outcome, features):
+    if outcome and features is None:   # (before a device is touched)
+        raise ValueError('outcome=True hands out the move-outcome planes in the dtype of features=: give features= too')
+
+
 def _puct_features_guard(evaluator, features):
     if features is not None:
         _feature_dtype(features)
@@ -1918,7 +2005,7 @@ def _puct_features_guard(evaluator, features):
 
 
 def puct_play(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, leaves=None, capacity=None, reuse=True, features=None,
-              symmetry=None, first_root=0, life=False, ladder=False):
+              symmetry=None, first_root=0, life=False, ladder=False, outcome=False):
     """Play `moves` moves from every root of batch_states ([R, 6, N, N]) with a PUCT search per move -> (actions int64
     [R, moves], the final states uint8 [R, 6, N, N]); device tensors for a device tensor, NumPy arrays for NumPy input.
     Per move: `iterations` rounds of PuctSearch (batch_puct's loop, with `leaves` and `capacity` as there), the move of
@@ -1938,16 +2025,18 @@ def puct_play(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, leav
     loop with it, with moves drawn from the visit counts and with the training records.  features: as batch_puct - the
     evaluator gets (planes, legal).  symmetry, first_root: as batch_puct; with reuse=False the search of move mv draws from
     the base seed symmetry + mv (a new search would repeat the first one's draws otherwise).  life: as batch_puct - the
-    evaluator gets (planes, legal, life).  ladder: as batch_puct - the ladder planes as the evaluator's last argument."""
+    evaluator gets (planes, legal, life).  ladder: as batch_puct - the ladder planes as the evaluator's next argument.
+    outcome: as batch_puct - the move-outcome planes as the evaluator's last argument."""
     _puct_komi_guard(evaluator, komi)
     _puct_features_guard(evaluator, features)
     _puct_life_guard(life, features)
     _puct_ladder_guard(ladder, features)
+    _puct_outcome_guard(outcome, features)
     moves = int(moves)
     if moves < 0:
         raise ValueError('need moves >= 0 (got %d)' % moves)
     search = PuctSearch(batch_states, iterations, c, komi, leaves=leaves, capacity=capacity, features=features, symmetry=symmetry,
-                        first_root=first_root, life=life, ladder=ladder)
+                        first_root=first_root, life=life, ladder=ladder, outcome=outcome)
     box = search._box
     played = torch.empty((search._R, moves), dtype=_I64, device=box.t.device)
     for mv in range(moves):
@@ -1962,7 +2051,7 @@ def puct_play(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, leav
             box.t = search._played_states(played[:, mv])
             search = PuctSearch(box, iterations, c, komi, leaves=leaves, capacity=capacity, features=features,
                                 symmetry=None if symmetry is None else int(symmetry) + mv + 1, first_root=first_root, life=life,
-                                ladder=ladder)
+                                ladder=ladder, outcome=outcome)
     return _back(box, played), box.back(search._root_states())
 
 
@@ -1998,7 +2087,7 @@ that ended, 0 for one still running), lengths (int32 [R]: moves played), final_s
 
 def puct_selfplay(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, leaves=None, capacity=None, noise=None,
                   eps=0.25, sample_moves=0, seed=20260927, first_game=0, record_states=False, features=None, symmetry=None,
-                  life=False, ladder=False):
+                  life=False, ladder=False, outcome=False):
     """Self-play games for training: `moves` moves from every root of batch_states ([R, 6, N, N]) with a PUCT search per move
     on the kept tree -> SelfPlay (device tensors for a device tensor, NumPy arrays for NumPy input).  puct_play's
     reuse=True loop (`iterations` rounds per move with `leaves` and `capacity` as there, then PuctSearch.advance) with
@@ -2025,11 +2114,13 @@ def puct_selfplay(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, 
     positions and the policy targets, in any of the eight orientations.  life: as batch_puct - the evaluator gets (planes,
     legal, life); the records do not change, and there is no stopping rule here: a driver that wants to stop settled games
     early asks batch_settled(search.root_states()) in a loop of its own.  ladder: as batch_puct - the ladder planes as the
-    evaluator's last argument; the records do not change."""
+    evaluator's next argument; the records do not change.  outcome: as batch_puct - the move-outcome planes as the evaluator's
+    last argument; the records do not change."""
     _puct_komi_guard(evaluator, komi)
     _puct_features_guard(evaluator, features)
     _puct_life_guard(life, features)
     _puct_ladder_guard(ladder, features)
+    _puct_outcome_guard(outcome, features)
     moves, sample_moves, eps = int(moves), int(sample_moves), float(eps)
     if moves < 0:
         raise ValueError('need moves >= 0 (got %d)' % moves)
@@ -2052,12 +2143,12 @@ def puct_selfplay(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, 
     pis = torch.zeros((R, moves, A), dtype=torch.float32, device=dev)
     vals = torch.zeros((R, moves), dtype=torch.float32, device=dev)
     lengths = torch.zeros(R, dtype=_I32, device=dev)
-    outcome = torch.zeros(R, dtype=torch.int8, device=dev)
+    won = torch.zeros(R, dtype=torch.int8, device=dev)   # (the record's outcome; `outcome` is the option)
     before = torch.empty((R, moves, govars.NUM_CHNLS, N, N), dtype=_U8, device=dev) if record_states else None
     if not R or not moves:
-        return _back(box, SelfPlay(played, pis, vals, outcome, lengths, st, before))
+        return _back(box, SelfPlay(played, pis, vals, won, lengths, st, before))
     search = PuctSearch(box, I, c, komi, leaves=leaves, capacity=capacity, features=features, symmetry=symmetry, first_root=first_game,
-                        life=life, ladder=ladder)
+                        life=life, ladder=ladder, outcome=outcome)
     rng = rng_seed(R, seed, first_game, device=dev)
     ones, todo = torch.ones(R, dtype=_U8, device=dev), torch.empty(R, dtype=_U8, device=dev)
     for mv in range(moves):
@@ -2080,8 +2171,8 @@ def puct_selfplay(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, 
     black, white = _areas_dev(final)
     x = (black - white).to(torch.float32) - torch.full((), komi, dtype=torch.float32, device=dev)   # gg_puct_backup's terminal rule
     ended = final[:, govars.DONE_CHNL, 0, 0] != 0
-    outcome = torch.where(ended, torch.sign(x), torch.zeros_like(x)).to(torch.int8)
-    return _back(box, SelfPlay(played, pis, vals, outcome, lengths, final, before))
+    won = torch.where(ended, torch.sign(x), torch.zeros_like(x)).to(torch.int8)
+    return _back(box, SelfPlay(played, pis, vals, won, lengths, final, before))
 
 
 def puct(state, iterations, evaluator, **kw):
@@ -2090,6 +2181,7 @@ def puct(state, iterations, evaluator, **kw):
     _puct_symmetry_guard(kw.get('symmetry'), kw.get('features'))
     _puct_life_guard(kw.get('life', False), kw.get('features'))
     _puct_ladder_guard(kw.get('ladder', False), kw.get('features'))
+    _puct_outcome_guard(kw.get('outcome', False), kw.get('features'))
     return _single(batch_puct, state, iterations, evaluator, **kw)
 
 
@@ -2099,6 +2191,7 @@ def puct_actions(batch_states, iterations, evaluator, **kw):
     _puct_symmetry_guard(kw.get('symmetry'), kw.get('features'))
     _puct_life_guard(kw.get('life', False), kw.get('features'))
     _puct_ladder_guard(kw.get('ladder', False), kw.get('features'))
+    _puct_outcome_guard(kw.get('outcome', False), kw.get('features'))
     box = _Box(batch_states)
     res = batch_puct(box.t, iterations, evaluator, **kw)
     return _best_legal(box, res.legal, res.visits.to(_I64))
@@ -2356,7 +2449,7 @@ def selfplay_targets(record, games, moves):
     return torch.where(white, -outcome, outcome), m < t(record.lengths, dev)[g].to(_I64)
 
 
-def selfplay_batch(record, games, moves, orient, dtype=torch.float16, life=False, ladder=False):
+def selfplay_batch(record, games, moves, orient, dtype=torch.float16, life=False, ladder=False, outcome=False):
     """Training samples from a self-play record, in one of the eight orientations each -> (planes [B, 16, N, N] of `dtype`,
     pi [B, A] float32, z float32 [B], valid bool [B]).  record: a SelfPlay of puct_selfplay(.., record_states=True)
     (ValueError if record.states is None); games, moves, orient: int [B] - sample i is the position before move moves[i] of
@@ -2365,7 +2458,9 @@ def selfplay_batch(record, games, moves, orient, dtype=torch.float16, life=False
     eightfold augmentation of a sample is this call with orient = 0 .. 7.  Nothing synchronises; device tensors, or NumPy
     arrays for a NumPy record (through the device).  life=True: a fifth element, the life planes [B, 4, N, N] of the
     recorded positions in view orient and dtype `dtype` (batch_life, one launch more).  ladder=True: as the last element the
-    ladder planes [B, 4, N, N] of the recorded positions in view orient and dtype `dtype` (batch_ladder, one launch more)."""
+    ladder planes [B, 4, N, N] of the recorded positions in view orient and dtype `dtype` (batch_ladder, one launch more).
+    outcome=True: as the last element, after those, the move-outcome planes [B, 12, N, N] of the recorded positions in view
+    orient and dtype `dtype` (batch_move_planes, one launch more)."""
     _feature_dtype(dtype)
     z, valid = selfplay_targets(record, games, moves)
     is_np = not isinstance(record.states, torch.Tensor)
@@ -2384,4 +2479,6 @@ def selfplay_batch(record, games, moves, orient, dtype=torch.float16, life=False
         res += (batch_life(positions, dtype, orient=orient),)
     if ladder:
         res += (batch_ladder(positions, dtype, orient=orient),)
+    if outcome:
+        res += (batch_move_planes(positions, dtype, orient=orient),)
     return tuple(x.cpu().numpy() for x in res) if is_np else res

@@ -835,6 +835,43 @@ int32_t gg_batch_ladder(const uint8_t *states, const int32_t *orient, void *out,
 int32_t gg_batch_ladder_tracked(const uint32_t *tracked, const int32_t *orient, void *out, uint8_t *aborted, int32_t out_dtype,
                                 int64_t B, int32_t N, void *hip_stream);
 
+/*
+ * Move-outcome planes: what a move WOULD do, for every point the mover may play - exact, all integers and
+ * sets, bit-exact against tests/outcome_expect.py.  Everything is from the mover's point of view; colours, chains and
+ * liberties as for the feature planes.
+ * A CANDIDATE is a point that is empty, has plane 3 clear, and lies on a board whose game has not ended: exactly the legal
+ * plane (plane 10) of gg_batch_features.  For a candidate p, from the stones alone (planes 0 and 1; of a tracked board
+ * the two stone row sets - its class rows are not read):
+ *   1. put a stone of the mover on p;
+ *   2. remove every opponent chain that now has no liberty: captured(p) = the number of stones removed;
+ *   3. take the chain that contains p: libs(p) = the number of its liberties, size(p) = the number of its stones;
+ *   4. if libs(p) == 0 (a suicide: it is a candidate only when the caller's plane 3 is not the true mask), then
+ *      libs(p) = captured(p) = size(p) = 0.
+ * At every point that is no candidate all three are 0.  The position is assumed to hold no chain without liberties; what a
+ * point next to such a chain gets is not specified (as for the ladder planes).
+ *   gg_batch_move_counts          states uint8 [B][6][N][N] -> out uint8 [B][GG_MOVE_COUNTS][N][N] =
+ *                                 min(libs, 255), min(captured, 255), min(size, 255)
+ *   gg_batch_move_planes          states -> out [B][GG_MOVE_PLANES][N][N] of out_dtype: GG_W_F32 / GG_W_BF16 / GG_W_F16 /
+ *                                 GG_FEAT_U8, every element exactly 0 or 1:
+ *                                    0 -  3  libs     == 1 / == 2 / == 3 / >= 4
+ *                                    4 -  7  captured == 1 / == 2 / == 3 / >= 4
+ *                                    8 - 11  libs == 1 and size == 1 / == 2 / == 3 / >= 4: a self-atari, by the size of the
+ *                                            chain it puts into atari
+ *   gg_batch_move_planes_tracked  the same from tracked boards uint32 [B][gg_tracked_words(N)]: the same bytes for
+ *                                 gg_batch_track_states(s) and s
+ * orient (NULL, or int32 [B], only orient[b] & 7 is read; gg_batch_symmetry's orientations): the planes are geometric, so
+ * out[b] is view orient[b] of the unoriented result and also the result of the turned position; the board is turned in
+ * registers after the load.  Alignment (out needs that of its element only), stores and the checks with their order and
+ * codes: gg_batch_life's.  Every call queues ONE launch on hip_stream and never synchronises; no global atomics.
+ */
+#define GG_MOVE_PLANES 12
+#define GG_MOVE_COUNTS 3
+int32_t gg_batch_move_planes(const uint8_t *states, const int32_t *orient, void *out, int32_t out_dtype, int64_t B, int32_t N,
+                             void *hip_stream);
+int32_t gg_batch_move_planes_tracked(const uint32_t *tracked, const int32_t *orient, void *out, int32_t out_dtype, int64_t B,
+                                     int32_t N, void *hip_stream);
+int32_t gg_batch_move_counts(const uint8_t *states, uint8_t *out, int64_t B, int32_t N, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
