@@ -153,6 +153,18 @@ static __device__ unsigned long long gg_sweeps5[10];
 #ifndef GG_AB_PRIO
 #define GG_AB_PRIO 1
 #endif
+// A/B switches of round 19, the hand-over behind the flood (gg_v5_kernel.h; docs/history/r19.md; 0 = round 17's code):
+// GG_AB_HAND1 1 (shipped: +1.8 % to +2.0 % on the headline launch): G leaves its lane by the same ds_or_b64 row pairs as a collected
+//   opponent group, one region under one exec mask, 0: G by ds_write_b128 in a region of its own;
+// GG_AB_PRIO_HAND 1: the wave's priority is raised again directly behind the flood and its liberties, inside the job loop, 0 (shipped):
+//   behind the loop.  On top of GG_AB_HAND1 its medians were +0.1 %, +0.6 % and +1.0 % in three alternations, never every run above
+//   every run without it: not shipped.
+#ifndef GG_AB_PRIO_HAND
+#define GG_AB_PRIO_HAND 0
+#endif
+#ifndef GG_AB_HAND1
+#define GG_AB_HAND1 1
+#endif
 
 // liberties (dilate & empty) of the group gt[], SATURATED: min(count, 2) - all any caller uses; m[] = the rows of its colour,
 // ot[] = the other colour's rows (read from LDS together with m[], BEFORE the flood: read behind it they cost the lane a round

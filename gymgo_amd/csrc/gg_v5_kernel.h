@@ -528,10 +528,34 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
             }
           }
         }
+        // (A/B builds with -DGG_AB_PRIO_HAND=1 raise the wave's priority HERE, behind the flood and its liberties, and not behind the
+        // job loop: what follows is LDS traffic and a wave-wide wait, like the set-up.  Not shipped - docs/history/r19.md.)
+        if (GG_AB_PRIO_HAND && plies >= 8) { if (lead) __builtin_amdgcn_s_setprio(2); else __builtin_amdgcn_s_setprio(3); }
         const uint32_t lib2 = cnt < 2u ? cnt : 2u;
         // G goes to its board's G block (over the stone phase 1 left there); an opponent group with no liberty left
         // (captured) or with one (it leaves M) is ORed into the board's collection block - one that keeps >= 2 is dropped
         uint32_t *gb = gblk + 2 * sj * RS;
+#if GG_AB_HAND1
+        // ONE path for both: a lane that hands a group over ORs its rows into the block its address chooses, gb for G, gb + RS for a
+        // collected opponent group, and one word into the board's info word.  The OR is exact for G too: phase 1 cleared both blocks
+        // of every board this ply and left only q in the G block, the flood of G starts at q (q is in res[]), a board has at most
+        // one G job, and every job's fill stays inside the rows of its own colour - so the G block ends as res[], as the plain
+        // store left it, and rows R .. RS - 1 stay zero.
+        // (two rows per ds_or_b64: the blocks and RS are even, and for odd R the last pair ORs zero into row R, inside the block;
+        // half the LDS instructions of nineteen ds_or_b32 - skipping empty rows by a per-row branch instead cost 4 %)
+        static_assert(Lds5<R>::kG % 2 == 0 && RS % 2 == 0 && R + 1 <= RS, "8-byte aligned row pairs inside the block");
+        if (isG || (have && cnt < 2u)) {
+          uint32_t *dst = gb + (isG ? 0 : RS);
+#pragma unroll
+          for (int r = 0; r < R; r += 2) {
+            const uint32_t hi = r + 1 < R ? res[r + 1] : 0u;
+            atomicOr(reinterpret_cast<unsigned long long *>(dst + r), ((unsigned long long)hi << 32) | res[r]);
+          }
+          // G: its liberties; an opponent group: the direction in which it was captured (a zero word is ORed, not branched around)
+          const uint32_t word = isG ? lib2 << 4 : (cnt == 0u ? 1u << ((d >> 19) & 3u) : 0u);
+          atomicOr(clsv + sj, word);
+        }
+#else
         if (isG) {
           uint4 *pz = reinterpret_cast<uint4 *>(gb);
 #pragma unroll
@@ -549,8 +573,10 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
           }
           if (cnt == 0u) atomicOr(clsv + sj, 1u << ((d >> 19) & 3u));
         }
+#endif
       }
-      if (plies >= 8) { if (lead) __builtin_amdgcn_s_setprio(2); else __builtin_amdgcn_s_setprio(3); }
+      // (-DGG_AB_PRIO_HAND=1: the priority is lowered and raised inside the loop body, a ply without a job never lowers it - nothing to raise)
+      if (!(GG_AB_PRIO && GG_AB_PRIO_HAND) && plies >= 8) { if (lead) __builtin_amdgcn_s_setprio(2); else __builtin_amdgcn_s_setprio(3); }
       WAVE_SYNC();
       GG_PROF(3);
 
