@@ -11,10 +11,13 @@ namespace gg {
 // 54 % of a ply's instructions, cost the same whatever their lanes carry.  Here a board is a PAIR of lanes (lane t owns
 // the RPL = ceil(R / 2) adjacent rows RPL t ..), a wave holds 32 boards, and a ply is
 //   1.  sampling, as in k_rollout4 (the pair scan is one DPP swap, the row of the k-th point a search tree over the prefix
-//       counts);
+//       counts); the point leaves the pair as (row << 5) | column and stays that way through the ply - phases 2a and 3 and the job
+//       lanes take it apart by shift and mask, the flat index is formed once for last_actions (round 20: three divisions by N per
+//       wave-ply gone, 12 -> 9 v_mul_lo_u32 in the ply loop, +1.7 % on the headline launch, docs/history/r20.md);
 //   2a. the board's own lanes look at q's four neighbours (two directions each) and post the floods the ply needs as JOBS:
 //       one per opponent stone next to q, and ONE for the mover's group G when q has a friendly neighbour (k_rollout4 runs
-//       that flood in every friendly lane); the slots come from two ballots (v_mbcnt prefix), the descriptors go to LDS;
+//       that flood in every friendly lane); the slots come from two ballots (v_mbcnt prefix), the descriptors - board, seed as
+//       (row, column), colour, direction - go to LDS;
 //   2b. lane L runs job L - 32 boards x 1.56 = 50 jobs in 64 lanes (a second batch when a ply posts more than 64: 0.7 %) -
 //       with the fill in registers from the seed to the liberty count.  The batch's loop ends as soon as every flood of a G
 //       is closed as far as stones OUTSIDE M go (the rows of M come out of the board lanes' registers by ds_bpermute): the
@@ -164,6 +167,16 @@ static __device__ unsigned long long gg_sweeps5[10];
 #endif
 #ifndef GG_AB_HAND1
 #define GG_AB_HAND1 1
+#endif
+
+// A/B switch of round 20, the move inside the ply (gg_v5_kernel.h, phases 1 / 2a / 2b / 3; docs/history/r20.md; 0 = round 19's code):
+// GG_AB_MOVE_RC 1 (shipped: +1.7 % on the headline launch): the move travels through the ply as (row << 5) | column and a job
+//   descriptor carries its seed that way in bits 5-14; the flat index is formed once by one v_mad_u32_u24, for last_actions and the
+//   pass / idle tests, 0: the flat index travels, and phases 2a and 3 and every job lane divide it by N again (split_action).
+// (The round's other part, phase 2a's neighbour rows read in phase 1 ahead of its stores, did not pay - +0.7 % alone, +0.2 % on top
+// of this one, neither told apart from the run-to-run spread - and is not in the source.)
+#ifndef GG_AB_MOVE_RC
+#define GG_AB_MOVE_RC 1
 #endif
 
 // liberties (dilate & empty) of the group gt[], SATURATED: min(count, 2) - all any caller uses; m[] = the rows of its colour,
@@ -445,7 +458,7 @@ static __device__ unsigned long long gg_lsplit[4];
 #define GG_LS_FLUSH do {} while (0)
 #endif
 
-// job descriptor: bits 0-4 board, 5-13 the seed (flat point index), 15 the colour flooded, 16 the job floods G, 18 the job exists,
+// job descriptor: bits 0-4 board, 5-14 the seed ((row << 5) | column; -DGG_AB_MOVE_RC=0: 5-13, the flat point index), 15 the colour flooded, 16 the job floods G, 18 the job exists,
 // 19-20 the direction of q's neighbour it starts from (0 up, 1 down, 2 left, 3 right)
 // info word of a board (cleared in phase 1, ORed by its jobs): bits 0-3 the directions whose opponent group was captured, 4-5 the
 // liberties of G (saturated at 2)

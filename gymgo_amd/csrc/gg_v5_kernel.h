@@ -269,6 +269,9 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
 
       int a_q;
       uint32_t fl_q;
+#if GG_AB_MOVE_RC
+      uint32_t rc_q;               // the drawn point as (row << 5) | column; 0 on a pass, never off the board
+#endif
       // phase 1 - two lanes per board, RPL rows each: liveness, the draw, the k-th valid point of the mask
       {
         const uint32_t fl = flr;
@@ -335,8 +338,17 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
         else kth_set_bit<RPL>(v, p, (k - Pb) & 0x3FFu, rr, pos);
         const int rabs = r0 + rr;
         // (k < n: exactly one lane of the pair holds the point and hands it to the other; k, n and live are the same in both)
+#if GG_AB_MOVE_RC
+        // the point travels as (row, column) through the ply: phases 2a and 3 and the job lanes take it apart by shift and mask,
+        // the flat index is formed once, for last_actions and the pass / idle tests.  (At most one lane of a pair hits, so the
+        // pair's word is a point of the board or zero.)
+        const uint32_t cand = hit ? ((uint32_t)rabs << 5) | pos : 0u;
+        rc_q = cand | dpp0<QP_X1>(cand);
+        const uint32_t pt = __umul24(rc_q >> 5, (uint32_t)N) + (rc_q & 31u);
+#else
         const uint32_t cand = hit ? (uint32_t)(rabs * N + (int)pos) : 0u;
         const uint32_t pt = cand | dpp0<QP_X1>(cand);
+#endif
         a_q = !live ? -1 : (k < n ? (int)pt : P);
         const bool place = live && hit;
         fl_q = reset ? 40u : fl;   // a board being reset: on, dirty, black to move
@@ -389,7 +401,12 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
         const uint32_t turn = fl_q & 1u;
         const uint32_t mv1 = ((uint32_t)a < (uint32_t)P) ? 1u : 0u;   // a stone was placed
         int ar, ac;
+#if GG_AB_MOVE_RC
+        ar = (int)(rc_q >> 5);    // (a point of the board or zero whatever the board does: the bits are masked, not the address)
+        ac = (int)(rc_q & 31u);
+#else
         split_action(mv1 ? a : 0, N, inv, ar, ac);
+#endif
         const uint32_t *pm = st + turn * PL + s4 * RS, *po = st + (1u - turn) * PL + s4 * RS;
         uint32_t obit[2], packed = 0;
 #pragma unroll
@@ -414,13 +431,21 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
         const uint32_t base = mbcnt64(b0) + 2u * mbcnt64(b1);
         njobs = (int)__popcll(b0) + 2 * (int)__popcll(b1);
         const uint32_t sG = base, s0 = base + gf, s1 = s0 + obit[0];
-        // (the seed travels as a flat point index: q itself for G, q -+ N / q -+ 1 for the opponent stone above / below / left / right)
         const uint32_t common = (uint32_t)s4 | (1u << 18) | ((turn ^ 1u) << 15);
+#if GG_AB_MOVE_RC
+        // (the seed travels as (row << 5) | column in bits 5-14: q itself for G, q -+ 32 / q -+ 1 for the opponent stone above / below /
+        // left / right - a job that is posted has its seed on the board, the others go to the dump slot)
+        const int step = t5 ? 1 : 32;
+        const int sd = (int)rc_q;
+#else
+        // (the seed travels as a flat point index: q itself for G, q -+ N / q -+ 1 for the opponent stone above / below / left / right)
         const int step = t5 ? 1 : N;
-        jobv[gf ? sG : (uint32_t)DUMP] = ((uint32_t)s4 | (1u << 18) | (turn << 15) | (1u << 16)) | ((uint32_t)a << 5);
+        const int sd = a;
+#endif
+        jobv[gf ? sG : (uint32_t)DUMP] = ((uint32_t)s4 | (1u << 18) | (turn << 15) | (1u << 16)) | ((uint32_t)sd << 5);
         const uint32_t dirs = (uint32_t)t5 << 20;   // bits 19-20: the direction of the job (0 up, 1 down, 2 left, 3 right)
-        jobv[obit[0] ? s0 : (uint32_t)DUMP] = common | dirs | ((uint32_t)(a - step) << 5);
-        jobv[obit[1] ? s1 : (uint32_t)DUMP] = common | dirs | (1u << 19) | ((uint32_t)(a + step) << 5);
+        jobv[obit[0] ? s0 : (uint32_t)DUMP] = common | dirs | ((uint32_t)(sd - step) << 5);
+        jobv[obit[1] ? s1 : (uint32_t)DUMP] = common | dirs | (1u << 19) | ((uint32_t)(sd + step) << 5);
       }
       WAVE_SYNC();
 
@@ -437,7 +462,12 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
         const uint32_t ex = have ? 1u : 0u;
         const int sj = (int)(d & 31u);
         int sr, scol;
+#if GG_AB_MOVE_RC
+        sr = (int)((d >> 10) & 31u);
+        scol = (int)((d >> 5) & 31u);
+#else
         split_action((int)((d >> 5) & 511u), N, inv, sr, scol);
+#endif
         const uint32_t ownc = (d >> 15) & 1u;
         const uint32_t isG = have ? (d >> 16) & 1u : 0u;
         uint32_t *blk = sc + ln * RS;   // this lane's seed block (all zero)
@@ -601,7 +631,12 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
         const bool moves_now = a >= 0;
         const bool is_pass = a == P;
         int ar, ac;
+#if GG_AB_MOVE_RC
+        ar = (int)(rc_q >> 5);
+        ac = (int)(rc_q & 31u);                                // (zero for a pass, some point for an idle board: masked below)
+#else
         split_action(a, N, inv, ar, ac);                       // (garbage for a pass / an idle board: masked below)
+#endif
         const uint32_t capt_m = info & 15u;   // the directions in which an opponent group died (never set on a board that does not move)
         // The collection block holds the opponent groups next to q with NO liberty left (captured: q was their only liberty, so
         // they were never in M) or with exactly ONE (they had q and one more: they were in M).  So it splits by M alone:
