@@ -62,6 +62,9 @@ _PUCT_TREE = (_params(_I32, 'boards', 'child') + _params(_F32, 'prior') + _param
 _PUCT_BACK = (_params(_f32, 'komi') + _params(_F32, 'priors', 'values') + _params(_I32, 'boards') + _params(_F32, 'prior')
               + _params(_I32, 'links', 'stats') + _LEAF)
 
+_MOVE_HASHES = (_params(_I64, 'history') + _params(_I32, 'count') + _params(_i32, 'H') + _params(_I64, 'hashes')
+                + _params(_U8, 'repeat') + _params(_I32, 'rows') + _BN)
+
 # THE description of the C ABI on the Python side: one entry per function of include/gymgo_amd.h, in header order, one Param
 # per parameter.  EXPORTS, the ctypes argtypes lib() sets and the marshalling of call() all come from here.
 ABI = {
@@ -153,6 +156,10 @@ ABI = {
     'gg_batch_move_planes': _params(_U8, 'states') + _params(_I32, 'orient') + _OUT + _OUT_BN,
     'gg_batch_move_planes_tracked': _params(_I32, 'tracked', 'orient') + _OUT + _OUT_BN,
     'gg_batch_move_counts': _params(_U8, 'states', 'out') + _BN,
+    'gg_batch_hash': _params(_U8, 'states') + _params(_I64, 'out') + _BN,
+    'gg_batch_hash_tracked': _params(_I32, 'tracked') + _params(_I64, 'out') + _BN,
+    'gg_batch_move_hashes': _params(_U8, 'states') + _MOVE_HASHES,
+    'gg_batch_move_hashes_tracked': _params(_I32, 'tracked') + _MOVE_HASHES,
 }
 EXPORTS = tuple(ABI)
 _SIGNATURES = {f: ([p.kind if isinstance(p.kind, type) else _vp for p in ps], _i32) for f, ps in ABI.items()}   # argtypes, restype

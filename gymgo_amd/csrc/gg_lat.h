@@ -85,6 +85,19 @@ template <int LPB> __device__ __forceinline__ int lat_board_max(int x) {
   if (LPB == 32) { y = __builtin_amdgcn_ds_swizzle(x, 0x401F); x = x > y ? x : y; }
   return x;
 }
+// XOR of a 64-bit word over the lanes of a board, result in every lane: lat_board_sum's moves on either half
+template <int LPB> __device__ __forceinline__ uint64_t lat_board_xor(uint64_t v) {
+  uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);
+  lo ^= dpp0<0x128>(lo); hi ^= dpp0<0x128>(hi);   // row_ror:8
+  lo ^= dpp0<0x124>(lo); hi ^= dpp0<0x124>(hi);
+  lo ^= dpp0<0x122>(lo); hi ^= dpp0<0x122>(hi);
+  lo ^= dpp0<0x121>(lo); hi ^= dpp0<0x121>(hi);
+  if (LPB == 32) {                                // lane ^ 16 (and 0x1F, or 0, xor 0x10)
+    lo ^= (uint32_t)__builtin_amdgcn_ds_swizzle((int)lo, 0x401F);
+    hi ^= (uint32_t)__builtin_amdgcn_ds_swizzle((int)hi, 0x401F);
+  }
+  return lo | ((uint64_t)hi << 32);
+}
 // inclusive prefix sum over the lanes of a board (half_scan of gg_v2.h without / with the row broadcast)
 template <int LPB> __device__ __forceinline__ uint32_t lat_board_scan(uint32_t v) {
   v += dpp0<0x111>(v);

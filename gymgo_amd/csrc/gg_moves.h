@@ -20,7 +20,8 @@
 //   2. THE EXACT PATH (moves_exact), one candidate per board and round, the boards of a wave in lock-step: the captured
 //      stones = the flood of (neighbours of p that are opponent stones of one-liberty groups) within those stones - such a
 //      group next to the empty p has p as its liberty, and groups of one colour never touch, so one flood gives them all;
-//      the chain = the flood of p within own | p; both floods run as one pair (plane_pair).  libs = the points of
+//      the chain = the flood of p within own | p; both floods run as one pair (plane_move_flood of gg_planes.h, which the
+//      move hashes share).  libs = the points of
 //      dilate(chain) & (empty | captured) without p; the three numbers are three 10-bit fields of one board sum.
 //      Candidates that capture, or that join two and more own groups, come here - with -DGG_AB_MOVES_EXACT=1 (make ab) every
 //      candidate does, and feat_groups files the one-liberty groups.
@@ -102,29 +103,18 @@ __device__ __forceinline__ void moves_neighbours(uint32_t X, uint32_t (&s)[3]) {
   s[2] = q0 & q1;
 }
 
-// the lowest point (row-major) of a row set of the board: the lowest bit of the first lane that holds one, zero elsewhere
-template <int LPB> __device__ __forceinline__ uint32_t moves_first(uint32_t x) {
-  const uint32_t incl = lat_board_scan<LPB>(x ? 1u : 0u);
-  return (x != 0u && incl == 1u) ? (x & (0u - x)) : 0u;
-}
-
 // THE EXACT PATH: every point of `todo` (empty points of the board), one per board and round.  own: the mover's stones,
 // opp1: the opponent's stones of groups with exactly one liberty, E: the empty points.
 template <int R, bool COUNTS>
 __device__ __forceinline__ void moves_exact(uint32_t own, uint32_t opp1, uint32_t E, uint32_t todo, MoveAcc<COUNTS> &acc) {
-  constexpr int LPB = Moves<R>::LPB, K = Moves<R>::K;
+  constexpr int LPB = Moves<R>::LPB;
 #pragma unroll 1
   for (int it = 0; it < R * R + 1; ++it) {   // (a round takes a point off every board that still has one)
     if (__ballot(todo != 0u) == 0ull) break;
-    const uint32_t Q = moves_first<LPB>(todo);
+    const uint32_t Q = plane_first<LPB>(todo);
     todo &= ~Q;
-    uint32_t Mk[K], Mkr[K], F[K];
-    plane_pair<R>(own | Q, opp1, Mk);
-    plane_pair<R>(Q, lat_dilate<LPB>(Q) & opp1, F);
-#pragma unroll
-    for (int k = 0; k < K; ++k) Mkr[k] = __brev(Mk[k]);
-    lat_flood<LPB, K>(F, Mk, Mkr);
-    const uint32_t G = plane_field<R>(F, 0), C = plane_field<R>(F, 1);
+    uint32_t G, C;
+    plane_move_flood<R, true>(own, opp1, Q, G, C);
     const uint32_t L = lat_dilate<LPB>(G) & ((E & ~Q) | C);
     const uint32_t S = lat_board_sum<LPB>((uint32_t)__popc(L) | ((uint32_t)__popc(C) << 10) | ((uint32_t)__popc(G) << 20));   // (<= 361 each)
     const uint32_t nl = S & 1023u;

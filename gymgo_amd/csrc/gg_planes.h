@@ -1,5 +1,6 @@
 // gg_planes.h - what the PLANE KERNELS share (gg_feat.h: network features and group liberties, gg_life.h: pass-alive life,
-// gg_ladder.h: ladders, gg_moves.h: move outcomes).  Only those four units compile from this header.
+// gg_ladder.h: ladders, gg_moves.h: move outcomes, gg_hash.h: position and move hashes).  Only those five units
+// compile from this header.
 //
 // Layout: ONE ROW PER LANE as in gg_lat.h - a board is the 16 lanes of a DPP row (R <= 13, four boards per wave) or 32 lanes
 // (R = 19, two boards per wave), the rows are bit masks in registers, one single-wave workgroup per wave of boards
@@ -7,6 +8,8 @@
 //   the frame      PlaneFrame: the lane's place on its board and the wave's boards of a grid-stride step;
 //   the load       plane_load: byte planes (staged through LDS) or tracked rows, turned into view orient[b] in registers;
 //   the pairs      plane_pair / plane_field / plane_seeds: black and white row sets side by side, as lat_flood floods them;
+//   the candidate  plane_first: the next point of a per-board work list; plane_move_flood: the stones a move there captures
+//                  (and the chain it makes) - one round of gg_moves.h's exact path and of gg_hash.h's capturing candidates;
 //   the emission   plane_bits: the wave's planes as ONE bit-string in LDS (its boards are contiguous in the output);
 //                  plane_store: the string expanded to 0 / 1 of the element type, aligned 16-byte vectors inside the wave's
 //                  slice, single elements at its ragged ends, nothing outside it (plane_emit: both, for an element-aligned
@@ -74,6 +77,39 @@ __device__ __forceinline__ void plane_seeds(const uint32_t (&X)[Planes<R>::K], u
   const uint32_t sb = (xb != 0u && (incl & 0xFFFFu) == 1u) ? (xb & (0u - xb)) : 0u;
   const uint32_t sw = (xw != 0u && (incl >> 16) == 1u) ? (xw & (0u - xw)) : 0u;
   plane_pair<R>(sb, sw, F);
+}
+
+// the lowest point (row-major) of a row set of the board: the lowest bit of the first lane that holds one, zero elsewhere
+template <int LPB> __device__ __forceinline__ uint32_t plane_first(uint32_t x) {
+  const uint32_t incl = lat_board_scan<LPB>(x ? 1u : 0u);
+  return (x != 0u && incl == 1u) ? (x & (0u - x)) : 0u;
+}
+
+// THE FLOODS OF ONE CANDIDATE per board, the boards of a wave in lock-step.  Q: the candidate (an empty point; one bit in the
+// lane of its row, or none), own: the mover's stones, opp1: the opponent's stones of groups with exactly one liberty.
+//   C = the stones a move at Q captures: the flood of (neighbours of Q in opp1) within opp1 - such a group next to the empty Q
+//       has Q as its liberty, and groups of one colour never touch, so one flood gives them all;
+//   G = (CHAIN) the chain of the played stone: the flood of Q within own | Q, run with the other as one pair; else 0, and
+//       the capture flood runs alone in one register.
+template <int R, bool CHAIN>
+__device__ __forceinline__ void plane_move_flood(uint32_t own, uint32_t opp1, uint32_t Q, uint32_t &G, uint32_t &C) {
+  constexpr int LPB = Planes<R>::LPB, K = Planes<R>::K;
+  const uint32_t seeds = lat_dilate<LPB>(Q) & opp1;
+  if constexpr (CHAIN) {
+    uint32_t Mk[K], Mkr[K], F[K];
+    plane_pair<R>(own | Q, opp1, Mk);
+    plane_pair<R>(Q, seeds, F);
+#pragma unroll
+    for (int k = 0; k < K; ++k) Mkr[k] = __brev(Mk[k]);
+    lat_flood<LPB, K>(F, Mk, Mkr);
+    G = plane_field<R>(F, 0);
+    C = plane_field<R>(F, 1);
+  } else {
+    uint32_t Mk[1] = {opp1}, Mkr[1] = {__brev(opp1)}, F[1] = {seeds};
+    lat_flood<LPB, 1>(F, Mk, Mkr);
+    G = 0;
+    C = F[0];
+  }
 }
 
 // The rows of the wave's boards from byte planes (uint8 [B][6][N][N]): the boards of a wave are ONE contiguous slice of HBM,

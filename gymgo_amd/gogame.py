@@ -1034,6 +1034,203 @@ def move_counts(state):
     return _back(box, batch_move_counts(box.t[None]), row0=True)
 
 
+# ---------------------------------------------------------------- position hashes and positional superko
+HASH_SEED = 0x676F2D6861736821   # GG_HASH_SEED of include/gymgo_amd.h
+
+
+def zobrist_keys():
+    """The key table of the position hashes -> NumPy int64 [2, 19, 19]: keys[c, y, x] for a black (c = 0) / white (c = 1) stone
+    at row y, column x - output number c * 361 + y * 19 + x + 1 of splitmix64 started at HASH_SEED, whatever the board size
+    (include/gymgo_amd.h).  Computed here on the host, from Python integers, for users who hash elsewhere; the kernels hold the
+    same numbers as a constant table."""
+    M, x, keys = (1 << 64) - 1, HASH_SEED, []
+    for _ in range(2 * 19 * 19):
+        x = (x + 0x9E3779B97F4A7C15) & M
+        z = x
+        z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & M
+        z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & M
+        keys.append(z ^ (z >> 31))
+    return np.array(keys, dtype=np.uint64).view(np.int64).reshape(2, 19, 19)
+
+
+class PositionHistory:
+    """The hashes of the positions a batch of games has been through, on the device: what the superko calls compare the move
+    hashes against.  hashes: int64 [B, capacity], count: int32 [B] - the number of pushes per board; a board's valid entries
+    are its first min(count, capacity).  A RING: push writes at count % capacity, so once a board has been pushed more than
+    `capacity` times it holds its LAST `capacity` positions and older ones are forgotten - give it the length of the game
+    (+ 1 for the starting position) to forget nothing.  device: None = the current ROCm device.  Plain torch ops on the
+    current stream; nothing synchronises."""
+
+    def __init__(self, batch_size, capacity, device=None):
+        batch_size, capacity = int(batch_size), int(capacity)
+        if batch_size < 0 or capacity < 1:
+            raise ValueError('need batch_size >= 0 and capacity >= 1 (got %d, %d)' % (batch_size, capacity))
+        dev = _device() if device is None else device
+        self.capacity = capacity
+        self.hashes = torch.zeros((batch_size, capacity), dtype=_I64, device=dev)
+        self.count = torch.zeros(batch_size, dtype=_I32, device=dev)
+
+    def _mask(self, mask):
+        if mask is None:
+            return None
+        mask = torch.as_tensor(mask, device=self.count.device)
+        if tuple(mask.shape) != tuple(self.count.shape) or mask.dtype not in (torch.bool, _U8):
+            raise ValueError('mask must be bool or uint8 [%d] (got %s %s)' % (self.count.shape[0], mask.dtype, tuple(mask.shape)))
+        return mask.bool()
+
+    def push(self, hashes, mask=None):
+        """Append hashes (int64 [B], batch_hash of the positions) to the boards where mask (None = all; bool or uint8 [B]) is
+        set: written at count % capacity, count + 1.  -> self."""
+        h = torch.as_tensor(hashes, device=self.count.device)
+        if tuple(h.shape) != tuple(self.count.shape) or h.dtype != _I64:
+            raise ValueError('hashes must be int64 [%d] (got %s %s)' % (self.count.shape[0], h.dtype, tuple(h.shape)))
+        mask = self._mask(mask)
+        at = (self.count.to(_I64) % self.capacity)[:, None]
+        if mask is not None:
+            h = torch.where(mask, h, self.hashes.gather(1, at)[:, 0])
+        self.hashes.scatter_(1, at, h[:, None])
+        self.count += 1 if mask is None else mask.to(_I32)
+        return self
+
+    def reset(self, mask=None):
+        """Forget everything about the boards where mask (None = all) is set: entries and count zero.  -> self."""
+        mask = self._mask(mask)
+        if mask is None:
+            self.hashes.zero_()
+            self.count.zero_()
+        else:
+            self.hashes.masked_fill_(mask[:, None], 0)
+            self.count.masked_fill_(mask, 0)
+        return self
+
+
+def _history_arg(history, B):
+    """(hashes int64 [B, H], count int32 [B], H) of a PositionHistory (or a (hashes, count) pair); ValueError otherwise -
+    before a device is touched."""
+    hashes, count = history if isinstance(history, tuple) else (getattr(history, 'hashes', None), getattr(history, 'count', None))
+    if (not isinstance(hashes, torch.Tensor) or not isinstance(count, torch.Tensor) or hashes.dtype != _I64 or count.dtype != _I32
+            or hashes.dim() != 2 or hashes.shape[0] != B or tuple(count.shape) != (B,) or not hashes.is_contiguous()
+            or not count.is_contiguous()):
+        raise ValueError('history must be a PositionHistory of %d boards: hashes int64 [%d, H], count int32 [%d]' % (B, B, B))
+    return hashes, count, hashes.shape[1]
+
+
+def _hash_shape(boards, tracked):
+    """(B, N) of byte planes (a tensor or an array) or tracked boards (a tensor); ValueError otherwise, before a device is touched."""
+    if not tracked:
+        return _states_shape(boards)
+    if not isinstance(boards, torch.Tensor) or boards.dim() != 2:
+        raise ValueError('tracked boards are int32 [B, 5N+1] device tensors')
+    return boards.shape[0], _tracked_size(boards)
+
+
+def _move_hashes(boards, tracked, history=None, out=None, hashes=False, repeat=False, rows=False):
+    """One launch of gg_batch_move_hashes[_tracked] -> (box or None, hashes, repeat, rows): device tensors, None where not asked for."""
+    B, N = _hash_shape(boards, tracked)
+    A = N * N + 1
+    hist = _history_arg(history, B) if repeat or rows else (None, None, 0)
+    _planes_out(out, (B, A), _I64, 8)
+    box = None if tracked else _Box(boards)
+    st = boards if tracked else box.t
+    dev = st.device
+    _planes_out(out, (B, A), _I64, 8, dev if st.is_cuda else None)
+    h = (out if out is not None else torch.empty((B, A), dtype=_I64, device=dev)) if hashes else None
+    rp = torch.empty((B, A), dtype=_U8, device=dev) if repeat else None
+    rw = torch.empty((B, N), dtype=_I32, device=dev) if rows else None
+    _lib.call('gg_batch_move_hashes_tracked' if tracked else 'gg_batch_move_hashes', st, hist[0], hist[1], hist[2], h, rp, rw, B, N,
+              _lib.stream_ptr(dev))
+    return box, h, rp, rw
+
+
+def _batch_hash(boards, tracked):
+    B, N = _hash_shape(boards, tracked)
+    box = None if tracked else _Box(boards)
+    st = boards if tracked else box.t
+    out = torch.empty(B, dtype=_I64, device=st.device)
+    _lib.call('gg_batch_hash_tracked' if tracked else 'gg_batch_hash', st, out, B, N, _lib.stream_ptr(st.device))
+    return out if box is None else _back(box, out)
+
+
+def batch_hash(batch_states):
+    """The 64-bit position hash of every board -> int64 [B] (gg_batch_hash): the XOR of zobrist_keys()[colour, y, x] over the
+    stones.  Positional: turn, pass, ko and game-over planes do not enter; the empty board hashes to 0.  For transposition
+    checks and the de-duplication of records without moving 6 N^2 bytes per board to the host.  One launch."""
+    return _batch_hash(batch_states, False)
+
+
+def batch_hash_tracked(tracked):
+    """batch_hash of tracked boards (int32 [B, 5N+1], a device tensor) -> int64 [B] (gg_batch_hash_tracked)."""
+    return _batch_hash(tracked, True)
+
+
+def position_hash(state):
+    """batch_hash of one state [6, N, N] -> an int64 scalar."""
+    box = _Box(state)
+    return _back(box, batch_hash(box.t[None]), row0=True)
+
+
+def batch_move_hashes(batch_states, out=None):
+    """The hash of the position after every move of the mover -> int64 [B, N*N + 1] (gg_batch_move_hashes), WITHOUT building the
+    children: at a candidate point (empty, plane 3 clear, game not over - the legal plane of batch_features) the hash after
+    the stone is put there and the opponent chains left without a liberty are removed; at the pass and at every other
+    point the board's own hash.  Every slot is written.  out: a contiguous int64 device tensor of that shape to write into.
+    One launch; device memory of the result: 8 * B * (N^2 + 1) bytes."""
+    box, h, _, _ = _move_hashes(batch_states, False, out=out, hashes=True)
+    return _back(box, h)
+
+
+def batch_move_hashes_tracked(tracked, out=None):
+    """batch_move_hashes of tracked boards (int32 [B, 5N+1], a device tensor; gg_batch_move_hashes_tracked).  The class rows
+    are read - they say which opponent stones are in atari, so no group is counted - and must belong to the position."""
+    return _move_hashes(tracked, True, out=out, hashes=True)[1]
+
+
+def move_hashes(state):
+    """batch_move_hashes of one state [6, N, N] -> int64 [N*N + 1]."""
+    box = _Box(state)
+    return _back(box, batch_move_hashes(box.t[None]), row0=True)
+
+
+def batch_superko_moves(batch_states, history):
+    """The moves positional superko forbids -> uint8 [B, N*N + 1] (the repeat mask of gg_batch_move_hashes): 1 at every
+    candidate point whose move hash equals a valid entry of `history` (a PositionHistory of the B games, the current
+    position included), 0 elsewhere; the pass is never a repeat.  Equal 64-bit hashes are taken as equal positions (a
+    collision, about 2^-64 per comparison, forbids a legal move).  One launch."""
+    box, _, rp, _ = _move_hashes(batch_states, False, history, repeat=True)
+    return _back(box, rp)
+
+
+def batch_superko_moves_tracked(tracked, history):
+    """batch_superko_moves of tracked boards (gg_batch_move_hashes_tracked)."""
+    return _move_hashes(tracked, True, history, repeat=True)[2]
+
+
+def batch_forbid_repeats(batch_states, history):
+    """OR the repeat points of batch_superko_moves into plane 3 of batch_states IN PLACE -> batch_states.  Plane 3 then means
+    "ko, suicide, occupied or superko", and every consumer of it - sampling, batch_valid_moves, the legal plane of
+    batch_features, the step kernels, the searches - treats those points as illegal with no change of its own.  The next
+    step recomputes plane 3 for the next mover, so the call is made once per position, before its move is chosen."""
+    B, N = _states_shape(batch_states)
+    if isinstance(batch_states, torch.Tensor) and batch_states.dtype != _U8:
+        raise ValueError('batch_states must be uint8 to be changed in place (got %s)' % batch_states.dtype)
+    rep = batch_superko_moves(batch_states, history)
+    if isinstance(batch_states, torch.Tensor):
+        batch_states[:, govars.INVD_CHNL].bitwise_or_(rep[:, :N * N].view(B, N, N))
+    else:
+        inv = batch_states[:, govars.INVD_CHNL]
+        np.maximum(inv, rep[:, :N * N].reshape(B, N, N).astype(inv.dtype), out=inv)
+    return batch_states
+
+
+def batch_forbid_repeats_tracked(tracked, history):
+    """OR the repeat points into the invalid rows of tracked boards IN PLACE -> tracked (the `rows` output of
+    gg_batch_move_hashes_tracked); gg_batch_play_moves_tracked, the tracked draws and gg_puct_legal then refuse them."""
+    rows = _move_hashes(tracked, True, history, rows=True)[3]
+    N = _tracked_size(tracked)
+    tracked[:, 2 * N:3 * N].bitwise_or_(rows)
+    return tracked
+
+
 def batch_play_moves_tracked(tracked, moves, played=None):
     """IN PLACE batch_play_moves on tracked boards; moves [B, T] (T = 1: one GoEnv.step per game) -> played int32 [B]."""
     N = _tracked_size(tracked)
@@ -1822,6 +2019,38 @@ class PuctSearch:
         self._done, self._I = 0, rounds
         return self._kept
 
+    def _root_hashes(self):
+        """int64 [R], a new device tensor: batch_hash of the current roots (node 0 of every tree)."""
+        R = self._R
+        if not R:
+            return torch.empty(0, dtype=_I64, device=self._dev)
+        self._advance_buffers()
+        with torch.cuda.device(self._dev):
+            self._next.copy_(self._boards[:, 0, :])
+        return batch_hash_tracked(self._next)
+
+    def forbid_repeats(self, history):
+        """Positional superko AT THE ROOTS: the moves that would recreate a position of `history` (a PositionHistory of the R
+        games, the current roots included) become illegal at node 0 of every tree - the repeat points of
+        gg_batch_move_hashes_tracked, as row masks, are ORed into the invalid rows of the root boards, and result().legal
+        follows.  Select, the prior mask of a root's first evaluation, add_root_noise and root_policy all read legality from
+        the board, so a child kept under a forbidden action simply stops being chosen or counted.  Only the roots are
+        marked: repetitions inside the tree below them are not checked.  Call it before the rounds of a move (and before
+        add_root_noise); advance() brings new root boards, whose invalid rows are their own.  Raises ValueError while leaves
+        are outstanding.  One copy, one launch and two torch ops; nothing synchronises."""
+        if self._pending:
+            raise ValueError('PuctSearch.forbid_repeats(): the leaves of the last select() have not been backed up')
+        R, N = self._R, self._N
+        _history_arg(history, R)
+        if not R:
+            return
+        self._advance_buffers()
+        with torch.cuda.device(self._dev):
+            self._next.copy_(self._boards[:, 0, :])
+            _, _, rep, rows = _move_hashes(self._next, True, history, repeat=True, rows=True)
+            self._boards[:, 0, 2 * N:3 * N].bitwise_or_(rows)
+            self._legal_roots = self._legal_roots & (rep == 0)
+
     def add_root_noise(self, noise, eps=0.25, todo=None):
         """Mix noise into the root's stored priors (gg_puct_root_noise) -> todo.  noise: float32 [R, A], a tensor or NumPy
         array, NOT normalised by the library (dirichlet_noise makes rows that sum to 1 over the legal actions); eps in
@@ -2005,7 +2234,7 @@ def _puct_features_guard(evaluator, features):
 
 
 def puct_play(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, leaves=None, capacity=None, reuse=True, features=None,
-              symmetry=None, first_root=0, life=False, ladder=False, outcome=False):
+              symmetry=None, first_root=0, life=False, ladder=False, outcome=False, superko=False):
     """Play `moves` moves from every root of batch_states ([R, 6, N, N]) with a PUCT search per move -> (actions int64
     [R, moves], the final states uint8 [R, 6, N, N]); device tensors for a device tensor, NumPy arrays for NumPy input.
     Per move: `iterations` rounds of PuctSearch (batch_puct's loop, with `leaves` and `capacity` as there), the move of
@@ -2026,7 +2255,11 @@ def puct_play(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, leav
     evaluator gets (planes, legal).  symmetry, first_root: as batch_puct; with reuse=False the search of move mv draws from
     the base seed symmetry + mv (a new search would repeat the first one's draws otherwise).  life: as batch_puct - the
     evaluator gets (planes, legal, life).  ladder: as batch_puct - the ladder planes as the evaluator's next argument.
-    outcome: as batch_puct - the move-outcome planes as the evaluator's last argument."""
+    outcome: as batch_puct - the move-outcome planes as the evaluator's last argument.
+    superko (False = everything above, launch for launch): positional superko at the roots - a PositionHistory of capacity
+    moves + 1 is seeded with the roots' hashes, PuctSearch.forbid_repeats runs before each move's rounds, and the new roots'
+    hashes are pushed after each move, so no move played recreates an earlier position of its game.  Repetitions inside the
+    tree below the root are not checked."""
     _puct_komi_guard(evaluator, komi)
     _puct_features_guard(evaluator, features)
     _puct_life_guard(life, features)
@@ -2039,7 +2272,10 @@ def puct_play(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, leav
                         first_root=first_root, life=life, ladder=ladder, outcome=outcome)
     box = search._box
     played = torch.empty((search._R, moves), dtype=_I64, device=box.t.device)
+    seen = PositionHistory(search._R, moves + 1, box.t.device).push(search._root_hashes()) if superko and search._R else None
     for mv in range(moves):
+        if seen is not None:
+            search.forbid_repeats(seen)
         for _ in range(search._I):
             priors, values = evaluator(*search.select())
             search.backup(priors, values)
@@ -2052,6 +2288,8 @@ def puct_play(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, leav
             search = PuctSearch(box, iterations, c, komi, leaves=leaves, capacity=capacity, features=features,
                                 symmetry=None if symmetry is None else int(symmetry) + mv + 1, first_root=first_root, life=life,
                                 ladder=ladder, outcome=outcome)
+        if seen is not None:
+            seen.push(search._root_hashes())
     return _back(box, played), box.back(search._root_states())
 
 
@@ -2087,7 +2325,7 @@ that ended, 0 for one still running), lengths (int32 [R]: moves played), final_s
 
 def puct_selfplay(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, leaves=None, capacity=None, noise=None,
                   eps=0.25, sample_moves=0, seed=20260927, first_game=0, record_states=False, features=None, symmetry=None,
-                  life=False, ladder=False, outcome=False):
+                  life=False, ladder=False, outcome=False, superko=False):
     """Self-play games for training: `moves` moves from every root of batch_states ([R, 6, N, N]) with a PUCT search per move
     on the kept tree -> SelfPlay (device tensors for a device tensor, NumPy arrays for NumPy input).  puct_play's
     reuse=True loop (`iterations` rounds per move with `leaves` and `capacity` as there, then PuctSearch.advance) with
@@ -2115,7 +2353,11 @@ def puct_selfplay(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, 
     legal, life); the records do not change, and there is no stopping rule here: a driver that wants to stop settled games
     early asks batch_settled(search.root_states()) in a loop of its own.  ladder: as batch_puct - the ladder planes as the
     evaluator's next argument; the records do not change.  outcome: as batch_puct - the move-outcome planes as the evaluator's
-    last argument; the records do not change."""
+    last argument; the records do not change.  superko (False = everything above, launch for launch): positional superko at
+    the roots, as puct_play - PuctSearch.forbid_repeats before each move's rounds and before the root noise, so
+    noise(mv, legal) sees the reduced legal set, and the new roots' hashes pushed after each advance: no recorded game
+    recreates an earlier position of its own, so games that would cycle until `moves` cuts them off with outcome 0 come to
+    an end.  Repetitions inside the tree below the root are not checked."""
     _puct_komi_guard(evaluator, komi)
     _puct_features_guard(evaluator, features)
     _puct_life_guard(life, features)
@@ -2151,9 +2393,12 @@ def puct_selfplay(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, 
                         life=life, ladder=ladder, outcome=outcome)
     rng = rng_seed(R, seed, first_game, device=dev)
     ones, todo = torch.ones(R, dtype=_U8, device=dev), torch.empty(R, dtype=_U8, device=dev)
+    seen = PositionHistory(R, moves + 1, dev).push(search._root_hashes()) if superko else None
     for mv in range(moves):
         if record_states:
             before[:, mv] = search._root_states()
+        if seen is not None:
+            search.forbid_repeats(seen)
         if noise is not None:
             z = noise(mv, search._legal_roots)
             todo.fill_(1)
@@ -2167,6 +2412,8 @@ def puct_selfplay(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, 
         played[:, mv], pis[:, mv], vals[:, mv] = acts, p, v
         lengths += (acts >= 0).to(_I32)
         search.advance(played[:, mv], check=False)
+        if seen is not None:
+            seen.push(search._root_hashes())
     final = search._root_states()
     black, white = _areas_dev(final)
     x = (black - white).to(torch.float32) - torch.full((), komi, dtype=torch.float32, device=dev)   # gg_puct_backup's terminal rule

@@ -872,6 +872,45 @@ int32_t gg_batch_move_planes_tracked(const uint32_t *tracked, const int32_t *ori
                                      int32_t N, void *hip_stream);
 int32_t gg_batch_move_counts(const uint8_t *states, uint8_t *out, int64_t B, int32_t N, void *hip_stream);
 
+/*
+ * Position hashes and positional superko: a 64-bit Zobrist hash of every board, the hash of the position after
+ * every move of the mover without building the child, and the moves that would recreate a position of the board's history.
+ * THE KEYS.  key(c, y, x), c = 0 black / 1 white, 0 <= y, x < 19, is output number i + 1, i = c * 361 + y * 19 + x, of the
+ * splitmix64 generator (state += 0x9E3779B97F4A7C15; z = state; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;
+ * z = (z ^ z >> 27) * 0x94D049BB133111EB; output z ^ z >> 31) started at state GG_HASH_SEED.  They do not depend on N; the
+ * 722 keys are distinct and non-zero; key(0, 0, 0) = 0xc8a43d929c6a465e, key(1, 18, 18) = 0x345c2fd1bcdda841.  The library
+ * holds them as a constant table of its code object: there is no initialisation call and no state.
+ * THE POSITION HASH.  hash(position) = the XOR of key(colour, y, x) over its stones, as int64.  It is POSITIONAL: the turn, the
+ * pass, ko and game-over flags do not enter, and the empty board hashes to 0.
+ * THE MOVE HASHES.  move_hash(position, a) for a in [0, N*N]: for a CANDIDATE point (empty, plane 3 clear, game not over: the
+ * candidates of the move-outcome planes) the hash of the position after the mover plays there and the opponent chains left
+ * without a liberty are removed (the played chain itself is never removed); for the pass and every point that is no
+ * candidate, hash(position).  Every slot is written.  The position is assumed to hold no chain without liberties; of a
+ * tracked board the class rows ARE read (they say which opponent stones are in atari) and must belong to the position.
+ * THE REPEAT MASK.  history int64 [B][H], count int32 [B]: board b's valid entries are its first min(max(count[b], 0), H).
+ * repeat[b][a] = 1 iff a is a candidate point and move_hash(b, a) equals a valid entry, else 0; the pass is never a repeat.
+ * Equal 64-bit hashes are TAKEN AS equal positions: two different positions collide with probability about 2^-64 per
+ * comparison, and a collision forbids a legal move; it never allows a repetition.
+ *   gg_batch_hash                 states uint8 [B][6][N][N] -> out int64 [B]
+ *   gg_batch_hash_tracked         the same from tracked boards uint32 [B][gg_tracked_words(N)]
+ *   gg_batch_move_hashes          states -> any of hashes int64 [B][N*N+1], repeat uint8 [B][N*N+1] and rows uint32 [B][N]
+ *                                 (the repeat points as row masks, bit x of rows[b][y]: the form a tracked board's invalid
+ *                                 rows take); each may be NULL, not all three
+ *   gg_batch_move_hashes_tracked  the same from tracked boards
+ * history and count may be NULL only when repeat and rows both are; they are not read then.  Checks, in this order and
+ * before any device work: N outside [2, 19] or B < 0 -> GG_E_BADSIZE; H < 0 -> GG_E_BADARG; B == 0 -> 0; the boards, every
+ * output, or a needed history / count NULL -> GG_E_NULLPTR; out / hashes / history not 8-byte aligned, rows / count not
+ * 4-byte aligned -> GG_E_BADARG.  Every call queues ONE launch on hip_stream and never synchronises; no global atomics; every
+ * store lies inside the outputs' B rows.
+ */
+#define GG_HASH_SEED 0x676F2D6861736821ull
+int32_t gg_batch_hash(const uint8_t *states, int64_t *out, int64_t B, int32_t N, void *hip_stream);
+int32_t gg_batch_hash_tracked(const uint32_t *tracked, int64_t *out, int64_t B, int32_t N, void *hip_stream);
+int32_t gg_batch_move_hashes(const uint8_t *states, const int64_t *history, const int32_t *count, int32_t H, int64_t *hashes,
+                             uint8_t *repeat, uint32_t *rows, int64_t B, int32_t N, void *hip_stream);
+int32_t gg_batch_move_hashes_tracked(const uint32_t *tracked, const int64_t *history, const int32_t *count, int32_t H,
+                                     int64_t *hashes, uint8_t *repeat, uint32_t *rows, int64_t B, int32_t N, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
