@@ -160,6 +160,8 @@ ABI = {
     'gg_batch_hash_tracked': _params(_I32, 'tracked') + _params(_I64, 'out') + _BN,
     'gg_batch_move_hashes': _params(_U8, 'states') + _MOVE_HASHES,
     'gg_batch_move_hashes_tracked': _params(_I32, 'tracked') + _MOVE_HASHES,
+    'gg_puct_superko': (_RNC + _params(_i32, 'L') + _params(_I32, 'links') + _params(_I64, 'node_hash', 'history')
+                        + _params(_I32, 'count') + _params(_i32, 'H') + _LEAF),
 }
 EXPORTS = tuple(ABI)
 _SIGNATURES = {f: ([p.kind if isinstance(p.kind, type) else _vp for p in ps], _i32) for f, ps in ABI.items()}   # argtypes, restype

@@ -1,5 +1,5 @@
 // gg_hash.hip - the position and move hashes (gg_hash.h) with their entry points (gg_batch_hash, gg_batch_hash_tracked,
-// gg_batch_move_hashes, gg_batch_move_hashes_tracked) as a translation unit of their own, compiled with the default
+// gg_batch_move_hashes, gg_batch_move_hashes_tracked, gg_puct_superko) as a translation unit of their own, compiled with the default
 // code-generation switches: the machine code of every kernel of the other units - and the hashes bench.py ties their PMC
 // records to - does not depend on anything in here.  The launch path is plane_launch of gg_planes.h.
 #include <hip/hip_runtime.h>
@@ -36,6 +36,21 @@ struct MoveHashCall {
   template <int R, bool TRACKED>
   void launch(unsigned grid, hipStream_t s, int, uint32_t) const {
     k_move_hashes<R, TRACKED><<<grid, kWave, 0, s>>>(in, history, count, H, hashes, repeat, rows, B, N);
+  }
+};
+
+struct SuperkoCall {
+  uint32_t *leaf;
+  const int32_t *move, *leaf_id, *links;
+  int64_t *node_hash;
+  const int64_t *history;
+  const int32_t *count;
+  int32_t H, C, L;
+  int64_t B;
+  int32_t N;
+  template <int R, bool TRACKED>
+  void launch(unsigned grid, hipStream_t s, int, uint32_t) const {   // (tracked boards only)
+    k_puct_superko<R><<<grid, kWave, 0, s>>>(leaf, move, leaf_id, links, node_hash, history, count, H, C, L, B, N);
   }
 };
 
@@ -81,6 +96,21 @@ int32_t gg_batch_move_hashes(const uint8_t *states, const int64_t *history, cons
 int32_t gg_batch_move_hashes_tracked(const uint32_t *tracked, const int64_t *history, const int32_t *count, int32_t H,
                                      int64_t *hashes, uint8_t *repeat, uint32_t *rows, int64_t B, int32_t N, void *hip_stream) {
   return batch_move_hashes(true, tracked, history, count, H, hashes, repeat, rows, B, N, hip_stream);
+}
+
+// the checks in the order of include/gymgo_amd.h, all before any device work
+int32_t gg_puct_superko(int64_t R, int32_t N, int32_t C, int32_t L, const int32_t *links, int64_t *node_hash, const int64_t *history,
+                        const int32_t *count, int32_t H, uint32_t *leaf, const int32_t *move, const int32_t *leaf_id,
+                        void *hip_stream) {
+  if (N < 2 || N > GG_MAX_BOARD || R < 0) return GG_E_BADSIZE;
+  if (C < 1 || C == INT32_MAX || L < 1 || L > C || H < 0) return GG_E_BADARG;
+  if (R == 0) return 0;
+  if (!links || !node_hash || !leaf || !move || !leaf_id || (history == nullptr) != (count == nullptr)) return GG_E_NULLPTR;
+  if (((uintptr_t)node_hash & 7u) || ((uintptr_t)history & 7u)) return GG_E_BADARG;
+  if ((((uintptr_t)links | (uintptr_t)count | (uintptr_t)leaf | (uintptr_t)move | (uintptr_t)leaf_id) & 3u)) return GG_E_BADARG;
+  const int64_t B = R * (int64_t)L;
+  return plane_launch(SuperkoCall{leaf, move, leaf_id, links, node_hash, history, count, H, C, L, B, N}, true, leaf, leaf, leaf, 3,
+                      GG_FEAT_U8, B, N, hip_stream);
 }
 
 }  // extern "C"

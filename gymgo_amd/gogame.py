@@ -1758,11 +1758,30 @@ class PuctSearch:
     move-outcome planes [R, 12, N, N] ([R * L, ..]) of the feature dtype as its last element, after the life and ladder
     planes when those are on - batch_move_planes of the leaves, from the tracked leaf boards
     (gg_batch_move_planes_tracked), in the orientation of `search.orient` with symmetry=.  One launch more per select();
-    nothing else changes."""
+    nothing else changes.
+
+    superko (None = everything above, every allocation and launch as without it; or a PositionHistory of the R games with
+    the current roots included; anything else raises _history_arg's ValueError): positional superko AT EVERY NODE below the
+    root (gg_puct_superko).  At node y a board move is illegal if it recreates - by its 64-bit hash - a valid entry of the
+    history or the position of any node on y's parent chain up to node 0.  The tree is a tree, so a node's chain never
+    changes and the rule is applied once, when the node is made: select() queues gg_puct_superko directly behind
+    gg_batch_play_moves_tracked and in front of every hand-out launch, it ORs the forbidden points into the invalid rows of
+    the new leaves, and the planes, `legal`, the stored priors and every later select follow from the board.  The search
+    keeps the history object - its tensors are read at launch time, nothing synchronises - and `node_hash`, int64
+    [R, capacity]: the hash of every evaluated node, refilled by one gg_batch_hash_tracked over the whole boards buffer
+    (allocated zeroed: an unused node is an empty board, hash 0, above nodes[r] and never read) after gg_puct_begin and
+    after every advance().  The caller still pushes the new roots' hashes after advance() and still calls forbid_repeats()
+    for node 0 - with no argument it uses the search's history.  THE INVARIANT that keeps the marks right across advance():
+    a kept node was marked against (old history + its old chain); the old root and the node under the action played leave
+    the chain and enter the history, so that set IS (new history + its new chain) - provided the history has dropped no
+    entry: give the PositionHistory the capacity of the whole game.  One launch more per select(), one per advance()."""
 
     def __init__(self, batch_states, iterations, c=1.25, komi=0.0, leaves=None, capacity=None, features=None, symmetry=None,
-                 first_root=0, life=False, ladder=False, outcome=False):
+                 first_root=0, life=False, ladder=False, outcome=False, superko=None):
         self._feat = None if features is None else (features, _feature_dtype(features))
+        if superko is not None:   # (before a device is touched)
+            shape = np.shape(batch_states.t if isinstance(batch_states, _Box) else batch_states)
+            _history_arg(superko, shape[0] if shape else -1)
         _puct_symmetry_guard(symmetry, features)
         _puct_life_guard(life, features)
         _puct_ladder_guard(ladder, features)
@@ -1783,11 +1802,17 @@ class PuctSearch:
         NN = _puct_capacity(self._I, self._L, capacity)
         R, N, dev = st.shape[0], st.shape[2], st.device
         self._R, self._N, self._dev = R, N, dev
+        self._history = superko
+        if superko is not None:
+            self._hist = _history_arg(superko, R)
+            if self._hist[0].device != dev or self._hist[1].device != dev:
+                raise ValueError('history must be a PositionHistory of %d boards on the device of batch_states (%s)' % (R, dev))
         self._C = NN - 1        # what the kernels get as I / C: only a capacity there
         self._scratch = None    # advance()'s buffers, allocated on its first call
         W, A, B = tracked_words(N), N * N + 1, R * (self._L or 1)   # B: the rows handed out per select()
         self._legal_roots = _legal_roots(st)
-        self._boards = torch.empty((R, NN, W), dtype=_I32, device=dev)
+        self._boards = (torch.empty if superko is None else torch.zeros)((R, NN, W), dtype=_I32, device=dev)
+        self.node_hash = None if superko is None else torch.zeros((R, NN), dtype=_I64, device=dev)
         self._child = torch.empty((R, NN, A), dtype=_I32, device=dev)
         self._prior = torch.empty((R, NN, A), dtype=torch.float32, device=dev)
         self._links = torch.empty((R, NN, 2), dtype=_I32, device=dev)
@@ -1820,6 +1845,15 @@ class PuctSearch:
                       _lib.ptrs('gg_batch_features_tracked', out=self._states)) + _lib.ptrs('gg_puct_legal', legal=self._legal, live=self.live)
         self._rows = [p for p in _lib.ABI['gg_puct_backup'] if p.name in ('priors', 'values')]
         _lib.call('gg_puct_begin', _track_roots(st), R, N, self._C, *self._tree, _lib.current_raw_stream(dev))
+        if superko is not None:
+            self._ko = _lib.ptrs('gg_puct_superko', links=self._links, node_hash=self.node_hash)
+            self._fill_node_hash()
+
+    def _fill_node_hash(self):
+        """node_hash = the hash of every board of the boards buffer (R > 0): one launch."""
+        R, NN = self._R, self._C + 1
+        _lib.call('gg_batch_hash_tracked', self._boards.view(R * NN, -1), self.node_hash, R * NN, self._N,
+                  _lib.current_raw_stream(self._dev))
 
     def _init_symmetry(self, B):
         """symmetry: the generators of the B rows handed out, their orientations, legal in the view, the priors turned back."""
@@ -1871,6 +1905,10 @@ class PuctSearch:
             name, slots = ('gg_puct_select', ()) if self._L is None else ('gg_puct_select_leaves', (self._L,))
             check(getattr(lib, name)(R, N, self._C, *slots, self._c, *self._tree, lp, mp, ip, stream), name)
             check(lib.gg_batch_play_moves_tracked(lp, mp, None, B, N, 1, stream), 'gg_batch_play_moves_tracked')
+            if self._history is not None:   # (the history's tensors as they are now: PositionHistory.push works in place)
+                hp, cp = _lib.ptrs('gg_puct_superko', history=self._hist[0], count=self._hist[1])
+                check(lib.gg_puct_superko(R, N, self._C, self._L or 1, *self._ko, hp, cp, self._hist[2], lp, mp, ip, stream),
+                      'gg_puct_superko')
             if self._feat is None:
                 check(lib.gg_batch_untrack_states(lp, sp, B, N, stream), 'gg_batch_untrack_states')
             else:   # (sp: the planes)
@@ -2015,6 +2053,8 @@ class PuctSearch:
                 raise ValueError('PuctSearch.advance(): action %d is not legal at root %d' % (int(acts[r]), r))
         ap, np_, rp, kp = self._play_on_roots(acts)
         _lib.call('gg_puct_advance', ap, np_, R, N, self._C, *self._tree, rp, kp, _lib.current_raw_stream(self._dev))
+        if self._history is not None:
+            self._fill_node_hash()
         self._legal_roots = _legal_roots(self._root_states())
         self._done, self._I = 0, rounds
         return self._kept
@@ -2029,18 +2069,21 @@ class PuctSearch:
             self._next.copy_(self._boards[:, 0, :])
         return batch_hash_tracked(self._next)
 
-    def forbid_repeats(self, history):
+    def forbid_repeats(self, history=None):
         """Positional superko AT THE ROOTS: the moves that would recreate a position of `history` (a PositionHistory of the R
         games, the current roots included) become illegal at node 0 of every tree - the repeat points of
         gg_batch_move_hashes_tracked, as row masks, are ORed into the invalid rows of the root boards, and result().legal
         follows.  Select, the prior mask of a root's first evaluation, add_root_noise and root_policy all read legality from
         the board, so a child kept under a forbidden action simply stops being chosen or counted.  Only the roots are
-        marked: repetitions inside the tree below them are not checked.  Call it before the rounds of a move (and before
+        marked here: the nodes below them are marked when they are made, and only by a search constructed with superko= (whose
+        history is the default of `history`; without one the argument is required).  Call it before the rounds of a move (and before
         add_root_noise); advance() brings new root boards, whose invalid rows are their own.  Raises ValueError while leaves
         are outstanding.  One copy, one launch and two torch ops; nothing synchronises."""
         if self._pending:
             raise ValueError('PuctSearch.forbid_repeats(): the leaves of the last select() have not been backed up')
         R, N = self._R, self._N
+        if history is None:
+            history = self._history
         _history_arg(history, R)
         if not R:
             return
@@ -2121,7 +2164,7 @@ class PuctSearch:
 
 
 def batch_puct(batch_states, iterations, evaluator, c=1.25, komi=0.0, tree=False, leaves=None, capacity=None, features=None,
-               symmetry=None, first_root=0, life=False, ladder=False, outcome=False):
+               symmetry=None, first_root=0, life=False, ladder=False, outcome=False, superko=None):
     """PUCT search (the AlphaZero search) of `iterations` iterations from every root of batch_states ([R, 6, N, N]) with the
     caller's evaluator -> Puct (device tensors for a device tensor, NumPy arrays for NumPy input).  The loop over PuctSearch.
 
@@ -2186,14 +2229,21 @@ def batch_puct(batch_states, iterations, evaluator, c=1.25, komi=0.0, tree=False
 
     outcome (False: the search above, launch for launch; True, with features=): the evaluator gets as its last argument,
     after life and ladder when those are on, the move-outcome planes [R, 12, N, N] ([R * L, ..]) of the feature dtype -
-    batch_move_planes of the leaves, in the leaf's orientation with symmetry= (PuctSearch)."""
+    batch_move_planes of the leaves, in the leaf's orientation with symmetry= (PuctSearch).
+
+    superko (None: the search above, launch for launch; or a PositionHistory of the R games, batch_states' own positions
+    included): the search of one position of a recorded game under positional superko - PuctSearch.forbid_repeats once before
+    round 0 for the roots, and gg_puct_superko in every round for the nodes below them (PuctSearch): no node of the tree
+    reached by a board move has the position of one of its ancestors or of the history.  result().legal is the reduced set."""
     _puct_komi_guard(evaluator, komi)
     _puct_features_guard(evaluator, features)
     _puct_life_guard(life, features)
     _puct_ladder_guard(ladder, features)
     _puct_outcome_guard(outcome, features)
     search = PuctSearch(batch_states, iterations, c, komi, leaves=leaves, capacity=capacity, features=features, symmetry=symmetry,
-                        first_root=first_root, life=life, ladder=ladder, outcome=outcome)
+                        first_root=first_root, life=life, ladder=ladder, outcome=outcome, superko=superko)
+    if superko is not None:
+        search.forbid_repeats()
     for _ in range(search._I):
         priors, values = evaluator(*search.select())
         search.backup(priors, values)
@@ -2224,6 +2274,20 @@ def _puct_ladder_guard(ladder, features):
 def _puct_outcome_guard(outcome, features):
     if outcome and features is None:   # (before a device is touched)
         raise ValueError('outcome=True hands out the move-outcome planes in the dtype of features=: give features= too')
+
+
+def _puct_superko_guard(superko):
+    if superko is not False and superko is not True and not (type(superko) is type('') and superko == 'tree'):   # (before a device is touched)
+        raise ValueError("superko must be False, True (the roots) or 'tree' (every node) (got %r)" % (superko,))
+
+
+def _puct_superko_history(superko, box, moves):
+    """The PositionHistory of a move loop with superko='tree' (else None), made BEFORE the search that keeps it: it is seeded
+    once the search stands, and the search reads it no earlier than its first select()."""
+    st = box.t
+    if superko is True or not superko or st.dim() != 4 or not st.shape[0]:
+        return None
+    return PositionHistory(st.shape[0], moves + 1, st.device)
 
 
 def _puct_features_guard(evaluator, features):
@@ -2258,8 +2322,11 @@ def puct_play(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, leav
     outcome: as batch_puct - the move-outcome planes as the evaluator's last argument.
     superko (False = everything above, launch for launch): positional superko at the roots - a PositionHistory of capacity
     moves + 1 is seeded with the roots' hashes, PuctSearch.forbid_repeats runs before each move's rounds, and the new roots'
-    hashes are pushed after each move, so no move played recreates an earlier position of its game.  Repetitions inside the
-    tree below the root are not checked."""
+    hashes are pushed after each move, so no move played recreates an earlier position of its game.  With True the
+    repetitions inside the tree below the root are not checked: the search still plans with them.  superko='tree': the loop of
+    True with the history also handed to the search (PuctSearch(superko=)), with reuse=False to the new search of every move
+    too: the rule holds at every node.  Any other value raises ValueError."""
+    _puct_superko_guard(superko)
     _puct_komi_guard(evaluator, komi)
     _puct_features_guard(evaluator, features)
     _puct_life_guard(life, features)
@@ -2268,11 +2335,18 @@ def puct_play(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, leav
     moves = int(moves)
     if moves < 0:
         raise ValueError('need moves >= 0 (got %d)' % moves)
+    deep = None
+    if superko is not True and superko:   # ('tree': the search keeps the history, which therefore stands before the search)
+        _puct_symmetry_guard(symmetry, features)
+        batch_states = batch_states if isinstance(batch_states, _Box) else _Box(batch_states)
+        deep = _puct_superko_history(superko, batch_states, moves)
     search = PuctSearch(batch_states, iterations, c, komi, leaves=leaves, capacity=capacity, features=features, symmetry=symmetry,
-                        first_root=first_root, life=life, ladder=ladder, outcome=outcome)
+                        first_root=first_root, life=life, ladder=ladder, outcome=outcome, superko=deep)
     box = search._box
     played = torch.empty((search._R, moves), dtype=_I64, device=box.t.device)
-    seen = PositionHistory(search._R, moves + 1, box.t.device).push(search._root_hashes()) if superko and search._R else None
+    seen = None
+    if superko and search._R:
+        seen = (deep or PositionHistory(search._R, moves + 1, box.t.device)).push(search._root_hashes())
     for mv in range(moves):
         if seen is not None:
             search.forbid_repeats(seen)
@@ -2287,7 +2361,7 @@ def puct_play(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, leav
             box.t = search._played_states(played[:, mv])
             search = PuctSearch(box, iterations, c, komi, leaves=leaves, capacity=capacity, features=features,
                                 symmetry=None if symmetry is None else int(symmetry) + mv + 1, first_root=first_root, life=life,
-                                ladder=ladder, outcome=outcome)
+                                ladder=ladder, outcome=outcome, superko=deep)
         if seen is not None:
             seen.push(search._root_hashes())
     return _back(box, played), box.back(search._root_states())
@@ -2357,7 +2431,10 @@ def puct_selfplay(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, 
     the roots, as puct_play - PuctSearch.forbid_repeats before each move's rounds and before the root noise, so
     noise(mv, legal) sees the reduced legal set, and the new roots' hashes pushed after each advance: no recorded game
     recreates an earlier position of its own, so games that would cycle until `moves` cuts them off with outcome 0 come to
-    an end.  Repetitions inside the tree below the root are not checked."""
+    an end.  With True the repetitions inside the tree below the root are not checked, and the visit counts recorded as pi
+    include plans through them; superko='tree' is the loop of True with the history also handed to the search
+    (PuctSearch(superko=)): the rule holds at every node.  Any other value raises ValueError."""
+    _puct_superko_guard(superko)
     _puct_komi_guard(evaluator, komi)
     _puct_features_guard(evaluator, features)
     _puct_life_guard(life, features)
@@ -2389,11 +2466,12 @@ def puct_selfplay(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, 
     before = torch.empty((R, moves, govars.NUM_CHNLS, N, N), dtype=_U8, device=dev) if record_states else None
     if not R or not moves:
         return _back(box, SelfPlay(played, pis, vals, won, lengths, st, before))
+    deep = _puct_superko_history(superko, box, moves)
     search = PuctSearch(box, I, c, komi, leaves=leaves, capacity=capacity, features=features, symmetry=symmetry, first_root=first_game,
-                        life=life, ladder=ladder, outcome=outcome)
+                        life=life, ladder=ladder, outcome=outcome, superko=deep)
     rng = rng_seed(R, seed, first_game, device=dev)
     ones, todo = torch.ones(R, dtype=_U8, device=dev), torch.empty(R, dtype=_U8, device=dev)
-    seen = PositionHistory(R, moves + 1, dev).push(search._root_hashes()) if superko else None
+    seen = (deep or PositionHistory(R, moves + 1, dev)).push(search._root_hashes()) if superko else None
     for mv in range(moves):
         if record_states:
             before[:, mv] = search._root_states()

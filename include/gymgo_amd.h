@@ -911,6 +911,45 @@ int32_t gg_batch_move_hashes(const uint8_t *states, const int64_t *history, cons
 int32_t gg_batch_move_hashes_tracked(const uint32_t *tracked, const int64_t *history, const int32_t *count, int32_t H,
                                      int64_t *hashes, uint8_t *repeat, uint32_t *rows, int64_t B, int32_t N, void *hip_stream);
 
+/*
+ * Positional superko AT EVERY NODE of a PUCT tree: one launch between gg_batch_play_moves_tracked and the
+ * evaluation of a round's leaves.  THE RULE: at node y of root r's tree a board move a is illegal if the position after a has
+ * the hash of a valid entry of game r's history, or of the position of any node on the parent chain of y, from y's parent up
+ * to node 0.  Equality is that of the 64-bit hashes (above); the pass is never forbidden; a node whose game has ended has no
+ * candidates.  The tree is a tree, so a node's chain never changes: the rule is applied ONCE, when the node is made - the
+ * forbidden points are ORed into the invalid rows of the new node's tracked board before it is evaluated and stored, and
+ * select, gg_puct_legal, the prior mask of the first evaluation, the feature planes, gg_puct_root_policy and
+ * gg_puct_root_noise, which all read legality from the board, follow.  After gg_puct_advance the marks of a kept node stay
+ * right: it was marked against (old history + its old chain), and that set equals (new history + its new chain) as long as the
+ * history has dropped no entry - the old root and the node under the action played have moved from the chain into the history.
+ * links int32 [R][C+1][2]: the tree's own.  node_hash int64 [R][C+1]: the position hash of every evaluated node.  history int64
+ * [R][H], count int32 [R]: the repeat mask's (root r's valid entries are its first min(max(count[r], 0), H)); both may be NULL
+ * - no game history, H is ignored -, one alone may not.  leaf uint32 [R*L][W], move and leaf_id int32 [R*L]: the outputs of the
+ * select launch AFTER gg_batch_play_moves_tracked; the one-leaf path passes L = 1.  Row i belongs to root r = i / L; y =
+ * leaf_id[i], m = move[i]:
+ *   y < 1, y > C or m < 0   the row is SKIPPED: no byte of leaf[i] and no entry of node_hash is written (an empty slot, a node
+ *                           evaluated again - its board carries its marks already -, the root of round 0 - that is
+ *                           gg_batch_move_hashes_tracked's `rows` -, a select without room);
+ *   otherwise               node_hash[r][y] = hash(leaf[i]), and every candidate point of leaf[i] (empty, invalid bit clear,
+ *                           game not over) whose move hash is in the forbidden set gets its bit set in words [2N, 3N) of
+ *                           leaf[i].  The forbidden set: the valid entries of history[r] and node_hash[r][x] for x =
+ *                           parent(y), parent(parent(y)), .. down to node 0.  No other word of leaf changes.
+ * THE WALK IS BOUNDED: it goes on only while the parent p of x satisfies 0 <= p < x, and takes at most C steps - corrupt links
+ * can neither loop nor leave root r's slice of links and node_hash.
+ * WHO FILLS node_hash: the caller fills node_hash[r][0] (gg_batch_hash_tracked of the roots), and after gg_puct_advance the
+ * entries of the kept nodes (one gg_batch_hash_tracked over the boards buffer does both).  The launch reads node_hash only at
+ * ancestors, which are evaluated nodes of earlier rounds, and writes it only at nodes made in this round; such a node is never
+ * on another slot's path (collision rule a of gg_puct_select_leaves), and an ended node that several slots take has m = -1
+ * and is skipped: the slots of one root do not race.
+ * Checks, in this order and before any device work: N outside [2, 19] or R < 0 -> GG_E_BADSIZE; C < 1, C = 2^31 - 1, L < 1,
+ * L > C or H < 0 -> GG_E_BADARG; R == 0 -> 0; a NULL pointer other than the history pair, or exactly one of the pair NULL ->
+ * GG_E_NULLPTR; node_hash or history not 8-byte aligned, any other buffer not 4-byte aligned -> GG_E_BADARG.  ONE launch on
+ * hip_stream, no synchronisation, no global atomics; every store is a vector store inside the rows named above.
+ */
+int32_t gg_puct_superko(int64_t R, int32_t N, int32_t C, int32_t L, const int32_t *links, int64_t *node_hash,
+                        const int64_t *history, const int32_t *count, int32_t H, uint32_t *leaf, const int32_t *move,
+                        const int32_t *leaf_id, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
