@@ -4,7 +4,8 @@ There is NO CPU fallback: if the shared library is missing, or a tensor is not a
 ROCm device tensor of the dtype its parameter takes, the call raises.  PyTorch is used only for device
 memory and the current HIP stream; every entry point of include/gymgo_amd.h is bound here with plain
 pointers, from ONE table (ABI) that tests/test_host_abi.py holds against the header, and reached through
-call().  A new entry point is one declaration in the header and one entry in the table.
+call().  A new entry point is one declaration in the header and one entry in the table.  The area family has a header of
+its own, include/gymgo_amd_area.h, and a table of its own, ABI_AREA, bound and called the same way.
 """
 import collections
 import ctypes
@@ -163,11 +164,24 @@ ABI = {
     'gg_puct_superko': (_RNC + _params(_i32, 'L') + _params(_I32, 'links') + _params(_I64, 'node_hash', 'history')
                         + _params(_I32, 'count') + _params(_i32, 'H') + _LEAF),
 }
+# ... and of include/gymgo_amd_area.h, the area family's header, in its order: a table of its own, so that ABI stays the
+# description of include/gymgo_amd.h alone (tests/test_area_host.py holds this one against its header the same way)
+ABI_AREA = {
+    'gg_area_planes': (),
+    'gg_batch_area': (_params(_U8, 'states') + _params(_I32, 'orient') + _params(_FLAGS, 'side') + _OUT + _params(_I32, 'counts')
+                      + _OUT_BN),
+    'gg_batch_area_tracked': (_params(_I32, 'tracked', 'orient') + _params(_FLAGS, 'side') + _OUT + _params(_I32, 'counts')
+                              + _OUT_BN),
+}
 EXPORTS = tuple(ABI)
-_SIGNATURES = {f: ([p.kind if isinstance(p.kind, type) else _vp for p in ps], _i32) for f, ps in ABI.items()}   # argtypes, restype
+EXPORTS_AREA = tuple(ABI_AREA)
+_signatures = lambda table: {f: ([p.kind if isinstance(p.kind, type) else _vp for p in ps], _i32) for f, ps in table.items()}
+_SIGNATURES = _signatures(ABI)   # argtypes, restype
+_SIGNATURES_AREA = _signatures(ABI_AREA)
 # call(): the number of parameters and (index, dtypes, name) of every pointer to device memory
 _POINTERS = {f: (len(ps), tuple((i, p.kind if isinstance(p.kind, tuple) else (p.kind,), p.name)
-                                for i, p in enumerate(ps) if not isinstance(p.kind, type))) for f, ps in ABI.items()}
+                                for i, p in enumerate(ps) if not isinstance(p.kind, type)))
+             for table in (ABI, ABI_AREA) for f, ps in table.items()}
 
 _lib = None
 
@@ -181,7 +195,7 @@ def build(force=False):
     import subprocess
     csrc = os.path.join(_HERE, 'csrc')
     srcs = [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(('.hip', '.h'))]
-    srcs.append(os.path.join(os.path.dirname(_HERE), 'include', 'gymgo_amd.h'))
+    srcs += [os.path.join(os.path.dirname(_HERE), 'include', h) for h in ('gymgo_amd.h', 'gymgo_amd_area.h')]
     stale = not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < max(os.path.getmtime(f) for f in srcs)
     if force or stale:
         subprocess.check_call(['make', '-C', os.path.join(_HERE, 'csrc'), '-s', '-B', '-j3'])
@@ -196,7 +210,7 @@ def lib():
                 'HIP library %s not built (run `make -C gymgo_amd/csrc` or __graft_entry__.build()); '
                 'gymgo_amd has no CPU fallback' % LIB_PATH)
         L = ctypes.CDLL(LIB_PATH)
-        for name, (argtypes, restype) in _SIGNATURES.items():
+        for name, (argtypes, restype) in list(_SIGNATURES.items()) + list(_SIGNATURES_AREA.items()):
             fn = getattr(L, name)  # AttributeError if the .so does not export what the header declares
             fn.argtypes, fn.restype = argtypes, restype
         if L.gg_version() != ABI_VERSION:
@@ -344,7 +358,7 @@ def dev_ptr(t, dtype, name):
 def ptrs(fn, **tensors):
     """dev_ptr of every tensor as the parameter of entry point `fn` it is named after - dtype(s) from the table -, in the order
     given: for the paths that check their buffers once and hand call() the pointers from then on."""
-    kinds = {p.name: p.kind for p in ABI[fn]}
+    kinds = {p.name: p.kind for p in (ABI[fn] if fn in ABI else ABI_AREA[fn])}
     return tuple(dev_ptr(t, kinds[n], n) for n, t in tensors.items())
 
 

@@ -740,8 +740,11 @@ __global__ __launch_bounds__(4 * kWave, 4) void k_rollout_lat_w4(uint8_t *__rest
 // Tromp-Taylor areas (gym_go/gogame.py:275-300) of the wave's boards in this layout: a colour owns its stones plus the empty
 // regions that touch only that colour, and a region touches a colour iff the flood of the EMPTY points seeded next to that
 // colour's stones covers it - two floods in two fields of one register (19x19: two registers), summed per board.
+// lat_area_floods: THE TWO FLOODS, stated once - fb / fw = this lane's row of the empty points black / white reaches.  Black
+// owns bl | (fb & ~fw), white wh | (fw & ~fb): lat_areas sums them, lat_areas_owned (gg_po.h) and area_owned (gg_area.h) keep
+// the rows as well.
 template <int R>
-__device__ __forceinline__ void lat_areas(uint32_t bl, uint32_t wh, uint32_t full, uint32_t &area_b, uint32_t &area_w) {
+__device__ __forceinline__ void lat_area_floods(uint32_t bl, uint32_t wh, uint32_t full, uint32_t &fb, uint32_t &fw) {
   using L = Lat<R>;
   constexpr int LPB = L::LPB, FW = L::FW, K = L::NF >= 2 ? 1 : 2;
   const uint32_t E = full & ~(bl | wh);
@@ -757,7 +760,14 @@ __device__ __forceinline__ void lat_areas(uint32_t bl, uint32_t wh, uint32_t ful
 #pragma unroll
   for (int k = 0; k < K; ++k) Mkr[k] = __brev(Mk[k]);
   lat_flood<LPB, K>(F, Mk, Mkr);
-  const uint32_t fb = K == 1 ? (F[0] & L::FM) : F[0], fw = K == 1 ? (F[0] >> (FW & 31)) : F[K - 1];
+  fb = K == 1 ? (F[0] & L::FM) : F[0];
+  fw = K == 1 ? (F[0] >> (FW & 31)) : F[K - 1];
+}
+template <int R>
+__device__ __forceinline__ void lat_areas(uint32_t bl, uint32_t wh, uint32_t full, uint32_t &area_b, uint32_t &area_w) {
+  constexpr int LPB = Lat<R>::LPB;
+  uint32_t fb, fw;
+  lat_area_floods<R>(bl, wh, full, fb, fw);
   const uint32_t cb = (uint32_t)__popc(bl) + (uint32_t)__popc(fb & ~fw), cw = (uint32_t)__popc(wh) + (uint32_t)__popc(fw & ~fb);
   const uint32_t sum = lat_board_sum<LPB>(cb | (cw << 16));     // (<= 361 each)
   area_b = sum & 0xFFFFu;

@@ -50,22 +50,9 @@ __device__ __forceinline__ uint64_t po_seed(uint64_t base_seed, int64_t p) {
 template <int R>
 __device__ __forceinline__ void lat_areas_owned(uint32_t bl, uint32_t wh, uint32_t full, uint32_t &own_b, uint32_t &own_w,
                                                 uint32_t &area_b, uint32_t &area_w) {
-  using L = Lat<R>;
-  constexpr int LPB = L::LPB, FW = L::FW, K = L::NF >= 2 ? 1 : 2;
-  const uint32_t E = full & ~(bl | wh);
-  const uint32_t sb = lat_dilate<LPB>(bl) & E, sw = lat_dilate<LPB>(wh) & E;
-  uint32_t F[K], Mk[K], Mkr[K];
-  if (K == 1) {
-    F[0] = sb | (sw << (FW & 31));
-    Mk[0] = E | (E << (FW & 31));
-  } else {
-    F[0] = sb; F[K - 1] = sw;
-    Mk[0] = E; Mk[K - 1] = E;
-  }
-#pragma unroll
-  for (int k = 0; k < K; ++k) Mkr[k] = __brev(Mk[k]);
-  lat_flood<LPB, K>(F, Mk, Mkr);
-  const uint32_t fb = K == 1 ? (F[0] & L::FM) : F[0], fw = K == 1 ? (F[0] >> (FW & 31)) : F[K - 1];
+  constexpr int LPB = Lat<R>::LPB;
+  uint32_t fb, fw;
+  lat_area_floods<R>(bl, wh, full, fb, fw);
   own_b = bl | (fb & ~fw);
   own_w = wh | (fw & ~fb);
   const uint32_t sum = lat_board_sum<LPB>((uint32_t)__popc(own_b) | ((uint32_t)__popc(own_w) << 16));   // (<= 361 each)

@@ -801,15 +801,45 @@ def _orient_arg(orient, B):
         raise ValueError('orient must be %d integers in 0..7, one per row (got %d of %s)' % (B, n, orient.dtype))
 
 
+def _side_arg(side, B):
+    """ValueError unless side is B integers or booleans (a tensor or an array) - before a device is touched."""
+    if isinstance(side, torch.Tensor):
+        n, integral = side.numel(), not (side.dtype.is_floating_point or side.dtype.is_complex)
+    else:
+        side = np.asarray(side)
+        n, integral = side.size, side.dtype.kind in 'iub'
+    if not integral or n != B:
+        raise ValueError('side must be %d integers, 0 = black\'s view, non-zero = white\'s, one per row (got %d of %s)' % (B, n, side.dtype))
+
+
+def _side_tensor(side, B, device):
+    """side (checked by _side_arg) as uint8 [B] on `device`: 0 / 1."""
+    s = side if isinstance(side, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(side) != 0))
+    return (s.to(device=device) != 0).to(_U8).reshape(B).contiguous()
+
+
+def _counts_arg(counts, B):
+    """ValueError unless counts is a flag or a contiguous int32 [B, 2] device tensor to write into - before a device is touched."""
+    if isinstance(counts, torch.Tensor) and (not counts.is_cuda or counts.dtype != _I32 or tuple(counts.shape) != (B, 2)
+                                             or not counts.is_contiguous()):
+        raise ValueError('counts must be a flag or a contiguous int32 [%d, 2] device tensor (got %s %s on %s)' % (
+            B, counts.dtype, list(counts.shape), counts.device))
+
+
 _NO_BYTES = ()   # _plane_launch's extra of an entry point that takes orient itself and writes no per-board bytes
+_AreaExtra = collections.namedtuple('_AreaExtra', 'side counts')   # _plane_launch's extra of gg_batch_area[_tracked]: its two optional pointers
 
 
 def _plane_launch(name, boards, orient, out, extra, code, B, N, stream, launch=_lib.call):
     """One launch of a plane entry point on tensors (_lib.call) or, launch=_lib.launch, on prepared pointers alone.  name: gg_batch_features[_tracked] - its
     _oriented form when orient is given, and no per-board bytes (extra is False) - or gg_batch_life[_tracked] /
     gg_batch_ladder[_tracked], which take orient (or None) and the per-board bytes (or None) themselves, or
-    gg_batch_move_planes[_tracked], which take orient (or None) and have no per-board bytes (extra is _NO_BYTES)."""
-    if extra is _NO_BYTES:
+    gg_batch_move_planes[_tracked], which take orient (or None) and have no per-board bytes (extra is _NO_BYTES), or
+    gg_batch_area[_tracked], which take orient, side (uint8 [B]) in front of out and counts (int32 [B, 2]) behind it, each
+    or None (extra is an _AreaExtra)."""
+    if type(extra) is _AreaExtra:
+        args = (boards, orient, extra.side, out, extra.counts)
+    elif extra is _NO_BYTES:
         args = (boards, orient, out)
     elif extra is not False:
         args = (boards, orient, out, extra)
@@ -821,12 +851,16 @@ def _plane_launch(name, boards, orient, out, extra, code, B, N, stream, launch=_
 
 
 def _planes(name, count, align, boards, tracked, dtype, out, orient, extra=None):
-    """The body of the eight batch plane calls: `count` planes per board from byte planes (a tensor or an array) or, `tracked`,
+    """The body of the ten batch plane calls: `count` planes per board from byte planes (a tensor or an array) or, `tracked`,
     from tracked boards (a device tensor), through the C entry point `name` (_plane_launch), into `out` (aligned to
     `align` bytes) or a new tensor.  extra: None (the entry point has no per-board bytes and an _oriented form), _NO_BYTES
-    (none either, orient is a parameter), or whether they are wanted -> planes, or (planes, bytes uint8 [B]).  Every
-    ValueError comes before a device is touched."""
+    (none either, orient is a parameter), or whether they are wanted -> planes, or (planes, bytes uint8 [B]); or an
+    _AreaExtra (side: None or B flags, a tensor or an array; counts: whether they are wanted) -> planes, or (planes, counts
+    int32 [B, 2]).  Every ValueError comes before a device is touched."""
     code = _feature_dtype(dtype)
+    area = extra if type(extra) is _AreaExtra else None
+    if area is not None:
+        extra = isinstance(area.counts, torch.Tensor) or bool(area.counts)
     if tracked:
         if not isinstance(boards, torch.Tensor) or boards.dim() != 2:
             raise ValueError('tracked boards are int32 [B, 5N+1] device tensors')
@@ -837,6 +871,10 @@ def _planes(name, count, align, boards, tracked, dtype, out, orient, extra=None)
         _planes_out(out, (B, count, N, N), dtype, align)
     if orient is not None:
         _orient_arg(orient, B)
+    if area is not None:
+        if area.side is not None:
+            _side_arg(area.side, B)
+        _counts_arg(area.counts, B)
     if tracked:
         box, st = None, boards
         _planes_out(out, (B, count, N, N), dtype, align, st.device if st.is_cuda else None)
@@ -847,10 +885,19 @@ def _planes(name, count, align, boards, tracked, dtype, out, orient, extra=None)
         st = box.t
         _planes_out(out, (B, count, N, N), dtype, align, st.device)
     planes = out if out is not None else torch.empty((B, count, N, N), dtype=dtype, device=st.device)
-    bytes_ = torch.empty(B, dtype=_U8, device=st.device) if extra else None
+    if area is not None and isinstance(area.counts, torch.Tensor):   # (checked by _counts_arg: the caller's buffer)
+        if area.counts.device != st.device:
+            raise ValueError('counts must live on the states\' device (got %s)' % (area.counts.device,))
+        bytes_ = area.counts
+    else:
+        bytes_ = (torch.empty(B, dtype=_U8, device=st.device) if area is None else
+                  torch.empty((B, 2), dtype=_I32, device=st.device)) if extra else None
     o = None if orient is None else _actions_tensor(orient, B, st.device)
-    _plane_launch(name, st, o, planes, False if extra is None else _NO_BYTES if extra is _NO_BYTES else bytes_, code, B, N,
-                  _lib.stream_ptr(st.device))
+    if area is not None:
+        how = _AreaExtra(None if area.side is None else _side_tensor(area.side, B, st.device), bytes_)
+    else:
+        how = False if extra is None else _NO_BYTES if extra is _NO_BYTES else bytes_
+    _plane_launch(name, st, o, planes, how, code, B, N, _lib.stream_ptr(st.device))
     if box is not None:
         planes, bytes_ = _back(box, planes), _back(box, bytes_)
     return (planes, bytes_) if extra else planes
@@ -1032,6 +1079,67 @@ def move_counts(state):
     """batch_move_counts of one state [6, N, N] -> uint8 [3, N, N]."""
     box = _Box(state)
     return _back(box, batch_move_counts(box.t[None]), row0=True)
+
+
+# ---------------------------------------------------------------- area ownership planes, ownership and score targets
+AREA_PLANES = 3   # gg_area_planes() of include/gymgo_amd_area.h
+AREA_NAMES = ('own_area', 'opp_area', 'neutral')
+
+
+def batch_area_planes(batch_states, dtype=torch.uint8, out=None, orient=None, side=None, counts=False):
+    """Area ownership planes of every board -> [B, 3, N, N] of `dtype` (gg_batch_area), each value exactly 0 or 1
+    (AREA_NAMES): the points Tromp-Taylor scoring (`areas`) counts for each side, and those it counts for neither.  E = the
+    empty points; a colour REACHES the empty points connected through E to an empty point next to one of its stones:
+       0  own_area   own stones, and the empty points only the own colour reaches
+       1  opp_area   the opponent's stones, and the empty points only the opponent reaches
+       2  neutral    the other empty points: their region touches both colours, or neither (a board without stones)
+    The three planes partition the board.  Exact; only planes 0, 1 and 2 of the states are read, so an ended game gets its
+    planes like any other.  side (None: "own" = the player to move, as in every other plane family; or B flags, a tensor or
+    an array): side[b] == 0 is black's view of board b, non-zero white's, whatever its turn plane says - what a training
+    target needs, where a game's final position is seen by the mover of a sampled one.  counts=True: -> (planes, int32
+    [B, 2]): the number of points in plane 0 and in plane 1; with side all 0 that is batch_areas.  (counts may also be a
+    contiguous int32 [B, 2] device tensor to write into.)  dtype: torch.uint8, float16, bfloat16 or float32 (ValueError
+    otherwise).  out: a contiguous device tensor of that shape and dtype to write into.  orient (None, or int [B], only
+    orient & 7 is read): row b is view orient[b] of its planes - also the planes of the turned position; the counts do not
+    turn.  NumPy in gives NumPy out (through the device; not for bfloat16).  One launch either way; device memory of the
+    result: 3 * B * N^2 elements (+ 8 B bytes)."""
+    return _planes('gg_batch_area', AREA_PLANES, 1, batch_states, False, dtype, out, orient, _AreaExtra(side, counts))
+
+
+def area_planes(state, dtype=torch.uint8, side=None, counts=False):
+    """batch_area_planes of one state [6, N, N] -> [3, N, N] (with counts=True: and int32 [2]); side: None or one flag."""
+    return _plane_single(batch_area_planes, state, dtype, side=None if side is None else [side], counts=bool(counts))
+
+
+def batch_area_planes_tracked(tracked, dtype=torch.uint8, out=None, orient=None, side=None, counts=False):
+    """batch_area_planes of tracked boards (int32 [B, 5N+1], a device tensor) -> [B, 3, N, N] of `dtype`
+    (gg_batch_area_tracked): bit for bit what batch_area_planes gives for batch_untrack(tracked); only the two stone row
+    sets and the turn flag are read."""
+    return _planes('gg_batch_area_tracked', AREA_PLANES, 1, tracked, True, dtype, out, orient, _AreaExtra(side, counts))
+
+
+def batch_ownership(batch_states, side=None, orient=None):
+    """Who owns every point under Tromp-Taylor scoring, and by how much that side leads -> (owner int8 [B, N, N], margin int32
+    [B]): owner = +1 on the points of batch_area_planes' plane 0, -1 on those of plane 1, 0 on neutral points; margin = the
+    number of +1 minus the number of -1 (no komi).  side, orient: as batch_area_planes - side=None is the view of the player
+    to move, orient turns owner and leaves margin.  One launch (gg_batch_area, byte planes and counts) plus a subtraction
+    each; NumPy in gives NumPy out."""
+    B, _ = _states_shape(batch_states)   # (every ValueError before a device is touched)
+    if orient is not None:
+        _orient_arg(orient, B)
+    if side is not None:
+        _side_arg(side, B)
+    box = _Box(batch_states)
+    planes, counts = batch_area_planes(box.t, torch.uint8, orient=orient, side=side, counts=True)
+    owner = planes[:, 0].to(torch.int8) - planes[:, 1].to(torch.int8)
+    return _back(box, owner), _back(box, counts[:, 0] - counts[:, 1])
+
+
+def ownership(state, side=None):
+    """batch_ownership of one state [6, N, N] -> (owner int8 [N, N], margin: an int32 scalar); side: None or one flag."""
+    box = _Box(state)
+    owner, margin = batch_ownership(box.t[None], None if side is None else [side])
+    return _back(box, owner, row0=True), _back(box, margin, row0=True)
 
 
 # ---------------------------------------------------------------- position hashes and positional superko
@@ -1760,6 +1868,12 @@ class PuctSearch:
     (gg_batch_move_planes_tracked), in the orientation of `search.orient` with symmetry=.  One launch more per select();
     nothing else changes.
 
+    area (False = everything above, launch for launch; True needs features=, ValueError otherwise): select() returns the
+    area ownership planes [R, 3, N, N] ([R * L, ..]) of the feature dtype as its LAST element, after the life, ladder and
+    move-outcome planes when those are on - batch_area_planes of the leaves from the mover's view, from the tracked leaf boards
+    (gg_batch_area_tracked), in the orientation of `search.orient` with symmetry=.  One launch more per select(); nothing
+    else changes.
+
     superko (None = everything above, every allocation and launch as without it; or a PositionHistory of the R games with
     the current roots included; anything else raises _history_arg's ValueError): positional superko AT EVERY NODE below the
     root (gg_puct_superko).  At node y a board move is illegal if it recreates - by its 64-bit hash - a valid entry of the
@@ -1777,7 +1891,7 @@ class PuctSearch:
     entry: give the PositionHistory the capacity of the whole game.  One launch more per select(), one per advance()."""
 
     def __init__(self, batch_states, iterations, c=1.25, komi=0.0, leaves=None, capacity=None, features=None, symmetry=None,
-                 first_root=0, life=False, ladder=False, outcome=False, superko=None):
+                 first_root=0, life=False, ladder=False, outcome=False, superko=None, area=False):
         self._feat = None if features is None else (features, _feature_dtype(features))
         if superko is not None:   # (before a device is touched)
             shape = np.shape(batch_states.t if isinstance(batch_states, _Box) else batch_states)
@@ -1786,9 +1900,11 @@ class PuctSearch:
         _puct_life_guard(life, features)
         _puct_ladder_guard(ladder, features)
         _puct_outcome_guard(outcome, features)
+        _puct_area_guard(area, features)
         self._life = bool(life)
         self._ladder = bool(ladder)
         self._outcome = bool(outcome)
+        self._area = bool(area)
         self._sym = None if symmetry is None else int(symmetry)
         self._first_root = int(first_root)
         self.orient = None
@@ -1832,6 +1948,8 @@ class PuctSearch:
             self._ladder_planes = torch.empty((B, LADDER_PLANES, N, N), dtype=self._feat[0], device=dev)
         if self._outcome:
             self._outcome_planes = torch.empty((B, MOVE_PLANES, N, N), dtype=self._feat[0], device=dev)
+        if self._area:
+            self._area_planes = torch.empty((B, AREA_PLANES, N, N), dtype=self._feat[0], device=dev)
         self.live = torch.full((R, self._L or 1), self._L is None, dtype=torch.bool, device=dev)   # (one leaf: always live)
         self._done, self._pending = 0, False
         self._init_symmetry(B)
@@ -1891,7 +2009,8 @@ class PuctSearch:
         """Step 1 and 2 of the next iteration -> (states uint8 [R, 6, N, N], legal bool [R, A]) of the R leaves ([R * L, ..]
         with leaves=L); with features=dtype (planes [R, 16, N, N] of that dtype, legal); with life=True (planes, legal, life
         [R, 4, N, N] of that dtype); with ladder=True the ladder planes [R, 4, N, N] of that dtype after those; with
-        outcome=True the move-outcome planes [R, 12, N, N] of that dtype as the last element."""
+        outcome=True the move-outcome planes [R, 12, N, N] of that dtype after those; with area=True the area planes
+        [R, 3, N, N] of that dtype as the last element."""
         if self._pending:
             raise ValueError('PuctSearch.select(): the leaves of the last select() have not been backed up')
         if self._done >= self._I:
@@ -1923,11 +2042,14 @@ class PuctSearch:
                 _plane_launch('gg_batch_ladder_tracked', lp, op, self._ladder_planes, None, self._feat[1], B, N, stream)
             if self._outcome:
                 _plane_launch('gg_batch_move_planes_tracked', lp, op, self._outcome_planes, _NO_BYTES, self._feat[1], B, N, stream)
+            if self._area:
+                _plane_launch('gg_batch_area_tracked', lp, op, self._area_planes, _AreaExtra(None, None), self._feat[1], B, N, stream)
         self._pending = True
         legal = self._legal if self._sym is None else self._legal_view
         res = (self._states, legal, self._life_planes) if self._life else (self._states, legal)
         res = res + (self._ladder_planes,) if self._ladder else res
-        return res + (self._outcome_planes,) if self._outcome else res
+        res = res + (self._outcome_planes,) if self._outcome else res
+        return res + (self._area_planes,) if self._area else res
 
     def backup(self, priors, values):
         """Step 4: priors float32 [R, A] and values float32 [R] (the value for the player to move at the leaf) of the leaves
@@ -2164,7 +2286,7 @@ class PuctSearch:
 
 
 def batch_puct(batch_states, iterations, evaluator, c=1.25, komi=0.0, tree=False, leaves=None, capacity=None, features=None,
-               symmetry=None, first_root=0, life=False, ladder=False, outcome=False, superko=None):
+               symmetry=None, first_root=0, life=False, ladder=False, outcome=False, superko=None, area=False):
     """PUCT search (the AlphaZero search) of `iterations` iterations from every root of batch_states ([R, 6, N, N]) with the
     caller's evaluator -> Puct (device tensors for a device tensor, NumPy arrays for NumPy input).  The loop over PuctSearch.
 
@@ -2234,14 +2356,19 @@ def batch_puct(batch_states, iterations, evaluator, c=1.25, komi=0.0, tree=False
     superko (None: the search above, launch for launch; or a PositionHistory of the R games, batch_states' own positions
     included): the search of one position of a recorded game under positional superko - PuctSearch.forbid_repeats once before
     round 0 for the roots, and gg_puct_superko in every round for the nodes below them (PuctSearch): no node of the tree
-    reached by a board move has the position of one of its ancestors or of the history.  result().legal is the reduced set."""
+    reached by a board move has the position of one of its ancestors or of the history.  result().legal is the reduced set.
+
+    area (False: the search above, launch for launch; True, with features=): the evaluator gets as its LAST argument, after
+    life, ladder and outcome when those are on, the area ownership planes [R, 3, N, N] ([R * L, ..]) of the feature dtype -
+    batch_area_planes of the leaves, in the leaf's orientation with symmetry= (PuctSearch)."""
     _puct_komi_guard(evaluator, komi)
     _puct_features_guard(evaluator, features)
     _puct_life_guard(life, features)
     _puct_ladder_guard(ladder, features)
     _puct_outcome_guard(outcome, features)
+    _puct_area_guard(area, features)
     search = PuctSearch(batch_states, iterations, c, komi, leaves=leaves, capacity=capacity, features=features, symmetry=symmetry,
-                        first_root=first_root, life=life, ladder=ladder, outcome=outcome, superko=superko)
+                        first_root=first_root, life=life, ladder=ladder, outcome=outcome, superko=superko, area=area)
     if superko is not None:
         search.forbid_repeats()
     for _ in range(search._I):
@@ -2276,6 +2403,11 @@ def _puct_outcome_guard(outcome, features):
         raise ValueError('outcome=True hands out the move-outcome planes in the dtype of features=: give features= too')
 
 
+def _puct_area_guard(area, features):
+    if area and features is None:   # (before a device is touched)
+        raise ValueError('area=True hands out the area planes in the dtype of features=: give features= too')
+
+
 def _puct_superko_guard(superko):
     if superko is not False and superko is not True and not (type(superko) is type('') and superko == 'tree'):   # (before a device is touched)
         raise ValueError("superko must be False, True (the roots) or 'tree' (every node) (got %r)" % (superko,))
@@ -2298,7 +2430,7 @@ def _puct_features_guard(evaluator, features):
 
 
 def puct_play(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, leaves=None, capacity=None, reuse=True, features=None,
-              symmetry=None, first_root=0, life=False, ladder=False, outcome=False, superko=False):
+              symmetry=None, first_root=0, life=False, ladder=False, outcome=False, superko=False, area=False):
     """Play `moves` moves from every root of batch_states ([R, 6, N, N]) with a PUCT search per move -> (actions int64
     [R, moves], the final states uint8 [R, 6, N, N]); device tensors for a device tensor, NumPy arrays for NumPy input.
     Per move: `iterations` rounds of PuctSearch (batch_puct's loop, with `leaves` and `capacity` as there), the move of
@@ -2325,13 +2457,15 @@ def puct_play(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, leav
     hashes are pushed after each move, so no move played recreates an earlier position of its game.  With True the
     repetitions inside the tree below the root are not checked: the search still plans with them.  superko='tree': the loop of
     True with the history also handed to the search (PuctSearch(superko=)), with reuse=False to the new search of every move
-    too: the rule holds at every node.  Any other value raises ValueError."""
+    too: the rule holds at every node.  Any other value raises ValueError.  area: as batch_puct - the area ownership planes as
+    the evaluator's last argument."""
     _puct_superko_guard(superko)
     _puct_komi_guard(evaluator, komi)
     _puct_features_guard(evaluator, features)
     _puct_life_guard(life, features)
     _puct_ladder_guard(ladder, features)
     _puct_outcome_guard(outcome, features)
+    _puct_area_guard(area, features)
     moves = int(moves)
     if moves < 0:
         raise ValueError('need moves >= 0 (got %d)' % moves)
@@ -2341,7 +2475,7 @@ def puct_play(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, leav
         batch_states = batch_states if isinstance(batch_states, _Box) else _Box(batch_states)
         deep = _puct_superko_history(superko, batch_states, moves)
     search = PuctSearch(batch_states, iterations, c, komi, leaves=leaves, capacity=capacity, features=features, symmetry=symmetry,
-                        first_root=first_root, life=life, ladder=ladder, outcome=outcome, superko=deep)
+                        first_root=first_root, life=life, ladder=ladder, outcome=outcome, superko=deep, area=area)
     box = search._box
     played = torch.empty((search._R, moves), dtype=_I64, device=box.t.device)
     seen = None
@@ -2361,7 +2495,7 @@ def puct_play(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, leav
             box.t = search._played_states(played[:, mv])
             search = PuctSearch(box, iterations, c, komi, leaves=leaves, capacity=capacity, features=features,
                                 symmetry=None if symmetry is None else int(symmetry) + mv + 1, first_root=first_root, life=life,
-                                ladder=ladder, outcome=outcome, superko=deep)
+                                ladder=ladder, outcome=outcome, superko=deep, area=area)
         if seen is not None:
             seen.push(search._root_hashes())
     return _back(box, played), box.back(search._root_states())
@@ -2399,7 +2533,7 @@ that ended, 0 for one still running), lengths (int32 [R]: moves played), final_s
 
 def puct_selfplay(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, leaves=None, capacity=None, noise=None,
                   eps=0.25, sample_moves=0, seed=20260927, first_game=0, record_states=False, features=None, symmetry=None,
-                  life=False, ladder=False, outcome=False, superko=False):
+                  life=False, ladder=False, outcome=False, superko=False, area=False):
     """Self-play games for training: `moves` moves from every root of batch_states ([R, 6, N, N]) with a PUCT search per move
     on the kept tree -> SelfPlay (device tensors for a device tensor, NumPy arrays for NumPy input).  puct_play's
     reuse=True loop (`iterations` rounds per move with `leaves` and `capacity` as there, then PuctSearch.advance) with
@@ -2433,13 +2567,16 @@ def puct_selfplay(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, 
     recreates an earlier position of its own, so games that would cycle until `moves` cuts them off with outcome 0 come to
     an end.  With True the repetitions inside the tree below the root are not checked, and the visit counts recorded as pi
     include plans through them; superko='tree' is the loop of True with the history also handed to the search
-    (PuctSearch(superko=)): the rule holds at every node.  Any other value raises ValueError."""
+    (PuctSearch(superko=)): the rule holds at every node.  Any other value raises ValueError.  area: as batch_puct - the area
+    ownership planes as the evaluator's last argument; the records do not change (selfplay_batch makes the ownership and
+    score targets from them)."""
     _puct_superko_guard(superko)
     _puct_komi_guard(evaluator, komi)
     _puct_features_guard(evaluator, features)
     _puct_life_guard(life, features)
     _puct_ladder_guard(ladder, features)
     _puct_outcome_guard(outcome, features)
+    _puct_area_guard(area, features)
     moves, sample_moves, eps = int(moves), int(sample_moves), float(eps)
     if moves < 0:
         raise ValueError('need moves >= 0 (got %d)' % moves)
@@ -2468,7 +2605,7 @@ def puct_selfplay(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, 
         return _back(box, SelfPlay(played, pis, vals, won, lengths, st, before))
     deep = _puct_superko_history(superko, box, moves)
     search = PuctSearch(box, I, c, komi, leaves=leaves, capacity=capacity, features=features, symmetry=symmetry, first_root=first_game,
-                        life=life, ladder=ladder, outcome=outcome, superko=deep)
+                        life=life, ladder=ladder, outcome=outcome, superko=deep, area=area)
     rng = rng_seed(R, seed, first_game, device=dev)
     ones, todo = torch.ones(R, dtype=_U8, device=dev), torch.empty(R, dtype=_U8, device=dev)
     seen = (deep or PositionHistory(R, moves + 1, dev)).push(search._root_hashes()) if superko else None
@@ -2507,6 +2644,7 @@ def puct(state, iterations, evaluator, **kw):
     _puct_life_guard(kw.get('life', False), kw.get('features'))
     _puct_ladder_guard(kw.get('ladder', False), kw.get('features'))
     _puct_outcome_guard(kw.get('outcome', False), kw.get('features'))
+    _puct_area_guard(kw.get('area', False), kw.get('features'))
     return _single(batch_puct, state, iterations, evaluator, **kw)
 
 
@@ -2517,6 +2655,7 @@ def puct_actions(batch_states, iterations, evaluator, **kw):
     _puct_life_guard(kw.get('life', False), kw.get('features'))
     _puct_ladder_guard(kw.get('ladder', False), kw.get('features'))
     _puct_outcome_guard(kw.get('outcome', False), kw.get('features'))
+    _puct_area_guard(kw.get('area', False), kw.get('features'))
     box = _Box(batch_states)
     res = batch_puct(box.t, iterations, evaluator, **kw)
     return _best_legal(box, res.legal, res.visits.to(_I64))
@@ -2774,7 +2913,8 @@ def selfplay_targets(record, games, moves):
     return torch.where(white, -outcome, outcome), m < t(record.lengths, dev)[g].to(_I64)
 
 
-def selfplay_batch(record, games, moves, orient, dtype=torch.float16, life=False, ladder=False, outcome=False):
+def selfplay_batch(record, games, moves, orient, dtype=torch.float16, life=False, ladder=False, outcome=False, area=False,
+                   ownership=False):
     """Training samples from a self-play record, in one of the eight orientations each -> (planes [B, 16, N, N] of `dtype`,
     pi [B, A] float32, z float32 [B], valid bool [B]).  record: a SelfPlay of puct_selfplay(.., record_states=True)
     (ValueError if record.states is None); games, moves, orient: int [B] - sample i is the position before move moves[i] of
@@ -2785,7 +2925,14 @@ def selfplay_batch(record, games, moves, orient, dtype=torch.float16, life=False
     recorded positions in view orient and dtype `dtype` (batch_life, one launch more).  ladder=True: as the last element the
     ladder planes [B, 4, N, N] of the recorded positions in view orient and dtype `dtype` (batch_ladder, one launch more).
     outcome=True: as the last element, after those, the move-outcome planes [B, 12, N, N] of the recorded positions in view
-    orient and dtype `dtype` (batch_move_planes, one launch more)."""
+    orient and dtype `dtype` (batch_move_planes, one launch more).  area=True: as the last element, after those, the area
+    ownership planes [B, 3, N, N] of the recorded positions in view orient and dtype `dtype`, from the mover's view
+    (batch_area_planes, one launch more).  ownership=True: two more elements after everything else, the KataGo-style
+    targets owner int8 [B, N, N] and margin float32 [B] - batch_ownership of record.final_states[games] in view orient with
+    side = the turn of the SAMPLED position (plane 2 of record.states[games, moves]): +1 = "ends up mine" for the player to
+    move in the sample, margin = that player's area minus the other's at the end of the game (one launch more).  Komi is not
+    in the record: subtract it from margin on black's samples and add it on white's.  For a game that had not ended after
+    the recorded moves the final position is just the last one: `valid` and record.outcome == 0 tell."""
     _feature_dtype(dtype)
     z, valid = selfplay_targets(record, games, moves)
     is_np = not isinstance(record.states, torch.Tensor)
@@ -2806,4 +2953,9 @@ def selfplay_batch(record, games, moves, orient, dtype=torch.float16, life=False
         res += (batch_ladder(positions, dtype, orient=orient),)
     if outcome:
         res += (batch_move_planes(positions, dtype, orient=orient),)
+    if area:
+        res += (batch_area_planes(positions, dtype, orient=orient),)
+    if ownership:
+        owner, margin = batch_ownership(t(record.final_states)[g], side=positions[:, govars.TURN_CHNL, 0, 0] != 0, orient=orient)
+        res += (owner, margin.to(torch.float32))
     return tuple(x.cpu().numpy() for x in res) if is_np else res
