@@ -1146,6 +1146,218 @@ def ownership(state, side=None):
 HASH_SEED = 0x676F2D6861736821   # GG_HASH_SEED of include/gymgo_amd.h
 
 
+# ---------------------------------------------------------------- history input planes: past positions and recent moves
+PAST_MAX_POSITIONS = 8   # GG_PAST_MAX_POSITIONS of include/gymgo_amd_past.h
+
+
+def _past_shape(positions, moves):
+    """(T, moves as 0 / 1) of a plane request; ValueError outside gg_past_planes' domain (before a device is touched)."""
+    if (isinstance(positions, bool) or not isinstance(positions, (int, np.integer))
+            or not 1 <= int(positions) <= PAST_MAX_POSITIONS):
+        raise ValueError('positions must be an integer in 1..%d (got %r)' % (PAST_MAX_POSITIONS, positions))
+    if not isinstance(moves, (bool, np.bool_)) and not (isinstance(moves, (int, np.integer)) and moves in (0, 1)):
+        raise ValueError('moves must be a flag (got %r)' % (moves,))
+    return int(positions), int(bool(moves))
+
+
+def past_plane_count(positions=8, moves=False):
+    """The planes per board of a history request (gg_past_planes): 2 T, plus T - 1 with moves - 23 at the most."""
+    T, mv = _past_shape(positions, moves)
+    return 2 * T + (T - 1 if mv else 0)
+
+
+class StoneHistory:
+    """The earlier positions of a batch of games, on the device: what the history planes (batch_past_planes, PuctSearch(past=))
+    read beside the current position.  positions = T (1 .. PAST_MAX_POSITIONS): position 0 is the current one, position t the
+    one t plies ago; moves: whether the T - 1 "stone played t plies ago" planes are wanted too; planes = 2 T + (T - 1 if moves
+    else 0).  rows: int32 [B, capacity, 2, N] - per entry the N black rows, then the N white rows, as bit masks, bit c = column
+    c, as in tracked boards; count: int32 [B], the pushes per board.  A RING like PositionHistory: push writes at
+    count % capacity, the position t >= 1 plies ago is entry (count - t) mod capacity and exists iff
+    t <= min(max(count, 0), capacity).  capacity: default and minimum max(T - 1, 1).
+    The ring holds the positions strictly BEFORE the current one: push a position before you play on it, one push per ply,
+    passes included.  push / push_tracked are one launch each (gg_past_push[_tracked]), reset is plain torch; nothing reads
+    back or synchronises.  device: None = the current ROCm device."""
+
+    def __init__(self, batch_size, board_size, positions=8, moves=False, capacity=None, device=None):
+        T, mv = _past_shape(positions, moves)
+        batch_size, board_size = int(batch_size), int(board_size)
+        if batch_size < 0 or not 2 <= board_size <= 19:
+            raise ValueError('need batch_size >= 0 and 2 <= board_size <= 19 (got %d, %d)' % (batch_size, board_size))
+        least = max(T - 1, 1)
+        if capacity is None:
+            capacity = least
+        if isinstance(capacity, bool) or not isinstance(capacity, (int, np.integer)) or capacity < least:
+            raise ValueError('capacity must be an integer >= max(positions - 1, 1) = %d (got %r)' % (least, capacity))
+        dev = _device() if device is None else device
+        self.positions, self.moves, self.capacity, self.board_size = T, bool(mv), int(capacity), board_size
+        self.planes = 2 * T + (T - 1 if mv else 0)
+        self.rows = torch.zeros((batch_size, self.capacity, 2, board_size), dtype=_I32, device=dev)
+        self.count = torch.zeros(batch_size, dtype=_I32, device=dev)
+
+    def _mask(self, mask):
+        """mask as uint8 / bool [B] on the ring's device, or None; ValueError first."""
+        if mask is None:
+            return None
+        B = self.count.shape[0]
+        if not isinstance(mask, torch.Tensor):
+            mask = np.asarray(mask)
+            ok = mask.dtype in (np.bool_, np.uint8)
+        else:
+            ok = mask.dtype in (torch.bool, _U8)
+        if not ok or tuple(mask.shape) != (B,):
+            raise ValueError('mask must be bool or uint8 [%d] (got %s %s)' % (B, mask.dtype, tuple(mask.shape)))
+        if not isinstance(mask, torch.Tensor):
+            mask = torch.from_numpy(np.ascontiguousarray(mask))
+        return mask.to(self.count.device).contiguous()
+
+    def _push(self, name, boards, mask):
+        B, N = self.count.shape[0], self.board_size
+        if B:
+            _lib.call(name, boards, mask, self.rows, self.count, self.capacity, B, N, _lib.stream_ptr(self.count.device))
+        return self
+
+    def push(self, batch_states, mask=None):
+        """The positions batch_states ([B, 6, N, N], a device tensor or an array: their stones) enter the rings of the
+        boards where mask (None = all; bool or uint8 [B]) is set - written at count % capacity, count + 1; a masked-out
+        board keeps every byte.  One launch (gg_past_push).  -> self."""
+        if _states_shape(batch_states) != (self.count.shape[0], self.board_size):
+            raise ValueError('batch_states must be [%d, 6, %d, %d] (got %s)' % (self.count.shape[0], self.board_size, self.board_size,
+                                                                               tuple(np.shape(batch_states))))
+        mask = self._mask(mask)
+        st = _Box(batch_states).t
+        if st.device != self.count.device:
+            raise ValueError('batch_states must live on the history\'s device (%s)' % (self.count.device,))
+        return self._push('gg_past_push', st, mask)
+
+    def push_tracked(self, tracked, mask=None):
+        """push of tracked boards (int32 [B, 5N+1], a device tensor): gg_past_push_tracked.  -> self."""
+        if (not isinstance(tracked, torch.Tensor) or tracked.dim() != 2 or tracked.shape[0] != self.count.shape[0]
+                or _tracked_size(tracked) != self.board_size):
+            raise ValueError('tracked must be int32 [%d, %d]' % (self.count.shape[0], tracked_words(self.board_size)))
+        mask = self._mask(mask)
+        if tracked.device != self.count.device:
+            raise ValueError('tracked must live on the history\'s device (%s)' % (self.count.device,))
+        return self._push('gg_past_push_tracked', tracked, mask)
+
+    def reset(self, mask=None):
+        """Forget everything about the boards where mask (None = all) is set: entries and count zero.  -> self."""
+        mask = self._mask(mask)
+        if mask is None:
+            self.rows.zero_()
+            self.count.zero_()
+        else:
+            self.rows.masked_fill_(mask.bool()[:, None, None, None], 0)
+            self.count.masked_fill_(mask.bool(), 0)
+        return self
+
+
+def _past_arg(history, B, N, what='history'):
+    """ValueError unless history is a StoneHistory of B boards of size N (sizes None: not checked) whose tensors have the
+    shapes its numbers say - before a device is touched."""
+    if not isinstance(history, StoneHistory):
+        raise ValueError('%s must be a StoneHistory (got %r)' % (what, type(history)))
+    rows, count = history.rows, history.count
+    _past_shape(history.positions, history.moves)
+    if (not isinstance(rows, torch.Tensor) or not isinstance(count, torch.Tensor) or rows.dtype != _I32 or count.dtype != _I32
+            or rows.dim() != 4 or tuple(rows.shape) != (count.shape[0], history.capacity, 2, history.board_size)
+            or tuple(count.shape) != (rows.shape[0],) or not rows.is_contiguous() or not count.is_contiguous()
+            or history.capacity < 1 or (B is not None and rows.shape[0] != B) or (N is not None and history.board_size != N)):
+        raise ValueError('%s must be a StoneHistory of %s boards of size %s: rows int32 [B, H, 2, N], count int32 [B]' % (what, B, N))
+    return history
+
+
+def _past_planes(name, boards, tracked, history, dtype, out, orient):
+    """The body of batch_past_planes[_tracked]: _planes' checks in its order, then one launch with the ring's pointers."""
+    code = _feature_dtype(dtype)
+    B, N = _hash_shape(boards, tracked)
+    _past_arg(history, B, N)
+    count = history.planes
+    if not tracked:
+        _planes_out(out, (B, count, N, N), dtype, 1)
+    if orient is not None:
+        _orient_arg(orient, B)
+    if tracked:
+        box, st = None, boards
+        _planes_out(out, (B, count, N, N), dtype, 1, st.device if st.is_cuda else None)
+    else:
+        if not isinstance(boards, torch.Tensor) and dtype == torch.bfloat16:
+            raise ValueError('NumPy has no bfloat16: pass a device tensor, or another dtype')
+        box = _Box(boards)
+        st = box.t
+        _planes_out(out, (B, count, N, N), dtype, 1, st.device)
+    if history.rows.device != st.device:
+        raise ValueError('history must live on the boards\' device (%s)' % (st.device,))
+    planes = out if out is not None else torch.empty((B, count, N, N), dtype=dtype, device=st.device)
+    o = None if orient is None else _actions_tensor(orient, B, st.device)
+    _lib.call(name, st, history.rows, history.count, history.capacity, history.positions, int(history.moves), o, planes, code, B, N,
+              _lib.stream_ptr(st.device))
+    return planes if box is None else _back(box, planes)
+
+
+def batch_past_planes(batch_states, history, dtype=torch.uint8, out=None, orient=None):
+    """History input planes of every board -> [B, history.planes, N, N] of `dtype` (gg_batch_past), each value exactly 0 or 1.
+    batch_states are the CURRENT positions, history (a StoneHistory of the B games) the positions before them; T and moves
+    are the history's.  From the view of the player to move NOW:
+       2 t      (t = 0 .. T-1)   own stones at position t (t plies ago; 0 = now)
+       2 t + 1                   the opponent's stones at position t
+       2 T + t  (t = 0 .. T-2)   with moves: the point of the move played t plies ago - the points occupied at position t and
+                                 empty at position t + 1 -, nothing for a pass or where position t + 1 does not exist
+    A position that does not exist (the game is younger, or the ring shorter) gives empty planes: AlphaGo Zero's convention.
+    T = 8 without moves plus batch_features' plane 13 is AlphaGo Zero's input; the move planes are KataGo's recent moves.
+    dtype, out (aligned to its element), orient (every position of a board is turned alike) and NumPy in / NumPy out: as
+    batch_area_planes.  One launch; nothing synchronises."""
+    return _past_planes('gg_batch_past', batch_states, False, history, dtype, out, orient)
+
+
+def batch_past_planes_tracked(tracked, history, dtype=torch.uint8, out=None, orient=None):
+    """batch_past_planes of tracked boards (int32 [B, 5N+1], a device tensor): gg_batch_past_tracked, bit for bit what
+    batch_past_planes gives for batch_untrack(tracked)."""
+    return _past_planes('gg_batch_past_tracked', tracked, True, history, dtype, out, orient)
+
+
+def past_planes(states, positions=8, moves=False, dtype=torch.uint8):
+    """The history planes of ONE game given as its positions [K, 6, N, N], oldest first (K >= 1) -> [planes, N, N] of the last
+    position: a StoneHistory of one board filled with the T - 1 positions before it, then batch_past_planes."""
+    T, mv = _past_shape(positions, moves)
+    _feature_dtype(dtype)
+    K, N = _states_shape(states, 'states')
+    if K < 1:
+        raise ValueError('states must hold at least one position')
+    if not isinstance(states, torch.Tensor) and dtype == torch.bfloat16:
+        raise ValueError('NumPy has no bfloat16: pass a device tensor, or another dtype')
+    box = _Box(states)
+    hist = StoneHistory(1, N, T, mv, device=box.t.device)
+    for k in range(max(0, K - T), K - 1):
+        hist.push(box.t[k:k + 1])
+    return _back(box, batch_past_planes(box.t[K - 1:K], hist, dtype), row0=True)
+
+
+def _puct_past_guard(past, features):
+    if past is not None and features is None:   # (before a device is touched)
+        raise ValueError('past= hands out the history planes in the dtype of features=: give features= too')
+
+
+def _puct_past_history(past, box):
+    """past= of a move loop -> its StoneHistory (or None): an int T or a pair (T, moves) makes an empty one for the roots of
+    box, made before the search that keeps it; a StoneHistory is used as given (PuctSearch checks it)."""
+    if past is None or isinstance(past, StoneHistory):
+        return past
+    T, mv = _past_request(past)
+    st = box.t
+    if st.dim() != 4 or st.shape[2] != st.shape[3]:
+        raise ValueError('batch_states must be [R, 6, N, N] (got %s)' % (tuple(st.shape),))
+    return StoneHistory(st.shape[0], st.shape[2], T, mv, device=st.device)
+
+
+def _past_request(past):
+    """(T, moves) of past= given as an int T or a pair (T, moves); ValueError otherwise (before a device is touched)."""
+    if isinstance(past, tuple) and len(past) == 2:
+        return _past_shape(*past)
+    if isinstance(past, bool) or not isinstance(past, (int, np.integer)):
+        raise ValueError('past must be an integer T, a pair (T, moves) or a StoneHistory (got %r)' % (past,))
+    return _past_shape(past, False)
+
+
 def zobrist_keys():
     """The key table of the position hashes -> NumPy int64 [2, 19, 19]: keys[c, y, x] for a black (c = 0) / white (c = 1) stone
     at row y, column x - output number c * 361 + y * 19 + x + 1 of splitmix64 started at HASH_SEED, whatever the board size
@@ -1874,6 +2086,15 @@ class PuctSearch:
     (gg_batch_area_tracked), in the orientation of `search.orient` with symmetry=.  One launch more per select(); nothing
     else changes.
 
+    past (None = everything above, launch for launch; or a StoneHistory of the R games holding the positions BEFORE the roots;
+    needs features=, ValueError otherwise): select() returns the history planes [R, past.planes, N, N] ([R * L, ..]) of the
+    feature dtype as its LAST element, after the life, ladder, move-outcome and area planes when those are on -
+    batch_past_planes of the leaves with their true past (gg_puct_past): one ply back is the leaf's parent node, further back
+    its ancestors' boards in the tree, beyond node 0 the history's ring - in the orientation of `search.orient` with
+    symmetry=.  One launch more per select().  advance() pushes node 0's board into the history for every root whose action
+    is not -1, before the tree is renumbered, so the history follows the game; the search keeps the object and reads its
+    tensors at launch time.
+
     superko (None = everything above, every allocation and launch as without it; or a PositionHistory of the R games with
     the current roots included; anything else raises _history_arg's ValueError): positional superko AT EVERY NODE below the
     root (gg_puct_superko).  At node y a board move is illegal if it recreates - by its 64-bit hash - a valid entry of the
@@ -1891,11 +2112,15 @@ class PuctSearch:
     entry: give the PositionHistory the capacity of the whole game.  One launch more per select(), one per advance()."""
 
     def __init__(self, batch_states, iterations, c=1.25, komi=0.0, leaves=None, capacity=None, features=None, symmetry=None,
-                 first_root=0, life=False, ladder=False, outcome=False, superko=None, area=False):
+                 first_root=0, life=False, ladder=False, outcome=False, superko=None, area=False, past=None):
         self._feat = None if features is None else (features, _feature_dtype(features))
         if superko is not None:   # (before a device is touched)
             shape = np.shape(batch_states.t if isinstance(batch_states, _Box) else batch_states)
             _history_arg(superko, shape[0] if shape else -1)
+        _puct_past_guard(past, features)
+        if past is not None:      # (before a device is touched)
+            shape = np.shape(batch_states.t if isinstance(batch_states, _Box) else batch_states)
+            _past_arg(past, shape[0] if shape else -1, shape[-1] if shape else -1, 'past')
         _puct_symmetry_guard(symmetry, features)
         _puct_life_guard(life, features)
         _puct_ladder_guard(ladder, features)
@@ -1905,6 +2130,7 @@ class PuctSearch:
         self._ladder = bool(ladder)
         self._outcome = bool(outcome)
         self._area = bool(area)
+        self._past = past
         self._sym = None if symmetry is None else int(symmetry)
         self._first_root = int(first_root)
         self.orient = None
@@ -1950,6 +2176,10 @@ class PuctSearch:
             self._outcome_planes = torch.empty((B, MOVE_PLANES, N, N), dtype=self._feat[0], device=dev)
         if self._area:
             self._area_planes = torch.empty((B, AREA_PLANES, N, N), dtype=self._feat[0], device=dev)
+        if past is not None:
+            if past.rows.device != dev or past.count.device != dev:
+                raise ValueError('past must be a StoneHistory of %d boards on the device of batch_states (%s)' % (R, dev))
+            self._past_planes = torch.empty((B, past.planes, N, N), dtype=self._feat[0], device=dev)
         self.live = torch.full((R, self._L or 1), self._L is None, dtype=torch.bool, device=dev)   # (one leaf: always live)
         self._done, self._pending = 0, False
         self._init_symmetry(B)
@@ -1966,6 +2196,9 @@ class PuctSearch:
         if superko is not None:
             self._ko = _lib.ptrs('gg_puct_superko', links=self._links, node_hash=self.node_hash)
             self._fill_node_hash()
+        if past is not None:   # (the history's tensors are written in place: their addresses hold)
+            self._past_ptrs = _lib.ptrs('gg_puct_past', boards=self._boards, links=self._links, rows=past.rows, count=past.count,
+                                        out=self._past_planes)
 
     def _fill_node_hash(self):
         """node_hash = the hash of every board of the boards buffer (R > 0): one launch."""
@@ -2010,7 +2243,8 @@ class PuctSearch:
         with leaves=L); with features=dtype (planes [R, 16, N, N] of that dtype, legal); with life=True (planes, legal, life
         [R, 4, N, N] of that dtype); with ladder=True the ladder planes [R, 4, N, N] of that dtype after those; with
         outcome=True the move-outcome planes [R, 12, N, N] of that dtype after those; with area=True the area planes
-        [R, 3, N, N] of that dtype as the last element."""
+        [R, 3, N, N] of that dtype after those; with past= the history planes [R, past.planes, N, N] of that dtype as the last
+        element."""
         if self._pending:
             raise ValueError('PuctSearch.select(): the leaves of the last select() have not been backed up')
         if self._done >= self._I:
@@ -2044,12 +2278,18 @@ class PuctSearch:
                 _plane_launch('gg_batch_move_planes_tracked', lp, op, self._outcome_planes, _NO_BYTES, self._feat[1], B, N, stream)
             if self._area:
                 _plane_launch('gg_batch_area_tracked', lp, op, self._area_planes, _AreaExtra(None, None), self._feat[1], B, N, stream)
+            if self._past is not None:
+                bp, kp, rp, cp, pp = self._past_ptrs
+                past = self._past
+                check(lib.gg_puct_past(R, N, self._C, self._L or 1, bp, kp, rp, cp, past.capacity, past.positions, int(past.moves),
+                                       lp, ip, op, pp, self._feat[1], stream), 'gg_puct_past')
         self._pending = True
         legal = self._legal if self._sym is None else self._legal_view
         res = (self._states, legal, self._life_planes) if self._life else (self._states, legal)
         res = res + (self._ladder_planes,) if self._ladder else res
         res = res + (self._outcome_planes,) if self._outcome else res
-        return res + (self._area_planes,) if self._area else res
+        res = res + (self._area_planes,) if self._area else res
+        return res + (self._past_planes,) if self._past is not None else res
 
     def backup(self, priors, values):
         """Step 4: priors float32 [R, A] and values float32 [R] (the value for the player to move at the leaf) of the leaves
@@ -2133,6 +2373,17 @@ class PuctSearch:
         _lib.call('gg_batch_play_moves_tracked', np_, ap, None, self._R, self._N, 1, _lib.current_raw_stream(self._dev))
         return ap, np_, rp, kp
 
+    def _push_past(self, acts):
+        """past=: node 0's boards, from the tree's boards buffer, enter the history of every root whose action (acts: int64 [R]
+        on the device; R > 0) is not -1 - the position the move is played on, pushed before it is played.  One copy, one
+        compare, one launch; nothing is read back."""
+        if self._past is None:
+            return
+        self._advance_buffers()
+        with torch.cuda.device(self._dev):
+            self._next.copy_(self._boards[:, 0, :])
+            self._past.push_tracked(self._next, acts != -1)
+
     def _played_states(self, acts):
         """-> uint8 [R, 6, N, N], a new device tensor: the roots after acts (int64 [R] on the device, -1 stays put), played on
         a copy of node 0's boards alone; the tree is not touched."""
@@ -2153,7 +2404,7 @@ class PuctSearch:
         the device that every action other than -1 is legal at its root - one synchronisation - and raises ValueError naming
         the first root where it is not; check=False does not synchronise: an illegal action then does what
         gg_batch_play_moves_tracked does with it, and its root gets a fresh tree (so does anything outside [-1, A): only -1
-        itself leaves a root alone)."""
+        itself leaves a root alone).  With past= the roots that move enter the history first (_push_past)."""
         if self._pending:
             raise ValueError('PuctSearch.advance(): the leaves of the last select() have not been backed up')
         R, N, A = self._R, self._N, self._N * self._N + 1
@@ -2173,6 +2424,7 @@ class PuctSearch:
             if bad.numel():   # (the synchronisation)
                 r = int(bad[0, 0])
                 raise ValueError('PuctSearch.advance(): action %d is not legal at root %d' % (int(acts[r]), r))
+        self._push_past(acts)
         ap, np_, rp, kp = self._play_on_roots(acts)
         _lib.call('gg_puct_advance', ap, np_, R, N, self._C, *self._tree, rp, kp, _lib.current_raw_stream(self._dev))
         if self._history is not None:
@@ -2286,7 +2538,7 @@ class PuctSearch:
 
 
 def batch_puct(batch_states, iterations, evaluator, c=1.25, komi=0.0, tree=False, leaves=None, capacity=None, features=None,
-               symmetry=None, first_root=0, life=False, ladder=False, outcome=False, superko=None, area=False):
+               symmetry=None, first_root=0, life=False, ladder=False, outcome=False, superko=None, area=False, past=None):
     """PUCT search (the AlphaZero search) of `iterations` iterations from every root of batch_states ([R, 6, N, N]) with the
     caller's evaluator -> Puct (device tensors for a device tensor, NumPy arrays for NumPy input).  The loop over PuctSearch.
 
@@ -2360,15 +2612,21 @@ def batch_puct(batch_states, iterations, evaluator, c=1.25, komi=0.0, tree=False
 
     area (False: the search above, launch for launch; True, with features=): the evaluator gets as its LAST argument, after
     life, ladder and outcome when those are on, the area ownership planes [R, 3, N, N] ([R * L, ..]) of the feature dtype -
-    batch_area_planes of the leaves, in the leaf's orientation with symmetry= (PuctSearch)."""
+    batch_area_planes of the leaves, in the leaf's orientation with symmetry= (PuctSearch).
+
+    past (None: the search above, launch for launch; or a StoneHistory of the R games holding the positions before the roots,
+    with features=): the evaluator gets as its LAST argument, after life, ladder, outcome and area when those are on, the
+    history planes [R, past.planes, N, N] ([R * L, ..]) of the feature dtype - the leaf, its ancestors in the tree and, beyond
+    node 0, the history (PuctSearch) - in the leaf's orientation with symmetry=."""
     _puct_komi_guard(evaluator, komi)
     _puct_features_guard(evaluator, features)
     _puct_life_guard(life, features)
     _puct_ladder_guard(ladder, features)
     _puct_outcome_guard(outcome, features)
     _puct_area_guard(area, features)
+    _puct_past_guard(past, features)
     search = PuctSearch(batch_states, iterations, c, komi, leaves=leaves, capacity=capacity, features=features, symmetry=symmetry,
-                        first_root=first_root, life=life, ladder=ladder, outcome=outcome, superko=superko, area=area)
+                        first_root=first_root, life=life, ladder=ladder, outcome=outcome, superko=superko, area=area, past=past)
     if superko is not None:
         search.forbid_repeats()
     for _ in range(search._I):
@@ -2430,7 +2688,7 @@ def _puct_features_guard(evaluator, features):
 
 
 def puct_play(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, leaves=None, capacity=None, reuse=True, features=None,
-              symmetry=None, first_root=0, life=False, ladder=False, outcome=False, superko=False, area=False):
+              symmetry=None, first_root=0, life=False, ladder=False, outcome=False, superko=False, area=False, past=None):
     """Play `moves` moves from every root of batch_states ([R, 6, N, N]) with a PUCT search per move -> (actions int64
     [R, moves], the final states uint8 [R, 6, N, N]); device tensors for a device tensor, NumPy arrays for NumPy input.
     Per move: `iterations` rounds of PuctSearch (batch_puct's loop, with `leaves` and `capacity` as there), the move of
@@ -2458,7 +2716,11 @@ def puct_play(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, leav
     repetitions inside the tree below the root are not checked: the search still plans with them.  superko='tree': the loop of
     True with the history also handed to the search (PuctSearch(superko=)), with reuse=False to the new search of every move
     too: the rule holds at every node.  Any other value raises ValueError.  area: as batch_puct - the area ownership planes as
-    the evaluator's last argument."""
+    the evaluator's last argument.  past (None = everything above, launch for launch; with features=): the history planes
+    as the evaluator's last argument (PuctSearch(past=)).  An int T or a pair (T, moves) makes an empty StoneHistory for games
+    that start here; the loop keeps it - every move the roots that move are pushed before they are played on, by advance or,
+    with reuse=False, before the new search gets the same object; a StoneHistory is used as given, for games that do not
+    start here (it holds the positions before batch_states)."""
     _puct_superko_guard(superko)
     _puct_komi_guard(evaluator, komi)
     _puct_features_guard(evaluator, features)
@@ -2466,16 +2728,23 @@ def puct_play(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, leav
     _puct_ladder_guard(ladder, features)
     _puct_outcome_guard(outcome, features)
     _puct_area_guard(area, features)
+    _puct_past_guard(past, features)
+    if past is not None and not isinstance(past, StoneHistory):
+        _past_request(past)
     moves = int(moves)
     if moves < 0:
         raise ValueError('need moves >= 0 (got %d)' % moves)
     deep = None
+    if past is not None:
+        _puct_symmetry_guard(symmetry, features)
+        batch_states = batch_states if isinstance(batch_states, _Box) else _Box(batch_states)
+        past = _puct_past_history(past, batch_states)
     if superko is not True and superko:   # ('tree': the search keeps the history, which therefore stands before the search)
         _puct_symmetry_guard(symmetry, features)
         batch_states = batch_states if isinstance(batch_states, _Box) else _Box(batch_states)
         deep = _puct_superko_history(superko, batch_states, moves)
     search = PuctSearch(batch_states, iterations, c, komi, leaves=leaves, capacity=capacity, features=features, symmetry=symmetry,
-                        first_root=first_root, life=life, ladder=ladder, outcome=outcome, superko=deep, area=area)
+                        first_root=first_root, life=life, ladder=ladder, outcome=outcome, superko=deep, area=area, past=past)
     box = search._box
     played = torch.empty((search._R, moves), dtype=_I64, device=box.t.device)
     seen = None
@@ -2492,10 +2761,12 @@ def puct_play(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, leav
         if reuse:
             search.advance(played[:, mv], check=False)
         else:   # only node 0's boards are played on: the tree goes, so no advance over it; the states stay on the device
+            if search._R:
+                search._push_past(played[:, mv])
             box.t = search._played_states(played[:, mv])
             search = PuctSearch(box, iterations, c, komi, leaves=leaves, capacity=capacity, features=features,
                                 symmetry=None if symmetry is None else int(symmetry) + mv + 1, first_root=first_root, life=life,
-                                ladder=ladder, outcome=outcome, superko=deep, area=area)
+                                ladder=ladder, outcome=outcome, superko=deep, area=area, past=past)
         if seen is not None:
             seen.push(search._root_hashes())
     return _back(box, played), box.back(search._root_states())
@@ -2533,7 +2804,7 @@ that ended, 0 for one still running), lengths (int32 [R]: moves played), final_s
 
 def puct_selfplay(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, leaves=None, capacity=None, noise=None,
                   eps=0.25, sample_moves=0, seed=20260927, first_game=0, record_states=False, features=None, symmetry=None,
-                  life=False, ladder=False, outcome=False, superko=False, area=False):
+                  life=False, ladder=False, outcome=False, superko=False, area=False, past=None):
     """Self-play games for training: `moves` moves from every root of batch_states ([R, 6, N, N]) with a PUCT search per move
     on the kept tree -> SelfPlay (device tensors for a device tensor, NumPy arrays for NumPy input).  puct_play's
     reuse=True loop (`iterations` rounds per move with `leaves` and `capacity` as there, then PuctSearch.advance) with
@@ -2569,7 +2840,12 @@ def puct_selfplay(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, 
     include plans through them; superko='tree' is the loop of True with the history also handed to the search
     (PuctSearch(superko=)): the rule holds at every node.  Any other value raises ValueError.  area: as batch_puct - the area
     ownership planes as the evaluator's last argument; the records do not change (selfplay_batch makes the ownership and
-    score targets from them)."""
+    score targets from them).  past: as puct_play - the history planes as the evaluator's last argument, an int T or a pair
+    (T, moves) for games that start here, or a StoneHistory of the positions before batch_states; the records do not change
+    (selfplay_batch(past=) makes the planes of the sampled positions from record.states)."""
+    _puct_past_guard(past, features)
+    if past is not None and not isinstance(past, StoneHistory):
+        _past_request(past)
     _puct_superko_guard(superko)
     _puct_komi_guard(evaluator, komi)
     _puct_features_guard(evaluator, features)
@@ -2605,7 +2881,7 @@ def puct_selfplay(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, 
         return _back(box, SelfPlay(played, pis, vals, won, lengths, st, before))
     deep = _puct_superko_history(superko, box, moves)
     search = PuctSearch(box, I, c, komi, leaves=leaves, capacity=capacity, features=features, symmetry=symmetry, first_root=first_game,
-                        life=life, ladder=ladder, outcome=outcome, superko=deep, area=area)
+                        life=life, ladder=ladder, outcome=outcome, superko=deep, area=area, past=_puct_past_history(past, box))
     rng = rng_seed(R, seed, first_game, device=dev)
     ones, todo = torch.ones(R, dtype=_U8, device=dev), torch.empty(R, dtype=_U8, device=dev)
     seen = (deep or PositionHistory(R, moves + 1, dev)).push(search._root_hashes()) if superko else None
@@ -2645,6 +2921,7 @@ def puct(state, iterations, evaluator, **kw):
     _puct_ladder_guard(kw.get('ladder', False), kw.get('features'))
     _puct_outcome_guard(kw.get('outcome', False), kw.get('features'))
     _puct_area_guard(kw.get('area', False), kw.get('features'))
+    _puct_past_guard(kw.get('past'), kw.get('features'))
     return _single(batch_puct, state, iterations, evaluator, **kw)
 
 
@@ -2656,6 +2933,7 @@ def puct_actions(batch_states, iterations, evaluator, **kw):
     _puct_ladder_guard(kw.get('ladder', False), kw.get('features'))
     _puct_outcome_guard(kw.get('outcome', False), kw.get('features'))
     _puct_area_guard(kw.get('area', False), kw.get('features'))
+    _puct_past_guard(kw.get('past'), kw.get('features'))
     box = _Box(batch_states)
     res = batch_puct(box.t, iterations, evaluator, **kw)
     return _best_legal(box, res.legal, res.visits.to(_I64))
@@ -2914,7 +3192,7 @@ def selfplay_targets(record, games, moves):
 
 
 def selfplay_batch(record, games, moves, orient, dtype=torch.float16, life=False, ladder=False, outcome=False, area=False,
-                   ownership=False):
+                   ownership=False, past=None):
     """Training samples from a self-play record, in one of the eight orientations each -> (planes [B, 16, N, N] of `dtype`,
     pi [B, A] float32, z float32 [B], valid bool [B]).  record: a SelfPlay of puct_selfplay(.., record_states=True)
     (ValueError if record.states is None); games, moves, orient: int [B] - sample i is the position before move moves[i] of
@@ -2932,8 +3210,14 @@ def selfplay_batch(record, games, moves, orient, dtype=torch.float16, life=False
     side = the turn of the SAMPLED position (plane 2 of record.states[games, moves]): +1 = "ends up mine" for the player to
     move in the sample, margin = that player's area minus the other's at the end of the game (one launch more).  Komi is not
     in the record: subtract it from margin on black's samples and add it on white's.  For a game that had not ended after
-    the recorded moves the final position is just the last one: `valid` and record.outcome == 0 tell."""
+    the recorded moves the final position is just the last one: `valid` and record.outcome == 0 tell.  past (None; an int T
+    or a pair (T, moves)): after the area planes and before the ownership targets, the history planes [B, planes, N, N] of
+    the sampled positions in view orient and dtype `dtype` - a StoneHistory of the B samples filled from
+    record.states[games, moves - t] for t = T - 1 .. 1, oldest first, where moves - t >= 0 (T - 1 pushes), then one
+    batch_past_planes launch with orient."""
     _feature_dtype(dtype)
+    if past is not None:
+        past = _past_request(past)
     z, valid = selfplay_targets(record, games, moves)
     is_np = not isinstance(record.states, torch.Tensor)
     B = z.shape[0]
@@ -2955,6 +3239,12 @@ def selfplay_batch(record, games, moves, orient, dtype=torch.float16, life=False
         res += (batch_move_planes(positions, dtype, orient=orient),)
     if area:
         res += (batch_area_planes(positions, dtype, orient=orient),)
+    if past is not None:
+        hist = StoneHistory(B, positions.shape[2], past[0], past[1], device=dev)
+        all_states = t(record.states)
+        for back in range(past[0] - 1, 0, -1):
+            hist.push(all_states[g, (m - back).clamp(min=0)], m - back >= 0)
+        res += (batch_past_planes(positions, hist, dtype, orient=orient),)
     if ownership:
         owner, margin = batch_ownership(t(record.final_states)[g], side=positions[:, govars.TURN_CHNL, 0, 0] != 0, orient=orient)
         res += (owner, margin.to(torch.float32))
