@@ -5,8 +5,8 @@ ROCm device tensor of the dtype its parameter takes, the call raises.  PyTorch i
 memory and the current HIP stream; every entry point of include/gymgo_amd.h is bound here with plain
 pointers, from ONE table (ABI) that tests/test_host_abi.py holds against the header, and reached through
 call().  A new entry point is one declaration in the header and one entry in the table.  The area family has a header of
-its own, include/gymgo_amd_area.h, and a table of its own, ABI_AREA, bound and called the same way; so has the past family
-(include/gymgo_amd_past.h, ABI_PAST).
+its own, include/gymgo_amd_area.h, and a table of its own, ABI_AREA, bound and called the same way; so have the past family
+(include/gymgo_amd_past.h, ABI_PAST) and the Gumbel root rule of the PUCT search (include/gymgo_amd_gumbel.h, ABI_GUMBEL).
 """
 import collections
 import ctypes
@@ -186,17 +186,32 @@ ABI_PAST = {
     'gg_puct_past': (_RNC + _params(_i32, 'L') + _params(_I32, 'boards', 'links') + _RING + _params(_i32, 'T', 'moves')
                      + _params(_I32, 'leaf', 'leaf_id', 'orient') + _OUT + _params(_i32, 'out_dtype') + _STREAM),
 }
+# ... and of include/gymgo_amd_gumbel.h, the Gumbel root rule's header, in its order (tests/test_gumbel_host.py holds it against its
+# header).  seq of gg_gumbel_sequence is HOST memory: call() passes the int address it is given
+_GUMBEL_TREE = _params(_I32, 'child', 'stats', 'nodes')
+ABI_GUMBEL = {
+    'gg_gumbel_sequence': _params(_i32, 'm', 'n') + _params(_I32, 'seq'),
+    'gg_gumbel_begin': _RNC + _GUMBEL_TREE + _params(_I32, 'seen', 'done') + _STREAM,
+    'gg_gumbel_select_leaves': (_RNC + _params(_i32, 'L') + _params(_f64, 'c') + _PUCT_TREE + _params(_F32, 'base')
+                                + _params(_I32, 'seen', 'done', 'seq') + _params(_i32, 'S') + _params(_f64, 'c_visit', 'c_scale')
+                                + _LEAF),
+    'gg_gumbel_root': (_RNC + _params(_I32, 'boards') + _GUMBEL_TREE + _params(_F32, 'base') + _params(_I32, 'seen')
+                       + _params(_f64, 'c_visit', 'c_scale') + _params(_I32, 'actions') + _params(_F32, 'q') + _params(_I32, 'visits')
+                       + _params(_F32, 'value') + _STREAM),
+}
 EXPORTS = tuple(ABI)
 EXPORTS_AREA = tuple(ABI_AREA)
 EXPORTS_PAST = tuple(ABI_PAST)
+EXPORTS_GUMBEL = tuple(ABI_GUMBEL)
 _signatures = lambda table: {f: ([p.kind if isinstance(p.kind, type) else _vp for p in ps], _i32) for f, ps in table.items()}
 _SIGNATURES = _signatures(ABI)   # argtypes, restype
 _SIGNATURES_AREA = _signatures(ABI_AREA)
 _SIGNATURES_PAST = _signatures(ABI_PAST)
+_SIGNATURES_GUMBEL = _signatures(ABI_GUMBEL)
 # call(): the number of parameters and (index, dtypes, name) of every pointer to device memory
 _POINTERS = {f: (len(ps), tuple((i, p.kind if isinstance(p.kind, tuple) else (p.kind,), p.name)
                                 for i, p in enumerate(ps) if not isinstance(p.kind, type)))
-             for table in (ABI, ABI_AREA, ABI_PAST) for f, ps in table.items()}
+             for table in (ABI, ABI_AREA, ABI_PAST, ABI_GUMBEL) for f, ps in table.items()}
 
 _lib = None
 
@@ -210,7 +225,7 @@ def build(force=False):
     import subprocess
     csrc = os.path.join(_HERE, 'csrc')
     srcs = [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(('.hip', '.h'))]
-    srcs += [os.path.join(os.path.dirname(_HERE), 'include', h) for h in ('gymgo_amd.h', 'gymgo_amd_area.h', 'gymgo_amd_past.h')]
+    srcs += [os.path.join(os.path.dirname(_HERE), 'include', h) for h in ('gymgo_amd.h', 'gymgo_amd_area.h', 'gymgo_amd_past.h', 'gymgo_amd_gumbel.h')]
     stale = not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < max(os.path.getmtime(f) for f in srcs)
     if force or stale:
         subprocess.check_call(['make', '-C', os.path.join(_HERE, 'csrc'), '-s', '-B', '-j3'])
@@ -225,7 +240,8 @@ def lib():
                 'HIP library %s not built (run `make -C gymgo_amd/csrc` or __graft_entry__.build()); '
                 'gymgo_amd has no CPU fallback' % LIB_PATH)
         L = ctypes.CDLL(LIB_PATH)
-        for name, (argtypes, restype) in list(_SIGNATURES.items()) + list(_SIGNATURES_AREA.items()) + list(_SIGNATURES_PAST.items()):
+        for name, (argtypes, restype) in (list(_SIGNATURES.items()) + list(_SIGNATURES_AREA.items()) + list(_SIGNATURES_PAST.items())
+                                          + list(_SIGNATURES_GUMBEL.items())):
             fn = getattr(L, name)  # AttributeError if the .so does not export what the header declares
             fn.argtypes, fn.restype = argtypes, restype
         if L.gg_version() != ABI_VERSION:
@@ -373,7 +389,8 @@ def dev_ptr(t, dtype, name):
 def ptrs(fn, **tensors):
     """dev_ptr of every tensor as the parameter of entry point `fn` it is named after - dtype(s) from the table -, in the order
     given: for the paths that check their buffers once and hand call() the pointers from then on."""
-    kinds = {p.name: p.kind for p in (ABI[fn] if fn in ABI else ABI_AREA[fn] if fn in ABI_AREA else ABI_PAST[fn])}
+    kinds = {p.name: p.kind for p in (ABI[fn] if fn in ABI else ABI_AREA[fn] if fn in ABI_AREA else ABI_PAST[fn] if fn in ABI_PAST
+                                      else ABI_GUMBEL[fn])}
     return tuple(dev_ptr(t, kinds[n], n) for n, t in tensors.items())
 
 

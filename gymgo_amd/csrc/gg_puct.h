@@ -2,7 +2,8 @@
 // gg_puct_backup, and gg_puct_select_leaves / gg_puct_backup_leaves with several leaves per root and round): the tree of
 // every root lives on the device, the select and backup kernels walk it, the leaves are handed out and their evaluations
 // (priors, value) come back from outside the library.  There is ONE walk and ONE backup, k_puct_select<VL> and
-// k_puct_backup<RR, VL>: VL = false is the one-leaf search, VL = true the search with virtual loss (further down).
+// k_puct_backup<RR, VL>: VL = false is the one-leaf search, VL = true the search with virtual loss (further down).  The walk
+// has a second parameter, Root: what chooses the action at node 0 (PuctNoRoot, the default: step d, as at every node).
 //
 // R independent searches of I iterations, one tree per root with room for I + 1 nodes (node 0 = the root).  Per node: its
 // tracked board, parent / action (-1 at the root), the stat record {w: float64 sum of the backed-up values from black's point
@@ -108,8 +109,20 @@ static __global__ void k_puct_begin(const uint32_t *__restrict__ roots, PuctArgs
   if (k == 0) a.nodes[r] = 1;
 }
 
-template <bool VL>
-static __global__ __launch_bounds__(4 * kWave) void k_puct_select(PuctArgs a) {
+// The root rule of the walk: what chooses a* at node 0 in place of step d.  PuctNoRoot is "nothing does", and with it every
+// `if constexpr (Root::kOn)` below is discarded before any code is made: k_puct_select<VL> is the walk alone.  These blocks
+// are the differences of a search with a root rule of its own (gg_gumbel.h has the one there is), and there are no others.
+// A root rule names the kernel's argument struct, Args (PuctArgs, or a struct derived from it), and gives
+//   begin(a, r)                                       -> the simulations of this move handed out so far (wave-uniform)
+//   choose(a, r, t, g, ch, st, nodes, s, N, A, lane)  -> a* at node 0 for simulation t (wave-uniform, A = none)
+//   end(a, r, t, lane)                                   the count after this launch's slots
+struct PuctNoRoot {
+  static constexpr bool kOn = false;
+  using Args = PuctArgs;
+};
+
+template <bool VL, class Root = PuctNoRoot>
+static __global__ __launch_bounds__(4 * kWave) void k_puct_select(typename Root::Args a) {
   const int lane = threadIdx.x & (kWave - 1);
   const int64_t wave = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) / kWave;
   const int64_t nwaves = (gridDim.x * (int64_t)blockDim.x) / kWave;
@@ -122,8 +135,11 @@ static __global__ __launch_bounds__(4 * kWave) void k_puct_select(PuctArgs a) {
     int32_t *ln = a.links + r * NN * 2;
     int nodes = max(1, min(a.nodes[r], NN));   // (1 <= nodes <= I + 1 by construction: every index below stays inside the tree)
     bool open = true;                          // false from the slot that met a collision on (VL)
+    [[maybe_unused]] int done = 0;             // (a root rule's count of this move's simulations)
+    if constexpr (Root::kOn) done = Root::begin(a, r);
     for (int j = 0; j < L; ++j) {
       int x = 0, mv = -1, y = -1;
+      [[maybe_unused]] bool ruled = false;     // the root rule chose this slot's action at node 0
       if (open) {
         if (VL) puct_handover();   // the links, child entries and v of the slots before this one
         // every step goes to a child with a larger id: at most I steps (the bound also stops a walk over corrupt links)
@@ -141,33 +157,41 @@ static __global__ __launch_bounds__(4 * kWave) void k_puct_select(PuctArgs a) {
           const double s = (flag & 1u) ? -1.0 : 1.0;
           double best = -__builtin_inf();
           int besta = A;
-          for (int a0 = 0; a0 < A; a0 += kWave) {
-            const int act = a0 + lane;
-            if (act >= A || !puct_legal(g, act, N)) continue;
-            const int c = ch[(int64_t)x * A + act];
-            const float p = pr[(int64_t)x * A + act];
-            double wc = 0.0;
-            int32_t nc = 0, vc = 0;
-            if (c > x && c < nodes) {   // (children always have larger ids than their parent)
-              const PuctStat k = st[c];
-              wc = k.w;
-              nc = k.n < 0 ? 0 : k.n;
-              if (VL) vc = k.v < 0 ? 0 : k.v;
-            }
-            const double u = puct_score<VL>(s, wc, nc, vc, p, nx, vx < 0 ? 0 : vx, a.c);
-            if (u > best || besta == A) {   // (this lane's actions ascend: the first of equal scores stays)
-              best = u;
-              besta = act;
+          if constexpr (Root::kOn) {
+            if (x == 0) {   // the root rule in place of step d
+              besta = Root::choose(a, r, done, g, ch, st, nodes, s, N, A, lane);
+              ruled = true;
             }
           }
-          // the wave's argmax, ties to the lowest action (a lane without a legal action holds -inf / A and loses every tie)
+          if (!Root::kOn || x != 0) {   // step d (a constant condition without a root rule)
+            for (int a0 = 0; a0 < A; a0 += kWave) {
+              const int act = a0 + lane;
+              if (act >= A || !puct_legal(g, act, N)) continue;
+              const int c = ch[(int64_t)x * A + act];
+              const float p = pr[(int64_t)x * A + act];
+              double wc = 0.0;
+              int32_t nc = 0, vc = 0;
+              if (c > x && c < nodes) {   // (children always have larger ids than their parent)
+                const PuctStat k = st[c];
+                wc = k.w;
+                nc = k.n < 0 ? 0 : k.n;
+                if (VL) vc = k.v < 0 ? 0 : k.v;
+              }
+              const double u = puct_score<VL>(s, wc, nc, vc, p, nx, vx < 0 ? 0 : vx, a.c);
+              if (u > best || besta == A) {   // (this lane's actions ascend: the first of equal scores stays)
+                best = u;
+                besta = act;
+              }
+            }
+            // the wave's argmax, ties to the lowest action (a lane without a legal action holds -inf / A and loses every tie)
 #pragma unroll
-          for (int o = kWave / 2; o > 0; o >>= 1) {
-            const double ob = __shfl_xor(best, o);
-            const int oa = __shfl_xor(besta, o);
-            if (ob > best || (ob == best && oa < besta)) {
-              best = ob;
-              besta = oa;
+            for (int o = kWave / 2; o > 0; o >>= 1) {
+              const double ob = __shfl_xor(best, o);
+              const int oa = __shfl_xor(besta, o);
+              if (ob > best || (ob == best && oa < besta)) {
+                best = ob;
+                besta = oa;
+              }
             }
           }
           if (besta >= A) break;   // (the pass is always legal: only with corrupt buffers)
@@ -202,6 +226,9 @@ static __global__ __launch_bounds__(4 * kWave) void k_puct_select(PuctArgs a) {
           z = ln[2 * z];
         }
       }
+      if constexpr (Root::kOn) {
+        if (y >= 0 && ruled) done += 1;   // (a collision leaves the count as it leaves everything else)
+      }
       // the leaf board: the new node's parent (its move is played by the next launch) or the node itself
       const uint32_t *g = bd + (int64_t)x * W;
       uint32_t *out = a.leaf + row * W;
@@ -212,6 +239,7 @@ static __global__ __launch_bounds__(4 * kWave) void k_puct_select(PuctArgs a) {
       }
     }
     if (VL && lane == 0) a.nodes[r] = nodes;   // (the clamped count, whether or not a slot expanded)
+    if constexpr (Root::kOn) Root::end(a, r, done, lane);
   }
 }
 

@@ -2008,6 +2008,63 @@ def _puct_capacity(iterations, leaves, capacity):
 _ON_DEVICE = collections.namedtuple('_OnDevice', 'numpy')(False)   # a _Box stand-in: results stay device tensors
 
 
+# ---------------------------------------------------------------- the Gumbel root rule (include/gymgo_amd_gumbel.h)
+Gumbel = collections.namedtuple('Gumbel', 'considered simulations c_visit c_scale', defaults=(16, None, 50.0, 0.5))
+Gumbel.__doc__ = """The Gumbel root rule of PuctSearch(gumbel=): considered (m, the actions drawn without replacement by the
+Gumbel-top-k trick), simulations (n, the budget sequential halving spreads over them; None = max(1, (iterations - 1) * leaves),
+what a fresh root gets, whose round 0 evaluates the root alone), c_visit and c_scale (sigma(q) = (c_visit + max visits) *
+c_scale * q; the paper's c_scale = 1.0 is for q in [0, 1], values here are in [-1, 1], and a constant shift changes neither an
+argmax nor a softmax)."""
+
+
+def _int_arg(x):
+    return not isinstance(x, bool) and isinstance(x, (int, np.integer))
+
+
+def gumbel_sequence(considered, simulations):
+    """The schedule of sequential halving -> int32 [simulations] (NumPy; gg_gumbel_sequence, host only): entry t is the number
+    of this move's simulations the action that gets simulation t must have had.  gumbel_sequence(4, 8) = 0,0,0,0,1,1,2,2."""
+    if not _int_arg(considered) or not _int_arg(simulations) or considered < 1 or simulations < 1 or max(considered, simulations) >= 2 ** 31:
+        raise ValueError('need integers considered >= 1 and simulations >= 1 below 2^31 (got %r, %r)' % (considered, simulations))
+    seq = np.empty(int(simulations), np.int32)
+    _lib.call('gg_gumbel_sequence', int(considered), int(simulations), seq.ctypes.data)
+    return seq
+
+
+def _gumbel_arg(gumbel, iterations, leaves):
+    """gumbel=None -> None; an int m or a Gumbel -> the validated Gumbel with its simulations filled in."""
+    if gumbel is None:
+        return None
+    if _int_arg(gumbel):
+        gumbel = Gumbel(int(gumbel))
+    if not isinstance(gumbel, Gumbel):
+        raise ValueError('gumbel must be None, an integer >= 1 (the actions considered) or a Gumbel (got %r)' % (gumbel,))
+    m, n, cv, cs = gumbel
+    if n is None:
+        n = max(1, (int(iterations) - 1) * leaves)
+    if not _int_arg(m) or not _int_arg(n) or m < 1 or n < 1 or max(m, n) >= 2 ** 31:
+        raise ValueError('need integers considered >= 1 and simulations >= 1 below 2^31 (got %r, %r)' % (m, n))
+    try:
+        cv, cs = float(cv), float(cs)
+    except (TypeError, ValueError):
+        raise ValueError('c_visit and c_scale must be numbers (got %r, %r)' % (gumbel.c_visit, gumbel.c_scale)) from None
+    if not (math.isfinite(cv) and cv >= 0 and math.isfinite(cs) and cs >= 0):
+        raise ValueError('need c_visit >= 0 and c_scale >= 0, both finite (got %r, %r)' % (cv, cs))
+    return Gumbel(int(m), int(n), cv, cs)
+
+
+def gumbel_noise(generator=None):
+    """The Gumbel(0, 1) draws of a Gumbel search -> a callable noise(move, legal) -> float32 [R, A] on legal's device:
+    -log(-log(u)) of torch's uniform draws u (`generator`: a torch.Generator of that device, None = torch's default), one per
+    action, legal or not (the search never reads the entries of illegal actions).  NOT bit-defined, like dirichlet_noise: the
+    draws and the logarithms are torch's; everything the library does with the noise is exact."""
+    def noise(move, legal):
+        u = torch.rand(legal.shape, dtype=torch.float32, device=legal.device, generator=generator)
+        return -torch.log(-torch.log(u.clamp(min=torch.finfo(torch.float32).tiny)))
+
+    return noise
+
+
 class PuctSearch:
     """The step-wise form of batch_puct, for callers who batch their network calls their own way:
 
@@ -2109,11 +2166,27 @@ class PuctSearch:
     for node 0 - with no argument it uses the search's history.  THE INVARIANT that keeps the marks right across advance():
     a kept node was marked against (old history + its old chain); the old root and the node under the action played leave
     the chain and enter the history, so that set IS (new history + its new chain) - provided the history has dropped no
-    entry: give the PositionHistory the capacity of the whole game.  One launch more per select(), one per advance()."""
+    entry: give the PositionHistory the capacity of the whole game.  One launch more per select(), one per advance().
+
+    gumbel (None = everything above, every allocation and launch as without it; or an int m, or a Gumbel): the Gumbel root
+    rule by sequential halving (include/gymgo_amd_gumbel.h, which holds the normative text).  At node 0 the walk takes the
+    action the schedule gumbel_sequence(m, n) asks for - among the legal actions with that many of this move's simulations,
+    the one with the largest base + sigma(q), base = g + log(prior) - instead of the largest U'; below the root nothing
+    changes.  leaves=None counts as leaves=1 (the same tree as the one-leaf path).  The schedule is uploaded once;
+    gg_gumbel_begin (seen = the visits the root's children have now, done = 0) runs at construction and at the end of every
+    advance().  g starts as zeros - noise-free sequential halving, for match play - and set_gumbel(g) replaces it (float32
+    [R, A]; gumbel_noise() makes the draws), only before the first select() after construction or after an advance
+    (ValueError otherwise).  select() refreshes `search.base` = g + log(prior[:, 0, :]) by torch, on the device, before the
+    select launches of the first two rounds after a begin or an advance - after round 0 every live root is evaluated - and
+    later rounds reuse the tensor; then it queues gg_gumbel_select_leaves in place of gg_puct_select_leaves.  gumbel_root() is
+    the read-out: the move, the improved policy and the root value.  add_root_noise() raises ValueError on such a search: the
+    exploration is g.  Rounds beyond the schedule (a kept root has iterations * leaves slots, a fresh one (iterations - 1) *
+    leaves) go to the actions with the most simulations of this move."""
 
     def __init__(self, batch_states, iterations, c=1.25, komi=0.0, leaves=None, capacity=None, features=None, symmetry=None,
-                 first_root=0, life=False, ladder=False, outcome=False, superko=None, area=False, past=None):
+                 first_root=0, life=False, ladder=False, outcome=False, superko=None, area=False, past=None, gumbel=None):
         self._feat = None if features is None else (features, _feature_dtype(features))
+        _gumbel_arg(gumbel, 2, 1)   # (what it is, before a device is touched; its simulations further down)
         if superko is not None:   # (before a device is touched)
             shape = np.shape(batch_states.t if isinstance(batch_states, _Box) else batch_states)
             _history_arg(superko, shape[0] if shape else -1)
@@ -2140,7 +2213,8 @@ class PuctSearch:
             raise ValueError('batch_states must be [R, 6, N, N] (got %s)' % (tuple(st.shape),))
         self._I, self._c, self._komi = _puct_args(iterations, c, komi)
         self._I0 = self._I      # the rounds as constructed: advance()'s default, whatever an earlier advance was given
-        self._L = _puct_leaves(self._I, leaves)
+        self._L = _puct_leaves(self._I, 1 if gumbel is not None and leaves is None else leaves)
+        self._gumbel = _gumbel_arg(gumbel, self._I, self._L or 1)
         NN = _puct_capacity(self._I, self._L, capacity)
         R, N, dev = st.shape[0], st.shape[2], st.device
         self._R, self._N, self._dev = R, N, dev
@@ -2183,6 +2257,12 @@ class PuctSearch:
         self.live = torch.full((R, self._L or 1), self._L is None, dtype=torch.bool, device=dev)   # (one leaf: always live)
         self._done, self._pending = 0, False
         self._init_symmetry(B)
+        if self._gumbel is not None:   # (g is zeros: noise-free sequential halving; base is written by select())
+            self._g = torch.zeros((R, A), dtype=torch.float32, device=dev)
+            self.base = torch.zeros((R, A), dtype=torch.float32, device=dev)
+            self._seen = torch.zeros((R, A), dtype=_I32, device=dev)
+            self._sims = torch.zeros(R, dtype=_I32, device=dev)
+            self._g_open, self._since = True, 0   # set_gumbel() is allowed; rounds selected since the last begin
         if not R:   # no device work at all: select / backup only keep the call order
             return
         # the search's own buffers are checked once, through the table; every call below gets their pointers
@@ -2199,6 +2279,80 @@ class PuctSearch:
         if past is not None:   # (the history's tensors are written in place: their addresses hold)
             self._past_ptrs = _lib.ptrs('gg_puct_past', boards=self._boards, links=self._links, rows=past.rows, count=past.count,
                                         out=self._past_planes)
+        if self._gumbel is not None:
+            self._seq = torch.from_numpy(gumbel_sequence(self._gumbel.considered, self._gumbel.simulations)).to(dev)
+            self._root = _lib.ptrs('gg_gumbel_select_leaves', base=self.base, seen=self._seen, done=self._sims, seq=self._seq)
+            self._gumbel_begin()
+
+    def _gumbel_begin(self):
+        """seen = the visits of node 0's children as they stand, done = 0 (R > 0): the search of a move begins; one launch."""
+        _, child, _, _, stats, nodes = self._tree
+        _lib.call('gg_gumbel_begin', self._R, self._N, self._C, child, stats, nodes, self._seen, self._sims,
+                  _lib.current_raw_stream(self._dev))
+
+    def _refresh_base(self):
+        """base = g + log(the root's stored priors), float32, by torch on the device (R > 0)."""
+        with torch.cuda.device(self._dev):
+            torch.add(self._g, torch.log(self._prior[:, 0, :]), out=self.base)
+
+    def set_gumbel(self, g):
+        """Replace g, the Gumbel draws of this move: floating point [R, A], a tensor or NumPy array (gumbel_noise() makes them;
+        the entries of illegal actions are never read).  Only before the first select() after construction or after an
+        advance(): ValueError otherwise, and on a search without gumbel=."""
+        if self._gumbel is None:
+            raise ValueError('PuctSearch.set_gumbel(): the search was made without gumbel=')
+        if not self._g_open:
+            raise ValueError('PuctSearch.set_gumbel(): only before the first select() after construction or after advance()')
+        R, A = self._R, self._N * self._N + 1
+        if not isinstance(g, torch.Tensor):
+            g = torch.from_numpy(np.ascontiguousarray(g))
+        if tuple(g.shape) != (R, A) or not g.dtype.is_floating_point:
+            raise ValueError('g must be floating point [%d, %d] (got %s %s)' % (R, A, g.dtype, tuple(g.shape)))
+        if R:
+            with torch.cuda.device(self._dev):
+                self._g.copy_(g.to(device=self._dev, dtype=torch.float32))
+
+    def gumbel_root(self, pi=True):
+        """The read-out of a Gumbel search (gg_gumbel_root) -> (actions int32 [R], pi float32 [R, A] or None with pi=False,
+        value float32 [R]); device tensors, or NumPy arrays for NumPy input.  actions: among the legal actions with the most
+        simulations of this move, the one with the largest base + sigma(q), ties to the lowest action; -1 for a root whose game
+        has ended.  pi: the improved policy, softmax over the legal actions of log(prior[a]) + (c_visit + max visits) * c_scale
+        * q[a], q the child's mean value for the player to move or, without visits, the root's - by torch on the device in
+        float64, cast to float32, +0 on illegal actions, a zero row for an ended root (where the largest term is infinite the
+        mass is shared by the actions that have it).  value: the root's mean value for the player to move.  May be called
+        whenever no leaf is outstanding; queues one launch and a handful of torch ops, reads nothing back."""
+        if self._gumbel is None:
+            raise ValueError('PuctSearch.gumbel_root(): the search was made without gumbel=')
+        if self._pending:
+            raise ValueError('PuctSearch.gumbel_root(): the leaves of the last select() have not been backed up')
+        return tuple(_back(self._box, t) for t in self._gumbel_root(pi))
+
+    def _gumbel_root(self, pi=True):
+        """gumbel_root() as new device tensors."""
+        R, A, dev = self._R, self._N * self._N + 1, self._dev
+        acts = torch.empty(R, dtype=_I32, device=dev)
+        v = torch.empty(R, dtype=torch.float32, device=dev)
+        q = torch.empty((R, A), dtype=torch.float32, device=dev) if pi else None
+        n = torch.empty((R, A), dtype=_I32, device=dev) if pi else None
+        if R:
+            if self._since < 2:   # (fewer than two selects since the begin: base is not yet the one of the evaluated roots)
+                self._refresh_base()
+            boards, child, _, _, stats, nodes = self._tree
+            _lib.call('gg_gumbel_root', R, self._N, self._C, boards, child, stats, nodes, self.base, self._seen, self._gumbel.c_visit,
+                      self._gumbel.c_scale, acts, q, n, v, _lib.current_raw_stream(dev))
+        if not pi:
+            return acts, None, v
+        if not R:
+            return acts, torch.zeros((R, A), dtype=torch.float32, device=dev), v
+        with torch.cuda.device(dev):
+            legal, f64 = self._legal_roots, torch.float64
+            scale = (self._gumbel.c_visit + n.max(dim=1, keepdim=True).values.to(f64)) * self._gumbel.c_scale
+            x = torch.log(self._prior[:, 0, :].to(f64)) + scale * q.to(f64)
+            x = torch.where(legal & (x == x), x, torch.full_like(x, -math.inf))
+            top = x.max(dim=1, keepdim=True).values
+            e = torch.where(legal, torch.where(x == top, torch.ones_like(x), torch.exp(x - top)), torch.zeros_like(x))
+            p = torch.where(legal, e / e.sum(dim=1, keepdim=True), torch.zeros_like(x)).to(torch.float32)
+        return acts, p, v
 
     def _fill_node_hash(self):
         """node_hash = the hash of every board of the boards buffer (R > 0): one launch."""
@@ -2255,8 +2409,15 @@ class PuctSearch:
             lib, check, stream = _lib.lib(), _lib.check, _lib.current_raw_stream(self._dev)
             lp, mp, ip = self._out
             sp, gp, vp = self._hand
-            name, slots = ('gg_puct_select', ()) if self._L is None else ('gg_puct_select_leaves', (self._L,))
-            check(getattr(lib, name)(R, N, self._C, *slots, self._c, *self._tree, lp, mp, ip, stream), name)
+            if self._gumbel is None:
+                name, slots = ('gg_puct_select', ()) if self._L is None else ('gg_puct_select_leaves', (self._L,))
+                check(getattr(lib, name)(R, N, self._C, *slots, self._c, *self._tree, lp, mp, ip, stream), name)
+            else:
+                if self._since < 2:   # (round 0 evaluates the fresh roots: from round 1 on every live root has its priors)
+                    self._refresh_base()
+                check(lib.gg_gumbel_select_leaves(R, N, self._C, self._L, self._c, *self._tree, *self._root, self._seq.numel(),
+                                                  self._gumbel.c_visit, self._gumbel.c_scale, lp, mp, ip, stream),
+                      'gg_gumbel_select_leaves')
             check(lib.gg_batch_play_moves_tracked(lp, mp, None, B, N, 1, stream), 'gg_batch_play_moves_tracked')
             if self._history is not None:   # (the history's tensors as they are now: PositionHistory.push works in place)
                 hp, cp = _lib.ptrs('gg_puct_superko', history=self._hist[0], count=self._hist[1])
@@ -2284,6 +2445,8 @@ class PuctSearch:
                 check(lib.gg_puct_past(R, N, self._C, self._L or 1, bp, kp, rp, cp, past.capacity, past.positions, int(past.moves),
                                        lp, ip, op, pp, self._feat[1], stream), 'gg_puct_past')
         self._pending = True
+        if self._gumbel is not None:
+            self._g_open, self._since = False, self._since + 1
         legal = self._legal if self._sym is None else self._legal_view
         res = (self._states, legal, self._life_planes) if self._life else (self._states, legal)
         res = res + (self._ladder_planes,) if self._ladder else res
@@ -2413,6 +2576,8 @@ class PuctSearch:
         if tuple(actions.shape) != (R,) or actions.dtype.is_floating_point or actions.dtype == torch.bool:
             raise ValueError('actions must be integers [%d] (got %s %s)' % (R, actions.dtype, tuple(actions.shape)))
         rounds = self._I0 if iterations is None else _puct_args(iterations, self._c, self._komi)[0]
+        if self._gumbel is not None:
+            self._g_open, self._since = True, 0
         if not R:
             self._done, self._I = 0, rounds
             return torch.empty(0, dtype=_I32, device=self._dev)
@@ -2431,6 +2596,8 @@ class PuctSearch:
             self._fill_node_hash()
         self._legal_roots = _legal_roots(self._root_states())
         self._done, self._I = 0, rounds
+        if self._gumbel is not None:
+            self._gumbel_begin()
         return self._kept
 
     def _root_hashes(self):
@@ -2477,6 +2644,8 @@ class PuctSearch:
         one call before round 0 reaches the kept roots, a second call with the same noise and todo after round 0 the fresh
         roots that round has just evaluated, and no root is changed twice.  May be called whenever no leaf is outstanding;
         queues one launch, reads nothing back."""
+        if self._gumbel is not None:
+            raise ValueError('PuctSearch.add_root_noise(): a Gumbel search explores through g (set_gumbel), not through the priors')
         if self._pending:
             raise ValueError('PuctSearch.add_root_noise(): the leaves of the last select() have not been backed up')
         R, A = self._R, self._N * self._N + 1
@@ -2538,7 +2707,8 @@ class PuctSearch:
 
 
 def batch_puct(batch_states, iterations, evaluator, c=1.25, komi=0.0, tree=False, leaves=None, capacity=None, features=None,
-               symmetry=None, first_root=0, life=False, ladder=False, outcome=False, superko=None, area=False, past=None):
+               symmetry=None, first_root=0, life=False, ladder=False, outcome=False, superko=None, area=False, past=None,
+               gumbel=None):
     """PUCT search (the AlphaZero search) of `iterations` iterations from every root of batch_states ([R, 6, N, N]) with the
     caller's evaluator -> Puct (device tensors for a device tensor, NumPy arrays for NumPy input).  The loop over PuctSearch.
 
@@ -2617,7 +2787,20 @@ def batch_puct(batch_states, iterations, evaluator, c=1.25, komi=0.0, tree=False
     past (None: the search above, launch for launch; or a StoneHistory of the R games holding the positions before the roots,
     with features=): the evaluator gets as its LAST argument, after life, ladder, outcome and area when those are on, the
     history planes [R, past.planes, N, N] ([R * L, ..]) of the feature dtype - the leaf, its ancestors in the tree and, beyond
-    node 0, the history (PuctSearch) - in the leaf's orientation with symmetry=."""
+    node 0, the history (PuctSearch) - in the leaf's orientation with symmetry=.
+
+    gumbel (None: the search above, launch for launch; or an int m, or a Gumbel): the Gumbel root rule by sequential halving
+    (PuctSearch): the root's simulations follow the schedule instead of U'.  The result type does not change - the visits
+    are those the schedule handed out -; puct_actions(gumbel=) gives the Gumbel move, PuctSearch.gumbel_root the improved
+    policy."""
+    return _puct_searched(batch_states, iterations, evaluator, c=c, komi=komi, leaves=leaves, capacity=capacity, features=features,
+                          symmetry=symmetry, first_root=first_root, life=life, ladder=ladder, outcome=outcome, superko=superko,
+                          area=area, past=past, gumbel=gumbel).result(tree=tree)
+
+
+def _puct_searched(batch_states, iterations, evaluator, c=1.25, komi=0.0, leaves=None, capacity=None, features=None, symmetry=None,
+                   first_root=0, life=False, ladder=False, outcome=False, superko=None, area=False, past=None, gumbel=None):
+    """batch_puct's loop -> the PuctSearch after its last backup."""
     _puct_komi_guard(evaluator, komi)
     _puct_features_guard(evaluator, features)
     _puct_life_guard(life, features)
@@ -2626,13 +2809,14 @@ def batch_puct(batch_states, iterations, evaluator, c=1.25, komi=0.0, tree=False
     _puct_area_guard(area, features)
     _puct_past_guard(past, features)
     search = PuctSearch(batch_states, iterations, c, komi, leaves=leaves, capacity=capacity, features=features, symmetry=symmetry,
-                        first_root=first_root, life=life, ladder=ladder, outcome=outcome, superko=superko, area=area, past=past)
+                        first_root=first_root, life=life, ladder=ladder, outcome=outcome, superko=superko, area=area, past=past,
+                        gumbel=gumbel)
     if superko is not None:
         search.forbid_repeats()
     for _ in range(search._I):
         priors, values = evaluator(*search.select())
         search.backup(priors, values)
-    return search.result(tree=tree)
+    return search
 
 
 def _puct_komi_guard(evaluator, komi):
@@ -2688,7 +2872,8 @@ def _puct_features_guard(evaluator, features):
 
 
 def puct_play(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, leaves=None, capacity=None, reuse=True, features=None,
-              symmetry=None, first_root=0, life=False, ladder=False, outcome=False, superko=False, area=False, past=None):
+              symmetry=None, first_root=0, life=False, ladder=False, outcome=False, superko=False, area=False, past=None,
+              gumbel=None, gumbel_noise=None):
     """Play `moves` moves from every root of batch_states ([R, 6, N, N]) with a PUCT search per move -> (actions int64
     [R, moves], the final states uint8 [R, 6, N, N]); device tensors for a device tensor, NumPy arrays for NumPy input.
     Per move: `iterations` rounds of PuctSearch (batch_puct's loop, with `leaves` and `capacity` as there), the move of
@@ -2720,7 +2905,12 @@ def puct_play(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, leav
     as the evaluator's last argument (PuctSearch(past=)).  An int T or a pair (T, moves) makes an empty StoneHistory for games
     that start here; the loop keeps it - every move the roots that move are pushed before they are played on, by advance or,
     with reuse=False, before the new search gets the same object; a StoneHistory is used as given, for games that do not
-    start here (it holds the positions before batch_states)."""
+    start here (it holds the positions before batch_states).  gumbel (None = everything above, launch for launch; or an int
+    m, or a Gumbel): every move's search runs under the Gumbel root rule (PuctSearch(gumbel=)) and the move played is the
+    Gumbel action (PuctSearch.gumbel_root; -1 for a root whose game has ended); gumbel_noise (None, or a callable
+    noise(mv, legal) -> float [R, A] as gumbel_noise() returns; needs gumbel=): g of move mv, set before its first round;
+    None leaves g at zeros - noise-free sequential halving, for match play."""
+    _gumbel_noise_guard(gumbel, gumbel_noise)
     _puct_superko_guard(superko)
     _puct_komi_guard(evaluator, komi)
     _puct_features_guard(evaluator, features)
@@ -2744,7 +2934,8 @@ def puct_play(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, leav
         batch_states = batch_states if isinstance(batch_states, _Box) else _Box(batch_states)
         deep = _puct_superko_history(superko, batch_states, moves)
     search = PuctSearch(batch_states, iterations, c, komi, leaves=leaves, capacity=capacity, features=features, symmetry=symmetry,
-                        first_root=first_root, life=life, ladder=ladder, outcome=outcome, superko=deep, area=area, past=past)
+                        first_root=first_root, life=life, ladder=ladder, outcome=outcome, superko=deep, area=area, past=past,
+                        gumbel=gumbel)
     box = search._box
     played = torch.empty((search._R, moves), dtype=_I64, device=box.t.device)
     seen = None
@@ -2753,11 +2944,16 @@ def puct_play(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, leav
     for mv in range(moves):
         if seen is not None:
             search.forbid_repeats(seen)
+        if gumbel_noise is not None:
+            search.set_gumbel(gumbel_noise(mv, search._legal_roots))
         for _ in range(search._I):
             priors, values = evaluator(*search.select())
             search.backup(priors, values)
-        res = search._result()
-        played[:, mv] = _best_legal(_ON_DEVICE, res.legal, res.visits.to(_I64))
+        if gumbel is None:
+            res = search._result()
+            played[:, mv] = _best_legal(_ON_DEVICE, res.legal, res.visits.to(_I64))
+        else:
+            played[:, mv] = search._gumbel_root(pi=False)[0]
         if reuse:
             search.advance(played[:, mv], check=False)
         else:   # only node 0's boards are played on: the tree goes, so no advance over it; the states stay on the device
@@ -2766,10 +2962,17 @@ def puct_play(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, leav
             box.t = search._played_states(played[:, mv])
             search = PuctSearch(box, iterations, c, komi, leaves=leaves, capacity=capacity, features=features,
                                 symmetry=None if symmetry is None else int(symmetry) + mv + 1, first_root=first_root, life=life,
-                                ladder=ladder, outcome=outcome, superko=deep, area=area, past=past)
+                                ladder=ladder, outcome=outcome, superko=deep, area=area, past=past, gumbel=gumbel)
         if seen is not None:
             seen.push(search._root_hashes())
     return _back(box, played), box.back(search._root_states())
+
+
+def _gumbel_noise_guard(gumbel, noise, default=None):
+    if noise is not None and noise != default and not callable(noise):   # (before a device is touched)
+        raise ValueError('gumbel_noise must be None or a callable noise(move, legal) -> float [R, A]')
+    if gumbel is None and callable(noise):
+        raise ValueError('gumbel_noise makes the draws of a Gumbel search: give gumbel= too')
 
 
 def dirichlet_noise(alpha, generator=None):
@@ -2804,7 +3007,7 @@ that ended, 0 for one still running), lengths (int32 [R]: moves played), final_s
 
 def puct_selfplay(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, leaves=None, capacity=None, noise=None,
                   eps=0.25, sample_moves=0, seed=20260927, first_game=0, record_states=False, features=None, symmetry=None,
-                  life=False, ladder=False, outcome=False, superko=False, area=False, past=None):
+                  life=False, ladder=False, outcome=False, superko=False, area=False, past=None, gumbel=None, gumbel_noise='default'):
     """Self-play games for training: `moves` moves from every root of batch_states ([R, 6, N, N]) with a PUCT search per move
     on the kept tree -> SelfPlay (device tensors for a device tensor, NumPy arrays for NumPy input).  puct_play's
     reuse=True loop (`iterations` rounds per move with `leaves` and `capacity` as there, then PuctSearch.advance) with
@@ -2842,7 +3045,15 @@ def puct_selfplay(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, 
     ownership planes as the evaluator's last argument; the records do not change (selfplay_batch makes the ownership and
     score targets from them).  past: as puct_play - the history planes as the evaluator's last argument, an int T or a pair
     (T, moves) for games that start here, or a StoneHistory of the positions before batch_states; the records do not change
-    (selfplay_batch(past=) makes the planes of the sampled positions from record.states)."""
+    (selfplay_batch(past=) makes the planes of the sampled positions from record.states).  gumbel (None = everything above,
+    launch for launch; or an int m, or a Gumbel): self-play under the Gumbel root rule (PuctSearch(gumbel=)).  Per move
+    g = gumbel_noise(mv, legal) is set before the first round (gumbel_noise: 'default' = gumbel_noise(), torch's default
+    generator; None = zeros; or a callable as gumbel_noise() returns), the move is the Gumbel action - already a draw from the
+    improved policy, so sample_moves > 0 raises ValueError, as does noise other than None: the exploration is g -, the
+    recorded pi is the improved policy and value the root's mean value (PuctSearch.gumbel_root).  selfplay_batch takes the
+    records as they are."""
+    _gumbel_noise_guard(gumbel, gumbel_noise, 'default')
+    _gumbel_arg(gumbel, 2, 1)
     _puct_past_guard(past, features)
     if past is not None and not isinstance(past, StoneHistory):
         _past_request(past)
@@ -2862,6 +3073,10 @@ def puct_selfplay(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, 
         raise ValueError('need 0 <= eps <= 1 (got %r)' % eps)
     if noise is not None and not callable(noise):
         raise ValueError('noise must be None or a callable noise(move, legal) -> float32 [R, A]')
+    if gumbel is not None and noise is not None:
+        raise ValueError('a Gumbel search explores through gumbel_noise, not through noise in the priors: noise must be None')
+    if gumbel is not None and sample_moves > 0:
+        raise ValueError('the Gumbel action is already a draw from the improved policy: sample_moves must be 0 with gumbel=')
     _puct_symmetry_guard(symmetry, features)
     box = batch_states if isinstance(batch_states, _Box) else _Box(batch_states)
     st = box.t
@@ -2869,6 +3084,8 @@ def puct_selfplay(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, 
         raise ValueError('batch_states must be [R, 6, N, N] (got %s)' % (tuple(st.shape),))
     I, c, komi = _puct_args(iterations, c, komi)
     _puct_capacity(I, _puct_leaves(I, leaves), capacity)
+    _gumbel_arg(gumbel, I, _puct_leaves(I, leaves) or 1)
+    draws = None if gumbel is None else (globals()['gumbel_noise']() if gumbel_noise == 'default' else gumbel_noise)
     R, N, dev = st.shape[0], st.shape[2], st.device
     A = N * N + 1
     played = torch.full((R, moves), -1, dtype=_I64, device=dev)
@@ -2881,7 +3098,8 @@ def puct_selfplay(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, 
         return _back(box, SelfPlay(played, pis, vals, won, lengths, st, before))
     deep = _puct_superko_history(superko, box, moves)
     search = PuctSearch(box, I, c, komi, leaves=leaves, capacity=capacity, features=features, symmetry=symmetry, first_root=first_game,
-                        life=life, ladder=ladder, outcome=outcome, superko=deep, area=area, past=_puct_past_history(past, box))
+                        life=life, ladder=ladder, outcome=outcome, superko=deep, area=area, past=_puct_past_history(past, box),
+                        gumbel=gumbel)
     rng = rng_seed(R, seed, first_game, device=dev)
     ones, todo = torch.ones(R, dtype=_U8, device=dev), torch.empty(R, dtype=_U8, device=dev)
     seen = (deep or PositionHistory(R, moves + 1, dev)).push(search._root_hashes()) if superko else None
@@ -2894,12 +3112,14 @@ def puct_selfplay(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, 
             z = noise(mv, search._legal_roots)
             todo.fill_(1)
             search.add_root_noise(z, eps, todo)     # the roots kept from the move before
+        if draws is not None:
+            search.set_gumbel(draws(mv, search._legal_roots))
         for t in range(search._I):
             priors, values = evaluator(*search.select())
             search.backup(priors, values)
             if t == 0 and noise is not None:
                 search.add_root_noise(z, eps, todo)   # the fresh roots round 0 has just evaluated
-        acts, p, v = search._root_policy(ones if mv < sample_moves else None, rng)
+        acts, p, v = search._root_policy(ones if mv < sample_moves else None, rng) if gumbel is None else search._gumbel_root()
         played[:, mv], pis[:, mv], vals[:, mv] = acts, p, v
         lengths += (acts >= 0).to(_I32)
         search.advance(played[:, mv], check=False)
@@ -2927,7 +3147,8 @@ def puct(state, iterations, evaluator, **kw):
 
 def puct_actions(batch_states, iterations, evaluator, **kw):
     """The PUCT move of every root -> int64 [R]: the legal root child with the most visits after batch_puct(batch_states,
-    iterations, evaluator, **kw); ties go to the lowest action, a root without a legal move gives -1."""
+    iterations, evaluator, **kw); ties go to the lowest action, a root without a legal move gives -1.  With gumbel= it is the
+    Gumbel move (PuctSearch.gumbel_root): among the actions with the most simulations the largest g + logit + sigma(q), g = 0."""
     _puct_symmetry_guard(kw.get('symmetry'), kw.get('features'))
     _puct_life_guard(kw.get('life', False), kw.get('features'))
     _puct_ladder_guard(kw.get('ladder', False), kw.get('features'))
@@ -2935,6 +3156,10 @@ def puct_actions(batch_states, iterations, evaluator, **kw):
     _puct_area_guard(kw.get('area', False), kw.get('features'))
     _puct_past_guard(kw.get('past'), kw.get('features'))
     box = _Box(batch_states)
+    if kw.get('gumbel') is not None:
+        kw.pop('tree', None)
+        search = _puct_searched(box.t, iterations, evaluator, **kw)
+        return _back(box, search._gumbel_root(pi=False)[0].to(_I64))
     res = batch_puct(box.t, iterations, evaluator, **kw)
     return _best_legal(box, res.legal, res.visits.to(_I64))
 
