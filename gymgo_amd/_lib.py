@@ -6,7 +6,8 @@ memory and the current HIP stream; every entry point of include/gymgo_amd.h is b
 pointers, from ONE table (ABI) that tests/test_host_abi.py holds against the header, and reached through
 call().  A new entry point is one declaration in the header and one entry in the table.  The area family has a header of
 its own, include/gymgo_amd_area.h, and a table of its own, ABI_AREA, bound and called the same way; so have the past family
-(include/gymgo_amd_past.h, ABI_PAST) and the Gumbel root rule of the PUCT search (include/gymgo_amd_gumbel.h, ABI_GUMBEL).
+(include/gymgo_amd_past.h, ABI_PAST), the Gumbel root rule of the PUCT search (include/gymgo_amd_gumbel.h, ABI_GUMBEL) and the
+tactical playout policy with its planes (include/gymgo_amd_tactics.h, ABI_TACTICS).
 """
 import collections
 import ctypes
@@ -199,19 +200,31 @@ ABI_GUMBEL = {
                        + _params(_f64, 'c_visit', 'c_scale') + _params(_I32, 'actions') + _params(_F32, 'q') + _params(_I32, 'visits')
                        + _params(_F32, 'value') + _STREAM),
 }
+# ... and of include/gymgo_amd_tactics.h, the tactical playout policy's header, in its order (tests/test_tactics_host.py holds it
+# against its header): the planes, and the three _policy calls of ABI under the names that accept GG_POLICY_TACTICAL too
+ABI_TACTICS = {
+    'gg_tactics_planes': (),
+    'gg_batch_tactics': _params(_U8, 'states') + _params(_I32, 'orient') + _OUT + _OUT_BN,
+    'gg_batch_tactics_tracked': _params(_I32, 'tracked', 'orient') + _OUT + _OUT_BN,
+    'gg_batch_rollout_tracked_policy2': ABI['gg_batch_rollout_tracked_policy'],
+    'gg_playouts_advance_policy2': ABI['gg_playouts_advance_policy'],
+    'gg_move_playouts_advance_policy2': ABI['gg_move_playouts_advance_policy'],
+}
 EXPORTS = tuple(ABI)
 EXPORTS_AREA = tuple(ABI_AREA)
 EXPORTS_PAST = tuple(ABI_PAST)
 EXPORTS_GUMBEL = tuple(ABI_GUMBEL)
+EXPORTS_TACTICS = tuple(ABI_TACTICS)
 _signatures = lambda table: {f: ([p.kind if isinstance(p.kind, type) else _vp for p in ps], _i32) for f, ps in table.items()}
 _SIGNATURES = _signatures(ABI)   # argtypes, restype
 _SIGNATURES_AREA = _signatures(ABI_AREA)
 _SIGNATURES_PAST = _signatures(ABI_PAST)
 _SIGNATURES_GUMBEL = _signatures(ABI_GUMBEL)
+_SIGNATURES_TACTICS = _signatures(ABI_TACTICS)
 # call(): the number of parameters and (index, dtypes, name) of every pointer to device memory
 _POINTERS = {f: (len(ps), tuple((i, p.kind if isinstance(p.kind, tuple) else (p.kind,), p.name)
                                 for i, p in enumerate(ps) if not isinstance(p.kind, type)))
-             for table in (ABI, ABI_AREA, ABI_PAST, ABI_GUMBEL) for f, ps in table.items()}
+             for table in (ABI, ABI_AREA, ABI_PAST, ABI_GUMBEL, ABI_TACTICS) for f, ps in table.items()}
 
 _lib = None
 
@@ -225,7 +238,8 @@ def build(force=False):
     import subprocess
     csrc = os.path.join(_HERE, 'csrc')
     srcs = [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(('.hip', '.h'))]
-    srcs += [os.path.join(os.path.dirname(_HERE), 'include', h) for h in ('gymgo_amd.h', 'gymgo_amd_area.h', 'gymgo_amd_past.h', 'gymgo_amd_gumbel.h')]
+    srcs += [os.path.join(os.path.dirname(_HERE), 'include', h) for h in ('gymgo_amd.h', 'gymgo_amd_area.h', 'gymgo_amd_past.h', 'gymgo_amd_gumbel.h',
+                                                                                  'gymgo_amd_tactics.h')]
     stale = not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < max(os.path.getmtime(f) for f in srcs)
     if force or stale:
         subprocess.check_call(['make', '-C', os.path.join(_HERE, 'csrc'), '-s', '-B', '-j3'])
@@ -241,7 +255,7 @@ def lib():
                 'gymgo_amd has no CPU fallback' % LIB_PATH)
         L = ctypes.CDLL(LIB_PATH)
         for name, (argtypes, restype) in (list(_SIGNATURES.items()) + list(_SIGNATURES_AREA.items()) + list(_SIGNATURES_PAST.items())
-                                          + list(_SIGNATURES_GUMBEL.items())):
+                                          + list(_SIGNATURES_GUMBEL.items()) + list(_SIGNATURES_TACTICS.items())):
             fn = getattr(L, name)  # AttributeError if the .so does not export what the header declares
             fn.argtypes, fn.restype = argtypes, restype
         if L.gg_version() != ABI_VERSION:
@@ -390,7 +404,7 @@ def ptrs(fn, **tensors):
     """dev_ptr of every tensor as the parameter of entry point `fn` it is named after - dtype(s) from the table -, in the order
     given: for the paths that check their buffers once and hand call() the pointers from then on."""
     kinds = {p.name: p.kind for p in (ABI[fn] if fn in ABI else ABI_AREA[fn] if fn in ABI_AREA else ABI_PAST[fn] if fn in ABI_PAST
-                                      else ABI_GUMBEL[fn])}
+                                      else ABI_GUMBEL[fn] if fn in ABI_GUMBEL else ABI_TACTICS[fn])}
     return tuple(dev_ptr(t, kinds[n], n) for n, t in tensors.items())
 
 

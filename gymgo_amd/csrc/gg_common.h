@@ -65,7 +65,7 @@ __device__ __forceinline__ uint32_t dpp0(uint32_t v) {
 }
 
 // Playout policies of the tracked multi-ply kernels (include/gymgo_amd.h: GG_POLICY_*)
-constexpr int kPolUniform = 0, kPolNoEyeFill = 1;
+constexpr int kPolUniform = 0, kPolNoEyeFill = 1, kPolTactical = 2;
 
 // One row of the MOVER'S EYES: an empty point whose on-board orthogonal neighbours are all the mover's stones and
 // whose on-board diagonal neighbours hold at most one opponent stone - none when the point lies on the first / last row or
@@ -82,6 +82,25 @@ __device__ __forceinline__ uint32_t eye_row(uint32_t me, uint32_t op, uint32_t m
   const uint32_t bad = B3(edge, any3 | d, two, T_SEL);
   const uint32_t empty = B3(full, me, op, TA & ~(TB | TC) & 0xFF);
   return B3(empty, orth, bad, T_AND_ANDN);
+}
+
+// One row of the CAPTURE and the ESCAPE points of the tactical policy (include/gymgo_amd_tactics.h holds the rule),
+// before the valid points are applied: C = the points orthogonally next to an opponent stone outside M (its group has one
+// liberty, so an empty point there is that liberty), E = the points next to a mover's stone outside M that have at least two
+// empty orthogonal neighbours.  me / op / M = the row's stones and its stones of groups with >= 2 liberties; meU / meD / opU /
+// opD / MU / MD = the rows above / below, where OFF THE BOARD meU / meD and MU / MD are all ones and opU / opD zero: the border
+// is a mover's stone inside M - never empty, never in atari; left and right the shifts bring zeros in, which is the same.
+// The caller masks both rows with the valid points (a subset of the empty points of the board's columns).
+__device__ __forceinline__ void tactical_rows(uint32_t me, uint32_t op, uint32_t M, uint32_t meU, uint32_t meD, uint32_t opU,
+                                              uint32_t opD, uint32_t MU, uint32_t MD, uint32_t full, uint32_t &C, uint32_t &E) {
+  const uint32_t lo = op & ~M, lm = me & ~M;                                         // the row's stones in atari
+  C = B3(shl1(lo), lo >> 1, opU & ~MU, T_OR3) | (opD & ~MD);
+  const uint32_t nm = B3(shl1(lm), lm >> 1, meU & ~MU, T_OR3) | (meD & ~MD);
+  const uint32_t e = B3(full, me, op, TA & ~(TB | TC) & 0xFF);
+  const uint32_t a = shl1(e), b = e >> 1;                                            // the four neighbours, empty or not
+  const uint32_t c = B3(full, meU, opU, TA & ~(TB | TC) & 0xFF), d = B3(full, meD, opD, TA & ~(TB | TC) & 0xFF);
+  const uint32_t any3 = B3(a, b, c, T_OR3), maj = B3(a, b, c, T_MAJ);
+  E = nm & B3(d, any3, maj, T_ANDOR);                                                // at least two of the four
 }
 
 // OR-accumulation of a compile-time-indexed series of terms, two per v_bitop3_b32: `acc |= a; acc |= b` is fused by the compiler

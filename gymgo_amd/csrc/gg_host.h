@@ -54,12 +54,12 @@ void launch_rollout4(int io, uint8_t *st, uint64_t *rng, int32_t *last_actions, 
 void launch_rollout5(int io, int N, uint8_t *st, uint64_t *rng, int32_t *last_actions, int64_t *steps_done, int64_t B, uint32_t inv,
                      int plies, int auto_reset, int nb, int grid, hipStream_t s, uint32_t *ws);
 void launch_rollout5_policy(int N, uint8_t *st, uint64_t *rng, int32_t *last_actions, int64_t *steps_done, int64_t B, uint32_t inv,
-                            int plies, int auto_reset, int nb, int grid, hipStream_t s);
+                            int plies, int auto_reset, int policy, int nb, int grid, hipStream_t s);
 // gg_lat.hip: the one-row-per-lane kernel, io 0 or 2; w4 (tracked boards only): four waves per workgroup
 void launch_rollout_lat(int io, uint8_t *st, uint64_t *rng, int32_t *last_actions, int64_t *steps_done, int64_t B, int32_t N, int plies,
                         int auto_reset, bool w4, hipStream_t s);
 void launch_rollout_lat_policy(uint8_t *st, uint64_t *rng, int32_t *last_actions, int64_t *steps_done, int64_t B, int32_t N, int plies,
-                               int auto_reset, hipStream_t s);
+                               int auto_reset, int policy, hipStream_t s);
 void launch_env_step_lat(uint32_t *tracked, uint64_t *rng, int64_t *steps_done, int64_t B, int32_t N, int auto_reset,
                          const EnvArgs &env, bool w4, hipStream_t s);
 

@@ -36,6 +36,7 @@
 #include "gg_uct.h"
 #include "gg_puct.h"
 #include "gymgo_amd.h"
+#include "gymgo_amd_tactics.h"
 
 namespace {
 
@@ -413,7 +414,7 @@ static void launch_harvest(const Args &a, int32_t N, int cus, hipStream_t s) {
   by_size(N, [&](auto t) { k_po_harvest<decltype(t)::R, decltype(t)::FULL, FILL, Args><<<grid, kWave, 0, s>>>(a, N); });
 }
 
-static bool policy_ok(int32_t policy) { return policy == GG_POLICY_UNIFORM || policy == GG_POLICY_NO_EYE_FILL; }
+static bool policy_ok(int32_t policy, int32_t max_policy) { return policy >= GG_POLICY_UNIFORM && policy <= max_policy; }
 
 // begin: zero the `cells` result cells (R, or R A), fill the slots with the first jobs
 template <class Args>
@@ -434,15 +435,16 @@ static int32_t po_begin(const Args &a, int64_t cells, int32_t N, void *hip_strea
 // advance: `chunks` times chunk_plies plies on every slot, then the harvest (refills, and in the first-move family the first
 // moves, happen there, between launches)
 template <class Args>
-static int32_t po_advance(const Args &a, int32_t N, int32_t chunk_plies, int32_t chunks, int32_t policy, void *hip_stream) {
-  if (chunks < 0 || !policy_ok(policy)) return GG_E_BADARG;
+static int32_t po_advance(const Args &a, int32_t N, int32_t chunk_plies, int32_t chunks, int32_t policy, int32_t max_policy,
+                          void *hip_stream) {
+  if (chunks < 0 || !policy_ok(policy, max_policy)) return GG_E_BADARG;
   if (a.J == 0 || chunks == 0) return 0;
   OnDeviceOf on_dev(a.slots);
   const int cus = on_dev.cus();
   hipStream_t s = (hipStream_t)hip_stream;
   for (int c = 0; c < chunks; ++c) {
     // the existing tracked dispatch, auto_reset = 0: finished and empty slots stay frozen
-    if (int32_t e = gg_batch_rollout_tracked_policy(a.slots, a.rng, nullptr, a.plies, a.S, N, chunk_plies, 0, policy, hip_stream)) return e;
+    if (int32_t e = gg_batch_rollout_tracked_policy2(a.slots, a.rng, nullptr, a.plies, a.S, N, chunk_plies, 0, policy, hip_stream)) return e;
     launch_harvest<false>(a, N, cus, s);
     if (int32_t e = (int32_t)hipGetLastError()) return e;
   }
@@ -992,21 +994,34 @@ int32_t gg_batch_rollout_tracked(uint32_t *tracked, uint64_t *rng, int32_t *last
 // The draw under a playout policy lives in the two families the playout queue runs on: k_rollout_lat where the
 // uniform path takes it, k_rollout5 where the uniform path takes it, and k_rollout_lat again - its plain form serves every batch
 // size and launch length - in the band that the uniform path gives to k_rollout4, which has no policy draw.
-int32_t gg_batch_rollout_tracked_policy(uint32_t *tracked, uint64_t *rng, int32_t *last_actions, int64_t *steps_done, int64_t B,
-                                        int32_t N, int32_t plies, int32_t auto_reset, int32_t policy, void *hip_stream) {
+// max_policy: the last policy the entry point accepts (GG_POLICY_NO_EYE_FILL: the _policy calls; GG_POLICY_TACTICAL: _policy2)
+static int32_t rollout_tracked_policy(uint32_t *tracked, uint64_t *rng, int32_t *last_actions, int64_t *steps_done, int64_t B, int32_t N,
+                                      int32_t plies, int32_t auto_reset, int32_t policy, int32_t max_policy, void *hip_stream) {
   if (policy == GG_POLICY_UNIFORM) return gg_batch_rollout_tracked(tracked, rng, last_actions, steps_done, B, N, plies, auto_reset, hip_stream);
-  if (plies < 0 || policy != GG_POLICY_NO_EYE_FILL) return GG_E_BADARG;
+  if (plies < 0 || policy < GG_POLICY_NO_EYE_FILL || policy > max_policy) return GG_E_BADARG;
   GG_ENTER(tracked);
   if (plies == 0) return 0;
   if (!rng) return GG_E_NULLPTR;
   uint8_t *st = reinterpret_cast<uint8_t *>(tracked);
   if (!use_lat(cus, B, N, plies, true) && use_rollout5(cus, B, N, plies)) {
     const WaveGrid w5 = boards_per_wave5(cus, B);
-    launch_rollout5_policy(N, st, rng, last_actions, steps_done, B, inv, plies, auto_reset, w5.nb, w5.grid, s);
+    launch_rollout5_policy(N, st, rng, last_actions, steps_done, B, inv, plies, auto_reset, policy, w5.nb, w5.grid, s);
     return (int32_t)hipGetLastError();
   }
-  launch_rollout_lat_policy(st, rng, last_actions, steps_done, B, N, plies, auto_reset, s);
+  launch_rollout_lat_policy(st, rng, last_actions, steps_done, B, N, plies, auto_reset, policy, s);
   return (int32_t)hipGetLastError();
+}
+
+int32_t gg_batch_rollout_tracked_policy(uint32_t *tracked, uint64_t *rng, int32_t *last_actions, int64_t *steps_done, int64_t B,
+                                        int32_t N, int32_t plies, int32_t auto_reset, int32_t policy, void *hip_stream) {
+  return rollout_tracked_policy(tracked, rng, last_actions, steps_done, B, N, plies, auto_reset, policy, GG_POLICY_NO_EYE_FILL, hip_stream);
+}
+
+// The _policy2 entry points (include/gymgo_amd_tactics.h): the parameter lists and the checks of their namesakes,
+// GG_POLICY_TACTICAL accepted as well.
+int32_t gg_batch_rollout_tracked_policy2(uint32_t *tracked, uint64_t *rng, int32_t *last_actions, int64_t *steps_done, int64_t B,
+                                         int32_t N, int32_t plies, int32_t auto_reset, int32_t policy, void *hip_stream) {
+  return rollout_tracked_policy(tracked, rng, last_actions, steps_done, B, N, plies, auto_reset, policy, GG_POLICY_TACTICAL, hip_stream);
 }
 
 int32_t gg_batch_eye_mask(const uint8_t *states, uint8_t *mask, int64_t B, int32_t N, void *hip_stream) {
@@ -1180,7 +1195,18 @@ int32_t gg_playouts_advance_policy(const uint32_t *roots, int64_t R, int32_t N, 
   if (int32_t e = po_args(a, 1, R, true, true, roots, R, N, K, first_root, base_seed, max_plies, chunk_plies, komi, slots, rng, plies,
                           job, S, counter, counts, sums, ownership))
     return e;
-  return po_advance(a, N, chunk_plies, chunks, policy, hip_stream);
+  return po_advance(a, N, chunk_plies, chunks, policy, GG_POLICY_NO_EYE_FILL, hip_stream);
+}
+
+int32_t gg_playouts_advance_policy2(const uint32_t *roots, int64_t R, int32_t N, int32_t K, int64_t first_root, uint64_t base_seed,
+                                    int32_t max_plies, int32_t chunk_plies, float komi, int32_t chunks, int32_t policy,
+                                    uint32_t *slots, uint64_t *rng, int64_t *plies, int64_t *job, int64_t S, int64_t *counter,
+                                    int32_t *counts, int64_t *sums, int32_t *ownership, void *hip_stream) {
+  PoArgs a;
+  if (int32_t e = po_args(a, 1, R, true, true, roots, R, N, K, first_root, base_seed, max_plies, chunk_plies, komi, slots, rng, plies,
+                          job, S, counter, counts, sums, ownership))
+    return e;
+  return po_advance(a, N, chunk_plies, chunks, policy, GG_POLICY_TACTICAL, hip_stream);
 }
 
 int32_t gg_move_playouts_plan(const uint32_t *roots, int64_t R, int32_t N, int32_t *offsets, int32_t *plan, void *hip_stream) {
@@ -1225,7 +1251,19 @@ int32_t gg_move_playouts_advance_policy(const uint32_t *roots, int64_t R, int32_
   if (int32_t e = mp_args(m, roots, R, N, plan, T, K, first_root, base_seed, max_plies, chunk_plies, komi, slots, rng, plies, job,
                           S, counter, counts, sums))
     return e;
-  return po_advance(m, N, chunk_plies, chunks, policy, hip_stream);
+  return po_advance(m, N, chunk_plies, chunks, policy, GG_POLICY_NO_EYE_FILL, hip_stream);
+}
+
+int32_t gg_move_playouts_advance_policy2(const uint32_t *roots, int64_t R, int32_t N, const int32_t *plan, int64_t T, int32_t K,
+                                         int64_t first_root, uint64_t base_seed, int32_t max_plies, int32_t chunk_plies,
+                                         float komi, int32_t chunks, int32_t policy, uint32_t *slots, uint64_t *rng,
+                                         int64_t *plies, int64_t *job, int64_t S, int64_t *counter, int32_t *counts,
+                                         int64_t *sums, void *hip_stream) {
+  MpArgs m;
+  if (int32_t e = mp_args(m, roots, R, N, plan, T, K, first_root, base_seed, max_plies, chunk_plies, komi, slots, rng, plies, job,
+                          S, counter, counts, sums))
+    return e;
+  return po_advance(m, N, chunk_plies, chunks, policy, GG_POLICY_TACTICAL, hip_stream);
 }
 
 int32_t gg_uct_begin(const uint32_t *roots, int64_t R, int32_t N, int32_t I, int32_t K, uint32_t *boards, int32_t *child,

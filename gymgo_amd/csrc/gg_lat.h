@@ -538,7 +538,7 @@ struct LdsLat {
 // also pays for every instruction-cache line it has to jump to (3.19 us per hipGraph node at config 2's size against 3.36)
 // WPB: waves per workgroup, each wave an independent group of boards (a launch of single-wave workgroups enters the machine over
 // ~0.26 ns per workgroup - tools/exp/oneply_ramp.py - which a ONE-ply launch of a thousand workgroups feels: k_rollout_lat_w4)
-// POL: the playout policy of the draw (kPolUniform; kPolNoEyeFill: tracked boards, the plain form - DESIGN 15)
+// POL: the playout policy of the draw (kPolUniform; kPolNoEyeFill, kPolTactical: tracked boards, the plain form - DESIGN 15, 34)
 template <int R, bool FULLN, bool AUTO, int IO, int WPB, bool SHORT, int POL = kPolUniform>
 __device__ __forceinline__ void rollout_lat_body(uint8_t *__restrict__ states, uint64_t *__restrict__ rng,
                                                  int32_t *__restrict__ last_actions,
@@ -668,15 +668,45 @@ __device__ __forceinline__ void rollout_lat_body(uint8_t *__restrict__ states, u
         const uint32_t edge = (top || bot) ? full : (1u | (1u << (N - 1)));
         valid &= ~eye_row(me, op, meU, meD, aboveO, belowO, full, edge, N);
       }
-      const uint32_t cnt = (uint32_t)__popc(valid);
-      const uint32_t incl = lat_board_scan<LPB>(cnt);
-      const uint32_t total = lat_board_sum<LPB>(cnt);
-      const uint32_t k = __umulhi(uh, POL == kPolNoEyeFill ? total : total + 1u);
+      uint32_t cnt, incl, total;
+      if constexpr (POL == kPolTactical) {
+        // tactical: the capture points C, else the escape points E, when the gate of this ply's draw is open and the
+        // set is not empty, else the candidates F of no_eye_fill.  "In atari" is stones & ~M, the rows above / below are the
+        // neighbouring lanes as for the eyes (six DPP moves, in every lane, outside any select: see above); the border is a
+        // mover's stone inside M.  The three per-lane counts (<= 361 on a board: ten bits each) travel in ONE word through one
+        // scan and one sum; the tier is the same in every lane of the board, the k-th-bit search runs on the chosen row.
+        const bool top = r == 0, bot = r == N - 1;
+        const uint32_t aboveM = lat_above<LPB>(me), belowM = lat_below<LPB>(me);
+        const uint32_t aboveO = lat_above<LPB>(op), belowO = lat_below<LPB>(op);
+        const uint32_t aboveC = lat_above<LPB>(M), belowC = lat_below<LPB>(M);
+        const uint32_t tf = top ? full : 0u, bf = bot ? full : 0u;
+        const uint32_t meU = aboveM | tf, meD = belowM | bf;
+        const uint32_t edge = (top || bot) ? full : (1u | (1u << (N - 1)));
+        uint32_t Cr, Er;
+        tactical_rows(me, op, M, meU, meD, aboveO, belowO, aboveC | tf, belowC | bf, full, Cr, Er);
+        Cr &= valid;
+        Er &= valid;
+        const uint32_t Fr = valid & ~eye_row(me, op, meU, meD, aboveO, belowO, full, edge, N);
+        const uint32_t w = (uint32_t)__popc(Fr) | ((uint32_t)__popc(Cr) << 10) | ((uint32_t)__popc(Er) << 20);
+        const uint32_t wi = lat_board_scan<LPB>(w), wt = lat_board_sum<LPB>(w);
+        const bool gate = (uh & 3u) != 0u;
+        const bool useC = gate && ((wt >> 10) & 0x3FFu) != 0u, useE = gate && !useC && (wt >> 20) != 0u;
+        const uint32_t sh = useC ? 10u : (useE ? 20u : 0u);
+        valid = useC ? Cr : (useE ? Er : Fr);
+        cnt = (w >> sh) & 0x3FFu;
+        incl = (wi >> sh) & 0x3FFu;
+        total = (wt >> sh) & 0x3FFu;
+      } else {
+        cnt = (uint32_t)__popc(valid);
+        incl = lat_board_scan<LPB>(cnt);
+        total = lat_board_sum<LPB>(cnt);
+      }
+      const uint32_t k = __umulhi(uh, POL != kPolUniform ? total : total + 1u);
       const uint32_t tt = k - (incl - cnt);
       const bool hit = live && tt < cnt;                 // this lane's row holds the k-th valid point
       const uint32_t pos = lat_kth_bit<L::kBits>(valid, tt);
       const uint32_t Q = hit ? (1u << pos) : 0u;
-      const bool pass = POL == kPolNoEyeFill ? total == 0u : k == total;   // (the same in every lane of the board)
+      const bool pass = POL != kPolUniform ? total == 0u : k == total;   // (the same in every lane of the board)
       {   // the action of the board's last live ply: the hit lane holds it, every lane holds a pass, the others -1
         const int cand = hit ? rN + (int)pos : (pass ? P : -1);
         lastv = (int)B3(lv, (uint32_t)cand, (uint32_t)lastv, T_SEL);

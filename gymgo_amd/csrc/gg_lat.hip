@@ -41,13 +41,14 @@ void launch_rollout_lat(int io, uint8_t *st, uint64_t *rng, int32_t *last_action
 // gg_batch_rollout_tracked_policy (policy != uniform): the plain tracked form with the policy in its draw, whatever the launch
 // length and the batch size (one wave per four / two boards)
 void launch_rollout_lat_policy(uint8_t *st, uint64_t *rng, int32_t *last_actions, int64_t *steps_done, int64_t B, int32_t N, int plies,
-                               int auto_reset, hipStream_t s) {
+                               int auto_reset, int policy, hipStream_t s) {
   by_size(N, [&](auto t) {
     by_flag(auto_reset != 0, [&](auto ar) {
       constexpr int R = decltype(t)::R;
-      constexpr bool AR = decltype(ar)::value;
+      constexpr bool F = decltype(t)::FULL, AR = decltype(ar)::value;
       const unsigned grid = (unsigned)((B + Lat<R>::NBW - 1) / Lat<R>::NBW);
-      k_rollout_lat_pol<R, decltype(t)::FULL, AR, kPolNoEyeFill><<<grid, kWave, 0, s>>>(st, rng, last_actions, steps_done, B, N, plies, (int)AR);
+      if (policy == kPolTactical) k_rollout_lat_pol<R, F, AR, kPolTactical><<<grid, kWave, 0, s>>>(st, rng, last_actions, steps_done, B, N, plies, (int)AR);
+      else k_rollout_lat_pol<R, F, AR, kPolNoEyeFill><<<grid, kWave, 0, s>>>(st, rng, last_actions, steps_done, B, N, plies, (int)AR);
     });
   });
 }

@@ -38,9 +38,11 @@ void launch_rollout5(int io, int N, uint8_t *st, uint64_t *rng, int32_t *last_ac
 
 // gg_batch_rollout_tracked_policy (policy != uniform) on a full machine: tracked boards, the policy in the draw of phase 1
 void launch_rollout5_policy(int N, uint8_t *st, uint64_t *rng, int32_t *last_actions, int64_t *steps_done, int64_t B, uint32_t inv,
-                            int plies, int auto_reset, int nb, int grid, hipStream_t s) {
+                            int plies, int auto_reset, int policy, int nb, int grid, hipStream_t s) {
   by_full_size(N, [&](auto t) {
-    k_rollout5_pol<decltype(t)::R, 2><<<grid, kWave, 0, s>>>(st, rng, last_actions, steps_done, B, inv, plies, auto_reset, nb, nullptr);
+    constexpr int R = decltype(t)::R;
+    if (policy == kPolTactical) k_rollout5_tac<R, 2><<<grid, kWave, 0, s>>>(st, rng, last_actions, steps_done, B, inv, plies, auto_reset, nb, nullptr);
+    else k_rollout5_pol<R, 2><<<grid, kWave, 0, s>>>(st, rng, last_actions, steps_done, B, inv, plies, auto_reset, nb, nullptr);
   });
 }
 

@@ -1,5 +1,5 @@
 // gg_v5_kernel.h - the body of k_rollout5 (gg_v5.h), included once per playout policy: GG_R5_NAME = the kernel's name,
-// GG_R5_POL = the policy of its draw (kPolUniform: k_rollout5; kPolNoEyeFill: k_rollout5_pol).  Textual inclusion
+// GG_R5_POL = the policy of its draw (kPolUniform: k_rollout5; kPolNoEyeFill: k_rollout5_pol; kPolTactical: k_rollout5_tac).  Textual inclusion
 // and not a shared inline body: k_rollout5 stays the kernel it was, instruction for instruction and by name (bench.py ties
 // its PMC record to the machine code behind the mangled name).  No include guard.
 // ws (byte planes only, nullable: gg_batch_rollout_ws): the caller's workspace, uint32 [B][5 N + 1] in the layout of a tracked board.
@@ -290,7 +290,8 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
         uint32_t v[RPL], p[RPL];
         const uint32_t rm = reset ? ~0u : 0u;   // a board being reset plays on the empty board
         uint32_t eye[RPL];
-        if constexpr (POL == kPolNoEyeFill) {
+        uint32_t tc[RPL], te[RPL];   // tactical: the capture and the escape points of the lane's rows
+        if constexpr (POL != kPolUniform) {
           // no_eye_fill: the mover's eyes leave the candidates.  The stone rows of the lane come out of LDS (the planes are as
           // phase 3 of the last ply - or the load - left them), the row beyond the pair's seam out of the partner lane by one
           // DPP swap per colour and side; off the board the mover's rows read as all ones and the opponent's as zero.
@@ -301,6 +302,10 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
           for (int r = 0; r < RPL; ++r) { me[r] = pm[r]; op[r] = po[r]; }   // (rows >= N are zero)
           const uint32_t me_up = dpp0<QP_X1>(me[RPL - 1]), op_up = dpp0<QP_X1>(op[RPL - 1]);   // row RPL - 1, for the odd lane
           const uint32_t me_dn = dpp0<QP_X1>(me[0]), op_dn = dpp0<QP_X1>(op[0]);               // row RPL, for the even lane
+          // tactical: M[] is in registers, its rows beyond the seam come by the same swaps; off the board M reads as all ones
+          // like the mover's rows (the border is a mover's stone with liberties: never empty, never in atari)
+          uint32_t m_up = 0u, m_dn = 0u;
+          if constexpr (POL == kPolTactical) { m_up = dpp0<QP_X1>(M[RPL - 1]); m_dn = dpp0<QP_X1>(M[0]); }
 #pragma unroll
           for (int r = 0; r < RPL; ++r) {
             const int rw = r0 + r;
@@ -309,18 +314,34 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
             const uint32_t meD = rw + 1 >= N ? FULLROW : meDn;
             const uint32_t edge = (rw == 0 || rw == N - 1) ? FULLROW : (1u | (1u << (N - 1)));
             eye[r] = eye_row(me[r], op[r], meU, meD, opU, opD, full[r], edge, N) & ~rm;
+            if constexpr (POL == kPolTactical) {
+              const uint32_t MU = r ? M[r - 1] : (t5 ? m_up : FULLROW);
+              const uint32_t MDn = r + 1 < RPL ? M[r + 1] : (t5 ? 0u : m_dn);
+              const uint32_t MD = rw + 1 >= N ? FULLROW : MDn;
+              tactical_rows(me[r], op[r], M[r], meU, meD, opU, opD, MU, MD, full[r], tc[r], te[r]);
+              tc[r] &= ~rm;   // (a board being reset: the planes and M still hold the finished game)
+              te[r] &= ~rm;
+            }
           }
         }
 #pragma unroll
         for (int r = 0; r < RPL; ++r) {
           v[r] = B3(full[r], rm, inv_r[r], TA & (TB | (~TC & 0xFF)));
-          if constexpr (POL == kPolNoEyeFill) v[r] &= ~eye[r];
-          p[r] = (uint32_t)__popc(v[r]) + (r ? p[r - 1] : 0u);
+          if constexpr (POL == kPolTactical) {
+            // the three sets of the row and their counts in ONE word: F in bits 0-9, C in 10-19, E in 20-29 (<= 361 per board)
+            tc[r] &= v[r];
+            te[r] &= v[r];
+            v[r] &= ~eye[r];
+            p[r] = ((uint32_t)__popc(v[r]) | ((uint32_t)__popc(tc[r]) << 10) | ((uint32_t)__popc(te[r]) << 20)) + (r ? p[r - 1] : 0u);
+          } else {
+            if constexpr (POL == kPolNoEyeFill) v[r] &= ~eye[r];
+            p[r] = (uint32_t)__popc(v[r]) + (r ? p[r - 1] : 0u);
+          }
         }
-        const uint32_t T = p[RPL - 1];
+        uint32_t T = p[RPL - 1];
         // valid points of the board before this lane's rows (Pb) and on the whole board (n): one swap inside the pair
         const uint32_t oth = dpp0<QP_X1>(T);
-        const uint32_t Pb = t5 ? oth : 0u, n = T + oth;
+        uint32_t Pb = t5 ? oth : 0u, n = T + oth;
         // The draws of a board, TWO plies at a time: the draw of ply t is mix(x0 + (t + 1) c) with x0 the generator the
         // launch found; lane j of the pair mixes the draw of ply t + j every second ply, a ply takes the even lane's and
         // the pair swaps
@@ -330,7 +351,23 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
         }
         const uint32_t uh = dpp0<QP_L0>(uq);
         uq = dpp0<QP_X1>(uq);
-        const uint32_t k = __umulhi(uh, POL == kPolNoEyeFill ? n : n + 1u);   // k == n: the pass (no_eye_fill: n == 0 alone)
+        if constexpr (POL == kPolTactical) {
+          // the tier: C, else E, when the gate of this draw is open and the set is not empty, else F - the same in both lanes of
+          // the pair (n holds the pair's three totals); the rows and the counts of the chosen set take the place of the valid ones
+          const bool gate = (uh & 3u) != 0u;
+          const bool useC = gate && ((n >> 10) & 0x3FFu) != 0u, useE = gate && !useC && (n >> 20) != 0u;
+          const uint32_t sh = useC ? 10u : (useE ? 20u : 0u);
+          const uint32_t mc = useC ? ~0u : 0u, me_ = useE ? ~0u : 0u;
+#pragma unroll
+          for (int r = 0; r < RPL; ++r) {
+            v[r] = B3(mc, tc[r], B3(me_, te[r], v[r], T_SEL), T_SEL);
+            p[r] = (p[r] >> sh) & 0x3FFu;
+          }
+          T = (T >> sh) & 0x3FFu;
+          Pb = (Pb >> sh) & 0x3FFu;
+          n = (n >> sh) & 0x3FFu;
+        }
+        const uint32_t k = __umulhi(uh, POL != kPolUniform ? n : n + 1u);   // k == n: the pass (a policy: n == 0 alone)
         const bool hit = k >= Pb && k < Pb + T;       // this lane holds the k-th valid point
         int rr;
         uint32_t pos;

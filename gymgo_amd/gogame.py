@@ -694,23 +694,27 @@ def batch_untrack(tracked, out=None):
 
 
 POLICIES = {'uniform': 0, 'no_eye_fill': 1}   # GG_POLICY_* of include/gymgo_amd.h
+PLAYOUT_POLICIES = {'uniform': 0, 'no_eye_fill': 1, 'tactical': 2}   # ... and GG_POLICY_TACTICAL of include/gymgo_amd_tactics.h
 
 
 def _policy_code(policy):
-    """The playout policy's C code; ValueError for anything but the names of POLICIES (checked before a device is touched)."""
-    if not any(policy is k or (type(policy) is type(k) and policy == k) for k in POLICIES):
-        raise ValueError("policy must be 'uniform' or 'no_eye_fill' (got %r)" % (policy,))
-    return POLICIES[policy]
+    """The playout policy's C code; ValueError for anything but the names of PLAYOUT_POLICIES (checked before a device is
+    touched).  Codes 0 and 1 go through the entry points of include/gymgo_amd.h, code 2 through the _policy2 ones."""
+    if not any(policy is k or (type(policy) is type(k) and policy == k) for k in PLAYOUT_POLICIES):
+        raise ValueError("policy must be 'uniform', 'no_eye_fill' or 'tactical' (got %r)" % (policy,))
+    return PLAYOUT_POLICIES[policy]
 
 
 def batch_rollout_tracked(tracked, rng, plies, auto_reset=True, last_actions=None, steps_done=None, *, policy='uniform'):
     """IN PLACE batch_rollout on tracked boards (gg_batch_rollout_tracked).  policy: 'uniform' (every legal point and the
     pass alike) or 'no_eye_fill' (the mover's eyes - batch_eye_mask - are never played, the pass only when nothing else is
-    left; gg_batch_rollout_tracked_policy)."""
+    left; gg_batch_rollout_tracked_policy) or 'tactical' (take what can be taken, pull out what is about to be taken, three plies
+    in four, else as 'no_eye_fill' - batch_tactics gives the three sets; gg_batch_rollout_tracked_policy2)."""
     pol = _policy_code(policy)
     N = _tracked_size(tracked)
     B = tracked.shape[0]
-    name, extra = ('gg_batch_rollout_tracked_policy', (pol,)) if pol else ('gg_batch_rollout_tracked', ())
+    name = 'gg_batch_rollout_tracked' + ('', '_policy', '_policy2')[pol]
+    extra = (pol,) if pol else ()
     _lib.call(name, tracked, rng, last_actions, steps_done, B, N, int(plies), int(bool(auto_reset)), *extra,
               _lib.stream_ptr(tracked.device))
     return tracked
@@ -1116,6 +1120,36 @@ def batch_area_planes_tracked(tracked, dtype=torch.uint8, out=None, orient=None,
     (gg_batch_area_tracked): bit for bit what batch_area_planes gives for batch_untrack(tracked); only the two stone row
     sets and the turn flag are read."""
     return _planes('gg_batch_area_tracked', AREA_PLANES, 1, tracked, True, dtype, out, orient, _AreaExtra(side, counts))
+
+
+# ---------------------------------------------------------------- the sets of the tactical playout policy
+TACTICS_PLANES = 3   # gg_tactics_planes() of include/gymgo_amd_tactics.h
+TACTICS_NAMES = ('capture', 'escape', 'no_eye_fill')
+
+
+def batch_tactics(batch_states, dtype=torch.uint8, out=None, orient=None):
+    """The three sets a ply of the 'tactical' playout policy draws from -> [B, 3, N, N] of `dtype` (gg_batch_tactics), each
+    value exactly 0 or 1 (TACTICS_NAMES), from the mover's view; all zero for a game that has ended.  low = the stones of
+    either colour whose group has fewer than two liberties (batch_group_liberties), valid = the points whose invalid bit is clear:
+       0  capture      C: valid points orthogonally next to an opponent stone in low - the move takes that group
+       1  escape       E: valid points next to a mover's stone in low with at least two empty orthogonal neighbours
+       2  no_eye_fill  F: valid points that are not eyes of the mover (batch_eye_mask): the candidates of 'no_eye_fill'
+    The ply: with u the high 32 bits of its draw and the gate open when (u & 3) != 0, it draws from C if the gate is open and
+    C is not empty, else from E if the gate is open and E is not empty, else from F; the pass when the set is empty (F only).
+    dtype, out, orient and NumPy input: as batch_area_planes.  One launch; device memory of the result: 3 * B * N^2 elements."""
+    return _planes('gg_batch_tactics', TACTICS_PLANES, 1, batch_states, False, dtype, out, orient, _NO_BYTES)
+
+
+def tactics(state, dtype=torch.uint8):
+    """batch_tactics of one state [6, N, N] -> [3, N, N]."""
+    return _plane_single(batch_tactics, state, dtype)
+
+
+def batch_tactics_tracked(tracked, dtype=torch.uint8, out=None, orient=None):
+    """batch_tactics of tracked boards (int32 [B, 5N+1], a device tensor) -> [B, 3, N, N] of `dtype`
+    (gg_batch_tactics_tracked): bit for bit what batch_tactics gives for batch_untrack(tracked); every group is counted from
+    the stones, the class rows are not read."""
+    return _planes('gg_batch_tactics_tracked', TACTICS_PLANES, 1, tracked, True, dtype, out, orient, _NO_BYTES)
 
 
 def batch_ownership(batch_states, side=None, orient=None):
@@ -1647,10 +1681,10 @@ def _drive_playouts(advance, counter, J, S, max_plies, chunk_plies, dev, what):
 
 
 def _run_queue(family, what, head, komi, bufs, counter, J, S, max_plies, chunk_plies, dev, policy=0):
-    """gg_<family>_begin, then gg_<family>_advance_policy until the counter drains (_drive_playouts).  head: the arguments up
-    to chunk_plies, bufs: those from slots on (_queue_args, and what the family adds); advance takes komi, the chunk count
-    and the playout policy's code between the two."""
-    begin, advance = 'gg_%s_begin' % family, 'gg_%s_advance_policy' % family
+    """gg_<family>_begin, then gg_<family>_advance_policy (_policy2 for a policy beyond no_eye_fill) until the counter drains
+    (_drive_playouts).  head: the arguments up to chunk_plies, bufs: those from slots on (_queue_args, and what the family
+    adds); advance takes komi, the chunk count and the playout policy's code between the two."""
+    begin, advance = 'gg_%s_begin' % family, 'gg_%s_advance_policy%s' % (family, '2' if int(policy) > 1 else '')
     stream = _lib.current_raw_stream(dev)   # torch's current stream: the counter copies of _drive_playouts go there too
     _lib.call(begin, *head, *bufs, stream)
     _drive_playouts(lambda n: _lib.call(advance, *head, float(komi), n, int(policy), *bufs, stream),
@@ -1751,7 +1785,8 @@ def batch_playouts(batch_states, playouts, max_plies=None, komi=0.0, seed=202609
     `slots` (working boards, default: enough to fill the device) or `chunk_plies` (plies per rollout launch between two
     harvests; max_plies must be a multiple of it), and shards by first_root concatenate to the whole.  Default max_plies:
     8 N^2 rounded up to a multiple of chunk_plies.  The roots are not modified.
-    policy: what a playout ply draws from - 'uniform' (batch_rollout's sampler) or 'no_eye_fill' (batch_rollout_tracked)."""
+    policy: what a playout ply draws from - 'uniform' (batch_rollout's sampler), 'no_eye_fill' or 'tactical'
+    (batch_rollout_tracked)."""
     pol = _policy_code(policy)
     box = _Box(batch_states)
     st = box.t
