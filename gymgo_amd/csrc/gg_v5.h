@@ -59,6 +59,10 @@ struct Lds5 {
   static constexpr int kG = kJob + kJobCap + 4;                  // [kNB5][2][RS]: G, the collected opponent groups
   static constexpr int kSc = kG + 2 * kNB5 * RS;                 // [kWave][RS]
   static constexpr int kLoopEnd = kSc + kWave * RS;
+  // (-DGG_AB_FLAT1=1) the meta words - flags, last action, played - of a board that does not move are stored into the words of kCls
+  // behind the boards' info words, which nothing else uses: laid out as kMeta's first three rows, never read
+  static constexpr int kDumpMeta = kCls + kNB5;
+  static_assert(kNB5 + 3 * kNB5 <= kJobCap, "the dump words end in front of the slot of an absent job");
   // load: the v2 analysis in its compact form (region 0 only); tracked boards: the DMA landing area, the parked rows
   static constexpr int kV2 = kUnion;
   static constexpr int kIoEnd = kV2 + (Lds2<R>::kRegion0 > 768 ? Lds2<R>::kRegion0 : 768);
@@ -179,6 +183,44 @@ static __device__ unsigned long long gg_sweeps5[10];
 #define GG_AB_MOVE_RC 1
 #endif
 
+// A/B switches of round 27, the per-ply bookkeeping of the main path (gg_v5_kernel.h, flood_jobs below; docs/history/r27.md; 0 = round
+// 20's code, line for line).  Shipped: all four together, +3.2 % and +3.7 % on the headline launch in two alternations, every run above
+// every run of the parent; singly each is inside the parent's spread, and leaving one out of the four costs 0.8 % to 2.0 % on the medians.
+// GG_AB_LANE1 1: the lane number and everything that depends on it alone - board, lane of the pair, first row, the lane-dependent row
+//   of full[], the LDS addresses of the board's planes, blocks, info and meta words and of the job lane's seed block - are formed once
+//   in front of the ply loop; the plane of the mover is a select between two kept addresses, not a multiply.  19x19 only (187 -> 202 of
+//   the 256 VGPRs two waves per SIMD allow; 13x13 and 9x9 have no register to spare for it), 0: a fresh v_mbcnt every ply and every
+//   address re-derived from it;
+// GG_AB_BALLOT1 1: the hot wave-wide tests are ONE compare of masked words, whose lane mask is the test's result, 0: a bool put
+//   together from several tests, which the compiler materialises as v_cndmask 0 / 1 and compares with zero again (two VALU and one more
+//   VALU -> SALU dependency per test; __builtin_amdgcn_ballot_w64 of such a bool compiles to the same pair);
+// GG_AB_FLAT1 1: the small stores of the main path run under the full exec mask - both lanes of a pair clear the board's info word,
+//   phase 1 ORs the new stone (or zero) into the mover's plane and into the cleared G block, phase 3 stores the board's meta words
+//   through an address that is the board's or, for a board that does not move, a dump word's (Lds5::kDumpMeta); the hand-over forms
+//   its block offset and info word by selects in front of its one region.  19x19 only (at 13x13 and 9x9 it costs the byte-plane kernels
+//   the two VGPRs they stand below three and four waves per SIMD), 0: one exec region per store;
+// GG_AB_TURN1 1: the first visit of a sweep of flood_jobs directly behind the opposite sweep - the row that sweep has just run-filled
+//   in both directions, no vertical input - is the bit-order flip alone (one v_bfrev instead of the visit's six), 0: the full visit.
+// GG_AB_PRIO_HAND (round 19's switch) on top of the four: -0.6 % on the median, stays 0.
+#ifndef GG_AB_LANE1
+#define GG_AB_LANE1 1
+#endif
+#ifndef GG_AB_BALLOT1
+#define GG_AB_BALLOT1 1
+#endif
+#ifndef GG_AB_FLAT1
+#define GG_AB_FLAT1 1
+#endif
+#ifndef GG_AB_TURN1
+#define GG_AB_TURN1 1
+#endif
+#if GG_AB_BALLOT1
+// (used where a board size R is in scope; 13x13 and 9x9 keep __ballot and with it round 20's machine code)
+#define GG_BALLOT5(p) (R == 19 ? (unsigned long long)__builtin_amdgcn_ballot_w64(p) : __ballot(p))
+#else
+#define GG_BALLOT5(p) __ballot(p)
+#endif
+
 // liberties (dilate & empty) of the group gt[], SATURATED: min(count, 2) - all any caller uses; m[] = the rows of its colour,
 // ot[] = the other colour's rows (read from LDS together with m[], BEFORE the flood: read behind it they cost the lane a round
 // trip).  Nothing is counted: o = the OR of the liberty rows, S = their integer SUM (R rows below 2^R: no carry leaves the
@@ -256,7 +298,7 @@ __device__ __forceinline__ void flood_jobs_restart(const uint32_t (&m)[R], const
       }
       if (!WEAK && ((R - 1) & 1)) op |= pend;
       open = op;
-      if (__ballot((WEAK ? opw : op) != 0 && need) == 0) { sweeps = 2 * it + 1; break; }
+      if (GG_BALLOT5((WEAK ? opw : op) != 0 && need) == 0) { sweeps = 2 * it + 1; break; }
     }
 #pragma unroll
     for (int r = R - 1; r >= 0; --r) FLOOD_VISIT(r, r + 1, ((r + 1) & 1) != 0);  // up: domain ((r+1)&1) -> (r&1)
@@ -275,7 +317,7 @@ __device__ __forceinline__ void flood_jobs_restart(const uint32_t (&m)[R], const
       }
       if (!WEAK && ((R - 1) & 1)) op |= pend;
       open = op;
-      if (__ballot((WEAK ? opw : op) != 0 && need) == 0) { sweeps = 2 * it + 2; break; }
+      if (GG_BALLOT5((WEAK ? opw : op) != 0 && need) == 0) { sweeps = 2 * it + 2; break; }
     }
   }
   (void)sweeps;
@@ -316,25 +358,45 @@ __device__ __forceinline__ uint32_t flood_jobs(const uint32_t (&m)[R], const uin
 #define GG_SW5_SWEEP() ((void)0)
 #endif
   // after a test (op / opw = where this lane is open / weakly open): is the batch done?
+#if GG_AB_BALLOT1
+  // (once per batch: the tests AND words and their one compare is the mask; through an empty asm, or the compiler turns the AND of a
+  // mask word back into the AND of two tests)
+  uint32_t gm = isG ? ~0u : 0u, hm = have ? ~0u : 0u;
+  asm volatile("" : "+v"(gm), "+v"(hm));
+#endif
   auto done = [&](uint32_t op, uint32_t opw) -> bool {
-    if (!resumed && __ballot(opw != 0u && isG) != 0) return false;
+#if GG_AB_BALLOT1
+    if (!resumed && GG_BALLOT5((opw & gm) != 0u) != 0) return false;
+    cnt = job_liberties<R>(res, ot, m);
+    // (cnt <= 2: cnt - 2 is negative iff cnt < 2)
+    const bool unsettled = B3(op, hm, (uint32_t)((int32_t)(cnt - 2u) >> 31), TA & TB & TC) != 0u;
+#else
+    if (!resumed && GG_BALLOT5(opw != 0u && isG) != 0) return false;
     cnt = job_liberties<R>(res, ot, m);
     const bool unsettled = have && op != 0u && cnt < 2u;
-    const uint64_t u = __ballot(unsettled);
+#endif
+    const uint64_t u = GG_BALLOT5(unsettled);
 #ifdef GG_AB_SWEEPS
-    if (!resumed) { sw0_ = sw_; ng_ = (uint32_t)__popcll(__ballot(unsettled && isG)); no_ = (uint32_t)__popcll(u) - ng_; }
+    if (!resumed) { sw0_ = sw_; ng_ = (uint32_t)__popcll(GG_BALLOT5(unsettled && isG)); no_ = (uint32_t)__popcll(u) - ng_; }
 #endif
     resumed = true;
     return u == 0;
   };
-  auto sweep_down = [&]() {   // domain (r&1) -> ((r+1)&1)
+  // turn (-DGG_AB_TURN1=1): the sweep comes directly behind the opposite one, whose last visit left this sweep's first row run-filled
+  // in both directions - the fill of a row is whole runs of m[] there - and in the bit order that visit ends in.  The first visit has
+  // no vertical input (NB is off the board), its two carry fills add nothing to whole runs, and what is left of it is the flip.
+  auto sweep_down = [&](bool turn) {   // domain (r&1) -> ((r+1)&1)
+    if (turn) f[0] = __brev(f[0]);
 #pragma unroll
-    for (int r = 0; r < R; ++r) FLOOD_VISIT(r, r - 1, (r & 1) != 0);
+    for (int r = 0; r < R; ++r)
+      if (!(turn && r == 0)) FLOOD_VISIT(r, r - 1, (r & 1) != 0);
     GG_SW5_SWEEP();
   };
-  auto sweep_up = [&]() {     // domain ((r+1)&1) -> (r&1)
+  auto sweep_up = [&](bool turn) {     // domain ((r+1)&1) -> (r&1)
+    if (turn) f[R - 1] = __brev(f[R - 1]);
 #pragma unroll
-    for (int r = R - 1; r >= 0; --r) FLOOD_VISIT(r, r + 1, ((r + 1) & 1) != 0);
+    for (int r = R - 1; r >= 0; --r)
+      if (!(turn && r == R - 1)) FLOOD_VISIT(r, r + 1, ((r + 1) & 1) != 0);
     GG_SW5_SWEEP();
   };
   // the test after a down sweep (is the fill closed UPWARDS?) and after an up sweep (downwards), with what follows it
@@ -373,17 +435,18 @@ __device__ __forceinline__ uint32_t flood_jobs(const uint32_t (&m)[R], const uin
   // the loop itself would have them there; from then on every sweep has its test.
   constexpr bool PEEL = GG_AB_PEEL != 0 && K == 2;
   bool fin = false;
+  constexpr bool TURN = GG_AB_TURN1 != 0;   // (the very first down sweep starts from the seed: it keeps its row-0 visit)
   if constexpr (PEEL) {
-    sweep_down();
-    sweep_up();
+    sweep_down(false);
+    sweep_up(TURN);
     fin = done_after_up();
   }
   if (!fin) {
 #pragma unroll 1
     for (int it = PEEL ? 1 : 0; it < R * R; ++it) {
-      sweep_down();
+      sweep_down(TURN && PEEL);   // (without the peeled trip the loop's first down sweep is the first of all)
       if ((PEEL || K <= 1 || it > 0) && done_after_down()) break;
-      sweep_up();
+      sweep_up(TURN);
       if ((PEEL || K <= 2 || it > 0) && done_after_up()) break;
     }
   }

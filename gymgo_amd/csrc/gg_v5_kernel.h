@@ -247,6 +247,21 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
     const uint32_t fair_lag = plies >= 192 ? 24u : (plies >= 16 ? (uint32_t)plies >> 3 : 2u);
     bool lead = false;   // this wave is >= fair_lag plies ahead of its SIMD-mate
     uint32_t uq = 0;   // this lane's pre-mixed draw: lane j of a pair holds the one of ply (t & ~1) + j, swapped every ply
+#if GG_AB_LANE1
+    // what depends on the lane number alone, formed ONCE and kept in registers through the plies (gg_v5.h: GG_AB_LANE1) - at 19x19,
+    // where two waves per SIMD leave ~70 VGPRs free; 13x13 and 9x9 stand at 168 and 127 of the 170 and 128 VGPRs their three and four
+    // waves allow and keep the fresh v_mbcnt (the constants below are dead code there)
+    constexpr bool KEEP = R == 19;
+    const int lnK = ln0;
+    const int s4K = (lnK >> 1) & 31, t5K = lnK & 1, r0K = RPL * t5K;
+    const bool blK = s4K < nb;
+    const uint32_t fullK = (r0K + RPL - 1 < N) ? FULLROW : 0u;   // the one row of full[] that depends on the lane: the pair's last
+    uint32_t *const stK = st + s4K * RS;        // the board's rows of the black plane; the white plane's lie PL words behind
+    uint32_t *const gbK = gblk + 2 * s4K * RS;  // the board's G block, behind it its collection block
+    uint32_t *const clsK = clsv + s4K;          // the board's info word
+    uint32_t *const metaK = flagsv + s4K;       // the board's flag word; last action and played plies kNB5 and 2 kNB5 words behind
+    uint32_t *const blkK = sc + lnK * RS;       // the seed block of this lane's job
+#endif
 #pragma unroll 1
     for (int t = 0; t < plies; ++t) {
       // Fair share of the SIMD (gg_common.h) every fourth ply - without it the older of a SIMD's two waves runs ahead and the
@@ -259,6 +274,15 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
         lead = fair.behind((uint32_t)t, left < fair_lag ? (left > 2u ? left : 2u) : fair_lag) != 0u;
         if (lead) __builtin_amdgcn_s_setprio(2); else __builtin_amdgcn_s_setprio(3);
       }
+#if GG_AB_LANE1
+      int ln = lnK;
+      if constexpr (!KEEP) asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ln));
+      const int s4 = KEEP ? s4K : (ln >> 1) & 31, t5 = KEEP ? t5K : ln & 1, r0 = KEEP ? r0K : RPL * t5;   // board, lane of the pair, first row of this lane
+      const bool bl = KEEP ? blK : s4 < nb;
+      uint32_t full[RPL];   // the N-bit row mask of the lane's rows that exist
+#pragma unroll
+      for (int r = 0; r < RPL; ++r) full[r] = (KEEP && RPL + r < N) ? FULLROW : (KEEP && r == RPL - 1 ? fullK : ((r0 + r < N) ? FULLROW : 0u));
+#else
       int ln;
       asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ln));
       const int s4 = (ln >> 1) & 31, t5 = ln & 1, r0 = RPL * t5;   // board, lane of the pair, first row of this lane
@@ -266,6 +290,19 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
       uint32_t full[RPL];   // the N-bit row mask of the lane's rows that exist
 #pragma unroll
       for (int r = 0; r < RPL; ++r) full[r] = (r0 + r < N) ? FULLROW : 0u;
+#endif
+      // the board's rows of the mover's (GG_PM) and of the other (GG_PO) plane, `turn` 0 black / 1 white
+#if GG_AB_LANE1
+#define GG_PM(turn) (KEEP ? ((turn) ? stK + PL : stK) : st + (turn) * PL + s4 * RS)
+#define GG_PO(turn) (KEEP ? ((turn) ? stK : stK + PL) : st + (1u - (turn)) * PL + s4 * RS)
+#define GG_GB (KEEP ? gbK : gblk + 2 * s4 * RS)
+#define GG_CLS (KEEP ? clsK : clsv + s4)
+#else
+#define GG_PM(turn) (st + (turn) * PL + s4 * RS)
+#define GG_PO(turn) (st + (1u - (turn)) * PL + s4 * RS)
+#define GG_GB (gblk + 2 * s4 * RS)
+#define GG_CLS (clsv + s4)
+#endif
 
       int a_q;
       uint32_t fl_q;
@@ -275,10 +312,23 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
       // phase 1 - two lanes per board, RPL rows each: liveness, the draw, the k-th valid point of the mask
       {
         const uint32_t fl = flr;
-        const bool on = bl && ((fl >> 3) & 1u);
-        const bool done = (fl >> 2) & 1u;
-        const bool live = on && !(done && !auto_reset);
-        const bool reset = live && done;           // auto-reset: the board is init_state from now on
+        // (-DGG_AB_BALLOT1=1 at 19x19 only, like the other cuts of round 27: 13x13 and 9x9 keep round 20's machine code)
+        constexpr bool CMP1 = GG_AB_BALLOT1 != 0 && R == 19;
+        bool live, reset;
+        if constexpr (CMP1) {
+          // bit 3 of the flag word is `on`, bit 2 `done`: live iff the board exists, is on and not (done without auto-reset), reset iff
+          // it exists, is on and done with auto-reset - each ONE compare of the masked bits, and a compare is the form whose wave-wide
+          // mask costs nothing more (a bool put together from several tests goes through v_cndmask 0 / 1 and a second compare)
+          uint32_t flb = bl ? fl : 0u;
+          asm volatile("" : "+v"(flb));   // (or the compiler turns the masked word back into the AND of two tests)
+          live = (flb & (auto_reset ? 8u : 12u)) == 8u;
+          reset = (flb & 12u) == (auto_reset ? 12u : ~0u);   // auto-reset: the board is init_state from now on
+        } else {
+          const bool on = bl && ((fl >> 3) & 1u);
+          const bool done = (fl >> 2) & 1u;
+          live = on && !(done && !auto_reset);
+          reset = live && done;           // auto-reset: the board is init_state from now on
+        }
         // Invariant: a board's live plies are a PREFIX of the launch (`on` never changes inside it; a done board stays done
         // unless auto_reset, and then it is live on every ply), and every live ply draws exactly once and moves (a_q >= 0:
         // phase 3 counts it) - so `played` equals the number of draws, which the write-back turns into the generator's advance.
@@ -296,7 +346,7 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
           // phase 3 of the last ply - or the load - left them), the row beyond the pair's seam out of the partner lane by one
           // DPP swap per colour and side; off the board the mover's rows read as all ones and the opponent's as zero.
           const uint32_t turn = fl & 1u;
-          const uint32_t *pm = st + turn * PL + s4 * RS + r0, *po = st + (1u - turn) * PL + s4 * RS + r0;
+          const uint32_t *pm = GG_PM(turn) + r0, *po = GG_PO(turn) + r0;
           uint32_t me[RPL], op[RPL];
 #pragma unroll
           for (int r = 0; r < RPL; ++r) { me[r] = pm[r]; op[r] = po[r]; }   // (rows >= N are zero)
@@ -389,8 +439,9 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
         a_q = !live ? -1 : (k < n ? (int)pt : P);
         const bool place = live && hit;
         fl_q = reset ? 40u : fl;   // a board being reset: on, dirty, black to move
-        uint64_t resetm = __ballot(reset && t5 == 0);
-        const bool none_live = __ballot(live) == 0;
+        // (CMP1: both lanes of a pair agree on `reset`, the even lanes by a scalar AND)
+        uint64_t resetm = CMP1 ? GG_BALLOT5(reset) & 0x5555555555555555ull : GG_BALLOT5(reset && t5 == 0);
+        const bool none_live = GG_BALLOT5(live) == 0;
         if (none_live && resetm == 0) break;
         if (resetm) {   // rare
           if (reset) {
@@ -411,17 +462,29 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
         // (the lanes of EVERY board clear its G block and its collection block - a board that passes or idles leaves them
         // empty, phase 3 reads them unmasked -, then the lane that holds the point writes the stone: DS instructions of a wave
         // execute in order)
-        uint32_t *gb = gblk + 2 * s4 * RS;
-        if (t5 == 0) clsv[s4] = 0u;   // the board's info word
+        uint32_t *gb = GG_GB;
+        // (-DGG_AB_FLAT1=1 at 19x19 only: at 13x13 and 9x9 the flat stores cost the byte-plane kernels two VGPRs, and they stand at 168
+        // and 127 of the 170 and 128 their three and four waves per SIMD allow)
+        constexpr bool FLAT = GG_AB_FLAT1 != 0 && R == 19;
+        if (FLAT || t5 == 0) *GG_CLS = 0u;   // the board's info word (FLAT: both lanes of the pair store the same zero, no exec region)
         {
           uint4 *pz = reinterpret_cast<uint4 *>(gb + t5 * RS);   // (lane 0 of the pair: the G block, lane 1: the collection block)
 #pragma unroll
           for (int i = 0; i < RV; ++i) pz[i] = make_uint4(0u, 0u, 0u, 0u);
         }
         asm volatile("" ::: "memory");
-        if (place) {
+        if constexpr (FLAT) {
+          // no exec region: EVERY lane ORs - the lane that places the stone its bit, any other lane zero, into a row of its own board's
+          // plane (nothing is written to a board that does not move) - and the G block takes the stone by an OR too: the pair's even
+          // lane has just cleared it, and DS instructions of a wave execute in order
+          const uint32_t turn = reset ? 0u : (fl & 1u);
+          const uint32_t bit = place ? 1u << pos : 0u;
+          const int rw = place ? rabs : r0;
+          atomicOr(GG_PM(turn) + rw, bit);   // (ds_or without a return value: no round trip inside the phase)
+          atomicOr(gb + rw, bit);
+        } else if (place) {
           const int turn = reset ? 0 : (int)(fl & 1u);
-          atomicOr(st + turn * PL + s4 * RS + rabs, 1u << pos);   // (ds_or without a return value: no round trip inside the phase)
+          atomicOr(GG_PM(turn) + rabs, 1u << pos);   // (ds_or without a return value: no round trip inside the phase)
           gb[rabs] = 1u << pos;
         }
       }
@@ -444,7 +507,7 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
 #else
         split_action(mv1 ? a : 0, N, inv, ar, ac);
 #endif
-        const uint32_t *pm = st + turn * PL + s4 * RS, *po = st + (1u - turn) * PL + s4 * RS;
+        const uint32_t *pm = GG_PM(turn), *po = GG_PO(turn);
         uint32_t obit[2], packed = 0;
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
@@ -464,7 +527,7 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
         const uint32_t friendly = (qs >> 11) & 1u;
         const uint32_t gf = t5 ? 0u : friendly;             // the pair's even lane posts the G job
         const uint32_t c = gf + obit[0] + obit[1];
-        const uint64_t b0 = __ballot((c & 1u) != 0u), b1 = __ballot((c & 2u) != 0u);
+        const uint64_t b0 = GG_BALLOT5((c & 1u) != 0u), b1 = GG_BALLOT5((c & 2u) != 0u);
         const uint32_t base = mbcnt64(b0) + 2u * mbcnt64(b1);
         njobs = (int)__popcll(b0) + 2 * (int)__popcll(b1);
         const uint32_t sG = base, s0 = base + gf, s1 = s0 + obit[0];
@@ -507,7 +570,11 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
 #endif
         const uint32_t ownc = (d >> 15) & 1u;
         const uint32_t isG = have ? (d >> 16) & 1u : 0u;
+#if GG_AB_LANE1
+        uint32_t *blk = KEEP ? blkK : sc + ln * RS;   // this lane's seed block (all zero)
+#else
         uint32_t *blk = sc + ln * RS;   // this lane's seed block (all zero)
+#endif
         const uint4 *lds4 = reinterpret_cast<const uint4 *>(lds);
         const uint4 *pmv = lds4 + (Lds5<R>::kState + (int)ownc * PL + sj * RS) / 4;
         const uint4 *pov = lds4 + (Lds5<R>::kState + (int)(ownc ^ 1u) * PL + sj * RS) / 4;
@@ -587,7 +654,7 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
             GG_PROF(2);
             cnt = job_liberties<R>(res, ot, m);
             const bool unsettled = have && open != 0u && cnt < 2u;
-            if (__ballot(unsettled)) {
+            if (GG_BALLOT5(unsettled)) {
 #pragma unroll
               for (int r = 0; r < R; ++r) f[r] = (r & 1) ? __brev(res[r]) : res[r];
               flood_jobs_restart<R, false>(m, mrev, f, res, unsettled, mm, open);
@@ -611,7 +678,29 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
         // (two rows per ds_or_b64: the blocks and RS are even, and for odd R the last pair ORs zero into row R, inside the block;
         // half the LDS instructions of nineteen ds_or_b32 - skipping empty rows by a per-row branch instead cost 4 %)
         static_assert(Lds5<R>::kG % 2 == 0 && RS % 2 == 0 && R + 1 <= RS, "8-byte aligned row pairs inside the block");
-        if (isG || (have && cnt < 2u)) {
+        // (-DGG_AB_FLAT1=1, 19x19: 13x13 and 9x9 stand two VGPRs below what their three and four waves per SIMD allow, and the words
+        // formed in front of the region are live beside all of res[])
+        constexpr bool HAND_FLAT = GG_AB_FLAT1 != 0 && R == 19;
+        if constexpr (HAND_FLAT) {
+          // the block's offset and the info word are formed by selects IN FRONT of the region (kept there by the empty asm), so that
+          // the hand-over is the one exec region round 19 meant and not the halves of a branch on isG around it
+          // G: its liberties; an opponent group: the direction in which it was captured (a zero word is ORed, not branched around)
+          // (value and shift are selected, then shifted once: a select between the two shifted words compiles to a branch on isG)
+          uint32_t off = isG ? 0u : (uint32_t)RS;
+          const uint32_t wv = isG ? lib2 : (cnt == 0u ? 1u : 0u), wsh = isG ? 4u : ((d >> 19) & 3u);
+          uint32_t word = wv << wsh;
+          uint32_t sji = (uint32_t)sj;   // (the info word's index on its own: not re-derived from the block's address)
+          asm volatile("" : "+v"(off), "+v"(word), "+v"(sji));
+          if (isG || (have && cnt < 2u)) {
+            uint32_t *dst = gb + off;
+#pragma unroll
+            for (int r = 0; r < R; r += 2) {
+              const uint32_t hi = r + 1 < R ? res[r + 1] : 0u;
+              atomicOr(reinterpret_cast<unsigned long long *>(dst + r), ((unsigned long long)hi << 32) | res[r]);
+            }
+            atomicOr(clsv + sji, word);
+          }
+        } else if (isG || (have && cnt < 2u)) {
           uint32_t *dst = gb + (isG ? 0 : RS);
 #pragma unroll
           for (int r = 0; r < R; r += 2) {
@@ -652,11 +741,11 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
       {
         const int a = a_q;
         const uint32_t fl = fl_q;
-        const uint32_t info = clsv[s4];
+        const uint32_t info = *GG_CLS;
         const int turn0 = fl & 1u;
-        uint32_t *pmine = st + turn0 * PL + s4 * RS + r0;
-        uint32_t *popp = st + (1 - turn0) * PL + s4 * RS + r0;
-        const uint32_t *gG = gblk + 2 * s4 * RS + r0;   // the board's G block, behind it the collected opponent groups
+        uint32_t *pmine = GG_PM(turn0) + r0;
+        uint32_t *popp = GG_PO(turn0) + r0;
+        const uint32_t *gG = GG_GB + r0;   // the board's G block, behind it the collected opponent groups
         uint32_t mine1[RPL], opp0[RPL], all4[RPL], bg[RPL];
 #pragma unroll
         for (int r = 0; r < RPL; ++r) {
@@ -690,17 +779,19 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
         uint32_t libsG = ((qs >> 11) & 1u) ? ((info >> 4) & 3u) : ne2;
         uint32_t ko_oh = 0, ko_bit = 0;   // the ko point: one-hot row of this lane / column bit (almost always none)
         GG_P3(0, 1u);
-        GG_P3(8, (uint32_t)__popcll(__ballot(capt_m != 0u && t5 == 0)));
-        GG_P3(9, (uint32_t)__popcll(__ballot(a >= 0 && t5 == 0)));
+        GG_P3(8, (uint32_t)__popcll(GG_BALLOT5(capt_m != 0u && t5 == 0)));
+        GG_P3(9, (uint32_t)__popcll(GG_BALLOT5(a >= 0 && t5 == 0)));
         GG_MARK(10);
-        if (__ballot(capt_m != 0u)) {   // a capture on some board of the wave
+        if (GG_BALLOT5(capt_m != 0u)) {   // a capture on some board of the wave
           GG_MARK(11);
           GG_P3(1, 1u);
           uint32_t cap[RPL];   // the captured stones
 #pragma unroll
           for (int r = 0; r < RPL; ++r) cap[r] = B3(all4[r], M[r], M[r], TA & ~TB & 0xFF);
           const uint32_t ncapn = (uint32_t)__popc(capt_m);        // captured neighbours of q
-          if (__ballot(ncapn == 1u && libsG == 0u)) {
+          constexpr bool CMP3 = GG_AB_BALLOT1 != 0 && R == 19;   // (ncapn == 1 && libsG == 0 as one compare)
+          const bool one0 = CMP3 ? B3(ncapn, 1u, libsG, (TA ^ TB) | TC) == 0u : (ncapn == 1u && libsG == 0u);
+          if (GG_BALLOT5(one0)) {
             GG_MARK(12);
             GG_P3(2, 1u);
             uint32_t dg[RPL];
@@ -710,15 +801,16 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
             for (int r = 0; r < RPL; ++r) cntc += (uint32_t)__popc(dg[r] & cap[r]);
             const uint32_t c2 = cntc < 2u ? cntc : 2u;
             const uint32_t tot = c2 + dpp0<QP_X1>(c2);
-            libsG += (ncapn == 1u && libsG == 0u) ? (tot < 2u ? tot : 2u) : ncapn;
+            libsG += one0 ? (tot < 2u ? tot : 2u) : ncapn;
             GG_MARK(13);
           } else {
             libsG += ncapn;
           }
           // gogame.py:72-75: ko iff exactly one stone died and the new stone is boxed in (one captured NEIGHBOUR and a boxed-in
           // stone first: rare enough to keep the rest off the usual path)
-          const bool ko1 = ncapn == 1u && !(qs & CL_OPEN);
-          if (__ballot(ko1)) {
+          // (CMP3: ncapn == 1 && !(qs & CL_OPEN) as one compare)
+          const bool ko1 = CMP3 ? B3(ncapn, 1u, qs & CL_OPEN, (TA ^ TB) | TC) == 0u : (ncapn == 1u && !(qs & CL_OPEN));
+          if (GG_BALLOT5(ko1)) {
             GG_MARK(14);
             GG_P3(3, 1u);
             uint32_t died = 0;   // captured stones on this lane's rows (one captured neighbour: exactly one stone died iff its group is that stone)
@@ -753,7 +845,7 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
             }
           }
           GG_MARK(17);
-          if (__ballot(anyf != 0u)) {
+          if (GG_BALLOT5(anyf != 0u)) {
             GG_MARK(18);
             GG_P3(5, 1u);
 #ifdef GG_AB_P3
@@ -783,9 +875,9 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
 #pragma unroll 1
             for (int it = 0; it < R * R; ++it) {
               GG_JOIN_TRIP(0, 1);
-              if (__ballot(chg != 0u) == 0) break;
+              if (GG_BALLOT5(chg != 0u) == 0) break;
               GG_JOIN_TRIP(RPL - 1, -1);
-              if (__ballot(chg != 0u) == 0) break;
+              if (GG_BALLOT5(chg != 0u) == 0) break;
             }
 #undef GG_JOIN_TRIP
 #undef GG_TRIP
@@ -827,7 +919,7 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
           const uint32_t invalid = B3(e[r], nbr[r], full[r], ~(TA & TB) & TC & 0xFF);
           inv_r[r] = B3(mv_m, invalid, inv_r[r], T_SEL);
         }
-        if (__ballot(ko_oh != 0u)) {   // (only a board that moved has a ko point)
+        if (GG_BALLOT5(ko_oh != 0u)) {   // (only a board that moved has a ko point)
 #pragma unroll
           for (int r = 0; r < RPL; ++r) inv_r[r] |= (uint32_t)__builtin_amdgcn_sbfe((int)ko_oh, r, 1) & ko_bit;
         }
@@ -836,19 +928,42 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
           for (int r = 0; r < RPL; ++r) popp[r] = opp1[r];
         }
         // (a board being reset found fl_q = on | dirty | black to move in phase 1: the register copy follows even if it does not move)
-        flr = fl;
-        if (moves_now) {
+        if constexpr (GG_AB_FLAT1 != 0 && R == 19) {
+          // no exec region: the new flag word by a select, and BOTH lanes of the pair store the board's three meta words (they hold
+          // the same values) - at the board's own words when it moves, else at the dump words nobody reads (Lds5::kDumpMeta)
           const uint32_t passed0 = (fl >> 1) & 1u, done0 = (fl >> 2) & 1u;
           const uint32_t passed = is_pass ? 1u : 0u, done = done0 | (passed & passed0);
-          flr = (uint32_t)(turn0 ^ 1) | (passed << 1) | (done << 2) | 8u | (fl & 32u);
-          playedr += 1;
-          if (t5 == 0) {
-            flagsv[s4] = flr;
-            lastv[s4] = a;
-            playedv[s4] = playedr;
+          const uint32_t flm = (uint32_t)(turn0 ^ 1) | (passed << 1) | (done << 2) | 8u | (fl & 32u);
+          flr = moves_now ? flm : fl;
+          playedr += moves_now ? 1 : 0;
+#if GG_AB_LANE1
+          uint32_t *mp = KEEP ? (moves_now ? metaK : metaK + (Lds5<R>::kDumpMeta - Lds5<R>::kMeta))
+                              : lds + (moves_now ? Lds5<R>::kMeta : Lds5<R>::kDumpMeta) + s4;
+#else
+          uint32_t *mp = lds + (moves_now ? Lds5<R>::kMeta : Lds5<R>::kDumpMeta) + s4;
+#endif
+          mp[0] = flr;
+          mp[kNB5] = (uint32_t)a;
+          mp[2 * kNB5] = (uint32_t)playedr;
+        } else {
+          flr = fl;
+          if (moves_now) {
+            const uint32_t passed0 = (fl >> 1) & 1u, done0 = (fl >> 2) & 1u;
+            const uint32_t passed = is_pass ? 1u : 0u, done = done0 | (passed & passed0);
+            flr = (uint32_t)(turn0 ^ 1) | (passed << 1) | (done << 2) | 8u | (fl & 32u);
+            playedr += 1;
+            if (t5 == 0) {
+              flagsv[s4] = flr;
+              lastv[s4] = a;
+              playedv[s4] = playedr;
+            }
           }
         }
       }
+#undef GG_PM
+#undef GG_PO
+#undef GG_GB
+#undef GG_CLS
       WAVE_SYNC();
       GG_PROF(4);
     }
