@@ -128,6 +128,11 @@ int32_t gg_batch_children(const uint8_t *states, uint8_t *children, int64_t B, i
  *      offsets[B] = the total.  The caller reads offsets[B] back and allocates children: uint8 [offsets[B]][6][N][N].
  *      order (int32 [B], may be NULL): the parents sorted by falling child count - the order in which the expansion should
  *      hand them to the machine (a parent's work grows with its children; heaviest first keeps the launch's tail short).
+ *      Parents with equal counts come in ANY order, which may differ from one call to the next (like the slot a playout of
+ *      gg_playouts_* lands in, it is settled by an atomic: it decides which work item a parent is, never what is written;
+ *      these two are the outputs of the library that are not functions of the arguments alone).
+ *      B = 0 is not "no work" for offsets: offsets[B] = the total holds there too, so offsets[0] = 0 is written (and no
+ *      other byte).
  *      GG_E_BADSIZE if B * (N*N+1) does not fit an int32.
  *   2. gg_batch_children_compact: parent b's children at children[offsets[b] .. offsets[b+1]), ascending action order - exactly
  *      the non-zero-padded slots of gg_batch_children, i.e. children_padded[b][valid_moves(states[b]) == 1] (a kept slot whose
@@ -380,7 +385,11 @@ int32_t gg_rng_seed(uint64_t *rng, uint64_t base_seed, int64_t first_game, int64
  * counter int64 [2] = {next job id, the value it reaches once every job is done}: counter[1] - counter[0] = jobs outstanding
  * (every harvested playout takes one id from the queue, ids from R K on refill nothing).
  *   gg_playouts_begin    zeroes counts / sums / ownership, sets counter = {m, R K + m} with m = min(S, R K) and fills the
- *                        first m slots with jobs 0, 1, ... (the other slots: empty, frozen boards)
+ *                        first m slots with jobs 0, 1, ... (the other slots: empty, frozen boards).  R = 0 is NOT "no work"
+ *                        here: it makes the empty queue - counter = {0, 0}, every slot empty -, which a driver that polls
+ *                        counter relies on (gg_move_playouts_begin with T = 0 likewise); an advance on it is no work.
+ *                        Which slot a job lands in is settled by an atomic on counter: the slots are opaque, and two runs of
+ *                        the same calls hold the same jobs in other slots.  counts / sums / ownership do not depend on it.
  *   gg_playouts_advance  queues `chunks` x (gg_batch_rollout_tracked of chunk_plies plies on all S slots + one harvest
  *                        launch that scores every slot whose playout has ended, adds it to its root and refills the slot
  *                        from the queue).  The work is done once counter[0] == counter[1]; a playout takes at most
@@ -408,7 +417,8 @@ int32_t gg_playouts_advance(const uint32_t *roots, int64_t R, int32_t N, int32_t
  * after a pass - gives a finished playout of 0 plies).  So row (r, a) equals gg_playouts_* of that child alone with
  * first_root = (first_root + r) A + a.  No ownership output.
  *   gg_move_playouts_plan     offsets int32 [R+1] = exclusive prefix sums of the number of legal first moves per root
- *                             (offsets[R] = T, the number of legal pairs: read it back before the calls below);
+ *                             (offsets[R] = T, the number of legal pairs: read it back before the calls below; R = 0
+ *                             writes offsets[0] = 0 and nothing else);
  *                             plan int32 [R*A]: plan[offsets[r] + k] = r A + a_k, a_k root r's k-th legal action in
  *                             ascending order (the pass last); only the first T entries are written.
  *                             GG_E_BADSIZE: N outside [2, 19], R < 0, R*A does not fit an int32; GG_E_NULLPTR.

@@ -242,9 +242,10 @@ _POINTEES = {'uint32_t': 'int32', 'int32_t': 'int32', 'uint64_t': 'int64', 'int6
              'double': 'float64', 'gg_puct_stat': 'int32'}
 
 
-def _header_declarations():
-    """{function: [(C type without const, is pointer, parameter name)]} of every `int32_t gg_*(...);` of the header."""
-    hdr = open(os.path.join(ROOT, 'include', 'gymgo_amd.h')).read()
+def header_declarations(header='gymgo_amd.h', const=False):
+    """{function: [(C type without const, is pointer, parameter name)]} of every `int32_t gg_*(...);` of a header of include/;
+    const: a fourth element, whether the parameter is declared const (tests/test_guard_cases_host.py reads the roles from it)."""
+    hdr = open(os.path.join(ROOT, 'include', header)).read()
     decls = {}
     for m in re.finditer(r'^\s*(?:int32_t|int)\s+(gg_\w+)\s*\((.*?)\);', hdr, flags=re.M | re.S):
         params = []
@@ -252,11 +253,15 @@ def _header_declarations():
             text = ' '.join(text.split())
             if text == 'void':
                 continue
-            pm = re.fullmatch(r'(?:const )?(\w+) ?(\*?) ?(\w+)', text)
+            pm = re.fullmatch(r'(const )?(\w+) ?(\*?) ?(\w+)', text)
             assert pm, (m.group(1), text)
-            params.append((pm.group(1), pm.group(2) == '*', pm.group(3)))
+            params.append((pm.group(2), pm.group(3) == '*', pm.group(4)) + ((bool(pm.group(1)),) if const else ()))
         decls[m.group(1)] = params
     return decls
+
+
+def _header_declarations():
+    return header_declarations()
 
 
 def _abi_mismatches(decls, table):
