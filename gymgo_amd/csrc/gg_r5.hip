@@ -73,6 +73,16 @@ extern "C" int32_t gg_ab_p3_read_r5(unsigned long long *out10) {
 }
 #endif
 
+#ifdef GG_AB_MCHECK
+// A/B builds only: read and clear the plane-of-M check of k_rollout5 (gg_v5.h: gg_mcheck; rows that differ, rows compared)
+extern "C" int32_t gg_ab_mcheck_read_r5(unsigned long long *out2) {
+  if (hipDeviceSynchronize() != hipSuccess) return 1;
+  if (hipMemcpyFromSymbol(out2, HIP_SYMBOL(gg::gg_mcheck), 16) != hipSuccess) return 2;
+  unsigned long long z[2] = {0, 0};
+  return hipMemcpyToSymbol(HIP_SYMBOL(gg::gg_mcheck), z, 16) == hipSuccess ? 0 : 3;
+}
+#endif
+
 #ifdef GG_AB_WS
 // A/B builds only: read and clear the workspace counters of k_rollout5's byte-plane load (gg_v5.h: gg_wsc; pairs skipped, pairs analysed)
 extern "C" int32_t gg_ab_ws_read_r5(unsigned long long *out2) {

@@ -20,7 +20,7 @@ namespace gg {
 //       (row, column), colour, direction - go to LDS;
 //   2b. lane L runs job L - 32 boards x 1.56 = 50 jobs in 64 lanes (a second batch when a ply posts more than 64: 0.7 %) -
 //       with the fill in registers from the seed to the liberty count.  The batch's loop ends as soon as every flood of a G
-//       is closed as far as stones OUTSIDE M go (the rows of M come out of the board lanes' registers by ds_bpermute): the
+//       is closed as far as stones OUTSIDE M go (the rows of M come out of an LDS plane the board lanes keep, round 29): the
 //       minimum of three sweeps on 98 % of the batches; an opponent group whose part found so far has two liberties is
 //       settled, the few lanes left with fewer flood on.  What phase 3 needs leaves the lane at the end: G as a block of its
 //       board, an opponent group that is captured or leaves M ORed into the board's collection block, a captured direction
@@ -35,6 +35,9 @@ namespace gg {
 // Scope: drawn moves on full-size boards (N == R), byte planes or tracked boards - the fused rollout of big batches; every
 // other form stays on k_rollout4.
 constexpr int kNB5 = 32;
+#ifndef GG_AB_MPLANE1
+#define GG_AB_MPLANE1 1   // (round 29's switch, described with the other switches below; Lds5 sizes the plane by it)
+#endif
 constexpr int kJobCap = 128;   // jobs of one ply: <= 4 per board (four opponent neighbours leave no friendly one)
 
 template <int R>
@@ -58,7 +61,12 @@ struct Lds5 {
   static constexpr int kJob = kCls + kJobCap + 4;                // [kJobCap + 4]
   static constexpr int kG = kJob + kJobCap + 4;                  // [kNB5][2][RS]: G, the collected opponent groups
   static constexpr int kSc = kG + 2 * kNB5 * RS;                 // [kWave][RS]
-  static constexpr int kLoopEnd = kSc + kWave * RS;
+  // (-DGG_AB_MPLANE1=1, 19x19) the rows of M of every board, [kNB5][RS] as one stone plane: live from the end of the load to the last
+  // ply, behind everything the ply loop uses - the load's scratch and landing area and the emitter's bits may lie over it, the plane
+  // is written when the load is done with them and dead when the write-back begins
+  static constexpr bool kHasMpl = GG_AB_MPLANE1 != 0 && R == 19;
+  static constexpr int kMpl = kSc + kWave * RS;
+  static constexpr int kLoopEnd = kMpl + (kHasMpl ? kNB5 * RS : 0);
   // (-DGG_AB_FLAT1=1) the meta words - flags, last action, played - of a board that does not move are stored into the words of kCls
   // behind the boards' info words, which nothing else uses: laid out as kMeta's first three rows, never read
   static constexpr int kDumpMeta = kCls + kNB5;
@@ -76,7 +84,7 @@ struct Lds5 {
   static constexpr int kMax2(int a, int b) { return a > b ? a : b; }
   static constexpr int kTotal = kMax2(kMax2(kLoopEnd, kIoEnd), kMax2(kDmaEnd, kGrpEnd));
   static_assert(kTotal * 4 <= 20480, "two waves per SIMD: 20 KB of LDS per wave");
-  static_assert(kUnion % 4 == 0 && kG % 4 == 0 && kSc % 4 == 0, "16-byte alignment of the flood blocks");
+  static_assert(kUnion % 4 == 0 && kG % 4 == 0 && kSc % 4 == 0 && kMpl % 4 == 0, "16-byte alignment of the flood blocks");
   static_assert(3 * kNB5 * RS <= kLoopEnd - kUnion, "parked tracked rows fit the loop area");
 };
 
@@ -213,6 +221,22 @@ static __device__ unsigned long long gg_sweeps5[10];
 #endif
 #ifndef GG_AB_TURN1
 #define GG_AB_TURN1 1
+#endif
+// A/B switches of round 29, the job loop's bookkeeping and phase 3's padding (gg_v5_kernel.h; docs/history/r29.md; both at 0 = round 27's
+// code, line for line).  Both are in force at 19x19 only: 13x13 and 9x9 keep round 20's machine code and their LDS size.
+// GG_AB_MPLANE1 1 (shipped: +1.4 % and +1.6 % on the headline launch in two alternations, every run above every run of the parent): the
+//   rows of M of every board stand in an LDS plane [kNB5][RS] (Lds5::kMpl) behind the ply loop's blocks - written once behind the load,
+//   zeroed by the reset path, rewritten by the board lanes at the end of phase 3 (flat, five row pairs a lane) - and a job lane reads
+//   the rows of its board's M beside its stone rows, in their wait group (four ds_read_b128 and one ds_read_b96), 0: nineteen
+//   ds_bpermute_b32 out of the board lanes' registers.  19 472 -> 20 016 B of LDS, of the 20 480 two waves per SIMD leave a wave;
+// GG_AB_SHL1 1: the atari-join of phase 3 forms the shl1 of all its rows in front of the rows' chains (seeds: of cap[], a trip: of the
+//   f[] it starts from), so that no consumer directly follows its inline-asm add and the compiler pads none of them with s_nop 0
+//   (18 s_nop and no other instruction fewer in the listing), 0 (shipped): each add directly in front of the v_bitop3 that takes it.
+//   Alone it measured 0.6 % and 0.7 % BELOW the parent on the medians, on top of GG_AB_MPLANE1 0.6 % and 0.8 % below it: stays 0.
+// (The round's third part, res[] of flood_jobs in two-element vectors so that the hand-over's ds_or_b64 take register pairs as they
+// are, took eight of the hand-over's ten v_mov_b32 out and put twenty-five into the flood's tests, at 221 VGPRs: not in the source.)
+#ifndef GG_AB_SHL1
+#define GG_AB_SHL1 0
 #endif
 #if GG_AB_BALLOT1
 // (used where a board size R is in scope; 13x13 and 9x9 keep __ballot and with it round 20's machine code)
@@ -488,6 +512,13 @@ static __device__ unsigned long long gg_p3[10];
 static __device__ unsigned long long gg_live_bad;
 #endif
 
+#ifdef GG_AB_MCHECK
+// A/B builds only (make ab EXTRA=-DGG_AB_MCHECK, tools/exp/r5_mplane_check.py): [0] rows of M a job lane of k_rollout5<19, ..> read out of
+// the plane of M (-DGG_AB_MPLANE1=1) that differ from the row the board's lanes hold in their registers, fetched by the ds_bpermute of
+// the other setting as well; [1] rows compared.  No result depends on the plane unless a flood batch ends early, which the parity tests
+// see only in rare positions: this counter is the direct check that plane and registers are the same.
+static __device__ unsigned long long gg_mcheck[2];
+#endif
 #ifdef GG_AB_WS
 // A/B builds only (make ab EXTRA=-DGG_AB_WS, tools/exp/r5_ws_counts.py): the pairs of boards of workspace launches whose analysis
 // the load skipped ([0]: both boards stand in the workspace stone for stone) and the pairs it analysed ([1]), counted in registers

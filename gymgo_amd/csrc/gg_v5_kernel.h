@@ -33,6 +33,9 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
   uint32_t *jobv = lds + Lds5<R>::kJob;
   uint32_t *gblk = lds + Lds5<R>::kG;
   uint32_t *sc = lds + Lds5<R>::kSc;
+  constexpr bool MPLANE = Lds5<R>::kHasMpl;   // (19x19, -DGG_AB_MPLANE1=1) the rows of M stand in LDS for the job lanes
+  static_assert(!MPLANE || (RPL % 2 == 0 && RS % 2 == 0 && Lds5<R>::kMpl % 2 == 0), "a lane's rows of the plane of M are 8-byte aligned pairs");
+  uint32_t *mplv = lds + Lds5<R>::kMpl;       // mplv[board * RS + row]
   uint32_t *v2 = lds + Lds5<R>::kV2;
   uint32_t *park = lds + Lds5<R>::kUnion;   // tracked I/O: park[set * PL + board * RS + row], set 0 invalid, 1 mb, 2 mw
   const int64_t ngroups = (B + nb - 1) / nb;
@@ -226,6 +229,13 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
     // the slot of an absent job: an all-zero block and class word (the loop area was the load's scratch)
     WAVE_SYNC();
     for (int i = hf.lane; i < kWave * RS; i += kWave) sc[i] = 0u;   // the seed blocks: all zero between two uses
+    if constexpr (MPLANE) {
+      // the plane of M (gg_v5.h: GG_AB_MPLANE1): every pair of lanes stores the rows the load left it - from the tracked board, from the
+      // workspace or from the from-scratch analysis, zero for an absent board - now that the load is done with the loop area
+      uint2 *pm2 = reinterpret_cast<uint2 *>(mplv + s5 * RS + r05);
+#pragma unroll
+      for (int r = 0; r < RPL; r += 2) pm2[r / 2] = make_uint2(M[r], M[r + 1]);
+    }
     WAVE_SYNC();
 
     // the flag word, the generator and the played plies of this lane's board travel in REGISTERS through the plies (the same
@@ -452,6 +462,7 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
             const int s = (__ffsll((unsigned long long)resetm) - 1) >> 1;   // lane 2 s -> board s
             resetm &= resetm - 1;
             for (int i = hf.lane; i < 2 * RS; i += kWave) st[(i / RS) * PL + s * RS + (i % RS)] = 0;
+            if constexpr (MPLANE) { if (hf.lane < RS) mplv[s * RS + hf.lane] = 0; }   // (its jobs of THIS ply read M from the plane)
             if (hf.lane == 0) flagsv[s] = 8u | 32u;   // on, reset (written back even if nothing is played)
           }
           if (none_live) break;
@@ -579,8 +590,11 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
         const uint4 *pmv = lds4 + (Lds5<R>::kState + (int)ownc * PL + sj * RS) / 4;
         const uint4 *pov = lds4 + (Lds5<R>::kState + (int)(ownc ^ 1u) * PL + sj * RS) / 4;
         // the rows of M (the classes BEFORE this move) of the job's board, out of the registers of the two lanes that hold them
+        // (-DGG_AB_MPLANE1=1, 19x19: out of the plane of M instead, below with the stone rows - the plane holds what the registers
+        // hold, phase 3 of the last ply, the load or the reset path stored it, and M does not change between phase 1 and phase 3)
+        const uint4 *pmmv = lds4 + (Lds5<R>::kMpl + sj * RS) / 4;
         uint32_t mm[R];
-        {
+        if constexpr (!MPLANE) {
           const int src = 8 * sj;   // byte address of lane 2 sj for ds_bpermute
 #pragma unroll
           for (int i = 0; i < RPL; ++i) {
@@ -602,6 +616,13 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
               if (4 * i + 1 < R) ot[4 * i + 1] = y.y;
               if (4 * i + 2 < R) ot[4 * i + 2] = y.z;
               if (4 * i + 3 < R) ot[4 * i + 3] = y.w;
+              if constexpr (MPLANE) {
+                const uint4 z = pmmv[i];
+                mm[4 * i] = z.x;
+                if (4 * i + 1 < R) mm[4 * i + 1] = z.y;
+                if (4 * i + 2 < R) mm[4 * i + 2] = z.z;
+                if (4 * i + 3 < R) mm[4 * i + 3] = z.w;
+              }
             }
             // the seed is one bit of one row: written into the lane's zero block at its (dynamic) row and read back as the
             // flood's row set - two LDS instructions instead of a select per row (odd rows bit-reversed) -, then cleared again
@@ -627,6 +648,18 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
               res[r] = 0u;
             }
           }
+#ifdef GG_AB_MCHECK
+          if constexpr (MPLANE) {   // (A/B builds only: the plane's rows against the registers', gg_v5.h: gg_mcheck)
+            uint32_t bad_ = 0;
+#pragma unroll
+            for (int i = 0; i < R; ++i) {
+              const uint32_t want_ = (uint32_t)__builtin_amdgcn_ds_bpermute(8 * sj + (i < RPL ? 0 : 4), (int)M[i < RPL ? i : i - RPL]);
+              bad_ += (have && want_ != mm[i]) ? 1u : 0u;
+            }
+            if (bad_) atomicAdd(&gg_mcheck[0], (unsigned long long)bad_);
+            if (have) atomicAdd(&gg_mcheck[1], (unsigned long long)R);
+          }
+#endif
           GG_PROF(1);
           // Which floods must reach their fixed point inside the batch's loop?  (Its length is the longest of its floods: 4.21
           // sweeps per batch when all 1.56 floods per board count, 3.87 when only G's 0.6 per board do, 3.00 with the weak
@@ -833,14 +866,23 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
           // fewer than with the Jacobi dilation of round 7 (2.40 against 2.87 per wave-ply that enters the loop, 47 % of
           // them), at 6 instead of 7 VALU per row and trip (profiles/r08_p3_counts.txt).
           uint32_t atari[RPL], f[RPL], anyf = 0;
+          constexpr bool SHL_FIRST = GG_AB_SHL1 != 0 && R == 19;
           {
             const uint32_t up = dpp0<0x138>(cap[RPL - 1]), dn = dpp0<0x130>(cap[0]);
+            // (-DGG_AB_SHL1=1, 19x19: the adds of all rows first - an inline-asm add directly in front of the v_bitop3 that takes its
+            // result is padded with an s_nop 0 by the compiler: by the listing none here, nine in each of the two trips below)
+            uint32_t cl[RPL];
+            if constexpr (SHL_FIRST) {
+#pragma unroll
+              for (int r = 0; r < RPL; ++r) cl[r] = shl1(cap[r]);
+              __builtin_amdgcn_sched_barrier(0);
+            }
 #pragma unroll
             for (int r = 0; r < RPL; ++r) {
               atari[r] = B3(mine1[r], M[r], g0[r], TA & ~(TB | TC) & 0xFF);   // mine & ~M & ~G
               const uint32_t above = r == 0 ? up : cap[r - 1], below = r == RPL - 1 ? dn : cap[r + 1];
               const uint32_t v = B3(cap[r] >> 1, above, below, T_OR3);
-              f[r] = B3(shl1(cap[r]), v, atari[r], (TA | TB) & TC);           // dilate(cap) & atari
+              f[r] = B3(SHL_FIRST ? cl[r] : shl1(cap[r]), v, atari[r], (TA | TB) & TC);           // dilate(cap) & atari
               anyf |= f[r];
             }
           }
@@ -861,12 +903,17 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
               GG_TRIP;                                                                                                    \
               const uint32_t up_ = dpp0<0x138>(f[RPL - 1]), dn_ = dpp0<0x130>(f[0]);                                      \
               chg = 0;                                                                                                    \
+              uint32_t fl_[RPL];   /* (SHL_FIRST: a row is shifted as the trip found it - its own visit is its first change) */ \
+              if constexpr (SHL_FIRST) {                                                                                  \
+                _Pragma("unroll") for (int i_ = 0; i_ < RPL; ++i_) fl_[i_] = shl1(f[i_]);                                 \
+                __builtin_amdgcn_sched_barrier(0);                                                                        \
+              }                                                                                                           \
               _Pragma("unroll") for (int i_ = 0; i_ < RPL; ++i_) {                                                        \
                 const int r_ = (R0) + (D) * i_;                                                                           \
                 const uint32_t above_ = r_ == 0 ? up_ : f[r_ == 0 ? 0 : r_ - 1];                                          \
                 const uint32_t below_ = r_ == RPL - 1 ? dn_ : f[r_ == RPL - 1 ? 0 : r_ + 1];                              \
                 const uint32_t v_ = B3(f[r_] >> 1, above_, below_, T_OR3);                                              \
-                const uint32_t g_ = B3(shl1(f[r_]), v_, atari[r_], (TA | TB) & TC);                                      \
+                const uint32_t g_ = B3(SHL_FIRST ? fl_[r_] : shl1(f[r_]), v_, atari[r_], (TA | TB) & TC);                \
                 chg = B3(g_, f[r_], chg, (TA & ~TB & 0xFF) | TC);                                                         \
                 f[r_] |= g_;                                                                                              \
               }                                                                                                           \
@@ -926,6 +973,13 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
         if (capt_m) {
 #pragma unroll
           for (int r = 0; r < RPL; ++r) popp[r] = opp1[r];
+        }
+        if constexpr (MPLANE) {
+          // the new M into its plane for the job lanes of the next ply: no exec region, every lane stores its rows (a board that does
+          // not move rewrites what is there; the odd lane's last row is row N of the board and zero)
+          uint2 *pm2 = reinterpret_cast<uint2 *>(mplv + s4 * RS + r0);
+#pragma unroll
+          for (int r = 0; r < RPL; r += 2) pm2[r / 2] = make_uint2(M[r], M[r + 1]);
         }
         // (a board being reset found fl_q = on | dirty | black to move in phase 1: the register copy follows even if it does not move)
         if constexpr (GG_AB_FLAT1 != 0 && R == 19) {
