@@ -6,8 +6,9 @@ memory and the current HIP stream; every entry point of include/gymgo_amd.h is b
 pointers, from ONE table (ABI) that tests/test_host_abi.py holds against the header, and reached through
 call().  A new entry point is one declaration in the header and one entry in the table.  The area family has a header of
 its own, include/gymgo_amd_area.h, and a table of its own, ABI_AREA, bound and called the same way; so have the past family
-(include/gymgo_amd_past.h, ABI_PAST), the Gumbel root rule of the PUCT search (include/gymgo_amd_gumbel.h, ABI_GUMBEL) and the
-tactical playout policy with its planes (include/gymgo_amd_tactics.h, ABI_TACTICS).
+(include/gymgo_amd_past.h, ABI_PAST), the Gumbel root rule of the PUCT search (include/gymgo_amd_gumbel.h, ABI_GUMBEL), the
+tactical playout policy with its planes (include/gymgo_amd_tactics.h, ABI_TACTICS) and the AMAF statistics of the playouts with
+RAVE in the UCT search (include/gymgo_amd_amaf.h, ABI_AMAF).
 """
 import collections
 import ctypes
@@ -210,21 +211,37 @@ ABI_TACTICS = {
     'gg_playouts_advance_policy2': ABI['gg_playouts_advance_policy'],
     'gg_move_playouts_advance_policy2': ABI['gg_move_playouts_advance_policy'],
 }
+# ... and of include/gymgo_amd_amaf.h, the AMAF / RAVE header, in its order (tests/test_amaf_host.py holds it against its header).
+# uint16_t * (the move log) is an int16 tensor, as uint32_t * is an int32 one
+_I16 = torch.int16
+ABI_AMAF = {
+    'gg_batch_rollout_tracked_log': (_params(_I32, 'tracked') + _ROLL + _params(_i64, 'B') + _params(_i32, 'N', 'plies', 'policy')
+                                     + _params(_I16, 'log') + _STREAM),
+    'gg_playouts_advance_amaf': (_params(_I32, 'roots') + _JOBS + _CHUNKS + _params(_i32, 'policy') + _QUEUE
+                                 + _params(_I32, 'ownership') + _params(_I16, 'log') + _params(_I32, 'first') + _params(_I64, 'mark')
+                                 + _params(_I32, 'amaf') + _STREAM),
+    'gg_uct_select_rave': (_RNI + _params(_i32, 'K') + _params(_f64, 'c', 'rave_equiv', 'fpu') + _params(torch.float64, 'log_table')
+                           + _params(_I32, 'boards', 'child', 'links', 'stats', 'node_amaf', 'nodes') + _LEAF),
+    'gg_uct_backup_rave': (_RNI + _params(_i32, 'K') + _params(_I32, 'counts') + _params(_I64, 'sums') + _params(_I32, 'amaf')
+                           + _params(_I64, 'totals') + _params(_I32, 'boards', 'links', 'stats', 'node_amaf') + _LEAF),
+}
 EXPORTS = tuple(ABI)
 EXPORTS_AREA = tuple(ABI_AREA)
 EXPORTS_PAST = tuple(ABI_PAST)
 EXPORTS_GUMBEL = tuple(ABI_GUMBEL)
 EXPORTS_TACTICS = tuple(ABI_TACTICS)
+EXPORTS_AMAF = tuple(ABI_AMAF)
 _signatures = lambda table: {f: ([p.kind if isinstance(p.kind, type) else _vp for p in ps], _i32) for f, ps in table.items()}
 _SIGNATURES = _signatures(ABI)   # argtypes, restype
 _SIGNATURES_AREA = _signatures(ABI_AREA)
 _SIGNATURES_PAST = _signatures(ABI_PAST)
 _SIGNATURES_GUMBEL = _signatures(ABI_GUMBEL)
 _SIGNATURES_TACTICS = _signatures(ABI_TACTICS)
+_SIGNATURES_AMAF = _signatures(ABI_AMAF)
 # call(): the number of parameters and (index, dtypes, name) of every pointer to device memory
 _POINTERS = {f: (len(ps), tuple((i, p.kind if isinstance(p.kind, tuple) else (p.kind,), p.name)
                                 for i, p in enumerate(ps) if not isinstance(p.kind, type)))
-             for table in (ABI, ABI_AREA, ABI_PAST, ABI_GUMBEL, ABI_TACTICS) for f, ps in table.items()}
+             for table in (ABI, ABI_AREA, ABI_PAST, ABI_GUMBEL, ABI_TACTICS, ABI_AMAF) for f, ps in table.items()}
 
 _lib = None
 
@@ -239,7 +256,7 @@ def build(force=False):
     csrc = os.path.join(_HERE, 'csrc')
     srcs = [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(('.hip', '.h'))]
     srcs += [os.path.join(os.path.dirname(_HERE), 'include', h) for h in ('gymgo_amd.h', 'gymgo_amd_area.h', 'gymgo_amd_past.h', 'gymgo_amd_gumbel.h',
-                                                                                  'gymgo_amd_tactics.h')]
+                                                                                  'gymgo_amd_tactics.h', 'gymgo_amd_amaf.h')]
     stale = not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < max(os.path.getmtime(f) for f in srcs)
     if force or stale:
         subprocess.check_call(['make', '-C', os.path.join(_HERE, 'csrc'), '-s', '-B', '-j3'])
@@ -255,7 +272,8 @@ def lib():
                 'gymgo_amd has no CPU fallback' % LIB_PATH)
         L = ctypes.CDLL(LIB_PATH)
         for name, (argtypes, restype) in (list(_SIGNATURES.items()) + list(_SIGNATURES_AREA.items()) + list(_SIGNATURES_PAST.items())
-                                          + list(_SIGNATURES_GUMBEL.items()) + list(_SIGNATURES_TACTICS.items())):
+                                          + list(_SIGNATURES_GUMBEL.items()) + list(_SIGNATURES_TACTICS.items())
+                                          + list(_SIGNATURES_AMAF.items())):
             fn = getattr(L, name)  # AttributeError if the .so does not export what the header declares
             fn.argtypes, fn.restype = argtypes, restype
         if L.gg_version() != ABI_VERSION:
@@ -404,7 +422,7 @@ def ptrs(fn, **tensors):
     """dev_ptr of every tensor as the parameter of entry point `fn` it is named after - dtype(s) from the table -, in the order
     given: for the paths that check their buffers once and hand call() the pointers from then on."""
     kinds = {p.name: p.kind for p in (ABI[fn] if fn in ABI else ABI_AREA[fn] if fn in ABI_AREA else ABI_PAST[fn] if fn in ABI_PAST
-                                      else ABI_GUMBEL[fn] if fn in ABI_GUMBEL else ABI_TACTICS[fn])}
+                                      else ABI_GUMBEL[fn] if fn in ABI_GUMBEL else ABI_TACTICS[fn] if fn in ABI_TACTICS else ABI_AMAF[fn])}
     return tuple(dev_ptr(t, kinds[n], n) for n, t in tensors.items())
 
 

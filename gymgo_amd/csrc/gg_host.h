@@ -60,6 +60,12 @@ void launch_rollout_lat(int io, uint8_t *st, uint64_t *rng, int32_t *last_action
                         int auto_reset, bool w4, hipStream_t s);
 void launch_rollout_lat_policy(uint8_t *st, uint64_t *rng, int32_t *last_actions, int64_t *steps_done, int64_t B, int32_t N, int plies,
                                int auto_reset, int policy, hipStream_t s);
+// gg_r5_log.hip / gg_lat_log.hip: the move-log variants of the two families (tracked boards, auto_reset = 0, policy 0 / 1 / 2; log:
+// uint16 [B][plies])
+void launch_rollout5_log(int N, uint8_t *st, uint64_t *rng, int32_t *last_actions, int64_t *steps_done, int64_t B, uint32_t inv,
+                         int plies, int policy, int nb, int grid, uint16_t *log, hipStream_t s);
+void launch_rollout_lat_log(uint8_t *st, uint64_t *rng, int32_t *last_actions, int64_t *steps_done, int64_t B, int32_t N, int plies,
+                            int policy, uint16_t *log, hipStream_t s);
 void launch_env_step_lat(uint32_t *tracked, uint64_t *rng, int64_t *steps_done, int64_t B, int32_t N, int auto_reset,
                          const EnvArgs &env, bool w4, hipStream_t s);
 

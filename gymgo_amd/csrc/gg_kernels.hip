@@ -6,7 +6,8 @@
 // big batches), gg_po.h (Monte Carlo playouts: the fill / harvest kernel of the playout queue and the plan of legal first
 // moves), gg_uct.h (UCT tree search: begin, select, backup) and gg_puct.h (PUCT tree search with priors and an outside
 // evaluator: begin, select, backup).  The playout and search entry points launch the multi-ply
-// kernels through gg_batch_rollout_tracked, whose launches live in the other three translation units.  Which kernel serves an entry point depends on the arguments only (board size, batch size, plies per
+// kernels through gg_batch_rollout_tracked - or, for the AMAF playouts and RAVE (include/gymgo_amd_amaf.h), through gg_batch_rollout_tracked_log -, whose
+// launches live in the other five rollout translation units (gg_rollout.hip, gg_lat.hip, gg_r5.hip, gg_lat_log.hip, gg_r5_log.hip).  Which kernel serves an entry point depends on the arguments only (board size, batch size, plies per
 // launch) and on the CU count the grids are sized for - the device's own, or GYMGO_AMD_CUS (forced_cus below), the one
 // environment variable the shipped build reads; results depend on neither.  Mutable global state, all of it performance-only
 // (no result depends on any of it): g_cus (CU count per device, relaxed atomics: racing first callers store the same value), the
@@ -37,6 +38,7 @@
 #include "gg_puct.h"
 #include "gymgo_amd.h"
 #include "gymgo_amd_tactics.h"
+#include "gymgo_amd_amaf.h"
 
 namespace {
 
@@ -491,6 +493,14 @@ static int32_t puct_leaves_args(PuctArgs &u, int64_t R, int32_t N, int32_t C, in
     return e;
   if (L < 1 || L > C) return GG_E_BADARG;
   u.L = L;
+  return 0;
+}
+
+// ---- RAVE (gg_uct.h): uct_args, then what the two RAVE entry points add to it
+static int32_t rave_args(RaveArgs &u, int32_t I, int32_t K, double rave_equiv, double fpu, const int32_t *node_amaf, const int32_t *amaf) {
+  if (2 * (int64_t)I * K > 0x7FFFFFFF) return GG_E_BADSIZE;   // s~ <= 2 I K is an int32
+  if (!(rave_equiv > 0.0 && rave_equiv <= __DBL_MAX__) || !(fpu >= -__DBL_MAX__ && fpu <= __DBL_MAX__)) return GG_E_BADARG;
+  u.node_amaf = const_cast<int32_t *>(node_amaf); u.amaf = amaf; u.k = rave_equiv; u.fpu = fpu;
   return 0;
 }
 }  // namespace
@@ -1024,6 +1034,24 @@ int32_t gg_batch_rollout_tracked_policy2(uint32_t *tracked, uint64_t *rng, int32
   return rollout_tracked_policy(tracked, rng, last_actions, steps_done, B, N, plies, auto_reset, policy, GG_POLICY_TACTICAL, hip_stream);
 }
 
+// The move log (include/gymgo_amd_amaf.h): rollout_tracked_policy's dispatch for policies 1 and 2, for the uniform policy
+// too - the band its plain path gives to k_rollout4 goes to the one-row-per-lane kernel -, on the log variants of the two families.
+int32_t gg_batch_rollout_tracked_log(uint32_t *tracked, uint64_t *rng, int32_t *last_actions, int64_t *steps_done, int64_t B,
+                                     int32_t N, int32_t plies, int32_t policy, uint16_t *log, void *hip_stream) {
+  if (plies < 0 || plies > 4096 || !policy_ok(policy, GG_POLICY_TACTICAL)) return GG_E_BADARG;
+  GG_ENTER(tracked);
+  if (plies == 0) return 0;
+  if (!rng || !log) return GG_E_NULLPTR;
+  uint8_t *st = reinterpret_cast<uint8_t *>(tracked);
+  if (!use_lat(cus, B, N, plies, true) && use_rollout5(cus, B, N, plies)) {
+    const WaveGrid w5 = boards_per_wave5(cus, B);
+    launch_rollout5_log(N, st, rng, last_actions, steps_done, B, inv, plies, policy, w5.nb, w5.grid, log, s);
+    return (int32_t)hipGetLastError();
+  }
+  launch_rollout_lat_log(st, rng, last_actions, steps_done, B, N, plies, policy, log, s);
+  return (int32_t)hipGetLastError();
+}
+
 int32_t gg_batch_eye_mask(const uint8_t *states, uint8_t *mask, int64_t B, int32_t N, void *hip_stream) {
   GG_ENTER(states);
   if (!mask) return GG_E_NULLPTR;
@@ -1209,6 +1237,31 @@ int32_t gg_playouts_advance_policy2(const uint32_t *roots, int64_t R, int32_t N,
   return po_advance(a, N, chunk_plies, chunks, policy, GG_POLICY_TACTICAL, hip_stream);
 }
 
+// AMAF playouts (include/gymgo_amd_amaf.h): po_advance with the chunks on the log variants and the harvest on AmafArgs
+int32_t gg_playouts_advance_amaf(const uint32_t *roots, int64_t R, int32_t N, int32_t K, int64_t first_root, uint64_t base_seed,
+                                 int32_t max_plies, int32_t chunk_plies, float komi, int32_t chunks, int32_t policy,
+                                 uint32_t *slots, uint64_t *rng, int64_t *plies, int64_t *job, int64_t S, int64_t *counter,
+                                 int32_t *counts, int64_t *sums, int32_t *ownership, uint16_t *log, uint32_t *first,
+                                 int64_t *mark, int32_t *amaf, void *hip_stream) {
+  AmafArgs a;
+  if (int32_t e = po_args(a, 1, R, true, true, roots, R, N, K, first_root, base_seed, max_plies, chunk_plies, komi, slots, rng, plies,
+                          job, S, counter, counts, sums, ownership))
+    return e;
+  if (chunks < 0 || !policy_ok(policy, GG_POLICY_TACTICAL) || chunk_plies > 4096) return GG_E_BADARG;
+  if (!log || !first || !mark || !amaf) return GG_E_NULLPTR;
+  a.log = log; a.first = first; a.mark = mark; a.amaf = amaf; a.chunk_plies = chunk_plies;
+  if (a.J == 0 || chunks == 0) return 0;
+  OnDeviceOf on_dev(a.slots);
+  const int cus = on_dev.cus();
+  hipStream_t s = (hipStream_t)hip_stream;
+  for (int c = 0; c < chunks; ++c) {
+    if (int32_t e = gg_batch_rollout_tracked_log(a.slots, a.rng, nullptr, a.plies, a.S, N, chunk_plies, policy, log, hip_stream)) return e;
+    launch_harvest<false>(a, N, cus, s);
+    if (int32_t e = (int32_t)hipGetLastError()) return e;
+  }
+  return 0;
+}
+
 int32_t gg_move_playouts_plan(const uint32_t *roots, int64_t R, int32_t N, int32_t *offsets, int32_t *plan, void *hip_stream) {
   if (N < 2 || N > GG_MAX_BOARD || R < 0) return GG_E_BADSIZE;
   if (R > (int64_t)0x7FFFFFFF / (N * N + 1)) return GG_E_BADSIZE;   // plan entries r A + a are int32
@@ -1304,6 +1357,32 @@ int32_t gg_uct_backup(int64_t R, int32_t N, int32_t I, int32_t K, const int32_t 
   if (!counts || !sums || !boards || !links || !stats || !leaf || !move || !leaf_id) return GG_E_NULLPTR;
   if (R == 0) return 0;
   return launch_roots(k_uct_backup, leaf, R, hip_stream, u);
+}
+
+int32_t gg_uct_select_rave(int64_t R, int32_t N, int32_t I, int32_t K, double c, double rave_equiv, double fpu,
+                           const double *log_table, const uint32_t *boards, int32_t *child, int32_t *links, int32_t *stats,
+                           const int32_t *node_amaf, int32_t *nodes, uint32_t *leaf, int32_t *move, int32_t *leaf_id,
+                           void *hip_stream) {
+  RaveArgs u;
+  if (int32_t e = uct_args(u, R, N, I, K, c, boards, child, links, stats, nodes, leaf, move, leaf_id, log_table)) return e;
+  if (int32_t e = rave_args(u, I, K, rave_equiv, fpu, node_amaf, nullptr)) return e;
+  if (!log_table || !boards || !child || !links || !stats || !node_amaf || !nodes || !leaf || !move || !leaf_id) return GG_E_NULLPTR;
+  if (R == 0) return 0;
+  return launch_roots(k_uct_select_rave, leaf, R, hip_stream, u);
+}
+
+int32_t gg_uct_backup_rave(int64_t R, int32_t N, int32_t I, int32_t K, const int32_t *counts, const int64_t *sums,
+                           const int32_t *amaf, int64_t *totals, uint32_t *boards, const int32_t *links, int32_t *stats,
+                           int32_t *node_amaf, const uint32_t *leaf, const int32_t *move, const int32_t *leaf_id,
+                           void *hip_stream) {
+  RaveArgs u;
+  if (int32_t e = uct_args(u, R, N, I, K, 0.0, boards, nullptr, links, stats, nullptr, leaf, move, leaf_id, nullptr, counts, sums,
+                           totals))
+    return e;
+  if (int32_t e = rave_args(u, I, K, 1.0, 0.0, node_amaf, amaf)) return e;
+  if (!counts || !sums || !amaf || !boards || !links || !stats || !node_amaf || !leaf || !move || !leaf_id) return GG_E_NULLPTR;
+  if (R == 0) return 0;
+  return launch_roots(k_uct_backup_rave, leaf, R, hip_stream, u);
 }
 
 int32_t gg_puct_begin(const uint32_t *roots, int64_t R, int32_t N, int32_t I, uint32_t *boards, int32_t *child, float *prior,

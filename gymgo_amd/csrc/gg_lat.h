@@ -539,11 +539,13 @@ struct LdsLat {
 // WPB: waves per workgroup, each wave an independent group of boards (a launch of single-wave workgroups enters the machine over
 // ~0.26 ns per workgroup - tools/exp/oneply_ramp.py - which a ONE-ply launch of a thousand workgroups feels: k_rollout_lat_w4)
 // POL: the playout policy of the draw (kPolUniform; kPolNoEyeFill, kPolTactical: tracked boards, the plain form - DESIGN 15, 34)
-template <int R, bool FULLN, bool AUTO, int IO, int WPB, bool SHORT, int POL = kPolUniform>
+// LOG: the move log (k_rollout_lat_log): mvlog uint16 [B][plies], entry [b][t] = the action board b played at ply t of the
+// launch (a point, or N^2 for the pass), stored by one lane of the board; a board that is not live on a ply stores nothing
+template <int R, bool FULLN, bool AUTO, int IO, int WPB, bool SHORT, int POL = kPolUniform, bool LOG = false>
 __device__ __forceinline__ void rollout_lat_body(uint8_t *__restrict__ states, uint64_t *__restrict__ rng,
                                                  int32_t *__restrict__ last_actions,
                                                  int64_t *__restrict__ steps_done, int64_t B, int N, int plies,
-                                                 int auto_reset) {
+                                                 int auto_reset, uint16_t *__restrict__ mvlog = nullptr) {
   using L = Lat<R>;
   constexpr int LPB = L::LPB, NBW = L::NBW, FW = L::FW, NF = L::NF, NREG = L::NREG;
   if (FULLN) N = R;
@@ -710,6 +712,10 @@ __device__ __forceinline__ void rollout_lat_body(uint8_t *__restrict__ states, u
       {   // the action of the board's last live ply: the hit lane holds it, every lane holds a pass, the others -1
         const int cand = hit ? rN + (int)pos : (pass ? P : -1);
         lastv = (int)B3(lv, (uint32_t)cand, (uint32_t)lastv, T_SEL);
+        // the log: the lane that holds the point, or the board's first lane on a pass (live: the board exists, b < B, and t < plies)
+        if constexpr (LOG) {
+          if (live && (hit || (pass && r == 0))) mvlog[b * (int64_t)plies + t] = (uint16_t)cand;
+        }
       }
       played -= (int)lv;
       GG_PROF(0);
@@ -757,6 +763,14 @@ __global__ __launch_bounds__(kWave, 4) void k_rollout_lat_pol(uint8_t *__restric
                                                               int64_t *__restrict__ steps_done, int64_t B, int N, int plies,
                                                               int auto_reset) {
   rollout_lat_body<R, FULLN, AUTO, 2, 1, false, POL>(states, rng, last_actions, steps_done, B, N, plies, auto_reset);
+}
+// tracked boards without auto-reset, the plain form with the move log, once per playout policy
+template <int R, bool FULLN, int POL>
+__global__ __launch_bounds__(kWave, 4) void k_rollout_lat_log(uint8_t *__restrict__ states, uint64_t *__restrict__ rng,
+                                                              int32_t *__restrict__ last_actions,
+                                                              int64_t *__restrict__ steps_done, int64_t B, int N, int plies,
+                                                              uint16_t *__restrict__ mvlog) {
+  rollout_lat_body<R, FULLN, false, 2, 1, false, POL, true>(states, rng, last_actions, steps_done, B, N, plies, 0, mvlog);
 }
 // tracked boards, a few plies per launch: four waves per workgroup
 template <int R, bool FULLN, bool AUTO, bool SHORT>

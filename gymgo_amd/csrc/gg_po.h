@@ -69,6 +69,18 @@ struct MpArgs : PoArgs {  // J = T K; first_job and own unused
   int32_t A;
 };
 
+// AMAF playouts (gg_playouts_advance_amaf, include/gymgo_amd_amaf.h): the chunks log their moves (the log variants of
+// the rollout kernels), and every harvest folds the new entries of every live slot into the slot's first-play rows - the points
+// black / white played first in the slot's current job - before anything else; a finished slot adds them to its root's counters
+// with the scored outcome, a refilled or emptied slot starts from zero rows.
+struct AmafArgs : PoArgs {
+  const uint16_t *log;   // [S][chunk_plies] the actions of the last chunk, entry t = the ply t of that launch
+  uint32_t *first;       // [S][2][N] rows of the points black / white played first in the slot's current job
+  int64_t *mark;         // [S] plies of the slot's job at the last harvest
+  int32_t *amaf;         // [R][2][3][N][N] per root and colour: first plays, those in black wins, those in white wins
+  int32_t chunk_plies;
+};
+
 // FILL (gg_playouts_begin): slot s takes job s (an empty, frozen board from s = J on) and the counter is set to
 // {min(S, J), J + min(S, J)}.  HARVEST (gg_playouts_advance, after every rollout chunk): see the file's header.
 // MOVE (gg_move_playouts_*): a refill loads the pair's root into the registers of the ply (as env_step_lat_body does), plays
@@ -77,6 +89,8 @@ struct MpArgs : PoArgs {  // J = T K; first_job and own unused
 template <int R, bool FULLN, bool FILL, typename Args = PoArgs>
 __global__ __launch_bounds__(kWave) void k_po_harvest(Args a, int N) {
   constexpr bool MOVE = std::is_same<Args, MpArgs>::value;
+  constexpr bool AMAF = std::is_same<Args, AmafArgs>::value;
+  static_assert(!(AMAF && FILL), "the AMAF queue is filled by the plain fill");
   using L = Lat<R>;
   constexpr int LPB = L::LPB, NBW = L::NBW;
   if (FULLN) N = R;
@@ -102,6 +116,56 @@ __global__ __launch_bounds__(kWave) void k_po_harvest(Args a, int N) {
         flag = slot[5 * N];
       }
       fin = valid && jid >= 0 && ((flag & 4u) != 0 || a.plies[s] >= a.max_plies);
+    }
+    // AMAF: the fold.  The lane of row r takes the new log entries of its slot - the plies since the last harvest, t < plies[s] -
+    // mark[s] <= chunk_plies - that fall in its row and are in neither row yet; ply i of a job is played by the root's mover,
+    // flipped for every earlier ply (passes included).  The entries come LPB at a time: lane i of the board loads entry t0 + i (one
+    // coalesced 2-byte load per lane), and the board walks them in ply order by ds_bpermute - every lane of the wave takes part in
+    // the walk, an entry beyond the board's count reads as 0xFFFF, which lies in no row.
+    uint32_t fb = 0, fw = 0;
+    if constexpr (AMAF) {
+      const bool livejob = valid && jid >= 0;
+      int64_t mk = 0;
+      int nt = 0;
+      uint32_t col0 = 0;
+      uint32_t *fr = a.first + (2 * (valid ? s : 0) * N + (r < N ? r : 0));
+      if (livejob) {
+        mk = a.mark[s];
+        const int64_t np = a.plies[s] - mk;
+        nt = np < 0 ? 0 : (np > a.chunk_plies ? a.chunk_plies : (int)np);
+        col0 = (a.roots[(jid / a.K) * W + 5 * N] ^ (uint32_t)mk) & 1u;
+        if (r < N) {
+          fb = fr[0];
+          fw = fr[N];
+        }
+      }
+      int ntw = nt;   // the longest walk of the wave's boards
+#pragma unroll
+      for (int o = kWave / 2; o > 0; o >>= 1) ntw = max(ntw, __shfl_xor(ntw, o));
+      const uint16_t *lg = a.log + (valid ? s : 0) * (int64_t)a.chunk_plies;
+      const int lo = r * N, hi = r < N ? lo + N : lo;
+      const int lane_b0 = lane & ~(LPB - 1);
+      for (int t0 = 0; t0 < ntw; t0 += LPB) {
+        const int mine = t0 + r < nt ? (int)lg[t0 + r] : 0xFFFF;
+        const int lim = ntw - t0 < LPB ? ntw - t0 : LPB;
+        for (int k = 0; k < lim; ++k) {
+          const int act = __shfl(mine, lane_b0 + k);
+          if (act >= lo && act < hi) {
+            const uint32_t bit = 1u << (act - lo);
+            if (!((fb | fw) & bit)) {
+              if ((col0 ^ (uint32_t)(t0 + k)) & 1u) fw |= bit;
+              else fb |= bit;
+            }
+          }
+        }
+      }
+      if (livejob && !fin) {   // (a finished slot's rows go to amaf below and are zeroed with the refill)
+        if (r < N) {
+          fr[0] = fb;
+          fr[N] = fw;
+        }
+        if (r == 0) a.mark[s] = mk + nt;
+      }
     }
     const uint64_t lead = __ballot(fin && r == 0);   // one bit per finished board, at its first lane
     if (lead == 0) continue;
@@ -131,6 +195,22 @@ __global__ __launch_bounds__(kWave) void k_po_harvest(Args a, int N) {
           int32_t *pb = a.own + (2 * root * N + r) * N, *pw = pb + N * N;
           for (uint32_t m = ob; m; m &= m - 1) atomicAdd(pb + __builtin_ctz(m), 1);
           for (uint32_t m = ow; m; m &= m - 1) atomicAdd(pw + __builtin_ctz(m), 1);
+        }
+        if constexpr (AMAF) {   // the finished job's first plays, with the outcome scored above: one vector atomic per set bit
+          if (r < N) {
+            const float x = (float)((int)ab - (int)aw) - a.komi;
+            const int win = x > 0.f ? 1 : (x < 0.f ? 2 : 0);
+            const int64_t PP = (int64_t)N * N;
+            int32_t *qb = a.amaf + 6 * root * PP + r * N, *qw = qb + 3 * PP;
+            for (uint32_t m = fb; m; m &= m - 1) {
+              atomicAdd(qb + __builtin_ctz(m), 1);
+              if (win) atomicAdd(qb + win * PP + __builtin_ctz(m), 1);
+            }
+            for (uint32_t m = fw; m; m &= m - 1) {
+              atomicAdd(qw + __builtin_ctz(m), 1);
+              if (win) atomicAdd(qw + win * PP + __builtin_ctz(m), 1);
+            }
+          }
         }
       }
       // the wave's finished boards: one returning atomicAdd takes their job ids (ids from J on: none left; every
@@ -181,6 +261,13 @@ __global__ __launch_bounds__(kWave) void k_po_harvest(Args a, int N) {
       }
     }
     if (!fin) continue;
+    if constexpr (AMAF) {   // a refilled or emptied slot starts from zero rows
+      if (r < N) {
+        a.first[2 * s * N + r] = 0u;
+        a.first[(2 * s + 1) * N + r] = 0u;
+      }
+      if (r == 0) a.mark[s] = 0;
+    }
     if (next < a.J) {   // refill: the root's words, a fresh generator, the ply count from zero
       const int64_t root = next / a.K;
       const uint32_t *src = a.roots + root * W;

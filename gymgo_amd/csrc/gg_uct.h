@@ -182,4 +182,217 @@ static __global__ __launch_bounds__(4 * kWave) void k_uct_backup(UctArgs a) {
   }
 }
 
+// ---- RAVE (gg_uct_select_rave / gg_uct_backup_rave, include/gymgo_amd_amaf.h): per node x and point p the pair
+// (n~, s~) - the simulations through x in which x's mover played p first after x, twice its wins plus the draws among them -
+// mixed into the value of every legal action, expanded or not, so that a node descends as soon as one action stands out.
+struct RaveArgs : UctArgs {
+  int32_t *node_amaf;      // [R][I+1][N^2][2] n~, s~
+  const int32_t *amaf;     // [R][2][3][N][N] the iteration's first-play counts (backup)
+  double k, fpu;           // rave_equiv, the value of an action without any count
+};
+
+// U(x, a) of the RAVE select in float64, each operation rounded to nearest in the order written, no contraction (the host
+// restatement computes the same expression in IEEE doubles): s = 2 w + d and s~ arrive as integers
+__device__ __noinline__ double rave_score(int32_t n, int32_t s, int32_t nt, int32_t st, double log_nx, double c, double k, double fpu) {
+#pragma clang fp contract(off)
+  const double dn = (double)n, dnt = (double)nt;
+  double v;
+  if (n > 0 && nt > 0) {
+    const double q = (double)s / (2.0 * dn), qt = (double)st / (2.0 * dnt);
+    const double beta = dnt / (dn + dnt + (dn * dnt) / k);
+    v = (1.0 - beta) * q + beta * qt;
+  } else if (n > 0) {
+    v = (double)s / (2.0 * dn);
+  } else if (nt > 0) {
+    v = (double)st / (2.0 * dnt);
+  } else {
+    v = fpu;
+  }
+  return n > 0 ? v + c * __dsqrt_rn(log_nx / dn) : v;
+}
+
+static __global__ __launch_bounds__(4 * kWave) void k_uct_select_rave(RaveArgs a) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t wave = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) / kWave;
+  const int64_t nwaves = (gridDim.x * (int64_t)blockDim.x) / kWave;
+  const int N = a.N, W = 5 * N + 1, P = N * N, A = P + 1, NN = a.I + 1;
+  for (int64_t r = wave; r < a.R; r += nwaves) {
+    const uint32_t *bd = a.boards + r * NN * W;
+    int32_t *ch = a.child + r * NN * A;
+    int32_t *st = a.stats + r * NN * 4;
+    const int2 *na = reinterpret_cast<const int2 *>(a.node_amaf) + r * NN * P;
+    const int nodes = min(a.nodes[r], NN);   // (nodes <= I + 1 by construction: every index below stays inside the tree)
+    int x = 0, mv = -1, y = 0;
+    // every step goes to a child with a larger id: at most I steps (the bound also stops a walk over corrupt links)
+    for (int depth = 0; depth <= a.I; ++depth) {
+      const uint32_t *g = bd + (int64_t)x * W;
+      const uint32_t flag = g[5 * N];
+      y = x;
+      if (flag & 4u) break;   // the game has ended at x: x is the leaf, nothing is added
+      const int t = st[4 * x] / a.K;   // n_x is a multiple of K, at most I K
+      const double lx = a.log_table[t < 0 ? 0 : (t > a.I ? a.I : t)];
+      const bool white = (flag & 1u) != 0;
+      double best = -__builtin_inf();
+      int besta = A;
+      for (int a0 = 0; a0 < A; a0 += kWave) {
+        const int act = a0 + lane;
+        if (act >= A) continue;
+        const int row = act / N;
+        const bool legal = act == P || !((g[2 * N + (act < P ? row : 0)] >> (act - row * N)) & 1u);
+        if (!legal) continue;
+        const int c = ch[(int64_t)x * A + act];
+        int32_t n = 0, s = 0, nt = 0, sw = 0;
+        if (c > x && c < nodes) {   // (children always have larger ids than their parent)
+          const int4 q = reinterpret_cast<const int4 *>(st)[c];
+          n = q.x;
+          s = 2 * (white ? q.z : q.y) + q.w;
+        }
+        if (act < P) {
+          const int2 e = na[(int64_t)x * P + act];
+          nt = e.x;
+          sw = e.y;
+        }
+        const double u = rave_score(n, s, nt, sw, lx, a.c, a.k, a.fpu);
+        if (u > best) {   // (this lane's actions ascend: the first of equal scores stays)
+          best = u;
+          besta = act;
+        }
+      }
+      // the wave's argmax, ties to the lowest action
+#pragma unroll
+      for (int o = kWave / 2; o > 0; o >>= 1) {
+        const double ob = __shfl_xor(best, o);
+        const int oa = __shfl_xor(besta, o);
+        if (ob > best || (ob == best && oa < besta)) {
+          best = ob;
+          besta = oa;
+        }
+      }
+      if (besta >= A) break;   // (no action scored: only with corrupt buffers - the pass is always legal)
+      const int nx = ch[(int64_t)x * A + besta];
+      if (nx < 0) {   // the winner has no child: expand it
+        if (nodes <= a.I) {   // (a select beyond I iterations finds no room: x is evaluated as it is)
+          y = nodes;
+          mv = besta;
+          if (lane == 0) {
+            ch[(int64_t)x * A + besta] = y;
+            a.links[(r * NN + y) * 2] = x;
+            a.links[(r * NN + y) * 2 + 1] = besta;
+            reinterpret_cast<int4 *>(st)[y] = make_int4(0, 0, 0, 0);
+            a.nodes[r] = nodes + 1;
+          }
+        }
+        break;
+      }
+      if (nx <= x || nx >= nodes) break;   // (only with corrupt buffers: stop here)
+      x = nx;
+      y = x;
+    }
+    // the leaf board: the new node's parent (its move is played by the next launch) or the node itself
+    const uint32_t *g = bd + (int64_t)x * W;
+    uint32_t *out = a.leaf + r * W;
+    for (int k = lane; k < W; k += kWave) out[k] = g[k];
+    if (lane == 0) {
+      a.move[r] = mv;
+      a.leaf_id[r] = y;
+    }
+  }
+}
+
+// One wave per root, the lanes stride over the points: lane l owns the points l, l + 64, ... (at most kRavePts = 6 on 19x19) and
+// keeps, per point, the path index of its first occurrence among the tree moves below the node the walk stands at.
+constexpr int kRavePts = (19 * 19 + kWave - 1) / kWave;
+static __global__ __launch_bounds__(4 * kWave) void k_uct_backup_rave(RaveArgs a) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t wave = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) / kWave;
+  const int64_t nwaves = (gridDim.x * (int64_t)blockDim.x) / kWave;
+  const int N = a.N, W = 5 * N + 1, NN = a.I + 1, P = N * N;
+  for (int64_t r = wave; r < a.R; r += nwaves) {
+    const int y = a.leaf_id[r];
+    if (y < 0 || y >= NN) continue;
+    const uint32_t *src = a.leaf + r * W;
+    if (a.move[r] >= 0) {   // a new node: the played board is its board
+      uint32_t *dst = a.boards + (r * NN + y) * W;
+      for (int k = lane; k < W; k += kWave) dst[k] = src[k];
+    }
+    const int32_t *cn = a.counts + 4 * r;
+    const int32_t bw = cn[0], ww = cn[1], d = cn[2];
+    int32_t *st = a.stats + r * NN * 4;
+    const int32_t *ln = a.links + r * NN * 2;
+    if (lane == 0) {
+      int x = y;
+      for (int depth = 0; depth <= a.I && x >= 0 && x < NN; ++depth) {   // (parents have smaller ids: at most I + 1 nodes)
+        st[4 * x] += a.K;
+        st[4 * x + 1] += bw;
+        st[4 * x + 2] += ww;
+        st[4 * x + 3] += d;
+        x = ln[2 * x];
+      }
+      if (a.totals) {
+        a.totals[2 * r] += cn[3];
+        a.totals[2 * r + 1] += a.sums[2 * r + 1];
+      }
+    }
+    // the playout's part per owned point and colour: (first plays, twice the colour's wins plus the draws among them)
+    int32_t pn[2][kRavePts], ps[2][kRavePts];
+    int firstj[kRavePts];   // path index j of the first tree move below the current node at this point, 0 = none
+    const int32_t *am = a.amaf + r * 6 * (int64_t)P;
+#pragma unroll
+    for (int k = 0; k < kRavePts; ++k) {
+      const int p = lane + k * kWave;
+      firstj[k] = 0;
+#pragma unroll
+      for (int c = 0; c < 2; ++c) {
+        pn[c][k] = ps[c][k] = 0;
+        if (p < P) {
+          const int32_t e0 = am[(3 * c) * P + p], e1 = am[(3 * c + 1) * P + p], e2 = am[(3 * c + 2) * P + p];
+          pn[c][k] = e0;
+          ps[c][k] = 2 * (c ? e2 : e1) + e0 - e1 - e2;
+        }
+      }
+    }
+    // the depth of the leaf: the links up to the root (parents have smaller ids: at most I of them, whatever the buffers hold)
+    int dpt = 0;
+    for (int x = y; dpt < a.I; ++dpt) {
+      const int p = ln[2 * x];
+      if (p < 0 || p >= x) break;
+      x = p;
+    }
+    // from the leaf up: node x = x_i gets its update, then the move that led to it joins the front of the sequence
+    int x = y;
+    for (int i = dpt; i >= 0; --i) {
+      // (the leaf's board is in `leaf`, whether it is a new node or not; every other node's board was stored by an earlier launch)
+      const uint32_t c = (i == dpt ? src[5 * N] : a.boards[(r * NN + x) * W + 5 * N]) & 1u;
+      const int32_t S = 2 * (c ? ww : bw) + d;
+      int2 *na = reinterpret_cast<int2 *>(a.node_amaf) + (r * NN + x) * (int64_t)P;
+#pragma unroll
+      for (int k = 0; k < kRavePts; ++k) {
+        const int p = lane + k * kWave;
+        if (p >= P) continue;
+        int32_t dn, ds;
+        if (firstj[k] == 0) {
+          dn = c ? pn[1][k] : pn[0][k];
+          ds = c ? ps[1][k] : ps[0][k];
+        } else {
+          const bool mine = ((firstj[k] - i) & 1) != 0;
+          dn = mine ? a.K : 0;
+          ds = mine ? S : 0;
+        }
+        if (dn | ds) {
+          int2 e = na[p];
+          e.x += dn;
+          e.y += ds;
+          na[p] = e;
+        }
+      }
+      if (i == 0) break;
+      const int m = ln[2 * x + 1];
+#pragma unroll
+      for (int k = 0; k < kRavePts; ++k)
+        if (m >= 0 && m == lane + k * kWave && m < P) firstj[k] = i;
+      x = ln[2 * x];
+    }
+  }
+}
+
 }  // namespace gg

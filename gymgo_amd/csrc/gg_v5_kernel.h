@@ -2,15 +2,23 @@
 // GG_R5_POL = the policy of its draw (kPolUniform: k_rollout5; kPolNoEyeFill: k_rollout5_pol; kPolTactical: k_rollout5_tac).  Textual inclusion
 // and not a shared inline body: k_rollout5 stays the kernel it was, instruction for instruction and by name (bench.py ties
 // its PMC record to the machine code behind the mangled name).  No include guard.
+// GG_R5_LOG (optional; defined: the move-log variants of gg_r5_log.hip): the kernel takes one more argument, mvlog uint16
+// [B][plies], and the even lane of every live pair stores the ply's action there - entry [b][t] is the action board b played at ply t of
+// the launch (a point, or N^2 for the pass); a board that is not live on a ply stores nothing.  Without it this file is what it was.
 // ws (byte planes only, nullable: gg_batch_rollout_ws): the caller's workspace, uint32 [B][5 N + 1] in the layout of a tracked board.
 // The load takes M of a board from there when its stones equal the workspace's rows EXACTLY (checked per pair of boards) and skips
 // the from-scratch analysis; the store leaves the stones and M of every board it wrote, or analysed, behind.  Words 0 .. 2 N (the
 // stones) and 3 N .. 5 N (M & black, M & white) of a board are used; the others are never touched.
+#ifdef GG_R5_LOG
+#define GG_R5_LOG_PARAM , uint16_t *__restrict__ mvlog
+#else
+#define GG_R5_LOG_PARAM
+#endif
 template <int R, int IO>
 __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ states, uint64_t *__restrict__ rng,
                                                        int32_t *__restrict__ last_actions, int64_t *__restrict__ steps_done,
                                                        int64_t B, uint32_t inv, int plies, int auto_reset, int nb,
-                                                       uint32_t *__restrict__ ws) {
+                                                       uint32_t *__restrict__ ws GG_R5_LOG_PARAM) {
   constexpr int POL = GG_R5_POL;
   static_assert(IO == 0 || IO == 2, "byte planes or tracked boards");
   constexpr int N = R;
@@ -447,6 +455,11 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
         const uint32_t pt = cand | dpp0<QP_X1>(cand);
 #endif
         a_q = !live ? -1 : (k < n ? (int)pt : P);
+#ifdef GG_R5_LOG
+        // the log: one predicated 2-byte store from the pair's even lane (live: the board exists, b_first + s4 < B, and t < plies).
+        // A store and no load: nothing in the ply waits for it (vmcnt is next looked at by the write-back)
+        if (a_q >= 0 && t5 == 0) mvlog[(b_first + s4) * (int64_t)plies + t] = (uint16_t)a_q;
+#endif
         const bool place = live && hit;
         fl_q = reset ? 40u : fl;   // a board being reset: on, dirty, black to move
         // (CMP1: both lanes of a pair agree on `reset`, the even lanes by a scalar AND)
@@ -1151,3 +1164,4 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
     GG_PROF_FLUSH;
   }
 }
+#undef GG_R5_LOG_PARAM

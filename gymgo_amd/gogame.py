@@ -720,6 +720,21 @@ def batch_rollout_tracked(tracked, rng, plies, auto_reset=True, last_actions=Non
     return tracked
 
 
+def batch_rollout_tracked_log(tracked, rng, plies, log, last_actions=None, steps_done=None, *, policy='uniform'):
+    """IN PLACE batch_rollout_tracked(..., auto_reset=False, policy=policy) that also logs its moves
+    (gg_batch_rollout_tracked_log): log is an int16 [B, plies] device tensor (the C side's uint16), entry [b, t] receives the
+    action board b played at ply t of this launch - a point, or N*N for the pass; a board writes exactly the plies it played,
+    every other entry keeps its bytes.  -> log."""
+    pol = _policy_code(policy)
+    N = _tracked_size(tracked)
+    B = tracked.shape[0]
+    if tuple(log.shape) != (B, int(plies)):
+        raise ValueError('log must be int16 [B, plies] = %s (got %s)' % ((B, int(plies)), tuple(log.shape)))
+    _lib.call('gg_batch_rollout_tracked_log', tracked, rng, last_actions, steps_done, B, N, int(plies), pol, log,
+              _lib.stream_ptr(tracked.device))
+    return log
+
+
 def batch_eye_mask(batch_states):
     """The mover's eyes of every board -> uint8 [B, N, N] (gg_batch_eye_mask): an empty point whose orthogonal neighbours on the
     board are all the mover's stones and of whose diagonal neighbours on the board at most one is the opponent's - none when
@@ -1635,6 +1650,10 @@ def batch_env_step_tracked(tracked, actions=None, rng=None, komi=0.0, reward_met
 # targets, ownership estimates.
 
 Playouts = collections.namedtuple('Playouts', 'black_wins white_wins draws unfinished margin_sum plies_sum ownership')
+PlayoutsAmaf = collections.namedtuple('PlayoutsAmaf', Playouts._fields + ('amaf',))
+PlayoutsAmaf.__doc__ = """Playouts plus amaf (batch_playouts(..., amaf=True)): int32 [R, 2, 3, N, N] - per root and colour (0 black,
+1 white), [0]: in how many playouts the colour was the first to play the point (all-moves-as-first), [1] / [2]: how many of
+those were scored as a black / a white win."""
 Playouts.__doc__ = """Per-root results of batch_playouts: black_wins / white_wins / draws / unfinished (int32: outcome
 sign(black - white - komi); playouts cut off by max_plies), margin_sum (int64: sum of black - white area), plies_sum (int64:
 plies played) and ownership (int32 [R, 2, N, N]: per point, in how many playouts it ended in black's / white's area; None
@@ -1708,18 +1727,36 @@ def _queue_args(slots, rng, plies, job, counter, counts, sums):
     return slots, rng, plies, job, slots.shape[0], counter, counts, sums
 
 
-def _run_playouts(roots, R, N, K, max_plies, komi, seed, first_root, ownership, S, chunk_plies, dev, buffers=None, policy=0):
+def _run_playouts(roots, R, N, K, max_plies, komi, seed, first_root, ownership, S, chunk_plies, dev, buffers=None, policy=0,
+                  amaf=None):
     """Device work of batch_playouts on tracked roots: -> (counts int32 [R, 4], sums int64 [R, 2], own or None); no launch
     for R = 0.  buffers: _playout_buffers(R, S, N, dev) to reuse (a search evaluates its leaves with the same buffers every
-    iteration)."""
+    iteration).  amaf: _amaf_buffers(R, S, N, chunk_plies, dev) - the playouts then run through gg_playouts_advance_amaf and
+    leave their first-play counts in amaf[3] (zeroed here)."""
     buffers = buffers if buffers is not None else _playout_buffers(R, S, N, dev)
     counter, counts, sums = buffers[4:]
     own = torch.empty((R, 2, N, N), dtype=_I32, device=dev) if ownership else None
     if R > 0:
         head = (roots, R, N, K, int(first_root), int(seed) & _M64, int(max_plies), int(chunk_plies))
-        _run_queue('playouts', 'batch_playouts', head, komi, _queue_args(*buffers) + (own,), counter, R * K, S, max_plies,
-                   chunk_plies, dev, policy)
+        if amaf is None:
+            _run_queue('playouts', 'batch_playouts', head, komi, _queue_args(*buffers) + (own,), counter, R * K, S, max_plies,
+                       chunk_plies, dev, policy)
+        else:
+            bufs = _queue_args(*buffers) + (own,)
+            stream = _lib.current_raw_stream(dev)
+            _lib.call('gg_playouts_begin', *head, *bufs, stream)
+            for t in amaf[1:]:      # first, mark and the output start from zero (the log needs no fill: only written entries are read)
+                t.zero_()
+            _drive_playouts(lambda n: _lib.call('gg_playouts_advance_amaf', *head, float(komi), n, int(policy), *bufs, *amaf, stream),
+                            counter, R * K, S, max_plies, chunk_plies, dev, 'batch_playouts')
     return counts, sums, own
+
+
+def _amaf_buffers(R, S, N, chunk_plies, dev):
+    """What gg_playouts_advance_amaf takes beyond the queue's buffers: (log int16 [S, chunk_plies], first int32 [S, 2, N],
+    mark int64 [S], amaf int32 [R, 2, 3, N, N])."""
+    return (torch.empty((S, chunk_plies), dtype=torch.int16, device=dev), torch.empty((S, 2, N), dtype=_I32, device=dev),
+            torch.empty(S, dtype=_I64, device=dev), torch.empty((R, 2, 3, N, N), dtype=_I32, device=dev))
 
 
 def _playout_args(st, playouts, max_plies, chunk_plies, first_root):
@@ -1775,7 +1812,7 @@ def _best_legal(box, legal, score):
 
 
 def batch_playouts(batch_states, playouts, max_plies=None, komi=0.0, seed=20260927, first_root=0, ownership=False, slots=None,
-                   chunk_plies=32, *, policy='uniform'):
+                   chunk_plies=32, *, policy='uniform', amaf=False):
     """`playouts` uniform-random playouts of every root of batch_states ([R, 6, N, N]) to the end of the game, scored and
     reduced per root on the device -> Playouts (device tensors for a device tensor, NumPy arrays for NumPy input).
 
@@ -1786,15 +1823,26 @@ def batch_playouts(batch_states, playouts, max_plies=None, komi=0.0, seed=202609
     harvests; max_plies must be a multiple of it), and shards by first_root concatenate to the whole.  Default max_plies:
     8 N^2 rounded up to a multiple of chunk_plies.  The roots are not modified.
     policy: what a playout ply draws from - 'uniform' (batch_rollout's sampler), 'no_eye_fill' or 'tactical'
-    (batch_rollout_tracked)."""
+    (batch_rollout_tracked).
+    amaf=True: the same playouts, with their all-moves-as-first statistics -> PlayoutsAmaf (gg_playouts_advance_amaf: the
+    rollouts log their moves, the harvest reduces per root which colour played each point first, and with what outcome)."""
     pol = _policy_code(policy)
     box = _Box(batch_states)
     st = box.t
     R, N, K, max_plies, chunk_plies = _playout_args(st, playouts, max_plies, chunk_plies, first_root)
     S = max(1, min(int(_default_slots(slots)), R * K))
+    if not amaf:
+        counts, sums, own = _run_playouts(_track_roots(st), R, N, K, max_plies, komi, seed, first_root, ownership, S, chunk_plies,
+                                          st.device, policy=pol)
+        return _back(box, Playouts(counts[:, 0], counts[:, 1], counts[:, 2], counts[:, 3], sums[:, 0], sums[:, 1], own))
+    if chunk_plies > 4096:
+        raise ValueError('amaf=True needs chunk_plies <= 4096 (got %d)' % chunk_plies)
+    abufs = _amaf_buffers(R, S, N, chunk_plies, st.device)
+    if R == 0:
+        abufs[3].zero_()
     counts, sums, own = _run_playouts(_track_roots(st), R, N, K, max_plies, komi, seed, first_root, ownership, S, chunk_plies,
-                                      st.device, policy=pol)
-    return _back(box, Playouts(counts[:, 0], counts[:, 1], counts[:, 2], counts[:, 3], sums[:, 0], sums[:, 1], own))
+                                      st.device, policy=pol, amaf=abufs)
+    return _back(box, PlayoutsAmaf(counts[:, 0], counts[:, 1], counts[:, 2], counts[:, 3], sums[:, 0], sums[:, 1], own, abufs[3]))
 
 
 def playouts(state, n, **kw):
@@ -1890,6 +1938,12 @@ Uct.__doc__ = """Results of batch_uct per root: legal (bool [R, A], A = N*N + 1)
 (int32 [R, A]: the stats of the root's children, 0 where there is none), root_visits (int32 [R]), unfinished / plies_sum
 (int64 [R]: over every playout of the search), nodes (int32 [R]: tree nodes in use) and tree (UctTree or None)."""
 UctTree = collections.namedtuple('UctTree', 'parent action visits black_wins white_wins draws')
+UctRave = collections.namedtuple('UctRave', Uct._fields + ('rave_visits', 'rave_score'))
+UctRave.__doc__ = """Uct of a RAVE search (batch_uct(..., rave_equiv=k)), plus the root's AMAF pairs: rave_visits / rave_score (int32
+[R, N*N]: per point, the simulations in which the root's mover played it first, and twice its wins plus the draws among them).
+tree, when asked for, is a UctRaveTree."""
+UctRaveTree = collections.namedtuple('UctRaveTree', UctTree._fields + ('node_amaf',))
+UctRaveTree.__doc__ = """UctTree plus node_amaf (int32 [R, iterations + 1, N*N, 2]: the pairs of every node)."""
 UctTree.__doc__ = """The whole tree of every root, each field int32 [R, iterations + 1] indexed by node (node 0 = the root;
 parent / action -1 at the root and at unused nodes, whose stats are 0)."""
 
@@ -1915,9 +1969,10 @@ def _legal_roots(st):
     return legal & ~ended[:, None]
 
 
-def _run_uct(roots, R, N, I, K, c, max_plies, komi, seed, first_root, S, chunk_plies, dev, policy=0):
+def _run_uct(roots, R, N, I, K, c, max_plies, komi, seed, first_root, S, chunk_plies, dev, policy=0, rave=None):
     """Device work of batch_uct on tracked roots -> (child int32 [R, I+1, A], links [R, I+1, 2], stats [R, I+1, 4],
-    nodes [R], totals int64 [R, 2]); no launch for R = 0."""
+    nodes [R], totals int64 [R, 2]); no launch for R = 0.  rave: None (the plain search, through the plain entry points) or
+    (rave_equiv, fpu) - then a sixth result, node_amaf int32 [R, I+1, N^2, 2]."""
     W, A, NN = tracked_words(N), N * N + 1, I + 1
     boards = torch.empty((R, NN, W), dtype=_I32, device=dev)
     child = torch.empty((R, NN, A), dtype=_I32, device=dev)
@@ -1925,8 +1980,9 @@ def _run_uct(roots, R, N, I, K, c, max_plies, komi, seed, first_root, S, chunk_p
     stats = torch.empty((R, NN, 4), dtype=_I32, device=dev)
     nodes = torch.empty(R, dtype=_I32, device=dev)
     totals = torch.zeros((R, 2), dtype=_I64, device=dev)
+    node_amaf = torch.zeros((R, NN, N * N, 2), dtype=_I32, device=dev) if rave is not None else None
     if R == 0:
-        return child, links, stats, nodes, totals
+        return (child, links, stats, nodes, totals) + ((node_amaf,) if rave is not None else ())
     leaf = torch.empty((R, W), dtype=_I32, device=dev)
     move = torch.empty(R, dtype=_I32, device=dev)
     leaf_id = torch.empty(R, dtype=_I32, device=dev)
@@ -1936,6 +1992,17 @@ def _run_uct(roots, R, N, I, K, c, max_plies, komi, seed, first_root, S, chunk_p
     counts, sums = pbufs[5], pbufs[6]
     stream = _lib.current_raw_stream(dev)
     _lib.call('gg_uct_begin', roots, R, N, I, K, boards, child, links, stats, nodes, stream)
+    if rave is not None:
+        abufs = _amaf_buffers(R, S, N, chunk_plies, dev)
+        for i in range(I):
+            _lib.call('gg_uct_select_rave', R, N, I, K, c, float(rave[0]), float(rave[1]), log_table, boards, child, links, stats,
+                      node_amaf, nodes, leaf, move, leaf_id, stream)
+            _lib.call('gg_batch_play_moves_tracked', leaf, move, None, R, N, 1, stream)
+            _run_playouts(leaf, R, N, K, max_plies, komi, _uct_seed(seed, i), first_root, False, S, chunk_plies, dev, pbufs, policy,
+                          amaf=abufs)
+            _lib.call('gg_uct_backup_rave', R, N, I, K, counts, sums, abufs[3], totals, boards, links, stats, node_amaf, leaf, move,
+                      leaf_id, stream)
+        return child, links, stats, nodes, totals, node_amaf
     for i in range(I):
         _lib.call('gg_uct_select', R, N, I, K, c, log_table, boards, child, links, stats, nodes, leaf, move, leaf_id, stream)
         _lib.call('gg_batch_play_moves_tracked', leaf, move, None, R, N, 1, stream)
@@ -1945,7 +2012,7 @@ def _run_uct(roots, R, N, I, K, c, max_plies, komi, seed, first_root, S, chunk_p
 
 
 def batch_uct(batch_states, iterations, playouts, c=math.sqrt(2), max_plies=None, komi=0.0, seed=20260927, first_root=0,
-              slots=None, chunk_plies=32, tree=False, *, policy='uniform'):
+              slots=None, chunk_plies=32, tree=False, *, policy='uniform', rave_equiv=None, fpu=1.0):
     """UCT search of `iterations` iterations from every root of batch_states ([R, 6, N, N]), the leaves evaluated with
     `playouts` playouts each -> Uct (device tensors for a device tensor, NumPy arrays for NumPy input).
 
@@ -1963,21 +2030,42 @@ def batch_uct(batch_states, iterations, playouts, c=math.sqrt(2), max_plies=None
 
     Device memory of the tree: R * (iterations + 1) * (4 (5N + 1) + 4 (N^2 + 1) + 24) bytes (boards, child tables, links and
     stats: 1 856 bytes per node at 19x19, 124 MB for 1 024 roots x 64 iterations), plus the playout slots of batch_playouts.
-    policy: as in batch_playouts; it governs the playouts of the leaves only - the tree keeps every legal action."""
+    policy: as in batch_playouts; it governs the playouts of the leaves only - the tree keeps every legal action.
+
+    rave_equiv: None - the search above, through the same entry points - or a positive number k, which turns RAVE on
+    (gg_uct_select_rave / gg_uct_backup_rave; the playouts then run with amaf=True) -> UctRave.  Every node keeps, per point p,
+    (n~, s~): the simulations through it in which its mover played p first - in the tree below it or in the playout - and
+    twice the mover's wins plus the draws among them.  At a node, every legal action a - expanded or not - gets the value
+    (1 - beta) q + beta q~ with q = (2 w + d) / (2 n) of its child, q~ = s~ / (2 n~) and beta = n~ / (n + n~ + n n~ / k); q or
+    q~ alone when only one of the counts is positive, `fpu` when neither is; U adds c * sqrt(log(n_parent) / n) when n > 0
+    (float64, in this order, no fused multiply-add).  The largest U wins, ties to the lowest action; a winner without a child
+    is expanded.  So a node descends as soon as one action stands out, where the plain search first expands every legal
+    action in board order.  The search needs 2 * iterations * playouts < 2^31 and chunk_plies <= 4096, and 8 N^2 more bytes
+    per node."""
     pol = _policy_code(policy)
     box = _Box(batch_states)
     st = box.t
     R, N, K, max_plies, chunk_plies = _playout_args(st, playouts, max_plies, chunk_plies, first_root)
     I, c = _uct_args(iterations, K, c)
+    rave = None
+    if rave_equiv is not None:
+        rave = (float(rave_equiv), float(fpu))
+        if not (math.isfinite(rave[0]) and rave[0] > 0 and math.isfinite(rave[1])) or 2 * I * K >= 2 ** 31 or chunk_plies > 4096:
+            raise ValueError('RAVE needs rave_equiv > 0 and finite, fpu finite, 2 * iterations * playouts < 2^31 and chunk_plies '
+                             '<= 4096 (got %r, %r, %d, %d)' % (rave_equiv, fpu, 2 * I * K, chunk_plies))
     S = max(1, min(int(_default_slots(slots)), R * K))
-    child, links, stats, nodes, totals = _run_uct(_track_roots(st), R, N, I, K, c, max_plies, komi, seed, first_root, S,
-                                                  chunk_plies, st.device, policy=pol)
+    child, links, stats, nodes, totals, *more = _run_uct(_track_roots(st), R, N, I, K, c, max_plies, komi, seed, first_root, S,
+                                                         chunk_plies, st.device, policy=pol, rave=rave)
     rc = child[:, 0, :]
     kid = torch.gather(stats, 1, rc.clamp(min=0).long()[..., None].expand(R, N * N + 1, 4))
     kid = torch.where((rc >= 0)[..., None], kid, torch.zeros_like(kid))
     whole = UctTree(links[..., 0], links[..., 1], stats[..., 0], stats[..., 1], stats[..., 2], stats[..., 3]) if tree else None
-    return _back(box, Uct(_legal_roots(st), kid[..., 0], kid[..., 1], kid[..., 2], kid[..., 3], stats[:, 0, 0], totals[:, 0],
-                          totals[:, 1], nodes, whole))
+    res = Uct(_legal_roots(st), kid[..., 0], kid[..., 1], kid[..., 2], kid[..., 3], stats[:, 0, 0], totals[:, 0], totals[:, 1], nodes,
+              whole)
+    if rave is not None:
+        node_amaf = more[0]
+        res = UctRave(*res[:-1], UctRaveTree(*whole, node_amaf) if tree else None, node_amaf[:, 0, :, 0], node_amaf[:, 0, :, 1])
+    return _back(box, res)
 
 
 def uct(state, iterations, playouts, **kw):

@@ -11,6 +11,8 @@ ratio = time (b) / time (a) per playout: what the select, one-move step and back
 them - cost on top of the playouts (1.0: nothing).  Both drain the playout queue once per iteration.  Plies are the plies
 the playouts played (plies_sum).  For the device-time split of k_uct_select, the one-move step (k_play_moves*) and
 k_uct_backup, run once under `rocprofv3 --kernel-trace --stats -- python tools/bench_uct.py --reps 1`.
+--rave-equiv K: a third side in the same alternation, (c) batch_uct(roots, I, K, rave_equiv=K) - keys with the suffix _rave,
+rave_ratio = iterations/s with RAVE / plain, and the mean depth of the deepest node per tree on both sides.
 """
 import argparse
 import json
@@ -26,6 +28,7 @@ def main():
     ap.add_argument('--size', type=int, default=19)
     ap.add_argument('--plies', type=int, default=120)
     ap.add_argument('--reps', type=int, default=3)
+    ap.add_argument('--rave-equiv', type=float, default=None)
     args = ap.parse_args()
 
     import torch
@@ -56,6 +59,25 @@ def main():
                'plies_per_s_plain': plies_b / sb, 'mean_plies_plain': plies_b / P,
                'ratio': (P / sa) / (P / sb), 'ratio_plies': (plies_a / sa) / (plies_b / sb),
                'mean_nodes': float(ref.nodes.float().mean()), 'reps': args.reps}
+        if args.rave_equiv is not None:
+            def run_c():
+                return gogame.batch_uct(roots, I, K, seed=1, rave_equiv=args.rave_equiv, **kw)
+
+            def depth(parent):   # the deepest node of every tree: parents have smaller ids
+                d = torch.zeros_like(parent)
+                for x in range(1, parent.shape[1]):
+                    p = parent[:, x]
+                    d[:, x] = torch.where(p >= 0, torch.gather(d, 1, p.clamp(min=0).long()[:, None])[:, 0] + 1, torch.zeros_like(p))
+                return float(d.max(dim=1).values.float().mean())
+
+            rv = run_c()   # warm-up
+            assert bool((rv.root_visits == I * K).all())
+            (sa2, _), (sc, out_c) = median_timed(run_a, run_c, reps=args.reps)
+            res.update(rave_equiv=args.rave_equiv, seconds_uct_alt=sa2, seconds_rave=sc, iterations_per_s_rave=I / sc,
+                       playouts_per_s_rave=P / sc, rave_ratio=sa2 / sc, mean_nodes_rave=float(out_c.nodes.float().mean()),
+                       mean_plies_rave=int(out_c.plies_sum.sum()) / P,
+                       mean_depth=depth(gogame.batch_uct(roots, I, K, seed=1, tree=True, **kw).tree.parent),
+                       mean_depth_rave=depth(gogame.batch_uct(roots, I, K, seed=1, tree=True, rave_equiv=args.rave_equiv, **kw).tree.parent))
         print(json.dumps(res), flush=True)
 
 

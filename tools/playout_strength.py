@@ -7,7 +7,14 @@ gogame.flat_mc_actions(states, k, komi, policy=the mover's policy) - equal playo
 of a half move in lockstep (game g differs from the others through its job numbers: the root index enters every playout's
 seed; the seed changes with the ply), each game to two passes or 8 N^2 plies, scored by area against komi as it stands.
 win_share = the policy's wins / decided games, ci95 its normal-approximation binomial interval.  For the record only
-(DESIGN 34): one opponent, flat Monte Carlo, no claim beyond the line it prints."""
+(DESIGN 34): one opponent, flat Monte Carlo, no claim beyond the line it prints.
+
+  python tools/playout_strength.py --rave-equiv 50 [--iters 64] [--k 4] [--games 200] [--policy uniform]
+
+RAVE against plain UCT: every move of one side is gogame.uct_actions(states, iters, k, rave_equiv=...), of the other
+gogame.uct_actions(states, iters, k) - equal iterations and playouts, the same playout policy (--policy) on both sides; win_share is
+the RAVE side's (--rave-c: its exploration constant, where it is to differ from the plain side's sqrt(2)).  The same lockstep
+games, colours, cap, scoring and interval."""
 import argparse
 import json
 import math
@@ -24,6 +31,9 @@ def main():
     ap.add_argument('--komi', type=float, default=7.5)
     ap.add_argument('--policy', default='tactical')
     ap.add_argument('--against', default='no_eye_fill')
+    ap.add_argument('--rave-equiv', type=float, default=None)
+    ap.add_argument('--iters', type=int, default=64)
+    ap.add_argument('--rave-c', type=float, default=None, help="exploration constant of the RAVE side (default: batch_uct's, as the plain side)")
     args = ap.parse_args()
 
     import torch
@@ -31,6 +41,9 @@ def main():
     N, K, half, cap = args.size, args.k, args.games, 8 * args.size * args.size
     res = {'size': N, 'komi': args.komi, 'playouts_per_move': K, 'games_per_colour': half, 'ply_cap': cap, 'policy': args.policy,
            'against': args.against}
+    rave = args.rave_equiv is not None
+    if rave:
+        res.update(mode='rave_vs_uct', rave_equiv=args.rave_equiv, iterations=args.iters, against='plain uct', rave_c=args.rave_c)
     t0 = time.time()
     wins, unfinished = [0, 0], 0
     for as_black in (True, False):
@@ -41,7 +54,14 @@ def main():
                 break
             pol = args.policy if (ply % 2 == 0) == as_black else args.against
             sub = st[live].contiguous()
-            act = gogame.flat_mc_actions(sub, K, komi=args.komi, seed=1000 * ply + (7 if as_black else 13), policy=pol)
+            seed = 1000 * ply + (7 if as_black else 13)
+            if rave:
+                mine = (ply % 2 == 0) == as_black
+                kw = {'c': args.rave_c} if mine and args.rave_c is not None else {}
+                act = gogame.uct_actions(sub, args.iters, K, komi=args.komi, seed=seed, policy=args.policy,
+                                         rave_equiv=args.rave_equiv if mine else None, **kw)
+            else:
+                act = gogame.flat_mc_actions(sub, K, komi=args.komi, seed=seed, policy=pol)
             st[live] = gogame.batch_next_states(sub, act.to(torch.int32))
         unfinished += int((gogame.batch_game_ended(st) == 0).sum())
         w = gogame.batch_winning(st, args.komi)
