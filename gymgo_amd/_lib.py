@@ -7,8 +7,9 @@ pointers, from ONE table (ABI) that tests/test_host_abi.py holds against the hea
 call().  A new entry point is one declaration in the header and one entry in the table.  The area family has a header of
 its own, include/gymgo_amd_area.h, and a table of its own, ABI_AREA, bound and called the same way; so have the past family
 (include/gymgo_amd_past.h, ABI_PAST), the Gumbel root rule of the PUCT search (include/gymgo_amd_gumbel.h, ABI_GUMBEL), the
-tactical playout policy with its planes (include/gymgo_amd_tactics.h, ABI_TACTICS) and the AMAF statistics of the playouts with
-RAVE in the UCT search (include/gymgo_amd_amaf.h, ABI_AMAF).
+tactical playout policy with its planes (include/gymgo_amd_tactics.h, ABI_TACTICS), the AMAF statistics of the playouts with
+RAVE in the UCT search (include/gymgo_amd_amaf.h, ABI_AMAF) and the pattern playout policy with its planes
+(include/gymgo_amd_pattern.h, ABI_PATTERN).
 """
 import collections
 import ctypes
@@ -225,12 +226,24 @@ ABI_AMAF = {
     'gg_uct_backup_rave': (_RNI + _params(_i32, 'K') + _params(_I32, 'counts') + _params(_I64, 'sums') + _params(_I32, 'amaf')
                            + _params(_I64, 'totals') + _params(_I32, 'boards', 'links', 'stats', 'node_amaf') + _LEAF),
 }
+# ... and of include/gymgo_amd_pattern.h, the pattern playout policy's header, in its order (tests/test_pattern_host.py holds it
+# against its header): the planes, and the three _policy2 calls under the names that accept GG_POLICY_PATTERN too - the two queue
+# calls with the slots' previous actions in front of the stream
+ABI_PATTERN = {
+    'gg_pattern_planes': (),
+    'gg_batch_patterns': _params(_U8, 'states') + _params(_I32, 'last', 'orient') + _OUT + _OUT_BN,
+    'gg_batch_patterns_tracked': _params(_I32, 'tracked', 'last', 'orient') + _OUT + _OUT_BN,
+    'gg_batch_rollout_tracked_policy3': ABI_TACTICS['gg_batch_rollout_tracked_policy2'],
+    'gg_playouts_advance_policy3': ABI_TACTICS['gg_playouts_advance_policy2'][:-1] + _params(_I32, 'last') + _STREAM,
+    'gg_move_playouts_advance_policy3': ABI_TACTICS['gg_move_playouts_advance_policy2'][:-1] + _params(_I32, 'last') + _STREAM,
+}
 EXPORTS = tuple(ABI)
 EXPORTS_AREA = tuple(ABI_AREA)
 EXPORTS_PAST = tuple(ABI_PAST)
 EXPORTS_GUMBEL = tuple(ABI_GUMBEL)
 EXPORTS_TACTICS = tuple(ABI_TACTICS)
 EXPORTS_AMAF = tuple(ABI_AMAF)
+EXPORTS_PATTERN = tuple(ABI_PATTERN)
 _signatures = lambda table: {f: ([p.kind if isinstance(p.kind, type) else _vp for p in ps], _i32) for f, ps in table.items()}
 _SIGNATURES = _signatures(ABI)   # argtypes, restype
 _SIGNATURES_AREA = _signatures(ABI_AREA)
@@ -238,10 +251,11 @@ _SIGNATURES_PAST = _signatures(ABI_PAST)
 _SIGNATURES_GUMBEL = _signatures(ABI_GUMBEL)
 _SIGNATURES_TACTICS = _signatures(ABI_TACTICS)
 _SIGNATURES_AMAF = _signatures(ABI_AMAF)
+_SIGNATURES_PATTERN = _signatures(ABI_PATTERN)
 # call(): the number of parameters and (index, dtypes, name) of every pointer to device memory
 _POINTERS = {f: (len(ps), tuple((i, p.kind if isinstance(p.kind, tuple) else (p.kind,), p.name)
                                 for i, p in enumerate(ps) if not isinstance(p.kind, type)))
-             for table in (ABI, ABI_AREA, ABI_PAST, ABI_GUMBEL, ABI_TACTICS, ABI_AMAF) for f, ps in table.items()}
+             for table in (ABI, ABI_AREA, ABI_PAST, ABI_GUMBEL, ABI_TACTICS, ABI_AMAF, ABI_PATTERN) for f, ps in table.items()}
 
 _lib = None
 
@@ -256,7 +270,7 @@ def build(force=False):
     csrc = os.path.join(_HERE, 'csrc')
     srcs = [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(('.hip', '.h'))]
     srcs += [os.path.join(os.path.dirname(_HERE), 'include', h) for h in ('gymgo_amd.h', 'gymgo_amd_area.h', 'gymgo_amd_past.h', 'gymgo_amd_gumbel.h',
-                                                                                  'gymgo_amd_tactics.h', 'gymgo_amd_amaf.h')]
+                                                                                  'gymgo_amd_tactics.h', 'gymgo_amd_amaf.h', 'gymgo_amd_pattern.h')]
     stale = not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < max(os.path.getmtime(f) for f in srcs)
     if force or stale:
         subprocess.check_call(['make', '-C', os.path.join(_HERE, 'csrc'), '-s', '-B', '-j3'])
@@ -273,7 +287,7 @@ def lib():
         L = ctypes.CDLL(LIB_PATH)
         for name, (argtypes, restype) in (list(_SIGNATURES.items()) + list(_SIGNATURES_AREA.items()) + list(_SIGNATURES_PAST.items())
                                           + list(_SIGNATURES_GUMBEL.items()) + list(_SIGNATURES_TACTICS.items())
-                                          + list(_SIGNATURES_AMAF.items())):
+                                          + list(_SIGNATURES_AMAF.items()) + list(_SIGNATURES_PATTERN.items())):
             fn = getattr(L, name)  # AttributeError if the .so does not export what the header declares
             fn.argtypes, fn.restype = argtypes, restype
         if L.gg_version() != ABI_VERSION:
@@ -422,7 +436,8 @@ def ptrs(fn, **tensors):
     """dev_ptr of every tensor as the parameter of entry point `fn` it is named after - dtype(s) from the table -, in the order
     given: for the paths that check their buffers once and hand call() the pointers from then on."""
     kinds = {p.name: p.kind for p in (ABI[fn] if fn in ABI else ABI_AREA[fn] if fn in ABI_AREA else ABI_PAST[fn] if fn in ABI_PAST
-                                      else ABI_GUMBEL[fn] if fn in ABI_GUMBEL else ABI_TACTICS[fn] if fn in ABI_TACTICS else ABI_AMAF[fn])}
+                                      else ABI_GUMBEL[fn] if fn in ABI_GUMBEL else ABI_TACTICS[fn] if fn in ABI_TACTICS else ABI_AMAF[fn] if fn in ABI_AMAF
+                                      else ABI_PATTERN[fn])}
     return tuple(dev_ptr(t, kinds[n], n) for n, t in tensors.items())
 
 

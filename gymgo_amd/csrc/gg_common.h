@@ -10,6 +10,7 @@
 #include <stdint.h>
 
 #include "gymgo_amd.h"
+#include "gg_pattern_tab.h"
 
 namespace gg {
 
@@ -66,6 +67,11 @@ __device__ __forceinline__ uint32_t dpp0(uint32_t v) {
 
 // Playout policies of the tracked multi-ply kernels (include/gymgo_amd.h: GG_POLICY_*)
 constexpr int kPolUniform = 0, kPolNoEyeFill = 1, kPolTactical = 2;
+// ... and GG_POLICY_PATTERN of include/gymgo_amd_pattern.h: tactical, then the local 3x3 response
+constexpr int kPolPattern = 3;
+// bits per count of the packed set counts a tactical / pattern draw carries in one word: F, C, E at 0, kPolBits, 2 kPolBits (a
+// board has <= 361 points), and for the pattern policy L (<= 8 points) at 3 kPolBits
+template <int POL> constexpr uint32_t kPolBits = POL == kPolPattern ? 9u : 10u;
 
 // One row of the MOVER'S EYES: an empty point whose on-board orthogonal neighbours are all the mover's stones and
 // whose on-board diagonal neighbours hold at most one opponent stone - none when the point lies on the first / last row or
@@ -101,6 +107,43 @@ __device__ __forceinline__ void tactical_rows(uint32_t me, uint32_t op, uint32_t
   const uint32_t c = B3(full, meU, opU, TA & ~(TB | TC) & 0xFF), d = B3(full, meD, opD, TA & ~(TB | TC) & 0xFF);
   const uint32_t any3 = B3(a, b, c, T_OR3), maj = B3(a, b, c, T_MAJ);
   E = nm & B3(d, any3, maj, T_ANDOR);                                                // at least two of the four
+}
+
+// THE 3x3 PATTERNS of the pattern policy (include/gymgo_amd_pattern.h holds the rule).  A neighbour is two bits: "a
+// mover's stone or off the board" and "an opponent's stone or off the board"; the sixteen bits of the eight neighbours index
+// kPatternTab (gg_pattern_tab.h, generated from the thirteen strings by tools/gen_pattern_table.py), one bit per neighbourhood.
+// Rows travel PADDED: the row shifted up by one with every bit off the board set - column c at bit c + 1, the three columns
+// around c at bits c .. c + 2 - and a row off the board is all ones in both colours.
+__device__ __forceinline__ uint32_t pattern_pad(uint32_t x, int N) { return (x << 1) | ~(((1u << N) - 1u) << 1); }
+// the index of the neighbourhood of column c (0 <= c < N) of a row, from the padded rows above / of / below it
+__device__ __forceinline__ uint32_t pattern_index(uint32_t meU, uint32_t opU, uint32_t me, uint32_t op, uint32_t meD, uint32_t opD,
+                                                  uint32_t c) {
+  const uint32_t a = (me >> c) & 5u, b = (op >> c) & 5u;   // west and east at bits 0 and 2
+  return ((meU >> c) & 7u) | (((opU >> c) & 7u) << 3) | (((a | (a >> 1)) & 3u) << 6) | (((b | (b >> 1)) & 3u) << 8) |
+         (((meD >> c) & 7u) << 10) | (((opD >> c) & 7u) << 13);
+}
+// does the neighbourhood match one of the thirteen patterns, in any view, under either colour assignment: THE decision
+__device__ __forceinline__ uint32_t pattern_match(uint32_t idx) { return (kPatternTab[(idx >> 5) & 2047u] >> (idx & 31u)) & 1u; }
+// the matching points among columns pc - 1, pc, pc + 1 of a row (those on the board; `centre` false: without pc itself), whether
+// they are empty or not - the caller masks with the candidates.  Branch-free: a column off the board looks at column 0 for nothing.
+__device__ __forceinline__ uint32_t pattern_cols3(uint32_t meU, uint32_t opU, uint32_t me, uint32_t op, uint32_t meD, uint32_t opD,
+                                                  int pc, bool centre, int N) {
+  uint32_t out = 0u;
+#pragma unroll
+  for (int k = -1; k <= 1; ++k) {
+    const int c = pc + k;
+    const bool ok = (uint32_t)c < (uint32_t)N && (k != 0 || centre);
+    const uint32_t cc = ok ? (uint32_t)c : 0u;
+    const uint32_t m = pattern_match(pattern_index(meU, opU, me, op, meD, opD, cc));
+    out |= ok ? m << cc : 0u;
+  }
+  return out;
+}
+// ... and among all N columns of a row (the planes)
+__device__ __forceinline__ uint32_t pattern_row(uint32_t meU, uint32_t opU, uint32_t me, uint32_t op, uint32_t meD, uint32_t opD, int N) {
+  uint32_t out = 0u;
+  for (int c = 0; c < N; ++c) out |= pattern_match(pattern_index(meU, opU, me, op, meD, opD, (uint32_t)c)) << c;
+  return out;
 }
 
 // OR-accumulation of a compile-time-indexed series of terms, two per v_bitop3_b32: `acc |= a; acc |= b` is fused by the compiler

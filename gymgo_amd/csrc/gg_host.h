@@ -66,6 +66,12 @@ void launch_rollout5_log(int N, uint8_t *st, uint64_t *rng, int32_t *last_action
                          int plies, int policy, int nb, int grid, uint16_t *log, hipStream_t s);
 void launch_rollout_lat_log(uint8_t *st, uint64_t *rng, int32_t *last_actions, int64_t *steps_done, int64_t B, int32_t N, int plies,
                             int policy, uint16_t *log, hipStream_t s);
+// gg_r5_pat.hip / gg_lat_pat.hip: the pattern policy's instantiations of the two families (tracked boards; last_actions is read as
+// the previous action of every board and must be there)
+void launch_rollout5_pattern(int N, uint8_t *st, uint64_t *rng, int32_t *last_actions, int64_t *steps_done, int64_t B, uint32_t inv,
+                             int plies, int auto_reset, int nb, int grid, hipStream_t s);
+void launch_rollout_lat_pattern(uint8_t *st, uint64_t *rng, int32_t *last_actions, int64_t *steps_done, int64_t B, int32_t N, int plies,
+                                int auto_reset, hipStream_t s);
 void launch_env_step_lat(uint32_t *tracked, uint64_t *rng, int64_t *steps_done, int64_t B, int32_t N, int auto_reset,
                          const EnvArgs &env, bool w4, hipStream_t s);
 

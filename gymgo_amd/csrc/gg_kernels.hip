@@ -39,6 +39,7 @@
 #include "gymgo_amd.h"
 #include "gymgo_amd_tactics.h"
 #include "gymgo_amd_amaf.h"
+#include "gymgo_amd_pattern.h"
 
 namespace {
 
@@ -436,17 +437,20 @@ static int32_t po_begin(const Args &a, int64_t cells, int32_t N, void *hip_strea
 
 // advance: `chunks` times chunk_plies plies on every slot, then the harvest (refills, and in the first-move family the first
 // moves, happen there, between launches)
+// last (the _policy3 calls, LastArgs; else null): the previous action of every slot, in and out of every chunk; the pattern
+// policy needs it
 template <class Args>
 static int32_t po_advance(const Args &a, int32_t N, int32_t chunk_plies, int32_t chunks, int32_t policy, int32_t max_policy,
-                          void *hip_stream) {
+                          void *hip_stream, int32_t *last = nullptr) {
   if (chunks < 0 || !policy_ok(policy, max_policy)) return GG_E_BADARG;
+  if (policy == GG_POLICY_PATTERN && !last) return GG_E_NULLPTR;
   if (a.J == 0 || chunks == 0) return 0;
   OnDeviceOf on_dev(a.slots);
   const int cus = on_dev.cus();
   hipStream_t s = (hipStream_t)hip_stream;
   for (int c = 0; c < chunks; ++c) {
     // the existing tracked dispatch, auto_reset = 0: finished and empty slots stay frozen
-    if (int32_t e = gg_batch_rollout_tracked_policy2(a.slots, a.rng, nullptr, a.plies, a.S, N, chunk_plies, 0, policy, hip_stream)) return e;
+    if (int32_t e = gg_batch_rollout_tracked_policy3(a.slots, a.rng, last, a.plies, a.S, N, chunk_plies, 0, policy, hip_stream)) return e;
     launch_harvest<false>(a, N, cus, s);
     if (int32_t e = (int32_t)hipGetLastError()) return e;
   }
@@ -1004,21 +1008,25 @@ int32_t gg_batch_rollout_tracked(uint32_t *tracked, uint64_t *rng, int32_t *last
 // The draw under a playout policy lives in the two families the playout queue runs on: k_rollout_lat where the
 // uniform path takes it, k_rollout5 where the uniform path takes it, and k_rollout_lat again - its plain form serves every batch
 // size and launch length - in the band that the uniform path gives to k_rollout4, which has no policy draw.
-// max_policy: the last policy the entry point accepts (GG_POLICY_NO_EYE_FILL: the _policy calls; GG_POLICY_TACTICAL: _policy2)
+// max_policy: the last policy the entry point accepts (GG_POLICY_NO_EYE_FILL: the _policy calls; GG_POLICY_TACTICAL: _policy2;
+// GG_POLICY_PATTERN: _policy3, include/gymgo_amd_pattern.h - that policy reads last_actions as every board's previous action)
 static int32_t rollout_tracked_policy(uint32_t *tracked, uint64_t *rng, int32_t *last_actions, int64_t *steps_done, int64_t B, int32_t N,
                                       int32_t plies, int32_t auto_reset, int32_t policy, int32_t max_policy, void *hip_stream) {
   if (policy == GG_POLICY_UNIFORM) return gg_batch_rollout_tracked(tracked, rng, last_actions, steps_done, B, N, plies, auto_reset, hip_stream);
   if (plies < 0 || policy < GG_POLICY_NO_EYE_FILL || policy > max_policy) return GG_E_BADARG;
   GG_ENTER(tracked);
   if (plies == 0) return 0;
-  if (!rng) return GG_E_NULLPTR;
+  if (!rng || (policy == GG_POLICY_PATTERN && !last_actions)) return GG_E_NULLPTR;   // (the pattern policy READS last_actions)
   uint8_t *st = reinterpret_cast<uint8_t *>(tracked);
+  const bool pat = policy == GG_POLICY_PATTERN;   // its instantiations live in gg_r5_pat.hip / gg_lat_pat.hip
   if (!use_lat(cus, B, N, plies, true) && use_rollout5(cus, B, N, plies)) {
     const WaveGrid w5 = boards_per_wave5(cus, B);
-    launch_rollout5_policy(N, st, rng, last_actions, steps_done, B, inv, plies, auto_reset, policy, w5.nb, w5.grid, s);
+    if (pat) launch_rollout5_pattern(N, st, rng, last_actions, steps_done, B, inv, plies, auto_reset, w5.nb, w5.grid, s);
+    else launch_rollout5_policy(N, st, rng, last_actions, steps_done, B, inv, plies, auto_reset, policy, w5.nb, w5.grid, s);
     return (int32_t)hipGetLastError();
   }
-  launch_rollout_lat_policy(st, rng, last_actions, steps_done, B, N, plies, auto_reset, policy, s);
+  if (pat) launch_rollout_lat_pattern(st, rng, last_actions, steps_done, B, N, plies, auto_reset, s);
+  else launch_rollout_lat_policy(st, rng, last_actions, steps_done, B, N, plies, auto_reset, policy, s);
   return (int32_t)hipGetLastError();
 }
 
@@ -1032,6 +1040,12 @@ int32_t gg_batch_rollout_tracked_policy(uint32_t *tracked, uint64_t *rng, int32_
 int32_t gg_batch_rollout_tracked_policy2(uint32_t *tracked, uint64_t *rng, int32_t *last_actions, int64_t *steps_done, int64_t B,
                                          int32_t N, int32_t plies, int32_t auto_reset, int32_t policy, void *hip_stream) {
   return rollout_tracked_policy(tracked, rng, last_actions, steps_done, B, N, plies, auto_reset, policy, GG_POLICY_TACTICAL, hip_stream);
+}
+
+// The _policy3 entry points (include/gymgo_amd_pattern.h): GG_POLICY_PATTERN accepted as well
+int32_t gg_batch_rollout_tracked_policy3(uint32_t *tracked, uint64_t *rng, int32_t *last_actions, int64_t *steps_done, int64_t B,
+                                         int32_t N, int32_t plies, int32_t auto_reset, int32_t policy, void *hip_stream) {
+  return rollout_tracked_policy(tracked, rng, last_actions, steps_done, B, N, plies, auto_reset, policy, GG_POLICY_PATTERN, hip_stream);
 }
 
 // The move log (include/gymgo_amd_amaf.h): rollout_tracked_policy's dispatch for policies 1 and 2, for the uniform policy
@@ -1237,6 +1251,21 @@ int32_t gg_playouts_advance_policy2(const uint32_t *roots, int64_t R, int32_t N,
   return po_advance(a, N, chunk_plies, chunks, policy, GG_POLICY_TACTICAL, hip_stream);
 }
 
+// ... and with the pattern policy accepted (include/gymgo_amd_pattern.h): the chunks carry `last`, the harvest on
+// LastArgs clears it for every slot it refills or empties.  Policies 0 - 2: the plain arguments, last not looked at.
+int32_t gg_playouts_advance_policy3(const uint32_t *roots, int64_t R, int32_t N, int32_t K, int64_t first_root, uint64_t base_seed,
+                                    int32_t max_plies, int32_t chunk_plies, float komi, int32_t chunks, int32_t policy,
+                                    uint32_t *slots, uint64_t *rng, int64_t *plies, int64_t *job, int64_t S, int64_t *counter,
+                                    int32_t *counts, int64_t *sums, int32_t *ownership, int32_t *last, void *hip_stream) {
+  LastArgs<PoArgs> a;
+  if (int32_t e = po_args(a, 1, R, true, true, roots, R, N, K, first_root, base_seed, max_plies, chunk_plies, komi, slots, rng, plies,
+                          job, S, counter, counts, sums, ownership))
+    return e;
+  if (policy != GG_POLICY_PATTERN) return po_advance(static_cast<const PoArgs &>(a), N, chunk_plies, chunks, policy, GG_POLICY_PATTERN, hip_stream);
+  a.last = last;
+  return po_advance(a, N, chunk_plies, chunks, policy, GG_POLICY_PATTERN, hip_stream, last);
+}
+
 // AMAF playouts (include/gymgo_amd_amaf.h): po_advance with the chunks on the log variants and the harvest on AmafArgs
 int32_t gg_playouts_advance_amaf(const uint32_t *roots, int64_t R, int32_t N, int32_t K, int64_t first_root, uint64_t base_seed,
                                  int32_t max_plies, int32_t chunk_plies, float komi, int32_t chunks, int32_t policy,
@@ -1317,6 +1346,20 @@ int32_t gg_move_playouts_advance_policy2(const uint32_t *roots, int64_t R, int32
                           S, counter, counts, sums))
     return e;
   return po_advance(m, N, chunk_plies, chunks, policy, GG_POLICY_TACTICAL, hip_stream);
+}
+
+int32_t gg_move_playouts_advance_policy3(const uint32_t *roots, int64_t R, int32_t N, const int32_t *plan, int64_t T, int32_t K,
+                                         int64_t first_root, uint64_t base_seed, int32_t max_plies, int32_t chunk_plies,
+                                         float komi, int32_t chunks, int32_t policy, uint32_t *slots, uint64_t *rng,
+                                         int64_t *plies, int64_t *job, int64_t S, int64_t *counter, int32_t *counts,
+                                         int64_t *sums, int32_t *last, void *hip_stream) {
+  LastArgs<MpArgs> m;
+  if (int32_t e = mp_args(m, roots, R, N, plan, T, K, first_root, base_seed, max_plies, chunk_plies, komi, slots, rng, plies, job,
+                          S, counter, counts, sums))
+    return e;
+  if (policy != GG_POLICY_PATTERN) return po_advance(static_cast<const MpArgs &>(m), N, chunk_plies, chunks, policy, GG_POLICY_PATTERN, hip_stream);
+  m.last = last;
+  return po_advance(m, N, chunk_plies, chunks, policy, GG_POLICY_PATTERN, hip_stream, last);
 }
 
 int32_t gg_uct_begin(const uint32_t *roots, int64_t R, int32_t N, int32_t I, int32_t K, uint32_t *boards, int32_t *child,

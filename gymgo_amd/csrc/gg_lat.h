@@ -538,7 +538,8 @@ struct LdsLat {
 // also pays for every instruction-cache line it has to jump to (3.19 us per hipGraph node at config 2's size against 3.36)
 // WPB: waves per workgroup, each wave an independent group of boards (a launch of single-wave workgroups enters the machine over
 // ~0.26 ns per workgroup - tools/exp/oneply_ramp.py - which a ONE-ply launch of a thousand workgroups feels: k_rollout_lat_w4)
-// POL: the playout policy of the draw (kPolUniform; kPolNoEyeFill, kPolTactical: tracked boards, the plain form - DESIGN 15, 34)
+// POL: the playout policy of the draw (kPolUniform; kPolNoEyeFill, kPolTactical, kPolPattern: tracked boards, the plain form - DESIGN 15, 34,
+// 36; kPolPattern READS last_actions, which must not be null: the previous action of every board)
 // LOG: the move log (k_rollout_lat_log): mvlog uint16 [B][plies], entry [b][t] = the action board b played at ply t of the
 // launch (a point, or N^2 for the pass), stored by one lane of the board; a board that is not live on a ply stores nothing
 template <int R, bool FULLN, bool AUTO, int IO, int WPB, bool SHORT, int POL = kPolUniform, bool LOG = false>
@@ -627,6 +628,13 @@ __device__ __forceinline__ void rollout_lat_body(uint8_t *__restrict__ states, u
       op = (fl & 1u) ? bl : wh;
     }
     int lastv = -1, played = 0;
+    // pattern: the board's previous action, the same in every lane of the board - a point of the board, or -1 for anything else
+    // (the caller's last_actions entry, whatever it holds, then the action of every live ply)
+    int prev = -1;
+    if constexpr (POL == kPolPattern) {
+      const int la = last_actions[b];
+      prev = (on && (uint32_t)la < (uint32_t)P) ? la : -1;
+    }
     const int rN = r * N;
     // The draws of a board, LPB plies at a time: the generator is a counter (x += c per draw) and a board draws once per ply
     // from ply 0 until it freezes for good, so the draw of ply t is mix(x0 + (t + 1) c) - lane r of the board computes the one
@@ -644,6 +652,7 @@ __device__ __forceinline__ void rollout_lat_body(uint8_t *__restrict__ states, u
       if (auto_reset && __ballot(live && (fl & 4u))) {     // auto-reset of a finished game (rare)
         const uint32_t keep = (live && (fl & 4u)) ? 0u : ~0u;
         me &= keep; op &= keep; M &= keep; inv &= keep; fl &= keep;
+        if constexpr (POL == kPolPattern) prev = keep ? prev : -1;   // (a reset ply has no previous point)
       }
       const uint32_t lv = live ? ~0u : 0u;
       // 1. the draw: uniform over the valid points + the pass (GoEnv.uniform_random_action; oracle/gg_oracle.c rollout_ply)
@@ -671,12 +680,16 @@ __device__ __forceinline__ void rollout_lat_body(uint8_t *__restrict__ states, u
         valid &= ~eye_row(me, op, meU, meD, aboveO, belowO, full, edge, N);
       }
       uint32_t cnt, incl, total;
-      if constexpr (POL == kPolTactical) {
+      if constexpr (POL == kPolTactical || POL == kPolPattern) {
         // tactical: the capture points C, else the escape points E, when the gate of this ply's draw is open and the
         // set is not empty, else the candidates F of no_eye_fill.  "In atari" is stones & ~M, the rows above / below are the
         // neighbouring lanes as for the eyes (six DPP moves, in every lane, outside any select: see above); the border is a
         // mover's stone inside M.  The three per-lane counts (<= 361 on a board: ten bits each) travel in ONE word through one
         // scan and one sum; the tier is the same in every lane of the board, the k-th-bit search runs on the chosen row.
+        // pattern: between E and F stands L, the candidates among the eight neighbours of the board's previous move
+        // whose 3x3 neighbourhood matches (pattern_cols3: one table bit per point, at most three points in each of three lanes);
+        // its count (<= 8) rides in the same word, above three fields of nine bits.
+        constexpr uint32_t FB = kPolBits<POL>, FM = (1u << FB) - 1u;
         const bool top = r == 0, bot = r == N - 1;
         const uint32_t aboveM = lat_above<LPB>(me), belowM = lat_below<LPB>(me);
         const uint32_t aboveO = lat_above<LPB>(op), belowO = lat_below<LPB>(op);
@@ -689,15 +702,27 @@ __device__ __forceinline__ void rollout_lat_body(uint8_t *__restrict__ states, u
         Cr &= valid;
         Er &= valid;
         const uint32_t Fr = valid & ~eye_row(me, op, meU, meD, aboveO, belowO, full, edge, N);
-        const uint32_t w = (uint32_t)__popc(Fr) | ((uint32_t)__popc(Cr) << 10) | ((uint32_t)__popc(Er) << 20);
+        uint32_t w = (uint32_t)__popc(Fr) | ((uint32_t)__popc(Cr) << FB) | ((uint32_t)__popc(Er) << (2 * FB));
+        uint32_t Lr = 0u;
+        if constexpr (POL == kPolPattern) {
+          // (prev is a point of the board or -1; a lane off the previous move's three rows, or beyond the board, has nothing)
+          const int pr = prev < 0 ? -4 : prev / N, pc = prev - pr * N;
+          if (r < N && r >= pr - 1 && r <= pr + 1) {
+            const uint32_t uM = top ? ~0u : pattern_pad(aboveM, N), uO = top ? ~0u : pattern_pad(aboveO, N);
+            const uint32_t dM = bot ? ~0u : pattern_pad(belowM, N), dO = bot ? ~0u : pattern_pad(belowO, N);
+            Lr = Fr & pattern_cols3(uM, uO, pattern_pad(me, N), pattern_pad(op, N), dM, dO, pc, r != pr, N);
+          }
+          w |= (uint32_t)__popc(Lr) << (3 * FB);
+        }
         const uint32_t wi = lat_board_scan<LPB>(w), wt = lat_board_sum<LPB>(w);
         const bool gate = (uh & 3u) != 0u;
-        const bool useC = gate && ((wt >> 10) & 0x3FFu) != 0u, useE = gate && !useC && (wt >> 20) != 0u;
-        const uint32_t sh = useC ? 10u : (useE ? 20u : 0u);
-        valid = useC ? Cr : (useE ? Er : Fr);
-        cnt = (w >> sh) & 0x3FFu;
-        incl = (wi >> sh) & 0x3FFu;
-        total = (wt >> sh) & 0x3FFu;
+        const bool useC = gate && ((wt >> FB) & FM) != 0u, useE = gate && !useC && (POL == kPolPattern ? (wt >> (2 * FB)) & FM : wt >> (2 * FB)) != 0u;
+        const bool useL = POL == kPolPattern && gate && !useC && !useE && (wt >> (3 * FB)) != 0u;
+        const uint32_t sh = useC ? FB : (useE ? 2 * FB : (useL ? 3 * FB : 0u));
+        valid = useC ? Cr : (useE ? Er : (useL ? Lr : Fr));
+        cnt = (w >> sh) & FM;
+        incl = (wi >> sh) & FM;
+        total = (wt >> sh) & FM;
       } else {
         cnt = (uint32_t)__popc(valid);
         incl = lat_board_scan<LPB>(cnt);
@@ -715,6 +740,11 @@ __device__ __forceinline__ void rollout_lat_body(uint8_t *__restrict__ states, u
         // the log: the lane that holds the point, or the board's first lane on a pass (live: the board exists, b < B, and t < plies)
         if constexpr (LOG) {
           if (live && (hit || (pass && r == 0))) mvlog[b * (int64_t)plies + t] = (uint16_t)cand;
+        }
+        // pattern: the action of a live ply is the next ply's previous one, in every lane of the board (a pass: none)
+        if constexpr (POL == kPolPattern) {
+          const int act = lat_board_max<LPB>(cand);
+          prev = live ? (act < P ? act : -1) : prev;
         }
       }
       played -= (int)lv;

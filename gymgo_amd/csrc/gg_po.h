@@ -81,6 +81,14 @@ struct AmafArgs : PoArgs {
   int32_t chunk_plies;
 };
 
+// The pattern policy's queues (gg_playouts_advance_policy3, gg_move_playouts_advance_policy3, include/gymgo_amd_pattern.h,
+// DESIGN 36): the chunks read and write `last`, the previous action of every slot, and the harvest sets last[s] = -1 for every
+// slot it refills or empties - a job's first playout ply has no previous point, whatever the slot played before.
+template <class Base>
+struct LastArgs : Base {
+  int32_t *last;   // [S]
+};
+
 // FILL (gg_playouts_begin): slot s takes job s (an empty, frozen board from s = J on) and the counter is set to
 // {min(S, J), J + min(S, J)}.  HARVEST (gg_playouts_advance, after every rollout chunk): see the file's header.
 // MOVE (gg_move_playouts_*): a refill loads the pair's root into the registers of the ply (as env_step_lat_body does), plays
@@ -88,8 +96,10 @@ struct AmafArgs : PoArgs {
 // the child in the tracked layout; the counters are per pair.
 template <int R, bool FULLN, bool FILL, typename Args = PoArgs>
 __global__ __launch_bounds__(kWave) void k_po_harvest(Args a, int N) {
-  constexpr bool MOVE = std::is_same<Args, MpArgs>::value;
+  constexpr bool MOVE = std::is_base_of<MpArgs, Args>::value;
   constexpr bool AMAF = std::is_same<Args, AmafArgs>::value;
+  constexpr bool LAST = std::is_same<Args, LastArgs<PoArgs>>::value || std::is_same<Args, LastArgs<MpArgs>>::value;
+  static_assert(!(LAST && FILL), "the pattern policy's queues are filled by the plain fill");
   static_assert(!(AMAF && FILL), "the AMAF queue is filled by the plain fill");
   using L = Lat<R>;
   constexpr int LPB = L::LPB, NBW = L::NBW;
@@ -256,6 +266,7 @@ __global__ __launch_bounds__(kWave) void k_po_harvest(Args a, int N) {
           a.rng[s] = po_seed(a.base_seed, gjob);
           a.plies[s] = 0;
           a.job[s] = pair;
+          if constexpr (LAST) a.last[s] = -1;   // (the first move is the root's business: the playout starts without a previous point)
         }
         continue;
       }
@@ -267,6 +278,9 @@ __global__ __launch_bounds__(kWave) void k_po_harvest(Args a, int N) {
         a.first[(2 * s + 1) * N + r] = 0u;
       }
       if (r == 0) a.mark[s] = 0;
+    }
+    if constexpr (LAST) {   // a refilled or emptied slot has no previous point
+      if (r == 0) a.last[s] = -1;
     }
     if (next < a.J) {   // refill: the root's words, a fresh generator, the ply count from zero
       const int64_t root = next / a.K;

@@ -572,5 +572,10 @@ static __device__ unsigned long long gg_lsplit[4];
 #include "gg_v5_kernel.h"
 #undef GG_R5_NAME
 #undef GG_R5_POL
+#define GG_R5_NAME k_rollout5_pat
+#define GG_R5_POL kPolPattern
+#include "gg_v5_kernel.h"
+#undef GG_R5_NAME
+#undef GG_R5_POL
 
 }  // namespace gg

@@ -1,5 +1,6 @@
 // gg_v5_kernel.h - the body of k_rollout5 (gg_v5.h), included once per playout policy: GG_R5_NAME = the kernel's name,
-// GG_R5_POL = the policy of its draw (kPolUniform: k_rollout5; kPolNoEyeFill: k_rollout5_pol; kPolTactical: k_rollout5_tac).  Textual inclusion
+// GG_R5_POL = the policy of its draw (kPolUniform: k_rollout5; kPolNoEyeFill: k_rollout5_pol; kPolTactical: k_rollout5_tac, DESIGN 34;
+// kPolPattern: k_rollout5_pat, DESIGN 36 - it READS last_actions, the previous action of every board, which must not be null).  Textual inclusion
 // and not a shared inline body: k_rollout5 stays the kernel it was, instruction for instruction and by name (bench.py ties
 // its PMC record to the machine code behind the mangled name).  No include guard.
 // GG_R5_LOG (optional; defined: the move-log variants of gg_r5_log.hip): the kernel takes one more argument, mvlog uint16
@@ -252,6 +253,14 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
     uint32_t flr = flagsv[s5];
     const uint64_t x0r = ((uint64_t)rngv[2 * s5 + 1] << 32) | rngv[2 * s5];
     int playedr = 0;
+    // pattern: the board's previous action (the same in both lanes of the pair) - a point of the board, or -1 for anything else: the
+    // caller's last_actions entry, whatever it holds, then the action of every live ply
+    int prevr = -1;
+    if constexpr (POL == kPolPattern) {
+      const bool have = s5 < nb && b_first + s5 < B;
+      const int la = last_actions[have ? b_first + s5 : B - 1];
+      prevr = (have && (uint32_t)la < (uint32_t)P) ? la : -1;
+    }
 #ifdef GG_AB_P3
     uint32_t p3c_[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #endif
@@ -358,7 +367,14 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
         uint32_t v[RPL], p[RPL];
         const uint32_t rm = reset ? ~0u : 0u;   // a board being reset plays on the empty board
         uint32_t eye[RPL];
+        uint32_t tl[RPL];            // pattern: the local-response points of the lane's rows
         uint32_t tc[RPL], te[RPL];   // tactical: the capture and the escape points of the lane's rows
+        constexpr bool TAC = POL == kPolTactical || POL == kPolPattern;   // (the pattern policy is the tactical one with a tier more)
+        constexpr uint32_t FB = kPolBits<POL>, FM = (1u << FB) - 1u;       // the fields of the packed counts
+        // pattern: the matching points of the three rows around the previous move (columns pc - 1 .. pc + 1 without the
+        // move itself), and the first of those rows (-4: no previous point - none given, a pass, or a board being reset)
+        uint32_t pk[3] = {0u, 0u, 0u};
+        int prw = -4;
         if constexpr (POL != kPolUniform) {
           // no_eye_fill: the mover's eyes leave the candidates.  The stone rows of the lane come out of LDS (the planes are as
           // phase 3 of the last ply - or the load - left them), the row beyond the pair's seam out of the partner lane by one
@@ -373,7 +389,7 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
           // tactical: M[] is in registers, its rows beyond the seam come by the same swaps; off the board M reads as all ones
           // like the mover's rows (the border is a mover's stone with liberties: never empty, never in atari)
           uint32_t m_up = 0u, m_dn = 0u;
-          if constexpr (POL == kPolTactical) { m_up = dpp0<QP_X1>(M[RPL - 1]); m_dn = dpp0<QP_X1>(M[0]); }
+          if constexpr (TAC) { m_up = dpp0<QP_X1>(M[RPL - 1]); m_dn = dpp0<QP_X1>(M[0]); }
 #pragma unroll
           for (int r = 0; r < RPL; ++r) {
             const int rw = r0 + r;
@@ -382,7 +398,7 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
             const uint32_t meD = rw + 1 >= N ? FULLROW : meDn;
             const uint32_t edge = (rw == 0 || rw == N - 1) ? FULLROW : (1u | (1u << (N - 1)));
             eye[r] = eye_row(me[r], op[r], meU, meD, opU, opD, full[r], edge, N) & ~rm;
-            if constexpr (POL == kPolTactical) {
+            if constexpr (TAC) {
               const uint32_t MU = r ? M[r - 1] : (t5 ? m_up : FULLROW);
               const uint32_t MDn = r + 1 < RPL ? M[r + 1] : (t5 ? 0u : m_dn);
               const uint32_t MD = rw + 1 >= N ? FULLROW : MDn;
@@ -391,16 +407,48 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
               te[r] &= ~rm;
             }
           }
+          if constexpr (POL == kPolPattern) {
+            // the five rows around the previous move come out of the board's planes in LDS at the move's own row - whichever lane
+            // of the pair holds them, both lanes look at all eight points -, padded (pattern_pad), all ones off the board; eight
+            // table bits (pattern_cols3).  Nothing is indexed without a previous point: row 0 is read for nothing.
+            const bool hasp = prevr >= 0 && !reset;
+            const int pv = hasp ? prevr : 0;
+            const int pr = pv / N, pc = pv - pr * N;
+            const uint32_t *bm = GG_PM(turn), *bo = GG_PO(turn);
+            uint32_t wm[5], wo[5];
+#pragma unroll
+            for (int d = 0; d < 5; ++d) {
+              const int rw = pr - 2 + d;
+              const bool inb = (uint32_t)rw < (uint32_t)N;
+              const uint32_t a = bm[inb ? rw : 0], b = bo[inb ? rw : 0];
+              wm[d] = inb ? pattern_pad(a, N) : ~0u;
+              wo[d] = inb ? pattern_pad(b, N) : ~0u;
+            }
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+              const bool inb = hasp && (uint32_t)(pr - 1 + a) < (uint32_t)N;
+              const uint32_t m = pattern_cols3(wm[a], wo[a], wm[a + 1], wo[a + 1], wm[a + 2], wo[a + 2], pc, a != 1, N);
+              pk[a] = inb ? m : 0u;
+            }
+            prw = hasp ? pr - 1 : -4;
+          }
         }
 #pragma unroll
         for (int r = 0; r < RPL; ++r) {
           v[r] = B3(full[r], rm, inv_r[r], TA & (TB | (~TC & 0xFF)));
-          if constexpr (POL == kPolTactical) {
-            // the three sets of the row and their counts in ONE word: F in bits 0-9, C in 10-19, E in 20-29 (<= 361 per board)
+          if constexpr (TAC) {
+            // the three sets of the row and their counts in ONE word: F in bits 0-9, C in 10-19, E in 20-29 (<= 361 per board;
+            // pattern: nine bits each, and L - at most eight points - from bit 27)
             tc[r] &= v[r];
             te[r] &= v[r];
             v[r] &= ~eye[r];
-            p[r] = ((uint32_t)__popc(v[r]) | ((uint32_t)__popc(tc[r]) << 10) | ((uint32_t)__popc(te[r]) << 20)) + (r ? p[r - 1] : 0u);
+            uint32_t pw = (uint32_t)__popc(v[r]) | ((uint32_t)__popc(tc[r]) << FB) | ((uint32_t)__popc(te[r]) << (2 * FB));
+            if constexpr (POL == kPolPattern) {
+              const int d = r0 + r - prw;   // 0, 1, 2: the rows around the previous move
+              tl[r] = v[r] & (d == 0 ? pk[0] : (d == 1 ? pk[1] : (d == 2 ? pk[2] : 0u)));
+              pw |= (uint32_t)__popc(tl[r]) << (3 * FB);
+            }
+            p[r] = pw + (r ? p[r - 1] : 0u);
           } else {
             if constexpr (POL == kPolNoEyeFill) v[r] &= ~eye[r];
             p[r] = (uint32_t)__popc(v[r]) + (r ? p[r - 1] : 0u);
@@ -419,21 +467,24 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
         }
         const uint32_t uh = dpp0<QP_L0>(uq);
         uq = dpp0<QP_X1>(uq);
-        if constexpr (POL == kPolTactical) {
-          // the tier: C, else E, when the gate of this draw is open and the set is not empty, else F - the same in both lanes of
+        if constexpr (TAC) {
+          // the tier: C, else E (pattern: else L), when the gate of this draw is open and the set is not empty, else F - the same in both lanes of
           // the pair (n holds the pair's three totals); the rows and the counts of the chosen set take the place of the valid ones
           const bool gate = (uh & 3u) != 0u;
-          const bool useC = gate && ((n >> 10) & 0x3FFu) != 0u, useE = gate && !useC && (n >> 20) != 0u;
-          const uint32_t sh = useC ? 10u : (useE ? 20u : 0u);
+          const bool useC = gate && ((n >> FB) & FM) != 0u, useE = gate && !useC && (POL == kPolPattern ? (n >> (2 * FB)) & FM : n >> (2 * FB)) != 0u;
+          const bool useL = POL == kPolPattern && gate && !useC && !useE && (n >> (3 * FB)) != 0u;
+          const uint32_t sh = useC ? FB : (useE ? 2 * FB : (useL ? 3 * FB : 0u));
           const uint32_t mc = useC ? ~0u : 0u, me_ = useE ? ~0u : 0u;
 #pragma unroll
           for (int r = 0; r < RPL; ++r) {
-            v[r] = B3(mc, tc[r], B3(me_, te[r], v[r], T_SEL), T_SEL);
-            p[r] = (p[r] >> sh) & 0x3FFu;
+            uint32_t vf = v[r];
+            if constexpr (POL == kPolPattern) vf = B3(useL ? ~0u : 0u, tl[r], vf, T_SEL);
+            v[r] = B3(mc, tc[r], B3(me_, te[r], vf, T_SEL), T_SEL);
+            p[r] = (p[r] >> sh) & FM;
           }
-          T = (T >> sh) & 0x3FFu;
-          Pb = (Pb >> sh) & 0x3FFu;
-          n = (n >> sh) & 0x3FFu;
+          T = (T >> sh) & FM;
+          Pb = (Pb >> sh) & FM;
+          n = (n >> sh) & FM;
         }
         const uint32_t k = __umulhi(uh, POL != kPolUniform ? n : n + 1u);   // k == n: the pass (a policy: n == 0 alone)
         const bool hit = k >= Pb && k < Pb + T;       // this lane holds the k-th valid point
@@ -455,6 +506,8 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
         const uint32_t pt = cand | dpp0<QP_X1>(cand);
 #endif
         a_q = !live ? -1 : (k < n ? (int)pt : P);
+        // pattern: the action of a live ply is the next ply's previous one (a pass: none)
+        if constexpr (POL == kPolPattern) prevr = live ? (k < n ? (int)pt : -1) : prevr;
 #ifdef GG_R5_LOG
         // the log: one predicated 2-byte store from the pair's even lane (live: the board exists, b_first + s4 < B, and t < plies).
         // A store and no load: nothing in the ply waits for it (vmcnt is next looked at by the write-back)

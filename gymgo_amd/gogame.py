@@ -695,26 +695,39 @@ def batch_untrack(tracked, out=None):
 
 POLICIES = {'uniform': 0, 'no_eye_fill': 1}   # GG_POLICY_* of include/gymgo_amd.h
 PLAYOUT_POLICIES = {'uniform': 0, 'no_eye_fill': 1, 'tactical': 2}   # ... and GG_POLICY_TACTICAL of include/gymgo_amd_tactics.h
+# ... and the policies that answer the board's previous move, which the playouts therefore carry from launch to launch:
+# GG_POLICY_PATTERN of include/gymgo_amd_pattern.h, reached through the _policy3 entry points only
+LOCAL_PLAYOUT_POLICIES = {'pattern': 3}
 
 
 def _policy_code(policy):
-    """The playout policy's C code; ValueError for anything but the names of PLAYOUT_POLICIES (checked before a device is
-    touched).  Codes 0 and 1 go through the entry points of include/gymgo_amd.h, code 2 through the _policy2 ones."""
-    if not any(policy is k or (type(policy) is type(k) and policy == k) for k in PLAYOUT_POLICIES):
-        raise ValueError("policy must be 'uniform', 'no_eye_fill' or 'tactical' (got %r)" % (policy,))
-    return PLAYOUT_POLICIES[policy]
+    """The playout policy's C code; ValueError for anything but the names of PLAYOUT_POLICIES and LOCAL_PLAYOUT_POLICIES
+    (checked before a device is touched).  Codes 0 and 1 go through the entry points of include/gymgo_amd.h, code 2 through
+    the _policy2 ones, code 3 through the _policy3 ones."""
+    for table in (PLAYOUT_POLICIES, LOCAL_PLAYOUT_POLICIES):
+        if any(policy is k or (type(policy) is type(k) and policy == k) for k in table):
+            return table[policy]
+    raise ValueError("policy must be 'uniform', 'no_eye_fill', 'tactical' or 'pattern' (got %r)" % (policy,))
 
 
 def batch_rollout_tracked(tracked, rng, plies, auto_reset=True, last_actions=None, steps_done=None, *, policy='uniform'):
     """IN PLACE batch_rollout on tracked boards (gg_batch_rollout_tracked).  policy: 'uniform' (every legal point and the
     pass alike) or 'no_eye_fill' (the mover's eyes - batch_eye_mask - are never played, the pass only when nothing else is
     left; gg_batch_rollout_tracked_policy) or 'tactical' (take what can be taken, pull out what is about to be taken, three plies
-    in four, else as 'no_eye_fill' - batch_tactics gives the three sets; gg_batch_rollout_tracked_policy2)."""
+    in four, else as 'no_eye_fill' - batch_tactics gives the three sets; gg_batch_rollout_tracked_policy2) or 'pattern' (as
+    'tactical', and between escaping and the plain draw it answers the board's previous move where a 3x3 shape around one of
+    that move's eight neighbours calls for it - batch_patterns gives the sets; gg_batch_rollout_tracked_policy3).
+    last_actions (int32 [B], or None): receives every board's last action of the launch, -1 for a board that did not play.
+    policy='pattern' also READS it, as the previous action of every board (any value that is no point of the board: no
+    previous point), so a tensor carried from launch to launch makes launches of any lengths play what one launch of the total
+    length plays; None: no board has a previous point (a tensor of -1 is made for the call)."""
     pol = _policy_code(policy)
     N = _tracked_size(tracked)
     B = tracked.shape[0]
-    name = 'gg_batch_rollout_tracked' + ('', '_policy', '_policy2')[pol]
+    name = 'gg_batch_rollout_tracked' + ('', '_policy', '_policy2', '_policy3')[pol]
     extra = (pol,) if pol else ()
+    if pol == LOCAL_PLAYOUT_POLICIES['pattern'] and last_actions is None:
+        last_actions = torch.full((B,), -1, dtype=_I32, device=tracked.device)
     _lib.call(name, tracked, rng, last_actions, steps_done, B, N, int(plies), int(bool(auto_reset)), *extra,
               _lib.stream_ptr(tracked.device))
     return tracked
@@ -726,6 +739,8 @@ def batch_rollout_tracked_log(tracked, rng, plies, log, last_actions=None, steps
     action board b played at ply t of this launch - a point, or N*N for the pass; a board writes exactly the plies it played,
     every other entry keeps its bytes.  -> log."""
     pol = _policy_code(policy)
+    if pol not in PLAYOUT_POLICIES.values():
+        raise ValueError('batch_rollout_tracked_log has no policy=%r: the move log serves %s' % (policy, sorted(PLAYOUT_POLICIES)))
     N = _tracked_size(tracked)
     B = tracked.shape[0]
     if tuple(log.shape) != (B, int(plies)):
@@ -820,6 +835,17 @@ def _orient_arg(orient, B):
         raise ValueError('orient must be %d integers in 0..7, one per row (got %d of %s)' % (B, n, orient.dtype))
 
 
+def _last_arg(last, B):
+    """ValueError unless last is B integers that fit an int32 (a tensor or an array) - before a device is touched."""
+    if isinstance(last, torch.Tensor):
+        n, integral = last.numel(), not (last.dtype.is_floating_point or last.dtype.is_complex or last.dtype == torch.bool)
+    else:
+        last = np.asarray(last)
+        n, integral = last.size, last.dtype.kind in 'iu'
+    if not integral or n != B:
+        raise ValueError('last must be %d integers, the previous action of every row (got %d of %s)' % (B, n, last.dtype))
+
+
 def _side_arg(side, B):
     """ValueError unless side is B integers or booleans (a tensor or an array) - before a device is touched."""
     if isinstance(side, torch.Tensor):
@@ -847,6 +873,7 @@ def _counts_arg(counts, B):
 
 _NO_BYTES = ()   # _plane_launch's extra of an entry point that takes orient itself and writes no per-board bytes
 _AreaExtra = collections.namedtuple('_AreaExtra', 'side counts')   # _plane_launch's extra of gg_batch_area[_tracked]: its two optional pointers
+_LastExtra = collections.namedtuple('_LastExtra', 'last')   # ... of gg_batch_patterns[_tracked]: the previous actions (int32 [B]) or None, in front of orient
 
 
 def _plane_launch(name, boards, orient, out, extra, code, B, N, stream, launch=_lib.call):
@@ -858,6 +885,8 @@ def _plane_launch(name, boards, orient, out, extra, code, B, N, stream, launch=_
     or None (extra is an _AreaExtra)."""
     if type(extra) is _AreaExtra:
         args = (boards, orient, extra.side, out, extra.counts)
+    elif type(extra) is _LastExtra:
+        args = (boards, extra.last, orient, out)
     elif extra is _NO_BYTES:
         args = (boards, orient, out)
     elif extra is not False:
@@ -880,6 +909,9 @@ def _planes(name, count, align, boards, tracked, dtype, out, orient, extra=None)
     area = extra if type(extra) is _AreaExtra else None
     if area is not None:
         extra = isinstance(area.counts, torch.Tensor) or bool(area.counts)
+    lastx = extra if type(extra) is _LastExtra else None   # (the pattern planes: previous actions in, nothing but planes out)
+    if lastx is not None:
+        extra = _NO_BYTES
     if tracked:
         if not isinstance(boards, torch.Tensor) or boards.dim() != 2:
             raise ValueError('tracked boards are int32 [B, 5N+1] device tensors')
@@ -890,6 +922,8 @@ def _planes(name, count, align, boards, tracked, dtype, out, orient, extra=None)
         _planes_out(out, (B, count, N, N), dtype, align)
     if orient is not None:
         _orient_arg(orient, B)
+    if lastx is not None and lastx.last is not None:
+        _last_arg(lastx.last, B)
     if area is not None:
         if area.side is not None:
             _side_arg(area.side, B)
@@ -914,6 +948,8 @@ def _planes(name, count, align, boards, tracked, dtype, out, orient, extra=None)
     o = None if orient is None else _actions_tensor(orient, B, st.device)
     if area is not None:
         how = _AreaExtra(None if area.side is None else _side_tensor(area.side, B, st.device), bytes_)
+    elif lastx is not None:
+        how = _LastExtra(None if lastx.last is None else _actions_tensor(lastx.last, B, st.device))
     else:
         how = False if extra is None else _NO_BYTES if extra is _NO_BYTES else bytes_
     _plane_launch(name, st, o, planes, how, code, B, N, _lib.stream_ptr(st.device))
@@ -1165,6 +1201,37 @@ def batch_tactics_tracked(tracked, dtype=torch.uint8, out=None, orient=None):
     (gg_batch_tactics_tracked): bit for bit what batch_tactics gives for batch_untrack(tracked); every group is counted from
     the stones, the class rows are not read."""
     return _planes('gg_batch_tactics_tracked', TACTICS_PLANES, 1, tracked, True, dtype, out, orient, _NO_BYTES)
+
+
+# ---------------------------------------------------------------- the sets of the pattern playout policy
+PATTERN_PLANES = 2   # gg_pattern_planes() of include/gymgo_amd_pattern.h
+PATTERN_NAMES = ('pattern', 'local')
+
+
+def batch_patterns(batch_states, last=None, dtype=torch.uint8, out=None, orient=None):
+    """The two sets the 'pattern' playout policy adds to those of batch_tactics -> [B, 2, N, N] of `dtype` (gg_batch_patterns),
+    each value exactly 0 or 1 (PATTERN_NAMES); all zero for a game that has ended:
+       0  pattern  P: the empty points whose eight neighbours (empty, black, white, off the board) match one of the thirteen
+                   3x3 patterns of include/gymgo_amd_pattern.h in some rotation or reflection, under either colouring
+       1  local    L: the points of P among the up to eight neighbours of the previous move that are candidates of
+                   'no_eye_fill' (batch_tactics' plane 2)
+    last: the previous action of every board, B integers (a tensor or an array) that refer to the board as it is given, before
+    orient turns it; a value outside [0, N*N) - -1, the pass, anything - means no previous point, as does last=None: plane 1 is
+    then all zero.
+    The ply: with the gate of 'tactical' open it draws from the first non-empty of C, E, L, F; with it closed, from F.
+    dtype, out, orient and NumPy input: as batch_area_planes.  One launch; device memory of the result: 2 * B * N^2 elements."""
+    return _planes('gg_batch_patterns', PATTERN_PLANES, 1, batch_states, False, dtype, out, orient, _LastExtra(last))
+
+
+def patterns(state, last=None, dtype=torch.uint8):
+    """batch_patterns of one state [6, N, N] and its previous action (an integer or None) -> [2, N, N]."""
+    return _plane_single(lambda st, dt: batch_patterns(st, None if last is None else [int(last)], dt), state, dtype)
+
+
+def batch_patterns_tracked(tracked, last=None, dtype=torch.uint8, out=None, orient=None):
+    """batch_patterns of tracked boards (int32 [B, 5N+1], a device tensor) -> [B, 2, N, N] of `dtype`
+    (gg_batch_patterns_tracked): bit for bit what batch_patterns gives for batch_untrack(tracked)."""
+    return _planes('gg_batch_patterns_tracked', PATTERN_PLANES, 1, tracked, True, dtype, out, orient, _LastExtra(last))
 
 
 def batch_ownership(batch_states, side=None, orient=None):
@@ -1700,12 +1767,16 @@ def _drive_playouts(advance, counter, J, S, max_plies, chunk_plies, dev, what):
 
 
 def _run_queue(family, what, head, komi, bufs, counter, J, S, max_plies, chunk_plies, dev, policy=0):
-    """gg_<family>_begin, then gg_<family>_advance_policy (_policy2 for a policy beyond no_eye_fill) until the counter drains
-    (_drive_playouts).  head: the arguments up to chunk_plies, bufs: those from slots on (_queue_args, and what the family
-    adds); advance takes komi, the chunk count and the playout policy's code between the two."""
-    begin, advance = 'gg_%s_begin' % family, 'gg_%s_advance_policy%s' % (family, '2' if int(policy) > 1 else '')
+    """gg_<family>_begin, then gg_<family>_advance_policy (_policy2 for a policy beyond no_eye_fill, _policy3 for one of
+    LOCAL_PLAYOUT_POLICIES) until the counter drains (_drive_playouts).  head: the arguments up to chunk_plies, bufs: those
+    from slots on (_queue_args, and what the family adds); advance takes komi, the chunk count and the playout policy's code
+    between the two, and _policy3 the slots' previous actions (int32 [S], -1 after begin) behind bufs."""
+    begin, advance = 'gg_%s_begin' % family, 'gg_%s_advance_policy%s' % (family, ('', '', '2', '3')[int(policy)])
     stream = _lib.current_raw_stream(dev)   # torch's current stream: the counter copies of _drive_playouts go there too
     _lib.call(begin, *head, *bufs, stream)
+    if int(policy) in LOCAL_PLAYOUT_POLICIES.values():
+        with torch.cuda.device(dev):
+            bufs = tuple(bufs) + (torch.full((S,), -1, dtype=_I32, device=dev),)
     _drive_playouts(lambda n: _lib.call(advance, *head, float(komi), n, int(policy), *bufs, stream),
                     counter, J, S, max_plies, chunk_plies, dev, what)
 
@@ -1795,9 +1866,18 @@ def _back(box, res, row0=False):
     return res.cpu().numpy() if box.numpy else res
 
 
+def _policy_kw(kw):
+    """The checks of a forwarding call's policy= (_policy_code) and of what goes with it, before a device is touched: the move
+    log behind amaf=True and rave_equiv= serves PLAYOUT_POLICIES only."""
+    pol = _policy_code(kw.get('policy', 'uniform'))
+    if pol not in PLAYOUT_POLICIES.values() and (kw.get('amaf') or kw.get('rave_equiv') is not None):
+        raise ValueError('amaf=True / rave_equiv= have no policy=%r: the move log serves %s' % (kw['policy'], sorted(PLAYOUT_POLICIES)))
+    return pol
+
+
 def _single(batch_fn, state, *args, **kw):
     """The single-state form of a batch function: state [6, N, N] as a batch of one, row 0 of every result."""
-    _policy_code(kw.get('policy', 'uniform'))
+    _policy_kw(kw)
     box = _Box(state)
     return _back(box, batch_fn(box.t[None], *args, **kw), row0=True)
 
@@ -1822,11 +1902,11 @@ def batch_playouts(batch_states, playouts, max_plies=None, komi=0.0, seed=202609
     `slots` (working boards, default: enough to fill the device) or `chunk_plies` (plies per rollout launch between two
     harvests; max_plies must be a multiple of it), and shards by first_root concatenate to the whole.  Default max_plies:
     8 N^2 rounded up to a multiple of chunk_plies.  The roots are not modified.
-    policy: what a playout ply draws from - 'uniform' (batch_rollout's sampler), 'no_eye_fill' or 'tactical'
-    (batch_rollout_tracked).
+    policy: what a playout ply draws from - 'uniform' (batch_rollout's sampler), 'no_eye_fill', 'tactical' or 'pattern'
+    (batch_rollout_tracked; under 'pattern' a playout's first ply has no previous move, whatever led to the root).
     amaf=True: the same playouts, with their all-moves-as-first statistics -> PlayoutsAmaf (gg_playouts_advance_amaf: the
     rollouts log their moves, the harvest reduces per root which colour played each point first, and with what outcome)."""
-    pol = _policy_code(policy)
+    pol = _policy_kw({'policy': policy, 'amaf': amaf})
     box = _Box(batch_states)
     st = box.t
     R, N, K, max_plies, chunk_plies = _playout_args(st, playouts, max_plies, chunk_plies, first_root)
@@ -2042,7 +2122,7 @@ def batch_uct(batch_states, iterations, playouts, c=math.sqrt(2), max_plies=None
     is expanded.  So a node descends as soon as one action stands out, where the plain search first expands every legal
     action in board order.  The search needs 2 * iterations * playouts < 2^31 and chunk_plies <= 4096, and 8 N^2 more bytes
     per node."""
-    pol = _policy_code(policy)
+    pol = _policy_kw({'policy': policy, 'rave_equiv': rave_equiv})
     box = _Box(batch_states)
     st = box.t
     R, N, K, max_plies, chunk_plies = _playout_args(st, playouts, max_plies, chunk_plies, first_root)
@@ -2076,7 +2156,7 @@ def uct(state, iterations, playouts, **kw):
 def uct_actions(batch_states, iterations, playouts, **kw):
     """The UCT move of every root -> int64 [R]: the legal root child with the most visits after batch_uct(batch_states,
     iterations, playouts, **kw); ties go to the lowest action, a root without a legal move gives -1."""
-    _policy_code(kw.get('policy', 'uniform'))
+    _policy_kw(kw)
     box = _Box(batch_states)
     res = batch_uct(box.t, iterations, playouts, **kw)
     return _best_legal(box, res.legal, res.visits.to(_I64))

@@ -1,13 +1,13 @@
 """Batched Monte Carlo playouts (gogame.batch_playouts) against the tracked rollout they are built on; prints one JSON line.
 
-  python tools/bench_playout.py [--roots 32768] [--k 16] [--size 19] [--slots S] [--reps 3] [--policy no_eye_fill | tactical]
+  python tools/bench_playout.py [--roots 32768] [--k 16] [--size 19] [--slots S] [--reps 3] [--policy no_eye_fill | tactical | pattern]
 
 Workload: R empty roots x K playouts to the end of the game (komi 7.5, default slot count: 256 per CU), without and with
 ownership.  Ceiling, in the same process: gg_batch_rollout_tracked on S boards x 256 plies with auto-reset (the rollout
 kernel the playouts run on, at the same batch size).  Plies are the plies the playouts actually played (plies_sum).
 For the split of device time between the rollout chunks and the harvest launches, run this once under
 `rocprofv3 --kernel-trace --stats -- python tools/bench_playout.py --reps 1` (k_rollout* vs k_po_harvest).
---policy no_eye_fill / tactical: the playouts (without ownership) under that policy NEXT TO the uniform ones in the same run, the two
+--policy no_eye_fill / tactical / pattern: the playouts (without ownership) under that policy NEXT TO the uniform ones in the same run, the two
 sides alternating (keys with the suffix _policy; policy_ratio_* = policy / uniform), and the tracked rollout under the policy.
 --amaf: under --policy (uniform included), the tracked rollout WITHOUT auto-reset from the same boards with and without the move log
 (gg_batch_rollout_tracked_log against gg_batch_rollout_tracked_policy2, 256 plies, the two sides alternating from copies:
@@ -29,7 +29,7 @@ def main():
     ap.add_argument('--slots', type=int, default=None)
     ap.add_argument('--chunk', type=int, default=32)
     ap.add_argument('--reps', type=int, default=3)
-    ap.add_argument('--policy', default='uniform', choices=sorted(('uniform', 'no_eye_fill', 'tactical')))
+    ap.add_argument('--policy', default='uniform', choices=sorted(('uniform', 'no_eye_fill', 'tactical', 'pattern')))
     ap.add_argument('--amaf', action='store_true')
     args = ap.parse_args()
 

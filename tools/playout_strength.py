@@ -1,6 +1,6 @@
 """Games of flat Monte Carlo under one playout policy against flat Monte Carlo under another; prints one JSON line.
 
-  python tools/playout_strength.py [--games 500] [--k 8] [--size 9] [--komi 7.5] [--policy tactical] [--against no_eye_fill]
+  python tools/playout_strength.py [--games 500] [--k 8] [--size 9] [--komi 7.5] [--policy tactical | pattern] [--against no_eye_fill | tactical]
 
 `--games` games with `--policy` as black and as many with it as white, from the empty board: every move is
 gogame.flat_mc_actions(states, k, komi, policy=the mover's policy) - equal playouts per candidate move on either side -, the games
