@@ -8,8 +8,8 @@ call().  A new entry point is one declaration in the header and one entry in the
 its own, include/gymgo_amd_area.h, and a table of its own, ABI_AREA, bound and called the same way; so have the past family
 (include/gymgo_amd_past.h, ABI_PAST), the Gumbel root rule of the PUCT search (include/gymgo_amd_gumbel.h, ABI_GUMBEL), the
 tactical playout policy with its planes (include/gymgo_amd_tactics.h, ABI_TACTICS), the AMAF statistics of the playouts with
-RAVE in the UCT search (include/gymgo_amd_amaf.h, ABI_AMAF) and the pattern playout policy with its planes
-(include/gymgo_amd_pattern.h, ABI_PATTERN).
+RAVE in the UCT search (include/gymgo_amd_amaf.h, ABI_AMAF), the pattern playout policy with its planes
+(include/gymgo_amd_pattern.h, ABI_PATTERN) and the move priors of the RAVE search (include/gymgo_amd_prior.h, ABI_PRIOR).
 """
 import collections
 import ctypes
@@ -237,6 +237,15 @@ ABI_PATTERN = {
     'gg_playouts_advance_policy3': ABI_TACTICS['gg_playouts_advance_policy2'][:-1] + _params(_I32, 'last') + _STREAM,
     'gg_move_playouts_advance_policy3': ABI_TACTICS['gg_move_playouts_advance_policy2'][:-1] + _params(_I32, 'last') + _STREAM,
 }
+# ... and of include/gymgo_amd_prior.h, the move priors of the RAVE search, in its order (tests/test_prior_host.py holds it against
+# its header).  weights is DEVICE memory: int32 [12], six (visits, wins) pairs
+_PRIOR_OUT = _params(_I32, 'weights', 'out') + _BN
+ABI_PRIOR = {
+    'gg_batch_move_priors': _params(_U8, 'states') + _params(_I32, 'last') + _PRIOR_OUT,
+    'gg_batch_move_priors_tracked': _params(_I32, 'tracked', 'last') + _PRIOR_OUT,
+    'gg_uct_prior_begin': _params(_I32, 'roots', 'last_actions') + _RNI + _params(_I32, 'weights', 'node_amaf') + _STREAM,
+    'gg_uct_prior_expand': _RNI + _params(_I32, 'weights', 'leaf', 'move', 'leaf_id', 'node_amaf') + _STREAM,
+}
 EXPORTS = tuple(ABI)
 EXPORTS_AREA = tuple(ABI_AREA)
 EXPORTS_PAST = tuple(ABI_PAST)
@@ -244,6 +253,7 @@ EXPORTS_GUMBEL = tuple(ABI_GUMBEL)
 EXPORTS_TACTICS = tuple(ABI_TACTICS)
 EXPORTS_AMAF = tuple(ABI_AMAF)
 EXPORTS_PATTERN = tuple(ABI_PATTERN)
+EXPORTS_PRIOR = tuple(ABI_PRIOR)
 _signatures = lambda table: {f: ([p.kind if isinstance(p.kind, type) else _vp for p in ps], _i32) for f, ps in table.items()}
 _SIGNATURES = _signatures(ABI)   # argtypes, restype
 _SIGNATURES_AREA = _signatures(ABI_AREA)
@@ -252,10 +262,11 @@ _SIGNATURES_GUMBEL = _signatures(ABI_GUMBEL)
 _SIGNATURES_TACTICS = _signatures(ABI_TACTICS)
 _SIGNATURES_AMAF = _signatures(ABI_AMAF)
 _SIGNATURES_PATTERN = _signatures(ABI_PATTERN)
+_SIGNATURES_PRIOR = _signatures(ABI_PRIOR)
 # call(): the number of parameters and (index, dtypes, name) of every pointer to device memory
 _POINTERS = {f: (len(ps), tuple((i, p.kind if isinstance(p.kind, tuple) else (p.kind,), p.name)
                                 for i, p in enumerate(ps) if not isinstance(p.kind, type)))
-             for table in (ABI, ABI_AREA, ABI_PAST, ABI_GUMBEL, ABI_TACTICS, ABI_AMAF, ABI_PATTERN) for f, ps in table.items()}
+             for table in (ABI, ABI_AREA, ABI_PAST, ABI_GUMBEL, ABI_TACTICS, ABI_AMAF, ABI_PATTERN, ABI_PRIOR) for f, ps in table.items()}
 
 _lib = None
 
@@ -270,7 +281,7 @@ def build(force=False):
     csrc = os.path.join(_HERE, 'csrc')
     srcs = [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(('.hip', '.h'))]
     srcs += [os.path.join(os.path.dirname(_HERE), 'include', h) for h in ('gymgo_amd.h', 'gymgo_amd_area.h', 'gymgo_amd_past.h', 'gymgo_amd_gumbel.h',
-                                                                                  'gymgo_amd_tactics.h', 'gymgo_amd_amaf.h', 'gymgo_amd_pattern.h')]
+                                                                                  'gymgo_amd_tactics.h', 'gymgo_amd_amaf.h', 'gymgo_amd_pattern.h', 'gymgo_amd_prior.h')]
     stale = not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < max(os.path.getmtime(f) for f in srcs)
     if force or stale:
         subprocess.check_call(['make', '-C', os.path.join(_HERE, 'csrc'), '-s', '-B', '-j3'])
@@ -287,7 +298,8 @@ def lib():
         L = ctypes.CDLL(LIB_PATH)
         for name, (argtypes, restype) in (list(_SIGNATURES.items()) + list(_SIGNATURES_AREA.items()) + list(_SIGNATURES_PAST.items())
                                           + list(_SIGNATURES_GUMBEL.items()) + list(_SIGNATURES_TACTICS.items())
-                                          + list(_SIGNATURES_AMAF.items()) + list(_SIGNATURES_PATTERN.items())):
+                                          + list(_SIGNATURES_AMAF.items()) + list(_SIGNATURES_PATTERN.items())
+                                          + list(_SIGNATURES_PRIOR.items())):
             fn = getattr(L, name)  # AttributeError if the .so does not export what the header declares
             fn.argtypes, fn.restype = argtypes, restype
         if L.gg_version() != ABI_VERSION:
@@ -437,7 +449,7 @@ def ptrs(fn, **tensors):
     given: for the paths that check their buffers once and hand call() the pointers from then on."""
     kinds = {p.name: p.kind for p in (ABI[fn] if fn in ABI else ABI_AREA[fn] if fn in ABI_AREA else ABI_PAST[fn] if fn in ABI_PAST
                                       else ABI_GUMBEL[fn] if fn in ABI_GUMBEL else ABI_TACTICS[fn] if fn in ABI_TACTICS else ABI_AMAF[fn] if fn in ABI_AMAF
-                                      else ABI_PATTERN[fn])}
+                                      else ABI_PATTERN[fn] if fn in ABI_PATTERN else ABI_PRIOR[fn])}
     return tuple(dev_ptr(t, kinds[n], n) for n, t in tensors.items())
 
 

@@ -1234,6 +1234,109 @@ def batch_patterns_tracked(tracked, last=None, dtype=torch.uint8, out=None, orie
     return _planes('gg_batch_patterns_tracked', PATTERN_PLANES, 1, tracked, True, dtype, out, orient, _LastExtra(last))
 
 
+# ---------------------------------------------------------------- move priors from the sets of both playout policies
+UctPrior = collections.namedtuple('UctPrior', 'even capture escape pattern local eye_fill')
+UctPrior.__doc__ = """A prior for the nodes of the RAVE search (batch_uct(prior=...), batch_move_priors; include/gymgo_amd_prior.h):
+six pairs (visits, wins) of integers with 0 <= wins <= visits, virtual simulations that a legal point of a new node starts with -
+`even` for every legal point, and on top of it `capture` for a point of C, `escape` for one of E (batch_tactics), `pattern` for one
+of P, `local` for one of L (batch_patterns, the previous point being the action that led to the node) and `eye_fill` for a legal
+point that is an eye of the mover (legal, and not in batch_tactics' plane 2)."""
+# The default: every legal point starts as eight simulations at 0.5; a capture, an escape and a local answer count as eight won
+# ones more, a pattern point as four, filling an own eye as sixteen lost ones.  UNTUNED: nobody has measured playing strength with
+# these values - they are data, not part of the rule.
+UCT_PRIOR = UctPrior(even=(8, 4), capture=(8, 8), escape=(8, 8), pattern=(4, 4), local=(8, 8), eye_fill=(16, 0))
+
+
+def _prior_arg(prior):
+    """prior=True -> UCT_PRIOR; else six (visits, wins) pairs of integers with 0 <= wins <= visits < 2^31 -> UctPrior of int pairs.
+    ValueError otherwise - before a device is touched."""
+    if prior is True:
+        prior = UCT_PRIOR
+    integral = lambda x: isinstance(x, (int, np.integer)) and not isinstance(x, (bool, np.bool_))
+    try:
+        pairs = [tuple(p) for p in prior]
+    except TypeError:
+        pairs = None
+    if (pairs is None or len(pairs) != len(UctPrior._fields) or any(len(p) != 2 or not all(integral(x) for x in p) for p in pairs)
+            or any(not 0 <= w <= v < 2 ** 31 for v, w in pairs)):
+        raise ValueError('prior must be True or six (visits, wins) pairs of integers with 0 <= wins <= visits, %s (got %r)'
+                         % (', '.join(UctPrior._fields), prior))
+    return UctPrior(*[(int(v), int(w)) for v, w in pairs])
+
+
+def _prior_weights(pr, device):
+    """The weights of the C entry points: int32 [12] on `device`, the six pairs in UctPrior's order."""
+    return torch.tensor([x for p in pr for x in p], dtype=_I32).to(device)
+
+
+def _move_priors(name, boards, pr, last, B, N):
+    out = torch.empty((B, N * N, 2), dtype=_I32, device=boards.device)
+    la = None if last is None else _actions_tensor(last, B, boards.device)
+    _lib.call(name, boards, la, _prior_weights(pr, boards.device), out, B, N, _lib.stream_ptr(boards.device))
+    return out
+
+
+def batch_move_priors(batch_states, prior=True, last=None):
+    """The pairs a prior gives the points of every board -> int32 [B, N*N, 2] (gg_batch_move_priors): entry [b, p] = (visits,
+    2 * wins) - the units of batch_uct's rave_visits / rave_score - of point p of board b: the sum of prior.even and of the pairs
+    of the sets p lies in (UctPrior) when p is legal (its plane-3 bit is clear and the game has not ended), (0, 0) otherwise.
+    prior: True (UCT_PRIOR) or a UctPrior; last: as in batch_patterns - the previous action of every board, anything that is no
+    point of the board means none.  This is what batch_uct(prior=...) adds to a new node.  One launch; NumPy in, NumPy out."""
+    pr = _prior_arg(prior)
+    B, N = _states_shape(batch_states)
+    if last is not None:
+        _last_arg(last, B)
+    box = _Box(batch_states)
+    return _back(box, _move_priors('gg_batch_move_priors', box.t, pr, last, B, N))
+
+
+def move_priors(state, prior=True, last=None):
+    """batch_move_priors of one state [6, N, N] and its previous action (an integer or None) -> int32 [N*N, 2]."""
+    pr = _prior_arg(prior)
+    box = _Box(state)
+    return _back(box, batch_move_priors(box.t[None], pr, None if last is None else [int(last)]), row0=True)
+
+
+def batch_move_priors_tracked(tracked, prior=True, last=None):
+    """batch_move_priors of tracked boards (int32 [B, 5N+1], a device tensor) -> int32 [B, N*N, 2] (gg_batch_move_priors_tracked):
+    bit for bit what batch_move_priors gives for batch_untrack(tracked)."""
+    pr = _prior_arg(prior)
+    if not isinstance(tracked, torch.Tensor) or tracked.dim() != 2:
+        raise ValueError('tracked boards are int32 [B, 5N+1] device tensors')
+    N, B = _tracked_size(tracked), tracked.shape[0]
+    if last is not None:
+        _last_arg(last, B)
+    return _move_priors('gg_batch_move_priors_tracked', tracked, pr, last, B, N)
+
+
+def _prior_kw(kw, R, N, iterations, playouts):
+    """The checks of batch_uct's prior= and last_actions= (kw: the keywords given) -> (UctPrior or None, int32 array [R] or None).
+    Every ValueError before a device is touched."""
+    prior, last = kw.get('prior'), kw.get('last_actions')
+    if prior is None:
+        if last is not None:
+            raise ValueError('last_actions= goes with prior=: it is the previous point of the root\'s prior')
+        return None, None
+    if kw.get('rave_equiv') is None:
+        raise ValueError('prior= needs rave_equiv=: the pairs it seeds are those of the RAVE search')
+    pr = _prior_arg(prior)
+    total = 2 * (int(iterations) * int(playouts) + sum(v for v, _ in pr))
+    if total >= 2 ** 31:
+        raise ValueError('a prior needs 2 * (iterations * playouts + the visits of its six pairs) < 2^31 (got %d)' % total)
+    if last is None:
+        return pr, None
+    if isinstance(last, torch.Tensor):
+        integral = not (last.dtype.is_floating_point or last.dtype.is_complex or last.dtype == torch.bool)
+        la = last.detach().cpu().numpy() if integral else None
+    else:
+        la = np.asarray(last)
+        integral = la.dtype.kind in 'iu'
+    if not integral or la.size != R or (la.size and (int(la.min()) < -1 or int(la.max()) > N * N)):
+        raise ValueError('last_actions must be %d integers in [-1, %d]: the previous action of every root, -1 or the pass for none'
+                         % (R, N * N))
+    return pr, la.astype(np.int32).reshape(R)
+
+
 def batch_ownership(batch_states, side=None, orient=None):
     """Who owns every point under Tromp-Taylor scoring, and by how much that side leads -> (owner int8 [B, N, N], margin int32
     [B]): owner = +1 on the points of batch_area_planes' plane 0, -1 on those of plane 1, 0 on neutral points; margin = the
@@ -2049,10 +2152,12 @@ def _legal_roots(st):
     return legal & ~ended[:, None]
 
 
-def _run_uct(roots, R, N, I, K, c, max_plies, komi, seed, first_root, S, chunk_plies, dev, policy=0, rave=None):
+def _run_uct(roots, R, N, I, K, c, max_plies, komi, seed, first_root, S, chunk_plies, dev, policy=0, rave=None, prior=None):
     """Device work of batch_uct on tracked roots -> (child int32 [R, I+1, A], links [R, I+1, 2], stats [R, I+1, 4],
     nodes [R], totals int64 [R, 2]); no launch for R = 0.  rave: None (the plain search, through the plain entry points) or
-    (rave_equiv, fpu) - then a sixth result, node_amaf int32 [R, I+1, N^2, 2]."""
+    (rave_equiv, fpu) - then a sixth result, node_amaf int32 [R, I+1, N^2, 2].  prior (with rave only): None - not one launch
+    more - or (weights int32 [12], last_actions int32 [R] or None) on the device: gg_uct_prior_begin seeds the roots,
+    gg_uct_prior_expand every new node once its board has been played."""
     W, A, NN = tracked_words(N), N * N + 1, I + 1
     boards = torch.empty((R, NN, W), dtype=_I32, device=dev)
     child = torch.empty((R, NN, A), dtype=_I32, device=dev)
@@ -2074,10 +2179,14 @@ def _run_uct(roots, R, N, I, K, c, max_plies, komi, seed, first_root, S, chunk_p
     _lib.call('gg_uct_begin', roots, R, N, I, K, boards, child, links, stats, nodes, stream)
     if rave is not None:
         abufs = _amaf_buffers(R, S, N, chunk_plies, dev)
+        if prior is not None:
+            _lib.call('gg_uct_prior_begin', roots, prior[1], R, N, I, prior[0], node_amaf, stream)
         for i in range(I):
             _lib.call('gg_uct_select_rave', R, N, I, K, c, float(rave[0]), float(rave[1]), log_table, boards, child, links, stats,
                       node_amaf, nodes, leaf, move, leaf_id, stream)
             _lib.call('gg_batch_play_moves_tracked', leaf, move, None, R, N, 1, stream)
+            if prior is not None:
+                _lib.call('gg_uct_prior_expand', R, N, I, prior[0], leaf, move, leaf_id, node_amaf, stream)
             _run_playouts(leaf, R, N, K, max_plies, komi, _uct_seed(seed, i), first_root, False, S, chunk_plies, dev, pbufs, policy,
                           amaf=abufs)
             _lib.call('gg_uct_backup_rave', R, N, I, K, counts, sums, abufs[3], totals, boards, links, stats, node_amaf, leaf, move,
@@ -2092,7 +2201,7 @@ def _run_uct(roots, R, N, I, K, c, max_plies, komi, seed, first_root, S, chunk_p
 
 
 def batch_uct(batch_states, iterations, playouts, c=math.sqrt(2), max_plies=None, komi=0.0, seed=20260927, first_root=0,
-              slots=None, chunk_plies=32, tree=False, *, policy='uniform', rave_equiv=None, fpu=1.0):
+              slots=None, chunk_plies=32, tree=False, *, policy='uniform', rave_equiv=None, fpu=1.0, prior=None, last_actions=None):
     """UCT search of `iterations` iterations from every root of batch_states ([R, 6, N, N]), the leaves evaluated with
     `playouts` playouts each -> Uct (device tensors for a device tensor, NumPy arrays for NumPy input).
 
@@ -2121,8 +2230,22 @@ def batch_uct(batch_states, iterations, playouts, c=math.sqrt(2), max_plies=None
     (float64, in this order, no fused multiply-add).  The largest U wins, ties to the lowest action; a winner without a child
     is expanded.  So a node descends as soon as one action stands out, where the plain search first expands every legal
     action in board order.  The search needs 2 * iterations * playouts < 2^31 and chunk_plies <= 4096, and 8 N^2 more bytes
-    per node."""
+    per node.
+
+    prior (with rave_equiv only): None - not one launch changes - or True (UCT_PRIOR, whose values are untuned) or a UctPrior:
+    heuristic prior knowledge in the tree.  Every node starts with batch_move_priors(its board, prior, last) ADDED to its
+    (n~, s~) pairs - the root before the first iteration, a new node when it is expanded -, `last` being the action that led to
+    the node, and for the roots last_actions: None, or R integers in [-1, N*N], -1 and the pass N*N meaning no previous point.
+    So a capture, an escape, a local answer to the previous move and a pattern point are tried before the rest of a new node's
+    points, and a move into the mover's own eye after them; no memory is added and the select and the backup are the same
+    kernels.  The pass has no pair - there is no slot for it -, its value stays q or fpu: a caller who seeds every point at 0.5
+    will usually want fpu at or below that.  rave_visits and rave_score of the result, and node_amaf of its tree, then include
+    the prior.  The search needs 2 * (iterations * playouts + the visits of the six pairs) < 2^31."""
     pol = _policy_kw({'policy': policy, 'rave_equiv': rave_equiv})
+    pr = la = None
+    if prior is not None or last_actions is not None:
+        pr, la = _prior_kw({'prior': prior, 'last_actions': last_actions, 'rave_equiv': rave_equiv}, *_states_shape(batch_states),
+                           iterations, playouts)
     box = _Box(batch_states)
     st = box.t
     R, N, K, max_plies, chunk_plies = _playout_args(st, playouts, max_plies, chunk_plies, first_root)
@@ -2135,7 +2258,10 @@ def batch_uct(batch_states, iterations, playouts, c=math.sqrt(2), max_plies=None
                              '<= 4096 (got %r, %r, %d, %d)' % (rave_equiv, fpu, 2 * I * K, chunk_plies))
     S = max(1, min(int(_default_slots(slots)), R * K))
     child, links, stats, nodes, totals, *more = _run_uct(_track_roots(st), R, N, I, K, c, max_plies, komi, seed, first_root, S,
-                                                         chunk_plies, st.device, policy=pol, rave=rave)
+                                                         chunk_plies, st.device, policy=pol, rave=rave,
+                                                         prior=None if pr is None or R == 0 else (
+                                                             _prior_weights(pr, st.device),
+                                                             None if la is None else torch.from_numpy(la).to(st.device)))
     rc = child[:, 0, :]
     kid = torch.gather(stats, 1, rc.clamp(min=0).long()[..., None].expand(R, N * N + 1, 4))
     kid = torch.where((rc >= 0)[..., None], kid, torch.zeros_like(kid))
@@ -2150,6 +2276,11 @@ def batch_uct(batch_states, iterations, playouts, c=math.sqrt(2), max_plies=None
 
 def uct(state, iterations, playouts, **kw):
     """batch_uct of one state [6, N, N] -> Uct of [N*N + 1] vectors and scalars (tree fields [iterations + 1])."""
+    if kw.get('prior') is not None or kw.get('last_actions') is not None:   # (its ValueErrors before a device is touched)
+        shape = tuple(np.shape(state))
+        if len(shape) != 3:
+            raise ValueError('state must be [6, N, N] (got %s)' % (shape,))
+        _prior_kw(kw, 1, shape[-1], iterations, playouts)
     return _single(batch_uct, state, iterations, playouts, **kw)
 
 
@@ -2157,6 +2288,8 @@ def uct_actions(batch_states, iterations, playouts, **kw):
     """The UCT move of every root -> int64 [R]: the legal root child with the most visits after batch_uct(batch_states,
     iterations, playouts, **kw); ties go to the lowest action, a root without a legal move gives -1."""
     _policy_kw(kw)
+    if kw.get('prior') is not None or kw.get('last_actions') is not None:   # (its ValueErrors before a device is touched)
+        _prior_kw(kw, *_states_shape(batch_states), iterations, playouts)
     box = _Box(batch_states)
     res = batch_uct(box.t, iterations, playouts, **kw)
     return _best_legal(box, res.legal, res.visits.to(_I64))
