@@ -381,6 +381,7 @@ int32_t launch_roots(void (*kern)(KArgs...), const void *p, int64_t R, void *hip
 // cells = A result cells per root, one per first move).  po_args: the argument checks both families share, in the order
 // the header documents, then the fill.  units = the roots (pairs) the jobs are counted over: J = units K.  The first-move
 // family's own checks arrive evaluated (mp_args) and are looked at where they stand in that order.
+// One body each, the exported functions forward: po_begin, po_advance (the chunk loop), po_advance_policy (the _policy* checks).
 static int32_t po_args(PoArgs &a, int64_t cells, int64_t units, bool own_sizes_ok, bool own_ptrs_ok, const uint32_t *roots, int64_t R,
                        int32_t N, int32_t K, int64_t first_root, uint64_t base_seed, int32_t max_plies, int32_t chunk_plies,
                        float komi, uint32_t *slots, uint64_t *rng, int64_t *plies, int64_t *job, int64_t S, int64_t *counter,
@@ -435,32 +436,52 @@ static int32_t po_begin(const Args &a, int64_t cells, int32_t N, void *hip_strea
   return (int32_t)hipGetLastError();
 }
 
-// advance: `chunks` times chunk_plies plies on every slot, then the harvest (refills, and in the first-move family the first
-// moves, happen there, between launches)
-// last (the _policy3 calls, LastArgs; else null): the previous action of every slot, in and out of every chunk; the pattern
-// policy needs it
-template <class Args>
-static int32_t po_advance(const Args &a, int32_t N, int32_t chunk_plies, int32_t chunks, int32_t policy, int32_t max_policy,
-                          void *hip_stream, int32_t *last = nullptr) {
-  if (chunks < 0 || !policy_ok(policy, max_policy)) return GG_E_BADARG;
-  if (policy == GG_POLICY_PATTERN && !last) return GG_E_NULLPTR;
+// advance, after the caller's checks: `chunks` times rollout() = chunk_plies plies on every slot, then the harvest on Args
+// (refills, and in the first-move family the first moves, happen there, between launches)
+template <class Args, class Rollout>
+static int32_t po_advance(const Args &a, int32_t N, int32_t chunks, void *hip_stream, Rollout &&rollout) {
   if (a.J == 0 || chunks == 0) return 0;
   OnDeviceOf on_dev(a.slots);
   const int cus = on_dev.cus();
   hipStream_t s = (hipStream_t)hip_stream;
   for (int c = 0; c < chunks; ++c) {
-    // the existing tracked dispatch, auto_reset = 0: finished and empty slots stay frozen
-    if (int32_t e = gg_batch_rollout_tracked_policy3(a.slots, a.rng, last, a.plies, a.S, N, chunk_plies, 0, policy, hip_stream)) return e;
+    if (int32_t e = rollout()) return e;
     launch_harvest<false>(a, N, cus, s);
     if (int32_t e = (int32_t)hipGetLastError()) return e;
   }
   return 0;
 }
 
+// the per-root family's po_args: one result cell per root, no checks of its own
+static int32_t playouts_args(PoArgs &a, const uint32_t *roots, int64_t R, int32_t N, int32_t K, int64_t first_root, uint64_t base_seed,
+                             int32_t max_plies, int32_t chunk_plies, float komi, uint32_t *slots, uint64_t *rng, int64_t *plies,
+                             int64_t *job, int64_t S, int64_t *counter, int32_t *counts, int64_t *sums, int32_t *ownership) {
+  return po_args(a, 1, R, true, true, roots, R, N, K, first_root, base_seed, max_plies, chunk_plies, komi, slots, rng, plies, job, S,
+                 counter, counts, sums, ownership);
+}
+
+// the _policy* entry points of both families: fill = the family's argument checks (playouts_args, mp_args) and q their arguments
+// as the entry point got them, max_policy = the highest policy the entry point accepts, last (_policy3; else null) = the
+// previous action of every slot, in and out of every chunk.  Only the pattern policy needs it: its chunks carry `last` and its harvest on LastArgs clears it for every slot it
+// refills or empties (include/gymgo_amd_pattern.h); policies 0 - 2 run on the plain arguments, last not looked at.
+template <class Args, class... P, class... Q>
+static int32_t po_advance_policy(int32_t max_policy, int32_t *last, int32_t N, int32_t chunk_plies, int32_t chunks, int32_t policy,
+                                 void *hip_stream, int32_t (*fill)(Args &, P...), Q... q) {
+  Args a;
+  if (int32_t e = fill(a, q...)) return e;
+  if (chunks < 0 || !policy_ok(policy, max_policy)) return GG_E_BADARG;
+  if (policy != GG_POLICY_PATTERN) last = nullptr;
+  else if (!last) return GG_E_NULLPTR;
+  // the existing tracked dispatch, auto_reset = 0: finished and empty slots stay frozen
+  auto rollout = [&] { return gg_batch_rollout_tracked_policy3(a.slots, a.rng, last, a.plies, a.S, N, chunk_plies, 0, policy, hip_stream); };
+  if (!last) return po_advance(a, N, chunks, hip_stream, rollout);
+  return po_advance(LastArgs<Args>{a, last}, N, chunks, hip_stream, rollout);
+}
+
 // ---- UCT tree search (gg_uct.h): the checks of po_args on the tree's sizes, in the same order, then the fill; the entry
-// points check their own pointers.  UctArgs serves three kernels and each of these members is written by one of them, so
-// they are not const there: gg_uct_select only reads boards, gg_uct_backup only reads links, leaf, move and leaf_id and
-// takes them as const - the casts below.
+// points check their own pointers (uct_select / uct_backup below).  UctArgs serves three kernels and each of these members is
+// written by one of them, so they are not const there: gg_uct_select only reads boards, gg_uct_backup only reads links, leaf,
+// move and leaf_id and takes them as const - the casts below.
 static int32_t uct_args(UctArgs &u, int64_t R, int32_t N, int32_t I, int32_t K, double c, const uint32_t *boards, int32_t *child,
                         const int32_t *links, int32_t *stats, int32_t *nodes, const uint32_t *leaf, const int32_t *move,
                         const int32_t *leaf_id, const double *log_table = nullptr, const int32_t *counts = nullptr,
@@ -501,11 +522,38 @@ static int32_t puct_leaves_args(PuctArgs &u, int64_t R, int32_t N, int32_t C, in
 }
 
 // ---- RAVE (gg_uct.h): uct_args, then what the two RAVE entry points add to it
-static int32_t rave_args(RaveArgs &u, int32_t I, int32_t K, double rave_equiv, double fpu, const int32_t *node_amaf, const int32_t *amaf) {
+static int32_t rave_args(UctArgs &u, int32_t I, int32_t K, double rave_equiv, double fpu, const int32_t *node_amaf, const int32_t *amaf) {
   if (2 * (int64_t)I * K > 0x7FFFFFFF) return GG_E_BADSIZE;   // s~ <= 2 I K is an int32
   if (!(rave_equiv > 0.0 && rave_equiv <= __DBL_MAX__) || !(fpu >= -__DBL_MAX__ && fpu <= __DBL_MAX__)) return GG_E_BADARG;
   u.node_amaf = const_cast<int32_t *>(node_amaf); u.amaf = amaf; u.k = rave_equiv; u.fpu = fpu;
   return 0;
+}
+
+// gg_uct_select[_rave] and gg_uct_backup[_rave]: one checked body each.  RAVE adds rave_args to the checks, its pointers
+// (node_amaf, amaf) to the null test and picks the kernel's instantiation; the plain entry points pass nothing for them.
+template <bool RAVE>
+static int32_t uct_select(int64_t R, int32_t N, int32_t I, int32_t K, double c, double rave_equiv, double fpu, const double *log_table,
+                          const uint32_t *boards, int32_t *child, int32_t *links, int32_t *stats, const int32_t *node_amaf,
+                          int32_t *nodes, uint32_t *leaf, int32_t *move, int32_t *leaf_id, void *hip_stream) {
+  UctArgs u;
+  if (int32_t e = uct_args(u, R, N, I, K, c, boards, child, links, stats, nodes, leaf, move, leaf_id, log_table)) return e;
+  if (int32_t e = RAVE ? rave_args(u, I, K, rave_equiv, fpu, node_amaf, nullptr) : 0) return e;
+  if (!log_table || !boards || !child || !links || !stats || (RAVE && !node_amaf) || !nodes || !leaf || !move || !leaf_id) return GG_E_NULLPTR;
+  if (R == 0) return 0;
+  return launch_roots(k_uct_select<RAVE>, leaf, R, hip_stream, u);
+}
+
+template <bool RAVE>
+static int32_t uct_backup(int64_t R, int32_t N, int32_t I, int32_t K, const int32_t *counts, const int64_t *sums, const int32_t *amaf,
+                          int64_t *totals, uint32_t *boards, const int32_t *links, int32_t *stats, int32_t *node_amaf,
+                          const uint32_t *leaf, const int32_t *move, const int32_t *leaf_id, void *hip_stream) {
+  UctArgs u;
+  if (int32_t e = uct_args(u, R, N, I, K, 0.0, boards, nullptr, links, stats, nullptr, leaf, move, leaf_id, nullptr, counts, sums, totals))
+    return e;
+  if (int32_t e = RAVE ? rave_args(u, I, K, 1.0, 0.0, node_amaf, amaf) : 0) return e;
+  if (!counts || !sums || (RAVE && (!amaf || !node_amaf)) || !boards || !links || !stats || !leaf || !move || !leaf_id) return GG_E_NULLPTR;
+  if (R == 0) return 0;
+  return launch_roots(k_uct_backup<RAVE>, leaf, R, hip_stream, u);
 }
 }  // namespace
 
@@ -1215,8 +1263,8 @@ int32_t gg_playouts_begin(const uint32_t *roots, int64_t R, int32_t N, int32_t K
                           int32_t max_plies, int32_t chunk_plies, uint32_t *slots, uint64_t *rng, int64_t *plies, int64_t *job,
                           int64_t S, int64_t *counter, int32_t *counts, int64_t *sums, int32_t *ownership, void *hip_stream) {
   PoArgs a;
-  if (int32_t e = po_args(a, 1, R, true, true, roots, R, N, K, first_root, base_seed, max_plies, chunk_plies, 0.f, slots, rng, plies,
-                          job, S, counter, counts, sums, ownership))
+  if (int32_t e = playouts_args(a, roots, R, N, K, first_root, base_seed, max_plies, chunk_plies, 0.f, slots, rng, plies, job, S, counter,
+                                counts, sums, ownership))
     return e;
   return po_begin(a, R, N, hip_stream);
 }
@@ -1233,62 +1281,44 @@ int32_t gg_playouts_advance_policy(const uint32_t *roots, int64_t R, int32_t N, 
                                    int32_t max_plies, int32_t chunk_plies, float komi, int32_t chunks, int32_t policy,
                                    uint32_t *slots, uint64_t *rng, int64_t *plies, int64_t *job, int64_t S, int64_t *counter,
                                    int32_t *counts, int64_t *sums, int32_t *ownership, void *hip_stream) {
-  PoArgs a;
-  if (int32_t e = po_args(a, 1, R, true, true, roots, R, N, K, first_root, base_seed, max_plies, chunk_plies, komi, slots, rng, plies,
-                          job, S, counter, counts, sums, ownership))
-    return e;
-  return po_advance(a, N, chunk_plies, chunks, policy, GG_POLICY_NO_EYE_FILL, hip_stream);
+  return po_advance_policy(GG_POLICY_NO_EYE_FILL, nullptr, N, chunk_plies, chunks, policy, hip_stream, playouts_args, roots, R, N, K, first_root,
+                           base_seed, max_plies, chunk_plies, komi, slots, rng, plies, job, S, counter, counts, sums, ownership);
 }
 
 int32_t gg_playouts_advance_policy2(const uint32_t *roots, int64_t R, int32_t N, int32_t K, int64_t first_root, uint64_t base_seed,
                                     int32_t max_plies, int32_t chunk_plies, float komi, int32_t chunks, int32_t policy,
                                     uint32_t *slots, uint64_t *rng, int64_t *plies, int64_t *job, int64_t S, int64_t *counter,
                                     int32_t *counts, int64_t *sums, int32_t *ownership, void *hip_stream) {
-  PoArgs a;
-  if (int32_t e = po_args(a, 1, R, true, true, roots, R, N, K, first_root, base_seed, max_plies, chunk_plies, komi, slots, rng, plies,
-                          job, S, counter, counts, sums, ownership))
-    return e;
-  return po_advance(a, N, chunk_plies, chunks, policy, GG_POLICY_TACTICAL, hip_stream);
+  return po_advance_policy(GG_POLICY_TACTICAL, nullptr, N, chunk_plies, chunks, policy, hip_stream, playouts_args, roots, R, N, K, first_root,
+                           base_seed, max_plies, chunk_plies, komi, slots, rng, plies, job, S, counter, counts, sums, ownership);
 }
 
-// ... and with the pattern policy accepted (include/gymgo_amd_pattern.h): the chunks carry `last`, the harvest on
-// LastArgs clears it for every slot it refills or empties.  Policies 0 - 2: the plain arguments, last not looked at.
+// ... and with the pattern policy accepted (include/gymgo_amd_pattern.h), which needs `last` (po_advance_policy)
 int32_t gg_playouts_advance_policy3(const uint32_t *roots, int64_t R, int32_t N, int32_t K, int64_t first_root, uint64_t base_seed,
                                     int32_t max_plies, int32_t chunk_plies, float komi, int32_t chunks, int32_t policy,
                                     uint32_t *slots, uint64_t *rng, int64_t *plies, int64_t *job, int64_t S, int64_t *counter,
                                     int32_t *counts, int64_t *sums, int32_t *ownership, int32_t *last, void *hip_stream) {
-  LastArgs<PoArgs> a;
-  if (int32_t e = po_args(a, 1, R, true, true, roots, R, N, K, first_root, base_seed, max_plies, chunk_plies, komi, slots, rng, plies,
-                          job, S, counter, counts, sums, ownership))
-    return e;
-  if (policy != GG_POLICY_PATTERN) return po_advance(static_cast<const PoArgs &>(a), N, chunk_plies, chunks, policy, GG_POLICY_PATTERN, hip_stream);
-  a.last = last;
-  return po_advance(a, N, chunk_plies, chunks, policy, GG_POLICY_PATTERN, hip_stream, last);
+  return po_advance_policy(GG_POLICY_PATTERN, last, N, chunk_plies, chunks, policy, hip_stream, playouts_args, roots, R, N, K, first_root,
+                           base_seed, max_plies, chunk_plies, komi, slots, rng, plies, job, S, counter, counts, sums, ownership);
 }
 
-// AMAF playouts (include/gymgo_amd_amaf.h): po_advance with the chunks on the log variants and the harvest on AmafArgs
+// AMAF playouts (include/gymgo_amd_amaf.h): its own checks, then po_advance with the chunks on the log variants and the
+// harvest on AmafArgs
 int32_t gg_playouts_advance_amaf(const uint32_t *roots, int64_t R, int32_t N, int32_t K, int64_t first_root, uint64_t base_seed,
                                  int32_t max_plies, int32_t chunk_plies, float komi, int32_t chunks, int32_t policy,
                                  uint32_t *slots, uint64_t *rng, int64_t *plies, int64_t *job, int64_t S, int64_t *counter,
                                  int32_t *counts, int64_t *sums, int32_t *ownership, uint16_t *log, uint32_t *first,
                                  int64_t *mark, int32_t *amaf, void *hip_stream) {
   AmafArgs a;
-  if (int32_t e = po_args(a, 1, R, true, true, roots, R, N, K, first_root, base_seed, max_plies, chunk_plies, komi, slots, rng, plies,
-                          job, S, counter, counts, sums, ownership))
+  if (int32_t e = playouts_args(a, roots, R, N, K, first_root, base_seed, max_plies, chunk_plies, komi, slots, rng, plies, job, S, counter,
+                                counts, sums, ownership))
     return e;
   if (chunks < 0 || !policy_ok(policy, GG_POLICY_TACTICAL) || chunk_plies > 4096) return GG_E_BADARG;
   if (!log || !first || !mark || !amaf) return GG_E_NULLPTR;
   a.log = log; a.first = first; a.mark = mark; a.amaf = amaf; a.chunk_plies = chunk_plies;
-  if (a.J == 0 || chunks == 0) return 0;
-  OnDeviceOf on_dev(a.slots);
-  const int cus = on_dev.cus();
-  hipStream_t s = (hipStream_t)hip_stream;
-  for (int c = 0; c < chunks; ++c) {
-    if (int32_t e = gg_batch_rollout_tracked_log(a.slots, a.rng, nullptr, a.plies, a.S, N, chunk_plies, policy, log, hip_stream)) return e;
-    launch_harvest<false>(a, N, cus, s);
-    if (int32_t e = (int32_t)hipGetLastError()) return e;
-  }
-  return 0;
+  return po_advance(a, N, chunks, hip_stream, [&] {
+    return gg_batch_rollout_tracked_log(a.slots, a.rng, nullptr, a.plies, a.S, N, chunk_plies, policy, log, hip_stream);
+  });
 }
 
 int32_t gg_move_playouts_plan(const uint32_t *roots, int64_t R, int32_t N, int32_t *offsets, int32_t *plan, void *hip_stream) {
@@ -1329,11 +1359,8 @@ int32_t gg_move_playouts_advance_policy(const uint32_t *roots, int64_t R, int32_
                                         float komi, int32_t chunks, int32_t policy, uint32_t *slots, uint64_t *rng,
                                         int64_t *plies, int64_t *job, int64_t S, int64_t *counter, int32_t *counts,
                                         int64_t *sums, void *hip_stream) {
-  MpArgs m;
-  if (int32_t e = mp_args(m, roots, R, N, plan, T, K, first_root, base_seed, max_plies, chunk_plies, komi, slots, rng, plies, job,
-                          S, counter, counts, sums))
-    return e;
-  return po_advance(m, N, chunk_plies, chunks, policy, GG_POLICY_NO_EYE_FILL, hip_stream);
+  return po_advance_policy(GG_POLICY_NO_EYE_FILL, nullptr, N, chunk_plies, chunks, policy, hip_stream, mp_args, roots, R, N, plan, T, K, first_root,
+                           base_seed, max_plies, chunk_plies, komi, slots, rng, plies, job, S, counter, counts, sums);
 }
 
 int32_t gg_move_playouts_advance_policy2(const uint32_t *roots, int64_t R, int32_t N, const int32_t *plan, int64_t T, int32_t K,
@@ -1341,11 +1368,8 @@ int32_t gg_move_playouts_advance_policy2(const uint32_t *roots, int64_t R, int32
                                          float komi, int32_t chunks, int32_t policy, uint32_t *slots, uint64_t *rng,
                                          int64_t *plies, int64_t *job, int64_t S, int64_t *counter, int32_t *counts,
                                          int64_t *sums, void *hip_stream) {
-  MpArgs m;
-  if (int32_t e = mp_args(m, roots, R, N, plan, T, K, first_root, base_seed, max_plies, chunk_plies, komi, slots, rng, plies, job,
-                          S, counter, counts, sums))
-    return e;
-  return po_advance(m, N, chunk_plies, chunks, policy, GG_POLICY_TACTICAL, hip_stream);
+  return po_advance_policy(GG_POLICY_TACTICAL, nullptr, N, chunk_plies, chunks, policy, hip_stream, mp_args, roots, R, N, plan, T, K, first_root,
+                           base_seed, max_plies, chunk_plies, komi, slots, rng, plies, job, S, counter, counts, sums);
 }
 
 int32_t gg_move_playouts_advance_policy3(const uint32_t *roots, int64_t R, int32_t N, const int32_t *plan, int64_t T, int32_t K,
@@ -1353,13 +1377,8 @@ int32_t gg_move_playouts_advance_policy3(const uint32_t *roots, int64_t R, int32
                                          float komi, int32_t chunks, int32_t policy, uint32_t *slots, uint64_t *rng,
                                          int64_t *plies, int64_t *job, int64_t S, int64_t *counter, int32_t *counts,
                                          int64_t *sums, int32_t *last, void *hip_stream) {
-  LastArgs<MpArgs> m;
-  if (int32_t e = mp_args(m, roots, R, N, plan, T, K, first_root, base_seed, max_plies, chunk_plies, komi, slots, rng, plies, job,
-                          S, counter, counts, sums))
-    return e;
-  if (policy != GG_POLICY_PATTERN) return po_advance(static_cast<const MpArgs &>(m), N, chunk_plies, chunks, policy, GG_POLICY_PATTERN, hip_stream);
-  m.last = last;
-  return po_advance(m, N, chunk_plies, chunks, policy, GG_POLICY_PATTERN, hip_stream, last);
+  return po_advance_policy(GG_POLICY_PATTERN, last, N, chunk_plies, chunks, policy, hip_stream, mp_args, roots, R, N, plan, T, K, first_root,
+                           base_seed, max_plies, chunk_plies, komi, slots, rng, plies, job, S, counter, counts, sums);
 }
 
 int32_t gg_uct_begin(const uint32_t *roots, int64_t R, int32_t N, int32_t I, int32_t K, uint32_t *boards, int32_t *child,
@@ -1383,49 +1402,28 @@ int32_t gg_uct_begin(const uint32_t *roots, int64_t R, int32_t N, int32_t I, int
 int32_t gg_uct_select(int64_t R, int32_t N, int32_t I, int32_t K, double c, const double *log_table, const uint32_t *boards,
                       int32_t *child, int32_t *links, int32_t *stats, int32_t *nodes, uint32_t *leaf, int32_t *move,
                       int32_t *leaf_id, void *hip_stream) {
-  UctArgs u;
-  if (int32_t e = uct_args(u, R, N, I, K, c, boards, child, links, stats, nodes, leaf, move, leaf_id, log_table)) return e;
-  if (!log_table || !boards || !child || !links || !stats || !nodes || !leaf || !move || !leaf_id) return GG_E_NULLPTR;
-  if (R == 0) return 0;
-  return launch_roots(k_uct_select, leaf, R, hip_stream, u);
+  return uct_select<false>(R, N, I, K, c, 1.0, 0.0, log_table, boards, child, links, stats, nullptr, nodes, leaf, move, leaf_id, hip_stream);
 }
 
 int32_t gg_uct_backup(int64_t R, int32_t N, int32_t I, int32_t K, const int32_t *counts, const int64_t *sums, int64_t *totals,
                       uint32_t *boards, const int32_t *links, int32_t *stats, const uint32_t *leaf, const int32_t *move,
                       const int32_t *leaf_id, void *hip_stream) {
-  UctArgs u;
-  if (int32_t e = uct_args(u, R, N, I, K, 0.0, boards, nullptr, links, stats, nullptr, leaf, move, leaf_id, nullptr, counts, sums,
-                           totals))
-    return e;
-  if (!counts || !sums || !boards || !links || !stats || !leaf || !move || !leaf_id) return GG_E_NULLPTR;
-  if (R == 0) return 0;
-  return launch_roots(k_uct_backup, leaf, R, hip_stream, u);
+  return uct_backup<false>(R, N, I, K, counts, sums, nullptr, totals, boards, links, stats, nullptr, leaf, move, leaf_id, hip_stream);
 }
 
 int32_t gg_uct_select_rave(int64_t R, int32_t N, int32_t I, int32_t K, double c, double rave_equiv, double fpu,
                            const double *log_table, const uint32_t *boards, int32_t *child, int32_t *links, int32_t *stats,
                            const int32_t *node_amaf, int32_t *nodes, uint32_t *leaf, int32_t *move, int32_t *leaf_id,
                            void *hip_stream) {
-  RaveArgs u;
-  if (int32_t e = uct_args(u, R, N, I, K, c, boards, child, links, stats, nodes, leaf, move, leaf_id, log_table)) return e;
-  if (int32_t e = rave_args(u, I, K, rave_equiv, fpu, node_amaf, nullptr)) return e;
-  if (!log_table || !boards || !child || !links || !stats || !node_amaf || !nodes || !leaf || !move || !leaf_id) return GG_E_NULLPTR;
-  if (R == 0) return 0;
-  return launch_roots(k_uct_select_rave, leaf, R, hip_stream, u);
+  return uct_select<true>(R, N, I, K, c, rave_equiv, fpu, log_table, boards, child, links, stats, node_amaf, nodes, leaf, move, leaf_id,
+                          hip_stream);
 }
 
 int32_t gg_uct_backup_rave(int64_t R, int32_t N, int32_t I, int32_t K, const int32_t *counts, const int64_t *sums,
                            const int32_t *amaf, int64_t *totals, uint32_t *boards, const int32_t *links, int32_t *stats,
                            int32_t *node_amaf, const uint32_t *leaf, const int32_t *move, const int32_t *leaf_id,
                            void *hip_stream) {
-  RaveArgs u;
-  if (int32_t e = uct_args(u, R, N, I, K, 0.0, boards, nullptr, links, stats, nullptr, leaf, move, leaf_id, nullptr, counts, sums,
-                           totals))
-    return e;
-  if (int32_t e = rave_args(u, I, K, 1.0, 0.0, node_amaf, amaf)) return e;
-  if (!counts || !sums || !amaf || !boards || !links || !stats || !node_amaf || !leaf || !move || !leaf_id) return GG_E_NULLPTR;
-  if (R == 0) return 0;
-  return launch_roots(k_uct_backup_rave, leaf, R, hip_stream, u);
+  return uct_backup<true>(R, N, I, K, counts, sums, amaf, totals, boards, links, stats, node_amaf, leaf, move, leaf_id, hip_stream);
 }
 
 int32_t gg_puct_begin(const uint32_t *roots, int64_t R, int32_t N, int32_t I, uint32_t *boards, int32_t *child, float *prior,

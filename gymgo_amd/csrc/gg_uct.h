@@ -1,5 +1,5 @@
-// gg_uct.h - batched UCT tree search (gg_uct_begin / gg_uct_select / gg_uct_backup): the tree of every root lives on the
-// device, the select and backup kernels walk it, the playouts of gg_po.h evaluate the leaves.
+// gg_uct.h - batched UCT tree search (gg_uct_begin / gg_uct_select[_rave] / gg_uct_backup[_rave]): the tree of every root lives
+// on the device, the select and backup kernels walk it, the playouts of gg_po.h evaluate the leaves.
 //
 // R independent searches of I iterations, one tree per root with room for I + 1 nodes (node 0 = the root).  Per node:
 // its tracked board, parent / action (-1 at the root), integer stats n / black wins / white wins / draws, and a child
@@ -7,13 +7,20 @@
 //   k_uct_select -> gg_batch_play_moves_tracked(leaf, move, T = 1) -> gg_playouts_begin / _advance on leaf -> k_uct_backup
 // so the leaf's move and its playouts reuse the existing kernels unchanged.
 //
+// One select and one backup kernel, each instantiated twice: <false> = plain UCT, <true> = RAVE (include/gymgo_amd_amaf.h,
+// DESIGN 35).  The modes differ in two places only, both under `if constexpr (RAVE)`: how a node scores its actions, and the
+// AMAF fold that follows the backup.
+//
 // SELECT (one wave per root): from x = 0, while x's game has not ended: the lanes stride over the A actions (legality from
-// the invalid rows and the flag word, the child table row, a gather of the child's stats); a ballot finds the lowest legal
-// action without a child - it is expanded (node y = nodes[r]++) and is the leaf - otherwise the wave's argmax of U (ties to
-// the lowest action) names the child to descend to.  leaf[r] gets the board of the node the walk stopped at (the new node's
-// parent, or the ended node itself), move[r] the expanded action (-1: evaluate the node as it is), leaf_id[r] the leaf.
+// the invalid rows and the flag word, the child table row, a gather of the child's stats) and the node names one action.
+// Plain: a ballot finds the lowest legal action without a child, otherwise the wave's argmax of uct_score over the children
+// (ties to the lowest action).  RAVE: the argmax of rave_score over every legal action, expanded or not.  An action without a
+// child is expanded (node y = nodes[r]++) and is the leaf; else the walk descends to the child.  leaf[r] gets the board of
+// the node the walk stopped at (the new node's parent, or the ended node itself), move[r] the expanded action (-1: evaluate
+// the node as it is), leaf_id[r] the leaf.
 // BACKUP (one wave per root): stores the played leaf board as node y's board and adds K and the iteration's counts along
-// the parent chain.  No atomics: a root's tree belongs to one wave.
+// the parent chain; RAVE then folds the iteration's first-play counts into the (n~, s~) of every node on the path.  No
+// atomics: a root's tree belongs to one wave.
 #pragma once
 #include "gg_common.h"
 
@@ -35,6 +42,11 @@ struct UctArgs {
   double c;
   int64_t R;
   int32_t N, I, K;
+  // RAVE only (no plain instantiation reads these): per node x and point p the pair (n~, s~) - the simulations through x in
+  // which x's mover played p first after x, twice its wins plus the draws among them
+  int32_t *node_amaf;        // [R][I+1][N^2][2] n~, s~
+  const int32_t *amaf;       // [R][2][3][N][N] the iteration's first-play counts (backup)
+  double k, fpu;             // rave_equiv, the value of an action without any count
 };
 
 // U(x, a) = (2 w + d) / (2 n) + c sqrt(L[n_x / K] / n) in float64, each operation rounded to nearest in this order: no
@@ -55,143 +67,8 @@ static __global__ void k_uct_begin(const uint32_t *__restrict__ roots, UctArgs a
   if (k == 0) a.nodes[r] = 1;
 }
 
-static __global__ __launch_bounds__(4 * kWave) void k_uct_select(UctArgs a) {
-  const int lane = threadIdx.x & (kWave - 1);
-  const int64_t wave = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) / kWave;
-  const int64_t nwaves = (gridDim.x * (int64_t)blockDim.x) / kWave;
-  const int N = a.N, W = 5 * N + 1, P = N * N, A = P + 1, NN = a.I + 1;
-  for (int64_t r = wave; r < a.R; r += nwaves) {
-    const uint32_t *bd = a.boards + r * NN * W;
-    int32_t *ch = a.child + r * NN * A;
-    int32_t *st = a.stats + r * NN * 4;
-    const int nodes = min(a.nodes[r], NN);   // (nodes <= I + 1 by construction: every index below stays inside the tree)
-    int x = 0, mv = -1, y = 0;
-    // every step goes to a child with a larger id: at most I steps (the bound also stops a walk over corrupt links)
-    for (int depth = 0; depth <= a.I; ++depth) {
-      const uint32_t *g = bd + (int64_t)x * W;
-      const uint32_t flag = g[5 * N];
-      if (flag & 4u) {   // the game has ended at x: x is the leaf, nothing is added
-        y = x;
-        break;
-      }
-      const int t = st[4 * x] / a.K;   // n_x is a multiple of K, at most I K
-      const double lx = a.log_table[t < 0 ? 0 : (t > a.I ? a.I : t)];
-      const bool white = (flag & 1u) != 0;
-      double best = -__builtin_inf();
-      int besta = A;
-      int freea = -1;
-      for (int a0 = 0; a0 < A; a0 += kWave) {
-        const int act = a0 + lane;
-        bool legal = false;
-        int c = -1;
-        if (act < A) {
-          const int row = act / N;
-          legal = act == P || !((g[2 * N + (act < P ? row : 0)] >> (act - row * N)) & 1u);
-          if (legal) c = ch[(int64_t)x * A + act];
-        }
-        const uint64_t free = __ballot(legal && c < 0);
-        if (free) {   // the lowest legal action without a child: expand it
-          freea = a0 + __builtin_ctzll(free);
-          break;
-        }
-        if (legal && c > x && c < nodes) {   // (children always have larger ids than their parent)
-          const int4 s = reinterpret_cast<const int4 *>(st)[c];
-          const double u = uct_score(white ? s.z : s.y, s.w, s.x, lx, a.c);
-          if (u > best) {   // (this lane's actions ascend: the first of equal scores stays)
-            best = u;
-            besta = act;
-          }
-        }
-      }
-      if (freea >= 0) {
-        if (nodes <= a.I) {   // (a select beyond I iterations finds no room: x is evaluated as it is)
-          y = nodes;
-          mv = freea;
-          if (lane == 0) {
-            ch[(int64_t)x * A + freea] = y;
-            a.links[(r * NN + y) * 2] = x;
-            a.links[(r * NN + y) * 2 + 1] = freea;
-            reinterpret_cast<int4 *>(st)[y] = make_int4(0, 0, 0, 0);
-            a.nodes[r] = nodes + 1;
-          }
-        } else {
-          y = x;
-        }
-        break;
-      }
-      // the wave's argmax, ties to the lowest action
-#pragma unroll
-      for (int o = kWave / 2; o > 0; o >>= 1) {
-        const double ob = __shfl_xor(best, o);
-        const int oa = __shfl_xor(besta, o);
-        if (ob > best || (ob == best && oa < besta)) {
-          best = ob;
-          besta = oa;
-        }
-      }
-      const int nx = besta < A ? ch[(int64_t)x * A + besta] : -1;
-      if (nx <= x || nx >= nodes) {   // (only with corrupt buffers: stop here)
-        y = x;
-        break;
-      }
-      x = nx;
-      y = x;
-    }
-    // the leaf board: the new node's parent (its move is played by the next launch) or the node itself
-    const uint32_t *g = bd + (int64_t)x * W;
-    uint32_t *out = a.leaf + r * W;
-    for (int k = lane; k < W; k += kWave) out[k] = g[k];
-    if (lane == 0) {
-      a.move[r] = mv;
-      a.leaf_id[r] = y;
-    }
-  }
-}
-
-static __global__ __launch_bounds__(4 * kWave) void k_uct_backup(UctArgs a) {
-  const int lane = threadIdx.x & (kWave - 1);
-  const int64_t wave = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) / kWave;
-  const int64_t nwaves = (gridDim.x * (int64_t)blockDim.x) / kWave;
-  const int W = 5 * a.N + 1, NN = a.I + 1;
-  for (int64_t r = wave; r < a.R; r += nwaves) {
-    const int y = a.leaf_id[r];
-    if (y < 0 || y >= NN) continue;
-    if (a.move[r] >= 0) {   // a new node: the played board is its board
-      const uint32_t *src = a.leaf + r * W;
-      uint32_t *dst = a.boards + (r * NN + y) * W;
-      for (int k = lane; k < W; k += kWave) dst[k] = src[k];
-    }
-    if (lane == 0) {
-      const int32_t *cn = a.counts + 4 * r;
-      const int32_t bw = cn[0], ww = cn[1], d = cn[2];
-      int32_t *st = a.stats + r * NN * 4;
-      const int32_t *ln = a.links + r * NN * 2;
-      int x = y;
-      for (int depth = 0; depth <= a.I && x >= 0 && x < NN; ++depth) {   // (parents have smaller ids: at most I + 1 nodes)
-        st[4 * x] += a.K;
-        st[4 * x + 1] += bw;
-        st[4 * x + 2] += ww;
-        st[4 * x + 3] += d;
-        x = ln[2 * x];
-      }
-      if (a.totals) {
-        a.totals[2 * r] += cn[3];
-        a.totals[2 * r + 1] += a.sums[2 * r + 1];
-      }
-    }
-  }
-}
-
-// ---- RAVE (gg_uct_select_rave / gg_uct_backup_rave, include/gymgo_amd_amaf.h): per node x and point p the pair
-// (n~, s~) - the simulations through x in which x's mover played p first after x, twice its wins plus the draws among them -
-// mixed into the value of every legal action, expanded or not, so that a node descends as soon as one action stands out.
-struct RaveArgs : UctArgs {
-  int32_t *node_amaf;      // [R][I+1][N^2][2] n~, s~
-  const int32_t *amaf;     // [R][2][3][N][N] the iteration's first-play counts (backup)
-  double k, fpu;           // rave_equiv, the value of an action without any count
-};
-
-// U(x, a) of the RAVE select in float64, each operation rounded to nearest in the order written, no contraction (the host
+// U(x, a) of the RAVE select: (n~, s~) mixed into the value of every legal action, expanded or not, so that a node descends as soon
+// as one action stands out.  In float64, each operation rounded to nearest in the order written, no contraction (the host
 // restatement computes the same expression in IEEE doubles): s = 2 w + d and s~ arrive as integers
 __device__ __noinline__ double rave_score(int32_t n, int32_t s, int32_t nt, int32_t st, double log_nx, double c, double k, double fpu) {
 #pragma clang fp contract(off)
@@ -211,7 +88,14 @@ __device__ __noinline__ double rave_score(int32_t n, int32_t s, int32_t nt, int3
   return n > 0 ? v + c * __dsqrt_rn(log_nx / dn) : v;
 }
 
-static __global__ __launch_bounds__(4 * kWave) void k_uct_select_rave(RaveArgs a) {
+// action act < A of the node with board g: the pass, or a point whose bit in the invalid rows is clear
+__device__ __forceinline__ bool uct_legal(const uint32_t *g, int act, int N, int P) {
+  const int row = act / N;
+  return act == P || !((g[2 * N + (act < P ? row : 0)] >> (act - row * N)) & 1u);
+}
+
+template <bool RAVE>
+static __global__ __launch_bounds__(4 * kWave) void k_uct_select(UctArgs a) {
   const int lane = threadIdx.x & (kWave - 1);
   const int64_t wave = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) / kWave;
   const int64_t nwaves = (gridDim.x * (int64_t)blockDim.x) / kWave;
@@ -220,7 +104,6 @@ static __global__ __launch_bounds__(4 * kWave) void k_uct_select_rave(RaveArgs a
     const uint32_t *bd = a.boards + r * NN * W;
     int32_t *ch = a.child + r * NN * A;
     int32_t *st = a.stats + r * NN * 4;
-    const int2 *na = reinterpret_cast<const int2 *>(a.node_amaf) + r * NN * P;
     const int nodes = min(a.nodes[r], NN);   // (nodes <= I + 1 by construction: every index below stays inside the tree)
     int x = 0, mv = -1, y = 0;
     // every step goes to a child with a larger id: at most I steps (the bound also stops a walk over corrupt links)
@@ -234,50 +117,63 @@ static __global__ __launch_bounds__(4 * kWave) void k_uct_select_rave(RaveArgs a
       const bool white = (flag & 1u) != 0;
       double best = -__builtin_inf();
       int besta = A;
+      int pick = -1;   // the action x chooses without an argmax
       for (int a0 = 0; a0 < A; a0 += kWave) {
         const int act = a0 + lane;
-        if (act >= A) continue;
-        const int row = act / N;
-        const bool legal = act == P || !((g[2 * N + (act < P ? row : 0)] >> (act - row * N)) & 1u);
-        if (!legal) continue;
-        const int c = ch[(int64_t)x * A + act];
-        int32_t n = 0, s = 0, nt = 0, sw = 0;
-        if (c > x && c < nodes) {   // (children always have larger ids than their parent)
-          const int4 q = reinterpret_cast<const int4 *>(st)[c];
-          n = q.x;
-          s = 2 * (white ? q.z : q.y) + q.w;
+        const bool legal = act < A && uct_legal(g, act, N, P);
+        const int c = legal ? ch[(int64_t)x * A + act] : -1;
+        double u;
+        if constexpr (RAVE) {   // every legal action has a score, expanded or not
+          if (!legal) continue;
+          int32_t n = 0, s = 0, nt = 0, sw = 0;
+          if (c > x && c < nodes) {   // (children always have larger ids than their parent)
+            const int4 q = reinterpret_cast<const int4 *>(st)[c];
+            n = q.x;
+            s = 2 * (white ? q.z : q.y) + q.w;
+          }
+          if (act < P) {
+            const int2 e = reinterpret_cast<const int2 *>(a.node_amaf)[(r * NN + x) * P + act];
+            nt = e.x;
+            sw = e.y;
+          }
+          u = rave_score(n, s, nt, sw, lx, a.c, a.k, a.fpu);
+        } else {   // the lowest legal action without a child goes first; only children have a score
+          const uint64_t free = __ballot(legal && c < 0);
+          if (free) {
+            pick = a0 + __builtin_ctzll(free);
+            break;
+          }
+          if (!(legal && c > x && c < nodes)) continue;
+          const int4 s = reinterpret_cast<const int4 *>(st)[c];
+          u = uct_score(white ? s.z : s.y, s.w, s.x, lx, a.c);
         }
-        if (act < P) {
-          const int2 e = na[(int64_t)x * P + act];
-          nt = e.x;
-          sw = e.y;
-        }
-        const double u = rave_score(n, s, nt, sw, lx, a.c, a.k, a.fpu);
         if (u > best) {   // (this lane's actions ascend: the first of equal scores stays)
           best = u;
           besta = act;
         }
       }
-      // the wave's argmax, ties to the lowest action
+      if (pick < 0) {   // the wave's argmax, ties to the lowest action
 #pragma unroll
-      for (int o = kWave / 2; o > 0; o >>= 1) {
-        const double ob = __shfl_xor(best, o);
-        const int oa = __shfl_xor(besta, o);
-        if (ob > best || (ob == best && oa < besta)) {
-          best = ob;
-          besta = oa;
+        for (int o = kWave / 2; o > 0; o >>= 1) {
+          const double ob = __shfl_xor(best, o);
+          const int oa = __shfl_xor(besta, o);
+          if (ob > best || (ob == best && oa < besta)) {
+            best = ob;
+            besta = oa;
+          }
         }
+        pick = besta;
       }
-      if (besta >= A) break;   // (no action scored: only with corrupt buffers - the pass is always legal)
-      const int nx = ch[(int64_t)x * A + besta];
-      if (nx < 0) {   // the winner has no child: expand it
+      if (pick >= A) break;   // (no action scored: only with corrupt buffers - the pass is always legal)
+      const int nx = ch[(int64_t)x * A + pick];
+      if (nx < 0) {   // the chosen action has no child: expand it
         if (nodes <= a.I) {   // (a select beyond I iterations finds no room: x is evaluated as it is)
           y = nodes;
-          mv = besta;
+          mv = pick;
           if (lane == 0) {
-            ch[(int64_t)x * A + besta] = y;
+            ch[(int64_t)x * A + pick] = y;
             a.links[(r * NN + y) * 2] = x;
-            a.links[(r * NN + y) * 2 + 1] = besta;
+            a.links[(r * NN + y) * 2 + 1] = pick;
             reinterpret_cast<int4 *>(st)[y] = make_int4(0, 0, 0, 0);
             a.nodes[r] = nodes + 1;
           }
@@ -299,10 +195,12 @@ static __global__ __launch_bounds__(4 * kWave) void k_uct_select_rave(RaveArgs a
   }
 }
 
-// One wave per root, the lanes stride over the points: lane l owns the points l, l + 64, ... (at most kRavePts = 6 on 19x19) and
-// keeps, per point, the path index of its first occurrence among the tree moves below the node the walk stands at.
+// The AMAF fold of the RAVE backup: the lanes stride over the points: lane l owns the points l, l + 64, ... (at most kRavePts = 6
+// on 19x19) and keeps, per point, the path index of its first occurrence among the tree moves below the node the walk stands at.
 constexpr int kRavePts = (19 * 19 + kWave - 1) / kWave;
-static __global__ __launch_bounds__(4 * kWave) void k_uct_backup_rave(RaveArgs a) {
+
+template <bool RAVE>
+static __global__ __launch_bounds__(4 * kWave) void k_uct_backup(UctArgs a) {
   const int lane = threadIdx.x & (kWave - 1);
   const int64_t wave = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) / kWave;
   const int64_t nwaves = (gridDim.x * (int64_t)blockDim.x) / kWave;
@@ -333,64 +231,66 @@ static __global__ __launch_bounds__(4 * kWave) void k_uct_backup_rave(RaveArgs a
         a.totals[2 * r + 1] += a.sums[2 * r + 1];
       }
     }
-    // the playout's part per owned point and colour: (first plays, twice the colour's wins plus the draws among them)
-    int32_t pn[2][kRavePts], ps[2][kRavePts];
-    int firstj[kRavePts];   // path index j of the first tree move below the current node at this point, 0 = none
-    const int32_t *am = a.amaf + r * 6 * (int64_t)P;
-#pragma unroll
-    for (int k = 0; k < kRavePts; ++k) {
-      const int p = lane + k * kWave;
-      firstj[k] = 0;
-#pragma unroll
-      for (int c = 0; c < 2; ++c) {
-        pn[c][k] = ps[c][k] = 0;
-        if (p < P) {
-          const int32_t e0 = am[(3 * c) * P + p], e1 = am[(3 * c + 1) * P + p], e2 = am[(3 * c + 2) * P + p];
-          pn[c][k] = e0;
-          ps[c][k] = 2 * (c ? e2 : e1) + e0 - e1 - e2;
-        }
-      }
-    }
-    // the depth of the leaf: the links up to the root (parents have smaller ids: at most I of them, whatever the buffers hold)
-    int dpt = 0;
-    for (int x = y; dpt < a.I; ++dpt) {
-      const int p = ln[2 * x];
-      if (p < 0 || p >= x) break;
-      x = p;
-    }
-    // from the leaf up: node x = x_i gets its update, then the move that led to it joins the front of the sequence
-    int x = y;
-    for (int i = dpt; i >= 0; --i) {
-      // (the leaf's board is in `leaf`, whether it is a new node or not; every other node's board was stored by an earlier launch)
-      const uint32_t c = (i == dpt ? src[5 * N] : a.boards[(r * NN + x) * W + 5 * N]) & 1u;
-      const int32_t S = 2 * (c ? ww : bw) + d;
-      int2 *na = reinterpret_cast<int2 *>(a.node_amaf) + (r * NN + x) * (int64_t)P;
+    if constexpr (RAVE) {
+      // the playout's part per owned point and colour: (first plays, twice the colour's wins plus the draws among them)
+      int32_t pn[2][kRavePts], ps[2][kRavePts];
+      int firstj[kRavePts];   // path index j of the first tree move below the current node at this point, 0 = none
+      const int32_t *am = a.amaf + r * 6 * (int64_t)P;
 #pragma unroll
       for (int k = 0; k < kRavePts; ++k) {
         const int p = lane + k * kWave;
-        if (p >= P) continue;
-        int32_t dn, ds;
-        if (firstj[k] == 0) {
-          dn = c ? pn[1][k] : pn[0][k];
-          ds = c ? ps[1][k] : ps[0][k];
-        } else {
-          const bool mine = ((firstj[k] - i) & 1) != 0;
-          dn = mine ? a.K : 0;
-          ds = mine ? S : 0;
-        }
-        if (dn | ds) {
-          int2 e = na[p];
-          e.x += dn;
-          e.y += ds;
-          na[p] = e;
+        firstj[k] = 0;
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+          pn[c][k] = ps[c][k] = 0;
+          if (p < P) {
+            const int32_t e0 = am[(3 * c) * P + p], e1 = am[(3 * c + 1) * P + p], e2 = am[(3 * c + 2) * P + p];
+            pn[c][k] = e0;
+            ps[c][k] = 2 * (c ? e2 : e1) + e0 - e1 - e2;
+          }
         }
       }
-      if (i == 0) break;
-      const int m = ln[2 * x + 1];
+      // the depth of the leaf: the links up to the root (parents have smaller ids: at most I of them, whatever the buffers hold)
+      int dpt = 0;
+      for (int x = y; dpt < a.I; ++dpt) {
+        const int p = ln[2 * x];
+        if (p < 0 || p >= x) break;
+        x = p;
+      }
+      // from the leaf up: node x = x_i gets its update, then the move that led to it joins the front of the sequence
+      int x = y;
+      for (int i = dpt; i >= 0; --i) {
+        // (the leaf's board is in `leaf`, whether it is a new node or not; every other node's board was stored by an earlier launch)
+        const uint32_t c = (i == dpt ? src[5 * N] : a.boards[(r * NN + x) * W + 5 * N]) & 1u;
+        const int32_t S = 2 * (c ? ww : bw) + d;
+        int2 *na = reinterpret_cast<int2 *>(a.node_amaf) + (r * NN + x) * (int64_t)P;
 #pragma unroll
-      for (int k = 0; k < kRavePts; ++k)
-        if (m >= 0 && m == lane + k * kWave && m < P) firstj[k] = i;
-      x = ln[2 * x];
+        for (int k = 0; k < kRavePts; ++k) {
+          const int p = lane + k * kWave;
+          if (p >= P) continue;
+          int32_t dn, ds;
+          if (firstj[k] == 0) {
+            dn = c ? pn[1][k] : pn[0][k];
+            ds = c ? ps[1][k] : ps[0][k];
+          } else {
+            const bool mine = ((firstj[k] - i) & 1) != 0;
+            dn = mine ? a.K : 0;
+            ds = mine ? S : 0;
+          }
+          if (dn | ds) {
+            int2 e = na[p];
+            e.x += dn;
+            e.y += ds;
+            na[p] = e;
+          }
+        }
+        if (i == 0) break;
+        const int m = ln[2 * x + 1];
+#pragma unroll
+        for (int k = 0; k < kRavePts; ++k)
+          if (m >= 0 && m == lane + k * kWave && m < P) firstj[k] = i;
+        x = ln[2 * x];
+      }
     }
   }
 }

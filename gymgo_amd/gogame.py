@@ -1869,15 +1869,21 @@ def _drive_playouts(advance, counter, J, S, max_plies, chunk_plies, dev, what):
             ev.synchronize()
 
 
-def _run_queue(family, what, head, komi, bufs, counter, J, S, max_plies, chunk_plies, dev, policy=0):
+def _run_queue(family, what, head, komi, bufs, counter, J, S, max_plies, chunk_plies, dev, policy=0, amaf=None):
     """gg_<family>_begin, then gg_<family>_advance_policy (_policy2 for a policy beyond no_eye_fill, _policy3 for one of
-    LOCAL_PLAYOUT_POLICIES) until the counter drains (_drive_playouts).  head: the arguments up to chunk_plies, bufs: those
-    from slots on (_queue_args, and what the family adds); advance takes komi, the chunk count and the playout policy's code
-    between the two, and _policy3 the slots' previous actions (int32 [S], -1 after begin) behind bufs."""
-    begin, advance = 'gg_%s_begin' % family, 'gg_%s_advance_policy%s' % (family, ('', '', '2', '3')[int(policy)])
+    LOCAL_PLAYOUT_POLICIES; _amaf with amaf) until the counter drains (_drive_playouts).  head: the arguments up to chunk_plies,
+    bufs: those from slots on (_queue_args, and what the family adds); advance takes komi, the chunk count and the playout
+    policy's code between the two, and behind bufs _policy3 the slots' previous actions (int32 [S], -1 after begin), _amaf the
+    buffers of amaf (_amaf_buffers; all but the log zeroed here: only written log entries are read)."""
+    begin = 'gg_%s_begin' % family
+    advance = 'gg_%s_advance_%s' % (family, 'policy' + ('', '', '2', '3')[int(policy)] if amaf is None else 'amaf')
     stream = _lib.current_raw_stream(dev)   # torch's current stream: the counter copies of _drive_playouts go there too
     _lib.call(begin, *head, *bufs, stream)
-    if int(policy) in LOCAL_PLAYOUT_POLICIES.values():
+    if amaf is not None:
+        for t in amaf[1:]:
+            t.zero_()
+        bufs = tuple(bufs) + tuple(amaf)
+    elif int(policy) in LOCAL_PLAYOUT_POLICIES.values():
         with torch.cuda.device(dev):
             bufs = tuple(bufs) + (torch.full((S,), -1, dtype=_I32, device=dev),)
     _drive_playouts(lambda n: _lib.call(advance, *head, float(komi), n, int(policy), *bufs, stream),
@@ -1906,23 +1912,16 @@ def _run_playouts(roots, R, N, K, max_plies, komi, seed, first_root, ownership, 
     """Device work of batch_playouts on tracked roots: -> (counts int32 [R, 4], sums int64 [R, 2], own or None); no launch
     for R = 0.  buffers: _playout_buffers(R, S, N, dev) to reuse (a search evaluates its leaves with the same buffers every
     iteration).  amaf: _amaf_buffers(R, S, N, chunk_plies, dev) - the playouts then run through gg_playouts_advance_amaf and
-    leave their first-play counts in amaf[3] (zeroed here)."""
+    leave their first-play counts in amaf[3]."""
     buffers = buffers if buffers is not None else _playout_buffers(R, S, N, dev)
     counter, counts, sums = buffers[4:]
     own = torch.empty((R, 2, N, N), dtype=_I32, device=dev) if ownership else None
     if R > 0:
         head = (roots, R, N, K, int(first_root), int(seed) & _M64, int(max_plies), int(chunk_plies))
-        if amaf is None:
-            _run_queue('playouts', 'batch_playouts', head, komi, _queue_args(*buffers) + (own,), counter, R * K, S, max_plies,
-                       chunk_plies, dev, policy)
-        else:
-            bufs = _queue_args(*buffers) + (own,)
-            stream = _lib.current_raw_stream(dev)
-            _lib.call('gg_playouts_begin', *head, *bufs, stream)
-            for t in amaf[1:]:      # first, mark and the output start from zero (the log needs no fill: only written entries are read)
-                t.zero_()
-            _drive_playouts(lambda n: _lib.call('gg_playouts_advance_amaf', *head, float(komi), n, int(policy), *bufs, *amaf, stream),
-                            counter, R * K, S, max_plies, chunk_plies, dev, 'batch_playouts')
+        # (amaf= only when given: tests/test_gpu_tactics.py and test_gpu_pattern.py stand in for _run_queue without that keyword)
+        with_amaf = {} if amaf is None else {'amaf': amaf}
+        _run_queue('playouts', 'batch_playouts', head, komi, _queue_args(*buffers) + (own,), counter, R * K, S, max_plies,
+                   chunk_plies, dev, policy, **with_amaf)
     return counts, sums, own
 
 
@@ -2013,19 +2012,16 @@ def batch_playouts(batch_states, playouts, max_plies=None, komi=0.0, seed=202609
     box = _Box(batch_states)
     st = box.t
     R, N, K, max_plies, chunk_plies = _playout_args(st, playouts, max_plies, chunk_plies, first_root)
-    S = max(1, min(int(_default_slots(slots)), R * K))
-    if not amaf:
-        counts, sums, own = _run_playouts(_track_roots(st), R, N, K, max_plies, komi, seed, first_root, ownership, S, chunk_plies,
-                                          st.device, policy=pol)
-        return _back(box, Playouts(counts[:, 0], counts[:, 1], counts[:, 2], counts[:, 3], sums[:, 0], sums[:, 1], own))
-    if chunk_plies > 4096:
+    if amaf and chunk_plies > 4096:
         raise ValueError('amaf=True needs chunk_plies <= 4096 (got %d)' % chunk_plies)
-    abufs = _amaf_buffers(R, S, N, chunk_plies, st.device)
-    if R == 0:
+    S = max(1, min(int(_default_slots(slots)), R * K))
+    abufs = _amaf_buffers(R, S, N, chunk_plies, st.device) if amaf else None
+    if amaf and R == 0:
         abufs[3].zero_()
     counts, sums, own = _run_playouts(_track_roots(st), R, N, K, max_plies, komi, seed, first_root, ownership, S, chunk_plies,
                                       st.device, policy=pol, amaf=abufs)
-    return _back(box, PlayoutsAmaf(counts[:, 0], counts[:, 1], counts[:, 2], counts[:, 3], sums[:, 0], sums[:, 1], own, abufs[3]))
+    res = Playouts(counts[:, 0], counts[:, 1], counts[:, 2], counts[:, 3], sums[:, 0], sums[:, 1], own)
+    return _back(box, PlayoutsAmaf(*res, abufs[3]) if amaf else res)
 
 
 def playouts(state, n, **kw):
@@ -2152,6 +2148,14 @@ def _legal_roots(st):
     return legal & ~ended[:, None]
 
 
+def _uct_prior_kw(kw, shape, iterations, playouts):
+    """_prior_kw for batch_uct and the calls that forward to it (its ValueErrors before a device is touched).  shape: a
+    function -> (R, N), asked only when prior= or last_actions= is given."""
+    if kw.get('prior') is None and kw.get('last_actions') is None:
+        return None, None
+    return _prior_kw(kw, *shape(), iterations, playouts)
+
+
 def _run_uct(roots, R, N, I, K, c, max_plies, komi, seed, first_root, S, chunk_plies, dev, policy=0, rave=None, prior=None):
     """Device work of batch_uct on tracked roots -> (child int32 [R, I+1, A], links [R, I+1, 2], stats [R, I+1, 4],
     nodes [R], totals int64 [R, 2]); no launch for R = 0.  rave: None (the plain search, through the plain entry points) or
@@ -2166,8 +2170,9 @@ def _run_uct(roots, R, N, I, K, c, max_plies, komi, seed, first_root, S, chunk_p
     nodes = torch.empty(R, dtype=_I32, device=dev)
     totals = torch.zeros((R, 2), dtype=_I64, device=dev)
     node_amaf = torch.zeros((R, NN, N * N, 2), dtype=_I32, device=dev) if rave is not None else None
+    res = (child, links, stats, nodes, totals) + ((node_amaf,) if rave is not None else ())
     if R == 0:
-        return (child, links, stats, nodes, totals) + ((node_amaf,) if rave is not None else ())
+        return res
     leaf = torch.empty((R, W), dtype=_I32, device=dev)
     move = torch.empty(R, dtype=_I32, device=dev)
     leaf_id = torch.empty(R, dtype=_I32, device=dev)
@@ -2177,27 +2182,24 @@ def _run_uct(roots, R, N, I, K, c, max_plies, komi, seed, first_root, S, chunk_p
     counts, sums = pbufs[5], pbufs[6]
     stream = _lib.current_raw_stream(dev)
     _lib.call('gg_uct_begin', roots, R, N, I, K, boards, child, links, stats, nodes, stream)
+    # the RAVE entry points take the plain ones' arguments with their own spliced in: rave_equiv and fpu, node_amaf, the AMAF counts
+    abufs, sfx, kf, na, am = None, '', (), (), ()
     if rave is not None:
         abufs = _amaf_buffers(R, S, N, chunk_plies, dev)
-        if prior is not None:
-            _lib.call('gg_uct_prior_begin', roots, prior[1], R, N, I, prior[0], node_amaf, stream)
-        for i in range(I):
-            _lib.call('gg_uct_select_rave', R, N, I, K, c, float(rave[0]), float(rave[1]), log_table, boards, child, links, stats,
-                      node_amaf, nodes, leaf, move, leaf_id, stream)
-            _lib.call('gg_batch_play_moves_tracked', leaf, move, None, R, N, 1, stream)
-            if prior is not None:
-                _lib.call('gg_uct_prior_expand', R, N, I, prior[0], leaf, move, leaf_id, node_amaf, stream)
-            _run_playouts(leaf, R, N, K, max_plies, komi, _uct_seed(seed, i), first_root, False, S, chunk_plies, dev, pbufs, policy,
-                          amaf=abufs)
-            _lib.call('gg_uct_backup_rave', R, N, I, K, counts, sums, abufs[3], totals, boards, links, stats, node_amaf, leaf, move,
-                      leaf_id, stream)
-        return child, links, stats, nodes, totals, node_amaf
+        sfx, kf, na, am = '_rave', (float(rave[0]), float(rave[1])), (node_amaf,), (abufs[3],)
+    select = ('gg_uct_select' + sfx, R, N, I, K, c, *kf, log_table, boards, child, links, stats, *na, nodes, leaf, move, leaf_id, stream)
+    backup = ('gg_uct_backup' + sfx, R, N, I, K, counts, sums, *am, totals, boards, links, stats, *na, leaf, move, leaf_id, stream)
+    if prior is not None:
+        _lib.call('gg_uct_prior_begin', roots, prior[1], R, N, I, prior[0], node_amaf, stream)
     for i in range(I):
-        _lib.call('gg_uct_select', R, N, I, K, c, log_table, boards, child, links, stats, nodes, leaf, move, leaf_id, stream)
+        _lib.call(*select)
         _lib.call('gg_batch_play_moves_tracked', leaf, move, None, R, N, 1, stream)
-        _run_playouts(leaf, R, N, K, max_plies, komi, _uct_seed(seed, i), first_root, False, S, chunk_plies, dev, pbufs, policy)
-        _lib.call('gg_uct_backup', R, N, I, K, counts, sums, totals, boards, links, stats, leaf, move, leaf_id, stream)
-    return child, links, stats, nodes, totals
+        if prior is not None:
+            _lib.call('gg_uct_prior_expand', R, N, I, prior[0], leaf, move, leaf_id, node_amaf, stream)
+        _run_playouts(leaf, R, N, K, max_plies, komi, _uct_seed(seed, i), first_root, False, S, chunk_plies, dev, pbufs, policy,
+                      amaf=abufs)
+        _lib.call(*backup)
+    return res
 
 
 def batch_uct(batch_states, iterations, playouts, c=math.sqrt(2), max_plies=None, komi=0.0, seed=20260927, first_root=0,
@@ -2242,10 +2244,8 @@ def batch_uct(batch_states, iterations, playouts, c=math.sqrt(2), max_plies=None
     will usually want fpu at or below that.  rave_visits and rave_score of the result, and node_amaf of its tree, then include
     the prior.  The search needs 2 * (iterations * playouts + the visits of the six pairs) < 2^31."""
     pol = _policy_kw({'policy': policy, 'rave_equiv': rave_equiv})
-    pr = la = None
-    if prior is not None or last_actions is not None:
-        pr, la = _prior_kw({'prior': prior, 'last_actions': last_actions, 'rave_equiv': rave_equiv}, *_states_shape(batch_states),
-                           iterations, playouts)
+    pr, la = _uct_prior_kw({'prior': prior, 'last_actions': last_actions, 'rave_equiv': rave_equiv},
+                           lambda: _states_shape(batch_states), iterations, playouts)
     box = _Box(batch_states)
     st = box.t
     R, N, K, max_plies, chunk_plies = _playout_args(st, playouts, max_plies, chunk_plies, first_root)
@@ -2276,11 +2276,11 @@ def batch_uct(batch_states, iterations, playouts, c=math.sqrt(2), max_plies=None
 
 def uct(state, iterations, playouts, **kw):
     """batch_uct of one state [6, N, N] -> Uct of [N*N + 1] vectors and scalars (tree fields [iterations + 1])."""
-    if kw.get('prior') is not None or kw.get('last_actions') is not None:   # (its ValueErrors before a device is touched)
-        shape = tuple(np.shape(state))
-        if len(shape) != 3:
-            raise ValueError('state must be [6, N, N] (got %s)' % (shape,))
-        _prior_kw(kw, 1, shape[-1], iterations, playouts)
+    def shape():
+        if len(np.shape(state)) != 3:
+            raise ValueError('state must be [6, N, N] (got %s)' % (tuple(np.shape(state)),))
+        return 1, np.shape(state)[-1]
+    _uct_prior_kw(kw, shape, iterations, playouts)
     return _single(batch_uct, state, iterations, playouts, **kw)
 
 
@@ -2288,8 +2288,7 @@ def uct_actions(batch_states, iterations, playouts, **kw):
     """The UCT move of every root -> int64 [R]: the legal root child with the most visits after batch_uct(batch_states,
     iterations, playouts, **kw); ties go to the lowest action, a root without a legal move gives -1."""
     _policy_kw(kw)
-    if kw.get('prior') is not None or kw.get('last_actions') is not None:   # (its ValueErrors before a device is touched)
-        _prior_kw(kw, *_states_shape(batch_states), iterations, playouts)
+    _uct_prior_kw(kw, lambda: _states_shape(batch_states), iterations, playouts)
     box = _Box(batch_states)
     res = batch_uct(box.t, iterations, playouts, **kw)
     return _best_legal(box, res.legal, res.visits.to(_I64))

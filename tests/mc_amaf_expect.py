@@ -149,6 +149,7 @@ class RaveTree(mc.Tree):
         self.I, self.P = I, N * N
         self.node_amaf = np.zeros((I + 1, N * N, 2), np.int64)
         self.max_depth = 0
+        self.replayed = 0      # the iterations in which a point of a tree move on the path was played again in a playout below it
 
     def select(self, K, c, L, k, fpu):
         """-> (leaf id, leaf board, new node or not)."""
@@ -210,53 +211,27 @@ class RaveTree(mc.Tree):
             self.node_amaf[x, :, 1] += ds
         self.backup(y, K, bw, ww, d)
 
+    def update(self, y, K, e, r):
+        """e: expected_playouts_amaf of the R leaves."""
+        tree_pts = {int(self.action[x]) for x in self.path(y)[1:] if self.action[x] < self.P}
+        if tree_pts and np.isin(e['sequences'][r * K:(r + 1) * K], list(tree_pts)).any():
+            self.replayed += 1
+        self.backup_rave(y, K, int(e['black_wins'][r]), int(e['white_wins'][r]), int(e['draws'][r]), e['amaf'][r].reshape(2, 3, self.P))
+
 
 def expected_uct_rave(roots, I, K, c=math.sqrt(2), rave_equiv=300.0, fpu=1.0, max_plies=None, komi=0.0, base_seed=20260927, first_root=0,
-                      chunk_plies=32, policy=0, iterations=None):
-    """-> dict of the outputs of batch_uct(rave_equiv=..., tree=True) (NumPy): mc_expect.ROOT_KEYS, 'rave_visits', 'rave_score',
-    'tree' (mc_expect.TREE_KEYS and 'node_amaf'), and for the premises 'trees', 'replayed' (per root: the iterations in which a
-    point of a tree move on the path was played again in a playout below it).  iterations: how many to run on trees with room
-    for I + 1 nodes (default I; more: a search past capacity)."""
+                      chunk_plies=32, policy=0, iterations=None, trees=None):
+    """-> dict of the outputs of batch_uct(rave_equiv=..., tree=True) (NumPy): mc_expect.run_uct's (mc_expect.ROOT_KEYS, 'tree',
+    'trees') on RaveTrees, plus 'rave_visits', 'rave_score', 'node_amaf' in 'tree', and for the premises 'replayed' (per root:
+    RaveTree.replayed).  iterations: how many to run on trees with room for I + 1 nodes (default I; more: a search past
+    capacity).  trees: the trees to search instead of new RaveTrees (mc_prior_expect's PriorTrees)."""
     roots = np.ascontiguousarray(roots, np.uint8)
-    R, _, N, _ = roots.shape
-    A, P = N * N + 1, N * N
-    if max_plies is None:
-        max_plies = -(-8 * N * N // chunk_plies) * chunk_plies
-    L = mc.log_table(I, K)
-    trees = [RaveTree(roots[r], I) for r in range(R)]
-    unfinished, plies, replayed = np.zeros(R, np.int64), np.zeros(R, np.int64), np.zeros(R, np.int64)
-    for i in range(I if iterations is None else iterations):
-        picked = [t.select(K, c, L, rave_equiv, fpu) for t in trees]
-        leaves = np.stack([b for _, b, _ in picked])
-        e = expected_playouts_amaf(leaves, K, max_plies, komi=komi, base_seed=int(mc.po_seed(base_seed, i)), first_root=first_root,
-                                   policy=policy)
-        am = e['amaf'].reshape(R, 2, 3, P)
-        for r, t in enumerate(trees):
-            y = picked[r][0]
-            tree_pts = {int(t.action[x]) for x in t.path(y)[1:] if t.action[x] < P}
-            seq = e['sequences'][r * K:(r + 1) * K]
-            if tree_pts and np.isin(seq, list(tree_pts)).any():
-                replayed[r] += 1
-            t.backup_rave(y, K, int(e['black_wins'][r]), int(e['white_wins'][r]), int(e['draws'][r]), am[r])
-        unfinished += e['unfinished']
-        plies += e['plies_sum']
-    out = {'legal': mc.legal_mask(roots)}
-    for k in ('visits', 'black_wins', 'white_wins', 'draws'):
-        out[k] = np.zeros((R, A), np.int32)
-    for r, t in enumerate(trees):
-        has = t.child[0] >= 0
-        for j, k in enumerate(('visits', 'black_wins', 'white_wins', 'draws')):
-            out[k][r, has] = t.stats[t.child[0, has], j]
-    out['root_visits'] = np.array([t.stats[0, 0] for t in trees], np.int32)
-    out['unfinished'], out['plies_sum'] = unfinished, plies
-    out['nodes'] = np.array([len(t.boards) for t in trees], np.int32)
-    tree = {'parent': np.stack([t.parent for t in trees]), 'action': np.stack([t.action for t in trees])}
-    for j, k in enumerate(('visits', 'black_wins', 'white_wins', 'draws')):
-        tree[k] = np.stack([t.stats[:, j] for t in trees]).astype(np.int32)
-    tree['node_amaf'] = np.stack([t.node_amaf for t in trees]).astype(np.int32)
-    out['tree'] = tree
-    out['rave_visits'], out['rave_score'] = tree['node_amaf'][:, 0, :, 0], tree['node_amaf'][:, 0, :, 1]
-    out['trees'], out['replayed'] = trees, replayed
+    trees = [RaveTree(root, I) for root in roots] if trees is None else trees
+    out = mc.run_uct(trees, roots, I if iterations is None else iterations, K, (K, c, mc.log_table(I, K), rave_equiv, fpu),
+                     functools.partial(expected_playouts_amaf, policy=policy), max_plies, komi, base_seed, first_root, chunk_plies)
+    out['tree']['node_amaf'] = na = np.stack([t.node_amaf for t in trees]).astype(np.int32)
+    out['rave_visits'], out['rave_score'] = na[:, 0, :, 0], na[:, 0, :, 1]
+    out['replayed'] = np.array([t.replayed for t in trees], np.int64)
     return out
 
 

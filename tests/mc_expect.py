@@ -2,7 +2,14 @@
 tests share, built from the C restatement under oracle/ (test infrastructure, CPU only).  Every playout is replayed whole
 (its job's generator, auto_reset off), scored with the restatement's areas and reduced on the host (replay); first moves
 and tree expansions are played by the restatement's next_state; the search itself is restated in Python (Tree: U in Python
-floats - IEEE doubles, the same operations in the same order, math.sqrt)."""
+floats - IEEE doubles, the same operations in the same order, math.sqrt).
+
+Each restatement exists once.  What a playout policy changes is the rollout that plays the playouts: replay, expected_playouts,
+expected_move_playouts, expected_uct and playout_evaluator_np take it as `rollout` - None: the uniform playouts, played by the C
+restatement; else a Python rollout of the policy modules (mc_policy_expect.policy_rollout's shape).  What a search mode changes
+is its tree class (Tree here, RaveTree in mc_amaf_expect, PriorTree in mc_prior_expect): run_uct drives any of them and packs
+the result."""
+import functools
 import math
 
 import numpy as np
@@ -79,12 +86,17 @@ def ownership(states):
 
 
 
-def replay(starts, jobs, K, max_plies, komi, base_seed, with_ownership=False):
+def replay(starts, jobs, K, max_plies, komi, base_seed, with_ownership=False, rollout=None):
     """K playouts from each of the G boards `starts` ([G, 6, N, N]); playout j of board g is global job jobs[g * K + j].
-    -> dict of KEYS (int64 [G]) and 'ownership' (int32 [G, 2, N, N] or None)."""
+    -> dict of KEYS (int64 [G]) and 'ownership' (int32 [G, 2, N, N] or None).  rollout: see the module's docstring; the plies
+    a Python rollout counts must be those its generators moved by."""
     G, _, N, _ = starts.shape
     rng0 = po_seed(base_seed, jobs)
-    fin, rng1, _ = c_oracle.batch_rollout_mt(np.repeat(starts, K, axis=0), rng0.copy(), max_plies, auto_reset=False)
+    if rollout is None:
+        fin, rng1, _ = c_oracle.batch_rollout_mt(np.repeat(starts, K, axis=0), rng0.copy(), max_plies, auto_reset=False)
+    else:
+        fin, rng1, _, steps = rollout(np.repeat(starts, K, axis=0), rng0.copy(), max_plies, auto_reset=False)
+        assert np.array_equal(plies_from_rng(rng0, rng1), steps)
     b, w = c_oracle.batch_areas_mt(fin)
     d = np.asarray(b, np.int64) - np.asarray(w, np.int64)
     x = d - komi
@@ -137,11 +149,11 @@ def most_visited(res):
 
 
 # ---------------------------------------------------------------- batch_playouts
-def expected_playouts(roots, K, max_plies, komi=0.0, base_seed=20260927, first_root=0, with_ownership=False):
+def expected_playouts(roots, K, max_plies, komi=0.0, base_seed=20260927, first_root=0, with_ownership=False, rollout=None):
     """-> dict of the per-root outputs of batch_playouts (NumPy), every playout replayed by the restatement."""
     roots = np.ascontiguousarray(roots, np.uint8)
     R = roots.shape[0]
-    out = replay(roots, first_root * K + np.arange(R * K), K, max_plies, komi, base_seed, with_ownership)
+    out = replay(roots, first_root * K + np.arange(R * K), K, max_plies, komi, base_seed, with_ownership, rollout)
     for k in KEYS[:4]:
         out[k] = out[k].astype(np.int32)
     return out
@@ -157,8 +169,9 @@ def children_of(roots, legal):
 
 
 
-def expected_move_playouts(roots, K, max_plies, komi=0.0, base_seed=20260927, first_root=0):
-    """-> dict of the outputs of batch_move_playouts ([R, A] NumPy arrays, legal included), every playout replayed."""
+def expected_move_playouts(roots, K, max_plies, komi=0.0, base_seed=20260927, first_root=0, rollout=None):
+    """-> dict of the outputs of batch_move_playouts ([R, A] NumPy arrays, legal included): every legal first move (whatever
+    the policy makes of it), every playout after it replayed."""
     roots = np.ascontiguousarray(roots, np.uint8)
     R, _, N, _ = roots.shape
     A = N * N + 1
@@ -170,7 +183,7 @@ def expected_move_playouts(roots, K, max_plies, komi=0.0, base_seed=20260927, fi
         return out
     r, a, kids = children_of(roots, legal)
     jobs = (((first_root + r) * A + a)[:, None] * K + np.arange(K)[None, :]).reshape(-1)
-    vals = replay(kids, jobs, K, max_plies, komi, base_seed)
+    vals = replay(kids, jobs, K, max_plies, komi, base_seed, rollout=rollout)
     for k in KEYS:
         out[k][r, a] = vals[k]
     return out
@@ -236,24 +249,28 @@ class Tree:
             self.stats[y] += (K, bw, ww, d)
             y = self.parent[y]
 
+    def update(self, y, K, e, r):
+        """Step 3 of an iteration: the results e (of the R leaves' playouts) of this tree's leaf y, the tree of root r."""
+        self.backup(y, K, e['black_wins'][r], e['white_wins'][r], e['draws'][r])
 
-def expected_uct(roots, I, K, c=math.sqrt(2), max_plies=None, komi=0.0, base_seed=20260927, first_root=0, chunk_plies=32):
-    """-> dict of the outputs of batch_uct (NumPy; ROOT_KEYS, plus 'tree': dict of TREE_KEYS arrays [R, I + 1])."""
-    roots = np.ascontiguousarray(roots, np.uint8)
+
+def run_uct(trees, roots, iterations, K, sel, playouts, max_plies, komi, base_seed, first_root, chunk_plies):
+    """The search over one tree per root, whatever the tree class: `iterations` times select a leaf per tree (t.select(*sel) ->
+    (leaf id, leaf board, ..)), evaluate the R leaves (playouts: expected_playouts or a function of its shape), update every
+    tree (t.update).  -> dict of the outputs of batch_uct (NumPy; ROOT_KEYS, 'tree': dict of TREE_KEYS arrays [R, nodes]) and
+    'trees'."""
     R, _, N, _ = roots.shape
     A = N * N + 1
     if max_plies is None:
         max_plies = -(-8 * N * N // chunk_plies) * chunk_plies
-    L = log_table(I, K)
-    trees = [Tree(roots[r], I) for r in range(R)]
     unfinished = np.zeros(R, np.int64)
     plies = np.zeros(R, np.int64)
-    for i in range(I):
-        picked = [t.select(K, c, L) for t in trees]
-        leaves = np.stack([b for _, b in picked])
-        e = expected_playouts(leaves, K, max_plies, komi=komi, base_seed=int(po_seed(base_seed, i)), first_root=first_root)
+    for i in range(iterations):
+        picked = [t.select(*sel) for t in trees]
+        leaves = np.stack([p[1] for p in picked])
+        e = playouts(leaves, K, max_plies, komi=komi, base_seed=int(po_seed(base_seed, i)), first_root=first_root)
         for r, t in enumerate(trees):
-            t.backup(picked[r][0], K, e['black_wins'][r], e['white_wins'][r], e['draws'][r])
+            t.update(picked[r][0], K, e, r)
         unfinished += e['unfinished']
         plies += e['plies_sum']
     out = {'legal': legal_mask(roots)}
@@ -274,6 +291,33 @@ def expected_uct(roots, I, K, c=math.sqrt(2), max_plies=None, komi=0.0, base_see
     out['trees'] = trees
     return out
 
+
+def expected_uct(roots, I, K, c=math.sqrt(2), max_plies=None, komi=0.0, base_seed=20260927, first_root=0, chunk_plies=32,
+                 rollout=None):
+    """-> run_uct's dict of the outputs of batch_uct, the leaves evaluated by expected_playouts (the tree keeps every legal
+    action, whatever the rollout)."""
+    roots = np.ascontiguousarray(roots, np.uint8)
+    return run_uct([Tree(root, I) for root in roots], roots, I, K, (K, c, log_table(I, K)),
+                   functools.partial(expected_playouts, rollout=rollout), max_plies, komi, base_seed, first_root, chunk_plies)
+
+
+def playout_evaluator_np(K, max_plies, komi=0.0, seed=20260927, first_root=0, rollout=None):
+    """The restatement of gogame.playout_evaluator (the evaluator of a PUCT search, mc_puct_expect): call j replays
+    batch_playouts(leaves, K, max_plies, komi, seed=po_seed(seed, j), first_root, policy=the rollout's) - uniform priors over
+    the legal actions, (the mover's wins - losses) / K."""
+    calls = [0]
+
+    def evaluate(states, legal):
+        j = calls[0]
+        calls[0] += 1
+        e = expected_playouts(states, K, max_plies, komi=komi, base_seed=int(po_seed(seed, j)), first_root=first_root, rollout=rollout)
+        with np.errstate(divide='ignore'):
+            p = np.where(legal, np.float32(1) / legal.sum(axis=1, keepdims=True).astype(np.float32), np.float32(0))
+        d = e['black_wins'].astype(np.int32) - e['white_wins'].astype(np.int32)
+        white = np.asarray(states)[:, 2, 0, 0] != 0
+        return p.astype(np.float32), np.where(white, -d, d).astype(np.float32) / np.float32(K)
+
+    return evaluate
 
 
 # ---------------------------------------------------------------- roots

@@ -8,8 +8,8 @@ The rule (include/gymgo_amd_pattern.h holds it word for word): P = the empty poi
 thirteen patterns in some view under either colouring; prev = the previous action if it is a point of the board; L = F and P and
 the up to eight neighbours of prev.  With the gate of `tactical` open the ply draws from the first non-empty of C, E, L, F, with
 it closed from F; the pass when the set is empty.  A reset ply, the ply after a pass and a job's first playout ply have no prev."""
+import functools
 import itertools
-import math
 
 import numpy as np
 
@@ -172,106 +172,12 @@ def trace_counts(trace):
     return out
 
 
-def replay_pattern(starts, jobs, K, max_plies, komi, base_seed, with_ownership=False):
-    """mc_expect.replay with the playouts played by pattern_rollout, every job from no previous point."""
-    G, _, N, _ = starts.shape
-    rng0 = mc.po_seed(base_seed, jobs)
-    fin, rng1, _, steps = pattern_rollout(np.repeat(starts, K, axis=0), rng0.copy(), max_plies, auto_reset=False)
-    assert np.array_equal(mc.plies_from_rng(rng0, rng1), steps)
-    b, w = c_oracle.batch_areas_mt(fin)
-    d = np.asarray(b, np.int64) - np.asarray(w, np.int64)
-    x = d - komi
-    ended = fin[:, 5, 0, 0] != 0
-    per = lambda v: np.asarray(v, np.int64).reshape(G, K).sum(axis=1)
-    out = {'black_wins': per(x > 0), 'white_wins': per(x < 0), 'draws': per(x == 0), 'unfinished': per(~ended),
-           'margin_sum': per(d), 'plies_sum': per(steps), 'ownership': None}
-    if with_ownership:
-        out['ownership'] = mc.ownership(fin).astype(np.int32).reshape(G, K, 2, N, N).sum(axis=1).astype(np.int32)
-    return out
-
-
-def expected_playouts_pattern(roots, K, max_plies, komi=0.0, base_seed=20260927, first_root=0, with_ownership=False):
-    """-> dict of the per-root outputs of batch_playouts(policy='pattern') (NumPy)."""
-    roots = np.ascontiguousarray(roots, np.uint8)
-    R = roots.shape[0]
-    out = replay_pattern(roots, first_root * K + np.arange(R * K), K, max_plies, komi, base_seed, with_ownership)
-    for k in mc.KEYS[:4]:
-        out[k] = out[k].astype(np.int32)
-    return out
-
-
-def expected_move_playouts_pattern(roots, K, max_plies, komi=0.0, base_seed=20260927, first_root=0):
-    """-> dict of the outputs of batch_move_playouts(policy='pattern'): every legal first move, the playouts after it under the
-    policy - from no previous point: the first move is not the playout's."""
-    roots = np.ascontiguousarray(roots, np.uint8)
-    R, _, N, _ = roots.shape
-    A = N * N + 1
-    legal = mc.legal_mask(roots)
-    out = {'legal': legal}
-    for k in mc.KEYS:
-        out[k] = np.zeros((R, A), np.int32 if k not in ('margin_sum', 'plies_sum') else np.int64)
-    if not legal.any():
-        return out
-    r, a, kids = mc.children_of(roots, legal)
-    jobs = (((first_root + r) * A + a)[:, None] * K + np.arange(K)[None, :]).reshape(-1)
-    vals = replay_pattern(kids, jobs, K, max_plies, komi, base_seed)
-    for k in mc.KEYS:
-        out[k][r, a] = vals[k]
-    return out
-
-
-def expected_uct_pattern(roots, I, K, c=math.sqrt(2), max_plies=None, komi=0.0, base_seed=20260927, first_root=0, chunk_plies=32):
-    """mc_expect.expected_uct with the leaves evaluated by expected_playouts_pattern (the tree keeps every legal action)."""
-    roots = np.ascontiguousarray(roots, np.uint8)
-    R, _, N, _ = roots.shape
-    A = N * N + 1
-    if max_plies is None:
-        max_plies = -(-8 * N * N // chunk_plies) * chunk_plies
-    L = mc.log_table(I, K)
-    trees = [mc.Tree(roots[r], I) for r in range(R)]
-    unfinished = np.zeros(R, np.int64)
-    plies = np.zeros(R, np.int64)
-    for i in range(I):
-        picked = [t.select(K, c, L) for t in trees]
-        leaves = np.stack([b for _, b in picked])
-        e = expected_playouts_pattern(leaves, K, max_plies, komi=komi, base_seed=int(mc.po_seed(base_seed, i)), first_root=first_root)
-        for r, t in enumerate(trees):
-            t.backup(picked[r][0], K, e['black_wins'][r], e['white_wins'][r], e['draws'][r])
-        unfinished += e['unfinished']
-        plies += e['plies_sum']
-    out = {'legal': mc.legal_mask(roots)}
-    for k in ('visits', 'black_wins', 'white_wins', 'draws'):
-        out[k] = np.zeros((R, A), np.int32)
-    for r, t in enumerate(trees):
-        has = t.child[0] >= 0
-        for j, k in enumerate(('visits', 'black_wins', 'white_wins', 'draws')):
-            out[k][r, has] = t.stats[t.child[0, has], j]
-    out['root_visits'] = np.array([t.stats[0, 0] for t in trees], np.int32)
-    out['unfinished'] = unfinished
-    out['plies_sum'] = plies
-    out['nodes'] = np.array([len(t.boards) for t in trees], np.int32)
-    tree = {'parent': np.stack([t.parent for t in trees]), 'action': np.stack([t.action for t in trees])}
-    for j, k in enumerate(('visits', 'black_wins', 'white_wins', 'draws')):
-        tree[k] = np.stack([t.stats[:, j] for t in trees]).astype(np.int32)
-    out['tree'] = tree
-    return out
-
-
-def playout_evaluator_np(K, max_plies, komi=0.0, seed=20260927, first_root=0):
-    """The restatement of gogame.playout_evaluator(policy='pattern') (mc_tactics_expect.playout_evaluator_np for this policy)."""
-    calls = [0]
-
-    def evaluate(states, legal):
-        j = calls[0]
-        calls[0] += 1
-        e = expected_playouts_pattern(states, K, max_plies, komi=komi, base_seed=int(mc.po_seed(seed, j)), first_root=first_root)
-        with np.errstate(divide='ignore'):
-            p = np.where(legal, np.float32(1) / legal.sum(axis=1, keepdims=True).astype(np.float32), np.float32(0))
-        d = e['black_wins'].astype(np.int32) - e['white_wins'].astype(np.int32)
-        white = np.asarray(states)[:, 2, 0, 0] != 0
-        return p.astype(np.float32), np.where(white, -d, d).astype(np.float32) / np.float32(K)
-
-    return evaluate
+# the restatements of mc_expect with the playouts played by pattern_rollout (policy='pattern'), every job from no previous
+# point: a first move is not the playout's
+expected_playouts_pattern = functools.partial(mc.expected_playouts, rollout=pattern_rollout)
+expected_move_playouts_pattern = functools.partial(mc.expected_move_playouts, rollout=pattern_rollout)
+expected_uct_pattern = functools.partial(mc.expected_uct, rollout=pattern_rollout)
+playout_evaluator_np = functools.partial(mc.playout_evaluator_np, rollout=pattern_rollout)
 
 
 # ---------------------------------------------------------------- hand-made positions

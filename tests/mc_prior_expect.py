@@ -70,47 +70,15 @@ class PriorTree(ma.RaveTree):
         return y, board, new
 
 
-def expected_uct_prior(roots, I, K, weights, last_actions=None, c=math.sqrt(2), rave_equiv=300.0, fpu=1.0, max_plies=None, komi=0.0,
-                       base_seed=20260927, first_root=0, chunk_plies=32, policy=0, iterations=None):
-    """mc_amaf_expect.expected_uct_rave on PriorTrees: -> dict of the outputs of batch_uct(rave_equiv=..., prior=weights,
-    last_actions=..., tree=True) (NumPy), and for the premises 'trees' and 'first' (per root: the first expanded action, None for a
-    root that expands nothing)."""
+def expected_uct_prior(roots, I, K, weights, last_actions=None, **kw):
+    """mc_amaf_expect.expected_uct_rave (and its keywords) on PriorTrees: -> dict of the outputs of batch_uct(rave_equiv=...,
+    prior=weights, last_actions=..., tree=True) (NumPy), 'replayed' included, plus 'child' in 'tree', and for the premises 'first'
+    (per root: the first expanded action, None for a root that expands nothing)."""
     roots = np.ascontiguousarray(roots, np.uint8)
-    R, _, N, _ = roots.shape
-    A, P = N * N + 1, N * N
-    if max_plies is None:
-        max_plies = -(-8 * N * N // chunk_plies) * chunk_plies
-    L = mc.log_table(I, K)
-    trees = [PriorTree(roots[r], I, weights, None if last_actions is None else int(last_actions[r])) for r in range(R)]
-    unfinished, plies = np.zeros(R, np.int64), np.zeros(R, np.int64)
-    for i in range(I if iterations is None else iterations):
-        picked = [t.select(K, c, L, rave_equiv, fpu) for t in trees]
-        leaves = np.stack([b for _, b, _ in picked])
-        e = ma.expected_playouts_amaf(leaves, K, max_plies, komi=komi, base_seed=int(mc.po_seed(base_seed, i)), first_root=first_root,
-                                      policy=policy)
-        am = e['amaf'].reshape(R, 2, 3, P)
-        for r, t in enumerate(trees):
-            t.backup_rave(picked[r][0], K, int(e['black_wins'][r]), int(e['white_wins'][r]), int(e['draws'][r]), am[r])
-        unfinished += e['unfinished']
-        plies += e['plies_sum']
-    out = {'legal': mc.legal_mask(roots)}
-    for k in ('visits', 'black_wins', 'white_wins', 'draws'):
-        out[k] = np.zeros((R, A), np.int32)
-    for r, t in enumerate(trees):
-        has = t.child[0] >= 0
-        for j, k in enumerate(('visits', 'black_wins', 'white_wins', 'draws')):
-            out[k][r, has] = t.stats[t.child[0, has], j]
-    out['root_visits'] = np.array([t.stats[0, 0] for t in trees], np.int32)
-    out['unfinished'], out['plies_sum'] = unfinished, plies
-    out['nodes'] = np.array([len(t.boards) for t in trees], np.int32)
-    tree = {'parent': np.stack([t.parent for t in trees]), 'action': np.stack([t.action for t in trees])}
-    for j, k in enumerate(('visits', 'black_wins', 'white_wins', 'draws')):
-        tree[k] = np.stack([t.stats[:, j] for t in trees]).astype(np.int32)
-    tree['node_amaf'] = np.stack([t.node_amaf for t in trees]).astype(np.int32)
-    tree['child'] = np.stack([t.child for t in trees]).astype(np.int32)
-    out['tree'] = tree
-    out['rave_visits'], out['rave_score'] = tree['node_amaf'][:, 0, :, 0], tree['node_amaf'][:, 0, :, 1]
-    out['trees'], out['first'] = trees, [t.first_expanded for t in trees]
+    trees = [PriorTree(roots[r], I, weights, None if last_actions is None else int(last_actions[r])) for r in range(len(roots))]
+    out = ma.expected_uct_rave(roots, I, K, trees=trees, **kw)
+    out['tree']['child'] = np.stack([t.child for t in trees]).astype(np.int32)
+    out['first'] = [t.first_expanded for t in trees]
     return out
 
 

@@ -147,23 +147,9 @@ def pass_evaluator_t(states, legal):
     return p, hash_evaluator_t(states, legal)[1]
 
 
-def playout_evaluator_np(K, max_plies, komi=0.0, seed=20260927, first_root=0, policy='uniform'):
-    """The restatement of gogame.playout_evaluator: call j replays batch_playouts(leaves, K, max_plies, komi,
-    seed=po_seed(seed, j), first_root) - uniform priors over the legal actions, (the mover's wins - losses) / K."""
-    calls = [0]
-    expected = mc.expected_playouts if policy == 'uniform' else mcp.expected_playouts_policy
-
-    def evaluate(states, legal):
-        j = calls[0]
-        calls[0] += 1
-        e = expected(states, K, max_plies, komi=komi, base_seed=int(mc.po_seed(seed, j)), first_root=first_root)
-        with np.errstate(divide='ignore'):
-            p = np.where(legal, np.float32(1) / legal.sum(axis=1, keepdims=True).astype(np.float32), np.float32(0))
-        d = e['black_wins'].astype(np.int32) - e['white_wins'].astype(np.int32)
-        white = np.asarray(states)[:, 2, 0, 0] != 0
-        return p.astype(np.float32), np.where(white, -d, d).astype(np.float32) / np.float32(K)
-
-    return evaluate
+def playout_evaluator_np(*args, policy='uniform', **kw):
+    """mc_expect.playout_evaluator_np for policy 'uniform' or 'no_eye_fill'."""
+    return mc.playout_evaluator_np(*args, rollout={'uniform': None, 'no_eye_fill': mcp.policy_rollout}[policy], **kw)
 
 
 # ---------------------------------------------------------------- the search

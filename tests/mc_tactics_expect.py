@@ -8,7 +8,7 @@ valid = the points whose invalid bit is clear; C = valid points next to an oppon
 mover's stone in low with at least two empty neighbours, F = valid points that are not eyes of the mover.  With u the high 32
 bits of the ply's draw the gate is open when (u & 3) != 0; the set is C if the gate is open and C is not empty, else E if the
 gate is open and E is not empty, else F; the pass when it is empty, else its floor(u n / 2^32)-th point."""
-import math
+import functools
 
 import numpy as np
 
@@ -136,89 +136,11 @@ def trace_counts(trace):
     return out
 
 
-def replay_tactical(starts, jobs, K, max_plies, komi, base_seed, with_ownership=False):
-    """mc_expect.replay with the playouts played by tactical_rollout."""
-    G, _, N, _ = starts.shape
-    rng0 = mc.po_seed(base_seed, jobs)
-    fin, rng1, _, steps = tactical_rollout(np.repeat(starts, K, axis=0), rng0.copy(), max_plies, auto_reset=False)
-    assert np.array_equal(mc.plies_from_rng(rng0, rng1), steps)
-    b, w = c_oracle.batch_areas_mt(fin)
-    d = np.asarray(b, np.int64) - np.asarray(w, np.int64)
-    x = d - komi
-    ended = fin[:, 5, 0, 0] != 0
-    per = lambda v: np.asarray(v, np.int64).reshape(G, K).sum(axis=1)
-    out = {'black_wins': per(x > 0), 'white_wins': per(x < 0), 'draws': per(x == 0), 'unfinished': per(~ended),
-           'margin_sum': per(d), 'plies_sum': per(steps), 'ownership': None}
-    if with_ownership:
-        out['ownership'] = mc.ownership(fin).astype(np.int32).reshape(G, K, 2, N, N).sum(axis=1).astype(np.int32)
-    return out
-
-
-def expected_playouts_tactical(roots, K, max_plies, komi=0.0, base_seed=20260927, first_root=0, with_ownership=False):
-    """-> dict of the per-root outputs of batch_playouts(policy='tactical') (NumPy)."""
-    roots = np.ascontiguousarray(roots, np.uint8)
-    R = roots.shape[0]
-    out = replay_tactical(roots, first_root * K + np.arange(R * K), K, max_plies, komi, base_seed, with_ownership)
-    for k in mc.KEYS[:4]:
-        out[k] = out[k].astype(np.int32)
-    return out
-
-
-def expected_move_playouts_tactical(roots, K, max_plies, komi=0.0, base_seed=20260927, first_root=0):
-    """-> dict of the outputs of batch_move_playouts(policy='tactical'): every legal first move, the playouts after it under
-    the policy."""
-    roots = np.ascontiguousarray(roots, np.uint8)
-    R, _, N, _ = roots.shape
-    A = N * N + 1
-    legal = mc.legal_mask(roots)
-    out = {'legal': legal}
-    for k in mc.KEYS:
-        out[k] = np.zeros((R, A), np.int32 if k not in ('margin_sum', 'plies_sum') else np.int64)
-    if not legal.any():
-        return out
-    r, a, kids = mc.children_of(roots, legal)
-    jobs = (((first_root + r) * A + a)[:, None] * K + np.arange(K)[None, :]).reshape(-1)
-    vals = replay_tactical(kids, jobs, K, max_plies, komi, base_seed)
-    for k in mc.KEYS:
-        out[k][r, a] = vals[k]
-    return out
-
-
-def expected_uct_tactical(roots, I, K, c=math.sqrt(2), max_plies=None, komi=0.0, base_seed=20260927, first_root=0, chunk_plies=32):
-    """mc_expect.expected_uct with the leaves evaluated by expected_playouts_tactical (the tree keeps every legal action)."""
-    roots = np.ascontiguousarray(roots, np.uint8)
-    R, _, N, _ = roots.shape
-    A = N * N + 1
-    if max_plies is None:
-        max_plies = -(-8 * N * N // chunk_plies) * chunk_plies
-    L = mc.log_table(I, K)
-    trees = [mc.Tree(roots[r], I) for r in range(R)]
-    unfinished = np.zeros(R, np.int64)
-    plies = np.zeros(R, np.int64)
-    for i in range(I):
-        picked = [t.select(K, c, L) for t in trees]
-        leaves = np.stack([b for _, b in picked])
-        e = expected_playouts_tactical(leaves, K, max_plies, komi=komi, base_seed=int(mc.po_seed(base_seed, i)), first_root=first_root)
-        for r, t in enumerate(trees):
-            t.backup(picked[r][0], K, e['black_wins'][r], e['white_wins'][r], e['draws'][r])
-        unfinished += e['unfinished']
-        plies += e['plies_sum']
-    out = {'legal': mc.legal_mask(roots)}
-    for k in ('visits', 'black_wins', 'white_wins', 'draws'):
-        out[k] = np.zeros((R, A), np.int32)
-    for r, t in enumerate(trees):
-        has = t.child[0] >= 0
-        for j, k in enumerate(('visits', 'black_wins', 'white_wins', 'draws')):
-            out[k][r, has] = t.stats[t.child[0, has], j]
-    out['root_visits'] = np.array([t.stats[0, 0] for t in trees], np.int32)
-    out['unfinished'] = unfinished
-    out['plies_sum'] = plies
-    out['nodes'] = np.array([len(t.boards) for t in trees], np.int32)
-    tree = {'parent': np.stack([t.parent for t in trees]), 'action': np.stack([t.action for t in trees])}
-    for j, k in enumerate(('visits', 'black_wins', 'white_wins', 'draws')):
-        tree[k] = np.stack([t.stats[:, j] for t in trees]).astype(np.int32)
-    out['tree'] = tree
-    return out
+# the restatements of mc_expect with the playouts played by tactical_rollout (policy='tactical')
+expected_playouts_tactical = functools.partial(mc.expected_playouts, rollout=tactical_rollout)
+expected_move_playouts_tactical = functools.partial(mc.expected_move_playouts, rollout=tactical_rollout)
+expected_uct_tactical = functools.partial(mc.expected_uct, rollout=tactical_rollout)
+playout_evaluator_np = functools.partial(mc.playout_evaluator_np, rollout=tactical_rollout)
 
 
 # ---------------------------------------------------------------- hand-made positions
@@ -309,25 +231,6 @@ def seam_roots():
         assert C[i, 0, 4] and C[i, 18, 4] and C[i, 4, 0] and C[i, 4, 18], i
     assert (counts[0][np.array([9, 10, 9, 10]), np.array([2, 6, 11, 15])] == 1).all()
     return roots
-
-
-def playout_evaluator_np(K, max_plies, komi=0.0, seed=20260927, first_root=0):
-    """The restatement of gogame.playout_evaluator(policy='tactical') (mc_puct_expect.playout_evaluator_np for this policy):
-    call j replays batch_playouts(leaves, K, max_plies, komi, seed=po_seed(seed, j), first_root, policy='tactical') - uniform
-    priors over the legal actions, (the mover's wins - losses) / K."""
-    calls = [0]
-
-    def evaluate(states, legal):
-        j = calls[0]
-        calls[0] += 1
-        e = expected_playouts_tactical(states, K, max_plies, komi=komi, base_seed=int(mc.po_seed(seed, j)), first_root=first_root)
-        with np.errstate(divide='ignore'):
-            p = np.where(legal, np.float32(1) / legal.sum(axis=1, keepdims=True).astype(np.float32), np.float32(0))
-        d = e['black_wins'].astype(np.int32) - e['white_wins'].astype(np.int32)
-        white = np.asarray(states)[:, 2, 0, 0] != 0
-        return p.astype(np.float32), np.where(white, -d, d).astype(np.float32) / np.float32(K)
-
-    return evaluate
 
 
 # ---------------------------------------------------------------- the batches of tests/test_gpu_tactics.py
