@@ -238,6 +238,32 @@ static __device__ unsigned long long gg_sweeps5[10];
 #ifndef GG_AB_SHL1
 #define GG_AB_SHL1 0
 #endif
+// A/B switches of round 32, the mask rows and the draw counter of phases 1 and 3 (gg_v5_kernel.h; docs/history/r32.md; all at 0 = round
+// 29's code, line for line).  All are in force at 19x19 only: 13x13 and 9x9 keep round 20's machine code.  Shipped: VALID1 and DRAWADD1
+// together, +2.0 % and +2.4 % on the headline launch in two alternations, every run above every run of the parent; VALID1 alone +2.0 % on
+// both medians with one run of twelve inside the parent's spread, DRAWADD1 alone +0.1 % and +0.6 %, not told apart from the spread;
+// ALLMOVE1 alone is inside the spread and on top of the other two it LOWERS the median both times (-0.3 %, -0.4 %): it stays 0.
+// GG_AB_VALID1 1 (shipped): a lane carries the VALID points of its rows (full & ~invalid) from the load to the write-back - the load converts once,
+//   the write-back forms full & ~valid once, so the stored words are what they were - and phase 1 draws from the carried rows as they
+//   are; the register part of the reset path (wave-uniform, known from the flag word) stands in front of the draw and sets the rows
+//   of a board being reset to full[] and its M to zero, its LDS clears with it (ahead of the policies' stone reads and of phase 1's
+//   stone store; the policy sets keep their & ~rm); phase 3 forms valid = (h3 | dn) & e in two v_bitop3 a row (e lies inside full) and
+//   ko clears its bit, 0: the invalid rows travel, phase 1 turns every row round (ten v_bitop3) and phase 3 takes three a row;
+// GG_AB_ALLMOVE1 1: when every lane's board moves (GG_BALLOT5(!moves_now) == 0: every full wave of live games) phase 3 assigns the new
+//   mask rows; otherwise - absent slots of a short wave, frozen boards - it selects as before, 0 (shipped): the select on every
+//   wave-ply (1: the compiler keeps two copies of the rows' last loop behind a scalar test and a branch);
+// GG_AB_DRAWADD1 1 (shipped): the pre-mix counter of the draw is a running 64-bit value that starts at x0 + t5 c and is advanced by 2 c behind each
+//   mix (one add-with-carry pair), 0: x0 + (t + t5) c by a 32 x 64 multiply every second ply.
+// (The round's fourth part, no row copy of M between the atari-join's branch and the mask rule, was not built: docs/history/r32.md.)
+#ifndef GG_AB_VALID1
+#define GG_AB_VALID1 1
+#endif
+#ifndef GG_AB_ALLMOVE1
+#define GG_AB_ALLMOVE1 0
+#endif
+#ifndef GG_AB_DRAWADD1
+#define GG_AB_DRAWADD1 1
+#endif
 #if GG_AB_BALLOT1
 // (used where a board size R is in scope; 13x13 and 9x9 keep __ballot and with it round 20's machine code)
 #define GG_BALLOT5(p) (R == 19 ? (unsigned long long)__builtin_amdgcn_ballot_w64(p) : __ballot(p))

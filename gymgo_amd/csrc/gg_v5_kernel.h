@@ -37,7 +37,7 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
   int *lastv = reinterpret_cast<int *>(lds + Lds5<R>::kMeta + kNB5);
   int *playedv = reinterpret_cast<int *>(lds + Lds5<R>::kMeta + 2 * kNB5);
   uint32_t *rngv = lds + Lds5<R>::kMeta + 3 * kNB5;   // [2 * s], [2 * s + 1]
-  uint32_t *tmp = lds + Lds5<R>::kTmp;      // tmp[(half * 2 + set) * RS + row], set 0 = invalid, 1 = M
+  uint32_t *tmp = lds + Lds5<R>::kTmp;      // tmp[(half * 2 + set) * RS + row], set 0 = invalid (GG_AB_VALID1, 19x19: valid), 1 = M
   uint32_t *clsv = lds + Lds5<R>::kCls;
   uint32_t *jobv = lds + Lds5<R>::kJob;
   uint32_t *gblk = lds + Lds5<R>::kG;
@@ -58,7 +58,11 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
     const int s5 = hf.lane >> 1, t2 = hf.lane & 1, r05 = RPL * t2;   // board / lane of the pair / first row of this lane
     // the next mover's invalid-move mask and the stones of groups with >= 2 liberties, rows r05 .. r05 + RPL - 1 of board
     // s5: in registers from here to the write-back
+    // (-DGG_AB_VALID1=1, 19x19: the rows carry the VALID points, full & ~invalid, under the name val_r - gg_v5.h; the load converts once,
+    // the write-back converts back once, and an absent board's rows are zero either way: nothing is ever drawn from them)
+    constexpr bool VAL = GG_AB_VALID1 != 0 && R == 19;
     uint32_t inv_r[RPL], M[RPL];
+#define val_r inv_r   /* (the same registers under the name of what they hold with VAL) */
 #pragma unroll
     for (int r = 0; r < RPL; ++r) inv_r[r] = M[r] = 0u;
     uint32_t wsmiss = 0;   // (workspace launches) bit s: board s was analysed from scratch at load - its workspace entry is rewritten
@@ -117,7 +121,8 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
           const bool ok = have && rw < N;
           const int rc = ok ? rw : 0;
           const uint32_t iv = bq[2 * N + rc], mb = bq[3 * N + rc], mw = bq[4 * N + rc];
-          inv_r[r] = ok ? iv : 0u;
+          if constexpr (VAL) val_r[r] = ok ? (FULLROW & ~iv) : 0u;
+          else inv_r[r] = ok ? iv : 0u;
           M[r] = ok ? (mb | mw) : 0u;
         }
       }
@@ -209,7 +214,7 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
         if (row) {
           st[0 * PL + s * RS + hf.hl] = black;
           st[1 * PL + s * RS + hf.hl] = white;
-          tmp[(hf.h * 2 + 0) * RS + hf.hl] = invalid;
+          tmp[(hf.h * 2 + 0) * RS + hf.hl] = VAL ? (hf.full_l1 & ~invalid) : invalid;   // (VAL: the row lane converts, zero for rows >= N)
           tmp[(hf.h * 2 + 1) * RS + hf.hl] = mb | mw;
         }
         if (hf.hl == 0) {
@@ -274,6 +279,10 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
     const uint32_t fair_lag = plies >= 192 ? 24u : (plies >= 16 ? (uint32_t)plies >> 3 : 2u);
     bool lead = false;   // this wave is >= fair_lag plies ahead of its SIMD-mate
     uint32_t uq = 0;   // this lane's pre-mixed draw: lane j of a pair holds the one of ply (t & ~1) + j, swapped every ply
+    // (-DGG_AB_DRAWADD1=1, 19x19) the draw's counter before the mix, x0 + (t + t5) c at the even ply t: a running value, advanced by 2 c
+    // behind each mix, instead of a 32 x 64 multiply every second ply (gg_v5.h)
+    constexpr bool DADD = GG_AB_DRAWADD1 != 0 && R == 19;
+    uint64_t xdr = x0r + (uint64_t)(uint32_t)(ln0 & 1) * 0x9E3779B97F4A7C15ull;   // (dead code without DADD)
 #if GG_AB_LANE1
     // what depends on the lane number alone, formed ONCE and kept in registers through the plies (gg_v5.h: GG_AB_LANE1) - at 19x19,
     // where two waves per SIMD leave ~70 VGPRs free; 13x13 and 9x9 stand at 168 and 127 of the 170 and 128 VGPRs their three and four
@@ -364,6 +373,30 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
         was_dead = was_dead || (bl && !live);
         drawsr += live ? 1 : 0;
 #endif
+        if constexpr (VAL) {
+          // the reset path in front of the draw: it is wave-uniform and known from the flag word.  A board being reset draws over the
+          // empty board - its valid rows are full[], its M is zero - and its planes are cleared HERE: DS instructions of a wave execute
+          // in order, so the clears stand ahead of the policies' stone reads below and of phase 1's stone store (the policy sets keep
+          // their & ~rm all the same).  The early exit moves with it: nothing below outlives the loop but what a live board writes.
+          uint64_t resetm = CMP1 ? GG_BALLOT5(reset) & 0x5555555555555555ull : GG_BALLOT5(reset && t5 == 0);
+          const bool none_live = GG_BALLOT5(live) == 0;
+          if (none_live && resetm == 0) break;
+          if (resetm) {   // rare
+            if (reset) {
+#pragma unroll
+              for (int r = 0; r < RPL; ++r) { val_r[r] = full[r]; M[r] = 0u; }
+            }
+            while (resetm) {
+              const int s = (__ffsll((unsigned long long)resetm) - 1) >> 1;   // lane 2 s -> board s
+              resetm &= resetm - 1;
+              for (int i = hf.lane; i < 2 * RS; i += kWave) st[(i / RS) * PL + s * RS + (i % RS)] = 0;
+              if constexpr (MPLANE) { if (hf.lane < RS) mplv[s * RS + hf.lane] = 0; }   // (its jobs of THIS ply read M from the plane)
+              if (hf.lane == 0) flagsv[s] = 8u | 32u;   // on, reset (written back even if nothing is played)
+            }
+            if (none_live) break;
+            WAVE_SYNC();
+          }
+        }
         uint32_t v[RPL], p[RPL];
         const uint32_t rm = reset ? ~0u : 0u;   // a board being reset plays on the empty board
         uint32_t eye[RPL];
@@ -435,7 +468,8 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
         }
 #pragma unroll
         for (int r = 0; r < RPL; ++r) {
-          v[r] = B3(full[r], rm, inv_r[r], TA & (TB | (~TC & 0xFF)));
+          if constexpr (VAL) v[r] = val_r[r];   // (a board being reset: full[r], set in front of the draw)
+          else v[r] = B3(full[r], rm, inv_r[r], TA & (TB | (~TC & 0xFF)));
           if constexpr (TAC) {
             // the three sets of the row and their counts in ONE word: F in bits 0-9, C in 10-19, E in 20-29 (<= 361 per board;
             // pattern: nine bits each, and L - at most eight points - from bit 27)
@@ -462,8 +496,9 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
         // launch found; lane j of the pair mixes the draw of ply t + j every second ply, a ply takes the even lane's and
         // the pair swaps
         if ((t & 1) == 0) {
-          uint64_t xx = x0r + (uint64_t)(uint32_t)(t + t5) * 0x9E3779B97F4A7C15ull;
+          uint64_t xx = DADD ? xdr : x0r + (uint64_t)(uint32_t)(t + t5) * 0x9E3779B97F4A7C15ull;
           uq = (uint32_t)(splitmix_next(xx) >> 32);
+          if constexpr (DADD) xdr += 2ull * 0x9E3779B97F4A7C15ull;
         }
         const uint32_t uh = dpp0<QP_L0>(uq);
         uq = dpp0<QP_X1>(uq);
@@ -516,8 +551,10 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
         const bool place = live && hit;
         fl_q = reset ? 40u : fl;   // a board being reset: on, dirty, black to move
         // (CMP1: both lanes of a pair agree on `reset`, the even lanes by a scalar AND)
-        uint64_t resetm = CMP1 ? GG_BALLOT5(reset) & 0x5555555555555555ull : GG_BALLOT5(reset && t5 == 0);
-        const bool none_live = GG_BALLOT5(live) == 0;
+        // (VAL: the reset path stands in front of the draw; here it is dead code by two constants - a block scope around it moves 13x13's
+        // and 9x9's instructions)
+        uint64_t resetm = VAL ? 0ull : (CMP1 ? GG_BALLOT5(reset) & 0x5555555555555555ull : GG_BALLOT5(reset && t5 == 0));
+        const bool none_live = VAL ? false : GG_BALLOT5(live) == 0;
         if (none_live && resetm == 0) break;
         if (resetm) {   // rare
           if (reset) {
@@ -1025,16 +1062,40 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
           x[r] = B3(full[r], y, y, TA & ~TB & 0xFF);
           e[r] = B3(full[r], opp1[r], mine1[r], TA & ~(TB | TC) & 0xFF);
         }
-        dilate_rows<RPL>(x, nbr);
+        // (-DGG_AB_VALID1=1, 19x19: the VALID rows, (h3 | dn) & e in two v_bitop3 a row - e lies inside full[] -, nbr[] holds them;
+        //  -DGG_AB_ALLMOVE1=1, 19x19: every lane's board moves - any full wave of live games - and the new rows are assigned; absent slots
+        //  of a short wave and frozen boards send the wave through the select)
+        constexpr bool AMOVE = GG_AB_ALLMOVE1 != 0 && R == 19;
+        if constexpr (VAL) {
+          const uint32_t up = dpp0<0x138>(x[RPL - 1]), dn = dpp0<0x130>(x[0]);
+#pragma unroll
+          for (int r = 0; r < RPL; ++r) {
+            const uint32_t above = r == 0 ? up : x[r - 1], below = r == RPL - 1 ? dn : x[r + 1];
+            nbr[r] = B3(B3(shl1(x[r]), x[r] >> 1, above, T_OR3), below, e[r], (TA | TB) & TC);
+          }
+        } else {
+          dilate_rows<RPL>(x, nbr);
+        }
         const uint32_t mv_m = moves_now ? ~0u : 0u;
+        if (AMOVE && GG_BALLOT5(!moves_now) == 0) {
+#pragma unroll
+          for (int r = 0; r < RPL; ++r) {
+            if constexpr (VAL) val_r[r] = nbr[r];
+            else inv_r[r] = B3(e[r], nbr[r], full[r], ~(TA & TB) & TC & 0xFF);
+          }
+        } else {
 #pragma unroll
         for (int r = 0; r < RPL; ++r) {
-          const uint32_t invalid = B3(e[r], nbr[r], full[r], ~(TA & TB) & TC & 0xFF);
+          const uint32_t invalid = VAL ? nbr[r] : B3(e[r], nbr[r], full[r], ~(TA & TB) & TC & 0xFF);
           inv_r[r] = B3(mv_m, invalid, inv_r[r], T_SEL);
+        }
         }
         if (GG_BALLOT5(ko_oh != 0u)) {   // (only a board that moved has a ko point)
 #pragma unroll
-          for (int r = 0; r < RPL; ++r) inv_r[r] |= (uint32_t)__builtin_amdgcn_sbfe((int)ko_oh, r, 1) & ko_bit;
+          for (int r = 0; r < RPL; ++r) {
+            if constexpr (VAL) val_r[r] &= ~((uint32_t)__builtin_amdgcn_sbfe((int)ko_oh, r, 1) & ko_bit);
+            else inv_r[r] |= (uint32_t)__builtin_amdgcn_sbfe((int)ko_oh, r, 1) & ko_bit;
+          }
         }
         if (capt_m) {
 #pragma unroll
@@ -1113,7 +1174,8 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
       for (int r = 0; r < RPL; ++r) {
         if (r05s + r < RS) {
           const uint32_t bk = st[0 * PL + s5s * RS + r05s + r], wh = st[1 * PL + s5s * RS + r05s + r];
-          park[0 * PL + s5s * RS + r05s + r] = inv_r[r];
+          // (VAL: the invalid row again, full & ~valid; row N of the odd lane stays zero, an absent board's words never leave LDS)
+          park[0 * PL + s5s * RS + r05s + r] = VAL ? (r05s + r < N ? FULLROW & ~val_r[r] : 0u) : inv_r[r];
           park[1 * PL + s5s * RS + r05s + r] = M[r] & bk;
           park[2 * PL + s5s * RS + r05s + r] = M[r] & wh;
         }
@@ -1162,6 +1224,11 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
       bool any_wr = false;
       if (lnS < nbrd) any_wr = playedv[lnS] != 0 || (flagsv[lnS] & 32u);
       // (the per-game words are read before the emitter takes the loop area over: the meta words live outside it)
+      // (VAL: the emitter takes the invalid rows, full & ~valid, formed once here; it reads rows < N of boards < nbrd only)
+      if constexpr (VAL) {
+#pragma unroll
+        for (int r = 0; r < RPL; ++r) inv_r[r] = FULLROW & ~val_r[r];
+      }
       if (__ballot(any_wr))
         emit_group<R, RPL, 2>(states + b_first * (int64_t)S, nbrd, N, st, PL, RS, inv_r, flagsv, lds + Lds5<R>::kGrpBits,
                               reinterpret_cast<uint2 *>(lds + Lds5<R>::kGrpLut), lnS);
@@ -1218,3 +1285,4 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
   }
 }
 #undef GG_R5_LOG_PARAM
+#undef val_r
