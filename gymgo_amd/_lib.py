@@ -9,7 +9,8 @@ its own, include/gymgo_amd_area.h, and a table of its own, ABI_AREA, bound and c
 (include/gymgo_amd_past.h, ABI_PAST), the Gumbel root rule of the PUCT search (include/gymgo_amd_gumbel.h, ABI_GUMBEL), the
 tactical playout policy with its planes (include/gymgo_amd_tactics.h, ABI_TACTICS), the AMAF statistics of the playouts with
 RAVE in the UCT search (include/gymgo_amd_amaf.h, ABI_AMAF), the pattern playout policy with its planes
-(include/gymgo_amd_pattern.h, ABI_PATTERN) and the move priors of the RAVE search (include/gymgo_amd_prior.h, ABI_PRIOR).
+(include/gymgo_amd_pattern.h, ABI_PATTERN), the move priors of the RAVE search (include/gymgo_amd_prior.h, ABI_PRIOR) and stone
+status with the final score from playout ownership (include/gymgo_amd_status.h, ABI_STATUS).
 """
 import collections
 import ctypes
@@ -246,6 +247,15 @@ ABI_PRIOR = {
     'gg_uct_prior_begin': _params(_I32, 'roots', 'last_actions') + _RNI + _params(_I32, 'weights', 'node_amaf') + _STREAM,
     'gg_uct_prior_expand': _RNI + _params(_I32, 'weights', 'leaf', 'move', 'leaf_id', 'node_amaf') + _STREAM,
 }
+# ... and of include/gymgo_amd_status.h, stone status and the final score from playout ownership, in its order
+# (tests/test_status_host.py holds it against its header)
+_STATUS = (_params(_FLAGS, 'side') + _params(_I32, 'own') + _params(_i32, 'playouts', 'num', 'den') + _OUT + _params(_I32, 'counts')
+           + _OUT_BN)
+ABI_STATUS = {
+    'gg_status_planes': (),
+    'gg_batch_status': _params(_U8, 'states') + _params(_I32, 'orient') + _STATUS,
+    'gg_batch_status_tracked': _params(_I32, 'tracked', 'orient') + _STATUS,
+}
 EXPORTS = tuple(ABI)
 EXPORTS_AREA = tuple(ABI_AREA)
 EXPORTS_PAST = tuple(ABI_PAST)
@@ -254,6 +264,7 @@ EXPORTS_TACTICS = tuple(ABI_TACTICS)
 EXPORTS_AMAF = tuple(ABI_AMAF)
 EXPORTS_PATTERN = tuple(ABI_PATTERN)
 EXPORTS_PRIOR = tuple(ABI_PRIOR)
+EXPORTS_STATUS = tuple(ABI_STATUS)
 _signatures = lambda table: {f: ([p.kind if isinstance(p.kind, type) else _vp for p in ps], _i32) for f, ps in table.items()}
 _SIGNATURES = _signatures(ABI)   # argtypes, restype
 _SIGNATURES_AREA = _signatures(ABI_AREA)
@@ -263,10 +274,12 @@ _SIGNATURES_TACTICS = _signatures(ABI_TACTICS)
 _SIGNATURES_AMAF = _signatures(ABI_AMAF)
 _SIGNATURES_PATTERN = _signatures(ABI_PATTERN)
 _SIGNATURES_PRIOR = _signatures(ABI_PRIOR)
+_SIGNATURES_STATUS = _signatures(ABI_STATUS)
 # call(): the number of parameters and (index, dtypes, name) of every pointer to device memory
 _POINTERS = {f: (len(ps), tuple((i, p.kind if isinstance(p.kind, tuple) else (p.kind,), p.name)
                                 for i, p in enumerate(ps) if not isinstance(p.kind, type)))
-             for table in (ABI, ABI_AREA, ABI_PAST, ABI_GUMBEL, ABI_TACTICS, ABI_AMAF, ABI_PATTERN, ABI_PRIOR) for f, ps in table.items()}
+             for table in (ABI, ABI_AREA, ABI_PAST, ABI_GUMBEL, ABI_TACTICS, ABI_AMAF, ABI_PATTERN, ABI_PRIOR, ABI_STATUS)
+             for f, ps in table.items()}
 
 _lib = None
 
@@ -281,7 +294,8 @@ def build(force=False):
     csrc = os.path.join(_HERE, 'csrc')
     srcs = [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(('.hip', '.h'))]
     srcs += [os.path.join(os.path.dirname(_HERE), 'include', h) for h in ('gymgo_amd.h', 'gymgo_amd_area.h', 'gymgo_amd_past.h', 'gymgo_amd_gumbel.h',
-                                                                                  'gymgo_amd_tactics.h', 'gymgo_amd_amaf.h', 'gymgo_amd_pattern.h', 'gymgo_amd_prior.h')]
+                                                                                  'gymgo_amd_tactics.h', 'gymgo_amd_amaf.h', 'gymgo_amd_pattern.h', 'gymgo_amd_prior.h',
+                                                                                  'gymgo_amd_status.h')]
     stale = not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < max(os.path.getmtime(f) for f in srcs)
     if force or stale:
         subprocess.check_call(['make', '-C', os.path.join(_HERE, 'csrc'), '-s', '-B', '-j3'])
@@ -299,7 +313,7 @@ def lib():
         for name, (argtypes, restype) in (list(_SIGNATURES.items()) + list(_SIGNATURES_AREA.items()) + list(_SIGNATURES_PAST.items())
                                           + list(_SIGNATURES_GUMBEL.items()) + list(_SIGNATURES_TACTICS.items())
                                           + list(_SIGNATURES_AMAF.items()) + list(_SIGNATURES_PATTERN.items())
-                                          + list(_SIGNATURES_PRIOR.items())):
+                                          + list(_SIGNATURES_PRIOR.items()) + list(_SIGNATURES_STATUS.items())):
             fn = getattr(L, name)  # AttributeError if the .so does not export what the header declares
             fn.argtypes, fn.restype = argtypes, restype
         if L.gg_version() != ABI_VERSION:
@@ -449,7 +463,7 @@ def ptrs(fn, **tensors):
     given: for the paths that check their buffers once and hand call() the pointers from then on."""
     kinds = {p.name: p.kind for p in (ABI[fn] if fn in ABI else ABI_AREA[fn] if fn in ABI_AREA else ABI_PAST[fn] if fn in ABI_PAST
                                       else ABI_GUMBEL[fn] if fn in ABI_GUMBEL else ABI_TACTICS[fn] if fn in ABI_TACTICS else ABI_AMAF[fn] if fn in ABI_AMAF
-                                      else ABI_PATTERN[fn] if fn in ABI_PATTERN else ABI_PRIOR[fn])}
+                                      else ABI_PATTERN[fn] if fn in ABI_PATTERN else ABI_PRIOR[fn] if fn in ABI_PRIOR else ABI_STATUS[fn])}
     return tuple(dev_ptr(t, kinds[n], n) for n, t in tensors.items())
 
 

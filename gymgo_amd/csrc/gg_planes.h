@@ -1,7 +1,7 @@
 // gg_planes.h - what the PLANE KERNELS share (gg_feat.h: network features and group liberties, gg_life.h: pass-alive life,
 // gg_ladder.h: ladders, gg_moves.h: move outcomes, gg_hash.h: position and move hashes, gg_area.h: area ownership, gg_past.h: history planes,
 // gg_tactics.h: the sets of the tactical playout policy, gg_pattern.h: those of the pattern playout policy, gg_prior.h: the move priors
-// of the RAVE search).  Only those ten units compile from this header.
+// of the RAVE search, gg_status.h: stone status from playout ownership).  Only those eleven units compile from this header.
 //
 // Layout: ONE ROW PER LANE as in gg_lat.h - a board is the 16 lanes of a DPP row (R <= 13, four boards per wave) or 32 lanes
 // (R = 19, two boards per wave), the rows are bit masks in registers, one single-wave workgroup per wave of boards

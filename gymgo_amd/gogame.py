@@ -863,17 +863,31 @@ def _side_tensor(side, B, device):
     return (s.to(device=device) != 0).to(_U8).reshape(B).contiguous()
 
 
-def _counts_arg(counts, B):
-    """ValueError unless counts is a flag or a contiguous int32 [B, 2] device tensor to write into - before a device is touched."""
-    if isinstance(counts, torch.Tensor) and (not counts.is_cuda or counts.dtype != _I32 or tuple(counts.shape) != (B, 2)
+def _counts_arg(counts, B, width=2):
+    """ValueError unless counts is a flag or a contiguous int32 [B, width] device tensor to write into - before a device is touched."""
+    if isinstance(counts, torch.Tensor) and (not counts.is_cuda or counts.dtype != _I32 or tuple(counts.shape) != (B, width)
                                              or not counts.is_contiguous()):
-        raise ValueError('counts must be a flag or a contiguous int32 [%d, 2] device tensor (got %s %s on %s)' % (
-            B, counts.dtype, list(counts.shape), counts.device))
+        raise ValueError('counts must be a flag or a contiguous int32 [%d, %d] device tensor (got %s %s on %s)' % (
+            B, width, counts.dtype, list(counts.shape), counts.device))
 
 
 _NO_BYTES = ()   # _plane_launch's extra of an entry point that takes orient itself and writes no per-board bytes
 _AreaExtra = collections.namedtuple('_AreaExtra', 'side counts')   # _plane_launch's extra of gg_batch_area[_tracked]: its two optional pointers
 _LastExtra = collections.namedtuple('_LastExtra', 'last')   # ... of gg_batch_patterns[_tracked]: the previous actions (int32 [B]) or None, in front of orient
+# ... of gg_batch_status[_tracked]: gg_batch_area's two optional pointers, the ownership counts (int32 [B, 2, N, N]) and the three scalars of the vote
+_StatusExtra = collections.namedtuple('_StatusExtra', 'side counts own playouts num den')
+
+
+def _status_own_arg(own, boards, B, N):
+    """ValueError unless own is the int32 [B, 2, N, N] ownership counts of the boards - a tensor on the boards' device when those
+    are a device tensor, else a tensor or an array - before a device is touched."""
+    tensor = isinstance(own, torch.Tensor)
+    if not tensor and not isinstance(own, np.ndarray):
+        raise ValueError('ownership must be an int32 [B, 2, N, N] tensor or array, or a Playouts that has one (got %s)' % (type(own),))
+    if tuple(own.shape) != (B, 2, N, N) or own.dtype != (_I32 if tensor else np.int32):
+        raise ValueError('ownership must be int32 %s (got %s %s)' % ([B, 2, N, N], own.dtype, list(own.shape)))
+    if tensor and isinstance(boards, torch.Tensor) and own.device != boards.device:
+        raise ValueError('ownership must live on the boards\' device (got %s, the boards are on %s)' % (own.device, boards.device))
 
 
 def _plane_launch(name, boards, orient, out, extra, code, B, N, stream, launch=_lib.call):
@@ -882,9 +896,12 @@ def _plane_launch(name, boards, orient, out, extra, code, B, N, stream, launch=_
     gg_batch_ladder[_tracked], which take orient (or None) and the per-board bytes (or None) themselves, or
     gg_batch_move_planes[_tracked], which take orient (or None) and have no per-board bytes (extra is _NO_BYTES), or
     gg_batch_area[_tracked], which take orient, side (uint8 [B]) in front of out and counts (int32 [B, 2]) behind it, each
-    or None (extra is an _AreaExtra)."""
+    or None (extra is an _AreaExtra), or gg_batch_status[_tracked], which take the ownership counts and the three scalars of
+    the vote between side and out as well (extra is a _StatusExtra)."""
     if type(extra) is _AreaExtra:
         args = (boards, orient, extra.side, out, extra.counts)
+    elif type(extra) is _StatusExtra:
+        args = (boards, orient, extra.side, extra.own, extra.playouts, extra.num, extra.den, out, extra.counts)
     elif type(extra) is _LastExtra:
         args = (boards, extra.last, orient, out)
     elif extra is _NO_BYTES:
@@ -899,14 +916,17 @@ def _plane_launch(name, boards, orient, out, extra, code, B, N, stream, launch=_
 
 
 def _planes(name, count, align, boards, tracked, dtype, out, orient, extra=None):
-    """The body of the ten batch plane calls: `count` planes per board from byte planes (a tensor or an array) or, `tracked`,
+    """The body of the batch plane calls: `count` planes per board from byte planes (a tensor or an array) or, `tracked`,
     from tracked boards (a device tensor), through the C entry point `name` (_plane_launch), into `out` (aligned to
     `align` bytes) or a new tensor.  extra: None (the entry point has no per-board bytes and an _oriented form), _NO_BYTES
     (none either, orient is a parameter), or whether they are wanted -> planes, or (planes, bytes uint8 [B]); or an
     _AreaExtra (side: None or B flags, a tensor or an array; counts: whether they are wanted) -> planes, or (planes, counts
-    int32 [B, 2]).  Every ValueError comes before a device is touched."""
+    int32 [B, 2]); or a _StatusExtra (those two, the ownership counts - a tensor or an array, checked here - and the scalars of
+    the vote, checked by the caller) -> planes, or (planes, counts int32 [B, 4]).  Every ValueError comes before a device is
+    touched."""
     code = _feature_dtype(dtype)
-    area = extra if type(extra) is _AreaExtra else None
+    area = extra if type(extra) in (_AreaExtra, _StatusExtra) else None
+    status = area if type(area) is _StatusExtra else None
     if area is not None:
         extra = isinstance(area.counts, torch.Tensor) or bool(area.counts)
     lastx = extra if type(extra) is _LastExtra else None   # (the pattern planes: previous actions in, nothing but planes out)
@@ -927,7 +947,9 @@ def _planes(name, count, align, boards, tracked, dtype, out, orient, extra=None)
     if area is not None:
         if area.side is not None:
             _side_arg(area.side, B)
-        _counts_arg(area.counts, B)
+        _counts_arg(area.counts, B, 2 if status is None else 4)
+    if status is not None:
+        _status_own_arg(status.own, boards, B, N)
     if tracked:
         box, st = None, boards
         _planes_out(out, (B, count, N, N), dtype, align, st.device if st.is_cuda else None)
@@ -944,10 +966,13 @@ def _planes(name, count, align, boards, tracked, dtype, out, orient, extra=None)
         bytes_ = area.counts
     else:
         bytes_ = (torch.empty(B, dtype=_U8, device=st.device) if area is None else
-                  torch.empty((B, 2), dtype=_I32, device=st.device)) if extra else None
+                  torch.empty((B, 2 if status is None else 4), dtype=_I32, device=st.device)) if extra else None
     o = None if orient is None else _actions_tensor(orient, B, st.device)
     if area is not None:
         how = _AreaExtra(None if area.side is None else _side_tensor(area.side, B, st.device), bytes_)
+        if status is not None:
+            own = status.own if isinstance(status.own, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(status.own))
+            how = status._replace(side=how.side, counts=bytes_, own=own.to(st.device).contiguous())
     elif lastx is not None:
         how = _LastExtra(None if lastx.last is None else _actions_tensor(lastx.last, B, st.device))
     else:
@@ -1359,6 +1384,79 @@ def ownership(state, side=None):
     box = _Box(state)
     owner, margin = batch_ownership(box.t[None], None if side is None else [side])
     return _back(box, owner, row0=True), _back(box, margin, row0=True)
+
+
+# ---------------------------------------------------------------- stone status and the final score from playout ownership
+STATUS_PLANES = 9   # gg_status_planes() of include/gymgo_amd_status.h
+STATUS_NAMES = ('own_alive', 'own_dead', 'own_unsettled', 'opp_alive', 'opp_dead', 'opp_unsettled', 'own_area', 'opp_area', 'neutral')
+STATUS_MAX_PLAYOUTS, STATUS_MAX_DEN = 1 << 20, 1024   # GG_STATUS_MAX_PLAYOUTS, GG_STATUS_MAX_DEN
+
+
+def _status_extra(ownership, playouts, threshold, side, counts):
+    """The _StatusExtra of a status call: ValueError for a Playouts without ownership, for playouts outside
+    [1, STATUS_MAX_PLAYOUTS] and for a threshold that is not two integers 1 <= num <= den <= STATUS_MAX_DEN with 2 num > den -
+    before a device is touched."""
+    if isinstance(ownership, tuple) and hasattr(ownership, 'ownership'):
+        ownership = ownership.ownership
+        if ownership is None:
+            raise ValueError('these Playouts carry no ownership: run batch_playouts(..., ownership=True)')
+    integral = lambda x: isinstance(x, (int, np.integer)) and not isinstance(x, (bool, np.bool_))
+    if not integral(playouts) or not 1 <= playouts <= STATUS_MAX_PLAYOUTS:
+        raise ValueError('playouts must be an integer in [1, %d] (got %r)' % (STATUS_MAX_PLAYOUTS, playouts))
+    try:
+        num, den = threshold
+    except (TypeError, ValueError):
+        raise ValueError('threshold must be (num, den) (got %r)' % (threshold,)) from None
+    if not integral(num) or not integral(den) or not (1 <= num <= den <= STATUS_MAX_DEN and 2 * num > den):
+        raise ValueError('threshold (num, den) must be integers with 1 <= num <= den <= %d and 2 num > den (got %r)'
+                         % (STATUS_MAX_DEN, threshold))
+    return _StatusExtra(side, counts, ownership, int(playouts), int(num), int(den))
+
+
+def batch_stone_status(batch_states, ownership, playouts, threshold=(2, 3), dtype=torch.uint8, out=None, orient=None, side=None,
+                       counts=False):
+    """Which chains the playouts of a position call alive, dead or unsettled, and the areas once the dead are gone ->
+    [B, 9, N, N] of `dtype` (gg_batch_status), each value exactly 0 or 1 (STATUS_NAMES):
+       0 / 1 / 2  own stones whose chain is alive / dead / unsettled
+       3 / 4 / 5  the opponent's stones whose chain is alive / dead / unsettled
+       6 / 7 / 8  own area / opponent's area / neutral points of the board with the dead chains of both colours taken off
+                  (batch_area_planes' rule on what remains; unsettled chains stay, so the liberties a seki shares are neutral)
+    ownership: int32 [B, 2, N, N], in how many of `playouts` playouts each point ended in black's / white's area, in the
+    stored frame of the board - the `ownership` of batch_playouts(..., ownership=True), or those Playouts themselves
+    (ValueError if they carry none).  threshold (num, den), integers with 1 <= num <= den <= 1024 and 2 num > den;
+    1 <= playouts <= 2^20.  With K = playouts, a chain C (4-connected stones of one colour) of |C| stones, D = the sum over
+    its stones of the other colour's count and A = that of its own colour's: C is dead iff D den >= num K |C|, else alive iff
+    A den >= num K |C|, else unsettled - in 64-bit integers, so the result is bit-defined.  The counts are expected to obey
+    0 <= count <= K and black + white <= K per point; other values give an unspecified status for their chain and nothing
+    worse.  Counts on empty points are not read.
+    Own = the player to move, or with side (B flags, a tensor or an array: 0 = black's view, non-zero = white's) the side
+    named, whatever the turn plane says.  counts=True: also int32 [B, 4] = own area, opponent's area, own dead stones,
+    opponent's dead stones (counts may also be a contiguous int32 [B, 4] device tensor to write into).  dtype, out (aligned to
+    its element), orient (the planes turn, ownership is always in the stored frame, the counts do not turn) and NumPy input:
+    as batch_area_planes.  Every bad argument is a ValueError before a device is touched.  One launch."""
+    return _planes('gg_batch_status', STATUS_PLANES, 1, batch_states, False, dtype, out, orient,
+                   _status_extra(ownership, playouts, threshold, side, counts))
+
+
+def stone_status(state, ownership, playouts, threshold=(2, 3), dtype=torch.uint8, side=None, counts=False):
+    """batch_stone_status of one state [6, N, N] and its ownership [2, N, N] (or the Playouts of that state) -> [9, N, N] (with
+    counts=True: and int32 [4]); side: None or one flag."""
+    own = _status_extra(ownership, playouts, threshold, None, False).own          # (every ValueError before a device is touched)
+    shape = tuple(state.shape) if isinstance(state, torch.Tensor) else np.shape(state)
+    if len(shape) != 3 or not isinstance(own, (torch.Tensor, np.ndarray)) or own.ndim != 3:
+        raise ValueError('stone_status takes one state [6, N, N] and its ownership, int32 [2, N, N], or the Playouts that hold it')
+    _status_own_arg(own[None], state if isinstance(state, torch.Tensor) else None, 1, shape[-1])
+    batch_fn = lambda st, dt, **kw: batch_stone_status(st, own[None], playouts, threshold, dt, **kw)
+    return _plane_single(batch_fn, state, dtype, side=None if side is None else [side], counts=bool(counts))
+
+
+def batch_stone_status_tracked(tracked, ownership, playouts, threshold=(2, 3), dtype=torch.uint8, out=None, orient=None, side=None,
+                               counts=False):
+    """batch_stone_status of tracked boards (int32 [B, 5N+1], a device tensor) -> [B, 9, N, N] of `dtype`
+    (gg_batch_status_tracked): bit for bit what batch_stone_status gives for batch_untrack(tracked); only the two stone row
+    sets and the turn bit are read."""
+    return _planes('gg_batch_status_tracked', STATUS_PLANES, 1, tracked, True, dtype, out, orient,
+                   _status_extra(ownership, playouts, threshold, side, counts))
 
 
 # ---------------------------------------------------------------- position hashes and positional superko
@@ -2027,6 +2125,41 @@ def batch_playouts(batch_states, playouts, max_plies=None, komi=0.0, seed=202609
 def playouts(state, n, **kw):
     """batch_playouts of one state [6, N, N] -> Playouts of scalars (and ownership [2, N, N])."""
     return _single(batch_playouts, state, n, **kw)
+
+
+# ---------------------------------------------------------------- the final score: playouts, stone status, areas
+FinalScore = collections.namedtuple('FinalScore', 'black_area white_area margin winner owner dead unsettled playouts')
+FinalScore.__doc__ = """Per-board results of batch_final_score: black_area / white_area (int32: the areas with the dead stones
+taken off), margin (int32: black - white, no komi), winner (float64: sign(margin - komi), as batch_winning), owner (int8
+[R, N, N]: +1 black's point, -1 white's, 0 neutral), dead / unsettled (uint8 [R, N, N]: the stones of either colour whose chain is
+dead / unsettled) and playouts (the Playouts that voted, ownership included)."""
+
+
+def batch_final_score(batch_states, playouts=64, komi=0.0, threshold=(2, 3), policy='no_eye_fill', **playout_kw):
+    """Who won: `playouts` playouts of every board (batch_playouts with ownership=True, policy and playout_kw - max_plies,
+    seed, first_root, slots, chunk_plies - passed on), then one batch_stone_status launch from black's view with that
+    ownership and `threshold` -> FinalScore.  The dead chains are taken off before the areas are counted, so a stone left
+    inside the other side's territory no longer turns that territory neutral, as it does for batch_areas / batch_winning.
+    NumPy in gives NumPy out; every ValueError of the two calls comes before a device is touched."""
+    B, N = _states_shape(batch_states)
+    if 'ownership' in playout_kw or 'amaf' in playout_kw:
+        raise ValueError('batch_final_score runs its playouts with ownership=True and without amaf')
+    _status_extra(None, playouts, threshold, None, True)
+    _policy_kw({'policy': policy})
+    box = _Box(batch_states)
+    st = box.t
+    po = batch_playouts(st, playouts, komi=komi, ownership=True, policy=policy, **playout_kw)
+    planes, counts = batch_stone_status(st, po.ownership, playouts, threshold, side=torch.zeros(B, dtype=_U8, device=st.device),
+                                        counts=True)
+    margin = counts[:, 0] - counts[:, 1]
+    return _back(box, FinalScore(counts[:, 0], counts[:, 1], margin, torch.sign(margin.to(torch.float64) - komi),
+                                 planes[:, 6].to(torch.int8) - planes[:, 7].to(torch.int8), planes[:, 1] | planes[:, 4],
+                                 planes[:, 2] | planes[:, 5], po))
+
+
+def final_score(state, playouts=64, **kw):
+    """batch_final_score of one state [6, N, N] -> FinalScore of scalars and [N, N] planes (its Playouts: those of `playouts`)."""
+    return _single(batch_final_score, state, playouts, **kw)
 
 
 # ---------------------------------------------------------------- flat Monte Carlo: playouts per legal first move
