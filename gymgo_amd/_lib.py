@@ -10,7 +10,8 @@ its own, include/gymgo_amd_area.h, and a table of its own, ABI_AREA, bound and c
 tactical playout policy with its planes (include/gymgo_amd_tactics.h, ABI_TACTICS), the AMAF statistics of the playouts with
 RAVE in the UCT search (include/gymgo_amd_amaf.h, ABI_AMAF), the pattern playout policy with its planes
 (include/gymgo_amd_pattern.h, ABI_PATTERN), the move priors of the RAVE search (include/gymgo_amd_prior.h, ABI_PRIOR) and stone
-status with the final score from playout ownership (include/gymgo_amd_status.h, ABI_STATUS).
+status with the final score from playout ownership (include/gymgo_amd_status.h, ABI_STATUS).  ABI_ALL is the nine merged: the
+one lookup lib(), call(), ptrs() and PARAMS (the parameter names of every entry point, in order) are made from.
 """
 import collections
 import ctypes
@@ -275,11 +276,14 @@ _SIGNATURES_AMAF = _signatures(ABI_AMAF)
 _SIGNATURES_PATTERN = _signatures(ABI_PATTERN)
 _SIGNATURES_PRIOR = _signatures(ABI_PRIOR)
 _SIGNATURES_STATUS = _signatures(ABI_STATUS)
+# every entry point of the nine headers in ONE lookup: what lib() binds and what call(), ptrs() and the plane launches of gogame
+# (PARAMS: the parameter names in order) look an entry point up in, whichever header declares it
+ABI_ALL = {**ABI, **ABI_AREA, **ABI_PAST, **ABI_GUMBEL, **ABI_TACTICS, **ABI_AMAF, **ABI_PATTERN, **ABI_PRIOR, **ABI_STATUS}
+PARAMS = {f: {p.name: i for i, p in enumerate(ps)} for f, ps in ABI_ALL.items()}   # the parameter names in order -> position
 # call(): the number of parameters and (index, dtypes, name) of every pointer to device memory
 _POINTERS = {f: (len(ps), tuple((i, p.kind if isinstance(p.kind, tuple) else (p.kind,), p.name)
                                 for i, p in enumerate(ps) if not isinstance(p.kind, type)))
-             for table in (ABI, ABI_AREA, ABI_PAST, ABI_GUMBEL, ABI_TACTICS, ABI_AMAF, ABI_PATTERN, ABI_PRIOR, ABI_STATUS)
-             for f, ps in table.items()}
+             for f, ps in ABI_ALL.items()}
 
 _lib = None
 
@@ -290,12 +294,11 @@ class GymGoNativeError(RuntimeError):
 
 def build(force=False):
     """Compile the HIP library in-tree for gfx950 (hipcc cross-compiles without a GPU)."""
+    import glob
     import subprocess
     csrc = os.path.join(_HERE, 'csrc')
     srcs = [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(('.hip', '.h'))]
-    srcs += [os.path.join(os.path.dirname(_HERE), 'include', h) for h in ('gymgo_amd.h', 'gymgo_amd_area.h', 'gymgo_amd_past.h', 'gymgo_amd_gumbel.h',
-                                                                                  'gymgo_amd_tactics.h', 'gymgo_amd_amaf.h', 'gymgo_amd_pattern.h', 'gymgo_amd_prior.h',
-                                                                                  'gymgo_amd_status.h')]
+    srcs += glob.glob(os.path.join(os.path.dirname(_HERE), 'include', 'gymgo_amd*.h'))
     stale = not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < max(os.path.getmtime(f) for f in srcs)
     if force or stale:
         subprocess.check_call(['make', '-C', os.path.join(_HERE, 'csrc'), '-s', '-B', '-j3'])
@@ -310,10 +313,7 @@ def lib():
                 'HIP library %s not built (run `make -C gymgo_amd/csrc` or __graft_entry__.build()); '
                 'gymgo_amd has no CPU fallback' % LIB_PATH)
         L = ctypes.CDLL(LIB_PATH)
-        for name, (argtypes, restype) in (list(_SIGNATURES.items()) + list(_SIGNATURES_AREA.items()) + list(_SIGNATURES_PAST.items())
-                                          + list(_SIGNATURES_GUMBEL.items()) + list(_SIGNATURES_TACTICS.items())
-                                          + list(_SIGNATURES_AMAF.items()) + list(_SIGNATURES_PATTERN.items())
-                                          + list(_SIGNATURES_PRIOR.items()) + list(_SIGNATURES_STATUS.items())):
+        for name, (argtypes, restype) in _signatures(ABI_ALL).items():
             fn = getattr(L, name)  # AttributeError if the .so does not export what the header declares
             fn.argtypes, fn.restype = argtypes, restype
         if L.gg_version() != ABI_VERSION:
@@ -461,9 +461,7 @@ def dev_ptr(t, dtype, name):
 def ptrs(fn, **tensors):
     """dev_ptr of every tensor as the parameter of entry point `fn` it is named after - dtype(s) from the table -, in the order
     given: for the paths that check their buffers once and hand call() the pointers from then on."""
-    kinds = {p.name: p.kind for p in (ABI[fn] if fn in ABI else ABI_AREA[fn] if fn in ABI_AREA else ABI_PAST[fn] if fn in ABI_PAST
-                                      else ABI_GUMBEL[fn] if fn in ABI_GUMBEL else ABI_TACTICS[fn] if fn in ABI_TACTICS else ABI_AMAF[fn] if fn in ABI_AMAF
-                                      else ABI_PATTERN[fn] if fn in ABI_PATTERN else ABI_PRIOR[fn] if fn in ABI_PRIOR else ABI_STATUS[fn])}
+    kinds = {p.name: p.kind for p in ABI_ALL[fn]}
     return tuple(dev_ptr(t, kinds[n], n) for n, t in tensors.items())
 
 

@@ -871,13 +871,6 @@ def _counts_arg(counts, B, width=2):
             B, width, counts.dtype, list(counts.shape), counts.device))
 
 
-_NO_BYTES = ()   # _plane_launch's extra of an entry point that takes orient itself and writes no per-board bytes
-_AreaExtra = collections.namedtuple('_AreaExtra', 'side counts')   # _plane_launch's extra of gg_batch_area[_tracked]: its two optional pointers
-_LastExtra = collections.namedtuple('_LastExtra', 'last')   # ... of gg_batch_patterns[_tracked]: the previous actions (int32 [B]) or None, in front of orient
-# ... of gg_batch_status[_tracked]: gg_batch_area's two optional pointers, the ownership counts (int32 [B, 2, N, N]) and the three scalars of the vote
-_StatusExtra = collections.namedtuple('_StatusExtra', 'side counts own playouts num den')
-
-
 def _status_own_arg(own, boards, B, N):
     """ValueError unless own is the int32 [B, 2, N, N] ownership counts of the boards - a tensor on the boards' device when those
     are a device tensor, else a tensor or an array - before a device is touched."""
@@ -890,66 +883,61 @@ def _status_own_arg(own, boards, B, N):
         raise ValueError('ownership must live on the boards\' device (got %s, the boards are on %s)' % (own.device, boards.device))
 
 
-def _plane_launch(name, boards, orient, out, extra, code, B, N, stream, launch=_lib.call):
-    """One launch of a plane entry point on tensors (_lib.call) or, launch=_lib.launch, on prepared pointers alone.  name: gg_batch_features[_tracked] - its
-    _oriented form when orient is given, and no per-board bytes (extra is False) - or gg_batch_life[_tracked] /
-    gg_batch_ladder[_tracked], which take orient (or None) and the per-board bytes (or None) themselves, or
-    gg_batch_move_planes[_tracked], which take orient (or None) and have no per-board bytes (extra is _NO_BYTES), or
-    gg_batch_area[_tracked], which take orient, side (uint8 [B]) in front of out and counts (int32 [B, 2]) behind it, each
-    or None (extra is an _AreaExtra), or gg_batch_status[_tracked], which take the ownership counts and the three scalars of
-    the vote between side and out as well (extra is a _StatusExtra)."""
-    if type(extra) is _AreaExtra:
-        args = (boards, orient, extra.side, out, extra.counts)
-    elif type(extra) is _StatusExtra:
-        args = (boards, orient, extra.side, extra.own, extra.playouts, extra.num, extra.den, out, extra.counts)
-    elif type(extra) is _LastExtra:
-        args = (boards, extra.last, orient, out)
-    elif extra is _NO_BYTES:
-        args = (boards, orient, out)
-    elif extra is not False:
-        args = (boards, orient, out, extra)
-    elif orient is None:
-        args = (boards, out)
-    else:
-        name, args = name + '_oriented', (boards, orient, out)
-    launch(name, *args, code, B, N, stream)
+def _plane_args(name, boards, orient, values):
+    """(entry point, *its arguments) of a plane launch, bound BY NAME from the entry point's row of the binding table (_lib.PARAMS),
+    the one place that knows the order: boards is the first parameter, every other one takes the value `values` (a dict) holds
+    under its name - out, out_dtype, B, N, hip_stream and what the family adds (settled / aborted, side and counts, last, own with
+    playouts, num and den, the ring's rows, count, H, T and moves) - and a pointer that is not given goes down as NULL.  An entry
+    point whose row has no orient, called with one, is its _oriented form (the feature planes).  A name the row does not have is
+    a TypeError."""
+    names = _lib.PARAMS[name]
+    if orient is not None and 'orient' not in names:
+        name += '_oriented'
+        names = _lib.PARAMS[name]
+    if 'orient' in names:
+        values['orient'] = orient
+    if not values.keys() <= names.keys():
+        raise TypeError('%s has no parameter %s' % (name, ', '.join(values.keys() - names.keys())))
+    args = list(map(values.get, names))
+    args[0] = boards
+    return (name, *args)
 
 
-def _planes(name, count, align, boards, tracked, dtype, out, orient, extra=None):
+def _plane_launch(name, boards, orient, values):
+    """One launch of a plane entry point on tensors, its arguments by name (_plane_args)."""
+    _lib.call(*_plane_args(name, boards, orient, values))
+
+
+def _planes(name, count, align, boards, tracked, dtype, out, orient, per_board=None, **inputs):
     """The body of the batch plane calls: `count` planes per board from byte planes (a tensor or an array) or, `tracked`,
     from tracked boards (a device tensor), through the C entry point `name` (_plane_launch), into `out` (aligned to
-    `align` bytes) or a new tensor.  extra: None (the entry point has no per-board bytes and an _oriented form), _NO_BYTES
-    (none either, orient is a parameter), or whether they are wanted -> planes, or (planes, bytes uint8 [B]); or an
-    _AreaExtra (side: None or B flags, a tensor or an array; counts: whether they are wanted) -> planes, or (planes, counts
-    int32 [B, 2]); or a _StatusExtra (those two, the ownership counts - a tensor or an array, checked here - and the scalars of
-    the vote, checked by the caller) -> planes, or (planes, counts int32 [B, 4]).  Every ValueError comes before a device is
-    touched."""
+    `align` bytes) or a new tensor.  inputs: what the family takes beside the boards, under the names of the entry point's
+    parameters, each with its checker - last (None or B actions: _last_arg), side (None or B flags: _side_arg, _side_tensor), own
+    (the ownership counts, a tensor or an array: _status_own_arg) with the scalars playouts, num and den, checked by the caller -
+    and history (a StoneHistory: _past_arg; its planes are `count`, its ring five more arguments).  per_board: the one optional
+    per-board output as (parameter name, wanted, shape behind B, dtype) - settled / aborted uint8 [B], counts int32 [B, 2] or
+    [B, 4]; wanted: a flag or, for counts, the caller's buffer (_counts_arg) -> planes, or (planes, that output).  Every ValueError
+    comes before a device is touched."""
     code = _feature_dtype(dtype)
-    area = extra if type(extra) in (_AreaExtra, _StatusExtra) else None
-    status = area if type(area) is _StatusExtra else None
-    if area is not None:
-        extra = isinstance(area.counts, torch.Tensor) or bool(area.counts)
-    lastx = extra if type(extra) is _LastExtra else None   # (the pattern planes: previous actions in, nothing but planes out)
-    if lastx is not None:
-        extra = _NO_BYTES
-    if tracked:
-        if not isinstance(boards, torch.Tensor) or boards.dim() != 2:
-            raise ValueError('tracked boards are int32 [B, 5N+1] device tensors')
-        N = _tracked_size(boards)
-        B = boards.shape[0]
-    else:
-        B, N = _states_shape(boards)
+    B, N = _hash_shape(boards, tracked)
+    past = 'history' in inputs
+    if past:
+        history = inputs.pop('history')
+        count = _past_arg(history, B, N).planes
+    if not tracked:
         _planes_out(out, (B, count, N, N), dtype, align)
     if orient is not None:
         _orient_arg(orient, B)
-    if lastx is not None and lastx.last is not None:
-        _last_arg(lastx.last, B)
-    if area is not None:
-        if area.side is not None:
-            _side_arg(area.side, B)
-        _counts_arg(area.counts, B, 2 if status is None else 4)
-    if status is not None:
-        _status_own_arg(status.own, boards, B, N)
+    last, side = inputs.get('last'), inputs.get('side')
+    if last is not None:
+        _last_arg(last, B)
+    if side is not None:
+        _side_arg(side, B)
+    pname, wanted, tail, pdtype = per_board or (None, False, (), None)
+    if pname == 'counts':
+        _counts_arg(wanted, B, *tail)
+    if 'own' in inputs:
+        _status_own_arg(inputs['own'], boards, B, N)
     if tracked:
         box, st = None, boards
         _planes_out(out, (B, count, N, N), dtype, align, st.device if st.is_cuda else None)
@@ -959,28 +947,33 @@ def _planes(name, count, align, boards, tracked, dtype, out, orient, extra=None)
         box = _Box(boards)
         st = box.t
         _planes_out(out, (B, count, N, N), dtype, align, st.device)
-    planes = out if out is not None else torch.empty((B, count, N, N), dtype=dtype, device=st.device)
-    if area is not None and isinstance(area.counts, torch.Tensor):   # (checked by _counts_arg: the caller's buffer)
-        if area.counts.device != st.device:
-            raise ValueError('counts must live on the states\' device (got %s)' % (area.counts.device,))
-        bytes_ = area.counts
+    dev = st.device
+    if past:
+        if history.rows.device != dev:
+            raise ValueError('history must live on the boards\' device (%s)' % (dev,))
+        inputs.update(rows=history.rows, count=history.count, H=history.capacity, T=history.positions, moves=int(history.moves))
+    planes = out if out is not None else torch.empty((B, count, N, N), dtype=dtype, device=dev)
+    if isinstance(wanted, torch.Tensor):   # (checked by _counts_arg: the caller's buffer)
+        if wanted.device != dev:
+            raise ValueError('counts must live on the states\' device (got %s)' % (wanted.device,))
+        extra = wanted
     else:
-        bytes_ = (torch.empty(B, dtype=_U8, device=st.device) if area is None else
-                  torch.empty((B, 2 if status is None else 4), dtype=_I32, device=st.device)) if extra else None
-    o = None if orient is None else _actions_tensor(orient, B, st.device)
-    if area is not None:
-        how = _AreaExtra(None if area.side is None else _side_tensor(area.side, B, st.device), bytes_)
-        if status is not None:
-            own = status.own if isinstance(status.own, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(status.own))
-            how = status._replace(side=how.side, counts=bytes_, own=own.to(st.device).contiguous())
-    elif lastx is not None:
-        how = _LastExtra(None if lastx.last is None else _actions_tensor(lastx.last, B, st.device))
-    else:
-        how = False if extra is None else _NO_BYTES if extra is _NO_BYTES else bytes_
-    _plane_launch(name, st, o, planes, how, code, B, N, _lib.stream_ptr(st.device))
+        extra = torch.empty((B,) + tail, dtype=pdtype, device=dev) if wanted else None
+    if pname is not None:
+        inputs[pname] = extra
+    o = None if orient is None else _actions_tensor(orient, B, dev)
+    if side is not None:
+        inputs['side'] = _side_tensor(side, B, dev)
+    if 'own' in inputs:
+        own = inputs['own'] if isinstance(inputs['own'], torch.Tensor) else torch.from_numpy(np.ascontiguousarray(inputs['own']))
+        inputs['own'] = own.to(dev).contiguous()
+    if last is not None:
+        inputs['last'] = _actions_tensor(last, B, dev)
+    inputs.update(out=planes, out_dtype=code, B=B, N=N, hip_stream=_lib.stream_ptr(dev))
+    _plane_launch(name, st, o, inputs)
     if box is not None:
-        planes, bytes_ = _back(box, planes), _back(box, bytes_)
-    return (planes, bytes_) if extra else planes
+        planes, extra = _back(box, planes), _back(box, extra)
+    return planes if extra is None else (planes, extra)
 
 
 def _plane_single(batch_fn, state, dtype, **kw):
@@ -1050,7 +1043,7 @@ def batch_life(batch_states, dtype=torch.uint8, out=None, orient=None, settled=F
     turned position.  settled=True: -> (planes, uint8 [B]): 1 iff every point of the board lies in some plane (nothing is
     left to play for; it does not depend on orient).  NumPy in gives NumPy out (through the device; not for bfloat16).
     One launch either way; device memory of the result: 4 * B * N^2 elements (+ B bytes)."""
-    return _planes('gg_batch_life', LIFE_PLANES, 1, batch_states, False, dtype, out, orient, bool(settled))
+    return _planes('gg_batch_life', LIFE_PLANES, 1, batch_states, False, dtype, out, orient, ('settled', bool(settled), (), _U8))
 
 
 def life(state, dtype=torch.uint8, settled=False):
@@ -1061,7 +1054,7 @@ def life(state, dtype=torch.uint8, settled=False):
 def batch_life_tracked(tracked, dtype=torch.uint8, out=None, orient=None, settled=False):
     """batch_life of tracked boards (int32 [B, 5N+1], a device tensor) -> [B, 4, N, N] of `dtype` (gg_batch_life_tracked):
     bit for bit what batch_life gives for batch_untrack(tracked); only the two stone row sets and the turn flag are read."""
-    return _planes('gg_batch_life_tracked', LIFE_PLANES, 1, tracked, True, dtype, out, orient, bool(settled))
+    return _planes('gg_batch_life_tracked', LIFE_PLANES, 1, tracked, True, dtype, out, orient, ('settled', bool(settled), (), _U8))
 
 
 def batch_settled(batch_states):
@@ -1092,7 +1085,7 @@ def batch_ladder(batch_states, dtype=torch.uint8, out=None, orient=None, aborted
     holds the planes of the turned position (turned first, then searched).  aborted=True: -> (planes, uint8 [B]): the
     aborted root queries of the board, saturated at 255.  NumPy in gives NumPy out (through the device; not for bfloat16).
     One launch either way; device memory of the result: 4 * B * N^2 elements (+ B bytes)."""
-    return _planes('gg_batch_ladder', LADDER_PLANES, 1, batch_states, False, dtype, out, orient, bool(aborted))
+    return _planes('gg_batch_ladder', LADDER_PLANES, 1, batch_states, False, dtype, out, orient, ('aborted', bool(aborted), (), _U8))
 
 
 def ladder(state, dtype=torch.uint8, aborted=False):
@@ -1103,7 +1096,7 @@ def ladder(state, dtype=torch.uint8, aborted=False):
 def batch_ladder_tracked(tracked, dtype=torch.uint8, out=None, orient=None, aborted=False):
     """batch_ladder of tracked boards (int32 [B, 5N+1], a device tensor) -> [B, 4, N, N] of `dtype` (gg_batch_ladder_tracked):
     bit for bit what batch_ladder gives for batch_untrack(tracked); the class rows are not read."""
-    return _planes('gg_batch_ladder_tracked', LADDER_PLANES, 1, tracked, True, dtype, out, orient, bool(aborted))
+    return _planes('gg_batch_ladder_tracked', LADDER_PLANES, 1, tracked, True, dtype, out, orient, ('aborted', bool(aborted), (), _U8))
 
 
 # ---------------------------------------------------------------- move-outcome planes
@@ -1128,7 +1121,7 @@ def batch_move_planes(batch_states, dtype=torch.uint8, out=None, orient=None):
     dtype to write into.  orient (None, or int [B], only orient & 7 is read): row b is view orient[b] of its planes - also the
     planes of the turned position.  NumPy in gives NumPy out (through the device; not for bfloat16).  One launch; device
     memory of the result: 12 * B * N^2 elements - against the (N^2 + 1) * 6 * N^2 bytes per board of batch_children."""
-    return _planes('gg_batch_move_planes', MOVE_PLANES, 1, batch_states, False, dtype, out, orient, _NO_BYTES)
+    return _planes('gg_batch_move_planes', MOVE_PLANES, 1, batch_states, False, dtype, out, orient)
 
 
 def move_planes(state, dtype=torch.uint8):
@@ -1140,7 +1133,7 @@ def batch_move_planes_tracked(tracked, dtype=torch.uint8, out=None, orient=None)
     """batch_move_planes of tracked boards (int32 [B, 5N+1], a device tensor) -> [B, 12, N, N] of `dtype`
     (gg_batch_move_planes_tracked): bit for bit what batch_move_planes gives for batch_untrack(tracked); the class rows
     are not read."""
-    return _planes('gg_batch_move_planes_tracked', MOVE_PLANES, 1, tracked, True, dtype, out, orient, _NO_BYTES)
+    return _planes('gg_batch_move_planes_tracked', MOVE_PLANES, 1, tracked, True, dtype, out, orient)
 
 
 def batch_move_counts(batch_states):
@@ -1183,7 +1176,7 @@ def batch_area_planes(batch_states, dtype=torch.uint8, out=None, orient=None, si
     orient & 7 is read): row b is view orient[b] of its planes - also the planes of the turned position; the counts do not
     turn.  NumPy in gives NumPy out (through the device; not for bfloat16).  One launch either way; device memory of the
     result: 3 * B * N^2 elements (+ 8 B bytes)."""
-    return _planes('gg_batch_area', AREA_PLANES, 1, batch_states, False, dtype, out, orient, _AreaExtra(side, counts))
+    return _planes('gg_batch_area', AREA_PLANES, 1, batch_states, False, dtype, out, orient, ('counts', counts, (2,), _I32), side=side)
 
 
 def area_planes(state, dtype=torch.uint8, side=None, counts=False):
@@ -1195,7 +1188,7 @@ def batch_area_planes_tracked(tracked, dtype=torch.uint8, out=None, orient=None,
     """batch_area_planes of tracked boards (int32 [B, 5N+1], a device tensor) -> [B, 3, N, N] of `dtype`
     (gg_batch_area_tracked): bit for bit what batch_area_planes gives for batch_untrack(tracked); only the two stone row
     sets and the turn flag are read."""
-    return _planes('gg_batch_area_tracked', AREA_PLANES, 1, tracked, True, dtype, out, orient, _AreaExtra(side, counts))
+    return _planes('gg_batch_area_tracked', AREA_PLANES, 1, tracked, True, dtype, out, orient, ('counts', counts, (2,), _I32), side=side)
 
 
 # ---------------------------------------------------------------- the sets of the tactical playout policy
@@ -1213,7 +1206,7 @@ def batch_tactics(batch_states, dtype=torch.uint8, out=None, orient=None):
     The ply: with u the high 32 bits of its draw and the gate open when (u & 3) != 0, it draws from C if the gate is open and
     C is not empty, else from E if the gate is open and E is not empty, else from F; the pass when the set is empty (F only).
     dtype, out, orient and NumPy input: as batch_area_planes.  One launch; device memory of the result: 3 * B * N^2 elements."""
-    return _planes('gg_batch_tactics', TACTICS_PLANES, 1, batch_states, False, dtype, out, orient, _NO_BYTES)
+    return _planes('gg_batch_tactics', TACTICS_PLANES, 1, batch_states, False, dtype, out, orient)
 
 
 def tactics(state, dtype=torch.uint8):
@@ -1225,7 +1218,7 @@ def batch_tactics_tracked(tracked, dtype=torch.uint8, out=None, orient=None):
     """batch_tactics of tracked boards (int32 [B, 5N+1], a device tensor) -> [B, 3, N, N] of `dtype`
     (gg_batch_tactics_tracked): bit for bit what batch_tactics gives for batch_untrack(tracked); every group is counted from
     the stones, the class rows are not read."""
-    return _planes('gg_batch_tactics_tracked', TACTICS_PLANES, 1, tracked, True, dtype, out, orient, _NO_BYTES)
+    return _planes('gg_batch_tactics_tracked', TACTICS_PLANES, 1, tracked, True, dtype, out, orient)
 
 
 # ---------------------------------------------------------------- the sets of the pattern playout policy
@@ -1245,7 +1238,7 @@ def batch_patterns(batch_states, last=None, dtype=torch.uint8, out=None, orient=
     then all zero.
     The ply: with the gate of 'tactical' open it draws from the first non-empty of C, E, L, F; with it closed, from F.
     dtype, out, orient and NumPy input: as batch_area_planes.  One launch; device memory of the result: 2 * B * N^2 elements."""
-    return _planes('gg_batch_patterns', PATTERN_PLANES, 1, batch_states, False, dtype, out, orient, _LastExtra(last))
+    return _planes('gg_batch_patterns', PATTERN_PLANES, 1, batch_states, False, dtype, out, orient, last=last)
 
 
 def patterns(state, last=None, dtype=torch.uint8):
@@ -1256,7 +1249,7 @@ def patterns(state, last=None, dtype=torch.uint8):
 def batch_patterns_tracked(tracked, last=None, dtype=torch.uint8, out=None, orient=None):
     """batch_patterns of tracked boards (int32 [B, 5N+1], a device tensor) -> [B, 2, N, N] of `dtype`
     (gg_batch_patterns_tracked): bit for bit what batch_patterns gives for batch_untrack(tracked)."""
-    return _planes('gg_batch_patterns_tracked', PATTERN_PLANES, 1, tracked, True, dtype, out, orient, _LastExtra(last))
+    return _planes('gg_batch_patterns_tracked', PATTERN_PLANES, 1, tracked, True, dtype, out, orient, last=last)
 
 
 # ---------------------------------------------------------------- move priors from the sets of both playout policies
@@ -1392,8 +1385,8 @@ STATUS_NAMES = ('own_alive', 'own_dead', 'own_unsettled', 'opp_alive', 'opp_dead
 STATUS_MAX_PLAYOUTS, STATUS_MAX_DEN = 1 << 20, 1024   # GG_STATUS_MAX_PLAYOUTS, GG_STATUS_MAX_DEN
 
 
-def _status_extra(ownership, playouts, threshold, side, counts):
-    """The _StatusExtra of a status call: ValueError for a Playouts without ownership, for playouts outside
+def _status_inputs(ownership, playouts, threshold):
+    """_planes' inputs of a status call - own, playouts, num, den -: ValueError for a Playouts without ownership, for playouts outside
     [1, STATUS_MAX_PLAYOUTS] and for a threshold that is not two integers 1 <= num <= den <= STATUS_MAX_DEN with 2 num > den -
     before a device is touched."""
     if isinstance(ownership, tuple) and hasattr(ownership, 'ownership'):
@@ -1410,7 +1403,7 @@ def _status_extra(ownership, playouts, threshold, side, counts):
     if not integral(num) or not integral(den) or not (1 <= num <= den <= STATUS_MAX_DEN and 2 * num > den):
         raise ValueError('threshold (num, den) must be integers with 1 <= num <= den <= %d and 2 num > den (got %r)'
                          % (STATUS_MAX_DEN, threshold))
-    return _StatusExtra(side, counts, ownership, int(playouts), int(num), int(den))
+    return dict(own=ownership, playouts=int(playouts), num=int(num), den=int(den))
 
 
 def batch_stone_status(batch_states, ownership, playouts, threshold=(2, 3), dtype=torch.uint8, out=None, orient=None, side=None,
@@ -1434,14 +1427,14 @@ def batch_stone_status(batch_states, ownership, playouts, threshold=(2, 3), dtyp
     opponent's dead stones (counts may also be a contiguous int32 [B, 4] device tensor to write into).  dtype, out (aligned to
     its element), orient (the planes turn, ownership is always in the stored frame, the counts do not turn) and NumPy input:
     as batch_area_planes.  Every bad argument is a ValueError before a device is touched.  One launch."""
-    return _planes('gg_batch_status', STATUS_PLANES, 1, batch_states, False, dtype, out, orient,
-                   _status_extra(ownership, playouts, threshold, side, counts))
+    return _planes('gg_batch_status', STATUS_PLANES, 1, batch_states, False, dtype, out, orient, ('counts', counts, (4,), _I32),
+                   side=side, **_status_inputs(ownership, playouts, threshold))
 
 
 def stone_status(state, ownership, playouts, threshold=(2, 3), dtype=torch.uint8, side=None, counts=False):
     """batch_stone_status of one state [6, N, N] and its ownership [2, N, N] (or the Playouts of that state) -> [9, N, N] (with
     counts=True: and int32 [4]); side: None or one flag."""
-    own = _status_extra(ownership, playouts, threshold, None, False).own          # (every ValueError before a device is touched)
+    own = _status_inputs(ownership, playouts, threshold)['own']          # (every ValueError before a device is touched)
     shape = tuple(state.shape) if isinstance(state, torch.Tensor) else np.shape(state)
     if len(shape) != 3 or not isinstance(own, (torch.Tensor, np.ndarray)) or own.ndim != 3:
         raise ValueError('stone_status takes one state [6, N, N] and its ownership, int32 [2, N, N], or the Playouts that hold it')
@@ -1455,8 +1448,8 @@ def batch_stone_status_tracked(tracked, ownership, playouts, threshold=(2, 3), d
     """batch_stone_status of tracked boards (int32 [B, 5N+1], a device tensor) -> [B, 9, N, N] of `dtype`
     (gg_batch_status_tracked): bit for bit what batch_stone_status gives for batch_untrack(tracked); only the two stone row
     sets and the turn bit are read."""
-    return _planes('gg_batch_status_tracked', STATUS_PLANES, 1, tracked, True, dtype, out, orient,
-                   _status_extra(ownership, playouts, threshold, side, counts))
+    return _planes('gg_batch_status_tracked', STATUS_PLANES, 1, tracked, True, dtype, out, orient, ('counts', counts, (4,), _I32),
+                   side=side, **_status_inputs(ownership, playouts, threshold))
 
 
 # ---------------------------------------------------------------- position hashes and positional superko
@@ -1583,34 +1576,6 @@ def _past_arg(history, B, N, what='history'):
     return history
 
 
-def _past_planes(name, boards, tracked, history, dtype, out, orient):
-    """The body of batch_past_planes[_tracked]: _planes' checks in its order, then one launch with the ring's pointers."""
-    code = _feature_dtype(dtype)
-    B, N = _hash_shape(boards, tracked)
-    _past_arg(history, B, N)
-    count = history.planes
-    if not tracked:
-        _planes_out(out, (B, count, N, N), dtype, 1)
-    if orient is not None:
-        _orient_arg(orient, B)
-    if tracked:
-        box, st = None, boards
-        _planes_out(out, (B, count, N, N), dtype, 1, st.device if st.is_cuda else None)
-    else:
-        if not isinstance(boards, torch.Tensor) and dtype == torch.bfloat16:
-            raise ValueError('NumPy has no bfloat16: pass a device tensor, or another dtype')
-        box = _Box(boards)
-        st = box.t
-        _planes_out(out, (B, count, N, N), dtype, 1, st.device)
-    if history.rows.device != st.device:
-        raise ValueError('history must live on the boards\' device (%s)' % (st.device,))
-    planes = out if out is not None else torch.empty((B, count, N, N), dtype=dtype, device=st.device)
-    o = None if orient is None else _actions_tensor(orient, B, st.device)
-    _lib.call(name, st, history.rows, history.count, history.capacity, history.positions, int(history.moves), o, planes, code, B, N,
-              _lib.stream_ptr(st.device))
-    return planes if box is None else _back(box, planes)
-
-
 def batch_past_planes(batch_states, history, dtype=torch.uint8, out=None, orient=None):
     """History input planes of every board -> [B, history.planes, N, N] of `dtype` (gg_batch_past), each value exactly 0 or 1.
     batch_states are the CURRENT positions, history (a StoneHistory of the B games) the positions before them; T and moves
@@ -1623,13 +1588,13 @@ def batch_past_planes(batch_states, history, dtype=torch.uint8, out=None, orient
     T = 8 without moves plus batch_features' plane 13 is AlphaGo Zero's input; the move planes are KataGo's recent moves.
     dtype, out (aligned to its element), orient (every position of a board is turned alike) and NumPy in / NumPy out: as
     batch_area_planes.  One launch; nothing synchronises."""
-    return _past_planes('gg_batch_past', batch_states, False, history, dtype, out, orient)
+    return _planes('gg_batch_past', None, 1, batch_states, False, dtype, out, orient, history=history)
 
 
 def batch_past_planes_tracked(tracked, history, dtype=torch.uint8, out=None, orient=None):
     """batch_past_planes of tracked boards (int32 [B, 5N+1], a device tensor): gg_batch_past_tracked, bit for bit what
     batch_past_planes gives for batch_untrack(tracked)."""
-    return _past_planes('gg_batch_past_tracked', tracked, True, history, dtype, out, orient)
+    return _planes('gg_batch_past_tracked', None, 1, tracked, True, dtype, out, orient, history=history)
 
 
 def past_planes(states, positions=8, moves=False, dtype=torch.uint8):
@@ -1647,11 +1612,6 @@ def past_planes(states, positions=8, moves=False, dtype=torch.uint8):
     for k in range(max(0, K - T), K - 1):
         hist.push(box.t[k:k + 1])
     return _back(box, batch_past_planes(box.t[K - 1:K], hist, dtype), row0=True)
-
-
-def _puct_past_guard(past, features):
-    if past is not None and features is None:   # (before a device is touched)
-        raise ValueError('past= hands out the history planes in the dtype of features=: give features= too')
 
 
 def _puct_past_history(past, box):
@@ -2144,7 +2104,7 @@ def batch_final_score(batch_states, playouts=64, komi=0.0, threshold=(2, 3), pol
     B, N = _states_shape(batch_states)
     if 'ownership' in playout_kw or 'amaf' in playout_kw:
         raise ValueError('batch_final_score runs its playouts with ownership=True and without amaf')
-    _status_extra(None, playouts, threshold, None, True)
+    _status_inputs(None, playouts, threshold)
     _policy_kw({'policy': policy})
     box = _Box(batch_states)
     st = box.t
@@ -2533,6 +2493,38 @@ def gumbel_noise(generator=None):
     return noise
 
 
+# THE table of the optional plane sets a leaf of the search (PuctSearch) or a sample of a record (selfplay_batch) can carry, in
+# hand-out order: the option's keyword, the entry point on tracked boards, the planes per board, the public call on byte planes and
+# the words of the error message.  The history planes (past=: always last, gg_puct_past reads the tree) and symmetry= are no rows:
+# they are written out where they differ.
+_LeafSet = collections.namedtuple('_LeafSet', 'key entry planes batch words')
+_LEAF_SETS = (_LeafSet('life', 'gg_batch_life_tracked', LIFE_PLANES, batch_life, 'life'),
+              _LeafSet('ladder', 'gg_batch_ladder_tracked', LADDER_PLANES, batch_ladder, 'ladder'),
+              _LeafSet('outcome', 'gg_batch_move_planes_tracked', MOVE_PLANES, batch_move_planes, 'move-outcome'),
+              _LeafSet('area', 'gg_batch_area_tracked', AREA_PLANES, batch_area_planes, 'area'))
+_SEARCH_OPTIONS = ('leaves', 'capacity', 'features', 'symmetry', 'first_root') + tuple(s.key for s in _LEAF_SETS) + ('past', 'gumbel')
+
+
+def _search_options(given):
+    """The options of PuctSearch among the arguments of a public function (given: its locals() on entry, or its **kw) -> one dict,
+    handed on as it is."""
+    return {k: given[k] for k in _SEARCH_OPTIONS if k in given}
+
+
+def _puct_planes_guard(opts):
+    """ValueError for an option that hands out planes - symmetry=, a set of _LEAF_SETS, past= - without features= (opts: a dict
+    of the options given) - before a device is touched."""
+    if opts.get('features') is not None:
+        return
+    if opts.get('symmetry') is not None:
+        raise ValueError('symmetry turns the planes and legal that features= hands out: give features= too')
+    for s in _LEAF_SETS:
+        if opts.get(s.key):
+            raise ValueError('%s=True hands out the %s planes in the dtype of features=: give features= too' % (s.key, s.words))
+    if opts.get('past') is not None:
+        raise ValueError('past= hands out the history planes in the dtype of features=: give features= too')
+
+
 class PuctSearch:
     """The step-wise form of batch_puct, for callers who batch their network calls their own way:
 
@@ -2653,24 +2645,16 @@ class PuctSearch:
 
     def __init__(self, batch_states, iterations, c=1.25, komi=0.0, leaves=None, capacity=None, features=None, symmetry=None,
                  first_root=0, life=False, ladder=False, outcome=False, superko=None, area=False, past=None, gumbel=None):
+        opts = _search_options(locals())
         self._feat = None if features is None else (features, _feature_dtype(features))
         _gumbel_arg(gumbel, 2, 1)   # (what it is, before a device is touched; its simulations further down)
         if superko is not None:   # (before a device is touched)
             shape = np.shape(batch_states.t if isinstance(batch_states, _Box) else batch_states)
             _history_arg(superko, shape[0] if shape else -1)
-        _puct_past_guard(past, features)
+        _puct_planes_guard(opts)
         if past is not None:      # (before a device is touched)
             shape = np.shape(batch_states.t if isinstance(batch_states, _Box) else batch_states)
             _past_arg(past, shape[0] if shape else -1, shape[-1] if shape else -1, 'past')
-        _puct_symmetry_guard(symmetry, features)
-        _puct_life_guard(life, features)
-        _puct_ladder_guard(ladder, features)
-        _puct_outcome_guard(outcome, features)
-        _puct_area_guard(area, features)
-        self._life = bool(life)
-        self._ladder = bool(ladder)
-        self._outcome = bool(outcome)
-        self._area = bool(area)
         self._past = past
         self._sym = None if symmetry is None else int(symmetry)
         self._first_root = int(first_root)
@@ -2710,14 +2694,9 @@ class PuctSearch:
         else:   # (the leaves go out as planes: no byte-plane buffer)
             self._states = torch.empty((B, FEATURE_PLANES, N, N), dtype=self._feat[0], device=dev)
         self._legal = torch.empty((B, A), dtype=torch.bool, device=dev)
-        if self._life:
-            self._life_planes = torch.empty((B, LIFE_PLANES, N, N), dtype=self._feat[0], device=dev)
-        if self._ladder:
-            self._ladder_planes = torch.empty((B, LADDER_PLANES, N, N), dtype=self._feat[0], device=dev)
-        if self._outcome:
-            self._outcome_planes = torch.empty((B, MOVE_PLANES, N, N), dtype=self._feat[0], device=dev)
-        if self._area:
-            self._area_planes = torch.empty((B, AREA_PLANES, N, N), dtype=self._feat[0], device=dev)
+        # the plane sets that are on, in hand-out order: (the set's row, its planes)
+        self._sets = [(s, torch.empty((B, s.planes, N, N), dtype=self._feat[0], device=dev)) for s in _LEAF_SETS if opts[s.key]]
+        self._set_launches = []
         if past is not None:
             if past.rows.device != dev or past.count.device != dev:
                 raise ValueError('past must be a StoneHistory of %d boards on the device of batch_states (%s)' % (R, dev))
@@ -2740,6 +2719,10 @@ class PuctSearch:
         self._hand = (_lib.ptrs('gg_batch_untrack_states', states=self._states) if self._feat is None else
                       _lib.ptrs('gg_batch_features_tracked', out=self._states)) + _lib.ptrs('gg_puct_legal', legal=self._legal, live=self.live)
         self._rows = [p for p in _lib.ABI['gg_puct_backup'] if p.name in ('priors', 'values')]
+        if self._feat is not None:   # the hand-out launches are prepared once: the feature planes first, then the sets that are on
+            self._op = None if self._sym is None else _lib.ptrs('gg_batch_draw_orient', orient=self.orient)[0]
+            self._feature_launch = self._prepared('gg_batch_features_tracked', self._states)
+            self._set_launches = [self._prepared(s.entry, planes) for s, planes in self._sets]
         _lib.call('gg_puct_begin', _track_roots(st), R, N, self._C, *self._tree, _lib.current_raw_stream(dev))
         if superko is not None:
             self._ko = _lib.ptrs('gg_puct_superko', links=self._links, node_hash=self.node_hash)
@@ -2751,6 +2734,12 @@ class PuctSearch:
             self._seq = torch.from_numpy(gumbel_sequence(self._gumbel.considered, self._gumbel.simulations)).to(dev)
             self._root = _lib.ptrs('gg_gumbel_select_leaves', base=self.base, seen=self._seen, done=self._sims, seq=self._seq)
             self._gumbel_begin()
+
+    def _prepared(self, name, planes):
+        """A plane launch on the leaf boards into `planes`, prepared: (entry point, *its arguments but the stream) with every
+        pointer an address - the leaves, search.orient with symmetry= and the planes are the search's own buffers and never move."""
+        out, = _lib.ptrs(name, out=planes)
+        return _plane_args(name, self._out[0], self._op, dict(out=out, out_dtype=self._feat[1], B=planes.shape[0], N=self._N))[:-1]
 
     def _gumbel_begin(self):
         """seen = the visits of node 0's children as they stand, done = 0 (R > 0): the search of a move begins; one launch."""
@@ -2843,9 +2832,8 @@ class PuctSearch:
 
     def _draw_orient(self, B, stream):
         """The orientations of this select()'s B rows -> the pointer of search.orient."""
-        op, = _lib.ptrs('gg_batch_draw_orient', orient=self.orient)
-        _lib.call('gg_batch_draw_orient', self._sym_rng, op, B, stream)
-        return op
+        _lib.call('gg_batch_draw_orient', self._sym_rng, self._op, B, stream)
+        return self._op
 
     def _turn_legal(self, op, B, stream):
         _lib.call('gg_batch_symmetry_policy', self._legal, op, self._legal_view, 1, 0, B, self._N, stream)
@@ -2893,20 +2881,14 @@ class PuctSearch:
                       'gg_puct_superko')
             if self._feat is None:
                 check(lib.gg_batch_untrack_states(lp, sp, B, N, stream), 'gg_batch_untrack_states')
-            else:   # (sp: the planes)
+            else:   # (the feature planes, into sp)
                 op = None if self._sym is None else self._draw_orient(B, stream)
-                _plane_launch('gg_batch_features_tracked', lp, op, sp, False, self._feat[1], B, N, stream, _lib.launch)
+                _lib.launch(*self._feature_launch, stream)
             check(lib.gg_puct_legal(lp, ip, B, N, gp, vp, stream), 'gg_puct_legal')
             if self._sym is not None:
                 self._turn_legal(op, B, stream)
-            if self._life:
-                _plane_launch('gg_batch_life_tracked', lp, op, self._life_planes, None, self._feat[1], B, N, stream)
-            if self._ladder:
-                _plane_launch('gg_batch_ladder_tracked', lp, op, self._ladder_planes, None, self._feat[1], B, N, stream)
-            if self._outcome:
-                _plane_launch('gg_batch_move_planes_tracked', lp, op, self._outcome_planes, _NO_BYTES, self._feat[1], B, N, stream)
-            if self._area:
-                _plane_launch('gg_batch_area_tracked', lp, op, self._area_planes, _AreaExtra(None, None), self._feat[1], B, N, stream)
+            for prepared in self._set_launches:   # (the sets that are on, in the table's order)
+                _lib.launch(*prepared, stream)
             if self._past is not None:
                 bp, kp, rp, cp, pp = self._past_ptrs
                 past = self._past
@@ -2916,10 +2898,7 @@ class PuctSearch:
         if self._gumbel is not None:
             self._g_open, self._since = False, self._since + 1
         legal = self._legal if self._sym is None else self._legal_view
-        res = (self._states, legal, self._life_planes) if self._life else (self._states, legal)
-        res = res + (self._ladder_planes,) if self._ladder else res
-        res = res + (self._outcome_planes,) if self._outcome else res
-        res = res + (self._area_planes,) if self._area else res
+        res = (self._states, legal) + tuple(planes for _, planes in self._sets)
         return res + (self._past_planes,) if self._past is not None else res
 
     def backup(self, priors, values):
@@ -2975,10 +2954,7 @@ class PuctSearch:
         R, N = self._R, self._N
         states = torch.empty((R, govars.NUM_CHNLS, N, N), dtype=_U8, device=self._dev)
         if R:
-            self._advance_buffers()
-            with torch.cuda.device(self._dev):
-                self._next.copy_(self._boards[:, 0, :])
-            _lib.call('gg_batch_untrack_states', self._next, states, R, N, _lib.current_raw_stream(self._dev))
+            _lib.call('gg_batch_untrack_states', self._root_boards(), states, R, N, _lib.current_raw_stream(self._dev))
         return states
 
     def _advance_buffers(self):
@@ -2991,6 +2967,13 @@ class PuctSearch:
             self._scratch = _lib.ptrs('gg_puct_advance', next=self._next, remap=self._remap, kept=self._kept) if R else ()
         return self._scratch
 
+    def _root_boards(self):
+        """-> next [R, W], the search's scratch boards, as a copy of node 0's boards (R > 0): one copy."""
+        self._advance_buffers()
+        with torch.cuda.device(self._dev):
+            self._next.copy_(self._boards[:, 0, :])
+        return self._next
+
     def _play_on_roots(self, acts):
         """next = node 0's boards after acts (int64 [R] on the device; R > 0) -> the pointers of (actions as int32, next,
         remap, kept).  Whatever lies outside [-1, A) - below -1 too, which must not become the -1 that leaves a root
@@ -2999,8 +2982,7 @@ class PuctSearch:
         acts = torch.where((acts < -1) | (acts > A), torch.full_like(acts, A), acts).to(_I32).contiguous()
         np_, rp, kp = self._advance_buffers()
         ap, = _lib.ptrs('gg_puct_advance', actions=acts)
-        with torch.cuda.device(self._dev):
-            self._next.copy_(self._boards[:, 0, :])
+        self._root_boards()
         _lib.call('gg_batch_play_moves_tracked', np_, ap, None, self._R, self._N, 1, _lib.current_raw_stream(self._dev))
         return ap, np_, rp, kp
 
@@ -3010,10 +2992,8 @@ class PuctSearch:
         compare, one launch; nothing is read back."""
         if self._past is None:
             return
-        self._advance_buffers()
         with torch.cuda.device(self._dev):
-            self._next.copy_(self._boards[:, 0, :])
-            self._past.push_tracked(self._next, acts != -1)
+            self._past.push_tracked(self._root_boards(), acts != -1)
 
     def _played_states(self, acts):
         """-> uint8 [R, 6, N, N], a new device tensor: the roots after acts (int64 [R] on the device, -1 stays put), played on
@@ -3073,10 +3053,7 @@ class PuctSearch:
         R = self._R
         if not R:
             return torch.empty(0, dtype=_I64, device=self._dev)
-        self._advance_buffers()
-        with torch.cuda.device(self._dev):
-            self._next.copy_(self._boards[:, 0, :])
-        return batch_hash_tracked(self._next)
+        return batch_hash_tracked(self._root_boards())
 
     def forbid_repeats(self, history=None):
         """Positional superko AT THE ROOTS: the moves that would recreate a position of `history` (a PositionHistory of the R
@@ -3096,10 +3073,8 @@ class PuctSearch:
         _history_arg(history, R)
         if not R:
             return
-        self._advance_buffers()
         with torch.cuda.device(self._dev):
-            self._next.copy_(self._boards[:, 0, :])
-            _, _, rep, rows = _move_hashes(self._next, True, history, repeat=True, rows=True)
+            _, _, rep, rows = _move_hashes(self._root_boards(), True, history, repeat=True, rows=True)
             self._boards[:, 0, 2 * N:3 * N].bitwise_or_(rows)
             self._legal_roots = self._legal_roots & (rep == 0)
 
@@ -3261,24 +3236,15 @@ def batch_puct(batch_states, iterations, evaluator, c=1.25, komi=0.0, tree=False
     (PuctSearch): the root's simulations follow the schedule instead of U'.  The result type does not change - the visits
     are those the schedule handed out -; puct_actions(gumbel=) gives the Gumbel move, PuctSearch.gumbel_root the improved
     policy."""
-    return _puct_searched(batch_states, iterations, evaluator, c=c, komi=komi, leaves=leaves, capacity=capacity, features=features,
-                          symmetry=symmetry, first_root=first_root, life=life, ladder=ladder, outcome=outcome, superko=superko,
-                          area=area, past=past, gumbel=gumbel).result(tree=tree)
+    return _puct_searched(batch_states, iterations, evaluator, c, komi, superko, **_search_options(locals())).result(tree=tree)
 
 
-def _puct_searched(batch_states, iterations, evaluator, c=1.25, komi=0.0, leaves=None, capacity=None, features=None, symmetry=None,
-                   first_root=0, life=False, ladder=False, outcome=False, superko=None, area=False, past=None, gumbel=None):
-    """batch_puct's loop -> the PuctSearch after its last backup."""
+def _puct_searched(batch_states, iterations, evaluator, c=1.25, komi=0.0, superko=None, **opts):
+    """batch_puct's loop -> the PuctSearch after its last backup.  opts: the options of PuctSearch (_SEARCH_OPTIONS)."""
     _puct_komi_guard(evaluator, komi)
-    _puct_features_guard(evaluator, features)
-    _puct_life_guard(life, features)
-    _puct_ladder_guard(ladder, features)
-    _puct_outcome_guard(outcome, features)
-    _puct_area_guard(area, features)
-    _puct_past_guard(past, features)
-    search = PuctSearch(batch_states, iterations, c, komi, leaves=leaves, capacity=capacity, features=features, symmetry=symmetry,
-                        first_root=first_root, life=life, ladder=ladder, outcome=outcome, superko=superko, area=area, past=past,
-                        gumbel=gumbel)
+    _puct_features_guard(evaluator, opts.get('features'))
+    _puct_planes_guard(opts)
+    search = PuctSearch(batch_states, iterations, c, komi, superko=superko, **opts)
     if superko is not None:
         search.forbid_repeats()
     for _ in range(search._I):
@@ -3291,31 +3257,6 @@ def _puct_komi_guard(evaluator, komi):
     ek = getattr(evaluator, 'komi', None)   # (playout_evaluator says what komi it scores with)
     if ek is not None and float(ek) != float(komi):
         raise ValueError('the evaluator scores its playouts with komi %r, the search its ended leaves with %r' % (ek, komi))
-
-
-def _puct_symmetry_guard(symmetry, features):
-    if symmetry is not None and features is None:   # (before a device is touched)
-        raise ValueError('symmetry turns the planes and legal that features= hands out: give features= too')
-
-
-def _puct_life_guard(life, features):
-    if life and features is None:   # (before a device is touched)
-        raise ValueError('life=True hands out the life planes in the dtype of features=: give features= too')
-
-
-def _puct_ladder_guard(ladder, features):
-    if ladder and features is None:   # (before a device is touched)
-        raise ValueError('ladder=True hands out the ladder planes in the dtype of features=: give features= too')
-
-
-def _puct_outcome_guard(outcome, features):
-    if outcome and features is None:   # (before a device is touched)
-        raise ValueError('outcome=True hands out the move-outcome planes in the dtype of features=: give features= too')
-
-
-def _puct_area_guard(area, features):
-    if area and features is None:   # (before a device is touched)
-        raise ValueError('area=True hands out the area planes in the dtype of features=: give features= too')
 
 
 def _puct_superko_guard(superko):
@@ -3378,15 +3319,12 @@ def puct_play(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, leav
     Gumbel action (PuctSearch.gumbel_root; -1 for a root whose game has ended); gumbel_noise (None, or a callable
     noise(mv, legal) -> float [R, A] as gumbel_noise() returns; needs gumbel=): g of move mv, set before its first round;
     None leaves g at zeros - noise-free sequential halving, for match play."""
+    opts = _search_options(locals())
     _gumbel_noise_guard(gumbel, gumbel_noise)
     _puct_superko_guard(superko)
     _puct_komi_guard(evaluator, komi)
     _puct_features_guard(evaluator, features)
-    _puct_life_guard(life, features)
-    _puct_ladder_guard(ladder, features)
-    _puct_outcome_guard(outcome, features)
-    _puct_area_guard(area, features)
-    _puct_past_guard(past, features)
+    _puct_planes_guard(opts)
     if past is not None and not isinstance(past, StoneHistory):
         _past_request(past)
     moves = int(moves)
@@ -3394,16 +3332,12 @@ def puct_play(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, leav
         raise ValueError('need moves >= 0 (got %d)' % moves)
     deep = None
     if past is not None:
-        _puct_symmetry_guard(symmetry, features)
         batch_states = batch_states if isinstance(batch_states, _Box) else _Box(batch_states)
-        past = _puct_past_history(past, batch_states)
+        opts['past'] = _puct_past_history(past, batch_states)
     if superko is not True and superko:   # ('tree': the search keeps the history, which therefore stands before the search)
-        _puct_symmetry_guard(symmetry, features)
         batch_states = batch_states if isinstance(batch_states, _Box) else _Box(batch_states)
         deep = _puct_superko_history(superko, batch_states, moves)
-    search = PuctSearch(batch_states, iterations, c, komi, leaves=leaves, capacity=capacity, features=features, symmetry=symmetry,
-                        first_root=first_root, life=life, ladder=ladder, outcome=outcome, superko=deep, area=area, past=past,
-                        gumbel=gumbel)
+    search = PuctSearch(batch_states, iterations, c, komi, superko=deep, **opts)
     box = search._box
     played = torch.empty((search._R, moves), dtype=_I64, device=box.t.device)
     seen = None
@@ -3428,9 +3362,9 @@ def puct_play(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, leav
             if search._R:
                 search._push_past(played[:, mv])
             box.t = search._played_states(played[:, mv])
-            search = PuctSearch(box, iterations, c, komi, leaves=leaves, capacity=capacity, features=features,
-                                symmetry=None if symmetry is None else int(symmetry) + mv + 1, first_root=first_root, life=life,
-                                ladder=ladder, outcome=outcome, superko=deep, area=area, past=past, gumbel=gumbel)
+            if symmetry is not None:   # (a new search would repeat the first one's draws otherwise)
+                opts['symmetry'] = int(symmetry) + mv + 1
+            search = PuctSearch(box, iterations, c, komi, superko=deep, **opts)
         if seen is not None:
             seen.push(search._root_hashes())
     return _back(box, played), box.back(search._root_states())
@@ -3520,18 +3454,15 @@ def puct_selfplay(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, 
     improved policy, so sample_moves > 0 raises ValueError, as does noise other than None: the exploration is g -, the
     recorded pi is the improved policy and value the root's mean value (PuctSearch.gumbel_root).  selfplay_batch takes the
     records as they are."""
+    opts = dict(_search_options(locals()), first_root=first_game)
     _gumbel_noise_guard(gumbel, gumbel_noise, 'default')
     _gumbel_arg(gumbel, 2, 1)
-    _puct_past_guard(past, features)
+    _puct_planes_guard(opts)
     if past is not None and not isinstance(past, StoneHistory):
         _past_request(past)
     _puct_superko_guard(superko)
     _puct_komi_guard(evaluator, komi)
     _puct_features_guard(evaluator, features)
-    _puct_life_guard(life, features)
-    _puct_ladder_guard(ladder, features)
-    _puct_outcome_guard(outcome, features)
-    _puct_area_guard(area, features)
     moves, sample_moves, eps = int(moves), int(sample_moves), float(eps)
     if moves < 0:
         raise ValueError('need moves >= 0 (got %d)' % moves)
@@ -3545,7 +3476,6 @@ def puct_selfplay(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, 
         raise ValueError('a Gumbel search explores through gumbel_noise, not through noise in the priors: noise must be None')
     if gumbel is not None and sample_moves > 0:
         raise ValueError('the Gumbel action is already a draw from the improved policy: sample_moves must be 0 with gumbel=')
-    _puct_symmetry_guard(symmetry, features)
     box = batch_states if isinstance(batch_states, _Box) else _Box(batch_states)
     st = box.t
     if st.dim() != 4 or st.shape[1] != govars.NUM_CHNLS or st.shape[2] != st.shape[3]:
@@ -3560,14 +3490,13 @@ def puct_selfplay(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, 
     pis = torch.zeros((R, moves, A), dtype=torch.float32, device=dev)
     vals = torch.zeros((R, moves), dtype=torch.float32, device=dev)
     lengths = torch.zeros(R, dtype=_I32, device=dev)
-    won = torch.zeros(R, dtype=torch.int8, device=dev)   # (the record's outcome; `outcome` is the option)
+    won = torch.zeros(R, dtype=torch.int8, device=dev)   # (who won, for the record: the field's own name is an option's here)
     before = torch.empty((R, moves, govars.NUM_CHNLS, N, N), dtype=_U8, device=dev) if record_states else None
     if not R or not moves:
         return _back(box, SelfPlay(played, pis, vals, won, lengths, st, before))
     deep = _puct_superko_history(superko, box, moves)
-    search = PuctSearch(box, I, c, komi, leaves=leaves, capacity=capacity, features=features, symmetry=symmetry, first_root=first_game,
-                        life=life, ladder=ladder, outcome=outcome, superko=deep, area=area, past=_puct_past_history(past, box),
-                        gumbel=gumbel)
+    opts['past'] = _puct_past_history(past, box)
+    search = PuctSearch(box, I, c, komi, superko=deep, **opts)
     rng = rng_seed(R, seed, first_game, device=dev)
     ones, todo = torch.ones(R, dtype=_U8, device=dev), torch.empty(R, dtype=_U8, device=dev)
     seen = (deep or PositionHistory(R, moves + 1, dev)).push(search._root_hashes()) if superko else None
@@ -3604,12 +3533,7 @@ def puct_selfplay(batch_states, moves, iterations, evaluator, c=1.25, komi=0.0, 
 def puct(state, iterations, evaluator, **kw):
     """batch_puct of one state [6, N, N] -> Puct of [N*N + 1] vectors and scalars (tree fields [iterations + 1]); the evaluator
     still sees a batch of one."""
-    _puct_symmetry_guard(kw.get('symmetry'), kw.get('features'))
-    _puct_life_guard(kw.get('life', False), kw.get('features'))
-    _puct_ladder_guard(kw.get('ladder', False), kw.get('features'))
-    _puct_outcome_guard(kw.get('outcome', False), kw.get('features'))
-    _puct_area_guard(kw.get('area', False), kw.get('features'))
-    _puct_past_guard(kw.get('past'), kw.get('features'))
+    _puct_planes_guard(kw)
     return _single(batch_puct, state, iterations, evaluator, **kw)
 
 
@@ -3617,12 +3541,7 @@ def puct_actions(batch_states, iterations, evaluator, **kw):
     """The PUCT move of every root -> int64 [R]: the legal root child with the most visits after batch_puct(batch_states,
     iterations, evaluator, **kw); ties go to the lowest action, a root without a legal move gives -1.  With gumbel= it is the
     Gumbel move (PuctSearch.gumbel_root): among the actions with the most simulations the largest g + logit + sigma(q), g = 0."""
-    _puct_symmetry_guard(kw.get('symmetry'), kw.get('features'))
-    _puct_life_guard(kw.get('life', False), kw.get('features'))
-    _puct_ladder_guard(kw.get('ladder', False), kw.get('features'))
-    _puct_outcome_guard(kw.get('outcome', False), kw.get('features'))
-    _puct_area_guard(kw.get('area', False), kw.get('features'))
-    _puct_past_guard(kw.get('past'), kw.get('features'))
+    _puct_planes_guard(kw)
     box = _Box(batch_states)
     if kw.get('gumbel') is not None:
         kw.pop('tree', None)
@@ -3908,6 +3827,7 @@ def selfplay_batch(record, games, moves, orient, dtype=torch.float16, life=False
     the sampled positions in view orient and dtype `dtype` - a StoneHistory of the B samples filled from
     record.states[games, moves - t] for t = T - 1 .. 1, oldest first, where moves - t >= 0 (T - 1 pushes), then one
     batch_past_planes launch with orient."""
+    given = locals()   # (the sets that are on are read from it by the table's keywords)
     _feature_dtype(dtype)
     if past is not None:
         past = _past_request(past)
@@ -3924,14 +3844,9 @@ def selfplay_batch(record, games, moves, orient, dtype=torch.float16, life=False
     planes = batch_features(positions, dtype, orient=orient)
     pi = batch_symmetry_policy(t(record.pi)[g, m].to(torch.float32), orient)
     res = (planes, pi, z.to(dev), valid.to(dev))
-    if life:
-        res += (batch_life(positions, dtype, orient=orient),)
-    if ladder:
-        res += (batch_ladder(positions, dtype, orient=orient),)
-    if outcome:
-        res += (batch_move_planes(positions, dtype, orient=orient),)
-    if area:
-        res += (batch_area_planes(positions, dtype, orient=orient),)
+    for s in _LEAF_SETS:
+        if given[s.key]:
+            res += (s.batch(positions, dtype, orient=orient),)
     if past is not None:
         hist = StoneHistory(B, positions.shape[2], past[0], past[1], device=dev)
         all_states = t(record.states)
