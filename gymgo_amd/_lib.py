@@ -9,9 +9,10 @@ its own, include/gymgo_amd_area.h, and a table of its own, ABI_AREA, bound and c
 (include/gymgo_amd_past.h, ABI_PAST), the Gumbel root rule of the PUCT search (include/gymgo_amd_gumbel.h, ABI_GUMBEL), the
 tactical playout policy with its planes (include/gymgo_amd_tactics.h, ABI_TACTICS), the AMAF statistics of the playouts with
 RAVE in the UCT search (include/gymgo_amd_amaf.h, ABI_AMAF), the pattern playout policy with its planes
-(include/gymgo_amd_pattern.h, ABI_PATTERN), the move priors of the RAVE search (include/gymgo_amd_prior.h, ABI_PRIOR) and stone
-status with the final score from playout ownership (include/gymgo_amd_status.h, ABI_STATUS).  ABI_ALL is the nine merged: the
-one lookup lib(), call(), ptrs() and PARAMS (the parameter names of every entry point, in order) are made from.
+(include/gymgo_amd_pattern.h, ABI_PATTERN), the move priors of the RAVE search (include/gymgo_amd_prior.h, ABI_PRIOR), stone
+status with the final score from playout ownership (include/gymgo_amd_status.h, ABI_STATUS) and the UCT search with several
+leaves per root and round (include/gymgo_amd_uct_leaves.h, ABI_UCT_LEAVES).  ABI_ALL is the ten merged: the one lookup lib(),
+call(), ptrs() and PARAMS (the parameter names of every entry point, in order) are made from.
 """
 import collections
 import ctypes
@@ -257,6 +258,27 @@ ABI_STATUS = {
     'gg_batch_status': _params(_U8, 'states') + _params(_I32, 'orient') + _STATUS,
     'gg_batch_status_tracked': _params(_I32, 'tracked', 'orient') + _STATUS,
 }
+# ... and of include/gymgo_amd_uct_leaves.h, the UCT search with several leaves per root and round, in its order
+# (tests/test_uct_leaves_host.py holds it against its header): each call is its namesake's list with L behind I and - select and
+# backup - virt behind nodes / behind stats or node_amaf
+def _with_leaves(ps, virt_after=None):
+    out = []
+    for p in ps:
+        out.append(p)
+        if p.name == 'I':
+            out += _params(_i32, 'L')
+        if p.name == virt_after:
+            out += _params(_I32, 'virt')
+    return tuple(out)
+
+
+ABI_UCT_LEAVES = {
+    'gg_uct_select_leaves': _with_leaves(ABI['gg_uct_select'], 'nodes'),
+    'gg_uct_backup_leaves': _with_leaves(ABI['gg_uct_backup'], 'stats'),
+    'gg_uct_select_leaves_rave': _with_leaves(ABI_AMAF['gg_uct_select_rave'], 'nodes'),
+    'gg_uct_backup_leaves_rave': _with_leaves(ABI_AMAF['gg_uct_backup_rave'], 'node_amaf'),
+    'gg_uct_prior_expand_leaves': _with_leaves(ABI_PRIOR['gg_uct_prior_expand']),
+}
 EXPORTS = tuple(ABI)
 EXPORTS_AREA = tuple(ABI_AREA)
 EXPORTS_PAST = tuple(ABI_PAST)
@@ -266,6 +288,7 @@ EXPORTS_AMAF = tuple(ABI_AMAF)
 EXPORTS_PATTERN = tuple(ABI_PATTERN)
 EXPORTS_PRIOR = tuple(ABI_PRIOR)
 EXPORTS_STATUS = tuple(ABI_STATUS)
+EXPORTS_UCT_LEAVES = tuple(ABI_UCT_LEAVES)
 _signatures = lambda table: {f: ([p.kind if isinstance(p.kind, type) else _vp for p in ps], _i32) for f, ps in table.items()}
 _SIGNATURES = _signatures(ABI)   # argtypes, restype
 _SIGNATURES_AREA = _signatures(ABI_AREA)
@@ -276,9 +299,11 @@ _SIGNATURES_AMAF = _signatures(ABI_AMAF)
 _SIGNATURES_PATTERN = _signatures(ABI_PATTERN)
 _SIGNATURES_PRIOR = _signatures(ABI_PRIOR)
 _SIGNATURES_STATUS = _signatures(ABI_STATUS)
-# every entry point of the nine headers in ONE lookup: what lib() binds and what call(), ptrs() and the plane launches of gogame
+_SIGNATURES_UCT_LEAVES = _signatures(ABI_UCT_LEAVES)
+# every entry point of the ten headers in ONE lookup: what lib() binds and what call(), ptrs() and the plane launches of gogame
 # (PARAMS: the parameter names in order) look an entry point up in, whichever header declares it
-ABI_ALL = {**ABI, **ABI_AREA, **ABI_PAST, **ABI_GUMBEL, **ABI_TACTICS, **ABI_AMAF, **ABI_PATTERN, **ABI_PRIOR, **ABI_STATUS}
+ABI_ALL = {**ABI, **ABI_AREA, **ABI_PAST, **ABI_GUMBEL, **ABI_TACTICS, **ABI_AMAF, **ABI_PATTERN, **ABI_PRIOR, **ABI_STATUS,
+           **ABI_UCT_LEAVES}
 PARAMS = {f: {p.name: i for i, p in enumerate(ps)} for f, ps in ABI_ALL.items()}   # the parameter names in order -> position
 # call(): the number of parameters and (index, dtypes, name) of every pointer to device memory
 _POINTERS = {f: (len(ps), tuple((i, p.kind if isinstance(p.kind, tuple) else (p.kind,), p.name)

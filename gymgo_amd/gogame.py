@@ -2216,7 +2216,7 @@ UctRave.__doc__ = """Uct of a RAVE search (batch_uct(..., rave_equiv=k)), plus t
 tree, when asked for, is a UctRaveTree."""
 UctRaveTree = collections.namedtuple('UctRaveTree', UctTree._fields + ('node_amaf',))
 UctRaveTree.__doc__ = """UctTree plus node_amaf (int32 [R, iterations + 1, N*N, 2]: the pairs of every node)."""
-UctTree.__doc__ = """The whole tree of every root, each field int32 [R, iterations + 1] indexed by node (node 0 = the root;
+UctTree.__doc__ = """The whole tree of every root, each field int32 [R, iterations + 1] ([R, iterations * leaves + 1] with `leaves`) indexed by node (node 0 = the root;
 parent / action -1 at the root and at unused nodes, whose stats are 0)."""
 
 
@@ -2241,20 +2241,43 @@ def _legal_roots(st):
     return legal & ~ended[:, None]
 
 
+def _uct_leaves(leaves):
+    """leaves=None -> None (the one-leaf path); else the validated int L >= 1."""
+    if leaves is None:
+        return None
+    if not _int_arg(leaves) or int(leaves) < 1:
+        raise ValueError('leaves must be None or an integer >= 1 (got %r)' % (leaves,))
+    return int(leaves)
+
+
 def _uct_prior_kw(kw, shape, iterations, playouts):
-    """_prior_kw for batch_uct and the calls that forward to it (its ValueErrors before a device is touched).  shape: a
-    function -> (R, N), asked only when prior= or last_actions= is given."""
+    """_prior_kw for batch_uct and the calls that forward to it (its ValueErrors before a device is touched), leaves= and its
+    bounds checked first: with it every bound counts iterations * leaves leaves.  shape: a function -> (R, N), asked only when
+    prior= or last_actions= is given."""
+    L = _uct_leaves(kw.get('leaves'))
+    # batch_uct states this bound again where the capacity is known; here it stands in front of the first use of a device (uct and
+    # uct_actions box the state before batch_uct runs).  Counts that are no integers are _uct_args' and _playout_args' to refuse
+    if L is not None and _int_arg(iterations) and _int_arg(playouts):
+        jobs = int(iterations) * L * int(playouts) * (1 if kw.get('rave_equiv') is None else 2)
+        if jobs >= 2 ** 31:
+            raise ValueError('leaves=%d needs iterations * leaves * playouts < 2^31, with rave_equiv twice that (got %d)' % (L, jobs))
     if kw.get('prior') is None and kw.get('last_actions') is None:
         return None, None
-    return _prior_kw(kw, *shape(), iterations, playouts)
+    return _prior_kw(kw, *shape(), int(iterations) * (L or 1), playouts)
 
 
-def _run_uct(roots, R, N, I, K, c, max_plies, komi, seed, first_root, S, chunk_plies, dev, policy=0, rave=None, prior=None):
+def _run_uct(roots, R, N, I, K, c, max_plies, komi, seed, first_root, S, chunk_plies, dev, policy=0, rave=None, prior=None,
+             leaves=None):
     """Device work of batch_uct on tracked roots -> (child int32 [R, I+1, A], links [R, I+1, 2], stats [R, I+1, 4],
     nodes [R], totals int64 [R, 2]); no launch for R = 0.  rave: None (the plain search, through the plain entry points) or
     (rave_equiv, fpu) - then a sixth result, node_amaf int32 [R, I+1, N^2, 2].  prior (with rave only): None - not one launch
     more - or (weights int32 [12], last_actions int32 [R] or None) on the device: gg_uct_prior_begin seeds the roots,
-    gg_uct_prior_expand every new node once its board has been played."""
+    gg_uct_prior_expand every new node once its board has been played.
+    leaves: None - everything above, not one launch different - or L >= 1: I rounds of L slots per root through the _leaves
+    entry points of include/gymgo_amd_uct_leaves.h.  The same loop on R L rows: the trees have I L + 1 nodes where they had
+    I + 1, leaf / move / leaf_id and the playout buffers have R L rows, virt int32 [R, I L + 1] is added."""
+    L = 1 if leaves is None else leaves
+    rounds, rows, I = I, R * L, I * L          # from here on I is the capacity of a tree, as the entry points take it
     W, A, NN = tracked_words(N), N * N + 1, I + 1
     boards = torch.empty((R, NN, W), dtype=_I32, device=dev)
     child = torch.empty((R, NN, A), dtype=_I32, device=dev)
@@ -2266,37 +2289,44 @@ def _run_uct(roots, R, N, I, K, c, max_plies, komi, seed, first_root, S, chunk_p
     res = (child, links, stats, nodes, totals) + ((node_amaf,) if rave is not None else ())
     if R == 0:
         return res
-    leaf = torch.empty((R, W), dtype=_I32, device=dev)
-    move = torch.empty(R, dtype=_I32, device=dev)
-    leaf_id = torch.empty(R, dtype=_I32, device=dev)
+    leaf = torch.empty((rows, W), dtype=_I32, device=dev)
+    move = torch.empty(rows, dtype=_I32, device=dev)
+    leaf_id = torch.empty(rows, dtype=_I32, device=dev)
     with np.errstate(divide='ignore'):   # (L[0] = -inf is never read: a node with children has n >= K)
         log_table = torch.from_numpy(np.log(np.arange(NN, dtype=np.float64) * K)).to(dev)
-    pbufs = _playout_buffers(R, S, N, dev)
+    pbufs = _playout_buffers(rows, S, N, dev)
     counts, sums = pbufs[5], pbufs[6]
     stream = _lib.current_raw_stream(dev)
     _lib.call('gg_uct_begin', roots, R, N, I, K, boards, child, links, stats, nodes, stream)
-    # the RAVE entry points take the plain ones' arguments with their own spliced in: rave_equiv and fpu, node_amaf, the AMAF counts
+    # the RAVE entry points take the plain ones' arguments with their own spliced in: rave_equiv and fpu, node_amaf, the AMAF counts;
+    # the _leaves entry points take either's with L behind I and virt behind the tree's buffers
     abufs, sfx, kf, na, am = None, '', (), (), ()
     if rave is not None:
-        abufs = _amaf_buffers(R, S, N, chunk_plies, dev)
+        abufs = _amaf_buffers(rows, S, N, chunk_plies, dev)
         sfx, kf, na, am = '_rave', (float(rave[0]), float(rave[1])), (node_amaf,), (abufs[3],)
-    select = ('gg_uct_select' + sfx, R, N, I, K, c, *kf, log_table, boards, child, links, stats, *na, nodes, leaf, move, leaf_id, stream)
-    backup = ('gg_uct_backup' + sfx, R, N, I, K, counts, sums, *am, totals, boards, links, stats, *na, leaf, move, leaf_id, stream)
+    lf, lv, vt = '', (), ()
+    if leaves is not None:
+        lf, lv, vt = '_leaves', (L,), (torch.zeros((R, NN), dtype=_I32, device=dev),)
+    select = ('gg_uct_select' + lf + sfx, R, N, I, *lv, K, c, *kf, log_table, boards, child, links, stats, *na, nodes, *vt, leaf, move,
+              leaf_id, stream)
+    backup = ('gg_uct_backup' + lf + sfx, R, N, I, *lv, K, counts, sums, *am, totals, boards, links, stats, *na, *vt, leaf, move,
+              leaf_id, stream)
     if prior is not None:
         _lib.call('gg_uct_prior_begin', roots, prior[1], R, N, I, prior[0], node_amaf, stream)
-    for i in range(I):
+    for i in range(rounds):
         _lib.call(*select)
-        _lib.call('gg_batch_play_moves_tracked', leaf, move, None, R, N, 1, stream)
+        _lib.call('gg_batch_play_moves_tracked', leaf, move, None, rows, N, 1, stream)
         if prior is not None:
-            _lib.call('gg_uct_prior_expand', R, N, I, prior[0], leaf, move, leaf_id, node_amaf, stream)
-        _run_playouts(leaf, R, N, K, max_plies, komi, _uct_seed(seed, i), first_root, False, S, chunk_plies, dev, pbufs, policy,
+            _lib.call('gg_uct_prior_expand' + lf, R, N, I, *lv, prior[0], leaf, move, leaf_id, node_amaf, stream)
+        _run_playouts(leaf, rows, N, K, max_plies, komi, _uct_seed(seed, i), first_root * L, False, S, chunk_plies, dev, pbufs, policy,
                       amaf=abufs)
         _lib.call(*backup)
     return res
 
 
 def batch_uct(batch_states, iterations, playouts, c=math.sqrt(2), max_plies=None, komi=0.0, seed=20260927, first_root=0,
-              slots=None, chunk_plies=32, tree=False, *, policy='uniform', rave_equiv=None, fpu=1.0, prior=None, last_actions=None):
+              slots=None, chunk_plies=32, tree=False, *, policy='uniform', rave_equiv=None, fpu=1.0, prior=None, last_actions=None,
+              leaves=None):
     """UCT search of `iterations` iterations from every root of batch_states ([R, 6, N, N]), the leaves evaluated with
     `playouts` playouts each -> Uct (device tensors for a device tensor, NumPy arrays for NumPy input).
 
@@ -2335,26 +2365,44 @@ def batch_uct(batch_states, iterations, playouts, c=math.sqrt(2), max_plies=None
     points, and a move into the mover's own eye after them; no memory is added and the select and the backup are the same
     kernels.  The pass has no pair - there is no slot for it -, its value stays q or fpu: a caller who seeds every point at 0.5
     will usually want fpu at or below that.  rave_visits and rave_score of the result, and node_amaf of its tree, then include
-    the prior.  The search needs 2 * (iterations * playouts + the visits of the six pairs) < 2^31."""
+    the prior.  The search needs 2 * (iterations * playouts + the visits of the six pairs) < 2^31.
+
+    leaves: None - everything above, not one launch different - or an integer L >= 1 (1 included): `iterations` ROUNDS that hand
+    out up to L leaves per root each (include/gymgo_amd_uct_leaves.h holds the rule; plain, RAVE and RAVE with priors).  The
+    slots of a root are chosen one after the other under VIRTUAL LOSS: a node counts v more visits of `playouts` lost playouts
+    each for the v leaves of this round that went through it - in the denominator of a child's U and in the argument of the
+    parent's logarithm, never in the wins.  A walk that reaches a node made earlier in the same round - it has no board yet -
+    is a collision: that slot and the later slots of the root stay empty.  The R * L rows are evaluated together by exactly
+    batch_playouts(rows, playouts, max_plies, komi, seed=s_t, first_root=first_root * L) for round t (empty rows too: they are
+    evaluated and ignored) and backed up in slot order.  So leaves=1 gives the trees of leaves=None bit for bit, root_visits is
+    playouts times the non-empty slots, and the results keep their fields with iterations * L + 1 nodes per tree (the tree
+    fields are [R, iterations * L + 1]).  The bounds above hold with iterations * L for iterations.  Device memory: the tree
+    with iterations * L + 1 nodes per root plus 4 bytes a node for the virtual visits, the playout slots for R * L roots, and
+    under RAVE the playouts' AMAF buffer of R * L rows (24 N^2 bytes each)."""
     pol = _policy_kw({'policy': policy, 'rave_equiv': rave_equiv})
-    pr, la = _uct_prior_kw({'prior': prior, 'last_actions': last_actions, 'rave_equiv': rave_equiv},
+    pr, la = _uct_prior_kw({'prior': prior, 'last_actions': last_actions, 'rave_equiv': rave_equiv, 'leaves': leaves},
                            lambda: _states_shape(batch_states), iterations, playouts)
+    L = None if leaves is None else int(leaves)     # (_uct_prior_kw has validated it)
     box = _Box(batch_states)
     st = box.t
     R, N, K, max_plies, chunk_plies = _playout_args(st, playouts, max_plies, chunk_plies, first_root)
     I, c = _uct_args(iterations, K, c)
+    C = I * (L or 1)     # the leaves a root can get: what the bounds count
+    if C * K >= 2 ** 31:
+        raise ValueError('need iterations * leaves * playouts < 2^31 (got %d)' % (C * K))
     rave = None
     if rave_equiv is not None:
         rave = (float(rave_equiv), float(fpu))
-        if not (math.isfinite(rave[0]) and rave[0] > 0 and math.isfinite(rave[1])) or 2 * I * K >= 2 ** 31 or chunk_plies > 4096:
-            raise ValueError('RAVE needs rave_equiv > 0 and finite, fpu finite, 2 * iterations * playouts < 2^31 and chunk_plies '
-                             '<= 4096 (got %r, %r, %d, %d)' % (rave_equiv, fpu, 2 * I * K, chunk_plies))
-    S = max(1, min(int(_default_slots(slots)), R * K))
+        if not (math.isfinite(rave[0]) and rave[0] > 0 and math.isfinite(rave[1])) or 2 * C * K >= 2 ** 31 or chunk_plies > 4096:
+            raise ValueError('RAVE needs rave_equiv > 0 and finite, fpu finite, 2 * iterations * playouts < 2^31 (with leaves: '
+                             'times leaves) and chunk_plies <= 4096 (got %r, %r, %d, %d)' % (rave_equiv, fpu, 2 * C * K, chunk_plies))
+    S = max(1, min(int(_default_slots(slots)), R * (L or 1) * K))
     child, links, stats, nodes, totals, *more = _run_uct(_track_roots(st), R, N, I, K, c, max_plies, komi, seed, first_root, S,
                                                          chunk_plies, st.device, policy=pol, rave=rave,
                                                          prior=None if pr is None or R == 0 else (
                                                              _prior_weights(pr, st.device),
-                                                             None if la is None else torch.from_numpy(la).to(st.device)))
+                                                             None if la is None else torch.from_numpy(la).to(st.device)),
+                                                         **({} if L is None else {'leaves': L}))
     rc = child[:, 0, :]
     kid = torch.gather(stats, 1, rc.clamp(min=0).long()[..., None].expand(R, N * N + 1, 4))
     kid = torch.where((rc >= 0)[..., None], kid, torch.zeros_like(kid))
