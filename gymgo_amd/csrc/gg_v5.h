@@ -254,7 +254,7 @@ static __device__ unsigned long long gg_sweeps5[10];
 //   wave-ply (1: the compiler keeps two copies of the rows' last loop behind a scalar test and a branch);
 // GG_AB_DRAWADD1 1 (shipped): the pre-mix counter of the draw is a running 64-bit value that starts at x0 + t5 c and is advanced by 2 c behind each
 //   mix (one add-with-carry pair), 0: x0 + (t + t5) c by a 32 x 64 multiply every second ply.
-// (The round's fourth part, no row copy of M between the atari-join's branch and the mask rule, was not built: docs/history/r32.md.)
+// (The round's fourth part, no row copy of M between the atari-join's branch and the mask rule, was built in round 35: GG_AB_MINPLACE1.)
 #ifndef GG_AB_VALID1
 #define GG_AB_VALID1 1
 #endif
@@ -264,12 +264,51 @@ static __device__ unsigned long long gg_sweeps5[10];
 #ifndef GG_AB_DRAWADD1
 #define GG_AB_DRAWADD1 1
 #endif
+// A/B switches of round 35, leftover copies and recomputed rows of the 19x19 ply (gg_v5_kernel.h, job_liberties / flood_jobs below;
+// docs/history/r35.md; all at 0 = round 32's code, line for line).  All are in force at 19x19 only: 13x13 and 9x9 keep round 20's machine
+// code.  Shipped: EMPTY1 and MINPLACE1 together, +1.2 % and +1.5 % on the headline launch in two alternations, every run above every run of
+// the parent; each alone +0.6 % on the medians, inside the parent's spread; DESC1 and DRAWC1 on top of the pair LOWER its median both
+// times (-0.3 % to -0.7 %) and stay 0.
+// GG_AB_EMPTY1 1 (shipped): the job set-up of phase 2b overwrites ot[r] - the other colour's rows, which nothing inside flood_jobs uses but
+//   the liberties - with the EMPTY row FULLROW & ~(ot[r] | m[r]), and job_liberties takes that array as it is: nineteen v_bitop3 fewer in
+//   every liberties pass of a batch after its first, none more on the straight path (the set-up pays what the first pass loses), the same
+//   registers, 0: every pass forms the empty rows again;
+// GG_AB_MINPLACE1 1 (shipped): the atari-join of phase 3 leaves M alone - its fill (the seeds when no trip is run, zero on a wave-ply
+//   without a capture) is a row set of its own that the mask rule ORs in, in the same two v_bitop3 a row: u = (M | fill) & ~all4, then
+//   G | u or u & ~G by gsel (the fill lies inside the mover's stones outside M and G) - so M is the same registers on every path to the
+//   rule: the ten v_mov_b32 that copied it in front of the join's wave-uniform branch and the ten v_or_b32 behind its loop are gone,
+//   0: the fill is ORed into M behind the loop;
+// GG_AB_DESC1 1: a job descriptor carries its board's row offset, board * RS (<= 620), in bits 21-30 - the board lane holds the word
+//   as a kept constant - and the job lane reaches the stone planes, the plane of M and the G blocks by a shift (a lane without a job
+//   reads the zero descriptor of the absent job, not the dump slot's), 0 (shipped): by board * RS again (three v_mul_u32_u24 in the
+//   set-up and a v_mad_u32_u24 in the hand-over);
+// GG_AB_DRAWC1 1 (needs GG_AB_DRAWADD1): the running draw counter starts one c further on, at x0 + (t5 + 1) c, and the mix takes it as
+//   it is, 0 (shipped): the mix adds c to a copy (one add-with-carry pair every second ply).
+#ifndef GG_AB_EMPTY1
+#define GG_AB_EMPTY1 1
+#endif
+#ifndef GG_AB_MINPLACE1
+#define GG_AB_MINPLACE1 1
+#endif
+#ifndef GG_AB_DESC1
+#define GG_AB_DESC1 0
+#endif
+#ifndef GG_AB_DRAWC1
+#define GG_AB_DRAWC1 0
+#endif
 #if GG_AB_BALLOT1
 // (used where a board size R is in scope; 13x13 and 9x9 keep __ballot and with it round 20's machine code)
 #define GG_BALLOT5(p) (R == 19 ? (unsigned long long)__builtin_amdgcn_ballot_w64(p) : __ballot(p))
 #else
 #define GG_BALLOT5(p) __ballot(p)
 #endif
+
+// the mix of splitmix_next (gg_common.h) alone, for a counter that is advanced already (-DGG_AB_DRAWC1=1)
+__device__ __forceinline__ uint64_t splitmix_mix(uint64_t z) {
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
 
 // liberties (dilate & empty) of the group gt[], SATURATED: min(count, 2) - all any caller uses; m[] = the rows of its colour,
 // ot[] = the other colour's rows (read from LDS together with m[], BEFORE the flood: read behind it they cost the lane a round
@@ -280,12 +319,13 @@ static __device__ unsigned long long gg_sweeps5[10];
 // v_or3_b32 and one v_add3_u32 take in two rows each.  Three chains over the row pairs p % 3 (for an odd R row 0 starts chain 0
 // for nothing), joined by one v_or3 / v_add3.  (Round 8 kept o and the doubly-set columns, one v_bitop3 a row each: six a row
 // and a majority to join the chains; counting took nineteen v_bcnt.)
-template <int R>
+// (EMPTY, -DGG_AB_EMPTY1=1 at 19x19: ot[] holds the EMPTY rows of the board already, formed once by the job set-up, and m[] is not read)
+template <int R, bool EMPTY = false>
 __device__ __forceinline__ uint32_t job_liberties(const uint32_t (&gt)[R], const uint32_t (&ot)[R], const uint32_t (&m)[R]) {
   constexpr uint32_t FULLROW = (1u << R) - 1u;
   static_assert(R < 27, "the sum of R rows below 2^R stays inside 32 bits");
   auto row = [&](int r) -> uint32_t {
-    const uint32_t e = B3(ot[r], m[r], FULLROW, ~(TA | TB) & TC & 0xFF);   // empty points
+    const uint32_t e = EMPTY ? ot[r] : B3(ot[r], m[r], FULLROW, ~(TA | TB) & TC & 0xFF);   // empty points
     const uint32_t up = r > 0 ? gt[r - 1] : 0u, dn = r + 1 < R ? gt[r + 1] : 0u;
     const uint32_t dd = B3(shl1(gt[r]), gt[r] >> 1, up, T_OR3);
     return B3(dd, dn, e, (TA | TB) & TC);
@@ -398,6 +438,7 @@ __device__ __forceinline__ uint32_t flood_jobs(const uint32_t (&m)[R], const uin
                                                const uint32_t (&ot)[R], const uint32_t (&mm)[R], bool isG, bool have) {
   constexpr int K = flood_first_test<R>();
   static_assert(K >= 1 && K <= 3, "the first closure test comes after one, two or three sweeps");
+  constexpr bool EMPTY = GG_AB_EMPTY1 != 0 && R == 19;   // (ot[] = the empty rows of the board: the set-up of phase 2b, gg_v5_kernel.h)
   uint32_t cnt = 0;
   bool resumed = false;   // (wave-uniform) the G lanes are weakly closed: every test from here on is followed by the liberties
 #ifdef GG_AB_SWEEPS
@@ -417,12 +458,12 @@ __device__ __forceinline__ uint32_t flood_jobs(const uint32_t (&m)[R], const uin
   auto done = [&](uint32_t op, uint32_t opw) -> bool {
 #if GG_AB_BALLOT1
     if (!resumed && GG_BALLOT5((opw & gm) != 0u) != 0) return false;
-    cnt = job_liberties<R>(res, ot, m);
+    cnt = job_liberties<R, EMPTY>(res, ot, m);
     // (cnt <= 2: cnt - 2 is negative iff cnt < 2)
     const bool unsettled = B3(op, hm, (uint32_t)((int32_t)(cnt - 2u) >> 31), TA & TB & TC) != 0u;
 #else
     if (!resumed && GG_BALLOT5(opw != 0u && isG) != 0) return false;
-    cnt = job_liberties<R>(res, ot, m);
+    cnt = job_liberties<R, EMPTY>(res, ot, m);
     const bool unsettled = have && op != 0u && cnt < 2u;
 #endif
     const uint64_t u = GG_BALLOT5(unsettled);
@@ -579,7 +620,7 @@ static __device__ unsigned long long gg_lsplit[4];
 #endif
 
 // job descriptor: bits 0-4 board, 5-14 the seed ((row << 5) | column; -DGG_AB_MOVE_RC=0: 5-13, the flat point index), 15 the colour flooded, 16 the job floods G, 18 the job exists,
-// 19-20 the direction of q's neighbour it starts from (0 up, 1 down, 2 left, 3 right)
+// 19-20 the direction of q's neighbour it starts from (0 up, 1 down, 2 left, 3 right); (-DGG_AB_DESC1=1, 19x19) 21-30 board * RS
 // info word of a board (cleared in phase 1, ORed by its jobs): bits 0-3 the directions whose opponent group was captured, 4-5 the
 // liberties of G (saturated at 2)
 // the kernel, once per playout policy of its draw (gg_v5_kernel.h)

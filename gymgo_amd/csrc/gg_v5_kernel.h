@@ -243,6 +243,9 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
     // the slot of an absent job: an all-zero block and class word (the loop area was the load's scratch)
     WAVE_SYNC();
     for (int i = hf.lane; i < kWave * RS; i += kWave) sc[i] = 0u;   // the seed blocks: all zero between two uses
+    // (-DGG_AB_DESC1=1, 19x19: a lane without a job reads the descriptor of the absent job - board 0, row offset 0 - and not the dump
+    // slot's, whose high bits hold whatever seed off the board was dumped last: its row offset must be one of a board)
+    if (GG_AB_DESC1 != 0 && R == 19 && hf.lane == 0) jobv[ZERO] = 0u;
     if constexpr (MPLANE) {
       // the plane of M (gg_v5.h: GG_AB_MPLANE1): every pair of lanes stores the rows the load left it - from the tracked board, from the
       // workspace or from the from-scratch analysis, zero for an absent board - now that the load is done with the loop area
@@ -282,7 +285,10 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
     // (-DGG_AB_DRAWADD1=1, 19x19) the draw's counter before the mix, x0 + (t + t5) c at the even ply t: a running value, advanced by 2 c
     // behind each mix, instead of a 32 x 64 multiply every second ply (gg_v5.h)
     constexpr bool DADD = GG_AB_DRAWADD1 != 0 && R == 19;
-    uint64_t xdr = x0r + (uint64_t)(uint32_t)(ln0 & 1) * 0x9E3779B97F4A7C15ull;   // (dead code without DADD)
+    // (-DGG_AB_DRAWC1=1 on top of it: the counter starts one c further on, x0 + (t + t5 + 1) c, which is what the mix takes in - no + c
+    // on a copy every second ply)
+    constexpr bool DRAWC = DADD && GG_AB_DRAWC1 != 0;
+    uint64_t xdr = x0r + (uint64_t)(uint32_t)((ln0 & 1) + (DRAWC ? 1 : 0)) * 0x9E3779B97F4A7C15ull;   // (dead code without DADD)
 #if GG_AB_LANE1
     // what depends on the lane number alone, formed ONCE and kept in registers through the plies (gg_v5.h: GG_AB_LANE1) - at 19x19,
     // where two waves per SIMD leave ~70 VGPRs free; 13x13 and 9x9 stand at 168 and 127 of the 170 and 128 VGPRs their three and four
@@ -298,6 +304,12 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
     uint32_t *const metaK = flagsv + s4K;       // the board's flag word; last action and played plies kNB5 and 2 kNB5 words behind
     uint32_t *const blkK = sc + lnK * RS;       // the seed block of this lane's job
 #endif
+    // (-DGG_AB_DESC1=1, 19x19) what the board's lanes put into every job descriptor they post: the board in bits 0-4 and its row offset
+    // board * RS in bits 21-30, one kept word (gg_v5.h); the job lane takes the offset out by one shift
+    constexpr bool DESC = GG_AB_DESC1 != 0 && R == 19;
+    static_assert((kNB5 - 1) * RS < 1024, "the row offset of a board fits bits 21-30 of a job descriptor");
+    uint32_t descK = (uint32_t)((ln0 >> 1) & 31) | ((uint32_t)(((ln0 >> 1) & 31) * RS) << 21);   // (dead code without DESC)
+    if constexpr (DESC) asm volatile("" : "+v"(descK));   // (kept as it is: not put together again every ply)
 #pragma unroll 1
     for (int t = 0; t < plies; ++t) {
       // Fair share of the SIMD (gg_common.h) every fourth ply - without it the older of a SIMD's two waves runs ahead and the
@@ -497,7 +509,7 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
         // the pair swaps
         if ((t & 1) == 0) {
           uint64_t xx = DADD ? xdr : x0r + (uint64_t)(uint32_t)(t + t5) * 0x9E3779B97F4A7C15ull;
-          uq = (uint32_t)(splitmix_next(xx) >> 32);
+          uq = (uint32_t)((DRAWC ? splitmix_mix(xx) : splitmix_next(xx)) >> 32);
           if constexpr (DADD) xdr += 2ull * 0x9E3779B97F4A7C15ull;
         }
         const uint32_t uh = dpp0<QP_L0>(uq);
@@ -645,7 +657,8 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
         const uint32_t base = mbcnt64(b0) + 2u * mbcnt64(b1);
         njobs = (int)__popcll(b0) + 2 * (int)__popcll(b1);
         const uint32_t sG = base, s0 = base + gf, s1 = s0 + obit[0];
-        const uint32_t common = (uint32_t)s4 | (1u << 18) | ((turn ^ 1u) << 15);
+        const uint32_t dsb = DESC ? descK : (uint32_t)s4;   // the board (DESC: and its row offset in bits 21-30)
+        const uint32_t common = dsb | (1u << 18) | ((turn ^ 1u) << 15);
 #if GG_AB_MOVE_RC
         // (the seed travels as (row << 5) | column in bits 5-14: q itself for G, q -+ 32 / q -+ 1 for the opponent stone above / below /
         // left / right - a job that is posted has its seed on the board, the others go to the dump slot)
@@ -656,7 +669,7 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
         const int step = t5 ? 1 : N;
         const int sd = a;
 #endif
-        jobv[gf ? sG : (uint32_t)DUMP] = ((uint32_t)s4 | (1u << 18) | (turn << 15) | (1u << 16)) | ((uint32_t)sd << 5);
+        jobv[gf ? sG : (uint32_t)DUMP] = (dsb | (1u << 18) | (turn << 15) | (1u << 16)) | ((uint32_t)sd << 5);
         const uint32_t dirs = (uint32_t)t5 << 20;   // bits 19-20: the direction of the job (0 up, 1 down, 2 left, 3 right)
         jobv[obit[0] ? s0 : (uint32_t)DUMP] = common | dirs | ((uint32_t)(sd - step) << 5);
         jobv[obit[1] ? s1 : (uint32_t)DUMP] = common | dirs | (1u << 19) | ((uint32_t)(sd + step) << 5);
@@ -672,9 +685,16 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
       for (int jb = 0; jb < njobs; jb += kWave) {
         const int j = jb + ln;
         const bool have = j < njobs;
-        const uint32_t d = jobv[have ? j : DUMP];
+        const uint32_t d = jobv[have ? j : (DESC ? ZERO : DUMP)];
         const uint32_t ex = have ? 1u : 0u;
         const int sj = (int)(d & 31u);
+#if GG_AB_DESC1
+        // the row offset of the job's board: (DESC) bits 21-30 of the descriptor, bit 31 is never set in a posted one
+        const int sjr = DESC ? (int)(d >> 21) : sj * RS;
+#define GG_SJR sjr
+#else
+#define GG_SJR (sj * RS)
+#endif
         int sr, scol;
 #if GG_AB_MOVE_RC
         sr = (int)((d >> 10) & 31u);
@@ -690,12 +710,16 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
         uint32_t *blk = sc + ln * RS;   // this lane's seed block (all zero)
 #endif
         const uint4 *lds4 = reinterpret_cast<const uint4 *>(lds);
-        const uint4 *pmv = lds4 + (Lds5<R>::kState + (int)ownc * PL + sj * RS) / 4;
-        const uint4 *pov = lds4 + (Lds5<R>::kState + (int)(ownc ^ 1u) * PL + sj * RS) / 4;
+        // (DESC: word offsets, not a quotient - the row offset out of the descriptor is a multiple of four the compiler cannot see, and the
+        // division costs a mask per address)
+        const uint4 *pmv = DESC ? reinterpret_cast<const uint4 *>(lds + Lds5<R>::kState + (int)ownc * PL + GG_SJR)
+                                : lds4 + (Lds5<R>::kState + (int)ownc * PL + sj * RS) / 4;
+        const uint4 *pov = DESC ? reinterpret_cast<const uint4 *>(lds + Lds5<R>::kState + (int)(ownc ^ 1u) * PL + GG_SJR)
+                                : lds4 + (Lds5<R>::kState + (int)(ownc ^ 1u) * PL + sj * RS) / 4;
         // the rows of M (the classes BEFORE this move) of the job's board, out of the registers of the two lanes that hold them
         // (-DGG_AB_MPLANE1=1, 19x19: out of the plane of M instead, below with the stone rows - the plane holds what the registers
         // hold, phase 3 of the last ply, the load or the reset path stored it, and M does not change between phase 1 and phase 3)
-        const uint4 *pmmv = lds4 + (Lds5<R>::kMpl + sj * RS) / 4;
+        const uint4 *pmmv = DESC ? reinterpret_cast<const uint4 *>(lds + Lds5<R>::kMpl + GG_SJR) : lds4 + (Lds5<R>::kMpl + sj * RS) / 4;
         uint32_t mm[R];
         if constexpr (!MPLANE) {
           const int src = 8 * sj;   // byte address of lane 2 sj for ds_bpermute
@@ -749,6 +773,8 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
               mrev[r] = __brev(m[r]);
               f[r] = ft[r];
               res[r] = 0u;
+              // (-DGG_AB_EMPTY1=1, 19x19: ot[] has no use inside flood_jobs but the liberties' empty rows - formed here, once per batch)
+              if constexpr (GG_AB_EMPTY1 != 0 && R == 19) ot[r] = B3(ot[r], m[r], FULLROW, ~(TA | TB) & TC & 0xFF);
             }
           }
 #ifdef GG_AB_MCHECK
@@ -804,7 +830,8 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
         const uint32_t lib2 = cnt < 2u ? cnt : 2u;
         // G goes to its board's G block (over the stone phase 1 left there); an opponent group with no liberty left
         // (captured) or with one (it leaves M) is ORed into the board's collection block - one that keeps >= 2 is dropped
-        uint32_t *gb = gblk + 2 * sj * RS;
+        uint32_t *gb = DESC ? gblk + 2 * GG_SJR : gblk + 2 * sj * RS;
+#undef GG_SJR
 #if GG_AB_HAND1
         // ONE path for both: a lane that hands a group over ORs its rows into the block its address chooses, gb for G, gb + RS for a
         // collected opponent group, and one word into the board's info word.  The OR is exact for G too: phase 1 cleared both blocks
@@ -903,9 +930,15 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
         // The collection block holds the opponent groups next to q with NO liberty left (captured: q was their only liberty, so
         // they were never in M) or with exactly ONE (they had q and one more: they were in M).  So it splits by M alone:
         // captured = all4 & ~M, leaving M = all4 & M.  (all4 holds opponent stones only.)
+#if GG_AB_MINPLACE1
+        uint32_t fj[RPL];
+#endif
         uint32_t g0[RPL], opp1[RPL];
 #pragma unroll
         for (int r = 0; r < RPL; ++r) {
+#if GG_AB_MINPLACE1
+          fj[r] = 0u;
+#endif
           g0[r] = bg[r];   // the G block: the flood of G, the stone alone as phase 1 left it there, or nothing (pass / idle board)
           opp1[r] = B3(opp0[r], all4[r], M[r], TA & ~(TB & ~TC) & 0xFF);   // opp0 & ~cap: the opponent's stones after the captures
         }
@@ -917,6 +950,9 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
         GG_P3(0, 1u);
         GG_P3(8, (uint32_t)__popcll(GG_BALLOT5(capt_m != 0u && t5 == 0)));
         GG_P3(9, (uint32_t)__popcll(GG_BALLOT5(a >= 0 && t5 == 0)));
+        // (-DGG_AB_MINPLACE1=1, 19x19) the atari-join does not touch M: its fill - the seeds when no trip is run, all zero on a wave-ply
+        // without a capture - is a row set of its own that the mask rule ORs in, so that M is the same registers on every path to the rule
+        constexpr bool MINPL = GG_AB_MINPLACE1 != 0 && R == 19;
         GG_MARK(10);
         if (GG_BALLOT5(capt_m != 0u)) {   // a capture on some board of the wave
           GG_MARK(11);
@@ -1035,10 +1071,18 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
             GG_P3(6, trips_);
             p3c_[7] = trips_ > p3c_[7] ? trips_ : p3c_[7];
 #endif
+            if constexpr (!MINPL) {
 #pragma unroll
-            for (int r = 0; r < RPL; ++r) M[r] |= f[r];
+              for (int r = 0; r < RPL; ++r) M[r] |= f[r];
+            }
             GG_MARK(19);
           }
+#if GG_AB_MINPLACE1
+          if constexpr (MINPL) {   // (the fill as the join left it - the seeds when no trip was run - is what the mask rule ORs in)
+#pragma unroll
+            for (int r = 0; r < RPL; ++r) fj[r] = f[r];
+          }
+#endif
         }
         GG_MARK(20);
         // The mask rule.  The new M: the stones of M outside G and the collected groups (those left with one liberty leave M; a
@@ -1056,8 +1100,16 @@ __global__ __launch_bounds__(kWave, 2) void GG_R5_NAME(uint8_t *__restrict__ sta
         uint32_t e[RPL], x[RPL], nbr[RPL];
 #pragma unroll
         for (int r = 0; r < RPL; ++r) {
+          // (MINPL: (M | fill) & ~all4, then G | u or u & ~G by gsel - the fill lies inside the mover's stones outside M and G, so this is
+          // the rule below with M | fill for M, in the same two v_bitop3)
+#if GG_AB_MINPLACE1
+          const uint32_t u = MINPL ? B3(M[r], fj[r], all4[r], (TA | TB) & ~TC & 0xFF)
+                                   : B3(M[r], g0[r], all4[r], TA & ~(TB | TC) & 0xFF);   // M & ~G & ~all4
+          M[r] = MINPL ? B3(gsel, g0[r], u, ((TA & TB) | (~TB & TC)) & 0xFF) : B3(gsel, g0[r], u, T_ANDOR);   // the new M
+#else
           const uint32_t u = B3(M[r], g0[r], all4[r], TA & ~(TB | TC) & 0xFF);   // M & ~G & ~all4
           M[r] = B3(gsel, g0[r], u, T_ANDOR);                                      // the new M
+#endif
           const uint32_t y = B3(M[r], mine1[r], opp1[r], T_SEL);
           x[r] = B3(full[r], y, y, TA & ~TB & 0xFF);
           e[r] = B3(full[r], opp1[r], mine1[r], TA & ~(TB | TC) & 0xFF);
