@@ -260,7 +260,8 @@ ABI_STATUS = {
 }
 # ... and of include/gymgo_amd_uct_leaves.h, the UCT search with several leaves per root and round, in its order
 # (tests/test_uct_leaves_host.py holds it against its header): each call is its namesake's list with L behind I and - select and
-# backup - virt behind nodes / behind stats or node_amaf
+# backup - virt behind nodes / behind stats or node_amaf (and lands in its namesake's checked body and kernel, with L = 1 and no
+# virt from the namesake: gg_kernels.hip, gg_prior.hip)
 def _with_leaves(ps, virt_after=None):
     out = []
     for p in ps:

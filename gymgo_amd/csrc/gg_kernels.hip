@@ -4,7 +4,7 @@
 // sixteen boards per wavefront, liberty classes carried from ply to ply), gg_aux.h (stand-alone sampler and capture
 // resolution), gg_ws.h (policy-weighted sampling), gg_sym.h (batched symmetries), gg_ns16.h (the per-ply kernels for
 // big batches), gg_po.h (Monte Carlo playouts: the fill / harvest kernel of the playout queue and the plan of legal first
-// moves), gg_uct.h (UCT tree search: begin, select, backup) and gg_puct.h (PUCT tree search with priors and an outside
+// moves), gg_uct.h (UCT tree search: begin, select, backup, one or several leaves a round) and gg_puct.h (PUCT tree search with priors and an outside
 // evaluator: begin, select, backup).  The playout and search entry points launch the multi-ply
 // kernels through gg_batch_rollout_tracked - or, for the AMAF playouts and RAVE (include/gymgo_amd_amaf.h), through gg_batch_rollout_tracked_log -, whose
 // launches live in the other five rollout translation units (gg_rollout.hip, gg_lat.hip, gg_r5.hip, gg_lat_log.hip, gg_r5_log.hip).  Which kernel serves an entry point depends on the arguments only (board size, batch size, plies per
@@ -40,6 +40,7 @@
 #include "gymgo_amd_tactics.h"
 #include "gymgo_amd_amaf.h"
 #include "gymgo_amd_pattern.h"
+#include "gymgo_amd_uct_leaves.h"
 
 namespace {
 
@@ -481,16 +482,18 @@ static int32_t po_advance_policy(int32_t max_policy, int32_t *last, int32_t N, i
 // ---- UCT tree search (gg_uct.h): the checks of po_args on the tree's sizes, in the same order, then the fill; the entry
 // points check their own pointers (uct_select / uct_backup below).  UctArgs serves three kernels and each of these members is
 // written by one of them, so they are not const there: gg_uct_select only reads boards, gg_uct_backup only reads links, leaf,
-// move and leaf_id and takes them as const - the casts below.
-static int32_t uct_args(UctArgs &u, int64_t R, int32_t N, int32_t I, int32_t K, double c, const uint32_t *boards, int32_t *child,
-                        const int32_t *links, int32_t *stats, int32_t *nodes, const uint32_t *leaf, const int32_t *move,
-                        const int32_t *leaf_id, const double *log_table = nullptr, const int32_t *counts = nullptr,
-                        const int64_t *sums = nullptr, int64_t *totals = nullptr) {
+// move and leaf_id and takes them as const - the casts below.  L = the slots of a root and virt their path counts (the _leaves
+// entry points; 1 and null from the others): L beside the other arguments, the R L rows - an int64 - beside the other sizes.
+static int32_t uct_args(UctArgs &u, int64_t R, int32_t N, int32_t I, int32_t L, int32_t K, double c, int32_t *virt,
+                        const uint32_t *boards, int32_t *child, const int32_t *links, int32_t *stats, int32_t *nodes,
+                        const uint32_t *leaf, const int32_t *move, const int32_t *leaf_id, const double *log_table = nullptr,
+                        const int32_t *counts = nullptr, const int64_t *sums = nullptr, int64_t *totals = nullptr) {
   if (N < 2 || N > GG_MAX_BOARD || R < 0) return GG_E_BADSIZE;
-  if (I < 1 || K < 1 || !(c >= 0.0 && c <= __DBL_MAX__)) return GG_E_BADARG;
-  if ((int64_t)I * K > 0x7FFFFFFF) return GG_E_BADSIZE;   // the root's n = I K is an int32
+  if (I < 1 || K < 1 || !(c >= 0.0 && c <= __DBL_MAX__) || L < 1) return GG_E_BADARG;
+  if ((int64_t)I * K > 0x7FFFFFFF || R > INT64_MAX / L) return GG_E_BADSIZE;   // the root's n = I K is an int32
   u = UctArgs{const_cast<uint32_t *>(boards), child, const_cast<int32_t *>(links), stats, nodes, const_cast<uint32_t *>(leaf),
               const_cast<int32_t *>(move), const_cast<int32_t *>(leaf_id), log_table, counts, sums, totals, c, R, N, I, K};
+  u.virt = virt; u.L = L;
   return 0;
 }
 
@@ -529,31 +532,37 @@ static int32_t rave_args(UctArgs &u, int32_t I, int32_t K, double rave_equiv, do
   return 0;
 }
 
-// gg_uct_select[_rave] and gg_uct_backup[_rave]: one checked body each.  RAVE adds rave_args to the checks, its pointers
-// (node_amaf, amaf) to the null test and picks the kernel's instantiation; the plain entry points pass nothing for them.
-template <bool RAVE>
-static int32_t uct_select(int64_t R, int32_t N, int32_t I, int32_t K, double c, double rave_equiv, double fpu, const double *log_table,
-                          const uint32_t *boards, int32_t *child, int32_t *links, int32_t *stats, const int32_t *node_amaf,
-                          int32_t *nodes, uint32_t *leaf, int32_t *move, int32_t *leaf_id, void *hip_stream) {
+// gg_uct_select[_leaves][_rave] and gg_uct_backup[_leaves][_rave]: one checked body each.  RAVE adds rave_args to the checks, its
+// pointers (node_amaf, amaf) to the null test and picks the kernel's instantiation; the plain entry points pass nothing for them.
+// VL (the _leaves entry points) does the same with virt; the others pass L = 1 and no virt.
+template <bool RAVE, bool VL>
+static int32_t uct_select(int64_t R, int32_t N, int32_t I, int32_t L, int32_t K, double c, double rave_equiv, double fpu,
+                          const double *log_table, const uint32_t *boards, int32_t *child, int32_t *links, int32_t *stats,
+                          const int32_t *node_amaf, int32_t *nodes, int32_t *virt, uint32_t *leaf, int32_t *move, int32_t *leaf_id,
+                          void *hip_stream) {
   UctArgs u;
-  if (int32_t e = uct_args(u, R, N, I, K, c, boards, child, links, stats, nodes, leaf, move, leaf_id, log_table)) return e;
+  if (int32_t e = uct_args(u, R, N, I, L, K, c, virt, boards, child, links, stats, nodes, leaf, move, leaf_id, log_table)) return e;
   if (int32_t e = RAVE ? rave_args(u, I, K, rave_equiv, fpu, node_amaf, nullptr) : 0) return e;
-  if (!log_table || !boards || !child || !links || !stats || (RAVE && !node_amaf) || !nodes || !leaf || !move || !leaf_id) return GG_E_NULLPTR;
+  if (!log_table || !boards || !child || !links || !stats || (RAVE && !node_amaf) || !nodes || (VL && !virt) || !leaf || !move || !leaf_id)
+    return GG_E_NULLPTR;
   if (R == 0) return 0;
-  return launch_roots(k_uct_select<RAVE>, leaf, R, hip_stream, u);
+  return launch_roots(k_uct_select<RAVE, VL>, leaf, R, hip_stream, u);
 }
 
-template <bool RAVE>
-static int32_t uct_backup(int64_t R, int32_t N, int32_t I, int32_t K, const int32_t *counts, const int64_t *sums, const int32_t *amaf,
-                          int64_t *totals, uint32_t *boards, const int32_t *links, int32_t *stats, int32_t *node_amaf,
-                          const uint32_t *leaf, const int32_t *move, const int32_t *leaf_id, void *hip_stream) {
+template <bool RAVE, bool VL>
+static int32_t uct_backup(int64_t R, int32_t N, int32_t I, int32_t L, int32_t K, const int32_t *counts, const int64_t *sums,
+                          const int32_t *amaf, int64_t *totals, uint32_t *boards, const int32_t *links, int32_t *stats,
+                          int32_t *node_amaf, int32_t *virt, const uint32_t *leaf, const int32_t *move, const int32_t *leaf_id,
+                          void *hip_stream) {
   UctArgs u;
-  if (int32_t e = uct_args(u, R, N, I, K, 0.0, boards, nullptr, links, stats, nullptr, leaf, move, leaf_id, nullptr, counts, sums, totals))
+  if (int32_t e = uct_args(u, R, N, I, L, K, 0.0, virt, boards, nullptr, links, stats, nullptr, leaf, move, leaf_id, nullptr, counts, sums,
+                           totals))
     return e;
   if (int32_t e = RAVE ? rave_args(u, I, K, 1.0, 0.0, node_amaf, amaf) : 0) return e;
-  if (!counts || !sums || (RAVE && (!amaf || !node_amaf)) || !boards || !links || !stats || !leaf || !move || !leaf_id) return GG_E_NULLPTR;
+  if (!counts || !sums || (RAVE && (!amaf || !node_amaf)) || !boards || !links || !stats || (VL && !virt) || !leaf || !move || !leaf_id)
+    return GG_E_NULLPTR;
   if (R == 0) return 0;
-  return launch_roots(k_uct_backup<RAVE>, leaf, R, hip_stream, u);
+  return launch_roots(k_uct_backup<RAVE, VL>, leaf, R, hip_stream, u);
 }
 }  // namespace
 
@@ -1384,7 +1393,7 @@ int32_t gg_move_playouts_advance_policy3(const uint32_t *roots, int64_t R, int32
 int32_t gg_uct_begin(const uint32_t *roots, int64_t R, int32_t N, int32_t I, int32_t K, uint32_t *boards, int32_t *child,
                      int32_t *links, int32_t *stats, int32_t *nodes, void *hip_stream) {
   UctArgs u;
-  if (int32_t e = uct_args(u, R, N, I, K, 0.0, boards, child, links, stats, nodes, nullptr, nullptr, nullptr)) return e;
+  if (int32_t e = uct_args(u, R, N, I, 1, K, 0.0, nullptr, boards, child, links, stats, nodes, nullptr, nullptr, nullptr)) return e;
   if (!roots || !boards || !child || !links || !stats || !nodes) return GG_E_NULLPTR;
   if (R == 0) return 0;
   OnDeviceOf on_dev(boards);
@@ -1402,28 +1411,61 @@ int32_t gg_uct_begin(const uint32_t *roots, int64_t R, int32_t N, int32_t I, int
 int32_t gg_uct_select(int64_t R, int32_t N, int32_t I, int32_t K, double c, const double *log_table, const uint32_t *boards,
                       int32_t *child, int32_t *links, int32_t *stats, int32_t *nodes, uint32_t *leaf, int32_t *move,
                       int32_t *leaf_id, void *hip_stream) {
-  return uct_select<false>(R, N, I, K, c, 1.0, 0.0, log_table, boards, child, links, stats, nullptr, nodes, leaf, move, leaf_id, hip_stream);
+  return uct_select<false, false>(R, N, I, 1, K, c, 1.0, 0.0, log_table, boards, child, links, stats, nullptr, nodes, nullptr, leaf, move,
+                                  leaf_id, hip_stream);
 }
 
 int32_t gg_uct_backup(int64_t R, int32_t N, int32_t I, int32_t K, const int32_t *counts, const int64_t *sums, int64_t *totals,
                       uint32_t *boards, const int32_t *links, int32_t *stats, const uint32_t *leaf, const int32_t *move,
                       const int32_t *leaf_id, void *hip_stream) {
-  return uct_backup<false>(R, N, I, K, counts, sums, nullptr, totals, boards, links, stats, nullptr, leaf, move, leaf_id, hip_stream);
+  return uct_backup<false, false>(R, N, I, 1, K, counts, sums, nullptr, totals, boards, links, stats, nullptr, nullptr, leaf, move, leaf_id,
+                                  hip_stream);
 }
 
 int32_t gg_uct_select_rave(int64_t R, int32_t N, int32_t I, int32_t K, double c, double rave_equiv, double fpu,
                            const double *log_table, const uint32_t *boards, int32_t *child, int32_t *links, int32_t *stats,
                            const int32_t *node_amaf, int32_t *nodes, uint32_t *leaf, int32_t *move, int32_t *leaf_id,
                            void *hip_stream) {
-  return uct_select<true>(R, N, I, K, c, rave_equiv, fpu, log_table, boards, child, links, stats, node_amaf, nodes, leaf, move, leaf_id,
-                          hip_stream);
+  return uct_select<true, false>(R, N, I, 1, K, c, rave_equiv, fpu, log_table, boards, child, links, stats, node_amaf, nodes, nullptr, leaf,
+                                 move, leaf_id, hip_stream);
 }
 
 int32_t gg_uct_backup_rave(int64_t R, int32_t N, int32_t I, int32_t K, const int32_t *counts, const int64_t *sums,
                            const int32_t *amaf, int64_t *totals, uint32_t *boards, const int32_t *links, int32_t *stats,
                            int32_t *node_amaf, const uint32_t *leaf, const int32_t *move, const int32_t *leaf_id,
                            void *hip_stream) {
-  return uct_backup<true>(R, N, I, K, counts, sums, amaf, totals, boards, links, stats, node_amaf, leaf, move, leaf_id, hip_stream);
+  return uct_backup<true, false>(R, N, I, 1, K, counts, sums, amaf, totals, boards, links, stats, node_amaf, nullptr, leaf, move, leaf_id,
+                                 hip_stream);
+}
+
+int32_t gg_uct_select_leaves(int64_t R, int32_t N, int32_t I, int32_t L, int32_t K, double c, const double *log_table,
+                             const uint32_t *boards, int32_t *child, int32_t *links, int32_t *stats, int32_t *nodes, int32_t *virt,
+                             uint32_t *leaf, int32_t *move, int32_t *leaf_id, void *hip_stream) {
+  return uct_select<false, true>(R, N, I, L, K, c, 1.0, 0.0, log_table, boards, child, links, stats, nullptr, nodes, virt, leaf, move,
+                                 leaf_id, hip_stream);
+}
+
+int32_t gg_uct_backup_leaves(int64_t R, int32_t N, int32_t I, int32_t L, int32_t K, const int32_t *counts, const int64_t *sums,
+                             int64_t *totals, uint32_t *boards, const int32_t *links, int32_t *stats, int32_t *virt,
+                             const uint32_t *leaf, const int32_t *move, const int32_t *leaf_id, void *hip_stream) {
+  return uct_backup<false, true>(R, N, I, L, K, counts, sums, nullptr, totals, boards, links, stats, nullptr, virt, leaf, move, leaf_id,
+                                 hip_stream);
+}
+
+int32_t gg_uct_select_leaves_rave(int64_t R, int32_t N, int32_t I, int32_t L, int32_t K, double c, double rave_equiv, double fpu,
+                                  const double *log_table, const uint32_t *boards, int32_t *child, int32_t *links, int32_t *stats,
+                                  const int32_t *node_amaf, int32_t *nodes, int32_t *virt, uint32_t *leaf, int32_t *move,
+                                  int32_t *leaf_id, void *hip_stream) {
+  return uct_select<true, true>(R, N, I, L, K, c, rave_equiv, fpu, log_table, boards, child, links, stats, node_amaf, nodes, virt, leaf,
+                                move, leaf_id, hip_stream);
+}
+
+int32_t gg_uct_backup_leaves_rave(int64_t R, int32_t N, int32_t I, int32_t L, int32_t K, const int32_t *counts, const int64_t *sums,
+                                  const int32_t *amaf, int64_t *totals, uint32_t *boards, const int32_t *links, int32_t *stats,
+                                  int32_t *node_amaf, int32_t *virt, const uint32_t *leaf, const int32_t *move,
+                                  const int32_t *leaf_id, void *hip_stream) {
+  return uct_backup<true, true>(R, N, I, L, K, counts, sums, amaf, totals, boards, links, stats, node_amaf, virt, leaf, move, leaf_id,
+                                hip_stream);
 }
 
 int32_t gg_puct_begin(const uint32_t *roots, int64_t R, int32_t N, int32_t I, uint32_t *boards, int32_t *child, float *prior,

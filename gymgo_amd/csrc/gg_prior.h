@@ -1,5 +1,6 @@
 // gg_prior.h - THE MOVE PRIORS (gg_batch_move_priors, gg_batch_move_priors_tracked, gg_uct_prior_begin, gg_uct_prior_expand of
-// include/gymgo_amd_prior.h): per legal point of a board the pair (visits, 2 wins) of virtual simulations that the sets
+// include/gymgo_amd_prior.h, gg_uct_prior_expand_leaves of include/gymgo_amd_uct_leaves.h): per legal point of a
+// board the pair (visits, 2 wins) of virtual simulations that the sets
 // of the tactical and the pattern playout policy give it - C capture points, E escape points, P pattern points, L pattern points
 // next to the previous move, X the mover's own eyes -, stored per board or ADDED to the (n~, s~) pairs of a node of the RAVE tree.
 //
@@ -14,7 +15,8 @@
 // outside the destination is written, no atomics - a board belongs to one group of lanes of one wave.  The destination needs the
 // alignment of an int32 only.
 //   TREE = false: the boards of a wave are one contiguous slice of out [B][N^2][2]: ONE segment per wave, stored.
-//   TREE = true:  board r goes to node y of its tree, node_amaf + ((r (I + 1) + y) N^2) 2: one segment per board, added.
+//   TREE = true:  board b goes to node y of its tree t, node_amaf + ((t (I + 1) + y) N^2) 2: one segment per board, added.
+//                 t = b, or with VL (the L slots of a root and round) t = b / L.
 #pragma once
 #include "gg_feat.h"
 
@@ -62,10 +64,14 @@ __device__ __forceinline__ void prior_store(uint32_t *dst, const uint32_t *seg, 
 // in: byte planes or tracked boards of B boards; last int32 [B] or null: the previous action of every board; weights int32 [6][2].
 // TREE = false: out int32 [B][N^2][2].  TREE = true: out = node_amaf int32 [B][I + 1][N^2][2], node int32 [B] or null (node 0):
 // the node of every board's tree; a board whose node is outside [0, I] is skipped, and with need_move one whose last[b] < 0.
-template <int R, bool TRACKED, bool TREE>
+// VL (TREE only): out = node_amaf int32 [B / L][I + 1][N^2][2], board b seeds a node of tree b / L.  The boards of a tree that
+// are not skipped name different nodes - each is a node of its own, made in this round -, so no two boards add to the same words.
+// L is a template switch and not a plain divisor: b / L at run time costs the one-leaf tree form a 64-bit division.
+template <int R, bool TRACKED, bool TREE, bool VL = false>
 __global__ __launch_bounds__(kWave) void k_move_priors(const void *__restrict__ in, const int32_t *__restrict__ last,
                                                        const int32_t *__restrict__ weights, uint32_t *__restrict__ out,
-                                                       const int32_t *__restrict__ node, int need_move, int I, int64_t B, int N) {
+                                                       const int32_t *__restrict__ node, int need_move, int I, int64_t B, int N, int L) {
+  static_assert(TREE || !VL, "the slots of a round belong to trees");
   using Q = Prior<R>;
   constexpr int LPB = Q::LPB;
   __shared__ __attribute__((aligned(16))) uint32_t lds[Q::kLdsWords];
@@ -121,7 +127,7 @@ __global__ __launch_bounds__(kWave) void k_move_priors(const void *__restrict__ 
     if (TREE) {
       const int y = (node && f.on) ? node[b] : 0;
       go = f.on && y >= 0 && y <= I && !(need_move && la < 0);
-      dst = out + ((b * (int64_t)(I + 1) + (go ? y : 0)) * P) * 2;
+      dst = out + (((VL ? b / L : b) * (int64_t)(I + 1) + (go ? y : 0)) * P) * 2;
       so = f.j * Q::kSegWords;
     }
     const int mo = (int)(((uintptr_t)dst & 15u) >> 2);
@@ -147,7 +153,7 @@ __global__ __launch_bounds__(kWave) void k_move_priors(const void *__restrict__ 
         const int64_t bj = f.b_first + j;
         const int y = node ? node[bj] : 0;
         if (y < 0 || y > I || (need_move && last[bj] < 0)) continue;
-        uint32_t *dj = out + ((bj * (int64_t)(I + 1) + y) * P) * 2;
+        uint32_t *dj = out + (((VL ? bj / L : bj) * (int64_t)(I + 1) + y) * P) * 2;
         prior_store<true>(dj, lds + j * Q::kSegWords, (int)(((uintptr_t)dj & 15u) >> 2), 2 * P, f.lane);
       }
     } else {

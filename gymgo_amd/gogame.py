@@ -2299,7 +2299,8 @@ def _run_uct(roots, R, N, I, K, c, max_plies, komi, seed, first_root, S, chunk_p
     stream = _lib.current_raw_stream(dev)
     _lib.call('gg_uct_begin', roots, R, N, I, K, boards, child, links, stats, nodes, stream)
     # the RAVE entry points take the plain ones' arguments with their own spliced in: rave_equiv and fpu, node_amaf, the AMAF counts;
-    # the _leaves entry points take either's with L behind I and virt behind the tree's buffers
+    # the _leaves entry points take either's with L behind I and virt behind the tree's buffers (one kernel body serves both:
+    # gg_uct.h's, with its VL switch on behind the _leaves names)
     abufs, sfx, kf, na, am = None, '', (), (), ()
     if rave is not None:
         abufs = _amaf_buffers(rows, S, N, chunk_plies, dev)

@@ -16,7 +16,7 @@ extern "C" {
 #endif
 
 /*
- * THE RULE.  This text is normative: the kernels (gymgo_amd/csrc/gg_uct.h, gg_uct_leaves.h) and the host restatement
+ * THE RULE.  This text is normative: the kernels (gymgo_amd/csrc/gg_uct.h, gg_prior.h) and the host restatement
  * (tests/mc_uct_leaves_expect.py) both implement it.
  *
  * THE TREE.  R roots, T rounds, L >= 1 leaves per root and round.  A tree has C + 1 nodes, C = T L.  Every buffer of

@@ -2,7 +2,8 @@
 bit against tests/mc_uct_leaves_expect.py - batch_uct(leaves=L, tree=True) in all three modes (plain, RAVE, RAVE with priors) at
 every board size, ended nodes inside the tree, 64 slots, c in {0, sqrt 2, 1e6}, komi and first_root, shards, the playout queue's
 slots and chunks, leaves=1 against leaves=None down to the tree buffers, NumPy and the forwarding calls, the entry points on the
-test's own buffers (virt between select and backup, empty rows, a search past its capacity, sentinel tails), the five entry
+test's own buffers (virt between select and backup, empty rows, a search past its capacity, sentinel tails; the one-leaf entry
+points against the _leaves ones with L = 1 launch for launch), the five entry
 points between guards at every start residue, and one child process with the library sized for one compute unit (later trips of
 the grid-stride loops; the playout policies on both kernel families).  tests/test_uct_leaves_host.py holds the cases to their
 premises on the CPU."""
@@ -132,7 +133,10 @@ def test_komi_first_root_shards_slots_and_chunks(mode):
 
 @pytest.mark.parametrize('N', (2, 9, 19))
 def test_one_leaf_per_round_is_the_search_without_the_keyword(N):
-    """leaves=1 against leaves=None, down to the tree buffers of the host loop."""
+    """leaves=1 against leaves=None, down to the tree buffers of the host loop.  Both run ONE kernel body (gg_uct.h, gg_prior.h):
+    leaves=None its VL = false instantiations, leaves=1 the VL = true ones with L = 1 and every v = 0 where a score reads it.  What
+    this guards is the `if (VL)` switches of that body - a difference of the several-leaves mode that is not under its switch, or a
+    statement of the one-leaf mode that fell under one, shows here - not the agreement of two copies of the text."""
     from gymgo_amd import gogame
     roots = cs.stack(N, ('late0', 'mid0', 'empty', 'ended'))
     R, T, K, cap = len(roots), 12, 2, 64
@@ -224,22 +228,24 @@ def _tree_buffers(new, R, N, C, rows, rave):
     return b
 
 
-def _calls(b, R, N, C, L, K, c, mode, log_table, counts, sums, amaf, weights):
-    """The argument tuples of the round's calls on the buffers b -> (select, expand or None, backup)."""
+def _calls(b, R, N, C, L, K, c, mode, log_table, counts, sums, amaf, weights, one_leaf=False):
+    """The argument tuples of the round's calls on the buffers b -> (select, expand or None, backup): the _leaves entry points, or
+    with one_leaf their namesakes - the same lists without L and virt."""
     s = _stream()
+    lf, lv, vt = ('', (), ()) if one_leaf else ('_leaves', (L,), (b['virt'],))
     if mode == 'plain':
-        select = ('gg_uct_select_leaves', R, N, C, L, K, c, log_table, b['boards'], b['child'], b['links'], b['stats'], b['nodes'], b['virt'],
+        select = ('gg_uct_select' + lf, R, N, C, *lv, K, c, log_table, b['boards'], b['child'], b['links'], b['stats'], b['nodes'], *vt,
                   b['leaf'], b['move'], b['leaf_id'], s)
-        backup = ('gg_uct_backup_leaves', R, N, C, L, K, counts, sums, b['totals'], b['boards'], b['links'], b['stats'], b['virt'], b['leaf'],
+        backup = ('gg_uct_backup' + lf, R, N, C, *lv, K, counts, sums, b['totals'], b['boards'], b['links'], b['stats'], *vt, b['leaf'],
                   b['move'], b['leaf_id'], s)
         return select, None, backup
-    select = ('gg_uct_select_leaves_rave', R, N, C, L, K, c, ml.EQUIV, ml.FPU, log_table, b['boards'], b['child'], b['links'], b['stats'],
-              b['node_amaf'], b['nodes'], b['virt'], b['leaf'], b['move'], b['leaf_id'], s)
-    backup = ('gg_uct_backup_leaves_rave', R, N, C, L, K, counts, sums, amaf, b['totals'], b['boards'], b['links'], b['stats'], b['node_amaf'],
-              b['virt'], b['leaf'], b['move'], b['leaf_id'], s)
+    select = ('gg_uct_select' + lf + '_rave', R, N, C, *lv, K, c, ml.EQUIV, ml.FPU, log_table, b['boards'], b['child'], b['links'],
+              b['stats'], b['node_amaf'], b['nodes'], *vt, b['leaf'], b['move'], b['leaf_id'], s)
+    backup = ('gg_uct_backup' + lf + '_rave', R, N, C, *lv, K, counts, sums, amaf, b['totals'], b['boards'], b['links'], b['stats'],
+              b['node_amaf'], *vt, b['leaf'], b['move'], b['leaf_id'], s)
     expand = None
     if mode == 'prior':
-        expand = ('gg_uct_prior_expand_leaves', R, N, C, L, weights, b['leaf'], b['move'], b['leaf_id'], b['node_amaf'], s)
+        expand = ('gg_uct_prior_expand' + lf, R, N, C, *lv, weights, b['leaf'], b['move'], b['leaf_id'], b['node_amaf'], s)
     return select, expand, backup
 
 
@@ -331,6 +337,83 @@ def test_a_select_past_capacity_writes_nothing_beyond_a_tree(mode):
     assert mode == 'prior' or (want['nodes'][:2] == ml.PAST_C + 1).all()
     got = _direct(roots, ml.PAST_T, ml.PAST_L, ml.PAST_K, ml.size_c(mode), mode, 13, 64, ml.KOMI, C=ml.PAST_C)
     _check_tree(got, want, mode, ('past capacity', mode))
+
+
+@pytest.mark.parametrize('mode', ml.MODES)
+@pytest.mark.parametrize('N', (2, 9, 19))
+def test_one_leaf_and_leaves_entry_points_agree_launch_for_launch(N, mode):
+    """The two instantiations of the one kernel body, launch for launch: side A through gg_uct_select[_rave] ->
+    gg_batch_play_moves_tracked -> (gg_uct_prior_expand) -> gg_uct_backup[_rave], side B through the _leaves entry points with
+    L = 1 and a virt buffer, each on buffers of its own with sentinel tails.  Trees of 7 nodes, K = 2, eight rounds - the last two
+    find no room in a tree that grew in every round before (at 9x9 and 19x19 there is one in every mode; on 2x2 a walk may end in a
+    finished game, which adds no node, so a tree may stay below its capacity there).  The counts, sums and AMAF rows of a backup are the test's own numbers, the same on both sides and others in
+    every round: no playout runs.  After every select and after every backup the tree and the round's rows are equal byte for byte;
+    virt is the round's path counts in between and 0 after the backup."""
+    from gymgo_amd import _lib, gogame
+    roots = cs.stack(N, ('late0', 'mid0', 'empty', 'ended'))
+    R, C, K, T, P = len(roots), 6, 2, 8, N * N
+    rave, prior = ml.mode_args(mode, R, N)
+    tr = gogame.batch_track(mc.to_dev(roots))
+    weights = _i32([x for p in prior[0] for x in p]) if prior is not None else None
+    counts = torch.zeros((R, 4), dtype=torch.int32, device='cuda')
+    sums = torch.zeros((R, 2), dtype=torch.int64, device='cuda')
+    amaf = torch.zeros((R, 2, 3, N, N), dtype=torch.int32, device='cuda') if rave is not None else None
+    s = _stream()
+    sides = []
+    for one_leaf in (True, False):
+        bufs = Bufs()
+        b = _tree_buffers(bufs.new, R, N, C, R, rave is not None)
+        log_table = bufs.new('log_table', (C + 1,), torch.float64, torch.from_numpy(mc.log_table(C, K)).cuda())
+        _lib.call('gg_uct_begin', tr, R, N, C, K, b['boards'], b['child'], b['links'], b['stats'], b['nodes'], s)
+        if prior is not None:
+            _lib.call('gg_uct_prior_begin', tr, _i32(prior[1]), R, N, C, weights, b['node_amaf'], s)
+        sides.append((bufs, b, _calls(b, R, N, C, 1, K, ml.size_c(mode), mode, log_table, counts, sums, amaf, weights, one_leaf)))
+    names = ('child', 'links', 'stats', 'nodes', 'leaf', 'move', 'leaf_id') + (('node_amaf',) if rave is not None else ())
+
+    def same(tag):
+        (_, a, _), (_, b, _) = sides
+        for k in names:
+            assert torch.equal(a[k], b[k]), (N, mode, tag, k)
+        assert (a['nodes'] <= C + 1).all() and (b['nodes'] <= C + 1).all(), (N, mode, tag)
+        for bufs, _, _ in sides:
+            assert bufs.broken() == [], (N, mode, tag)
+
+    virt = sides[1][1]['virt']
+    rng = np.random.RandomState(100 * N + len(mode))
+    same('begin')
+    met_full = False
+    for t in range(T):
+        full = sides[0][1]['nodes'].cpu().numpy() == C + 1                        # before the select
+        for _, b, (select, _, _) in sides:
+            _lib.call(*select)
+        same((t, 'select'))
+        links, leaf_id = sides[1][1]['links'].cpu().numpy(), sides[1][1]['leaf_id'].cpu().numpy()
+        assert ((leaf_id >= 0) & (leaf_id <= C)).all(), (N, mode, t)            # L = 1: no collision, no empty slot
+        assert np.array_equal(virt.cpu().numpy(), _path_counts(links, leaf_id, R, C, 1)), (N, mode, t, 'virt')
+        if t >= C:                                                                # a tree that is full: nothing is added
+            assert (sides[0][1]['move'].cpu().numpy()[full] == -1).all(), (N, mode, t)
+            assert (sides[0][1]['nodes'].cpu().numpy()[full] == C + 1).all(), (N, mode, t)
+            met_full |= bool(full.any())
+        for _, b, (_, expand, _) in sides:
+            _lib.call('gg_batch_play_moves_tracked', b['leaf'], b['move'], None, R, N, 1, s)
+            if expand is not None:
+                _lib.call(*expand)
+        # the round's results: K playouts per row split into black wins, white wins and draws, first plays of at most K a point
+        bw = rng.randint(0, K + 1, R)
+        ww = rng.randint(0, K + 1 - bw)
+        counts.copy_(_i32(np.stack([bw, ww, K - bw - ww, rng.randint(0, 2, R)], axis=-1)))
+        sums.copy_(torch.from_numpy(rng.randint(0, 1000, (R, 2)).astype(np.int64)).cuda())
+        if amaf is not None:
+            e0 = rng.randint(0, K + 1, (R, 2, N, N))
+            e1 = rng.randint(0, e0 + 1)
+            amaf.copy_(_i32(np.stack([e0, e1, rng.randint(0, e0 - e1 + 1)], axis=2)))
+        for _, b, (_, _, backup) in sides:
+            _lib.call(*backup)
+        same((t, 'backup'))
+        assert torch.equal(sides[0][1]['totals'], sides[1][1]['totals']), (N, mode, t)
+        assert not bool(virt.any()), (N, mode, t, 'virt after the backup')
+    nodes = sides[0][1]['nodes'].cpu().numpy()
+    assert (met_full or N == 2) and nodes[-1] == 1, (N, mode, nodes)             # full trees; the ended root stays alone
 
 
 # ---------------------------------------------------------------- guards

@@ -9,8 +9,8 @@ of K playouts per leaf.  In one process, alternating, median of `--reps` runs ea
   (b) I calls of batch_playouts(roots, K, seed=i): the same playout volume with no tree (the roots as leaves).
 ratio = time (b) / time (a) per playout: what the select, one-move step and backup launches - and the host loop around
 them - cost on top of the playouts (1.0: nothing).  Both drain the playout queue once per iteration.  Plies are the plies
-the playouts played (plies_sum).  For the device-time split of k_uct_select, the one-move step (k_play_moves*) and
-k_uct_backup, run once under `rocprofv3 --kernel-trace --stats -- python tools/bench_uct.py --reps 1`.
+the playouts played (plies_sum).  For the device-time split of k_uct_select<RAVE, false>, the one-move step
+(k_play_moves*) and k_uct_backup<RAVE, false>, run once under `rocprofv3 --kernel-trace --stats -- python tools/bench_uct.py --reps 1`.
 --rave-equiv K: a third side in the same alternation, (c) batch_uct(roots, I, K, rave_equiv=K) - keys with the suffix _rave,
 rave_ratio = iterations/s with RAVE / plain, and the mean depth of the deepest node per tree on both sides.
 """

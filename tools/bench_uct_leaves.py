@@ -14,7 +14,7 @@ the playouts that reached a tree (plies_sum): the playouts of empty slots - a co
 the root empty - are run and thrown away.  live_slots = the mean number of non-empty slots per round; ratio = plies_per_s of
 (b) / of (a).  The two sides grow different trees, so their playouts differ in length (mean_plies, mean_plies_one_leaf: plies
 per playout that reached a tree) and ratio differs from time_ratio by that much.  For the device-time split of
-k_uct_select_leaves and k_uct_backup_leaves, run once under `rocprofv3 --kernel-trace --stats -- python
+k_uct_select<RAVE, true> and k_uct_backup<RAVE, true> (side (a): <RAVE, false>), run once under `rocprofv3 --kernel-trace --stats -- python
 tools/bench_uct_leaves.py --reps 1`.
 """
 import argparse
